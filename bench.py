@@ -146,6 +146,55 @@ def cold_cli(names, seqs, contra):
     return {"wall_s": wall, "command": "dafs -s CONTRAfold --no-alifold%s FASTA" % (" -a CONTRAlign" if contra else ""), "stdout": r.stdout}
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, lens, px, py, th, rp_off, o):
+    """--dump-outputs: what the caller of the timed path receives from its last step, as .npy files (float32 / float64),
+    every pair x < y of the set in row-major order:
+      pairs.npy (P, 2) x, y    sim.npy (P,) similarity score    nnz.npy (P,) entries of mp[x][y]
+    and, for a fixed seeded sample of the pairs (sample.npy: indices into pairs.npy, ascending), their sparse rows in the
+    kernel's layout, concatenated pair after pair:
+      rowptr.npy  the L1+1 row pointers of mp[x][y], then the L2+1 of mp[y][x] (relative to the pair)
+      col.npy / val.npy  the nnz entries of mp[x][y], then the nnz of mp[y][x]
+    The sample depends on the inputs alone: at most min(L2, 1/th + 1) entries of a row exceed th (a row of match
+    posteriors sums to at most 1), which bounds the bytes of every pair; pairs are taken in a seeded order while the
+    bound of the files stays under 64 MB."""
+    n = len(lens)
+    xs, ys = np.triu_indices(n, 1)
+    k_of = np.full((n, n), -1, np.int64)
+    k_of[px, py] = np.arange(len(px))
+    ks = k_of[xs, ys]
+    assert np.all(ks >= 0), "the dump needs every pair of the set on this rank"
+    idt = np.float32 if int(lens.max()) ** 2 < (1 << 24) else np.float64  # integers exact in the float type
+    isz = np.dtype(idt).itemsize
+    per_row = lens[ys] if th <= 0 else np.minimum(lens[ys], int(1.0 / th) + 1)
+    bound = isz * (lens[xs] + lens[ys] + 2) + 2 * (isz + 4) * lens[xs] * per_row
+    budget = DUMP_BYTES - len(ks) * (2 * 8 + 4 + 8) - 8 * len(ks)
+    order = np.random.default_rng(0).permutation(len(ks))
+    sample = np.sort(order[:int(np.searchsorted(np.cumsum(bound[order]), budget, side="right"))])
+
+    h_nnz = o["pair_nnz"].cpu().numpy().view(np.uint32)[ks]
+    h_off = o["pair_off"].cpu().numpy().view(np.uint64)
+    h_rp = o["rowptr"].cpu().numpy().view(np.uint32)
+    rp, col, val = [np.zeros(0, np.uint32)], [np.zeros(0, np.uint32)], [np.zeros(0, np.float32)]
+    for p in sample:
+        k, nz = int(ks[p]), int(h_nnz[p])
+        r0, e0 = int(rp_off[k]), int(h_off[k])
+        rp.append(h_rp[r0:r0 + int(lens[xs[p]]) + int(lens[ys[p]]) + 2])
+        col.append(o["col"][e0:e0 + 2 * nz].cpu().numpy().view(np.uint32))
+        val.append(o["val"][e0:e0 + 2 * nz].cpu().numpy())
+    arrays = {"pairs": np.stack([xs, ys], 1).astype(np.float64), "sim": o["sim"].cpu().numpy()[ks].astype(np.float32),
+              "nnz": h_nnz.astype(np.float64), "sample": sample.astype(np.float64),
+              "rowptr": np.concatenate(rp).astype(idt), "col": np.concatenate(col).astype(idt),
+              "val": np.concatenate(val).astype(np.float32)}
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_BYTES
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "pairs": len(ks), "sampled_pairs": len(sample)}
+
+
 def _pmc_file(kernel_name):
     """the newest committed PMC summary (profiles/*_pmc.json, tools/pmc_summary.py) of this kernel instance and of these kernel sources"""
     import glob
@@ -247,7 +296,12 @@ def main():
     ap.add_argument("--no-verify", action="store_true", help="tuning builds only (tools/build_exp.sh: kernels that stop after a sweep): skip the check of the "
                     "timed launch against the oracle; the JSON line then says verified_pairs 0")
     ap.add_argument("--no-e2e", action="store_true", help="skip the end-to-end wall-clock legs (warm driver run, cold CLI, forced-iteration DD run)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/*.npy (one GPU only; see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.gpus != 1:
+        ap.error("--dump-outputs needs --gpus 1")
     cfg_n, cfg_l = CONFIGS[args.config]
     args.length = args.length or cfg_l
 
@@ -426,6 +480,10 @@ def main():
                          "frac": valu * 4.0 / (SIMDS * CLOCK_HZ * kern_ms * 1e-3),
                          "formula": "SQ_INSTS_VALU x 4 cycles / (1024 SIMDs x 2.4 GHz x kernel_ms)", "pmc_file": "profiles/" + pmf[0]}
 
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, lens, px, py, args.th, rp_off, sets[(nstep[0] - 1) % nsets])
+
     # ---- the timed call path against the oracle: a strided sample of the last launch's outputs, bit for bit ----
     verified = 0
     if rank == 0 and not args.no_verify:
@@ -601,6 +659,8 @@ def main():
             "cpu_baseline": cpu,
             "verified_pairs": verified,
         }
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
         if exchange_verified is not None:
             out["exchange"] = {"backend": dist.get_backend(), "world": world, "verified_pairs": exchange_verified,
                                "slab_bytes_per_rank": int(ex.send.numel()) * 4}

@@ -113,12 +113,88 @@ def main():
             k += 1
     np.savez_compressed(os.path.join(HERE, "decoders_dense.npz"), n=np.int64(k), **cases)
 
+    reference_fuzz(ref)
+    align_aux(ref)
+
     with open(os.path.join(HERE, "synth_checksums.txt"), "w") as f:
         for n, L, seed in ((32, 80, 12345), (128, 150, 12345), (256, 200, 12345), (512, 400, 12345)):
             f.write("random %d %d %d %s\n" % (n, L, seed, synth.checksum(synth.random_set(n, L, seed=seed, jitter=0.0 if L == 80 else 0.07))))
         for n, L, seed in ((32, 80, 12346), (128, 150, 12346)):
             f.write("family %d %d %d %s\n" % (n, L, seed, synth.checksum(synth.family_set(n, L, seed=seed))))
     print("golden vectors written to", HERE)
+
+
+def reference_fuzz(ref):
+    """random inputs and the reference's answers for the fuzz tests of tests/test_oracle_cpu.py"""
+    rng = np.random.default_rng(5)
+    s1s, s2s, post, post_off, fold, fold_off, csr = [], [], [], [0], [], [0], []
+    for t in range(40):
+        L1, L2 = int(rng.integers(1, 120)), int(rng.integers(1, 120))
+        alpha = "ACGU" if t % 3 else "ACGUTNacgux-"
+        s1 = "".join(rng.choice(list(alpha), L1)); s2 = "".join(rng.choice(list(alpha), L2))
+        s1s.append(s1); s2s.append(s2)
+        for th in (0.0, 0.01):  # post[2t + (th != 0)]
+            post.append(ref.probcons_posterior(s1, s2, th).ravel()); post_off.append(post_off[-1] + len(post[-1]))
+        if t < 12:
+            fold.append(ref.contrafold_posterior(s1)); fold_off.append(fold_off[-1] + len(fold[-1]))
+        csr.append(ref.align_calculate(s1, s2, 0.01, 0))
+    fa = ref.fasta(os.path.join(HERE, "RF00017_4.fa"))
+    # the dense decoder classes on random matrices
+    rng = np.random.default_rng(5)
+    dense = {}
+    for t in range(12):
+        L, L2 = int(rng.integers(1, 60)), int(rng.integers(1, 60))
+        p = (rng.random((L, L)) * (rng.random((L, L)) < 0.2)).astype(np.float32)
+        q = ((rng.random((L, L)) - 0.4) * (rng.random((L, L)) < 0.3)).astype(np.float32)
+        dense.update({"p%d" % t: p, "q%d" % t: q})
+        for tag, qq in (("", q), ("f", None)):
+            s, ss = ref.nussinov_dense(p, qq, 0.1, 3.0)
+            dense.update({"s%s%d" % (tag, t): s, "ss%s%d" % (tag, t): ss})
+        pz = (rng.random((L, L2)) * (rng.random((L, L2)) < 0.1)).astype(np.float32)
+        qz = (rng.random((L, L2)) * (rng.random((L, L2)) < 0.2)).astype(np.float32)
+        dense.update({"pz%d" % t: pz, "qz%d" % t: qz})
+        for tag, qq in (("", qz), ("f", None)):
+            s, al = ref.nw_dense(pz, qq, 0.01)
+            dense.update({"sz%s%d" % (tag, t): s, "al%s%d" % (tag, t): al})
+    np.savez_compressed(os.path.join(HERE, "reference_fuzz.npz"), seq1=np.array(s1s), seq2=np.array(s2s),
+                        post=np.concatenate(post), post_off=np.array(post_off, np.int64),
+                        fold=np.concatenate(fold), fold_off=np.array(fold_off, np.int64), **csr_pack(csr),
+                        fasta_names=np.array([n for n, _ in fa]), fasta_seqs=np.array([s for _, s in fa]),
+                        n_dense=np.int64(12), **{"dense_" + k: v for k, v in dense.items()})
+
+
+def _aux_text(seqs, rows):
+    """the --align-aux file format as `dafs --save-align-aux` writes it: "> x y", then "i k:p ..." per row, 1-based,
+    9 significant digits (the writer's ostream precision)"""
+    out, p = [], 0
+    for x in range(len(seqs)):
+        for y in range(x + 1, len(seqs)):
+            rp, col, val = rows[p]
+            out.append("> %d %d\n" % (x + 1, y + 1))
+            for i in range(len(seqs[x])):
+                out.append("%d" % (i + 1) + "".join(" %d:%s" % (col[k] + 1, format(float(val[k]), ".9g"))
+                                                    for k in range(rp[i], rp[i + 1])) + "\n")
+            p += 1
+    return "".join(out)
+
+
+def align_aux(ref):
+    """for tests/test_cli_gpu.py: the --align-aux file of a small set under both alignment models, and what the
+    reference's own reader (AUXAlign::calculate) loads from it"""
+    recs = synth.family_set(6, 55, seed=25) + synth.random_set(2, 40, seed=26)
+    seqs = [r[1] for r in recs]
+    out = {}
+    for model, flag in ((0, "ProbCons"), (1, "CONTRAlign")):
+        rows = [ref.align_calculate(seqs[x], seqs[y], 0.01, model) for x in range(len(seqs)) for y in range(x + 1, len(seqs))]
+        text = _aux_text(seqs, rows)
+        path = os.path.join(HERE, "_aux.tmp")
+        with open(path, "w") as f:
+            f.write(text)
+        nnz, rowptr, col, val = ref.auxalign_load(path, seqs)
+        os.remove(path)
+        out.update({"text_" + flag: np.array(text), "nnz_" + flag: nnz, "rowptr_" + flag: rowptr,
+                    "col_" + flag: col, "val_" + flag: val})
+    np.savez_compressed(os.path.join(HERE, "align_aux.npz"), checksum=np.array(synth.checksum(recs)), **out)
 
 
 if __name__ == "__main__":

@@ -121,20 +121,23 @@ def test_align_aux_round_trip(tmp_path):
     assert rc == 0 and out3 == out1, err
 
 
-def test_align_aux_file_read_by_the_reference_reader(ref, tmp_path):
-    """The wire format pinned from the other side: the file `dafs --save-align-aux` writes is parsed by the reference's
-    own AUXAlign::calculate (src/align.cpp:204-246, compiled into oracle/_ref), and what it loads equals the rows the
-    device computed, bit for bit (9 significant digits carry a float32 exactly)."""
+def test_align_aux_file_read_by_the_reference_reader(tmp_path):
+    """The wire format pinned from the other side: the file `dafs --save-align-aux` writes is, byte for byte, the one the
+    reference's own AUXAlign::calculate (src/align.cpp:204-246) was run on by tests/golden/make_golden.py, and what that
+    reader loaded from it equals the rows the device computed, bit for bit (9 significant digits carry a float32 exactly)."""
     from dafs_amd import capi
     recs = synth.family_set(6, 55, seed=25) + synth.random_set(2, 40, seed=26)
     seqs = [r[1] for r in recs]
+    z = np.load(os.path.join(G, "align_aux.npz"))
+    assert synth.checksum(recs) == str(z["checksum"])
     fa = tmp_path / "f.fa"
     fa.write_text(synth.to_fasta(recs))
     for model, flag in ((capi.ALIGN_PROBCONS, "ProbCons"), (capi.ALIGN_CONTRALIGN, "CONTRAlign")):
         aux = tmp_path / ("mp_%s.aux" % flag)
         rc, out, err = run_cli("-a", flag, "--save-align-aux", str(aux), str(fa))
         assert rc == 0, err
-        nnz, rowptr, col, val = ref.auxalign_load(str(aux), seqs)
+        assert aux.read_text() == str(z["text_" + flag])
+        nnz, rowptr, col, val = (z[k + "_" + flag] for k in ("nnz", "rowptr", "col", "val"))
         ctx = capi.Context(0)
         ctx.set_sequences(seqs)
         dev = ctx.align_posteriors(model, 0.01)

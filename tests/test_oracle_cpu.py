@@ -1,7 +1,6 @@
 """CPU tests (no GPU): the oracle restatement against the golden vectors generated from the
 reference's own code (tests/golden/make_golden.py) and against the known answers of the whole
-pipeline (tests/golden/known_answers.txt).  Where oracle/_ref is present (build container) the
-oracle is additionally fuzzed against it."""
+pipeline (tests/golden/known_answers.txt), and fuzzed against the reference's stored answers on random inputs."""
 import os
 
 import numpy as np
@@ -148,20 +147,18 @@ def test_dense_decoders_golden(oracle):
         assert np.float32(s).tobytes() == np.float32(z["szf%d" % k]).tobytes() and np.array_equal(al, z["alf%d" % k]), k
 
 
-def test_dense_decoders_fuzz_vs_reference(oracle, ref):
-    rng = np.random.default_rng(5)
-    for t in range(12):
-        L, L2 = int(rng.integers(1, 60)), int(rng.integers(1, 60))
-        p = (rng.random((L, L)) * (rng.random((L, L)) < 0.2)).astype(np.float32)
-        q = ((rng.random((L, L)) - 0.4) * (rng.random((L, L)) < 0.3)).astype(np.float32)
-        for qq in (q, None):
-            a, b = oracle.nussinov_dense(p, qq, 0.1, 3.0), ref.nussinov_dense(p, qq, 0.1, 3.0)
-            assert np.float32(a[0]).tobytes() == np.float32(b[0]).tobytes() and np.array_equal(a[1], b[1]), t
-        pz = (rng.random((L, L2)) * (rng.random((L, L2)) < 0.1)).astype(np.float32)
-        qz = (rng.random((L, L2)) * (rng.random((L, L2)) < 0.2)).astype(np.float32)
-        for qq in (qz, None):
-            a, b = oracle.nw_dense(pz, qq, 0.01), ref.nw_dense(pz, qq, 0.01)
-            assert np.float32(a[0]).tobytes() == np.float32(b[0]).tobytes() and np.array_equal(a[1], b[1]), t
+def test_dense_decoders_fuzz_vs_reference(oracle):
+    """random matrices against the reference's own dense classes (answers stored by tests/golden/make_golden.py)"""
+    z = np.load(os.path.join(G, "reference_fuzz.npz"))
+    for t in range(int(z["n_dense"])):
+        d = lambda k: z["dense_%s%d" % (k, t)]
+        p, q, pz, qz = d("p"), d("q"), d("pz"), d("qz")
+        for tag, qq in (("", q), ("f", None)):
+            a = oracle.nussinov_dense(p, qq, 0.1, 3.0)
+            assert np.float32(a[0]).tobytes() == np.float32(d("s" + tag)).tobytes() and np.array_equal(a[1], d("ss" + tag)), t
+        for tag, qq in (("", qz), ("f", None)):
+            a = oracle.nw_dense(pz, qq, 0.01)
+            assert np.float32(a[0]).tobytes() == np.float32(d("sz" + tag)).tobytes() and np.array_equal(a[1], d("al" + tag)), t
 
 
 def _orc_fold_post(oracle, s, cons=None):
@@ -271,16 +268,19 @@ def test_synth_checksums():
         assert len(recs) == n
 
 
-def test_oracle_vs_reference_fuzz(oracle, ref):
-    rng = np.random.default_rng(5)
-    for t in range(40):
-        L1, L2 = int(rng.integers(1, 120)), int(rng.integers(1, 120))
-        alpha = "ACGU" if t % 3 else "ACGUTNacgux-"
-        s1 = "".join(rng.choice(list(alpha), L1)); s2 = "".join(rng.choice(list(alpha), L2))
-        for th in (0.0, 0.01):
-            assert oracle.probcons_posterior(s1, s2, th).tobytes() == ref.probcons_posterior(s1, s2, th).tobytes()
+def test_oracle_vs_reference_fuzz(oracle):
+    """random sequences (odd residues among them) against the reference's own answers (tests/golden/make_golden.py)"""
+    z = np.load(os.path.join(G, "reference_fuzz.npz"))
+    po, fo = z["post_off"], z["fold_off"]
+    cases = list(_cases("reference_fuzz.npz"))
+    assert len(cases) == 40
+    for t, (s1, s2, rp, col, val) in enumerate(cases):
+        for k, th in enumerate((0.0, 0.01)):
+            want = z["post"][po[2 * t + k]:po[2 * t + k + 1]]
+            assert oracle.probcons_posterior(s1, s2, th).tobytes() == want.tobytes(), t
         if t < 12:
-            assert _orc_fold_post(oracle, s1).tobytes() == ref.contrafold_posterior(s1).tobytes()
-        a, b = oracle.align_calculate(s1, s2, 0.01, 0), ref.align_calculate(s1, s2, 0.01, 0)
-        assert all(x.tobytes() == y.tobytes() for x, y in zip(a, b))
-    assert oracle.fasta(os.path.join(G, "RF00017_4.fa")) == ref.fasta(os.path.join(G, "RF00017_4.fa"))
+            assert _orc_fold_post(oracle, s1).tobytes() == z["fold"][fo[t]:fo[t + 1]].tobytes(), t
+        a = oracle.align_calculate(s1, s2, 0.01, 0)
+        assert all(x.tobytes() == y.tobytes() for x, y in zip(a, (rp, col, val))), t
+    want = list(zip((str(n) for n in z["fasta_names"]), (str(s) for s in z["fasta_seqs"])))
+    assert oracle.fasta(os.path.join(G, "RF00017_4.fa")) == want
