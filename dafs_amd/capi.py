@@ -72,6 +72,7 @@ _last_error = _sig("dafs_hip_last_error", C.c_char_p, [])
 _create = _sig("dafs_hip_create", C.c_int, [C.c_int, C.POINTER(C.c_void_p)])
 _destroy = _sig("dafs_hip_destroy", None, [C.c_void_p])
 _set_sequences = _sig("dafs_hip_set_sequences", C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_char_p), u32p])
+_set_families = _sig("dafs_hip_set_families", C.c_int, [C.c_void_p, C.c_uint32, u32p])
 _align_posteriors = _sig("dafs_hip_align_posteriors", C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_uint64, C.c_uint64])
 _align_result_size = _sig("dafs_hip_align_result_size", C.c_int,
                           [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)])
@@ -204,6 +205,7 @@ class Context:
         self._h = C.c_void_p()
         check(_create(device, C.byref(self._h)))
         self._lens = None
+        self._first = np.array([0, 0], np.uint32)
         self.device_index = device
 
     def close(self):
@@ -223,6 +225,16 @@ class Context:
         lens = np.array([len(b) for b in bs], dtype=np.uint32)
         check(_set_sequences(self._h, len(bs), arr, lens.ctypes.data_as(u32p)))
         self._lens = lens
+        self._first = np.array([0, len(bs)], np.uint32)
+
+    def set_families(self, first):
+        """Family partition of the sequences (dafs_hip_set_families): family f is sequences first[f] .. first[f+1]-1, with
+        first[0] = 0 and first[-1] = the number of sequences.  Invalidates the stores."""
+        first = np.ascontiguousarray(first, np.uint32)
+        if len(first) < 2:
+            raise ValueError("set_families: first needs nfam + 1 >= 2 entries")
+        check(_set_families(self._h, len(first) - 1, first.ctypes.data_as(u32p)))
+        self._first = first
 
     def align_posteriors(self, model=ALIGN_PROBCONS, th=0.01, pair_begin=0, pair_end=0, fetch=True):
         check(_align_posteriors(self._h, model, th, pair_begin, pair_end))
@@ -252,9 +264,20 @@ class Context:
         return PairPosteriors(px, py, None, cnt, rowptr, col, val, self._lens)
 
     def sim(self):
-        n = len(self._lens)
-        out = np.zeros((n, n), np.float32)
-        check(_get_sim(self._h, out.ctypes.data))
+        """the N x N similarity matrix of a one-family context (sim_blocks() for several families)"""
+        if len(self._first) != 2:
+            raise ValueError("Context.sim: the context holds %d families; use sim_blocks()" % (len(self._first) - 1))
+        return self.sim_blocks()[0]
+
+    def sim_blocks(self):
+        """per family its n x n similarity block (unit diagonal)"""
+        sizes = np.diff(self._first.astype(np.int64))
+        flat = np.zeros(int((sizes * sizes).sum()), np.float32)
+        check(_get_sim(self._h, flat.ctypes.data))
+        out, o = [], 0
+        for n in sizes:
+            out.append(flat[o:o + n * n].reshape(n, n).copy())
+            o += n * n
         return out
 
     def set_bp(self, rows):

@@ -217,10 +217,21 @@ extern "C" int dafs_hip_set_sequences(dafs_hip_ctx* c, uint32_t nseq, const char
   if ((rc = c->codes.upload(codes.data(), codes.size(), c->stream))) return rc;
   if ((rc = c->d_len.upload(c->len.data(), nseq, c->stream))) return rc;
   if ((rc = c->d_seq_rp_off.upload(c->seq_rp_off.data(), nseq + 1, c->stream))) return rc;
+  const uint32_t one[2] = {0, nseq};  // one family until dafs_hip_set_families says otherwise
+  if ((rc = c->fam.build(one, 1, nseq, c->stream))) return rc;
   for (int k = 0; k < 2; ++k) { c->mp[k].valid = false; c->bp[k].valid = false; }
   c->cur_mp = c->cur_bp = 0;
   c->sim.clear();
   return DAFS_HIP_OK;
+}
+
+extern "C" int dafs_hip_set_families(dafs_hip_ctx* c, uint32_t nfam, const uint32_t* first) {
+  if (!c || c->len.empty() || !first || nfam == 0) return DAFS_HIP_EINVAL;
+  if (hip_check(hipSetDevice(c->device))) return DAFS_HIP_ENODEV;
+  for (int k = 0; k < 2; ++k) { c->mp[k].valid = false; c->bp[k].valid = false; }
+  c->cur_mp = c->cur_bp = 0;
+  c->sim.clear();
+  return c->fam.build(first, nfam, (uint32_t)c->len.size(), c->stream);
 }
 
 // make_brackets, reference src/nussinov.cpp:401-413 with brackets[0] = "()" (src/fold.cpp:57-58)

@@ -13,21 +13,24 @@
 
 using namespace dafs;
 
-// pair index p <-> (i<j), row-major as in Align::Model::calculate (align.cpp:39-50)
-static void pair_from_index(uint64_t p, uint32_t n, uint32_t* i, uint32_t* j) {
-  uint32_t a = 0;
-  uint64_t rem = p;
-  while (rem >= (uint64_t)(n - 1 - a)) { rem -= (n - 1 - a); ++a; }
-  *i = a;
-  *j = a + 1 + (uint32_t)rem;
+// the host and device copies of the similarity blocks (family_layout::sim0, unit diagonals) from per-pair scores in pair-id
+// order (ts[task_of_pair[p]] when task_of_pair is given)
+static int store_sim_blocks(dafs_hip_ctx* c, const mp_store& st, const std::vector<float>& ts, bool by_task) {
+  c->sim.assign(c->fam.sim_floats(), 0.0f);
+  for (uint32_t i = 0; i < (uint32_t)c->len.size(); ++i) c->sim[c->fam.sim_at(i, i)] = 1.0f;
+  for (uint64_t p = 0; p < st.n_tasks; ++p) {
+    const float s = ts[by_task ? st.task_of_pair[p] : p];
+    c->sim[c->fam.sim_at(st.pair_x[p], st.pair_y[p])] = s;
+    c->sim[c->fam.sim_at(st.pair_y[p], st.pair_x[p])] = s;
+  }
+  return c->d_sim.upload(c->sim.data(), c->sim.size(), c->stream);
 }
 
 extern "C" int dafs_hip_align_posteriors(dafs_hip_ctx* c, int model, float th, uint64_t pair_begin, uint64_t pair_end) {
   if (!c || c->len.empty() || !(th >= 0.0f)) return DAFS_HIP_EINVAL;
   if (model != DAFS_ALIGN_PROBCONS && model != DAFS_ALIGN_CONTRALIGN) return DAFS_HIP_EINVAL;
   if (hip_check(hipSetDevice(c->device))) return DAFS_HIP_ENODEV;
-  const uint32_t n = (uint32_t)c->len.size();
-  const uint64_t all = (uint64_t)n * (n - 1) / 2;
+  const uint64_t all = c->fam.npairs();  // the pairs within the families, family by family (sparse_view.h)
   if (pair_end == 0) pair_end = all;
   if (pair_begin > pair_end || pair_end > all) return DAFS_HIP_EINVAL;
   const uint64_t np = pair_end - pair_begin;
@@ -39,16 +42,11 @@ extern "C" int dafs_hip_align_posteriors(dafs_hip_ctx* c, int model, float th, u
   st.pair_x.resize(np);
   st.pair_y.resize(np);
   st.n_tasks = np;
-  if (np == 0) { st.valid = true; st.rp_total = st.pool_used = 0; return DAFS_HIP_OK; }
-  {
-    uint32_t i, j;
-    pair_from_index(pair_begin, n, &i, &j);
-    for (uint64_t p = 0; p < np; ++p) {
-      st.pair_x[p] = i;
-      st.pair_y[p] = j;
-      if (++j == n) { ++i; j = i + 1; }
-    }
+  if (np == 0) {  // families of one sequence only: no pairs, the similarity blocks are their unit diagonals
+    st.valid = true; st.rp_total = st.pool_used = 0; st.task_of_pair.clear(); st.rp_by_pair.clear();
+    return all == 0 ? store_sim_blocks(c, st, {}, false) : DAFS_HIP_OK;
   }
+  c->fam.pairs(pair_begin, pair_end, st.pair_x.data(), st.pair_y.data());
   // processing order: longest first (cost ~ len1*len2), so the work queue balances the tail
   std::vector<uint32_t> order(np);
   std::iota(order.begin(), order.end(), 0u);
@@ -138,18 +136,11 @@ extern "C" int dafs_hip_align_posteriors(dafs_hip_ctx* c, int model, float th, u
       st.pool_cap_hint = cap;
       st.valid = true;
       c->plan = plan;
-      // similarity matrix (dafs.cpp:1813-1819) when the shard is the whole pair set
+      // similarity blocks (dafs.cpp:1813-1819) when the shard is the whole pair set
       if (np == all) {
         std::vector<float> ts(np);
         if ((rc = c->task_sim.download(ts.data(), np))) return rc;
-        c->sim.assign((size_t)n * n, 0.0f);
-        for (uint32_t i = 0; i < n; ++i) c->sim[(size_t)i * n + i] = 1.0f;
-        for (uint64_t p = 0; p < np; ++p) {
-          const float s = ts[st.task_of_pair[p]];
-          c->sim[(size_t)st.pair_x[p] * n + st.pair_y[p]] = s;
-          c->sim[(size_t)st.pair_y[p] * n + st.pair_x[p]] = s;
-        }
-        if ((rc = c->d_sim.upload(c->sim.data(), c->sim.size(), c->stream))) return rc;
+        if ((rc = store_sim_blocks(c, st, ts, true))) return rc;
       }
       return DAFS_HIP_OK;
     }
@@ -164,7 +155,7 @@ extern "C" int dafs_hip_align_posteriors(dafs_hip_ctx* c, int model, float th, u
 // transposes (transpose_mp, dafs.cpp:155-167) are laid out here and the similarity scores
 // (calculate_similarity_score, :713-764, :1813-1819) are computed on the device.
 extern "C" int dafs_hip_set_mp(dafs_hip_ctx* c, const uint32_t* nnz, const uint32_t* rowptr, const uint32_t* col, const float* val) {
-  if (!c || c->len.size() < 2 || !nnz || !rowptr || !col || !val) return DAFS_HIP_EINVAL;
+  if (!c || c->len.size() < 2 || !nnz || !rowptr || !col || !val || c->fam.nfam() != 1) return DAFS_HIP_EINVAL;
   if (hip_check(hipSetDevice(c->device))) return DAFS_HIP_ENODEV;
   const uint32_t n = (uint32_t)c->len.size();
   const uint64_t np = (uint64_t)n * (n - 1) / 2;
@@ -243,8 +234,7 @@ extern "C" int dafs_hip_set_mp(dafs_hip_ctx* c, const uint32_t* nnz, const uint3
 // Similarity scores (calculate_similarity_score, dafs.cpp:713-764, :1813-1819) of every pair from the rows of a store
 // whose pairs are in row-major order (task == pair): device DP, then the host and device copies of sim.
 int dafs_recompute_sim(dafs_hip_ctx* c, dafs::mp_store& st) {
-  const uint32_t n = (uint32_t)c->len.size();
-  const uint64_t np = (uint64_t)n * (n - 1) / 2;
+  const uint64_t np = c->fam.npairs();
   int rc;
   if ((rc = c->d_pair_x.upload(st.pair_x.data(), np, c->stream))) return rc;
   if ((rc = c->d_pair_y.upload(st.pair_y.data(), np, c->stream))) return rc;
@@ -253,17 +243,11 @@ int dafs_recompute_sim(dafs_hip_ctx* c, dafs::mp_store& st) {
   if ((rc = c->scratch.reserve(2 * ((size_t)max_len + 1) * np))) return rc;
   float* row_dp = c->scratch.ptr;
   int* row_tr = (int*)(c->scratch.ptr + ((size_t)max_len + 1) * np);
-  if ((rc = mp_sim_launch(st.view(c->d_len.ptr, n), c->d_pair_x.ptr, c->d_pair_y.ptr, (uint32_t)np, c->task_sim.ptr, row_dp, row_tr, c->stream))) return rc;
+  if ((rc = mp_sim_launch(c->mp_view(st), c->d_pair_x.ptr, c->d_pair_y.ptr, (uint32_t)np, c->task_sim.ptr, row_dp, row_tr, c->stream))) return rc;
   std::vector<float> ts(np);
   if (hip_check(hipStreamSynchronize(c->stream))) return DAFS_HIP_ELAUNCH;
   if ((rc = c->task_sim.download(ts.data(), np))) return rc;
-  c->sim.assign((size_t)n * n, 0.0f);
-  for (uint32_t i = 0; i < n; ++i) c->sim[(size_t)i * n + i] = 1.0f;
-  for (uint64_t p = 0; p < np; ++p) {
-    c->sim[(size_t)st.pair_x[p] * n + st.pair_y[p]] = ts[p];
-    c->sim[(size_t)st.pair_y[p] * n + st.pair_x[p]] = ts[p];
-  }
-  return c->d_sim.upload(c->sim.data(), c->sim.size(), c->stream);
+  return store_sim_blocks(c, st, ts, false);
 }
 
 // A complete matching-probability store from arrays in the layout dafs_hip_mp_fetch / dafs_hip_align_fetch write (all
@@ -274,7 +258,7 @@ int dafs_recompute_sim(dafs_hip_ctx* c, dafs::mp_store& st) {
 // consistency transform on top of an installed or computed un-relaxed store.  Nothing is recomputed: uploads only.
 extern "C" int dafs_hip_mp_install(dafs_hip_ctx* c, int relaxed, const uint32_t* nnz, const uint32_t* rowptr, const uint32_t* col,
                                    const float* val, const float* sim) {
-  if (!c || c->len.size() < 2 || relaxed < 0 || relaxed > 1 || !nnz || !rowptr) return DAFS_HIP_EINVAL;
+  if (!c || c->len.size() < 2 || relaxed < 0 || relaxed > 1 || !nnz || !rowptr || c->fam.nfam() != 1) return DAFS_HIP_EINVAL;
   if (relaxed == 0 && !sim) return DAFS_HIP_EINVAL;
   if (relaxed == 1 && (!c->mp[0].valid || c->sim.empty())) return DAFS_HIP_EINVAL;
   if (hip_check(hipSetDevice(c->device))) return DAFS_HIP_ENODEV;
@@ -388,7 +372,8 @@ extern "C" int dafs_hip_align_fetch(dafs_hip_ctx* c, uint32_t* pair_x, uint32_t*
   return DAFS_HIP_OK;
 }
 
-// sim_ (dafs.cpp:1813-1819), N*N with unit diagonal; needs a full-pair-set align_posteriors
+// sim_ (dafs.cpp:1813-1819): the families' n x n blocks with unit diagonal, one after another (N*N for one family); needs a
+// full-pair-set align_posteriors
 extern "C" int dafs_hip_get_sim(dafs_hip_ctx* c, float* sim) {
   if (!c || !sim || c->sim.empty()) return DAFS_HIP_EINVAL;
   memcpy(sim, c->sim.data(), c->sim.size() * sizeof(float));

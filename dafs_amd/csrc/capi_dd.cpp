@@ -310,8 +310,7 @@ bool fail_injected(int stage) {
 int nodes_open_impl(dafs_hip_ctx* c, const dd_lane& ln, uint32_t nnodes, const dafs_node_input* in, const dd_params& dp, open_blocks& ob) {
   const mp_store& mps = c->mp[c->cur_mp];
   const bp_store& bps = c->bp[c->cur_bp];
-  const uint32_t nseq = (uint32_t)c->len.size();
-  if (!mps.valid || !bps.valid || mps.n_tasks != (uint64_t)nseq * (nseq - 1) / 2) return DAFS_HIP_EINVAL;
+  if (!mps.valid || !bps.valid || mps.n_tasks != c->fam.npairs()) return DAFS_HIP_EINVAL;
 
   // ---- host geometry ----
   std::vector<geom> g1(nnodes), g2(nnodes);
@@ -321,6 +320,10 @@ int nodes_open_impl(dafs_hip_ctx* c, const dd_lane& ln, uint32_t nnodes, const d
     int rc;
     if ((rc = make_geom(c, ni.n1, ni.len1, ni.seq1, ni.mask1, g1[b]))) return rc;
     if ((rc = make_geom(c, ni.n2, ni.len2, ni.seq2, ni.mask2, g2[b]))) return rc;
+    // only pairs within a family exist (dafs_hip_set_families): every row of a node must come from one family
+    const uint32_t s0 = ni.seq1[0];
+    for (uint32_t r = 0; r < ni.n1; ++r) if (!c->fam.same_family(s0, ni.seq1[r])) return DAFS_HIP_EINVAL;
+    for (uint32_t r = 0; r < ni.n2; ++r) if (!c->fam.same_family(s0, ni.seq2[r])) return DAFS_HIP_EINVAL;
   }
 
   // DAFS_HIP_DD_WIDE=1 (tests): every node takes the forms of alignments too wide for the on-chip placements -- foldings
@@ -478,7 +481,7 @@ int nodes_open_impl(dafs_hip_ctx* c, const dd_lane& ln, uint32_t nnodes, const d
   int rc;
   if (fail_injected(1)) return DAFS_HIP_ELAUNCH;
   if ((rc = ln.d_nodes->upload(nodes.data(), nnodes, ln.st))) return rc;  // synchronises: host vectors stay valid until here
-  const mp_store_dev mpv = mps.view(c->d_len.ptr, nseq);
+  const mp_store_dev mpv = c->mp_view(mps);
   const bp_store_dev bpv = bps.view();
   uint32_t max_len = 0;
   for (uint32_t b = 0; b < nnodes; ++b) max_len = std::max(max_len, std::max(in[b].len1, in[b].len2));

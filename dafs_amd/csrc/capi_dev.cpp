@@ -51,7 +51,7 @@ extern "C" int dafs_hip_mp_export_dev(dafs_hip_ctx* c, int relaxed, uint64_t fir
 
 extern "C" int dafs_hip_mp_install_dev(dafs_hip_ctx* c, int relaxed, const uint32_t* nnz, const uint32_t* rowptr, const uint32_t* col, const float* val,
                                        const float* sim, uint64_t n_entries) {
-  if (!c || c->len.size() < 2 || relaxed < 0 || relaxed > 1 || !nnz || !rowptr) return DAFS_HIP_EINVAL;
+  if (!c || c->len.size() < 2 || relaxed < 0 || relaxed > 1 || !nnz || !rowptr || c->fam.nfam() != 1) return DAFS_HIP_EINVAL;
   if (relaxed == 0 && !sim) return DAFS_HIP_EINVAL;
   if (relaxed == 1 && (!c->mp[0].valid || c->sim.empty())) return DAFS_HIP_EINVAL;
   if (n_entries && (!col || !val)) return DAFS_HIP_EINVAL;
@@ -98,7 +98,7 @@ extern "C" int dafs_hip_mp_install_dev(dafs_hip_ctx* c, int relaxed, const uint3
     if ((rc = d2d(c->task_sim.ptr, sim, np * sizeof(float), c->stream))) return rc;
     if ((rc = c->d_sim.reserve((size_t)n * n))) return rc;
     if (hip_check(hipMemsetAsync(c->d_sim.ptr, 0, (size_t)n * n * sizeof(float), c->stream))) return DAFS_HIP_ELAUNCH;
-    if ((rc = sim_matrix_launch(c->d_pair_x.ptr, c->d_pair_y.ptr, c->task_sim.ptr, np, n, c->d_sim.ptr, c->stream))) return rc;
+    if ((rc = sim_matrix_launch(c->d_pair_x.ptr, c->d_pair_y.ptr, c->task_sim.ptr, np, c->fam.d_seq.ptr, n, c->d_sim.ptr, c->stream))) return rc;
     c->sim.assign((size_t)n * n, 0.0f);  // the guide tree is host work (dafs_host_build_tree): N * N floats come down
     if (hip_check(hipMemcpyAsync(c->sim.data(), c->d_sim.ptr, c->sim.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream)) ||
         hip_check(hipStreamSynchronize(c->stream))) return DAFS_HIP_ELAUNCH;

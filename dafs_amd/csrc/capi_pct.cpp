@@ -119,12 +119,12 @@ static int consistency_parts(dafs_hip_ctx* c, float w_pct_a, float w_pct_s, int 
   if (!c || c->len.empty()) return DAFS_HIP_EINVAL;
   if (hip_check(hipSetDevice(c->device))) return DAFS_HIP_ENODEV;
   const uint32_t n = (uint32_t)c->len.size();
-  const uint64_t all = (uint64_t)n * (n - 1) / 2;
+  const uint64_t all = c->fam.npairs();  // every output pair reads its own family only (sparse_view.h)
   mp_store& raw = c->mp[0];
   if (!raw.valid || raw.n_tasks != all || (c->sim.empty() && !fourway)) return DAFS_HIP_EINVAL;
   if (fourway && !c->bp[0].valid) return DAFS_HIP_EINVAL;
   const uint32_t max_len = c->max_len();
-  mp_store_dev mpv = raw.view(c->d_len.ptr, n);
+  mp_store_dev mpv = c->mp_view(raw);
   int rc;
   // the row kernels gather {column, value} pairs: one interleaved copy of the input entries per transform
   if ((rc = c->mp_ent2.reserve(raw.pool_used + 32))) return rc;  // + slack: k_pct_rows' unpredicated fetch reads up to 15 entries behind a row

@@ -92,7 +92,7 @@ extern "C" void dafs_hip_pair_range(uint64_t npairs, uint32_t world, uint32_t ra
 
 extern "C" int dafs_hip_phase1_sharded(dafs_hip_ctx* c, uint32_t rank, uint32_t world, int align_model, float th_a, float w_pct_a, float w_pct_s,
                                        int fold_model, float fold_th, dafs_allgather_fn allgather, void* user) {
-  if (!c || !allgather || world == 0 || rank >= world || c->len.size() < 2) return DAFS_HIP_EINVAL;
+  if (!c || !allgather || world == 0 || rank >= world || c->len.size() < 2 || c->fam.nfam() != 1) return DAFS_HIP_EINVAL;
   if (hip_check(hipSetDevice(c->device))) return DAFS_HIP_ENODEV;
   const uint32_t n = (uint32_t)c->len.size();
   const uint64_t npairs = (uint64_t)n * (n - 1) / 2;

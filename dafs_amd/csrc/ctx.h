@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <algorithm>
 #include <iterator>
 #include <map>
 #include <string>
@@ -59,10 +60,10 @@ struct mp_store {
   dev_buf<uint32_t> rowptr_pool, col, pair_nnz, d_task_of_pair;
   dev_buf<float> val;
   dev_buf<uint64_t> pair_off, rp_off;
-  mp_store_dev view(const uint32_t* d_len, uint32_t nseq) const {
+  mp_store_dev view(const uint32_t* d_len, const seq_family* d_fam, uint32_t nseq, uint32_t max_fam) const {
     mp_store_dev v;
     v.rowptr_pool = rowptr_pool.ptr; v.col = col.ptr; v.val = val.ptr; v.ent2 = nullptr; v.ident2 = nullptr; v.ident_rp = nullptr; v.pair_off = pair_off.ptr;
-    v.pair_nnz = pair_nnz.ptr; v.rp_off = rp_off.ptr; v.task_of_pair = d_task_of_pair.ptr; v.len = d_len; v.nseq = nseq;
+    v.pair_nnz = pair_nnz.ptr; v.rp_off = rp_off.ptr; v.task_of_pair = d_task_of_pair.ptr; v.len = d_len; v.fam = d_fam; v.nseq = nseq; v.max_fam = max_fam;
     return v;
   }
   void release() {
@@ -86,6 +87,76 @@ struct bp_store {
   void release() { rowptr.release(); col.release(); nnz.release(); val.release(); rp_off.release(); bp_off.release(); valid = false; }
 };
 
+// The family partition of a context (sparse_view.h): the one place that decides how pairs and similarity blocks are laid
+// out.  Families are contiguous index ranges first[f] .. first[f + 1]; the pairs are numbered family by family, row-major
+// inside each (pair_id), and family f's n x n similarity block starts at sim0[f].
+struct family_layout {
+  std::vector<uint32_t> first;   // [nfam + 1]
+  std::vector<seq_family> seq;   // per sequence
+  std::vector<uint64_t> pair0;   // [nfam + 1]: first pair id of each family; pair0[nfam] = all pairs
+  std::vector<uint64_t> sim0;    // [nfam + 1]: first float of each family's similarity block
+  uint32_t max_fam = 0;
+  dev_buf<seq_family> d_seq;
+
+  uint32_t nfam() const { return first.empty() ? 0 : (uint32_t)first.size() - 1; }
+  uint64_t npairs() const { return pair0.empty() ? 0 : pair0.back(); }
+  uint64_t sim_floats() const { return sim0.empty() ? 0 : sim0.back(); }
+  // family of pair id p (p < npairs())
+  uint32_t family_of_pair(uint64_t p) const { return (uint32_t)(std::upper_bound(pair0.begin(), pair0.end(), p) - pair0.begin()) - 1; }
+  // where sim[x][y] of two sequences of one family lies in the concatenated blocks
+  uint64_t sim_at(uint32_t x, uint32_t y) const { const seq_family& f = seq[x]; return f.sim_blk + (uint64_t)(x - f.first) * f.n + (y - f.first); }
+  bool same_family(uint32_t x, uint32_t y) const { return seq[x].first == seq[y].first; }
+  // host tables for the partition `fst` of nseq sequences (DAFS_HIP_EINVAL unless fst[0] = 0, fst[nfam] = nseq, strictly
+  // increasing), then their device copy
+  int build(const uint32_t* fst, uint32_t nfam_in, uint32_t nseq, hipStream_t st) {
+    if (nfam_in == 0 || fst[0] != 0 || fst[nfam_in] != nseq) return DAFS_HIP_EINVAL;
+    for (uint32_t f = 0; f < nfam_in; ++f)
+      if (fst[f + 1] <= fst[f]) return DAFS_HIP_EINVAL;
+    std::vector<uint32_t> nf(fst, fst + nfam_in + 1);
+    std::vector<seq_family> sq(nseq);
+    std::vector<uint64_t> p0(nfam_in + 1, 0), s0(nfam_in + 1, 0);
+    uint32_t mx = 0;
+    for (uint32_t f = 0; f < nfam_in; ++f) {
+      const uint64_t n = fst[f + 1] - fst[f];
+      mx = std::max(mx, (uint32_t)n);
+      p0[f + 1] = p0[f] + n * (n - 1) / 2;
+      s0[f + 1] = s0[f] + n * n;
+      for (uint64_t la = 0; la < n; ++la) {
+        seq_family& q = sq[fst[f] + la];
+        q.row_base = (uint32_t)(p0[f] + la * n - la * (la + 1) / 2);
+        q.first = fst[f]; q.n = (uint32_t)n; q.pad = 0; q.sim_blk = s0[f];
+      }
+    }
+    if (p0[nfam_in] > 0xFFFFFFFFull) return DAFS_HIP_EINVAL;  // pair ids are 32-bit
+    int rc;
+    if ((rc = d_seq.upload(sq.data(), nseq, st))) return rc;
+    first.swap(nf); seq.swap(sq); pair0.swap(p0); sim0.swap(s0); max_fam = mx;
+    return DAFS_HIP_OK;
+  }
+  // the pairs with ids [begin, end), in id order
+  void pairs(uint64_t begin, uint64_t end, uint32_t* px, uint32_t* py) const {
+    if (begin >= end) return;
+    uint32_t f = family_of_pair(begin);
+    const uint32_t n = first[f + 1] - first[f];
+    uint64_t rem = begin - pair0[f];
+    uint32_t a = 0;
+    while (rem >= (uint64_t)(n - 1 - a)) { rem -= (n - 1 - a); ++a; }
+    uint32_t i = first[f] + a, j = i + 1 + (uint32_t)rem;
+    for (uint64_t p = 0; p < end - begin; ++p) {
+      px[p] = i; py[p] = j;
+      if (++j == first[f + 1]) {
+        ++i; j = i + 1;
+        if (j >= first[f + 1]) {  // next family with a pair (families of one sequence have none)
+          do { ++f; } while (f + 1 < first.size() && first[f + 1] - first[f] < 2);
+          if (f + 1 >= first.size()) break;
+          i = first[f]; j = i + 1;
+        }
+      }
+    }
+  }
+  void release() { d_seq.release(); }
+};
+
 }  // namespace dafs
 
 struct dafs_hip_ctx {
@@ -104,6 +175,8 @@ struct dafs_hip_ctx {
   dafs::dev_buf<uint8_t> codes;
   dafs::dev_buf<uint32_t> d_len;
   dafs::dev_buf<uint64_t> d_seq_rp_off;
+  dafs::family_layout fam;  // the family partition (dafs_hip_set_families; one family by default)
+  dafs::mp_store_dev mp_view(const dafs::mp_store& st) const { return st.view(d_len.ptr, fam.d_seq.ptr, (uint32_t)len.size(), fam.max_fam); }
   // pair-HMM launch workspace
   dafs_pairhmm_plan plan{};
   dafs::dev_buf<dafs_pair_task> tasks;
@@ -114,7 +187,7 @@ struct dafs_hip_ctx {
   dafs::bp_store bp[2];
   dafs::bp_store bp_rows;  // dafs_hip_update_basepairing: constrained posteriors of the rows of one alignment (store index = row)
   int cur_mp = 0, cur_bp = 0;
-  // similarity matrix (host copy + device dense N*N)
+  // similarity scores (host copy + device): one dense n x n block per family, unit diagonal (family_layout::sim0)
   std::vector<float> sim;
   dafs::dev_buf<float> d_sim;
   dafs::dev_buf<uint32_t> d_pair_x, d_pair_y;
@@ -241,7 +314,7 @@ struct dafs_hip_ctx {
   uint32_t max_len() const { uint32_t m = 0; for (uint32_t l : len) m = l > m ? l : m; return m; }
 
   void free_all() {
-    codes.release(); d_len.release(); d_seq_rp_off.release(); tasks.release(); scratch.release(); task_sim.release();
+    codes.release(); d_len.release(); d_seq_rp_off.release(); fam.release(); tasks.release(); scratch.release(); task_sim.release();
     counters.release(); d_sim.release(); d_pair_x.release(); d_pair_y.release(); mp_ent2.release(); mp_ident2.release(); pct_tasks.release(); work.release(); work2.release(); d_nodes.release(); d_paused.release(); d_nodes2.release(); d_paused2.release(); d_tref.release(); for (int k = 0; k < 2; ++k) { d_pack_off[k].release(); d_pack[k].release(); } dd_release();
     for (int k = 0; k < 2; ++k) { if (h_paused[k]) (void)hipHostFree(h_paused[k]); h_paused[k] = nullptr; h_paused_cap[k] = 0; }
     d_cf_params.release(); cf_seqs.release(); cf_codes.release(); cf_iws.release(); cf_cons.release(); cf_fws.release(); cf_post.release(); cf_logz.release();

@@ -70,11 +70,14 @@ struct Options {
   int device = 0;
   std::vector<int> devices;  // --devices: one process per entry for phase 1
   std::string input;
+  std::vector<std::string> inputs;  // every FILE argument; with two or more, one output block per file
 };
 
 const char* kHelp =
     "DAFS: dual decomposition for simultaneous aligning and folding RNA sequences (MI355X build).\n"
-    "Usage:\n  dafs [OPTION...] FILE\n\n"
+    "Usage:\n  dafs [OPTION...] FILE [FILE ...]\n"
+    "  With several files every file is aligned as it would be alone; stdout holds one block per file, in argument\n"
+    "  order: a line \"==> FILE <==\" and then that file's output.\n\n"
     "  -h, --help            Print usage\n"
     "      --version         Print version\n"
     "  -r, --refinement N    The number of iteration of the iterative refinment (default: 0)\n"
@@ -143,6 +146,7 @@ Options parse(int argc, char** argv) {
       if (arg.size() > 2) { value = arg.substr(2); have_value = true; }
     } else {
       o.input = arg;
+      o.inputs.push_back(arg);
       continue;
     }
     const auto it = spec.find(name);
@@ -182,7 +186,12 @@ Options parse(int argc, char** argv) {
       for (float d : parse_floats(value)) o.devices.push_back((int)d);
       if (o.devices.empty()) throw std::string("--devices needs at least one device index");
     }
-    else if (name == "input") o.input = value;
+    else if (name == "input") { o.input = value; o.inputs.push_back(value); }
+  }
+  if (o.inputs.size() > 1) {
+    if (!o.align_aux.empty() || !o.fold_aux.empty() || !o.save_align_aux.empty() || !o.save_fold_aux.empty())
+      throw std::string("--align-aux, --fold-aux, --save-align-aux and --save-fold-aux name one file each: they need a single input FILE");
+    if (!o.devices.empty()) throw std::string("--devices shards one input: it needs a single input FILE");
   }
   // thresholds, reference src/dafs.cpp:1709-1750
   if (!th_given && !gamma.empty()) {
@@ -598,6 +607,26 @@ int rank_allgather(void* user, const void* send, void* recv, size_t bytes, void*
   return 0;
 }
 
+int align_group(dafs_hip_ctx* ctx, const Options& o, Ranks& rk, int align_model, const std::vector<std::vector<Fasta> >& fams,
+                const std::vector<size_t>& members, const std::vector<std::ostream*>& out);
+
+// rand() as a process that has not called it yet sees it: glibc's default generator is the one initstate(1, state, 128)
+// sets up, and rand() returns random()
+struct FreshRand {
+  random_data rd;
+  char state[128];
+  FreshRand() {
+    memset(&rd, 0, sizeof rd);
+    memset(state, 0, sizeof state);
+    initstate_r(1, state, sizeof state, &rd);
+  }
+  int next() {
+    int32_t r = 0;
+    random_r(&rd, &r);
+    return (int)r;
+  }
+};
+
 int run(const Options& o, Ranks& rk) {
   // ---- option checks mirroring parse_options (:1683-1763)
   int align_model;
@@ -619,19 +648,77 @@ int run(const Options& o, Ranks& rk) {
     if (!o.fold_model_given && o.fold_aux.empty()) std::cerr << "note: default folding model is CONTRAfold in this build" << std::endl;
   }
 
-  std::vector<Fasta> fa;
-  Fasta::load(fa, o.input.c_str());
-  const uint N = (uint)fa.size();
-  if (N == 0) throw "no sequences in the input";
+  // one family per input file
+  const bool multi = o.inputs.size() > 1;
+  std::vector<std::vector<Fasta> > fams(o.inputs.size());
+  for (size_t f = 0; f < o.inputs.size(); ++f) {
+    const std::string& file = o.inputs[f];
+    try {
+      Fasta::load(fams[f], file.c_str());
+    } catch (const std::system_error& e) {
+      if (multi) throw file + ": " + e.code().message();
+      throw;
+    }
+    if (fams[f].empty()) {
+      if (multi) throw file + ": no sequences in the input";
+      throw "no sequences in the input";
+    }
+  }
 
   dafs_hip_ctx* ctx = nullptr;
   check(dafs_hip_create(o.devices.empty() ? o.device : o.devices[rk.rank], &ctx));
   struct Guard { dafs_hip_ctx* c; ~Guard() { dafs_hip_destroy(c); } } guard{ctx};
 
+  if (!multi) return align_group(ctx, o, rk, align_model, fams, {0}, {&std::cout});
+  // Several files: every file with two or more sequences in one batch (dafs_hip_set_families: shared launches, one guide
+  // tree per family, the forest walked together); a file of one sequence takes the single-sequence path of a run of its
+  // own (no pairs, no consistency transforms) on the same context.  Each block is what `dafs FILE` prints.
+  std::vector<std::ostringstream> outs(o.inputs.size());
+  std::vector<size_t> batch;
+  for (size_t f = 0; f < fams.size(); ++f)
+    if (fams[f].size() > 1) batch.push_back(f);
+  auto names = [&](const std::vector<size_t>& members) {
+    std::string s;
+    for (size_t f : members) s += (s.empty() ? "" : ", ") + o.inputs[f];
+    return s;
+  };
+  auto group = [&](const std::vector<size_t>& members) {
+    std::vector<std::ostream*> os;
+    for (size_t f : members) os.push_back(&outs[f]);
+    try {
+      align_group(ctx, o, rk, align_model, fams, members, os);
+    } catch (const char* str) {
+      throw names(members) + ": " + str;
+    } catch (const std::string& str) {
+      throw names(members) + ": " + str;
+    }
+  };
+  if (!batch.empty()) group(batch);
+  for (size_t f = 0; f < fams.size(); ++f)
+    if (fams[f].size() == 1) group({f});
+  for (size_t f = 0; f < fams.size(); ++f) std::cout << "==> " << o.inputs[f] << " <==" << std::endl << outs[f].str();
+  std::cout.flush();
+  return 0;
+}
+
+// The run of one or more families (members: indices into fams) on the context: phase 1 once over all of them, one guide
+// tree per family, the progressive phase over the forest (the ready nodes of every family share each round), then per
+// family the refinement, the common structure and the output on *out[k].
+int align_group(dafs_hip_ctx* ctx, const Options& o, Ranks& rk, int align_model, const std::vector<std::vector<Fasta> >& fams,
+                const std::vector<size_t>& members, const std::vector<std::ostream*>& out) {
+  const uint F = (uint)members.size();
+  std::vector<Fasta> fa;         // every sequence of the group, family after family
+  std::vector<uint32_t> first(1, 0);
+  for (size_t f : members) {
+    fa.insert(fa.end(), fams[f].begin(), fams[f].end());
+    first.push_back((uint32_t)fa.size());
+  }
+  const uint N = (uint)fa.size();
   std::vector<const char*> seqs(N);
   std::vector<uint32_t> lens(N);
   for (uint i = 0; i < N; ++i) { seqs[i] = fa[i].seq().c_str(); lens[i] = fa[i].size(); }
   check(dafs_hip_set_sequences(ctx, N, seqs.data(), lens.data()));
+  if (F > 1) check(dafs_hip_set_families(ctx, F, first.data()));
 
   // base-pairing probabilities (:1787).  The device folding is only started here: it keeps one workgroup per
   // sequence busy, and the alignment posteriors and the matching-probability transform run beside it.
@@ -653,7 +740,8 @@ int run(const Options& o, Ranks& rk) {
     if (!o.save_fold_aux.empty() && !fold_saved) { save_fold_aux(ctx, o.save_fold_aux, fa); fold_saved = true; }
   };
 
-  std::vector<node_t> tree(1, std::make_pair(0.0f, std::make_pair(-1u, -1u)));
+  // per family its guide tree (a family of one sequence: the leaf alone)
+  std::vector<std::vector<node_t> > trees(F, std::vector<node_t>(1, std::make_pair(0.0f, std::make_pair(-1u, -1u))));
   if (N == 1) finish_folding();
   if (sharded) {
     // phase 1 (:1787-1827) on rk.world ranks: every rank ends with the complete stores, rank 0 goes on alone
@@ -665,7 +753,7 @@ int run(const Options& o, Ranks& rk) {
     if (!o.save_align_aux.empty()) save_align_aux(ctx, o.save_align_aux, fa);
     std::vector<float> sim((size_t)N * N);
     check(dafs_hip_get_sim(ctx, sim.data()));
-    tree = build_tree(sim, N);
+    trees[0] = build_tree(sim, N);
   } else if (N > 1) {
     // matching probabilities, transposes, similarities (:1796-1819), PCTs (:1822-1827), tree (:1830)
     if (!o.align_aux.empty()) load_align_aux(ctx, o.align_aux, fa);
@@ -675,15 +763,25 @@ int run(const Options& o, Ranks& rk) {
       finish_folding();
       check(dafs_hip_fourway_consistency(ctx, o.fourway));
     }
-    std::vector<float> sim((size_t)N * N);
+    size_t sim_floats = 0;  // one n x n block per family, one after another
+    for (uint f = 0; f < F; ++f) sim_floats += (size_t)(first[f + 1] - first[f]) * (first[f + 1] - first[f]);
+    std::vector<float> sim(sim_floats);
     check(dafs_hip_get_sim(ctx, sim.data()));
     check(dafs_hip_consistency_match(ctx, o.align_pct));
     finish_folding();
     check(dafs_hip_consistency_bp(ctx, o.fold_pct));
-    tree = build_tree(sim, N);
+    size_t blk = 0;
+    for (uint f = 0; f < F; ++f) {
+      const uint n = first[f + 1] - first[f];
+      trees[f] = build_tree(std::vector<float>(sim.begin() + blk, sim.begin() + blk + (size_t)n * n), n);
+      blk += (size_t)n * n;
+    }
   }
-  print_tree(std::cout, tree, fa, (int)tree.size() - 1);
-  std::cout << std::endl;
+  for (uint f = 0; f < F; ++f) {
+    const std::vector<Fasta>& ff = fams[members[f]];
+    print_tree(*out[f], trees[f], ff, (int)trees[f].size() - 1);
+    *out[f] << std::endl;
+  }
 
   // progressive alignment (:1838): every node whose children are ready is solved in the same batch
   dafs_dd_params prm;
@@ -696,35 +794,46 @@ int run(const Options& o, Ranks& rk) {
   // (dafs_dd_params::skip_uncoupled_folds).  The refinement itself compares scores.
   dafs_dd_params prm_prog = prm;
   prm_prog.skip_uncoupled_folds = (o.refinement == 0 && o.verbose == 0) ? 1 : 0;
-  std::vector<ALN> aln(tree.size());
-  std::vector<bool> done(tree.size(), false);
-  for (uint i = 0; i < N; ++i) {
-    aln[i].push_back(std::make_pair(i, std::vector<bool>(fa[i].size(), true)));
-    done[i] = true;
-  }
-  float s = 0.0f;
+  // The forest of the families' guide trees, one node array: family f's node i is tbase[f] + i, its leaf i the sequence
+  // first[f] + i.  A node is ready when both of its children are done, whatever its family.
+  std::vector<size_t> tbase(F + 1, 0);
+  for (uint f = 0; f < F; ++f) tbase[f + 1] = tbase[f] + trees[f].size();
+  std::vector<ALN> aln(tbase[F]);
+  std::vector<bool> done(tbase[F], false);
+  for (uint f = 0; f < F; ++f)
+    for (uint i = 0; i < first[f + 1] - first[f]; ++i) {
+      aln[tbase[f] + i].push_back(std::make_pair(first[f] + i, std::vector<bool>(fa[first[f] + i].size(), true)));
+      done[tbase[f] + i] = true;
+    }
+  std::vector<float> score(F, 0.0f);
   {
     // The nodes stay resident on the device (dafs_hip_nodes_*).  A round is one call (dafs_hip_nodes_round): the open
     // nodes advance while the nodes whose children have just finished are set up and started beside them, and all of
     // them stop together after kRoundUs microseconds, so a node that needs the full iteration budget does not hold
     // back its level and the set-up of new nodes does not stand between two launches.
     const uint32_t kRoundUs = getenv("DAFS_ROUND_US") ? (uint32_t)atoi(getenv("DAFS_ROUND_US")) : 2500u;
-    struct Open { uint node; uint32_t handle; NodeJob job; };
+    struct Open { uint fam; uint node; uint32_t handle; NodeJob job; };  // node: index within the family's tree
     std::vector<Open> open;
-    size_t remaining = tree.size() - N;
-    std::vector<bool> opened(tree.size(), false);
+    size_t remaining = tbase[F] - N;
+    std::vector<bool> opened(tbase[F], false);
     while (remaining) {
-      std::vector<uint> ready;
-      for (uint i = N; i < tree.size(); ++i)
-        if (!done[i] && !opened[i] && done[tree[i].second.first] && done[tree[i].second.second]) ready.push_back(i);
+      std::vector<std::pair<uint, uint> > ready;  // (family, node)
+      for (uint f = 0; f < F; ++f) {
+        const std::vector<node_t>& tree = trees[f];
+        const size_t tb = tbase[f];
+        for (uint i = first[f + 1] - first[f]; i < tree.size(); ++i)
+          if (!done[tb + i] && !opened[tb + i] && done[tb + tree[i].second.first] && done[tb + tree[i].second.second]) ready.push_back(std::make_pair(f, i));
+      }
       const size_t n_old = open.size();
       std::vector<dafs_node_input> in(ready.size() ? ready.size() : 1);
       for (size_t b = 0; b < ready.size(); ++b) {
-        open.push_back(Open{ready[b], 0, NodeJob()});
-        opened[ready[b]] = true;
+        open.push_back(Open{ready[b].first, ready[b].second, 0, NodeJob()});
+        opened[tbase[ready[b].first] + ready[b].second] = true;
       }
       for (size_t b = 0; b < ready.size(); ++b) {
-        const ALN &a1 = aln[tree[ready[b]].second.first], &a2 = aln[tree[ready[b]].second.second];
+        const std::vector<node_t>& tree = trees[ready[b].first];
+        const size_t tb = tbase[ready[b].first];
+        const ALN &a1 = aln[tb + tree[ready[b].second].second.first], &a2 = aln[tb + tree[ready[b].second].second.second];
         NodeJob& j = open[n_old + b].job;
         flatten(a1, j.s1, j.m1);
         flatten(a2, j.s2, j.m2);
@@ -732,7 +841,7 @@ int run(const Options& o, Ranks& rk) {
         in[b].len1 = (uint32_t)a1[0].second.size(); in[b].len2 = (uint32_t)a2[0].second.size();
         in[b].seq1 = j.s1.data(); in[b].seq2 = j.s2.data(); in[b].mask1 = j.m1.data(); in[b].mask2 = j.m2.data();
         j.x.resize(in[b].len1); j.y.resize(in[b].len2); j.z.resize(in[b].len1);
-        if (o.bp_update && ready[b] == tree.size() - 1) {
+        if (o.bp_update && ready[b].second == tree.size() - 1) {
           // the top call of the recursion re-estimates both base-pairing matrices under the structure decoded from
           // their averages (align_alignments(ss, ...), :919-934)
           j.px.resize((size_t)in[b].len1 * in[b].len1);
@@ -755,75 +864,83 @@ int run(const Options& o, Ranks& rk) {
         dafs_node_output r;
         r.x = o1.job.x.data(); r.y = o1.job.y.data(); r.z = o1.job.z.data();
         check(dafs_hip_nodes_result(ctx, o1.handle, &r));
-        const uint l = tree[o1.node].second.first, rr = tree[o1.node].second.second;
+        const std::vector<node_t>& tree = trees[o1.fam];
+        const size_t tb = tbase[o1.fam];
+        const size_t l = tb + tree[o1.node].second.first, rr = tb + tree[o1.node].second.second;
         ALN merged;
         project_alignment(merged, aln[l], aln[rr], o1.job.z);
-        aln[o1.node].swap(merged);
-        done[o1.node] = true;
+        aln[tb + o1.node].swap(merged);
+        done[tb + o1.node] = true;
         ALN().swap(aln[l]);
         ALN().swap(aln[rr]);
         if (o.verbose >= 1) std::cerr << "Step: " << r.iterations << ", Violated: " << r.violated << std::endl;  // :1292
-        if (o1.node == tree.size() - 1) s = r.score;
+        if (o1.node == tree.size() - 1) score[o1.fam] = r.score;
         --remaining;
       }
       open.swap(still);
     }
     check(dafs_hip_nodes_close(ctx));
   }
-  ALN& root = aln[tree.size() - 1];
-
-  // iterative refinement (:1841-1855, refine :1539-1576; rand() is unseeded there too)
-  for (int it = 0; it < o.refinement && root.size() > 1; ++it) {
-    VU group[2];
-    do {
-      group[0].clear();
-      group[1].clear();
-      for (uint i = 0; i != root.size(); ++i) group[rand() % 2].push_back(i);
-    } while (group[0].empty() || group[1].empty());
-    ALN part[2];
-    for (uint g = 0; g != 2; ++g) {
-      const uint n = (uint)group[g].size(), L = (uint)root[group[g][0]].second.size();
-      part[g].resize(n);
-      for (uint j = 0; j != n; ++j) part[g][j].first = root[group[g][j]].first;
-      for (uint k = 0; k != L; ++k) {
-        bool gap = true;
-        for (uint j = 0; j != n; ++j) gap &= !root[group[g][j]].second[k];
-        if (!gap)
-          for (uint j = 0; j != n; ++j) part[g][j].second.push_back(root[group[g][j]].second[k]);
+  for (uint f = 0; f < F; ++f) {
+    ALN& root = aln[tbase[f + 1] - 1];
+    float s = score[f];
+    // iterative refinement (:1841-1855, refine :1539-1576; rand() is unseeded there too).  The draws come from a generator
+    // of the family's own in the state rand() has at the start of a process, so that they are those of a run of its own
+    // whatever else in the process (other families, the runtime's threads) calls rand()
+    FreshRand rng;
+    for (int it = 0; it < o.refinement && root.size() > 1; ++it) {
+      VU group[2];
+      do {
+        group[0].clear();
+        group[1].clear();
+        for (uint i = 0; i != root.size(); ++i) group[rng.next() % 2].push_back(i);
+      } while (group[0].empty() || group[1].empty());
+      ALN part[2];
+      for (uint g = 0; g != 2; ++g) {
+        const uint n = (uint)group[g].size(), L = (uint)root[group[g][0]].second.size();
+        part[g].resize(n);
+        for (uint j = 0; j != n; ++j) part[g][j].first = root[group[g][j]].first;
+        for (uint k = 0; k != L; ++k) {
+          bool gap = true;
+          for (uint j = 0; j != n; ++j) gap &= !root[group[g][j]].second[k];
+          if (!gap)
+            for (uint j = 0; j != n; ++j) part[g][j].second.push_back(root[group[g][j]].second[k]);
+        }
       }
+      std::vector<ALN> merged;
+      const std::vector<float> sc = solve_batch(ctx, prm, {&part[0]}, {&part[1]}, merged, o.verbose, o.bp_update);
+      if (sc[0] > s) { s = sc[0]; root.swap(merged[0]); }
     }
-    std::vector<ALN> merged;
-    const std::vector<float> sc = solve_batch(ctx, prm, {&part[0]}, {&part[1]}, merged, o.verbose, o.bp_update);
-    if (sc[0] > s) { s = sc[0]; root.swap(merged[0]); }
-  }
 
-  // common secondary structure of the final alignment (:1857-1871; no RNAalifold term here)
-  std::string str;
-  {
-    std::vector<uint32_t> rs;
-    std::vector<uint8_t> rm;
-    flatten(root, rs, rm);
-    const uint32_t L = (uint32_t)root[0].second.size();
-    VU ss(L);
-    check(dafs_hip_consensus_structure(ctx, (uint32_t)root.size(), L, rs.data(), rm.data(), o.fold_th1[0], ss.data(), nullptr, nullptr));
-    if (o.bp_update1) {  // :1863-1869: re-estimate under the decoded structure, decode again (SparseNussinov::decode(p, ss, str))
-      std::vector<float> p((size_t)L * L);
-      check(dafs_hip_update_basepairing(ctx, (uint32_t)root.size(), L, rs.data(), rm.data(), ss.data(), p.data()));
-      check(dafs_hip_nussinov_decode(ctx, o.fold_th1[0], 0.0f, L, p.data(), nullptr, ss.data(), nullptr));
+    // common secondary structure of the final alignment (:1857-1871; no RNAalifold term here)
+    std::string str;
+    {
+      std::vector<uint32_t> rs;
+      std::vector<uint8_t> rm;
+      flatten(root, rs, rm);
+      const uint32_t L = (uint32_t)root[0].second.size();
+      VU ss(L);
+      check(dafs_hip_consensus_structure(ctx, (uint32_t)root.size(), L, rs.data(), rm.data(), o.fold_th1[0], ss.data(), nullptr, nullptr));
+      if (o.bp_update1) {  // :1863-1869: re-estimate under the decoded structure, decode again (SparseNussinov::decode(p, ss, str))
+        std::vector<float> p((size_t)L * L);
+        check(dafs_hip_update_basepairing(ctx, (uint32_t)root.size(), L, rs.data(), rm.data(), ss.data(), p.data()));
+        check(dafs_hip_nussinov_decode(ctx, o.fold_th1[0], 0.0f, L, p.data(), nullptr, ss.data(), nullptr));
+      }
+      std::vector<char> buf(L + 1);
+      dafs_hip_make_brackets(L, ss.data(), buf.data());
+      str.assign(buf.data());
     }
-    std::vector<char> buf(L + 1);
-    dafs_hip_make_brackets(L, ss.data(), buf.data());
-    str.assign(buf.data());
-  }
 
-  // output (:1876-1879, :1584-1601)
-  std::sort(root.begin(), root.end());
-  std::cout << ">SS_cons" << std::endl << str << std::endl;
-  for (const auto& row : root) {
-    const std::string& sq = fa[row.first].seq();
-    std::cout << "> " << fa[row.first].name() << std::endl;
-    for (uint j = 0, k = 0; j != row.second.size(); ++j) std::cout << (row.second[j] ? sq[k++] : '-');
-    std::cout << std::endl;
+    // output (:1876-1879, :1584-1601)
+    std::sort(root.begin(), root.end());
+    std::ostream& os = *out[f];
+    os << ">SS_cons" << std::endl << str << std::endl;
+    for (const auto& row : root) {
+      const std::string& sq = fa[row.first].seq();
+      os << "> " << fa[row.first].name() << std::endl;
+      for (uint j = 0, k = 0; j != row.second.size(); ++j) os << (row.second[j] ? sq[k++] : '-');
+      os << std::endl;
+    }
   }
   return 0;
 }

@@ -211,20 +211,21 @@ __host__ __device__ static inline size_t pct_group_words(uint32_t row_cap) { ret
 
 __global__ __launch_bounds__(256) void k_pct_rows(pct_match_args a, uint32_t pair0, uint32_t row_cap) {
   extern __shared__ unsigned char s_raw[];
-  const uint32_t N = a.in.nseq;
+  const uint32_t Z = a.in.max_fam;  // the per-z tables hold the largest family of the launch
   const uint32_t tid = threadIdx.x, nt = blockDim.x;
   const uint32_t t = tid & 15u;
   const int gw = (int)(tid >> 4);
   // workgroup tables, per z: ADDRESSES of the row pointers and of the entries of mp[x][z] (a-side) and of mp[z][y] (b-side),
   // and w_z.  The identity matrices mp[x][x] and mp[y][y] (align.cpp:42-44) are ordinary CSRs here (ident_rp / ident2), so
   // that no step of the row loop knows about them.
+  // The z of the tables run over the output pair's family (dafs_hip_set_families): entry zl is sequence fx.first + zl.
   uint64_t* a_rp = (uint64_t*)s_raw;
-  uint64_t* a_ent = a_rp + N;
-  uint64_t* b_rp = a_ent + N;
-  uint64_t* b_ent = b_rp + N;
-  float* wz = (float*)(b_ent + N);
+  uint64_t* a_ent = a_rp + Z;
+  uint64_t* b_rp = a_ent + Z;
+  uint64_t* b_ent = b_rp + Z;
+  float* wz = (float*)(b_ent + Z);
   // per group (= per output row): the accumulator row, the lanes' trash cells, the a-row bookkeeping of the current chunk
-  float* acc = wz + ((N + 1) & ~1u) + (size_t)gw * pct_group_words(row_cap);
+  float* acc = wz + ((Z + 1) & ~1u) + (size_t)gw * pct_group_words(row_cap);
   uint64_t* zabase = (uint64_t*)(acc + row_cap + PCT_TRASH);  // per z-lane: address of item tl of the chunk = zabase + 8 tl
   uint32_t* zoff = (uint32_t*)(zabase + 16);                   // exclusive item offsets of the z-lanes (zoff[16] = items of the chunk)
 
@@ -241,28 +242,31 @@ __global__ __launch_bounds__(256) void k_pct_rows(pct_match_args a, uint32_t pai
   const uint32_t L1 = a.in.len[x], L2 = a.in.len[y];
   const uint32_t row0 = rb * PCT_ROWS_PER_WG;
   if (row0 >= L1) return;
+  const seq_family fx = a.in.fam[x];
+  const uint32_t N = fx.n;  // the family's size takes the place of the reference's N
   // dafs.cpp:280-288 and the two sparse matrices every z contributes
-  for (uint32_t z = tid; z < N; z += nt) {
-    float w = a.sim[(size_t)z * N + x] * a.sim[(size_t)z * N + y];
+  for (uint32_t zl = tid; zl < N; zl += nt) {
+    const uint32_t z = fx.first + zl;
+    float w = fam_sim(a.sim, fx, z, x) * fam_sim(a.sim, fx, z, y);
     if (a.w_pct < 0.0) w *= 1.0 / N;
     else if (z == x || z == y) w *= (1.0 - a.w_pct) / 2;
     else w *= a.w_pct / (N - 2);
-    wz[z] = w;
-    if (z == x) { a_rp[z] = (uint64_t)a.in.ident_rp; a_ent[z] = (uint64_t)a.in.ident2; }  // mp[x][x]
+    wz[zl] = w;
+    if (z == x) { a_rp[zl] = (uint64_t)a.in.ident_rp; a_ent[zl] = (uint64_t)a.in.ident2; }  // mp[x][x]
     else {
       const uint32_t lo = x < z ? x : z, hi = x < z ? z : x;
-      const uint32_t tk = a.in.task_of_pair[pair_id(lo, hi, N)];
+      const uint32_t tk = a.in.task_of_pair[pair_id(lo, hi, a.in.fam)];
       const bool fwd = x < z;
-      a_rp[z] = (uint64_t)(a.in.rowptr_pool + (a.in.rp_off[tk] + (fwd ? 0 : a.in.len[lo] + 1)));
-      a_ent[z] = (uint64_t)(a.in.ent2 + (a.in.pair_off[tk] + (fwd ? 0 : a.in.pair_nnz[tk])));
+      a_rp[zl] = (uint64_t)(a.in.rowptr_pool + (a.in.rp_off[tk] + (fwd ? 0 : a.in.len[lo] + 1)));
+      a_ent[zl] = (uint64_t)(a.in.ent2 + (a.in.pair_off[tk] + (fwd ? 0 : a.in.pair_nnz[tk])));
     }
-    if (z == y) { b_rp[z] = (uint64_t)a.in.ident_rp; b_ent[z] = (uint64_t)a.in.ident2; }  // mp[y][y]
+    if (z == y) { b_rp[zl] = (uint64_t)a.in.ident_rp; b_ent[zl] = (uint64_t)a.in.ident2; }  // mp[y][y]
     else {
       const uint32_t lo = z < y ? z : y, hi = z < y ? y : z;
-      const uint32_t tk = a.in.task_of_pair[pair_id(lo, hi, N)];
+      const uint32_t tk = a.in.task_of_pair[pair_id(lo, hi, a.in.fam)];
       const bool fwd = z < y;
-      b_rp[z] = (uint64_t)(a.in.rowptr_pool + (a.in.rp_off[tk] + (fwd ? 0 : a.in.len[lo] + 1)));
-      b_ent[z] = (uint64_t)(a.in.ent2 + (a.in.pair_off[tk] + (fwd ? 0 : a.in.pair_nnz[tk])));
+      b_rp[zl] = (uint64_t)(a.in.rowptr_pool + (a.in.rp_off[tk] + (fwd ? 0 : a.in.len[lo] + 1)));
+      b_ent[zl] = (uint64_t)(a.in.ent2 + (a.in.pair_off[tk] + (fwd ? 0 : a.in.pair_nnz[tk])));
     }
   }
   __syncthreads();
@@ -450,16 +454,16 @@ __global__ __launch_bounds__(256) void k_pct_emit(pct_match_args a, uint32_t pai
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_pct_bp_rows(pct_bp_args a, uint32_t row_cap) {
   extern __shared__ unsigned char s_raw[];
-  const uint32_t N = a.mp.nseq;
+  const uint32_t Z = a.mp.max_fam;  // the per-y tables hold the largest family of the launch
   const uint32_t tid = threadIdx.x, nt = blockDim.x;
   const int t = (int)(tid & 15), gw = (int)(tid >> 4);
-  // per y: bases of mp[x][y] (a-side) and of mp[y][x] (c-side), and w_y
+  // per y of x's family (entry yl is sequence first + yl): bases of mp[x][y] (a-side) and of mp[y][x] (c-side), and w_y
   uint64_t* a_rp = (uint64_t*)s_raw;
-  uint64_t* a_ent = a_rp + N;
-  uint64_t* c_rp = a_ent + N;
-  uint64_t* c_ent = c_rp + N;
-  float* wy = (float*)(c_ent + N);
-  unsigned char* gbase = (unsigned char*)(wy + ((N + 1) & ~1u)) + (size_t)gw * ((size_t)row_cap * 4 + 16 * 8 + 20 * 4 + 16 * 4);
+  uint64_t* a_ent = a_rp + Z;
+  uint64_t* c_rp = a_ent + Z;
+  uint64_t* c_ent = c_rp + Z;
+  float* wy = (float*)(c_ent + Z);
+  unsigned char* gbase = (unsigned char*)(wy + ((Z + 1) & ~1u)) + (size_t)gw * ((size_t)row_cap * 4 + 16 * 8 + 20 * 4 + 16 * 4);
   uint64_t* zaent = (uint64_t*)gbase;
   uint32_t* zoff = (uint32_t*)(zaent + 16);
   uint32_t* zid = zoff + 20;
@@ -469,20 +473,23 @@ __global__ __launch_bounds__(256) void k_pct_bp_rows(pct_bp_args a, uint32_t row
   const uint32_t L1 = a.mp.len[x];
   const uint32_t row0 = blockIdx.y * PCT_ROWS_PER_WG;
   if (row0 >= L1) return;
-  for (uint32_t y = tid; y < N; y += nt) {
-    float w = a.sim[(size_t)y * N + x];  // dafs.cpp:341-348
+  const seq_family fx = a.mp.fam[x];
+  const uint32_t N = fx.n, y0 = fx.first;  // the family's size takes the place of the reference's N
+  for (uint32_t yl = tid; yl < N; yl += nt) {
+    const uint32_t y = y0 + yl;
+    float w = fam_sim(a.sim, fx, y, x);  // dafs.cpp:341-348
     if (a.w_pct < 0.0) w *= 1.0 / N;
     else if (y == x) w *= 1.0 - a.w_pct;
     else w *= a.w_pct / (N - 1);
-    wy[y] = w;
-    a_rp[y] = 0; a_ent[y] = 0; c_rp[y] = 0; c_ent[y] = 0;
+    wy[yl] = w;
+    a_rp[yl] = 0; a_ent[yl] = 0; c_rp[yl] = 0; c_ent[yl] = 0;
     if (y != x) {
       const uint32_t lo = x < y ? x : y, hi = x < y ? y : x;
-      const uint32_t tk = a.mp.task_of_pair[pair_id(lo, hi, N)];
+      const uint32_t tk = a.mp.task_of_pair[pair_id(lo, hi, a.mp.fam)];
       const uint64_t rp = a.mp.rp_off[tk], ent = a.mp.pair_off[tk], nz = a.mp.pair_nnz[tk];
       const uint64_t rp2 = rp + a.mp.len[lo] + 1, ent2 = ent + nz;  // the transposed half of the task
-      a_rp[y] = x < y ? rp : rp2; a_ent[y] = x < y ? ent : ent2;    // mp[x][y]
-      c_rp[y] = x < y ? rp2 : rp; c_ent[y] = x < y ? ent2 : ent;    // mp[y][x]
+      a_rp[yl] = x < y ? rp : rp2; a_ent[yl] = x < y ? ent : ent2;    // mp[x][y]
+      c_rp[yl] = x < y ? rp2 : rp; c_ent[yl] = x < y ? ent2 : ent;    // mp[y][x]
     }
   }
   __syncthreads();
@@ -500,18 +507,18 @@ __global__ __launch_bounds__(256) void k_pct_bp_rows(pct_bp_args a, uint32_t row
     // ---- rows mp[x][y][i] of the chunk, one lane per y (y == x: the identity row {(i, 1)})
     uint32_t na = 0;
     {
-      const uint32_t y = yc + (uint32_t)t;
+      const uint32_t yl = yc + (uint32_t)t;  // index within the family
       uint64_t ent = 0;
-      if (rowact && y < N) {
-        if (y == x) na = 1;
+      if (rowact && yl < N) {
+        if (y0 + yl == x) na = 1;
         else {
-          const uint32_t beg = a.mp.rowptr_pool[a_rp[y] + i], end = a.mp.rowptr_pool[a_rp[y] + i + 1];
+          const uint32_t beg = a.mp.rowptr_pool[a_rp[yl] + i], end = a.mp.rowptr_pool[a_rp[yl] + i + 1];
           na = end - beg;
-          ent = a_ent[y] + beg;
+          ent = a_ent[yl] + beg;
         }
       }
       zaent[t] = ent;
-      zid[t] = y;
+      zid[t] = yl;
     }
     uint32_t incl = na;
 #pragma unroll
@@ -536,11 +543,11 @@ __global__ __launch_bounds__(256) void k_pct_bp_rows(pct_bp_args a, uint32_t row
         uint32_t zz = 0;
 #pragma unroll
         for (int q = 1; q < PCT_G; ++q) zz += (tl >= zoff[q]) ? 1u : 0u;
-        my_y = zid[zz];
+        my_y = zid[zz];  // within the family
         uint32_t k = i;
         my_pik = 1.0f;
-        if (my_y != x) { const uint2 cv = a.mp.ent2[zaent[zz] + (tl - zoff[zz])]; k = cv.x; my_pik = __uint_as_float(cv.y); }
-        const row_ref b = bp_row(a.bp, my_y, k);  // (l, p_kl)
+        if (y0 + my_y != x) { const uint2 cv = a.mp.ent2[zaent[zz] + (tl - zoff[zz])]; k = cv.x; my_pik = __uint_as_float(cv.y); }
+        const row_ref b = bp_row(a.bp, y0 + my_y, k);  // (l, p_kl)
         my_nb = b.n;
         const uint64_t off = (uint64_t)(b.col - a.bp.col);
         my_lo = (uint32_t)off; my_hi = (uint32_t)(off >> 32);
@@ -564,7 +571,7 @@ __global__ __launch_bounds__(256) void k_pct_bp_rows(pct_bp_args a, uint32_t row
             const float pkl = a.bp.val[boff + e0 + (uint32_t)t];
             it.pik = pkl * pik;  // p_kl * p_ik, then * p_jl * w (:359, :368)
             it.w = wy[yq];
-            if (yq == x) {  // mp[x][x][l] = {(l, 1)}
+            if (y0 + yq == x) {  // mp[x][x][l] = {(l, 1)}
               const uint64_t adr = (uint64_t)(a.mp.ident2 + l);
               it.n = 1; it.ptr_lo = (uint32_t)adr; it.ptr_hi = (uint32_t)(adr >> 32);
             } else {
@@ -709,12 +716,13 @@ int mp_sim_launch(mp_store_dev in, const uint32_t* pair_x, const uint32_t* pair_
 
 static const size_t kPctLdsBytes = 150 * 1024;  // leave room for the static LDS and alignment
 
-size_t pct_rows_lds_bytes(uint32_t nseq, uint32_t row_cap) {
-  return (size_t)nseq * 32 + (((size_t)nseq + 1) & ~(size_t)1) * 4 + (size_t)PCT_ROWS_PER_WG * ((size_t)row_cap * 4 + 16 * 8 + 20 * 4 + 16 * 4) + 64;
+// The per-z (per-y) tables take 36 bytes per sequence of the largest family of the launch (max_fam), not of the context.
+size_t pct_rows_lds_bytes(uint32_t max_fam, uint32_t row_cap) {
+  return (size_t)max_fam * 32 + (((size_t)max_fam + 1) & ~(size_t)1) * 4 + (size_t)PCT_ROWS_PER_WG * ((size_t)row_cap * 4 + 16 * 8 + 20 * 4 + 16 * 4) + 64;
 }
 // k_pct_rows (round 3 layout: trash cells behind every accumulator row)
-size_t pct_rows2_lds_bytes(uint32_t nseq, uint32_t row_cap) {
-  return (size_t)nseq * 32 + (((size_t)nseq + 1) & ~(size_t)1) * 4 + (size_t)PCT_ROWS_PER_WG * pct_group_words(row_cap) * 4 + 64;
+size_t pct_rows2_lds_bytes(uint32_t max_fam, uint32_t row_cap) {
+  return (size_t)max_fam * 32 + (((size_t)max_fam + 1) & ~(size_t)1) * 4 + (size_t)PCT_ROWS_PER_WG * pct_group_words(row_cap) * 4 + 64;
 }
 
 // pairs [pair0, pair0 + count) whose tiles (a.tile, a.tile_off, a.sum_w) have been laid out by the caller
@@ -738,7 +746,7 @@ __global__ __launch_bounds__(256) void k_fourway_rows(pct_match_args a, uint32_t
   if (tid == 0) a.sum_w[blockIdx.x] = 1.0f;
   __syncthreads();
   const float w = a.w_f;
-  const uint32_t t = a.in.task_of_pair[pair_id(x, y, a.in.nseq)];
+  const uint32_t t = a.in.task_of_pair[pair_id(x, y, a.in.fam)];
   const uint32_t* rp = a.in.rowptr_pool + a.in.rp_off[t];  // row pointers of mp[x][y]
   const uint32_t nnz = a.in.pair_nnz[t];
   const uint32_t* mcol = a.in.col + a.in.pair_off[t];
@@ -823,7 +831,7 @@ int pct_match_launch(pct_match_args a, uint32_t max_len, uint32_t pair0, uint32_
   // second row sixteen banks away from the first (four banks away: two lanes per bank on almost every update -- 1.9 G
   // conflict cycles per 2.3 G LDS instructions at N = 128).
   const uint32_t row_cap = max_len + ((28u - max_len) & 31u);
-  const size_t lds = pct_rows2_lds_bytes(a.in.nseq, row_cap);
+  const size_t lds = pct_rows2_lds_bytes(a.in.max_fam, row_cap);
   if (lds > kPctLdsBytes) return DAFS_HIP_ETOOLONG;
   a.max_len = max_len;
   static bool attr[16] = {false};
@@ -844,7 +852,7 @@ int pct_bp_launch(pct_bp_args a, uint32_t max_len, hipStream_t st) {
   // sixteen banks away from the first (a multiple of 16, as before, put it four banks away: two lanes per bank on
   // almost every update -- 1.9 G conflict cycles per 2.3 G LDS instructions at N = 128).
   const uint32_t row_cap = max_len + ((12u - max_len) & 31u);
-  const size_t lds = pct_rows_lds_bytes(a.mp.nseq, row_cap);
+  const size_t lds = pct_rows_lds_bytes(a.mp.max_fam, row_cap);
   if (lds > kPctLdsBytes) return DAFS_HIP_ETOOLONG;
   a.max_len = max_len;
   static bool attr[16] = {false};

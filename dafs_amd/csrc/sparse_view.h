@@ -4,11 +4,27 @@
 // mp[a][b] and, right behind them, of mp[b][a] (the layout k_pairhmm3 writes, include/dafs_hip.h).
 // mp_rows(a,b,i) returns row i of mp[a][b] for any a != b; mp[a][a] is the identity
 // (reference src/align.cpp:42-44) and is handled by the callers.
+//
+// Family partition: the sequences of a context are split into contiguous ranges ("families", dafs_hip_set_families) and
+// only pairs within a family exist.  Pairs are numbered family by family, row-major inside each: pair_id(a, b) =
+// row_base[a] + (b - a - 1), with row_base[a] = (pairs of the families before a's) + la * n - la * (la + 1) / 2 for
+// a's index la inside its family of n sequences.  With one family this is the plain row-major triangle over all N.
+// The similarity scores are one dense n x n block per family (unit diagonal), the blocks one after another.
+// family_layout (ctx.h) is the one host helper that builds these tables.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 namespace dafs {
+
+// per sequence: where its family's pairs and similarity block lie
+struct seq_family {
+  uint32_t row_base;  // pair id of (a, a + 1) if that pair exists; see pair_id
+  uint32_t first;     // first sequence of the family
+  uint32_t n;         // sequences in the family
+  uint32_t pad;
+  uint64_t sim_blk;   // first float of the family's n x n similarity block
+};
 
 struct mp_store_dev {
   const uint32_t* rowptr_pool;
@@ -21,9 +37,11 @@ struct mp_store_dev {
   const uint64_t* pair_off;      // per task: first entry of mp[a][b]; mp[b][a] follows after nnz entries
   const uint32_t* pair_nnz;      // per task
   const uint64_t* rp_off;        // per task: first row pointer (len[a]+1 of them, then len[b]+1)
-  const uint32_t* task_of_pair;  // row-major pair id (a<b) -> task
+  const uint32_t* task_of_pair;  // pair id (a<b, pair_id) -> task
   const uint32_t* len;           // sequence lengths
+  const seq_family* fam;         // per sequence
   uint32_t nseq;
+  uint32_t max_fam;              // sequences in the largest family
 };
 
 struct bp_store_dev {
@@ -40,15 +58,20 @@ struct row_ref {
   uint32_t n;
 };
 
-__device__ __forceinline__ uint32_t pair_id(uint32_t a, uint32_t b, uint32_t n) {  // a < b
-  return a * n - a * (a + 1) / 2 + (b - a - 1);
+__device__ __forceinline__ uint32_t pair_id(uint32_t a, uint32_t b, const seq_family* fam) {  // a < b, one family
+  return fam[a].row_base + (b - a - 1);
+}
+
+// sim of sequences u, v of one family
+__device__ __forceinline__ float fam_sim(const float* sim, const seq_family& f, uint32_t u, uint32_t v) {
+  return sim[f.sim_blk + (size_t)(u - f.first) * f.n + (v - f.first)];
 }
 
 // row i of mp[a][b], a != b
 __device__ __forceinline__ row_ref mp_row(const mp_store_dev& s, uint32_t a, uint32_t b, uint32_t i) {
   row_ref r;
   if (a < b) {
-    const uint32_t t = s.task_of_pair[pair_id(a, b, s.nseq)];
+    const uint32_t t = s.task_of_pair[pair_id(a, b, s.fam)];
     const uint32_t* rp = s.rowptr_pool + s.rp_off[t];
     const uint64_t base = s.pair_off[t];
     const uint32_t beg = rp[i];
@@ -56,7 +79,7 @@ __device__ __forceinline__ row_ref mp_row(const mp_store_dev& s, uint32_t a, uin
     r.col = s.col + base + beg;
     r.val = s.val + base + beg;
   } else {
-    const uint32_t t = s.task_of_pair[pair_id(b, a, s.nseq)];
+    const uint32_t t = s.task_of_pair[pair_id(b, a, s.fam)];
     const uint32_t* rp = s.rowptr_pool + s.rp_off[t] + s.len[b] + 1;
     const uint64_t base = s.pair_off[t] + s.pair_nnz[t];
     const uint32_t beg = rp[i];

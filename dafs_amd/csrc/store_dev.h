@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "sparse_view.h"
 
 namespace dafs {
 int scan_excl_launch(const uint32_t* in, uint32_t mul, uint64_t* out, uint64_t n, hipStream_t st);  // out[n + 1]
@@ -13,5 +14,6 @@ int bp_block_nnz_launch(const uint32_t* rowptr, const uint64_t* blk_rp_off, cons
 int bp_by_seq_launch(const uint32_t* seq_of_blk, uint32_t nblk, const uint32_t* nnz_by_blk, const uint64_t* off_by_blk, uint32_t* nnz, uint64_t* bp_off, hipStream_t st);
 int bp_pack_launch(uint32_t nseq, const uint64_t* bp_off, const uint32_t* nnz, const uint32_t* col, const float* val, const uint64_t* prefix, uint32_t* col_out,
                    float* val_out, hipStream_t st);
-int sim_matrix_launch(const uint32_t* pair_x, const uint32_t* pair_y, const float* sim, uint64_t np, uint32_t n, float* out, hipStream_t st);
+// the similarity blocks of the family partition (sparse_view.h) from per-pair scores in pair-id order
+int sim_matrix_launch(const uint32_t* pair_x, const uint32_t* pair_y, const float* sim, uint64_t np, const seq_family* fam, uint32_t n, float* out, hipStream_t st);
 }  // namespace dafs

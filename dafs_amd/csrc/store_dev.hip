@@ -70,12 +70,19 @@ __global__ __launch_bounds__(256) void k_bp_pack(const uint64_t* __restrict__ bp
   const uint64_t src = bp_off[x], dst = prefix[x], n = nnz[x];
   for (uint64_t e = threadIdx.x; e < n; e += blockDim.x) { col_out[dst + e] = col[src + e]; val_out[dst + e] = val[src + e]; }
 }
-// dense N x N similarity matrix with unit diagonal from the per-pair scores in row-major pair order
+// the similarity blocks of the family partition (sparse_view.h: one dense n x n block per family, unit diagonal) from the
+// per-pair scores in pair-id order
 __global__ __launch_bounds__(256) void k_sim_matrix(const uint32_t* __restrict__ pair_x, const uint32_t* __restrict__ pair_y, const float* __restrict__ sim, uint64_t np,
-                                                    uint32_t n, float* __restrict__ out) {
+                                                    const seq_family* __restrict__ fam, uint32_t n, float* __restrict__ out) {
   const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (k < np) { const uint32_t x = pair_x[k], y = pair_y[k]; out[(size_t)x * n + y] = sim[k]; out[(size_t)y * n + x] = sim[k]; }
-  if (k < n) out[(size_t)k * n + k] = 1.0f;
+  if (k < np) {
+    const uint32_t x = pair_x[k], y = pair_y[k];
+    const seq_family f = fam[x];
+    const size_t lx = x - f.first, ly = y - f.first;
+    out[f.sim_blk + lx * f.n + ly] = sim[k];
+    out[f.sim_blk + ly * f.n + lx] = sim[k];
+  }
+  if (k < n) { const seq_family f = fam[k]; const size_t lk = k - f.first; out[f.sim_blk + lk * f.n + lk] = 1.0f; }
 }
 
 int scan_excl_launch(const uint32_t* in, uint32_t mul, uint64_t* out, uint64_t n, hipStream_t st) {
@@ -110,9 +117,9 @@ int bp_pack_launch(uint32_t nseq, const uint64_t* bp_off, const uint32_t* nnz, c
   hipLaunchKernelGGL(k_bp_pack, dim3(nseq), dim3(256), 0, st, bp_off, nnz, col, val, prefix, col_out, val_out);
   return hip_check(hipGetLastError()) ? DAFS_HIP_ELAUNCH : DAFS_HIP_OK;
 }
-int sim_matrix_launch(const uint32_t* pair_x, const uint32_t* pair_y, const float* sim, uint64_t np, uint32_t n, float* out, hipStream_t st) {
+int sim_matrix_launch(const uint32_t* pair_x, const uint32_t* pair_y, const float* sim, uint64_t np, const seq_family* fam, uint32_t n, float* out, hipStream_t st) {
   const uint64_t m = np > n ? np : n;
-  hipLaunchKernelGGL(k_sim_matrix, dim3((uint32_t)((m + 255) / 256)), dim3(256), 0, st, pair_x, pair_y, sim, np, n, out);
+  hipLaunchKernelGGL(k_sim_matrix, dim3((uint32_t)((m + 255) / 256)), dim3(256), 0, st, pair_x, pair_y, sim, np, fam, n, out);
   return hip_check(hipGetLastError()) ? DAFS_HIP_ELAUNCH : DAFS_HIP_OK;
 }
 

@@ -120,69 +120,126 @@ def run(names, seqs, ctx=None, bp=None, w=4.0, eta0=0.5, t_max=600, w_pct_a=0.25
                    skip_uncoupled_folds, round_us, bp_update, bp_update1)
 
 
-def _phase1_local(ctx, seqs, bp, mp, align_model, th_a, w_pct_a, w_pct_s, t, w_pct_f=0.0):
+def _phase1_local(ctx, seqs, bp, mp, align_model, th_a, w_pct_a, w_pct_s, t, w_pct_f=0.0, first=None):
+    """Phase 1 on the context: folds, pair posteriors, consistency transforms.  first: family partition (run_batch); the
+    result is then the list of the families' similarity blocks instead of one matrix."""
     import time
     ctx.set_sequences(seqs)
+    if first is not None and len(first) > 2:
+        ctx.set_families(first)
     # The folding (one workgroup per sequence) leaves most of the device idle, and nothing before the base-pair
     # transform needs its result: it is started on its own stream, and the all-pairs alignment posteriors and the
     # matching-probability transform run beside it.
-    if bp is not None:
-        ctx.set_bp(bp)
-    else:
-        ctx.fold_begin(0.01)
-    t.append(time.perf_counter())
-    if mp is not None:
-        ctx.set_mp(*mp)  # (nnz, rowptr, col, val) of every pair, --align-aux
-    else:
-        ctx.align_posteriors(align_model, th_a, fetch=False)
-    t.append(time.perf_counter())
-    folded = bp is not None
-    if w_pct_f != 0.0:  # relax_fourway_consistency (dafs.cpp:1808): needs the base-pairing rows, replaces mp_ before sim_
-        if not folded:
+    folding = False
+    try:
+        if bp is not None:
+            ctx.set_bp(bp)
+        else:
+            ctx.fold_begin(0.01)
+            folding = True
+        t.append(time.perf_counter())
+        if mp is not None:
+            ctx.set_mp(*mp)  # (nnz, rowptr, col, val) of every pair, --align-aux
+        else:
+            ctx.align_posteriors(align_model, th_a, fetch=False)
+        t.append(time.perf_counter())
+        if w_pct_f != 0.0:  # relax_fourway_consistency (dafs.cpp:1808): needs the base-pairing rows, replaces mp_ before sim_
+            if folding:
+                folding = False
+                ctx.fold_end()
+            ctx.fourway_consistency(w_pct_f)
+        sim = ctx.sim() if first is None or len(first) <= 2 else ctx.sim_blocks()
+        ctx.consistency_match(w_pct_a)
+        if folding:
+            folding = False
             ctx.fold_end()
-            folded = True
-        ctx.fourway_consistency(w_pct_f)
-    sim = ctx.sim()
-    ctx.consistency_match(w_pct_a)
-    if not folded:
-        ctx.fold_end()
-    ctx.consistency_bp(w_pct_s)
-    return sim
+        ctx.consistency_bp(w_pct_s)
+    except Exception:
+        if folding:  # the folding kernels still own their workspaces: wait for them, so that the context can be used again
+            try:
+                ctx.fold_end()
+            except Exception:
+                pass
+        raise
+    return [sim] if first is not None and len(first) <= 2 else sim
+
+
+def forest_ready(trees, pending, done):
+    """The nodes of `pending` ((family, node) in scheduling order) whose two children are in `done`, in that order.
+    trees[f] = (left, right) of family f's guide tree (leaves -1)."""
+    return [(f, i) for f, i in pending if (f, trees[f][0][i]) in done and (f, trees[f][1][i]) in done]
 
 
 def _phase2(ctx, own, names, seqs, n, sim, score, left, right, t, w, eta0, t_max, th_a, th_s, th_s1, force_iters, level_sync, slice_iters,
             skip_uncoupled_folds, round_us=None, bp_update=False, bp_update1=False):
+    fam = dict(names=names, seqs=seqs, first=0, sim=sim, tree=(score, left, right))
+    return _phase2_forest(ctx, own, [fam], t, w, eta0, t_max, th_a, th_s, th_s1, force_iters, level_sync, slice_iters,
+                          skip_uncoupled_folds, round_us, bp_update, bp_update1)[0]
+
+
+def _phase2_forest(ctx, own, fams, t, w, eta0, t_max, th_a, th_s, th_s1, force_iters, level_sync, slice_iters,
+                   skip_uncoupled_folds, round_us=None, bp_update=False, bp_update1=False):
+    """The progressive phase and the output of every family of the context at once.  fams: per family a dict with names,
+    seqs, first (index of its first sequence in the context), sim and tree = (score, left, right).  The guide trees form one
+    forest: a node is ready when both of its children are done, whatever its family, and the ready nodes of all families
+    share each launch.  Returns one Result per family."""
     import time
-    res = Result()
-    res.sim = sim
-    res.tree = (score, left, right)
-    res.tree_line = tree_string(score, left, right, names)
+    nf = len(fams)
+    results = []
+    trees = []
+    aln = {}  # (family, node) -> (global sequence indices, mask)
+    pending = []
+    for f, fm in enumerate(fams):
+        score, left, right = fm["tree"]
+        n = len(fm["seqs"])
+        res = Result()
+        res.sim = fm["sim"]
+        res.tree = (score, left, right)
+        res.tree_line = tree_string(score, left, right, fm["names"])
+        res.dd_log = {}
+        res.dd_dims = {}  # node -> (columns of the left, of the right alignment); resident-node mode only
+        res.levels = 0
+        res.rounds = []  # resident-node mode: (seconds, [(node, columns left, columns right), ...]) per round (diagnostics)
+        results.append(res)
+        trees.append((left, right))
+        for i in range(n):
+            aln[(f, i)] = (np.array([fm["first"] + i], np.uint32), np.ones((1, len(fm["seqs"][i])), np.uint8))
+        pending += [(f, i) for i in range(n, 2 * n - 1)]
+    done = set(aln)
+
+    def key(f, i):  # node names in the diagnostics: the plain node index for one family
+        return i if nf == 1 else (f, i)
+
+    def finish(f, i, o, dims=None):
+        left, right = trees[f]
+        aln[(f, i)] = project_alignment(aln[(f, left[i])], aln[(f, right[i])], o["z"])
+        done.add((f, i))
+        results[f].dd_log[i] = (o["iterations"], o["violated"], o["ncbp"], o["score"])
+        if dims is not None:
+            results[f].dd_dims[i] = dims
+        del aln[(f, left[i])], aln[(f, right[i])]
+
     # progressive phase.  level_sync: solve every node whose children are ready, level by level (one blocking
     # call per level).  Otherwise the nodes stay resident on the device and every round advances all open
     # nodes by at most `slice_iters` iterations in one launch: a node that needs 600 iterations no longer
     # holds back the parents of its level-mates.  Same results either way.
-    lens = [len(s) for s in seqs]
-    aln = {i: (np.array([i], np.uint32), np.ones((1, lens[i]), np.uint8)) for i in range(n)}
-    pending = [i for i in range(n, 2 * n - 1)]
     # only the alignment z of a node is consumed here (DAFS::align_alignments, dafs.cpp:896-912), so nodes that have no
     # consensus base pair to couple their subproblems need not run their two folding DPs (dafs_dd_params doc)
     prm = capi.dd_params(w=w, eta0=eta0, th_a=th_a, th_s=th_s, t_max=t_max, force_iters=force_iters,
                          skip_uncoupled_folds=1 if skip_uncoupled_folds else 0)
     trace = os.environ.get("DAFS_PIPELINE_TRACE") == "1"  # node shapes on stderr as they are opened (diagnostics)
-    res.dd_log = {}
-    res.dd_dims = {}  # node -> (columns of the left, of the right alignment); resident-node mode only
-    res.levels = 0
-    res.rounds = []  # resident-node mode: (seconds, [(node, columns left, columns right), ...]) per round (diagnostics)
+    levels = 0
+    rounds = []
     if level_sync:
         while pending:
-            ready = [i for i in pending if left[i] in aln and right[i] in aln]
-            outs = ctx.solve_nodes([(aln[left[i]][0], aln[left[i]][1], aln[right[i]][0], aln[right[i]][1]) for i in ready], prm)
-            for i, o in zip(ready, outs):
-                aln[i] = project_alignment(aln[left[i]], aln[right[i]], o["z"])
-                res.dd_log[i] = (o["iterations"], o["violated"], o["ncbp"], o["score"])
-                del aln[left[i]], aln[right[i]]
-            pending = [i for i in pending if i not in ready]
-            res.levels += 1
+            ready = forest_ready(trees, pending, done)
+            outs = ctx.solve_nodes([(aln[(f, trees[f][0][i])][0], aln[(f, trees[f][0][i])][1],
+                                     aln[(f, trees[f][1][i])][0], aln[(f, trees[f][1][i])][1]) for f, i in ready], prm)
+            for (f, i), o in zip(ready, outs):
+                finish(f, i, o)
+            rs = set(ready)
+            pending = [q for q in pending if q not in rs]
+            levels += 1
     else:
         # A round = one call: the open nodes advance while the nodes whose children finished in the last round are set up
         # and started beside them (Context.nodes_round).  A round ends after `round_us` microseconds (all its nodes stop at
@@ -190,17 +247,21 @@ def _phase2(ctx, own, names, seqs, n, sim, score, left, right, t, w, eta0, t_max
         # loop in many ways: the results do not depend on it).
         if slice_iters is None and round_us is None:
             round_us = int(os.environ.get("DAFS_ROUND_US", "2500"))
-        open_nodes = {}  # node -> (handle, len1, len2)
+        open_nodes = {}  # (family, node) -> (handle, len1, len2)
         while pending or open_nodes:
-            ready = [i for i in pending if left[i] in aln and right[i] in aln]
+            ready = forest_ready(trees, pending, done)
             if ready and trace:
-                print("open", [(i, aln[left[i]][1].shape, aln[right[i]][1].shape) for i in ready], file=sys.stderr, flush=True)
-            pending = [i for i in pending if i not in ready]
+                print("open", [(key(f, i), aln[(f, trees[f][0][i])][1].shape, aln[(f, trees[f][1][i])][1].shape) for f, i in ready],
+                      file=sys.stderr, flush=True)
+            rs = set(ready)
+            pending = [q for q in pending if q not in rs]
             ids = sorted(open_nodes)
             t_round = time.perf_counter()
-            def node_input(i):
-                a1, a2 = aln[left[i]], aln[right[i]]
-                if bp_update and i == 2 * n - 2:
+
+            def node_input(f, i):
+                left, right = trees[f]
+                a1, a2 = aln[(f, left[i])], aln[(f, right[i])]
+                if bp_update and i == 2 * len(fams[f]["seqs"]) - 2:
                     # --bp-update: the top call of the recursion (DAFS::align(ss, aln, root), dafs.cpp:1518-1537) re-estimates
                     # both base-pairing matrices under the structure decoded from their averages (:919-934)
                     upd = []
@@ -209,49 +270,145 @@ def _phase2(ctx, own, names, seqs, n, sim, score, left, right, t, w, eta0, t_max
                         upd.append(ctx.update_basepairing(s_idx, msk, ss0))
                     return (a1[0], a1[1], a2[0], a2[1], upd[0], upd[1])
                 return (a1[0], a1[1], a2[0], a2[1])
-            hs, dims, fin_old, fin_new = ctx.nodes_round([node_input(i) for i in ready],
-                                                         [open_nodes[i][0] for i in ids], prm, slice_iters or 0, round_us or 0)
-            for i, h, d in zip(ready, hs, dims):
-                open_nodes[i] = (h, d[0], d[1])
-            res.rounds.append((time.perf_counter() - t_round, [(i, open_nodes[i][1], open_nodes[i][2]) for i in ids + ready]))
-            for i, f in list(zip(ids, fin_old)) + list(zip(ready, fin_new)):
-                if not f:
+            hs, dims, fin_old, fin_new = ctx.nodes_round([node_input(f, i) for f, i in ready],
+                                                         [open_nodes[q][0] for q in ids], prm, slice_iters or 0, round_us or 0)
+            for q, h, d in zip(ready, hs, dims):
+                open_nodes[q] = (h, d[0], d[1])
+            rounds.append((time.perf_counter() - t_round, [(key(*q), open_nodes[q][1], open_nodes[q][2]) for q in ids + ready]))
+            for q, fin in list(zip(ids, fin_old)) + list(zip(ready, fin_new)):
+                if not fin:
                     continue
-                h, l1, l2 = open_nodes.pop(i)
-                o = ctx.nodes_result(h, l1, l2)
-                aln[i] = project_alignment(aln[left[i]], aln[right[i]], o["z"])
-                res.dd_log[i] = (o["iterations"], o["violated"], o["ncbp"], o["score"])
-                res.dd_dims[i] = (l1, l2)
-                del aln[left[i]], aln[right[i]]
-            res.levels += 1
-        res.dd_memory = ctx.nodes_memory()  # (reserved, in use, peak) bytes of the resident nodes
-        res.dd_demotions = ctx.nodes_demotions()  # split nodes that lost their folders (0 on an undisturbed device)
-        res.skip_uncoupled_folds = bool(skip_uncoupled_folds)  # nodes without consensus pairs then carry no folding arrays
+                h, l1, l2 = open_nodes.pop(q)
+                finish(q[0], q[1], ctx.nodes_result(h, l1, l2), (l1, l2))
+            levels += 1
+        dd_memory = ctx.nodes_memory()  # (reserved, in use, peak) bytes of the resident nodes
+        dd_demotions = ctx.nodes_demotions()  # split nodes that lost their folders (0 on an undisturbed device)
+        for res in results:
+            res.dd_memory = dd_memory
+            res.dd_demotions = dd_demotions
+            res.skip_uncoupled_folds = bool(skip_uncoupled_folds)  # nodes without consensus pairs then carry no folding arrays
         ctx.nodes_close()
-    root = 2 * n - 2
-    sidx, mask = aln[root]
     t.append(time.perf_counter())
     th1 = th_s if th_s1 is None else th_s1
-    _, ss, _ = ctx.consensus_structure(sidx, mask, th1)
-    if bp_update1:  # :1863-1869: decode, re-estimate under that structure, decode again
-        _, ss = ctx.nussinov(ctx.update_basepairing(sidx, mask, ss), None, th1)
-    res.ss = ss
-    res.ss_str = capi.make_brackets(ss)
-    order = np.argsort(sidx, kind="stable")  # std::sort(aln) :1876
-    lines = [res.tree_line, ">SS_cons", res.ss_str]
-    res.rows = []
-    for r in order:
-        row_bytes = np.full(mask.shape[1], ord("-"), np.uint8)
-        row_bytes[mask[r].astype(bool)] = np.frombuffer(seqs[sidx[r]].encode("latin-1"), np.uint8)  # residues into their columns
-        row = row_bytes.tobytes().decode("latin-1")
-        res.rows.append(row)
-        lines += ["> " + names[sidx[r]], row]
-    res.output = "\n".join(lines) + "\n"
+    for f, (fm, res) in enumerate(zip(fams, results)):
+        res.levels = levels
+        res.rounds = rounds
+        n = len(fm["seqs"])
+        sidx, mask = aln[(f, 2 * n - 2)]
+        _, ss, _ = ctx.consensus_structure(sidx, mask, th1)
+        if bp_update1:  # :1863-1869: decode, re-estimate under that structure, decode again
+            _, ss = ctx.nussinov(ctx.update_basepairing(sidx, mask, ss), None, th1)
+        res.ss = ss
+        res.ss_str = capi.make_brackets(ss)
+        order = np.argsort(sidx, kind="stable")  # std::sort(aln) :1876
+        lines = [res.tree_line, ">SS_cons", res.ss_str]
+        res.rows = []
+        for r in order:
+            row_bytes = np.full(mask.shape[1], ord("-"), np.uint8)
+            local = int(sidx[r]) - fm["first"]
+            row_bytes[mask[r].astype(bool)] = np.frombuffer(fm["seqs"][local].encode("latin-1"), np.uint8)  # residues into their columns
+            row = row_bytes.tobytes().decode("latin-1")
+            res.rows.append(row)
+            lines += ["> " + fm["names"][local], row]
+        res.output = "\n".join(lines) + "\n"
     t.append(time.perf_counter())
     # fold_launch: the folding is only started there; its kernels overlap `pair` and the first half of `pct_fold_tree`,
     # which also holds the wait for them
-    res.seconds = dict(fold_launch=t[1] - t[0], pair=t[2] - t[1], pct_fold_tree=t[3] - t[2], progressive=t[4] - t[3], final=t[5] - t[4],
-                       total=t[5] - t[0])
+    seconds = dict(fold_launch=t[1] - t[0], pair=t[2] - t[1], pct_fold_tree=t[3] - t[2], progressive=t[4] - t[3], final=t[5] - t[4],
+                   total=t[5] - t[0])
+    for res in results:
+        res.seconds = seconds
     if own:
         ctx.close()
-    return res
+    return results
+
+
+def family_bytes(lens):
+    """Device memory one family takes in phase 1, estimated from the stores' sizes (bytes): per pair its row pointers in
+    both matching stores, its entries (as the pair kernels reserve them: 24 per shorter-sequence column and direction, col
+    + val, the relaxed copy and the interleaved copy of the transforms) and its dense consistency tile; per sequence its
+    base-pairing tile and rows; the similarity block.  Not counted: the folding kernels' workspaces and the resident
+    nodes of the progressive phase, which hold only the open nodes (tools/time_batch.py reports their measured peak)."""
+    lens = [int(x) for x in lens]
+    n = len(lens)
+    b = 4 * n * n
+    for x in range(n):
+        b += 8 * lens[x] * lens[x] + 64 * lens[x] + 4096
+        for y in range(x + 1, n):
+            b += 8 * (lens[x] + lens[y] + 2) + 2 * min(lens[x], lens[y]) * 24 * 32 + 4 * lens[x] * lens[y]
+    return b
+
+
+def pack_families(sizes, max_bytes):
+    """Sub-batches of the families (greedy, in input order) whose estimated sizes add up to at most max_bytes each; a
+    family over the budget runs alone.  Returns lists of family indices."""
+    out, cur, used = [], [], 0
+    for k, b in enumerate(sizes):
+        if cur and used + b > max_bytes:
+            out.append(cur)
+            cur, used = [], 0
+        cur.append(k)
+        used += b
+    if cur:
+        out.append(cur)
+    return out
+
+
+# per sub-batch, against the 288 GB of an MI355X.  A choice, not a measured limit.  Measured on 512 families of 5-15
+# sequences of 80-200 nt (profiles/r04_a_time_batch.json): phase-1 estimate 8.6 GB (one sub-batch), peak of the
+# progressive phase's resident nodes 6.0 GB, which family_bytes does not count.
+DEFAULT_BATCH_BYTES = 16 << 30
+
+
+def run_batch(families, ctx=None, max_bytes=None, **kw):
+    """Align many independent families in one context, sharing every device launch between them.  families: a list of
+    (names, seqs).  kw: the options of run() except mp / bp / shard.  Returns one Result per family, in input order, each
+    with the .output, .dd_log and .sim a separate run() of that family gives.  The families are packed greedily, in input
+    order, into sub-batches under max_bytes of estimated device memory (family_bytes; default DEFAULT_BATCH_BYTES); phase 1
+    runs once per sub-batch over the whole sub-batch, the guide trees are built per family and the progressive phase walks
+    their forest."""
+    import time
+    for k in ("mp", "bp", "shard"):
+        if k in kw:
+            raise ValueError("pipeline.run_batch: %s is a single-family option (use run)" % k)
+    if kw.get("level_sync") and kw.get("bp_update"):
+        raise ValueError("pipeline.run_batch: bp_update needs the resident-node schedule (level_sync=False)")
+    opts = dict(w=4.0, eta0=0.5, t_max=600, w_pct_a=0.25, w_pct_s=0.25, th_a=0.01, th_s=0.2, th_s1=None, align_model=capi.ALIGN_PROBCONS,
+                force_iters=0, timers=None, level_sync=False, slice_iters=None, skip_uncoupled_folds=True, round_us=None, w_pct_f=0.0,
+                bp_update=False, bp_update1=False)
+    unknown = set(kw) - set(opts)
+    if unknown:
+        raise TypeError("pipeline.run_batch: unknown options %s" % sorted(unknown))
+    opts.update(kw)
+    families = [(list(nm), list(sq)) for nm, sq in families]
+    for nm, sq in families:
+        if not sq or len(nm) != len(sq):
+            raise ValueError("pipeline.run_batch: every family needs at least one sequence and one name per sequence")
+    budget = DEFAULT_BATCH_BYTES if max_bytes is None else int(max_bytes)
+    groups = pack_families([family_bytes([len(s) for s in sq]) for _, sq in families], budget)
+    own = ctx is None
+    if own:
+        ctx = capi.Context(0)
+    out = [None] * len(families)
+    try:
+        for grp in groups:
+            t = [time.perf_counter()]
+            seqs, first = [], [0]
+            for k in grp:
+                seqs += families[k][1]
+                first.append(len(seqs))
+            sims = _phase1_local(ctx, seqs, None, None, opts["align_model"], opts["th_a"], opts["w_pct_a"], opts["w_pct_s"], t,
+                                 opts["w_pct_f"], first)
+            fams = []
+            for j, k in enumerate(grp):
+                fams.append(dict(names=families[k][0], seqs=families[k][1], first=first[j], sim=sims[j], tree=capi.build_tree(sims[j])))
+            t.append(time.perf_counter())
+            res = _phase2_forest(ctx, False, fams, t, opts["w"], opts["eta0"], opts["t_max"], opts["th_a"], opts["th_s"], opts["th_s1"],
+                                 opts["force_iters"], opts["level_sync"], opts["slice_iters"], opts["skip_uncoupled_folds"], opts["round_us"],
+                                 opts["bp_update"], opts["bp_update1"])
+            for k, r in zip(grp, res):
+                out[k] = r
+    finally:
+        if own:
+            ctx.close()
+    return out

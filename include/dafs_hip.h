@@ -161,6 +161,15 @@ int dafs_hip_create(int device, dafs_hip_ctx** ctx);
 void dafs_hip_destroy(dafs_hip_ctx* ctx);
 
 int dafs_hip_set_sequences(dafs_hip_ctx* ctx, uint32_t nseq, const char* const* seqs, const uint32_t* lens);
+/* Family partition (many independent alignments in one context): family f holds the sequences first[f] .. first[f+1]-1;
+ * first[0] = 0, first[nfam] = nseq, strictly increasing (families of one sequence are allowed).  Every stage then works
+ * within each family and batches across them: only pairs within a family exist, numbered family by family and row-major
+ * inside each (the pair order of dafs_hip_align_posteriors' [pair_begin, pair_end), of the fetches and of the stores); the
+ * similarity scores are one n_f x n_f block per family (dafs_hip_get_sim); the consistency transforms sum over the output
+ * pair's family with its size in the weights; a progressive node whose rows span two families is refused (EINVAL).
+ * Call after dafs_hip_set_sequences (which sets one family of all sequences); it invalidates the stores.
+ * dafs_hip_set_mp, dafs_hip_mp_install, dafs_hip_mp_install_dev and dafs_hip_phase1_sharded need a single family. */
+int dafs_hip_set_families(dafs_hip_ctx* ctx, uint32_t nfam, const uint32_t* first);
 int dafs_hip_align_posteriors(dafs_hip_ctx* ctx, int model, float th, uint64_t pair_begin, uint64_t pair_end);
 /* sizes of the result held in the context */
 int dafs_hip_align_result_size(dafs_hip_ctx* ctx, uint64_t* npairs, uint64_t* total_nnz, uint64_t* total_rowptr);
@@ -187,7 +196,8 @@ int dafs_hip_set_mp(dafs_hip_ctx* ctx, const uint32_t* nnz, const uint32_t* rowp
  * computed them; relaxed = 1: the consistency transform's result, on top of an un-relaxed store (sim may be NULL). */
 int dafs_hip_mp_install(dafs_hip_ctx* ctx, int relaxed, const uint32_t* nnz, const uint32_t* rowptr, const uint32_t* col,
                         const float* val, const float* sim);
-/* sim_ (src/dafs.cpp:1813-1819): N*N floats, unit diagonal; needs a full-pair-set align_posteriors, dafs_hip_set_mp or dafs_hip_mp_install. */
+/* sim_ (src/dafs.cpp:1813-1819): N*N floats, unit diagonal -- with families, the n_f*n_f blocks one after another; needs a
+ * full-pair-set align_posteriors, dafs_hip_set_mp or dafs_hip_mp_install. */
 int dafs_hip_get_sim(dafs_hip_ctx* ctx, float* sim);
 
 /* ------------------------------------------------------------------------------------------
