@@ -144,6 +144,8 @@ _mp_export_dev = _sig("dafs_hip_mp_export_dev", C.c_int, [C.c_void_p, C.c_int, C
 _mp_install_dev = _sig("dafs_hip_mp_install_dev", C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_uint64])
 _bp_export_dev = _sig("dafs_hip_bp_export_dev", C.c_int, [C.c_void_p] + [C.c_void_p] * 3 + [C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)])
 _set_bp_dev = _sig("dafs_hip_set_bp_dev", C.c_int, [C.c_void_p, C.c_uint32] + [C.c_void_p] * 4 + [C.c_uint64])
+_alignment_reliability = _sig("dafs_hip_alignment_reliability", C.c_int,
+                              [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5)
 
 
 class StageTime(C.Structure):
@@ -548,6 +550,25 @@ class Context:
         check(_consensus_structure(self._h, n, L, seq.ctypes.data, mask.ctypes.data, th, ss.ctypes.data, C.byref(score),
                                    None if p is None else p.ctypes.data))
         return np.float32(score.value), ss, p
+
+    def alignment_reliability(self, seq, mask, ss=None, mp_relaxed=None, bp_relaxed=None):
+        """Reliability of the alignment (seq, mask) from the context's stores (dafs_hip_alignment_reliability).  ss: the
+        consensus structure (left column -> right column, NONE otherwise) or None.  mp_relaxed / bp_relaxed: 0, 1, or None
+        for the store the progressive phase reads.  Returns a dict of numpy arrays: residue (float64, the rows' residues
+        one row after another in the given order), col (per column), pair and pair_rows (at the left column of each pair),
+        and expected_accuracy (a float)."""
+        seq = np.ascontiguousarray(seq, np.uint32); mask = np.ascontiguousarray(mask, np.uint8)
+        n, L = mask.shape
+        ss = None if ss is None else np.ascontiguousarray(ss, np.uint32)
+        if ss is not None and ss.shape != (L,):
+            raise ValueError("alignment_reliability: ss needs one entry per column")
+        res = np.zeros(int(mask.astype(bool).sum()), np.float64)
+        col = np.zeros(L, np.float64); pair = np.zeros(L, np.float64); rows = np.zeros(L, np.uint32)
+        ea = C.c_double()
+        check(_alignment_reliability(self._h, n, L, seq.ctypes.data, mask.ctypes.data, None if ss is None else ss.ctypes.data,
+                                     -1 if mp_relaxed is None else int(mp_relaxed), -1 if bp_relaxed is None else int(bp_relaxed),
+                                     res.ctypes.data, col.ctypes.data, pair.ctypes.data, rows.ctypes.data, C.byref(ea)))
+        return dict(residue=res, col=col, pair=pair, pair_rows=rows, expected_accuracy=ea.value)
 
 
 def build_tree(sim):

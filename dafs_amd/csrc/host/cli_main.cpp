@@ -22,6 +22,8 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <cctype>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -69,6 +71,7 @@ struct Options {
   bool no_alifold = false, ipknot = false, bp_update = false, bp_update1 = false;
   int device = 0;
   std::vector<int> devices;  // --devices: one process per entry for phase 1
+  std::string stockholm;  // --stockholm FILE
   std::string input;
   std::vector<std::string> inputs;  // every FILE argument; with two or more, one output block per file
 };
@@ -89,6 +92,8 @@ const char* kHelp =
     "      --device N        HIP device index (default: 0)\n"
     "      --devices A,B,... One process per listed HIP device for the posteriors and the consistency transform\n"
     "                        (shards exchanged over RCCL); the progressive alignment runs on the first\n"
+    "      --stockholm FILE  Also write every printed alignment to FILE in Stockholm format, one block per input\n"
+    "                        file, with per-residue (#=GR PP) and per-column (#=GC PP_cons) reliabilities\n"
     "\n Aligning options:\n"
     "  -a, --align-model arg Alignment model (value=CONTRAlign, ProbCons) (default: ProbCons)\n"
     "  -p, --align-pct arg   Weight of PCT for matching probabilities (default: 0.25)\n"
@@ -127,7 +132,8 @@ Options parse(int argc, char** argv) {
       {"fold-decoder", {0, true}}, {"fold-pct", {'q', true}}, {"fold-th", {'t', true}}, {"gamma", {'g', true}},
       {"no-alifold", {0, false}}, {"fold-th1", {'T', true}}, {"gamma1", {'G', true}}, {"ipknot", {0, false}},
       {"bp-update", {0, false}}, {"bp-update1", {0, false}}, {"fold-aux", {0, true}}, {"save-align-aux", {0, true}},
-      {"save-fold-aux", {0, true}}, {"device", {0, true}}, {"devices", {0, true}}, {"input", {0, true}}};
+      {"save-fold-aux", {0, true}}, {"device", {0, true}}, {"devices", {0, true}}, {"input", {0, true}},
+      {"stockholm", {0, true}}};
   std::map<char, std::string> shorts;
   for (const auto& kv : spec)
     if (kv.second.first) shorts[kv.second.first] = kv.first;
@@ -187,6 +193,10 @@ Options parse(int argc, char** argv) {
       if (o.devices.empty()) throw std::string("--devices needs at least one device index");
     }
     else if (name == "input") { o.input = value; o.inputs.push_back(value); }
+    else if (name == "stockholm") {
+      if (value.empty()) throw std::string("--stockholm needs a file name");
+      o.stockholm = value;
+    }
   }
   if (o.inputs.size() > 1) {
     if (!o.align_aux.empty() || !o.fold_aux.empty() || !o.save_align_aux.empty() || !o.save_fold_aux.empty())
@@ -454,6 +464,66 @@ void save_align_aux(dafs_hip_ctx* ctx, const std::string& file, const std::vecto
 }
 
 // ---------------------------------------------------------------------------------------------
+// --stockholm: every printed alignment as a Stockholm block with posterior-probability lines (dafs_hip_alignment_reliability).
+// dafs_amd/stockholm.py is the Python twin; both write the same bytes.
+
+// Infernal's PP character: '*' for p >= 0.95, else the digit floor(p * 10 + 0.5), in double
+char pp_char(double p) {
+  if (p >= 0.95) return '*';
+  return (char)('0' + (int)std::floor(p * 10.0 + 0.5));
+}
+
+// per sequence of a file, in input order: the first whitespace-separated word of its header, "seq<k>" (k 1-based) for an
+// empty one, ".2", ".3", ... appended to the second, third, ... occurrence of a name
+std::vector<std::string> stockholm_names(const std::vector<Fasta>& ff) {
+  std::vector<std::string> out;
+  std::map<std::string, int> seen;
+  for (size_t k = 0; k < ff.size(); ++k) {
+    const std::string& h = ff[k].name();
+    size_t b = 0;
+    while (b < h.size() && std::isspace((unsigned char)h[b])) ++b;
+    size_t e = b;
+    while (e < h.size() && !std::isspace((unsigned char)h[e])) ++e;
+    const std::string nm = e > b ? h.substr(b, e - b) : "seq" + std::to_string(k + 1);
+    const int c = ++seen[nm];
+    out.push_back(c == 1 ? nm : nm + "." + std::to_string(c));
+  }
+  return out;
+}
+
+// rows in stdout order: name, printed text and the reliabilities of its residues; col_rel per column ('.' where a column
+// holds no residue).  Labels padded to the longest plus one.
+std::string stockholm_block(const std::string& tree_line, const std::vector<std::string>& names, const std::vector<std::string>& rows,
+                            const std::vector<const double*>& rel, const std::vector<double>& col_rel, const std::string& ss) {
+  size_t width = std::max(std::string("#=GC SS_cons").size(), std::string("#=GC PP_cons").size());
+  for (const std::string& nm : names) width = std::max(width, nm.size() + 8);  // "#=GR " + name + " PP"
+  ++width;
+  auto label = [&](const std::string& l) { return l + std::string(width - l.size(), ' '); };
+  std::string out = "# STOCKHOLM 1.0\n#=GF CC " + tree_line + "\n";
+  for (size_t r = 0; r < rows.size(); ++r) {
+    out += label(names[r]) + rows[r] + "\n";
+    std::string pp(rows[r].size(), '.');
+    for (size_t c = 0, k = 0; c < rows[r].size(); ++c)
+      if (rows[r][c] != '-') pp[c] = pp_char(rel[r][k++]);
+    out += label("#=GR " + names[r] + " PP") + pp + "\n";
+  }
+  std::string cons(col_rel.size(), '.');
+  for (size_t c = 0; c < col_rel.size(); ++c)
+    for (const std::string& row : rows)
+      if (row[c] != '-') { cons[c] = pp_char(col_rel[c]); break; }
+  out += label("#=GC SS_cons") + ss + "\n" + label("#=GC PP_cons") + cons + "\n//\n";
+  return out;
+}
+
+void write_stockholm(const std::string& file, const std::vector<std::string>& blocks) {
+  std::ofstream os(file.c_str(), std::ios::binary);
+  if (!os.is_open()) throw "--stockholm: cannot open " + file;
+  for (const std::string& b : blocks) os << b;
+  os.flush();
+  if (!os) throw "--stockholm: cannot write " + file;
+}
+
+// ---------------------------------------------------------------------------------------------
 // --devices: the ranks of phase 1, one process per listed GPU.  The processes are forked before the first GPU call of
 // the program (a process that has initialised the GPU must neither fork nor exec); rank 0 is the original process and
 // the only one that goes on after phase 1.  What the ranks share is one anonymous mapping made before the fork.
@@ -608,7 +678,7 @@ int rank_allgather(void* user, const void* send, void* recv, size_t bytes, void*
 }
 
 int align_group(dafs_hip_ctx* ctx, const Options& o, Ranks& rk, int align_model, const std::vector<std::vector<Fasta> >& fams,
-                const std::vector<size_t>& members, const std::vector<std::ostream*>& out);
+                const std::vector<size_t>& members, const std::vector<std::ostream*>& out, const std::vector<std::string*>& sto);
 
 // rand() as a process that has not called it yet sees it: glibc's default generator is the one initstate(1, state, 128)
 // sets up, and rand() returns random()
@@ -669,7 +739,19 @@ int run(const Options& o, Ranks& rk) {
   check(dafs_hip_create(o.devices.empty() ? o.device : o.devices[rk.rank], &ctx));
   struct Guard { dafs_hip_ctx* c; ~Guard() { dafs_hip_destroy(c); } } guard{ctx};
 
-  if (!multi) return align_group(ctx, o, rk, align_model, fams, {0}, {&std::cout});
+  // --stockholm: one block per input file, in input order, written by the process that prints
+  std::vector<std::string> sto_blocks(o.stockholm.empty() ? 0 : o.inputs.size());
+  auto sto_of = [&](const std::vector<size_t>& members) {
+    std::vector<std::string*> v;
+    if (!sto_blocks.empty())
+      for (size_t f : members) v.push_back(&sto_blocks[f]);
+    return v;
+  };
+  if (!multi) {
+    align_group(ctx, o, rk, align_model, fams, {0}, {&std::cout}, sto_of({0}));
+    if (rk.rank == 0 && !o.stockholm.empty()) write_stockholm(o.stockholm, sto_blocks);
+    return 0;
+  }
   // Several files: every file with two or more sequences in one batch (dafs_hip_set_families: shared launches, one guide
   // tree per family, the forest walked together); a file of one sequence takes the single-sequence path of a run of its
   // own (no pairs, no consistency transforms) on the same context.  Each block is what `dafs FILE` prints.
@@ -686,7 +768,7 @@ int run(const Options& o, Ranks& rk) {
     std::vector<std::ostream*> os;
     for (size_t f : members) os.push_back(&outs[f]);
     try {
-      align_group(ctx, o, rk, align_model, fams, members, os);
+      align_group(ctx, o, rk, align_model, fams, members, os, sto_of(members));
     } catch (const char* str) {
       throw names(members) + ": " + str;
     } catch (const std::string& str) {
@@ -698,14 +780,16 @@ int run(const Options& o, Ranks& rk) {
     if (fams[f].size() == 1) group({f});
   for (size_t f = 0; f < fams.size(); ++f) std::cout << "==> " << o.inputs[f] << " <==" << std::endl << outs[f].str();
   std::cout.flush();
+  if (!o.stockholm.empty()) write_stockholm(o.stockholm, sto_blocks);
   return 0;
 }
 
 // The run of one or more families (members: indices into fams) on the context: phase 1 once over all of them, one guide
 // tree per family, the progressive phase over the forest (the ready nodes of every family share each round), then per
-// family the refinement, the common structure and the output on *out[k].
+// family the refinement, the common structure and the output on *out[k]; with --stockholm (sto not empty) also the
+// family's Stockholm block in *sto[k].
 int align_group(dafs_hip_ctx* ctx, const Options& o, Ranks& rk, int align_model, const std::vector<std::vector<Fasta> >& fams,
-                const std::vector<size_t>& members, const std::vector<std::ostream*>& out) {
+                const std::vector<size_t>& members, const std::vector<std::ostream*>& out, const std::vector<std::string*>& sto) {
   const uint F = (uint)members.size();
   std::vector<Fasta> fa;         // every sequence of the group, family after family
   std::vector<uint32_t> first(1, 0);
@@ -914,6 +998,8 @@ int align_group(dafs_hip_ctx* ctx, const Options& o, Ranks& rk, int align_model,
 
     // common secondary structure of the final alignment (:1857-1871; no RNAalifold term here)
     std::string str;
+    std::vector<double> rel, col_rel;   // --stockholm: the reliabilities of this alignment and structure
+    std::map<uint32_t, size_t> rel_at;  // sequence -> its first residue in rel
     {
       std::vector<uint32_t> rs;
       std::vector<uint8_t> rm;
@@ -929,17 +1015,42 @@ int align_group(dafs_hip_ctx* ctx, const Options& o, Ranks& rk, int align_model,
       std::vector<char> buf(L + 1);
       dafs_hip_make_brackets(L, ss.data(), buf.data());
       str.assign(buf.data());
+      if (!sto.empty()) {  // from the stores the progressive phase read (with --bp-update1 too: ss is the re-decoded one)
+        size_t tot = 0;
+        for (uint32_t s0 : rs) { rel_at[s0] = tot; tot += fa[s0].size(); }
+        rel.resize(tot);
+        col_rel.resize(L);
+        check(dafs_hip_alignment_reliability(ctx, (uint32_t)root.size(), L, rs.data(), rm.data(), ss.data(), -1, -1, rel.data(), col_rel.data(),
+                                             nullptr, nullptr, nullptr));
+      }
     }
 
     // output (:1876-1879, :1584-1601)
     std::sort(root.begin(), root.end());
     std::ostream& os = *out[f];
     os << ">SS_cons" << std::endl << str << std::endl;
+    std::vector<std::string> rows;
     for (const auto& row : root) {
       const std::string& sq = fa[row.first].seq();
       os << "> " << fa[row.first].name() << std::endl;
-      for (uint j = 0, k = 0; j != row.second.size(); ++j) os << (row.second[j] ? sq[k++] : '-');
-      os << std::endl;
+      std::string text(row.second.size(), '-');
+      for (uint j = 0, k = 0; j != row.second.size(); ++j)
+        if (row.second[j]) text[j] = sq[k++];
+      os << text << std::endl;
+      rows.push_back(text);
+    }
+    if (!sto.empty()) {
+      const std::vector<Fasta>& ff = fams[members[f]];
+      const std::vector<std::string> all_names = stockholm_names(ff);
+      std::vector<std::string> names;
+      std::vector<const double*> rr;
+      for (const auto& row : root) {
+        names.push_back(all_names[row.first - first[f]]);
+        rr.push_back(rel.data() + rel_at[row.first]);
+      }
+      std::ostringstream tl;
+      print_tree(tl, trees[f], ff, (int)trees[f].size() - 1);
+      *sto[f] = stockholm_block(tl.str(), names, rows, rr, col_rel, str);
     }
   }
   return 0;

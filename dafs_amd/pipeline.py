@@ -9,7 +9,7 @@ import sys
 
 import numpy as np
 
-from . import capi
+from . import capi, stockholm
 
 NONE = 0xFFFFFFFF
 
@@ -88,12 +88,14 @@ class Result:
 
 def run(names, seqs, ctx=None, bp=None, w=4.0, eta0=0.5, t_max=600, w_pct_a=0.25, w_pct_s=0.25, th_a=0.01,
         th_s=0.2, th_s1=None, align_model=capi.ALIGN_PROBCONS, force_iters=0, timers=None, level_sync=False, slice_iters=None,
-        mp=None, skip_uncoupled_folds=True, shard=None, round_us=None, w_pct_f=0.0, bp_update=False, bp_update1=False):
+        mp=None, skip_uncoupled_folds=True, shard=None, round_us=None, w_pct_f=0.0, bp_update=False, bp_update1=False,
+        reliability=False):
     """The whole run.  bp: per-sequence (rowptr, col, val) base-pairing rows (--fold-aux); None
     computes them with the device fold model.  mp: supplied matching probabilities (--align-aux), see Context.set_mp.
     shard: (torch.distributed module, torch device) of an initialised process group -- phase 1 (folds, pair posteriors,
     matching consistency transform) is then split over the ranks and gathered (dist.phase1_sharded); every rank
-    finishes the run and holds the same result."""
+    finishes the run and holds the same result.  reliability: the result also gets .reliability and .stockholm (see
+    _phase2_forest)."""
     import time
     # combinations this driver does not implement are refused, not ignored (the command line, cli_main.cpp, covers
     # --bp-update with level batches through its own solve_batch)
@@ -117,7 +119,7 @@ def run(names, seqs, ctx=None, bp=None, w=4.0, eta0=0.5, t_max=600, w_pct_a=0.25
     score, left, right = capi.build_tree(sim)  # same code as the command line (build_tree below is its Python twin, kept for the CPU tests)
     t.append(time.perf_counter())
     return _phase2(ctx, own, names, seqs, n, sim, score, left, right, t, w, eta0, t_max, th_a, th_s, th_s1, force_iters, level_sync, slice_iters,
-                   skip_uncoupled_folds, round_us, bp_update, bp_update1)
+                   skip_uncoupled_folds, round_us, bp_update, bp_update1, reliability)
 
 
 def _phase1_local(ctx, seqs, bp, mp, align_model, th_a, w_pct_a, w_pct_s, t, w_pct_f=0.0, first=None):
@@ -171,18 +173,22 @@ def forest_ready(trees, pending, done):
 
 
 def _phase2(ctx, own, names, seqs, n, sim, score, left, right, t, w, eta0, t_max, th_a, th_s, th_s1, force_iters, level_sync, slice_iters,
-            skip_uncoupled_folds, round_us=None, bp_update=False, bp_update1=False):
+            skip_uncoupled_folds, round_us=None, bp_update=False, bp_update1=False, reliability=False):
     fam = dict(names=names, seqs=seqs, first=0, sim=sim, tree=(score, left, right))
     return _phase2_forest(ctx, own, [fam], t, w, eta0, t_max, th_a, th_s, th_s1, force_iters, level_sync, slice_iters,
-                          skip_uncoupled_folds, round_us, bp_update, bp_update1)[0]
+                          skip_uncoupled_folds, round_us, bp_update, bp_update1, reliability)[0]
 
 
 def _phase2_forest(ctx, own, fams, t, w, eta0, t_max, th_a, th_s, th_s1, force_iters, level_sync, slice_iters,
-                   skip_uncoupled_folds, round_us=None, bp_update=False, bp_update1=False):
+                   skip_uncoupled_folds, round_us=None, bp_update=False, bp_update1=False, reliability=False):
     """The progressive phase and the output of every family of the context at once.  fams: per family a dict with names,
     seqs, first (index of its first sequence in the context), sim and tree = (score, left, right).  The guide trees form one
     forest: a node is ready when both of its children are done, whatever its family, and the ready nodes of all families
-    share each launch.  Returns one Result per family."""
+    share each launch.  Returns one Result per family.
+    reliability: each Result also gets .reliability, the annotation of its final alignment and structure from the stores
+    the progressive phase read (Context.alignment_reliability): a dict with residue (per printed row, its residues'
+    values), col, pair, pair_rows and expected_accuracy; and .stockholm, that alignment as a Stockholm block with PP lines
+    (dafs_amd/stockholm.py, the same bytes `dafs --stockholm` writes)."""
     import time
     nf = len(fams)
     results = []
@@ -311,6 +317,15 @@ def _phase2_forest(ctx, own, fams, t, w, eta0, t_max, th_a, th_s, th_s1, force_i
             res.rows.append(row)
             lines += ["> " + fm["names"][local], row]
         res.output = "\n".join(lines) + "\n"
+        if reliability:
+            rl = ctx.alignment_reliability(sidx, mask, ss)
+            cuts = np.cumsum([len(fm["seqs"][int(s) - fm["first"]]) for s in sidx])[:-1]
+            per_row = np.split(rl["residue"], cuts)  # rows in the order of sidx
+            rl["residue"] = [per_row[r] for r in order]
+            res.reliability = rl
+            sto_names = stockholm.names(fm["names"])
+            res.stockholm = stockholm.block(res.tree_line, [sto_names[int(sidx[r]) - fm["first"]] for r in order], res.rows, rl["residue"],
+                                            rl["col"], res.ss_str)
     t.append(time.perf_counter())
     # fold_launch: the folding is only started there; its kernels overlap `pair` and the first half of `pct_fold_tree`,
     # which also holds the wait for them
@@ -375,7 +390,7 @@ def run_batch(families, ctx=None, max_bytes=None, **kw):
         raise ValueError("pipeline.run_batch: bp_update needs the resident-node schedule (level_sync=False)")
     opts = dict(w=4.0, eta0=0.5, t_max=600, w_pct_a=0.25, w_pct_s=0.25, th_a=0.01, th_s=0.2, th_s1=None, align_model=capi.ALIGN_PROBCONS,
                 force_iters=0, timers=None, level_sync=False, slice_iters=None, skip_uncoupled_folds=True, round_us=None, w_pct_f=0.0,
-                bp_update=False, bp_update1=False)
+                bp_update=False, bp_update1=False, reliability=False)
     unknown = set(kw) - set(opts)
     if unknown:
         raise TypeError("pipeline.run_batch: unknown options %s" % sorted(unknown))
@@ -405,7 +420,7 @@ def run_batch(families, ctx=None, max_bytes=None, **kw):
             t.append(time.perf_counter())
             res = _phase2_forest(ctx, False, fams, t, opts["w"], opts["eta0"], opts["t_max"], opts["th_a"], opts["th_s"], opts["th_s1"],
                                  opts["force_iters"], opts["level_sync"], opts["slice_iters"], opts["skip_uncoupled_folds"], opts["round_us"],
-                                 opts["bp_update"], opts["bp_update1"])
+                                 opts["bp_update"], opts["bp_update1"], opts["reliability"])
             for k, r in zip(grp, res):
                 out[k] = r
     finally:

@@ -356,6 +356,23 @@ int dafs_hip_consensus_structure(dafs_hip_ctx* ctx, uint32_t n, uint32_t len, co
 int dafs_hip_update_basepairing(dafs_hip_ctx* ctx, uint32_t n, uint32_t len, const uint32_t* seq, const uint8_t* mask,
                                 const uint32_t* ss, float* p_out);
 
+/* Reliability of an alignment (no counterpart in the reference; definitions in DESIGN.md "Alignment reliability").  Rows
+ * seq / mask as in dafs_node_input: n distinct sequences of one family (else DAFS_HIP_EINVAL), each mask row placing every
+ * residue of its sequence.  ss: the consensus structure over the len columns in the decoders' convention (ss[c] = right
+ * partner at the left column, DAFS_HIP_NONE otherwise; every column in at most one pair), or NULL for no pairs.
+ * mp_relaxed / bp_relaxed: 0 = the un-relaxed store (with -f the four-way result), 1 = the relaxed one, negative = the
+ * store the progressive phase reads now; the matching store must be valid and hold every pair (not needed for n = 1), the
+ * base-pairing store must be valid when ss is given.  Every sum is taken in double, rows in ascending sequence order, so
+ * the order of the given rows changes no bit.  Outputs (host; any may be NULL):
+ *   res_rel[sum of the rows' lengths]  rel(r, i): the rows in the given order, residues in sequence order (1.0 for n = 1)
+ *   col_rel[len]                       mean of rel over the residues of each column (0 for a column of gaps)
+ *   pair_rel[len], pair_rows[len]      at the left column of each pair of ss: the mean of bp[x](i, j) over the rows that
+ *                                      hold both residues, and their number; 0 elsewhere
+ *   expected_accuracy                  mean of rel over all residues */
+int dafs_hip_alignment_reliability(dafs_hip_ctx* ctx, uint32_t n, uint32_t len, const uint32_t* seq, const uint8_t* mask,
+                                   const uint32_t* ss, int mp_relaxed, int bp_relaxed, double* res_rel, double* col_rel,
+                                   double* pair_rel, uint32_t* pair_rows, double* expected_accuracy);
+
 /* ---- device-resident exchange of the sparse stores (multi-GPU runs) ---------------------------------------------------
  * One process per GPU shards phase 1 of DAFS::run (src/dafs.cpp:1787-1827): the folds (src/fold.cpp:66-67), the pair jobs
  * (src/align.cpp:46-50) and the output pairs of relax_matching_probability (src/dafs.cpp:265-315) are independent.  The
