@@ -127,6 +127,7 @@ _dd_default_params = _sig("dafs_hip_dd_default_params", None, [C.POINTER(DDParam
 _solve_nodes = _sig("dafs_hip_solve_nodes", C.c_int,
                     [C.c_void_p, C.c_uint32, C.POINTER(NodeInput), C.POINTER(DDParams), C.POINTER(NodeOutput)])
 _build_tree = _sig("dafs_host_build_tree", C.c_int, [C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])
+_merge_added = _sig("dafs_host_merge_added", C.c_int, [C.c_uint32, C.c_uint32] + [C.c_void_p] * 5)
 _set_mp = _sig("dafs_hip_set_mp", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])
 _nodes_open = _sig("dafs_hip_nodes_open", C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(NodeInput), C.POINTER(DDParams), C.c_void_p])
 _nodes_advance = _sig("dafs_hip_nodes_advance", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(DDParams), C.c_uint32, C.c_void_p])
@@ -578,6 +579,20 @@ def build_tree(sim):
     score = np.zeros(2 * n - 1, np.float32); left = np.zeros(2 * n - 1, np.int32); right = np.zeros(2 * n - 1, np.int32)
     check(_build_tree(n, sim.ctypes.data, score.ctypes.data, left.ctypes.data, right.ctypes.data))
     return score, left.astype(np.int64), right.astype(np.int64)
+
+
+def merge_added(ncols, zs):
+    """dafs_host_merge_added (host code in the library): k new sequences into a seed of ncols columns from their column maps
+    zs (per sequence a uint32 array, NONE for an unmatched residue).  Returns (seed_col, [res_col per sequence], width):
+    the merged column of every seed column and of every new residue, and the merged width."""
+    lens = np.array([len(z) for z in zs], np.uint32)
+    z = np.ascontiguousarray(np.concatenate([np.asarray(z, np.uint32) for z in zs]) if len(zs) else np.zeros(0, np.uint32), np.uint32)
+    seed_col = np.zeros(max(ncols, 1), np.uint32)
+    res_col = np.zeros(max(len(z), 1), np.uint32)
+    width = C.c_uint32()
+    check(_merge_added(ncols, len(zs), lens.ctypes.data, z.ctypes.data, seed_col.ctypes.data, res_col.ctypes.data, C.byref(width)))
+    cuts = np.cumsum(lens)[:-1] if len(zs) else []
+    return seed_col[:ncols], np.split(res_col[:len(z)], cuts) if len(zs) else [], width.value
 
 
 def dd_params(**kw):

@@ -72,6 +72,8 @@ struct Options {
   int device = 0;
   std::vector<int> devices;  // --devices: one process per entry for phase 1
   std::string stockholm;  // --stockholm FILE
+  std::string seed;       // --seed SEED: add FILE's sequences to this alignment
+  bool refinement_given = false;
   std::string input;
   std::vector<std::string> inputs;  // every FILE argument; with two or more, one output block per file
 };
@@ -94,6 +96,10 @@ const char* kHelp =
     "                        (shards exchanged over RCCL); the progressive alignment runs on the first\n"
     "      --stockholm FILE  Also write every printed alignment to FILE in Stockholm format, one block per input\n"
     "                        file, with per-residue (#=GR PP) and per-column (#=GC PP_cons) reliabilities\n"
+    "      --seed SEED       Add the sequences of the one FILE to the alignment SEED (Stockholm, or aligned FASTA\n"
+    "                        as dafs prints it) without changing its columns; the output has no tree line, and\n"
+    "                        --stockholm adds a #=GC RF line (x: seed column).  Not with -r, --bp-update, --devices,\n"
+    "                        --align-aux, --fold-aux or --save-*-aux\n"
     "\n Aligning options:\n"
     "  -a, --align-model arg Alignment model (value=CONTRAlign, ProbCons) (default: ProbCons)\n"
     "  -p, --align-pct arg   Weight of PCT for matching probabilities (default: 0.25)\n"
@@ -133,7 +139,7 @@ Options parse(int argc, char** argv) {
       {"no-alifold", {0, false}}, {"fold-th1", {'T', true}}, {"gamma1", {'G', true}}, {"ipknot", {0, false}},
       {"bp-update", {0, false}}, {"bp-update1", {0, false}}, {"fold-aux", {0, true}}, {"save-align-aux", {0, true}},
       {"save-fold-aux", {0, true}}, {"device", {0, true}}, {"devices", {0, true}}, {"input", {0, true}},
-      {"stockholm", {0, true}}};
+      {"stockholm", {0, true}}, {"seed", {0, true}}};
   std::map<char, std::string> shorts;
   for (const auto& kv : spec)
     if (kv.second.first) shorts[kv.second.first] = kv.first;
@@ -163,7 +169,7 @@ Options parse(int argc, char** argv) {
     }
     if (name == "help") { std::cout << kHelp << std::endl; exit(0); }
     else if (name == "version") { std::cout << "DAFS version " << DAFS_VERSION << std::endl; exit(0); }
-    else if (name == "refinement") o.refinement = std::stoi(value);
+    else if (name == "refinement") { o.refinement = std::stoi(value); o.refinement_given = true; }
     else if (name == "weight") o.w = std::stof(value);
     else if (name == "eta") o.eta = std::stof(value);
     else if (name == "max-iter") o.max_iter = std::stoi(value);
@@ -197,6 +203,18 @@ Options parse(int argc, char** argv) {
       if (value.empty()) throw std::string("--stockholm needs a file name");
       o.stockholm = value;
     }
+    else if (name == "seed") {
+      if (value.empty()) throw std::string("--seed needs a file name");
+      o.seed = value;
+    }
+  }
+  if (!o.seed.empty()) {  // the seed's columns stay as they are: nothing may realign its rows
+    if (o.refinement_given) throw std::string("--seed: -r would realign the seed's rows; it cannot be combined with --seed");
+    if (o.bp_update) throw std::string("--seed: --bp-update cannot be combined with --seed (--bp-update1 can)");
+    if (!o.devices.empty()) throw std::string("--seed: --devices cannot be combined with --seed (use --device)");
+    if (!o.align_aux.empty() || !o.fold_aux.empty() || !o.save_align_aux.empty() || !o.save_fold_aux.empty())
+      throw std::string("--seed: --align-aux, --fold-aux, --save-align-aux and --save-fold-aux cannot be combined with --seed");
+    if (o.inputs.size() != 1) throw std::string("--seed needs exactly one FILE of new sequences");
   }
   if (o.inputs.size() > 1) {
     if (!o.align_aux.empty() || !o.fold_aux.empty() || !o.save_align_aux.empty() || !o.save_fold_aux.empty())
@@ -492,14 +510,17 @@ std::vector<std::string> stockholm_names(const std::vector<Fasta>& ff) {
 }
 
 // rows in stdout order: name, printed text and the reliabilities of its residues; col_rel per column ('.' where a column
-// holds no residue).  Labels padded to the longest plus one.
-std::string stockholm_block(const std::string& tree_line, const std::vector<std::string>& names, const std::vector<std::string>& rows,
-                            const std::vector<const double*>& rel, const std::vector<double>& col_rel, const std::string& ss) {
+// holds no residue).  Labels padded to the longest plus one.  tree_line nullptr: no "#=GF CC" line; rf: per column a seed
+// column ('x') or an insert column ('.') of --seed, written as "#=GC RF" after PP_cons (nullptr: no RF line).
+std::string stockholm_block(const std::string* tree_line, const std::vector<std::string>& names, const std::vector<std::string>& rows,
+                            const std::vector<const double*>& rel, const std::vector<double>& col_rel, const std::string& ss,
+                            const std::vector<bool>* rf = nullptr) {
   size_t width = std::max(std::string("#=GC SS_cons").size(), std::string("#=GC PP_cons").size());
   for (const std::string& nm : names) width = std::max(width, nm.size() + 8);  // "#=GR " + name + " PP"
   ++width;
   auto label = [&](const std::string& l) { return l + std::string(width - l.size(), ' '); };
-  std::string out = "# STOCKHOLM 1.0\n#=GF CC " + tree_line + "\n";
+  std::string out = "# STOCKHOLM 1.0\n";
+  if (tree_line) out += "#=GF CC " + *tree_line + "\n";
   for (size_t r = 0; r < rows.size(); ++r) {
     out += label(names[r]) + rows[r] + "\n";
     std::string pp(rows[r].size(), '.');
@@ -511,7 +532,14 @@ std::string stockholm_block(const std::string& tree_line, const std::vector<std:
   for (size_t c = 0; c < col_rel.size(); ++c)
     for (const std::string& row : rows)
       if (row[c] != '-') { cons[c] = pp_char(col_rel[c]); break; }
-  out += label("#=GC SS_cons") + ss + "\n" + label("#=GC PP_cons") + cons + "\n//\n";
+  out += label("#=GC SS_cons") + ss + "\n" + label("#=GC PP_cons") + cons + "\n";
+  if (rf) {
+    std::string line(rf->size(), '.');
+    for (size_t c = 0; c < rf->size(); ++c)
+      if ((*rf)[c]) line[c] = 'x';
+    out += label("#=GC RF") + line + "\n";
+  }
+  out += "//\n";
   return out;
 }
 
@@ -521,6 +549,95 @@ void write_stockholm(const std::string& file, const std::vector<std::string>& bl
   for (const std::string& b : blocks) os << b;
   os.flush();
   if (!os) throw "--stockholm: cannot write " + file;
+}
+
+// ---------------------------------------------------------------------------------------------
+// --seed: the seed alignment.  The twin of stockholm.parse_seed / clean_seed in dafs_amd/stockholm.py:
+// the same files are read and refused, with the same messages.
+const char kSpace[] = " \t\n\v\f\r";  // isspace() in the "C" locale
+
+std::vector<std::string> fields(const std::string& s) {
+  std::vector<std::string> out;
+  size_t b = s.find_first_not_of(kSpace);
+  while (b != std::string::npos) {
+    const size_t e = s.find_first_of(kSpace, b);
+    out.push_back(s.substr(b, e == std::string::npos ? std::string::npos : e - b));
+    b = e == std::string::npos ? e : s.find_first_not_of(kSpace, e);
+  }
+  return out;
+}
+
+// Stockholm when the first line is "# STOCKHOLM 1.0": the first alignment up to "//", interleaved blocks concatenated by
+// name, '#' lines ignored, every other non-blank line "name row".  Otherwise aligned FASTA as this program prints it: lines
+// before the first '>' ignored, leading blanks of a name stripped, a record named SS_cons skipped, rows over several lines.
+void parse_seed(const std::string& file, std::vector<std::string>& names, std::vector<std::string>& rows) {
+  std::ifstream is(file.c_str(), std::ios::binary);
+  if (!is.is_open()) throw "--seed: cannot open " + file;
+  std::vector<std::string> lines;
+  std::string ln;
+  while (std::getline(is, ln)) {
+    const size_t e = ln.find_last_not_of(kSpace);
+    lines.push_back(e == std::string::npos ? std::string() : ln.substr(0, e + 1));
+  }
+  if (!lines.empty() && lines[0] == "# STOCKHOLM 1.0") {
+    std::map<std::string, size_t> at;
+    for (size_t k = 1; k < lines.size(); ++k) {
+      const std::string& l = lines[k];
+      if (l == "//") break;
+      if (l.empty() || l[0] == '#') continue;  // rstripped: a blank line is empty
+      const std::vector<std::string> f = fields(l);
+      if (f.size() != 2) throw "seed: line " + std::to_string(k + 1) + " is neither a #= annotation nor 'name row'";
+      if (!at.count(f[0])) {
+        at[f[0]] = names.size();
+        names.push_back(f[0]);
+        rows.push_back(std::string());
+      }
+      rows[at[f[0]]] += f[1];
+    }
+    return;
+  }
+  bool keep = false;
+  for (const std::string& l : lines) {
+    if (!l.empty() && l[0] == '>') {
+      const size_t b = l.find_first_not_of(kSpace, 1);
+      const std::string nm = b == std::string::npos ? std::string() : l.substr(b);
+      keep = nm != "SS_cons";
+      if (keep) {
+        names.push_back(nm);
+        rows.push_back(std::string());
+      }
+    } else if (keep) {
+      for (const std::string& f : fields(l)) rows.back() += f;
+    }
+  }
+}
+
+// refuses an empty seed, rows of unequal length, a character that is neither a letter nor a gap ('.', '-') and a row without
+// residues; drops the all-gap columns and writes every gap as '-'
+void clean_seed(const std::vector<std::string>& names, std::vector<std::string>& rows) {
+  if (rows.empty()) throw std::string("seed: no rows");
+  auto gap = [](char ch) { return ch == '.' || ch == '-'; };
+  for (size_t r = 0; r < rows.size(); ++r) {
+    if (rows[r].size() != rows[0].size())
+      throw "seed: rows of unequal length (" + names[0] + ": " + std::to_string(rows[0].size()) + " columns, " + names[r] + ": " +
+          std::to_string(rows[r].size()) + ")";
+    bool residue = false;
+    for (char ch : rows[r]) {
+      if (!gap(ch) && !std::isalpha((unsigned char)ch))
+        throw "seed: row " + names[r] + " holds '" + std::string(1, ch) + "', which is neither a letter nor a gap";
+      residue |= !gap(ch);
+    }
+    if (!residue) throw "seed: row " + names[r] + " has no residues";
+  }
+  std::vector<size_t> keep;  // not empty: every row has a residue
+  for (size_t c = 0; c < rows[0].size(); ++c)
+    for (const std::string& row : rows)
+      if (!gap(row[c])) { keep.push_back(c); break; }
+  for (std::string& row : rows) {
+    std::string out;
+    for (size_t c : keep) out += gap(row[c]) ? '-' : row[c];
+    row.swap(out);
+  }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -680,6 +797,117 @@ int rank_allgather(void* user, const void* send, void* recv, size_t bytes, void*
 int align_group(dafs_hip_ctx* ctx, const Options& o, Ranks& rk, int align_model, const std::vector<std::vector<Fasta> >& fams,
                 const std::vector<size_t>& members, const std::vector<std::ostream*>& out, const std::vector<std::string*>& sto);
 
+// Phase 1 on this process (:1787-1827; the twin of pipeline._phase1_local) over the context's sequences fa, families
+// [first[f], first[f + 1]): base-pairing probabilities (computed, or --fold-aux), and with two or more sequences the matching
+// probabilities (computed, or --align-aux), -f, the similarity blocks into sim (one n x n block per family, one after
+// another) and both consistency transforms.  The device folding is only started at the beginning: it keeps one workgroup
+// per sequence busy, and the alignment posteriors and the matching-probability transform run beside it.
+void phase1_local(dafs_hip_ctx* ctx, const Options& o, int align_model, const std::vector<Fasta>& fa, const std::vector<uint32_t>& first,
+                  std::vector<float>& sim) {
+  const uint N = (uint)fa.size(), F = (uint)first.size() - 1;
+  bool folding = false;
+  if (!o.fold_aux.empty()) {
+    std::vector<BP> bp;
+    load_fold_aux(o.fold_aux, fa, bp);
+    upload_bp(ctx, bp);
+  } else {
+    check(dafs_hip_fold_posteriors_begin(ctx, DAFS_FOLD_CONTRAFOLD, kCutoff));
+    folding = true;
+  }
+  bool fold_saved = false;
+  auto finish_folding = [&]() {
+    if (folding) { check(dafs_hip_fold_posteriors_end(ctx)); folding = false; }
+    if (!o.save_fold_aux.empty() && !fold_saved) { save_fold_aux(ctx, o.save_fold_aux, fa); fold_saved = true; }
+  };
+  if (N == 1) {
+    finish_folding();
+    return;
+  }
+  // matching probabilities, transposes, similarities (:1796-1819), PCTs (:1822-1827)
+  if (!o.align_aux.empty()) load_align_aux(ctx, o.align_aux, fa);
+  else check(dafs_hip_align_posteriors(ctx, align_model, o.align_th, 0, 0));
+  if (!o.save_align_aux.empty()) save_align_aux(ctx, o.save_align_aux, fa);
+  if (o.fourway != 0.0f) {  // relax_fourway_consistency (:1808-1809): needs the base-pairing rows, replaces mp_ before sim_
+    finish_folding();
+    check(dafs_hip_fourway_consistency(ctx, o.fourway));
+  }
+  size_t sim_floats = 0;
+  for (uint f = 0; f < F; ++f) sim_floats += (size_t)(first[f + 1] - first[f]) * (first[f + 1] - first[f]);
+  sim.assign(sim_floats, 0.0f);
+  check(dafs_hip_get_sim(ctx, sim.data()));
+  check(dafs_hip_consistency_match(ctx, o.align_pct));
+  finish_folding();
+  check(dafs_hip_consistency_bp(ctx, o.fold_pct));
+}
+
+// the node parameters of the options (-w, --eta, -u, -t, -m)
+dafs_dd_params dd_params_of(const Options& o) {
+  dafs_dd_params prm;
+  dafs_hip_dd_default_params(&prm);
+  prm.w = o.w; prm.eta0 = o.eta; prm.th_a = o.align_th; prm.th_s = *std::min_element(o.fold_th.begin(), o.fold_th.end());
+  prm.t_max = (uint32_t)o.max_iter;
+  return prm;
+}
+
+// The common secondary structure of a final alignment (:1857-1871; no RNAalifold term here) and its output (:1876-1879,
+// :1584-1601) on os: ">SS_cons", the brackets, then the rows sorted by sequence index.  The structure is decoded over the
+// rows in the order root holds them.  fa: the context's sequences; ff: the family's, its first one at index first.  With sto,
+// also the family's Stockholm block: tree_line (nullptr: no CC line), rf (nullptr: no RF line).
+void finish_alignment(dafs_hip_ctx* ctx, const Options& o, const std::vector<Fasta>& fa, ALN& root, const std::vector<Fasta>& ff,
+                      uint32_t first, std::ostream& os, std::string* sto, const std::string* tree_line, const std::vector<bool>* rf) {
+  std::string str;
+  std::vector<double> rel, col_rel;   // --stockholm: the reliabilities of this alignment and structure
+  std::map<uint32_t, size_t> rel_at;  // sequence -> its first residue in rel
+  {
+    std::vector<uint32_t> rs;
+    std::vector<uint8_t> rm;
+    flatten(root, rs, rm);
+    const uint32_t L = (uint32_t)root[0].second.size();
+    VU ss(L);
+    check(dafs_hip_consensus_structure(ctx, (uint32_t)root.size(), L, rs.data(), rm.data(), o.fold_th1[0], ss.data(), nullptr, nullptr));
+    if (o.bp_update1) {  // :1863-1869: re-estimate under the decoded structure, decode again (SparseNussinov::decode(p, ss, str))
+      std::vector<float> p((size_t)L * L);
+      check(dafs_hip_update_basepairing(ctx, (uint32_t)root.size(), L, rs.data(), rm.data(), ss.data(), p.data()));
+      check(dafs_hip_nussinov_decode(ctx, o.fold_th1[0], 0.0f, L, p.data(), nullptr, ss.data(), nullptr));
+    }
+    std::vector<char> buf(L + 1);
+    dafs_hip_make_brackets(L, ss.data(), buf.data());
+    str.assign(buf.data());
+    if (sto) {  // from the stores the progressive phase read (with --bp-update1 too: ss is the re-decoded one)
+      size_t tot = 0;
+      for (uint32_t s0 : rs) { rel_at[s0] = tot; tot += fa[s0].size(); }
+      rel.resize(tot);
+      col_rel.resize(L);
+      check(dafs_hip_alignment_reliability(ctx, (uint32_t)root.size(), L, rs.data(), rm.data(), ss.data(), -1, -1, rel.data(), col_rel.data(),
+                                           nullptr, nullptr, nullptr));
+    }
+  }
+
+  // output (:1876-1879, :1584-1601)
+  std::sort(root.begin(), root.end());
+  os << ">SS_cons" << std::endl << str << std::endl;
+  std::vector<std::string> rows;
+  for (const auto& row : root) {
+    const std::string& sq = fa[row.first].seq();
+    os << "> " << fa[row.first].name() << std::endl;
+    std::string text(row.second.size(), '-');
+    for (uint j = 0, k = 0; j != row.second.size(); ++j)
+      if (row.second[j]) text[j] = sq[k++];
+    os << text << std::endl;
+    rows.push_back(text);
+  }
+  if (sto) {
+    const std::vector<std::string> all_names = stockholm_names(ff);
+    std::vector<std::string> names;
+    std::vector<const double*> rr;
+    for (const auto& row : root) {
+      names.push_back(all_names[row.first - first]);
+      rr.push_back(rel.data() + rel_at[row.first]);
+    }
+    *sto = stockholm_block(tree_line, names, rows, rr, col_rel, str, rf);
+  }
+}
+
 // rand() as a process that has not called it yet sees it: glibc's default generator is the one initstate(1, state, 128)
 // sets up, and rand() returns random()
 struct FreshRand {
@@ -696,6 +924,109 @@ struct FreshRand {
     return (int)r;
   }
 };
+
+// `dafs --seed SEED FILE` (pipeline.add is the Python twin).  The context holds the seed's m sequences
+// in seed order and then FILE's k.  Phase 1 is a normal run's over all of them; one node per new sequence j, its leaf (left)
+// against the seed (right), and all k go through the resident-node rounds together; dafs_host_merge_added places them into
+// the seed; the structure is decoded over the rows new sequences, then seed rows, as in a run whose tree joins a leaf last.
+int run_add(const Options& o, int align_model) {
+  std::vector<std::string> snames, srows;
+  parse_seed(o.seed, snames, srows);
+  clean_seed(snames, srows);
+  std::vector<Fasta> added;
+  Fasta::load(added, o.input.c_str());
+  if (added.empty()) throw "no sequences in the input";
+  const uint32_t m = (uint32_t)srows.size(), k = (uint32_t)added.size(), C = (uint32_t)srows[0].size();
+  std::vector<Fasta> fa;
+  std::vector<uint8_t> smask((size_t)m * C, 0);
+  for (uint32_t r = 0; r < m; ++r) {
+    std::string sq;
+    for (uint32_t c = 0; c < C; ++c)
+      if (srows[r][c] != '-') { sq += srows[r][c]; smask[(size_t)r * C + c] = 1; }
+    fa.push_back(Fasta(snames[r], sq));
+  }
+  fa.insert(fa.end(), added.begin(), added.end());
+  const uint32_t N = m + k;
+
+  dafs_hip_ctx* ctx = nullptr;
+  check(dafs_hip_create(o.device, &ctx));
+  struct Guard { dafs_hip_ctx* c; ~Guard() { dafs_hip_destroy(c); } } guard{ctx};
+  std::vector<const char*> seqs(N);
+  std::vector<uint32_t> lens(N);
+  for (uint32_t i = 0; i < N; ++i) { seqs[i] = fa[i].seq().c_str(); lens[i] = fa[i].size(); }
+  check(dafs_hip_set_sequences(ctx, N, seqs.data(), lens.data()));
+  std::vector<float> sim;
+  phase1_local(ctx, o, align_model, fa, {0, N}, sim);
+
+  // the k nodes: opened in the first round, then advanced round after round until every one has finished
+  dafs_dd_params prm = dd_params_of(o);
+  prm.skip_uncoupled_folds = o.verbose == 0 ? 1 : 0;  // as the progressive loop of a run without -r
+  const uint32_t kRoundUs = getenv("DAFS_ROUND_US") ? (uint32_t)atoi(getenv("DAFS_ROUND_US")) : 2500u;
+  std::vector<NodeJob> jobs(k);
+  std::vector<dafs_node_input> in(k);
+  std::vector<uint32_t> seed_idx(m);
+  for (uint32_t r = 0; r < m; ++r) seed_idx[r] = r;
+  for (uint32_t j = 0; j < k; ++j) {
+    NodeJob& jb = jobs[j];
+    jb.s1.assign(1, m + j);
+    jb.m1.assign(lens[m + j], 1);
+    jb.s2 = seed_idx;
+    jb.m2 = smask;
+    jb.x.resize(lens[m + j]); jb.y.resize(C); jb.z.resize(lens[m + j]);
+    in[j].n1 = 1; in[j].n2 = m; in[j].len1 = lens[m + j]; in[j].len2 = C;
+    in[j].seq1 = jb.s1.data(); in[j].seq2 = jb.s2.data(); in[j].mask1 = jb.m1.data(); in[j].mask2 = jb.m2.data();
+  }
+  std::vector<uint32_t> handle(k), open_ids;  // open_ids: the nodes still running, in handle order
+  std::vector<uint8_t> fin(k, 0);
+  uint8_t none = 0;  // the finished flags and handles of an empty list
+  uint32_t none_handle = 0;
+  check(dafs_hip_nodes_round(ctx, k, in.data(), handle.data(), 0, nullptr, &prm, 0, kRoundUs, &none, fin.data()));
+  for (uint32_t j = 0; j < k; ++j) open_ids.push_back(j);
+  while (true) {
+    std::vector<uint32_t> still;
+    for (size_t b = 0; b < open_ids.size(); ++b) {
+      const uint32_t j = open_ids[b];
+      if (!fin[b]) { still.push_back(j); continue; }
+      dafs_node_output r;
+      r.x = jobs[j].x.data(); r.y = jobs[j].y.data(); r.z = jobs[j].z.data();
+      check(dafs_hip_nodes_result(ctx, handle[j], &r));
+      if (o.verbose >= 1) std::cerr << "Step: " << r.iterations << ", Violated: " << r.violated << std::endl;  // :1292
+    }
+    open_ids.swap(still);
+    if (open_ids.empty()) break;
+    std::vector<uint32_t> old_handles;
+    for (uint32_t j : open_ids) old_handles.push_back(handle[j]);
+    fin.assign(open_ids.size(), 0);
+    check(dafs_hip_nodes_round(ctx, 0, in.data(), &none_handle, (uint32_t)old_handles.size(), old_handles.data(), &prm, 0, kRoundUs, fin.data(),
+                               &none));
+  }
+  check(dafs_hip_nodes_close(ctx));
+
+  // the merge; the rows new sequences (file order), then seed rows (seed order)
+  std::vector<uint32_t> z, seed_col(C), res_col;
+  for (uint32_t j = 0; j < k; ++j) z.insert(z.end(), jobs[j].z.begin(), jobs[j].z.end());
+  res_col.resize(z.size() ? z.size() : 1);
+  uint32_t width = 0;
+  check(dafs_host_merge_added(C, k, lens.data() + m, z.data(), seed_col.data(), res_col.data(), &width));
+  ALN root;
+  for (uint32_t j = 0, off = 0; j < k; off += lens[m + j], ++j) {
+    std::vector<bool> msk(width, false);
+    for (uint32_t i = 0; i < lens[m + j]; ++i) msk[res_col[off + i]] = true;
+    root.push_back(std::make_pair(m + j, msk));
+  }
+  for (uint32_t r = 0; r < m; ++r) {
+    std::vector<bool> msk(width, false);
+    for (uint32_t c = 0; c < C; ++c) msk[seed_col[c]] = smask[(size_t)r * C + c] != 0;
+    root.push_back(std::make_pair(r, msk));
+  }
+  std::vector<bool> rf(width, false);
+  for (uint32_t c = 0; c < C; ++c) rf[seed_col[c]] = true;
+  std::string sto;
+  finish_alignment(ctx, o, fa, root, fa, 0, std::cout, o.stockholm.empty() ? nullptr : &sto, nullptr, &rf);
+  std::cout.flush();
+  if (!o.stockholm.empty()) write_stockholm(o.stockholm, {sto});
+  return 0;
+}
 
 int run(const Options& o, Ranks& rk) {
   // ---- option checks mirroring parse_options (:1683-1763)
@@ -717,6 +1048,7 @@ int run(const Options& o, Ranks& rk) {
     if (!o.no_alifold) std::cerr << "note: RNAalifold is not available in this build; running as with --no-alifold" << std::endl;
     if (!o.fold_model_given && o.fold_aux.empty()) std::cerr << "note: default folding model is CONTRAfold in this build" << std::endl;
   }
+  if (!o.seed.empty()) return run_add(o, align_model);
 
   // one family per input file
   const bool multi = o.inputs.size() > 1;
@@ -804,29 +1136,11 @@ int align_group(dafs_hip_ctx* ctx, const Options& o, Ranks& rk, int align_model,
   check(dafs_hip_set_sequences(ctx, N, seqs.data(), lens.data()));
   if (F > 1) check(dafs_hip_set_families(ctx, F, first.data()));
 
-  // base-pairing probabilities (:1787).  The device folding is only started here: it keeps one workgroup per
-  // sequence busy, and the alignment posteriors and the matching-probability transform run beside it.
   const bool sharded = !o.devices.empty() && N > 1;
   if (!sharded && rk.rank != 0) return 0;  // a single sequence: nothing to share
-  bool folding = false;
-  if (sharded) {
-  } else if (!o.fold_aux.empty()) {
-    std::vector<BP> bp;
-    load_fold_aux(o.fold_aux, fa, bp);
-    upload_bp(ctx, bp);
-  } else {
-    check(dafs_hip_fold_posteriors_begin(ctx, DAFS_FOLD_CONTRAFOLD, kCutoff));
-    folding = true;
-  }
-  bool fold_saved = false;
-  auto finish_folding = [&]() {
-    if (folding) { check(dafs_hip_fold_posteriors_end(ctx)); folding = false; }
-    if (!o.save_fold_aux.empty() && !fold_saved) { save_fold_aux(ctx, o.save_fold_aux, fa); fold_saved = true; }
-  };
 
   // per family its guide tree (a family of one sequence: the leaf alone)
   std::vector<std::vector<node_t> > trees(F, std::vector<node_t>(1, std::make_pair(0.0f, std::make_pair(-1u, -1u))));
-  if (N == 1) finish_folding();
   if (sharded) {
     // phase 1 (:1787-1827) on rk.world ranks: every rank ends with the complete stores, rank 0 goes on alone
     rk.connect();
@@ -838,24 +1152,11 @@ int align_group(dafs_hip_ctx* ctx, const Options& o, Ranks& rk, int align_model,
     std::vector<float> sim((size_t)N * N);
     check(dafs_hip_get_sim(ctx, sim.data()));
     trees[0] = build_tree(sim, N);
-  } else if (N > 1) {
-    // matching probabilities, transposes, similarities (:1796-1819), PCTs (:1822-1827), tree (:1830)
-    if (!o.align_aux.empty()) load_align_aux(ctx, o.align_aux, fa);
-    else check(dafs_hip_align_posteriors(ctx, align_model, o.align_th, 0, 0));
-    if (!o.save_align_aux.empty()) save_align_aux(ctx, o.save_align_aux, fa);
-    if (o.fourway != 0.0f) {  // relax_fourway_consistency (:1808-1809): needs the base-pairing rows, replaces mp_ before sim_
-      finish_folding();
-      check(dafs_hip_fourway_consistency(ctx, o.fourway));
-    }
-    size_t sim_floats = 0;  // one n x n block per family, one after another
-    for (uint f = 0; f < F; ++f) sim_floats += (size_t)(first[f + 1] - first[f]) * (first[f + 1] - first[f]);
-    std::vector<float> sim(sim_floats);
-    check(dafs_hip_get_sim(ctx, sim.data()));
-    check(dafs_hip_consistency_match(ctx, o.align_pct));
-    finish_folding();
-    check(dafs_hip_consistency_bp(ctx, o.fold_pct));
-    size_t blk = 0;
-    for (uint f = 0; f < F; ++f) {
+  } else {
+    std::vector<float> sim;
+    phase1_local(ctx, o, align_model, fa, first, sim);
+    size_t blk = 0;  // the guide trees (:1830) from the families' similarity blocks; a single sequence has none
+    for (uint f = 0; N > 1 && f < F; ++f) {
       const uint n = first[f + 1] - first[f];
       trees[f] = build_tree(std::vector<float>(sim.begin() + blk, sim.begin() + blk + (size_t)n * n), n);
       blk += (size_t)n * n;
@@ -868,10 +1169,7 @@ int align_group(dafs_hip_ctx* ctx, const Options& o, Ranks& rk, int align_model,
   }
 
   // progressive alignment (:1838): every node whose children are ready is solved in the same batch
-  dafs_dd_params prm;
-  dafs_hip_dd_default_params(&prm);
-  prm.w = o.w; prm.eta0 = o.eta; prm.th_a = o.align_th; prm.th_s = *std::min_element(o.fold_th.begin(), o.fold_th.end());
-  prm.t_max = (uint32_t)o.max_iter;
+  const dafs_dd_params prm = dd_params_of(o);
   // The progressive loop below uses the alignment of a node and nothing else (dafs.cpp:896-912), except that the
   // score of the root seeds the iterative refinement and -v prints every node's iteration count (:1292): without
   // either, nodes with no consensus base pair may leave out their folding DPs
@@ -996,62 +1294,13 @@ int align_group(dafs_hip_ctx* ctx, const Options& o, Ranks& rk, int align_model,
       if (sc[0] > s) { s = sc[0]; root.swap(merged[0]); }
     }
 
-    // common secondary structure of the final alignment (:1857-1871; no RNAalifold term here)
-    std::string str;
-    std::vector<double> rel, col_rel;   // --stockholm: the reliabilities of this alignment and structure
-    std::map<uint32_t, size_t> rel_at;  // sequence -> its first residue in rel
-    {
-      std::vector<uint32_t> rs;
-      std::vector<uint8_t> rm;
-      flatten(root, rs, rm);
-      const uint32_t L = (uint32_t)root[0].second.size();
-      VU ss(L);
-      check(dafs_hip_consensus_structure(ctx, (uint32_t)root.size(), L, rs.data(), rm.data(), o.fold_th1[0], ss.data(), nullptr, nullptr));
-      if (o.bp_update1) {  // :1863-1869: re-estimate under the decoded structure, decode again (SparseNussinov::decode(p, ss, str))
-        std::vector<float> p((size_t)L * L);
-        check(dafs_hip_update_basepairing(ctx, (uint32_t)root.size(), L, rs.data(), rm.data(), ss.data(), p.data()));
-        check(dafs_hip_nussinov_decode(ctx, o.fold_th1[0], 0.0f, L, p.data(), nullptr, ss.data(), nullptr));
-      }
-      std::vector<char> buf(L + 1);
-      dafs_hip_make_brackets(L, ss.data(), buf.data());
-      str.assign(buf.data());
-      if (!sto.empty()) {  // from the stores the progressive phase read (with --bp-update1 too: ss is the re-decoded one)
-        size_t tot = 0;
-        for (uint32_t s0 : rs) { rel_at[s0] = tot; tot += fa[s0].size(); }
-        rel.resize(tot);
-        col_rel.resize(L);
-        check(dafs_hip_alignment_reliability(ctx, (uint32_t)root.size(), L, rs.data(), rm.data(), ss.data(), -1, -1, rel.data(), col_rel.data(),
-                                             nullptr, nullptr, nullptr));
-      }
-    }
-
-    // output (:1876-1879, :1584-1601)
-    std::sort(root.begin(), root.end());
-    std::ostream& os = *out[f];
-    os << ">SS_cons" << std::endl << str << std::endl;
-    std::vector<std::string> rows;
-    for (const auto& row : root) {
-      const std::string& sq = fa[row.first].seq();
-      os << "> " << fa[row.first].name() << std::endl;
-      std::string text(row.second.size(), '-');
-      for (uint j = 0, k = 0; j != row.second.size(); ++j)
-        if (row.second[j]) text[j] = sq[k++];
-      os << text << std::endl;
-      rows.push_back(text);
-    }
+    std::string tree_line;
     if (!sto.empty()) {
-      const std::vector<Fasta>& ff = fams[members[f]];
-      const std::vector<std::string> all_names = stockholm_names(ff);
-      std::vector<std::string> names;
-      std::vector<const double*> rr;
-      for (const auto& row : root) {
-        names.push_back(all_names[row.first - first[f]]);
-        rr.push_back(rel.data() + rel_at[row.first]);
-      }
       std::ostringstream tl;
-      print_tree(tl, trees[f], ff, (int)trees[f].size() - 1);
-      *sto[f] = stockholm_block(tl.str(), names, rows, rr, col_rel, str);
+      print_tree(tl, trees[f], fams[members[f]], (int)trees[f].size() - 1);
+      tree_line = tl.str();
     }
+    finish_alignment(ctx, o, fa, root, fams[members[f]], first[f], *out[f], sto.empty() ? nullptr : sto[f], &tree_line, nullptr);
   }
   return 0;
 }

@@ -1,7 +1,9 @@
 // dafs_amd/csrc/host_tree.cpp -- DAFS::build_tree (reference src/dafs.cpp:446-492) as a C entry point, so that
 // every host (the C++ command line, the Python driver of tests and bench.py) builds the guide tree with the same
 // code: greedy joins taken from a max-heap of (similarity, (i, j)), merged distance (d[ii][l] + d[ii][r]) * s / 2.
+// Also the merge of new sequences into a fixed seed alignment (dafs_host_merge_added), shared the same way.
 // Host logic only; nothing here touches the device.
+#include <cstdint>
 #include <queue>
 #include <utility>
 #include <vector>
@@ -41,5 +43,56 @@ extern "C" int dafs_host_build_tree(uint32_t n0, const float* sim, float* score,
     right[n] = (int32_t)b;
     idx[n++] = l;
   }
+  return DAFS_HIP_OK;
+}
+
+// The merge of `dafs --seed`: k new sequences placed into a fixed seed of C columns from their
+// column maps z.  Anchors are shifted by one below (slot 0 is anchor -1, slot c + 1 is seed column c).
+extern "C" int dafs_host_merge_added(uint32_t C, uint32_t k, const uint32_t* lens, const uint32_t* z, uint32_t* seed_col,
+                                     uint32_t* res_col, uint32_t* width) {
+  if (!width || (C && !seed_col) || (k && !lens)) return DAFS_HIP_EINVAL;
+  uint64_t total = 0;
+  for (uint32_t j = 0; j != k; ++j) total += lens[j];
+  if (total && (!z || !res_col)) return DAFS_HIP_EINVAL;
+  // per anchor slot the widest insert block any sequence needs; matched columns must rise strictly within a sequence
+  std::vector<uint32_t> W((size_t)C + 1, 0);
+  const uint32_t* zj = z;
+  for (uint32_t j = 0; j != k; zj += lens[j], ++j) {
+    uint32_t a = 0, cnt = 0;
+    for (uint32_t i = 0; i != lens[j]; ++i) {
+      if (zj[i] == DAFS_HIP_NONE) { ++cnt; continue; }
+      if (zj[i] >= C || zj[i] + 1 <= a) return DAFS_HIP_EINVAL;
+      if (cnt > W[a]) W[a] = cnt;
+      a = zj[i] + 1;
+      cnt = 0;
+    }
+    if (cnt > W[a]) W[a] = cnt;
+  }
+  // layout: the anchor -1 block, then per seed column the column and its block
+  std::vector<uint32_t> start((size_t)C + 1);
+  uint64_t pos = W[0];
+  start[0] = 0;
+  for (uint32_t c = 0; c != C; ++c) {
+    seed_col[c] = (uint32_t)pos;
+    start[c + 1] = (uint32_t)++pos;
+    pos += W[c + 1];
+    if (pos >= DAFS_HIP_NONE) return DAFS_HIP_EINVAL;
+  }
+  // every residue: its seed column, or the next free place of its block (left-justified)
+  zj = z;
+  uint32_t* rj = res_col;
+  for (uint32_t j = 0; j != k; zj += lens[j], rj += lens[j], ++j) {
+    uint32_t a = 0, t = 0;
+    for (uint32_t i = 0; i != lens[j]; ++i) {
+      if (zj[i] == DAFS_HIP_NONE) {
+        rj[i] = start[a] + t++;
+      } else {
+        rj[i] = seed_col[zj[i]];
+        a = zj[i] + 1;
+        t = 0;
+      }
+    }
+  }
+  *width = (uint32_t)pos;
   return DAFS_HIP_OK;
 }

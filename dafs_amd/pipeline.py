@@ -301,31 +301,7 @@ def _phase2_forest(ctx, own, fams, t, w, eta0, t_max, th_a, th_s, th_s1, force_i
         res.rounds = rounds
         n = len(fm["seqs"])
         sidx, mask = aln[(f, 2 * n - 2)]
-        _, ss, _ = ctx.consensus_structure(sidx, mask, th1)
-        if bp_update1:  # :1863-1869: decode, re-estimate under that structure, decode again
-            _, ss = ctx.nussinov(ctx.update_basepairing(sidx, mask, ss), None, th1)
-        res.ss = ss
-        res.ss_str = capi.make_brackets(ss)
-        order = np.argsort(sidx, kind="stable")  # std::sort(aln) :1876
-        lines = [res.tree_line, ">SS_cons", res.ss_str]
-        res.rows = []
-        for r in order:
-            row_bytes = np.full(mask.shape[1], ord("-"), np.uint8)
-            local = int(sidx[r]) - fm["first"]
-            row_bytes[mask[r].astype(bool)] = np.frombuffer(fm["seqs"][local].encode("latin-1"), np.uint8)  # residues into their columns
-            row = row_bytes.tobytes().decode("latin-1")
-            res.rows.append(row)
-            lines += ["> " + fm["names"][local], row]
-        res.output = "\n".join(lines) + "\n"
-        if reliability:
-            rl = ctx.alignment_reliability(sidx, mask, ss)
-            cuts = np.cumsum([len(fm["seqs"][int(s) - fm["first"]]) for s in sidx])[:-1]
-            per_row = np.split(rl["residue"], cuts)  # rows in the order of sidx
-            rl["residue"] = [per_row[r] for r in order]
-            res.reliability = rl
-            sto_names = stockholm.names(fm["names"])
-            res.stockholm = stockholm.block(res.tree_line, [sto_names[int(sidx[r]) - fm["first"]] for r in order], res.rows, rl["residue"],
-                                            rl["col"], res.ss_str)
+        _final(ctx, res, fm["names"], fm["seqs"], fm["first"], sidx, mask, th1, bp_update1, reliability, res.tree_line)
     t.append(time.perf_counter())
     # fold_launch: the folding is only started there; its kernels overlap `pair` and the first half of `pct_fold_tree`,
     # which also holds the wait for them
@@ -336,6 +312,114 @@ def _phase2_forest(ctx, own, fams, t, w, eta0, t_max, th_a, th_s, th_s1, force_i
     if own:
         ctx.close()
     return results
+
+
+def _final(ctx, res, names, seqs, first, sidx, mask, th1, bp_update1, reliability, tree_line, rf=None):
+    """The common structure of a final alignment (sidx: global sequence index per row, mask) and its output, into res:
+    .ss, .ss_str, .rows, .output and, with reliability, .reliability and .stockholm.  names / seqs: the family's, its first
+    sequence at global index `first`.  tree_line None: no tree line (pipeline.add); rf: the RF line of the Stockholm
+    block."""
+    _, ss, _ = ctx.consensus_structure(sidx, mask, th1)
+    if bp_update1:  # :1863-1869: decode, re-estimate under that structure, decode again
+        _, ss = ctx.nussinov(ctx.update_basepairing(sidx, mask, ss), None, th1)
+    res.ss = ss
+    res.ss_str = capi.make_brackets(ss)
+    order = np.argsort(sidx, kind="stable")  # std::sort(aln) :1876
+    lines = ([] if tree_line is None else [tree_line]) + [">SS_cons", res.ss_str]
+    res.rows = []
+    for r in order:
+        row_bytes = np.full(mask.shape[1], ord("-"), np.uint8)
+        local = int(sidx[r]) - first
+        row_bytes[mask[r].astype(bool)] = np.frombuffer(seqs[local].encode("latin-1"), np.uint8)  # residues into their columns
+        row = row_bytes.tobytes().decode("latin-1")
+        res.rows.append(row)
+        lines += ["> " + names[local], row]
+    res.output = "\n".join(lines) + "\n"
+    if reliability:
+        rl = ctx.alignment_reliability(sidx, mask, ss)
+        cuts = np.cumsum([len(seqs[int(s) - first]) for s in sidx])[:-1]
+        per_row = np.split(rl["residue"], cuts)  # rows in the order of sidx
+        rl["residue"] = [per_row[r] for r in order]
+        res.reliability = rl
+        sto_names = stockholm.names(names)
+        res.stockholm = stockholm.block(tree_line, [sto_names[int(sidx[r]) - first] for r in order], res.rows, rl["residue"],
+                                        rl["col"], res.ss_str, rf)
+
+
+def add(seed_names, seed_rows, names, seqs, ctx=None, w=4.0, eta0=0.5, t_max=600, w_pct_a=0.25, w_pct_s=0.25, th_a=0.01,
+        th_s=0.2, th_s1=None, align_model=capi.ALIGN_PROBCONS, force_iters=0, slice_iters=None, skip_uncoupled_folds=True,
+        round_us=None, w_pct_f=0.0, bp_update1=False, reliability=False):
+    """Add new sequences to a fixed seed alignment without changing its columns (`dafs --seed`).
+    seed_names / seed_rows: the seed's rows (letters and '.' / '-' gaps; stockholm.read_seed reads a file), checked and
+    without their all-gap columns (stockholm.clean_seed).  names / seqs: the new sequences.  The options are run()'s.
+
+    The context holds the m seed sequences and then the k new ones; phase 1 is a normal run's over all of them.  One node per
+    new sequence j (its leaf against the seed), all k through the resident-node rounds together; the merge is
+    capi.merge_added (dafs_host_merge_added); the structure is decoded over the rows new sequences then seed rows.
+    Returns a Result: .output (a normal run's format without the tree line: rows in context order), .rows, .ss, .ss_str,
+    .z (per new sequence its column map into the seed), .rf (per merged column True for a seed column), .dd_log
+    ({j: (iterations, violated, ncbp, score)}), .dd_memory, .seconds; with reliability, .reliability and .stockholm (no CC
+    line, a `#=GC RF` line)."""
+    import time
+    seed_names, seed_rows = stockholm.clean_seed(seed_names, seed_rows)
+    names, seqs = list(names), list(seqs)
+    if not seqs or len(names) != len(seqs):
+        raise ValueError("pipeline.add: at least one new sequence and one name per sequence")
+    m, k = len(seed_rows), len(seqs)
+    seed_seqs = [r.replace("-", "") for r in seed_rows]
+    seed_mask = np.array([[ch != "-" for ch in r] for r in seed_rows], np.uint8)
+    all_names, all_seqs = seed_names + names, seed_seqs + seqs
+    own = ctx is None
+    if own:
+        ctx = capi.Context(0)
+    try:
+        t = [time.perf_counter()]
+        _phase1_local(ctx, all_seqs, None, None, align_model, th_a, w_pct_a, w_pct_s, t, w_pct_f)
+        t.append(time.perf_counter())
+        prm = capi.dd_params(w=w, eta0=eta0, th_a=th_a, th_s=th_s, t_max=t_max, force_iters=force_iters,
+                             skip_uncoupled_folds=1 if skip_uncoupled_folds else 0)
+        seed_idx = np.arange(m, dtype=np.uint32)
+        new = [(np.array([m + j], np.uint32), np.ones((1, len(seqs[j])), np.uint8), seed_idx, seed_mask) for j in range(k)]
+        new_ids = list(range(k))
+        if slice_iters is None and round_us is None:
+            round_us = int(os.environ.get("DAFS_ROUND_US", "2500"))
+        outs = [None] * k
+        open_nodes = {}  # j -> (handle, len1, len2)
+        while new or open_nodes:  # as the resident-node loop of _phase2_forest; every node is ready in the first round
+            ids = sorted(open_nodes)
+            hs, dims, fin_old, fin_new = ctx.nodes_round(new, [open_nodes[j][0] for j in ids], prm, slice_iters or 0, round_us or 0)
+            for j, h, d in zip(new_ids, hs, dims):
+                open_nodes[j] = (h, d[0], d[1])
+            for j, fin in list(zip(ids, fin_old)) + list(zip(new_ids, fin_new)):
+                if fin:
+                    h, l1, l2 = open_nodes.pop(j)
+                    outs[j] = ctx.nodes_result(h, l1, l2)
+            new, new_ids = [], []
+        dd_memory = ctx.nodes_memory()
+        ctx.nodes_close()
+        t.append(time.perf_counter())
+        # the merge, then the rows in the order new sequences, seed rows (the sidx of a run that joins a leaf last)
+        seed_col, res_col, width = capi.merge_added(seed_mask.shape[1], [o["z"] for o in outs])
+        mask = np.zeros((m + k, width), np.uint8)
+        mask[:m, seed_col] = seed_mask
+        for j in range(k):
+            mask[m + j, res_col[j]] = 1
+        rf = np.zeros(width, bool)
+        rf[seed_col] = True
+        sidx = np.concatenate([np.arange(m, m + k), np.arange(m)]).astype(np.uint32)
+        res = Result()
+        res.z = [o["z"] for o in outs]
+        res.rf = rf
+        res.dd_log = {j: (o["iterations"], o["violated"], o["ncbp"], o["score"]) for j, o in enumerate(outs)}
+        res.dd_memory = dd_memory
+        _final(ctx, res, all_names, all_seqs, 0, sidx, np.concatenate([mask[m:], mask[:m]]), th_s if th_s1 is None else th_s1,
+               bp_update1, reliability, None, rf)
+        t.append(time.perf_counter())
+        res.seconds = dict(phase1=t[3] - t[0], nodes=t[4] - t[3], final=t[5] - t[4], total=t[5] - t[0])
+    finally:
+        if own:
+            ctx.close()
+    return res
 
 
 def family_bytes(lens):

@@ -232,6 +232,18 @@ int dafs_hip_fold_posterior_dense(dafs_hip_ctx* ctx, const char* seq, uint32_t l
  * score/left/right: 2N-1 entries; leaves have left = right = -1, node N+k is the k-th join of slots left, right. */
 int dafs_host_build_tree(uint32_t n, const float* sim, float* score, int32_t* left, int32_t* right);
 
+/* Host-side helper (no device work): the merge of `dafs --seed` and pipeline.add, k new sequences
+ * placed into a fixed seed alignment of C columns.  lens: k sequence lengths; z: their column maps from the k nodes (leaf j
+ * against the seed) concatenated, per residue a seed column or DAFS_HIP_NONE, the seed columns strictly increasing within
+ * each sequence (else DAFS_HIP_EINVAL).  A matched residue goes in its seed column; an unmatched one is anchored after the
+ * seed column of the nearest earlier matched residue of its sequence, or at the start (anchor -1).  The merged alignment is,
+ * for c = -1, 0, ..., C-1: seed column c (c >= 0), then max_j (residues of j anchored at c) insert columns, which every
+ * sequence fills from the left.  For k = 1 this is DAFS::project_alignment((leaf), seed, z) (src/dafs.cpp:766-825).
+ * seed_col[C]: the merged column of each seed column; res_col[sum lens]: the merged column of each residue, sequence after
+ * sequence; *width: the number of merged columns. */
+int dafs_host_merge_added(uint32_t C, uint32_t k, const uint32_t* lens, const uint32_t* z, uint32_t* seed_col, uint32_t* res_col,
+                          uint32_t* width);
+
 /* ------------------------------------------------------------------------------------------
  * L1: probabilistic consistency transforms.
  * Replaces DAFS::relax_basepairing_probability (src/dafs.cpp:326-375) and
