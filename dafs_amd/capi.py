@@ -103,6 +103,26 @@ class NodeInput(C.Structure):
                 ("p_x", C.c_void_p), ("p_y", C.c_void_p)]
 
 
+def _node_inputs(nodes):
+    """The NodeInput array of nodes (s1, m1, s2, m2) or (s1, m1, s2, m2, p_x, p_y) (one entry at least: an empty list
+    passes a valid pointer), and per node the arrays it points into, (s1, s2, m1, m2, p_x, p_y), which must outlive the C
+    call."""
+    ins = (NodeInput * max(len(nodes), 1))()
+    keep = []
+    for b, node in enumerate(nodes):  # p_x, p_y: supplied base-pairing matrices
+        s1, m1, s2, m2 = node[:4]
+        s1 = np.ascontiguousarray(s1, np.uint32); s2 = np.ascontiguousarray(s2, np.uint32)
+        m1 = np.ascontiguousarray(m1, np.uint8); m2 = np.ascontiguousarray(m2, np.uint8)
+        px = np.ascontiguousarray(node[4], np.float32) if len(node) > 4 and node[4] is not None else None
+        py = np.ascontiguousarray(node[5], np.float32) if len(node) > 5 and node[5] is not None else None
+        keep.append((s1, s2, m1, m2, px, py))
+        ins[b].n1, ins[b].n2, ins[b].len1, ins[b].len2 = m1.shape[0], m2.shape[0], m1.shape[1], m2.shape[1]
+        ins[b].seq1, ins[b].seq2, ins[b].mask1, ins[b].mask2 = s1.ctypes.data, s2.ctypes.data, m1.ctypes.data, m2.ctypes.data
+        ins[b].p_x = px.ctypes.data if px is not None else None
+        ins[b].p_y = py.ctypes.data if py is not None else None
+    return ins, keep
+
+
 class NodeOutput(C.Structure):
     _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("z", C.c_void_p), ("score", C.c_float),
                 ("ncbp", C.c_uint32), ("iterations", C.c_uint32), ("violated", C.c_uint32)]
@@ -396,25 +416,22 @@ class Context:
 
     # --- fused node solver ---
     def solve_nodes(self, nodes, prm=None):
-        """nodes: list of (seq1, mask1, seq2, mask2) with seq* uint32 arrays and mask* uint8 [n, len].
+        """nodes: list of (seq1, mask1, seq2, mask2) with seq* uint32 arrays and mask* uint8 [n, len], or
+        (seq1, mask1, seq2, mask2, p_x, p_y) with supplied base-pairing matrices.
         Returns list of dicts x, y, z, score, ncbp, iterations, violated."""
         if prm is None:
             prm = dd_params()
         n = len(nodes)
-        ins = (NodeInput * n)()
+        ins, keep = _node_inputs(nodes)
         outs = (NodeOutput * n)()
-        keep = []
-        for b, (s1, m1, s2, m2) in enumerate(nodes):
-            s1 = np.ascontiguousarray(s1, np.uint32); s2 = np.ascontiguousarray(s2, np.uint32)
-            m1 = np.ascontiguousarray(m1, np.uint8); m2 = np.ascontiguousarray(m2, np.uint8)
-            x = np.zeros(m1.shape[1], np.uint32); y = np.zeros(m2.shape[1], np.uint32); z = np.zeros(m1.shape[1], np.uint32)
-            keep.append((s1, s2, m1, m2, x, y, z))
-            ins[b].n1, ins[b].n2, ins[b].len1, ins[b].len2 = m1.shape[0], m2.shape[0], m1.shape[1], m2.shape[1]
-            ins[b].seq1, ins[b].seq2, ins[b].mask1, ins[b].mask2 = s1.ctypes.data, s2.ctypes.data, m1.ctypes.data, m2.ctypes.data
+        xyz = []
+        for b, k in enumerate(keep):
+            x = np.zeros(k[2].shape[1], np.uint32); y = np.zeros(k[3].shape[1], np.uint32); z = np.zeros(k[2].shape[1], np.uint32)
+            xyz.append((x, y, z))
             outs[b].x, outs[b].y, outs[b].z = x.ctypes.data, y.ctypes.data, z.ctypes.data
         check(_solve_nodes(self._h, n, ins, C.byref(prm), outs))
-        return [dict(x=k[4], y=k[5], z=k[6], score=np.float32(outs[b].score), ncbp=outs[b].ncbp,
-                     iterations=outs[b].iterations, violated=outs[b].violated) for b, k in enumerate(keep)]
+        return [dict(x=x, y=y, z=z, score=np.float32(outs[b].score), ncbp=outs[b].ncbp, iterations=outs[b].iterations,
+                     violated=outs[b].violated) for b, (x, y, z) in enumerate(xyz)]
 
     def set_mp(self, nnz, rowptr, col, val):
         """Supplied matching probabilities (--align-aux, or the shards of several GPUs after their all-gather): per
@@ -425,16 +442,9 @@ class Context:
 
     # --- resident nodes (no level barrier) ---
     def nodes_open(self, nodes, prm):
-        """nodes as in solve_nodes; returns their handles"""
+        """nodes as in solve_nodes; returns their handles and their (len1, len2)"""
         n = len(nodes)
-        ins = (NodeInput * n)()
-        keep = []
-        for b, (s1, m1, s2, m2) in enumerate(nodes):
-            s1 = np.ascontiguousarray(s1, np.uint32); s2 = np.ascontiguousarray(s2, np.uint32)
-            m1 = np.ascontiguousarray(m1, np.uint8); m2 = np.ascontiguousarray(m2, np.uint8)
-            keep.append((s1, s2, m1, m2))
-            ins[b].n1, ins[b].n2, ins[b].len1, ins[b].len2 = m1.shape[0], m2.shape[0], m1.shape[1], m2.shape[1]
-            ins[b].seq1, ins[b].seq2, ins[b].mask1, ins[b].mask2 = s1.ctypes.data, s2.ctypes.data, m1.ctypes.data, m2.ctypes.data
+        ins, keep = _node_inputs(nodes)
         handles = np.zeros(n, np.uint32)
         check(_nodes_open(self._h, n, ins, C.byref(prm), handles.ctypes.data))
         return [int(h) for h in handles], [(k[2].shape[1], k[3].shape[1]) for k in keep]
@@ -451,19 +461,7 @@ class Context:
         them; at most max_iterations iterations each and, with budget_us, a common stop budget_us microseconds after the
         round began.  Returns (handles of the new nodes, their (len1, len2), finished flags of the old, of the new)."""
         n = len(new_nodes)
-        ins = (NodeInput * max(n, 1))()
-        keep = []
-        for b, node in enumerate(new_nodes):  # (s1, m1, s2, m2) or (s1, m1, s2, m2, p_x, p_y): supplied base-pairing matrices
-            s1, m1, s2, m2 = node[:4]
-            s1 = np.ascontiguousarray(s1, np.uint32); s2 = np.ascontiguousarray(s2, np.uint32)
-            m1 = np.ascontiguousarray(m1, np.uint8); m2 = np.ascontiguousarray(m2, np.uint8)
-            px = np.ascontiguousarray(node[4], np.float32) if len(node) > 4 and node[4] is not None else None
-            py = np.ascontiguousarray(node[5], np.float32) if len(node) > 5 and node[5] is not None else None
-            keep.append((s1, s2, m1, m2, px, py))
-            ins[b].n1, ins[b].n2, ins[b].len1, ins[b].len2 = m1.shape[0], m2.shape[0], m1.shape[1], m2.shape[1]
-            ins[b].seq1, ins[b].seq2, ins[b].mask1, ins[b].mask2 = s1.ctypes.data, s2.ctypes.data, m1.ctypes.data, m2.ctypes.data
-            ins[b].p_x = px.ctypes.data if px is not None else None
-            ins[b].p_y = py.ctypes.data if py is not None else None
+        ins, keep = _node_inputs(new_nodes)
         nh = np.zeros(max(n, 1), np.uint32)
         h = np.ascontiguousarray(old_handles, np.uint32)
         fo = np.zeros(max(len(h), 1), np.uint8); fn = np.zeros(max(n, 1), np.uint8)

@@ -28,6 +28,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <functional>
 #include <iostream>
 #include <map>
 #include <queue>
@@ -290,11 +291,13 @@ void project_alignment(ALN& aln, const ALN& a1, const ALN& a2, const VU& z) {
   }
 }
 
-struct NodeJob {  // flattened child alignments of one node, kept alive across the C call
+struct NodeJob {  // one node: its flattened child alignments and output buffers, and in / out pointing into them (moved, never copied)
   std::vector<uint32_t> s1, s2;
   std::vector<uint8_t> m1, m2;
   std::vector<float> px, py;  // --bp-update: re-estimated base-pairing matrices
   VU x, y, z;
+  dafs_node_input in;
+  dafs_node_output out;
 };
 
 // the `if (use_bp_update_)` blocks of align_alignments(ss, ...), :919-934, and of DAFS::run, :1863-1869: decode the averaged
@@ -316,38 +319,71 @@ void flatten(const ALN& a, std::vector<uint32_t>& s, std::vector<uint8_t>& m) {
   }
 }
 
-// align_alignments for a batch of independent (aln1, aln2) pairs: :896-981
-std::vector<float> solve_batch(dafs_hip_ctx* ctx, const dafs_dd_params& prm, const std::vector<const ALN*>& a1,
-                               const std::vector<const ALN*>& a2, std::vector<ALN>& out, int verbose, bool bp_update) {
-  const size_t nb = a1.size();
-  std::vector<NodeJob> jobs(nb);
-  std::vector<dafs_node_input> in(nb);
-  std::vector<dafs_node_output> res(nb);
-  for (size_t b = 0; b < nb; ++b) {
-    NodeJob& j = jobs[b];
-    flatten(*a1[b], j.s1, j.m1);
-    flatten(*a2[b], j.s2, j.m2);
-    in[b].n1 = (uint32_t)a1[b]->size(); in[b].n2 = (uint32_t)a2[b]->size();
-    in[b].len1 = (uint32_t)(*a1[b])[0].second.size(); in[b].len2 = (uint32_t)(*a2[b])[0].second.size();
-    in[b].seq1 = j.s1.data(); in[b].seq2 = j.s2.data(); in[b].mask1 = j.m1.data(); in[b].mask2 = j.m2.data();
-    j.x.resize(in[b].len1); j.y.resize(in[b].len2); j.z.resize(in[b].len1);
-    res[b].x = j.x.data(); res[b].y = j.y.data(); res[b].z = j.z.data();
+// The node that aligns the flattened alignments j.s1 / j.m1 (left) and j.s2 / j.m2 (right): sizes its output buffers and
+// sets j.in and j.out.  bp_update: both base-pairing matrices re-estimated under the structure decoded from their averages
+// (updated_bp), the top call of the recursion and refine() (align_alignments(ss, ...), :919-934).
+void node_job(dafs_hip_ctx* ctx, NodeJob& j, bool bp_update, float th_s) {
+  const uint32_t n1 = (uint32_t)j.s1.size(), n2 = (uint32_t)j.s2.size(), len1 = (uint32_t)(j.m1.size() / n1),
+                 len2 = (uint32_t)(j.m2.size() / n2);
+  j.x.resize(len1); j.y.resize(len2); j.z.resize(len1);
+  j.in = dafs_node_input{n1, n2, len1, len2, j.s1.data(), j.s2.data(), j.m1.data(), j.m2.data(), nullptr, nullptr};
+  if (bp_update) {
+    updated_bp(ctx, n1, len1, j.s1, j.m1, th_s, j.px);
+    updated_bp(ctx, n2, len2, j.s2, j.m2, th_s, j.py);
+    j.in.p_x = j.px.data(); j.in.p_y = j.py.data();
   }
-  if (bp_update)
-    for (size_t b = 0; b < nb; ++b) {  // refine() goes through align_alignments(ss, ...) too
-      updated_bp(ctx, in[b].n1, in[b].len1, jobs[b].s1, jobs[b].m1, prm.th_s, jobs[b].px);
-      updated_bp(ctx, in[b].n2, in[b].len2, jobs[b].s2, jobs[b].m2, prm.th_s, jobs[b].py);
-      in[b].p_x = jobs[b].px.data(); in[b].p_y = jobs[b].py.data();
+  j.out = dafs_node_output{j.x.data(), j.y.data(), j.z.data(), 0.0f, 0, 0, 0};
+}
+
+// align_alignments of a1 with a2 (:896-981) into out; returns the node's score
+float solve_node(dafs_hip_ctx* ctx, const dafs_dd_params& prm, const ALN& a1, const ALN& a2, ALN& out, int verbose, bool bp_update) {
+  NodeJob j;
+  flatten(a1, j.s1, j.m1);
+  flatten(a2, j.s2, j.m2);
+  node_job(ctx, j, bp_update, prm.th_s);  // refine() goes through align_alignments(ss, ...) too
+  check(dafs_hip_solve_nodes(ctx, 1, &j.in, &prm, &j.out));
+  project_alignment(out, a1, a2, j.z);
+  if (verbose >= 1) std::cerr << "Step: " << j.out.iterations << ", Violated: " << j.out.violated << std::endl;  // :1292
+  return j.out.score;
+}
+
+// The resident-node rounds (dafs_hip_nodes_*; pipeline._solve_nodes is the Python twin).  A round is one call
+// (dafs_hip_nodes_round): the open nodes advance, in opening order, while the nodes take_ready() returns (key, job) are set
+// up and started beside them, and all of them stop together after the round's budget of microseconds, so a node that needs
+// the full iteration budget does not hold back its level and the set-up of new nodes does not stand between two launches.
+// take_ready() is called once per round, after the last round's finished nodes have gone to finish(key, job), which gets
+// every node once, its result in job.out; -v prints its "Step:" line (:1292).  The rounds end when take_ready() returns
+// nothing and no node is open.
+void run_rounds(dafs_hip_ctx* ctx, const dafs_dd_params& prm, int verbose,
+                const std::function<std::vector<std::pair<size_t, NodeJob> >()>& take_ready,
+                const std::function<void(size_t, NodeJob&)>& finish) {
+  const uint32_t round_us = getenv("DAFS_ROUND_US") ? (uint32_t)atoi(getenv("DAFS_ROUND_US")) : 2500u;
+  struct Open { size_t key; uint32_t handle; NodeJob job; };
+  std::vector<Open> open;
+  while (true) {
+    std::vector<std::pair<size_t, NodeJob> > ready = take_ready();
+    const size_t n_old = open.size(), n_new = ready.size();
+    if (!n_old && !n_new) break;
+    // one entry more than the nodes: an empty list passes valid pointers too
+    std::vector<dafs_node_input> in(n_new + 1);
+    std::vector<uint32_t> handles(n_old + n_new + 1);
+    std::vector<uint8_t> fin(n_old + n_new + 1, 0);
+    for (size_t k = 0; k < n_old; ++k) handles[k] = open[k].handle;
+    for (size_t b = 0; b < n_new; ++b) in[b] = ready[b].second.in;
+    check(dafs_hip_nodes_round(ctx, (uint32_t)n_new, in.data(), handles.data() + n_old, (uint32_t)n_old, handles.data(), &prm, 0, round_us,
+                               fin.data(), fin.data() + n_old));
+    for (size_t b = 0; b < n_new; ++b) open.push_back(Open{ready[b].first, handles[n_old + b], std::move(ready[b].second)});
+    std::vector<Open> still;
+    for (size_t k = 0; k < open.size(); ++k) {
+      if (!fin[k]) { still.push_back(std::move(open[k])); continue; }
+      NodeJob& j = open[k].job;
+      check(dafs_hip_nodes_result(ctx, open[k].handle, &j.out));
+      if (verbose >= 1) std::cerr << "Step: " << j.out.iterations << ", Violated: " << j.out.violated << std::endl;  // :1292
+      finish(open[k].key, j);
     }
-  check(dafs_hip_solve_nodes(ctx, (uint32_t)nb, in.data(), &prm, res.data()));
-  std::vector<float> score(nb);
-  out.resize(nb);
-  for (size_t b = 0; b < nb; ++b) {
-    project_alignment(out[b], *a1[b], *a2[b], jobs[b].z);
-    score[b] = res[b].score;
-    if (verbose >= 1) std::cerr << "Step: " << res[b].iterations << ", Violated: " << res[b].violated << std::endl;  // :1292
+    open.swap(still);
   }
-  return score;
+  check(dafs_hip_nodes_close(ctx));
 }
 
 // --fold-aux reader, reference src/fold.cpp:230-259 ("> x" then "i j:p j:p ...", all 1-based)
@@ -797,6 +833,18 @@ int rank_allgather(void* user, const void* send, void* recv, size_t bytes, void*
 int align_group(dafs_hip_ctx* ctx, const Options& o, Ranks& rk, int align_model, const std::vector<std::vector<Fasta> >& fams,
                 const std::vector<size_t>& members, const std::vector<std::ostream*>& out, const std::vector<std::string*>& sto);
 
+struct Guard {  // the context of a run, destroyed however the run ends
+  dafs_hip_ctx* c;
+  ~Guard() { dafs_hip_destroy(c); }
+};
+
+void set_sequences(dafs_hip_ctx* ctx, const std::vector<Fasta>& fa) {
+  std::vector<const char*> seqs;
+  std::vector<uint32_t> lens;
+  for (const Fasta& s : fa) { seqs.push_back(s.seq().c_str()); lens.push_back(s.size()); }
+  check(dafs_hip_set_sequences(ctx, (uint32_t)fa.size(), seqs.data(), lens.data()));
+}
+
 // Phase 1 on this process (:1787-1827; the twin of pipeline._phase1_local) over the context's sequences fa, families
 // [first[f], first[f + 1]): base-pairing probabilities (computed, or --fold-aux), and with two or more sequences the matching
 // probabilities (computed, or --align-aux), -f, the similarity blocks into sim (one n x n block per family, one after
@@ -946,72 +994,47 @@ int run_add(const Options& o, int align_model) {
     fa.push_back(Fasta(snames[r], sq));
   }
   fa.insert(fa.end(), added.begin(), added.end());
-  const uint32_t N = m + k;
 
   dafs_hip_ctx* ctx = nullptr;
   check(dafs_hip_create(o.device, &ctx));
-  struct Guard { dafs_hip_ctx* c; ~Guard() { dafs_hip_destroy(c); } } guard{ctx};
-  std::vector<const char*> seqs(N);
-  std::vector<uint32_t> lens(N);
-  for (uint32_t i = 0; i < N; ++i) { seqs[i] = fa[i].seq().c_str(); lens[i] = fa[i].size(); }
-  check(dafs_hip_set_sequences(ctx, N, seqs.data(), lens.data()));
+  Guard guard{ctx};
+  set_sequences(ctx, fa);
   std::vector<float> sim;
-  phase1_local(ctx, o, align_model, fa, {0, N}, sim);
+  phase1_local(ctx, o, align_model, fa, {0, m + k}, sim);
 
-  // the k nodes: opened in the first round, then advanced round after round until every one has finished
+  // the k nodes: all opened in the first round
   dafs_dd_params prm = dd_params_of(o);
   prm.skip_uncoupled_folds = o.verbose == 0 ? 1 : 0;  // as the progressive loop of a run without -r
-  const uint32_t kRoundUs = getenv("DAFS_ROUND_US") ? (uint32_t)atoi(getenv("DAFS_ROUND_US")) : 2500u;
-  std::vector<NodeJob> jobs(k);
-  std::vector<dafs_node_input> in(k);
-  std::vector<uint32_t> seed_idx(m);
+  std::vector<uint32_t> seed_idx(m), lens(k);
   for (uint32_t r = 0; r < m; ++r) seed_idx[r] = r;
-  for (uint32_t j = 0; j < k; ++j) {
-    NodeJob& jb = jobs[j];
-    jb.s1.assign(1, m + j);
-    jb.m1.assign(lens[m + j], 1);
-    jb.s2 = seed_idx;
-    jb.m2 = smask;
-    jb.x.resize(lens[m + j]); jb.y.resize(C); jb.z.resize(lens[m + j]);
-    in[j].n1 = 1; in[j].n2 = m; in[j].len1 = lens[m + j]; in[j].len2 = C;
-    in[j].seq1 = jb.s1.data(); in[j].seq2 = jb.s2.data(); in[j].mask1 = jb.m1.data(); in[j].mask2 = jb.m2.data();
-  }
-  std::vector<uint32_t> handle(k), open_ids;  // open_ids: the nodes still running, in handle order
-  std::vector<uint8_t> fin(k, 0);
-  uint8_t none = 0;  // the finished flags and handles of an empty list
-  uint32_t none_handle = 0;
-  check(dafs_hip_nodes_round(ctx, k, in.data(), handle.data(), 0, nullptr, &prm, 0, kRoundUs, &none, fin.data()));
-  for (uint32_t j = 0; j < k; ++j) open_ids.push_back(j);
-  while (true) {
-    std::vector<uint32_t> still;
-    for (size_t b = 0; b < open_ids.size(); ++b) {
-      const uint32_t j = open_ids[b];
-      if (!fin[b]) { still.push_back(j); continue; }
-      dafs_node_output r;
-      r.x = jobs[j].x.data(); r.y = jobs[j].y.data(); r.z = jobs[j].z.data();
-      check(dafs_hip_nodes_result(ctx, handle[j], &r));
-      if (o.verbose >= 1) std::cerr << "Step: " << r.iterations << ", Violated: " << r.violated << std::endl;  // :1292
+  for (uint32_t j = 0; j < k; ++j) lens[j] = added[j].size();
+  std::vector<VU> zs(k);
+  bool opened = false;
+  run_rounds(ctx, prm, o.verbose, [&]() {
+    std::vector<std::pair<size_t, NodeJob> > ready(opened ? 0 : k);
+    for (uint32_t j = 0; j < ready.size(); ++j) {
+      NodeJob& jb = ready[j].second;
+      ready[j].first = j;
+      jb.s1.assign(1, m + j);
+      jb.m1.assign(lens[j], 1);
+      jb.s2 = seed_idx;
+      jb.m2 = smask;
+      node_job(ctx, jb, false, prm.th_s);
     }
-    open_ids.swap(still);
-    if (open_ids.empty()) break;
-    std::vector<uint32_t> old_handles;
-    for (uint32_t j : open_ids) old_handles.push_back(handle[j]);
-    fin.assign(open_ids.size(), 0);
-    check(dafs_hip_nodes_round(ctx, 0, in.data(), &none_handle, (uint32_t)old_handles.size(), old_handles.data(), &prm, 0, kRoundUs, fin.data(),
-                               &none));
-  }
-  check(dafs_hip_nodes_close(ctx));
+    opened = true;
+    return ready;
+  }, [&](size_t j, NodeJob& jb) { zs[j].swap(jb.z); });
 
   // the merge; the rows new sequences (file order), then seed rows (seed order)
   std::vector<uint32_t> z, seed_col(C), res_col;
-  for (uint32_t j = 0; j < k; ++j) z.insert(z.end(), jobs[j].z.begin(), jobs[j].z.end());
+  for (uint32_t j = 0; j < k; ++j) z.insert(z.end(), zs[j].begin(), zs[j].end());
   res_col.resize(z.size() ? z.size() : 1);
   uint32_t width = 0;
-  check(dafs_host_merge_added(C, k, lens.data() + m, z.data(), seed_col.data(), res_col.data(), &width));
+  check(dafs_host_merge_added(C, k, lens.data(), z.data(), seed_col.data(), res_col.data(), &width));
   ALN root;
-  for (uint32_t j = 0, off = 0; j < k; off += lens[m + j], ++j) {
+  for (uint32_t j = 0, off = 0; j < k; off += lens[j], ++j) {
     std::vector<bool> msk(width, false);
-    for (uint32_t i = 0; i < lens[m + j]; ++i) msk[res_col[off + i]] = true;
+    for (uint32_t i = 0; i < lens[j]; ++i) msk[res_col[off + i]] = true;
     root.push_back(std::make_pair(m + j, msk));
   }
   for (uint32_t r = 0; r < m; ++r) {
@@ -1069,7 +1092,7 @@ int run(const Options& o, Ranks& rk) {
 
   dafs_hip_ctx* ctx = nullptr;
   check(dafs_hip_create(o.devices.empty() ? o.device : o.devices[rk.rank], &ctx));
-  struct Guard { dafs_hip_ctx* c; ~Guard() { dafs_hip_destroy(c); } } guard{ctx};
+  Guard guard{ctx};
 
   // --stockholm: one block per input file, in input order, written by the process that prints
   std::vector<std::string> sto_blocks(o.stockholm.empty() ? 0 : o.inputs.size());
@@ -1130,10 +1153,7 @@ int align_group(dafs_hip_ctx* ctx, const Options& o, Ranks& rk, int align_model,
     first.push_back((uint32_t)fa.size());
   }
   const uint N = (uint)fa.size();
-  std::vector<const char*> seqs(N);
-  std::vector<uint32_t> lens(N);
-  for (uint i = 0; i < N; ++i) { seqs[i] = fa[i].seq().c_str(); lens[i] = fa[i].size(); }
-  check(dafs_hip_set_sequences(ctx, N, seqs.data(), lens.data()));
+  set_sequences(ctx, fa);
   if (F > 1) check(dafs_hip_set_families(ctx, F, first.data()));
 
   const bool sharded = !o.devices.empty() && N > 1;
@@ -1177,92 +1197,45 @@ int align_group(dafs_hip_ctx* ctx, const Options& o, Ranks& rk, int align_model,
   dafs_dd_params prm_prog = prm;
   prm_prog.skip_uncoupled_folds = (o.refinement == 0 && o.verbose == 0) ? 1 : 0;
   // The forest of the families' guide trees, one node array: family f's node i is tbase[f] + i, its leaf i the sequence
-  // first[f] + i.  A node is ready when both of its children are done, whatever its family.
+  // first[f] + i.  A node is ready when both of its children are done, whatever its family; the ready nodes of every
+  // family share each round (run_rounds).
   std::vector<size_t> tbase(F + 1, 0);
   for (uint f = 0; f < F; ++f) tbase[f + 1] = tbase[f] + trees[f].size();
   std::vector<ALN> aln(tbase[F]);
-  std::vector<bool> done(tbase[F], false);
+  std::vector<bool> done(tbase[F], false), opened(tbase[F], false);
   for (uint f = 0; f < F; ++f)
     for (uint i = 0; i < first[f + 1] - first[f]; ++i) {
       aln[tbase[f] + i].push_back(std::make_pair(first[f] + i, std::vector<bool>(fa[first[f] + i].size(), true)));
       done[tbase[f] + i] = true;
     }
   std::vector<float> score(F, 0.0f);
-  {
-    // The nodes stay resident on the device (dafs_hip_nodes_*).  A round is one call (dafs_hip_nodes_round): the open
-    // nodes advance while the nodes whose children have just finished are set up and started beside them, and all of
-    // them stop together after kRoundUs microseconds, so a node that needs the full iteration budget does not hold
-    // back its level and the set-up of new nodes does not stand between two launches.
-    const uint32_t kRoundUs = getenv("DAFS_ROUND_US") ? (uint32_t)atoi(getenv("DAFS_ROUND_US")) : 2500u;
-    struct Open { uint fam; uint node; uint32_t handle; NodeJob job; };  // node: index within the family's tree
-    std::vector<Open> open;
-    size_t remaining = tbase[F] - N;
-    std::vector<bool> opened(tbase[F], false);
-    while (remaining) {
-      std::vector<std::pair<uint, uint> > ready;  // (family, node)
-      for (uint f = 0; f < F; ++f) {
-        const std::vector<node_t>& tree = trees[f];
-        const size_t tb = tbase[f];
-        for (uint i = first[f + 1] - first[f]; i < tree.size(); ++i)
-          if (!done[tb + i] && !opened[tb + i] && done[tb + tree[i].second.first] && done[tb + tree[i].second.second]) ready.push_back(std::make_pair(f, i));
+  run_rounds(ctx, prm_prog, o.verbose, [&]() {
+    std::vector<std::pair<size_t, NodeJob> > ready;
+    for (uint f = 0; f < F; ++f) {
+      const std::vector<node_t>& tree = trees[f];
+      const size_t tb = tbase[f];
+      for (uint i = first[f + 1] - first[f]; i < tree.size(); ++i) {
+        const size_t l = tb + tree[i].second.first, r = tb + tree[i].second.second;
+        if (done[tb + i] || opened[tb + i] || !done[l] || !done[r]) continue;
+        opened[tb + i] = true;
+        ready.emplace_back(tb + i, NodeJob());
+        NodeJob& j = ready.back().second;
+        flatten(aln[l], j.s1, j.m1);
+        flatten(aln[r], j.s2, j.m2);
+        node_job(ctx, j, o.bp_update && i == tree.size() - 1, prm.th_s);  // --bp-update: the top call of the recursion
       }
-      const size_t n_old = open.size();
-      std::vector<dafs_node_input> in(ready.size() ? ready.size() : 1);
-      for (size_t b = 0; b < ready.size(); ++b) {
-        open.push_back(Open{ready[b].first, ready[b].second, 0, NodeJob()});
-        opened[tbase[ready[b].first] + ready[b].second] = true;
-      }
-      for (size_t b = 0; b < ready.size(); ++b) {
-        const std::vector<node_t>& tree = trees[ready[b].first];
-        const size_t tb = tbase[ready[b].first];
-        const ALN &a1 = aln[tb + tree[ready[b].second].second.first], &a2 = aln[tb + tree[ready[b].second].second.second];
-        NodeJob& j = open[n_old + b].job;
-        flatten(a1, j.s1, j.m1);
-        flatten(a2, j.s2, j.m2);
-        in[b].n1 = (uint32_t)a1.size(); in[b].n2 = (uint32_t)a2.size();
-        in[b].len1 = (uint32_t)a1[0].second.size(); in[b].len2 = (uint32_t)a2[0].second.size();
-        in[b].seq1 = j.s1.data(); in[b].seq2 = j.s2.data(); in[b].mask1 = j.m1.data(); in[b].mask2 = j.m2.data();
-        j.x.resize(in[b].len1); j.y.resize(in[b].len2); j.z.resize(in[b].len1);
-        if (o.bp_update && ready[b].second == tree.size() - 1) {
-          // the top call of the recursion re-estimates both base-pairing matrices under the structure decoded from
-          // their averages (align_alignments(ss, ...), :919-934)
-          j.px.resize((size_t)in[b].len1 * in[b].len1);
-          j.py.resize((size_t)in[b].len2 * in[b].len2);
-          updated_bp(ctx, in[b].n1, in[b].len1, j.s1, j.m1, prm.th_s, j.px);
-          updated_bp(ctx, in[b].n2, in[b].len2, j.s2, j.m2, prm.th_s, j.py);
-          in[b].p_x = j.px.data(); in[b].p_y = j.py.data();
-        }
-      }
-      std::vector<uint32_t> old_handles(n_old ? n_old : 1), new_handles(ready.size() ? ready.size() : 1);
-      std::vector<uint8_t> fin(open.size() ? open.size() : 1, 0);
-      for (size_t k = 0; k < n_old; ++k) old_handles[k] = open[k].handle;
-      check(dafs_hip_nodes_round(ctx, (uint32_t)ready.size(), in.data(), new_handles.data(), (uint32_t)n_old, old_handles.data(), &prm_prog, 0,
-                                 kRoundUs, fin.data(), fin.data() + n_old));
-      for (size_t b = 0; b < ready.size(); ++b) open[n_old + b].handle = new_handles[b];
-      std::vector<Open> still;
-      for (size_t k = 0; k < open.size(); ++k) {
-        if (!fin[k]) { still.push_back(std::move(open[k])); continue; }
-        Open& o1 = open[k];
-        dafs_node_output r;
-        r.x = o1.job.x.data(); r.y = o1.job.y.data(); r.z = o1.job.z.data();
-        check(dafs_hip_nodes_result(ctx, o1.handle, &r));
-        const std::vector<node_t>& tree = trees[o1.fam];
-        const size_t tb = tbase[o1.fam];
-        const size_t l = tb + tree[o1.node].second.first, rr = tb + tree[o1.node].second.second;
-        ALN merged;
-        project_alignment(merged, aln[l], aln[rr], o1.job.z);
-        aln[tb + o1.node].swap(merged);
-        done[tb + o1.node] = true;
-        ALN().swap(aln[l]);
-        ALN().swap(aln[rr]);
-        if (o.verbose >= 1) std::cerr << "Step: " << r.iterations << ", Violated: " << r.violated << std::endl;  // :1292
-        if (o1.node == tree.size() - 1) score[o1.fam] = r.score;
-        --remaining;
-      }
-      open.swap(still);
     }
-    check(dafs_hip_nodes_close(ctx));
-  }
+    return ready;
+  }, [&](size_t g, NodeJob& j) {
+    const uint f = (uint)(std::upper_bound(tbase.begin(), tbase.end(), g) - tbase.begin()) - 1;
+    const node_t& nd = trees[f][g - tbase[f]];
+    const size_t l = tbase[f] + nd.second.first, r = tbase[f] + nd.second.second;
+    project_alignment(aln[g], aln[l], aln[r], j.z);
+    done[g] = true;
+    ALN().swap(aln[l]);
+    ALN().swap(aln[r]);
+    if (g == tbase[f + 1] - 1) score[f] = j.out.score;
+  });
   for (uint f = 0; f < F; ++f) {
     ALN& root = aln[tbase[f + 1] - 1];
     float s = score[f];
@@ -1289,9 +1262,9 @@ int align_group(dafs_hip_ctx* ctx, const Options& o, Ranks& rk, int align_model,
             for (uint j = 0; j != n; ++j) part[g][j].second.push_back(root[group[g][j]].second[k]);
         }
       }
-      std::vector<ALN> merged;
-      const std::vector<float> sc = solve_batch(ctx, prm, {&part[0]}, {&part[1]}, merged, o.verbose, o.bp_update);
-      if (sc[0] > s) { s = sc[0]; root.swap(merged[0]); }
+      ALN merged;
+      const float sc = solve_node(ctx, prm, part[0], part[1], merged, o.verbose, o.bp_update);
+      if (sc > s) { s = sc; root.swap(merged); }
     }
 
     std::string tree_line;

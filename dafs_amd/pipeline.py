@@ -4,6 +4,7 @@ done by libdafs_hip.so on the GPU; this file only holds the guide tree, the alig
 (project_alignment) and the output format.  The C++ `dafs` executable (dafs_amd/csrc/cli_main.cpp)
 is the same logic for the drop-in command line."""
 import heapq
+import inspect
 import os
 import sys
 
@@ -97,8 +98,8 @@ def run(names, seqs, ctx=None, bp=None, w=4.0, eta0=0.5, t_max=600, w_pct_a=0.25
     finishes the run and holds the same result.  reliability: the result also gets .reliability and .stockholm (see
     _phase2_forest)."""
     import time
-    # combinations this driver does not implement are refused, not ignored (the command line, cli_main.cpp, covers
-    # --bp-update with level batches through its own solve_batch)
+    # combinations this driver does not implement are refused, not ignored (the command line, cli_main.cpp, has no level
+    # batches: its --bp-update runs in the resident-node rounds and in the refinement's solve_node)
     if level_sync and bp_update:
         raise ValueError("pipeline.run: bp_update needs the resident-node schedule (level_sync=False)")
     if shard is not None and (bp is not None or mp is not None or w_pct_f != 0.0):
@@ -108,7 +109,6 @@ def run(names, seqs, ctx=None, bp=None, w=4.0, eta0=0.5, t_max=600, w_pct_a=0.25
     if own:
         ctx = capi.Context(0)
     t = [time.perf_counter()]
-    n = len(seqs)
     if shard is not None:
         from . import dist as ddist
         ddist.phase1_sharded(ctx, seqs, shard[0], shard[1], align_model, th_a, w_pct_a, w_pct_s)
@@ -118,8 +118,9 @@ def run(names, seqs, ctx=None, bp=None, w=4.0, eta0=0.5, t_max=600, w_pct_a=0.25
         sim = _phase1_local(ctx, seqs, bp, mp, align_model, th_a, w_pct_a, w_pct_s, t, w_pct_f)
     score, left, right = capi.build_tree(sim)  # same code as the command line (build_tree below is its Python twin, kept for the CPU tests)
     t.append(time.perf_counter())
-    return _phase2(ctx, own, names, seqs, n, sim, score, left, right, t, w, eta0, t_max, th_a, th_s, th_s1, force_iters, level_sync, slice_iters,
-                   skip_uncoupled_folds, round_us, bp_update, bp_update1, reliability)
+    fam = dict(names=names, seqs=seqs, first=0, sim=sim, tree=(score, left, right))
+    return _phase2_forest(ctx, own, [fam], t, w, eta0, t_max, th_a, th_s, th_s1, force_iters, level_sync, slice_iters,
+                          skip_uncoupled_folds, round_us, bp_update, bp_update1, reliability)[0]
 
 
 def _phase1_local(ctx, seqs, bp, mp, align_model, th_a, w_pct_a, w_pct_s, t, w_pct_f=0.0, first=None):
@@ -172,11 +173,47 @@ def forest_ready(trees, pending, done):
     return [(f, i) for f, i in pending if (f, trees[f][0][i]) in done and (f, trees[f][1][i]) in done]
 
 
-def _phase2(ctx, own, names, seqs, n, sim, score, left, right, t, w, eta0, t_max, th_a, th_s, th_s1, force_iters, level_sync, slice_iters,
-            skip_uncoupled_folds, round_us=None, bp_update=False, bp_update1=False, reliability=False):
-    fam = dict(names=names, seqs=seqs, first=0, sim=sim, tree=(score, left, right))
-    return _phase2_forest(ctx, own, [fam], t, w, eta0, t_max, th_a, th_s, th_s1, force_iters, level_sync, slice_iters,
-                          skip_uncoupled_folds, round_us, bp_update, bp_update1, reliability)[0]
+def _solve_nodes(ctx, prm, take_ready, finish, level_sync=False, slice_iters=None, round_us=None):
+    """The node schedule of _phase2_forest and add.  take_ready() returns [(key, node)] for the nodes that have just become
+    ready (node: a Context.solve_nodes tuple); it is called once per level or round, after the last one's finished nodes
+    have gone to finish(key, out, dims) (dims: (len1, len2), None in level mode).  level_sync: one blocking solve_nodes call
+    per batch.  Otherwise the nodes stay resident and a round is one Context.nodes_round call, old handles in key order,
+    that ends after round_us microseconds or slice_iters iterations of every node (results do not depend on the cut).
+    Returns (levels, per round (seconds from take_ready() to the end of the call, [(key, len1, len2)]), nodes_memory(),
+    nodes_demotions()); in level mode the last three are [], None, None."""
+    import time
+    if level_sync:
+        levels = 0
+        while True:
+            ready = take_ready()
+            if not ready:
+                return levels, [], None, None
+            for (k, _), o in zip(ready, ctx.solve_nodes([node for _, node in ready], prm)):
+                finish(k, o, None)
+            levels += 1
+    if slice_iters is None and round_us is None:
+        round_us = int(os.environ.get("DAFS_ROUND_US", "2500"))
+    open_nodes = {}  # key -> (handle, len1, len2)
+    rounds = []
+    while True:
+        t_round = time.perf_counter()
+        ready = take_ready()
+        if not ready and not open_nodes:
+            break
+        ids, new = sorted(open_nodes), [k for k, _ in ready]
+        hs, dims, fin_old, fin_new = ctx.nodes_round([node for _, node in ready], [open_nodes[k][0] for k in ids], prm, slice_iters or 0,
+                                                     round_us or 0)
+        for k, h, d in zip(new, hs, dims):
+            open_nodes[k] = (h, d[0], d[1])
+        rounds.append((time.perf_counter() - t_round, [(k, open_nodes[k][1], open_nodes[k][2]) for k in ids + new]))
+        for k, fin in list(zip(ids, fin_old)) + list(zip(new, fin_new)):
+            if fin:
+                h, l1, l2 = open_nodes.pop(k)
+                finish(k, ctx.nodes_result(h, l1, l2), (l1, l2))
+    memory = ctx.nodes_memory()  # (reserved, in use, peak) bytes of the resident nodes
+    demotions = ctx.nodes_demotions()  # split nodes that lost their folders (0 on an undisturbed device)
+    ctx.nodes_close()
+    return len(rounds), rounds, memory, demotions
 
 
 def _phase2_forest(ctx, own, fams, t, w, eta0, t_max, th_a, th_s, th_s1, force_iters, level_sync, slice_iters,
@@ -213,10 +250,34 @@ def _phase2_forest(ctx, own, fams, t, w, eta0, t_max, th_a, th_s, th_s1, force_i
         pending += [(f, i) for i in range(n, 2 * n - 1)]
     done = set(aln)
 
-    def key(f, i):  # node names in the diagnostics: the plain node index for one family
+    def key(f, i):  # node names in the diagnostics and keys of the schedule: the plain node index for one family
         return i if nf == 1 else (f, i)
 
-    def finish(f, i, o, dims=None):
+    def node_input(f, i):
+        left, right = trees[f]
+        a1, a2 = aln[(f, left[i])], aln[(f, right[i])]
+        if bp_update and i == 2 * len(fams[f]["seqs"]) - 2:
+            # --bp-update: the top call of the recursion (DAFS::align(ss, aln, root), dafs.cpp:1518-1537) re-estimates
+            # both base-pairing matrices under the structure decoded from their averages (:919-934)
+            upd = []
+            for s_idx, msk in (a1, a2):
+                _, ss0, _ = ctx.consensus_structure(s_idx, msk, th_s)
+                upd.append(ctx.update_basepairing(s_idx, msk, ss0))
+            return (a1[0], a1[1], a2[0], a2[1], upd[0], upd[1])
+        return (a1[0], a1[1], a2[0], a2[1])
+
+    def take_ready():
+        nonlocal pending
+        ready = forest_ready(trees, pending, done)
+        if ready and trace and not level_sync:
+            print("open", [(key(f, i), aln[(f, trees[f][0][i])][1].shape, aln[(f, trees[f][1][i])][1].shape) for f, i in ready],
+                  file=sys.stderr, flush=True)
+        rs = set(ready)
+        pending = [q for q in pending if q not in rs]
+        return [(key(f, i), node_input(f, i)) for f, i in ready]
+
+    def finish(k, o, dims):
+        f, i = (0, k) if nf == 1 else k
         left, right = trees[f]
         aln[(f, i)] = project_alignment(aln[(f, left[i])], aln[(f, right[i])], o["z"])
         done.add((f, i))
@@ -225,75 +286,18 @@ def _phase2_forest(ctx, own, fams, t, w, eta0, t_max, th_a, th_s, th_s1, force_i
             results[f].dd_dims[i] = dims
         del aln[(f, left[i])], aln[(f, right[i])]
 
-    # progressive phase.  level_sync: solve every node whose children are ready, level by level (one blocking
-    # call per level).  Otherwise the nodes stay resident on the device and every round advances all open
-    # nodes by at most `slice_iters` iterations in one launch: a node that needs 600 iterations no longer
-    # holds back the parents of its level-mates.  Same results either way.
-    # only the alignment z of a node is consumed here (DAFS::align_alignments, dafs.cpp:896-912), so nodes that have no
-    # consensus base pair to couple their subproblems need not run their two folding DPs (dafs_dd_params doc)
+    # progressive phase (_solve_nodes).  Only the alignment z of a node is consumed here (DAFS::align_alignments,
+    # dafs.cpp:896-912), so nodes that have no consensus base pair to couple their subproblems need not run their two
+    # folding DPs (dafs_dd_params doc)
     prm = capi.dd_params(w=w, eta0=eta0, th_a=th_a, th_s=th_s, t_max=t_max, force_iters=force_iters,
                          skip_uncoupled_folds=1 if skip_uncoupled_folds else 0)
     trace = os.environ.get("DAFS_PIPELINE_TRACE") == "1"  # node shapes on stderr as they are opened (diagnostics)
-    levels = 0
-    rounds = []
-    if level_sync:
-        while pending:
-            ready = forest_ready(trees, pending, done)
-            outs = ctx.solve_nodes([(aln[(f, trees[f][0][i])][0], aln[(f, trees[f][0][i])][1],
-                                     aln[(f, trees[f][1][i])][0], aln[(f, trees[f][1][i])][1]) for f, i in ready], prm)
-            for (f, i), o in zip(ready, outs):
-                finish(f, i, o)
-            rs = set(ready)
-            pending = [q for q in pending if q not in rs]
-            levels += 1
-    else:
-        # A round = one call: the open nodes advance while the nodes whose children finished in the last round are set up
-        # and started beside them (Context.nodes_round).  A round ends after `round_us` microseconds (all its nodes stop at
-        # the next iteration end) or, when slice_iters is given, after that many iterations of every node (tests cut the
-        # loop in many ways: the results do not depend on it).
-        if slice_iters is None and round_us is None:
-            round_us = int(os.environ.get("DAFS_ROUND_US", "2500"))
-        open_nodes = {}  # (family, node) -> (handle, len1, len2)
-        while pending or open_nodes:
-            ready = forest_ready(trees, pending, done)
-            if ready and trace:
-                print("open", [(key(f, i), aln[(f, trees[f][0][i])][1].shape, aln[(f, trees[f][1][i])][1].shape) for f, i in ready],
-                      file=sys.stderr, flush=True)
-            rs = set(ready)
-            pending = [q for q in pending if q not in rs]
-            ids = sorted(open_nodes)
-            t_round = time.perf_counter()
-
-            def node_input(f, i):
-                left, right = trees[f]
-                a1, a2 = aln[(f, left[i])], aln[(f, right[i])]
-                if bp_update and i == 2 * len(fams[f]["seqs"]) - 2:
-                    # --bp-update: the top call of the recursion (DAFS::align(ss, aln, root), dafs.cpp:1518-1537) re-estimates
-                    # both base-pairing matrices under the structure decoded from their averages (:919-934)
-                    upd = []
-                    for s_idx, msk in (a1, a2):
-                        _, ss0, _ = ctx.consensus_structure(s_idx, msk, th_s)
-                        upd.append(ctx.update_basepairing(s_idx, msk, ss0))
-                    return (a1[0], a1[1], a2[0], a2[1], upd[0], upd[1])
-                return (a1[0], a1[1], a2[0], a2[1])
-            hs, dims, fin_old, fin_new = ctx.nodes_round([node_input(f, i) for f, i in ready],
-                                                         [open_nodes[q][0] for q in ids], prm, slice_iters or 0, round_us or 0)
-            for q, h, d in zip(ready, hs, dims):
-                open_nodes[q] = (h, d[0], d[1])
-            rounds.append((time.perf_counter() - t_round, [(key(*q), open_nodes[q][1], open_nodes[q][2]) for q in ids + ready]))
-            for q, fin in list(zip(ids, fin_old)) + list(zip(ready, fin_new)):
-                if not fin:
-                    continue
-                h, l1, l2 = open_nodes.pop(q)
-                finish(q[0], q[1], ctx.nodes_result(h, l1, l2), (l1, l2))
-            levels += 1
-        dd_memory = ctx.nodes_memory()  # (reserved, in use, peak) bytes of the resident nodes
-        dd_demotions = ctx.nodes_demotions()  # split nodes that lost their folders (0 on an undisturbed device)
+    levels, rounds, dd_memory, dd_demotions = _solve_nodes(ctx, prm, take_ready, finish, level_sync, slice_iters, round_us)
+    if not level_sync:
         for res in results:
             res.dd_memory = dd_memory
             res.dd_demotions = dd_demotions
             res.skip_uncoupled_folds = bool(skip_uncoupled_folds)  # nodes without consensus pairs then carry no folding arrays
-        ctx.nodes_close()
     t.append(time.perf_counter())
     th1 = th_s if th_s1 is None else th_s1
     for f, (fm, res) in enumerate(zip(fams, results)):
@@ -379,24 +383,13 @@ def add(seed_names, seed_rows, names, seqs, ctx=None, w=4.0, eta0=0.5, t_max=600
         prm = capi.dd_params(w=w, eta0=eta0, th_a=th_a, th_s=th_s, t_max=t_max, force_iters=force_iters,
                              skip_uncoupled_folds=1 if skip_uncoupled_folds else 0)
         seed_idx = np.arange(m, dtype=np.uint32)
-        new = [(np.array([m + j], np.uint32), np.ones((1, len(seqs[j])), np.uint8), seed_idx, seed_mask) for j in range(k)]
-        new_ids = list(range(k))
-        if slice_iters is None and round_us is None:
-            round_us = int(os.environ.get("DAFS_ROUND_US", "2500"))
+        new = [(j, (np.array([m + j], np.uint32), np.ones((1, len(seqs[j])), np.uint8), seed_idx, seed_mask)) for j in range(k)]
         outs = [None] * k
-        open_nodes = {}  # j -> (handle, len1, len2)
-        while new or open_nodes:  # as the resident-node loop of _phase2_forest; every node is ready in the first round
-            ids = sorted(open_nodes)
-            hs, dims, fin_old, fin_new = ctx.nodes_round(new, [open_nodes[j][0] for j in ids], prm, slice_iters or 0, round_us or 0)
-            for j, h, d in zip(new_ids, hs, dims):
-                open_nodes[j] = (h, d[0], d[1])
-            for j, fin in list(zip(ids, fin_old)) + list(zip(new_ids, fin_new)):
-                if fin:
-                    h, l1, l2 = open_nodes.pop(j)
-                    outs[j] = ctx.nodes_result(h, l1, l2)
-            new, new_ids = [], []
-        dd_memory = ctx.nodes_memory()
-        ctx.nodes_close()
+        batches = iter([new])  # every node is ready in the first round, none later
+
+        def finish(j, o, dims):
+            outs[j] = o
+        _, _, dd_memory, _ = _solve_nodes(ctx, prm, lambda: next(batches, []), finish, slice_iters=slice_iters, round_us=round_us)
         t.append(time.perf_counter())
         # the merge, then the rows in the order new sequences, seed rows (the sidx of a run that joins a leaf last)
         seed_col, res_col, width = capi.merge_added(seed_mask.shape[1], [o["z"] for o in outs])
@@ -472,9 +465,7 @@ def run_batch(families, ctx=None, max_bytes=None, **kw):
             raise ValueError("pipeline.run_batch: %s is a single-family option (use run)" % k)
     if kw.get("level_sync") and kw.get("bp_update"):
         raise ValueError("pipeline.run_batch: bp_update needs the resident-node schedule (level_sync=False)")
-    opts = dict(w=4.0, eta0=0.5, t_max=600, w_pct_a=0.25, w_pct_s=0.25, th_a=0.01, th_s=0.2, th_s1=None, align_model=capi.ALIGN_PROBCONS,
-                force_iters=0, timers=None, level_sync=False, slice_iters=None, skip_uncoupled_folds=True, round_us=None, w_pct_f=0.0,
-                bp_update=False, bp_update1=False, reliability=False)
+    opts = {k: p.default for k, p in inspect.signature(run).parameters.items() if k not in ("names", "seqs", "ctx", "bp", "mp", "shard")}
     unknown = set(kw) - set(opts)
     if unknown:
         raise TypeError("pipeline.run_batch: unknown options %s" % sorted(unknown))
