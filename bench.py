@@ -16,9 +16,12 @@ to the ranks by cost, each rank runs its shard, and the sparse posteriors are ex
 (the only collective of the path).  --scaling weak grows the set by sqrt(N) instead (~8128 pairs per GPU);
 --config c2|c3|c4|c5 picks another BASELINE configuration (c4 = N=256, L~200, the multi-GPU config).
 
-Prints ONE JSON line on rank 0 (contract in the task description) with two extra objects:
-"roofline" (algorithmic bytes / kernel time against the 8 TB/s HBM peak) and "cpu_baseline"
-(the CPU path timed on this box's host cores on a bounded sample of the same pairs).
+Prints ONE JSON line on rank 0 with the headline figure and a "roofline" object (algorithmic bytes / kernel time of the
+timed steps against the 8 TB/s HBM peak).  A plain run does only what that line needs: set up, warm up, time the steps,
+write --dump-outputs, print.  --full adds every other leg, each reported beside the headline figure: "cpu_baseline" (the
+CPU path timed on the host cores on a bounded sample of the same pairs), the check of the last timed launch against the
+oracle ("verified_pairs") and, with several ranks, of the exchanged slabs, the end-to-end wall-clock runs, the per-stage
+device times ("stages") and the forced-iteration DD run.  --no-cpu, --no-e2e and --no-verify leave legs out of a --full run.
 """
 import argparse
 import ctypes as C
@@ -292,10 +295,13 @@ def main():
     ap.add_argument("--length", type=int, default=0, help="override the nominal length")
     ap.add_argument("--th", type=float, default=0.01)
     ap.add_argument("--model", choices=("probcons", "contralign"), default="probcons", help="alignment model of the timed kernel")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--no-verify", action="store_true", help="tuning builds only (tools/build_exp.sh: kernels that stop after a sweep): skip the check of the "
-                    "timed launch against the oracle; the JSON line then says verified_pairs 0")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the end-to-end wall-clock legs (warm driver run, cold CLI, forced-iteration DD run)")
+    ap.add_argument("--full", action="store_true", help="also run every leg beside the headline figure: CPU baseline, check against the "
+                    "oracle (and of the exchange), end-to-end runs, per-stage device times, forced-iteration DD run")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the cpu_baseline leg")
+    ap.add_argument("--no-verify", action="store_true", help="--full, tuning builds only (tools/build_exp.sh: kernels that stop after a sweep): "
+                    "skip the check of the timed launch against the oracle; the JSON line then says verified_pairs 0")
+    ap.add_argument("--no-e2e", action="store_true", help="--full: skip the end-to-end wall-clock legs (warm driver run, cold CLI, "
+                    "forced-iteration DD run, per-stage device times; the sharded phase 1 with several ranks)")
     ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/*.npy (one GPU only; see dump_outputs)")
     args = ap.parse_args()
     if args.steps < 1:
@@ -315,15 +321,15 @@ def main():
     names, seqs, lens, px, py, total_pairs = build_shard(n_seq, args.length, world, rank)
     np_local = len(px)
 
-    # ---- CPU legs first: they fork worker processes, which must happen before this process touches the GPU ----
+    # ---- --full: CPU legs first: they fork worker processes, which must happen before this process touches the GPU ----
     cpu = cpu_e2e = cli = None
     cpu_out = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         cpu = cpu_baseline(seqs, px, py, args.th, 1 if contra else 0, args.length)
         if not args.no_e2e:
             cpu_e2e, cpu_out = cpu_end_to_end(names, seqs, 1 if contra else 0)
             cpu["end_to_end"] = cpu_e2e
-    if rank == 0 and world == 1 and not args.no_e2e:
+    if args.full and rank == 0 and world == 1 and not args.no_e2e:
         cli = cold_cli(names, seqs, contra)  # a child process with a GPU context of its own
 
     import torch
@@ -484,9 +490,9 @@ def main():
     if args.dump_outputs:
         dumped = dump_outputs(args.dump_outputs, lens, px, py, args.th, rp_off, sets[(nstep[0] - 1) % nsets])
 
-    # ---- the timed call path against the oracle: a strided sample of the last launch's outputs, bit for bit ----
-    verified = 0
-    if rank == 0 and not args.no_verify:
+    # ---- --full: the timed call path against the oracle: a strided sample of the last launch's outputs, bit for bit ----
+    verified = 0 if args.full else None
+    if args.full and rank == 0 and not args.no_verify:
         import oracle_lib
         orc = oracle_lib.load_oracle()
         o = sets[(nstep[0] - 1) % nsets]
@@ -508,11 +514,11 @@ def main():
                 raise SystemExit("bench: pair (%d, %d) of the timed launch differs from the oracle" % (x, y))
             verified += 1
 
-    # ---- the exchange (RCCL all-gather of the packed slabs) against what this rank produced: every pair of this rank's shard
-    # must come back from the gathered slab exactly as the kernel wrote it (with one rank and DAFS_BENCH_FORCE_EXCHANGE=1 this
-    # is the whole set: the test that runs the nccl = RCCL backend on a one-GPU box)
+    # ---- --full: the exchange (RCCL all-gather of the packed slabs) against what this rank produced: every pair of this rank's
+    # shard must come back from the gathered slab exactly as the kernel wrote it (with one rank and DAFS_BENCH_FORCE_EXCHANGE=1
+    # this is the whole set: the test that runs the nccl = RCCL backend on a one-GPU box)
     exchange_verified = None
-    if ex is not None:
+    if args.full and ex is not None:
         o = sets[(nstep[0] - 1) % nsets]
         g = ex.gathered(lens)
         h_nnz = o["pair_nnz"].cpu().numpy().view(np.uint32)
@@ -541,7 +547,7 @@ def main():
     # (dist.phase1_sharded), the base-pairing transform replicated.  Timed like the step: barrier + synchronize on both
     # sides, max over ranks.  Not part of `value` (the metric is the pair-posterior path); reported beside it.
     sharded_phase1 = None
-    if world > 1 and not args.no_e2e:
+    if args.full and world > 1 and not args.no_e2e:
         try:
             from dafs_amd import dist as ddist
             sctx = capi.Context(local_rank)
@@ -565,7 +571,7 @@ def main():
     e2e = None
     dd_forced = None
     stages = None
-    if rank == 0 and world == 1 and not args.no_e2e:
+    if args.full and rank == 0 and world == 1 and not args.no_e2e:
         # BASELINE.json's second quantity: end-to-end wall-clock of the whole run (fold, pair posteriors,
         # consistency, tree, progressive DD, final structure) on the same set; not part of `value`.
         from dafs_amd import pipeline
@@ -658,10 +664,11 @@ def main():
                          "kernel_ms": kern_ms, "algorithmic_bytes_per_launch": alg_bytes, "secondary": secondary},
             "cpu_baseline": cpu,
             "verified_pairs": verified,
+            "full": args.full,
         }
         if dumped is not None:
             out["dumped_outputs"] = dumped
-        if exchange_verified is not None:
+        if ex is not None:
             out["exchange"] = {"backend": dist.get_backend(), "world": world, "verified_pairs": exchange_verified,
                                "slab_bytes_per_rank": int(ex.send.numel()) * 4}
         if e2e is not None:

@@ -5,7 +5,7 @@
 tag=${1:-rXX}
 root=$(pwd)
 out=$root/gpurun_out
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > $out/${tag}_bench_line.json 2> $out/${tag}_bench_line.err
+python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $out/${tag}_bench_line.json 2> $out/${tag}_bench_line.err
 tail -c 400 $out/${tag}_bench_line.json; echo
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_${tag}_pc -o p -- python3 $root/bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu --no-e2e > $out/prof_${tag}_pc.log 2>&1
