@@ -38,6 +38,10 @@ class PairhmmPlan(C.Structure):
                 ("scratch_bytes", C.c_uint64)]
 
 
+class DdNodePlan(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("lds_flags", "fold_fast", "nw_w", "lds", "split_lds", "s_x", "s_y", "s_xs", "s_ys")]
+
+
 class Pairhmm3Model(C.Structure):
     _fields_ = [("init", C.c_float * 3), ("trans", (C.c_float * 3) * 3), ("match", (C.c_float * 8) * 7),
                 ("ins", C.c_float * 8)]
@@ -182,6 +186,8 @@ pairhmm5_plan = _sig("dafs_hipk_pairhmm5_plan", C.c_int, [C.c_uint32, C.c_uint32
 pairhmm5_launch = _sig("dafs_hipk_pairhmm5_launch", C.c_int, [C.POINTER(Pairhmm5Args), C.POINTER(PairhmmPlan), C.c_void_p])
 pairhmm5_default_model = _sig("dafs_hip_pairhmm5_default_model", None, [C.POINTER(Pairhmm5Model)])
 residue_code = _sig("dafs_hip_residue_code", C.c_uint8, [C.c_char])
+dd_node_plan = _sig("dafs_hipk_dd_node_plan", C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(DdNodePlan)])
+dd_lds_words = _sig("dafs_hipk_dd_lds_words", C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int])
 
 
 def check(rc):

@@ -34,23 +34,21 @@ struct region { size_t off, bytes; int value; };
 
 void carve_nuss(carver& cv, uint32_t L, nuss_ws& w);
 // What only the folding DPs touch -- their work arrays (16 L^2 bytes each), the HBM copies of the traceback codes and the
-// pair scores in the order the DPs read them (sweep order for the column-owning forms unless no launch uses them, by span
-// for the span and workgroup forms; nd.lds_flags / nd.fold_fast say which) -- goes into the node's SECOND block, which is
-// carved when the consensus-pair count is known: a node that leaves its foldings out (dafs_dd_params::skip_uncoupled_folds and
-// no consensus pair) gets none of it, a third of its memory instead of all (27 GB -> 9 GB at the 27 000-column root of c5-random).
-void carve_folding(carver& cv, dd_node& nd, bool force_wide) {
+// pair scores in the order the DPs read them (the score copies of the node's plan, plan_node) -- goes into the node's SECOND
+// block, which is carved when the consensus-pair count is known: a node that leaves its foldings out (dafs_dd_params::
+// skip_uncoupled_folds and no consensus pair) gets none of it, a third of its memory instead of all (27 GB -> 9 GB at the
+// 27 000-column root of c5-random).
+void carve_folding(carver& cv, dd_node& nd, const dafs_dd_node_plan& pl) {
   const uint32_t L1 = nd.L1, L2 = nd.L2;
   const size_t XX = (size_t)L1 * L1, YY = (size_t)L2 * L2;
   carve_nuss(cv, L1, nd.wx);
   carve_nuss(cv, L2, nd.wy);
   nd.trk_x = nd.wx.tr; nd.trk_y = nd.wy.tr;  // the L*L uint32 tables double as bifurcation codes
   nd.trb_x = cv.take<uint8_t>(XX / 2 + L1 + 16); nd.trb_y = cv.take<uint8_t>(YY / 2 + L2 + 16);
-  const bool span_only = (nd.lds_flags & 64u) != 0;
-  const bool span_any = span_only || (nd.fold_fast & (16u | 32u)) != 0;
-  nd.s_x = (dd_fold_cols(L1) <= DD_WFOLD && !force_wide && !span_only) ? cv.take<float>(((size_t)L1 + 63) * dd_fold_cols(L1) * 64) : nullptr;
-  nd.s_y = (dd_fold_cols(L2) <= DD_WFOLD && !force_wide && !span_only) ? cv.take<float>(((size_t)L2 + 63) * dd_fold_cols(L2) * 64) : nullptr;
-  nd.s_xs = (span_any || (nd.fold_fast & 64u)) ? cv.take<float>((size_t)L1 * ((L1 + 63) & ~63u) + 64) : nullptr;
-  nd.s_ys = (span_any || (nd.fold_fast & 128u)) ? cv.take<float>((size_t)L2 * ((L2 + 63) & ~63u) + 64) : nullptr;
+  nd.s_x = pl.s_x ? cv.take<float>(((size_t)L1 + 63) * dd_fold_cols(L1) * 64) : nullptr;
+  nd.s_y = pl.s_y ? cv.take<float>(((size_t)L2 + 63) * dd_fold_cols(L2) * 64) : nullptr;
+  nd.s_xs = pl.s_xs ? cv.take<float>((size_t)L1 * ((L1 + 63) & ~63u) + 64) : nullptr;
+  nd.s_ys = pl.s_ys ? cv.take<float>((size_t)L2 * ((L2 + 63) & ~63u) + 64) : nullptr;
 }
 
 void carve_nuss(carver& cv, uint32_t L, nuss_ws& w) {
@@ -223,19 +221,81 @@ extern "C" void dafs_hip_dd_default_params(dafs_dd_params* p) {
 
 namespace {
 
-dd_params device_params(const dafs_dd_params* prm) {
+// The solver's environment switches (tests and tuning aids), read once per call that opens or advances nodes (tests change
+// them between calls).  DAFS_HIP_DD_WIDE=1: every node takes the forms of alignments too wide for the on-chip placements
+// (foldings span-ordered on HBM tables without sweep-order copies, the alignment DP in panels of 64 columns with its codes in
+// HBM slots, row pointers searched in HBM, one averaging row per workgroup).  DAFS_HIP_DD_NWG: no alignment codes in LDS.
+// DAFS_HIP_DD_WG=2: every folder takes the workgroup form, whatever its width.  The others turn a form or a placement off.
+struct dd_switches { bool wide, span, nwg, wg, wg_force, span_mw, split, avg_coop, stamps, lose_folders; };
+
+dd_switches read_switches() {
+  auto val = [](const char* name, int unset) { const char* e = getenv(name); return e ? atoi(e) : unset; };
+  const int wg = val("DAFS_HIP_DD_WG", 1);
+  return {val("DAFS_HIP_DD_WIDE", 0) != 0, val("DAFS_HIP_DD_SPAN", 1) != 0, getenv("DAFS_HIP_DD_NWG") != nullptr, wg != 0, wg == 2,
+          val("DAFS_HIP_DD_SPAN_MW", 1) != 0, val("DAFS_HIP_DD_SPLIT", 1) != 0, getenv("DAFS_HIP_AVG_COOP0") == nullptr,
+          getenv("DAFS_HIP_DD_STAMPS") != nullptr, getenv("DAFS_HIP_DD_LOSE_FOLDERS") != nullptr};
+}
+
+dd_params device_params(const dafs_dd_params* prm, const dd_switches& sw) {
   dd_params dp;
   dp.w = prm->w; dp.eta0 = prm->eta0; dp.th_a = prm->th_a; dp.th_s = prm->th_s; dp.t_max = prm->t_max; dp.force_iters = prm->force_iters;
-  dp.stamps = getenv("DAFS_HIP_DD_STAMPS") ? 1 : 0;
+  dp.stamps = sw.stamps; dp.debug_lose_folders = sw.lose_folders; dp.span_one_wave = !sw.span_mw;
   dp.skip_xy = prm->skip_uncoupled_folds ? 1 : 0;
-  dp.debug_lose_folders = getenv("DAFS_HIP_DD_LOSE_FOLDERS") ? 1 : 0;
-  {
-    const char* e = getenv("DAFS_HIP_DD_SPAN_MW");
-    dp.span_one_wave = (e && atoi(e) == 0) ? 1 : 0;
-  }
   dp.slice = 0;
   dp.budget = 0; dp.t_ref = nullptr; dp.t_ref_write = 0;
   return dp;
+}
+
+// The one place that chooses a node's forms, their LDS bytes (by the kernels' layout, dd_node_lds / dd_folder_lds)
+// and the score copies they read.  Foldings without a form here run span-ordered on HBM tables and need no LDS.
+dafs_dd_node_plan plan_node(uint32_t L1, uint32_t L2, const dd_switches& sw) {
+  dafs_dd_node_plan p = {};
+  p.nw_w = sw.wide ? 1u : dd_nw_cols(L2);  // columns per lane of the alignment DP
+  auto bytes = [&](uint32_t flags) { return (size_t)dd_node_lds(L1, L2, flags).end * 4; };
+  auto folder_bytes = [](uint32_t L, uint32_t form, uint32_t K) { return (size_t)dd_folder_lds(L, form, K).end * 4; };
+  auto reg = [](uint32_t L, uint32_t cols) { return dd_fold_cols(L) <= cols; };  // a register form exists for this width
+  const bool span_fits = sw.span && L1 <= DD_SPAN_LMAX && L2 <= DD_SPAN_LMAX;
+  uint32_t f = 0;
+  // the node's workgroup: both span forms (up to ~170 + 170 columns, with the alignment codes on chip too), else both register
+  // forms, else one region for x then y, else the same with the codes in HBM; the alignment codes where it runs in one panel
+  if (sw.wide) {}
+  else if (span_fits && bytes(kLdsSpanXY | kLdsNwTab) <= kDdLdsBudget) f = kLdsSpanXY;
+  else if (bytes(kLdsFastX | kLdsFastY) <= kDdLdsBudget) f = kLdsFastX | kLdsFastY;
+  else if (reg(L1, DD_WREG) && reg(L2, DD_WREG) && bytes(kLdsShared) <= kDdLdsBudget) f = kLdsShared;
+  else if (reg(L1, DD_WFOLD) && reg(L2, DD_WFOLD) && bytes(kLdsShared | kLdsSharedHbm) <= kDdLdsBudget) f = kLdsShared | kLdsSharedHbm;
+  if (!sw.wide && !sw.nwg && p.nw_w <= DD_WNW && L2 < 64u * p.nw_w && bytes(f | kLdsNwTab) <= kDdLdsBudget) f |= kLdsNwTab;
+  p.lds_flags = f; p.lds = (uint32_t)bytes(f);
+  // split plan: each folding on a workgroup of its own, the leader keeping the alignment DP (within p.lds).  Worth it when the
+  // two do not run side by side; when their span forms fit a folder but not the node; when the span forms run side by side
+  // but have more than one row slot, which a folder shares out to its wavefronts (nuss_span_mw); or without a register form.
+  const uint32_t Lm = std::max(L1, L2);
+  const bool span_folders = span_fits && !sw.wide && folder_bytes(Lm, kFoldSpan, 0) <= kDdLdsBudget &&
+                            (!(f & kLdsSpanXY) || (sw.span_mw && Lm > 64));
+  if ((!(f & (kLdsFastX | kLdsSpanXY)) || span_folders || sw.wg_force) && !sw.wide) {
+    size_t worst = 0;
+    for (uint32_t r = 0; r < 2; ++r) {
+      const uint32_t L = r ? L2 : L1;
+      const bool no_reg = !reg(L, DD_WFOLD) || sw.wg_force;
+      uint32_t form = 0, K = 0;
+      if (span_folders && !sw.wg_force) form = kFoldSpan;
+      else if (!no_reg && reg(L, DD_WREG) && folder_bytes(L, kFoldReg, 0) <= kDdLdsBudget) form = kFoldReg;
+      else if (!no_reg && folder_bytes(L, kFoldRegHbm, 0) <= kDdLdsBudget) form = kFoldRegHbm;
+      else if (no_reg && sw.wg)  // as many candidates per column on chip as fit; beyond ~10 000 columns not even the rolling rows do
+        for (uint32_t k : {4u, 2u, 0u})
+          if (folder_bytes(L, kFoldWg, k) <= kDdLdsBudget) { form = kFoldWg; K = k; break; }
+      p.fold_fast |= dd_fold_bits(r, form, K);
+      worst = std::max(worst, folder_bytes(L, form, K));
+    }
+    if (p.fold_fast || !reg(L1, DD_WFOLD) || !reg(L2, DD_WFOLD)) p.split_lds = (uint32_t)std::max(worst, (size_t)p.lds);
+  }
+  // the score copies these forms read: sweep order for the register forms, by span for the span and workgroup forms
+  const uint32_t fx = dd_fold_form(p.fold_fast, 0), fy = dd_fold_form(p.fold_fast, 1);
+  const bool span_any = (f & kLdsSpanXY) || ((fx | fy) & kFoldSpan);
+  p.s_x = reg(L1, DD_WFOLD) && !sw.wide && !(f & kLdsSpanXY);
+  p.s_y = reg(L2, DD_WFOLD) && !sw.wide && !(f & kLdsSpanXY);
+  p.s_xs = span_any || (fx & kFoldWg);
+  p.s_ys = span_any || (fy & kFoldWg);
+  return p;
 }
 
 // Builds nnodes resident nodes (appended to c->dd_open): geometry upload, profile averages, sparse lists and
@@ -272,24 +332,22 @@ int plan_check(const dd_node& nd, bool split, bool folds) {
   const bool regx = dd_fold_cols(nd.L1) <= DD_WFOLD, regy = dd_fold_cols(nd.L2) <= DD_WFOLD;
   if (!split) {
     const uint32_t f = nd.lds_flags;
-    if ((f & 64u) && (!nd.s_xs || !nd.s_ys)) return bad("span form without the by-span score copies");
-    if ((f & 64u) && (nd.L1 > DD_SPAN_LMAX || nd.L2 > DD_SPAN_LMAX)) return bad("span form beyond its width");
-    if (!(f & 64u) && (f & (2u | 8u)) && regx && !nd.s_x) return bad("register form of the x folding without its sweep-order scores");
-    if (!(f & 64u) && (f & (4u | 8u)) && regy && !nd.s_y) return bad("register form of the y folding without its sweep-order scores");
+    const bool span = (f & kLdsSpanXY) != 0;
+    if (span && (!nd.s_xs || !nd.s_ys)) return bad("span form without the by-span score copies");
+    if (span && (nd.L1 > DD_SPAN_LMAX || nd.L2 > DD_SPAN_LMAX)) return bad("span form beyond its width");
+    if (!span && (f & (kLdsFastX | kLdsShared)) && regx && !nd.s_x) return bad("register form of the x folding without its sweep-order scores");
+    if (!span && (f & (kLdsFastY | kLdsShared)) && regy && !nd.s_y) return bad("register form of the y folding without its sweep-order scores");
   } else {
-    if (nd.lds_flags & ~1u) return bad("a split leader keeps the alignment DP only");
-    for (int r = 0; r < 2; ++r) {
-      const uint32_t L = r ? nd.L2 : nd.L1;
+    if (nd.lds_flags & ~kLdsNwTab) return bad("a split leader keeps the alignment DP only");
+    for (uint32_t r = 0; r < 2; ++r) {
+      const uint32_t L = r ? nd.L2 : nd.L1, form = dd_fold_form(nd.fold_fast, r);
       const bool reg = r ? regy : regx;
-      const float* sweep = r ? nd.s_y : nd.s_x;
-      const float* byspan = r ? nd.s_ys : nd.s_xs;
-      if (nd.fold_fast & (16u << r)) {
+      const float *sweep = r ? nd.s_y : nd.s_x, *byspan = r ? nd.s_ys : nd.s_xs;
+      if (form & kFoldSpan) {
         if (!byspan) return bad("span-form folder without the by-span score copy");
         if (L > DD_SPAN_LMAX) return bad("span-form folder beyond its width");
-      } else if ((nd.fold_fast & (5u << r)) && reg && !sweep) return bad("register-form folder without its sweep-order scores");
-      if (nd.fold_fast & (64u << r)) {
-        if (!byspan) return bad("workgroup-form folder without the by-span score copy");
-      }
+      } else if ((form & (kFoldReg | kFoldRegHbm)) && reg && !sweep) return bad("register-form folder without its sweep-order scores");
+      if ((form & kFoldWg) && !byspan) return bad("workgroup-form folder without the by-span score copy");
     }
   }
   return DAFS_HIP_OK;
@@ -307,7 +365,8 @@ bool fail_injected(int stage) {
   return e && atoi(e) == stage;
 }
 
-int nodes_open_impl(dafs_hip_ctx* c, const dd_lane& ln, uint32_t nnodes, const dafs_node_input* in, const dd_params& dp, open_blocks& ob) {
+int nodes_open_impl(dafs_hip_ctx* c, const dd_lane& ln, uint32_t nnodes, const dafs_node_input* in, const dd_params& dp, const dd_switches& sw,
+                    open_blocks& ob) {
   const mp_store& mps = c->mp[c->cur_mp];
   const bp_store& bps = c->bp[c->cur_bp];
   if (!mps.valid || !bps.valid || mps.n_tasks != c->fam.npairs()) return DAFS_HIP_EINVAL;
@@ -326,15 +385,10 @@ int nodes_open_impl(dafs_hip_ctx* c, const dd_lane& ln, uint32_t nnodes, const d
     for (uint32_t r = 0; r < ni.n2; ++r) if (!c->fam.same_family(s0, ni.seq2[r])) return DAFS_HIP_EINVAL;
   }
 
-  // DAFS_HIP_DD_WIDE=1 (tests): every node takes the forms of alignments too wide for the on-chip placements -- foldings
-  // span-ordered on HBM tables without sweep-order copies, the alignment DP in panels of 64 columns with its codes in
-  // HBM slots, row pointers searched in HBM, one averaging row per workgroup
-  const char* wide_env = getenv("DAFS_HIP_DD_WIDE");
-  const bool force_wide = wide_env && atoi(wide_env) != 0;
   // ---- carve each node's block (two passes: size, then pointers) ----
   std::vector<dd_node> nodes(nnodes);
   std::vector<std::vector<uint8_t>> heads(nnodes);  // upload staging, alive until the first synchronisation below
-  std::vector<size_t> lds(nnodes, 0), split_lds(nnodes, 0);
+  std::vector<dafs_dd_node_plan> plans(nnodes);
   ob.blk0.assign(nnodes, nullptr); ob.blk1.assign(nnodes, nullptr);
   ob.bytes0.assign(nnodes, 0); ob.bytes1.assign(nnodes, 0);
   std::vector<uint8_t*>&blk0 = ob.blk0, &blk1 = ob.blk1;
@@ -344,6 +398,7 @@ int nodes_open_impl(dafs_hip_ctx* c, const dd_lane& ln, uint32_t nnodes, const d
     dd_node& nd = nodes[b];
     carver cv;
     std::vector<region> fills;
+    const dafs_dd_node_plan& pl = plans[b] = plan_node(ni.len1, ni.len2, sw);
     for (int pass = 0; pass < 2; ++pass) {
       cv.used = 0;
       fills.clear();
@@ -370,81 +425,12 @@ int nodes_open_impl(dafs_hip_ctx* c, const dd_lane& ln, uint32_t nnodes, const d
       // (the folding DPs' work arrays, codes and score copies are carved into the node's second block, once the
       // consensus-pair count says whether this node folds at all: carve_folding below)
       // the alignment DP: columns per lane, and with them the panels of second alignments beyond 64 nw_w - 1 columns
-      nd.nw_w = force_wide ? 1u : dd_nw_cols(L2);
+      nd.nw_w = pl.nw_w; nd.lds_flags = pl.lds_flags; nd.fold_fast = pl.fold_fast;
       const size_t nw_panels = dd_nw_panels(L2, nd.nw_w);
       nd.nw_edge = cv.take<float>(2 * ((size_t)L1 + 2));
       nd.tr_z = cv.take<uint8_t>(nw_panels * (L1 + 1) * 512);  // a 64-bit slot per (panel, row, lane)
       // sweep-order inputs of the alignment DP: steps x columns per lane x 64 lanes, panel by panel
       nd.pz_s = cv.take<float>(nw_panels * ((size_t)L1 + 63) * nd.nw_w * 64); nd.qz_s = cv.take<float>(nw_panels * ((size_t)L1 + 63) * nd.nw_w * 64);
-      {  // LDS plan (mirrors the carving at the top of k_dd_solve / dd_folder)
-        auto nib = [](uint32_t L) { return ((size_t)L * (L + 1) / 2 + 7) / 8; };           // packed traceback codes, words
-        // a fast folding DP: codes, the rows in flight (one per active lane), DD_CAP split rows per column
-        auto fast = [&](uint32_t L) { return (nib(L) + dd_ring_words(L) + (size_t)DD_CAP * L) * 4; };
-        const size_t need_z = (size_t)dd_nwtab_words(L1, L2) * 4;                           // packed alignment traceback
-        const uint32_t Lm = std::max(L1, L2);
-        const size_t shared = (std::max(nib(L1), nib(L2)) + std::max(dd_ring_words(L1), dd_ring_words(L2)) + (size_t)DD_CAP * Lm) * 4;
-        const size_t shared_g = (std::max(dd_ring_words(L1), dd_ring_words(L2)) + (size_t)DD_CAP * Lm) * 4;
-        auto fast_g = [&](uint32_t L) { return ((size_t)dd_ring_words(L) + (size_t)DD_CAP * L) * 4; };  // traceback codes in HBM
-        auto wide_ok = [](uint32_t L, uint32_t cols) { return dd_fold_cols(L) <= cols; };  // a register form exists for this width
-        size_t used = 0;
-        nd.lds_flags = 0;
-        // span form of both foldings side by side (whole dp triangles on chip: up to ~170 + 170 columns); DAFS_HIP_DD_SPAN=0
-        // keeps the column-owning forms (tests run both)
-        const char* span_env = getenv("DAFS_HIP_DD_SPAN");
-        const bool span_allowed = !(span_env && atoi(span_env) == 0);
-        const size_t span_xy = ((size_t)dd_span_words(L1) + dd_span_words(L2)) * 4 + 16;
-        if (force_wide) {}
-        else if (span_allowed && L1 <= DD_SPAN_LMAX && L2 <= DD_SPAN_LMAX && used + span_xy + need_z <= kDdLdsBudget) { used += span_xy; nd.lds_flags |= 64u; }  // only with the alignment traceback on chip too
-        else if (used + fast(L1) + fast(L2) <= kDdLdsBudget) { used += fast(L1) + fast(L2); nd.lds_flags |= 2u | 4u; }  // x and y side by side
-        else if (wide_ok(L1, DD_WREG) && wide_ok(L2, DD_WREG) && used + shared <= kDdLdsBudget) { used += shared; nd.lds_flags |= 8u; }      // one region, x then y
-        else if (wide_ok(L1, DD_WFOLD) && wide_ok(L2, DD_WFOLD) && used + shared_g <= kDdLdsBudget) { used += shared_g; nd.lds_flags |= 8u | 16u; }  // the same, codes in HBM
-        // else: foldings without a register form run span-ordered on HBM tables and need no LDS
-        // DAFS_HIP_DD_NWG=1 (tests): no alignment codes in LDS, so that every node takes the register form with its codes in HBM slots
-        if (used + need_z <= kDdLdsBudget && !force_wide && !getenv("DAFS_HIP_DD_NWG") && nd.nw_w <= DD_WNW && L2 < 64u * nd.nw_w) { used += need_z; nd.lds_flags |= 1u; }
-        lds[b] = used;
-        // split plan: each folding DP on a workgroup of its own.  Worth it when the two do not run side by side
-        // in one workgroup; the leader then keeps only the alignment DP (its LDS need is covered by `used`).
-        nd.split = 0; nd.fold_fast = 0;
-        split_lds[b] = 0;
-        // Nodes whose foldings cannot take the span form side by side, but can on a workgroup of their own, are worth
-        // splitting even when the column-owning forms fit side by side: the span form is about twice as fast.
-        // ... and since round 3 also when they do fit side by side, as soon as a folding has more than one row slot: its
-        // folder shares the slots out to its wavefronts (nuss_span_mw: a span costs one slot step + a barrier instead of
-        // one slot step per live slot), which the node's own workgroup -- one wavefront per subproblem -- cannot do.
-        const char* mw_env = getenv("DAFS_HIP_DD_SPAN_MW");
-        const bool mw_allowed = !(mw_env && atoi(mw_env) == 0);
-        const char* wg_env = getenv("DAFS_HIP_DD_WG");
-        const bool wg_allowed = !(wg_env && atoi(wg_env) == 0);
-        const bool wg_force = wg_env && atoi(wg_env) == 2;  // tests: every folder takes the workgroup form, whatever its width
-        const bool span_folders = span_allowed && !force_wide && L1 <= DD_SPAN_LMAX && L2 <= DD_SPAN_LMAX &&
-                                  (size_t)dd_span_words(std::max(L1, L2)) * 4 + 16 <= kDdLdsBudget &&
-                                  (!(nd.lds_flags & 64u) || (mw_allowed && std::max(L1, L2) > 64));
-        if ((!(nd.lds_flags & (2u | 64u)) || span_folders || wg_force) && !force_wide) {
-          size_t worst = 0;
-          const uint32_t Ls[2] = {L1, L2};
-          for (int r = 0; r < 2; ++r) {
-            const uint32_t L = Ls[r];
-            const bool no_reg = !wide_ok(L, DD_WFOLD) || wg_force;
-            if (span_folders && !wg_force) { nd.fold_fast |= 16u << r; worst = std::max(worst, (size_t)dd_span_words(L) * 4 + 16); }
-            else if (!no_reg && wide_ok(L, DD_WREG) && fast(L) <= kDdLdsBudget) { nd.fold_fast |= 1u << r; worst = std::max(worst, fast(L)); }
-            else if (!no_reg && wide_ok(L, DD_WFOLD) && fast_g(L) <= kDdLdsBudget) { nd.fold_fast |= 4u << r; worst = std::max(worst, fast_g(L)); }
-            else if (no_reg && wg_allowed) {
-              // no register form: the workgroup form with as many candidates per column on chip as fit (dd_wg_words); beyond
-              // ~10 000 columns not even its rolling rows fit and the span-ordered form on HBM tables remains
-              for (uint32_t K : {4u, 2u, 0u})
-                if ((size_t)dd_wg_words(L, K) * 4 + 16 <= kDdLdsBudget) {
-                  nd.fold_fast |= (64u << r) | (K << (8 + 4 * r));
-                  worst = std::max(worst, (size_t)dd_wg_words(L, K) * 4 + 16);
-                  break;
-                }
-            }
-            // else span-ordered on HBM tables: no LDS
-          }
-          // also worth it when a folding has no register form at all: its folder runs the span-ordered form on a
-          // whole workgroup, far ahead of the HBM-table wave form the leader would run for it
-          if (nd.fold_fast || !wide_ok(L1, DD_WFOLD) || !wide_ok(L2, DD_WFOLD)) split_lds[b] = std::max(worst, used);
-        }
-      }
       nd.env = cv.take<uint32_t>(2 * ((size_t)L1 + 1));
       nd.env4 = cv.take<uint32_t>(2 * ((size_t)L1 + 130));
       nd.px_ptr = cv.take<uint32_t>((size_t)L1 + 2); nd.px_j = cv.take<uint32_t>(XX / 2 + 2);
@@ -488,15 +474,15 @@ int nodes_open_impl(dafs_hip_ctx* c, const dd_lane& ln, uint32_t nnodes, const d
   // few nodes with hundreds of source rows per row of p_z (the top of the guide tree): a workgroup per p_z row
   uint64_t srcs = 0;
   for (uint32_t b = 0; b < nnodes; ++b) srcs = std::max<uint64_t>(srcs, (uint64_t)in[b].n1 * in[b].n2);
-  const int coop = (nnodes <= 4 && srcs >= 512 && !getenv("DAFS_HIP_AVG_COOP0")) ? 1 : 0;
-  if ((rc = dd_avg_launch(ln.d_nodes->ptr, nnodes, max_len, mpv, bpv, force_wide ? 1 : 0, coop, ln.st))) return rc;
+  const int coop = (nnodes <= 4 && srcs >= 512 && sw.avg_coop) ? 1 : 0;
+  if ((rc = dd_avg_launch(ln.d_nodes->ptr, nnodes, max_len, mpv, bpv, sw.wide ? 1 : 0, coop, ln.st))) return rc;
   for (uint32_t b = 0; b < nnodes; ++b) {  // base-pairing matrices supplied by the caller (--bp-update) replace the averages
     const size_t XX = (size_t)in[b].len1 * in[b].len1, YY = (size_t)in[b].len2 * in[b].len2;
     if (in[b].p_x && hip_check(hipMemcpyAsync(nodes[b].p_x, in[b].p_x, XX * 4, hipMemcpyHostToDevice, ln.st))) return DAFS_HIP_ELAUNCH;
     if (in[b].p_y && hip_check(hipMemcpyAsync(nodes[b].p_y, in[b].p_y, YY * 4, hipMemcpyHostToDevice, ln.st))) return DAFS_HIP_ELAUNCH;
   }
   if ((rc = ln.d_paused->reserve(nnodes))) return rc;  // doubles as the landing place of the per-node counts
-  if ((rc = dd_lists_launch(ln.d_nodes->ptr, nnodes, force_wide ? 0 : max_len, dp, ln.d_paused->ptr, ln.st))) return rc;
+  if ((rc = dd_lists_launch(ln.d_nodes->ptr, nnodes, sw.wide ? 0 : max_len, dp, ln.d_paused->ptr, ln.st))) return rc;
   // ---- consensus base-pair counts -> each node's second block ----
   std::vector<uint32_t> counts(nnodes);
   if (hip_check(hipMemcpyAsync(counts.data(), ln.d_paused->ptr, (size_t)nnodes * 4, hipMemcpyDeviceToHost, ln.st))) return DAFS_HIP_ELAUNCH;
@@ -510,7 +496,7 @@ int nodes_open_impl(dafs_hip_ctx* c, const dd_lane& ln, uint32_t nnodes, const d
       nodes[b].ncbp_cap = ncbp;
       nodes[b].cbp = cb.take<uint32_t>((size_t)8 * ncbp + 8);
       nodes[b].sw = cb.take<float>((size_t)ncbp + 1);
-      if (!(dp.skip_xy && ncbp == 0)) carve_folding(cb, nodes[b], force_wide);  // the kernel's fold_on
+      if (!(dp.skip_xy && ncbp == 0)) carve_folding(cb, nodes[b], plans[b]);  // the kernel's fold_on
       if (pass == 0) {
         cb.base = c->dd_alloc(cb.used + 256);
         if (!cb.base) return DAFS_HIP_ENOMEM;
@@ -522,11 +508,11 @@ int nodes_open_impl(dafs_hip_ctx* c, const dd_lane& ln, uint32_t nnodes, const d
   for (uint32_t b = 0; b < nnodes; ++b)  // both placements a launch may choose for this node, before anything runs on it
     if ((rc = plan_check(nodes[b], false, !(dp.skip_xy && counts[b] == 0)))) return rc;
   if ((rc = ln.d_nodes->upload(nodes.data(), nnodes, ln.st))) return rc;
-  if ((rc = dd_cbp_fill_launch(ln.d_nodes->ptr, nnodes, force_wide ? 0 : max_len, dp, ln.st))) return rc;
+  if ((rc = dd_cbp_fill_launch(ln.d_nodes->ptr, nnodes, sw.wide ? 0 : max_len, dp, ln.st))) return rc;
   if (fail_injected(4)) return DAFS_HIP_ELAUNCH;
   for (uint32_t b = 0; b < nnodes; ++b) {
     dafs_hip_ctx::dd_open_node on;
-    on.nd = nodes[b]; on.lds = lds[b]; on.split_lds = split_lds[b];
+    on.nd = nodes[b]; on.lds = plans[b].lds; on.split_lds = plans[b].split_lds;
     on.blk[0] = blk0[b]; on.blk[1] = blk1[b]; on.blk_bytes[0] = blk0_bytes[b]; on.blk_bytes[1] = blk1_bytes[b];
     c->dd_open.push_back(on);
   }
@@ -536,10 +522,10 @@ int nodes_open_impl(dafs_hip_ctx* c, const dd_lane& ln, uint32_t nnodes, const d
 // A failed open leaves nothing behind: the fills, uploads and set-up kernels it has queued on the lane's stream may still
 // write into the blocks it carved, so the stream is drained before they go back to the free list (the next dd_alloc,
 // possibly for the other lane, may hand them out at once), and the nodes it may have appended are dropped.
-int nodes_open(dafs_hip_ctx* c, const dd_lane& ln, uint32_t nnodes, const dafs_node_input* in, const dd_params& dp) {
+int nodes_open(dafs_hip_ctx* c, const dd_lane& ln, uint32_t nnodes, const dafs_node_input* in, const dd_params& dp, const dd_switches& sw) {
   const size_t first = c->dd_open.size();
   open_blocks ob;
-  const int rc = nodes_open_impl(c, ln, nnodes, in, dp, ob);
+  const int rc = nodes_open_impl(c, ln, nnodes, in, dp, sw, ob);
   if (rc) {
     (void)hipStreamSynchronize(ln.st);
     c->dd_open.resize(first);
@@ -559,8 +545,8 @@ struct advance_state {
   bool complete = false;  // ... and the per-node words are on their way to the landing place
 };
 
-int advance_launch(dafs_hip_ctx* c, const dd_lane& ln, uint32_t n, const uint32_t* handles, dd_params dp, uint32_t max_iterations, uint8_t* finished,
-                   advance_state& stt) {
+int advance_launch(dafs_hip_ctx* c, const dd_lane& ln, uint32_t n, const uint32_t* handles, dd_params dp, const dd_switches& sw,
+                   uint32_t max_iterations, uint8_t* finished, advance_state& stt) {
   std::vector<dd_node> nodes;
   std::vector<uint32_t>& who = stt.who;
   who.clear();
@@ -579,19 +565,17 @@ int advance_launch(dafs_hip_ctx* c, const dd_lane& ln, uint32_t n, const uint32_
   if (nodes.empty()) return DAFS_HIP_OK;
   // split mode (three workgroups per node) when the launch is small enough for all of them to be on the
   // machine at once and some node profits; DAFS_HIP_DD_SPLIT=0 turns it off
-  const char* split_env = getenv("DAFS_HIP_DD_SPLIT");
-  const bool split_allowed = !(split_env && atoi(split_env) == 0);
   bool split = false;
   // three workgroups per node, one per CU (their LDS does not leave room for a second): all of them must fit the device,
   // next to the workgroups of the other lane's launch when that one is still in flight (dafs_hip_nodes_round)
   const uint32_t other_wgs = c->dd_wgs_in_flight[ln.id ^ 1];
-  if (split_allowed && (int)(nodes.size() * 3 + other_wgs) <= c->num_cus - 16)
+  if (sw.split && (int)(nodes.size() * 3 + other_wgs) <= c->num_cus - 16)
     for (size_t b = 0; b < nodes.size(); ++b) split = split || (c->dd_open[handles[who[b]]].split_lds != 0 && !c->dd_open[handles[who[b]]].no_split);
   for (size_t b = 0; b < nodes.size(); ++b) {
     const dafs_hip_ctx::dd_open_node& on = c->dd_open[handles[who[b]]];
     if (split && on.split_lds && !on.no_split) {
       nodes[b].split = 1;
-      nodes[b].lds_flags &= 1u;  // the leader keeps the alignment DP only
+      nodes[b].lds_flags &= kLdsNwTab;  // the leader keeps the alignment DP only
       lds_max = std::max(lds_max, on.split_lds);
       if (hip_check(hipMemsetAsync(nodes[b].sync, 0, 4, ln.st))) return DAFS_HIP_ELAUNCH;  // clear the exit mark of the last launch
     } else {
@@ -649,10 +633,10 @@ int advance_collect(dafs_hip_ctx* c, const dd_lane& ln, advance_state& stt, uint
   return DAFS_HIP_OK;
 }
 
-int nodes_advance(dafs_hip_ctx* c, uint32_t n, const uint32_t* handles, dd_params dp, uint32_t max_iterations, uint8_t* finished) {
+int nodes_advance(dafs_hip_ctx* c, uint32_t n, const uint32_t* handles, dd_params dp, const dd_switches& sw, uint32_t max_iterations, uint8_t* finished) {
   advance_state stt;
   const dd_lane ln = lane_of(c, 0);
-  const int rc = advance_launch(c, ln, n, handles, dp, max_iterations, finished, stt);
+  const int rc = advance_launch(c, ln, n, handles, dp, sw, max_iterations, finished, stt);
   const int rc2 = advance_collect(c, ln, stt, finished);  // also after a failure: whatever was enqueued is waited for
   return rc ? rc : rc2;
 }
@@ -677,7 +661,7 @@ int nodes_result(dafs_hip_ctx* c, uint32_t handle, dafs_node_output* out, bool s
   if (out->z) memcpy(out->z, at(nd.z), (size_t)nd.L1 * 4);
   memcpy(&score, at(nd.score), 4);
   memcpy(info, at(nd.info), sizeof info);
-  if (stamps && nd.fold_fast & (16u | 32u | 64u | 128u)) {
+  if (stamps && ((dd_fold_form(nd.fold_fast, 0) | dd_fold_form(nd.fold_fast, 1)) & (kFoldSpan | kFoldWg))) {
     uint32_t sy[8] = {0};
     if (!hip_check(hipMemcpy(sy, nd.sync, sizeof sy, hipMemcpyDeviceToHost)))
       fprintf(stderr, "dd node L1=%u L2=%u folders | us: x-dp %.0f y-dp %.0f tracebacks %.0f\n", nd.L1, nd.L2, sy[5] / 100.0, sy[6] / 100.0, sy[7] / 100.0);
@@ -718,7 +702,8 @@ extern "C" int dafs_hip_nodes_open(dafs_hip_ctx* c, uint32_t nnodes, const dafs_
   if (!c || !in || !prm || !handles || nnodes == 0) return DAFS_HIP_EINVAL;
   if (hip_check(hipSetDevice(c->device))) return DAFS_HIP_ENODEV;
   const uint32_t first = (uint32_t)c->dd_open.size();
-  const int rc = nodes_open(c, lane_of(c, 0), nnodes, in, device_params(prm));
+  const dd_switches sw = read_switches();
+  const int rc = nodes_open(c, lane_of(c, 0), nnodes, in, device_params(prm, sw), sw);
   if (rc) return rc;
   for (uint32_t b = 0; b < nnodes; ++b) handles[b] = first + b;
   return DAFS_HIP_OK;
@@ -728,7 +713,8 @@ extern "C" int dafs_hip_nodes_advance(dafs_hip_ctx* c, uint32_t n, const uint32_
                                       uint8_t* finished) {
   if (!c || !handles || !prm || n == 0) return DAFS_HIP_EINVAL;
   if (hip_check(hipSetDevice(c->device))) return DAFS_HIP_ENODEV;
-  return nodes_advance(c, n, handles, device_params(prm), max_iterations, finished);
+  const dd_switches sw = read_switches();
+  return nodes_advance(c, n, handles, device_params(prm, sw), sw, max_iterations, finished);
 }
 
 // One round of the progressive phase in a single call: the open nodes advance (lane 0) while the nodes whose children have
@@ -740,7 +726,8 @@ extern "C" int dafs_hip_nodes_round(dafs_hip_ctx* c, uint32_t n_new, const dafs_
                                     uint8_t* finished_old, uint8_t* finished_new) {
   if (!c || !prm || (n_new && (!in || !new_handles)) || (n_old && !old_handles) || (n_new == 0 && n_old == 0)) return DAFS_HIP_EINVAL;
   if (hip_check(hipSetDevice(c->device))) return DAFS_HIP_ENODEV;
-  dd_params dp = device_params(prm);
+  const dd_switches sw = read_switches();
+  dd_params dp = device_params(prm, sw);
   dp.budget = (unsigned long long)budget_us * 100ull;  // wall_clock64 ticks at 100 MHz
   int rc = DAFS_HIP_OK;
   advance_state st_old, st_new;
@@ -754,7 +741,7 @@ extern "C" int dafs_hip_nodes_round(dafs_hip_ctx* c, uint32_t n_new, const dafs_
       dp.t_ref = c->d_tref.ptr;
       dp.t_ref_write = 1;
     }
-    if ((rc = advance_launch(c, l0, n_old, old_handles, dp, max_iterations, finished_old, st_old))) {
+    if ((rc = advance_launch(c, l0, n_old, old_handles, dp, sw, max_iterations, finished_old, st_old))) {
       (void)advance_collect(c, l0, st_old, finished_old);  // whatever part of the launch was enqueued is waited for
       return rc;
     }
@@ -764,20 +751,31 @@ extern "C" int dafs_hip_nodes_round(dafs_hip_ctx* c, uint32_t n_new, const dafs_
     dd_params dpn = dp;
     dpn.t_ref_write = 0;  // a late starter takes the round's reference tick (none when it runs alone)
     if (!n_old) dpn.t_ref = nullptr;
-    rc = nodes_open(c, l1, n_new, in, dpn);
+    rc = nodes_open(c, l1, n_new, in, dpn, sw);
     if (rc) { (void)advance_collect(c, l0, st_old, finished_old); return rc; }
     for (uint32_t b = 0; b < n_new; ++b) new_handles[b] = first + b;
-    rc = advance_launch(c, l1, n_new, new_handles, dpn, max_iterations, finished_new, st_new);
+    rc = advance_launch(c, l1, n_new, new_handles, dpn, sw, max_iterations, finished_new, st_new);
   }
   const int rc0 = advance_collect(c, l0, st_old, finished_old);
   const int rc1 = n_new ? advance_collect(c, l1, st_new, finished_new) : DAFS_HIP_OK;
   return rc ? rc : (rc0 ? rc0 : rc1);
 }
 
+extern "C" int dafs_hipk_dd_node_plan(uint32_t len1, uint32_t len2, dafs_dd_node_plan* out) {
+  if (!out || !len1 || !len2) return DAFS_HIP_EINVAL;
+  *out = plan_node(len1, len2, read_switches());
+  return DAFS_HIP_OK;
+}
+
+extern "C" uint32_t dafs_hipk_dd_lds_words(uint32_t len1, uint32_t len2, uint32_t lds_flags, uint32_t fold_fast, int role) {
+  const uint32_t r = role == 2 ? 1 : 0;
+  return role ? dd_folder_lds(r ? len2 : len1, dd_fold_form(fold_fast, r), dd_fold_k(fold_fast, r)).end : dd_node_lds(len1, len2, lds_flags).end;
+}
+
 extern "C" int dafs_hip_nodes_result(dafs_hip_ctx* c, uint32_t handle, dafs_node_output* out) {
   if (!c || !out) return DAFS_HIP_EINVAL;
   if (hip_check(hipSetDevice(c->device))) return DAFS_HIP_ENODEV;
-  return nodes_result(c, handle, out, getenv("DAFS_HIP_DD_STAMPS") != nullptr);
+  return nodes_result(c, handle, out, read_switches().stamps);
 }
 
 extern "C" int dafs_hip_nodes_close(dafs_hip_ctx* c) {
@@ -811,15 +809,16 @@ extern "C" int dafs_hip_solve_nodes(dafs_hip_ctx* c, uint32_t nnodes, const dafs
   if (!c || !in || !prm || !out || nnodes == 0) return DAFS_HIP_EINVAL;
   if (hip_check(hipSetDevice(c->device))) return DAFS_HIP_ENODEV;
   if (!c->dd_open.empty()) return DAFS_HIP_EINVAL;
-  const dd_params dp = device_params(prm);
-  int rc = nodes_open(c, lane_of(c, 0), nnodes, in, dp);
+  const dd_switches sw = read_switches();
+  const dd_params dp = device_params(prm, sw);
+  int rc = nodes_open(c, lane_of(c, 0), nnodes, in, dp, sw);
   std::vector<uint32_t> handles(nnodes);
   for (uint32_t b = 0; b < nnodes; ++b) handles[b] = b;
   // one launch runs every node to its end -- unless a split node lost its folding workgroups and was parked for the
   // one-workgroup form (k_dd_solve): then the unfinished nodes go round again
   std::vector<uint8_t> fin(nnodes, 0);
   for (int round = 0; !rc && round < 4; ++round) {
-    rc = nodes_advance(c, nnodes, handles.data(), dp, 0, fin.data());
+    rc = nodes_advance(c, nnodes, handles.data(), dp, sw, 0, fin.data());
     if (std::all_of(fin.begin(), fin.end(), [](uint8_t f) { return f != 0; })) break;
   }
   if (!rc && !std::all_of(fin.begin(), fin.end(), [](uint8_t f) { return f != 0; })) rc = DAFS_HIP_ELAUNCH;

@@ -34,8 +34,7 @@ struct dd_node {
   float *s_xs, *s_ys;       // L*Lp each (Lp = L rounded up to 64): the same scores stored by span, S[(j-i)*Lp + i], for the span form
                             // (nuss_wave_span); null when no launch of this node can take that form
   float *pz_s, *qz_s;       // panels*(L1+63)*nw_w*64 each: p_z, q_z in sweep order of the alignment DP, panel by panel
-  uint32_t lds_flags;       // LDS plan: bit 0 packed alignment traceback, bit 1 / bit 2 fast form of the x / y folding DP, bit 3 / 4 shared region / codes in HBM,
-                            // bit 6 span form of both folding DPs side by side (whole triangles in LDS; scores from s_xs / s_ys)
+  uint32_t lds_flags;       // LDS plan of the node's own workgroup: kLds* below (dd_node_lds lays it out)
   uint32_t* env;      // 2*(L1+1)
   uint32_t* env4;     // 2*(L1+130): the same envelope for the register-resident alignment DP -- {max(first,1), second} of row r at
                       // index r + 64, the empty range {1, 0} for the 64 rows before row 1 and the 65 behind row L1 (no clamping, no selects)
@@ -56,9 +55,7 @@ struct dd_node {
   float* fstate;                  // [4]: c, eta, previous dual value of a paused node
   // split mode: the two folding DPs of this node run on workgroups of their own (blockIdx.y = 1, 2) next to
   // the leader (blockIdx.y = 0, alignment DP + constraints + updates); sync[0] go / exit, [1] x done, [2] y done,
-  // [3] [4] the folding scores.  fold_fast: bit 0 / 1 the fast form of x / y fits the folder's LDS, bit 2 / 3 the same with the
-  // codes in HBM, bit 4 / 5 the span form fits it (preferred), bit 6 / 7 no register form but the workgroup form fits
-  // (nuss_wg_span; needs s_xs / s_ys) with K = bits 8..11 / 12..15 candidates per column in LDS.
+  // [3] [4] the folding scores.  fold_fast: the form of each folder, kFold* below (dd_fold_form / dd_fold_k read it).
   uint32_t* sync;
   uint32_t split, fold_fast;
 };
@@ -124,6 +121,60 @@ static inline __host__ __device__ uint32_t dd_span_words(uint32_t L) { return dd
 static inline __host__ __device__ uint32_t dd_nwtab_row_words(uint32_t L2) { return (L2 + 1 + 15) / 16; }
 static inline __host__ __device__ uint32_t dd_nwtab_words(uint32_t L1, uint32_t L2) { return (L1 + 1) * dd_nwtab_row_words(L2); }
 static const size_t kDdLdsBudget = 156 * 1024;  // dynamic LDS of k_dd_solve (the CU has 160 KB; ~2.2 KB is static)
+
+// The forms of a node's folding and alignment DPs (the host's plan_node chooses them).  dd_node::lds_flags, what the
+// node's workgroup keeps in LDS: the packed alignment codes; the register forms of x and y side by side; one region for both
+// (x, then y), with the codes in HBM too; the span form of both side by side.
+constexpr uint32_t kLdsNwTab = 1u, kLdsFastX = 2u, kLdsFastY = 4u, kLdsShared = 8u, kLdsSharedHbm = 16u, kLdsSpanXY = 64u;
+// dd_node::fold_fast, the form of each folder r (0 = x, 1 = y) of a split node, at bit r of: the register form, the same
+// with its codes in HBM, the span form, the workgroup form nuss_wg_span (no register form); and that form's K
+// (candidates per column in LDS) at bits 8 + 4r ..
+constexpr uint32_t kFoldReg = 1u, kFoldRegHbm = 4u, kFoldSpan = 16u, kFoldWg = 64u, kFoldKShift = 8, kFoldKMask = 15u;
+static inline __host__ __device__ uint32_t dd_fold_form(uint32_t fold_fast, uint32_t r) { return (fold_fast >> r) & (kFoldReg | kFoldRegHbm | kFoldSpan | kFoldWg); }
+static inline __host__ __device__ uint32_t dd_fold_k(uint32_t fold_fast, uint32_t r) { return (fold_fast >> (kFoldKShift + 4 * r)) & kFoldKMask; }
+static inline __host__ __device__ uint32_t dd_fold_bits(uint32_t r, uint32_t form, uint32_t K) { return (form << r) | (K << (kFoldKShift + 4 * r)); }
+
+// The dynamic LDS of k_dd_solve (dd_node_lds) and of a split node's folder (dd_folder_lds): word offsets of each region from
+// the base, which is first rounded up to 16 bytes when align16 (16-byte candidate slots; `end` counts the three words this
+// may take).  The host sizes its plans by `end`, the kernels carve by the offsets (dd_lds_at).
+constexpr uint32_t kDdNoLds = 0xFFFFFFFFu;  // region absent
+struct dd_fold_lds {  // a folding DP: packed codes, rows in flight, split rows (span form: candidate heads), span triangle,
+                      // candidate values and row offsets, traceback stack, workgroup-form rows
+  uint32_t trb = kDdNoLds, ring = kDdNoLds, lck = kDdNoLds, tri = kDdNoLds, cv = kDdNoLds, ck = kDdNoLds, stk = kDdNoLds, wg = kDdNoLds;
+};
+struct dd_lds { dd_fold_lds f[2]; uint32_t trz = kDdNoLds, end = 0; bool align16 = false; };  // f: x, y (a folder: f[0]); trz: alignment codes
+static inline __host__ __device__ uint32_t dd_code_words(uint32_t L) { return (uint32_t)(((size_t)L * (L + 1) / 2 + 7) / 8); }
+static inline __host__ __device__ void dd_span_lds(dd_fold_lds& f, uint32_t& w, uint32_t L) {
+  f.trb = w; w += dd_span_nib_words(L); f.tri = w; w += dd_span_tri_words(L);
+  f.cv = f.stk = w; w += DD_CAP * (L + 1); f.ck = w; w += DD_CAP * (L + 1); f.lck = w; w += DD_CAP * L;  // stack: dead values
+}
+static inline __host__ __device__ void dd_reg_lds(dd_fold_lds& f, uint32_t& w, uint32_t codes, uint32_t ring, uint32_t lck) {
+  if (codes) { f.trb = w; w += codes; }
+  f.ring = f.stk = w; w += ring; f.lck = w; w += lck;  // stack: the ring, idle by then
+}
+static inline __host__ __device__ dd_lds dd_node_lds(uint32_t L1, uint32_t L2, uint32_t flags) {
+  dd_lds m; uint32_t w = 0;
+  m.align16 = (flags & kLdsSpanXY) != 0;
+  if (m.align16) { dd_span_lds(m.f[0], w, L1); dd_span_lds(m.f[1], w, L2); }
+  if (flags & kLdsNwTab) { m.trz = w; w += dd_nwtab_words(L1, L2); }
+  if (flags & kLdsFastX) dd_reg_lds(m.f[0], w, dd_code_words(L1), dd_ring_words(L1), DD_CAP * L1);
+  if (flags & kLdsFastY) dd_reg_lds(m.f[1], w, dd_code_words(L2), dd_ring_words(L2), DD_CAP * L2);
+  const uint32_t c1 = dd_code_words(L1), c2 = dd_code_words(L2), r1 = dd_ring_words(L1), r2 = dd_ring_words(L2);
+  if (flags & kLdsShared) { dd_reg_lds(m.f[0], w, (flags & kLdsSharedHbm) ? 0 : (c1 > c2 ? c1 : c2), r1 > r2 ? r1 : r2, DD_CAP * (L1 > L2 ? L1 : L2)); m.f[1] = m.f[0]; }
+  m.end = w + (m.align16 ? 4 : 0); return m;
+}
+static inline __host__ __device__ dd_lds dd_folder_lds(uint32_t L, uint32_t form, uint32_t K) {
+  dd_lds m; uint32_t w = 0;
+  m.align16 = (form & (kFoldSpan | kFoldWg)) != 0;
+  if (form & kFoldSpan) dd_span_lds(m.f[0], w, L);
+  else if (form & (kFoldReg | kFoldRegHbm)) dd_reg_lds(m.f[0], w, (form & kFoldReg) ? dd_code_words(L) : 0, dd_ring_words(L), DD_CAP * L);
+  else if (form & kFoldWg) { m.f[0].wg = w; w += dd_wg_words(L, K); }
+  m.end = w + (m.align16 ? 4 : 0); return m;
+}
+static inline __device__ uint32_t* dd_lds_at(unsigned char* s, const dd_lds& m, uint32_t off) {
+  uint32_t* b = (uint32_t*)(m.align16 ? (((uintptr_t)s + 15) & ~(uintptr_t)15) : (uintptr_t)s);
+  return off == kDdNoLds ? nullptr : b + off;
+}
 int dd_pack_launch(const dd_node* d_nodes, uint32_t nnodes, const uint32_t* d_off, uint32_t* d_out, hipStream_t st);
 int dd_solve_launch(const dd_node* d_nodes, uint32_t nnodes, dd_params prm, size_t lds_bytes, bool split, uint32_t* d_paused, hipStream_t st);
 // standalone decoders on dense device matrices (one workgroup each)

@@ -1922,24 +1922,16 @@ __device__ __forceinline__ void dd_folder(const dd_node& nd, const dd_params& pr
   const nuss_ws& ws = isx ? nd.wx : nd.wy;
   uint8_t* trb_g = isx ? nd.trb_x : nd.trb_y;
   uint32_t* ss = isx ? nd.x : nd.y;
-  const uint32_t nw = (uint32_t)(((size_t)L * (L + 1) / 2 + 7) / 8);
-  uint32_t *trbp = nullptr, *lck = nullptr;
-  float* ring = nullptr;
-  float* P = (float*)s_dd;  // traceback stack of the register form: inside its ring, which is idle by then
-  // span form (fold_fast bit 4 / 5): codes, dp triangle, candidate values and row offsets, split rows -- as in k_dd_solve
-  const bool span = (nd.fold_fast & (isx ? 16u : 32u)) != 0;
+  const uint32_t nw = dd_code_words(L);
+  // this folder's form (nd.fold_fast) and its LDS regions (dd_folder_lds); P: the traceback stack
+  const uint32_t form = dd_fold_form(nd.fold_fast, isx ? 0 : 1), K = dd_fold_k(nd.fold_fast, isx ? 0 : 1);
+  const dd_lds lay = dd_folder_lds(L, form, K);
+  uint32_t *trbp = dd_lds_at(s_dd, lay, lay.f[0].trb), *lck = dd_lds_at(s_dd, lay, lay.f[0].lck), *ckl = dd_lds_at(s_dd, lay, lay.f[0].ck);
+  float *ring = (float*)dd_lds_at(s_dd, lay, lay.f[0].ring), *P = (float*)dd_lds_at(s_dd, lay, lay.f[0].stk);
+  float *tri = (float*)dd_lds_at(s_dd, lay, lay.f[0].tri), *cvl = (float*)dd_lds_at(s_dd, lay, lay.f[0].cv);
+  const bool span = (form & kFoldSpan) != 0;
   const bool span_mw = L > 64 && !prm.span_one_wave;  // a wavefront per row slot (one slot: nothing to share out)
-  float *tri = nullptr, *cvl = nullptr;
-  uint32_t* ckl = nullptr;
-  if (span) {
-    uint32_t* w = (uint32_t*)(((uintptr_t)s_dd + 15) & ~(uintptr_t)15);
-    trbp = w; w += dd_span_nib_words(L); tri = (float*)w; w += dd_span_tri_words(L);
-    cvl = (float*)w; w += DD_CAP * (L + 1); ckl = w; w += DD_CAP * (L + 1); lck = w;
-    P = cvl;  // traceback stack: the candidate values are dead once the DP is through
-    for (uint32_t e = tid; e < dd_span_tri_words(L); e += nt) tri[e] = 0.0f;  // spans 0..2 hold 0 and are never written
-  } else
-  if (nd.fold_fast & (isx ? 1u : 2u)) { trbp = (uint32_t*)s_dd; ring = (float*)(trbp + nw); lck = (uint32_t*)(ring + dd_ring_words(L)); P = ring; }
-  else if (nd.fold_fast & (isx ? 4u : 8u)) { ring = (float*)s_dd; lck = (uint32_t*)(ring + dd_ring_words(L)); P = ring; }  // codes in HBM
+  if (span) for (uint32_t e = tid; e < dd_span_tri_words(L); e += nt) tri[e] = 0.0f;  // spans 0..2 hold 0 and are never written
   for (uint32_t it = t_first;; ++it) {
     if (tid == 0) {
       uint32_t g = 0;
@@ -1993,10 +1985,9 @@ __device__ __forceinline__ void dd_folder(const dd_node& nd, const dd_params& pr
       const nuss_ws none = {nullptr, nullptr, nullptr, nullptr, nullptr};
       const float wf = prm.w * 2 * (isx ? nd.n1 : nd.n2) / (nd.n1 + nd.n2);  // dafs.cpp:1091-1092, as in k_dd_solve
       for (uint32_t i = tid; i < L; i += nt) ss[i] = DD_NONE;  // a register-form traceback cut short may have left marks
-      if (nd.fold_fast & (isx ? 64u : 128u)) {
+      if (form & kFoldWg) {
         // beyond the register forms: the workgroup form (rolling rows and candidate heads in LDS, tables by span)
-        float* lds = (float*)(((uintptr_t)s_dd + 15) & ~(uintptr_t)15);
-        const uint32_t K = (nd.fold_fast >> (isx ? 8 : 12)) & 15u;
+        float* lds = (float*)dd_lds_at(s_dd, lay, lay.f[0].wg);
         const float* Ss = isx ? nd.s_xs : nd.s_ys;
         const unsigned long long tf0 = prm.stamps ? wall_clock64() : 0ull;
         const float sc = K == 4 ? nuss_wg_span<4>(L, Ss, ws, lds) : K == 2 ? nuss_wg_span<2>(L, Ss, ws, lds) : nuss_wg_span<0>(L, Ss, ws, lds);
@@ -2063,51 +2054,21 @@ __global__ __launch_bounds__(DD_SOLVE_THREADS) void k_dd_solve(const dd_node* no
     if (resume) { c = nd.fstate[0]; eta = nd.fstate[1]; s_prev = nd.fstate[2]; }
     s_eta = eta; s_bad = 0; s_lost = 0;
   }
-  // dynamic LDS: whichever traceback tables and in-flight rows fit (nd.lds_flags, decided by the host): bit 0 alignment,
-  // bit 1 x, bit 2 y
+  // dynamic LDS: whichever traceback tables and in-flight rows fit (nd.lds_flags, decided by the host; regions: dd_node_lds)
   extern __shared__ unsigned char s_dd[];
   const uint32_t Wx = dd_fold_cols(L1), Wy = dd_fold_cols(L2), Wz = nd.nw_w;
-  // previous-row buffers and candidate counters of the HBM-table folding forms: room of their own only when the
-  // fold has no on-chip region (otherwise they borrow its ring, see dd_ring_words) and this workgroup folds at all
-  const bool fastx = (nd.lds_flags & (2u | 8u)) != 0, fasty = (nd.lds_flags & (4u | 8u)) != 0;
-  float *Px = nullptr, *Py = nullptr;
-  unsigned char* lds_tail;
-  lds_tail = s_dd;
-  // bit 0: packed alignment traceback; bit 1 / bit 2: the fast form of the x / y folding DP
-  // (in-flight rows, candidate lists and packed traceback codes)
-  const uint32_t nzw = dd_nwtab_words(L1, L2), nxw = (uint32_t)(((size_t)L1 * (L1 + 1) / 2 + 7) / 8),
-                 nyw = (uint32_t)(((size_t)L2 * (L2 + 1) / 2 + 7) / 8);
-  uint32_t *trzp = nullptr, *trxp = nullptr, *tryp = nullptr;
-  float *ringx = nullptr, *ringy = nullptr;
-  uint32_t *lckx = nullptr, *lcky = nullptr;
-  // span form (bit 6): dp triangle, candidate values and row offsets of each folding
-  const bool spanxy = (nd.lds_flags & 64u) != 0;
-  float *trix = nullptr, *triy = nullptr, *cvx = nullptr, *cvy = nullptr;
-  uint32_t *ckx = nullptr, *cky = nullptr;
-  {
-    uint32_t* w = (uint32_t*)lds_tail;
-    if (spanxy) {
-      w = (uint32_t*)(((uintptr_t)w + 15) & ~(uintptr_t)15);  // 16-byte candidate slots
-      trxp = w; w += dd_span_nib_words(L1); trix = (float*)w; w += dd_span_tri_words(L1);
-      cvx = (float*)w; w += DD_CAP * (L1 + 1); ckx = w; w += DD_CAP * (L1 + 1); lckx = w; w += DD_CAP * L1;
-      tryp = w; w += dd_span_nib_words(L2); triy = (float*)w; w += dd_span_tri_words(L2);
-      cvy = (float*)w; w += DD_CAP * (L2 + 1); cky = w; w += DD_CAP * (L2 + 1); lcky = w; w += DD_CAP * L2;
-    }
-    if (nd.lds_flags & 1) { trzp = w; w += nzw; }
-    if (nd.lds_flags & 2) { trxp = w; w += nxw; ringx = (float*)w; w += dd_ring_words(L1); lckx = w; w += DD_CAP * L1; }
-    if (nd.lds_flags & 4) { tryp = w; w += nyw; ringy = (float*)w; w += dd_ring_words(L2); lcky = w; w += DD_CAP * L2; }
-    if (nd.lds_flags & 8) {  // one region for both folding DPs, used by x and then by y
-      const uint32_t Lm = L1 > L2 ? L1 : L2, rw1 = dd_ring_words(L1), rw2 = dd_ring_words(L2);
-      if (!(nd.lds_flags & 16)) { trxp = tryp = w; w += nxw > nyw ? nxw : nyw; }  // bit 4: the codes go to HBM instead
-      ringx = ringy = (float*)w; w += rw1 > rw2 ? rw1 : rw2;
-      lckx = lcky = w; w += DD_CAP * Lm;
-    }
-    if (fastx) Px = ringx;
-    if (fasty) Py = ringy;
-    if (spanxy) { Px = cvx; Py = cvy; }  // traceback stacks: the candidate values are dead once the DP is through
-  }
-
-  const bool shared_xy = (nd.lds_flags & 8) != 0;
+  const uint32_t nzw = dd_nwtab_words(L1, L2), nxw = dd_code_words(L1), nyw = dd_code_words(L2);
+  const dd_lds lay = dd_node_lds(L1, L2, nd.lds_flags);
+  const dd_fold_lds &lx = lay.f[0], &ly = lay.f[1];
+  uint32_t *trzp = dd_lds_at(s_dd, lay, lay.trz), *trxp = dd_lds_at(s_dd, lay, lx.trb), *tryp = dd_lds_at(s_dd, lay, ly.trb);
+  float *ringx = (float*)dd_lds_at(s_dd, lay, lx.ring), *ringy = (float*)dd_lds_at(s_dd, lay, ly.ring);
+  uint32_t *lckx = dd_lds_at(s_dd, lay, lx.lck), *lcky = dd_lds_at(s_dd, lay, ly.lck);
+  const bool spanxy = (nd.lds_flags & kLdsSpanXY) != 0;
+  float *trix = (float*)dd_lds_at(s_dd, lay, lx.tri), *triy = (float*)dd_lds_at(s_dd, lay, ly.tri);
+  float *cvx = (float*)dd_lds_at(s_dd, lay, lx.cv), *cvy = (float*)dd_lds_at(s_dd, lay, ly.cv);
+  uint32_t *ckx = dd_lds_at(s_dd, lay, lx.ck), *cky = dd_lds_at(s_dd, lay, ly.ck);
+  float *Px = (float*)dd_lds_at(s_dd, lay, lx.stk), *Py = (float*)dd_lds_at(s_dd, lay, ly.stk);  // traceback stacks
+  const bool shared_xy = (nd.lds_flags & kLdsShared) != 0;
   __shared__ uint32_t s_x_done;  // iteration whose x folding (DP + traceback) has released the shared region
   if (tid == 0) s_x_done = 0xFFFFFFFFu;
   uint8_t* trz = nd.tr_z;
@@ -2217,7 +2178,7 @@ __global__ __launch_bounds__(DD_SOLVE_THREADS) void k_dd_solve(const dd_node* no
     if (wave == 2) {
       float sc;
       const unsigned long long tz0 = prm.stamps ? wall_clock64() : 0ull;
-      // the register form: codes packed in LDS when the plan has room for them (bit 0; one panel, up to DD_WNW columns per
+      // the register form: codes packed in LDS when the plan has room for them (kLdsNwTab; one panel, up to DD_WNW columns per
       // lane), else in HBM slots (any width: panels of 64 Wz columns)
       const bool reg_l = trzp && Wz <= DD_WNW && L2 < 64u * Wz;
       if (reg_l) sc = nw_wave_fast<1>(Wz, L1, L2, nd.pz_s, nd.qz_s, prm.th_a, nd.env4, (uint8_t*)trzp, nullptr, lane);

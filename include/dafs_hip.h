@@ -349,6 +349,17 @@ int dafs_hip_nodes_round(dafs_hip_ctx* ctx, uint32_t n_new, const dafs_node_inpu
                          const uint32_t* old_handles, const dafs_dd_params* prm, uint32_t max_iterations, uint32_t budget_us,
                          uint8_t* finished_old, uint8_t* finished_new);
 int dafs_hip_nodes_result(dafs_hip_ctx* ctx, uint32_t handle, dafs_node_output* out);
+/* The plan nodes_open gives a node of len1 x len2 columns under the solver's environment switches (DAFS_HIP_DD_*), read as
+ * it reads them: the LDS forms of its workgroup and of its split folders, the bytes each needs, the score copies it carves. */
+typedef struct {
+  uint32_t lds_flags, fold_fast, nw_w;  /* as in the device descriptor (dafs_amd/csrc/dd.h)                                 */
+  uint32_t lds, split_lds;              /* dynamic LDS bytes of the node's workgroup; of a split launch (0 = never split)   */
+  uint32_t s_x, s_y, s_xs, s_ys;        /* 1 = the node carves this score copy (sweep order x / y, by span x / y)          */
+} dafs_dd_node_plan;
+int dafs_hipk_dd_node_plan(uint32_t len1, uint32_t len2, dafs_dd_node_plan* out);
+/* 32-bit words of dynamic LDS the solver's layout gives a node's workgroup (role 0, lds_flags) or its x / y folder
+ * (role 1 / 2, the folder's form in fold_fast).                                                                        */
+uint32_t dafs_hipk_dd_lds_words(uint32_t len1, uint32_t len2, uint32_t lds_flags, uint32_t fold_fast, int role);
 int dafs_hip_nodes_close(dafs_hip_ctx* ctx);
 /* Device memory of the resident nodes (diagnostics): bytes reserved from the device, bytes held by open nodes now, and
  * the largest value the latter has had.  A node's memory is returned when dafs_hip_nodes_result has copied it out. */

@@ -86,6 +86,48 @@ def test_plan_covers_lengths():
     assert capi.pairhmm_plan(0, 10, 10, p) == -1
 
 
+def test_dd_node_plan_reproduces_the_recorded_plans(monkeypatch):
+    """dafs_hipk_dd_node_plan (the solver's node planner, as nodes_open runs it) against the plans recorded in
+    tests/golden/dd_node_plan.npz: (L1, L2) across every threshold of the forms, under each switch setting the GPU tests
+    use; and the planner's invariants -- every byte count within the solver's LDS budget, a form only where its score copy
+    is carved, the byte counts those of the kernels' LDS layout."""
+    from dafs_amd import capi
+    g = np.load(os.path.join(ROOT, "tests", "golden", "dd_node_plan.npz"))
+    cols = list(g["columns"])
+    budget = 156 * 1024
+    for k, switch in enumerate(g["switches"]):
+        for name in ("WIDE", "SPAN", "NWG", "WG", "SPAN_MW"):
+            monkeypatch.delenv("DAFS_HIP_DD_" + name, raising=False)
+        if switch:
+            monkeypatch.setenv(*switch.split("="))
+        rows = g["plans"][g["plans"][:, 0] == k]
+        assert len(rows) > 900
+        p = capi.DdNodePlan()
+        for row in rows:
+            L1, L2 = int(row[1]), int(row[2])
+            assert capi.dd_node_plan(L1, L2, p) == 0
+            got = [getattr(p, c) for c in cols[3:]]
+            assert got == [int(v) for v in row[3:]], (switch, L1, L2)
+            f, ff = p.lds_flags, p.fold_fast
+            assert p.lds <= budget and p.split_lds <= budget
+            assert p.lds == 4 * capi.dd_lds_words(L1, L2, f, 0, 0)
+            if f & 64:                                         # span form side by side: by-span copies
+                assert p.s_xs and p.s_ys and not f & (2 | 4 | 8)
+            else:                                              # register forms: sweep-order copies
+                assert not (f & (2 | 8)) or p.s_x
+                assert not (f & (4 | 8)) or p.s_y
+            folders = [4 * capi.dd_lds_words(L1, L2, 0, ff, r + 1) for r in range(2)]
+            for r, (sweep, byspan) in enumerate(((p.s_x, p.s_xs), (p.s_y, p.s_ys))):
+                form = (ff >> r) & (1 | 4 | 16 | 64)
+                assert bin(form).count("1") <= 1
+                assert not form & (16 | 64) or byspan
+                assert not form & (1 | 4) or sweep
+            if p.split_lds:
+                assert p.split_lds == max([p.lds] + folders)
+            else:
+                assert ff == 0
+
+
 def test_host_build_tree_matches_python_twin():
     """dafs_host_build_tree (host code inside the library, used by the CLI and the pipeline driver) against the
     Python restatement of DAFS::build_tree, on random similarity matrices with ties."""
