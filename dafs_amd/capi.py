@@ -95,8 +95,6 @@ _consistency = _sig("dafs_hip_consistency", C.c_int, [C.c_void_p, C.c_float, C.c
 _consistency_match = _sig("dafs_hip_consistency_match", C.c_int, [C.c_void_p, C.c_float])
 _consistency_bp = _sig("dafs_hip_consistency_bp", C.c_int, [C.c_void_p, C.c_float])
 _fourway_consistency = _sig("dafs_hip_fourway_consistency", C.c_int, [C.c_void_p, C.c_float])
-_consistency_match_range = _sig("dafs_hip_consistency_match_range", C.c_int, [C.c_void_p, C.c_float, C.c_uint64, C.c_uint64])
-_mp_install = _sig("dafs_hip_mp_install", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])
 _fold_begin = _sig("dafs_hip_fold_posteriors_begin", C.c_int, [C.c_void_p, C.c_int, C.c_float])
 _fold_end = _sig("dafs_hip_fold_posteriors_end", C.c_int, [C.c_void_p])
 
@@ -165,12 +163,12 @@ _update_basepairing = _sig("dafs_hip_update_basepairing", C.c_int, [C.c_void_p, 
 _consensus_structure = _sig("dafs_hip_consensus_structure", C.c_int,
                             [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p,
                              C.POINTER(C.c_float), C.c_void_p])
-_mp_export_dev = _sig("dafs_hip_mp_export_dev", C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.c_uint64] + [C.c_void_p] * 5 + [C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)])
-_mp_install_dev = _sig("dafs_hip_mp_install_dev", C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_uint64])
-_bp_export_dev = _sig("dafs_hip_bp_export_dev", C.c_int, [C.c_void_p] + [C.c_void_p] * 3 + [C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)])
-_set_bp_dev = _sig("dafs_hip_set_bp_dev", C.c_int, [C.c_void_p, C.c_uint32] + [C.c_void_p] * 4 + [C.c_uint64])
 _alignment_reliability = _sig("dafs_hip_alignment_reliability", C.c_int,
                               [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5)
+# dafs_allgather_fn(user, send, recv, bytes, hip_stream): the caller's collective of a sharded phase 1
+_allgather_fn = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
+_phase1_sharded = _sig("dafs_hip_phase1_sharded", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_float, C.c_float, C.c_float,
+                                                           C.c_int, C.c_float, _allgather_fn, C.c_void_p])
 
 
 class StageTime(C.Structure):
@@ -193,6 +191,19 @@ dd_lds_words = _sig("dafs_hipk_dd_lds_words", C.c_uint32, [C.c_uint32, C.c_uint3
 def check(rc):
     if rc != 0:
         raise DafsHipError("%s (code %d; hip: %s)" % (_strerror(rc).decode(), rc, _last_error().decode()))
+
+
+def _allgather_callback(allgather, failures):
+    """allgather(send_ptr, recv_ptr, nbytes) as a dafs_allgather_fn.  No exception may cross the library's frames: one that
+    allgather raises is appended to `failures` and the callback returns 1, which the library reports as DAFS_HIP_ECOMM."""
+    def cb(user, send, recv, nbytes, stream):
+        try:
+            allgather(send, recv, nbytes)
+        except BaseException as e:  # noqa: BLE001
+            failures.append(e)
+            return 1
+        return 0
+    return _allgather_fn(cb)
 
 
 def encode(seq):
@@ -361,19 +372,20 @@ class Context:
     def consistency_match(self, w_pct_a=0.25):
         check(_consistency_match(self._h, w_pct_a))
 
-    def consistency_match_range(self, w_pct_a, pair_begin, pair_end):
-        check(_consistency_match_range(self._h, w_pct_a, pair_begin, pair_end))
-
-    def mp_install(self, relaxed, nnz, rowptr, col, val, sim=None):
-        """a whole store from arrays in the layout of mp() / align_posteriors() results (dafs_hip_mp_install)"""
-        nnz = np.ascontiguousarray(nnz, np.uint32); rowptr = np.ascontiguousarray(rowptr, np.uint32)
-        col = np.ascontiguousarray(col, np.uint32); val = np.ascontiguousarray(val, np.float32)
-        sim = None if sim is None else np.ascontiguousarray(sim, np.float32)
-        check(_mp_install(self._h, relaxed, nnz.ctypes.data, rowptr.ctypes.data, col.ctypes.data if len(col) else None,
-                          val.ctypes.data if len(val) else None, None if sim is None else sim.ctypes.data))
-
     def consistency_bp(self, w_pct_s=0.25):
         check(_consistency_bp(self._h, w_pct_s))
+
+    def phase1_sharded(self, rank, world, align_model, th_a, w_pct_a, w_pct_s, fold_th, allgather, fold_model=0):
+        """dafs_hip_phase1_sharded: phase 1 on rank `rank` of `world` (every rank has set all the sequences, two at least);
+        afterwards every rank's context holds the complete stores.  allgather(send_ptr, recv_ptr, nbytes) is the collective:
+        nbytes of device memory from every rank into recv (world * nbytes, rank order), landed when it returns.  An exception
+        it raises ends the call with a DafsHipError (DAFS_HIP_ECOMM) chained to it."""
+        failures = []
+        fn = _allgather_callback(allgather, failures)  # referenced until the library returns
+        rc = _phase1_sharded(self._h, rank, world, align_model, th_a, w_pct_a, w_pct_s, fold_model, fold_th, fn, None)
+        if rc and failures:
+            raise DafsHipError("%s (code %d): %r" % (_strerror(rc).decode(), rc, failures[0])) from failures[0]
+        check(rc)
 
     # --- decoder plugins ---
     def nussinov(self, p, q, th, w=0.0):
@@ -490,35 +502,6 @@ class Context:
         r, u, p = C.c_uint64(), C.c_uint64(), C.c_uint64()
         check(_nodes_memory(self._h, C.byref(r), C.byref(u), C.byref(p)))
         return r.value, u.value, p.value
-
-    # --- device-resident exchange of the stores (device pointers as integers, e.g. torch.Tensor.data_ptr()) ---
-    def mp_sizes(self, relaxed):
-        """(pairs, entries = 2 * sum of nnz, row pointers) of a matching store"""
-        npairs, nnz, nrp = C.c_uint64(), C.c_uint64(), C.c_uint64()
-        check(_mp_result_size(self._h, relaxed, C.byref(npairs), C.byref(nnz), C.byref(nrp)))
-        return npairs.value, 2 * nnz.value, nrp.value
-
-    def mp_export_dev(self, relaxed, first, count, nnz, rowptr, col, val, sim, cap_entries):
-        nr, ne = C.c_uint64(), C.c_uint64()
-        check(_mp_export_dev(self._h, relaxed, first, count, nnz, rowptr, col, val, sim, cap_entries, C.byref(nr), C.byref(ne)))
-        return nr.value, ne.value
-
-    def mp_install_dev(self, relaxed, nnz, rowptr, col, val, sim, n_entries):
-        check(_mp_install_dev(self._h, relaxed, nnz, rowptr, col, val, sim, n_entries))
-
-    def bp_sizes(self, relaxed=0):
-        nnz, nrp = C.c_uint64(), C.c_uint64()
-        check(_bp_result_size(self._h, relaxed, C.byref(nnz), C.byref(nrp)))
-        return nnz.value, nrp.value
-
-    def bp_export_dev(self, rowptr, col, val, cap_entries):
-        nr, ne = C.c_uint64(), C.c_uint64()
-        check(_bp_export_dev(self._h, rowptr, col, val, cap_entries, C.byref(nr), C.byref(ne)))
-        return nr.value, ne.value
-
-    def set_bp_dev(self, seq_of_block, rowptr, col, val, n_entries):
-        order = np.ascontiguousarray(seq_of_block, np.uint32)
-        check(_set_bp_dev(self._h, len(order), order.ctypes.data, rowptr, col, val, n_entries))
 
     def stage_timing(self, enable=True):
         """per-kernel device timings on / off (dafs_hip_stage_timing: HIP events around every launch of the library)"""

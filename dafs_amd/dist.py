@@ -2,10 +2,11 @@
 
 Two users.  bench.py times phase 1 at the L0 (device pointer) level: cost-sorted deal of the pair jobs
 (shard_pairs) and ONE all-gather of a packed slab per step (ShardExchange).  phase1_sharded is the whole
-sharded phase 1 of a run on top of the L1 C ABI: folds by x mod G, pair posteriors and the matching
-consistency transform by contiguous pair-index ranges, each followed by a gather; after it every rank's
-context holds the complete stores and the rest of the run (guide tree, progressive phase) is replicated
-(phase 2 is tree-sequential).
+sharded phase 1 of a run: the library's dafs_hip_phase1_sharded (folds by x mod G, pair posteriors and the
+matching consistency transform by contiguous pair-index ranges, each followed by a gather), with
+torch.distributed supplying the collective (_allgather_into); after it every rank's context holds the
+complete stores and the rest of the run (guide tree, progressive phase) is replicated (SURVEY.md 8e:
+phase 2 is tree-sequential).
 
 One process per GPU (torch.distributed; backend "nccl" is RCCL over xGMI on ROCm, "gloo" in the CPU
 tests).  The N(N-1)/2 pair jobs are independent: they are sorted by cost and dealt round-robin to the
@@ -151,205 +152,45 @@ class ShardExchange:
 
 
 # ---------------------------------------------------------------------------------------------
-# sharded phase 1 of a whole run (L1 C ABI + torch.distributed; gloo in the tests, nccl = RCCL on a node)
+# sharded phase 1 of a whole run: dafs_hip_phase1_sharded, torch.distributed as its collective
 # ---------------------------------------------------------------------------------------------
-def _comm_device(dist, device):
+def _allgather_into(dist, send_t, recv_t):
+    """recv_t[r * n:(r + 1) * n] = send_t of rank r (n elements each), landed when this returns: what dafs_allgather_fn
+    promises the library, which enqueues its reads of recv on a stream of its own as soon as the callback returns.  nccl
+    (RCCL) gathers on the device; gloo, which the tests with several ranks on one GPU use, through host memory."""
     import torch
-    return device if dist.get_backend() == "nccl" else torch.device("cpu")
+    if dist.get_backend() == "nccl":
+        dist.all_gather_into_tensor(recv_t, send_t)
+    else:
+        host = torch.empty(recv_t.shape, dtype=recv_t.dtype)
+        dist.all_gather_into_tensor(host, send_t.cpu())
+        recv_t.copy_(host)
+    if recv_t.is_cuda:
+        torch.cuda.synchronize(recv_t.device)
 
 
-def allgather_concat(dist, arr, device):
-    """concatenation over ranks (in rank order) of 1-D numpy arrays of different lengths: one size exchange, one
-    all-gather of max-padded rows"""
-    import torch
-    arr = np.ascontiguousarray(arr)
-    world = dist.get_world_size()
-    dev = _comm_device(dist, device)
-    n = torch.tensor([arr.size], dtype=torch.int64, device=dev)
-    sizes = [torch.zeros(1, dtype=torch.int64, device=dev) for _ in range(world)]
-    dist.all_gather(sizes, n)
-    sizes = [int(v.item()) for v in sizes]
-    mx = max(sizes + [1])
-    raw = np.zeros(mx * arr.itemsize, np.uint8)
-    raw[:arr.nbytes] = arr.view(np.uint8).reshape(-1)
-    send = torch.from_numpy(raw).to(dev)
-    recv = torch.empty(world * raw.size, dtype=torch.uint8, device=dev)
-    dist.all_gather_into_tensor(recv, send)
-    rows = recv.cpu().numpy().reshape(world, raw.size)
-    return np.concatenate([rows[r, :sizes[r] * arr.itemsize].view(arr.dtype) for r in range(world)])
+class _DeviceBytes:
+    """nbytes of device memory at ptr, in the form torch.as_tensor takes without copying (__cuda_array_interface__)"""
 
-
-def allreduce_sum(dist, arr, device):
-    """elementwise sum over ranks of equally shaped integer arrays (shards that are zero outside their own part)"""
-    import torch
-    dev = _comm_device(dist, device)
-    t = torch.from_numpy(np.ascontiguousarray(arr).astype(np.int64)).to(dev)
-    dist.all_reduce(t, op=dist.ReduceOp.SUM)
-    return t.cpu().numpy().astype(arr.dtype)
-
-
-def pair_ranges(npairs, world):
-    """contiguous row-major pair-index ranges, one per rank (what dafs_hip_align_posteriors takes)"""
-    return [npairs * k // world for k in range(world + 1)]
-
-
-def gather_parts(dist, parts, device):
-    """The one collective of an exchange: every rank contributes a list of 1-D 4-byte tensors on `device` (the same number
-    on every rank, lengths differ); returns, per part, the concatenation over the ranks in rank order -- on the device.
-    One tiny all-gather of the lengths (the strides have to be agreed), then ONE all_gather_into_tensor of the packed,
-    max-padded slab.  With the nccl backend (RCCL over xGMI) nothing touches host memory; gloo, which the CPU-side tests
-    use, carries the slab through the host."""
-    import torch
-    world = dist.get_world_size()
-    nccl = dist.get_backend() == "nccl"
-    cdev = device if nccl else torch.device("cpu")
-    mine = torch.tensor([int(p.numel()) for p in parts], dtype=torch.int64, device=cdev)
-    allsz = torch.empty(world * len(parts), dtype=torch.int64, device=cdev)
-    dist.all_gather_into_tensor(allsz, mine)
-    sizes = allsz.cpu().numpy().reshape(world, len(parts))
-    strides = sizes.max(axis=0)
-    offs = np.concatenate([[0], np.cumsum(strides)])
-    total = int(offs[-1])
-    if total == 0:
-        return [p[:0] for p in parts]
-    slab = torch.zeros(total, dtype=torch.int32, device=device)
-    for k, p in enumerate(parts):
-        if p.numel():
-            slab[int(offs[k]):int(offs[k]) + p.numel()] = p.view(torch.int32)
-    recv = torch.empty(world * total, dtype=torch.int32, device=cdev)
-    dist.all_gather_into_tensor(recv, slab if nccl else slab.cpu())
-    if not nccl:
-        recv = recv.to(device)
-    out = []
-    for k, p in enumerate(parts):
-        segs = [recv[r * total + int(offs[k]):r * total + int(offs[k]) + int(sizes[r, k])] for r in range(world)]
-        out.append(torch.cat(segs).view(p.dtype))
-    # the results go to the library next, which works on a stream of its own: what torch has queued (copies, concatenations)
-    # must have landed before it reads them
-    if device.type == "cuda":
-        torch.cuda.current_stream(device).synchronize()
-    return out
+    def __init__(self, ptr, nbytes):
+        self.__cuda_array_interface__ = {"shape": (nbytes,), "typestr": "|u1", "data": (ptr, False), "strides": None, "version": 2}
 
 
 def phase1_sharded(ctx, seqs, dist, device, align_model, th_a, w_pct_a, w_pct_s, fold_th=0.01):
-    """Phase 1 of DAFS::run (dafs.cpp:1787-1827) on `world` ranks, one context (one GPU) each, device-resident:
-      * base-pairing posteriors of the sequences x = rank (mod world): exported to device buffers, ONE all-gather, installed
-        by block (dafs_hip_bp_export_dev / dafs_hip_set_bp_dev);
-      * pair posteriors + similarity scores of this rank's contiguous pair-index range: ONE all-gather, installed
-        (dafs_hip_mp_export_dev / _install_dev) -- concatenating the ranks' ranges in rank order IS the whole in pair order;
-      * relax_matching_probability for this rank's range of OUTPUT pairs: ONE more all-gather, installed as the relaxed store;
-      * relax_basepairing_probability replicated (milliseconds).
-    Afterwards ctx is in the state a single-GPU phase 1 leaves it in, bit for bit.  torch supplies the buffers and the
-    collective (gather_parts); no array of the stores passes through host memory on the nccl backend."""
+    """Phase 1 of DAFS::run (dafs.cpp:1787-1827) on `world` ranks, one context (one GPU) each: dafs_hip_phase1_sharded,
+    with all_gather_into_tensor on the library's device buffers as the collective.  Afterwards ctx is in the state a
+    single-GPU phase 1 leaves it in, bit for bit.  `device` (the rank's GPU) is not needed: the buffers are the library's."""
     import torch
-    from . import capi
-    rank, world = dist.get_rank(), dist.get_world_size()
-    n = len(seqs)
-    npairs = n * (n - 1) // 2
-    i32 = lambda k: torch.empty(max(int(k), 1), dtype=torch.int32, device=device)
-    f32 = lambda k: torch.empty(max(int(k), 1), dtype=torch.float32, device=device)
     ctx.set_sequences(seqs)
-    # ---- folds: x = rank mod world, in a context of their own ----
-    mine = list(range(rank, n, world))
-    rp_t, col_t, val_t = i32(0)[:0], i32(0)[:0], f32(0)[:0]
-    if mine:
-        fc = capi.Context(ctx.device_index)
-        try:
-            fc.set_sequences([seqs[x] for x in mine])
-            fc.fold_posteriors(fold_th)
-            ne, nr = fc.bp_sizes(0)
-            rp_b, col_b, val_b = i32(nr), i32(ne), f32(ne)
-            nr, ne = fc.bp_export_dev(rp_b.data_ptr(), col_b.data_ptr(), val_b.data_ptr(), ne)
-            rp_t, col_t, val_t = rp_b[:nr], col_b[:ne], val_b[:ne]
-        finally:
-            fc.close()
-    rp_g, col_g, val_g = gather_parts(dist, [rp_t, col_t, val_t], device)
-    order = [x for r in range(world) for x in range(r, n, world)]  # sequence of the k-th gathered block
-    ctx.set_bp_dev(order, rp_g.data_ptr(), col_g.data_ptr(), val_g.data_ptr(), int(col_g.numel()))
-    # ---- pair posteriors of [b0, b1) ----
-    b = pair_ranges(npairs, world)
-    cnt = b[rank + 1] - b[rank]
-    parts = [i32(0)[:0], i32(0)[:0], i32(0)[:0], f32(0)[:0], f32(0)[:0]]
-    if cnt:
-        ctx.align_posteriors(align_model, th_a, pair_begin=b[rank], pair_end=b[rank + 1], fetch=False)
-        _, ne, nr = ctx.mp_sizes(0)
-        nnz_b, rp_b, col_b, val_b, sim_b = i32(cnt), i32(nr), i32(ne), f32(ne), f32(cnt)
-        nr, ne = ctx.mp_export_dev(0, 0, cnt, nnz_b.data_ptr(), rp_b.data_ptr(), col_b.data_ptr(), val_b.data_ptr(), sim_b.data_ptr(), ne)
-        parts = [nnz_b[:cnt], rp_b[:nr], col_b[:ne], val_b[:ne], sim_b[:cnt]]
-    nnz_g, rp_g, col_g, val_g, sim_g = gather_parts(dist, parts, device)
-    ctx.mp_install_dev(0, nnz_g.data_ptr(), rp_g.data_ptr(), col_g.data_ptr(), val_g.data_ptr(), sim_g.data_ptr(), int(col_g.numel()))
-    # ---- consistency: matching transform sharded by output pair, base-pairing transform replicated ----
-    if w_pct_a != 0.0:
-        parts = [i32(0)[:0], i32(0)[:0], i32(0)[:0], f32(0)[:0]]
-        if cnt:
-            ctx.consistency_match_range(w_pct_a, b[rank], b[rank + 1])
-            _, ne, nr = ctx.mp_sizes(1)          # entries of the shard; row pointers of all pairs (the range's are exported)
-            nnz_b, rp_b, col_b, val_b = i32(cnt), i32(nr), i32(ne), f32(ne)
-            nr, ne = ctx.mp_export_dev(1, b[rank], cnt, nnz_b.data_ptr(), rp_b.data_ptr(), col_b.data_ptr(), val_b.data_ptr(), None, ne)
-            parts = [nnz_b[:cnt], rp_b[:nr], col_b[:ne], val_b[:ne]]
-        nnz_g, rp_g, col_g, val_g = gather_parts(dist, parts, device)
-        ctx.mp_install_dev(1, nnz_g.data_ptr(), rp_g.data_ptr(), col_g.data_ptr(), val_g.data_ptr(), None, int(col_g.numel()))
-    if w_pct_s != 0.0:
+    if len(seqs) < 2:  # no pairs to share (the library refuses them): every rank runs the phase itself, as dafs --devices does
+        ctx.fold_posteriors(fold_th)
+        ctx.align_posteriors(align_model, th_a, fetch=False)
+        ctx.consistency_match(w_pct_a)
         ctx.consistency_bp(w_pct_s)
+        return
+    world = dist.get_world_size()
 
+    def allgather(send, recv, nbytes):
+        _allgather_into(dist, torch.as_tensor(_DeviceBytes(send, nbytes)), torch.as_tensor(_DeviceBytes(recv, world * nbytes)))
 
-def phase1_sharded_host(ctx, seqs, dist, device, align_model, th_a, w_pct_a, w_pct_s, fold_th=0.01):
-    """The same exchange through host arrays (round 2's form, kept as the cross-check of the device-resident one in
-    tests/test_dist_gpu.py)."""
-    from . import capi
-    rank, world = dist.get_rank(), dist.get_world_size()
-    n = len(seqs)
-    npairs = n * (n - 1) // 2
-    ctx.set_sequences(seqs)
-    # ---- folds: x = rank mod world, in a context of their own; rows gathered as three flat arrays ----
-    mine = list(range(rank, n, world))
-    rows = []
-    if mine:
-        fc = capi.Context(ctx.device_index)
-        try:
-            fc.set_sequences([seqs[x] for x in mine])
-            fc.fold_posteriors(fold_th)
-            rows = fc.bp(0)
-        finally:
-            fc.close()
-    rp = allgather_concat(dist, np.concatenate([r[0] for r in rows]) if rows else np.zeros(0, np.uint32), device)
-    col = allgather_concat(dist, np.concatenate([r[1] for r in rows]) if rows else np.zeros(0, np.uint32), device)
-    val = allgather_concat(dist, np.concatenate([r[2] for r in rows]) if rows else np.zeros(0, np.float32), device)
-    order = [x for r in range(world) for x in range(r, n, world)]  # sequence of the k-th gathered row block
-    all_rows = [None] * n
-    r0 = e0 = 0
-    for x in order:
-        L = len(seqs[x])
-        r = rp[r0:r0 + L + 1]
-        k = int(r[-1])
-        all_rows[x] = (r, col[e0:e0 + k], val[e0:e0 + k])
-        r0 += L + 1
-        e0 += k
-    ctx.set_bp(all_rows)
-    # ---- pair posteriors of [b0, b1): concatenating the ranks' arrays in rank order IS the whole in pair order ----
-    b = pair_ranges(npairs, world)
-    res = ctx.align_posteriors(align_model, th_a, pair_begin=b[rank], pair_end=b[rank + 1]) if b[rank + 1] > b[rank] else None
-    z32, zf = np.zeros(0, np.uint32), np.zeros(0, np.float32)
-    nnz = allgather_concat(dist, res.nnz if res else z32, device)
-    rowptr = allgather_concat(dist, res._rowptr if res else z32, device)
-    col = allgather_concat(dist, res._col if res else z32, device)
-    val = allgather_concat(dist, res._val if res else zf, device)
-    sim = allgather_concat(dist, res.sim if res else zf, device)
-    ctx.mp_install(0, nnz, rowptr, col, val, sim)
-    # ---- consistency: matching transform sharded by output pair, base-pairing transform replicated ----
-    if w_pct_a != 0.0:
-        if b[rank + 1] > b[rank]:
-            ctx.consistency_match_range(w_pct_a, b[rank], b[rank + 1])
-            part = ctx.mp(1)
-            p_nnz, p_rp, p_col, p_val = part.nnz, part._rowptr, part._col, part._val
-        else:
-            lens = np.array([len(s) for s in seqs], np.int64)
-            ii, jj = np.triu_indices(n, k=1)
-            p_nnz, p_rp, p_col, p_val = np.zeros(npairs, np.uint32), np.zeros(int((lens[ii] + lens[jj] + 2).sum()), np.uint32), z32, zf
-        nnz = allreduce_sum(dist, p_nnz, device)      # zero outside the shard
-        rowptr = allreduce_sum(dist, p_rp, device)
-        col = allgather_concat(dist, p_col, device)   # shard entries only, shards are in pair order
-        val = allgather_concat(dist, p_val, device)
-        ctx.mp_install(1, nnz, rowptr, col, val)
-    if w_pct_s != 0.0:
-        ctx.consistency_bp(w_pct_s)
+    ctx.phase1_sharded(dist.get_rank(), world, align_model, th_a, w_pct_a, w_pct_s, fold_th, allgather)

@@ -30,21 +30,39 @@ def test_strerror_and_codes():
     assert b"unknown" in capi._strerror(-99)
 
 
-def test_pair_ranges_of_the_sharded_phase_agree_with_the_python_driver():
-    """dafs_hip_pair_range (what dafs --devices shards by) = dist.pair_ranges (what the torch driver shards by): contiguous,
-    covering, in rank order -- so the ranks' shards concatenated in rank order are the whole in pair order"""
-    from dafs_amd import capi, dist
+def test_pair_ranges_of_the_sharded_phase():
+    """dafs_hip_pair_range (what dafs_hip_phase1_sharded shards by) = npairs * k // world: contiguous, covering, in rank
+    order -- so the ranks' shards concatenated in rank order are the whole in pair order"""
+    from dafs_amd import capi
     assert capi._strerror(-7).startswith(b"dafs_hip: the collective")
     f = capi.lib.dafs_hip_pair_range
     f.restype = None
     f.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     for npairs in (0, 1, 3, 8128, 130816, 10 ** 12 + 7):
         for world in (1, 2, 3, 8, 64):
-            want = dist.pair_ranges(npairs, world)
+            want = [npairs * k // world for k in range(world + 1)]
             for r in range(world):
                 b, e = C.c_uint64(), C.c_uint64()
                 f(npairs, world, r, C.byref(b), C.byref(e))
                 assert (b.value, e.value) == (want[r], want[r + 1]), (npairs, world, r)
+
+
+def test_a_raising_collective_makes_the_callback_fail():
+    """an exception of the caller's collective does not cross the library's frames: the dafs_allgather_fn returns non-zero
+    (DAFS_HIP_ECOMM in the library) and the exception is kept for Context.phase1_sharded to chain"""
+    from dafs_amd import capi
+    calls, failures = [], []
+
+    def ok(send, recv, nbytes):
+        calls.append((send, recv, nbytes))
+
+    def lost(send, recv, nbytes):
+        raise ConnectionError("peer gone")
+
+    assert capi._allgather_callback(ok, failures)(None, 4096, 8192, 24, None) == 0
+    assert calls == [(4096, 8192, 24)] and failures == []
+    assert capi._allgather_callback(lost, failures)(None, 4096, 8192, 24, None) != 0
+    assert len(failures) == 1 and isinstance(failures[0], ConnectionError)
 
 
 def test_residue_codes():

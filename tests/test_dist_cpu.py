@@ -135,8 +135,8 @@ def test_two_rank_all_gather_gloo():
     assert sorted(res) == [(0, "ok"), (1, "ok")], res
 
 
-def _worker_gathers(rank, world, port, q):
-    """the gather helpers of dist.phase1_sharded on ragged inputs (an empty contribution included)"""
+def _worker_allgather_into(rank, world, port, q):
+    """the collective phase1_sharded hands to the library: rank r's bytes land at recv[r * n:(r + 1) * n], several sizes"""
     sys.path.insert(0, ROOT)
     import torch
     import torch.distributed as dist
@@ -145,27 +145,15 @@ def _worker_gathers(rank, world, port, q):
     os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
     try:
-        dev = torch.device("cpu")
-        parts = [np.arange(5, dtype=np.uint32) * 3, np.zeros(0, np.uint32), np.array([7, 9], np.uint32)][:world]
-        got = dd.allgather_concat(dist, parts[rank], dev)
-        assert got.dtype == np.uint32 and np.array_equal(got, np.concatenate(parts))
-        fparts = [np.array([0.5, -2.0], np.float32), np.array([1e-9], np.float32), np.zeros(0, np.float32)][:world]
-        got = dd.allgather_concat(dist, fparts[rank], dev)
-        assert got.dtype == np.float32 and got.tobytes() == np.concatenate(fparts).tobytes()
-        full = np.zeros(11, np.uint32)
-        lo, hi = dd.pair_ranges(11, world)[rank], dd.pair_ranges(11, world)[rank + 1]
-        full[lo:hi] = np.arange(lo, hi) + 100
-        s = dd.allreduce_sum(dist, full, dev)
-        assert s.dtype == np.uint32 and np.array_equal(s, np.arange(11) + 100)
-        b = dd.pair_ranges(21, world)
-        assert b[0] == 0 and b[-1] == 21 and all(b[k] <= b[k + 1] for k in range(world))
-        # gather_parts: the packed one-collective form phase1_sharded uses (tensors in, tensors out; ragged and empty parts)
-        tparts = [[torch.from_numpy(parts[r].view(np.int32).copy()), torch.from_numpy(fparts[r].copy())] for r in range(world)]
-        gi, gf = dd.gather_parts(dist, tparts[rank], dev)
-        assert gi.dtype == torch.int32 and np.array_equal(gi.numpy().view(np.uint32), np.concatenate(parts))
-        assert gf.dtype == torch.float32 and gf.numpy().tobytes() == np.concatenate(fparts).tobytes()
-        ge, = dd.gather_parts(dist, [torch.zeros(0, dtype=torch.int32)], dev)   # nothing from anybody
-        assert ge.numel() == 0
+        mine = lambda r, n: (np.arange(n, dtype=np.int64) * 7 + 31 * r + n) % 256
+        for n in (1, 8, 24, 1000, 65536 + 3):
+            send = torch.from_numpy(mine(rank, n).astype(np.uint8))
+            recv = torch.full((world * n,), 0xEE, dtype=torch.uint8)
+            dd._allgather_into(dist, send, recv)
+            got = recv.numpy()
+            for r in range(world):
+                assert np.array_equal(got[r * n:(r + 1) * n], mine(r, n).astype(np.uint8)), (n, r)
+            assert np.array_equal(send.numpy(), mine(rank, n).astype(np.uint8)), n  # the send buffer is left as it was
         q.put((rank, "ok"))
     except Exception:  # noqa: BLE001
         import traceback
@@ -175,12 +163,12 @@ def _worker_gathers(rank, world, port, q):
 
 
 @pytest.mark.parametrize("world", [2, 3])
-def test_ragged_gathers_gloo(world):
+def test_allgather_into_gloo(world):
     import torch.multiprocessing as mp
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     port = _free_port()
-    procs = [ctx.Process(target=_worker_gathers, args=(r, world, port, q)) for r in range(world)]
+    procs = [ctx.Process(target=_worker_allgather_into, args=(r, world, port, q)) for r in range(world)]
     for p in procs:
         p.start()
     res = [q.get(timeout=180) for _ in procs]

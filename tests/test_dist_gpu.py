@@ -85,12 +85,11 @@ def test_rccl_exchange_on_one_rank():
     assert line["exchange"]["verified_pairs"] >= 200 and line["verified_pairs"] > 0
 
 
-def _worker_nccl(q, port, host_path):
+def _worker_nccl(q, port):
     sys.path.insert(0, ROOT)
     import torch
     import torch.distributed as dist
     from dafs_amd import capi, pipeline, synth
-    from dafs_amd import dist as dd
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY="0")
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(0)
@@ -98,8 +97,6 @@ def _worker_nccl(q, port, host_path):
     try:
         recs = synth.family_set(7, 60, seed=41) + synth.random_set(4, 50, seed=42)
         names, seqs = [r[0] for r in recs], [r[1] for r in recs]
-        if host_path:
-            dd.phase1_sharded, keep = dd.phase1_sharded_host, dd.phase1_sharded
         ctx = capi.Context(0)
         res = pipeline.run(names, seqs, ctx=ctx, align_model=1, shard=(dist, dev))
         sim = ctx.sim()
@@ -112,12 +109,10 @@ def _worker_nccl(q, port, host_path):
         dist.destroy_process_group()
 
 
-@pytest.mark.parametrize("host_path", [False, True])
-def test_sharded_whole_run_over_rccl(host_path):
-    """The whole sharded run with the nccl backend (= RCCL), world size 1 on the box's one GPU: phase 1's three exchanges are
-    all_gather_into_tensor calls on DEVICE buffers (dist.gather_parts; dafs_hip_*_export_dev / *_install_dev on either
-    side), nothing of the stores passes through host memory.  Must equal the ordinary single-process run; the host-array
-    form of round 2 (phase1_sharded_host) is run through the same backend as the cross-check."""
+def test_sharded_whole_run_over_rccl():
+    """The whole sharded run with the nccl backend (= RCCL), world size 1 on the box's one GPU: dafs_hip_phase1_sharded's
+    exchanges are all_gather_into_tensor calls on the library's DEVICE buffers (dist._allgather_into), nothing of the
+    stores passes through host memory.  Must equal the ordinary single-process run."""
     import torch.multiprocessing as mp
     from dafs_amd import capi, pipeline, synth
     recs = synth.family_set(7, 60, seed=41) + synth.random_set(4, 50, seed=42)
@@ -128,9 +123,30 @@ def test_sharded_whole_run_over_rccl(host_path):
     ctx.close()
     mpc = mp.get_context("spawn")
     q = mpc.Queue()
-    p = mpc.Process(target=_worker_nccl, args=(q, _free_port(), host_path))
+    p = mpc.Process(target=_worker_nccl, args=(q, _free_port()))
     p.start()
     out, sim, backend = q.get(timeout=120)
     p.join(timeout=60)
     assert not out.startswith("FAILED"), out
     assert backend == "nccl" and out == want.output and sim == want_sim
+
+
+def test_a_raising_collective_ends_the_sharded_phase_with_its_cause():
+    """The collective of Context.phase1_sharded raises: the library returns DAFS_HIP_ECOMM at the first exchange and the
+    DafsHipError it becomes carries the original exception as its cause"""
+    from dafs_amd import capi, synth
+
+    class Lost(Exception):
+        pass
+
+    def allgather(send, recv, nbytes):
+        raise Lost("peer gone")
+
+    ctx = capi.Context(0)
+    try:
+        ctx.set_sequences([s for _, s in synth.random_set(3, 40, seed=5)])
+        with pytest.raises(capi.DafsHipError) as e:
+            ctx.phase1_sharded(0, 1, capi.ALIGN_PROBCONS, 0.01, 0.25, 0.25, 0.01, allgather)
+        assert "code -7" in str(e.value) and isinstance(e.value.__cause__, Lost)
+    finally:
+        ctx.close()
