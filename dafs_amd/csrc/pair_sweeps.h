@@ -68,12 +68,19 @@ __device__ __forceinline__ int pair_width(int L2) {
 // instantiate every sweep for both), W = slab stride.  post(sv, p) turns the WR slab values of a step into posteriors.
 //
 // Entries are rare (a few per row), so sweep 3 does not write the thresholded plane back for a fourth sweep over every
-// cell to re-read: each lane appends a 12-byte record per entry {p, row-1 | c<<16, position in its row | position in
-// its column << 16} to a private list (`list`: a second plane of the wave's scratch, same [k*64 + lane] layout), and
-// sweep 4 walks the lists -- a third less HBM traffic for the whole kernel, and ~40 list steps instead of ~190 grid
-// steps.  A lane whose list is full (more than a third of its cells are entries: th near 0) makes the call return
-// false with nothing emitted and the slab untouched; the caller then runs the dense = true instantiation, which is
-// the plane-and-rescan form.
+// cell to re-read: a lane with at least one entry in a step appends ONE record for that step to a private list (`list`: a
+// second plane of the wave's scratch), {entry mask of its WR cells, row-1 | entries of the row left of its columns << 16,
+// the WR posteriors}, padded to whole 16-byte words (WR <= 6: 32 bytes, two dwordx4 stores, one branch per step), and
+// sweep 4 walks the lists, rebuilding an entry's position in its row from the carried count plus the mask's lower bits
+// and its position in its column from a running count per column -- a third less HBM traffic for the whole kernel, and
+// one list step per lane-step with entries instead of ~190 grid steps.  A lane whose list is full (entries in most of
+// its steps: th near 0) makes the call return false with nothing emitted and the slab untouched; the caller then runs
+// the dense = true instantiation, which is the plane-and-rescan form.
+template <int WR>
+struct pair_rec {
+  static constexpr int Q = (2 + WR + 3) / 4;  // 16-byte words per record
+  static constexpr int D = 4 * Q;             // dwords per record (a lane's list holds list_cap / D records)
+};
 template <int G, int W, int WR, bool dense, class Args, class Post>
 __device__ __forceinline__ bool pair_finish(const Args& a, float* __restrict__ slab, float* __restrict__ list, int list_cap, uint32_t* __restrict__ s_rowptr,
                                             int lane, int t, int g, int L1, int L2, int nsteps, bool act, uint32_t task, float th, Post post) {
@@ -118,8 +125,7 @@ __device__ __forceinline__ bool pair_finish(const Args& a, float* __restrict__ s
       // One straight-line block for the WR cells (the posteriors' polynomials, the similarity DP and the counts as
       // selects: five independent chains the scheduler can interleave), then the rare appends.  Written as per-cell
       // if / else, every cell becomes a handful of basic blocks and its polynomial waits for the cell before it.
-      bool ent[WR];
-      int runa[WR];  // entries of the row up to and including cell c
+      uint32_t emask = 0;  // entries among the WR cells, bit c = cell c
 #pragma unroll
       for (int c = 0; c < WR; ++c) {
         const int j = j0 + c;
@@ -128,7 +134,6 @@ __device__ __forceinline__ bool pair_finish(const Args& a, float* __restrict__ s
         // wrapper (>= th keeps) then adapter (> th keeps): align.cpp:69-78
         const float p = pp[c];
         const bool entry = inner && (p >= th) && (p > th);
-        ent[c] = entry;
         if (dense) slab_s[c * 64 + lane] = entry ? p : 0.0f;
         // calculate_similarity_score, dafs.cpp:720-760: an entry starts from the diagonal (dp = ddp + p) and is replaced
         // by the left, then the upper neighbour where that is strictly larger; a non-entry starts from the left one.
@@ -146,29 +151,27 @@ __device__ __forceinline__ bool pair_finish(const Args& a, float* __restrict__ s
         ddp = udp; dtr = utr;
         pdp[c] = dp; ptr[c] = tr;
         ldp = dp; ltr = tr;
-        run += entry ? 1 : 0;
-        colcnt[c] += entry ? 1 : 0;
-        runa[c] = run;
+        const int e = entry ? 1 : 0;
+        run += e;
+        colcnt[c] += e;
+        emask |= (uint32_t)e << c;
       }
-      if (!dense) {
-        bool any = false;
+      if (!dense && emask != 0) {  // one record for the step (pair_rec): the only branch of the step's entries
+        if ((nrec + 1) * pair_rec<WR>::D <= list_cap) {
+          float w[pair_rec<WR>::D];
+          w[0] = __uint_as_float(emask);
+          w[1] = __int_as_float((i - 1) | (rcnt << 16));
 #pragma unroll
-        for (int c = 0; c < WR; ++c) any = any || ent[c];
-        if (any) {
+          for (int c = 0; c < WR; ++c) w[2 + c] = pp[c];
 #pragma unroll
-          for (int c = 0; c < WR; ++c) {
-            if (ent[c]) {
-              if (3 * nrec + 3 <= list_cap) {
-                float* __restrict__ r = list + (size_t)(3 * nrec) * 64 + lane;
-                r[0] = pp[c];
-                r[64] = __int_as_float((i - 1) | (c << 16));
-                r[128] = __int_as_float((runa[c] - 1) | ((colcnt[c] - 1) << 16));  // positions before this entry
-                ++nrec;
-              } else {
-                ovf = true;
-              }
-            }
-          }
+          for (int c = 2 + WR; c < pair_rec<WR>::D; ++c) w[c] = 0.0f;
+          // 32-bit byte offset from the wave's list base (scalar base + vector offset: no 64-bit address per lane)
+          char* __restrict__ r = (char*)list + (uint32_t)(((uint32_t)nrec * pair_rec<WR>::Q * 64 + lane) * 16);
+#pragma unroll
+          for (int q = 0; q < pair_rec<WR>::Q; ++q) *(float4*)(r + q * 1024) = make_float4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
+          ++nrec;
+        } else {
+          ovf = true;
         }
       }
       dgdp = rdp; dgtr = rtr;
@@ -242,28 +245,43 @@ __device__ __forceinline__ bool pair_finish(const Args& a, float* __restrict__ s
 #pragma unroll
       for (int o = 1; o < 64; o <<= 1) maxrec = max(maxrec, __shfl_xor(maxrec, o));
       maxrec = __builtin_amdgcn_readfirstlane(maxrec);
-      float rp = 0.0f;
-      int r1 = 0, r2 = 0;
-      if (slab_nrec > 0) { rp = list[lane]; r1 = __float_as_int(list[64 + lane]); r2 = __float_as_int(list[128 + lane]); }
-      for (int k = 0; k < maxrec; ++k) {
-        const bool live = k < slab_nrec;
-        const float p = rp;
-        const int q1 = r1, q2 = r2;
-        if (k + 1 < slab_nrec) {  // next record, one iteration ahead
-          const float* __restrict__ r = list + (size_t)(3 * (k + 1)) * 64 + lane;
-          rp = r[0]; r1 = __float_as_int(r[64]); r2 = __float_as_int(r[128]);
-        }
-        if (live && ok) {
-          const int im1 = q1 & 0xFFFF, c = q1 >> 16;
-          int cb = 0;
+      constexpr int Q = pair_rec<WR>::Q;
+      int colrun[WR];  // entries of this lane's column c in the rows before the record's
 #pragma unroll
-          for (int cc = 0; cc < WR; ++cc) cb = (c == cc) ? colbase[cc] : cb;
-          const unsigned long long pos = off + s_rowptr[im1] + (uint32_t)(q2 & 0xFFFF);
-          a.ent_col[pos] = (uint32_t)(j0 + c - 1);
-          a.ent_val[pos] = p;
-          const unsigned long long tpos = off + nnz + (uint32_t)(cb + (q2 >> 16));
-          a.ent_col[tpos] = (uint32_t)im1;
-          a.ent_val[tpos] = p;
+      for (int c = 0; c < WR; ++c) colrun[c] = 0;
+      float4 nx[Q];  // next record, one iteration ahead
+#pragma unroll
+      for (int q = 0; q < Q; ++q) nx[q] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+      if (slab_nrec > 0) {
+#pragma unroll
+        for (int q = 0; q < Q; ++q) nx[q] = *(const float4*)((const char*)list + (uint32_t)((q * 64 + lane) * 16));
+      }
+      for (int k = 0; k < maxrec; ++k) {
+        float w[4 * Q];
+#pragma unroll
+        for (int q = 0; q < Q; ++q) { w[4 * q] = nx[q].x; w[4 * q + 1] = nx[q].y; w[4 * q + 2] = nx[q].z; w[4 * q + 3] = nx[q].w; }
+        if (k + 1 < slab_nrec) {
+#pragma unroll
+          for (int q = 0; q < Q; ++q) nx[q] = *(const float4*)((const char*)list + (uint32_t)((((uint32_t)(k + 1) * Q + q) * 64 + lane) * 16));
+        }
+        const uint32_t m = (k < slab_nrec) ? __float_as_uint(w[0]) : 0u;
+        const int im1 = __float_as_int(w[1]) & 0xFFFF;
+        const uint32_t rowpos = s_rowptr[im1] + (uint32_t)(__float_as_int(w[1]) >> 16);  // the row's first entry of this lane
+        int before = 0;  // entries of the record left of cell c
+#pragma unroll
+        for (int c = 0; c < WR; ++c) {
+          const int e = (int)((m >> c) & 1u);
+          if (e && ok) {
+            const float p = w[2 + c];
+            const unsigned long long pos = off + rowpos + (uint32_t)before;
+            a.ent_col[pos] = (uint32_t)(j0 + c - 1);
+            a.ent_val[pos] = p;
+            const unsigned long long tpos = off + nnz + (uint32_t)(colbase[c] + colrun[c]);
+            a.ent_col[tpos] = (uint32_t)im1;
+            a.ent_val[tpos] = p;
+          }
+          before += e;
+          colrun[c] += e;
         }
       }
     }
