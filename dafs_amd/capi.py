@@ -97,6 +97,7 @@ _consistency_bp = _sig("dafs_hip_consistency_bp", C.c_int, [C.c_void_p, C.c_floa
 _fourway_consistency = _sig("dafs_hip_fourway_consistency", C.c_int, [C.c_void_p, C.c_float])
 _fold_begin = _sig("dafs_hip_fold_posteriors_begin", C.c_int, [C.c_void_p, C.c_int, C.c_float])
 _fold_end = _sig("dafs_hip_fold_posteriors_end", C.c_int, [C.c_void_p])
+_pairs_from = _sig("dafs_hip_pairs_from", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, u32p, u32p])
 
 
 class NodeInput(C.Structure):
@@ -374,6 +375,20 @@ class Context:
 
     def consistency_bp(self, w_pct_s=0.25):
         check(_consistency_bp(self._h, w_pct_s))
+
+    def pairs_from(self, src, pair_x, pair_y):
+        """dafs_hip_pairs_from: this context becomes the P two-sequence families [pair_x[p], pair_y[p]] of src's sequences
+        (rows 2p and 2p + 1), with the raw stores and similarity blocks those inputs give, gathered from src on the device.
+        src: a one-family context after fold_posteriors and a full-pair-set align_posteriors, left unchanged."""
+        px = np.ascontiguousarray(pair_x, np.uint32)
+        py = np.ascontiguousarray(pair_y, np.uint32)
+        if px.ndim != 1 or px.shape != py.shape:
+            raise ValueError("pairs_from: pair_x and pair_y need one entry per pair")
+        check(_pairs_from(self._h, src._h, len(px), px.ctypes.data_as(u32p), py.ctypes.data_as(u32p)))
+        lens = np.empty(2 * len(px), np.uint32)
+        lens[0::2], lens[1::2] = src._lens[px], src._lens[py]
+        self._lens = lens
+        self._first = np.arange(0, 2 * len(px) + 1, 2, dtype=np.uint32)
 
     def phase1_sharded(self, rank, world, align_model, th_a, w_pct_a, w_pct_s, fold_th, allgather, fold_model=0):
         """dafs_hip_phase1_sharded: phase 1 on rank `rank` of `world` (every rank has set all the sequences, two at least);

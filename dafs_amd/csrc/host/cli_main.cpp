@@ -74,6 +74,8 @@ struct Options {
   std::vector<int> devices;  // --devices: one process per entry for phase 1
   std::string stockholm;  // --stockholm FILE
   std::string seed;       // --seed SEED: add FILE's sequences to this alignment
+  bool pairwise = false;  // --pairwise: every pair of FILE's sequences aligned as a two-sequence run
+  std::string pairwise_scores;  // --pairwise-scores OUT
   bool refinement_given = false;
   std::string input;
   std::vector<std::string> inputs;  // every FILE argument; with two or more, one output block per file
@@ -101,6 +103,12 @@ const char* kHelp =
     "                        as dafs prints it) without changing its columns; the output has no tree line, and\n"
     "                        --stockholm adds a #=GC RF line (x: seed column).  Not with -r, --bp-update, --devices,\n"
     "                        --align-aux, --fold-aux or --save-*-aux\n"
+    "      --pairwise        Align every pair of the one FILE's sequences (at least two) as two-sequence runs, the pairs\n"
+    "                        in row-major order: per pair a line \"==> i j <==\" (1-based input indices) and then what\n"
+    "                        dafs prints for a file of those two sequences; --stockholm writes one block per pair.\n"
+    "                        Not with -r, --seed, --devices, --align-aux, --fold-aux or --save-*-aux\n"
+    "      --pairwise-scores OUT  With --pairwise: a tab-separated table, one line per pair:\n"
+    "                        i j name_i name_j similarity score iterations (the root node's objective and iterations)\n"
     "\n Aligning options:\n"
     "  -a, --align-model arg Alignment model (value=CONTRAlign, ProbCons) (default: ProbCons)\n"
     "  -p, --align-pct arg   Weight of PCT for matching probabilities (default: 0.25)\n"
@@ -140,7 +148,7 @@ Options parse(int argc, char** argv) {
       {"no-alifold", {0, false}}, {"fold-th1", {'T', true}}, {"gamma1", {'G', true}}, {"ipknot", {0, false}},
       {"bp-update", {0, false}}, {"bp-update1", {0, false}}, {"fold-aux", {0, true}}, {"save-align-aux", {0, true}},
       {"save-fold-aux", {0, true}}, {"device", {0, true}}, {"devices", {0, true}}, {"input", {0, true}},
-      {"stockholm", {0, true}}, {"seed", {0, true}}};
+      {"stockholm", {0, true}}, {"seed", {0, true}}, {"pairwise", {0, false}}, {"pairwise-scores", {0, true}}};
   std::map<char, std::string> shorts;
   for (const auto& kv : spec)
     if (kv.second.first) shorts[kv.second.first] = kv.first;
@@ -208,6 +216,20 @@ Options parse(int argc, char** argv) {
       if (value.empty()) throw std::string("--seed needs a file name");
       o.seed = value;
     }
+    else if (name == "pairwise") o.pairwise = true;
+    else if (name == "pairwise-scores") {
+      if (value.empty()) throw std::string("--pairwise-scores needs a file name");
+      o.pairwise_scores = value;
+    }
+  }
+  if (!o.pairwise_scores.empty() && !o.pairwise) throw std::string("--pairwise-scores needs --pairwise");
+  if (o.pairwise) {  // every pair is a two-sequence run of its own: nothing that reads or writes one run's whole state
+    if (o.refinement_given) throw std::string("--pairwise: -r cannot be combined with --pairwise");
+    if (!o.seed.empty()) throw std::string("--pairwise: --seed cannot be combined with --pairwise");
+    if (!o.devices.empty()) throw std::string("--pairwise: --devices cannot be combined with --pairwise (use --device)");
+    if (!o.align_aux.empty() || !o.fold_aux.empty() || !o.save_align_aux.empty() || !o.save_fold_aux.empty())
+      throw std::string("--pairwise: --align-aux, --fold-aux, --save-align-aux and --save-fold-aux cannot be combined with --pairwise");
+    if (o.inputs.size() > 1) throw std::string("--pairwise needs exactly one input FILE");
   }
   if (!o.seed.empty()) {  // the seed's columns stay as they are: nothing may realign its rows
     if (o.refinement_given) throw std::string("--seed: -r would realign the seed's rows; it cannot be combined with --seed");
@@ -830,8 +852,19 @@ int rank_allgather(void* user, const void* send, void* recv, size_t bytes, void*
   return 0;
 }
 
+// --pairwise: the pairs of one chunk, whose two-sequence families a run of align_group gathers from the source context of
+// the N sequences (dafs_hip_pairs_from) instead of computing its phase-1 inputs; per family its root node's score and
+// iteration count come back in score / iterations
+struct PairChunk {
+  const dafs_hip_ctx* src = nullptr;
+  std::vector<uint32_t> px, py;
+  std::vector<float> score;
+  std::vector<uint32_t> iterations;
+};
+
 int align_group(dafs_hip_ctx* ctx, const Options& o, Ranks& rk, int align_model, const std::vector<std::vector<Fasta> >& fams,
-                const std::vector<size_t>& members, const std::vector<std::ostream*>& out, const std::vector<std::string*>& sto);
+                const std::vector<size_t>& members, const std::vector<std::ostream*>& out, const std::vector<std::string*>& sto,
+                PairChunk* pc = nullptr);
 
 struct Guard {  // the context of a run, destroyed however the run ends
   dafs_hip_ctx* c;
@@ -851,10 +884,12 @@ void set_sequences(dafs_hip_ctx* ctx, const std::vector<Fasta>& fa) {
 // another) and both consistency transforms.  The device folding is only started at the beginning: it keeps one workgroup
 // per sequence busy, and the alignment posteriors and the matching-probability transform run beside it.
 void phase1_local(dafs_hip_ctx* ctx, const Options& o, int align_model, const std::vector<Fasta>& fa, const std::vector<uint32_t>& first,
-                  std::vector<float>& sim) {
+                  std::vector<float>& sim, const PairChunk* pc = nullptr) {
   const uint N = (uint)fa.size(), F = (uint)first.size() - 1;
   bool folding = false;
-  if (!o.fold_aux.empty()) {
+  if (pc) {  // --pairwise: both raw stores and the similarity blocks gathered from the N-sequence source
+    check(dafs_hip_pairs_from(ctx, pc->src, (uint32_t)pc->px.size(), pc->px.data(), pc->py.data()));
+  } else if (!o.fold_aux.empty()) {
     std::vector<BP> bp;
     load_fold_aux(o.fold_aux, fa, bp);
     upload_bp(ctx, bp);
@@ -872,7 +907,8 @@ void phase1_local(dafs_hip_ctx* ctx, const Options& o, int align_model, const st
     return;
   }
   // matching probabilities, transposes, similarities (:1796-1819), PCTs (:1822-1827)
-  if (!o.align_aux.empty()) load_align_aux(ctx, o.align_aux, fa);
+  if (pc) {}  // gathered by dafs_hip_pairs_from above
+  else if (!o.align_aux.empty()) load_align_aux(ctx, o.align_aux, fa);
   else check(dafs_hip_align_posteriors(ctx, align_model, o.align_th, 0, 0));
   if (!o.save_align_aux.empty()) save_align_aux(ctx, o.save_align_aux, fa);
   if (o.fourway != 0.0f) {  // relax_fourway_consistency (:1808-1809): needs the base-pairing rows, replaces mp_ before sim_
@@ -1051,6 +1087,113 @@ int run_add(const Options& o, int align_model) {
   return 0;
 }
 
+// --pairwise: the estimated device memory of one two-sequence family of lengths a, b (pipeline.pair_bytes: its phase-1
+// stores as pipeline.family_bytes counts them, and its root node, resident for the whole chunk), and the budget per chunk
+// (pipeline.DEFAULT_BATCH_BYTES)
+uint64_t pair_bytes(uint64_t a, uint64_t b) {
+  const uint64_t stores = 16 + 8 * (a * a + b * b) + 64 * (a + b) + 2 * 4096 + 8 * (a + b + 2) + 2 * std::min(a, b) * 24 * 32 + 4 * a * b;
+  const uint64_t node = 44 * (a * a + b * b) + 26 * (a + 1) * (b + 1) + 8 * (a + 63) * (b + 64) + 512 * (a + 1) * ((b + 2048) / 2048) + 128 * (a + b) +
+                        (1 << 14);
+  return stores + node;
+}
+const uint64_t kPairChunkBytes = 16ull << 30;
+
+// --pairwise-scores: one line per pair (pipeline.pairwise_scores_tsv writes the same bytes)
+std::string fmt9(float v) {
+  if (std::isnan(v)) return "nan";
+  char buf[64];
+  snprintf(buf, sizeof buf, "%.9g", (double)v);
+  return buf;
+}
+
+// `dafs --pairwise FILE` (pipeline.pairwise is the Python twin).  Phase 1 runs once over FILE's N
+// sequences in a source context, the folding beside the all-pairs posteriors and no transform; the pairs, row-major, go in
+// chunks under kPairChunkBytes through a second context, where dafs_hip_pairs_from gathers a chunk's two-sequence families
+// and align_group runs them as one batch of families.  Each pair prints "==> i j <==" and then what `dafs` prints for a file
+// of its two sequences.
+int run_pairwise(const Options& o, int align_model) {
+  std::vector<Fasta> fa;
+  Fasta::load(fa, o.input.c_str());
+  if (fa.size() < 2) throw std::string("--pairwise needs at least two sequences in the input");
+  const uint32_t N = (uint32_t)fa.size();
+  dafs_hip_ctx* src = nullptr;
+  check(dafs_hip_create(o.device, &src));
+  Guard src_guard{src};
+  set_sequences(src, fa);
+  check(dafs_hip_fold_posteriors_begin(src, DAFS_FOLD_CONTRAFOLD, kCutoff));
+  const int rc_align = dafs_hip_align_posteriors(src, align_model, o.align_th, 0, 0);
+  const int rc_fold = dafs_hip_fold_posteriors_end(src);
+  check(rc_align);
+  check(rc_fold);
+  std::vector<float> sim((size_t)N * N);
+  check(dafs_hip_get_sim(src, sim.data()));
+  dafs_hip_ctx* ctx = nullptr;
+  check(dafs_hip_create(o.device, &ctx));
+  Guard guard{ctx};
+
+  std::vector<std::pair<uint32_t, uint32_t> > pairs;
+  for (uint32_t x = 0; x < N; ++x)
+    for (uint32_t y = x + 1; y < N; ++y) pairs.push_back(std::make_pair(x, y));
+  std::vector<float> score(pairs.size(), 0.0f);
+  std::vector<uint32_t> iterations(pairs.size(), 0);
+  std::vector<std::string> sto_blocks;
+  Ranks rk;  // one process
+  for (size_t p0 = 0; p0 < pairs.size();) {
+    // the chunk: greedy in pair order (pipeline.pair_chunks); a pair over the budget runs alone
+    size_t p1 = p0;
+    uint64_t used = 0;
+    while (p1 < pairs.size()) {
+      const uint64_t b = pair_bytes(fa[pairs[p1].first].size(), fa[pairs[p1].second].size());
+      if (p1 > p0 && used + b > kPairChunkBytes) break;
+      used += b;
+      ++p1;
+    }
+    const size_t n = p1 - p0;
+    PairChunk pc;
+    pc.src = src;
+    pc.score.assign(n, 0.0f);
+    pc.iterations.assign(n, 0);
+    std::vector<std::vector<Fasta> > fams;
+    for (size_t k = p0; k < p1; ++k) {
+      pc.px.push_back(pairs[k].first);
+      pc.py.push_back(pairs[k].second);
+      fams.push_back({fa[pairs[k].first], fa[pairs[k].second]});
+    }
+    std::vector<size_t> members(n);
+    std::vector<std::ostringstream> outs(n);
+    std::vector<std::ostream*> os(n);
+    std::vector<std::string> sto(o.stockholm.empty() ? 0 : n);
+    std::vector<std::string*> sp;
+    for (size_t j = 0; j < n; ++j) {
+      members[j] = j;
+      os[j] = &outs[j];
+      if (!sto.empty()) sp.push_back(&sto[j]);
+    }
+    align_group(ctx, o, rk, align_model, fams, members, os, sp, &pc);
+    for (size_t j = 0; j < n; ++j) {
+      std::cout << "==> " << pairs[p0 + j].first + 1 << " " << pairs[p0 + j].second + 1 << " <==" << std::endl << outs[j].str();
+      score[p0 + j] = pc.score[j];
+      iterations[p0 + j] = pc.iterations[j];
+    }
+    sto_blocks.insert(sto_blocks.end(), sto.begin(), sto.end());
+    p0 = p1;
+  }
+  std::cout.flush();
+  if (!o.stockholm.empty()) write_stockholm(o.stockholm, sto_blocks);
+  if (!o.pairwise_scores.empty()) {
+    std::ofstream ts(o.pairwise_scores.c_str(), std::ios::binary);
+    if (!ts.is_open()) throw "--pairwise-scores: cannot open " + o.pairwise_scores;
+    for (size_t k = 0; k < pairs.size(); ++k) {
+      const uint32_t x = pairs[k].first, y = pairs[k].second;
+      ts << x + 1 << "\t" << y + 1 << "\t" << fa[x].name() << "\t" << fa[y].name() << "\t" << fmt9(sim[(size_t)x * N + y]) << "\t" << fmt9(score[k])
+         << "\t" << iterations[k] << "\n";
+    }
+    ts.flush();
+    if (!ts) throw "--pairwise-scores: cannot write " + o.pairwise_scores;
+  }
+  return 0;
+}
+
 int run(const Options& o, Ranks& rk) {
   // ---- option checks mirroring parse_options (:1683-1763)
   int align_model;
@@ -1072,6 +1215,7 @@ int run(const Options& o, Ranks& rk) {
     if (!o.fold_model_given && o.fold_aux.empty()) std::cerr << "note: default folding model is CONTRAfold in this build" << std::endl;
   }
   if (!o.seed.empty()) return run_add(o, align_model);
+  if (o.pairwise) return run_pairwise(o, align_model);
 
   // one family per input file
   const bool multi = o.inputs.size() > 1;
@@ -1144,7 +1288,8 @@ int run(const Options& o, Ranks& rk) {
 // family the refinement, the common structure and the output on *out[k]; with --stockholm (sto not empty) also the
 // family's Stockholm block in *sto[k].
 int align_group(dafs_hip_ctx* ctx, const Options& o, Ranks& rk, int align_model, const std::vector<std::vector<Fasta> >& fams,
-                const std::vector<size_t>& members, const std::vector<std::ostream*>& out, const std::vector<std::string*>& sto) {
+                const std::vector<size_t>& members, const std::vector<std::ostream*>& out, const std::vector<std::string*>& sto,
+                PairChunk* pc) {
   const uint F = (uint)members.size();
   std::vector<Fasta> fa;         // every sequence of the group, family after family
   std::vector<uint32_t> first(1, 0);
@@ -1153,8 +1298,10 @@ int align_group(dafs_hip_ctx* ctx, const Options& o, Ranks& rk, int align_model,
     first.push_back((uint32_t)fa.size());
   }
   const uint N = (uint)fa.size();
-  set_sequences(ctx, fa);
-  if (F > 1) check(dafs_hip_set_families(ctx, F, first.data()));
+  if (!pc) {  // dafs_hip_pairs_from sets the sequences and families itself
+    set_sequences(ctx, fa);
+    if (F > 1) check(dafs_hip_set_families(ctx, F, first.data()));
+  }
 
   const bool sharded = !o.devices.empty() && N > 1;
   if (!sharded && rk.rank != 0) return 0;  // a single sequence: nothing to share
@@ -1174,7 +1321,7 @@ int align_group(dafs_hip_ctx* ctx, const Options& o, Ranks& rk, int align_model,
     trees[0] = build_tree(sim, N);
   } else {
     std::vector<float> sim;
-    phase1_local(ctx, o, align_model, fa, first, sim);
+    phase1_local(ctx, o, align_model, fa, first, sim, pc);
     size_t blk = 0;  // the guide trees (:1830) from the families' similarity blocks; a single sequence has none
     for (uint f = 0; N > 1 && f < F; ++f) {
       const uint n = first[f + 1] - first[f];
@@ -1234,7 +1381,10 @@ int align_group(dafs_hip_ctx* ctx, const Options& o, Ranks& rk, int align_model,
     done[g] = true;
     ALN().swap(aln[l]);
     ALN().swap(aln[r]);
-    if (g == tbase[f + 1] - 1) score[f] = j.out.score;
+    if (g == tbase[f + 1] - 1) {
+      score[f] = j.out.score;
+      if (pc) { pc->score[f] = j.out.score; pc->iterations[f] = j.out.iterations; }
+    }
   });
   for (uint f = 0; f < F; ++f) {
     ALN& root = aln[tbase[f + 1] - 1];

@@ -502,3 +502,153 @@ def run_batch(families, ctx=None, max_bytes=None, **kw):
         if own:
             ctx.close()
     return out
+
+
+# ------------------------------------------------------------------------------------------------ all-against-all pairs
+def node_bytes(l1, l2):
+    """Device memory of one resident node of l1 x l2 columns (bytes), the bound test_configs_gpu._node_bytes_bound states
+    from capi_dd.cpp's nodes_open, folding arrays included: per cell of the two base-pairing matrices 19 + 25 bytes, per cell
+    of the alignment tables 26 bytes plus the padded sweep-order copies, traceback slots, row arrays and slack."""
+    l1, l2 = int(l1), int(l2)
+    return (44 * (l1 * l1 + l2 * l2) + 26 * (l1 + 1) * (l2 + 1) + 8 * (l1 + 63) * (l2 + 64) + 512 * (l1 + 1) * ((l2 + 2048) // 2048)
+            + 128 * (l1 + l2) + (1 << 14))
+
+
+def pair_bytes(l1, l2):
+    """Device memory of one two-sequence family of a pairwise run: its phase-1 stores (family_bytes) and its root node, which
+    is resident for the whole progressive phase of the chunk (every pair's one node opens in the first round)."""
+    return family_bytes([l1, l2]) + node_bytes(l1, l2)
+
+
+def all_pairs(n):
+    """every pair (x, y), x < y < n, in row-major order"""
+    return [(x, y) for x in range(n) for y in range(x + 1, n)]
+
+
+def check_pairs(n, pairs):
+    """The pair list of a pairwise run over n sequences as a list of (x, y) ints (all_pairs(n) for None); ValueError for
+    n < 2, a pair with x >= y, an index out of range or a repeated pair."""
+    if n < 2:
+        raise ValueError("pipeline.pairwise: at least two sequences")
+    if pairs is None:
+        return all_pairs(n)
+    out, seen = [], set()
+    for pr in pairs:
+        x, y = (int(v) for v in pr)
+        if not 0 <= x < y < n:
+            raise ValueError("pipeline.pairwise: pair (%d, %d) needs 0 <= x < y < %d" % (x, y, n))
+        if (x, y) in seen:
+            raise ValueError("pipeline.pairwise: pair (%d, %d) is repeated" % (x, y))
+        seen.add((x, y))
+        out.append((x, y))
+    if not out:
+        raise ValueError("pipeline.pairwise: the pair list is empty")
+    return out
+
+
+def pair_chunks(lens, pairs, max_bytes):
+    """The pairs (indices into `pairs`) in chunks of at most max_bytes of estimated device memory each (pair_bytes), greedy
+    in pair order; a pair over the budget runs alone."""
+    return pack_families([pair_bytes(lens[x], lens[y]) for x, y in pairs], max_bytes)
+
+
+def _fmt9(v):
+    """%.9g as C's printf writes it for the table (a NaN of either sign as "nan")"""
+    v = float(v)
+    return "nan" if v != v else "%.9g" % v
+
+
+def pairwise_scores_tsv(names, pairs, sim, score, iterations):
+    """The table of `dafs --pairwise FILE --pairwise-scores OUT` (the C++ writer in cli_main.cpp writes the same bytes): per
+    pair, in pair order, "i<TAB>j<TAB>name_i<TAB>name_j<TAB>sim<TAB>score<TAB>iterations" with 1-based i, j and the floats
+    as %.9g."""
+    return "".join("%d\t%d\t%s\t%s\t%s\t%s\t%d\n" % (x + 1, y + 1, names[x], names[y], _fmt9(sim[x, y]), _fmt9(score[x, y]),
+                                                     int(iterations[x, y])) for x, y in pairs)
+
+
+class Pairwise:
+    pass
+
+
+def pairwise(names, seqs, pairs=None, ctx=None, max_bytes=None, **opts):
+    """All pairwise structural alignments of a set of sequences (`dafs --pairwise`).  pairs: (x, y)
+    with x < y, default every pair in row-major order.  opts: the options of run() except mp / bp / shard.  Each pair's
+    Result is, bit for bit, what run([names[x], names[y]], [seqs[x], seqs[y]], **opts) gives (.output, .dd_log, .ss, .rows,
+    .sim and, with reliability, .reliability / .stockholm).
+
+    Phase 1 (folds, all-pairs posteriors, no transforms) runs once over the N sequences in a source context of its own; the
+    pairs go in chunks of at most max_bytes of estimated device memory (pair_chunks; default DEFAULT_BATCH_BYTES) through
+    `ctx`: Context.pairs_from builds the chunk's two-sequence families on the device, then the transforms, the nodes of all
+    of them in shared rounds (a two-leaf tree: its root alone) and the output.  Returns an object with .pairs, .results (one
+    Result per pair, in pair order), .sim (N x N: the pair kernels' scores, Context.sim() of the N-sequence phase 1),
+    .score and .iterations (N x N: the root node's final objective and iteration count, dd_log's 4th and 1st entries; NaN
+    and -1 on the diagonal and for pairs not asked), .chunks (pair indices per chunk), .dd_memory (per chunk the nodes'
+    (reserved, in use, peak) bytes) and .seconds (phase1, transforms, nodes, final, total)."""
+    import time
+    for k in ("mp", "bp", "shard"):
+        if k in opts:
+            raise ValueError("pipeline.pairwise: %s is a single-run option (use run)" % k)
+    if opts.get("level_sync") and opts.get("bp_update"):
+        raise ValueError("pipeline.pairwise: bp_update needs the resident-node schedule (level_sync=False)")
+    o = {k: p.default for k, p in inspect.signature(run).parameters.items() if k not in ("names", "seqs", "ctx", "bp", "mp", "shard")}
+    unknown = set(opts) - set(o)
+    if unknown:
+        raise TypeError("pipeline.pairwise: unknown options %s" % sorted(unknown))
+    o.update(opts)
+    names, seqs = list(names), list(seqs)
+    if len(names) != len(seqs):
+        raise ValueError("pipeline.pairwise: one name per sequence")
+    n = len(seqs)
+    pairs = check_pairs(n, pairs)
+    chunks = pair_chunks([len(s) for s in seqs], pairs, DEFAULT_BATCH_BYTES if max_bytes is None else int(max_bytes))
+    own = ctx is None
+    out = Pairwise()
+    out.pairs, out.chunks, out.results, out.dd_memory = pairs, chunks, [None] * len(pairs), []
+    out.score = np.full((n, n), np.nan, np.float32)
+    out.iterations = np.full((n, n), -1, np.int64)
+    secs = dict(phase1=0.0, transforms=0.0, nodes=0.0, final=0.0)
+    t_start = time.perf_counter()
+    src = capi.Context(0 if own else ctx.device_index)
+    try:
+        if own:
+            ctx = capi.Context(0)
+        # phase 1 once: the folding beside the all-pairs posteriors (as _phase1_local), no transform
+        src.set_sequences(seqs)
+        src.fold_begin(0.01)
+        try:
+            src.align_posteriors(o["align_model"], o["th_a"], fetch=False)
+        finally:
+            src.fold_end()
+        out.sim = src.sim()
+        secs["phase1"] = time.perf_counter() - t_start
+        for chunk in chunks:
+            t = [time.perf_counter()]
+            cp = [pairs[k] for k in chunk]
+            ctx.pairs_from(src, [x for x, _ in cp], [y for _, y in cp])
+            if o["w_pct_f"] != 0.0:
+                ctx.fourway_consistency(o["w_pct_f"])
+            sims = ctx.sim_blocks()
+            ctx.consistency_match(o["w_pct_a"])
+            ctx.consistency_bp(o["w_pct_s"])
+            t += [time.perf_counter()] * 3  # _phase2_forest's timestamps: fold_launch, pair, pct_fold_tree
+            fams = [dict(names=[names[x], names[y]], seqs=[seqs[x], seqs[y]], first=2 * j, sim=sims[j], tree=capi.build_tree(sims[j]))
+                    for j, (x, y) in enumerate(cp)]
+            res = _phase2_forest(ctx, False, fams, t, o["w"], o["eta0"], o["t_max"], o["th_a"], o["th_s"], o["th_s1"], o["force_iters"],
+                                 o["level_sync"], o["slice_iters"], o["skip_uncoupled_folds"], o["round_us"], o["bp_update"],
+                                 o["bp_update1"], o["reliability"])
+            secs["transforms"] += t[3] - t[0]
+            secs["nodes"] += t[4] - t[3]
+            secs["final"] += t[5] - t[4]
+            out.dd_memory.append(getattr(res[0], "dd_memory", None))
+            for k, (x, y), r in zip(chunk, cp, res):
+                it, _, _, sc = r.dd_log[2]
+                out.score[x, y] = out.score[y, x] = sc
+                out.iterations[x, y] = out.iterations[y, x] = it
+                out.results[k] = r
+    finally:
+        src.close()
+        if own and ctx is not None:
+            ctx.close()
+    secs["total"] = time.perf_counter() - t_start
+    out.seconds = secs
+    return out

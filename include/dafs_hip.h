@@ -421,6 +421,19 @@ int dafs_hip_bp_export_dev(dafs_hip_ctx* ctx, uint32_t* rowptr, uint32_t* col, f
 int dafs_hip_set_bp_dev(dafs_hip_ctx* ctx, uint32_t nblocks, const uint32_t* seq_of_block, const uint32_t* rowptr, const uint32_t* col, const float* val,
                         uint64_t n_entries);
 
+/* ---- all-against-all pairwise runs (dafs --pairwise, pipeline.pairwise) ----
+ * dafs_hip_pairs_from fills dst with the npairs two-sequence families [pair_x[p], pair_y[p]] (host arrays, x < y < N) of the
+ * N sequences of src: dst row 2p is sequence pair_x[p], row 2p + 1 is pair_y[p], family p holds rows 2p and 2p + 1.  src must
+ * hold one family of N >= 2 sequences with its raw stores complete (dafs_hip_fold_posteriors, or _begin/_end, and
+ * dafs_hip_align_posteriors of the whole pair set; no transform run on it).  dst receives the raw base-pairing rows of its
+ * sequences, per family its pair's raw mp[x][y] and transpose and the similarity block [[1, s_xy], [s_xy, 1]]: the state
+ * dafs_hip_set_sequences + dafs_hip_set_families + dafs_hip_fold_posteriors + dafs_hip_align_posteriors leave for that input,
+ * bit for bit, by device-to-device gathers (no recomputation).  The transforms, node rounds and decoders then run on dst
+ * unchanged.  src is not modified, so calls with different pair chunks may follow one another.  DAFS_HIP_EINVAL: contexts on
+ * different devices (or the same context), src with more than one family, missing or partial stores, a folding in flight,
+ * a pair with x >= y or y >= N. */
+int dafs_hip_pairs_from(dafs_hip_ctx* dst, const dafs_hip_ctx* src, uint32_t npairs, const uint32_t* pair_x, const uint32_t* pair_y);
+
 /* ---- phase 1 of DAFS::run on one rank of a multi-GPU run (src/dafs.cpp:1787-1827) ----
  * One process per GPU; every rank has called dafs_hip_set_sequences with all N sequences.  Rank r folds the sequences
  * x = r (mod world) (independent per sequence, src/fold.cpp:66-67), computes the pair posteriors and similarity scores of
