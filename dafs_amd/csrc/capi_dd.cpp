@@ -39,16 +39,11 @@ void carve_nuss(carver& cv, uint32_t L, nuss_ws& w);
 // skip_uncoupled_folds and no consensus pair) gets none of it, a third of its memory instead of all (27 GB -> 9 GB at the
 // 27 000-column root of c5-random).
 void carve_folding(carver& cv, dd_node& nd, const dafs_dd_node_plan& pl) {
-  const uint32_t L1 = nd.L1, L2 = nd.L2;
-  const size_t XX = (size_t)L1 * L1, YY = (size_t)L2 * L2;
-  carve_nuss(cv, L1, nd.wx);
-  carve_nuss(cv, L2, nd.wy);
-  nd.trk_x = nd.wx.tr; nd.trk_y = nd.wy.tr;  // the L*L uint32 tables double as bifurcation codes
-  nd.trb_x = cv.take<uint8_t>(XX / 2 + L1 + 16); nd.trb_y = cv.take<uint8_t>(YY / 2 + L2 + 16);
-  nd.s_x = pl.s_x ? cv.take<float>(((size_t)L1 + 63) * dd_fold_cols(L1) * 64) : nullptr;
-  nd.s_y = pl.s_y ? cv.take<float>(((size_t)L2 + 63) * dd_fold_cols(L2) * 64) : nullptr;
-  nd.s_xs = pl.s_xs ? cv.take<float>((size_t)L1 * ((L1 + 63) & ~63u) + 64) : nullptr;
-  nd.s_ys = pl.s_ys ? cv.take<float>((size_t)L2 * ((L2 + 63) & ~63u) + 64) : nullptr;
+  const uint32_t sweep[2] = {pl.s_x, pl.s_y}, by_span[2] = {pl.s_xs, pl.s_ys};
+  for (dd_fold& f : nd.f) { carve_nuss(cv, f.L, f.w); f.trk = f.w.tr; }  // the L*L uint32 tables double as bifurcation codes
+  for (dd_fold& f : nd.f) f.trb = cv.take<uint8_t>((size_t)f.L * f.L / 2 + f.L + 16);
+  for (int r = 0; r < 2; ++r) nd.f[r].s = sweep[r] ? cv.take<float>(((size_t)nd.f[r].L + 63) * dd_fold_cols(nd.f[r].L) * 64) : nullptr;
+  for (int r = 0; r < 2; ++r) nd.f[r].s_span = by_span[r] ? cv.take<float>((size_t)nd.f[r].L * ((nd.f[r].L + 63) & ~63u) + 64) : nullptr;
 }
 
 void carve_nuss(carver& cv, uint32_t L, nuss_ws& w) {
@@ -268,13 +263,13 @@ dafs_dd_node_plan plan_node(uint32_t L1, uint32_t L2, const dd_switches& sw) {
   // split plan: each folding on a workgroup of its own, the leader keeping the alignment DP (within p.lds).  Worth it when the
   // two do not run side by side; when their span forms fit a folder but not the node; when the span forms run side by side
   // but have more than one row slot, which a folder shares out to its wavefronts (nuss_span_mw); or without a register form.
-  const uint32_t Lm = std::max(L1, L2);
+  const uint32_t Lm = std::max(L1, L2), Ls[2] = {L1, L2};
   const bool span_folders = span_fits && !sw.wide && folder_bytes(Lm, kFoldSpan, 0) <= kDdLdsBudget &&
                             (!(f & kLdsSpanXY) || (sw.span_mw && Lm > 64));
   if ((!(f & (kLdsFastX | kLdsSpanXY)) || span_folders || sw.wg_force) && !sw.wide) {
     size_t worst = 0;
     for (uint32_t r = 0; r < 2; ++r) {
-      const uint32_t L = r ? L2 : L1;
+      const uint32_t L = Ls[r];
       const bool no_reg = !reg(L, DD_WFOLD) || sw.wg_force;
       uint32_t form = 0, K = 0;
       if (span_folders && !sw.wg_force) form = kFoldSpan;
@@ -289,12 +284,12 @@ dafs_dd_node_plan plan_node(uint32_t L1, uint32_t L2, const dd_switches& sw) {
     if (p.fold_fast || !reg(L1, DD_WFOLD) || !reg(L2, DD_WFOLD)) p.split_lds = (uint32_t)std::max(worst, (size_t)p.lds);
   }
   // the score copies these forms read: sweep order for the register forms, by span for the span and workgroup forms
-  const uint32_t fx = dd_fold_form(p.fold_fast, 0), fy = dd_fold_form(p.fold_fast, 1);
-  const bool span_any = (f & kLdsSpanXY) || ((fx | fy) & kFoldSpan);
-  p.s_x = reg(L1, DD_WFOLD) && !sw.wide && !(f & kLdsSpanXY);
-  p.s_y = reg(L2, DD_WFOLD) && !sw.wide && !(f & kLdsSpanXY);
-  p.s_xs = span_any || (fx & kFoldWg);
-  p.s_ys = span_any || (fy & kFoldWg);
+  const bool span_any = (f & kLdsSpanXY) || ((dd_fold_form(p.fold_fast, 0) | dd_fold_form(p.fold_fast, 1)) & kFoldSpan);
+  uint32_t *sweep[2] = {&p.s_x, &p.s_y}, *by_span[2] = {&p.s_xs, &p.s_ys};
+  for (uint32_t r = 0; r < 2; ++r) {
+    *sweep[r] = reg(Ls[r], DD_WFOLD) && !sw.wide && !(f & kLdsSpanXY);
+    *by_span[r] = span_any || (dd_fold_form(p.fold_fast, r) & kFoldWg);
+  }
   return p;
 }
 
@@ -306,11 +301,11 @@ struct dd_lane { hipStream_t st; dev_buf<dd_node>* d_nodes; dev_buf<uint32_t>* d
 dd_lane lane_of(dafs_hip_ctx* c, int k) { return k == 0 ? dd_lane{c->stream, &c->d_nodes, &c->d_paused, 0} : dd_lane{c->node_stream, &c->d_nodes2, &c->d_paused2, 1}; }
 
 // What a node's launch would read, checked on the host before anything is enqueued.  Every form of the folding DPs
-// reads one of the two score copies (s_x / s_y in sweep order for the column-owning register forms, s_xs / s_ys by span
+// reads one of the two score copies (dd_fold::s in sweep order for the column-owning register forms, dd_fold::s_span by span
 // for the span form), and nodes_open leaves out the copies no form of the node can use.  A plan that selects a form
 // whose copy is absent would make the kernel use a null base + cell offset as an address: that was the memory-access
-// fault of round 2 ("the fault at 16 x ~1100 columns": the multiplier updates wrote s_x[skew(i, j)] of
-// nodes beyond 1024 columns, whose s_x had just become optional).  The kernel's writes are guarded now; this check
+// fault of round 2 ("the fault at 16 x ~1100 columns": the multiplier updates wrote f[0].s[skew(i, j)] of
+// nodes beyond 1024 columns, whose sweep-order copy had just become optional).  The kernel's writes are guarded now; this check
 // turns any future mismatch between the carving and the form selection into DAFS_HIP_ELAUNCH instead of a fault.
 // folds: this launch runs the node's folding DPs (the kernel's fold_on: not (skip_uncoupled_folds and no consensus pair))
 int plan_check(const dd_node& nd, bool split, bool folds) {
@@ -318,36 +313,35 @@ int plan_check(const dd_node& nd, bool split, bool folds) {
     fprintf(stderr, "dafs_hip: node plan refused: %s\n", what);
     return DAFS_HIP_ELAUNCH;
   };
-  const void* always[] = {nd.seq1, nd.seq2, nd.rank1, nd.rank2, nd.idx1, nd.idx2, nd.idxoff1, nd.idxoff2, nd.p_x, nd.p_y, nd.p_z, nd.q_x, nd.q_y, nd.q_z,
-                          nd.nw_edge, nd.tr_z, nd.pz_s, nd.qz_s, nd.env, nd.env4, nd.xmap, nd.ymap, nd.zmap, nd.px_ptr, nd.px_j,
-                          nd.py_ptr, nd.py_l, nd.pz_ptr, nd.pz_k, nd.cz_ptr, nd.cz_k, nd.cx_flag, nd.cy_flag, nd.cz_flag, nd.cbp_cnt, nd.cbp, nd.sw,
-                          nd.tx, nd.ty, nd.tz, nd.x, nd.y, nd.z, nd.score, nd.info, nd.fstate, nd.sync};
-  for (const void* q : always)
-    if (!q) return bad("a null array in the node descriptor");
-  if (!nd.L1 || !nd.L2 || !nd.n1 || !nd.n2) return bad("empty child alignment");
+  auto any_null = [](std::initializer_list<const void*> arrays) { return std::find(arrays.begin(), arrays.end(), nullptr) != arrays.end(); };
+  if (any_null({nd.p_z, nd.q_z, nd.nw_edge, nd.tr_z, nd.pz_s, nd.qz_s, nd.env, nd.env4, nd.zmap, nd.pz_ptr, nd.pz_k, nd.cz_ptr, nd.cz_k, nd.cz_flag, nd.cbp_cnt,
+                nd.cbp, nd.sw, nd.tz, nd.z, nd.score, nd.info, nd.fstate, nd.sync}))
+    return bad("a null array in the node descriptor");
+  for (const dd_fold& f : nd.f) {
+    if (any_null({f.seq, f.rank, f.idx, f.idxoff, f.p, f.q, f.map, f.ptr, f.col, f.cflag, f.tc, f.ss})) return bad("a null array in the node descriptor");
+    if (!f.L || !f.n) return bad("empty child alignment");
+  }
   if (!folds) return DAFS_HIP_OK;  // nothing below is touched
-  const void* folding[] = {nd.wx.dp, nd.wx.tr, nd.wx.ck, nd.wx.cv, nd.wx.cc, nd.wy.dp, nd.wy.tr, nd.wy.ck, nd.wy.cv, nd.wy.cc, nd.trb_x, nd.trb_y, nd.trk_x, nd.trk_y};
-  for (const void* q : folding)
-    if (!q) return bad("a node that folds without its folding arrays (opened with skip_uncoupled_folds, advanced without?)");
-  const bool regx = dd_fold_cols(nd.L1) <= DD_WFOLD, regy = dd_fold_cols(nd.L2) <= DD_WFOLD;
-  if (!split) {
-    const uint32_t f = nd.lds_flags;
-    const bool span = (f & kLdsSpanXY) != 0;
-    if (span && (!nd.s_xs || !nd.s_ys)) return bad("span form without the by-span score copies");
-    if (span && (nd.L1 > DD_SPAN_LMAX || nd.L2 > DD_SPAN_LMAX)) return bad("span form beyond its width");
-    if (!span && (f & (kLdsFastX | kLdsShared)) && regx && !nd.s_x) return bad("register form of the x folding without its sweep-order scores");
-    if (!span && (f & (kLdsFastY | kLdsShared)) && regy && !nd.s_y) return bad("register form of the y folding without its sweep-order scores");
-  } else {
-    if (nd.lds_flags & ~kLdsNwTab) return bad("a split leader keeps the alignment DP only");
-    for (uint32_t r = 0; r < 2; ++r) {
-      const uint32_t L = r ? nd.L2 : nd.L1, form = dd_fold_form(nd.fold_fast, r);
-      const bool reg = r ? regy : regx;
-      const float *sweep = r ? nd.s_y : nd.s_x, *byspan = r ? nd.s_ys : nd.s_xs;
+  for (const dd_fold& f : nd.f)
+    if (any_null({f.w.dp, f.w.tr, f.w.ck, f.w.cv, f.w.cc, f.trb, f.trk}))
+      return bad("a node that folds without its folding arrays (opened with skip_uncoupled_folds, advanced without?)");
+  if (split && (nd.lds_flags & ~kLdsNwTab)) return bad("a split leader keeps the alignment DP only");
+  const bool span = !split && (nd.lds_flags & kLdsSpanXY) != 0;
+  static_assert(kLdsFastY == kLdsFastX << 1, "the register-form flag of folding r is kLdsFastX << r");
+  for (uint32_t r = 0; r < 2; ++r) {
+    const dd_fold& f = nd.f[r];
+    const bool reg = dd_fold_cols(f.L) <= DD_WFOLD;
+    if (!split) {
+      if (span && !f.s_span) return bad("span form without the by-span score copies");
+      if (span && f.L > DD_SPAN_LMAX) return bad("span form beyond its width");
+      if (!span && (nd.lds_flags & ((kLdsFastX << r) | kLdsShared)) && reg && !f.s) return bad("register form of a folding without its sweep-order scores");
+    } else {
+      const uint32_t form = dd_fold_form(nd.fold_fast, r);
       if (form & kFoldSpan) {
-        if (!byspan) return bad("span-form folder without the by-span score copy");
-        if (L > DD_SPAN_LMAX) return bad("span-form folder beyond its width");
-      } else if ((form & (kFoldReg | kFoldRegHbm)) && reg && !sweep) return bad("register-form folder without its sweep-order scores");
-      if ((form & kFoldWg) && !byspan) return bad("workgroup-form folder without the by-span score copy");
+        if (!f.s_span) return bad("span-form folder without the by-span score copy");
+        if (f.L > DD_SPAN_LMAX) return bad("span-form folder beyond its width");
+      } else if ((form & (kFoldReg | kFoldRegHbm)) && reg && !f.s) return bad("register-form folder without its sweep-order scores");
+      if ((form & kFoldWg) && !f.s_span) return bad("workgroup-form folder without the by-span score copy");
     }
   }
   return DAFS_HIP_OK;
@@ -399,28 +393,33 @@ int nodes_open_impl(dafs_hip_ctx* c, const dd_lane& ln, uint32_t nnodes, const d
     carver cv;
     std::vector<region> fills;
     const dafs_dd_node_plan& pl = plans[b] = plan_node(ni.len1, ni.len2, sw);
+    const geom* g[2] = {&g1[b], &g2[b]};
     for (int pass = 0; pass < 2; ++pass) {
       cv.used = 0;
       fills.clear();
       memset(&nd, 0, sizeof nd);
       const uint32_t L1 = ni.len1, L2 = ni.len2;
-      nd.n1 = ni.n1; nd.n2 = ni.n2; nd.L1 = L1; nd.L2 = L2;
-      const size_t XX = (size_t)L1 * L1, YY = (size_t)L2 * L2, ZZ = (size_t)L1 * L2;
-      nd.seq1 = cv.take<uint32_t>(ni.n1); nd.seq2 = cv.take<uint32_t>(ni.n2);
-      nd.rank1 = cv.take<uint32_t>((size_t)ni.n1 * L1); nd.rank2 = cv.take<uint32_t>((size_t)ni.n2 * L2);
-      nd.idx1 = cv.take<uint32_t>(g1[b].idx.size() + 1); nd.idx2 = cv.take<uint32_t>(g2[b].idx.size() + 1);
-      nd.idxoff1 = cv.take<uint32_t>(ni.n1); nd.idxoff2 = cv.take<uint32_t>(ni.n2);
+      nd.f[0].n = ni.n1; nd.f[1].n = ni.n2; nd.f[0].L = L1; nd.f[1].L = L2;
+      const size_t ZZ = (size_t)L1 * L2;
+      auto LL = [](const dd_fold& f) { return (size_t)f.L * f.L; };
+      for (dd_fold& f : nd.f) f.seq = cv.take<uint32_t>(f.n);
+      for (dd_fold& f : nd.f) f.rank = cv.take<uint32_t>((size_t)f.n * f.L);
+      for (int r = 0; r < 2; ++r) nd.f[r].idx = cv.take<uint32_t>(g[r]->idx.size() + 1);
+      for (dd_fold& f : nd.f) f.idxoff = cv.take<uint32_t>(f.n);
       // zero-filled block: posteriors, multipliers, flags
       const size_t z0 = (cv.used + 255) & ~(size_t)255;
-      nd.p_x = cv.take<float>(XX); nd.p_y = cv.take<float>(YY); nd.p_z = cv.take<float>(ZZ);
-      nd.q_x = cv.take<float>(XX); nd.q_y = cv.take<float>(YY); nd.q_z = cv.take<float>(ZZ);
+      for (dd_fold& f : nd.f) f.p = cv.take<float>(LL(f));
+      nd.p_z = cv.take<float>(ZZ);
+      for (dd_fold& f : nd.f) f.q = cv.take<float>(LL(f));
+      nd.q_z = cv.take<float>(ZZ);
       nd.cz_flag = cv.take<uint8_t>(ZZ);
-      nd.cx_flag = cv.take<uint8_t>(XX / 2 + 2); nd.cy_flag = cv.take<uint8_t>(YY / 2 + 2);
+      for (dd_fold& f : nd.f) f.cflag = cv.take<uint8_t>(LL(f) / 2 + 2);
       nd.sync = cv.take<uint32_t>(8);
       fills.push_back({z0, cv.used - z0, 0});
       // -1-filled block: dense id maps
       const size_t m0 = (cv.used + 255) & ~(size_t)255;
-      nd.xmap = cv.take<int32_t>(XX); nd.ymap = cv.take<int32_t>(YY); nd.zmap = cv.take<int32_t>(ZZ);
+      for (dd_fold& f : nd.f) f.map = cv.take<int32_t>(LL(f));
+      nd.zmap = cv.take<int32_t>(ZZ);
       fills.push_back({m0, cv.used - m0, 0xFF});
       // (the folding DPs' work arrays, codes and score copies are carved into the node's second block, once the
       // consensus-pair count says whether this node folds at all: carve_folding below)
@@ -433,13 +432,14 @@ int nodes_open_impl(dafs_hip_ctx* c, const dd_lane& ln, uint32_t nnodes, const d
       nd.pz_s = cv.take<float>(nw_panels * ((size_t)L1 + 63) * nd.nw_w * 64); nd.qz_s = cv.take<float>(nw_panels * ((size_t)L1 + 63) * nd.nw_w * 64);
       nd.env = cv.take<uint32_t>(2 * ((size_t)L1 + 1));
       nd.env4 = cv.take<uint32_t>(2 * ((size_t)L1 + 130));
-      nd.px_ptr = cv.take<uint32_t>((size_t)L1 + 2); nd.px_j = cv.take<uint32_t>(XX / 2 + 2);
-      nd.py_ptr = cv.take<uint32_t>((size_t)L2 + 2); nd.py_l = cv.take<uint32_t>(YY / 2 + 2);
+      for (dd_fold& f : nd.f) { f.ptr = cv.take<uint32_t>((size_t)f.L + 2); f.col = cv.take<uint32_t>(LL(f) / 2 + 2); }
       nd.pz_ptr = cv.take<uint32_t>((size_t)L1 + 2); nd.pz_k = cv.take<uint32_t>(ZZ + 1);
       nd.cz_ptr = cv.take<uint32_t>((size_t)L1 + 2); nd.cz_k = cv.take<uint32_t>(ZZ + 1);
-      nd.cbp_cnt = cv.take<uint32_t>(XX / 2 + 2);
-      nd.tx = cv.take<int32_t>(XX / 2 + 2); nd.ty = cv.take<int32_t>(YY / 2 + 2); nd.tz = cv.take<int32_t>(ZZ + 1);
-      nd.x = cv.take<uint32_t>((size_t)L1 + 2); nd.y = cv.take<uint32_t>((size_t)L2 + 2); nd.z = cv.take<uint32_t>((size_t)L1 + 2);
+      nd.cbp_cnt = cv.take<uint32_t>(LL(nd.f[0]) / 2 + 2);
+      for (dd_fold& f : nd.f) f.tc = cv.take<int32_t>(LL(f) / 2 + 2);
+      nd.tz = cv.take<int32_t>(ZZ + 1);
+      for (dd_fold& f : nd.f) f.ss = cv.take<uint32_t>((size_t)f.L + 2);
+      nd.z = cv.take<uint32_t>((size_t)L1 + 2);
       nd.score = cv.take<float>(1); nd.info = cv.take<uint32_t>(16); nd.fstate = cv.take<float>(4);
       if (pass == 0) {
         cv.base = c->dd_alloc(cv.used + 256);
@@ -451,16 +451,20 @@ int nodes_open_impl(dafs_hip_ctx* c, const dd_lane& ln, uint32_t nnodes, const d
       if (hip_check(hipMemsetAsync(cv.base + r.off, r.value, r.bytes, ln.st))) return DAFS_HIP_ELAUNCH;
     // the geometry arrays were carved first and back to back: one upload of the head of the block brings them all
     {
-      const size_t head = (size_t)((const uint8_t*)(nd.idxoff2 + ni.n2) - cv.base);
+      const size_t head = (size_t)((const uint8_t*)(nd.f[1].idxoff + ni.n2) - cv.base);
       std::vector<uint8_t>& blob = heads[b];
       blob.assign(head, 0);
       auto put = [&](const void* dst, const void* src, size_t bytes) {
         if (bytes) memcpy(blob.data() + ((const uint8_t*)dst - cv.base), src, bytes);
       };
-      put(nd.seq1, ni.seq1, (size_t)ni.n1 * 4); put(nd.seq2, ni.seq2, (size_t)ni.n2 * 4);
-      put(nd.rank1, g1[b].rank.data(), g1[b].rank.size() * 4); put(nd.rank2, g2[b].rank.data(), g2[b].rank.size() * 4);
-      put(nd.idx1, g1[b].idx.data(), g1[b].idx.size() * 4); put(nd.idx2, g2[b].idx.data(), g2[b].idx.size() * 4);
-      put(nd.idxoff1, g1[b].idxoff.data(), (size_t)ni.n1 * 4); put(nd.idxoff2, g2[b].idxoff.data(), (size_t)ni.n2 * 4);
+      const uint32_t* seqs[2] = {ni.seq1, ni.seq2};
+      for (int r = 0; r < 2; ++r) {
+        const dd_fold& f = nd.f[r];
+        put(f.seq, seqs[r], (size_t)f.n * 4);
+        put(f.rank, g[r]->rank.data(), g[r]->rank.size() * 4);
+        put(f.idx, g[r]->idx.data(), g[r]->idx.size() * 4);
+        put(f.idxoff, g[r]->idxoff.data(), (size_t)f.n * 4);
+      }
       if (hip_check(hipMemcpyAsync(cv.base, blob.data(), head, hipMemcpyHostToDevice, ln.st))) return DAFS_HIP_ELAUNCH;
     }
   }
@@ -478,8 +482,8 @@ int nodes_open_impl(dafs_hip_ctx* c, const dd_lane& ln, uint32_t nnodes, const d
   if ((rc = dd_avg_launch(ln.d_nodes->ptr, nnodes, max_len, mpv, bpv, sw.wide ? 1 : 0, coop, ln.st))) return rc;
   for (uint32_t b = 0; b < nnodes; ++b) {  // base-pairing matrices supplied by the caller (--bp-update) replace the averages
     const size_t XX = (size_t)in[b].len1 * in[b].len1, YY = (size_t)in[b].len2 * in[b].len2;
-    if (in[b].p_x && hip_check(hipMemcpyAsync(nodes[b].p_x, in[b].p_x, XX * 4, hipMemcpyHostToDevice, ln.st))) return DAFS_HIP_ELAUNCH;
-    if (in[b].p_y && hip_check(hipMemcpyAsync(nodes[b].p_y, in[b].p_y, YY * 4, hipMemcpyHostToDevice, ln.st))) return DAFS_HIP_ELAUNCH;
+    if (in[b].p_x && hip_check(hipMemcpyAsync(nodes[b].f[0].p, in[b].p_x, XX * 4, hipMemcpyHostToDevice, ln.st))) return DAFS_HIP_ELAUNCH;
+    if (in[b].p_y && hip_check(hipMemcpyAsync(nodes[b].f[1].p, in[b].p_y, YY * 4, hipMemcpyHostToDevice, ln.st))) return DAFS_HIP_ELAUNCH;
   }
   if ((rc = ln.d_paused->reserve(nnodes))) return rc;  // doubles as the landing place of the per-node counts
   if ((rc = dd_lists_launch(ln.d_nodes->ptr, nnodes, sw.wide ? 0 : max_len, dp, ln.d_paused->ptr, ln.st))) return rc;
@@ -596,7 +600,7 @@ int advance_launch(dafs_hip_ctx* c, const dd_lane& ln, uint32_t n, const uint32_
   // the result words of every node of the launch come along (one packed copy): a node that finishes here needs no
   // copy and no synchronisation of its own in dafs_hip_nodes_result
   stt.off.assign(nodes.size() + 1, 0);
-  for (size_t b = 0; b < nodes.size(); ++b) stt.off[b + 1] = stt.off[b] + (uint32_t)((nodes[b].info + 16) - nodes[b].x);
+  for (size_t b = 0; b < nodes.size(); ++b) stt.off[b + 1] = stt.off[b] + (uint32_t)((nodes[b].info + 16) - nodes[b].f[0].ss);
   const size_t total = stt.off[nodes.size()];
   dev_buf<uint32_t>& d_off = c->d_pack_off[ln.id];
   dev_buf<uint32_t>& d_pack = c->d_pack[ln.id];
@@ -647,28 +651,29 @@ int nodes_result(dafs_hip_ctx* c, uint32_t handle, dafs_node_output* out, bool s
   uint32_t info[16];
   float score = 0.0f;
   // x, y, z, score and info were carved back to back (nodes_open): one copy brings them all
-  const uint8_t* lo = (const uint8_t*)nd.x;
+  const dd_fold &fx = nd.f[0], &fy = nd.f[1];
+  const uint8_t* lo = (const uint8_t*)fx.ss;
   const uint8_t* hi = (const uint8_t*)(nd.info + 16);
-  if (hi <= lo || (size_t)(hi - lo) > ((size_t)2 * nd.L1 + nd.L2 + 64) * 4 + 8 * 256) return DAFS_HIP_EINVAL;
+  if (hi <= lo || (size_t)(hi - lo) > ((size_t)2 * fx.L + fy.L + 64) * 4 + 8 * 256) return DAFS_HIP_EINVAL;
   std::vector<uint8_t> blob((size_t)(hi - lo));
   const std::vector<uint32_t>& pre = c->dd_open[handle].result;
   if (pre.size() * 4 == blob.size()) memcpy(blob.data(), pre.data(), blob.size());  // came along with the launch the node finished in
   else if (hip_check(hipMemcpyAsync(blob.data(), lo, blob.size(), hipMemcpyDeviceToHost, c->stream)) || hip_check(hipStreamSynchronize(c->stream)))
     return DAFS_HIP_ELAUNCH;
   auto at = [&](const void* dev_ptr) { return blob.data() + ((const uint8_t*)dev_ptr - lo); };
-  if (out->x) memcpy(out->x, at(nd.x), (size_t)nd.L1 * 4);
-  if (out->y) memcpy(out->y, at(nd.y), (size_t)nd.L2 * 4);
-  if (out->z) memcpy(out->z, at(nd.z), (size_t)nd.L1 * 4);
+  if (out->x) memcpy(out->x, at(fx.ss), (size_t)fx.L * 4);
+  if (out->y) memcpy(out->y, at(fy.ss), (size_t)fy.L * 4);
+  if (out->z) memcpy(out->z, at(nd.z), (size_t)fx.L * 4);
   memcpy(&score, at(nd.score), 4);
   memcpy(info, at(nd.info), sizeof info);
   if (stamps && ((dd_fold_form(nd.fold_fast, 0) | dd_fold_form(nd.fold_fast, 1)) & (kFoldSpan | kFoldWg))) {
     uint32_t sy[8] = {0};
     if (!hip_check(hipMemcpy(sy, nd.sync, sizeof sy, hipMemcpyDeviceToHost)))
-      fprintf(stderr, "dd node L1=%u L2=%u folders | us: x-dp %.0f y-dp %.0f tracebacks %.0f\n", nd.L1, nd.L2, sy[5] / 100.0, sy[6] / 100.0, sy[7] / 100.0);
+      fprintf(stderr, "dd node L1=%u L2=%u folders | us: x-dp %.0f y-dp %.0f tracebacks %.0f\n", fx.L, fy.L, sy[5] / 100.0, sy[6] / 100.0, sy[7] / 100.0);
   }
   if (stamps)
-    fprintf(stderr, "dd node L1=%u L2=%u n=%u+%u ncbp=%u iters=%u slow-xy=%u+%u | us: x-dp %.0f x-traceback %.0f wait %.0f cbp %.0f update %.0f tail %.0f | y %.0f z %.0f flags %x\n", nd.L1,
-            nd.L2, nd.n1, nd.n2, info[0], info[1], info[4], info[5], info[8] / 100.0, info[9] / 100.0, info[10] / 100.0, info[11] / 100.0, info[12] / 100.0,
+    fprintf(stderr, "dd node L1=%u L2=%u n=%u+%u ncbp=%u iters=%u slow-xy=%u+%u | us: x-dp %.0f x-traceback %.0f wait %.0f cbp %.0f update %.0f tail %.0f | y %.0f z %.0f flags %x\n", fx.L,
+            fy.L, fx.n, fy.n, info[0], info[1], info[4], info[5], info[8] / 100.0, info[9] / 100.0, info[10] / 100.0, info[11] / 100.0, info[12] / 100.0,
             info[13] / 100.0, info[14] / 100.0, info[15] / 100.0, nd.lds_flags);
   out->score = score;
   out->ncbp = info[0];
@@ -842,19 +847,20 @@ static int average_and_decode(dafs_hip_ctx* c, uint32_t n, uint32_t len, const u
   int rc;
   if ((rc = make_geom(c, n, len, seq, mask, g))) return rc;
   dd_node nd;
+  dd_fold& f = nd.f[0];  // the one alignment; the node has no second one and no z
   carver cv;
   const size_t LL = (size_t)len * len;
   uint32_t* d_ss = nullptr;
   for (int pass = 0; pass < 2; ++pass) {
     cv.used = 0;
     memset(&nd, 0, sizeof nd);
-    nd.n1 = n; nd.L1 = len;
-    nd.seq1 = cv.take<uint32_t>(n);
-    nd.rank1 = cv.take<uint32_t>((size_t)n * len);
-    nd.idx1 = cv.take<uint32_t>(g.idx.size() + 1);
-    nd.idxoff1 = cv.take<uint32_t>(n);
-    nd.p_x = cv.take<float>(LL);
-    carve_nuss(cv, len, nd.wx);
+    f.n = n; f.L = len;
+    f.seq = cv.take<uint32_t>(n);
+    f.rank = cv.take<uint32_t>((size_t)n * len);
+    f.idx = cv.take<uint32_t>(g.idx.size() + 1);
+    f.idxoff = cv.take<uint32_t>(n);
+    f.p = cv.take<float>(LL);
+    carve_nuss(cv, len, f.w);
     d_ss = cv.take<uint32_t>((size_t)len + 1);
     nd.score = cv.take<float>(1);
     if (pass == 0) {
@@ -862,24 +868,24 @@ static int average_and_decode(dafs_hip_ctx* c, uint32_t n, uint32_t len, const u
       cv.base = c->work.ptr;
     }
   }
-  if (hip_check(hipMemsetAsync(nd.p_x, 0, LL * 4, c->stream))) return DAFS_HIP_ELAUNCH;
+  if (hip_check(hipMemsetAsync(f.p, 0, LL * 4, c->stream))) return DAFS_HIP_ELAUNCH;
   std::vector<uint32_t> rows(n);
   for (uint32_t r = 0; r < n; ++r) rows[r] = by_row ? r : seq[r];
-  if (hip_check(hipMemcpyAsync((void*)nd.seq1, rows.data(), n * 4, hipMemcpyHostToDevice, c->stream))) return DAFS_HIP_ELAUNCH;
-  if (hip_check(hipMemcpyAsync((void*)nd.rank1, g.rank.data(), g.rank.size() * 4, hipMemcpyHostToDevice, c->stream))) return DAFS_HIP_ELAUNCH;
-  if (hip_check(hipMemcpyAsync((void*)nd.idx1, g.idx.data(), g.idx.size() * 4, hipMemcpyHostToDevice, c->stream))) return DAFS_HIP_ELAUNCH;
-  if (hip_check(hipMemcpyAsync((void*)nd.idxoff1, g.idxoff.data(), n * 4, hipMemcpyHostToDevice, c->stream))) return DAFS_HIP_ELAUNCH;
+  if (hip_check(hipMemcpyAsync((void*)f.seq, rows.data(), n * 4, hipMemcpyHostToDevice, c->stream))) return DAFS_HIP_ELAUNCH;
+  if (hip_check(hipMemcpyAsync((void*)f.rank, g.rank.data(), g.rank.size() * 4, hipMemcpyHostToDevice, c->stream))) return DAFS_HIP_ELAUNCH;
+  if (hip_check(hipMemcpyAsync((void*)f.idx, g.idx.data(), g.idx.size() * 4, hipMemcpyHostToDevice, c->stream))) return DAFS_HIP_ELAUNCH;
+  if (hip_check(hipMemcpyAsync((void*)f.idxoff, g.idxoff.data(), n * 4, hipMemcpyHostToDevice, c->stream))) return DAFS_HIP_ELAUNCH;
   if ((rc = c->d_nodes.upload(&nd, 1, c->stream))) return rc;
   mp_store_dev none;
   memset(&none, 0, sizeof none);
   if ((rc = dd_avg_launch(c->d_nodes.ptr, 1, len, none, bps.view(), 0, 0, c->stream))) return rc;
   float s = 0;
   if (decode) {
-    if ((rc = nussinov_launch(len, nd.p_x, nullptr, 0.0f, th, nd.wx, d_ss, nd.score, c->stream))) return rc;
+    if ((rc = nussinov_launch(len, f.p, nullptr, 0.0f, th, f.w, d_ss, nd.score, c->stream))) return rc;
     if (hip_check(hipMemcpyAsync(ss, d_ss, (size_t)len * 4, hipMemcpyDeviceToHost, c->stream))) return DAFS_HIP_ELAUNCH;
     if (hip_check(hipMemcpyAsync(&s, nd.score, 4, hipMemcpyDeviceToHost, c->stream))) return DAFS_HIP_ELAUNCH;
   }
-  if (p_out && hip_check(hipMemcpyAsync(p_out, nd.p_x, LL * 4, hipMemcpyDeviceToHost, c->stream))) return DAFS_HIP_ELAUNCH;
+  if (p_out && hip_check(hipMemcpyAsync(p_out, f.p, LL * 4, hipMemcpyDeviceToHost, c->stream))) return DAFS_HIP_ELAUNCH;
   if (hip_check(hipStreamSynchronize(c->stream))) return DAFS_HIP_ELAUNCH;
   if (score) *score = s;
   return DAFS_HIP_OK;

@@ -15,40 +15,52 @@ struct nuss_ws {      // SparseNussinov work arrays for one problem of size L
   uint32_t* cc;       // L    candidates per column
 };
 
+// One child alignment of a node and the folding of its columns.  A node has two, f[0] = x and f[1] = y, indexed like
+// dd_lds::f and dd_fold_form; everything over a folding is written once and takes this.
+struct dd_fold {
+  uint32_t n, L;      // rows (sequences) and columns of the child alignment
+  // per row the sequence index, per (row, column) the residue rank or NONE, and per (row, residue) its column
+  const uint32_t *seq, *rank, *idx, *idxoff;
+  float *p, *q;       // L*L each: averaged base-pairing posteriors (dafs.cpp:561-607) and Lagrange multipliers
+  nuss_ws w;
+  uint8_t* trb;       // L(L+1)/2: Nussinov traceback codes 0..4 (HBM copy)
+  uint32_t* trk;      // L*L: bifurcation code of the cells whose traceback code is 4
+  float* s;           // (L+63)*ceil(L/64)*64: pair scores w*(p-th)-q in sweep order of the folding DP; null when the
+                      // folding has no register form (more than DD_WFOLD columns per lane)
+  float* s_span;      // L*Lp (Lp = L rounded up to 64): the same scores stored by span, S[(j-i)*Lp + i], for the span form
+                      // (nuss_wave_span); null when no launch of this node can take that form
+  // sparse structure of p (> CUTOFF, upper triangle) and of the consensus base pairs
+  int32_t* map;       // dense cell -> entry id or -1
+  uint32_t *ptr, *col;  // row pointers and columns of the entries
+  uint8_t* cflag;     // per entry: part of a consensus base pair (c_x / c_y, dafs.cpp:1038-1039)
+  int32_t* tc;        // per entry violation counter
+  uint32_t* ss;       // result: per column its partner or NONE
+};
+
 struct dd_node {
-  uint32_t n1, n2, L1, L2;
-  // child alignments: per row the sequence index, per (row, column) the residue rank or NONE,
-  // and per (row, residue) its column
-  const uint32_t *seq1, *seq2, *rank1, *rank2, *idx1, *idx2, *idxoff1, *idxoff2;
-  // averaged posteriors (dafs.cpp:513-607) and Lagrange multipliers
-  float *p_x, *p_y, *p_z, *q_x, *q_y, *q_z;
-  nuss_ws wx, wy;
+  dd_fold f[2];
+  // averaged matching posteriors of the alignment z of the two (dafs.cpp:513-559) and its Lagrange multipliers: f[0].L x f[1].L
+  float *p_z, *q_z;
   float* nw_edge;     // 2*(L1+2): the last column of a panel of the alignment DP, for the next panel (nw_wave_reg)
   uint8_t* tr_z;      // panels*(L1+1)*512: traceback codes of the alignment DP when they are not packed in LDS -- a 64-bit slot per (panel, row, lane)
   uint32_t nw_w;      // columns per lane of the alignment DP (dd_nw_cols; DAFS_HIP_DD_WIDE=1 makes it 1): second alignments beyond
                       // 64*nw_w - 1 columns run as panels of 64*nw_w columns; also the layout of pz_s / qz_s (nw_idx)
-  uint8_t *trb_x, *trb_y;   // L(L+1)/2 each: Nussinov traceback codes 0..4 (HBM copies)
-  uint32_t *trk_x, *trk_y;  // L*L each: bifurcation code of the cells whose traceback code is 4
-  float *s_x, *s_y;         // (L+63)*ceil(L/64)*64 each: pair scores w*(p-th)-q in sweep order of the folding DP; null when the
-                            // folding has no register form (more than DD_WFOLD columns per lane)
-  float *s_xs, *s_ys;       // L*Lp each (Lp = L rounded up to 64): the same scores stored by span, S[(j-i)*Lp + i], for the span form
-                            // (nuss_wave_span); null when no launch of this node can take that form
   float *pz_s, *qz_s;       // panels*(L1+63)*nw_w*64 each: p_z, q_z in sweep order of the alignment DP, panel by panel
   uint32_t lds_flags;       // LDS plan of the node's own workgroup: kLds* below (dd_node_lds lays it out)
   uint32_t* env;      // 2*(L1+1)
   uint32_t* env4;     // 2*(L1+130): the same envelope for the register-resident alignment DP -- {max(first,1), second} of row r at
                       // index r + 64, the empty range {1, 0} for the 64 rows before row 1 and the 65 behind row L1 (no clamping, no selects)
-  // sparse structure of p_x / p_y / p_z (> CUTOFF) and of the consensus base pairs
-  int32_t *xmap, *ymap, *zmap;    // dense cell -> entry id (px / py / cz lists) or -1
-  uint32_t *px_ptr, *px_j, *py_ptr, *py_l, *pz_ptr, *pz_k, *cz_ptr, *cz_k;
-  uint8_t *cx_flag, *cy_flag, *cz_flag;
-  uint32_t* cbp_cnt;              // per px entry
-  uint32_t* cbp;                  // 8 per consensus base pair: i j k l pxid pyid zid1 zid2
+  // sparse structure of p_z (> CUTOFF) and of the cells of z in a consensus base pair (c_z)
+  int32_t* zmap;                  // dense cell -> entry id (cz lists) or -1
+  uint32_t *pz_ptr, *pz_k, *cz_ptr, *cz_k;
+  uint8_t* cz_flag;
+  uint32_t* cbp_cnt;              // per entry of f[0]
+  uint32_t* cbp;                  // 8 per consensus base pair: i j k l, entry of f[0], entry of f[1], zid1 zid2
   uint32_t ncbp_cap;
-  int32_t *tx, *ty, *tz;          // per entry violation counters
+  int32_t* tz;                    // per cz entry violation counter
   float* sw;                      // ncbp: positive s_w, compacted in cbp order
-  // results
-  uint32_t *x, *y, *z;
+  // results (the foldings: f[r].ss)
+  uint32_t* z;
   float* score;                   // [1]
   uint32_t* info;                 // [16]: ncbp, iterations (next iteration while paused), violated, status, slow-x, slow-y,
                                   //       started, paused; [8..13] optional phase ticks
@@ -59,6 +71,8 @@ struct dd_node {
   uint32_t* sync;
   uint32_t split, fold_fast;
 };
+// k_dd_solve keeps the node in LDS beside its dynamic regions: kDdLdsBudget assumes this static part
+static_assert(sizeof(dd_node) <= 568, "dd_node must not grow");
 
 struct dd_params {
   float w, eta0, th_a, th_s;

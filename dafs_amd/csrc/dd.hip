@@ -1362,19 +1362,20 @@ __global__ __launch_bounds__(256) void k_node_avg(const dd_node* nodes, mp_store
   const uint32_t role = blockIdx.z;
   const int wave = (int)(threadIdx.x >> 6), lane = (int)(threadIdx.x & 63);
   if (coop && role == 2) {
-    const uint32_t L1 = nd.L1, L2 = nd.L2, I = blockIdx.x, tid = threadIdx.x;
+    const dd_fold &fx = nd.f[0], &fy = nd.f[1];
+    const uint32_t L1 = fx.L, L2 = fy.L, I = blockIdx.x, tid = threadIdx.x;
     if (I >= L1) return;
-    const uint32_t nsrc = nd.n1 * nd.n2;
+    const uint32_t nsrc = fx.n * fy.n;
     const float nn = (float)nsrc;
     float* row = s_rows;
     for (uint32_t J = tid; J < L2; J += 256) row[J] = 0.0f;
     auto get = [&](uint32_t me) {
       avg_src sr = {nullptr, nullptr, 0, nullptr};
-      const uint32_t r1 = me / nd.n2, r2 = me - r1 * nd.n2;
-      const uint32_t ii = nd.rank1[(size_t)r1 * L1 + I];
+      const uint32_t r1 = me / fy.n, r2 = me - r1 * fy.n;
+      const uint32_t ii = fx.rank[(size_t)r1 * L1 + I];
       if (ii != DD_NONE) {
-        const row_ref m = mp_row(mp, nd.seq1[r1], nd.seq2[r2], ii);
-        sr.col = m.col; sr.val = m.val; sr.n = m.n; sr.map = nd.idx2 + nd.idxoff2[r2];
+        const row_ref m = mp_row(mp, fx.seq[r1], fy.seq[r2], ii);
+        sr.col = m.col; sr.val = m.val; sr.n = m.n; sr.map = fy.idx + fy.idxoff[r2];
       }
       return sr;
     };
@@ -1429,21 +1430,18 @@ __global__ __launch_bounds__(256) void k_node_avg(const dd_node* nodes, mp_store
   float* row = s_rows + (size_t)wave * row_cap;
   uint2* stage = s_stage[wave];
   if (role < 2) {
-    const uint32_t L = role ? nd.L2 : nd.L1, n = role ? nd.n2 : nd.n1;
+    const dd_fold& f = nodes[blockIdx.y].f[role];  // from global memory: a run-time index into the private copy would send it to scratch
+    const uint32_t L = f.L, n = f.n;
     if (I >= L) return;
-    const uint32_t* seq = role ? nd.seq2 : nd.seq1;
-    const uint32_t* rank = role ? nd.rank2 : nd.rank1;
-    const uint32_t* idx = role ? nd.idx2 : nd.idx1;
-    const uint32_t* idxoff = role ? nd.idxoff2 : nd.idxoff1;
-    float* P = (role ? nd.p_y : nd.p_x) + (size_t)I * L;
+    float* P = f.p + (size_t)I * L;
     for (uint32_t J = lane; J < L; J += 64) row[J] = 0.0f;
     wave_lds_fence();
     avg_row(n, (float)n, [&](uint32_t r) {
       avg_src sr = {nullptr, nullptr, 0, nullptr};
-      const uint32_t ii = rank[(size_t)r * L + I];
+      const uint32_t ii = f.rank[(size_t)r * L + I];
       if (ii != DD_NONE) {
-        const row_ref b = bp_row(bp, seq[r], ii);
-        sr.col = b.col; sr.val = b.val; sr.n = b.n; sr.map = idx + idxoff[r];
+        const row_ref b = bp_row(bp, f.seq[r], ii);
+        sr.col = b.col; sr.val = b.val; sr.n = b.n; sr.map = f.idx + f.idxoff[r];
       }
       return sr;
     }, row, stage, lane);
@@ -1453,19 +1451,20 @@ __global__ __launch_bounds__(256) void k_node_avg(const dd_node* nodes, mp_store
       P[J] = v;
     }
   } else {
-    const uint32_t L1 = nd.L1, L2 = nd.L2;
+    const dd_fold &fx = nd.f[0], &fy = nd.f[1];
+    const uint32_t L1 = fx.L, L2 = fy.L;
     if (I >= L1) return;
-    const uint32_t nn = nd.n1 * nd.n2;
+    const uint32_t nn = fx.n * fy.n;
     float* P = nd.p_z + (size_t)I * L2;
     for (uint32_t J = lane; J < L2; J += 64) row[J] = 0.0f;
     wave_lds_fence();
-    for (uint32_t r1 = 0; r1 < nd.n1; ++r1) {
-      const uint32_t ii = nd.rank1[(size_t)r1 * L1 + I];
+    for (uint32_t r1 = 0; r1 < fx.n; ++r1) {
+      const uint32_t ii = fx.rank[(size_t)r1 * L1 + I];
       if (ii == DD_NONE) continue;
-      const uint32_t s1 = nd.seq1[r1];
-      avg_row(nd.n2, (float)nn, [&](uint32_t r2) {
-        const row_ref m = mp_row(mp, s1, nd.seq2[r2], ii);
-        avg_src sr = {m.col, m.val, m.n, nd.idx2 + nd.idxoff2[r2]};
+      const uint32_t s1 = fx.seq[r1];
+      avg_row(fy.n, (float)nn, [&](uint32_t r2) {
+        const row_ref m = mp_row(mp, s1, fy.seq[r2], ii);
+        avg_src sr = {m.col, m.val, m.n, fy.idx + fy.idxoff[r2]};
         return sr;
       }, row, stage, lane);
     }
@@ -1480,11 +1479,12 @@ __global__ __launch_bounds__(256) void k_node_avg(const dd_node* nodes, mp_store
 
 // ------------------------------------------------------------------------------------------
 // sparse structure of one node: entry lists of p_x, p_y, p_z, consensus base-pair counts,
-// alignment envelope, table initialisation.  xmap/ymap/zmap arrive filled with -1, q_* with 0.
+// alignment envelope, table initialisation.  The id maps (f[r].map, zmap) arrive filled with -1, the multipliers with 0.
 // ------------------------------------------------------------------------------------------
 __device__ __forceinline__ bool cbp_ok(const dd_node& nd, const dd_params& prm, float px, float py, float pzik, float pzjl) {
-  const float p = (nd.n1 * px + nd.n2 * py) / (nd.n1 + nd.n2);  // dafs.cpp:1032
-  const float q = (pzik + pzjl) / 2;                               // :1033
+  const uint32_t n1 = nd.f[0].n, n2 = nd.f[1].n;
+  const float p = (n1 * px + n2 * py) / (n1 + n2);  // dafs.cpp:1032
+  const float q = (pzik + pzjl) / 2;                // :1033
   return (p - prm.th_s > 0.0f) && (prm.w * (p - prm.th_s) + (q - prm.th_a) > 0.0f);
 }
 
@@ -1522,54 +1522,72 @@ __device__ void block_scan_inclusive(uint32_t* a, uint32_t n) {
   __syncthreads();
 }
 
-// sorted column lists of the entries > CUTOFF of every row (upper: only j > i).  A wavefront per row, the lanes
-// across the columns (coalesced reads), positions by ballot
-__device__ void row_lists(uint32_t R, uint32_t Cn, const float* P, bool upper, uint32_t* ptr, uint32_t* lst, int32_t* map) {
-  const uint32_t tid = threadIdx.x, nt = blockDim.x;
-  const uint32_t wave = tid >> 6, lane = tid & 63, nwaves = nt >> 6;
-  // four 64-column chunks of a row are fetched before the first is counted: the walk is a chain of round trips to
-  // L2 otherwise (a row of 150 columns: one trip instead of three)
-  for (uint32_t i = wave; i < R; i += nwaves) {
-    uint32_t c = 0;
-    for (uint32_t j0 = upper ? ((i + 1) & ~63u) : 0; j0 < Cn; j0 += 256) {
-      float v[4];
+// Sorted column lists of the kept cells of every row of a matrix -- the entries > CUTOFF of p_x / p_y (upper: only j > i) and
+// p_z, the flagged cells of c_z -- with the dense id map where there is one.  A wavefront per row, the lanes across the
+// columns (coalesced reads), positions by ballot: row_count counts a row, a scan of the counts gives the row pointers,
+// row_write puts the columns at the scanned positions.
+template <class T>
+struct dd_mat { const T* P; uint32_t R, C; bool upper; uint32_t* ptr; uint32_t* lst; int32_t* map; };
+__device__ __forceinline__ bool row_keep(float v) { return v > DD_CUTOFF; }
+__device__ __forceinline__ bool row_keep(uint8_t flag) { return flag != 0; }
+// row i read by column; what lies outside it (the diagonal and below of an upper matrix, the lanes beyond the last column)
+// reads as `pad`, which is neither kept nor inside the envelope
+template <class T>
+struct dd_row {
+  const T* row; uint32_t C, jmin; T pad;
+  __device__ dd_row(const dd_mat<T>& m, uint32_t i, T pad_) : row(m.P + (size_t)i * m.C), C(m.C), jmin(m.upper ? i + 1 : 0), pad(pad_) {}
+  __device__ T operator()(uint32_t j) const { return (j < C && j >= jmin) ? row[j] : pad; }
+};
+// visit(j0, v): the lanes hold columns j0 .. j0 + 63 of the row.  Four 64-column chunks of a row are fetched before the first
+// is visited: the walk is a chain of round trips to L2 otherwise (a row of 150 columns: one trip instead of three)
+template <class T, class Visit>
+__device__ __forceinline__ void row_chunks(const dd_row<T>& r, uint32_t lane, Visit visit) {
+  for (uint32_t j0 = r.jmin & ~63u; j0 < r.C; j0 += 256) {
+    T v[4];
 #pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const uint32_t j = j0 + 64 * u + lane;
-        v[u] = (j < Cn && (!upper || j > i)) ? P[(size_t)i * Cn + j] : 0.0f;
-      }
+    for (int u = 0; u < 4; ++u) v[u] = r(j0 + 64 * u + lane);
 #pragma unroll
-      for (int u = 0; u < 4; ++u) c += (uint32_t)__popcll(__ballot(v[u] > DD_CUTOFF));
-    }
-    if (lane == 0) ptr[i + 1] = c;
+    for (int u = 0; u < 4; ++u) visit(j0 + 64 * u, v[u]);
   }
-  if (tid == 0) ptr[0] = 0;
-  __syncthreads();
-  block_scan_inclusive(ptr + 1, R);
-  for (uint32_t i = wave; i < R; i += nwaves) {
-    uint32_t pos = ptr[i];
-    for (uint32_t j0 = upper ? ((i + 1) & ~63u) : 0; j0 < Cn; j0 += 256) {
-      float v[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const uint32_t j = j0 + 64 * u + lane;
-        v[u] = (j < Cn && (!upper || j > i)) ? P[(size_t)i * Cn + j] : 0.0f;
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const uint32_t j = j0 + 64 * u + lane;
-        const bool keep = v[u] > DD_CUTOFF;
-        const unsigned long long m = __ballot(keep);
-        if (keep) {
-          const uint32_t q = pos + (uint32_t)__popcll(m & ((1ull << lane) - 1));
-          lst[q] = j;
-          if (map) map[(size_t)i * Cn + j] = (int32_t)q;
-        }
-        pos += (uint32_t)__popcll(m);
-      }
+}
+// also(j0, v): whatever else the caller takes from the same pass over the row
+template <class T, class Also>
+__device__ __forceinline__ uint32_t row_count(const dd_row<T>& r, uint32_t lane, Also also) {
+  uint32_t c = 0;
+  row_chunks(r, lane, [&](uint32_t j0, T v) { c += (uint32_t)__popcll(__ballot(row_keep(v))); also(j0, v); });
+  return c;
+}
+template <class T>
+__device__ __forceinline__ void row_write(const dd_row<T>& r, uint32_t lane, uint32_t pos, uint32_t* lst, int32_t* map_row) {
+  row_chunks(r, lane, [&](uint32_t j0, T v) {
+    const bool keep = row_keep(v);
+    const unsigned long long m = __ballot(keep);
+    if (keep) {
+      const uint32_t q = pos + (uint32_t)__popcll(m & ((1ull << lane) - 1));
+      lst[q] = j0 + lane;
+      if (map_row) map_row[j0 + lane] = (int32_t)q;
     }
+    pos += (uint32_t)__popcll(m);
+  });
+}
+// the lists of a whole matrix by one workgroup
+template <class T>
+__device__ void row_lists(const dd_mat<T>& m) {
+  const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, nwaves = blockDim.x >> 6;
+  for (uint32_t i = wave; i < m.R; i += nwaves) {
+    const uint32_t c = row_count(dd_row<T>(m, i, T(0)), lane, [](uint32_t, T) {});
+    if (lane == 0) m.ptr[i + 1] = c;
   }
+  if (tid == 0) m.ptr[0] = 0;
   __syncthreads();
+  block_scan_inclusive(m.ptr + 1, m.R);
+  for (uint32_t i = wave; i < m.R; i += nwaves) row_write(dd_row<T>(m, i, T(0)), lane, m.ptr[i], m.lst, m.map ? m.map + (size_t)i * m.C : nullptr);
+  __syncthreads();
+}
+// the three posterior matrices of a node: p_x, p_y, p_z
+__device__ __forceinline__ dd_mat<float> dd_list_matrix(const dd_node& nd, uint32_t which) {
+  if (which < 2) { const dd_fold& f = nd.f[which]; return {f.p, f.L, f.L, true, f.ptr, f.col, f.map}; }
+  return {nd.p_z, nd.f[0].L, nd.f[1].L, false, nd.pz_ptr, nd.pz_k, nullptr};
 }
 
 // row of entry e: the largest i with ptr[i] <= e (ptr = exclusive row pointers, here an LDS copy)
@@ -1581,6 +1599,55 @@ __device__ __forceinline__ uint32_t row_of_entry(const uint32_t* ptr, uint32_t R
   }
   return lo;
 }
+// row pointers of p_x for the entry -> row searches: in LDS when the launch gave this node's L1 + 1 words room
+__device__ __forceinline__ const uint32_t* px_ptr_view(const dd_node& nd, uint32_t lds_bytes) {
+  extern __shared__ uint32_t s_pxptr_dyn[];
+  const uint32_t L1 = nd.f[0].L;
+  const bool in_lds = (size_t)(L1 + 1) * 4 <= lds_bytes;
+  if (in_lds) for (uint32_t i = threadIdx.x; i <= L1; i += blockDim.x) s_pxptr_dyn[i] = nd.f[0].ptr[i];
+  __syncthreads();
+  return in_lds ? s_pxptr_dyn : nd.f[0].ptr;
+}
+
+// The consensus base pairs of entry e = (i, j) of p_x (dafs.cpp:1022-1044), in the reference's order: row i of p_z gives k,
+// row k of p_y gives l; fn(i, j, k, l, b) for every accepted pair, b the entry (k, l) of p_y.  The one walk that the counts
+// and the fill share: they cannot disagree on the acceptance test or on the order.
+template <class Fn>
+__device__ __forceinline__ void cbp_walk(const dd_node& nd, const dd_params& prm, const uint32_t* px_ptr, uint32_t e, Fn fn) {
+  const dd_fold &fx = nd.f[0], &fy = nd.f[1];
+  const uint32_t L2 = fy.L;
+  const uint32_t i = row_of_entry(px_ptr, fx.L, e), j = fx.col[e];
+  const float px = fx.p[(size_t)i * fx.L + j];
+  for (uint32_t a = nd.pz_ptr[i]; a < nd.pz_ptr[i + 1]; ++a) {
+    const uint32_t k = nd.pz_k[a];
+    const float pzik = nd.p_z[(size_t)i * L2 + k];
+    for (uint32_t b = fy.ptr[k]; b < fy.ptr[k + 1]; ++b) {
+      const uint32_t l = fy.col[b];
+      const float pzjl = nd.p_z[(size_t)j * L2 + l];
+      if (pzjl > DD_CUTOFF && cbp_ok(nd, prm, px, fy.p[(size_t)k * L2 + l], pzik, pzjl)) fn(i, j, k, l, b);
+    }
+  }
+}
+// all threads, a thread per entry of p_x: the consensus pairs of every entry -> cbp_cnt, their total -> info[0] and
+// ncbp_out (the host sizes the constraint block from this: one copy per call); the loop state info[1..7] starts at 0
+__device__ void cbp_count(const dd_node& nd, const dd_params& prm, const uint32_t* px_ptr, uint32_t* ncbp_out) {
+  __shared__ uint32_t s_total;
+  const uint32_t tid = threadIdx.x;
+  if (tid == 0) s_total = 0;
+  __syncthreads();
+  uint32_t mine = 0;
+  const uint32_t npx = px_ptr[nd.f[0].L];
+  for (uint32_t e = tid; e < npx; e += blockDim.x) {
+    uint32_t c = 0;
+    cbp_walk(nd, prm, px_ptr, e, [&](uint32_t, uint32_t, uint32_t, uint32_t, uint32_t) { ++c; });
+    nd.cbp_cnt[e] = c;
+    mine += c;
+  }
+  atomicAdd(&s_total, mine);
+  __syncthreads();
+  if (tid == 0 && ncbp_out) ncbp_out[blockIdx.x] = s_total;
+  if (tid == 0) { nd.info[0] = s_total; nd.info[1] = 0; nd.info[2] = 0; nd.info[3] = 0; nd.info[4] = 0; nd.info[5] = 0; nd.info[6] = 0; nd.info[7] = 0; }
+}
 
 // parts == 1: one workgroup does everything.  parts == 4 (launches of a few nodes, where the node's set-up stands between
 // its children and its own first iteration): the lists of p_x, p_y, p_z and the alignment envelope + table initialisation
@@ -1588,14 +1655,15 @@ __device__ __forceinline__ uint32_t row_of_entry(const uint32_t* ptr, uint32_t R
 // its part is in memory, and the one that arrives last counts the consensus base pairs, which need all three lists.
 __global__ __launch_bounds__(DD_THREADS) void k_node_lists(const dd_node* nodes, dd_params prm, uint32_t* ncbp_out, uint32_t pxptr_lds, uint32_t parts) {
   const dd_node nd = nodes[blockIdx.x];
-  const uint32_t tid = threadIdx.x, nt = blockDim.x;
-  const uint32_t L1 = nd.L1, L2 = nd.L2;
+  const uint32_t tid = threadIdx.x;
+  const uint32_t L1 = nd.f[0].L, L2 = nd.f[1].L;
   const uint32_t part = blockIdx.y;
-  if (parts == 1 || part == 0) row_lists(L1, L1, nd.p_x, true, nd.px_ptr, nd.px_j, nd.xmap);
-  if (parts == 1 || part == 1) row_lists(L2, L2, nd.p_y, true, nd.py_ptr, nd.py_l, nd.ymap);
-  if (parts == 1 || part == 2) row_lists(L1, L2, nd.p_z, false, nd.pz_ptr, nd.pz_k, nullptr);
+  if (parts == 1 || part == 0) row_lists(dd_list_matrix(nd, 0));
+  if (parts == 1 || part == 1) row_lists(dd_list_matrix(nd, 1));
+  if (parts == 1 || part == 2) row_lists(dd_list_matrix(nd, 2));
+  // alignment envelope; x / z double as scratch here
+  if (parts == 1 || part == 3) nw_envelope(L1, L2, nd.p_z, prm.th_a, nd.env, nd.f[0].ss, nd.z);
   if (parts > 1) {
-    if (part == 3) nw_envelope(L1, L2, nd.p_z, prm.th_a, nd.env, nd.x, nd.z);  // alignment envelope; x / z double as scratch here
     __shared__ uint32_t s_ticket;
     __threadfence();  // this part's lists, before the arrival
     __syncthreads();
@@ -1605,44 +1673,7 @@ __global__ __launch_bounds__(DD_THREADS) void k_node_lists(const dd_node* nodes,
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");  // the other parts' lists, after the arrival
     if (tid == 0) nd.sync[5] = 0;
   }
-  // consensus base pairs per p_x entry (dafs.cpp:1022-1044)
-  __shared__ uint32_t s_total;
-  if (tid == 0) s_total = 0;
-  __syncthreads();
-  uint32_t mine = 0;
-  // row pointers of p_x for the entry -> row searches: in LDS when the launch gave this node's L1 + 1 words room
-  extern __shared__ uint32_t s_pxptr_dyn[];
-  const uint32_t* s_pxptr = nd.px_ptr;
-  if ((size_t)(L1 + 1) * 4 <= pxptr_lds) {
-    for (uint32_t i = tid; i <= L1; i += nt) s_pxptr_dyn[i] = nd.px_ptr[i];
-    s_pxptr = s_pxptr_dyn;
-  }
-  __syncthreads();
-  const uint32_t npx = s_pxptr[L1];
-  for (uint32_t e = tid; e < npx; e += nt) {  // a thread per entry of p_x
-    {
-      const uint32_t i = row_of_entry(s_pxptr, L1, e);
-      const uint32_t j = nd.px_j[e];
-      const float px = nd.p_x[(size_t)i * L1 + j];
-      uint32_t c = 0;
-      for (uint32_t a = nd.pz_ptr[i]; a < nd.pz_ptr[i + 1]; ++a) {
-        const uint32_t k = nd.pz_k[a];
-        const float pzik = nd.p_z[(size_t)i * L2 + k];
-        for (uint32_t b = nd.py_ptr[k]; b < nd.py_ptr[k + 1]; ++b) {
-          const uint32_t l = nd.py_l[b];
-          const float pzjl = nd.p_z[(size_t)j * L2 + l];
-          if (pzjl > DD_CUTOFF && cbp_ok(nd, prm, px, nd.p_y[(size_t)k * L2 + l], pzik, pzjl)) ++c;
-        }
-      }
-      nd.cbp_cnt[e] = c;
-      mine += c;
-    }
-  }
-  atomicAdd(&s_total, mine);
-  if (parts == 1) nw_envelope(L1, L2, nd.p_z, prm.th_a, nd.env, nd.x, nd.z);  // alignment envelope; x / z double as scratch here
-  __syncthreads();
-  if (tid == 0 && ncbp_out) ncbp_out[blockIdx.x] = s_total;  // the host sizes the constraint block from this (one copy per call)
-  if (tid == 0) { nd.info[0] = s_total; nd.info[1] = 0; nd.info[2] = 0; nd.info[3] = 0; nd.info[4] = 0; nd.info[5] = 0; nd.info[6] = 0; nd.info[7] = 0; }
+  cbp_count(nd, prm, px_ptr_view(nd, pxptr_lds), ncbp_out);
 }
 
 // ---- set-up of WIDE nodes (round 3) ------------------------------------------------------------------------------------
@@ -1652,73 +1683,32 @@ __global__ __launch_bounds__(DD_THREADS) void k_node_lists(const dd_node* nodes,
 // matrices: counts (+ the first / last column of the envelope from the same pass over p_z), a scan per matrix, the fill,
 // the table initialisation -- and a last one-workgroup kernel for what is small (envelope smoothing, consensus-pair
 // counts).  Same lists, same order, same envelope.
-struct dd_mat { const float* P; uint32_t R, C; bool upper; uint32_t* ptr; uint32_t* lst; int32_t* map; };
-__device__ __forceinline__ dd_mat dd_list_matrix(const dd_node& nd, uint32_t which) {
-  if (which == 0) return dd_mat{nd.p_x, nd.L1, nd.L1, true, nd.px_ptr, nd.px_j, nd.xmap};
-  if (which == 1) return dd_mat{nd.p_y, nd.L2, nd.L2, true, nd.py_ptr, nd.py_l, nd.ymap};
-  return dd_mat{nd.p_z, nd.L1, nd.L2, false, nd.pz_ptr, nd.pz_k, nullptr};
-}
 // grid (row blocks of 8, node, matrix), 512 threads: a wavefront per row.  fill = 0: entries > CUTOFF per row -> ptr[i + 1];
-// for p_z also the row's first / last column with p - th >= 0 (1-based, 0 = none) -> fa / la (= nd.x / nd.z, scratch
+// for p_z also the row's first / last column with p - th >= 0 (1-based, 0 = none) -> fa / la (= f[0].ss / nd.z, scratch
 // here as in nw_envelope).  fill = 1: the columns (and the id map) at the scanned positions.
 template <int WHICH>
 __device__ __forceinline__ void lists_rows_body(const dd_node& nd, float th_a, int fill) {
   // (the matrix is a template argument: with the three cases merged behind one run-time selection the compiler left the
   // p_z case's pointers unset -- a fault at address 0 on the first launch; one instantiation per matrix is also leaner)
-  const dd_mat m = dd_list_matrix(nd, (uint32_t)WHICH);
+  const dd_mat<float> m = dd_list_matrix(nd, (uint32_t)WHICH);
   const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const uint32_t i = blockIdx.x * 8 + wave;
   if (i >= m.R) return;
-  const uint32_t jbeg = m.upper ? ((i + 1) & ~63u) : 0;
-  const float* row = m.P + (size_t)i * m.C;
-  if (!fill) {
-    uint32_t c = 0, f = 0, l = 0;
-    for (uint32_t j0 = jbeg; j0 < m.C; j0 += 256) {
-      float v[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const uint32_t j = j0 + 64 * u + lane;
-        v[u] = (j < m.C && (!m.upper || j > i)) ? row[j] : (WHICH == 2 ? -1.0f : 0.0f);
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        c += (uint32_t)__popcll(__ballot(v[u] > DD_CUTOFF));
-        if (WHICH == 2) {  // needleman_wunsch.cpp:205-216: p - th >= 0 (padding lanes hold -1)
-          const unsigned long long e = __ballot(v[u] - th_a >= 0.0f);
-          if (e) {
-            const uint32_t k0 = j0 + 64 * u;
-            if (!f) f = k0 + (uint32_t)__ffsll((long long)e);
-            l = k0 + 64 - (uint32_t)__clzll((long long)e);
-          }
-        }
+  const dd_row<float> row(m, i, -1.0f);
+  if (fill) { row_write(row, lane, m.ptr[i], m.lst, m.map ? m.map + (size_t)i * m.C : nullptr); return; }
+  uint32_t f = 0, l = 0;
+  const uint32_t c = row_count(row, lane, [&](uint32_t k0, float v) {
+    if (WHICH == 2) {  // needleman_wunsch.cpp:205-216: p - th >= 0 (padding lanes hold -1)
+      const unsigned long long e = __ballot(v - th_a >= 0.0f);
+      if (e) {
+        if (!f) f = k0 + (uint32_t)__ffsll((long long)e);
+        l = k0 + 64 - (uint32_t)__clzll((long long)e);
       }
     }
-    if (lane == 0) {
-      m.ptr[i + 1] = c;
-      if (WHICH == 2) { nd.x[i + 1] = f; nd.z[i + 1] = l; }
-    }
-    return;
-  }
-  uint32_t pos = m.ptr[i];
-  for (uint32_t j0 = jbeg; j0 < m.C; j0 += 256) {
-    float v[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const uint32_t j = j0 + 64 * u + lane;
-      v[u] = (j < m.C && (!m.upper || j > i)) ? row[j] : 0.0f;
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const uint32_t j = j0 + 64 * u + lane;
-      const bool keep = v[u] > DD_CUTOFF;
-      const unsigned long long mk = __ballot(keep);
-      if (keep) {
-        const uint32_t q = pos + (uint32_t)__popcll(mk & ((1ull << lane) - 1));
-        m.lst[q] = j;
-        if (m.map) m.map[(size_t)i * m.C + j] = (int32_t)q;
-      }
-      pos += (uint32_t)__popcll(mk);
-    }
+  });
+  if (lane == 0) {
+    m.ptr[i + 1] = c;
+    if (WHICH == 2) { nd.f[0].ss[i + 1] = f; nd.z[i + 1] = l; }
   }
 }
 __global__ __launch_bounds__(512) void k_lists_rows(const dd_node* nodes, float th_a, int fill) {
@@ -1729,15 +1719,16 @@ __global__ __launch_bounds__(512) void k_lists_rows(const dd_node* nodes, float 
 }
 // grid (node, matrix): exclusive row pointers from the counts
 __global__ __launch_bounds__(DD_THREADS) void k_lists_scan(const dd_node* nodes) {
-  const dd_node nd = nodes[blockIdx.x];
-  uint32_t* ptr = blockIdx.y == 0 ? nd.px_ptr : (blockIdx.y == 1 ? nd.py_ptr : nd.pz_ptr);
-  const uint32_t R = blockIdx.y == 1 ? nd.L2 : nd.L1;
+  const dd_node& nd = nodes[blockIdx.x];  // read in place: a run-time index into a private copy would send it to scratch
+  const uint32_t which = blockIdx.y;
+  uint32_t* ptr = which < 2 ? nd.f[which].ptr : nd.pz_ptr;
+  const uint32_t R = nd.f[which == 1].L;
   if (threadIdx.x == 0) ptr[0] = 0;
   __syncthreads();
   block_scan_inclusive(ptr + 1, R);
 }
 // the envelope's sequential smoothing passes (needleman_wunsch.cpp:218-243) over first / last columns that are already
-// there (fa = nd.x, la = nd.z): thread 0, on an LDS copy while it fits
+// there (fa = f[0].ss, la = nd.z): thread 0, on an LDS copy while it fits
 __device__ void nw_envelope_smooth(uint32_t L1, uint32_t L2, const uint32_t* fa, const uint32_t* la, uint32_t* env) {
   __shared__ uint32_t s_env[2 * 4097];
   const uint32_t tid = threadIdx.x, nt = blockDim.x;
@@ -1774,42 +1765,15 @@ __device__ void nw_envelope_smooth(uint32_t L1, uint32_t L2, const uint32_t* fa,
 // grid (node): what is left of k_node_lists once the lists, the first / last columns and the table are there
 __global__ __launch_bounds__(DD_THREADS) void k_node_lists_tail(const dd_node* nodes, dd_params prm, uint32_t* ncbp_out) {
   const dd_node nd = nodes[blockIdx.x];
-  const uint32_t tid = threadIdx.x, nt = blockDim.x;
-  const uint32_t L1 = nd.L1, L2 = nd.L2;
-  __shared__ uint32_t s_total;
-  if (tid == 0) s_total = 0;
-  __syncthreads();
-  uint32_t mine = 0;
-  const uint32_t npx = nd.px_ptr[L1];
-  for (uint32_t e = tid; e < npx; e += nt) {  // a thread per entry of p_x: consensus base pairs (dafs.cpp:1022-1044), as in k_node_lists
-    const uint32_t i = row_of_entry(nd.px_ptr, L1, e);
-    const uint32_t j = nd.px_j[e];
-    const float px = nd.p_x[(size_t)i * L1 + j];
-    uint32_t c = 0;
-    for (uint32_t a = nd.pz_ptr[i]; a < nd.pz_ptr[i + 1]; ++a) {
-      const uint32_t k = nd.pz_k[a];
-      const float pzik = nd.p_z[(size_t)i * L2 + k];
-      for (uint32_t b = nd.py_ptr[k]; b < nd.py_ptr[k + 1]; ++b) {
-        const uint32_t l = nd.py_l[b];
-        const float pzjl = nd.p_z[(size_t)j * L2 + l];
-        if (pzjl > DD_CUTOFF && cbp_ok(nd, prm, px, nd.p_y[(size_t)k * L2 + l], pzik, pzjl)) ++c;
-      }
-    }
-    nd.cbp_cnt[e] = c;
-    mine += c;
-  }
-  atomicAdd(&s_total, mine);
-  __syncthreads();
-  nw_envelope_smooth(L1, L2, nd.x, nd.z, nd.env);
-  if (tid == 0 && ncbp_out) ncbp_out[blockIdx.x] = s_total;
-  if (tid == 0) { nd.info[0] = s_total; nd.info[1] = 0; nd.info[2] = 0; nd.info[3] = 0; nd.info[4] = 0; nd.info[5] = 0; nd.info[6] = 0; nd.info[7] = 0; }
+  cbp_count(nd, prm, nd.f[0].ptr, ncbp_out);
+  nw_envelope_smooth(nd.f[0].L, nd.f[1].L, nd.f[0].ss, nd.z, nd.env);
 }
 
 __global__ __launch_bounds__(DD_THREADS) void k_node_cbp_fill(const dd_node* nodes, dd_params prm, uint32_t pxptr_lds) {
   const dd_node nd = nodes[blockIdx.x];
   const uint32_t tid = threadIdx.x, nt = blockDim.x;
-  const uint32_t L1 = nd.L1, L2 = nd.L2;
-  const uint32_t npx = nd.px_ptr[L1];
+  const uint32_t L1 = nd.f[0].L, L2 = nd.f[1].L;
+  const uint32_t npx = nd.f[0].ptr[L1];
   if (nd.info[0] == 0) {
     // no consensus base pair (k_node_lists counted them): the flags keep their zero fill, the id map its -1, and the c_z
     // row lists are empty -- nothing to enumerate and no pass over the L1 x L2 cells (75 ms at the 27 000-column root of c5-random)
@@ -1819,70 +1783,25 @@ __global__ __launch_bounds__(DD_THREADS) void k_node_cbp_fill(const dd_node* nod
   // prefix of the per-entry counts (entries are already in (i,j) order); entry e starts at incl[e] - count[e],
   // i.e. at incl[e-1]
   block_scan_inclusive(nd.cbp_cnt, npx);
-  extern __shared__ uint32_t s_pxptr_dyn[];
-  const uint32_t* s_pxptr = nd.px_ptr;
-  if ((size_t)(L1 + 1) * 4 <= pxptr_lds) {
-    for (uint32_t i = tid; i <= L1; i += nt) s_pxptr_dyn[i] = nd.px_ptr[i];
-    s_pxptr = s_pxptr_dyn;
-  }
-  __syncthreads();
+  const uint32_t* px_ptr = px_ptr_view(nd, pxptr_lds);
   for (uint32_t e = tid; e < npx; e += nt) {  // a thread per entry of p_x
-    {
-      const uint32_t i = row_of_entry(s_pxptr, L1, e);
-      const uint32_t j = nd.px_j[e];
-      const float px = nd.p_x[(size_t)i * L1 + j];
-      uint32_t u = e ? nd.cbp_cnt[e - 1] : 0u;
-      const uint32_t u0 = u;
-      for (uint32_t a = nd.pz_ptr[i]; a < nd.pz_ptr[i + 1]; ++a) {
-        const uint32_t k = nd.pz_k[a];
-        const float pzik = nd.p_z[(size_t)i * L2 + k];
-        for (uint32_t b = nd.py_ptr[k]; b < nd.py_ptr[k + 1]; ++b) {
-          const uint32_t l = nd.py_l[b];
-          const float pzjl = nd.p_z[(size_t)j * L2 + l];
-          if (pzjl > DD_CUTOFF && cbp_ok(nd, prm, px, nd.p_y[(size_t)k * L2 + l], pzik, pzjl)) {
-            if (u < nd.ncbp_cap) {
-              uint32_t* c = nd.cbp + (size_t)8 * u;
-              c[0] = i; c[1] = j; c[2] = k; c[3] = l; c[4] = e; c[5] = b;
-            }
-            nd.cy_flag[b] = 1;                       // c_y (dafs.cpp:1039)
-            nd.cz_flag[(size_t)i * L2 + k] = 1;      // c_z (:1040-1041)
-            nd.cz_flag[(size_t)j * L2 + l] = 1;
-            ++u;
-          }
-        }
+    uint32_t u = e ? nd.cbp_cnt[e - 1] : 0u;
+    const uint32_t u0 = u;
+    cbp_walk(nd, prm, px_ptr, e, [&](uint32_t i, uint32_t j, uint32_t k, uint32_t l, uint32_t b) {
+      if (u < nd.ncbp_cap) {
+        uint32_t* c = nd.cbp + (size_t)8 * u;
+        c[0] = i; c[1] = j; c[2] = k; c[3] = l; c[4] = e; c[5] = b;
       }
-      nd.cx_flag[e] = u > u0 ? 1 : 0;                // c_x (:1038)
-    }
+      nd.f[1].cflag[b] = 1;                    // c_y (dafs.cpp:1039)
+      nd.cz_flag[(size_t)i * L2 + k] = 1;      // c_z (:1040-1041)
+      nd.cz_flag[(size_t)j * L2 + l] = 1;
+      ++u;
+    });
+    nd.f[0].cflag[e] = u > u0 ? 1 : 0;         // c_x (:1038)
   }
   __syncthreads();
   // c_z as sorted row lists (:1056-1060) + dense id map
-  const uint32_t wave = tid >> 6, lane = tid & 63, nwaves = nt >> 6;
-  for (uint32_t i = wave; i < L1; i += nwaves) {
-    uint32_t c = 0;
-    for (uint32_t k0 = 0; k0 < L2; k0 += 64) {
-      const uint32_t k = k0 + lane;
-      c += (uint32_t)__popcll(__ballot(k < L2 && nd.cz_flag[(size_t)i * L2 + k] != 0));
-    }
-    if (lane == 0) nd.cz_ptr[i + 1] = c;
-  }
-  if (tid == 0) nd.cz_ptr[0] = 0;
-  __syncthreads();
-  block_scan_inclusive(nd.cz_ptr + 1, L1);
-  for (uint32_t i = wave; i < L1; i += nwaves) {
-    uint32_t pos = nd.cz_ptr[i];
-    for (uint32_t k0 = 0; k0 < L2; k0 += 64) {
-      const uint32_t k = k0 + lane;
-      const bool keep = k < L2 && nd.cz_flag[(size_t)i * L2 + k] != 0;
-      const unsigned long long m = __ballot(keep);
-      if (keep) {
-        const uint32_t q = pos + (uint32_t)__popcll(m & ((1ull << lane) - 1));
-        nd.cz_k[q] = k;
-        nd.zmap[(size_t)i * L2 + k] = (int32_t)q;
-      }
-      pos += (uint32_t)__popcll(m);
-    }
-  }
-  __syncthreads();
+  row_lists(dd_mat<uint8_t>{nd.cz_flag, L1, L2, false, nd.cz_ptr, nd.cz_k, nd.zmap});
   const uint32_t ncbp = nd.info[0] < nd.ncbp_cap ? nd.info[0] : nd.ncbp_cap;
   for (uint32_t u = tid; u < ncbp; u += nt) {
     uint32_t* c = nd.cbp + (size_t)8 * u;
@@ -1908,34 +1827,42 @@ __device__ __forceinline__ unsigned long long dd_lost_ticks(uint32_t L1, uint32_
 __device__ __forceinline__ uint32_t sync_load(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void sync_store(uint32_t* p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT); }
 
-__device__ __forceinline__ void dd_folder(const dd_node& nd, const dd_params& prm, uint32_t role, uint32_t t_first) {
+// the LDS regions of one folding DP (dd_fold_lds) as pointers; stk: the traceback stack
+struct dd_fold_ptrs { uint32_t *trb, *lck, *ck; float *ring, *stk, *tri, *cv; };
+__device__ __forceinline__ dd_fold_ptrs dd_fold_at(unsigned char* s, const dd_lds& m, const dd_fold_lds& f) {
+  return {dd_lds_at(s, m, f.trb), dd_lds_at(s, m, f.lck), dd_lds_at(s, m, f.ck), (float*)dd_lds_at(s, m, f.ring), (float*)dd_lds_at(s, m, f.stk),
+          (float*)dd_lds_at(s, m, f.tri), (float*)dd_lds_at(s, m, f.cv)};
+}
+__device__ __forceinline__ float dd_fold_weight(const dd_node& nd, float w, uint32_t r) { return w * 2 * nd.f[r].n / (nd.f[0].n + nd.f[1].n); }  // dafs.cpp:1091-1092
+
+// r: the folding, 0 = x, 1 = y (blockIdx.y - 1)
+__device__ __forceinline__ void dd_folder(const dd_node& nd, const dd_params& prm, uint32_t r, uint32_t t_first) {
   extern __shared__ unsigned char s_dd[];
   __shared__ float s_fscore;
   __shared__ uint32_t s_go, s_slow;
   bool gave_up = false;  // the register form overflowed earlier in this launch: straight to the span-ordered form
   const uint32_t tid = threadIdx.x, nt = blockDim.x;
   const int wave = (int)(tid >> 6), lane = (int)(tid & 63);
-  const bool isx = role == 1;
-  const uint32_t L = isx ? nd.L1 : nd.L2;
+  const dd_fold& f = nd.f[r];  // nd lives in LDS (k_dd_solve): a run-time index is an address computation there
+  const uint32_t L = f.L;
   const uint32_t W = dd_fold_cols(L);
-  const float* S = isx ? nd.s_x : nd.s_y;
-  const nuss_ws& ws = isx ? nd.wx : nd.wy;
-  uint8_t* trb_g = isx ? nd.trb_x : nd.trb_y;
-  uint32_t* ss = isx ? nd.x : nd.y;
+  const nuss_ws& ws = f.w;
+  uint8_t* trb_g = f.trb;
+  uint32_t* ss = f.ss;
   const uint32_t nw = dd_code_words(L);
-  // this folder's form (nd.fold_fast) and its LDS regions (dd_folder_lds); P: the traceback stack
-  const uint32_t form = dd_fold_form(nd.fold_fast, isx ? 0 : 1), K = dd_fold_k(nd.fold_fast, isx ? 0 : 1);
+  // this folder's form (nd.fold_fast) and its LDS regions (dd_folder_lds)
+  const uint32_t form = dd_fold_form(nd.fold_fast, r), K = dd_fold_k(nd.fold_fast, r);
   const dd_lds lay = dd_folder_lds(L, form, K);
-  uint32_t *trbp = dd_lds_at(s_dd, lay, lay.f[0].trb), *lck = dd_lds_at(s_dd, lay, lay.f[0].lck), *ckl = dd_lds_at(s_dd, lay, lay.f[0].ck);
-  float *ring = (float*)dd_lds_at(s_dd, lay, lay.f[0].ring), *P = (float*)dd_lds_at(s_dd, lay, lay.f[0].stk);
-  float *tri = (float*)dd_lds_at(s_dd, lay, lay.f[0].tri), *cvl = (float*)dd_lds_at(s_dd, lay, lay.f[0].cv);
+  const dd_fold_ptrs lp = dd_fold_at(s_dd, lay, lay.f[0]);
+  uint32_t *trbp = lp.trb, *lck = lp.lck, *ckl = lp.ck;
+  float *ring = lp.ring, *P = lp.stk, *tri = lp.tri, *cvl = lp.cv;
   const bool span = (form & kFoldSpan) != 0;
   const bool span_mw = L > 64 && !prm.span_one_wave;  // a wavefront per row slot (one slot: nothing to share out)
   if (span) for (uint32_t e = tid; e < dd_span_tri_words(L); e += nt) tri[e] = 0.0f;  // spans 0..2 hold 0 and are never written
   for (uint32_t it = t_first;; ++it) {
     if (tid == 0) {
       uint32_t g = 0;
-      const unsigned long long t_wait = wall_clock64(), t_max_wait = dd_lost_ticks(nd.L1, nd.L2);
+      const unsigned long long t_wait = wall_clock64(), t_max_wait = dd_lost_ticks(nd.f[0].L, nd.f[1].L);
       while ((g = sync_load(&nd.sync[0])) != it + 1 && g != DD_SYNC_EXIT && wall_clock64() - t_wait <= t_max_wait) __builtin_amdgcn_s_sleep(16);
       s_go = (g == it + 1) ? 1u : 0u;  // a leader that does not show up in time: leave (it will find its folders lost and be relaunched)
     }
@@ -1953,7 +1880,7 @@ __device__ __forceinline__ void dd_folder(const dd_node& nd, const dd_params& pr
       __syncthreads();
       bool slow = true;
       const unsigned long long tf0 = prm.stamps ? wall_clock64() : 0ull;
-      const float sc = nuss_span_mw(L, isx ? nd.s_xs : nd.s_ys, trbp, tri, cvl, ckl, lck, wave, lane, &slow);
+      const float sc = nuss_span_mw(L, f.s_span, trbp, tri, cvl, ckl, lck, wave, lane, &slow);
       if (slow && lane == 0) atomicOr(&s_slow, 1u);
       __syncthreads();
       if (wave == 0) {
@@ -1961,7 +1888,7 @@ __device__ __forceinline__ void dd_folder(const dd_node& nd, const dd_params& pr
         if (!s_slow) nuss_traceback_fast(L, trbp, trb_g, lck, ss, (uint32_t*)P, lane);
         if (lane == 0) {
           s_fscore = sc;
-          if (prm.stamps) { nd.sync[isx ? 5 : 6] += (uint32_t)(tf1 - tf0); nd.sync[7] += (uint32_t)(wall_clock64() - tf1); }  // DP of x / y, tracebacks of both
+          if (prm.stamps) { nd.sync[5 + r] += (uint32_t)(tf1 - tf0); nd.sync[7] += (uint32_t)(wall_clock64() - tf1); }  // DP of x / y, tracebacks of both
         }
       }
       __syncthreads();
@@ -1970,8 +1897,8 @@ __device__ __forceinline__ void dd_folder(const dd_node& nd, const dd_params& pr
     if ((span || (ring && W <= DD_WFOLD)) && !gave_up) {
       if (wave == 0) {
         bool slow = true;
-        const float sc = span ? nuss_wave_span_t(L, isx ? nd.s_xs : nd.s_ys, trbp, tri, cvl, ckl, lck, lane, &slow)
-                              : nuss_wave_fast(W, L, S, trbp, trb_g, ring, lck, lane, &slow);
+        const float sc = span ? nuss_wave_span_t(L, f.s_span, trbp, tri, cvl, ckl, lck, lane, &slow)
+                              : nuss_wave_fast(W, L, f.s, trbp, trb_g, ring, lck, lane, &slow);
         if (!slow) nuss_traceback_fast(L, trbp, trb_g, lck, ss, (uint32_t*)P, lane);
         if (lane == 0) { s_fscore = sc; s_slow = slow ? 1u : 0u; }
       }
@@ -1983,12 +1910,12 @@ __device__ __forceinline__ void dd_folder(const dd_node& nd, const dd_params& pr
       // which outruns the HBM-table wave form from a few hundred columns on (2143 columns: 31 -> 11 ms a pass).
       // It takes p and q as they are (no sweep-order copy).
       const nuss_ws none = {nullptr, nullptr, nullptr, nullptr, nullptr};
-      const float wf = prm.w * 2 * (isx ? nd.n1 : nd.n2) / (nd.n1 + nd.n2);  // dafs.cpp:1091-1092, as in k_dd_solve
+      const float wf = dd_fold_weight(nd, prm.w, r);
       for (uint32_t i = tid; i < L; i += nt) ss[i] = DD_NONE;  // a register-form traceback cut short may have left marks
       if (form & kFoldWg) {
         // beyond the register forms: the workgroup form (rolling rows and candidate heads in LDS, tables by span)
         float* lds = (float*)dd_lds_at(s_dd, lay, lay.f[0].wg);
-        const float* Ss = isx ? nd.s_xs : nd.s_ys;
+        const float* Ss = f.s_span;
         const unsigned long long tf0 = prm.stamps ? wall_clock64() : 0ull;
         const float sc = K == 4 ? nuss_wg_span<4>(L, Ss, ws, lds) : K == 2 ? nuss_wg_span<2>(L, Ss, ws, lds) : nuss_wg_span<0>(L, Ss, ws, lds);
         if (wave == 0) {
@@ -1996,11 +1923,11 @@ __device__ __forceinline__ void dd_folder(const dd_node& nd, const dd_params& pr
           nuss_traceback_span(L, ws.tr, ss, (uint32_t*)lds, lane);  // the rolling rows are free again: the stack
           if (lane == 0) {
             s_fscore = sc;
-            if (prm.stamps) { nd.sync[isx ? 5 : 6] += (uint32_t)(tf1 - tf0); nd.sync[7] += (uint32_t)(wall_clock64() - tf1); }  // DP of x / y, tracebacks of both
+            if (prm.stamps) { nd.sync[5 + r] += (uint32_t)(tf1 - tf0); nd.sync[7] += (uint32_t)(wall_clock64() - tf1); }  // DP of x / y, tracebacks of both
           }
         }
       } else {
-      nuss_pair_dp(L, isx ? nd.p_x : nd.p_y, isx ? nd.q_x : nd.q_y, wf, ws, 0, nullptr, nullptr, 0.0f, none, prm.th_s);
+      nuss_pair_dp(L, f.p, f.q, wf, ws, 0, nullptr, nullptr, 0.0f, none, prm.th_s);
       if (tid == 0) {
         nuss_traceback(L, ws, ss, ws.ck);  // the candidate-key array is free again: reuse it as the stack
         s_fscore = ws.dp[L - 1];
@@ -2009,8 +1936,8 @@ __device__ __forceinline__ void dd_folder(const dd_node& nd, const dd_params& pr
     }
     __syncthreads();
     if (tid == 0) {
-      nd.sync[2 + role] = __float_as_uint(s_fscore);
-      sync_store(&nd.sync[role], it + 1);
+      nd.sync[3 + r] = __float_as_uint(s_fscore);
+      sync_store(&nd.sync[1 + r], it + 1);
     }
   }
 }
@@ -2030,22 +1957,22 @@ __global__ __launch_bounds__(DD_SOLVE_THREADS) void k_dd_solve(const dd_node* no
   __syncthreads();
   const dd_node& nd = s_nd;
   if (blockIdx.y != 0) {  // folding workgroups of a split node
-    if (nd.split) dd_folder(nd, prm, blockIdx.y, nd.info[6] != 0 ? nd.info[1] : 0u);
+    if (nd.split) dd_folder(nd, prm, blockIdx.y - 1, nd.info[6] != 0 ? nd.info[1] : 0u);
     return;
   }
   const bool split = nd.split != 0;
   const uint32_t tid = threadIdx.x, nt = blockDim.x;
-  const uint32_t L1 = nd.L1, L2 = nd.L2;
+  const dd_fold &fx = nd.f[0], &fy = nd.f[1];
+  const uint32_t L1 = fx.L, L2 = fy.L;
   const uint32_t ncbp = nd.info[0];
-  const uint32_t npx = nd.px_ptr[L1], npy = nd.py_ptr[L2], ncz = nd.cz_ptr[L1];
-  const float w_x = prm.w * 2 * nd.n1 / (nd.n1 + nd.n2);  // dafs.cpp:1091
-  const float w_y = prm.w * 2 * nd.n2 / (nd.n1 + nd.n2);  // :1092
+  const uint32_t npx = fx.ptr[L1], npy = fy.ptr[L2], ncz = nd.cz_ptr[L1];
+  const float w_x = dd_fold_weight(nd, prm.w, 0), w_y = dd_fold_weight(nd, prm.w, 1);
   __shared__ uint32_t s_violated, s_npos;
   __shared__ int s_stop, s_bad, s_lost;  // s_lost: a folder of this split node did not answer in time
   __shared__ float s_eta;
   __shared__ float s_score[3];
   __shared__ uint32_t s_slowxy[2];       // this iteration's x / y folding is still to be done by the span-ordered form
-  bool gave_up_x = false, gave_up_y = false;
+  bool gave_up[2] = {false, false};  // indexed by compile-time constants only
   float c = 0.0f, eta = prm.eta0, s_prev = 0.0f;  // meaningful in thread 0
   uint32_t t = 0, violated = 0;
   const bool resume = nd.info[6] != 0;  // a node paused by an earlier launch (prm.slice): pick up its loop state
@@ -2056,33 +1983,31 @@ __global__ __launch_bounds__(DD_SOLVE_THREADS) void k_dd_solve(const dd_node* no
   }
   // dynamic LDS: whichever traceback tables and in-flight rows fit (nd.lds_flags, decided by the host; regions: dd_node_lds)
   extern __shared__ unsigned char s_dd[];
-  const uint32_t Wx = dd_fold_cols(L1), Wy = dd_fold_cols(L2), Wz = nd.nw_w;
-  const uint32_t nzw = dd_nwtab_words(L1, L2), nxw = dd_code_words(L1), nyw = dd_code_words(L2);
+  // the widths as values for the code shared by the two foldings: read through nd they are loaded from LDS again (and the
+  // columns per lane formed again) after every store of the update phase, which may alias it for all the compiler knows
+  const uint32_t Ls[2] = {L1, L2}, Ws[2] = {dd_fold_cols(L1), dd_fold_cols(L2)}, Wz = nd.nw_w;
+  const uint32_t nzw = dd_nwtab_words(L1, L2);
   const dd_lds lay = dd_node_lds(L1, L2, nd.lds_flags);
-  const dd_fold_lds &lx = lay.f[0], &ly = lay.f[1];
-  uint32_t *trzp = dd_lds_at(s_dd, lay, lay.trz), *trxp = dd_lds_at(s_dd, lay, lx.trb), *tryp = dd_lds_at(s_dd, lay, ly.trb);
-  float *ringx = (float*)dd_lds_at(s_dd, lay, lx.ring), *ringy = (float*)dd_lds_at(s_dd, lay, ly.ring);
-  uint32_t *lckx = dd_lds_at(s_dd, lay, lx.lck), *lcky = dd_lds_at(s_dd, lay, ly.lck);
+  uint32_t* trzp = dd_lds_at(s_dd, lay, lay.trz);
+  const dd_fold_ptrs lp[2] = {dd_fold_at(s_dd, lay, lay.f[0]), dd_fold_at(s_dd, lay, lay.f[1])};  // indexed by compile-time constants only
   const bool spanxy = (nd.lds_flags & kLdsSpanXY) != 0;
-  float *trix = (float*)dd_lds_at(s_dd, lay, lx.tri), *triy = (float*)dd_lds_at(s_dd, lay, ly.tri);
-  float *cvx = (float*)dd_lds_at(s_dd, lay, lx.cv), *cvy = (float*)dd_lds_at(s_dd, lay, ly.cv);
-  uint32_t *ckx = dd_lds_at(s_dd, lay, lx.ck), *cky = dd_lds_at(s_dd, lay, ly.ck);
-  float *Px = (float*)dd_lds_at(s_dd, lay, lx.stk), *Py = (float*)dd_lds_at(s_dd, lay, ly.stk);  // traceback stacks
   const bool shared_xy = (nd.lds_flags & kLdsShared) != 0;
   __shared__ uint32_t s_x_done;  // iteration whose x folding (DP + traceback) has released the shared region
   if (tid == 0) s_x_done = 0xFFFFFFFFu;
   uint8_t* trz = nd.tr_z;
   if (spanxy) {  // spans 0..2 of the dp triangles hold 0 and are never written
-    for (uint32_t e = tid; e < dd_span_tri_words(L1); e += nt) trix[e] = 0.0f;
-    for (uint32_t e = tid; e < dd_span_tri_words(L2); e += nt) triy[e] = 0.0f;
+    for (uint32_t e = tid; e < dd_span_tri_words(L1); e += nt) lp[0].tri[e] = 0.0f;
+    for (uint32_t e = tid; e < dd_span_tri_words(L2); e += nt) lp[1].tri[e] = 0.0f;
   }
   if (!resume) {
     // sweep-order inputs of the three DPs, built once; the multiplier updates below keep them current
     if (!(prm.skip_xy && ncbp == 0)) {  // a node that leaves its foldings out (see fold_on below) needs no scores
-      if (nd.s_x) dd_fill_scores(false, L1, nd.p_x, nd.q_x, w_x, prm.th_s, nd.s_x);  // only foldings with a register form keep one
-      if (nd.s_y) dd_fill_scores(false, L2, nd.p_y, nd.q_y, w_y, prm.th_s, nd.s_y);
-      if (nd.s_xs) dd_fill_scores(true, L1, nd.p_x, nd.q_x, w_x, prm.th_s, nd.s_xs);  // the copy the span form reads
-      if (nd.s_ys) dd_fill_scores(true, L2, nd.p_y, nd.q_y, w_y, prm.th_s, nd.s_ys);
+      for (uint32_t r = 0; r < 2; ++r) {
+        const dd_fold& f = nd.f[r];
+        const float wf = dd_fold_weight(nd, prm.w, r);
+        if (f.s) dd_fill_scores(false, f.L, f.p, f.q, wf, prm.th_s, f.s);  // only foldings with a register form keep one
+        if (f.s_span) dd_fill_scores(true, f.L, f.p, f.q, wf, prm.th_s, f.s_span);  // the copy the span form reads
+      }
     }
     dd_fill_nw(L1, L2, Wz, nd.p_z, nd.q_z, nd.pz_s, nd.qz_s);
     for (uint32_t r = tid; r < L1 + 130; r += nt) {  // the padded envelope (dd_node::env4)
@@ -2101,6 +2026,24 @@ __global__ __launch_bounds__(DD_SOLVE_THREADS) void k_dd_solve(const dd_node* no
   if (tid == 0) { s_tky = 0; s_tkz = 0; }
 #define DD_TICK(k) if (prm.stamps && tid == 0) { const unsigned long long now = wall_clock64(); tk[k] += now - t_prev; t_prev = now; }
   if (prm.stamps && tid == 0) t_prev = wall_clock64();
+  // One folding (r as a compile-time constant: 0 = x, 1 = y) inside the node's own workgroup, by the calling wavefront: DP, then
+  // traceback.  (The lane is formed here, not captured: a captured one lives in memory until the lambda is inlined, which hides its
+  // range 0..63 from the out-of-line DPs -- they are specialised on it, here as in their other callers.)
+  auto fold_wave = [&](auto r_tag) {
+    constexpr uint32_t r = decltype(r_tag)::value;
+    const int lane = (int)(threadIdx.x & 63);
+    const dd_fold& f = nd.f[r];
+    const dd_fold_ptrs& l = lp[r];
+    const uint32_t L = Ls[r], W = Ws[r];
+    bool slow = true;
+    float sc = 0.0f;
+    if (spanxy && !gave_up[r]) sc = nuss_wave_span_t(L, f.s_span, l.trb, l.tri, l.cv, l.ck, l.lck, lane, &slow);
+    else if (l.ring && !gave_up[r] && W <= DD_WFOLD) sc = nuss_wave_fast(W, L, f.s, l.trb, f.trb, l.ring, l.lck, lane, &slow);
+    if (slow && lane == 0 && prm.stamps) nd.info[4 + r] += 1;  // iterations that took the slower form
+    if (lane == 0) { s_slowxy[r] = slow ? 1u : 0u; s_score[r] = sc; }  // slow: the span-ordered form below, by everybody
+    if (r == 0) DD_TICK(0);
+    if (!slow) nuss_traceback_fast(L, l.trb, f.trb, l.lck, f.ss, (uint32_t*)l.stk, lane);
+  };
   // time bound of the launch (dd_params::budget); meaningful in thread 0
   unsigned long long deadline = 0;
   if (prm.budget && tid == 0) {
@@ -2127,17 +2070,17 @@ __global__ __launch_bounds__(DD_SOLVE_THREADS) void k_dd_solve(const dd_node* no
       // after the initial fill); one release publishes them together with the go signal
       if (tid == 0) sync_store(&nd.sync[0], t + 1);
     } else {
-      for (uint32_t i = tid; i < L1; i += nt) nd.x[i] = DD_NONE;
-      for (uint32_t k = tid; k < L2; k += nt) nd.y[k] = DD_NONE;
+      for (uint32_t i = tid; i < L1; i += nt) fx.ss[i] = DD_NONE;
+      for (uint32_t k = tid; k < L2; k += nt) fy.ss[k] = DD_NONE;
     }
     if (tid == 0) { s_slowxy[0] = 0; s_slowxy[1] = 0; }
     // packed traceback tables are filled by OR
     if (trzp) for (uint32_t e = tid; e < nzw; e += nt) trzp[e] = 0;
-    if (trxp) for (uint32_t e = tid; e < nxw; e += nt) trxp[e] = 0;
-    if (tryp && !shared_xy) for (uint32_t e = tid; e < nyw; e += nt) tryp[e] = 0;
+    if (lp[0].trb) for (uint32_t e = tid; e < dd_code_words(L1); e += nt) lp[0].trb[e] = 0;
+    if (lp[1].trb && !shared_xy) for (uint32_t e = tid; e < dd_code_words(L2); e += nt) lp[1].trb[e] = 0;
     if (spanxy) {  // empty candidate lists (entry L / L2 is the list that stays empty)
-      for (uint32_t e = tid; e < DD_CAP * (L1 + 1); e += nt) { cvx[e] = -INFINITY; ckx[e] = 0; }
-      for (uint32_t e = tid; e < DD_CAP * (L2 + 1); e += nt) { cvy[e] = -INFINITY; cky[e] = 0; }
+      for (uint32_t e = tid; e < DD_CAP * (L1 + 1); e += nt) { lp[0].cv[e] = -INFINITY; lp[0].ck[e] = 0; }
+      for (uint32_t e = tid; e < DD_CAP * (L2 + 1); e += nt) { lp[1].cv[e] = -INFINITY; lp[1].ck[e] = 0; }
     }
     // the three subproblems (dafs.cpp:1091-1093) side by side, one wavefront each, DP then traceback
     __syncthreads();
@@ -2146,33 +2089,20 @@ __global__ __launch_bounds__(DD_SOLVE_THREADS) void k_dd_solve(const dd_node* no
     } else if (split) {
       // the folders are at work on their own CUs
     } else if (wave == 0) {
-      bool slow = true;
-      float sc = 0.0f;
-      if (spanxy && !gave_up_x) sc = nuss_wave_span_t(L1, nd.s_xs, trxp, trix, cvx, ckx, lckx, lane, &slow);
-      else if (ringx && !gave_up_x && Wx <= DD_WFOLD) sc = nuss_wave_fast(Wx, L1, nd.s_x, trxp, nd.trb_x, ringx, lckx, lane, &slow);
-      if (slow && lane == 0 && prm.stamps) nd.info[4] += 1;  // iterations that took the slower form
-      if (lane == 0) { s_slowxy[0] = slow ? 1u : 0u; s_score[0] = sc; }  // slow: the span-ordered form below, by everybody
-      DD_TICK(0);
-      if (!slow) nuss_traceback_fast(L1, trxp, nd.trb_x, lckx, nd.x, (uint32_t*)Px, lane);
+      fold_wave(std::integral_constant<uint32_t, 0>());
       DD_TICK(1);
       if (shared_xy) {  // hand the region to the y folding
         wave_lds_fence();
         if (lane == 0) __hip_atomic_store(&s_x_done, t, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
       }
     } else if (wave == 1) {
-      bool slow = true;
-      float sc = 0.0f;
       const unsigned long long ty0 = prm.stamps ? wall_clock64() : 0ull;
       if (shared_xy) {
         while (__hip_atomic_load(&s_x_done, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) != t) __builtin_amdgcn_s_sleep(8);
-        if (tryp) for (uint32_t e = (uint32_t)lane; e < nyw; e += 64) tryp[e] = 0;
+        if (lp[1].trb) for (uint32_t e = (uint32_t)lane; e < dd_code_words(L2); e += 64) lp[1].trb[e] = 0;
         wave_lds_fence();
       }
-      if (spanxy && !gave_up_y) sc = nuss_wave_span_t(L2, nd.s_ys, tryp, triy, cvy, cky, lcky, lane, &slow);
-      else if (ringy && !gave_up_y && Wy <= DD_WFOLD) sc = nuss_wave_fast(Wy, L2, nd.s_y, tryp, nd.trb_y, ringy, lcky, lane, &slow);
-      if (slow && lane == 0 && prm.stamps) nd.info[5] += 1;
-      if (lane == 0) { s_slowxy[1] = slow ? 1u : 0u; s_score[1] = sc; }
-      if (!slow) nuss_traceback_fast(L2, tryp, nd.trb_y, lcky, nd.y, (uint32_t*)Py, lane);
+      fold_wave(std::integral_constant<uint32_t, 1>());
       if (prm.stamps && lane == 0) s_tky += wall_clock64() - ty0;
     }
     if (wave == 2) {
@@ -2199,8 +2129,8 @@ __global__ __launch_bounds__(DD_SOLVE_THREADS) void k_dd_solve(const dd_node* no
       // the counts (atomics) and the list of positive s_w (compacted in consensus-pair order: the dual value adds them in
       // that order) are ready when the DPs are.
       const uint32_t l3 = tid - 192;
-      for (uint32_t e = l3; e < npx; e += 64) nd.tx[e] = 0;
-      for (uint32_t e = l3; e < npy; e += 64) nd.ty[e] = 0;
+      for (uint32_t e = l3; e < npx; e += 64) fx.tc[e] = 0;
+      for (uint32_t e = l3; e < npy; e += 64) fy.tc[e] = 0;
       for (uint32_t e = l3; e < ncz; e += 64) nd.tz[e] = 0;
       __threadfence();  // the zeros are in place before the first count
       const uint32_t chunk = (ncbp + 63) / 64;
@@ -2209,12 +2139,12 @@ __global__ __launch_bounds__(DD_SOLVE_THREADS) void k_dd_solve(const dd_node* no
       uint32_t npos = 0;
       for (uint32_t u = u0; u < u1; ++u) {
         const uint32_t* cb = nd.cbp + (size_t)8 * u;
-        const float s_w = nd.q_x[(size_t)cb[0] * L1 + cb[1]] + nd.q_y[(size_t)cb[2] * L2 + cb[3]] -
+        const float s_w = fx.q[(size_t)cb[0] * L1 + cb[1]] + fy.q[(size_t)cb[2] * L2 + cb[3]] -
                           nd.q_z[(size_t)cb[0] * L2 + cb[2]] - nd.q_z[(size_t)cb[1] * L2 + cb[3]];
         if (s_w > 0.0f) {
           ++npos;
-          atomicAdd(&nd.tx[cb[4]], 1);
-          atomicAdd(&nd.ty[cb[5]], 1);
+          atomicAdd(&fx.tc[cb[4]], 1);
+          atomicAdd(&fy.tc[cb[5]], 1);
           atomicAdd(&nd.tz[cb[6]], 1);
           atomicAdd(&nd.tz[cb[7]], 1);
         }
@@ -2229,7 +2159,7 @@ __global__ __launch_bounds__(DD_SOLVE_THREADS) void k_dd_solve(const dd_node* no
       uint32_t pos = incl - npos;
       for (uint32_t u = u0; u < u1; ++u) {
         const uint32_t* cb = nd.cbp + (size_t)8 * u;
-        const float s_w = nd.q_x[(size_t)cb[0] * L1 + cb[1]] + nd.q_y[(size_t)cb[2] * L2 + cb[3]] -
+        const float s_w = fx.q[(size_t)cb[0] * L1 + cb[1]] + fy.q[(size_t)cb[2] * L2 + cb[3]] -
                           nd.q_z[(size_t)cb[0] * L2 + cb[2]] - nd.q_z[(size_t)cb[1] * L2 + cb[3]];
         if (s_w > 0.0f) nd.sw[pos++] = s_w;
       }
@@ -2260,12 +2190,12 @@ __global__ __launch_bounds__(DD_SOLVE_THREADS) void k_dd_solve(const dd_node* no
       // width: the span-ordered form of the standalone decoder, both at once, on all threads; and no further
       // register attempts in this launch.
       const bool slx = s_slowxy[0] != 0, sly = s_slowxy[1] != 0;
-      gave_up_x = gave_up_x || slx;
-      gave_up_y = gave_up_y || sly;
+      gave_up[0] = gave_up[0] || slx;
+      gave_up[1] = gave_up[1] || sly;
       if (slx || sly) {
-        nuss_pair_dp(slx ? L1 : 0u, nd.p_x, nd.q_x, w_x, nd.wx, sly ? L2 : 0u, nd.p_y, nd.q_y, w_y, nd.wy, prm.th_s);
-        if (tid == 0 && slx) { nuss_traceback(L1, nd.wx, nd.x, nd.wx.ck); s_score[0] = nd.wx.dp[L1 - 1]; }
-        if (tid == 64 && sly) { nuss_traceback(L2, nd.wy, nd.y, nd.wy.ck); s_score[1] = nd.wy.dp[L2 - 1]; }
+        nuss_pair_dp(slx ? L1 : 0u, fx.p, fx.q, w_x, fx.w, sly ? L2 : 0u, fy.p, fy.q, w_y, fy.w, prm.th_s);
+        if (tid == 0 && slx) { nuss_traceback(L1, fx.w, fx.ss, fx.w.ck); s_score[0] = fx.w.dp[L1 - 1]; }
+        if (tid == 64 && sly) { nuss_traceback(L2, fy.w, fy.ss, fy.w.ck); s_score[1] = fy.w.dp[L2 - 1]; }
         __syncthreads();
       }
     }
@@ -2276,45 +2206,50 @@ __global__ __launch_bounds__(DD_SOLVE_THREADS) void k_dd_solve(const dd_node* no
 
     // multiplier updates (:1121-1254), every cell touched by exactly one lane
     uint32_t viol = 0;
+    // Row i of folding f, whose predicted partner is j (or NONE): the multiplier of the predicted pair, then those of the row's
+    // flagged entries, each with both score copies kept current.  The predicted cell's multiplier q0, posterior p0, entry id0 and
+    // that entry's count tc0 come preloaded (see the x/z loop); the two tests stay nested as written -- merged into one the
+    // phase measured 6.4 us per iteration instead of 5.6 (profiles/r09_a_dd_ab.txt).
+    auto update_fold_row = [&](const dd_fold& f, float wf, uint32_t L, uint32_t W, uint32_t i, uint32_t j, size_t o0, float q0, float p0, int32_t id0, int tc0, uint32_t e0,
+                               uint32_t e1) {
+      auto put_score = [&](uint32_t jj, float p, float qn) {
+        const float sv = wf * (p - prm.th_s) - qn;
+        if (f.s) f.s[fold_sidx(false, L, W, i, jj)] = sv;
+        if (f.s_span) f.s_span[fold_sidx(true, L, W, i, jj)] = sv;
+      };
+      if (j != DD_NONE) {
+        const int tc = id0 >= 0 ? tc0 : 0;
+        if (tc != 1) {
+          ++viol;
+          const float qn = q0 - eta * (tc - 1);
+          f.q[o0] = qn;
+          if (j >= i + 3) put_score(j, p0, qn);  // shorter spans stay 0 (dd_fill_scores)
+        }
+      }
+      for (uint32_t e = e0; e < e1; ++e) {
+        if (!f.cflag[e]) continue;
+        const uint32_t jj = f.col[e];
+        const int tc = f.tc[e];
+        if (j != jj && tc != 0) {
+          ++viol;
+          const size_t o = (size_t)i * L + jj;
+          const float qn = f.q[o] - eta * tc;
+          f.q[o] = qn;
+          if (jj >= i + 3) put_score(jj, f.p[o], qn);
+        }
+      }
+    };
     for (uint32_t i = tid; i < L1; i += nt) {
       // The loads of a row's x and z cell are issued level by level, whether the row has such a cell or not (the indices of
       // the missing ones point at cell 0 of the row): the chain x -> map -> count -> multiplier, followed by the same chain
       // for z, was a dozen dependent trips to L2 per iteration.
-      const uint32_t j = nd.x[i], kz = nd.z[i];
-      const uint32_t pe0 = nd.px_ptr[i], pe1 = nd.px_ptr[i + 1], ce0 = nd.cz_ptr[i], ce1 = nd.cz_ptr[i + 1];
+      const uint32_t j = fx.ss[i], kz = nd.z[i];
+      const uint32_t pe0 = fx.ptr[i], pe1 = fx.ptr[i + 1], ce0 = nd.cz_ptr[i], ce1 = nd.cz_ptr[i + 1];
       const size_t ox = (size_t)i * L1 + (j != DD_NONE ? j : 0u), oz = (size_t)i * L2 + (kz != DD_NONE ? kz : 0u);
-      const int32_t idx = nd.xmap[ox], idz = nd.zmap[oz];
-      const float qx0 = nd.q_x[ox], px0 = nd.p_x[ox], qz0 = nd.q_z[oz];
-      const int tcx0 = nd.tx[idx >= 0 ? idx : 0], tcz0 = nd.tz[idz >= 0 ? idz : 0];
-      if (j != DD_NONE) {
-        const int tc = idx >= 0 ? tcx0 : 0;
-        if (tc != 1) {
-          ++viol;
-          const float qn = qx0 - eta * (tc - 1);
-          nd.q_x[ox] = qn;
-          if (j >= i + 3) {
-            const float sv = w_x * (px0 - prm.th_s) - qn;
-            if (nd.s_x) nd.s_x[fold_sidx(false, L1, Wx, i, j)] = sv;
-            if (nd.s_xs) nd.s_xs[fold_sidx(true, L1, Wx, i, j)] = sv;
-          }
-        }
-      }
-      for (uint32_t e = pe0; e < pe1; ++e) {
-        if (!nd.cx_flag[e]) continue;
-        const uint32_t jj = nd.px_j[e];
-        const int tc = nd.tx[e];
-        if (j != jj && tc != 0) {
-          ++viol;
-          const size_t o = (size_t)i * L1 + jj;
-          const float qn = nd.q_x[o] - eta * tc;
-          nd.q_x[o] = qn;
-          if (jj >= i + 3) {  // shorter spans stay 0 (dd_fill_scores)
-            const float sv = w_x * (nd.p_x[o] - prm.th_s) - qn;
-            if (nd.s_x) nd.s_x[fold_sidx(false, L1, Wx, i, jj)] = sv;
-            if (nd.s_xs) nd.s_xs[fold_sidx(true, L1, Wx, i, jj)] = sv;
-          }
-        }
-      }
+      const int32_t idx = fx.map[ox], idz = nd.zmap[oz];
+      const float qx0 = fx.q[ox], px0 = fx.p[ox], qz0 = nd.q_z[oz];
+      const int tcx0 = fx.tc[idx >= 0 ? idx : 0], tcz0 = nd.tz[idz >= 0 ? idz : 0];
+      update_fold_row(fx, w_x, L1, Ws[0], i, j, ox, qx0, px0, idx, tcx0, pe0, pe1);
       if (kz != DD_NONE) {
         const int tc = idz >= 0 ? tcz0 : 0;
         if (tc > 1) ++viol;
@@ -2336,41 +2271,13 @@ __global__ __launch_bounds__(DD_SOLVE_THREADS) void k_dd_solve(const dd_node* no
       }
     }
     for (uint32_t k = (tid + nt / 2) % nt; k < L2; k += nt) {  // the upper half of the workgroup starts on y while the lower half is on x
-      const uint32_t l = nd.y[k];
-      const uint32_t ye0 = nd.py_ptr[k], ye1 = nd.py_ptr[k + 1];
+      const uint32_t l = fy.ss[k];
+      const uint32_t ye0 = fy.ptr[k], ye1 = fy.ptr[k + 1];
       const size_t oy = (size_t)k * L2 + (l != DD_NONE ? l : 0u);
-      const int32_t idy = nd.ymap[oy];
-      const float qy0 = nd.q_y[oy], py0 = nd.p_y[oy];
-      const int tcy0 = nd.ty[idy >= 0 ? idy : 0];
-      if (l != DD_NONE) {
-        const int tc = idy >= 0 ? tcy0 : 0;
-        if (tc != 1) {
-          ++viol;
-          const float qn = qy0 - eta * (tc - 1);
-          nd.q_y[oy] = qn;
-          if (l >= k + 3) {
-            const float sv = w_y * (py0 - prm.th_s) - qn;
-            if (nd.s_y) nd.s_y[fold_sidx(false, L2, Wy, k, l)] = sv;
-            if (nd.s_ys) nd.s_ys[fold_sidx(true, L2, Wy, k, l)] = sv;
-          }
-        }
-      }
-      for (uint32_t e = ye0; e < ye1; ++e) {
-        if (!nd.cy_flag[e]) continue;
-        const uint32_t ll = nd.py_l[e];
-        const int tc = nd.ty[e];
-        if (l != ll && tc != 0) {
-          ++viol;
-          const size_t o = (size_t)k * L2 + ll;
-          const float qn = nd.q_y[o] - eta * tc;
-          nd.q_y[o] = qn;
-          if (ll >= k + 3) {
-            const float sv = w_y * (nd.p_y[o] - prm.th_s) - qn;
-            if (nd.s_y) nd.s_y[fold_sidx(false, L2, Wy, k, ll)] = sv;
-            if (nd.s_ys) nd.s_ys[fold_sidx(true, L2, Wy, k, ll)] = sv;
-          }
-        }
-      }
+      const int32_t idy = fy.map[oy];
+      const float qy0 = fy.q[oy], py0 = fy.p[oy];
+      const int tcy0 = fy.tc[idy >= 0 ? idy : 0];
+      update_fold_row(fy, w_y, L2, Ws[1], k, l, oy, qy0, py0, idy, tcy0, ye0, ye1);
     }
     if (viol) atomicAdd(&s_violated, viol);
     __syncthreads();
@@ -2506,8 +2413,8 @@ int dd_cbp_fill_launch(const dd_node* d_nodes, uint32_t nnodes, uint32_t max_len
 // into one buffer, so that one copy brings the results of all the nodes that finished in the launch.
 __global__ __launch_bounds__(256) void k_node_pack(const dd_node* nodes, const uint32_t* off_words, uint32_t* out) {
   const dd_node& nd = nodes[blockIdx.x];
-  const uint32_t* src = nd.x;
-  const uint32_t n = (uint32_t)((nd.info + 16) - nd.x);
+  const uint32_t* src = nd.f[0].ss;
+  const uint32_t n = (uint32_t)((nd.info + 16) - src);
   uint32_t* dst = out + off_words[blockIdx.x];
   for (uint32_t k = threadIdx.x; k < n; k += blockDim.x) dst[k] = src[k];
 }
