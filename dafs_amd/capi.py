@@ -166,6 +166,8 @@ _consensus_structure = _sig("dafs_hip_consensus_structure", C.c_int,
                              C.POINTER(C.c_float), C.c_void_p])
 _alignment_reliability = _sig("dafs_hip_alignment_reliability", C.c_int,
                               [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5)
+_alignment_covariation = _sig("dafs_hip_alignment_covariation", C.c_int,
+                              [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64] + [C.c_void_p] * 11)
 # dafs_allgather_fn(user, send, recv, bytes, hip_stream): the caller's collective of a sharded phase 1
 _allgather_fn = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 _phase1_sharded = _sig("dafs_hip_phase1_sharded", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_float, C.c_float, C.c_float,
@@ -212,6 +214,21 @@ def encode(seq):
     b = seq.encode() if isinstance(seq, str) else bytes(seq)
     table = np.array([residue_code(bytes([i])) for i in range(256)], dtype=np.uint8)
     return table[np.frombuffer(b, dtype=np.uint8)]
+
+
+_COV_CODE = np.full(256, 4, np.uint8)
+for _k, _chars in enumerate(("Aa", "Cc", "Gg", "UuTt")):
+    for _ch in _chars:
+        _COV_CODE[ord(_ch)] = _k
+
+
+def encode_alignment(rows):
+    """Alignment text (equally long rows) -> the uint8 [n, len] codes of Context.alignment_covariation: A 0, C 1, G 2, U / T 3
+    in either case, everything else (gaps, N, IUPAC codes) 4."""
+    rows = [r.encode("latin-1") if isinstance(r, str) else bytes(r) for r in rows]
+    if not rows or any(len(r) != len(rows[0]) for r in rows):
+        raise ValueError("encode_alignment: at least one row, all of one length")
+    return _COV_CODE[np.frombuffer(b"".join(rows), np.uint8)].reshape(len(rows), len(rows[0]))
 
 
 class PairPosteriors:
@@ -572,6 +589,39 @@ class Context:
                                      -1 if mp_relaxed is None else int(mp_relaxed), -1 if bp_relaxed is None else int(bp_relaxed),
                                      res.ctypes.data, col.ctypes.data, pair.ctypes.data, rows.ctypes.data, C.byref(ea)))
         return dict(residue=res, col=col, pair=pair, pair_rows=rows, expected_accuracy=ea.value)
+
+
+    def alignment_covariation(self, rows, ss=None, shuffles=100, seed=1, matrix=False):
+        """Covariation statistics of an alignment (dafs_hip_alignment_covariation).  rows: the text
+        rows, or their codes (uint8 [n, len], encode_alignment).  ss: the consensus structure or None.  shuffles, seed: the
+        column-shuffle null behind the E-values (0: no null, every E is NaN).  Returns a dict of numpy arrays per column:
+        col_sum (int64), best, best_score, best_e, and at the left column of each pair of ss pair_score, pair_e, pair_rows,
+        pair_canonical, pair_types; total (int); with matrix, g (int64 [len, len])."""
+        if isinstance(rows, np.ndarray) and rows.ndim == 2 and rows.dtype.kind in "iu":  # codes: any integer type, checked
+            if rows.size and (rows.min() < 0 or rows.max() > 255):
+                raise ValueError("alignment_covariation: codes must fit a byte (the library refuses a code above 4)")
+            code = np.ascontiguousarray(rows, np.uint8)
+        elif isinstance(rows, np.ndarray):
+            raise ValueError("alignment_covariation: rows are text rows or a 2-D integer array of codes")
+        else:
+            code = encode_alignment(rows)
+        n, L = code.shape
+        ss = None if ss is None else np.ascontiguousarray(ss, np.uint32)
+        if ss is not None and ss.shape != (L,):
+            raise ValueError("alignment_covariation: ss needs one entry per column")
+        out = dict(col_sum=np.zeros(L, np.int64), best=np.zeros(L, np.uint32), best_score=np.zeros(L, np.float64),
+                   best_e=np.zeros(L, np.float64), pair_score=np.zeros(L, np.float64), pair_e=np.zeros(L, np.float64),
+                   pair_rows=np.zeros(L, np.uint32), pair_canonical=np.zeros(L, np.uint32), pair_types=np.zeros(L, np.uint32))
+        total = C.c_int64()
+        g = np.zeros((L, L), np.int64) if matrix else None
+        check(_alignment_covariation(self._h, n, L, code.ctypes.data, None if ss is None else ss.ctypes.data, int(shuffles), int(seed),
+                                     *[out[k].ctypes.data for k in ("col_sum", "best", "best_score", "best_e", "pair_score", "pair_e",
+                                                                     "pair_rows", "pair_canonical", "pair_types")],
+                                     C.byref(total), None if g is None else g.ctypes.data))
+        out["total"] = total.value
+        if matrix:
+            out["g"] = g
+        return out
 
 
 def build_tree(sim):

@@ -32,6 +32,7 @@
 #include <iostream>
 #include <map>
 #include <queue>
+#include <set>
 #include <sstream>
 #include <string>
 #include <system_error>
@@ -76,6 +77,10 @@ struct Options {
   std::string seed;       // --seed SEED: add FILE's sequences to this alignment
   bool pairwise = false;  // --pairwise: every pair of FILE's sequences aligned as a two-sequence run
   std::string pairwise_scores;  // --pairwise-scores OUT
+  std::string covariation;      // --covariation OUT
+  uint32_t cov_shuffles = 100;  // --cov-shuffles K
+  uint64_t cov_seed = 1;        // --cov-seed S
+  bool cov_shuffles_given = false, cov_seed_given = false;
   bool refinement_given = false;
   std::string input;
   std::vector<std::string> inputs;  // every FILE argument; with two or more, one output block per file
@@ -109,6 +114,14 @@ const char* kHelp =
     "                        Not with -r, --seed, --devices, --align-aux, --fold-aux or --save-*-aux\n"
     "      --pairwise-scores OUT  With --pairwise: a tab-separated table, one line per pair:\n"
     "                        i j name_i name_j similarity score iterations (the root node's objective and iterations)\n"
+    "      --covariation OUT Also write the covariation statistics of every printed alignment to OUT, one tab-separated\n"
+    "                        line per column pair: c1 c2 kind S E rows canonical types (columns 1-based; S: the G statistic\n"
+    "                        with average-product correction, in nats; E: expected number of column pairs that reach S in\n"
+    "                        column-shuffled alignments, a null that ignores phylogeny).  First the pairs of SS_cons (kind\n"
+    "                        ss), then each column's best partner where it is no such pair and E <= 0.05 (kind other).\n"
+    "                        With --stockholm a #=GC cov_SS_cons line marks the pairs with E <= 0.05.  Not with --pairwise\n"
+    "      --cov-shuffles K  Shuffled alignments behind E (default: 100; 0: no E-values); needs --covariation\n"
+    "      --cov-seed S      Seed of the shuffles (default: 1); needs --covariation\n"
     "\n Aligning options:\n"
     "  -a, --align-model arg Alignment model (value=CONTRAlign, ProbCons) (default: ProbCons)\n"
     "  -p, --align-pct arg   Weight of PCT for matching probabilities (default: 0.25)\n"
@@ -148,7 +161,8 @@ Options parse(int argc, char** argv) {
       {"no-alifold", {0, false}}, {"fold-th1", {'T', true}}, {"gamma1", {'G', true}}, {"ipknot", {0, false}},
       {"bp-update", {0, false}}, {"bp-update1", {0, false}}, {"fold-aux", {0, true}}, {"save-align-aux", {0, true}},
       {"save-fold-aux", {0, true}}, {"device", {0, true}}, {"devices", {0, true}}, {"input", {0, true}},
-      {"stockholm", {0, true}}, {"seed", {0, true}}, {"pairwise", {0, false}}, {"pairwise-scores", {0, true}}};
+      {"stockholm", {0, true}}, {"seed", {0, true}}, {"pairwise", {0, false}}, {"pairwise-scores", {0, true}},
+      {"covariation", {0, true}}, {"cov-shuffles", {0, true}}, {"cov-seed", {0, true}}};
   std::map<char, std::string> shorts;
   for (const auto& kv : spec)
     if (kv.second.first) shorts[kv.second.first] = kv.first;
@@ -221,7 +235,28 @@ Options parse(int argc, char** argv) {
       if (value.empty()) throw std::string("--pairwise-scores needs a file name");
       o.pairwise_scores = value;
     }
+    else if (name == "covariation") {
+      if (value.empty()) throw std::string("--covariation needs a file name");
+      o.covariation = value;
+    }
+    else if (name == "cov-shuffles" || name == "cov-seed") {
+      size_t used = 0;
+      unsigned long long v = 0;
+      try {
+        if (value.empty() || value[0] < '0' || value[0] > '9') throw std::invalid_argument(value);
+        v = std::stoull(value, &used, 10);
+      } catch (const std::exception&) {
+        used = 0;
+      }
+      if (used == 0 || used != value.size() || (name == "cov-shuffles" && v > 0xFFFFFFFFull))
+        throw "--" + name + " needs a non-negative integer";
+      if (name == "cov-shuffles") { o.cov_shuffles = (uint32_t)v; o.cov_shuffles_given = true; }
+      else { o.cov_seed = v; o.cov_seed_given = true; }
+    }
   }
+  if ((o.cov_shuffles_given || o.cov_seed_given) && o.covariation.empty()) throw std::string("--cov-shuffles and --cov-seed need --covariation");
+  if (o.pairwise && (!o.covariation.empty() || o.cov_shuffles_given || o.cov_seed_given))
+    throw std::string("--pairwise: two rows carry no covariation; --covariation, --cov-shuffles and --cov-seed cannot be combined with --pairwise");
   if (!o.pairwise_scores.empty() && !o.pairwise) throw std::string("--pairwise-scores needs --pairwise");
   if (o.pairwise) {  // every pair is a two-sequence run of its own: nothing that reads or writes one run's whole state
     if (o.refinement_given) throw std::string("--pairwise: -r cannot be combined with --pairwise");
@@ -569,11 +604,13 @@ std::vector<std::string> stockholm_names(const std::vector<Fasta>& ff) {
 
 // rows in stdout order: name, printed text and the reliabilities of its residues; col_rel per column ('.' where a column
 // holds no residue).  Labels padded to the longest plus one.  tree_line nullptr: no "#=GF CC" line; rf: per column a seed
-// column ('x') or an insert column ('.') of --seed, written as "#=GC RF" after PP_cons (nullptr: no RF line).
+// column ('x') or an insert column ('.') of --seed, written as "#=GC RF" after PP_cons (nullptr: no RF line).  cov: the
+// characters of "#=GC cov_SS_cons", written directly after PP_cons (nullptr: no such line, labels as wide as without it).
 std::string stockholm_block(const std::string* tree_line, const std::vector<std::string>& names, const std::vector<std::string>& rows,
                             const std::vector<const double*>& rel, const std::vector<double>& col_rel, const std::string& ss,
-                            const std::vector<bool>* rf = nullptr) {
+                            const std::vector<bool>* rf = nullptr, const std::string* cov = nullptr) {
   size_t width = std::max(std::string("#=GC SS_cons").size(), std::string("#=GC PP_cons").size());
+  if (cov) width = std::max(width, std::string("#=GC cov_SS_cons").size());
   for (const std::string& nm : names) width = std::max(width, nm.size() + 8);  // "#=GR " + name + " PP"
   ++width;
   auto label = [&](const std::string& l) { return l + std::string(width - l.size(), ' '); };
@@ -591,6 +628,7 @@ std::string stockholm_block(const std::string* tree_line, const std::vector<std:
     for (const std::string& row : rows)
       if (row[c] != '-') { cons[c] = pp_char(col_rel[c]); break; }
   out += label("#=GC SS_cons") + ss + "\n" + label("#=GC PP_cons") + cons + "\n";
+  if (cov) out += label("#=GC cov_SS_cons") + *cov + "\n";
   if (rf) {
     std::string line(rf->size(), '.');
     for (size_t c = 0; c < rf->size(); ++c)
@@ -599,6 +637,80 @@ std::string stockholm_block(const std::string* tree_line, const std::vector<std:
   }
   out += "//\n";
   return out;
+}
+
+// --covariation: the statistics of one printed alignment (dafs_hip_alignment_covariation).
+// pipeline.covariation_tsv and stockholm.cov_ss_cons are the Python twins; both sides write the same bytes.
+const double kCovEMax = 0.05;
+
+std::string fmt9d(double v) {
+  if (std::isnan(v)) return "nan";
+  char buf[64];
+  snprintf(buf, sizeof buf, "%.9g", v);
+  return buf;
+}
+
+uint8_t cov_code(char ch) {
+  switch (ch) {
+    case 'A': case 'a': return 0;
+    case 'C': case 'c': return 1;
+    case 'G': case 'g': return 2;
+    case 'U': case 'u': case 'T': case 't': return 3;
+    default: return 4;
+  }
+}
+
+// rows: the printed rows; ss: the structure.  tsv: the table of this alignment; chars: the cov_SS_cons characters.
+void covariation_of(dafs_hip_ctx* ctx, const Options& o, const std::vector<std::string>& rows, const std::vector<uint32_t>& ss,
+                    std::string& tsv, std::string& chars) {
+  const uint32_t n = (uint32_t)rows.size(), L = (uint32_t)ss.size();
+  std::vector<uint8_t> code((size_t)n * L);
+  for (uint32_t r = 0; r < n; ++r)
+    for (uint32_t c = 0; c < L; ++c) code[(size_t)r * L + c] = cov_code(rows[r][c]);
+  std::vector<uint32_t> best(L), prow(L), pcan(L), ptyp(L);
+  std::vector<double> bscore(L), be(L), pscore(L), pe(L);
+  check(dafs_hip_alignment_covariation(ctx, n, L, code.data(), ss.data(), o.cov_shuffles, o.cov_seed, nullptr, best.data(), bscore.data(),
+                                       be.data(), pscore.data(), pe.data(), prow.data(), pcan.data(), ptyp.data(), nullptr, nullptr));
+  chars.assign(L, '.');
+  std::ostringstream os;
+  std::set<std::pair<uint32_t, uint32_t> > cons;
+  for (uint32_t c = 0; c < L; ++c) {
+    if (ss[c] == DAFS_HIP_NONE) continue;
+    cons.insert(std::make_pair(c, ss[c]));
+    if (pe[c] <= kCovEMax) chars[c] = chars[ss[c]] = '2';
+    os << c + 1 << "\t" << ss[c] + 1 << "\tss\t" << fmt9d(pscore[c]) << "\t" << fmt9d(pe[c]) << "\t" << prow[c] << "\t" << pcan[c] << "\t" << ptyp[c] << "\n";
+  }
+  std::map<std::pair<uint32_t, uint32_t>, uint32_t> other;  // pair -> the first column that names it
+  for (uint32_t c = 0; c < L; ++c) {
+    if (best[c] == DAFS_HIP_NONE || !(be[c] <= kCovEMax)) continue;
+    const std::pair<uint32_t, uint32_t> pr(std::min(c, best[c]), std::max(c, best[c]));
+    if (!cons.count(pr) && !other.count(pr)) other[pr] = c;
+  }
+  for (const auto& kv : other) {
+    const uint32_t c1 = kv.first.first, c2 = kv.first.second, c = kv.second;
+    uint32_t cnt[4][4] = {{0}};
+    uint32_t both = 0;
+    for (uint32_t r = 0; r < n; ++r) {
+      const uint8_t a = code[(size_t)r * L + c1], b = code[(size_t)r * L + c2];
+      if (a < 4 && b < 4) { ++cnt[a][b]; ++both; }
+    }
+    const uint32_t six[6] = {cnt[0][3], cnt[3][0], cnt[2][1], cnt[1][2], cnt[2][3], cnt[3][2]};  // AU UA GC CG GU UG
+    uint32_t canonical = 0, types = 0;
+    for (uint32_t v : six) { canonical += v; types += v ? 1 : 0; }
+    os << c1 + 1 << "\t" << c2 + 1 << "\tother\t" << fmt9d(bscore[c]) << "\t" << fmt9d(be[c]) << "\t" << both << "\t" << canonical << "\t" << types << "\n";
+  }
+  tsv = os.str();
+}
+
+void write_covariation(const std::string& file, const std::vector<std::string>& tables, const std::vector<std::string>* headers) {
+  std::ofstream os(file.c_str(), std::ios::binary);
+  if (!os.is_open()) throw "--covariation: cannot open " + file;
+  for (size_t k = 0; k < tables.size(); ++k) {
+    if (headers) os << "==> " << (*headers)[k] << " <==\n";
+    os << tables[k];
+  }
+  os.flush();
+  if (!os) throw "--covariation: cannot write " + file;
 }
 
 void write_stockholm(const std::string& file, const std::vector<std::string>& blocks) {
@@ -864,7 +976,7 @@ struct PairChunk {
 
 int align_group(dafs_hip_ctx* ctx, const Options& o, Ranks& rk, int align_model, const std::vector<std::vector<Fasta> >& fams,
                 const std::vector<size_t>& members, const std::vector<std::ostream*>& out, const std::vector<std::string*>& sto,
-                PairChunk* pc = nullptr);
+                PairChunk* pc = nullptr, const std::vector<std::string*>& cov = std::vector<std::string*>());
 
 struct Guard {  // the context of a run, destroyed however the run ends
   dafs_hip_ctx* c;
@@ -936,10 +1048,13 @@ dafs_dd_params dd_params_of(const Options& o) {
 // The common secondary structure of a final alignment (:1857-1871; no RNAalifold term here) and its output (:1876-1879,
 // :1584-1601) on os: ">SS_cons", the brackets, then the rows sorted by sequence index.  The structure is decoded over the
 // rows in the order root holds them.  fa: the context's sequences; ff: the family's, its first one at index first.  With sto,
-// also the family's Stockholm block: tree_line (nullptr: no CC line), rf (nullptr: no RF line).
+// also the family's Stockholm block: tree_line (nullptr: no CC line), rf (nullptr: no RF line).  With cov (--covariation), the
+// alignment's covariation table into *cov, and its cov_SS_cons line into the Stockholm block.
 void finish_alignment(dafs_hip_ctx* ctx, const Options& o, const std::vector<Fasta>& fa, ALN& root, const std::vector<Fasta>& ff,
-                      uint32_t first, std::ostream& os, std::string* sto, const std::string* tree_line, const std::vector<bool>* rf) {
+                      uint32_t first, std::ostream& os, std::string* sto, const std::string* tree_line, const std::vector<bool>* rf,
+                      std::string* cov = nullptr) {
   std::string str;
+  VU ss_final;
   std::vector<double> rel, col_rel;   // --stockholm: the reliabilities of this alignment and structure
   std::map<uint32_t, size_t> rel_at;  // sequence -> its first residue in rel
   {
@@ -957,6 +1072,7 @@ void finish_alignment(dafs_hip_ctx* ctx, const Options& o, const std::vector<Fas
     std::vector<char> buf(L + 1);
     dafs_hip_make_brackets(L, ss.data(), buf.data());
     str.assign(buf.data());
+    ss_final = ss;
     if (sto) {  // from the stores the progressive phase read (with --bp-update1 too: ss is the re-decoded one)
       size_t tot = 0;
       for (uint32_t s0 : rs) { rel_at[s0] = tot; tot += fa[s0].size(); }
@@ -980,6 +1096,8 @@ void finish_alignment(dafs_hip_ctx* ctx, const Options& o, const std::vector<Fas
     os << text << std::endl;
     rows.push_back(text);
   }
+  std::string cov_chars;
+  if (cov) covariation_of(ctx, o, rows, ss_final, *cov, cov_chars);
   if (sto) {
     const std::vector<std::string> all_names = stockholm_names(ff);
     std::vector<std::string> names;
@@ -988,7 +1106,7 @@ void finish_alignment(dafs_hip_ctx* ctx, const Options& o, const std::vector<Fas
       names.push_back(all_names[row.first - first]);
       rr.push_back(rel.data() + rel_at[row.first]);
     }
-    *sto = stockholm_block(tree_line, names, rows, rr, col_rel, str, rf);
+    *sto = stockholm_block(tree_line, names, rows, rr, col_rel, str, rf, cov ? &cov_chars : nullptr);
   }
 }
 
@@ -1080,10 +1198,11 @@ int run_add(const Options& o, int align_model) {
   }
   std::vector<bool> rf(width, false);
   for (uint32_t c = 0; c < C; ++c) rf[seed_col[c]] = true;
-  std::string sto;
-  finish_alignment(ctx, o, fa, root, fa, 0, std::cout, o.stockholm.empty() ? nullptr : &sto, nullptr, &rf);
+  std::string sto, cov;
+  finish_alignment(ctx, o, fa, root, fa, 0, std::cout, o.stockholm.empty() ? nullptr : &sto, nullptr, &rf, o.covariation.empty() ? nullptr : &cov);
   std::cout.flush();
   if (!o.stockholm.empty()) write_stockholm(o.stockholm, {sto});
+  if (!o.covariation.empty()) write_covariation(o.covariation, {cov}, nullptr);
   return 0;
 }
 
@@ -1246,9 +1365,18 @@ int run(const Options& o, Ranks& rk) {
       for (size_t f : members) v.push_back(&sto_blocks[f]);
     return v;
   };
+  // --covariation: one table per input file, in input order, written by the process that prints
+  std::vector<std::string> cov_tables(o.covariation.empty() ? 0 : o.inputs.size());
+  auto cov_of = [&](const std::vector<size_t>& members) {
+    std::vector<std::string*> v;
+    if (!cov_tables.empty())
+      for (size_t f : members) v.push_back(&cov_tables[f]);
+    return v;
+  };
   if (!multi) {
-    align_group(ctx, o, rk, align_model, fams, {0}, {&std::cout}, sto_of({0}));
+    align_group(ctx, o, rk, align_model, fams, {0}, {&std::cout}, sto_of({0}), nullptr, cov_of({0}));
     if (rk.rank == 0 && !o.stockholm.empty()) write_stockholm(o.stockholm, sto_blocks);
+    if (rk.rank == 0 && !o.covariation.empty()) write_covariation(o.covariation, cov_tables, nullptr);
     return 0;
   }
   // Several files: every file with two or more sequences in one batch (dafs_hip_set_families: shared launches, one guide
@@ -1267,7 +1395,7 @@ int run(const Options& o, Ranks& rk) {
     std::vector<std::ostream*> os;
     for (size_t f : members) os.push_back(&outs[f]);
     try {
-      align_group(ctx, o, rk, align_model, fams, members, os, sto_of(members));
+      align_group(ctx, o, rk, align_model, fams, members, os, sto_of(members), nullptr, cov_of(members));
     } catch (const char* str) {
       throw names(members) + ": " + str;
     } catch (const std::string& str) {
@@ -1280,16 +1408,17 @@ int run(const Options& o, Ranks& rk) {
   for (size_t f = 0; f < fams.size(); ++f) std::cout << "==> " << o.inputs[f] << " <==" << std::endl << outs[f].str();
   std::cout.flush();
   if (!o.stockholm.empty()) write_stockholm(o.stockholm, sto_blocks);
+  if (!o.covariation.empty()) write_covariation(o.covariation, cov_tables, &o.inputs);
   return 0;
 }
 
 // The run of one or more families (members: indices into fams) on the context: phase 1 once over all of them, one guide
 // tree per family, the progressive phase over the forest (the ready nodes of every family share each round), then per
 // family the refinement, the common structure and the output on *out[k]; with --stockholm (sto not empty) also the
-// family's Stockholm block in *sto[k].
+// family's Stockholm block in *sto[k], and with --covariation (cov not empty) its covariation table in *cov[k].
 int align_group(dafs_hip_ctx* ctx, const Options& o, Ranks& rk, int align_model, const std::vector<std::vector<Fasta> >& fams,
                 const std::vector<size_t>& members, const std::vector<std::ostream*>& out, const std::vector<std::string*>& sto,
-                PairChunk* pc) {
+                PairChunk* pc, const std::vector<std::string*>& cov) {
   const uint F = (uint)members.size();
   std::vector<Fasta> fa;         // every sequence of the group, family after family
   std::vector<uint32_t> first(1, 0);
@@ -1423,7 +1552,8 @@ int align_group(dafs_hip_ctx* ctx, const Options& o, Ranks& rk, int align_model,
       print_tree(tl, trees[f], fams[members[f]], (int)trees[f].size() - 1);
       tree_line = tl.str();
     }
-    finish_alignment(ctx, o, fa, root, fams[members[f]], first[f], *out[f], sto.empty() ? nullptr : sto[f], &tree_line, nullptr);
+    finish_alignment(ctx, o, fa, root, fams[members[f]], first[f], *out[f], sto.empty() ? nullptr : sto[f], &tree_line, nullptr,
+                     cov.empty() ? nullptr : cov[f]);
   }
   return 0;
 }

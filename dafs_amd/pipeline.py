@@ -90,13 +90,14 @@ class Result:
 def run(names, seqs, ctx=None, bp=None, w=4.0, eta0=0.5, t_max=600, w_pct_a=0.25, w_pct_s=0.25, th_a=0.01,
         th_s=0.2, th_s1=None, align_model=capi.ALIGN_PROBCONS, force_iters=0, timers=None, level_sync=False, slice_iters=None,
         mp=None, skip_uncoupled_folds=True, shard=None, round_us=None, w_pct_f=0.0, bp_update=False, bp_update1=False,
-        reliability=False):
+        reliability=False, covariation=False):
     """The whole run.  bp: per-sequence (rowptr, col, val) base-pairing rows (--fold-aux); None
     computes them with the device fold model.  mp: supplied matching probabilities (--align-aux), see Context.set_mp.
     shard: (torch.distributed module, torch device) of an initialised process group -- phase 1 (folds, pair posteriors,
     matching consistency transform) is then split over the ranks and gathered (dist.phase1_sharded); every rank
     finishes the run and holds the same result.  reliability: the result also gets .reliability and .stockholm (see
-    _phase2_forest)."""
+    _phase2_forest).  covariation: True or a dict with shuffles (100), seed (1), e_max (0.05): the result also gets
+    .covariation (see _final)."""
     import time
     # combinations this driver does not implement are refused, not ignored (the command line, cli_main.cpp, has no level
     # batches: its --bp-update runs in the resident-node rounds and in the refinement's solve_node)
@@ -120,7 +121,7 @@ def run(names, seqs, ctx=None, bp=None, w=4.0, eta0=0.5, t_max=600, w_pct_a=0.25
     t.append(time.perf_counter())
     fam = dict(names=names, seqs=seqs, first=0, sim=sim, tree=(score, left, right))
     return _phase2_forest(ctx, own, [fam], t, w, eta0, t_max, th_a, th_s, th_s1, force_iters, level_sync, slice_iters,
-                          skip_uncoupled_folds, round_us, bp_update, bp_update1, reliability)[0]
+                          skip_uncoupled_folds, round_us, bp_update, bp_update1, reliability, covariation)[0]
 
 
 def _phase1_local(ctx, seqs, bp, mp, align_model, th_a, w_pct_a, w_pct_s, t, w_pct_f=0.0, first=None):
@@ -217,7 +218,7 @@ def _solve_nodes(ctx, prm, take_ready, finish, level_sync=False, slice_iters=Non
 
 
 def _phase2_forest(ctx, own, fams, t, w, eta0, t_max, th_a, th_s, th_s1, force_iters, level_sync, slice_iters,
-                   skip_uncoupled_folds, round_us=None, bp_update=False, bp_update1=False, reliability=False):
+                   skip_uncoupled_folds, round_us=None, bp_update=False, bp_update1=False, reliability=False, covariation=False):
     """The progressive phase and the output of every family of the context at once.  fams: per family a dict with names,
     seqs, first (index of its first sequence in the context), sim and tree = (score, left, right).  The guide trees form one
     forest: a node is ready when both of its children are done, whatever its family, and the ready nodes of all families
@@ -225,8 +226,9 @@ def _phase2_forest(ctx, own, fams, t, w, eta0, t_max, th_a, th_s, th_s1, force_i
     reliability: each Result also gets .reliability, the annotation of its final alignment and structure from the stores
     the progressive phase read (Context.alignment_reliability): a dict with residue (per printed row, its residues'
     values), col, pair, pair_rows and expected_accuracy; and .stockholm, that alignment as a Stockholm block with PP lines
-    (dafs_amd/stockholm.py, the same bytes `dafs --stockholm` writes)."""
+    (dafs_amd/stockholm.py, the same bytes `dafs --stockholm` writes).  covariation: see _final."""
     import time
+    covariation = cov_options(covariation)
     nf = len(fams)
     results = []
     trees = []
@@ -305,7 +307,7 @@ def _phase2_forest(ctx, own, fams, t, w, eta0, t_max, th_a, th_s, th_s1, force_i
         res.rounds = rounds
         n = len(fm["seqs"])
         sidx, mask = aln[(f, 2 * n - 2)]
-        _final(ctx, res, fm["names"], fm["seqs"], fm["first"], sidx, mask, th1, bp_update1, reliability, res.tree_line)
+        _final(ctx, res, fm["names"], fm["seqs"], fm["first"], sidx, mask, th1, bp_update1, reliability, res.tree_line, None, covariation)
     t.append(time.perf_counter())
     # fold_launch: the folding is only started there; its kernels overlap `pair` and the first half of `pct_fold_tree`,
     # which also holds the wait for them
@@ -318,11 +320,26 @@ def _phase2_forest(ctx, own, fams, t, w, eta0, t_max, th_a, th_s, th_s1, force_i
     return results
 
 
-def _final(ctx, res, names, seqs, first, sidx, mask, th1, bp_update1, reliability, tree_line, rf=None):
+def cov_options(covariation):
+    """The covariation option of run / run_batch / add as a dict with shuffles, seed and e_max, or None for off"""
+    if covariation is None or covariation is False:
+        return None
+    opt = dict(shuffles=100, seed=1, e_max=0.05)
+    if covariation is not True:
+        unknown = set(covariation) - set(opt)
+        if unknown:
+            raise ValueError("covariation: unknown keys %s (shuffles, seed, e_max)" % sorted(unknown))
+        opt.update(covariation)
+    return opt
+
+
+def _final(ctx, res, names, seqs, first, sidx, mask, th1, bp_update1, reliability, tree_line, rf=None, covariation=None):
     """The common structure of a final alignment (sidx: global sequence index per row, mask) and its output, into res:
     .ss, .ss_str, .rows, .output and, with reliability, .reliability and .stockholm.  names / seqs: the family's, its first
     sequence at global index `first`.  tree_line None: no tree line (pipeline.add); rf: the RF line of the Stockholm
-    block."""
+    block.  covariation (cov_options): .covariation, the dict of Context.alignment_covariation on the printed rows and
+    structure with the options' shuffles, seed and e_max beside the arrays; the Stockholm block then
+    carries a `#=GC cov_SS_cons` line."""
     _, ss, _ = ctx.consensus_structure(sidx, mask, th1)
     if bp_update1:  # :1863-1869: decode, re-estimate under that structure, decode again
         _, ss = ctx.nussinov(ctx.update_basepairing(sidx, mask, ss), None, th1)
@@ -339,6 +356,12 @@ def _final(ctx, res, names, seqs, first, sidx, mask, th1, bp_update1, reliabilit
         res.rows.append(row)
         lines += ["> " + names[local], row]
     res.output = "\n".join(lines) + "\n"
+    cov_chars = None
+    if covariation:
+        cv = ctx.alignment_covariation(res.rows, ss, shuffles=covariation["shuffles"], seed=covariation["seed"])
+        cv.update(covariation)
+        res.covariation = cv
+        cov_chars = stockholm.cov_ss_cons(ss, cv["pair_e"], cv["e_max"])
     if reliability:
         rl = ctx.alignment_reliability(sidx, mask, ss)
         cuts = np.cumsum([len(seqs[int(s) - first]) for s in sidx])[:-1]
@@ -347,12 +370,12 @@ def _final(ctx, res, names, seqs, first, sidx, mask, th1, bp_update1, reliabilit
         res.reliability = rl
         sto_names = stockholm.names(names)
         res.stockholm = stockholm.block(tree_line, [sto_names[int(sidx[r]) - first] for r in order], res.rows, rl["residue"],
-                                        rl["col"], res.ss_str, rf)
+                                        rl["col"], res.ss_str, rf, cov_chars)
 
 
 def add(seed_names, seed_rows, names, seqs, ctx=None, w=4.0, eta0=0.5, t_max=600, w_pct_a=0.25, w_pct_s=0.25, th_a=0.01,
         th_s=0.2, th_s1=None, align_model=capi.ALIGN_PROBCONS, force_iters=0, slice_iters=None, skip_uncoupled_folds=True,
-        round_us=None, w_pct_f=0.0, bp_update1=False, reliability=False):
+        round_us=None, w_pct_f=0.0, bp_update1=False, reliability=False, covariation=False):
     """Add new sequences to a fixed seed alignment without changing its columns (`dafs --seed`).
     seed_names / seed_rows: the seed's rows (letters and '.' / '-' gaps; stockholm.read_seed reads a file), checked and
     without their all-gap columns (stockholm.clean_seed).  names / seqs: the new sequences.  The options are run()'s.
@@ -363,8 +386,9 @@ def add(seed_names, seed_rows, names, seqs, ctx=None, w=4.0, eta0=0.5, t_max=600
     Returns a Result: .output (a normal run's format without the tree line: rows in context order), .rows, .ss, .ss_str,
     .z (per new sequence its column map into the seed), .rf (per merged column True for a seed column), .dd_log
     ({j: (iterations, violated, ncbp, score)}), .dd_memory, .seconds; with reliability, .reliability and .stockholm (no CC
-    line, a `#=GC RF` line)."""
+    line, a `#=GC RF` line); with covariation (as in run), .covariation."""
     import time
+    covariation = cov_options(covariation)
     seed_names, seed_rows = stockholm.clean_seed(seed_names, seed_rows)
     names, seqs = list(names), list(seqs)
     if not seqs or len(names) != len(seqs):
@@ -406,7 +430,7 @@ def add(seed_names, seed_rows, names, seqs, ctx=None, w=4.0, eta0=0.5, t_max=600
         res.dd_log = {j: (o["iterations"], o["violated"], o["ncbp"], o["score"]) for j, o in enumerate(outs)}
         res.dd_memory = dd_memory
         _final(ctx, res, all_names, all_seqs, 0, sidx, np.concatenate([mask[m:], mask[:m]]), th_s if th_s1 is None else th_s1,
-               bp_update1, reliability, None, rf)
+               bp_update1, reliability, None, rf, covariation)
         t.append(time.perf_counter())
         res.seconds = dict(phase1=t[3] - t[0], nodes=t[4] - t[3], final=t[5] - t[4], total=t[5] - t[0])
     finally:
@@ -495,7 +519,7 @@ def run_batch(families, ctx=None, max_bytes=None, **kw):
             t.append(time.perf_counter())
             res = _phase2_forest(ctx, False, fams, t, opts["w"], opts["eta0"], opts["t_max"], opts["th_a"], opts["th_s"], opts["th_s1"],
                                  opts["force_iters"], opts["level_sync"], opts["slice_iters"], opts["skip_uncoupled_folds"], opts["round_us"],
-                                 opts["bp_update"], opts["bp_update1"], opts["reliability"])
+                                 opts["bp_update"], opts["bp_update1"], opts["reliability"], opts["covariation"])
             for k, r in zip(grp, res):
                 out[k] = r
     finally:
@@ -570,6 +594,40 @@ class Pairwise:
     pass
 
 
+COV_TABLE_E_MAX = 0.05  # the cut of the table's `other` pairs: fixed, as on the command line (e_max moves cov_SS_cons only)
+_CANONICAL = ((0, 3), (3, 0), (2, 1), (1, 2), (2, 3), (3, 2))  # AU UA GC CG GU UG
+
+
+def covariation_tsv(result):
+    """The table of `dafs --covariation OUT` for one result with .covariation (the C++ writer in cli_main.cpp writes the same
+    bytes): one line "c1<TAB>c2<TAB>kind<TAB>S<TAB>E<TAB>rows<TAB>canonical<TAB>types" per pair, columns 1-based, floats as
+    %.9g.  First every consensus pair by ascending left column (kind ss); then every distinct pair {c, best(c)} that is no
+    consensus pair and has E <= 0.05 (COV_TABLE_E_MAX, whatever the result's e_max), ordered by (c1, c2) (kind other), its
+    counts taken from the rows."""
+    cv, ss = result.covariation, result.ss
+    lines, cons = [], set()
+    for c in range(len(ss)):
+        if int(ss[c]) != NONE:
+            cons.add((c, int(ss[c])))
+            lines.append("%d\t%d\tss\t%s\t%s\t%d\t%d\t%d\n" % (c + 1, int(ss[c]) + 1, _fmt9(cv["pair_score"][c]), _fmt9(cv["pair_e"][c]),
+                                                                 int(cv["pair_rows"][c]), int(cv["pair_canonical"][c]), int(cv["pair_types"][c])))
+    other = {}
+    for c in range(len(ss)):
+        b = int(cv["best"][c])
+        if b == NONE or not float(cv["best_e"][c]) <= COV_TABLE_E_MAX:
+            continue
+        pr = (min(c, b), max(c, b))
+        if pr not in cons and pr not in other:
+            other[pr] = c
+    code = capi.encode_alignment(result.rows) if other else None
+    for (c1, c2), c in sorted(other.items()):
+        both = (code[:, c1] < 4) & (code[:, c2] < 4)
+        each = [int(((code[:, c1] == a) & (code[:, c2] == b)).sum()) for a, b in _CANONICAL]
+        lines.append("%d\t%d\tother\t%s\t%s\t%d\t%d\t%d\n" % (c1 + 1, c2 + 1, _fmt9(cv["best_score"][c]), _fmt9(cv["best_e"][c]), int(both.sum()),
+                                                                sum(each), sum(1 for v in each if v)))
+    return "".join(lines)
+
+
 def pairwise(names, seqs, pairs=None, ctx=None, max_bytes=None, **opts):
     """All pairwise structural alignments of a set of sequences (`dafs --pairwise`).  pairs: (x, y)
     with x < y, default every pair in row-major order.  opts: the options of run() except mp / bp / shard.  Each pair's
@@ -588,6 +646,8 @@ def pairwise(names, seqs, pairs=None, ctx=None, max_bytes=None, **opts):
     for k in ("mp", "bp", "shard"):
         if k in opts:
             raise ValueError("pipeline.pairwise: %s is a single-run option (use run)" % k)
+    if opts.get("covariation"):
+        raise ValueError("pipeline.pairwise: two rows carry no covariation; covariation is an option of run, run_batch and add")
     if opts.get("level_sync") and opts.get("bp_update"):
         raise ValueError("pipeline.pairwise: bp_update needs the resident-node schedule (level_sync=False)")
     o = {k: p.default for k, p in inspect.signature(run).parameters.items() if k not in ("names", "seqs", "ctx", "bp", "mp", "shard")}

@@ -10,6 +10,9 @@ dafs_amd/csrc/host/cli_main.cpp; both produce the same bytes).  One block per al
     #=GC PP_cons     <PP characters of the column reliabilities>
     //
 
+With covariation statistics (Context.alignment_covariation) a `#=GC cov_SS_cons` line follows PP_cons:
+'2' at both columns of every consensus pair whose E-value is at most e_max, '.' elsewhere.
+
 The reliabilities come from Context.alignment_reliability (DESIGN.md "Alignment reliability").  An alignment with new
 sequences added to a seed (pipeline.add, `dafs --seed`) has no tree line, so no CC line, and a `#=GC RF` line after
 PP_cons.
@@ -59,12 +62,25 @@ def row_pp(row, rel):
     return "".join(out)
 
 
-def block(tree_line, row_names, rows, residue_rel, col_rel, ss_str, rf=None):
+def cov_ss_cons(ss, pair_e, e_max=0.05):
+    """The `#=GC cov_SS_cons` characters: '2' at both columns of every pair of ss (left column -> right column, 0xFFFFFFFF
+    otherwise) with pair_e <= e_max (compared in double; a NaN never is), '.' elsewhere"""
+    out = ["."] * len(ss)
+    for c in range(len(ss)):
+        if int(ss[c]) != 0xFFFFFFFF and float(pair_e[c]) <= float(e_max):
+            out[c] = out[int(ss[c])] = "2"
+    return "".join(out)
+
+
+def block(tree_line, row_names, rows, residue_rel, col_rel, ss_str, rf=None, cov=None):
     """One alignment.  row_names / rows / residue_rel: per printed row (stdout order) its Stockholm name, its text and its
     residues' reliabilities; col_rel: per column; a column without residues gets '.' in PP_cons.  tree_line None: no
     `#=GF CC` line.  rf: per column True for a seed column ('x'), False for an insert column ('.'), written as `#=GC RF`
-    after PP_cons; None: no RF line."""
+    after PP_cons; None: no RF line.  cov: the cov_SS_cons characters (cov_ss_cons), written as `#=GC cov_SS_cons` directly after
+    PP_cons; None: no such line, and the labels are as wide as without it."""
     labels = list(row_names) + ["#=GR %s PP" % nm for nm in row_names] + ["#=GC SS_cons", "#=GC PP_cons"]
+    if cov is not None:
+        labels.append("#=GC cov_SS_cons")
     width = max(len(s) for s in labels) + 1
     lines = ["# STOCKHOLM 1.0"]
     if tree_line is not None:
@@ -75,6 +91,8 @@ def block(tree_line, row_names, rows, residue_rel, col_rel, ss_str, rf=None):
     cons = "".join("." if all(r[c] == "-" for r in rows) else pp_char(col_rel[c]) for c in range(len(col_rel)))
     lines.append("#=GC SS_cons".ljust(width) + ss_str)
     lines.append("#=GC PP_cons".ljust(width) + cons)
+    if cov is not None:
+        lines.append("#=GC cov_SS_cons".ljust(width) + cov)
     if rf is not None:
         lines.append("#=GC RF".ljust(width) + "".join("x" if f else "." for f in rf))
     lines.append("//")

@@ -396,6 +396,30 @@ int dafs_hip_alignment_reliability(dafs_hip_ctx* ctx, uint32_t n, uint32_t len, 
                                    const uint32_t* ss, int mp_relaxed, int bp_relaxed, double* res_rel, double* col_rel,
                                    double* pair_rel, uint32_t* pair_rows, double* expected_accuracy);
 
+/* Covariation statistics of an alignment (no counterpart in the reference; definitions, to the bit, in DESIGN.md section 13
+ * "Covariation").  The call reads the alignment and the structure alone, none of the context's stores.
+ *   code[n * len]  row-major, one byte per cell: A 0, C 1, G 2, U/T 3, everything else (gaps, N, IUPAC) 4
+ *   ss             the consensus structure as in dafs_hip_alignment_reliability, or NULL
+ *   shuffles, seed the null: `shuffles` alignments whose columns are each permuted on their own (counter-based generator
+ *                  from `seed`); 0 = no null, every E is NaN
+ * For columns c1 != c2: n_ab = rows with base a at c1 and b at c2; Gq = 2 * sum n_ab * (LNQ[n_ab] + LNQ[m] - LNQ[r_a] -
+ * LNQ[s_b]) with LNQ[k] = floor(log(k) * 65536 + 0.5), an exact int64 (the G statistic in 2^-16 nats); R(c) = sum of Gq(c, .),
+ * T = sum of R; S(c1, c2) = (Gq - R(c1) * R(c2) / T * (len / (len - 1))) / 65536 in double, in that order (average-product
+ * correction); E(s) = number of (shuffle, c1 < c2) with a shuffled S >= s, divided by `shuffles`: the expected number of
+ * column pairs that reach s by chance under a null that ignores phylogeny.  Outputs (host; any may be NULL):
+ *   col_sum[len], total                 R and T
+ *   best[len], best_score[len], best_e[len]   per column the partner with the largest S (the smallest such column), that S, its E
+ *   pair_score[len], pair_e[len], pair_rows[len], pair_canonical[len], pair_types[len]
+ *                                       at the left column of each pair of ss: S, E, m, the rows holding AU UA GC CG GU UG and
+ *                                       how many of those six occur; 0 elsewhere
+ *   g[len * len]                        the whole Gq matrix (small alignments, tests)
+ * DAFS_HIP_EINVAL: n or len 0, a code above 4, a bad ss, n > 2^20 or n * len^2 > 2^45 (T then fits an int64); the context
+ * stays usable.  With n < 2 or len < 2 everything is 0, best is DAFS_HIP_NONE, E is 0 (NaN for shuffles = 0), without a launch. */
+int dafs_hip_alignment_covariation(dafs_hip_ctx* ctx, uint32_t n, uint32_t len, const uint8_t* code, const uint32_t* ss,
+                                   uint32_t shuffles, uint64_t seed, int64_t* col_sum, uint32_t* best, double* best_score,
+                                   double* best_e, double* pair_score, double* pair_e, uint32_t* pair_rows,
+                                   uint32_t* pair_canonical, uint32_t* pair_types, int64_t* total, int64_t* g);
+
 /* ---- device-resident exchange of the sparse stores (multi-GPU runs) ---------------------------------------------------
  * One process per GPU shards phase 1 of DAFS::run (src/dafs.cpp:1787-1827): the folds (src/fold.cpp:66-67), the pair jobs
  * (src/align.cpp:46-50) and the output pairs of relax_matching_probability (src/dafs.cpp:265-315) are independent.  The
