@@ -151,6 +151,24 @@ _solve_nodes = _sig("dafs_hip_solve_nodes", C.c_int,
                     [C.c_void_p, C.c_uint32, C.POINTER(NodeInput), C.POINTER(DDParams), C.POINTER(NodeOutput)])
 _build_tree = _sig("dafs_host_build_tree", C.c_int, [C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])
 _merge_added = _sig("dafs_host_merge_added", C.c_int, [C.c_uint32, C.c_uint32] + [C.c_void_p] * 5)
+# host text (dafs_amd/csrc/host_text.cpp): returned text is a char* the caller frees with dafs_host_free
+_strs = C.POINTER(C.c_char_p)
+_text = C.POINTER(C.c_void_p)
+_host_free = _sig("dafs_host_free", None, [C.c_void_p])
+_pp_char = _sig("dafs_host_pp_char", C.c_char, [C.c_double])
+_stockholm_names = _sig("dafs_host_stockholm_names", C.c_int, [C.c_uint32, _strs, _text])
+_stockholm_block = _sig("dafs_host_stockholm_block", C.c_int, [C.c_char_p, C.c_uint32, C.c_uint32, _strs, _strs, C.POINTER(C.c_void_p), C.c_void_p,
+                                                                C.c_char_p, C.c_void_p, C.c_char_p, _text])
+_cov_code = _sig("dafs_host_cov_code", C.c_uint8, [C.c_char])
+_cov_ss_cons = _sig("dafs_host_cov_ss_cons", C.c_int, [C.c_uint32, C.c_void_p, C.c_void_p, C.c_double, _text])
+_covariation_table = _sig("dafs_host_covariation_table", C.c_int, [C.c_uint32, C.c_uint32] + [C.c_void_p] * 10 + [_text])
+_pairwise_table = _sig("dafs_host_pairwise_table", C.c_int, [C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, _strs] + [C.c_void_p] * 3 + [_text])
+_seed_parse = _sig("dafs_host_seed_parse", C.c_int, [C.c_char_p, C.c_size_t, u32p, _text, _text])
+_seed_clean = _sig("dafs_host_seed_clean", C.c_int, [C.c_uint32, _strs, _strs, _text])
+_family_bytes = _sig("dafs_host_family_bytes", C.c_uint64, [C.c_uint32, C.c_void_p])
+_node_bytes = _sig("dafs_host_node_bytes", C.c_uint64, [C.c_uint32, C.c_uint32])
+_batch_bytes = _sig("dafs_host_batch_bytes", C.c_uint64, [])
+_pack_greedy = _sig("dafs_host_pack_greedy", C.c_int, [C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p])
 _set_mp = _sig("dafs_hip_set_mp", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])
 _nodes_open = _sig("dafs_hip_nodes_open", C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(NodeInput), C.POINTER(DDParams), C.c_void_p])
 _nodes_advance = _sig("dafs_hip_nodes_advance", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(DDParams), C.c_uint32, C.c_void_p])
@@ -216,10 +234,7 @@ def encode(seq):
     return table[np.frombuffer(b, dtype=np.uint8)]
 
 
-_COV_CODE = np.full(256, 4, np.uint8)
-for _k, _chars in enumerate(("Aa", "Cc", "Gg", "UuTt")):
-    for _ch in _chars:
-        _COV_CODE[ord(_ch)] = _k
+_COV_CODE = np.array([_cov_code(bytes([i])) for i in range(256)], np.uint8)
 
 
 def encode_alignment(rows):
@@ -645,6 +660,36 @@ def merge_added(ncols, zs):
     check(_merge_added(ncols, len(zs), lens.ctypes.data, z.ctypes.data, seed_col.ctypes.data, res_col.ctypes.data, C.byref(width)))
     cuts = np.cumsum(lens)[:-1] if len(zs) else []
     return seed_col[:ncols], np.split(res_col[:len(z)], cuts) if len(zs) else [], width.value
+
+
+# ---- host text (dafs_amd/csrc/host_text.cpp, which the command line calls too); stockholm.py and pipeline.py hold the callers ----
+def c_strings(strings):
+    """a list of str (latin-1) or bytes as a char* array for the library (one entry at least)"""
+    bs = [s.encode("latin-1") if isinstance(s, str) else bytes(s) for s in strings]
+    if any(b"\0" in b for b in bs):
+        raise ValueError("a string for the library holds a NUL byte")
+    return (C.c_char_p * max(len(bs), 1))(*bs)
+
+
+def host_text(fn, *args, outs=1, refusal=ValueError):
+    """fn(*args, &text, ...) of a host text function: the returned texts as str (latin-1), freed; a single one as itself.
+    DAFS_HIP_EINVAL raises refusal(the library's message)."""
+    texts = [C.c_void_p() for _ in range(outs)]
+    rc = fn(*args, *[C.byref(t) for t in texts])
+    if rc == -1:
+        raise refusal(_last_error().decode("latin-1"))
+    check(rc)
+    try:
+        got = [C.string_at(t).decode("latin-1") for t in texts]
+    finally:
+        for t in texts:
+            _host_free(t)
+    return got[0] if outs == 1 else got
+
+
+def split_lines(joined, n):
+    """the n strings of a list the library returned joined by newlines"""
+    return joined.split("\n") if n else []
 
 
 def dd_params(**kw):

@@ -13,6 +13,7 @@
 #include "../../include/dafs_hip.h"
 #include "ctx.h"
 #include "hip_util.h"
+#include "last_error.h"
 #include "stage.h"
 
 namespace dafs {
@@ -23,9 +24,10 @@ stage_recorder*& stage_current() {
 }
 
 static thread_local std::string g_last_error;
+void set_last_error(const char* msg) { g_last_error = msg; }
 bool hip_check(hipError_t e) {
   if (e == hipSuccess) return false;
-  g_last_error = hipGetErrorString(e);
+  set_last_error(hipGetErrorString(e));
   return true;
 }
 

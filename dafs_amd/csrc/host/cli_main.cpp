@@ -5,7 +5,9 @@
 // numeric stage executed on the GPU through the C ABI: base-pairing posteriors, all-pairs matching
 // posteriors, similarity, both consistency transforms, and per guide-tree node the averaging +
 // dual-decomposition solve.  The host keeps what is inherently serial and tiny: option parsing,
-// the guide tree, the alignment bookkeeping (project_alignment) and printing.
+// the guide tree, the alignment bookkeeping (project_alignment) and printing.  The guide tree, the Stockholm block, the
+// --covariation and --pairwise-scores tables, the seed reader and the memory estimates are host code of the library
+// (host_tree.cpp, host_text.cpp), shared with the Python driver.
 //
 // Differences from the reference, all forced by what its tree does not contain:
 //   -s Boltzmann / -s Vienna and the RNAalifold term need ViennaRNA arithmetic: not available.
@@ -22,8 +24,6 @@
 #include <unistd.h>
 
 #include <algorithm>
-#include <cctype>
-#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -32,7 +32,6 @@
 #include <iostream>
 #include <map>
 #include <queue>
-#include <set>
 #include <sstream>
 #include <string>
 #include <system_error>
@@ -575,90 +574,40 @@ void save_align_aux(dafs_hip_ctx* ctx, const std::string& file, const std::vecto
 }
 
 // ---------------------------------------------------------------------------------------------
-// --stockholm: every printed alignment as a Stockholm block with posterior-probability lines (dafs_hip_alignment_reliability).
-// dafs_amd/stockholm.py is the Python twin; both write the same bytes.
+// The text formats -- the Stockholm block of --stockholm, the tables of --covariation and --pairwise-scores, the seed reader of
+// --seed -- and the memory estimates of --pairwise are the library's (dafs_amd/csrc/host_text.cpp; the Python driver calls
+// the same functions).  Here: the calls.
 
-// Infernal's PP character: '*' for p >= 0.95, else the digit floor(p * 10 + 0.5), in double
-char pp_char(double p) {
-  if (p >= 0.95) return '*';
-  return (char)('0' + (int)std::floor(p * 10.0 + 0.5));
+std::string take(char* text) {  // a text the library returned: copied and freed
+  std::string s(text);
+  dafs_host_free(text);
+  return s;
 }
 
-// per sequence of a file, in input order: the first whitespace-separated word of its header, "seq<k>" (k 1-based) for an
-// empty one, ".2", ".3", ... appended to the second, third, ... occurrence of a name
-std::vector<std::string> stockholm_names(const std::vector<Fasta>& ff) {
+void check_text(int rc) {  // a refusal of a host text function carries its own message
+  if (rc == DAFS_HIP_EINVAL) throw std::string(dafs_hip_last_error());
+  check(rc);
+}
+
+std::vector<const char*> c_strs(const std::vector<std::string>& v) {
+  std::vector<const char*> p;
+  for (const std::string& s : v) p.push_back(s.c_str());
+  return p;
+}
+
+std::vector<std::string> lines_of(const std::string& joined, size_t n) {  // the n strings of a '\n'-joined list
   std::vector<std::string> out;
-  std::map<std::string, int> seen;
-  for (size_t k = 0; k < ff.size(); ++k) {
-    const std::string& h = ff[k].name();
-    size_t b = 0;
-    while (b < h.size() && std::isspace((unsigned char)h[b])) ++b;
-    size_t e = b;
-    while (e < h.size() && !std::isspace((unsigned char)h[e])) ++e;
-    const std::string nm = e > b ? h.substr(b, e - b) : "seq" + std::to_string(k + 1);
-    const int c = ++seen[nm];
-    out.push_back(c == 1 ? nm : nm + "." + std::to_string(c));
+  for (size_t b = 0; out.size() < n;) {
+    const size_t e = joined.find('\n', b);
+    out.push_back(joined.substr(b, e == std::string::npos ? e : e - b));
+    if (e == std::string::npos) break;
+    b = e + 1;
   }
-  return out;
-}
-
-// rows in stdout order: name, printed text and the reliabilities of its residues; col_rel per column ('.' where a column
-// holds no residue).  Labels padded to the longest plus one.  tree_line nullptr: no "#=GF CC" line; rf: per column a seed
-// column ('x') or an insert column ('.') of --seed, written as "#=GC RF" after PP_cons (nullptr: no RF line).  cov: the
-// characters of "#=GC cov_SS_cons", written directly after PP_cons (nullptr: no such line, labels as wide as without it).
-std::string stockholm_block(const std::string* tree_line, const std::vector<std::string>& names, const std::vector<std::string>& rows,
-                            const std::vector<const double*>& rel, const std::vector<double>& col_rel, const std::string& ss,
-                            const std::vector<bool>* rf = nullptr, const std::string* cov = nullptr) {
-  size_t width = std::max(std::string("#=GC SS_cons").size(), std::string("#=GC PP_cons").size());
-  if (cov) width = std::max(width, std::string("#=GC cov_SS_cons").size());
-  for (const std::string& nm : names) width = std::max(width, nm.size() + 8);  // "#=GR " + name + " PP"
-  ++width;
-  auto label = [&](const std::string& l) { return l + std::string(width - l.size(), ' '); };
-  std::string out = "# STOCKHOLM 1.0\n";
-  if (tree_line) out += "#=GF CC " + *tree_line + "\n";
-  for (size_t r = 0; r < rows.size(); ++r) {
-    out += label(names[r]) + rows[r] + "\n";
-    std::string pp(rows[r].size(), '.');
-    for (size_t c = 0, k = 0; c < rows[r].size(); ++c)
-      if (rows[r][c] != '-') pp[c] = pp_char(rel[r][k++]);
-    out += label("#=GR " + names[r] + " PP") + pp + "\n";
-  }
-  std::string cons(col_rel.size(), '.');
-  for (size_t c = 0; c < col_rel.size(); ++c)
-    for (const std::string& row : rows)
-      if (row[c] != '-') { cons[c] = pp_char(col_rel[c]); break; }
-  out += label("#=GC SS_cons") + ss + "\n" + label("#=GC PP_cons") + cons + "\n";
-  if (cov) out += label("#=GC cov_SS_cons") + *cov + "\n";
-  if (rf) {
-    std::string line(rf->size(), '.');
-    for (size_t c = 0; c < rf->size(); ++c)
-      if ((*rf)[c]) line[c] = 'x';
-    out += label("#=GC RF") + line + "\n";
-  }
-  out += "//\n";
   return out;
 }
 
 // --covariation: the statistics of one printed alignment (dafs_hip_alignment_covariation).
-// pipeline.covariation_tsv and stockholm.cov_ss_cons are the Python twins; both sides write the same bytes.
-const double kCovEMax = 0.05;
-
-std::string fmt9d(double v) {
-  if (std::isnan(v)) return "nan";
-  char buf[64];
-  snprintf(buf, sizeof buf, "%.9g", v);
-  return buf;
-}
-
-uint8_t cov_code(char ch) {
-  switch (ch) {
-    case 'A': case 'a': return 0;
-    case 'C': case 'c': return 1;
-    case 'G': case 'g': return 2;
-    case 'U': case 'u': case 'T': case 't': return 3;
-    default: return 4;
-  }
-}
+const double kCovEMax = 0.05;  // the cut of cov_SS_cons
 
 // rows: the printed rows; ss: the structure.  tsv: the table of this alignment; chars: the cov_SS_cons characters.
 void covariation_of(dafs_hip_ctx* ctx, const Options& o, const std::vector<std::string>& rows, const std::vector<uint32_t>& ss,
@@ -666,40 +615,17 @@ void covariation_of(dafs_hip_ctx* ctx, const Options& o, const std::vector<std::
   const uint32_t n = (uint32_t)rows.size(), L = (uint32_t)ss.size();
   std::vector<uint8_t> code((size_t)n * L);
   for (uint32_t r = 0; r < n; ++r)
-    for (uint32_t c = 0; c < L; ++c) code[(size_t)r * L + c] = cov_code(rows[r][c]);
+    for (uint32_t c = 0; c < L; ++c) code[(size_t)r * L + c] = dafs_host_cov_code(rows[r][c]);
   std::vector<uint32_t> best(L), prow(L), pcan(L), ptyp(L);
   std::vector<double> bscore(L), be(L), pscore(L), pe(L);
   check(dafs_hip_alignment_covariation(ctx, n, L, code.data(), ss.data(), o.cov_shuffles, o.cov_seed, nullptr, best.data(), bscore.data(),
                                        be.data(), pscore.data(), pe.data(), prow.data(), pcan.data(), ptyp.data(), nullptr, nullptr));
-  chars.assign(L, '.');
-  std::ostringstream os;
-  std::set<std::pair<uint32_t, uint32_t> > cons;
-  for (uint32_t c = 0; c < L; ++c) {
-    if (ss[c] == DAFS_HIP_NONE) continue;
-    cons.insert(std::make_pair(c, ss[c]));
-    if (pe[c] <= kCovEMax) chars[c] = chars[ss[c]] = '2';
-    os << c + 1 << "\t" << ss[c] + 1 << "\tss\t" << fmt9d(pscore[c]) << "\t" << fmt9d(pe[c]) << "\t" << prow[c] << "\t" << pcan[c] << "\t" << ptyp[c] << "\n";
-  }
-  std::map<std::pair<uint32_t, uint32_t>, uint32_t> other;  // pair -> the first column that names it
-  for (uint32_t c = 0; c < L; ++c) {
-    if (best[c] == DAFS_HIP_NONE || !(be[c] <= kCovEMax)) continue;
-    const std::pair<uint32_t, uint32_t> pr(std::min(c, best[c]), std::max(c, best[c]));
-    if (!cons.count(pr) && !other.count(pr)) other[pr] = c;
-  }
-  for (const auto& kv : other) {
-    const uint32_t c1 = kv.first.first, c2 = kv.first.second, c = kv.second;
-    uint32_t cnt[4][4] = {{0}};
-    uint32_t both = 0;
-    for (uint32_t r = 0; r < n; ++r) {
-      const uint8_t a = code[(size_t)r * L + c1], b = code[(size_t)r * L + c2];
-      if (a < 4 && b < 4) { ++cnt[a][b]; ++both; }
-    }
-    const uint32_t six[6] = {cnt[0][3], cnt[3][0], cnt[2][1], cnt[1][2], cnt[2][3], cnt[3][2]};  // AU UA GC CG GU UG
-    uint32_t canonical = 0, types = 0;
-    for (uint32_t v : six) { canonical += v; types += v ? 1 : 0; }
-    os << c1 + 1 << "\t" << c2 + 1 << "\tother\t" << fmt9d(bscore[c]) << "\t" << fmt9d(be[c]) << "\t" << both << "\t" << canonical << "\t" << types << "\n";
-  }
-  tsv = os.str();
+  char* text = nullptr;
+  check_text(dafs_host_cov_ss_cons(L, ss.data(), pe.data(), kCovEMax, &text));
+  chars = take(text);
+  check_text(dafs_host_covariation_table(n, L, code.data(), ss.data(), best.data(), bscore.data(), be.data(), pscore.data(), pe.data(),
+                                         prow.data(), pcan.data(), ptyp.data(), &text));
+  tsv = take(text);
 }
 
 void write_covariation(const std::string& file, const std::vector<std::string>& tables, const std::vector<std::string>* headers) {
@@ -722,92 +648,19 @@ void write_stockholm(const std::string& file, const std::vector<std::string>& bl
 }
 
 // ---------------------------------------------------------------------------------------------
-// --seed: the seed alignment.  The twin of stockholm.parse_seed / clean_seed in dafs_amd/stockholm.py:
-// the same files are read and refused, with the same messages.
-const char kSpace[] = " \t\n\v\f\r";  // isspace() in the "C" locale
-
-std::vector<std::string> fields(const std::string& s) {
-  std::vector<std::string> out;
-  size_t b = s.find_first_not_of(kSpace);
-  while (b != std::string::npos) {
-    const size_t e = s.find_first_of(kSpace, b);
-    out.push_back(s.substr(b, e == std::string::npos ? std::string::npos : e - b));
-    b = e == std::string::npos ? e : s.find_first_not_of(kSpace, e);
-  }
-  return out;
-}
-
-// Stockholm when the first line is "# STOCKHOLM 1.0": the first alignment up to "//", interleaved blocks concatenated by
-// name, '#' lines ignored, every other non-blank line "name row".  Otherwise aligned FASTA as this program prints it: lines
-// before the first '>' ignored, leading blanks of a name stripped, a record named SS_cons skipped, rows over several lines.
-void parse_seed(const std::string& file, std::vector<std::string>& names, std::vector<std::string>& rows) {
+// --seed: the seed alignment, read (Stockholm, or aligned FASTA as this program prints it) and checked
+// by the library: names and rows without their all-gap columns, '-' for every gap
+void read_seed(const std::string& file, std::vector<std::string>& names, std::vector<std::string>& rows) {
   std::ifstream is(file.c_str(), std::ios::binary);
   if (!is.is_open()) throw "--seed: cannot open " + file;
-  std::vector<std::string> lines;
-  std::string ln;
-  while (std::getline(is, ln)) {
-    const size_t e = ln.find_last_not_of(kSpace);
-    lines.push_back(e == std::string::npos ? std::string() : ln.substr(0, e + 1));
-  }
-  if (!lines.empty() && lines[0] == "# STOCKHOLM 1.0") {
-    std::map<std::string, size_t> at;
-    for (size_t k = 1; k < lines.size(); ++k) {
-      const std::string& l = lines[k];
-      if (l == "//") break;
-      if (l.empty() || l[0] == '#') continue;  // rstripped: a blank line is empty
-      const std::vector<std::string> f = fields(l);
-      if (f.size() != 2) throw "seed: line " + std::to_string(k + 1) + " is neither a #= annotation nor 'name row'";
-      if (!at.count(f[0])) {
-        at[f[0]] = names.size();
-        names.push_back(f[0]);
-        rows.push_back(std::string());
-      }
-      rows[at[f[0]]] += f[1];
-    }
-    return;
-  }
-  bool keep = false;
-  for (const std::string& l : lines) {
-    if (!l.empty() && l[0] == '>') {
-      const size_t b = l.find_first_not_of(kSpace, 1);
-      const std::string nm = b == std::string::npos ? std::string() : l.substr(b);
-      keep = nm != "SS_cons";
-      if (keep) {
-        names.push_back(nm);
-        rows.push_back(std::string());
-      }
-    } else if (keep) {
-      for (const std::string& f : fields(l)) rows.back() += f;
-    }
-  }
-}
-
-// refuses an empty seed, rows of unequal length, a character that is neither a letter nor a gap ('.', '-') and a row without
-// residues; drops the all-gap columns and writes every gap as '-'
-void clean_seed(const std::vector<std::string>& names, std::vector<std::string>& rows) {
-  if (rows.empty()) throw std::string("seed: no rows");
-  auto gap = [](char ch) { return ch == '.' || ch == '-'; };
-  for (size_t r = 0; r < rows.size(); ++r) {
-    if (rows[r].size() != rows[0].size())
-      throw "seed: rows of unequal length (" + names[0] + ": " + std::to_string(rows[0].size()) + " columns, " + names[r] + ": " +
-          std::to_string(rows[r].size()) + ")";
-    bool residue = false;
-    for (char ch : rows[r]) {
-      if (!gap(ch) && !std::isalpha((unsigned char)ch))
-        throw "seed: row " + names[r] + " holds '" + std::string(1, ch) + "', which is neither a letter nor a gap";
-      residue |= !gap(ch);
-    }
-    if (!residue) throw "seed: row " + names[r] + " has no residues";
-  }
-  std::vector<size_t> keep;  // not empty: every row has a residue
-  for (size_t c = 0; c < rows[0].size(); ++c)
-    for (const std::string& row : rows)
-      if (!gap(row[c])) { keep.push_back(c); break; }
-  for (std::string& row : rows) {
-    std::string out;
-    for (size_t c : keep) out += gap(row[c]) ? '-' : row[c];
-    row.swap(out);
-  }
+  const std::string text((std::istreambuf_iterator<char>(is)), std::istreambuf_iterator<char>());
+  uint32_t n = 0;
+  char *nm = nullptr, *rw = nullptr;
+  check_text(dafs_host_seed_parse(text.data(), text.size(), &n, &nm, &rw));
+  names = lines_of(take(nm), n);
+  rows = lines_of(take(rw), n);
+  check_text(dafs_host_seed_clean(n, c_strs(names).data(), c_strs(rows).data(), &rw));
+  rows = lines_of(take(rw), n);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1051,7 +904,7 @@ dafs_dd_params dd_params_of(const Options& o) {
 // also the family's Stockholm block: tree_line (nullptr: no CC line), rf (nullptr: no RF line).  With cov (--covariation), the
 // alignment's covariation table into *cov, and its cov_SS_cons line into the Stockholm block.
 void finish_alignment(dafs_hip_ctx* ctx, const Options& o, const std::vector<Fasta>& fa, ALN& root, const std::vector<Fasta>& ff,
-                      uint32_t first, std::ostream& os, std::string* sto, const std::string* tree_line, const std::vector<bool>* rf,
+                      uint32_t first, std::ostream& os, std::string* sto, const std::string* tree_line, const std::vector<uint8_t>* rf,
                       std::string* cov = nullptr) {
   std::string str;
   VU ss_final;
@@ -1099,14 +952,20 @@ void finish_alignment(dafs_hip_ctx* ctx, const Options& o, const std::vector<Fas
   std::string cov_chars;
   if (cov) covariation_of(ctx, o, rows, ss_final, *cov, cov_chars);
   if (sto) {
-    const std::vector<std::string> all_names = stockholm_names(ff);
-    std::vector<std::string> names;
+    std::vector<std::string> headers, names;
+    for (const Fasta& s : ff) headers.push_back(s.name());
+    char* text = nullptr;
+    check_text(dafs_host_stockholm_names((uint32_t)headers.size(), c_strs(headers).data(), &text));
+    const std::vector<std::string> all_names = lines_of(take(text), headers.size());
     std::vector<const double*> rr;
     for (const auto& row : root) {
       names.push_back(all_names[row.first - first]);
       rr.push_back(rel.data() + rel_at[row.first]);
     }
-    *sto = stockholm_block(tree_line, names, rows, rr, col_rel, str, rf, cov ? &cov_chars : nullptr);
+    check_text(dafs_host_stockholm_block(tree_line ? tree_line->c_str() : nullptr, (uint32_t)rows.size(), (uint32_t)col_rel.size(),
+                                         c_strs(names).data(), c_strs(rows).data(), rr.data(), col_rel.data(), str.c_str(),
+                                         rf ? rf->data() : nullptr, cov ? cov_chars.c_str() : nullptr, &text));
+    *sto = take(text);
   }
 }
 
@@ -1133,8 +992,7 @@ struct FreshRand {
 // the seed; the structure is decoded over the rows new sequences, then seed rows, as in a run whose tree joins a leaf last.
 int run_add(const Options& o, int align_model) {
   std::vector<std::string> snames, srows;
-  parse_seed(o.seed, snames, srows);
-  clean_seed(snames, srows);
+  read_seed(o.seed, snames, srows);
   std::vector<Fasta> added;
   Fasta::load(added, o.input.c_str());
   if (added.empty()) throw "no sequences in the input";
@@ -1196,8 +1054,8 @@ int run_add(const Options& o, int align_model) {
     for (uint32_t c = 0; c < C; ++c) msk[seed_col[c]] = smask[(size_t)r * C + c] != 0;
     root.push_back(std::make_pair(r, msk));
   }
-  std::vector<bool> rf(width, false);
-  for (uint32_t c = 0; c < C; ++c) rf[seed_col[c]] = true;
+  std::vector<uint8_t> rf(width, 0);
+  for (uint32_t c = 0; c < C; ++c) rf[seed_col[c]] = 1;
   std::string sto, cov;
   finish_alignment(ctx, o, fa, root, fa, 0, std::cout, o.stockholm.empty() ? nullptr : &sto, nullptr, &rf, o.covariation.empty() ? nullptr : &cov);
   std::cout.flush();
@@ -1206,30 +1064,11 @@ int run_add(const Options& o, int align_model) {
   return 0;
 }
 
-// --pairwise: the estimated device memory of one two-sequence family of lengths a, b (pipeline.pair_bytes: its phase-1
-// stores as pipeline.family_bytes counts them, and its root node, resident for the whole chunk), and the budget per chunk
-// (pipeline.DEFAULT_BATCH_BYTES)
-uint64_t pair_bytes(uint64_t a, uint64_t b) {
-  const uint64_t stores = 16 + 8 * (a * a + b * b) + 64 * (a + b) + 2 * 4096 + 8 * (a + b + 2) + 2 * std::min(a, b) * 24 * 32 + 4 * a * b;
-  const uint64_t node = 44 * (a * a + b * b) + 26 * (a + 1) * (b + 1) + 8 * (a + 63) * (b + 64) + 512 * (a + 1) * ((b + 2048) / 2048) + 128 * (a + b) +
-                        (1 << 14);
-  return stores + node;
-}
-const uint64_t kPairChunkBytes = 16ull << 30;
-
-// --pairwise-scores: one line per pair (pipeline.pairwise_scores_tsv writes the same bytes)
-std::string fmt9(float v) {
-  if (std::isnan(v)) return "nan";
-  char buf[64];
-  snprintf(buf, sizeof buf, "%.9g", (double)v);
-  return buf;
-}
-
 // `dafs --pairwise FILE` (pipeline.pairwise is the Python twin).  Phase 1 runs once over FILE's N
 // sequences in a source context, the folding beside the all-pairs posteriors and no transform; the pairs, row-major, go in
-// chunks under kPairChunkBytes through a second context, where dafs_hip_pairs_from gathers a chunk's two-sequence families
-// and align_group runs them as one batch of families.  Each pair prints "==> i j <==" and then what `dafs` prints for a file
-// of its two sequences.
+// chunks under dafs_host_batch_bytes() through a second context, where dafs_hip_pairs_from gathers a chunk's two-sequence
+// families and align_group runs them as one batch of families.  Each pair prints "==> i j <==" and then what `dafs` prints
+// for a file of its two sequences.
 int run_pairwise(const Options& o, int align_model) {
   std::vector<Fasta> fa;
   Fasta::load(fa, o.input.c_str());
@@ -1253,20 +1092,22 @@ int run_pairwise(const Options& o, int align_model) {
   std::vector<std::pair<uint32_t, uint32_t> > pairs;
   for (uint32_t x = 0; x < N; ++x)
     for (uint32_t y = x + 1; y < N; ++y) pairs.push_back(std::make_pair(x, y));
-  std::vector<float> score(pairs.size(), 0.0f);
-  std::vector<uint32_t> iterations(pairs.size(), 0);
+  std::vector<double> score(pairs.size(), 0.0);
+  std::vector<int64_t> iterations(pairs.size(), 0);
   std::vector<std::string> sto_blocks;
   Ranks rk;  // one process
+  // the chunks: greedy in pair order under the estimated device memory of each pair, its phase-1 stores and its root node,
+  // which is resident for the whole chunk; a pair over the budget runs alone
+  std::vector<uint64_t> bytes(pairs.size());
+  for (size_t k = 0; k < pairs.size(); ++k) {
+    const uint32_t l[2] = {(uint32_t)fa[pairs[k].first].size(), (uint32_t)fa[pairs[k].second].size()};
+    bytes[k] = dafs_host_family_bytes(2, l) + dafs_host_node_bytes(l[0], l[1]);
+  }
+  std::vector<uint32_t> chunk_of(pairs.size());
+  check(dafs_host_pack_greedy((uint32_t)pairs.size(), bytes.data(), dafs_host_batch_bytes(), chunk_of.data()));
   for (size_t p0 = 0; p0 < pairs.size();) {
-    // the chunk: greedy in pair order (pipeline.pair_chunks); a pair over the budget runs alone
     size_t p1 = p0;
-    uint64_t used = 0;
-    while (p1 < pairs.size()) {
-      const uint64_t b = pair_bytes(fa[pairs[p1].first].size(), fa[pairs[p1].second].size());
-      if (p1 > p0 && used + b > kPairChunkBytes) break;
-      used += b;
-      ++p1;
-    }
+    while (p1 < pairs.size() && chunk_of[p1] == chunk_of[p0]) ++p1;
     const size_t n = p1 - p0;
     PairChunk pc;
     pc.src = src;
@@ -1302,11 +1143,18 @@ int run_pairwise(const Options& o, int align_model) {
   if (!o.pairwise_scores.empty()) {
     std::ofstream ts(o.pairwise_scores.c_str(), std::ios::binary);
     if (!ts.is_open()) throw "--pairwise-scores: cannot open " + o.pairwise_scores;
-    for (size_t k = 0; k < pairs.size(); ++k) {
-      const uint32_t x = pairs[k].first, y = pairs[k].second;
-      ts << x + 1 << "\t" << y + 1 << "\t" << fa[x].name() << "\t" << fa[y].name() << "\t" << fmt9(sim[(size_t)x * N + y]) << "\t" << fmt9(score[k])
-         << "\t" << iterations[k] << "\n";
+    std::vector<uint32_t> px, py;
+    std::vector<double> psim;
+    std::vector<std::string> names;
+    for (const Fasta& s : fa) names.push_back(s.name());
+    for (const auto& pr : pairs) {
+      px.push_back(pr.first);
+      py.push_back(pr.second);
+      psim.push_back(sim[(size_t)pr.first * N + pr.second]);
     }
+    char* text = nullptr;
+    check_text(dafs_host_pairwise_table(pairs.size(), px.data(), py.data(), N, c_strs(names).data(), psim.data(), score.data(), iterations.data(), &text));
+    ts << take(text);
     ts.flush();
     if (!ts) throw "--pairwise-scores: cannot write " + o.pairwise_scores;
   }

@@ -1,0 +1,401 @@
+// dafs_amd/csrc/host_text.cpp -- the text formats and memory estimates of both drivers as C entry points (include/dafs_hip.h,
+// "host text"): the Stockholm block, the --covariation and --pairwise-scores tables, the seed reader of --seed, the estimates
+// and the greedy chunking.  The C++ command line calls them directly and the Python driver through capi.py, so every byte and
+// every formula is defined here once.  Host logic only: nothing here includes HIP or touches a device.
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <map>
+#include <new>
+#include <set>
+#include <sstream>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "../../include/dafs_hip.h"
+#include "last_error.h"
+
+namespace {
+
+char* copy_text(const std::string& s) {
+  char* p = (char*)malloc(s.size() + 1);
+  if (!p) throw std::bad_alloc();
+  memcpy(p, s.c_str(), s.size() + 1);
+  return p;
+}
+
+// the entry points' frame: the text of body() into *out; a std::string thrown by body() is a refusal
+template <class F>
+int text_out(char** out, F body) {
+  if (!out) return DAFS_HIP_EINVAL;
+  *out = nullptr;
+  try {
+    *out = copy_text(body());
+    return DAFS_HIP_OK;
+  } catch (const std::string& refusal) {
+    dafs::set_last_error(refusal.c_str());
+    return DAFS_HIP_EINVAL;
+  } catch (const std::bad_alloc&) {
+    return DAFS_HIP_ENOMEM;
+  }
+}
+
+const std::string kBadArgument = "host text: invalid argument";
+
+std::vector<std::string> strings(uint32_t n, const char* const* s) {
+  std::vector<std::string> out(n);
+  for (uint32_t k = 0; k < n; ++k) {
+    if (!s || !s[k]) throw kBadArgument;
+    out[k] = s[k];
+  }
+  return out;
+}
+
+std::string joined(const std::vector<std::string>& v) {
+  std::string out;
+  for (size_t k = 0; k < v.size(); ++k) out += (k ? "\n" : "") + v[k];
+  return out;
+}
+
+// isspace() and isalpha() as the "C" locale has them, whatever locale the host process has set
+const char kSpace[] = " \t\n\v\f\r";
+bool is_space(char ch) { return memchr(kSpace, ch, sizeof kSpace - 1) != nullptr; }
+bool is_alpha(char ch) { return (ch >= 'A' && ch <= 'Z') || (ch >= 'a' && ch <= 'z'); }
+
+// Infernal's PP character: '*' for p >= 0.95, else the digit floor(p * 10 + 0.5), in double
+char pp_char(double p) {
+  if (p >= 0.95) return '*';
+  return (char)('0' + (int)std::floor(p * 10.0 + 0.5));
+}
+
+// rows in stdout order: name, printed text and the reliabilities of its residues; col_rel per column ('.' where a column
+// holds no residue).  Labels padded to the longest plus one.  tree_line nullptr: no "#=GF CC" line; rf: per column a seed
+// column ('x') or an insert column ('.') of --seed, written as "#=GC RF" after PP_cons (nullptr: no RF line).  cov: the
+// characters of "#=GC cov_SS_cons", written directly after PP_cons (nullptr: no such line, labels as wide as without it).
+std::string stockholm_block(const char* tree_line, const std::vector<std::string>& names, const std::vector<std::string>& rows,
+                            const double* const* rel, const double* col_rel, uint32_t len, const std::string& ss, const uint8_t* rf,
+                            const char* cov) {
+  size_t width = std::max(std::string("#=GC SS_cons").size(), std::string("#=GC PP_cons").size());
+  if (cov) width = std::max(width, std::string("#=GC cov_SS_cons").size());
+  for (const std::string& nm : names) width = std::max(width, nm.size() + 8);  // "#=GR " + name + " PP"
+  ++width;
+  auto label = [&](const std::string& l) { return l + std::string(width - l.size(), ' '); };
+  std::string out = "# STOCKHOLM 1.0\n";
+  if (tree_line) out += "#=GF CC " + std::string(tree_line) + "\n";
+  for (size_t r = 0; r < rows.size(); ++r) {
+    out += label(names[r]) + rows[r] + "\n";
+    std::string pp(rows[r].size(), '.');
+    for (size_t c = 0, k = 0; c < rows[r].size(); ++c)
+      if (rows[r][c] != '-') pp[c] = pp_char(rel[r][k++]);
+    out += label("#=GR " + names[r] + " PP") + pp + "\n";
+  }
+  std::string cons(len, '.');
+  for (size_t c = 0; c < len; ++c)
+    for (const std::string& row : rows)
+      if (row[c] != '-') { cons[c] = pp_char(col_rel[c]); break; }
+  out += label("#=GC SS_cons") + ss + "\n" + label("#=GC PP_cons") + cons + "\n";
+  if (cov) out += label("#=GC cov_SS_cons") + std::string(cov) + "\n";
+  if (rf) {
+    std::string line(len, '.');
+    for (size_t c = 0; c < len; ++c)
+      if (rf[c]) line[c] = 'x';
+    out += label("#=GC RF") + line + "\n";
+  }
+  out += "//\n";
+  return out;
+}
+
+// --covariation
+const double kCovEMax = 0.05;  // the cut of the table's `other` pairs: fixed (e_max moves cov_SS_cons only)
+
+std::string fmt9d(double v) {
+  if (std::isnan(v)) return "nan";
+  char buf[64];
+  snprintf(buf, sizeof buf, "%.9g", v);
+  return buf;
+}
+
+// --seed: the seed alignment
+std::vector<std::string> fields(const std::string& s) {
+  std::vector<std::string> out;
+  size_t b = s.find_first_not_of(kSpace);
+  while (b != std::string::npos) {
+    const size_t e = s.find_first_of(kSpace, b);
+    out.push_back(s.substr(b, e == std::string::npos ? std::string::npos : e - b));
+    b = e == std::string::npos ? e : s.find_first_not_of(kSpace, e);
+  }
+  return out;
+}
+
+// Stockholm when the first line is "# STOCKHOLM 1.0": the first alignment up to "//", interleaved blocks concatenated by
+// name, '#' lines ignored, every other non-blank line "name row".  Otherwise aligned FASTA as `dafs` prints it: lines
+// before the first '>' ignored, leading blanks of a name stripped, a record named SS_cons skipped, rows over several lines.
+void parse_seed(const std::string& text, std::vector<std::string>& names, std::vector<std::string>& rows) {
+  if (text.find('\0') != std::string::npos) throw std::string("seed: the file holds a NUL byte");  // names and rows are C strings
+  std::istringstream is(text);
+  std::vector<std::string> lines;
+  std::string ln;
+  while (std::getline(is, ln)) {
+    const size_t e = ln.find_last_not_of(kSpace);
+    lines.push_back(e == std::string::npos ? std::string() : ln.substr(0, e + 1));
+  }
+  if (!lines.empty() && lines[0] == "# STOCKHOLM 1.0") {
+    std::map<std::string, size_t> at;
+    for (size_t k = 1; k < lines.size(); ++k) {
+      const std::string& l = lines[k];
+      if (l == "//") break;
+      if (l.empty() || l[0] == '#') continue;  // rstripped: a blank line is empty
+      const std::vector<std::string> f = fields(l);
+      if (f.size() != 2) throw "seed: line " + std::to_string(k + 1) + " is neither a #= annotation nor 'name row'";
+      if (!at.count(f[0])) {
+        at[f[0]] = names.size();
+        names.push_back(f[0]);
+        rows.push_back(std::string());
+      }
+      rows[at[f[0]]] += f[1];
+    }
+    return;
+  }
+  bool keep = false;
+  for (const std::string& l : lines) {
+    if (!l.empty() && l[0] == '>') {
+      const size_t b = l.find_first_not_of(kSpace, 1);
+      const std::string nm = b == std::string::npos ? std::string() : l.substr(b);
+      keep = nm != "SS_cons";
+      if (keep) {
+        names.push_back(nm);
+        rows.push_back(std::string());
+      }
+    } else if (keep) {
+      for (const std::string& f : fields(l)) rows.back() += f;
+    }
+  }
+}
+
+// refuses an empty seed, rows of unequal length, a character that is neither a letter nor a gap ('.', '-') and a row without
+// residues; drops the all-gap columns and writes every gap as '-'
+void clean_seed(const std::vector<std::string>& names, std::vector<std::string>& rows) {
+  if (rows.empty()) throw std::string("seed: no rows");
+  auto gap = [](char ch) { return ch == '.' || ch == '-'; };
+  for (size_t r = 0; r < rows.size(); ++r) {
+    if (rows[r].size() != rows[0].size())
+      throw "seed: rows of unequal length (" + names[0] + ": " + std::to_string(rows[0].size()) + " columns, " + names[r] + ": " +
+          std::to_string(rows[r].size()) + ")";
+    bool residue = false;
+    for (char ch : rows[r]) {
+      if (!gap(ch) && !is_alpha(ch))
+        throw "seed: row " + names[r] + " holds '" + std::string(1, ch) + "', which is neither a letter nor a gap";
+      residue |= !gap(ch);
+    }
+    if (!residue) throw "seed: row " + names[r] + " has no residues";
+  }
+  std::vector<size_t> keep;  // not empty: every row has a residue
+  for (size_t c = 0; c < rows[0].size(); ++c)
+    for (const std::string& row : rows)
+      if (!gap(row[c])) { keep.push_back(c); break; }
+  for (std::string& row : rows) {
+    std::string out;
+    for (size_t c : keep) out += gap(row[c]) ? '-' : row[c];
+    row.swap(out);
+  }
+}
+
+}  // namespace
+
+extern "C" void dafs_host_free(void* p) { free(p); }
+
+extern "C" char dafs_host_pp_char(double p) { return pp_char(p); }
+
+// per sequence of a file, in input order: the first whitespace-separated word of its header, "seq<k>" (k 1-based) for an
+// empty one, ".2", ".3", ... appended to the second, third, ... occurrence of a name
+extern "C" int dafs_host_stockholm_names(uint32_t n, const char* const* header_strs, char** names) {
+  return text_out(names, [&]() {
+    const std::vector<std::string> headers = strings(n, header_strs);
+    std::vector<std::string> out;
+    std::map<std::string, int> seen;
+    for (size_t k = 0; k < headers.size(); ++k) {
+      const std::string& h = headers[k];
+      size_t b = 0;
+      while (b < h.size() && is_space(h[b])) ++b;
+      size_t e = b;
+      while (e < h.size() && !is_space(h[e])) ++e;
+      const std::string nm = e > b ? h.substr(b, e - b) : "seq" + std::to_string(k + 1);
+      const int c = ++seen[nm];
+      out.push_back(c == 1 ? nm : nm + "." + std::to_string(c));
+    }
+    return joined(out);
+  });
+}
+
+extern "C" int dafs_host_stockholm_block(const char* tree_line, uint32_t n, uint32_t len, const char* const* names, const char* const* rows,
+                                         const double* const* residue_rel, const double* col_rel, const char* ss, const uint8_t* rf,
+                                         const char* cov, char** block) {
+  return text_out(block, [&]() {
+    const std::vector<std::string> nm = strings(n, names), rw = strings(n, rows);
+    if (!ss || (len && !col_rel) || (n && !residue_rel)) throw kBadArgument;
+    for (uint32_t r = 0; r < n; ++r) {
+      if (rw[r].size() != len) throw "stockholm block: row " + nm[r] + " has " + std::to_string(rw[r].size()) + " columns, not " + std::to_string(len);
+      if (!residue_rel[r] && rw[r] != std::string(len, '-')) throw kBadArgument;
+    }
+    return stockholm_block(tree_line, nm, rw, residue_rel, col_rel, len, ss, rf, cov);
+  });
+}
+
+extern "C" uint8_t dafs_host_cov_code(char ch) {
+  switch (ch) {
+    case 'A': case 'a': return 0;
+    case 'C': case 'c': return 1;
+    case 'G': case 'g': return 2;
+    case 'U': case 'u': case 'T': case 't': return 3;
+    default: return 4;
+  }
+}
+
+extern "C" int dafs_host_cov_ss_cons(uint32_t len, const uint32_t* ss, const double* pair_e, double e_max, char** chars) {
+  return text_out(chars, [&]() {
+    if (len && (!ss || !pair_e)) throw kBadArgument;
+    std::string out(len, '.');
+    for (uint32_t c = 0; c < len; ++c) {
+      if (ss[c] == DAFS_HIP_NONE) continue;
+      if (ss[c] >= len) throw std::string("cov_SS_cons: a pair's right column is outside the alignment");
+      if (pair_e[c] <= e_max) out[c] = out[ss[c]] = '2';
+    }
+    return out;
+  });
+}
+
+extern "C" int dafs_host_covariation_table(uint32_t n, uint32_t L, const uint8_t* code, const uint32_t* ss, const uint32_t* best,
+                                           const double* bscore, const double* be, const double* pscore, const double* pe,
+                                           const uint32_t* prow, const uint32_t* pcan, const uint32_t* ptyp, char** table) {
+  return text_out(table, [&]() {
+    if (L && (!ss || !best || !bscore || !be || !pscore || !pe || !prow || !pcan || !ptyp || (n && !code))) throw kBadArgument;
+    for (uint32_t c = 0; c < L; ++c)
+      if ((ss[c] != DAFS_HIP_NONE && ss[c] >= L) || (best[c] != DAFS_HIP_NONE && best[c] >= L))
+        throw std::string("covariation table: a partner column is outside the alignment");
+    std::ostringstream os;
+    std::set<std::pair<uint32_t, uint32_t> > cons;
+    for (uint32_t c = 0; c < L; ++c) {
+      if (ss[c] == DAFS_HIP_NONE) continue;
+      cons.insert(std::make_pair(c, ss[c]));
+      os << c + 1 << "\t" << ss[c] + 1 << "\tss\t" << fmt9d(pscore[c]) << "\t" << fmt9d(pe[c]) << "\t" << prow[c] << "\t" << pcan[c] << "\t" << ptyp[c] << "\n";
+    }
+    std::map<std::pair<uint32_t, uint32_t>, uint32_t> other;  // pair -> the first column that names it
+    for (uint32_t c = 0; c < L; ++c) {
+      if (best[c] == DAFS_HIP_NONE || !(be[c] <= kCovEMax)) continue;
+      const std::pair<uint32_t, uint32_t> pr(std::min(c, best[c]), std::max(c, best[c]));
+      if (!cons.count(pr) && !other.count(pr)) other[pr] = c;
+    }
+    for (const auto& kv : other) {
+      const uint32_t c1 = kv.first.first, c2 = kv.first.second, c = kv.second;
+      uint32_t cnt[4][4] = {{0}};
+      uint32_t both = 0;
+      for (uint32_t r = 0; r < n; ++r) {
+        const uint8_t a = code[(size_t)r * L + c1], b = code[(size_t)r * L + c2];
+        if (a < 4 && b < 4) { ++cnt[a][b]; ++both; }
+      }
+      const uint32_t six[6] = {cnt[0][3], cnt[3][0], cnt[2][1], cnt[1][2], cnt[2][3], cnt[3][2]};  // AU UA GC CG GU UG
+      uint32_t canonical = 0, types = 0;
+      for (uint32_t v : six) { canonical += v; types += v ? 1 : 0; }
+      os << c1 + 1 << "\t" << c2 + 1 << "\tother\t" << fmt9d(bscore[c]) << "\t" << fmt9d(be[c]) << "\t" << both << "\t" << canonical << "\t" << types << "\n";
+    }
+    return os.str();
+  });
+}
+
+// --pairwise-scores: one line per pair
+extern "C" int dafs_host_pairwise_table(uint64_t npairs, const uint32_t* x, const uint32_t* y, uint32_t nnames, const char* const* names,
+                                        const double* sim, const double* score, const int64_t* iterations, char** table) {
+  return text_out(table, [&]() {
+    const std::vector<std::string> nm = strings(nnames, names);
+    if (npairs && (!x || !y || !sim || !score || !iterations)) throw kBadArgument;
+    std::ostringstream ts;
+    for (uint64_t k = 0; k < npairs; ++k) {
+      if (x[k] >= nnames || y[k] >= nnames) throw std::string("pairwise table: a pair names a sequence that is not there");
+      ts << x[k] + 1 << "\t" << y[k] + 1 << "\t" << nm[x[k]] << "\t" << nm[y[k]] << "\t" << fmt9d(sim[k]) << "\t" << fmt9d(score[k]) << "\t"
+         << iterations[k] << "\n";
+    }
+    return ts.str();
+  });
+}
+
+extern "C" int dafs_host_seed_parse(const char* text, size_t bytes, uint32_t* n, char** names, char** rows) {
+  if (rows) *rows = nullptr;
+  const int rc = text_out(names, [&]() {
+    if (!n || !rows || (bytes && !text)) throw kBadArgument;
+    std::vector<std::string> nm, rw;
+    parse_seed(std::string(bytes ? text : "", bytes), nm, rw);
+    const std::string names_text = joined(nm);
+    *rows = copy_text(joined(rw));
+    *n = (uint32_t)nm.size();
+    return names_text;
+  });
+  if (rc != DAFS_HIP_OK && rows) {  // the names' copy failed after the rows'
+    free(*rows);
+    *rows = nullptr;
+  }
+  return rc;
+}
+
+extern "C" int dafs_host_seed_clean(uint32_t n, const char* const* names, const char* const* rows, char** cleaned) {
+  return text_out(cleaned, [&]() {
+    const std::vector<std::string> nm = strings(n, names);
+    std::vector<std::string> rw = strings(n, rows);
+    clean_seed(nm, rw);
+    return joined(rw);
+  });
+}
+
+// ---------------------------------------------------------------------------------------------
+// Device memory one family takes in phase 1, estimated from the stores' sizes (bytes): per pair its row pointers in both
+// matching stores, its entries (as the pair kernels reserve them: 24 per shorter-sequence column and direction, col + val,
+// the relaxed copy and the interleaved copy of the transforms) and its dense consistency tile; per sequence its base-pairing
+// tile and rows; the similarity block.  Not counted: the folding kernels' workspaces and the resident nodes of the
+// progressive phase, which hold only the open nodes (tools/time_batch.py reports their measured peak).
+extern "C" uint64_t dafs_host_family_bytes(uint32_t n, const uint32_t* lens) {
+  if (n && !lens) return 0;
+  uint64_t b = 4 * (uint64_t)n * n;
+  for (uint32_t x = 0; x < n; ++x) {
+    const uint64_t lx = lens[x];
+    b += 8 * lx * lx + 64 * lx + 4096;
+    for (uint32_t y = x + 1; y < n; ++y) {
+      const uint64_t ly = lens[y];
+      b += 8 * (lx + ly + 2) + 2 * std::min(lx, ly) * 24 * 32 + 4 * lx * ly;
+    }
+  }
+  return b;
+}
+
+// Device memory of one resident node of l1 x l2 columns (bytes), the bound capi_dd.cpp's nodes_open keeps, folding arrays
+// included: per cell of the two base-pairing matrices 19 + 25 bytes, per cell of the alignment tables 26 bytes plus the
+// padded sweep-order copies, traceback slots, row arrays and slack.
+extern "C" uint64_t dafs_host_node_bytes(uint32_t len1, uint32_t len2) {
+  const uint64_t l1 = len1, l2 = len2;
+  return 44 * (l1 * l1 + l2 * l2) + 26 * (l1 + 1) * (l2 + 1) + 8 * (l1 + 63) * (l2 + 64) + 512 * (l1 + 1) * ((l2 + 2048) / 2048) + 128 * (l1 + l2) +
+         (1 << 14);
+}
+
+// per sub-batch or chunk, against the 288 GB of an MI355X.  A choice, not a measured limit.  Measured on 512 families of
+// 5-15 sequences of 80-200 nt (profiles/r04_a_time_batch.json): phase-1 estimate 8.6 GB (one sub-batch), peak of the
+// progressive phase's resident nodes 6.0 GB, which dafs_host_family_bytes does not count.
+extern "C" uint64_t dafs_host_batch_bytes(void) { return 16ull << 30; }
+
+// greedy, in input order: a group is closed before the item that would take it over max_bytes; an item over the budget
+// is a group of its own
+extern "C" int dafs_host_pack_greedy(uint32_t n, const uint64_t* sizes, uint64_t max_bytes, uint32_t* group_of) {
+  if (n && (!sizes || !group_of)) return DAFS_HIP_EINVAL;
+  uint32_t group = 0;
+  uint64_t used = 0;
+  for (uint32_t k = 0; k < n; ++k) {
+    if (k && (used > max_bytes || sizes[k] > max_bytes - used)) {  // used + sizes[k] > max_bytes, without the overflow
+      ++group;
+      used = 0;
+    }
+    group_of[k] = group;
+    used += sizes[k];
+  }
+  return DAFS_HIP_OK;
+}

@@ -1,9 +1,9 @@
 """Host-side driver of the whole DAFS run on top of the C ABI -- the Python mirror of
 DAFS::run (reference src/dafs.cpp:1781-1889) used by tests and bench.py.  Everything numeric is
-done by libdafs_hip.so on the GPU; this file only holds the guide tree, the alignment bookkeeping
-(project_alignment) and the output format.  The C++ `dafs` executable (dafs_amd/csrc/cli_main.cpp)
-is the same logic for the drop-in command line."""
-import heapq
+done by libdafs_hip.so on the GPU; this file only holds the schedule, the alignment bookkeeping
+(project_alignment) and the FASTA-style output.  The C++ `dafs` executable (dafs_amd/csrc/host/cli_main.cpp)
+is the same logic for the drop-in command line; the guide tree, the Stockholm block, the tables and the memory estimates
+of both are the library's host code (dafs_amd/csrc/host_tree.cpp, host_text.cpp)."""
 import inspect
 import os
 import sys
@@ -13,42 +13,6 @@ import numpy as np
 from . import capi, stockholm
 
 NONE = 0xFFFFFFFF
-
-
-def build_tree(sim):
-    """DAFS::build_tree, src/dafs.cpp:446-492.  Returns (score[2n-1], left, right) with -1 for leaves."""
-    n = sim.shape[0]
-    T = 2 * n - 1
-    score = np.zeros(T, np.float32)
-    left = -np.ones(T, np.int64)
-    right = -np.ones(T, np.int64)
-    d = np.zeros((n, n), np.float32)
-    idx = [-1] * T
-    for i in range(n):
-        idx[i] = i
-    pq = []
-    for i in range(n - 1):
-        for j in range(i + 1, n):
-            d[i, j] = d[j, i] = sim[i, j]
-            heapq.heappush(pq, (-float(sim[i, j]), -i, -j))  # max-heap on (sim, (i, j))
-    cur = n
-    while pq:
-        s, a, b = heapq.heappop(pq)
-        s, a, b = np.float32(-s), -a, -b
-        if idx[a] != -1 and idx[b] != -1:
-            l, r = idx[a], idx[b]
-            idx[a] = idx[b] = -1
-            for i in range(cur):
-                if idx[i] != -1:
-                    ii = idx[i]
-                    v = np.float32(np.float32(d[ii, l] + d[ii, r]) * s) / np.float32(2)
-                    d[ii, l] = d[l, ii] = v
-                    heapq.heappush(pq, (-float(v), -i, -cur))
-            score[cur] = s
-            left[cur], right[cur] = a, b
-            idx[cur] = l
-            cur += 1
-    return score, left, right
 
 
 def tree_string(score, left, right, names, i=None):
@@ -117,7 +81,7 @@ def run(names, seqs, ctx=None, bp=None, w=4.0, eta0=0.5, t_max=600, w_pct_a=0.25
         sim = ctx.sim()
     else:
         sim = _phase1_local(ctx, seqs, bp, mp, align_model, th_a, w_pct_a, w_pct_s, t, w_pct_f)
-    score, left, right = capi.build_tree(sim)  # same code as the command line (build_tree below is its Python twin, kept for the CPU tests)
+    score, left, right = capi.build_tree(sim)  # same code as the command line
     t.append(time.perf_counter())
     fam = dict(names=names, seqs=seqs, first=0, sim=sim, tree=(score, left, right))
     return _phase2_forest(ctx, own, [fam], t, w, eta0, t_max, th_a, th_s, th_s1, force_iters, level_sync, slice_iters,
@@ -226,7 +190,7 @@ def _phase2_forest(ctx, own, fams, t, w, eta0, t_max, th_a, th_s, th_s1, force_i
     reliability: each Result also gets .reliability, the annotation of its final alignment and structure from the stores
     the progressive phase read (Context.alignment_reliability): a dict with residue (per printed row, its residues'
     values), col, pair, pair_rows and expected_accuracy; and .stockholm, that alignment as a Stockholm block with PP lines
-    (dafs_amd/stockholm.py, the same bytes `dafs --stockholm` writes).  covariation: see _final."""
+    (dafs_amd/stockholm.py: the block `dafs --stockholm` writes).  covariation: see _final."""
     import time
     covariation = cov_options(covariation)
     nf = len(fams)
@@ -440,40 +404,28 @@ def add(seed_names, seed_rows, names, seqs, ctx=None, w=4.0, eta0=0.5, t_max=600
 
 
 def family_bytes(lens):
-    """Device memory one family takes in phase 1, estimated from the stores' sizes (bytes): per pair its row pointers in
-    both matching stores, its entries (as the pair kernels reserve them: 24 per shorter-sequence column and direction, col
-    + val, the relaxed copy and the interleaved copy of the transforms) and its dense consistency tile; per sequence its
-    base-pairing tile and rows; the similarity block.  Not counted: the folding kernels' workspaces and the resident
-    nodes of the progressive phase, which hold only the open nodes (tools/time_batch.py reports their measured peak)."""
-    lens = [int(x) for x in lens]
-    n = len(lens)
-    b = 4 * n * n
-    for x in range(n):
-        b += 8 * lens[x] * lens[x] + 64 * lens[x] + 4096
-        for y in range(x + 1, n):
-            b += 8 * (lens[x] + lens[y] + 2) + 2 * min(lens[x], lens[y]) * 24 * 32 + 4 * lens[x] * lens[y]
-    return b
+    """Device memory one family takes in phase 1, estimated from the stores' sizes (bytes; dafs_host_family_bytes states what
+    is counted).  Not counted: the folding kernels' workspaces and the resident nodes of the progressive phase, which hold
+    only the open nodes (tools/time_batch.py reports their measured peak)."""
+    lens = np.ascontiguousarray([int(x) for x in lens], np.uint32)
+    return int(capi._family_bytes(len(lens), lens.ctypes.data))
 
 
 def pack_families(sizes, max_bytes):
-    """Sub-batches of the families (greedy, in input order) whose estimated sizes add up to at most max_bytes each; a
-    family over the budget runs alone.  Returns lists of family indices."""
-    out, cur, used = [], [], 0
-    for k, b in enumerate(sizes):
-        if cur and used + b > max_bytes:
-            out.append(cur)
-            cur, used = [], 0
-        cur.append(k)
-        used += b
-    if cur:
-        out.append(cur)
+    """Sub-batches of the families (greedy, in input order; dafs_host_pack_greedy) whose estimated sizes add up to at most
+    max_bytes each; a family over the budget runs alone.  Returns lists of family indices."""
+    sizes = np.ascontiguousarray([int(b) for b in sizes], np.uint64)
+    group = np.zeros(max(len(sizes), 1), np.uint32)
+    capi.check(capi._pack_greedy(len(sizes), sizes.ctypes.data, int(max_bytes), group.ctypes.data))
+    out = []
+    for k in range(len(sizes)):
+        if group[k] == len(out):
+            out.append([])
+        out[-1].append(k)
     return out
 
 
-# per sub-batch, against the 288 GB of an MI355X.  A choice, not a measured limit.  Measured on 512 families of 5-15
-# sequences of 80-200 nt (profiles/r04_a_time_batch.json): phase-1 estimate 8.6 GB (one sub-batch), peak of the
-# progressive phase's resident nodes 6.0 GB, which family_bytes does not count.
-DEFAULT_BATCH_BYTES = 16 << 30
+DEFAULT_BATCH_BYTES = int(capi._batch_bytes())  # per sub-batch or chunk: the library's choice (dafs_host_batch_bytes)
 
 
 def run_batch(families, ctx=None, max_bytes=None, **kw):
@@ -530,12 +482,9 @@ def run_batch(families, ctx=None, max_bytes=None, **kw):
 
 # ------------------------------------------------------------------------------------------------ all-against-all pairs
 def node_bytes(l1, l2):
-    """Device memory of one resident node of l1 x l2 columns (bytes), the bound test_configs_gpu._node_bytes_bound states
-    from capi_dd.cpp's nodes_open, folding arrays included: per cell of the two base-pairing matrices 19 + 25 bytes, per cell
-    of the alignment tables 26 bytes plus the padded sweep-order copies, traceback slots, row arrays and slack."""
-    l1, l2 = int(l1), int(l2)
-    return (44 * (l1 * l1 + l2 * l2) + 26 * (l1 + 1) * (l2 + 1) + 8 * (l1 + 63) * (l2 + 64) + 512 * (l1 + 1) * ((l2 + 2048) // 2048)
-            + 128 * (l1 + l2) + (1 << 14))
+    """Device memory of one resident node of l1 x l2 columns (bytes; dafs_host_node_bytes), the bound
+    test_configs_gpu._node_bytes_bound states from capi_dd.cpp's nodes_open, folding arrays included."""
+    return int(capi._node_bytes(int(l1), int(l2)))
 
 
 def pair_bytes(l1, l2):
@@ -576,56 +525,38 @@ def pair_chunks(lens, pairs, max_bytes):
     return pack_families([pair_bytes(lens[x], lens[y]) for x, y in pairs], max_bytes)
 
 
-def _fmt9(v):
-    """%.9g as C's printf writes it for the table (a NaN of either sign as "nan")"""
-    v = float(v)
-    return "nan" if v != v else "%.9g" % v
-
-
 def pairwise_scores_tsv(names, pairs, sim, score, iterations):
-    """The table of `dafs --pairwise FILE --pairwise-scores OUT` (the C++ writer in cli_main.cpp writes the same bytes): per
-    pair, in pair order, "i<TAB>j<TAB>name_i<TAB>name_j<TAB>sim<TAB>score<TAB>iterations" with 1-based i, j and the floats
-    as %.9g."""
-    return "".join("%d\t%d\t%s\t%s\t%s\t%s\t%d\n" % (x + 1, y + 1, names[x], names[y], _fmt9(sim[x, y]), _fmt9(score[x, y]),
-                                                     int(iterations[x, y])) for x, y in pairs)
+    """The table of `dafs --pairwise FILE --pairwise-scores OUT` (dafs_host_pairwise_table): per pair, in pair order,
+    "i<TAB>j<TAB>name_i<TAB>name_j<TAB>sim<TAB>score<TAB>iterations" with 1-based i, j and the floats as %.9g.  sim, score,
+    iterations: N x N, as pipeline.pairwise returns them."""
+    names = list(names)
+    xy = np.ascontiguousarray(np.array([(int(x), int(y)) for x, y in pairs], np.uint32).reshape(-1, 2).T)
+    per_pair = [np.ascontiguousarray(np.asarray(a)[xy[0], xy[1]], t) for a, t in ((sim, np.float64), (score, np.float64), (iterations, np.int64))]
+    return capi.host_text(capi._pairwise_table, xy.shape[1], xy[0].ctypes.data, xy[1].ctypes.data, len(names), capi.c_strings(names),
+                          *[a.ctypes.data for a in per_pair])
 
 
 class Pairwise:
     pass
 
 
-COV_TABLE_E_MAX = 0.05  # the cut of the table's `other` pairs: fixed, as on the command line (e_max moves cov_SS_cons only)
-_CANONICAL = ((0, 3), (3, 0), (2, 1), (1, 2), (2, 3), (3, 2))  # AU UA GC CG GU UG
+COV_TABLE_E_MAX = 0.05  # the cut of the table's `other` pairs: fixed in the library, as on the command line (e_max moves cov_SS_cons only)
 
 
 def covariation_tsv(result):
-    """The table of `dafs --covariation OUT` for one result with .covariation (the C++ writer in cli_main.cpp writes the same
-    bytes): one line "c1<TAB>c2<TAB>kind<TAB>S<TAB>E<TAB>rows<TAB>canonical<TAB>types" per pair, columns 1-based, floats as
-    %.9g.  First every consensus pair by ascending left column (kind ss); then every distinct pair {c, best(c)} that is no
-    consensus pair and has E <= 0.05 (COV_TABLE_E_MAX, whatever the result's e_max), ordered by (c1, c2) (kind other), its
-    counts taken from the rows."""
-    cv, ss = result.covariation, result.ss
-    lines, cons = [], set()
-    for c in range(len(ss)):
-        if int(ss[c]) != NONE:
-            cons.add((c, int(ss[c])))
-            lines.append("%d\t%d\tss\t%s\t%s\t%d\t%d\t%d\n" % (c + 1, int(ss[c]) + 1, _fmt9(cv["pair_score"][c]), _fmt9(cv["pair_e"][c]),
-                                                                 int(cv["pair_rows"][c]), int(cv["pair_canonical"][c]), int(cv["pair_types"][c])))
-    other = {}
-    for c in range(len(ss)):
-        b = int(cv["best"][c])
-        if b == NONE or not float(cv["best_e"][c]) <= COV_TABLE_E_MAX:
-            continue
-        pr = (min(c, b), max(c, b))
-        if pr not in cons and pr not in other:
-            other[pr] = c
-    code = capi.encode_alignment(result.rows) if other else None
-    for (c1, c2), c in sorted(other.items()):
-        both = (code[:, c1] < 4) & (code[:, c2] < 4)
-        each = [int(((code[:, c1] == a) & (code[:, c2] == b)).sum()) for a, b in _CANONICAL]
-        lines.append("%d\t%d\tother\t%s\t%s\t%d\t%d\t%d\n" % (c1 + 1, c2 + 1, _fmt9(cv["best_score"][c]), _fmt9(cv["best_e"][c]), int(both.sum()),
-                                                                sum(each), sum(1 for v in each if v)))
-    return "".join(lines)
+    """The table of `dafs --covariation OUT` for one result with .covariation (dafs_host_covariation_table): one line
+    "c1<TAB>c2<TAB>kind<TAB>S<TAB>E<TAB>rows<TAB>canonical<TAB>types" per pair, columns 1-based, floats as %.9g.  First every
+    consensus pair by ascending left column (kind ss); then every distinct pair {c, best(c)} that is no consensus pair and has
+    E <= 0.05 (COV_TABLE_E_MAX, whatever the result's e_max), ordered by (c1, c2) (kind other), its counts taken from the rows."""
+    cv = result.covariation
+    code = capi.encode_alignment(result.rows)
+    ss = np.ascontiguousarray(result.ss, np.uint32)
+    arrs = [np.ascontiguousarray(cv[k], t) for k, t in (("best", np.uint32), ("best_score", np.float64), ("best_e", np.float64),
+                                                         ("pair_score", np.float64), ("pair_e", np.float64), ("pair_rows", np.uint32),
+                                                         ("pair_canonical", np.uint32), ("pair_types", np.uint32))]
+    if any(a.shape != (code.shape[1],) for a in [ss] + arrs):
+        raise ValueError("covariation_tsv: the structure and every array need one entry per column")
+    return capi.host_text(capi._covariation_table, code.shape[0], code.shape[1], code.ctypes.data, ss.ctypes.data, *[a.ctypes.data for a in arrs])
 
 
 def pairwise(names, seqs, pairs=None, ctx=None, max_bytes=None, **opts):

@@ -39,7 +39,7 @@ enum {
   DAFS_HIP_ECOMM = -7      /* the caller's collective (dafs_allgather_fn) reported a failure */
 };
 const char* dafs_hip_strerror(int code);
-/* last HIP runtime error text seen by this thread (diagnostics) */
+/* last HIP runtime error text seen by this thread (diagnostics), or the message of the last refusal of a host text function */
 const char* dafs_hip_last_error(void);
 
 /* Alignment models: reference -a ProbCons | CONTRAlign (src/dafs.cpp:1683-1690) */
@@ -243,6 +243,49 @@ int dafs_host_build_tree(uint32_t n, const float* sim, float* score, int32_t* le
  * sequence; *width: the number of merged columns. */
 int dafs_host_merge_added(uint32_t C, uint32_t k, const uint32_t* lens, const uint32_t* z, uint32_t* seed_col, uint32_t* res_col,
                           uint32_t* width);
+
+/* ------------------------------------------------------------------------------------------
+ * Host text (no device work; dafs_amd/csrc/host_text.cpp): the text formats and memory estimates that the `dafs` command line
+ * and the Python driver share, each defined once.  Returned text (the char** argument) is allocated by the library and freed
+ * by the caller with dafs_host_free; a list of strings comes back joined by '\n' (no name or row holds one).  DAFS_HIP_EINVAL
+ * leaves its message in dafs_hip_last_error(): for the seed reader it is the refusal the user sees.
+ * ---------------------------------------------------------------------------------------- */
+void dafs_host_free(void* text);
+/* Infernal's PP character: '*' for p >= 0.95, else the digit floor(p * 10 + 0.5) */
+char dafs_host_pp_char(double p);
+/* Stockholm names of n FASTA headers: the first word, "seq<k>" (k 1-based) for an empty header, ".2", ".3", ... for repeats */
+int dafs_host_stockholm_names(uint32_t n, const char* const* headers, char** names);
+/* One alignment as a Stockholm block (DESIGN.md "Alignment reliability"): n rows of len columns in printed order ('-' for
+ * gaps), residue_rel[r] the reliabilities of row r's residues, col_rel[len] per column, ss the bracket string.  Optional
+ * (NULL: no such line): tree_line ("#=GF CC"), rf[len] ("#=GC RF": 'x' where nonzero), cov ("#=GC cov_SS_cons"). */
+int dafs_host_stockholm_block(const char* tree_line, uint32_t n, uint32_t len, const char* const* names, const char* const* rows,
+                              const double* const* residue_rel, const double* col_rel, const char* ss, const uint8_t* rf,
+                              const char* cov, char** block);
+/* The code of a residue for dafs_hip_alignment_covariation: A 0, C 1, G 2, U / T 3 in either case, everything else 4 */
+uint8_t dafs_host_cov_code(char residue);
+/* The cov_SS_cons characters: '2' at both columns of every pair of ss with pair_e <= e_max (a NaN never is), '.' elsewhere */
+int dafs_host_cov_ss_cons(uint32_t len, const uint32_t* ss, const double* pair_e, double e_max, char** chars);
+/* The --covariation table of the rows' codes code[n * len], the structure ss and the arrays
+ * dafs_hip_alignment_covariation returned: the pairs of ss (kind ss), then every other pair {c, best[c]} with best_e <= 0.05 */
+int dafs_host_covariation_table(uint32_t n, uint32_t len, const uint8_t* code, const uint32_t* ss, const uint32_t* best,
+                                const double* best_score, const double* best_e, const double* pair_score, const double* pair_e,
+                                const uint32_t* pair_rows, const uint32_t* pair_canonical, const uint32_t* pair_types, char** table);
+/* The --pairwise-scores table: per pair k the line "x+1 y+1 names[x] names[y] sim score iterations", tab-separated, floats as
+ * %.9g; iterations is signed (-1: a pair that was not asked) */
+int dafs_host_pairwise_table(uint64_t npairs, const uint32_t* x, const uint32_t* y, uint32_t nnames, const char* const* names,
+                             const double* sim, const double* score, const int64_t* iterations, char** table);
+/* The seed reader of --seed.  _parse: the bytes of a Stockholm or aligned-FASTA file into *n names and
+ * rows as the file holds them.  _clean: the checks (an empty seed, rows of unequal length, a character that is neither a letter
+ * nor a gap, a row without residues), then the rows without their all-gap columns, '-' for every gap. */
+int dafs_host_seed_parse(const char* text, size_t bytes, uint32_t* n, char** names, char** rows);
+int dafs_host_seed_clean(uint32_t n, const char* const* names, const char* const* rows, char** cleaned);
+/* Estimated device memory (bytes) of one family's phase-1 stores and of one resident node; the default budget of a sub-batch
+ * of families or a chunk of pairs.  _pack_greedy: group_of[k] is the group of item k, groups filled in input order up to
+ * max_bytes, an item over the budget alone. */
+uint64_t dafs_host_family_bytes(uint32_t n, const uint32_t* lens);
+uint64_t dafs_host_node_bytes(uint32_t len1, uint32_t len2);
+uint64_t dafs_host_batch_bytes(void);
+int dafs_host_pack_greedy(uint32_t n, const uint64_t* sizes, uint64_t max_bytes, uint32_t* group_of);
 
 /* ------------------------------------------------------------------------------------------
  * L1: probabilistic consistency transforms.

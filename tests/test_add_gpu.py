@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import reliability_ref as rr
+import text_ref
 from dafs_amd import synth
 
 pytestmark = pytest.mark.gpu
@@ -149,6 +150,9 @@ def test_cli_matches_python(tmp_path):
     seed_sto = str(tmp_path / "seed.sto")
     _write_sto(seed_sto, snames, srows)
     assert stockholm.read_seed(seed_sto) == (snames, srows)
+    # the reader is the command line's own: the restatement reads both files alike
+    for seed in (seed_sto, seed_aln):
+        assert text_ref.clean_seed(*text_ref.parse_seed(open(seed, "rb").read().decode("latin-1"))) == (snames, srows)
     want = pipeline.add(snames, srows, names[4:], seqs[4:], reliability=True)
     for seed in (seed_sto, seed_aln):
         out_sto = str(tmp_path / "out.sto")
@@ -156,6 +160,8 @@ def test_cli_matches_python(tmp_path):
         assert rc == 0, err
         assert out == want.output
         assert open(out_sto).read() == want.stockholm
+        # and the block writer: the restatement builds the same bytes from the result's arrays
+        assert open(out_sto).read() == text_ref.result_block(want, snames + names[4:], want.rf)
     assert "#=GC RF" in want.stockholm and "#=GF CC" not in want.stockholm
     # -f and --bp-update1 agree too
     for flags, kw in ((["-f", "0.5"], dict(w_pct_f=0.5)), (["--bp-update1"], dict(bp_update1=True))):

@@ -149,14 +149,15 @@ def test_dd_node_plan_reproduces_the_recorded_plans(monkeypatch):
 def test_host_build_tree_matches_python_twin():
     """dafs_host_build_tree (host code inside the library, used by the CLI and the pipeline driver) against the
     Python restatement of DAFS::build_tree, on random similarity matrices with ties."""
-    from dafs_amd import capi, pipeline
+    from dafs_amd import capi
+    from text_ref import build_tree
     rng = np.random.default_rng(5)
     for n in (1, 2, 3, 9, 33):
         s = rng.integers(0, 50, size=(n, n)).astype(np.float32) / np.float32(64)
         s = np.maximum(s, s.T)
         np.fill_diagonal(s, 1.0)
         a = capi.build_tree(s)
-        b = pipeline.build_tree(s)
+        b = build_tree(s)
         assert np.array_equal(a[0].view(np.uint32), b[0].view(np.uint32))
         assert np.array_equal(a[1], b[1]) and np.array_equal(a[2], b[2])
 

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import covariation_ref as cr
+import text_ref
 from dafs_amd import synth
 
 pytestmark = pytest.mark.gpu
@@ -218,11 +219,13 @@ def test_cli_equals_python(tmp_path, flags):
     assert res.output == out
     assert open(tsv).read() == pipeline.covariation_tsv(res) and open(tsv).read().count("\tss\t") == int((res.ss != NONE).sum())
     assert open(sto).read() == res.stockholm and "#=GC cov_SS_cons" in res.stockholm
+    # both sides of those two go through the library's formatter: the restatement builds the same bytes from the result's arrays
+    assert open(tsv).read() == text_ref.covariation_tsv(res) and open(sto).read() == text_ref.result_block(res, names)
     # the defaults: 100 shuffles, seed 1; without --stockholm the table alone
     rc, out, err = run_cli(*flags, "--covariation", tsv, path)
     assert rc == 0 and out == want_out, err
     dflt = pipeline.run(names, seqs, covariation=True, **kw)
-    assert open(tsv).read() == pipeline.covariation_tsv(dflt)
+    assert open(tsv).read() == pipeline.covariation_tsv(dflt) == text_ref.covariation_tsv(dflt)
     if flags:
         return
     # two files: the blocks of stdout, in order, each the file's own
@@ -237,6 +240,8 @@ def test_cli_equals_python(tmp_path, flags):
     res2 = pipeline.run(*_split(recs), covariation=dict(shuffles=30, seed=11), **kw)
     assert open(tsv).read() == "==> %s <==\n%s==> %s <==\n%s" % (path, pipeline.covariation_tsv(res), fam, pipeline.covariation_tsv(res2))
     assert open(sto).read() == res.stockholm + res2.stockholm
+    assert open(tsv).read() == "==> %s <==\n%s==> %s <==\n%s" % (path, text_ref.covariation_tsv(res), fam, text_ref.covariation_tsv(res2))
+    assert open(sto).read() == text_ref.result_block(res, names) + text_ref.result_block(res2, _split(recs)[0])
     # --seed: the new sequences of fam added to the alignment of its first three
     n5, s5 = _split(recs)
     seed_fa, new_fa, seed_aln = str(tmp_path / "seed.fa"), str(tmp_path / "new.fa"), str(tmp_path / "seed.aln")
@@ -256,6 +261,8 @@ def test_cli_equals_python(tmp_path, flags):
     assert rc == 0 and out == out3, err
     added = pipeline.add(snames, srows, n5[3:], s5[3:], reliability=True, covariation=dict(shuffles=30, seed=11))
     assert added.output == out and open(tsv).read() == pipeline.covariation_tsv(added) and open(sto).read() == added.stockholm
+    assert open(tsv).read() == text_ref.covariation_tsv(added) and open(sto).read() == text_ref.result_block(added, snames + n5[3:], added.rf)
+    assert text_ref.clean_seed(*text_ref.parse_seed(aln)) == (snames, srows)
 
 
 def test_refusals_leave_the_context_usable():

@@ -7,6 +7,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import text_ref
 from dafs_amd import capi, pipeline, synth
 
 pytestmark = pytest.mark.gpu
@@ -184,6 +185,8 @@ def test_cli_pairwise_equals_two_sequence_files(tmp_path):
     names, seqs = [n for n, _ in recs], [s for _, s in recs]
     pw = pipeline.pairwise(names, seqs)
     assert tsv.read_bytes() == pipeline.pairwise_scores_tsv(names, pw.pairs, pw.sim, pw.score, pw.iterations).encode()
+    # that writer is the command line's own: the restatement builds the same bytes from the result's arrays
+    assert tsv.read_bytes() == text_ref.pairwise_scores_tsv(names, pw.pairs, pw.sim, pw.score, pw.iterations).encode()
     assert out == "".join("==> %d %d <==\n" % (x + 1, y + 1) + r.output for (x, y), r in zip(pw.pairs, pw.results))
 
 

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import reliability_ref as rr
+import text_ref
 from dafs_amd import synth
 
 pytestmark = pytest.mark.gpu
@@ -182,11 +183,12 @@ def test_cli_stockholm(tmp_path, flags):
     lines = out.split("\n")
     assert ss == lines[2]
     assert rows == lines[4::2][:len(rows)] and len(rows) == (len(lines) - 4) // 2
-    # the Python twin writes the same bytes
+    # the Python driver writes the same bytes, with the same writer; the restatement builds them from the result's arrays
     names, seqs = _headers(path)
     res = pipeline.run(names, seqs, reliability=True, align_model=capi.ALIGN_CONTRALIGN if flags else capi.ALIGN_PROBCONS)
     assert res.output == out
     assert res.stockholm == text
+    assert text_ref.result_block(res, names) == text
     # several files: one block each, in input order, each the file's own
     fam = str(tmp_path / "fam.fa")
     with open(fam, "w") as f:
