@@ -159,6 +159,8 @@ _pp_char = _sig("dafs_host_pp_char", C.c_char, [C.c_double])
 _stockholm_names = _sig("dafs_host_stockholm_names", C.c_int, [C.c_uint32, _strs, _text])
 _stockholm_block = _sig("dafs_host_stockholm_block", C.c_int, [C.c_char_p, C.c_uint32, C.c_uint32, _strs, _strs, C.POINTER(C.c_void_p), C.c_void_p,
                                                                 C.c_char_p, C.c_void_p, C.c_char_p, _text])
+_stockholm_block_rows = _sig("dafs_host_stockholm_block_rows", C.c_int, [C.c_char_p, C.c_uint32, C.c_uint32, _strs, _strs, C.POINTER(C.c_void_p),
+                                                                          C.c_void_p, C.c_char_p, C.c_void_p, C.c_char_p, _strs, _text])
 _cov_code = _sig("dafs_host_cov_code", C.c_uint8, [C.c_char])
 _cov_ss_cons = _sig("dafs_host_cov_ss_cons", C.c_int, [C.c_uint32, C.c_void_p, C.c_void_p, C.c_double, _text])
 _covariation_table = _sig("dafs_host_covariation_table", C.c_int, [C.c_uint32, C.c_uint32] + [C.c_void_p] * 10 + [_text])
@@ -168,6 +170,8 @@ _seed_clean = _sig("dafs_host_seed_clean", C.c_int, [C.c_uint32, _strs, _strs, _
 _family_bytes = _sig("dafs_host_family_bytes", C.c_uint64, [C.c_uint32, C.c_void_p])
 _node_bytes = _sig("dafs_host_node_bytes", C.c_uint64, [C.c_uint32, C.c_uint32])
 _batch_bytes = _sig("dafs_host_batch_bytes", C.c_uint64, [])
+_structure_bytes = _sig("dafs_host_structure_bytes", C.c_uint64, [C.c_uint32, C.c_uint32])
+_structures_batch_bytes = _sig("dafs_host_structures_batch_bytes", C.c_uint64, [])
 _pack_greedy = _sig("dafs_host_pack_greedy", C.c_int, [C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p])
 _set_mp = _sig("dafs_hip_set_mp", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])
 _nodes_open = _sig("dafs_hip_nodes_open", C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(NodeInput), C.POINTER(DDParams), C.c_void_p])
@@ -182,6 +186,8 @@ _update_basepairing = _sig("dafs_hip_update_basepairing", C.c_int, [C.c_void_p, 
 _consensus_structure = _sig("dafs_hip_consensus_structure", C.c_int,
                             [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p,
                              C.POINTER(C.c_float), C.c_void_p])
+_consensus_structures = _sig("dafs_hip_consensus_structures", C.c_int,
+                             [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p])
 _alignment_reliability = _sig("dafs_hip_alignment_reliability", C.c_int,
                               [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5)
 _alignment_covariation = _sig("dafs_hip_alignment_covariation", C.c_int,
@@ -585,6 +591,26 @@ class Context:
         check(_consensus_structure(self._h, n, L, seq.ctypes.data, mask.ctypes.data, th, ss.ctypes.data, C.byref(score),
                                    None if p is None else p.ctypes.data))
         return np.float32(score.value), ss, p
+
+    def consensus_structures(self, alignments, th):
+        """dafs_hip_consensus_structures: the common structures of many alignments in one call.  alignments: a list of
+        (seq, mask) as consensus_structure takes them; returns a list of (score, ss), each what consensus_structure gives."""
+        als = [(np.ascontiguousarray(s, np.uint32).reshape(-1), np.ascontiguousarray(m, np.uint8)) for s, m in alignments]
+        if any(m.ndim != 2 or m.shape[0] != len(s) for s, m in als):
+            raise ValueError("consensus_structures: every alignment is (seq[n], mask[n, len])")
+        if not als:
+            check(_consensus_structures(self._h, 0, None, None, None, None, th, None, None))
+            return []
+        n_rows = np.array([m.shape[0] for _, m in als], np.uint32)
+        lens = np.array([m.shape[1] for _, m in als], np.uint32)
+        seq = np.ascontiguousarray(np.concatenate([s for s, _ in als]), np.uint32)
+        mask = np.ascontiguousarray(np.concatenate([m.reshape(-1) for _, m in als]), np.uint8)
+        ss = np.zeros(max(int(lens.sum()), 1), np.uint32)
+        score = np.zeros(len(als), np.float32)
+        check(_consensus_structures(self._h, len(als), n_rows.ctypes.data, lens.ctypes.data, seq.ctypes.data, mask.ctypes.data, th,
+                                    ss.ctypes.data, score.ctypes.data))
+        cuts = np.cumsum(lens)[:-1]
+        return [(sc, x) for sc, x in zip(score, np.split(ss[:int(lens.sum())], cuts))]
 
     def alignment_reliability(self, seq, mask, ss=None, mp_relaxed=None, bp_relaxed=None):
         """Reliability of the alignment (seq, mask) from the context's stores (dafs_hip_alignment_reliability).  ss: the

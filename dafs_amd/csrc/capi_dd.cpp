@@ -897,6 +897,184 @@ extern "C" int dafs_hip_consensus_structure(dafs_hip_ctx* c, uint32_t n, uint32_
   return average_and_decode(c, n, len, seq, mask, c->bp[c->cur_bp], false, true, th, ss, score, p_out);
 }
 
+// Many alignments in one call.  Per chunk (greedy in input order under a byte budget): every alignment
+// is carved out of c->work as average_and_decode carves its one -- the small arrays of all of them first, so that one upload
+// brings the geometry, the node and the decoder descriptors, and the structures and scores back to back, so that one copy
+// brings the results -- then, size class by size class, one dd_avg_launch over the class's nodes and one k_nussinov_batch
+// over its descriptors.  Each alignment takes the form nussinov_launch gives its width, so its bits are the single call's.
+namespace {
+
+struct cs_class { uint32_t threads; size_t lds_cap; };
+// Size classes of a launch.  The decoder takes ~130 VGPRs, three wavefronts per SIMD, so registers admit twelve wavefronts per
+// CU whatever the workgroup size.  Up to 256 columns one wavefront sweeps a span in one step: 64
+// threads, twelve workgroups per CU.  Up to 48 KB of LDS (~1 000 columns) 256 threads, three workgroups per CU by registers
+// and by LDS alike.  Wider: the 512 threads of the single decoder, one workgroup per CU (opt-in above 64 KB).  The form on
+// global tables (no LDS) has the last class to itself, so that a 12 000-column alignment does not set the averaging
+// kernel's row length for a class of narrow ones.
+constexpr uint32_t kCsClassCount = 4, kCsGlobalClass = 3;
+const cs_class kCsClasses[kCsClassCount] = {{64, 12320}, {256, 48 * 1024}, {512, kDdLdsBudget}, {512, 0}};
+const uint32_t kCsMaxLaunch = 32768;  // alignments per chunk: the averaging kernel's grid has one y per node
+
+uint32_t cs_class_of(uint32_t L, uint32_t form, size_t lds) {
+  if (form == DAFS_HIP_NONE) return kCsGlobalClass;
+  if (L <= 256 && lds <= kCsClasses[0].lds_cap) return 0;
+  return lds <= kCsClasses[1].lds_cap ? 1 : 2;
+}
+
+}  // namespace
+
+extern "C" int dafs_hip_consensus_structures(dafs_hip_ctx* c, uint32_t nalign, const uint32_t* n_rows, const uint32_t* len, const uint32_t* seq,
+                                             const uint8_t* mask, float th, uint32_t* ss, float* score) {
+  if (!c) return DAFS_HIP_EINVAL;
+  if (nalign == 0) return DAFS_HIP_OK;
+  if (!n_rows || !len || !seq || !mask || !ss) return DAFS_HIP_EINVAL;
+  if (hip_check(hipSetDevice(c->device))) return DAFS_HIP_ENODEV;
+  const bp_store& bps = c->bp[c->cur_bp];
+  if (!bps.valid || c->fold_pending) return DAFS_HIP_EINVAL;
+  // ---- everything the launches will read, checked on the host first ----
+  std::vector<geom> g(nalign);
+  std::vector<size_t> row0(nalign + 1, 0), mask0(nalign + 1, 0), col0(nalign + 1, 0);
+  std::vector<uint64_t> bytes(nalign);
+  for (uint32_t a = 0; a < nalign; ++a) {
+    if (!n_rows[a] || !len[a]) return DAFS_HIP_EINVAL;
+    row0[a + 1] = row0[a] + n_rows[a];
+    mask0[a + 1] = mask0[a] + (size_t)n_rows[a] * len[a];
+    col0[a + 1] = col0[a] + len[a];
+    bytes[a] = dafs_host_structure_bytes(n_rows[a], len[a]);
+  }
+  for (uint32_t a = 0; a < nalign; ++a) {
+    const int rc = make_geom(c, n_rows[a], len[a], seq + row0[a], mask + mask0[a], g[a]);
+    if (rc) return rc;
+  }
+  uint64_t budget = dafs_host_structures_batch_bytes();
+  if (const char* e = getenv("DAFS_HIP_CS_BATCH_BYTES")) {  // a value that is no number is ignored
+    char* end = nullptr;
+    const unsigned long long v = strtoull(e, &end, 10);
+    if (end != e && *end == '\0' && *e >= '0' && *e <= '9') budget = v;
+  }
+  std::vector<uint32_t> chunk_of(nalign);
+  int rc;
+  if ((rc = dafs_host_pack_greedy(nalign, bytes.data(), budget, chunk_of.data()))) return rc;
+
+  mp_store_dev none;
+  memset(&none, 0, sizeof none);
+  const bp_store_dev bpv = bps.view();
+  std::vector<uint32_t> order;
+  std::vector<dd_node> nodes;
+  std::vector<cs_desc> descs;
+  std::vector<uint8_t> head, out;
+  for (uint32_t a0 = 0; a0 < nalign;) {
+    uint32_t a1 = a0;
+    while (a1 < nalign && chunk_of[a1] == chunk_of[a0] && a1 - a0 < kCsMaxLaunch) ++a1;
+    const uint32_t m = a1 - a0;
+    // the chunk's alignments class by class, input order inside a class
+    std::vector<uint32_t> cls(m), form(m);
+    uint32_t first_of[kCsClassCount + 1] = {0};
+    size_t lds_of[kCsClassCount] = {0};
+    uint32_t len_of[kCsClassCount] = {0};
+    for (uint32_t k = 0; k < m; ++k) {
+      size_t lds = 0;
+      form[k] = nussinov_form(len[a0 + k], &lds);
+      cls[k] = cs_class_of(len[a0 + k], form[k], lds);
+      ++first_of[cls[k] + 1];
+      lds_of[cls[k]] = std::max(lds_of[cls[k]], lds);
+      len_of[cls[k]] = std::max(len_of[cls[k]], len[a0 + k]);
+    }
+    for (uint32_t k = 0; k < kCsClassCount; ++k) first_of[k + 1] += first_of[k];
+    order.assign(m, 0);
+    {
+      uint32_t at[kCsClassCount];
+      std::copy(first_of, first_of + kCsClassCount, at);
+      for (uint32_t k = 0; k < m; ++k) order[at[cls[k]]++] = k;
+    }
+    // ---- carve: head (uploaded), results (copied back), then the matrices and tables ----
+    nodes.assign(m, dd_node());
+    descs.assign(m, cs_desc());
+    carver cv;
+    dd_node* d_nodes = nullptr;
+    cs_desc* d_descs = nullptr;
+    size_t head_bytes = 0, out_off = 0, out_bytes = 0;
+    std::vector<size_t> ss_off(m);
+    float* d_scores = nullptr;
+    for (int pass = 0; pass < 2; ++pass) {
+      cv.used = 0;
+      d_nodes = cv.take<dd_node>(m);
+      d_descs = cv.take<cs_desc>(m);
+      for (uint32_t j = 0; j < m; ++j) {
+        const uint32_t k = order[j], a = a0 + k;
+        dd_node& nd = nodes[j];
+        memset(&nd, 0, sizeof nd);
+        dd_fold& f = nd.f[0];  // the one alignment; the node has no second one and no z
+        f.n = n_rows[a]; f.L = len[a];
+        f.seq = cv.take<uint32_t>(f.n);
+        f.rank = cv.take<uint32_t>((size_t)f.n * f.L);
+        f.idx = cv.take<uint32_t>(g[a].idx.size() + 1);
+        f.idxoff = cv.take<uint32_t>(f.n);
+      }
+      head_bytes = cv.used;
+      out_off = (cv.used + 255) & ~(size_t)255;
+      for (uint32_t j = 0; j < m; ++j) {
+        uint32_t* p = cv.take<uint32_t>((size_t)len[a0 + order[j]] + 1);
+        descs[j].ss = p;
+        ss_off[j] = (size_t)((uint8_t*)p - cv.base);
+      }
+      d_scores = cv.take<float>(m);
+      out_bytes = cv.used - out_off;
+      for (uint32_t j = 0; j < m; ++j) {
+        const uint32_t L = len[a0 + order[j]];
+        dd_fold& f = nodes[j].f[0];
+        f.p = cv.take<float>((size_t)L * L);
+        carve_nuss(cv, L, f.w);
+        nodes[j].score = d_scores + j;
+        descs[j].L = L; descs[j].form = form[order[j]]; descs[j].p = f.p; descs[j].ws = f.w; descs[j].score = d_scores + j;
+      }
+      if (pass == 0) {
+        uint64_t estimate = 0;
+        for (uint32_t a = a0; a < a1; ++a) estimate += bytes[a];
+        if (cv.used + 256 > estimate) {  // dafs_host_structure_bytes is the bound of this carving
+          fprintf(stderr, "dafs_hip: a chunk of %u alignments takes %zu bytes, over its estimate of %llu\n", m, cv.used + 256, (unsigned long long)estimate);
+          return DAFS_HIP_ELAUNCH;
+        }
+        if ((rc = c->work.reserve(cv.used + 256))) return rc;
+        cv.base = c->work.ptr;
+      }
+    }
+    head.assign(head_bytes, 0);
+    auto put = [&](const void* dst, const void* src, size_t n) {
+      if (n) memcpy(head.data() + ((const uint8_t*)dst - cv.base), src, n);
+    };
+    put(d_nodes, nodes.data(), (size_t)m * sizeof(dd_node));
+    put(d_descs, descs.data(), (size_t)m * sizeof(cs_desc));
+    for (uint32_t j = 0; j < m; ++j) {
+      const uint32_t a = a0 + order[j];
+      const dd_fold& f = nodes[j].f[0];
+      put(f.seq, seq + row0[a], (size_t)f.n * 4);
+      put(f.rank, g[a].rank.data(), g[a].rank.size() * 4);
+      put(f.idx, g[a].idx.data(), g[a].idx.size() * 4);
+      put(f.idxoff, g[a].idxoff.data(), (size_t)f.n * 4);
+    }
+    if (hip_check(hipMemcpyAsync(cv.base, head.data(), head_bytes, hipMemcpyHostToDevice, c->stream))) return DAFS_HIP_ELAUNCH;
+    // (no fill of the matrices: k_node_avg writes every cell of every row of p)
+    for (uint32_t k = 0; k < kCsClassCount; ++k) {
+      const uint32_t n = first_of[k + 1] - first_of[k];
+      if (!n) continue;
+      if ((rc = dd_avg_launch(d_nodes + first_of[k], n, len_of[k], none, bpv, 0, 0, c->stream))) break;
+      if ((rc = nussinov_batch_launch(d_descs + first_of[k], n, th, kCsClasses[k].threads, lds_of[k], c->stream))) break;
+    }
+    out.resize(out_bytes);
+    if (!rc && hip_check(hipMemcpyAsync(out.data(), cv.base + out_off, out_bytes, hipMemcpyDeviceToHost, c->stream))) rc = DAFS_HIP_ELAUNCH;
+    if (hip_check(hipStreamSynchronize(c->stream)) && !rc) rc = DAFS_HIP_ELAUNCH;  // also after a failure: `head` is in flight
+    if (rc) return rc;
+    for (uint32_t j = 0; j < m; ++j) {
+      const uint32_t a = a0 + order[j];
+      memcpy(ss + col0[a], out.data() + (ss_off[j] - out_off), (size_t)len[a] * 4);
+      if (score) memcpy(score + a, out.data() + ((size_t)((uint8_t*)(d_scores + j) - cv.base) - out_off), 4);
+    }
+    a0 = a1;
+  }
+  return DAFS_HIP_OK;
+}
+
 // DAFS::update_basepairing_probability (dafs.cpp:609-712, options --bp-update / --bp-update1; no RNAalifold term, one level
 // of brackets): every sequence of the alignment is folded again under the constraint that the common structure ss puts on
 // it -- paired columns whose two residues exist in the row become '(' and ')', everything else stays free -- and the

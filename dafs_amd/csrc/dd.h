@@ -193,6 +193,19 @@ int dd_pack_launch(const dd_node* d_nodes, uint32_t nnodes, const uint32_t* d_of
 int dd_solve_launch(const dd_node* d_nodes, uint32_t nnodes, dd_params prm, size_t lds_bytes, bool split, uint32_t* d_paused, hipStream_t st);
 // standalone decoders on dense device matrices (one workgroup each)
 int nussinov_launch(uint32_t L, const float* p, const float* q, float w, float th, nuss_ws ws, uint32_t* ss, float* score, hipStream_t st);
+// One alignment of a batched decode (k_nussinov_batch, one workgroup each): the standalone decoder's arguments without q.
+// form: the candidates per column that nuss_wg_span keeps in LDS (4 / 2 / 0), or 0xFFFFFFFF for the span-ordered form on
+// global tables -- per alignment what nussinov_launch chooses for its width, so both give the same table and structure.
+struct cs_desc {
+  uint32_t L, form;
+  const float* p;  // L*L
+  nuss_ws ws;
+  uint32_t* ss;    // L
+  float* score;    // [1]
+};
+uint32_t nussinov_form(uint32_t L, size_t* lds_bytes);  // the form of an alignment of L columns and its dynamic LDS
+// descs[0..n): alignments of one size class -- `threads` per workgroup, lds_bytes >= every member's
+int nussinov_batch_launch(const cs_desc* d_descs, uint32_t n, float th, uint32_t threads, size_t lds_bytes, hipStream_t st);
 int nussinov_dense_launch(uint32_t L, const float* p, const float* q, float w, float th, float* dp, uint32_t* tr, uint32_t* stack, uint32_t* ss,
                           float* score, hipStream_t st);
 int nw_launch(uint32_t L1, uint32_t L2, const float* p, const float* q, float th, uint32_t* env, int compute_env,

@@ -1228,6 +1228,33 @@ __global__ __launch_bounds__(DD_THREADS) void k_nussinov_single(uint32_t L, cons
   }
 }
 
+// The same decoder for many alignments at once (dafs_hip_consensus_structures): a workgroup per alignment, its arguments in
+// descs[blockIdx.x].  The alignments of a launch are one size class (the host groups them), so the dynamic LDS is the widest
+// member's and not the widest alignment's of the whole call.  The body is k_nussinov_single's with q absent: the same
+// device functions in the same forms, hence the same table, codes, structure and score.  Every workgroup writes its own
+// alignment's arrays only.
+__global__ __launch_bounds__(DD_THREADS) void k_nussinov_batch(const cs_desc* descs, float th) {
+  extern __shared__ unsigned char s_dd[];
+  const cs_desc d = descs[blockIdx.x];
+  const uint32_t L = d.L;
+  for (uint32_t i = threadIdx.x; i < L; i += blockDim.x) d.ss[i] = DD_NONE;
+  if (d.form != DD_NONE && L >= 3) {
+    float* lds = (float*)(((uintptr_t)s_dd + 15) & ~(uintptr_t)15);
+    const float sc = d.form == 4 ? nuss_wg_span<4, true>(L, d.p, d.ws, lds, nullptr, 0.0f, th)
+                   : d.form == 2 ? nuss_wg_span<2, true>(L, d.p, d.ws, lds, nullptr, 0.0f, th)
+                                 : nuss_wg_span<0, true>(L, d.p, d.ws, lds, nullptr, 0.0f, th);
+    if (threadIdx.x < 64) nuss_traceback_span(L, d.ws.tr, d.ss, (uint32_t*)lds, (int)threadIdx.x);
+    if (threadIdx.x == 0) *d.score = sc;
+    return;
+  }
+  nuss_ws none = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  nuss_pair_dp(L, d.p, nullptr, 0.0f, d.ws, 0, nullptr, nullptr, 0.0f, none, th);
+  if (threadIdx.x == 0) {
+    nuss_traceback(L, d.ws, d.ss, d.ws.ck);
+    *d.score = d.ws.dp[L - 1];
+  }
+}
+
 // Nussinov::decode, the dense class (reference src/nussinov.cpp:32-113 with q, :115-204 without): every pair scores
 // sm = w(p-th)-q (or p-th), and the bifurcation runs over every split k in (i, j): dp[i][k] + dp[k+1][j].  Span-ordered,
 // one barrier per span, a thread per cell; the traceback pushes (i,k) and (k+1,j) for code k-i+3.
@@ -2342,7 +2369,7 @@ __global__ __launch_bounds__(DD_SOLVE_THREADS) void k_dd_solve(const dd_node* no
 // ------------------------------------------------------------------------------------------
 // dynamic-LDS opt-in above 64 KB, once per device and kernel
 static int lds_optin(const void* fn, int slot, size_t bytes, size_t budget = kDdLdsBudget) {
-  static bool done[5][16] = {{false}};
+  static bool done[6][16] = {{false}};
   int dev = 0;
   if (hip_check(hipGetDevice(&dev))) return DAFS_HIP_ENODEV;
   if (bytes <= 64 * 1024) return DAFS_HIP_OK;
@@ -2446,6 +2473,24 @@ int nussinov_launch(uint32_t L, const float* p, const float* q, float w, float t
     if (rc) return rc;
   }
   STAGE_LAUNCH(ST_NUSSINOV_SINGLE, st) hipLaunchKernelGGL(k_nussinov_single, dim3(1), dim3(DD_THREADS), lds, st, L, p, q, w, th, ws, ss, score, heads);
+  return hip_check(hipGetLastError()) ? DAFS_HIP_ELAUNCH : DAFS_HIP_OK;
+}
+// what nussinov_launch chooses for L columns: the most candidate heads whose workgroup form fits, else the global tables
+uint32_t nussinov_form(uint32_t L, size_t* lds_bytes) {
+  *lds_bytes = 0;
+  if (!getenv("DAFS_HIP_NUSS_GLOBAL"))
+    for (uint32_t K : {4u, 2u, 0u})
+      if ((size_t)dd_wg_words(L, K) * 4 + 16 <= kDdLdsBudget) { *lds_bytes = (size_t)dd_wg_words(L, K) * 4 + 16; return K; }
+  return DD_NONE;
+}
+int nussinov_batch_launch(const cs_desc* d_descs, uint32_t n, float th, uint32_t threads, size_t lds_bytes, hipStream_t st) {
+  if (!n) return DAFS_HIP_OK;
+  if (lds_bytes > kDdLdsBudget || threads < 64 || threads > DD_THREADS || (threads & 63)) return DAFS_HIP_EINVAL;
+  if (lds_bytes > 64 * 1024) {
+    const int rc = lds_optin((const void*)k_nussinov_batch, 5, lds_bytes);
+    if (rc) return rc;
+  }
+  STAGE_LAUNCH(ST_NUSSINOV_BATCH, st) hipLaunchKernelGGL(k_nussinov_batch, dim3(n), dim3(threads), lds_bytes, st, d_descs, th);
   return hip_check(hipGetLastError()) ? DAFS_HIP_ELAUNCH : DAFS_HIP_OK;
 }
 int nussinov_dense_launch(uint32_t L, const float* p, const float* q, float w, float th, float* dp, uint32_t* tr, uint32_t* stack, uint32_t* ss,

@@ -73,6 +73,7 @@ struct Options {
   int device = 0;
   std::vector<int> devices;  // --devices: one process per entry for phase 1
   std::string stockholm;  // --stockholm FILE
+  bool row_structures = false;  // --row-structures: a #=GR SS line per row of the Stockholm blocks
   std::string seed;       // --seed SEED: add FILE's sequences to this alignment
   bool pairwise = false;  // --pairwise: every pair of FILE's sequences aligned as a two-sequence run
   std::string pairwise_scores;  // --pairwise-scores OUT
@@ -103,6 +104,9 @@ const char* kHelp =
     "                        (shards exchanged over RCCL); the progressive alignment runs on the first\n"
     "      --stockholm FILE  Also write every printed alignment to FILE in Stockholm format, one block per input\n"
     "                        file, with per-residue (#=GR PP) and per-column (#=GC PP_cons) reliabilities\n"
+    "      --row-structures  With --stockholm: after every row's #=GR PP line a #=GR SS line, the structure of that row alone\n"
+    "                        (its own base-pairing probabilities after the consistency transform, decoded at the threshold\n"
+    "                        of SS_cons), in the row's columns\n"
     "      --seed SEED       Add the sequences of the one FILE to the alignment SEED (Stockholm, or aligned FASTA\n"
     "                        as dafs prints it) without changing its columns; the output has no tree line, and\n"
     "                        --stockholm adds a #=GC RF line (x: seed column).  Not with -r, --bp-update, --devices,\n"
@@ -160,7 +164,7 @@ Options parse(int argc, char** argv) {
       {"no-alifold", {0, false}}, {"fold-th1", {'T', true}}, {"gamma1", {'G', true}}, {"ipknot", {0, false}},
       {"bp-update", {0, false}}, {"bp-update1", {0, false}}, {"fold-aux", {0, true}}, {"save-align-aux", {0, true}},
       {"save-fold-aux", {0, true}}, {"device", {0, true}}, {"devices", {0, true}}, {"input", {0, true}},
-      {"stockholm", {0, true}}, {"seed", {0, true}}, {"pairwise", {0, false}}, {"pairwise-scores", {0, true}},
+      {"stockholm", {0, true}}, {"row-structures", {0, false}}, {"seed", {0, true}}, {"pairwise", {0, false}}, {"pairwise-scores", {0, true}},
       {"covariation", {0, true}}, {"cov-shuffles", {0, true}}, {"cov-seed", {0, true}}};
   std::map<char, std::string> shorts;
   for (const auto& kv : spec)
@@ -225,6 +229,7 @@ Options parse(int argc, char** argv) {
       if (value.empty()) throw std::string("--stockholm needs a file name");
       o.stockholm = value;
     }
+    else if (name == "row-structures") o.row_structures = true;
     else if (name == "seed") {
       if (value.empty()) throw std::string("--seed needs a file name");
       o.seed = value;
@@ -253,6 +258,7 @@ Options parse(int argc, char** argv) {
       else { o.cov_seed = v; o.cov_seed_given = true; }
     }
   }
+  if (o.row_structures && o.stockholm.empty()) throw std::string("--row-structures needs --stockholm");
   if ((o.cov_shuffles_given || o.cov_seed_given) && o.covariation.empty()) throw std::string("--cov-shuffles and --cov-seed need --covariation");
   if (o.pairwise && (!o.covariation.empty() || o.cov_shuffles_given || o.cov_seed_given))
     throw std::string("--pairwise: two rows carry no covariation; --covariation, --cov-shuffles and --cov-seed cannot be combined with --pairwise");
@@ -898,14 +904,63 @@ dafs_dd_params dd_params_of(const Options& o) {
   return prm;
 }
 
+// The first decode of many final alignments in one library call (dafs_hip_consensus_structures): ss[k] of *alns[k], decoded
+// over the rows in the order each holds them.
+void consensus_structures(dafs_hip_ctx* ctx, const std::vector<const ALN*>& alns, float th, std::vector<VU>& ss) {
+  std::vector<uint32_t> n_rows, len, seq, all;
+  std::vector<uint8_t> mask;
+  for (const ALN* a : alns) {
+    std::vector<uint32_t> rs;
+    std::vector<uint8_t> rm;
+    flatten(*a, rs, rm);
+    n_rows.push_back((uint32_t)a->size());
+    len.push_back((uint32_t)(*a)[0].second.size());
+    seq.insert(seq.end(), rs.begin(), rs.end());
+    mask.insert(mask.end(), rm.begin(), rm.end());
+  }
+  size_t total = 0;
+  for (uint32_t l : len) total += l;
+  all.resize(total ? total : 1);
+  check(dafs_hip_consensus_structures(ctx, (uint32_t)alns.size(), n_rows.data(), len.data(), seq.data(), mask.data(), th, all.data(), nullptr));
+  ss.clear();
+  size_t at = 0;
+  for (uint32_t l : len) {
+    ss.push_back(VU(all.begin() + at, all.begin() + at + l));
+    at += l;
+  }
+}
+
+// --row-structures: the structure of every listed sequence alone -- its one-row alignment decoded from the base-pairing
+// store the progressive phase read, at the threshold of SS_cons -- all in one library call
+std::map<uint32_t, VU> row_structures(dafs_hip_ctx* ctx, const std::vector<Fasta>& fa, const std::vector<uint32_t>& seqs, float th) {
+  std::vector<uint32_t> n_rows(seqs.size(), 1), len, all;
+  size_t total = 0;
+  for (uint32_t x : seqs) {
+    len.push_back((uint32_t)fa[x].size());
+    total += fa[x].size();
+  }
+  const std::vector<uint8_t> mask(total ? total : 1, 1);
+  all.resize(total ? total : 1);
+  check(dafs_hip_consensus_structures(ctx, (uint32_t)seqs.size(), n_rows.data(), len.data(), seqs.data(), mask.data(), th, all.data(), nullptr));
+  std::map<uint32_t, VU> out;
+  size_t at = 0;
+  for (size_t k = 0; k < seqs.size(); ++k) {
+    out[seqs[k]] = VU(all.begin() + at, all.begin() + at + len[k]);
+    at += len[k];
+  }
+  return out;
+}
+
 // The common secondary structure of a final alignment (:1857-1871; no RNAalifold term here) and its output (:1876-1879,
 // :1584-1601) on os: ">SS_cons", the brackets, then the rows sorted by sequence index.  The structure is decoded over the
 // rows in the order root holds them.  fa: the context's sequences; ff: the family's, its first one at index first.  With sto,
 // also the family's Stockholm block: tree_line (nullptr: no CC line), rf (nullptr: no RF line).  With cov (--covariation), the
-// alignment's covariation table into *cov, and its cov_SS_cons line into the Stockholm block.
+// alignment's covariation table into *cov, and its cov_SS_cons line into the Stockholm block.  ss0: the first decode of the
+// alignment where the caller has it already (consensus_structures over many alignments); row_ss (--row-structures): per
+// sequence of the alignment its own structure (row_structures), written as the block's #=GR SS lines.
 void finish_alignment(dafs_hip_ctx* ctx, const Options& o, const std::vector<Fasta>& fa, ALN& root, const std::vector<Fasta>& ff,
                       uint32_t first, std::ostream& os, std::string* sto, const std::string* tree_line, const std::vector<uint8_t>* rf,
-                      std::string* cov = nullptr) {
+                      std::string* cov = nullptr, const VU* ss0 = nullptr, const std::map<uint32_t, VU>* row_ss = nullptr) {
   std::string str;
   VU ss_final;
   std::vector<double> rel, col_rel;   // --stockholm: the reliabilities of this alignment and structure
@@ -916,7 +971,8 @@ void finish_alignment(dafs_hip_ctx* ctx, const Options& o, const std::vector<Fas
     flatten(root, rs, rm);
     const uint32_t L = (uint32_t)root[0].second.size();
     VU ss(L);
-    check(dafs_hip_consensus_structure(ctx, (uint32_t)root.size(), L, rs.data(), rm.data(), o.fold_th1[0], ss.data(), nullptr, nullptr));
+    if (ss0) ss = *ss0;
+    else check(dafs_hip_consensus_structure(ctx, (uint32_t)root.size(), L, rs.data(), rm.data(), o.fold_th1[0], ss.data(), nullptr, nullptr));
     if (o.bp_update1) {  // :1863-1869: re-estimate under the decoded structure, decode again (SparseNussinov::decode(p, ss, str))
       std::vector<float> p((size_t)L * L);
       check(dafs_hip_update_basepairing(ctx, (uint32_t)root.size(), L, rs.data(), rm.data(), ss.data(), p.data()));
@@ -962,9 +1018,20 @@ void finish_alignment(dafs_hip_ctx* ctx, const Options& o, const std::vector<Fas
       names.push_back(all_names[row.first - first]);
       rr.push_back(rel.data() + rel_at[row.first]);
     }
-    check_text(dafs_host_stockholm_block(tree_line ? tree_line->c_str() : nullptr, (uint32_t)rows.size(), (uint32_t)col_rel.size(),
-                                         c_strs(names).data(), c_strs(rows).data(), rr.data(), col_rel.data(), str.c_str(),
-                                         rf ? rf->data() : nullptr, cov ? cov_chars.c_str() : nullptr, &text));
+    std::vector<std::string> rss;  // each row's own structure in the row's columns
+    for (size_t r = 0; row_ss && r < root.size(); ++r) {
+      const VU& own = row_ss->at(root[r].first);
+      std::vector<char> buf(own.size() + 1);
+      dafs_hip_make_brackets((uint32_t)own.size(), own.data(), buf.data());
+      std::string line(rows[r].size(), '.');
+      for (size_t c = 0, k = 0; c < line.size(); ++c)
+        if (rows[r][c] != '-') line[c] = buf[k++];
+      rss.push_back(line);
+    }
+    check_text(dafs_host_stockholm_block_rows(tree_line ? tree_line->c_str() : nullptr, (uint32_t)rows.size(), (uint32_t)col_rel.size(),
+                                              c_strs(names).data(), c_strs(rows).data(), rr.data(), col_rel.data(), str.c_str(),
+                                              rf ? rf->data() : nullptr, cov ? cov_chars.c_str() : nullptr,
+                                              row_ss ? c_strs(rss).data() : nullptr, &text));
     *sto = take(text);
   }
 }
@@ -1057,7 +1124,14 @@ int run_add(const Options& o, int align_model) {
   std::vector<uint8_t> rf(width, 0);
   for (uint32_t c = 0; c < C; ++c) rf[seed_col[c]] = 1;
   std::string sto, cov;
-  finish_alignment(ctx, o, fa, root, fa, 0, std::cout, o.stockholm.empty() ? nullptr : &sto, nullptr, &rf, o.covariation.empty() ? nullptr : &cov);
+  std::map<uint32_t, VU> row_ss;
+  if (o.row_structures) {
+    std::vector<uint32_t> every(m + k);
+    for (uint32_t x = 0; x < m + k; ++x) every[x] = x;
+    row_ss = row_structures(ctx, fa, every, o.fold_th1[0]);
+  }
+  finish_alignment(ctx, o, fa, root, fa, 0, std::cout, o.stockholm.empty() ? nullptr : &sto, nullptr, &rf, o.covariation.empty() ? nullptr : &cov,
+                   nullptr, o.row_structures ? &row_ss : nullptr);
   std::cout.flush();
   if (!o.stockholm.empty()) write_stockholm(o.stockholm, {sto});
   if (!o.covariation.empty()) write_covariation(o.covariation, {cov}, nullptr);
@@ -1393,7 +1467,20 @@ int align_group(dafs_hip_ctx* ctx, const Options& o, Ranks& rk, int align_model,
       const float sc = solve_node(ctx, prm, part[0], part[1], merged, o.verbose, o.bp_update);
       if (sc > s) { s = sc; root.swap(merged); }
     }
-
+  }
+  // the first decode of every family's final alignment in one call; with --row-structures, every row's own structure in another
+  std::vector<const ALN*> roots;
+  for (uint f = 0; f < F; ++f) roots.push_back(&aln[tbase[f + 1] - 1]);
+  std::vector<VU> ss0;
+  consensus_structures(ctx, roots, o.fold_th1[0], ss0);
+  std::map<uint32_t, VU> row_ss;
+  if (o.row_structures && !sto.empty()) {
+    std::vector<uint32_t> every(N);
+    for (uint x = 0; x < N; ++x) every[x] = x;
+    row_ss = row_structures(ctx, fa, every, o.fold_th1[0]);
+  }
+  for (uint f = 0; f < F; ++f) {
+    ALN& root = aln[tbase[f + 1] - 1];
     std::string tree_line;
     if (!sto.empty()) {
       std::ostringstream tl;
@@ -1401,7 +1488,7 @@ int align_group(dafs_hip_ctx* ctx, const Options& o, Ranks& rk, int align_model,
       tree_line = tl.str();
     }
     finish_alignment(ctx, o, fa, root, fams[members[f]], first[f], *out[f], sto.empty() ? nullptr : sto[f], &tree_line, nullptr,
-                     cov.empty() ? nullptr : cov[f]);
+                     cov.empty() ? nullptr : cov[f], &ss0[f], row_ss.empty() ? nullptr : &row_ss);
   }
   return 0;
 }

@@ -76,9 +76,10 @@ char pp_char(double p) {
 // holds no residue).  Labels padded to the longest plus one.  tree_line nullptr: no "#=GF CC" line; rf: per column a seed
 // column ('x') or an insert column ('.') of --seed, written as "#=GC RF" after PP_cons (nullptr: no RF line).  cov: the
 // characters of "#=GC cov_SS_cons", written directly after PP_cons (nullptr: no such line, labels as wide as without it).
+// row_ss: per row its own structure in the row's columns, written as "#=GR <name> SS" after its PP line (nullptr: no such lines).
 std::string stockholm_block(const char* tree_line, const std::vector<std::string>& names, const std::vector<std::string>& rows,
                             const double* const* rel, const double* col_rel, uint32_t len, const std::string& ss, const uint8_t* rf,
-                            const char* cov) {
+                            const char* cov, const std::vector<std::string>* row_ss) {
   size_t width = std::max(std::string("#=GC SS_cons").size(), std::string("#=GC PP_cons").size());
   if (cov) width = std::max(width, std::string("#=GC cov_SS_cons").size());
   for (const std::string& nm : names) width = std::max(width, nm.size() + 8);  // "#=GR " + name + " PP"
@@ -92,6 +93,7 @@ std::string stockholm_block(const char* tree_line, const std::vector<std::string
     for (size_t c = 0, k = 0; c < rows[r].size(); ++c)
       if (rows[r][c] != '-') pp[c] = pp_char(rel[r][k++]);
     out += label("#=GR " + names[r] + " PP") + pp + "\n";
+    if (row_ss) out += label("#=GR " + names[r] + " SS") + (*row_ss)[r] + "\n";
   }
   std::string cons(len, '.');
   for (size_t c = 0; c < len; ++c)
@@ -231,9 +233,9 @@ extern "C" int dafs_host_stockholm_names(uint32_t n, const char* const* header_s
   });
 }
 
-extern "C" int dafs_host_stockholm_block(const char* tree_line, uint32_t n, uint32_t len, const char* const* names, const char* const* rows,
-                                         const double* const* residue_rel, const double* col_rel, const char* ss, const uint8_t* rf,
-                                         const char* cov, char** block) {
+extern "C" int dafs_host_stockholm_block_rows(const char* tree_line, uint32_t n, uint32_t len, const char* const* names,
+                                              const char* const* rows, const double* const* residue_rel, const double* col_rel,
+                                              const char* ss, const uint8_t* rf, const char* cov, const char* const* row_ss, char** block) {
   return text_out(block, [&]() {
     const std::vector<std::string> nm = strings(n, names), rw = strings(n, rows);
     if (!ss || (len && !col_rel) || (n && !residue_rel)) throw kBadArgument;
@@ -241,8 +243,25 @@ extern "C" int dafs_host_stockholm_block(const char* tree_line, uint32_t n, uint
       if (rw[r].size() != len) throw "stockholm block: row " + nm[r] + " has " + std::to_string(rw[r].size()) + " columns, not " + std::to_string(len);
       if (!residue_rel[r] && rw[r] != std::string(len, '-')) throw kBadArgument;
     }
-    return stockholm_block(tree_line, nm, rw, residue_rel, col_rel, len, ss, rf, cov);
+    std::vector<std::string> rs;
+    if (row_ss) {
+      rs = strings(n, row_ss);
+      for (uint32_t r = 0; r < n; ++r) {
+        if (rs[r].size() != len)
+          throw "stockholm block: the structure of row " + nm[r] + " has " + std::to_string(rs[r].size()) + " columns, not " + std::to_string(len);
+        for (uint32_t c = 0; c < len; ++c)
+          if (rw[r][c] == '-' && rs[r][c] != '.')
+            throw "stockholm block: the structure of row " + nm[r] + " has '" + std::string(1, rs[r][c]) + "' at gap column " + std::to_string(c + 1);
+      }
+    }
+    return stockholm_block(tree_line, nm, rw, residue_rel, col_rel, len, ss, rf, cov, row_ss ? &rs : nullptr);
   });
+}
+
+extern "C" int dafs_host_stockholm_block(const char* tree_line, uint32_t n, uint32_t len, const char* const* names, const char* const* rows,
+                                         const double* const* residue_rel, const double* col_rel, const char* ss, const uint8_t* rf,
+                                         const char* cov, char** block) {
+  return dafs_host_stockholm_block_rows(tree_line, n, len, names, rows, residue_rel, col_rel, ss, rf, cov, nullptr, block);
 }
 
 extern "C" uint8_t dafs_host_cov_code(char ch) {
@@ -382,6 +401,21 @@ extern "C" uint64_t dafs_host_node_bytes(uint32_t len1, uint32_t len2) {
 // 5-15 sequences of 80-200 nt (profiles/r04_a_time_batch.json): phase-1 estimate 8.6 GB (one sub-batch), peak of the
 // progressive phase's resident nodes 6.0 GB, which dafs_host_family_bytes does not count.
 extern "C" uint64_t dafs_host_batch_bytes(void) { return 16ull << 30; }
+
+// Device memory of one alignment of n_rows rows and len columns inside dafs_hip_consensus_structures (bytes), a bound that its
+// carving checks for every chunk (capi_dd.cpp): the averaged matrix and the four tables of carve_nuss, 20 bytes a cell; the
+// rows' ranks and residue columns, 8 bytes per row and column; the structure, the candidate counters and stack (16 bytes a
+// column), the row arrays; then the constant part: the node and decoder descriptors and the score (644 bytes), the arrays'
+// tails (88), and the 256-byte alignment of the alignment's eleven arrays and of a chunk's three shared ones plus its slack,
+// which an alignment alone in its chunk carries all (under 3 900 bytes together).
+extern "C" uint64_t dafs_host_structure_bytes(uint32_t n_rows, uint32_t len) {
+  const uint64_t n = n_rows, l = len;
+  return 20 * l * l + 8 * n * l + 24 * l + 8 * n + 16 * 256 + 1024;
+}
+
+// per chunk of dafs_hip_consensus_structures.  A choice, not a limit: 2 GiB hold some 3 500 pair alignments of 170 columns,
+// a dozen times what the device keeps resident at once, and the buffer stays with the context.
+extern "C" uint64_t dafs_host_structures_batch_bytes(void) { return 2ull << 30; }
 
 // greedy, in input order: a group is closed before the item that would take it over max_bytes; an item over the budget
 // is a group of its own

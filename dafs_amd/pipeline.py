@@ -54,14 +54,15 @@ class Result:
 def run(names, seqs, ctx=None, bp=None, w=4.0, eta0=0.5, t_max=600, w_pct_a=0.25, w_pct_s=0.25, th_a=0.01,
         th_s=0.2, th_s1=None, align_model=capi.ALIGN_PROBCONS, force_iters=0, timers=None, level_sync=False, slice_iters=None,
         mp=None, skip_uncoupled_folds=True, shard=None, round_us=None, w_pct_f=0.0, bp_update=False, bp_update1=False,
-        reliability=False, covariation=False):
+        reliability=False, covariation=False, row_structures=False):
     """The whole run.  bp: per-sequence (rowptr, col, val) base-pairing rows (--fold-aux); None
     computes them with the device fold model.  mp: supplied matching probabilities (--align-aux), see Context.set_mp.
     shard: (torch.distributed module, torch device) of an initialised process group -- phase 1 (folds, pair posteriors,
     matching consistency transform) is then split over the ranks and gathered (dist.phase1_sharded); every rank
     finishes the run and holds the same result.  reliability: the result also gets .reliability and .stockholm (see
     _phase2_forest).  covariation: True or a dict with shuffles (100), seed (1), e_max (0.05): the result also gets
-    .covariation (see _final)."""
+    .covariation (see _final).  row_structures: the result also gets .row_ss and .row_ss_str, the structure of every printed
+    row on its own (see _phase2_forest)."""
     import time
     # combinations this driver does not implement are refused, not ignored (the command line, cli_main.cpp, has no level
     # batches: its --bp-update runs in the resident-node rounds and in the refinement's solve_node)
@@ -85,7 +86,7 @@ def run(names, seqs, ctx=None, bp=None, w=4.0, eta0=0.5, t_max=600, w_pct_a=0.25
     t.append(time.perf_counter())
     fam = dict(names=names, seqs=seqs, first=0, sim=sim, tree=(score, left, right))
     return _phase2_forest(ctx, own, [fam], t, w, eta0, t_max, th_a, th_s, th_s1, force_iters, level_sync, slice_iters,
-                          skip_uncoupled_folds, round_us, bp_update, bp_update1, reliability, covariation)[0]
+                          skip_uncoupled_folds, round_us, bp_update, bp_update1, reliability, covariation, row_structures)[0]
 
 
 def _phase1_local(ctx, seqs, bp, mp, align_model, th_a, w_pct_a, w_pct_s, t, w_pct_f=0.0, first=None):
@@ -182,7 +183,8 @@ def _solve_nodes(ctx, prm, take_ready, finish, level_sync=False, slice_iters=Non
 
 
 def _phase2_forest(ctx, own, fams, t, w, eta0, t_max, th_a, th_s, th_s1, force_iters, level_sync, slice_iters,
-                   skip_uncoupled_folds, round_us=None, bp_update=False, bp_update1=False, reliability=False, covariation=False):
+                   skip_uncoupled_folds, round_us=None, bp_update=False, bp_update1=False, reliability=False, covariation=False,
+                   row_structures=False):
     """The progressive phase and the output of every family of the context at once.  fams: per family a dict with names,
     seqs, first (index of its first sequence in the context), sim and tree = (score, left, right).  The guide trees form one
     forest: a node is ready when both of its children are done, whatever its family, and the ready nodes of all families
@@ -190,7 +192,13 @@ def _phase2_forest(ctx, own, fams, t, w, eta0, t_max, th_a, th_s, th_s1, force_i
     reliability: each Result also gets .reliability, the annotation of its final alignment and structure from the stores
     the progressive phase read (Context.alignment_reliability): a dict with residue (per printed row, its residues'
     values), col, pair, pair_rows and expected_accuracy; and .stockholm, that alignment as a Stockholm block with PP lines
-    (dafs_amd/stockholm.py: the block `dafs --stockholm` writes).  covariation: see _final."""
+    (dafs_amd/stockholm.py: the block `dafs --stockholm` writes).  covariation: see _final.
+    The first decode of every family's final alignment is one Context.consensus_structures call over all of them.
+    row_structures: each Result also gets .row_ss, per printed row the structure of that row alone (a uint32 array over its
+    residues, NONE for unpaired): the one-row alignment of its sequence decoded from the base-pairing store this phase read,
+    at the threshold of the common structure -- after the consistency transform that store holds what the row's homologs
+    say; and .row_ss_str, those structures laid into the rows' columns (stockholm.row_ss_str), which
+    the Stockholm block carries as `#=GR <name> SS` lines.  All rows of all families are one consensus_structures call."""
     import time
     covariation = cov_options(covariation)
     nf = len(fams)
@@ -266,12 +274,18 @@ def _phase2_forest(ctx, own, fams, t, w, eta0, t_max, th_a, th_s, th_s1, force_i
             res.skip_uncoupled_folds = bool(skip_uncoupled_folds)  # nodes without consensus pairs then carry no folding arrays
     t.append(time.perf_counter())
     th1 = th_s if th_s1 is None else th_s1
+    roots = [aln[(f, 2 * len(fm["seqs"]) - 2)] for f, fm in enumerate(fams)]
+    decoded = ctx.consensus_structures(roots, th1)
+    rows_ss = [None] * nf
+    if row_structures:
+        lens = {fm["first"] + i: len(sq) for fm in fams for i, sq in enumerate(fm["seqs"])}
+        rows_ss = _row_structures(ctx, [sidx for sidx, _ in roots], lens, th1)
     for f, (fm, res) in enumerate(zip(fams, results)):
         res.levels = levels
         res.rounds = rounds
-        n = len(fm["seqs"])
-        sidx, mask = aln[(f, 2 * n - 2)]
-        _final(ctx, res, fm["names"], fm["seqs"], fm["first"], sidx, mask, th1, bp_update1, reliability, res.tree_line, None, covariation)
+        sidx, mask = roots[f]
+        _final(ctx, res, fm["names"], fm["seqs"], fm["first"], sidx, mask, th1, bp_update1, reliability, res.tree_line, None, covariation,
+               decoded[f][1], rows_ss[f])
     t.append(time.perf_counter())
     # fold_launch: the folding is only started there; its kernels overlap `pair` and the first half of `pct_fold_tree`,
     # which also holds the wait for them
@@ -297,14 +311,32 @@ def cov_options(covariation):
     return opt
 
 
-def _final(ctx, res, names, seqs, first, sidx, mask, th1, bp_update1, reliability, tree_line, rf=None, covariation=None):
+def _row_structures(ctx, sidx_per_alignment, lens, th):
+    """Per alignment (its rows' global sequence indices) and per printed row (ascending index) the structure of that row's
+    sequence alone from the context's current base-pairing store: one Context.consensus_structures call over all of them.
+    lens: global sequence index -> length."""
+    printed = [np.sort(np.asarray(sidx, np.uint32), kind="stable") for sidx in sidx_per_alignment]
+    flat = [int(x) for rows in printed for x in rows]
+    got = ctx.consensus_structures([(np.array([x], np.uint32), np.ones((1, lens[x]), np.uint8)) for x in flat], th)
+    out, k = [], 0
+    for rows in printed:
+        out.append([ss for _, ss in got[k:k + len(rows)]])
+        k += len(rows)
+    return out
+
+
+def _final(ctx, res, names, seqs, first, sidx, mask, th1, bp_update1, reliability, tree_line, rf=None, covariation=None, ss=None,
+           row_ss=None):
     """The common structure of a final alignment (sidx: global sequence index per row, mask) and its output, into res:
     .ss, .ss_str, .rows, .output and, with reliability, .reliability and .stockholm.  names / seqs: the family's, its first
     sequence at global index `first`.  tree_line None: no tree line (pipeline.add); rf: the RF line of the Stockholm
     block.  covariation (cov_options): .covariation, the dict of Context.alignment_covariation on the printed rows and
     structure with the options' shuffles, seed and e_max beside the arrays; the Stockholm block then
-    carries a `#=GC cov_SS_cons` line."""
-    _, ss, _ = ctx.consensus_structure(sidx, mask, th1)
+    carries a `#=GC cov_SS_cons` line.  ss: the first decode of the alignment where the caller has it already (a batched
+    Context.consensus_structures call).  row_ss: per printed row its own structure (_row_structures) -> .row_ss, .row_ss_str
+    and the `#=GR <name> SS` lines of the Stockholm block."""
+    if ss is None:
+        _, ss, _ = ctx.consensus_structure(sidx, mask, th1)
     if bp_update1:  # :1863-1869: decode, re-estimate under that structure, decode again
         _, ss = ctx.nussinov(ctx.update_basepairing(sidx, mask, ss), None, th1)
     res.ss = ss
@@ -320,6 +352,9 @@ def _final(ctx, res, names, seqs, first, sidx, mask, th1, bp_update1, reliabilit
         res.rows.append(row)
         lines += ["> " + names[local], row]
     res.output = "\n".join(lines) + "\n"
+    if row_ss is not None:
+        res.row_ss = row_ss
+        res.row_ss_str = [stockholm.row_ss_str(row, x) for row, x in zip(res.rows, row_ss)]
     cov_chars = None
     if covariation:
         cv = ctx.alignment_covariation(res.rows, ss, shuffles=covariation["shuffles"], seed=covariation["seed"])
@@ -334,12 +369,12 @@ def _final(ctx, res, names, seqs, first, sidx, mask, th1, bp_update1, reliabilit
         res.reliability = rl
         sto_names = stockholm.names(names)
         res.stockholm = stockholm.block(tree_line, [sto_names[int(sidx[r]) - first] for r in order], res.rows, rl["residue"],
-                                        rl["col"], res.ss_str, rf, cov_chars)
+                                        rl["col"], res.ss_str, rf, cov_chars, None if row_ss is None else res.row_ss_str)
 
 
 def add(seed_names, seed_rows, names, seqs, ctx=None, w=4.0, eta0=0.5, t_max=600, w_pct_a=0.25, w_pct_s=0.25, th_a=0.01,
         th_s=0.2, th_s1=None, align_model=capi.ALIGN_PROBCONS, force_iters=0, slice_iters=None, skip_uncoupled_folds=True,
-        round_us=None, w_pct_f=0.0, bp_update1=False, reliability=False, covariation=False):
+        round_us=None, w_pct_f=0.0, bp_update1=False, reliability=False, covariation=False, row_structures=False):
     """Add new sequences to a fixed seed alignment without changing its columns (`dafs --seed`).
     seed_names / seed_rows: the seed's rows (letters and '.' / '-' gaps; stockholm.read_seed reads a file), checked and
     without their all-gap columns (stockholm.clean_seed).  names / seqs: the new sequences.  The options are run()'s.
@@ -350,7 +385,8 @@ def add(seed_names, seed_rows, names, seqs, ctx=None, w=4.0, eta0=0.5, t_max=600
     Returns a Result: .output (a normal run's format without the tree line: rows in context order), .rows, .ss, .ss_str,
     .z (per new sequence its column map into the seed), .rf (per merged column True for a seed column), .dd_log
     ({j: (iterations, violated, ncbp, score)}), .dd_memory, .seconds; with reliability, .reliability and .stockholm (no CC
-    line, a `#=GC RF` line); with covariation (as in run), .covariation."""
+    line, a `#=GC RF` line); with covariation (as in run), .covariation; with row_structures (as in run), .row_ss and
+    .row_ss_str."""
     import time
     covariation = cov_options(covariation)
     seed_names, seed_rows = stockholm.clean_seed(seed_names, seed_rows)
@@ -393,8 +429,9 @@ def add(seed_names, seed_rows, names, seqs, ctx=None, w=4.0, eta0=0.5, t_max=600
         res.rf = rf
         res.dd_log = {j: (o["iterations"], o["violated"], o["ncbp"], o["score"]) for j, o in enumerate(outs)}
         res.dd_memory = dd_memory
-        _final(ctx, res, all_names, all_seqs, 0, sidx, np.concatenate([mask[m:], mask[:m]]), th_s if th_s1 is None else th_s1,
-               bp_update1, reliability, None, rf, covariation)
+        th1 = th_s if th_s1 is None else th_s1
+        _final(ctx, res, all_names, all_seqs, 0, sidx, np.concatenate([mask[m:], mask[:m]]), th1, bp_update1, reliability, None, rf,
+               covariation, None, _row_structures(ctx, [sidx], dict(enumerate(map(len, all_seqs))), th1)[0] if row_structures else None)
         t.append(time.perf_counter())
         res.seconds = dict(phase1=t[3] - t[0], nodes=t[4] - t[3], final=t[5] - t[4], total=t[5] - t[0])
     finally:
@@ -471,7 +508,7 @@ def run_batch(families, ctx=None, max_bytes=None, **kw):
             t.append(time.perf_counter())
             res = _phase2_forest(ctx, False, fams, t, opts["w"], opts["eta0"], opts["t_max"], opts["th_a"], opts["th_s"], opts["th_s1"],
                                  opts["force_iters"], opts["level_sync"], opts["slice_iters"], opts["skip_uncoupled_folds"], opts["round_us"],
-                                 opts["bp_update"], opts["bp_update1"], opts["reliability"], opts["covariation"])
+                                 opts["bp_update"], opts["bp_update1"], opts["reliability"], opts["covariation"], opts["row_structures"])
             for k, r in zip(grp, res):
                 out[k] = r
     finally:
@@ -563,7 +600,7 @@ def pairwise(names, seqs, pairs=None, ctx=None, max_bytes=None, **opts):
     """All pairwise structural alignments of a set of sequences (`dafs --pairwise`).  pairs: (x, y)
     with x < y, default every pair in row-major order.  opts: the options of run() except mp / bp / shard.  Each pair's
     Result is, bit for bit, what run([names[x], names[y]], [seqs[x], seqs[y]], **opts) gives (.output, .dd_log, .ss, .rows,
-    .sim and, with reliability, .reliability / .stockholm).
+    .sim and, with reliability, .reliability / .stockholm; with row_structures, .row_ss / .row_ss_str from the pair's stores).
 
     Phase 1 (folds, all-pairs posteriors, no transforms) runs once over the N sequences in a source context of its own; the
     pairs go in chunks of at most max_bytes of estimated device memory (pair_chunks; default DEFAULT_BATCH_BYTES) through
@@ -626,7 +663,7 @@ def pairwise(names, seqs, pairs=None, ctx=None, max_bytes=None, **opts):
                     for j, (x, y) in enumerate(cp)]
             res = _phase2_forest(ctx, False, fams, t, o["w"], o["eta0"], o["t_max"], o["th_a"], o["th_s"], o["th_s1"], o["force_iters"],
                                  o["level_sync"], o["slice_iters"], o["skip_uncoupled_folds"], o["round_us"], o["bp_update"],
-                                 o["bp_update1"], o["reliability"])
+                                 o["bp_update1"], o["reliability"], False, o["row_structures"])
             secs["transforms"] += t[3] - t[0]
             secs["nodes"] += t[4] - t[3]
             secs["final"] += t[5] - t[4]
@@ -642,4 +679,29 @@ def pairwise(names, seqs, pairs=None, ctx=None, max_bytes=None, **opts):
             ctx.close()
     secs["total"] = time.perf_counter() - t_start
     out.seconds = secs
+    return out
+
+
+def fold_each(names, seqs, th=0.2, ctx=None):
+    """Every sequence folded alone: CONTRAfold posteriors (Context.fold_posteriors, no consistency transform), then the MEA
+    structure of every sequence's own base-pairing rows at threshold th, all in one Context.consensus_structures call.
+    Returns one Result per sequence with .name, .ss (uint32 per residue, NONE for unpaired), .ss_str and .score."""
+    names, seqs = list(names), list(seqs)
+    if not seqs or len(names) != len(seqs):
+        raise ValueError("pipeline.fold_each: at least one sequence and one name per sequence")
+    own = ctx is None
+    if own:
+        ctx = capi.Context(0)
+    try:
+        ctx.set_sequences(seqs)
+        ctx.fold_posteriors(0.01)
+        got = ctx.consensus_structures([(np.array([x], np.uint32), np.ones((1, len(s)), np.uint8)) for x, s in enumerate(seqs)], th)
+    finally:
+        if own:
+            ctx.close()
+    out = []
+    for nm, (score, ss) in zip(names, got):
+        res = Result()
+        res.name, res.ss, res.ss_str, res.score = nm, ss, capi.make_brackets(ss), score
+        out.append(res)
     return out

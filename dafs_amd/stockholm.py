@@ -5,6 +5,7 @@ host text code (dafs_amd/csrc/host_text.cpp), which the `dafs` command line call
     #=GF CC <the tree line>
     <name>           <row, '-' for gaps>
     #=GR <name> PP   <PP characters>
+    #=GR <name> SS   <the row's own structure, with row structures>
     ...
     #=GC SS_cons     <bracket string>
     #=GC PP_cons     <PP characters of the column reliabilities>
@@ -47,12 +48,20 @@ def cov_ss_cons(ss, pair_e, e_max=0.05):
     return capi.host_text(capi._cov_ss_cons, len(ss), ss.ctypes.data, e.ctypes.data, float(e_max))
 
 
-def block(tree_line, row_names, rows, residue_rel, col_rel, ss_str, rf=None, cov=None):
+def row_ss_str(row, ss):
+    """A row's own structure (ss over its residues: partner index at the left one, 0xFFFFFFFF otherwise) laid into the row's
+    columns: the bracket characters of capi.make_brackets at the residues' columns, '.' at gaps"""
+    chars = iter(capi.make_brackets(ss))
+    return "".join("." if ch == "-" else next(chars) for ch in row)
+
+
+def block(tree_line, row_names, rows, residue_rel, col_rel, ss_str, rf=None, cov=None, row_ss=None):
     """One alignment.  row_names / rows / residue_rel: per printed row (stdout order) its Stockholm name, its text and its
     residues' reliabilities; col_rel: per column; a column without residues gets '.' in PP_cons.  tree_line None: no
     `#=GF CC` line.  rf: per column True for a seed column ('x'), False for an insert column ('.'), written as `#=GC RF`
     after PP_cons; None: no RF line.  cov: the cov_SS_cons characters (cov_ss_cons), written as `#=GC cov_SS_cons` directly after
-    PP_cons; None: no such line, and the labels are as wide as without it."""
+    PP_cons; None: no such line, and the labels are as wide as without it.  row_ss: per row its own structure in the row's
+    columns (row_ss_str), written as `#=GR <name> SS` after the row's PP line; None: no such lines."""
     row_names, rows = list(row_names), list(rows)
     col = np.ascontiguousarray(col_rel, np.float64)
     rel = [np.ascontiguousarray(r, np.float64) for r in residue_rel]
@@ -64,9 +73,11 @@ def block(tree_line, row_names, rows, residue_rel, col_rel, ss_str, rf=None, cov
     if rf8 is not None and rf8.shape != col.shape:
         raise ValueError("stockholm.block: rf needs one entry per column")
     text = [None if t is None else t.encode("latin-1") for t in (tree_line, ss_str, cov)]
-    return capi.host_text(capi._stockholm_block, text[0], len(rows), len(col), capi.c_strings(row_names), capi.c_strings(rows),
+    if row_ss is not None and len(row_ss) != len(rows):
+        raise ValueError("stockholm.block: one structure per row")
+    return capi.host_text(capi._stockholm_block_rows, text[0], len(rows), len(col), capi.c_strings(row_names), capi.c_strings(rows),
                           (C.c_void_p * max(len(rel), 1))(*[r.ctypes.data for r in rel]), col.ctypes.data, text[1],
-                          None if rf8 is None else rf8.ctypes.data, text[2])
+                          None if rf8 is None else rf8.ctypes.data, text[2], None if row_ss is None else capi.c_strings(list(row_ss)))
 
 
 class SeedError(ValueError):

@@ -261,6 +261,13 @@ int dafs_host_stockholm_names(uint32_t n, const char* const* headers, char** nam
 int dafs_host_stockholm_block(const char* tree_line, uint32_t n, uint32_t len, const char* const* names, const char* const* rows,
                               const double* const* residue_rel, const double* col_rel, const char* ss, const uint8_t* rf,
                               const char* cov, char** block);
+/* The same block with per-row structures: row_ss[r] (NULL array: none, the block of
+ * dafs_host_stockholm_block) is row r's structure laid into its columns -- a bracket character of dafs_hip_make_brackets at a
+ * residue's column, '.' elsewhere -- and is written as "#=GR <name> SS" after the row's PP line.  A string whose length is
+ * not len, or with anything but '.' at a gap column, is refused (DAFS_HIP_EINVAL). */
+int dafs_host_stockholm_block_rows(const char* tree_line, uint32_t n, uint32_t len, const char* const* names, const char* const* rows,
+                                   const double* const* residue_rel, const double* col_rel, const char* ss, const uint8_t* rf,
+                                   const char* cov, const char* const* row_ss, char** block);
 /* The code of a residue for dafs_hip_alignment_covariation: A 0, C 1, G 2, U / T 3 in either case, everything else 4 */
 uint8_t dafs_host_cov_code(char residue);
 /* The cov_SS_cons characters: '2' at both columns of every pair of ss with pair_e <= e_max (a NaN never is), '.' elsewhere */
@@ -285,6 +292,10 @@ int dafs_host_seed_clean(uint32_t n, const char* const* names, const char* const
 uint64_t dafs_host_family_bytes(uint32_t n, const uint32_t* lens);
 uint64_t dafs_host_node_bytes(uint32_t len1, uint32_t len2);
 uint64_t dafs_host_batch_bytes(void);
+/* Estimated device memory (bytes) of one alignment of n_rows rows and len columns inside dafs_hip_consensus_structures, and the
+ * default budget of one of its chunks. */
+uint64_t dafs_host_structure_bytes(uint32_t n_rows, uint32_t len);
+uint64_t dafs_host_structures_batch_bytes(void);
 int dafs_host_pack_greedy(uint32_t n, const uint64_t* sizes, uint64_t max_bytes, uint32_t* group_of);
 
 /* ------------------------------------------------------------------------------------------
@@ -414,6 +425,15 @@ int dafs_hip_nodes_demotions(dafs_hip_ctx* ctx, uint32_t* n);
  * averaged base-pairing matrix -> SparseNussinov::decode(p,ss,str) with threshold th. */
 int dafs_hip_consensus_structure(dafs_hip_ctx* ctx, uint32_t n, uint32_t len, const uint32_t* seq, const uint8_t* mask,
                                  float th, uint32_t* ss, float* score, float* p_out);
+/* The same for nalign alignments in one call: alignment a has n_rows[a] rows of len[a] columns; seq
+ * holds the rows' sequence indices of all alignments one after another, mask their n_rows[a] * len[a] bytes, ss their len[a]
+ * entries; score[nalign] may be NULL.  Alignment a's results are, bit for bit, those of dafs_hip_consensus_structure on its
+ * rows in the same order.  Rows of different alignments may belong to different families, and a sequence to many alignments.
+ * Everything is checked before the first launch: DAFS_HIP_EINVAL leaves ss and score untouched.  nalign = 0 does nothing.
+ * The alignments run in chunks under a budget of device memory (dafs_host_structures_batch_bytes; DAFS_HIP_CS_BATCH_BYTES
+ * overrides it), which does not change any result. */
+int dafs_hip_consensus_structures(dafs_hip_ctx* ctx, uint32_t nalign, const uint32_t* n_rows, const uint32_t* len, const uint32_t* seq,
+                                  const uint8_t* mask, float th, uint32_t* ss, float* score);
 
 /* DAFS::update_basepairing_probability (src/dafs.cpp:609-712; options --bp-update and --bp-update1), without the RNAalifold
  * term: the sequences of the alignment (rows seq / mask as in dafs_node_input) are folded again with CONTRAfold under the
