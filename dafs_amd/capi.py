@@ -98,6 +98,8 @@ _fourway_consistency = _sig("dafs_hip_fourway_consistency", C.c_int, [C.c_void_p
 _fold_begin = _sig("dafs_hip_fold_posteriors_begin", C.c_int, [C.c_void_p, C.c_int, C.c_float])
 _fold_end = _sig("dafs_hip_fold_posteriors_end", C.c_int, [C.c_void_p])
 _pairs_from = _sig("dafs_hip_pairs_from", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, u32p, u32p])
+_families_from = _sig("dafs_hip_families_from", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, u32p, u32p])
+_consistency_match_pairs = _sig("dafs_hip_consistency_match_pairs", C.c_int, [C.c_void_p, C.c_float, C.c_uint64, C.c_void_p])
 
 
 class NodeInput(C.Structure):
@@ -165,6 +167,8 @@ _cov_code = _sig("dafs_host_cov_code", C.c_uint8, [C.c_char])
 _cov_ss_cons = _sig("dafs_host_cov_ss_cons", C.c_int, [C.c_uint32, C.c_void_p, C.c_void_p, C.c_double, _text])
 _covariation_table = _sig("dafs_host_covariation_table", C.c_int, [C.c_uint32, C.c_uint32] + [C.c_void_p] * 10 + [_text])
 _pairwise_table = _sig("dafs_host_pairwise_table", C.c_int, [C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, _strs] + [C.c_void_p] * 3 + [_text])
+_seed_table = _sig("dafs_host_seed_table", C.c_int, [C.c_uint32, _strs] + [C.c_void_p] * 4 + [_text])
+_seed_each_bytes = _sig("dafs_host_seed_each_bytes", C.c_uint64, [C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32])
 _seed_parse = _sig("dafs_host_seed_parse", C.c_int, [C.c_char_p, C.c_size_t, u32p, _text, _text])
 _seed_clean = _sig("dafs_host_seed_clean", C.c_int, [C.c_uint32, _strs, _strs, _text])
 _family_bytes = _sig("dafs_host_family_bytes", C.c_uint64, [C.c_uint32, C.c_void_p])
@@ -427,6 +431,27 @@ class Context:
         lens[0::2], lens[1::2] = src._lens[px], src._lens[py]
         self._lens = lens
         self._first = np.arange(0, 2 * len(px) + 1, 2, dtype=np.uint32)
+
+    def families_from(self, src, families):
+        """dafs_hip_families_from: this context becomes the families `families` (per family the strictly ascending indices
+        of its members among src's sequences; a sequence may be in many), with the raw stores and similarity blocks those
+        inputs give, gathered from src on the device.  src: a one-family context after fold_posteriors and an
+        align_posteriors over a prefix of its pairs that holds every pair the families need, left unchanged."""
+        fams = [np.ascontiguousarray(f, np.uint32).reshape(-1) for f in families]
+        first = np.zeros(len(fams) + 1, np.uint32)
+        first[1:] = np.cumsum([len(f) for f in fams])
+        member = np.ascontiguousarray(np.concatenate(fams) if fams else np.zeros(0, np.uint32), np.uint32)
+        if len(member) == 0:
+            member = np.zeros(1, np.uint32)  # a valid pointer: the library refuses the empty family itself
+        check(_families_from(self._h, src._h, len(fams), first.ctypes.data_as(u32p), member.ctypes.data_as(u32p)))
+        self._lens = src._lens[member[:int(first[-1])]]
+        self._first = first
+
+    def consistency_match_pairs(self, w_pct_a, pair_ids):
+        """dafs_hip_consistency_match_pairs: the matching transform for the strictly ascending pair ids `pair_ids` of the
+        context only; the other pairs of the relaxed store stay empty and alignment_reliability refuses to read it."""
+        ids = np.ascontiguousarray(pair_ids, np.uint64).reshape(-1)
+        check(_consistency_match_pairs(self._h, w_pct_a, len(ids), ids.ctypes.data if len(ids) else None))
 
     def phase1_sharded(self, rank, world, align_model, th_a, w_pct_a, w_pct_s, fold_th, allgather, fold_model=0):
         """dafs_hip_phase1_sharded: phase 1 on rank `rank` of `world` (every rank has set all the sequences, two at least);

@@ -36,6 +36,7 @@ extern "C" int dafs_hip_align_posteriors(dafs_hip_ctx* c, int model, float th, u
   const uint64_t np = pair_end - pair_begin;
   mp_store& st = c->mp[0];
   st.valid = false;
+  st.listed = false;
   c->mp[1].valid = false;
   c->cur_mp = 0;
   c->sim.clear();
@@ -161,6 +162,7 @@ extern "C" int dafs_hip_set_mp(dafs_hip_ctx* c, const uint32_t* nnz, const uint3
   const uint64_t np = (uint64_t)n * (n - 1) / 2;
   mp_store& st = c->mp[0];
   st.valid = false;
+  st.listed = false;
   c->mp[1].valid = false;
   c->cur_mp = 0;
   c->sim.clear();
@@ -266,6 +268,7 @@ extern "C" int dafs_hip_mp_install(dafs_hip_ctx* c, int relaxed, const uint32_t*
   const uint64_t np = (uint64_t)n * (n - 1) / 2;
   mp_store& st = c->mp[relaxed];
   st.valid = false;
+  st.listed = false;
   if (relaxed == 0) { c->mp[1].valid = false; c->cur_mp = 0; c->sim.clear(); }
   st.pair_x.resize(np); st.pair_y.resize(np); st.task_of_pair.resize(np); st.rp_by_pair.resize(np);
   st.n_tasks = np;

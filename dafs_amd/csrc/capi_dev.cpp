@@ -60,6 +60,7 @@ extern "C" int dafs_hip_mp_install_dev(dafs_hip_ctx* c, int relaxed, const uint3
   const uint64_t np = (uint64_t)n * (n - 1) / 2;
   mp_store& st = c->mp[relaxed];
   st.valid = false;
+  st.listed = false;
   if (relaxed == 0) { c->mp[1].valid = false; c->cur_mp = 0; c->sim.clear(); }
   st.pair_x.resize(np); st.pair_y.resize(np); st.task_of_pair.resize(np); st.rp_by_pair.resize(np);
   st.n_tasks = np;

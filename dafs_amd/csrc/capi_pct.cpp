@@ -114,8 +114,9 @@ void pct_task_order(const uint32_t* pair_x, const uint32_t* pair_y, const uint32
 // may be run in either order, e.g. the matching transform while the folding kernels are still busy)
 // fourway: the matching part runs DAFS::relax_fourway_consistency (weight w_pct_a) instead, and its result becomes the
 // un-relaxed store (dafs_hip_fourway_consistency below)
+// list: the matching transform's output pairs as nlist strictly ascending pair ids instead of the range (not with fourway)
 static int consistency_parts(dafs_hip_ctx* c, float w_pct_a, float w_pct_s, int which, uint64_t pair_begin = 0, uint64_t pair_end = 0,
-                             bool fourway = false) {
+                             bool fourway = false, uint64_t nlist = 0, const uint64_t* list = nullptr) {
   if (!c || c->len.empty()) return DAFS_HIP_EINVAL;
   if (hip_check(hipSetDevice(c->device))) return DAFS_HIP_ENODEV;
   const uint32_t n = (uint32_t)c->len.size();
@@ -123,6 +124,15 @@ static int consistency_parts(dafs_hip_ctx* c, float w_pct_a, float w_pct_s, int 
   mp_store& raw = c->mp[0];
   if (!raw.valid || raw.n_tasks != all || (c->sim.empty() && !fourway)) return DAFS_HIP_EINVAL;
   if (fourway && !c->bp[0].valid) return DAFS_HIP_EINVAL;
+  std::vector<uint32_t> plist;  // pair ids are 32-bit (family_layout::build)
+  if (list) {
+    if (fourway || nlist == 0) return DAFS_HIP_EINVAL;
+    plist.resize(nlist);
+    for (uint64_t q = 0; q < nlist; ++q) {
+      if (list[q] >= all || (q && list[q] <= list[q - 1])) return DAFS_HIP_EINVAL;
+      plist[q] = (uint32_t)list[q];
+    }
+  }
   const uint32_t max_len = c->max_len();
   mp_store_dev mpv = c->mp_view(raw);
   int rc;
@@ -141,7 +151,8 @@ static int consistency_parts(dafs_hip_ctx* c, float w_pct_a, float w_pct_s, int 
   if ((rc = c->counters.reserve(4))) return rc;
   if (pair_end == 0) pair_end = all;
   if (pair_begin > pair_end || pair_end > all) return DAFS_HIP_EINVAL;
-  const bool shard = pair_begin != 0 || pair_end != all;  // only these output pairs are computed, the others stay empty
+  if (list) { pair_begin = 0; pair_end = nlist; }  // the launches walk the positions of the list
+  const bool shard = list || pair_begin != 0 || pair_end != all;  // only these output pairs are computed, the others stay empty
 
   if (which & 1) c->cur_bp = 0;
   if ((which & 1) && w_pct_s != 0.0f) {
@@ -191,6 +202,7 @@ static int consistency_parts(dafs_hip_ctx* c, float w_pct_a, float w_pct_s, int 
   if ((which & 2) && w_pct_a != 0.0f) {
     mp_store& out = c->mp[1];
     out.valid = false;
+    out.listed = list != nullptr;
     out.n_tasks = all;
     out.pair_x = raw.pair_x;
     out.pair_y = raw.pair_y;
@@ -205,6 +217,7 @@ static int consistency_parts(dafs_hip_ctx* c, float w_pct_a, float w_pct_s, int 
     if ((rc = out.pair_nnz.reserve(all))) return rc;
     if ((rc = c->d_pair_x.upload(raw.pair_x.data(), all, c->stream))) return rc;
     if ((rc = c->d_pair_y.upload(raw.pair_y.data(), all, c->stream))) return rc;
+    if (list && (rc = c->pct_list.upload(plist.data(), nlist, c->stream))) return rc;
     uint64_t cap = std::max<uint64_t>(raw.pool_used * 2 + 1024, out.pool_cap_hint);
     for (int attempt = 0;; ++attempt) {
       if ((rc = out.col.reserve(cap))) return rc;
@@ -218,6 +231,7 @@ static int consistency_parts(dafs_hip_ctx* c, float w_pct_a, float w_pct_s, int 
       pct_match_args a;
       memset(&a, 0, sizeof a);
       a.in = mpv; a.sim = c->d_sim.ptr; a.pair_x = c->d_pair_x.ptr; a.pair_y = c->d_pair_y.ptr;
+      a.pair_list = list ? c->pct_list.ptr : nullptr;
       a.npairs = (uint32_t)all; a.w_pct = w_pct_a;
       a.rp_off = out.rp_off.ptr; a.rowptr_pool = out.rowptr_pool.ptr; a.col = out.col.ptr; a.val = out.val.ptr;
       a.pool_top = c->counters.ptr; a.pool_cap = cap; a.pair_off = out.pair_off.ptr; a.pair_nnz = out.pair_nnz.ptr;
@@ -229,7 +243,8 @@ static int consistency_parts(dafs_hip_ctx* c, float w_pct_a, float w_pct_s, int 
         std::vector<uint64_t> toff;
         uint64_t cells = 0, p1 = p0;
         while (p1 < pair_end) {
-          const uint64_t need = (uint64_t)c->len[raw.pair_x[p1]] * c->len[raw.pair_y[p1]];
+          const uint64_t pr = list ? plist[p1] : p1;
+          const uint64_t need = (uint64_t)c->len[raw.pair_x[pr]] * c->len[raw.pair_y[pr]];
           if (p1 > p0 && cells + need > kTileFloats) break;
           toff.push_back(cells);
           cells += need;
@@ -245,8 +260,8 @@ static int consistency_parts(dafs_hip_ctx* c, float w_pct_a, float w_pct_s, int 
         a.wg_task = nullptr; a.wg_tasks = 0;
         // DAFS_HIP_PCT_YORDER=1 (tuning aid): workgroups ordered by (y, row block, x) and dealt to the XCDs in contiguous ranges.
         // Measured slower than the plain 2-D grid (N=128: 13.3 against 12.8 ms for the stage, N=256: 135 against 120): the
-        // gathers are not what binds the kernel, so the default stays the 2-D grid.
-        if (!fourway && getenv("DAFS_HIP_PCT_YORDER")) {
+        // gathers are not what binds the kernel, so the default stays the 2-D grid.  A pair list always takes the 2-D grid.
+        if (!fourway && !list && getenv("DAFS_HIP_PCT_YORDER")) {
           std::vector<uint2> order;
           pct_task_order(raw.pair_x.data(), raw.pair_y.data(), c->len.data(), n, p0, (uint32_t)cnt, order);
           if ((rc = c->pct_tasks.upload(order.data(), order.size(), c->stream))) return rc;  // synchronises
@@ -291,4 +306,10 @@ extern "C" int dafs_hip_consistency_bp(dafs_hip_ctx* c, float w_pct_s) { return 
 extern "C" int dafs_hip_consistency_match_range(dafs_hip_ctx* c, float w_pct_a, uint64_t pair_begin, uint64_t pair_end) {
   if (w_pct_a == 0.0f) return DAFS_HIP_EINVAL;
   return consistency_parts(c, w_pct_a, 0.0f, 2, pair_begin, pair_end);
+}
+// The same for an arbitrary strictly ascending list of output pairs: the relaxed store is marked as holding listed pairs only
+// (mp_store::listed), which dafs_hip_alignment_reliability refuses to read.
+extern "C" int dafs_hip_consistency_match_pairs(dafs_hip_ctx* c, float w_pct_a, uint64_t npairs, const uint64_t* pair_ids) {
+  if (w_pct_a == 0.0f || npairs == 0 || !pair_ids) return DAFS_HIP_EINVAL;
+  return consistency_parts(c, w_pct_a, 0.0f, 2, 0, 0, false, npairs, pair_ids);
 }

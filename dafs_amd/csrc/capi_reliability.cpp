@@ -63,6 +63,7 @@ extern "C" int dafs_hip_alignment_reliability(dafs_hip_ctx* c, uint32_t n, uint3
   const int m = mp_relaxed < 0 ? c->cur_mp : mp_relaxed;
   const int b = bp_relaxed < 0 ? c->cur_bp : bp_relaxed;
   if (n > 1 && (!c->mp[m].valid || c->mp[m].n_tasks != c->fam.npairs())) return DAFS_HIP_EINVAL;
+  if (n > 1 && c->mp[m].listed) return DAFS_HIP_EINVAL;  // dafs_hip_consistency_match_pairs: the unlisted pairs are empty, not zero
   if (ss && !c->bp[b].valid) return DAFS_HIP_EINVAL;
 
   // device workspace, carved from c->work

@@ -75,6 +75,8 @@ struct Options {
   std::string stockholm;  // --stockholm FILE
   bool row_structures = false;  // --row-structures: a #=GR SS line per row of the Stockholm blocks
   std::string seed;       // --seed SEED: add FILE's sequences to this alignment
+  bool seed_each = false;       // --seed-each: with --seed, every sequence of FILE added on its own
+  std::string seed_scores;      // --seed-scores OUT
   bool pairwise = false;  // --pairwise: every pair of FILE's sequences aligned as a two-sequence run
   std::string pairwise_scores;  // --pairwise-scores OUT
   std::string covariation;      // --covariation OUT
@@ -111,6 +113,13 @@ const char* kHelp =
     "                        as dafs prints it) without changing its columns; the output has no tree line, and\n"
     "                        --stockholm adds a #=GC RF line (x: seed column).  Not with -r, --bp-update, --devices,\n"
     "                        --align-aux, --fold-aux or --save-*-aux\n"
+    "      --seed-each       With --seed: add every sequence of FILE on its own, as if it were the only one in FILE, from one\n"
+    "                        shared computation of the posteriors: per sequence a line \"==> j <==\" (1-based, file order) and\n"
+    "                        then what dafs --seed SEED prints for a file of that sequence alone; --stockholm writes one block\n"
+    "                        per sequence.  Without it the new sequences of FILE inform one another\n"
+    "      --seed-scores OUT With --seed-each: a tab-separated table, one line per new sequence:\n"
+    "                        j name length matched inserted score iterations (residues in seed columns and in columns of\n"
+    "                        their own; the objective and iterations of the sequence's node)\n"
     "      --pairwise        Align every pair of the one FILE's sequences (at least two) as two-sequence runs, the pairs\n"
     "                        in row-major order: per pair a line \"==> i j <==\" (1-based input indices) and then what\n"
     "                        dafs prints for a file of those two sequences; --stockholm writes one block per pair.\n"
@@ -165,6 +174,7 @@ Options parse(int argc, char** argv) {
       {"bp-update", {0, false}}, {"bp-update1", {0, false}}, {"fold-aux", {0, true}}, {"save-align-aux", {0, true}},
       {"save-fold-aux", {0, true}}, {"device", {0, true}}, {"devices", {0, true}}, {"input", {0, true}},
       {"stockholm", {0, true}}, {"row-structures", {0, false}}, {"seed", {0, true}}, {"pairwise", {0, false}}, {"pairwise-scores", {0, true}},
+      {"seed-each", {0, false}}, {"seed-scores", {0, true}},
       {"covariation", {0, true}}, {"cov-shuffles", {0, true}}, {"cov-seed", {0, true}}};
   std::map<char, std::string> shorts;
   for (const auto& kv : spec)
@@ -234,6 +244,11 @@ Options parse(int argc, char** argv) {
       if (value.empty()) throw std::string("--seed needs a file name");
       o.seed = value;
     }
+    else if (name == "seed-each") o.seed_each = true;
+    else if (name == "seed-scores") {
+      if (value.empty()) throw std::string("--seed-scores needs a file name");
+      o.seed_scores = value;
+    }
     else if (name == "pairwise") o.pairwise = true;
     else if (name == "pairwise-scores") {
       if (value.empty()) throw std::string("--pairwise-scores needs a file name");
@@ -263,6 +278,8 @@ Options parse(int argc, char** argv) {
   if (o.pairwise && (!o.covariation.empty() || o.cov_shuffles_given || o.cov_seed_given))
     throw std::string("--pairwise: two rows carry no covariation; --covariation, --cov-shuffles and --cov-seed cannot be combined with --pairwise");
   if (!o.pairwise_scores.empty() && !o.pairwise) throw std::string("--pairwise-scores needs --pairwise");
+  if (o.seed_each && o.seed.empty()) throw std::string("--seed-each needs --seed");
+  if (!o.seed_scores.empty() && !o.seed_each) throw std::string("--seed-scores needs --seed-each");
   if (o.pairwise) {  // every pair is a two-sequence run of its own: nothing that reads or writes one run's whole state
     if (o.refinement_given) throw std::string("--pairwise: -r cannot be combined with --pairwise");
     if (!o.seed.empty()) throw std::string("--pairwise: --seed cannot be combined with --pairwise");
@@ -1138,6 +1155,170 @@ int run_add(const Options& o, int align_model) {
   return 0;
 }
 
+// `dafs --seed SEED --seed-each FILE` (pipeline.add_each is the Python twin): every sequence of FILE added
+// to the seed as run_add adds a file of that sequence alone.  Phase 1 runs once in a source context over the seed's m sequences
+// and then FILE's k: the folds and the posteriors of the pairs with a seed sequence on the left, no transform.  The new
+// sequences go in chunks under dafs_host_batch_bytes() (dafs_host_seed_each_bytes each) through a second context, where
+// dafs_hip_families_from gathers the chunk's families seed + [new]; then the transforms -- the matching transform for the pairs
+// (seed, new) alone unless --stockholm's reliabilities read the seed-seed rows --, one node per family in shared rounds,
+// run_add's merge per family and the structures of the chunk in one call.
+int run_add_each(const Options& o, int align_model) {
+  std::vector<std::string> snames, srows;
+  read_seed(o.seed, snames, srows);
+  std::vector<Fasta> added;
+  Fasta::load(added, o.input.c_str());
+  if (added.empty()) throw "no sequences in the input";
+  const uint32_t m = (uint32_t)srows.size(), k = (uint32_t)added.size(), C = (uint32_t)srows[0].size(), n = m + 1;
+  std::vector<Fasta> seed;
+  std::vector<uint8_t> smask((size_t)m * C, 0);
+  std::vector<uint32_t> seed_lens(m), lens(k);
+  for (uint32_t r = 0; r < m; ++r) {
+    std::string sq;
+    for (uint32_t c = 0; c < C; ++c)
+      if (srows[r][c] != '-') { sq += srows[r][c]; smask[(size_t)r * C + c] = 1; }
+    seed.push_back(Fasta(snames[r], sq));
+    seed_lens[r] = (uint32_t)sq.size();
+  }
+  for (uint32_t j = 0; j < k; ++j) lens[j] = added[j].size();
+
+  dafs_hip_ctx* src = nullptr;
+  check(dafs_hip_create(o.device, &src));
+  Guard src_guard{src};
+  {
+    std::vector<Fasta> all(seed);
+    all.insert(all.end(), added.begin(), added.end());
+    set_sequences(src, all);
+  }
+  check(dafs_hip_fold_posteriors_begin(src, DAFS_FOLD_CONTRAFOLD, kCutoff));
+  // the pairs (x, y) with x < m are the first m (m + k) - m (m + 1) / 2 pair ids
+  const int rc_align = dafs_hip_align_posteriors(src, align_model, o.align_th, 0, (uint64_t)m * (m + k) - (uint64_t)m * (m + 1) / 2);
+  const int rc_fold = dafs_hip_fold_posteriors_end(src);
+  check(rc_align);
+  check(rc_fold);
+  dafs_hip_ctx* ctx = nullptr;
+  check(dafs_hip_create(o.device, &ctx));
+  Guard guard{ctx};
+
+  std::vector<uint64_t> bytes(k);
+  for (uint32_t j = 0; j < k; ++j) bytes[j] = dafs_host_seed_each_bytes(m, seed_lens.data(), C, lens[j]);
+  std::vector<uint32_t> chunk_of(k);
+  check(dafs_host_pack_greedy(k, bytes.data(), dafs_host_batch_bytes(), chunk_of.data()));
+  dafs_dd_params prm = dd_params_of(o);
+  prm.skip_uncoupled_folds = o.verbose == 0 ? 1 : 0;  // as run_add
+  const bool listed = o.stockholm.empty() && o.align_pct != 0.0f;  // the reliabilities of --stockholm read the seed-seed rows
+  std::vector<uint32_t> matched(k, 0);
+  std::vector<double> score(k, 0.0);
+  std::vector<int64_t> iterations(k, 0);
+  std::vector<std::string> sto_blocks, cov_tables, cov_headers;
+  for (uint32_t j0 = 0; j0 < k;) {
+    uint32_t j1 = j0;
+    while (j1 < k && chunk_of[j1] == chunk_of[j0]) ++j1;
+    const uint32_t nf = j1 - j0;
+    // family f: the seed's sequences at f n .. f n + m - 1, the new one at f n + m
+    std::vector<uint32_t> first(nf + 1), member;
+    std::vector<Fasta> fa;
+    for (uint32_t f = 0; f < nf; ++f) {
+      first[f] = f * n;
+      for (uint32_t r = 0; r < m; ++r) member.push_back(r);
+      member.push_back(m + j0 + f);
+      fa.insert(fa.end(), seed.begin(), seed.end());
+      fa.push_back(added[j0 + f]);
+    }
+    first[nf] = nf * n;
+    check(dafs_hip_families_from(ctx, src, nf, first.data(), member.data()));
+    if (o.fourway != 0.0f) check(dafs_hip_fourway_consistency(ctx, o.fourway));
+    check(dafs_hip_consistency_bp(ctx, o.fold_pct));
+    if (listed) {  // the pairs (s, new) of every family: local id s n - s (s + 1) / 2 + m - s - 1
+      std::vector<uint64_t> ids;
+      for (uint32_t f = 0; f < nf; ++f)
+        for (uint64_t s = 0; s < m; ++s) ids.push_back((uint64_t)f * ((uint64_t)n * m / 2) + s * n - s * (s + 1) / 2 + m - s - 1);
+      check(dafs_hip_consistency_match_pairs(ctx, o.align_pct, ids.size(), ids.data()));
+    } else {
+      check(dafs_hip_consistency_match(ctx, o.align_pct));
+    }
+
+    // the nf nodes: all opened in the first round
+    std::vector<VU> zs(nf);
+    bool opened = false;
+    run_rounds(ctx, prm, o.verbose, [&]() {
+      std::vector<std::pair<size_t, NodeJob> > ready(opened ? 0 : nf);
+      for (uint32_t f = 0; f < ready.size(); ++f) {
+        NodeJob& jb = ready[f].second;
+        ready[f].first = f;
+        jb.s1.assign(1, f * n + m);
+        jb.m1.assign(lens[j0 + f], 1);
+        jb.s2.resize(m);
+        for (uint32_t r = 0; r < m; ++r) jb.s2[r] = f * n + r;
+        jb.m2 = smask;
+        node_job(ctx, jb, false, prm.th_s);
+      }
+      opened = true;
+      return ready;
+    }, [&](size_t f, NodeJob& jb) {
+      score[j0 + f] = jb.out.score;
+      iterations[j0 + f] = jb.out.iterations;
+      zs[f].swap(jb.z);
+    });
+
+    // per family run_add's merge of its one map; the rows new sequence, then seed rows
+    std::vector<ALN> roots(nf);
+    std::vector<std::vector<uint8_t> > rfs(nf);
+    for (uint32_t f = 0; f < nf; ++f) {
+      const uint32_t len = lens[j0 + f];
+      for (uint32_t z : zs[f]) matched[j0 + f] += z != DAFS_HIP_NONE ? 1 : 0;
+      std::vector<uint32_t> seed_col(C), res_col(len ? len : 1);
+      uint32_t width = 0;
+      check(dafs_host_merge_added(C, 1, &len, zs[f].data(), seed_col.data(), res_col.data(), &width));
+      std::vector<bool> msk(width, false);
+      for (uint32_t i = 0; i < len; ++i) msk[res_col[i]] = true;
+      roots[f].push_back(std::make_pair(f * n + m, msk));
+      for (uint32_t r = 0; r < m; ++r) {
+        std::vector<bool> row(width, false);
+        for (uint32_t c = 0; c < C; ++c) row[seed_col[c]] = smask[(size_t)r * C + c] != 0;
+        roots[f].push_back(std::make_pair(f * n + r, row));
+      }
+      rfs[f].assign(width, 0);
+      for (uint32_t c = 0; c < C; ++c) rfs[f][seed_col[c]] = 1;
+    }
+    std::vector<const ALN*> ptrs;
+    for (const ALN& a : roots) ptrs.push_back(&a);
+    std::vector<VU> ss;
+    consensus_structures(ctx, ptrs, o.fold_th1[0], ss);
+    std::map<uint32_t, VU> row_ss;
+    if (o.row_structures) {
+      std::vector<uint32_t> every(nf * n);
+      for (uint32_t x = 0; x < nf * n; ++x) every[x] = x;
+      row_ss = row_structures(ctx, fa, every, o.fold_th1[0]);
+    }
+    for (uint32_t f = 0; f < nf; ++f) {
+      const std::vector<Fasta> ff(fa.begin() + (size_t)f * n, fa.begin() + (size_t)(f + 1) * n);
+      std::ostringstream os;
+      std::string sto, cov;
+      finish_alignment(ctx, o, fa, roots[f], ff, f * n, os, o.stockholm.empty() ? nullptr : &sto, nullptr, &rfs[f],
+                       o.covariation.empty() ? nullptr : &cov, &ss[f], o.row_structures ? &row_ss : nullptr);
+      std::cout << "==> " << j0 + f + 1 << " <==" << std::endl << os.str();
+      if (!o.stockholm.empty()) sto_blocks.push_back(sto);
+      if (!o.covariation.empty()) { cov_tables.push_back(cov); cov_headers.push_back(std::to_string(j0 + f + 1)); }
+    }
+    j0 = j1;
+  }
+  std::cout.flush();
+  if (!o.stockholm.empty()) write_stockholm(o.stockholm, sto_blocks);
+  if (!o.covariation.empty()) write_covariation(o.covariation, cov_tables, &cov_headers);
+  if (!o.seed_scores.empty()) {
+    std::ofstream ts(o.seed_scores.c_str(), std::ios::binary);
+    if (!ts.is_open()) throw "--seed-scores: cannot open " + o.seed_scores;
+    std::vector<std::string> headers;
+    for (const Fasta& s : added) headers.push_back(s.name());
+    char* text = nullptr;
+    check_text(dafs_host_seed_table(k, c_strs(headers).data(), lens.data(), matched.data(), score.data(), iterations.data(), &text));
+    ts << take(text);
+    ts.flush();
+    if (!ts) throw "--seed-scores: cannot write " + o.seed_scores;
+  }
+  return 0;
+}
+
 // `dafs --pairwise FILE` (pipeline.pairwise is the Python twin).  Phase 1 runs once over FILE's N
 // sequences in a source context, the folding beside the all-pairs posteriors and no transform; the pairs, row-major, go in
 // chunks under dafs_host_batch_bytes() through a second context, where dafs_hip_pairs_from gathers a chunk's two-sequence
@@ -1255,7 +1436,7 @@ int run(const Options& o, Ranks& rk) {
     if (!o.no_alifold) std::cerr << "note: RNAalifold is not available in this build; running as with --no-alifold" << std::endl;
     if (!o.fold_model_given && o.fold_aux.empty()) std::cerr << "note: default folding model is CONTRAfold in this build" << std::endl;
   }
-  if (!o.seed.empty()) return run_add(o, align_model);
+  if (!o.seed.empty()) return o.seed_each ? run_add_each(o, align_model) : run_add(o, align_model);
   if (o.pairwise) return run_pairwise(o, align_model);
 
   // one family per input file

@@ -206,31 +206,32 @@ void clean_seed(const std::vector<std::string>& names, std::vector<std::string>&
   }
 }
 
+// per sequence of a file, in input order: the first whitespace-separated word of its header, "seq<k>" (k 1-based) for an
+// empty one, ".2", ".3", ... appended to the second, third, ... occurrence of a name
+std::vector<std::string> stockholm_names(const std::vector<std::string>& headers) {
+  std::vector<std::string> out;
+  std::map<std::string, int> seen;
+  for (size_t k = 0; k < headers.size(); ++k) {
+    const std::string& h = headers[k];
+    size_t b = 0;
+    while (b < h.size() && is_space(h[b])) ++b;
+    size_t e = b;
+    while (e < h.size() && !is_space(h[e])) ++e;
+    const std::string nm = e > b ? h.substr(b, e - b) : "seq" + std::to_string(k + 1);
+    const int c = ++seen[nm];
+    out.push_back(c == 1 ? nm : nm + "." + std::to_string(c));
+  }
+  return out;
+}
+
 }  // namespace
 
 extern "C" void dafs_host_free(void* p) { free(p); }
 
 extern "C" char dafs_host_pp_char(double p) { return pp_char(p); }
 
-// per sequence of a file, in input order: the first whitespace-separated word of its header, "seq<k>" (k 1-based) for an
-// empty one, ".2", ".3", ... appended to the second, third, ... occurrence of a name
 extern "C" int dafs_host_stockholm_names(uint32_t n, const char* const* header_strs, char** names) {
-  return text_out(names, [&]() {
-    const std::vector<std::string> headers = strings(n, header_strs);
-    std::vector<std::string> out;
-    std::map<std::string, int> seen;
-    for (size_t k = 0; k < headers.size(); ++k) {
-      const std::string& h = headers[k];
-      size_t b = 0;
-      while (b < h.size() && is_space(h[b])) ++b;
-      size_t e = b;
-      while (e < h.size() && !is_space(h[e])) ++e;
-      const std::string nm = e > b ? h.substr(b, e - b) : "seq" + std::to_string(k + 1);
-      const int c = ++seen[nm];
-      out.push_back(c == 1 ? nm : nm + "." + std::to_string(c));
-    }
-    return joined(out);
-  });
+  return text_out(names, [&]() { return joined(stockholm_names(strings(n, header_strs))); });
 }
 
 extern "C" int dafs_host_stockholm_block_rows(const char* tree_line, uint32_t n, uint32_t len, const char* const* names,
@@ -341,6 +342,22 @@ extern "C" int dafs_host_pairwise_table(uint64_t npairs, const uint32_t* x, cons
   });
 }
 
+// --seed-scores: one line per new sequence of a --seed-each run, named by the Stockholm rule over the file's headers
+extern "C" int dafs_host_seed_table(uint32_t n, const char* const* headers, const uint32_t* length, const uint32_t* matched, const double* score,
+                                    const int64_t* iterations, char** table) {
+  return text_out(table, [&]() {
+    const std::vector<std::string> nm = stockholm_names(strings(n, headers));
+    if (n && (!length || !matched || !score || !iterations)) throw kBadArgument;
+    std::ostringstream ts;
+    for (uint32_t j = 0; j < n; ++j) {
+      if (matched[j] > length[j]) throw std::string("seed table: more matched residues than residues");
+      ts << j + 1 << "\t" << nm[j] << "\t" << length[j] << "\t" << matched[j] << "\t" << length[j] - matched[j] << "\t" << fmt9d(score[j]) << "\t"
+         << iterations[j] << "\n";
+    }
+    return ts.str();
+  });
+}
+
 extern "C" int dafs_host_seed_parse(const char* text, size_t bytes, uint32_t* n, char** names, char** rows) {
   if (rows) *rows = nullptr;
   const int rc = text_out(names, [&]() {
@@ -395,6 +412,16 @@ extern "C" uint64_t dafs_host_node_bytes(uint32_t len1, uint32_t len2) {
   const uint64_t l1 = len1, l2 = len2;
   return 44 * (l1 * l1 + l2 * l2) + 26 * (l1 + 1) * (l2 + 1) + 8 * (l1 + 63) * (l2 + 64) + 512 * (l1 + 1) * ((l2 + 2048) / 2048) + 128 * (l1 + l2) +
          (1 << 14);
+}
+
+// Device memory of one new sequence of a --seed-each run: the phase-1 stores of its family, the m seed
+// sequences and itself, and its one node, the leaf against the seed's `seed_columns` columns, resident for the whole progressive
+// phase of its chunk.
+extern "C" uint64_t dafs_host_seed_each_bytes(uint32_t m, const uint32_t* seed_lens, uint32_t seed_columns, uint32_t new_len) {
+  if (m && !seed_lens) return 0;
+  std::vector<uint32_t> lens(seed_lens, seed_lens + m);
+  lens.push_back(new_len);
+  return dafs_host_family_bytes(m + 1, lens.data()) + dafs_host_node_bytes(new_len, seed_columns);
 }
 
 // per sub-batch or chunk, against the 288 GB of an MI355X.  A choice, not a measured limit.  Measured on 512 families of

@@ -12,6 +12,9 @@ struct pct_match_args {
   const float* sim;       // N*N similarity matrix (diagonal 1)
   const uint32_t* pair_x; // output pair p -> (x, y), row-major x<y
   const uint32_t* pair_y;
+  // optional: the output pairs of the launches as a list of pair ids (dafs_hip_consistency_match_pairs); workgroup k of a launch
+  // then takes pair pair_list[pair0 + k] instead of pair pair0 + k.  Null = the contiguous range.  Not read by the four-way kernel.
+  const uint32_t* pair_list;
   uint32_t npairs;
   float w_pct;            // reference -p (w_pct_a_)
   // output store; task == row-major pair id
@@ -69,6 +72,7 @@ void pct_task_order(const uint32_t* pair_x, const uint32_t* pair_y, const uint32
 // ent2[e] = {col[e], bits of val[e]} for e < n: the interleaved copy the row kernels gather from (mp_store_dev::ent2)
 int pct_interleave_launch(const uint32_t* col, const float* val, uint2* ent2, uint64_t n, hipStream_t st);
 int pct_ident_launch(uint2* ident2, uint32_t* ident_rp, uint32_t n, hipStream_t st);  // ident2[k] = {k, bits of 1.0f}, ident_rp[k] = k for k < n
+// the output pairs [pair0, pair0 + count), or with a.pair_list the pairs a.pair_list[pair0 .. pair0 + count)
 int pct_match_launch(pct_match_args a, uint32_t max_len, uint32_t pair0, uint32_t count, hipStream_t st);
 int pct_bp_launch(pct_bp_args a, uint32_t max_len, hipStream_t st);
 // DAFS::relax_fourway_consistency (dafs.cpp:377-444) for the pairs [pair0, pair0 + count): same outputs as pct_match_launch

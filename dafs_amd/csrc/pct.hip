@@ -237,7 +237,7 @@ __global__ __launch_bounds__(256) void k_pct_rows(pct_match_args a, uint32_t pai
     pl = tk.x; rb = tk.y;
     if (pl == 0xFFFFFFFFu) return;  // padding of the XCD interleave
   }
-  const uint32_t p = pair0 + pl;
+  const uint32_t p = a.pair_list ? a.pair_list[pair0 + pl] : pair0 + pl;  // wave-uniform
   const uint32_t x = a.pair_x[p], y = a.pair_y[p];
   const uint32_t L1 = a.in.len[x], L2 = a.in.len[y];
   const uint32_t row0 = rb * PCT_ROWS_PER_WG;
@@ -367,7 +367,7 @@ __global__ __launch_bounds__(256) void k_pct_emit(pct_match_args a, uint32_t pai
   const int wave = (int)(tid >> 6), lane = (int)(tid & 63);
   uint32_t* rowptr = s_ptrs;
   uint32_t* colptr = s_ptrs + a.max_len + 2;
-  const uint32_t p = pair0 + blockIdx.x;
+  const uint32_t p = a.pair_list ? a.pair_list[pair0 + blockIdx.x] : pair0 + blockIdx.x;
   const uint32_t x = a.pair_x[p], y = a.pair_y[p];
   const uint32_t L1 = a.in.len[x], L2 = a.in.len[y];
   const float* tile = a.tile + a.tile_off[blockIdx.x];

@@ -682,6 +682,160 @@ def pairwise(names, seqs, pairs=None, ctx=None, max_bytes=None, **opts):
     return out
 
 
+# ------------------------------------------------------------------------------------- each new sequence against a seed
+def seed_each_bytes(seed_lens, columns, new_len):
+    """Device memory of one new sequence of add_each (bytes; dafs_host_seed_each_bytes): family_bytes of the seed's lengths and
+    its own, plus node_bytes(new_len, columns) for its one node against the seed's columns."""
+    lens = np.ascontiguousarray([int(x) for x in seed_lens], np.uint32)
+    return int(capi._seed_each_bytes(len(lens), lens.ctypes.data, int(columns), int(new_len)))
+
+
+def seed_scores_tsv(names, each):
+    """The table of `dafs --seed SEED --seed-each --seed-scores OUT` (dafs_host_seed_table) for the result of add_each on the
+    new sequences `names`: per sequence "j<TAB>name<TAB>length<TAB>matched<TAB>inserted<TAB>score<TAB>iterations" with 1-based j,
+    the Stockholm name (stockholm.names over the new sequences' headers) and the floats as %.9g."""
+    names = list(names)
+    if len(names) != len(each.results):
+        raise ValueError("seed_scores_tsv: one name per new sequence")
+    arrs = [np.ascontiguousarray(a, t) for a, t in ((each.lengths, np.uint32), (each.matched, np.uint32), (each.score, np.float64),
+                                                    (each.iterations, np.int64))]
+    return capi.host_text(capi._seed_table, len(names), capi.c_strings(names), *[a.ctypes.data for a in arrs])
+
+
+class AddEach:
+    pass
+
+
+def add_each(seed_names, seed_rows, names, seqs, ctx=None, max_bytes=None, **opts):
+    """Each new sequence added to a fixed seed alignment on its own (`dafs --seed SEED --seed-each`).
+    opts: the options of add().  results[j] is, bit for bit, what add(seed_names, seed_rows, [names[j]], [seqs[j]], **opts)
+    returns (.output, .rows, .ss, .ss_str, .z, .rf, .dd_log and, when asked, .reliability / .stockholm / .row_ss* /
+    .covariation), so neither the order of the new sequences nor which others are present matters.
+
+    Phase 1 runs once, in a source context of its own over the m seed sequences and then the k new ones: the folds and the pair
+    posteriors of the pairs with a seed sequence on the left (a prefix of the pair ids; no new-new pair), no transform.  The new
+    sequences go in chunks, in input order, of at most max_bytes of estimated device memory (seed_each_bytes; default
+    DEFAULT_BATCH_BYTES) through `ctx`: Context.families_from builds the chunk's families seed + [new] on the device, then
+    the transforms -- the matching transform only for the pairs (seed, new) the node reads
+    (Context.consistency_match_pairs), unless reliability asks for the seed-seed rows too -- one node per family, all in
+    shared rounds, the merges, and the structures of the whole chunk in one Context.consensus_structures call.  Returns an
+    object with .results (one Result per new sequence, in input order), .score and .iterations (the node's final objective
+    and iteration count, dd_log's 4th and 1st entries), .lengths, .matched (residues that landed in seed columns), .chunks
+    (indices per chunk), .dd_memory (per chunk the nodes' (reserved, in use, peak) bytes) and .seconds (phase1, gather,
+    transforms, nodes, final, total)."""
+    import time
+    o = {k: p.default for k, p in inspect.signature(add).parameters.items() if k not in ("seed_names", "seed_rows", "names", "seqs", "ctx")}
+    unknown = set(opts) - set(o)
+    if unknown:
+        raise TypeError("pipeline.add_each: unknown options %s" % sorted(unknown))
+    o.update(opts)
+    covariation = cov_options(o["covariation"])
+    seed_names, seed_rows = stockholm.clean_seed(seed_names, seed_rows)
+    names, seqs = list(names), list(seqs)
+    if not seqs or len(names) != len(seqs):
+        raise ValueError("pipeline.add_each: at least one new sequence and one name per sequence")
+    if any(len(sq) == 0 for sq in seqs):
+        raise ValueError("pipeline.add_each: a new sequence has no residues")
+    budget = DEFAULT_BATCH_BYTES if max_bytes is None else int(max_bytes)
+    if budget < 0:
+        raise ValueError("pipeline.add_each: max_bytes is negative")
+    m, k = len(seed_rows), len(seqs)
+    n = m + 1  # sequences of a family: the seed's, then the new one
+    seed_seqs = [r.replace("-", "") for r in seed_rows]
+    seed_mask = np.array([[ch != "-" for ch in r] for r in seed_rows], np.uint8)
+    columns = seed_mask.shape[1]
+    seed_lens = [len(sq) for sq in seed_seqs]
+    chunks = pack_families([seed_each_bytes(seed_lens, columns, len(sq)) for sq in seqs], budget)
+    th1 = o["th_s"] if o["th_s1"] is None else o["th_s1"]
+    prm = capi.dd_params(w=o["w"], eta0=o["eta0"], th_a=o["th_a"], th_s=o["th_s"], t_max=o["t_max"], force_iters=o["force_iters"],
+                         skip_uncoupled_folds=1 if o["skip_uncoupled_folds"] else 0)
+    # the pairs (s, new) of a family, the only ones its node reads: local id s n - s (s + 1) / 2 + m - s - 1
+    node_pairs = np.array([s * n - s * (s + 1) // 2 + m - s - 1 for s in range(m)], np.uint64)
+    listed = not o["reliability"] and o["w_pct_a"] != 0.0  # the reliability annotation reads the seed-seed relaxed rows
+    out = AddEach()
+    out.chunks, out.results, out.dd_memory = chunks, [None] * k, []
+    out.score = np.full(k, np.nan, np.float32)
+    out.iterations = np.full(k, -1, np.int64)
+    out.lengths = np.array([len(sq) for sq in seqs], np.uint32)
+    out.matched = np.zeros(k, np.uint32)
+    secs = dict(phase1=0.0, gather=0.0, transforms=0.0, nodes=0.0, final=0.0)
+    own = ctx is None
+    t_start = time.perf_counter()
+    src = capi.Context(0 if own else ctx.device_index)
+    try:
+        if own:
+            ctx = capi.Context(0)
+        # phase 1 once: the folding beside the pair posteriors of the pairs (x, y) with x < m, no transform
+        src.set_sequences(seed_seqs + seqs)
+        src.fold_begin(0.01)
+        try:
+            src.align_posteriors(o["align_model"], o["th_a"], 0, m * (m + k) - m * (m + 1) // 2, fetch=False)
+        finally:
+            src.fold_end()
+        secs["phase1"] = time.perf_counter() - t_start
+        for chunk in chunks:
+            t = [time.perf_counter()]
+            ctx.families_from(src, [list(range(m)) + [m + j] for j in chunk])
+            t.append(time.perf_counter())
+            if o["w_pct_f"] != 0.0:
+                ctx.fourway_consistency(o["w_pct_f"])
+            ctx.consistency_bp(o["w_pct_s"])
+            if listed:
+                ctx.consistency_match_pairs(o["w_pct_a"], np.concatenate([node_pairs + np.uint64(f * (n * m // 2)) for f in range(len(chunk))]))
+            else:
+                ctx.consistency_match(o["w_pct_a"])
+            t.append(time.perf_counter())
+            nodes = [(f, (np.array([f * n + m], np.uint32), np.ones((1, len(seqs[j])), np.uint8), np.arange(f * n, f * n + m, dtype=np.uint32),
+                          seed_mask)) for f, j in enumerate(chunk)]
+            outs = [None] * len(chunk)
+            batches = iter([nodes])  # every node is ready in the first round, none later
+
+            def finish(f, res, dims):
+                outs[f] = res
+            _, _, dd_memory, _ = _solve_nodes(ctx, prm, lambda: next(batches, []), finish, slice_iters=o["slice_iters"], round_us=o["round_us"])
+            out.dd_memory.append(dd_memory)
+            t.append(time.perf_counter())
+            # per family add()'s merge of its one map; rows in the order new sequence, seed rows
+            alns, rfs = [], []
+            for f, j in enumerate(chunk):
+                seed_col, res_col, width = capi.merge_added(columns, [outs[f]["z"]])
+                mask = np.zeros((n, width), np.uint8)
+                mask[0, res_col[0]] = 1
+                mask[1:, seed_col] = seed_mask
+                rf = np.zeros(width, bool)
+                rf[seed_col] = True
+                alns.append((np.concatenate([[f * n + m], np.arange(f * n, f * n + m)]).astype(np.uint32), mask))
+                rfs.append(rf)
+            decoded = ctx.consensus_structures(alns, th1)
+            rows_ss = [None] * len(chunk)
+            if o["row_structures"]:
+                lens = {f * n + i: ln for f, j in enumerate(chunk) for i, ln in enumerate(seed_lens + [len(seqs[j])])}
+                rows_ss = _row_structures(ctx, [sidx for sidx, _ in alns], lens, th1)
+            for f, j in enumerate(chunk):
+                res = Result()
+                oj = outs[f]
+                res.z = [oj["z"]]
+                res.rf = rfs[f]
+                res.dd_log = {0: (oj["iterations"], oj["violated"], oj["ncbp"], oj["score"])}
+                res.dd_memory = dd_memory
+                _final(ctx, res, seed_names + [names[j]], seed_seqs + [seqs[j]], f * n, alns[f][0], alns[f][1], th1, o["bp_update1"],
+                       o["reliability"], None, rfs[f], covariation, decoded[f][1], rows_ss[f])
+                out.results[j] = res
+                out.score[j] = oj["score"]
+                out.iterations[j] = oj["iterations"]
+                out.matched[j] = int((np.asarray(oj["z"]) != NONE).sum())
+            t.append(time.perf_counter())
+            for key, a, b in (("gather", 0, 1), ("transforms", 1, 2), ("nodes", 2, 3), ("final", 3, 4)):
+                secs[key] += t[b] - t[a]
+    finally:
+        src.close()
+        if own and ctx is not None:
+            ctx.close()
+    secs["total"] = time.perf_counter() - t_start
+    out.seconds = secs
+    return out
+
+
 def fold_each(names, seqs, th=0.2, ctx=None):
     """Every sequence folded alone: CONTRAfold posteriors (Context.fold_posteriors, no consistency transform), then the MEA
     structure of every sequence's own base-pairing rows at threshold th, all in one Context.consensus_structures call.

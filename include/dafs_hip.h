@@ -281,6 +281,11 @@ int dafs_host_covariation_table(uint32_t n, uint32_t len, const uint8_t* code, c
  * %.9g; iterations is signed (-1: a pair that was not asked) */
 int dafs_host_pairwise_table(uint64_t npairs, const uint32_t* x, const uint32_t* y, uint32_t nnames, const char* const* names,
                              const double* sim, const double* score, const int64_t* iterations, char** table);
+/* The --seed-scores table of a --seed-each run: per new sequence j the line "j+1 name length matched
+ * length-matched score iterations", tab-separated, floats as %.9g; the names are dafs_host_stockholm_names of the n headers.
+ * matched[j] > length[j] is refused (DAFS_HIP_EINVAL). */
+int dafs_host_seed_table(uint32_t n, const char* const* headers, const uint32_t* length, const uint32_t* matched, const double* score,
+                         const int64_t* iterations, char** table);
 /* The seed reader of --seed.  _parse: the bytes of a Stockholm or aligned-FASTA file into *n names and
  * rows as the file holds them.  _clean: the checks (an empty seed, rows of unequal length, a character that is neither a letter
  * nor a gap, a row without residues), then the rows without their all-gap columns, '-' for every gap. */
@@ -292,6 +297,9 @@ int dafs_host_seed_clean(uint32_t n, const char* const* names, const char* const
 uint64_t dafs_host_family_bytes(uint32_t n, const uint32_t* lens);
 uint64_t dafs_host_node_bytes(uint32_t len1, uint32_t len2);
 uint64_t dafs_host_batch_bytes(void);
+/* Estimated device memory (bytes) of one new sequence of a --seed-each run: dafs_host_family_bytes of the m seed lengths and
+ * new_len, plus dafs_host_node_bytes(new_len, seed_columns) */
+uint64_t dafs_host_seed_each_bytes(uint32_t m, const uint32_t* seed_lens, uint32_t seed_columns, uint32_t new_len);
 /* Estimated device memory (bytes) of one alignment of n_rows rows and len columns inside dafs_hip_consensus_structures, and the
  * default budget of one of its chunks. */
 uint64_t dafs_host_structure_bytes(uint32_t n_rows, uint32_t len);
@@ -317,6 +325,13 @@ int dafs_hip_fourway_consistency(dafs_hip_ctx* ctx, float w_pct_f);
  * output pair is independent of the others, src/dafs.cpp:265-315): the shard of one rank of a multi-GPU run.  The
  * other pairs of the relaxed store stay empty until the gathered whole is installed with dafs_hip_mp_install. */
 int dafs_hip_consistency_match_range(dafs_hip_ctx* ctx, float w_pct_a, uint64_t pair_begin, uint64_t pair_end);
+/* The same for a list of output pairs: npairs >= 1 strictly ascending pair ids of the context (families one after another,
+ * row-major inside each).  The listed pairs' relaxed rows are those of dafs_hip_consistency_match, bit for bit; the others are
+ * empty (zero counts, offsets and row pointers).  The relaxed store is marked as holding listed pairs only until another call
+ * produces it: dafs_hip_alignment_reliability refuses to read it (DAFS_HIP_EINVAL) instead of taking the empty pairs for zero
+ * probabilities.  DAFS_HIP_EINVAL also for w_pct_a = 0, an empty list, an id that does not ascend or is not a pair of the
+ * context, and a missing or partial un-relaxed store. */
+int dafs_hip_consistency_match_pairs(dafs_hip_ctx* ctx, float w_pct_a, uint64_t npairs, const uint64_t* pair_ids);
 
 /* ------------------------------------------------------------------------------------------
  * L1: decoder plugins on dense row-major matrices (host buffers).
@@ -520,6 +535,19 @@ int dafs_hip_set_bp_dev(dafs_hip_ctx* ctx, uint32_t nblocks, const uint32_t* seq
  * different devices (or the same context), src with more than one family, missing or partial stores, a folding in flight,
  * a pair with x >= y or y >= N. */
 int dafs_hip_pairs_from(dafs_hip_ctx* dst, const dafs_hip_ctx* src, uint32_t npairs, const uint32_t* pair_x, const uint32_t* pair_y);
+/* The same gather for arbitrary families (dafs --seed-each, pipeline.add_each): dst becomes nfam
+ * families, family f holding the sequences member[first[f] .. first[f + 1]) of src (host arrays; first[0] = 0, no empty
+ * family, members strictly ascending within a family, so that a dst pair is the src pair in the same orientation).  A sequence
+ * may be a member of many families; a family of one has no pair and the similarity block [[1]].  src: one family of N
+ * sequences with its base-pairing store and an un-relaxed matching store that covers a row-major prefix [0, n_tasks) of its
+ * pairs (dafs_hip_align_posteriors(ctx, model, th, 0, pair_end); the whole set is the special case): every pair a family needs
+ * must lie in it.  The pairs (x, y) with x < m are the ids below m N - m (m + 1) / 2.  dst's sequences, families, raw stores
+ * (un-relaxed, pair p = task p) and similarity blocks are, bit for bit, those of a context built directly on the listed
+ * sequences with that partition, dafs_hip_fold_posteriors and dafs_hip_align_posteriors.  src is not modified.
+ * DAFS_HIP_EINVAL (dst left usable): null or equal contexts or different devices, src with more than one family, a missing
+ * store, a folding in flight on either context, nfam = 0, first[0] != 0, an empty family, a member >= N or not ascending, a
+ * pair that is not in src's store.  DAFS_HIP_EOVERFLOW: more than 2^31 dst sequences or pairs. */
+int dafs_hip_families_from(dafs_hip_ctx* dst, const dafs_hip_ctx* src, uint32_t nfam, const uint32_t* first, const uint32_t* member);
 
 /* ---- phase 1 of DAFS::run on one rank of a multi-GPU run (src/dafs.cpp:1787-1827) ----
  * One process per GPU; every rank has called dafs_hip_set_sequences with all N sequences.  Rank r folds the sequences
