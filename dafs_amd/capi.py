@@ -97,6 +97,9 @@ _consistency_bp = _sig("dafs_hip_consistency_bp", C.c_int, [C.c_void_p, C.c_floa
 _fourway_consistency = _sig("dafs_hip_fourway_consistency", C.c_int, [C.c_void_p, C.c_float])
 _fold_begin = _sig("dafs_hip_fold_posteriors_begin", C.c_int, [C.c_void_p, C.c_int, C.c_float])
 _fold_end = _sig("dafs_hip_fold_posteriors_end", C.c_int, [C.c_void_p])
+_fold_constrained_begin = _sig("dafs_hip_fold_posteriors_constrained_begin", C.c_int, [C.c_void_p, C.c_int, C.c_float, C.POINTER(C.c_char_p)])
+_fold_constrained = _sig("dafs_hip_fold_posteriors_constrained", C.c_int, [C.c_void_p, C.c_int, C.c_float, C.POINTER(C.c_char_p)])
+_structure_support = _sig("dafs_hip_structure_support", C.c_int, [C.c_void_p, C.c_uint32] + [C.c_void_p] * 9)
 _pairs_from = _sig("dafs_hip_pairs_from", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, u32p, u32p])
 _families_from = _sig("dafs_hip_families_from", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, u32p, u32p])
 _consistency_match_pairs = _sig("dafs_hip_consistency_match_pairs", C.c_int, [C.c_void_p, C.c_float, C.c_uint64, C.c_void_p])
@@ -168,6 +171,11 @@ _cov_ss_cons = _sig("dafs_host_cov_ss_cons", C.c_int, [C.c_uint32, C.c_void_p, C
 _covariation_table = _sig("dafs_host_covariation_table", C.c_int, [C.c_uint32, C.c_uint32] + [C.c_void_p] * 10 + [_text])
 _pairwise_table = _sig("dafs_host_pairwise_table", C.c_int, [C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, _strs] + [C.c_void_p] * 3 + [_text])
 _seed_table = _sig("dafs_host_seed_table", C.c_int, [C.c_uint32, _strs] + [C.c_void_p] * 4 + [_text])
+_seed_table_support = _sig("dafs_host_seed_table_support", C.c_int, [C.c_uint32, _strs] + [C.c_void_p] * 8 + [_text])
+_seed_parse_structure = _sig("dafs_host_seed_parse_structure", C.c_int, [C.c_char_p, C.c_size_t, u32p, C.POINTER(C.c_int), _text, _text, _text])
+_seed_clean_structure = _sig("dafs_host_seed_clean_structure", C.c_int, [C.c_uint32, _strs, _strs, C.c_char_p, C.c_void_p, u32p, _text])
+_fold_complementary = _sig("dafs_host_fold_complementary", C.c_int, [C.c_char, C.c_char])
+_row_constraint = _sig("dafs_host_row_constraint", C.c_int, [C.c_uint32, C.c_void_p, C.c_void_p, C.c_char_p, C.c_char_p])
 _seed_each_bytes = _sig("dafs_host_seed_each_bytes", C.c_uint64, [C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32])
 _seed_parse = _sig("dafs_host_seed_parse", C.c_int, [C.c_char_p, C.c_size_t, u32p, _text, _text])
 _seed_clean = _sig("dafs_host_seed_clean", C.c_int, [C.c_uint32, _strs, _strs, _text])
@@ -386,13 +394,32 @@ class Context:
             e0 += n
         return out
 
-    def fold_posteriors(self, th=0.01, model=0):
-        """CONTRAfold base-pairing posteriors of every sequence -> the un-relaxed bp store"""
-        check(_fold_posteriors(self._h, model, th))
+    def _constraints(self, constraints):
+        """per sequence a constraint string or None as the char* array of the library"""
+        cons = list(constraints)
+        if self._lens is None or len(cons) != len(self._lens):
+            raise ValueError("fold constraints: one entry (a string or None) per sequence of the context")
+        bs = [None if x is None else (x.encode("latin-1") if isinstance(x, str) else bytes(x)) for x in cons]
+        if any(b is not None and b"\0" in b for b in bs):
+            raise ValueError("fold constraints: a string holds a NUL byte")
+        return (C.c_char_p * len(bs))(*bs)
 
-    def fold_begin(self, th=0.01, model=0):
-        """enqueue the folding kernels on their own stream; fold_end() waits and fills the bp store"""
-        check(_fold_begin(self._h, model, th))
+    def fold_posteriors(self, th=0.01, model=0, constraints=None):
+        """CONTRAfold base-pairing posteriors of every sequence -> the un-relaxed bp store.  constraints: per sequence None
+        or "" (folded free) or len characters of "?.()" (dafs_hip_fold_posteriors_constrained); a refused string raises
+        DafsHipError with the sequence index in its text."""
+        if constraints is None:
+            check(_fold_posteriors(self._h, model, th))
+        else:
+            check(_fold_constrained(self._h, model, th, self._constraints(constraints)))
+
+    def fold_begin(self, th=0.01, model=0, constraints=None):
+        """enqueue the folding kernels on their own stream; fold_end() waits and fills the bp store.  constraints: as in
+        fold_posteriors"""
+        if constraints is None:
+            check(_fold_begin(self._h, model, th))
+        else:
+            check(_fold_constrained_begin(self._h, model, th, self._constraints(constraints)))
 
     def fold_end(self):
         check(_fold_end(self._h))
@@ -637,6 +664,32 @@ class Context:
         cuts = np.cumsum(lens)[:-1]
         return [(sc, x) for sc, x in zip(score, np.split(ss[:int(lens.sum())], cuts))]
 
+    def structure_support(self, alignments, structures):
+        """dafs_hip_structure_support: how far every row of each alignment keeps the structure given for it.  alignments: a
+        list of (seq, mask) as consensus_structures takes them; structures: per alignment its ss (left column -> right
+        column, NONE otherwise).  Returns per alignment a dict of arrays with one entry per row, in the given row order: both,
+        canonical, half (uint32) and expected (float64), read from the base-pairing store the progressive phase reads."""
+        als = [(np.ascontiguousarray(s, np.uint32).reshape(-1), np.ascontiguousarray(m, np.uint8)) for s, m in alignments]
+        sss = [np.ascontiguousarray(x, np.uint32).reshape(-1) for x in structures]
+        if any(m.ndim != 2 or m.shape[0] != len(s) for s, m in als):
+            raise ValueError("structure_support: every alignment is (seq[n], mask[n, len])")
+        if len(sss) != len(als) or any(len(x) != m.shape[1] for x, (_, m) in zip(sss, als)):
+            raise ValueError("structure_support: one structure per alignment, one entry per column")
+        if not als:
+            return []
+        n_rows = np.array([m.shape[0] for _, m in als], np.uint32)
+        lens = np.array([m.shape[1] for _, m in als], np.uint32)
+        seq = np.ascontiguousarray(np.concatenate([s for s, _ in als]), np.uint32)
+        mask = np.ascontiguousarray(np.concatenate([m.reshape(-1) for _, m in als] + [np.zeros(1, np.uint8)]), np.uint8)
+        ss = np.ascontiguousarray(np.concatenate(sss + [np.zeros(1, np.uint32)]), np.uint32)
+        R = max(int(n_rows.sum()), 1)
+        out = dict(both=np.zeros(R, np.uint32), canonical=np.zeros(R, np.uint32), half=np.zeros(R, np.uint32), expected=np.zeros(R, np.float64))
+        check(_structure_support(self._h, len(als), n_rows.ctypes.data, lens.ctypes.data, seq.ctypes.data, mask.ctypes.data, ss.ctypes.data,
+                                 *[out[k].ctypes.data for k in ("both", "canonical", "half", "expected")]))
+        cuts = np.cumsum(n_rows)[:-1]
+        per = {k: np.split(v[:int(n_rows.sum())], cuts) for k, v in out.items()}
+        return [{k: per[k][a] for k in per} for a in range(len(als))]
+
     def alignment_reliability(self, seq, mask, ss=None, mp_relaxed=None, bp_relaxed=None):
         """Reliability of the alignment (seq, mask) from the context's stores (dafs_hip_alignment_reliability).  ss: the
         consensus structure (left column -> right column, NONE otherwise) or None.  mp_relaxed / bp_relaxed: 0, 1, or None
@@ -688,6 +741,27 @@ class Context:
         if matrix:
             out["g"] = g
         return out
+
+
+def fold_complementary(a, b):
+    """True when CONTRAfold can pair the two residues: AU, GC, GU in either order and case; T is not U in its alphabet"""
+    return bool(_fold_complementary(a.encode("latin-1"), b.encode("latin-1")))
+
+
+def row_constraint(mask_row, ss, residues):
+    """dafs_host_row_constraint: the folding constraint the structure ss (left column -> right column, NONE otherwise) puts on
+    the row whose residues `residues` lie at the non-zero columns of mask_row: '?' everywhere, '(' and ')' at the residues of a
+    pair the row holds both ends of when they are complementary and at least 4 apart."""
+    m = np.ascontiguousarray(mask_row, np.uint8).reshape(-1)
+    ss = np.ascontiguousarray(ss, np.uint32).reshape(-1)
+    if ss.shape != m.shape:
+        raise ValueError("row_constraint: one structure entry per column")
+    b = residues.encode("latin-1") if isinstance(residues, str) else bytes(residues)
+    if b"\0" in b:
+        raise ValueError("row_constraint: the residues hold a NUL byte")
+    buf = C.create_string_buffer(int(m.astype(bool).sum()) + 1)
+    check(_row_constraint(len(m), m.ctypes.data if len(m) else None, ss.ctypes.data if len(m) else None, b, buf))
+    return buf.value.decode("latin-1")
 
 
 def build_tree(sim):

@@ -13,6 +13,7 @@
 #include "contrafold_params.h"
 #include "ctx.h"
 #include "hip_util.h"
+#include "last_error.h"
 
 namespace dafs {
 
@@ -64,8 +65,11 @@ using namespace dafs;
 
 namespace {
 
-// SStruct::ConvertParensToMapping (reference src/contrafold/SStruct.cpp:389-417; '-' reads as '.')
-int parse_constraint(const char* cons, uint32_t L, std::vector<int>& map) {
+// SStruct::ConvertParensToMapping (reference src/contrafold/SStruct.cpp:389-417; '-' reads as '.').  why (optional): what was
+// wrong with a refused string.
+int parse_constraint(const char* cons, uint32_t L, std::vector<int>& map, const char** why = nullptr) {
+  const char* dummy;
+  if (!why) why = &dummy;
   map.assign(L + 1, -1);
   std::vector<int> stack;
   for (uint32_t i = 1; i <= L; ++i) {
@@ -74,12 +78,13 @@ int parse_constraint(const char* cons, uint32_t L, std::vector<int>& map) {
     if (ch == '.' || ch == '-') map[i] = 0;
     else if (ch == '(') stack.push_back((int)i);
     else if (ch == ')') {
-      if (stack.empty()) return DAFS_HIP_EINVAL;
+      if (stack.empty()) { *why = "unbalanced brackets"; return DAFS_HIP_EINVAL; }
       map[i] = stack.back();
       map[stack.back()] = (int)i;
       stack.pop_back();
-    } else return DAFS_HIP_EINVAL;
+    } else { *why = "a character that is none of \"?.()\""; return DAFS_HIP_EINVAL; }
   }
+  if (!stack.empty()) *why = "unbalanced brackets";
   return stack.empty() ? DAFS_HIP_OK : DAFS_HIP_EINVAL;
 }
 
@@ -143,99 +148,14 @@ int run_job(dafs_hip_ctx* c, const fold_job& job, const uint8_t* d_codes, const 
   return rc;
 }
 
-}  // namespace
-
-// Batch hook: Fold::Model::calculate(const vector<Fasta>&, vector<BP>&) for -s CONTRAfold.
-// Result: the context's un-relaxed base-pairing store (rows with p > th; reference CUTOFF 0.01).
-// _begin enqueues the inside/outside/posterior kernels on the context's folding stream and returns; the pair
-// posteriors and the matching-probability transform do not depend on them and may run meanwhile.  _end waits
-// for the kernels and compacts the posteriors into the store.
-extern "C" int dafs_hip_fold_posteriors_begin(dafs_hip_ctx* c, int model, float th) {
-  if (!c || c->len.empty() || model != DAFS_FOLD_CONTRAFOLD) return DAFS_HIP_EINVAL;
-  if (hip_check(hipSetDevice(c->device))) return DAFS_HIP_ENODEV;
-  if (c->fold_pending) return DAFS_HIP_EINVAL;
-  const uint32_t n = (uint32_t)c->len.size();
-  fold_job job;
-  for (uint32_t x = 0; x < n; ++x) job.add(c->len[x], c->off[x], false, 0);
-  cf_batch B;
-  int rc = run_job(c, job, c->codes.ptr, nullptr, &B, c->fold_stream);
-  if (rc) return rc;
-  c->fold_batch.assign((const uint8_t*)&B, (const uint8_t*)&B + sizeof B);
-  c->fold_pending = true;
-  c->fold_th = th;
-  c->bp[0].valid = false;
-  c->bp[1].valid = false;
-  c->cur_bp = 0;
-  return DAFS_HIP_OK;
-}
-
-extern "C" int dafs_hip_fold_posteriors_end(dafs_hip_ctx* c) {
-  if (!c || !c->fold_pending || c->fold_batch.size() != sizeof(cf_batch)) return DAFS_HIP_EINVAL;
-  if (hip_check(hipSetDevice(c->device))) return DAFS_HIP_ENODEV;
-  c->fold_pending = false;
-  if (hip_check(hipStreamSynchronize(c->fold_stream))) return DAFS_HIP_ELAUNCH;
-  cf_batch B;
-  memcpy(&B, c->fold_batch.data(), sizeof B);
-  const float th = c->fold_th;
-  const uint32_t n = (uint32_t)c->len.size();
+// The posteriors of a finished job of n sequences compacted with threshold th into st (rows with p > th), whose row pointers
+// lie at rp_off[0..n]; the entry arrays start at 8 entries per residue and grow when the kernel reports an overflow.
+int compact_job(dafs_hip_ctx* c, const cf_batch& B, uint32_t n, float th, const uint64_t* rp_off, uint64_t residues, bp_store& st) {
   int rc;
-  bp_store& st = c->bp[0];
-  if ((rc = st.rowptr.reserve(c->seq_rp_off[n]))) return rc;
-  if ((rc = st.nnz.reserve(n))) return rc;
-  if ((rc = st.bp_off.reserve(n + 1))) return rc;
-  if ((rc = st.rp_off.upload(c->seq_rp_off.data(), n + 1, c->stream))) return rc;
-  if ((rc = c->counters.reserve(4))) return rc;
-  uint64_t cap = 8ull * c->off[n] + 1024;
-  for (int attempt = 0;; ++attempt) {
-    if ((rc = st.col.reserve(cap))) return rc;
-    if ((rc = st.val.reserve(cap))) return rc;
-    if (hip_check(hipMemsetAsync(c->counters.ptr, 0, 4 * sizeof(unsigned long long), c->stream))) return DAFS_HIP_ELAUNCH;
-    if ((rc = bp_compact_launch(B, n, th, st.rp_off.ptr, st.rowptr.ptr, st.col.ptr, st.val.ptr, st.bp_off.ptr, st.nnz.ptr,
-                                c->counters.ptr, cap, (int*)(c->counters.ptr + 2), c->stream)))
-      return rc;
-    unsigned long long h[4];
-    if (hip_check(hipMemcpyAsync(h, c->counters.ptr, sizeof h, hipMemcpyDeviceToHost, c->stream))) return DAFS_HIP_ELAUNCH;
-    if (hip_check(hipStreamSynchronize(c->stream))) return DAFS_HIP_ELAUNCH;
-    const int status = (int)(h[2] & 0xffffffffu);
-    if (status == 0) { st.total_nnz = h[0]; st.valid = true; return DAFS_HIP_OK; }
-    if (status != DAFS_HIP_EOVERFLOW || attempt >= 4) return status;
-    cap = std::max<uint64_t>(h[0], cap * 2);
-  }
-}
-
-extern "C" int dafs_hip_fold_posteriors(dafs_hip_ctx* c, int model, float th) {
-  const int rc = dafs_hip_fold_posteriors_begin(c, model, th);
-  return rc ? rc : dafs_hip_fold_posteriors_end(c);
-}
-
-// Constrained posteriors of the rows of one alignment (DAFS::update_basepairing_probability, dafs.cpp:657-663: one
-// s_model_->calculate(seq, con, bp) per sequence), as one batch; the result is a store whose index is the row.
-int dafs_fold_rows_constrained(dafs_hip_ctx* c, uint32_t n, const uint32_t* seq, const std::vector<std::string>& cons, float th, dafs::bp_store& st) {
-  if (!c || !n || !seq || cons.size() != n || c->fold_pending) return DAFS_HIP_EINVAL;
-  st.valid = false;
-  fold_job job;
-  std::vector<int> maps, one;
-  std::vector<uint64_t> rp_off(n + 1, 0);
-  uint64_t residues = 0;
-  for (uint32_t r = 0; r < n; ++r) {
-    if (seq[r] >= c->len.size()) return DAFS_HIP_EINVAL;
-    const uint32_t L = c->len[seq[r]];
-    if (cons[r].size() < L) return DAFS_HIP_EINVAL;
-    int rc = parse_constraint(cons[r].c_str(), L, one);
-    if (rc) return rc;
-    job.add(L, c->off[seq[r]], true, (uint32_t)maps.size());
-    maps.insert(maps.end(), one.begin(), one.end());
-    rp_off[r + 1] = rp_off[r] + L + 1;
-    residues += L;
-  }
-  int rc;
-  if ((rc = c->cf_cons.upload(maps.data(), maps.size(), c->stream))) return rc;
-  cf_batch B;
-  if ((rc = run_job(c, job, c->codes.ptr, c->cf_cons.ptr, &B, c->stream))) return rc;
   if ((rc = st.rowptr.reserve(rp_off[n]))) return rc;
   if ((rc = st.nnz.reserve(n))) return rc;
   if ((rc = st.bp_off.reserve(n + 1))) return rc;
-  if ((rc = st.rp_off.upload(rp_off.data(), n + 1, c->stream))) return rc;
+  if ((rc = st.rp_off.upload(rp_off, n + 1, c->stream))) return rc;
   if ((rc = c->counters.reserve(4))) return rc;
   uint64_t cap = 8ull * residues + 1024;
   for (int attempt = 0;; ++attempt) {
@@ -253,6 +173,122 @@ int dafs_fold_rows_constrained(dafs_hip_ctx* c, uint32_t n, const uint32_t* seq,
     if (status != DAFS_HIP_EOVERFLOW || attempt >= 4) return status;
     cap = std::max<uint64_t>(h[0], cap * 2);
   }
+}
+
+// The job of folding the context's sequences seq[0..n) (seq nullptr: 0 .. n-1), sequence r under cons[r] (nullptr or empty:
+// free), and the constraint maps of the constrained ones one after another.  A refused string leaves its row in *bad and the
+// reason in *why.  check_pairs: a forced pair must be one CONTRAfold can form.
+int make_job(const dafs_hip_ctx* c, uint32_t n, const uint32_t* seq, const char* const* cons, bool check_pairs, fold_job& job,
+             std::vector<int>& maps, uint32_t* bad, const char** why) {
+  std::vector<int> one;
+  for (uint32_t r = 0; r < n; ++r) {
+    const uint32_t x = seq ? seq[r] : r;
+    *bad = r;
+    if (x >= c->len.size()) { *why = "an unknown sequence"; return DAFS_HIP_EINVAL; }
+    const uint32_t L = c->len[x];
+    const char* con = cons ? cons[r] : nullptr;
+    if (!con || !con[0]) {  // empty = unconstrained (wrapper.cpp:188)
+      job.add(L, c->off[x], false, 0);
+      continue;
+    }
+    if (strnlen(con, L) < L) { *why = "a constraint shorter than its sequence"; return DAFS_HIP_EINVAL; }
+    const int rc = parse_constraint(con, L, one, why);
+    if (rc) return rc;
+    for (uint32_t i = 1; check_pairs && i <= L; ++i)
+      if (one[i] > (int)i && !dafs_host_fold_complementary(c->seq[c->off[x] + i - 1], c->seq[c->off[x] + one[i] - 1])) {
+        *why = "a forced pair of residues that CONTRAfold cannot pair";
+        return DAFS_HIP_EINVAL;
+      }
+    job.add(L, c->off[x], true, (uint32_t)maps.size());
+    maps.insert(maps.end(), one.begin(), one.end());
+  }
+  return DAFS_HIP_OK;
+}
+
+}  // namespace
+
+// Batch hook: Fold::Model::calculate(const vector<Fasta>&, vector<BP>&) for -s CONTRAfold, each sequence free or under a
+// constraint string of its own (Fold::Model::calculate(seq, str, bp), fold.cpp:191-207).
+// Result: the context's un-relaxed base-pairing store (rows with p > th; reference CUTOFF 0.01).
+// _begin enqueues the inside/outside/posterior kernels on the context's folding stream and returns; the pair
+// posteriors and the matching-probability transform do not depend on them and may run meanwhile.  _end waits
+// for the kernels and compacts the posteriors into the store.
+extern "C" int dafs_hip_fold_posteriors_constrained_begin(dafs_hip_ctx* c, int model, float th, const char* const* constraints) {
+  if (!c || c->len.empty() || model != DAFS_FOLD_CONTRAFOLD) return DAFS_HIP_EINVAL;
+  if (hip_check(hipSetDevice(c->device))) return DAFS_HIP_ENODEV;
+  if (c->fold_pending) return DAFS_HIP_EINVAL;
+  const uint32_t n = (uint32_t)c->len.size();
+  fold_job job;
+  std::vector<int> maps;
+  uint32_t bad = 0;
+  const char* why = "";
+  int rc = make_job(c, n, nullptr, constraints, true, job, maps, &bad, &why);
+  if (rc) {
+    set_last_error(("fold constraints: sequence " + std::to_string(bad) + ": " + why).c_str());
+    return rc;
+  }
+  // the maps travel on the folding stream, in front of the kernels that read them (upload waits for the copy)
+  if (!maps.empty() && (rc = c->cf_cons.upload(maps.data(), maps.size(), c->fold_stream))) return rc;
+  cf_batch B;
+  rc = run_job(c, job, c->codes.ptr, maps.empty() ? nullptr : c->cf_cons.ptr, &B, c->fold_stream);
+  if (rc) return rc;
+  c->fold_batch.assign((const uint8_t*)&B, (const uint8_t*)&B + sizeof B);
+  c->fold_pending = true;
+  c->fold_th = th;
+  c->bp[0].valid = false;
+  c->bp[1].valid = false;
+  c->cur_bp = 0;
+  return DAFS_HIP_OK;
+}
+
+extern "C" int dafs_hip_fold_posteriors_begin(dafs_hip_ctx* c, int model, float th) {
+  return dafs_hip_fold_posteriors_constrained_begin(c, model, th, nullptr);
+}
+
+extern "C" int dafs_hip_fold_posteriors_end(dafs_hip_ctx* c) {
+  if (!c || !c->fold_pending || c->fold_batch.size() != sizeof(cf_batch)) return DAFS_HIP_EINVAL;
+  if (hip_check(hipSetDevice(c->device))) return DAFS_HIP_ENODEV;
+  c->fold_pending = false;
+  if (hip_check(hipStreamSynchronize(c->fold_stream))) return DAFS_HIP_ELAUNCH;
+  cf_batch B;
+  memcpy(&B, c->fold_batch.data(), sizeof B);
+  const uint32_t n = (uint32_t)c->len.size();
+  return compact_job(c, B, n, c->fold_th, c->seq_rp_off.data(), c->off[n], c->bp[0]);
+}
+
+extern "C" int dafs_hip_fold_posteriors_constrained(dafs_hip_ctx* c, int model, float th, const char* const* constraints) {
+  const int rc = dafs_hip_fold_posteriors_constrained_begin(c, model, th, constraints);
+  return rc ? rc : dafs_hip_fold_posteriors_end(c);
+}
+
+extern "C" int dafs_hip_fold_posteriors(dafs_hip_ctx* c, int model, float th) {
+  return dafs_hip_fold_posteriors_constrained(c, model, th, nullptr);
+}
+
+// Constrained posteriors of the rows of one alignment (DAFS::update_basepairing_probability, dafs.cpp:657-663: one
+// s_model_->calculate(seq, con, bp) per sequence), as one batch; the result is a store whose index is the row.
+int dafs_fold_rows_constrained(dafs_hip_ctx* c, uint32_t n, const uint32_t* seq, const std::vector<std::string>& cons, float th, dafs::bp_store& st) {
+  if (!c || !n || !seq || cons.size() != n || c->fold_pending) return DAFS_HIP_EINVAL;
+  st.valid = false;
+  fold_job job;
+  std::vector<int> maps;
+  std::vector<const char*> strs(n);
+  std::vector<uint64_t> rp_off(n + 1, 0);
+  uint64_t residues = 0;
+  for (uint32_t r = 0; r < n; ++r) {
+    if (seq[r] >= c->len.size() || cons[r].empty()) return DAFS_HIP_EINVAL;  // every row is constrained here
+    strs[r] = cons[r].c_str();
+    rp_off[r + 1] = rp_off[r] + c->len[seq[r]] + 1;
+    residues += c->len[seq[r]];
+  }
+  uint32_t bad = 0;
+  const char* why = "";
+  int rc = make_job(c, n, seq, strs.data(), false, job, maps, &bad, &why);
+  if (rc) return rc;
+  if ((rc = c->cf_cons.upload(maps.data(), maps.size(), c->stream))) return rc;
+  cf_batch B;
+  if ((rc = run_job(c, job, c->codes.ptr, c->cf_cons.ptr, &B, c->stream))) return rc;
+  return compact_job(c, B, n, th, rp_off.data(), residues, st);
 }
 
 // Single-sequence plugin call: CONTRAfold<float>::ComputePosterior (reference

@@ -77,6 +77,7 @@ struct Options {
   std::string seed;       // --seed SEED: add FILE's sequences to this alignment
   bool seed_each = false;       // --seed-each: with --seed, every sequence of FILE added on its own
   std::string seed_scores;      // --seed-scores OUT
+  bool seed_structure = false;  // --seed-structure: with --seed, the seed's SS_cons is fixed like its columns
   bool pairwise = false;  // --pairwise: every pair of FILE's sequences aligned as a two-sequence run
   std::string pairwise_scores;  // --pairwise-scores OUT
   std::string covariation;      // --covariation OUT
@@ -120,6 +121,11 @@ const char* kHelp =
     "      --seed-scores OUT With --seed-each: a tab-separated table, one line per new sequence:\n"
     "                        j name length matched inserted score iterations (residues in seed columns and in columns of\n"
     "                        their own; the objective and iterations of the sequence's node)\n"
+    "                        With --seed-structure four more columns: pairs canonical half expected\n"
+    "      --seed-structure  With --seed (and --seed-each): the seed's consensus structure -- the #=GC SS_cons lines of a\n"
+    "                        Stockholm seed, the SS_cons record of an aligned-FASTA seed -- is fixed like its columns: the seed\n"
+    "                        rows are folded under it, nothing is decoded, and the printed SS_cons is the seed's with '.' at\n"
+    "                        insert columns.  Not with --bp-update1, -T or -G\n"
     "      --pairwise        Align every pair of the one FILE's sequences (at least two) as two-sequence runs, the pairs\n"
     "                        in row-major order: per pair a line \"==> i j <==\" (1-based input indices) and then what\n"
     "                        dafs prints for a file of those two sequences; --stockholm writes one block per pair.\n"
@@ -174,7 +180,7 @@ Options parse(int argc, char** argv) {
       {"bp-update", {0, false}}, {"bp-update1", {0, false}}, {"fold-aux", {0, true}}, {"save-align-aux", {0, true}},
       {"save-fold-aux", {0, true}}, {"device", {0, true}}, {"devices", {0, true}}, {"input", {0, true}},
       {"stockholm", {0, true}}, {"row-structures", {0, false}}, {"seed", {0, true}}, {"pairwise", {0, false}}, {"pairwise-scores", {0, true}},
-      {"seed-each", {0, false}}, {"seed-scores", {0, true}},
+      {"seed-each", {0, false}}, {"seed-scores", {0, true}}, {"seed-structure", {0, false}},
       {"covariation", {0, true}}, {"cov-shuffles", {0, true}}, {"cov-seed", {0, true}}};
   std::map<char, std::string> shorts;
   for (const auto& kv : spec)
@@ -245,6 +251,7 @@ Options parse(int argc, char** argv) {
       o.seed = value;
     }
     else if (name == "seed-each") o.seed_each = true;
+    else if (name == "seed-structure") o.seed_structure = true;
     else if (name == "seed-scores") {
       if (value.empty()) throw std::string("--seed-scores needs a file name");
       o.seed_scores = value;
@@ -280,6 +287,11 @@ Options parse(int argc, char** argv) {
   if (!o.pairwise_scores.empty() && !o.pairwise) throw std::string("--pairwise-scores needs --pairwise");
   if (o.seed_each && o.seed.empty()) throw std::string("--seed-each needs --seed");
   if (!o.seed_scores.empty() && !o.seed_each) throw std::string("--seed-scores needs --seed-each");
+  if (o.seed_structure) {  // the structure is the seed's: nothing is decoded, so nothing sets a decoder's threshold
+    if (o.seed.empty()) throw std::string("--seed-structure needs --seed");
+    if (o.bp_update1) throw std::string("--seed-structure: nothing is decoded; --bp-update1 cannot be combined with --seed-structure");
+    if (th1_given || !gamma1.empty()) throw std::string("--seed-structure: nothing is decoded; -T and -G cannot be combined with --seed-structure");
+  }
   if (o.pairwise) {  // every pair is a two-sequence run of its own: nothing that reads or writes one run's whole state
     if (o.refinement_given) throw std::string("--pairwise: -r cannot be combined with --pairwise");
     if (!o.seed.empty()) throw std::string("--pairwise: --seed cannot be combined with --pairwise");
@@ -673,17 +685,56 @@ void write_stockholm(const std::string& file, const std::vector<std::string>& bl
 // ---------------------------------------------------------------------------------------------
 // --seed: the seed alignment, read (Stockholm, or aligned FASTA as this program prints it) and checked
 // by the library: names and rows without their all-gap columns, '-' for every gap
-void read_seed(const std::string& file, std::vector<std::string>& names, std::vector<std::string>& rows) {
+// ss (--seed-structure): also the seed's consensus structure over the cleaned columns; a seed without
+// one is refused
+void read_seed(const std::string& file, std::vector<std::string>& names, std::vector<std::string>& rows, VU* ss = nullptr) {
   std::ifstream is(file.c_str(), std::ios::binary);
   if (!is.is_open()) throw "--seed: cannot open " + file;
   const std::string text((std::istreambuf_iterator<char>(is)), std::istreambuf_iterator<char>());
   uint32_t n = 0;
-  char *nm = nullptr, *rw = nullptr;
-  check_text(dafs_host_seed_parse(text.data(), text.size(), &n, &nm, &rw));
+  char *nm = nullptr, *rw = nullptr, *st = nullptr;
+  if (!ss) {
+    check_text(dafs_host_seed_parse(text.data(), text.size(), &n, &nm, &rw));
+    names = lines_of(take(nm), n);
+    rows = lines_of(take(rw), n);
+    check_text(dafs_host_seed_clean(n, c_strs(names).data(), c_strs(rows).data(), &rw));
+    rows = lines_of(take(rw), n);
+    return;
+  }
+  int has = 0;
+  check_text(dafs_host_seed_parse_structure(text.data(), text.size(), &n, &has, &nm, &rw, &st));
   names = lines_of(take(nm), n);
   rows = lines_of(take(rw), n);
-  check_text(dafs_host_seed_clean(n, c_strs(names).data(), c_strs(rows).data(), &rw));
+  const std::string structure = take(st);
+  if (!has) throw "--seed-structure: " + file + " holds no SS_cons";
+  ss->assign(rows.empty() ? 1 : rows[0].size() + 1, DAFS_HIP_NONE);
+  uint32_t columns = 0;
+  check_text(dafs_host_seed_clean_structure(n, c_strs(names).data(), c_strs(rows).data(), structure.c_str(), ss->data(), &columns, &rw));
   rows = lines_of(take(rw), n);
+  ss->resize(columns);
+}
+
+// the folding constraint of every seed row under the seed's structure (dafs_host_row_constraint)
+std::vector<std::string> seed_constraints(const std::vector<std::string>& srows, const std::vector<uint8_t>& smask, const VU& ss) {
+  const uint32_t C = (uint32_t)ss.size();
+  std::vector<std::string> out;
+  for (size_t r = 0; r < srows.size(); ++r) {
+    std::string sq;
+    for (char ch : srows[r])
+      if (ch != '-') sq += ch;
+    std::vector<char> buf(sq.size() + 1);
+    check(dafs_host_row_constraint(C, smask.data() + r * C, ss.data(), sq.c_str(), buf.data()));
+    out.push_back(buf.data());
+  }
+  return out;
+}
+
+// the seed's structure in the merged columns: insert columns unpaired
+VU carry_structure(const VU& ss, const std::vector<uint32_t>& seed_col, uint32_t width) {
+  VU out(width, DAFS_HIP_NONE);
+  for (size_t c = 0; c < ss.size(); ++c)
+    if (ss[c] != DAFS_HIP_NONE) out[seed_col[c]] = seed_col[ss[c]];
+  return out;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -872,7 +923,7 @@ void set_sequences(dafs_hip_ctx* ctx, const std::vector<Fasta>& fa) {
 // another) and both consistency transforms.  The device folding is only started at the beginning: it keeps one workgroup
 // per sequence busy, and the alignment posteriors and the matching-probability transform run beside it.
 void phase1_local(dafs_hip_ctx* ctx, const Options& o, int align_model, const std::vector<Fasta>& fa, const std::vector<uint32_t>& first,
-                  std::vector<float>& sim, const PairChunk* pc = nullptr) {
+                  std::vector<float>& sim, const PairChunk* pc = nullptr, const std::vector<const char*>* constraints = nullptr) {
   const uint N = (uint)fa.size(), F = (uint)first.size() - 1;
   bool folding = false;
   if (pc) {  // --pairwise: both raw stores and the similarity blocks gathered from the N-sequence source
@@ -881,8 +932,8 @@ void phase1_local(dafs_hip_ctx* ctx, const Options& o, int align_model, const st
     std::vector<BP> bp;
     load_fold_aux(o.fold_aux, fa, bp);
     upload_bp(ctx, bp);
-  } else {
-    check(dafs_hip_fold_posteriors_begin(ctx, DAFS_FOLD_CONTRAFOLD, kCutoff));
+  } else {  // constraints: per sequence its folding constraint, nullptr for a free fold (--seed-structure)
+    check(dafs_hip_fold_posteriors_constrained_begin(ctx, DAFS_FOLD_CONTRAFOLD, kCutoff, constraints ? constraints->data() : nullptr));
     folding = true;
   }
   bool fold_saved = false;
@@ -945,6 +996,27 @@ void consensus_structures(dafs_hip_ctx* ctx, const std::vector<const ALN*>& alns
     ss.push_back(VU(all.begin() + at, all.begin() + at + l));
     at += l;
   }
+}
+
+// The structure support of every row of many alignments in one library call (dafs_hip_structure_support): the rows of *alns[0]
+// in the order it holds them, then those of *alns[1], ...
+void structure_support(dafs_hip_ctx* ctx, const std::vector<const ALN*>& alns, const std::vector<VU>& ss, std::vector<uint32_t>& both,
+                       std::vector<uint32_t>& canonical, std::vector<uint32_t>& half, std::vector<double>& expected) {
+  std::vector<uint32_t> n_rows, len, seq, all;
+  std::vector<uint8_t> mask;
+  for (size_t k = 0; k < alns.size(); ++k) {
+    std::vector<uint32_t> rs;
+    std::vector<uint8_t> rm;
+    flatten(*alns[k], rs, rm);
+    n_rows.push_back((uint32_t)alns[k]->size());
+    len.push_back((uint32_t)(*alns[k])[0].second.size());
+    seq.insert(seq.end(), rs.begin(), rs.end());
+    mask.insert(mask.end(), rm.begin(), rm.end());
+    all.insert(all.end(), ss[k].begin(), ss[k].end());
+  }
+  both.assign(seq.size(), 0); canonical.assign(seq.size(), 0); half.assign(seq.size(), 0); expected.assign(seq.size(), 0.0);
+  check(dafs_hip_structure_support(ctx, (uint32_t)alns.size(), n_rows.data(), len.data(), seq.data(), mask.data(), all.data(), both.data(),
+                                   canonical.data(), half.data(), expected.data()));
 }
 
 // --row-structures: the structure of every listed sequence alone -- its one-row alignment decoded from the base-pairing
@@ -1076,7 +1148,8 @@ struct FreshRand {
 // the seed; the structure is decoded over the rows new sequences, then seed rows, as in a run whose tree joins a leaf last.
 int run_add(const Options& o, int align_model) {
   std::vector<std::string> snames, srows;
-  read_seed(o.seed, snames, srows);
+  VU seed_ss;
+  read_seed(o.seed, snames, srows, o.seed_structure ? &seed_ss : nullptr);
   std::vector<Fasta> added;
   Fasta::load(added, o.input.c_str());
   if (added.empty()) throw "no sequences in the input";
@@ -1096,7 +1169,14 @@ int run_add(const Options& o, int align_model) {
   Guard guard{ctx};
   set_sequences(ctx, fa);
   std::vector<float> sim;
-  phase1_local(ctx, o, align_model, fa, {0, m + k}, sim);
+  std::vector<std::string> cons;  // --seed-structure: the seed rows under their constraints, the new sequences free
+  std::vector<const char*> cons_ptr;
+  if (o.seed_structure) {
+    cons = seed_constraints(srows, smask, seed_ss);
+    for (const std::string& s : cons) cons_ptr.push_back(s.c_str());
+    cons_ptr.resize(m + k, nullptr);
+  }
+  phase1_local(ctx, o, align_model, fa, {0, m + k}, sim, nullptr, o.seed_structure ? &cons_ptr : nullptr);
 
   // the k nodes: all opened in the first round
   dafs_dd_params prm = dd_params_of(o);
@@ -1147,8 +1227,10 @@ int run_add(const Options& o, int align_model) {
     for (uint32_t x = 0; x < m + k; ++x) every[x] = x;
     row_ss = row_structures(ctx, fa, every, o.fold_th1[0]);
   }
+  VU carried;  // --seed-structure: nothing is decoded
+  if (o.seed_structure) carried = carry_structure(seed_ss, seed_col, width);
   finish_alignment(ctx, o, fa, root, fa, 0, std::cout, o.stockholm.empty() ? nullptr : &sto, nullptr, &rf, o.covariation.empty() ? nullptr : &cov,
-                   nullptr, o.row_structures ? &row_ss : nullptr);
+                   o.seed_structure ? &carried : nullptr, o.row_structures ? &row_ss : nullptr);
   std::cout.flush();
   if (!o.stockholm.empty()) write_stockholm(o.stockholm, {sto});
   if (!o.covariation.empty()) write_covariation(o.covariation, {cov}, nullptr);
@@ -1164,7 +1246,8 @@ int run_add(const Options& o, int align_model) {
 // run_add's merge per family and the structures of the chunk in one call.
 int run_add_each(const Options& o, int align_model) {
   std::vector<std::string> snames, srows;
-  read_seed(o.seed, snames, srows);
+  VU seed_ss;
+  read_seed(o.seed, snames, srows, o.seed_structure ? &seed_ss : nullptr);
   std::vector<Fasta> added;
   Fasta::load(added, o.input.c_str());
   if (added.empty()) throw "no sequences in the input";
@@ -1189,7 +1272,16 @@ int run_add_each(const Options& o, int align_model) {
     all.insert(all.end(), added.begin(), added.end());
     set_sequences(src, all);
   }
-  check(dafs_hip_fold_posteriors_begin(src, DAFS_FOLD_CONTRAFOLD, kCutoff));
+  {  // --seed-structure: the seed rows under their constraints, the new sequences free, once for every chunk
+    std::vector<std::string> cons;
+    std::vector<const char*> cons_ptr;
+    if (o.seed_structure) {
+      cons = seed_constraints(srows, smask, seed_ss);
+      for (const std::string& s : cons) cons_ptr.push_back(s.c_str());
+      cons_ptr.resize(m + k, nullptr);
+    }
+    check(dafs_hip_fold_posteriors_constrained_begin(src, DAFS_FOLD_CONTRAFOLD, kCutoff, o.seed_structure ? cons_ptr.data() : nullptr));
+  }
   // the pairs (x, y) with x < m are the first m (m + k) - m (m + 1) / 2 pair ids
   const int rc_align = dafs_hip_align_posteriors(src, align_model, o.align_th, 0, (uint64_t)m * (m + k) - (uint64_t)m * (m + 1) / 2);
   const int rc_fold = dafs_hip_fold_posteriors_end(src);
@@ -1209,6 +1301,8 @@ int run_add_each(const Options& o, int align_model) {
   std::vector<uint32_t> matched(k, 0);
   std::vector<double> score(k, 0.0);
   std::vector<int64_t> iterations(k, 0);
+  std::vector<uint32_t> sup_both(k, 0), sup_can(k, 0), sup_half(k, 0);  // --seed-structure: the support of each new sequence's row
+  std::vector<double> sup_exp(k, 0.0);
   std::vector<std::string> sto_blocks, cov_tables, cov_headers;
   for (uint32_t j0 = 0; j0 < k;) {
     uint32_t j1 = j0;
@@ -1283,7 +1377,23 @@ int run_add_each(const Options& o, int align_model) {
     std::vector<const ALN*> ptrs;
     for (const ALN& a : roots) ptrs.push_back(&a);
     std::vector<VU> ss;
-    consensus_structures(ctx, ptrs, o.fold_th1[0], ss);
+    if (!o.seed_structure) {
+      consensus_structures(ctx, ptrs, o.fold_th1[0], ss);
+    } else {  // nothing is decoded: the seed's structure in every family's merged columns, and each row's support of it
+      for (uint32_t f = 0; f < nf; ++f) {
+        std::vector<uint32_t> seed_col;
+        for (uint32_t c = 0; c < rfs[f].size(); ++c)
+          if (rfs[f][c]) seed_col.push_back(c);
+        ss.push_back(carry_structure(seed_ss, seed_col, (uint32_t)rfs[f].size()));
+      }
+      std::vector<uint32_t> both, can, half;
+      std::vector<double> expd;
+      structure_support(ctx, ptrs, ss, both, can, half, expd);
+      for (uint32_t f = 0; f < nf; ++f) {  // the new sequence is the first row of its alignment
+        sup_both[j0 + f] = both[(size_t)f * n]; sup_can[j0 + f] = can[(size_t)f * n]; sup_half[j0 + f] = half[(size_t)f * n];
+        sup_exp[j0 + f] = expd[(size_t)f * n];
+      }
+    }
     std::map<uint32_t, VU> row_ss;
     if (o.row_structures) {
       std::vector<uint32_t> every(nf * n);
@@ -1311,7 +1421,9 @@ int run_add_each(const Options& o, int align_model) {
     std::vector<std::string> headers;
     for (const Fasta& s : added) headers.push_back(s.name());
     char* text = nullptr;
-    check_text(dafs_host_seed_table(k, c_strs(headers).data(), lens.data(), matched.data(), score.data(), iterations.data(), &text));
+    check_text(dafs_host_seed_table_support(k, c_strs(headers).data(), lens.data(), matched.data(), score.data(), iterations.data(),
+                                            o.seed_structure ? sup_both.data() : nullptr, o.seed_structure ? sup_can.data() : nullptr,
+                                            o.seed_structure ? sup_half.data() : nullptr, o.seed_structure ? sup_exp.data() : nullptr, &text));
     ts << take(text);
     ts.flush();
     if (!ts) throw "--seed-scores: cannot write " + o.seed_scores;

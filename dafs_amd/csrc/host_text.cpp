@@ -136,7 +136,10 @@ std::vector<std::string> fields(const std::string& s) {
 // Stockholm when the first line is "# STOCKHOLM 1.0": the first alignment up to "//", interleaved blocks concatenated by
 // name, '#' lines ignored, every other non-blank line "name row".  Otherwise aligned FASTA as `dafs` prints it: lines
 // before the first '>' ignored, leading blanks of a name stripped, a record named SS_cons skipped, rows over several lines.
-void parse_seed(const std::string& text, std::vector<std::string>& names, std::vector<std::string>& rows) {
+// structure (optional): the "#=GC SS_cons" lines of that first alignment concatenated in order, or the SS_cons record; *has says
+// whether the file holds one.
+void parse_seed(const std::string& text, std::vector<std::string>& names, std::vector<std::string>& rows, std::string* structure = nullptr,
+                bool* has = nullptr) {
   if (text.find('\0') != std::string::npos) throw std::string("seed: the file holds a NUL byte");  // names and rows are C strings
   std::istringstream is(text);
   std::vector<std::string> lines;
@@ -150,6 +153,14 @@ void parse_seed(const std::string& text, std::vector<std::string>& names, std::v
     for (size_t k = 1; k < lines.size(); ++k) {
       const std::string& l = lines[k];
       if (l == "//") break;
+      if (structure && l.compare(0, 4, "#=GC") == 0) {
+        const std::vector<std::string> f = fields(l);
+        if (f.size() >= 2 && f[1] == "SS_cons") {
+          if (f.size() != 3) throw "seed: line " + std::to_string(k + 1) + " is not '#=GC SS_cons structure'";
+          *structure += f[2];
+          *has = true;
+        }
+      }
       if (l.empty() || l[0] == '#') continue;  // rstripped: a blank line is empty
       const std::vector<std::string> f = fields(l);
       if (f.size() != 2) throw "seed: line " + std::to_string(k + 1) + " is neither a #= annotation nor 'name row'";
@@ -162,25 +173,68 @@ void parse_seed(const std::string& text, std::vector<std::string>& names, std::v
     }
     return;
   }
-  bool keep = false;
+  bool keep = false, in_ss = false;
   for (const std::string& l : lines) {
     if (!l.empty() && l[0] == '>') {
       const size_t b = l.find_first_not_of(kSpace, 1);
       const std::string nm = b == std::string::npos ? std::string() : l.substr(b);
       keep = nm != "SS_cons";
+      in_ss = !keep && structure;
+      if (in_ss) {
+        if (*has) throw std::string("seed: more than one SS_cons record");
+        *has = true;
+      }
       if (keep) {
         names.push_back(nm);
         rows.push_back(std::string());
       }
     } else if (keep) {
       for (const std::string& f : fields(l)) rows.back() += f;
+    } else if (in_ss) {
+      for (const std::string& f : fields(l)) *structure += f;
     }
   }
 }
 
+// The pairs of a structure line: "()", "<>", "[]", "{}" each matched with its own kind, letters and ". , : _ - ~" unpaired.
+// partner[c] = the other column of c's pair, DAFS_HIP_NONE for an unpaired column.
+std::vector<uint32_t> structure_pairs(const std::string& st) {
+  const std::string open = "(<[{", close = ")>]}", unpaired = ".,:_-~";
+  std::vector<uint32_t> partner(st.size(), DAFS_HIP_NONE);
+  std::vector<size_t> stack[4];
+  for (size_t c = 0; c < st.size(); ++c) {
+    const char ch = st[c];
+    size_t k;
+    if ((k = open.find(ch)) != std::string::npos) stack[k].push_back(c);
+    else if ((k = close.find(ch)) != std::string::npos) {
+      if (stack[k].empty()) throw "seed: SS_cons has a '" + std::string(1, ch) + "' at column " + std::to_string(c + 1) + " that closes nothing";
+      partner[c] = (uint32_t)stack[k].back();
+      partner[stack[k].back()] = (uint32_t)c;
+      stack[k].pop_back();
+    } else if (!is_alpha(ch) && unpaired.find(ch) == std::string::npos)
+      throw "seed: SS_cons holds '" + std::string(1, ch) + "', which is neither a bracket, a letter nor one of \".,:_-~\"";
+  }
+  for (size_t k = 0; k < 4; ++k)
+    if (!stack[k].empty()) throw "seed: SS_cons has a '" + std::string(1, open[k]) + "' at column " + std::to_string(stack[k].back() + 1) + " that is never closed";
+  // all kinds merged: the pairs must nest
+  std::vector<uint32_t> st_open;
+  for (uint32_t c = 0; c < partner.size(); ++c) {
+    if (partner[c] == DAFS_HIP_NONE) continue;
+    if (partner[c] > c) st_open.push_back(c);
+    else {
+      if (st_open.back() != partner[c])
+        throw "seed: the pairs of SS_cons cross (columns " + std::to_string(st_open.back() + 1) + " and " + std::to_string(partner[c] + 1) +
+            " are open at column " + std::to_string(c + 1) + ")";
+      st_open.pop_back();
+    }
+  }
+  return partner;
+}
+
 // refuses an empty seed, rows of unequal length, a character that is neither a letter nor a gap ('.', '-') and a row without
 // residues; drops the all-gap columns and writes every gap as '-'
-void clean_seed(const std::vector<std::string>& names, std::vector<std::string>& rows) {
+// kept (optional): the columns that stay.
+void clean_seed(const std::vector<std::string>& names, std::vector<std::string>& rows, std::vector<size_t>* kept = nullptr) {
   if (rows.empty()) throw std::string("seed: no rows");
   auto gap = [](char ch) { return ch == '.' || ch == '-'; };
   for (size_t r = 0; r < rows.size(); ++r) {
@@ -203,6 +257,18 @@ void clean_seed(const std::vector<std::string>& names, std::vector<std::string>&
     std::string out;
     for (size_t c : keep) out += gap(row[c]) ? '-' : row[c];
     row.swap(out);
+  }
+  if (kept) kept->swap(keep);
+}
+
+// CONTRAfold's alphabet, case-insensitive "ACGU" (InferenceEngine constructor); everything else, T included, is its symbol 4
+int fold_symbol(char ch) {
+  switch (ch) {
+    case 'A': case 'a': return 0;
+    case 'C': case 'c': return 1;
+    case 'G': case 'g': return 2;
+    case 'U': case 'u': return 3;
+    default: return 4;
   }
 }
 
@@ -342,20 +408,34 @@ extern "C" int dafs_host_pairwise_table(uint64_t npairs, const uint32_t* x, cons
   });
 }
 
-// --seed-scores: one line per new sequence of a --seed-each run, named by the Stockholm rule over the file's headers
-extern "C" int dafs_host_seed_table(uint32_t n, const char* const* headers, const uint32_t* length, const uint32_t* matched, const double* score,
-                                    const int64_t* iterations, char** table) {
+// --seed-scores: one line per new sequence of a --seed-each run, named by the Stockholm rule over the file's headers; with
+// --seed-structure four more columns, the sequence's structure support
+extern "C" int dafs_host_seed_table_support(uint32_t n, const char* const* headers, const uint32_t* length, const uint32_t* matched,
+                                            const double* score, const int64_t* iterations, const uint32_t* both, const uint32_t* canonical,
+                                            const uint32_t* half, const double* expected, char** table) {
   return text_out(table, [&]() {
     const std::vector<std::string> nm = stockholm_names(strings(n, headers));
     if (n && (!length || !matched || !score || !iterations)) throw kBadArgument;
+    const bool support = both || canonical || half || expected;
+    if (support && n && (!both || !canonical || !half || !expected)) throw kBadArgument;
     std::ostringstream ts;
     for (uint32_t j = 0; j < n; ++j) {
       if (matched[j] > length[j]) throw std::string("seed table: more matched residues than residues");
       ts << j + 1 << "\t" << nm[j] << "\t" << length[j] << "\t" << matched[j] << "\t" << length[j] - matched[j] << "\t" << fmt9d(score[j]) << "\t"
-         << iterations[j] << "\n";
+         << iterations[j];
+      if (support) {
+        if (canonical[j] > both[j]) throw std::string("seed table: more canonical pairs than pairs");
+        ts << "\t" << both[j] << "\t" << canonical[j] << "\t" << half[j] << "\t" << fmt9d(expected[j]);
+      }
+      ts << "\n";
     }
     return ts.str();
   });
+}
+
+extern "C" int dafs_host_seed_table(uint32_t n, const char* const* headers, const uint32_t* length, const uint32_t* matched, const double* score,
+                                    const int64_t* iterations, char** table) {
+  return dafs_host_seed_table_support(n, headers, length, matched, score, iterations, nullptr, nullptr, nullptr, nullptr, table);
 }
 
 extern "C" int dafs_host_seed_parse(const char* text, size_t bytes, uint32_t* n, char** names, char** rows) {
@@ -383,6 +463,82 @@ extern "C" int dafs_host_seed_clean(uint32_t n, const char* const* names, const 
     clean_seed(nm, rw);
     return joined(rw);
   });
+}
+
+// the seed with its consensus structure
+extern "C" int dafs_host_seed_parse_structure(const char* text, size_t bytes, uint32_t* n, int* has_structure, char** names, char** rows,
+                                              char** structure) {
+  if (rows) *rows = nullptr;
+  if (structure) *structure = nullptr;
+  const int rc = text_out(names, [&]() {
+    if (!n || !has_structure || !rows || !structure || (bytes && !text)) throw kBadArgument;
+    std::vector<std::string> nm, rw;
+    std::string st;
+    bool has = false;
+    parse_seed(std::string(bytes ? text : "", bytes), nm, rw, &st, &has);
+    const std::string names_text = joined(nm);
+    *rows = copy_text(joined(rw));
+    *structure = copy_text(st);
+    *n = (uint32_t)nm.size();
+    *has_structure = has ? 1 : 0;
+    return names_text;
+  });
+  if (rc != DAFS_HIP_OK) {  // a later copy failed after an earlier one
+    if (rows) { free(*rows); *rows = nullptr; }
+    if (structure) { free(*structure); *structure = nullptr; }
+  }
+  return rc;
+}
+
+extern "C" int dafs_host_seed_clean_structure(uint32_t n, const char* const* names, const char* const* rows, const char* structure,
+                                              uint32_t* ss, uint32_t* columns, char** cleaned) {
+  return text_out(cleaned, [&]() {
+    if (!structure || !ss || !columns) throw kBadArgument;
+    const std::vector<std::string> nm = strings(n, names);
+    std::vector<std::string> rw = strings(n, rows);
+    const size_t raw = rw.empty() ? 0 : rw[0].size();
+    std::vector<size_t> kept;
+    clean_seed(nm, rw, &kept);
+    const std::string st = structure;
+    if (st.size() != raw)
+      throw "seed: SS_cons has " + std::to_string(st.size()) + " columns, the rows have " + std::to_string(raw);
+    const std::vector<uint32_t> partner = structure_pairs(st);
+    std::vector<uint32_t> now(raw, DAFS_HIP_NONE);  // raw column -> cleaned column
+    for (size_t k = 0; k < kept.size(); ++k) now[kept[k]] = (uint32_t)k;
+    for (size_t k = 0; k < kept.size(); ++k) {
+      const uint32_t p = partner[kept[k]];
+      // a pair that lost its right column reads NONE here; one that lost its left column is named by nothing any more
+      ss[k] = p != DAFS_HIP_NONE && p > kept[k] ? now[p] : DAFS_HIP_NONE;
+    }
+    *columns = (uint32_t)kept.size();
+    return joined(rw);
+  });
+}
+
+extern "C" int dafs_host_fold_complementary(char a, char b) {
+  const int x = fold_symbol(a), y = fold_symbol(b);
+  return ((x == 0 && y == 3) || (x == 3 && y == 0) || (x == 2 && y == 3) || (x == 3 && y == 2) || (x == 1 && y == 2) || (x == 2 && y == 1)) ? 1 : 0;
+}
+
+extern "C" int dafs_host_row_constraint(uint32_t len, const uint8_t* mask_row, const uint32_t* ss, const char* residues, char* out) {
+  if ((len && (!mask_row || !ss)) || !residues || !out) return DAFS_HIP_EINVAL;
+  std::vector<uint32_t> rev(len);
+  uint32_t k = 0;
+  for (uint32_t c = 0; c < len; ++c) rev[c] = mask_row[c] ? k++ : DAFS_HIP_NONE;
+  if (strnlen(residues, (size_t)k + 1) != k) return DAFS_HIP_EINVAL;
+  for (uint32_t c = 0; c < len; ++c)
+    if (ss[c] != DAFS_HIP_NONE && (ss[c] <= c || ss[c] >= len)) return DAFS_HIP_EINVAL;
+  memset(out, '?', k);
+  out[k] = 0;
+  for (uint32_t c = 0; c < len; ++c) {
+    if (ss[c] == DAFS_HIP_NONE) continue;
+    const uint32_t i = rev[c], j = rev[ss[c]];
+    if (i == DAFS_HIP_NONE || j == DAFS_HIP_NONE) continue;
+    if (j - i < 4 || !dafs_host_fold_complementary(residues[i], residues[j])) continue;
+    out[i] = '(';
+    out[j] = ')';
+  }
+  return DAFS_HIP_OK;
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -89,9 +89,10 @@ def run(names, seqs, ctx=None, bp=None, w=4.0, eta0=0.5, t_max=600, w_pct_a=0.25
                           skip_uncoupled_folds, round_us, bp_update, bp_update1, reliability, covariation, row_structures)[0]
 
 
-def _phase1_local(ctx, seqs, bp, mp, align_model, th_a, w_pct_a, w_pct_s, t, w_pct_f=0.0, first=None):
+def _phase1_local(ctx, seqs, bp, mp, align_model, th_a, w_pct_a, w_pct_s, t, w_pct_f=0.0, first=None, constraints=None):
     """Phase 1 on the context: folds, pair posteriors, consistency transforms.  first: family partition (run_batch); the
-    result is then the list of the families' similarity blocks instead of one matrix."""
+    result is then the list of the families' similarity blocks instead of one matrix.  constraints: per sequence a folding
+    constraint or None (Context.fold_begin)."""
     import time
     ctx.set_sequences(seqs)
     if first is not None and len(first) > 2:
@@ -104,7 +105,7 @@ def _phase1_local(ctx, seqs, bp, mp, align_model, th_a, w_pct_a, w_pct_s, t, w_p
         if bp is not None:
             ctx.set_bp(bp)
         else:
-            ctx.fold_begin(0.01)
+            ctx.fold_begin(0.01, constraints=constraints)
             folding = True
         t.append(time.perf_counter())
         if mp is not None:
@@ -372,9 +373,43 @@ def _final(ctx, res, names, seqs, first, sidx, mask, th1, bp_update1, reliabilit
                                         rl["col"], res.ss_str, rf, cov_chars, None if row_ss is None else res.row_ss_str)
 
 
+def _seed_structure(seed_ss, seed_mask, seed_seqs, th_s1, bp_update1, who):
+    """The checks of a seed structure (seed_ss over the seed's cleaned columns) and the folding constraint it puts on every
+    seed row (capi.row_constraint).  Returns (seed_ss as uint32, constraints)."""
+    ss = np.ascontiguousarray(seed_ss, np.uint32).reshape(-1)
+    C = seed_mask.shape[1]
+    if len(ss) != C:
+        raise ValueError("%s: seed_ss has %d entries, the seed has %d columns" % (who, len(ss), C))
+    if bp_update1 or th_s1 is not None:
+        raise ValueError("%s: with seed_ss nothing is decoded: bp_update1 and th_s1 cannot be combined with it" % who)
+    used = np.zeros(C, bool)
+    for c in range(C):
+        p = int(ss[c])
+        if p == NONE:
+            continue
+        if p <= c or p >= C or used[c] or used[p]:
+            raise ValueError("%s: seed_ss is no structure over the seed's columns (column %d)" % (who, c))
+        used[c] = used[p] = True
+    return ss, [capi.row_constraint(seed_mask[r], ss, seed_seqs[r]) for r in range(len(seed_seqs))]
+
+
+def carry_structure(seed_ss, seed_col, width):
+    """The seed's structure in the merged columns: ss_m[seed_col[c]] = seed_col[seed_ss[c]], insert columns unpaired"""
+    ss_m = np.full(width, NONE, np.uint32)
+    paired = np.flatnonzero(seed_ss != NONE)
+    ss_m[seed_col[paired]] = seed_col[seed_ss[paired]]
+    return ss_m
+
+
+def _printed_support(sup, sidx):
+    """one alignment's Context.structure_support in the order of its printed rows (ascending sequence index)"""
+    order = np.argsort(sidx, kind="stable")
+    return {k: v[order] for k, v in sup.items()}
+
+
 def add(seed_names, seed_rows, names, seqs, ctx=None, w=4.0, eta0=0.5, t_max=600, w_pct_a=0.25, w_pct_s=0.25, th_a=0.01,
         th_s=0.2, th_s1=None, align_model=capi.ALIGN_PROBCONS, force_iters=0, slice_iters=None, skip_uncoupled_folds=True,
-        round_us=None, w_pct_f=0.0, bp_update1=False, reliability=False, covariation=False, row_structures=False):
+        round_us=None, w_pct_f=0.0, bp_update1=False, reliability=False, covariation=False, row_structures=False, seed_ss=None):
     """Add new sequences to a fixed seed alignment without changing its columns (`dafs --seed`).
     seed_names / seed_rows: the seed's rows (letters and '.' / '-' gaps; stockholm.read_seed reads a file), checked and
     without their all-gap columns (stockholm.clean_seed).  names / seqs: the new sequences.  The options are run()'s.
@@ -386,7 +421,13 @@ def add(seed_names, seed_rows, names, seqs, ctx=None, w=4.0, eta0=0.5, t_max=600
     .z (per new sequence its column map into the seed), .rf (per merged column True for a seed column), .dd_log
     ({j: (iterations, violated, ncbp, score)}), .dd_memory, .seconds; with reliability, .reliability and .stockholm (no CC
     line, a `#=GC RF` line); with covariation (as in run), .covariation; with row_structures (as in run), .row_ss and
-    .row_ss_str."""
+    .row_ss_str.
+
+    seed_ss (`dafs --seed-structure`): the seed's consensus structure over its cleaned columns
+    (stockholm.read_seed_structure), fixed like the columns.  The seed rows are folded under the constraints it puts on them
+    (capi.row_constraint), the new sequences free; nothing is decoded: the output's structure is the seed's carried into the
+    merged columns, insert columns unpaired, and the annotations see it.  The Result gains .support: per printed row, both,
+    canonical, half and expected of Context.structure_support."""
     import time
     covariation = cov_options(covariation)
     seed_names, seed_rows = stockholm.clean_seed(seed_names, seed_rows)
@@ -397,12 +438,16 @@ def add(seed_names, seed_rows, names, seqs, ctx=None, w=4.0, eta0=0.5, t_max=600
     seed_seqs = [r.replace("-", "") for r in seed_rows]
     seed_mask = np.array([[ch != "-" for ch in r] for r in seed_rows], np.uint8)
     all_names, all_seqs = seed_names + names, seed_seqs + seqs
+    constraints = None
+    if seed_ss is not None:
+        seed_ss, constraints = _seed_structure(seed_ss, seed_mask, seed_seqs, th_s1, bp_update1, "pipeline.add")
+        constraints += [None] * k
     own = ctx is None
     if own:
         ctx = capi.Context(0)
     try:
         t = [time.perf_counter()]
-        _phase1_local(ctx, all_seqs, None, None, align_model, th_a, w_pct_a, w_pct_s, t, w_pct_f)
+        _phase1_local(ctx, all_seqs, None, None, align_model, th_a, w_pct_a, w_pct_s, t, w_pct_f, constraints=constraints)
         t.append(time.perf_counter())
         prm = capi.dd_params(w=w, eta0=eta0, th_a=th_a, th_s=th_s, t_max=t_max, force_iters=force_iters,
                              skip_uncoupled_folds=1 if skip_uncoupled_folds else 0)
@@ -430,8 +475,12 @@ def add(seed_names, seed_rows, names, seqs, ctx=None, w=4.0, eta0=0.5, t_max=600
         res.dd_log = {j: (o["iterations"], o["violated"], o["ncbp"], o["score"]) for j, o in enumerate(outs)}
         res.dd_memory = dd_memory
         th1 = th_s if th_s1 is None else th_s1
-        _final(ctx, res, all_names, all_seqs, 0, sidx, np.concatenate([mask[m:], mask[:m]]), th1, bp_update1, reliability, None, rf,
-               covariation, None, _row_structures(ctx, [sidx], dict(enumerate(map(len, all_seqs))), th1)[0] if row_structures else None)
+        rows_mask = np.concatenate([mask[m:], mask[:m]])
+        ss_m = None if seed_ss is None else carry_structure(seed_ss, seed_col, width)
+        if ss_m is not None:
+            res.support = _printed_support(ctx.structure_support([(sidx, rows_mask)], [ss_m])[0], sidx)
+        _final(ctx, res, all_names, all_seqs, 0, sidx, rows_mask, th1, bp_update1, reliability, None, rf,
+               covariation, ss_m, _row_structures(ctx, [sidx], dict(enumerate(map(len, all_seqs))), th1)[0] if row_structures else None)
         t.append(time.perf_counter())
         res.seconds = dict(phase1=t[3] - t[0], nodes=t[4] - t[3], final=t[5] - t[4], total=t[5] - t[0])
     finally:
@@ -693,13 +742,19 @@ def seed_each_bytes(seed_lens, columns, new_len):
 def seed_scores_tsv(names, each):
     """The table of `dafs --seed SEED --seed-each --seed-scores OUT` (dafs_host_seed_table) for the result of add_each on the
     new sequences `names`: per sequence "j<TAB>name<TAB>length<TAB>matched<TAB>inserted<TAB>score<TAB>iterations" with 1-based j,
-    the Stockholm name (stockholm.names over the new sequences' headers) and the floats as %.9g."""
+    the Stockholm name (stockholm.names over the new sequences' headers) and the floats as %.9g.  A result of add_each with
+    seed_ss has four more columns, "pairs<TAB>canonical<TAB>half<TAB>expected" of the sequence's structure support."""
     names = list(names)
     if len(names) != len(each.results):
         raise ValueError("seed_scores_tsv: one name per new sequence")
     arrs = [np.ascontiguousarray(a, t) for a, t in ((each.lengths, np.uint32), (each.matched, np.uint32), (each.score, np.float64),
                                                     (each.iterations, np.int64))]
-    return capi.host_text(capi._seed_table, len(names), capi.c_strings(names), *[a.ctypes.data for a in arrs])
+    sup = getattr(each, "support", None)
+    if sup is None:
+        return capi.host_text(capi._seed_table, len(names), capi.c_strings(names), *[a.ctypes.data for a in arrs])
+    arrs += [np.ascontiguousarray(sup[key], t) for key, t in (("both", np.uint32), ("canonical", np.uint32), ("half", np.uint32),
+                                                             ("expected", np.float64))]
+    return capi.host_text(capi._seed_table_support, len(names), capi.c_strings(names), *[a.ctypes.data for a in arrs])
 
 
 class AddEach:
@@ -722,7 +777,11 @@ def add_each(seed_names, seed_rows, names, seqs, ctx=None, max_bytes=None, **opt
     object with .results (one Result per new sequence, in input order), .score and .iterations (the node's final objective
     and iteration count, dd_log's 4th and 1st entries), .lengths, .matched (residues that landed in seed columns), .chunks
     (indices per chunk), .dd_memory (per chunk the nodes' (reserved, in use, peak) bytes) and .seconds (phase1, gather,
-    transforms, nodes, final, total)."""
+    transforms, nodes, final, total).
+
+    seed_ss: as in add().  The seed rows are folded under their constraints once, in the source context; every result's
+    structure is the seed's carried into its merged columns, and its .support comes from one Context.structure_support call
+    per chunk.  The object gains .support: per new sequence both, canonical, half and expected of its own row."""
     import time
     o = {k: p.default for k, p in inspect.signature(add).parameters.items() if k not in ("seed_names", "seed_rows", "names", "seqs", "ctx")}
     unknown = set(opts) - set(o)
@@ -745,6 +804,10 @@ def add_each(seed_names, seed_rows, names, seqs, ctx=None, max_bytes=None, **opt
     seed_mask = np.array([[ch != "-" for ch in r] for r in seed_rows], np.uint8)
     columns = seed_mask.shape[1]
     seed_lens = [len(sq) for sq in seed_seqs]
+    seed_ss, constraints = None, None
+    if o["seed_ss"] is not None:
+        seed_ss, constraints = _seed_structure(o["seed_ss"], seed_mask, seed_seqs, o["th_s1"], o["bp_update1"], "pipeline.add_each")
+        constraints += [None] * k
     chunks = pack_families([seed_each_bytes(seed_lens, columns, len(sq)) for sq in seqs], budget)
     th1 = o["th_s"] if o["th_s1"] is None else o["th_s1"]
     prm = capi.dd_params(w=o["w"], eta0=o["eta0"], th_a=o["th_a"], th_s=o["th_s"], t_max=o["t_max"], force_iters=o["force_iters"],
@@ -758,6 +821,9 @@ def add_each(seed_names, seed_rows, names, seqs, ctx=None, max_bytes=None, **opt
     out.iterations = np.full(k, -1, np.int64)
     out.lengths = np.array([len(sq) for sq in seqs], np.uint32)
     out.matched = np.zeros(k, np.uint32)
+    if seed_ss is not None:
+        out.support = dict(both=np.zeros(k, np.uint32), canonical=np.zeros(k, np.uint32), half=np.zeros(k, np.uint32),
+                           expected=np.zeros(k, np.float64))
     secs = dict(phase1=0.0, gather=0.0, transforms=0.0, nodes=0.0, final=0.0)
     own = ctx is None
     t_start = time.perf_counter()
@@ -767,7 +833,7 @@ def add_each(seed_names, seed_rows, names, seqs, ctx=None, max_bytes=None, **opt
             ctx = capi.Context(0)
         # phase 1 once: the folding beside the pair posteriors of the pairs (x, y) with x < m, no transform
         src.set_sequences(seed_seqs + seqs)
-        src.fold_begin(0.01)
+        src.fold_begin(0.01, constraints=constraints)
         try:
             src.align_posteriors(o["align_model"], o["th_a"], 0, m * (m + k) - m * (m + 1) // 2, fetch=False)
         finally:
@@ -806,7 +872,11 @@ def add_each(seed_names, seed_rows, names, seqs, ctx=None, max_bytes=None, **opt
                 rf[seed_col] = True
                 alns.append((np.concatenate([[f * n + m], np.arange(f * n, f * n + m)]).astype(np.uint32), mask))
                 rfs.append(rf)
-            decoded = ctx.consensus_structures(alns, th1)
+            if seed_ss is None:
+                decoded = ctx.consensus_structures(alns, th1)
+            else:  # nothing is decoded: the seed's structure in every family's merged columns (seed columns where rf is set)
+                decoded = [(None, carry_structure(seed_ss, np.flatnonzero(rf).astype(np.uint32), len(rf))) for rf in rfs]
+                support = ctx.structure_support(alns, [ss for _, ss in decoded])
             rows_ss = [None] * len(chunk)
             if o["row_structures"]:
                 lens = {f * n + i: ln for f, j in enumerate(chunk) for i, ln in enumerate(seed_lens + [len(seqs[j])])}
@@ -818,6 +888,10 @@ def add_each(seed_names, seed_rows, names, seqs, ctx=None, max_bytes=None, **opt
                 res.rf = rfs[f]
                 res.dd_log = {0: (oj["iterations"], oj["violated"], oj["ncbp"], oj["score"])}
                 res.dd_memory = dd_memory
+                if seed_ss is not None:
+                    res.support = _printed_support(support[f], alns[f][0])
+                    for key in out.support:  # the new sequence is the first row of its alignment
+                        out.support[key][j] = support[f][key][0]
                 _final(ctx, res, seed_names + [names[j]], seed_seqs + [seqs[j]], f * n, alns[f][0], alns[f][1], th1, o["bp_update1"],
                        o["reliability"], None, rfs[f], covariation, decoded[f][1], rows_ss[f])
                 out.results[j] = res

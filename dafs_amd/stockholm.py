@@ -19,7 +19,8 @@ sequences added to a seed (pipeline.add, `dafs --seed`) has no tree line, so no 
 PP_cons.
 
 read_seed reads a seed alignment for pipeline.add: Stockholm or aligned FASTA; a file the library
-refuses raises SeedError with the message `dafs --seed` prints."""
+refuses raises SeedError with the message `dafs --seed` prints.  read_seed_structure also returns the seed's consensus
+structure."""
 import ctypes as C
 
 import numpy as np
@@ -112,3 +113,42 @@ def read_seed(path):
     (clean_seed): (names, rows), '-' for gaps"""
     with open(path, "rb") as fh:
         return clean_seed(*parse_seed(fh.read()))
+
+
+def parse_seed_structure(text):
+    """parse_seed with the seed's consensus structure: (names, rows, structure), the structure as the
+    file holds it -- the `#=GC SS_cons` lines of a Stockholm seed's first alignment concatenated over its blocks, the record
+    named SS_cons of an aligned-FASTA seed -- or None when the file has none."""
+    data = text.encode("latin-1") if isinstance(text, str) else bytes(text)
+    n, has = C.c_uint32(), C.c_int()
+    got = capi.host_text(capi._seed_parse_structure, data, len(data), C.byref(n), C.byref(has), outs=3, refusal=SeedError)
+    return capi.split_lines(got[0], n.value), capi.split_lines(got[1], n.value), got[2] if has.value else None
+
+
+def clean_seed_structure(names, rows, structure):
+    """clean_seed with the structure's characters: (names, rows, ss), ss a uint32 array over the cleaned columns, the partner
+    column at the left column of a pair and 0xFFFFFFFF elsewhere.  `()`, `<>`, `[]`, `{}` are pairs, each kind matched with
+    its own kind; letters and `. , : _ - ~` are unpaired; a pair that loses a column with the all-gap columns is dropped.
+    Refuses (SeedError) what clean_seed refuses, any other character, a length that is not the rows', an unbalanced kind and
+    pairs that cross once all kinds are merged."""
+    names, rows = list(names), list(rows)
+    if len(names) != len(rows):
+        raise SeedError("seed: one name per row")
+    st = structure.encode("latin-1") if isinstance(structure, str) else bytes(structure)
+    if b"\0" in st:
+        raise SeedError("seed: SS_cons holds a NUL byte")
+    ss = np.zeros(max(len(rows[0]) if rows else 0, 1), np.uint32)
+    cols = C.c_uint32()
+    cleaned = capi.host_text(capi._seed_clean_structure, len(rows), capi.c_strings(names), capi.c_strings(rows), st, ss.ctypes.data,
+                             C.byref(cols), refusal=SeedError)
+    return names, capi.split_lines(cleaned, len(rows)), ss[:cols.value].copy()
+
+
+def read_seed_structure(path):
+    """read_seed with the seed's consensus structure: (names, rows, ss), ss as clean_seed_structure returns it, None when the
+    file has no structure"""
+    with open(path, "rb") as fh:
+        names, rows, structure = parse_seed_structure(fh.read())
+    if structure is None:
+        return clean_seed(names, rows) + (None,)
+    return clean_seed_structure(names, rows, structure)

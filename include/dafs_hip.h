@@ -221,6 +221,14 @@ int dafs_hip_fold_posteriors(dafs_hip_ctx* ctx, int model, float th);
  * most of the device idle at N < #CUs. */
 int dafs_hip_fold_posteriors_begin(dafs_hip_ctx* ctx, int model, float th);
 int dafs_hip_fold_posteriors_end(dafs_hip_ctx* ctx);
+/* The same under per-sequence constraints: constraints[x] NULL or empty folds sequence x free, exactly
+ * as dafs_hip_fold_posteriors_begin does (which is the case constraints = NULL); otherwise it is len[x] characters of "?.()"
+ * as in dafs_hip_fold_posterior_dense.  _end is shared.  DAFS_HIP_EINVAL, with the sequence index in dafs_hip_last_error, for a
+ * short string, an unknown character, unbalanced brackets, and a forced pair whose residues CONTRAfold cannot pair
+ * (dafs_host_fold_complementary): the recursions exclude such a pair and the posterior is then no probability.  The context
+ * stays usable after a refusal. */
+int dafs_hip_fold_posteriors_constrained_begin(dafs_hip_ctx* ctx, int model, float th, const char* const* constraints);
+int dafs_hip_fold_posteriors_constrained(dafs_hip_ctx* ctx, int model, float th, const char* const* constraints);
 /* Single-sequence call replacing CONTRAfold<float>::ComputePosterior (src/contrafold/wrapper.cpp:181-200)
  * and, with a constraint string of len chars from "?.()" ('?' free, '.' unpaired, brackets forced),
  * Fold::Model::calculate(seq, str, bp) (src/fold.cpp:191-207).  post: (len+1)(len+2)/2 floats,
@@ -291,6 +299,32 @@ int dafs_host_seed_table(uint32_t n, const char* const* headers, const uint32_t*
  * nor a gap, a row without residues), then the rows without their all-gap columns, '-' for every gap. */
 int dafs_host_seed_parse(const char* text, size_t bytes, uint32_t* n, char** names, char** rows);
 int dafs_host_seed_clean(uint32_t n, const char* const* names, const char* const* rows, char** cleaned);
+/* The same reader with the seed's consensus structure.  _parse_structure: also the structure's characters
+ * as the file holds them -- the "#=GC SS_cons" lines of a Stockholm seed's first alignment, concatenated over its blocks in
+ * order; the record named SS_cons of an aligned-FASTA seed -- and *has_structure = 1, or an empty text and 0 when the file has
+ * none.  _clean_structure: dafs_host_seed_clean's checks and rows; then the structure over the cleaned columns into ss (room
+ * for strlen(rows[0]) entries; the first *columns are written): the partner column at the left column of a pair,
+ * DAFS_HIP_NONE elsewhere.  "()", "<>", "[]", "{}" are pairs, each kind matched with its own kind; letters and ". , : _ - ~"
+ * are unpaired; a pair that loses a column with the all-gap columns is dropped.  Refused (DAFS_HIP_EINVAL, message in
+ * dafs_hip_last_error): any other character, a length that is not the rows', an unbalanced kind, pairs that cross once all
+ * kinds are merged. */
+int dafs_host_seed_parse_structure(const char* text, size_t bytes, uint32_t* n, int* has_structure, char** names, char** rows,
+                                   char** structure);
+int dafs_host_seed_clean_structure(uint32_t n, const char* const* names, const char* const* rows, const char* structure,
+                                   uint32_t* ss, uint32_t* columns, char** cleaned);
+/* 1 when CONTRAfold can pair the two residues: AU, UA, GC, CG, GU, UG in either case.  Its alphabet is "ACGU": T is not U
+ * there, so a pair with a T is not complementary (dafs_amd/csrc/contrafold.hip, cf_comp on the loaded symbols). */
+int dafs_host_fold_complementary(char a, char b);
+/* The folding constraint that the structure ss (len columns, as above) puts on one row: mask_row[len]
+ * marks the row's residues, residues holds them (as many characters as mask_row has non-zero bytes, else DAFS_HIP_EINVAL), out
+ * receives one character per residue and a NUL.  '?' everywhere; '(' and ')' at the two residues of a pair of ss when the row
+ * holds both, they are complementary (dafs_host_fold_complementary) and at least 4 residues apart (j - i >= 4). */
+int dafs_host_row_constraint(uint32_t len, const uint8_t* mask_row, const uint32_t* ss, const char* residues, char* out);
+/* dafs_host_seed_table with the structure support of every placed sequence (dafs_hip_structure_support) as four more columns,
+ * "pairs canonical half expected" (expected as %.9g); all four arrays NULL: the table of dafs_host_seed_table. */
+int dafs_host_seed_table_support(uint32_t n, const char* const* headers, const uint32_t* length, const uint32_t* matched,
+                                 const double* score, const int64_t* iterations, const uint32_t* both, const uint32_t* canonical,
+                                 const uint32_t* half, const double* expected, char** table);
 /* Estimated device memory (bytes) of one family's phase-1 stores and of one resident node; the default budget of a sub-batch
  * of families or a chunk of pairs.  _pack_greedy: group_of[k] is the group of item k, groups filled in input order up to
  * max_bytes, an item over the budget alone. */
@@ -473,6 +507,23 @@ int dafs_hip_update_basepairing(dafs_hip_ctx* ctx, uint32_t n, uint32_t len, con
 int dafs_hip_alignment_reliability(dafs_hip_ctx* ctx, uint32_t n, uint32_t len, const uint32_t* seq, const uint8_t* mask,
                                    const uint32_t* ss, int mp_relaxed, int bp_relaxed, double* res_rel, double* col_rel,
                                    double* pair_rel, uint32_t* pair_rows, double* expected_accuracy);
+
+/* How far every row of an alignment keeps a given structure, for nalign alignments laid out as in
+ * dafs_hip_consensus_structures (n_rows, len, seq, mask), ss holding their len[a] entries one after another (the convention
+ * of dafs_hip_alignment_reliability).  Per row r (sequence x), over the pairs c1 -> c2 of its alignment's ss in ascending c1,
+ * with i, j the residues of r at the two columns (outputs [sum of n_rows], rows in the given order; any may be NULL):
+ *   both       pairs of which the row holds both residues
+ *   canonical  those of `both` whose residues CONTRAfold can pair (dafs_host_fold_complementary)
+ *   half       pairs of which the row holds exactly one residue
+ *   expected   the sum over the `both` pairs of bp[x](i, j) from the base-pairing store the progressive phase reads now, 0 for
+ *              a pair that is not stored; each term widened to double and added in ascending c1, no contraction
+ * DAFS_HIP_EINVAL before any launch (outputs untouched, context usable): a row count or length of 0, an unknown sequence, a
+ * mask that does not place every residue of its sequence, a bad ss, an invalid store or a folding in flight.  The call reads
+ * no matching store, so a relaxed matching store that holds listed pairs only (dafs_hip_consistency_match_pairs) is no
+ * obstacle. */
+int dafs_hip_structure_support(dafs_hip_ctx* ctx, uint32_t nalign, const uint32_t* n_rows, const uint32_t* len, const uint32_t* seq,
+                               const uint8_t* mask, const uint32_t* ss, uint32_t* both, uint32_t* canonical, uint32_t* half,
+                               double* expected);
 
 /* Covariation statistics of an alignment (no counterpart in the reference; definitions, to the bit, in DESIGN.md section 13
  * "Covariation").  The call reads the alignment and the structure alone, none of the context's stores.
