@@ -166,6 +166,9 @@ _stockholm_block = _sig("dafs_host_stockholm_block", C.c_int, [C.c_char_p, C.c_u
                                                                 C.c_char_p, C.c_void_p, C.c_char_p, _text])
 _stockholm_block_rows = _sig("dafs_host_stockholm_block_rows", C.c_int, [C.c_char_p, C.c_uint32, C.c_uint32, _strs, _strs, C.POINTER(C.c_void_p),
                                                                           C.c_void_p, C.c_char_p, C.c_void_p, C.c_char_p, _strs, _text])
+_stockholm_block_merged = _sig("dafs_host_stockholm_block_merged", C.c_int, [C.c_uint32, C.c_uint32, _strs, _strs, C.POINTER(C.c_void_p), C.c_char_p,
+                                                                              C.c_void_p, C.c_void_p, _text])
+_merged_refusal = _sig("dafs_host_merged_refusal", C.c_char_p, [])
 _cov_code = _sig("dafs_host_cov_code", C.c_uint8, [C.c_char])
 _cov_ss_cons = _sig("dafs_host_cov_ss_cons", C.c_int, [C.c_uint32, C.c_void_p, C.c_void_p, C.c_double, _text])
 _covariation_table = _sig("dafs_host_covariation_table", C.c_int, [C.c_uint32, C.c_uint32] + [C.c_void_p] * 10 + [_text])
@@ -184,6 +187,8 @@ _node_bytes = _sig("dafs_host_node_bytes", C.c_uint64, [C.c_uint32, C.c_uint32])
 _batch_bytes = _sig("dafs_host_batch_bytes", C.c_uint64, [])
 _structure_bytes = _sig("dafs_host_structure_bytes", C.c_uint64, [C.c_uint32, C.c_uint32])
 _structures_batch_bytes = _sig("dafs_host_structures_batch_bytes", C.c_uint64, [])
+_reliability_bytes = _sig("dafs_host_reliability_bytes", C.c_uint64, [C.c_uint32, C.c_uint32])
+_reliability_batch_bytes = _sig("dafs_host_reliability_batch_bytes", C.c_uint64, [])
 _pack_greedy = _sig("dafs_host_pack_greedy", C.c_int, [C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p])
 _set_mp = _sig("dafs_hip_set_mp", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])
 _nodes_open = _sig("dafs_hip_nodes_open", C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(NodeInput), C.POINTER(DDParams), C.c_void_p])
@@ -202,6 +207,8 @@ _consensus_structures = _sig("dafs_hip_consensus_structures", C.c_int,
                              [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p])
 _alignment_reliability = _sig("dafs_hip_alignment_reliability", C.c_int,
                               [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5)
+_alignment_reliabilities = _sig("dafs_hip_alignment_reliabilities", C.c_int,
+                                [C.c_void_p, C.c_uint32] + [C.c_void_p] * 6 + [C.c_int, C.c_int] + [C.c_void_p] * 5)
 _alignment_covariation = _sig("dafs_hip_alignment_covariation", C.c_int,
                               [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64] + [C.c_void_p] * 11)
 # dafs_allgather_fn(user, send, recv, bytes, hip_stream): the caller's collective of a sharded phase 1
@@ -476,7 +483,8 @@ class Context:
 
     def consistency_match_pairs(self, w_pct_a, pair_ids):
         """dafs_hip_consistency_match_pairs: the matching transform for the strictly ascending pair ids `pair_ids` of the
-        context only; the other pairs of the relaxed store stay empty and alignment_reliability refuses to read it."""
+        context only; the other pairs of the relaxed store stay empty, and alignment_reliabilities refuses an alignment that
+        needs one."""
         ids = np.ascontiguousarray(pair_ids, np.uint64).reshape(-1)
         check(_consistency_match_pairs(self._h, w_pct_a, len(ids), ids.ctypes.data if len(ids) else None))
 
@@ -708,6 +716,53 @@ class Context:
                                      -1 if mp_relaxed is None else int(mp_relaxed), -1 if bp_relaxed is None else int(bp_relaxed),
                                      res.ctypes.data, col.ctypes.data, pair.ctypes.data, rows.ctypes.data, C.byref(ea)))
         return dict(residue=res, col=col, pair=pair, pair_rows=rows, expected_accuracy=ea.value)
+
+    def alignment_reliabilities(self, alns, sss=None, want=None, mp_relaxed=None, bp_relaxed=None, residue=None):
+        """dafs_hip_alignment_reliabilities: the reliability of many alignments in one call.  alns: a list of (seq, mask) as
+        consensus_structures takes them; sss: per alignment its ss or None (no pairs), or None for no pairs anywhere; want:
+        per alignment a bool per row (None: every row of it), or None for every row; mp_relaxed / bp_relaxed as in
+        alignment_reliability.  Returns per alignment the dict alignment_reliability returns for it, bit for bit; the residue
+        values of a row that is not wanted keep what `residue` held (a writable C-contiguous float64 array over all residues,
+        written in place and refused otherwise; default zeros), and col and expected_accuracy of an alignment with such a row
+        are NaN."""
+        als = [(np.ascontiguousarray(s, np.uint32).reshape(-1), np.ascontiguousarray(m, np.uint8)) for s, m in alns]
+        if any(m.ndim != 2 or m.shape[0] != len(s) for s, m in als):
+            raise ValueError("alignment_reliabilities: every alignment is (seq[n], mask[n, len])")
+        if sss is not None and (len(sss) != len(als) or any(x is not None and np.shape(x) != (m.shape[1],) for x, (_, m) in zip(sss, als))):
+            raise ValueError("alignment_reliabilities: one structure per alignment, one entry per column")
+        if want is not None and (len(want) != len(als) or any(x is not None and np.shape(x) != (len(s),) for x, (s, _) in zip(want, als))):
+            raise ValueError("alignment_reliabilities: one want entry per row")
+        if not als:
+            return []
+        n_rows = np.array([m.shape[0] for _, m in als], np.uint32)
+        lens = np.array([m.shape[1] for _, m in als], np.uint32)
+        seq = np.ascontiguousarray(np.concatenate([s for s, _ in als]), np.uint32)
+        mask = np.ascontiguousarray(np.concatenate([m.reshape(-1) for _, m in als]), np.uint8)
+        ss = None
+        if sss is not None and any(x is not None for x in sss):
+            ss = np.ascontiguousarray(np.concatenate([np.full(m.shape[1], 0xFFFFFFFF, np.uint32) if x is None else np.asarray(x, np.uint32)
+                                                      for x, (_, m) in zip(sss, als)]), np.uint32)
+        w8 = None
+        if want is not None and any(x is not None for x in want):
+            w8 = np.ascontiguousarray(np.concatenate([np.ones(len(s), np.uint8) if x is None else np.asarray(x, bool).astype(np.uint8)
+                                                      for x, (s, _) in zip(want, als)]), np.uint8)
+        nres = [m.astype(bool).sum(1) for _, m in als]  # per alignment, per row
+        total, L = int(sum(int(x.sum()) for x in nres)), int(lens.sum())
+        res = np.zeros(max(total, 1), np.float64) if residue is None else residue
+        if residue is not None and not (isinstance(res, np.ndarray) and res.dtype == np.float64 and res.flags.c_contiguous and res.flags.writeable
+                                        and res.shape == (total,)):  # written in place: no copy may stand in for it
+            raise ValueError("alignment_reliabilities: residue is a writable C-contiguous float64 array with one entry per residue of every row")
+        col = np.zeros(max(L, 1), np.float64); pair = np.zeros(max(L, 1), np.float64); rows = np.zeros(max(L, 1), np.uint32)
+        ea = np.zeros(len(als), np.float64)
+        check(_alignment_reliabilities(self._h, len(als), n_rows.ctypes.data, lens.ctypes.data, seq.ctypes.data, mask.ctypes.data,
+                                       None if ss is None else ss.ctypes.data, None if w8 is None else w8.ctypes.data,
+                                       -1 if mp_relaxed is None else int(mp_relaxed), -1 if bp_relaxed is None else int(bp_relaxed),
+                                       res.ctypes.data, col.ctypes.data, pair.ctypes.data, rows.ctypes.data, ea.ctypes.data))
+        rcut = np.cumsum([int(x.sum()) for x in nres])[:-1]
+        ccut = np.cumsum(lens)[:-1]
+        per = [np.split(v[:n], cut) for v, n, cut in ((res, total, rcut), (col, L, ccut), (pair, L, ccut), (rows, L, ccut))]
+        return [dict(residue=per[0][a], col=per[1][a], pair=per[2][a], pair_rows=per[3][a], expected_accuracy=float(ea[a]))
+                for a in range(len(als))]
 
 
     def alignment_covariation(self, rows, ss=None, shuffles=100, seed=1, matrix=False):

@@ -203,6 +203,7 @@ static int consistency_parts(dafs_hip_ctx* c, float w_pct_a, float w_pct_s, int 
     mp_store& out = c->mp[1];
     out.valid = false;
     out.listed = list != nullptr;
+    out.listed_pairs = plist;
     out.n_tasks = all;
     out.pair_x = raw.pair_x;
     out.pair_y = raw.pair_y;
@@ -308,7 +309,8 @@ extern "C" int dafs_hip_consistency_match_range(dafs_hip_ctx* c, float w_pct_a, 
   return consistency_parts(c, w_pct_a, 0.0f, 2, pair_begin, pair_end);
 }
 // The same for an arbitrary strictly ascending list of output pairs: the relaxed store is marked as holding listed pairs only
-// (mp_store::listed), which dafs_hip_alignment_reliability refuses to read.
+// (mp_store::listed, the list in mp_store::listed_pairs); dafs_hip_alignment_reliabilities reads it only where every pair it
+// needs is listed.
 extern "C" int dafs_hip_consistency_match_pairs(dafs_hip_ctx* c, float w_pct_a, uint64_t npairs, const uint64_t* pair_ids) {
   if (w_pct_a == 0.0f || npairs == 0 || !pair_ids) return DAFS_HIP_EINVAL;
   return consistency_parts(c, w_pct_a, 0.0f, 2, 0, 0, false, npairs, pair_ids);

@@ -54,6 +54,8 @@ struct dev_buf {
 struct mp_store {
   bool valid = false;
   bool listed = false;  // a relaxed store of dafs_hip_consistency_match_pairs: the pairs outside its list are empty, not zero
+  std::vector<uint32_t> listed_pairs;  // with listed: that list, ascending pair ids
+  bool holds(uint32_t pair) const { return !listed || std::binary_search(listed_pairs.begin(), listed_pairs.end(), pair); }
   uint64_t n_tasks = 0, rp_total = 0, pool_used = 0, pool_cap_hint = 0;
   std::vector<uint32_t> pair_x, pair_y;   // per pair of the shard, shard order
   std::vector<uint32_t> task_of_pair;     // shard-order pair -> task (processing order)

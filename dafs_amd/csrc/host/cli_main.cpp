@@ -77,6 +77,7 @@ struct Options {
   std::string seed;       // --seed SEED: add FILE's sequences to this alignment
   bool seed_each = false;       // --seed-each: with --seed, every sequence of FILE added on its own
   std::string seed_scores;      // --seed-scores OUT
+  std::string seed_merged;      // --seed-merged OUT: with --seed-each and --seed-structure, all placements in one Stockholm block
   bool seed_structure = false;  // --seed-structure: with --seed, the seed's SS_cons is fixed like its columns
   bool pairwise = false;  // --pairwise: every pair of FILE's sequences aligned as a two-sequence run
   std::string pairwise_scores;  // --pairwise-scores OUT
@@ -122,6 +123,11 @@ const char* kHelp =
     "                        j name length matched inserted score iterations (residues in seed columns and in columns of\n"
     "                        their own; the objective and iterations of the sequence's node)\n"
     "                        With --seed-structure four more columns: pairs canonical half expected\n"
+    "      --seed-merged OUT With --seed-each and --seed-structure: also write all placements as one alignment to OUT, one\n"
+    "                        Stockholm block: the seed rows, then the new rows in file order, each placed as --seed-each places\n"
+    "                        it; an insert block as wide as the widest insert there, new rows left-justified in it; #=GR PP for\n"
+    "                        the new rows (each from its own placement), SS_cons the seed's, and a #=GC RF line.  OUT can be\n"
+    "                        read again as a SEED\n"
     "      --seed-structure  With --seed (and --seed-each): the seed's consensus structure -- the #=GC SS_cons lines of a\n"
     "                        Stockholm seed, the SS_cons record of an aligned-FASTA seed -- is fixed like its columns: the seed\n"
     "                        rows are folded under it, nothing is decoded, and the printed SS_cons is the seed's with '.' at\n"
@@ -180,7 +186,7 @@ Options parse(int argc, char** argv) {
       {"bp-update", {0, false}}, {"bp-update1", {0, false}}, {"fold-aux", {0, true}}, {"save-align-aux", {0, true}},
       {"save-fold-aux", {0, true}}, {"device", {0, true}}, {"devices", {0, true}}, {"input", {0, true}},
       {"stockholm", {0, true}}, {"row-structures", {0, false}}, {"seed", {0, true}}, {"pairwise", {0, false}}, {"pairwise-scores", {0, true}},
-      {"seed-each", {0, false}}, {"seed-scores", {0, true}}, {"seed-structure", {0, false}},
+      {"seed-each", {0, false}}, {"seed-scores", {0, true}}, {"seed-merged", {0, true}}, {"seed-structure", {0, false}},
       {"covariation", {0, true}}, {"cov-shuffles", {0, true}}, {"cov-seed", {0, true}}};
   std::map<char, std::string> shorts;
   for (const auto& kv : spec)
@@ -256,6 +262,10 @@ Options parse(int argc, char** argv) {
       if (value.empty()) throw std::string("--seed-scores needs a file name");
       o.seed_scores = value;
     }
+    else if (name == "seed-merged") {
+      if (value.empty()) throw std::string("--seed-merged needs a file name");
+      o.seed_merged = value;
+    }
     else if (name == "pairwise") o.pairwise = true;
     else if (name == "pairwise-scores") {
       if (value.empty()) throw std::string("--pairwise-scores needs a file name");
@@ -287,6 +297,8 @@ Options parse(int argc, char** argv) {
   if (!o.pairwise_scores.empty() && !o.pairwise) throw std::string("--pairwise-scores needs --pairwise");
   if (o.seed_each && o.seed.empty()) throw std::string("--seed-each needs --seed");
   if (!o.seed_scores.empty() && !o.seed_each) throw std::string("--seed-scores needs --seed-each");
+  if (!o.seed_merged.empty() && !o.seed_each) throw std::string("--seed-merged needs --seed-each");
+  if (!o.seed_merged.empty() && !o.seed_structure) throw std::string(dafs_host_merged_refusal());
   if (o.seed_structure) {  // the structure is the seed's: nothing is decoded, so nothing sets a decoder's threshold
     if (o.seed.empty()) throw std::string("--seed-structure needs --seed");
     if (o.bp_update1) throw std::string("--seed-structure: nothing is decoded; --bp-update1 cannot be combined with --seed-structure");
@@ -1040,45 +1052,83 @@ std::map<uint32_t, VU> row_structures(dafs_hip_ctx* ctx, const std::vector<Fasta
   return out;
 }
 
-// The common secondary structure of a final alignment (:1857-1871; no RNAalifold term here) and its output (:1876-1879,
-// :1584-1601) on os: ">SS_cons", the brackets, then the rows sorted by sequence index.  The structure is decoded over the
-// rows in the order root holds them.  fa: the context's sequences; ff: the family's, its first one at index first.  With sto,
-// also the family's Stockholm block: tree_line (nullptr: no CC line), rf (nullptr: no RF line).  With cov (--covariation), the
-// alignment's covariation table into *cov, and its cov_SS_cons line into the Stockholm block.  ss0: the first decode of the
-// alignment where the caller has it already (consensus_structures over many alignments); row_ss (--row-structures): per
-// sequence of the alignment its own structure (row_structures), written as the block's #=GR SS lines.
+// The common secondary structure of a final alignment (:1857-1871; no RNAalifold term here), decoded over the rows in the
+// order root holds them.  ss0: the first decode of the alignment where the caller has it already (consensus_structures over
+// many alignments).
+VU final_structure(dafs_hip_ctx* ctx, const Options& o, const ALN& root, const VU* ss0) {
+  std::vector<uint32_t> rs;
+  std::vector<uint8_t> rm;
+  flatten(root, rs, rm);
+  const uint32_t L = (uint32_t)root[0].second.size();
+  VU ss(L);
+  if (ss0) ss = *ss0;
+  else check(dafs_hip_consensus_structure(ctx, (uint32_t)root.size(), L, rs.data(), rm.data(), o.fold_th1[0], ss.data(), nullptr, nullptr));
+  if (o.bp_update1) {  // :1863-1869: re-estimate under the decoded structure, decode again (SparseNussinov::decode(p, ss, str))
+    std::vector<float> p((size_t)L * L);
+    check(dafs_hip_update_basepairing(ctx, (uint32_t)root.size(), L, rs.data(), rm.data(), ss.data(), p.data()));
+    check(dafs_hip_nussinov_decode(ctx, o.fold_th1[0], 0.0f, L, p.data(), nullptr, ss.data(), nullptr));
+  }
+  return ss;
+}
+
+// The reliabilities of many final alignments and their final structures in one library call (dafs_hip_alignment_reliabilities),
+// from the stores the progressive phase read (with --bp-update1 too: ss is the re-decoded one).  fa: the context's sequences.
+// first_row_only: only the first row of every alignment is wanted (the placed row of --seed-merged); col is NaN then.
+struct Reliability {
+  std::vector<double> rel, col;  // the residues of the rows in the order the alignment held them at the call; per column
+};
+void reliabilities(dafs_hip_ctx* ctx, const std::vector<Fasta>& fa, const std::vector<const ALN*>& alns, const std::vector<VU>& ss,
+                   bool first_row_only, std::vector<Reliability>& out) {
+  std::vector<uint32_t> n_rows, len, seq, all_ss;
+  std::vector<uint8_t> mask, want;
+  std::vector<uint32_t> rs;
+  std::vector<uint8_t> rm;
+  out.assign(alns.size(), Reliability());
+  size_t residues = 0;
+  for (size_t k = 0; k < alns.size(); ++k) {
+    flatten(*alns[k], rs, rm);
+    n_rows.push_back((uint32_t)alns[k]->size());
+    len.push_back((uint32_t)(*alns[k])[0].second.size());
+    seq.insert(seq.end(), rs.begin(), rs.end());
+    mask.insert(mask.end(), rm.begin(), rm.end());
+    all_ss.insert(all_ss.end(), ss[k].begin(), ss[k].end());
+    for (size_t r = 0; r < rs.size(); ++r) {
+      want.push_back(r == 0 || !first_row_only ? 1 : 0);
+      residues += fa[rs[r]].size();
+    }
+  }
+  std::vector<double> rel(residues ? residues : 1), col(all_ss.size() ? all_ss.size() : 1);
+  check(dafs_hip_alignment_reliabilities(ctx, (uint32_t)alns.size(), n_rows.data(), len.data(), seq.data(), mask.data(), all_ss.data(),
+                                         first_row_only ? want.data() : nullptr, -1, -1, rel.data(), col.data(), nullptr, nullptr, nullptr));
+  size_t at = 0, col_at = 0;
+  for (size_t k = 0; k < alns.size(); ++k) {
+    size_t tot = 0;
+    for (const auto& row : *alns[k]) tot += fa[row.first].size();
+    out[k].rel.assign(rel.begin() + at, rel.begin() + at + tot);
+    out[k].col.assign(col.begin() + col_at, col.begin() + col_at + len[k]);
+    at += tot;
+    col_at += len[k];
+  }
+}
+
+// The output of a final alignment with its final structure ss_final (:1876-1879, :1584-1601) on os: ">SS_cons", the brackets,
+// then the rows sorted by sequence index.  fa: the context's sequences; ff: the family's, its first one at index first.  With
+// sto, also the family's Stockholm block from rl (reliabilities, made while root held its rows in the present order): tree_line
+// (nullptr: no CC line), rf (nullptr: no RF line).  With cov (--covariation), the alignment's covariation table into *cov, and
+// its cov_SS_cons line into the Stockholm block.  row_ss (--row-structures): per sequence of the alignment its own structure
+// (row_structures), written as the block's #=GR SS lines.
 void finish_alignment(dafs_hip_ctx* ctx, const Options& o, const std::vector<Fasta>& fa, ALN& root, const std::vector<Fasta>& ff,
                       uint32_t first, std::ostream& os, std::string* sto, const std::string* tree_line, const std::vector<uint8_t>* rf,
-                      std::string* cov = nullptr, const VU* ss0 = nullptr, const std::map<uint32_t, VU>* row_ss = nullptr) {
+                      std::string* cov, const VU& ss_final, const Reliability* rl, const std::map<uint32_t, VU>* row_ss = nullptr) {
   std::string str;
-  VU ss_final;
-  std::vector<double> rel, col_rel;   // --stockholm: the reliabilities of this alignment and structure
-  std::map<uint32_t, size_t> rel_at;  // sequence -> its first residue in rel
+  std::map<uint32_t, size_t> rel_at;  // sequence -> its first residue in rl->rel
   {
-    std::vector<uint32_t> rs;
-    std::vector<uint8_t> rm;
-    flatten(root, rs, rm);
     const uint32_t L = (uint32_t)root[0].second.size();
-    VU ss(L);
-    if (ss0) ss = *ss0;
-    else check(dafs_hip_consensus_structure(ctx, (uint32_t)root.size(), L, rs.data(), rm.data(), o.fold_th1[0], ss.data(), nullptr, nullptr));
-    if (o.bp_update1) {  // :1863-1869: re-estimate under the decoded structure, decode again (SparseNussinov::decode(p, ss, str))
-      std::vector<float> p((size_t)L * L);
-      check(dafs_hip_update_basepairing(ctx, (uint32_t)root.size(), L, rs.data(), rm.data(), ss.data(), p.data()));
-      check(dafs_hip_nussinov_decode(ctx, o.fold_th1[0], 0.0f, L, p.data(), nullptr, ss.data(), nullptr));
-    }
     std::vector<char> buf(L + 1);
-    dafs_hip_make_brackets(L, ss.data(), buf.data());
+    dafs_hip_make_brackets(L, ss_final.data(), buf.data());
     str.assign(buf.data());
-    ss_final = ss;
-    if (sto) {  // from the stores the progressive phase read (with --bp-update1 too: ss is the re-decoded one)
-      size_t tot = 0;
-      for (uint32_t s0 : rs) { rel_at[s0] = tot; tot += fa[s0].size(); }
-      rel.resize(tot);
-      col_rel.resize(L);
-      check(dafs_hip_alignment_reliability(ctx, (uint32_t)root.size(), L, rs.data(), rm.data(), ss.data(), -1, -1, rel.data(), col_rel.data(),
-                                           nullptr, nullptr, nullptr));
-    }
+    size_t tot = 0;
+    for (const auto& row : root) { rel_at[row.first] = tot; tot += fa[row.first].size(); }
   }
 
   // output (:1876-1879, :1584-1601)
@@ -1105,7 +1155,7 @@ void finish_alignment(dafs_hip_ctx* ctx, const Options& o, const std::vector<Fas
     std::vector<const double*> rr;
     for (const auto& row : root) {
       names.push_back(all_names[row.first - first]);
-      rr.push_back(rel.data() + rel_at[row.first]);
+      rr.push_back(rl->rel.data() + rel_at[row.first]);
     }
     std::vector<std::string> rss;  // each row's own structure in the row's columns
     for (size_t r = 0; row_ss && r < root.size(); ++r) {
@@ -1117,8 +1167,8 @@ void finish_alignment(dafs_hip_ctx* ctx, const Options& o, const std::vector<Fas
         if (rows[r][c] != '-') line[c] = buf[k++];
       rss.push_back(line);
     }
-    check_text(dafs_host_stockholm_block_rows(tree_line ? tree_line->c_str() : nullptr, (uint32_t)rows.size(), (uint32_t)col_rel.size(),
-                                              c_strs(names).data(), c_strs(rows).data(), rr.data(), col_rel.data(), str.c_str(),
+    check_text(dafs_host_stockholm_block_rows(tree_line ? tree_line->c_str() : nullptr, (uint32_t)rows.size(), (uint32_t)rl->col.size(),
+                                              c_strs(names).data(), c_strs(rows).data(), rr.data(), rl->col.data(), str.c_str(),
                                               rf ? rf->data() : nullptr, cov ? cov_chars.c_str() : nullptr,
                                               row_ss ? c_strs(rss).data() : nullptr, &text));
     *sto = take(text);
@@ -1229,8 +1279,11 @@ int run_add(const Options& o, int align_model) {
   }
   VU carried;  // --seed-structure: nothing is decoded
   if (o.seed_structure) carried = carry_structure(seed_ss, seed_col, width);
+  const VU ss = final_structure(ctx, o, root, o.seed_structure ? &carried : nullptr);
+  std::vector<Reliability> rl(1);
+  if (!o.stockholm.empty()) reliabilities(ctx, fa, {&root}, {ss}, false, rl);
   finish_alignment(ctx, o, fa, root, fa, 0, std::cout, o.stockholm.empty() ? nullptr : &sto, nullptr, &rf, o.covariation.empty() ? nullptr : &cov,
-                   o.seed_structure ? &carried : nullptr, o.row_structures ? &row_ss : nullptr);
+                   ss, &rl[0], o.row_structures ? &row_ss : nullptr);
   std::cout.flush();
   if (!o.stockholm.empty()) write_stockholm(o.stockholm, {sto});
   if (!o.covariation.empty()) write_covariation(o.covariation, {cov}, nullptr);
@@ -1243,7 +1296,8 @@ int run_add(const Options& o, int align_model) {
 // sequences go in chunks under dafs_host_batch_bytes() (dafs_host_seed_each_bytes each) through a second context, where
 // dafs_hip_families_from gathers the chunk's families seed + [new]; then the transforms -- the matching transform for the pairs
 // (seed, new) alone unless --stockholm's reliabilities read the seed-seed rows --, one node per family in shared rounds,
-// run_add's merge per family and the structures of the chunk in one call.
+// run_add's merge per family and the structures of the chunk in one call.  --seed-merged: the placements' maps are kept, and
+// after the last chunk dafs_host_merge_added places all k into the seed at once.
 int run_add_each(const Options& o, int align_model) {
   std::vector<std::string> snames, srows;
   VU seed_ss;
@@ -1304,6 +1358,8 @@ int run_add_each(const Options& o, int align_model) {
   std::vector<uint32_t> sup_both(k, 0), sup_can(k, 0), sup_half(k, 0);  // --seed-structure: the support of each new sequence's row
   std::vector<double> sup_exp(k, 0.0);
   std::vector<std::string> sto_blocks, cov_tables, cov_headers;
+  std::vector<VU> all_z(k);                     // --seed-merged: every placement's map, kept until the last chunk is done,
+  std::vector<std::vector<double> > new_pp(k);  // and the residue values of its row in its own family
   for (uint32_t j0 = 0; j0 < k;) {
     uint32_t j1 = j0;
     while (j1 < k && chunk_of[j1] == chunk_of[j0]) ++j1;
@@ -1400,12 +1456,21 @@ int run_add_each(const Options& o, int align_model) {
       for (uint32_t x = 0; x < nf * n; ++x) every[x] = x;
       row_ss = row_structures(ctx, fa, every, o.fold_th1[0]);
     }
+    for (uint32_t f = 0; f < nf; ++f) ss[f] = final_structure(ctx, o, roots[f], &ss[f]);
+    // the annotation, once every structure is final: all rows of every family for --stockholm, or for --seed-merged alone the
+    // new row of every family (the first), which reads the listed pairs only
+    std::vector<Reliability> rl(nf);
+    if (!o.stockholm.empty() || !o.seed_merged.empty()) reliabilities(ctx, fa, ptrs, ss, o.stockholm.empty(), rl);
+    for (uint32_t f = 0; !o.seed_merged.empty() && f < nf; ++f) {
+      all_z[j0 + f] = zs[f];
+      new_pp[j0 + f].assign(rl[f].rel.begin(), rl[f].rel.begin() + lens[j0 + f]);
+    }
     for (uint32_t f = 0; f < nf; ++f) {
       const std::vector<Fasta> ff(fa.begin() + (size_t)f * n, fa.begin() + (size_t)(f + 1) * n);
       std::ostringstream os;
       std::string sto, cov;
       finish_alignment(ctx, o, fa, roots[f], ff, f * n, os, o.stockholm.empty() ? nullptr : &sto, nullptr, &rfs[f],
-                       o.covariation.empty() ? nullptr : &cov, &ss[f], o.row_structures ? &row_ss : nullptr);
+                       o.covariation.empty() ? nullptr : &cov, ss[f], &rl[f], o.row_structures ? &row_ss : nullptr);
       std::cout << "==> " << j0 + f + 1 << " <==" << std::endl << os.str();
       if (!o.stockholm.empty()) sto_blocks.push_back(sto);
       if (!o.covariation.empty()) { cov_tables.push_back(cov); cov_headers.push_back(std::to_string(j0 + f + 1)); }
@@ -1415,6 +1480,42 @@ int run_add_each(const Options& o, int align_model) {
   std::cout.flush();
   if (!o.stockholm.empty()) write_stockholm(o.stockholm, sto_blocks);
   if (!o.covariation.empty()) write_covariation(o.covariation, cov_tables, &cov_headers);
+  if (!o.seed_merged.empty()) {  // all k placements in one alignment: the seed rows, then the new rows
+    std::vector<uint32_t> z, seed_col(C), res_col;
+    for (uint32_t j = 0; j < k; ++j) z.insert(z.end(), all_z[j].begin(), all_z[j].end());
+    res_col.resize(z.size() ? z.size() : 1);
+    uint32_t width = 0;
+    check(dafs_host_merge_added(C, k, lens.data(), z.data(), seed_col.data(), res_col.data(), &width));
+    std::vector<std::string> headers, rows;
+    std::vector<const double*> rr(m, nullptr);
+    for (uint32_t r = 0; r < m; ++r) {
+      headers.push_back(snames[r]);
+      rows.push_back(std::string(width, '-'));
+      for (uint32_t c = 0; c < C; ++c) rows.back()[seed_col[c]] = srows[r][c];
+    }
+    for (uint32_t j = 0, off = 0; j < k; off += lens[j], ++j) {
+      headers.push_back(added[j].name());
+      rows.push_back(std::string(width, '-'));
+      const std::string& sq = added[j].seq();
+      for (uint32_t i = 0; i < lens[j]; ++i) rows.back()[res_col[off + i]] = sq[i];
+      rr.push_back(new_pp[j].data());
+    }
+    std::vector<uint8_t> rf(width, 0);
+    for (uint32_t c = 0; c < C; ++c) rf[seed_col[c]] = 1;
+    const VU carried = carry_structure(seed_ss, seed_col, width);
+    std::vector<char> brackets(width + 1);
+    dafs_hip_make_brackets(width, carried.data(), brackets.data());
+    char* text = nullptr;
+    check_text(dafs_host_stockholm_names((uint32_t)headers.size(), c_strs(headers).data(), &text));
+    const std::vector<std::string> names = lines_of(take(text), headers.size());
+    check_text(dafs_host_stockholm_block_merged(m + k, width, c_strs(names).data(), c_strs(rows).data(), rr.data(), brackets.data(), rf.data(),
+                                                nullptr, &text));
+    std::ofstream ms(o.seed_merged.c_str(), std::ios::binary);
+    if (!ms.is_open()) throw "--seed-merged: cannot open " + o.seed_merged;
+    ms << take(text);
+    ms.flush();
+    if (!ms) throw "--seed-merged: cannot write " + o.seed_merged;
+  }
   if (!o.seed_scores.empty()) {
     std::ofstream ts(o.seed_scores.c_str(), std::ios::binary);
     if (!ts.is_open()) throw "--seed-scores: cannot open " + o.seed_scores;
@@ -1772,6 +1873,10 @@ int align_group(dafs_hip_ctx* ctx, const Options& o, Ranks& rk, int align_model,
     for (uint x = 0; x < N; ++x) every[x] = x;
     row_ss = row_structures(ctx, fa, every, o.fold_th1[0]);
   }
+  // the annotation of all of them in one call, once every structure is final (-r and --bp-update1 are behind it)
+  for (uint f = 0; f < F; ++f) ss0[f] = final_structure(ctx, o, *roots[f], &ss0[f]);
+  std::vector<Reliability> rl(F);
+  if (!sto.empty()) reliabilities(ctx, fa, roots, ss0, false, rl);
   for (uint f = 0; f < F; ++f) {
     ALN& root = aln[tbase[f + 1] - 1];
     std::string tree_line;
@@ -1781,7 +1886,7 @@ int align_group(dafs_hip_ctx* ctx, const Options& o, Ranks& rk, int align_model,
       tree_line = tl.str();
     }
     finish_alignment(ctx, o, fa, root, fams[members[f]], first[f], *out[f], sto.empty() ? nullptr : sto[f], &tree_line, nullptr,
-                     cov.empty() ? nullptr : cov[f], &ss0[f], row_ss.empty() ? nullptr : &row_ss);
+                     cov.empty() ? nullptr : cov[f], ss0[f], &rl[f], row_ss.empty() ? nullptr : &row_ss);
   }
   return 0;
 }

@@ -111,6 +111,42 @@ std::string stockholm_block(const char* tree_line, const std::vector<std::string
   return out;
 }
 
+// The merged alignment of a --seed-each run: all rows, then the PP lines of the rows that have values
+// (rel[r] not null: the placed rows), SS_cons, PP_cons, RF.  PP_cons is the mean over those rows' values per column, a running
+// double sum in row order, '.' where none of them has a residue; col_out (optional) receives the means, NaN for '.'.
+std::string stockholm_block_merged(const std::vector<std::string>& names, const std::vector<std::string>& rows, const double* const* rel,
+                                   uint32_t len, const std::string& ss, const uint8_t* rf, double* col_out) {
+  size_t width = std::string("#=GC SS_cons").size();
+  for (size_t r = 0; r < rows.size(); ++r) width = std::max(width, names[r].size() + (rel[r] ? 8 : 0));  // "#=GR " + name + " PP"
+  ++width;
+  auto label = [&](const std::string& l) { return l + std::string(width - l.size(), ' '); };
+  std::string out = "# STOCKHOLM 1.0\n";
+  for (size_t r = 0; r < rows.size(); ++r) out += label(names[r]) + rows[r] + "\n";
+  std::vector<double> sum(len, 0.0);
+  std::vector<uint32_t> cnt(len, 0);
+  for (size_t r = 0; r < rows.size(); ++r) {
+    if (!rel[r]) continue;
+    std::string pp(len, '.');
+    for (size_t c = 0, k = 0; c < len; ++c)
+      if (rows[r][c] != '-') {
+        const double v = rel[r][k++];
+        pp[c] = pp_char(v);
+        sum[c] += v;
+        ++cnt[c];
+      }
+    out += label("#=GR " + names[r] + " PP") + pp + "\n";
+  }
+  std::string cons(len, '.'), line(len, '.');
+  for (size_t c = 0; c < len; ++c) {
+    const double mean = cnt[c] ? sum[c] / (double)cnt[c] : std::nan("");
+    if (cnt[c]) cons[c] = pp_char(mean);
+    if (col_out) col_out[c] = mean;
+    if (rf[c]) line[c] = 'x';
+  }
+  out += label("#=GC SS_cons") + ss + "\n" + label("#=GC PP_cons") + cons + "\n" + label("#=GC RF") + line + "\n//\n";
+  return out;
+}
+
 // --covariation
 const double kCovEMax = 0.05;  // the cut of the table's `other` pairs: fixed (e_max moves cov_SS_cons only)
 
@@ -329,6 +365,22 @@ extern "C" int dafs_host_stockholm_block(const char* tree_line, uint32_t n, uint
                                          const double* const* residue_rel, const double* col_rel, const char* ss, const uint8_t* rf,
                                          const char* cov, char** block) {
   return dafs_host_stockholm_block_rows(tree_line, n, len, names, rows, residue_rel, col_rel, ss, rf, cov, nullptr, block);
+}
+
+extern "C" int dafs_host_stockholm_block_merged(uint32_t n, uint32_t len, const char* const* names, const char* const* rows,
+                                                const double* const* residue_rel, const char* ss, const uint8_t* rf, double* col_rel, char** block) {
+  return text_out(block, [&]() {
+    const std::vector<std::string> nm = strings(n, names), rw = strings(n, rows);
+    if (!ss || (len && !rf) || (n && !residue_rel)) throw kBadArgument;
+    if (strlen(ss) != len) throw "stockholm block: the structure has " + std::to_string(strlen(ss)) + " columns, not " + std::to_string(len);
+    for (uint32_t r = 0; r < n; ++r)
+      if (rw[r].size() != len) throw "stockholm block: row " + nm[r] + " has " + std::to_string(rw[r].size()) + " columns, not " + std::to_string(len);
+    return stockholm_block_merged(nm, rw, residue_rel, len, ss, rf, col_rel);
+  });
+}
+
+extern "C" const char* dafs_host_merged_refusal(void) {
+  return "a merged alignment needs the seed's structure (--seed-structure, seed_ss): without it there is no structure to print";
 }
 
 extern "C" uint8_t dafs_host_cov_code(char ch) {
@@ -599,6 +651,21 @@ extern "C" uint64_t dafs_host_structure_bytes(uint32_t n_rows, uint32_t len) {
 // per chunk of dafs_hip_consensus_structures.  A choice, not a limit: 2 GiB hold some 3 500 pair alignments of 170 columns,
 // a dozen times what the device keeps resident at once, and the buffer stays with the context.
 extern "C" uint64_t dafs_host_structures_batch_bytes(void) { return 2ull << 30; }
+
+// Device memory of one alignment of n_rows rows and len columns inside dafs_hip_alignment_reliabilities (bytes), a bound that its
+// carving checks for every chunk (capi_reliability.cpp).  Per cell the mask byte, the column -> residue map and, for at most as
+// many residues, the residue -> column map and the value (17 bytes) and the residue blocks' share (1/8); per row its descriptor
+// and its last residue block (40); per column the structure, the three column outputs and the column blocks' share (under 25);
+// the alignment's descriptor and last column block (48); then the 256-byte alignment of a chunk's twelve arrays plus its slack,
+// which an alignment alone in its chunk carries all (under 3 400 bytes).
+extern "C" uint64_t dafs_host_reliability_bytes(uint32_t n_rows, uint32_t len) {
+  const uint64_t n = n_rows, l = len;
+  return 18 * n * l + 40 * n + 25 * l + 64 + 4096;
+}
+
+// per chunk of dafs_hip_alignment_reliabilities.  A choice, not a limit: 1 GiB holds some 100 000 pair alignments of 170
+// columns or 1 500 alignments of 33 rows and 1 000 columns, and the buffer stays with the context.
+extern "C" uint64_t dafs_host_reliability_batch_bytes(void) { return 1ull << 30; }
 
 // greedy, in input order: a group is closed before the item that would take it over max_bytes; an item over the budget
 // is a group of its own

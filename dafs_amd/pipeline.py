@@ -191,7 +191,7 @@ def _phase2_forest(ctx, own, fams, t, w, eta0, t_max, th_a, th_s, th_s1, force_i
     forest: a node is ready when both of its children are done, whatever its family, and the ready nodes of all families
     share each launch.  Returns one Result per family.
     reliability: each Result also gets .reliability, the annotation of its final alignment and structure from the stores
-    the progressive phase read (Context.alignment_reliability): a dict with residue (per printed row, its residues'
+    the progressive phase read (one Context.alignment_reliabilities call over all families): a dict with residue (per printed row, its residues'
     values), col, pair, pair_rows and expected_accuracy; and .stockholm, that alignment as a Stockholm block with PP lines
     (dafs_amd/stockholm.py: the block `dafs --stockholm` writes).  covariation: see _final.
     The first decode of every family's final alignment is one Context.consensus_structures call over all of them.
@@ -281,12 +281,13 @@ def _phase2_forest(ctx, own, fams, t, w, eta0, t_max, th_a, th_s, th_s1, force_i
     if row_structures:
         lens = {fm["first"] + i: len(sq) for fm in fams for i, sq in enumerate(fm["seqs"])}
         rows_ss = _row_structures(ctx, [sidx for sidx, _ in roots], lens, th1)
+    finals = [_final_structure(ctx, sidx, mask, th1, bp_update1, ss) for (sidx, mask), (_, ss) in zip(roots, decoded)]
+    rls = ctx.alignment_reliabilities(roots, finals) if reliability else [None] * nf  # once every structure is final
     for f, (fm, res) in enumerate(zip(fams, results)):
         res.levels = levels
         res.rounds = rounds
         sidx, mask = roots[f]
-        _final(ctx, res, fm["names"], fm["seqs"], fm["first"], sidx, mask, th1, bp_update1, reliability, res.tree_line, None, covariation,
-               decoded[f][1], rows_ss[f])
+        _final(ctx, res, fm["names"], fm["seqs"], fm["first"], sidx, mask, finals[f], rls[f], res.tree_line, None, covariation, rows_ss[f])
     t.append(time.perf_counter())
     # fold_launch: the folding is only started there; its kernels overlap `pair` and the first half of `pct_fold_tree`,
     # which also holds the wait for them
@@ -326,20 +327,23 @@ def _row_structures(ctx, sidx_per_alignment, lens, th):
     return out
 
 
-def _final(ctx, res, names, seqs, first, sidx, mask, th1, bp_update1, reliability, tree_line, rf=None, covariation=None, ss=None,
-           row_ss=None):
-    """The common structure of a final alignment (sidx: global sequence index per row, mask) and its output, into res:
-    .ss, .ss_str, .rows, .output and, with reliability, .reliability and .stockholm.  names / seqs: the family's, its first
-    sequence at global index `first`.  tree_line None: no tree line (pipeline.add); rf: the RF line of the Stockholm
-    block.  covariation (cov_options): .covariation, the dict of Context.alignment_covariation on the printed rows and
-    structure with the options' shuffles, seed and e_max beside the arrays; the Stockholm block then
-    carries a `#=GC cov_SS_cons` line.  ss: the first decode of the alignment where the caller has it already (a batched
-    Context.consensus_structures call).  row_ss: per printed row its own structure (_row_structures) -> .row_ss, .row_ss_str
-    and the `#=GR <name> SS` lines of the Stockholm block."""
-    if ss is None:
-        _, ss, _ = ctx.consensus_structure(sidx, mask, th1)
+def _final_structure(ctx, sidx, mask, th1, bp_update1, ss):
+    """The common structure of a final alignment (sidx: global sequence index per row, mask) from its first decode ss (a
+    batched Context.consensus_structures call)"""
     if bp_update1:  # :1863-1869: decode, re-estimate under that structure, decode again
         _, ss = ctx.nussinov(ctx.update_basepairing(sidx, mask, ss), None, th1)
+    return ss
+
+
+def _final(ctx, res, names, seqs, first, sidx, mask, ss, rl, tree_line, rf=None, covariation=None, row_ss=None):
+    """The output of a final alignment (sidx: global sequence index per row, mask) with its common structure ss
+    (_final_structure), into res: .ss, .ss_str, .rows, .output and, with rl, .reliability and .stockholm.  names / seqs: the
+    family's, its first sequence at global index `first`.  rl: the alignment's dict of Context.alignment_reliabilities for
+    (sidx, mask, ss), made by the caller in one call over all its alignments, or None for no annotation.  tree_line None: no
+    tree line (pipeline.add); rf: the RF line of the Stockholm block.  covariation (cov_options): .covariation, the dict of
+    Context.alignment_covariation on the printed rows and structure with the options' shuffles, seed
+    and e_max beside the arrays; the Stockholm block then carries a `#=GC cov_SS_cons` line.  row_ss: per printed row its own structure (_row_structures) -> .row_ss, .row_ss_str
+    and the `#=GR <name> SS` lines of the Stockholm block."""
     res.ss = ss
     res.ss_str = capi.make_brackets(ss)
     order = np.argsort(sidx, kind="stable")  # std::sort(aln) :1876
@@ -362,8 +366,8 @@ def _final(ctx, res, names, seqs, first, sidx, mask, th1, bp_update1, reliabilit
         cv.update(covariation)
         res.covariation = cv
         cov_chars = stockholm.cov_ss_cons(ss, cv["pair_e"], cv["e_max"])
-    if reliability:
-        rl = ctx.alignment_reliability(sidx, mask, ss)
+    if rl is not None:
+        rl = dict(rl)
         cuts = np.cumsum([len(seqs[int(s) - first]) for s in sidx])[:-1]
         per_row = np.split(rl["residue"], cuts)  # rows in the order of sidx
         rl["residue"] = [per_row[r] for r in order]
@@ -479,8 +483,11 @@ def add(seed_names, seed_rows, names, seqs, ctx=None, w=4.0, eta0=0.5, t_max=600
         ss_m = None if seed_ss is None else carry_structure(seed_ss, seed_col, width)
         if ss_m is not None:
             res.support = _printed_support(ctx.structure_support([(sidx, rows_mask)], [ss_m])[0], sidx)
-        _final(ctx, res, all_names, all_seqs, 0, sidx, rows_mask, th1, bp_update1, reliability, None, rf,
-               covariation, ss_m, _row_structures(ctx, [sidx], dict(enumerate(map(len, all_seqs))), th1)[0] if row_structures else None)
+        else:
+            ss_m = _final_structure(ctx, sidx, rows_mask, th1, bp_update1, ctx.consensus_structure(sidx, rows_mask, th1)[1])
+        rl = ctx.alignment_reliability(sidx, rows_mask, ss_m) if reliability else None
+        _final(ctx, res, all_names, all_seqs, 0, sidx, rows_mask, ss_m, rl, None, rf, covariation,
+               _row_structures(ctx, [sidx], dict(enumerate(map(len, all_seqs))), th1)[0] if row_structures else None)
         t.append(time.perf_counter())
         res.seconds = dict(phase1=t[3] - t[0], nodes=t[4] - t[3], final=t[5] - t[4], total=t[5] - t[0])
     finally:
@@ -761,7 +768,35 @@ class AddEach:
     pass
 
 
-def add_each(seed_names, seed_rows, names, seqs, ctx=None, max_bytes=None, **opts):
+class Merged:
+    pass
+
+
+def _merge_each(seed_names, seed_rows, seed_ss, names, seqs, zs, pps):
+    """The merged alignment of add_each from the k column maps zs and the k rows' residue values pps"""
+    m, k, columns = len(seed_rows), len(seqs), len(seed_rows[0])
+    seed_col, res_col, width = capi.merge_added(columns, zs)
+    mg = Merged()
+    mg.z, mg.pp = zs, pps
+    mg.names = stockholm.names(seed_names + names)
+    cells = np.full((m + k, width), ord("-"), np.uint8)
+    cells[:m, seed_col] = np.frombuffer("".join(seed_rows).encode("latin-1"), np.uint8).reshape(m, columns)
+    for j in range(k):
+        cells[m + j, res_col[j]] = np.frombuffer(seqs[j].encode("latin-1"), np.uint8)
+    mg.rows = [row.tobytes().decode("latin-1") for row in cells]
+    mg.rf = np.zeros(width, bool)
+    mg.rf[seed_col] = True
+    mg.ss = carry_structure(seed_ss, seed_col, width)
+    mg.ss_str = capi.make_brackets(mg.ss)
+    mg.stockholm, mg.col = stockholm.block_merged(mg.names, mg.rows, [None] * m + pps, mg.ss_str, mg.rf)
+    lines = [">SS_cons", mg.ss_str]
+    for nm, row in zip(seed_names + names, mg.rows):
+        lines += ["> " + nm, row]
+    mg.output = "\n".join(lines) + "\n"
+    return mg
+
+
+def add_each(seed_names, seed_rows, names, seqs, ctx=None, max_bytes=None, merged=False, **opts):
     """Each new sequence added to a fixed seed alignment on its own (`dafs --seed SEED --seed-each`).
     opts: the options of add().  results[j] is, bit for bit, what add(seed_names, seed_rows, [names[j]], [seqs[j]], **opts)
     returns (.output, .rows, .ss, .ss_str, .z, .rf, .dd_log and, when asked, .reliability / .stockholm / .row_ss* /
@@ -777,11 +812,19 @@ def add_each(seed_names, seed_rows, names, seqs, ctx=None, max_bytes=None, **opt
     object with .results (one Result per new sequence, in input order), .score and .iterations (the node's final objective
     and iteration count, dd_log's 4th and 1st entries), .lengths, .matched (residues that landed in seed columns), .chunks
     (indices per chunk), .dd_memory (per chunk the nodes' (reserved, in use, peak) bytes) and .seconds (phase1, gather,
-    transforms, nodes, final, total).
+    transforms, nodes, final, total; with merged, merge).
 
     seed_ss: as in add().  The seed rows are folded under their constraints once, in the source context; every result's
     structure is the seed's carried into its merged columns, and its .support comes from one Context.structure_support call
-    per chunk.  The object gains .support: per new sequence both, canonical, half and expected of its own row."""
+    per chunk.  The object gains .support: per new sequence both, canonical, half and expected of its own row.
+
+    merged (`dafs --seed-merged`; needs seed_ss): the object gains .merged, all k placements in one
+    alignment, beside the unchanged results.  Columns: capi.merge_added over the k maps, after the last chunk.  .names
+    (stockholm.names over the seed's and the new names), .rows (the m seed rows, then the k new rows in input order), .rf,
+    .ss / .ss_str (the seed's structure carried into the merged columns), .z (the k maps), .pp (per new row the residue
+    values of that row in its own family seed + [j]: one Context.alignment_reliabilities call per chunk that wants the new row
+    of every family, so the matching transform stays the listed one), .col (per column the mean of the new rows' values, NaN
+    where none has a residue), .stockholm (stockholm.block_merged) and .output (as add prints)."""
     import time
     o = {k: p.default for k, p in inspect.signature(add).parameters.items() if k not in ("seed_names", "seed_rows", "names", "seqs", "ctx")}
     unknown = set(opts) - set(o)
@@ -805,6 +848,8 @@ def add_each(seed_names, seed_rows, names, seqs, ctx=None, max_bytes=None, **opt
     columns = seed_mask.shape[1]
     seed_lens = [len(sq) for sq in seed_seqs]
     seed_ss, constraints = None, None
+    if merged and o["seed_ss"] is None:
+        raise ValueError(capi._merged_refusal().decode())
     if o["seed_ss"] is not None:
         seed_ss, constraints = _seed_structure(o["seed_ss"], seed_mask, seed_seqs, o["th_s1"], o["bp_update1"], "pipeline.add_each")
         constraints += [None] * k
@@ -821,6 +866,7 @@ def add_each(seed_names, seed_rows, names, seqs, ctx=None, max_bytes=None, **opt
     out.iterations = np.full(k, -1, np.int64)
     out.lengths = np.array([len(sq) for sq in seqs], np.uint32)
     out.matched = np.zeros(k, np.uint32)
+    pps = [None] * k  # merged: per new sequence the residue values of its row
     if seed_ss is not None:
         out.support = dict(both=np.zeros(k, np.uint32), canonical=np.zeros(k, np.uint32), half=np.zeros(k, np.uint32),
                            expected=np.zeros(k, np.float64))
@@ -881,6 +927,19 @@ def add_each(seed_names, seed_rows, names, seqs, ctx=None, max_bytes=None, **opt
             if o["row_structures"]:
                 lens = {f * n + i: ln for f, j in enumerate(chunk) for i, ln in enumerate(seed_lens + [len(seqs[j])])}
                 rows_ss = _row_structures(ctx, [sidx for sidx, _ in alns], lens, th1)
+            finals = [_final_structure(ctx, sidx, mask, th1, o["bp_update1"], ss) for (sidx, mask), (_, ss) in zip(alns, decoded)]
+            # the annotation, once every structure is final: all rows of every family, or for the merged alignment alone the new
+            # row of every family (the first), which reads the listed pairs only
+            rls = [None] * len(chunk)
+            if o["reliability"]:
+                rls = ctx.alignment_reliabilities(alns, finals)
+                new_pp = [rl["residue"][:len(seqs[j])] for rl, j in zip(rls, chunk)]
+            elif merged:
+                new_first = [np.arange(n) == 0] * len(chunk)
+                new_pp = [rl["residue"][:len(seqs[j])] for rl, j in zip(ctx.alignment_reliabilities(alns, finals, want=new_first), chunk)]
+            if merged:
+                for j, pp in zip(chunk, new_pp):
+                    pps[j] = pp.copy()
             for f, j in enumerate(chunk):
                 res = Result()
                 oj = outs[f]
@@ -892,8 +951,8 @@ def add_each(seed_names, seed_rows, names, seqs, ctx=None, max_bytes=None, **opt
                     res.support = _printed_support(support[f], alns[f][0])
                     for key in out.support:  # the new sequence is the first row of its alignment
                         out.support[key][j] = support[f][key][0]
-                _final(ctx, res, seed_names + [names[j]], seed_seqs + [seqs[j]], f * n, alns[f][0], alns[f][1], th1, o["bp_update1"],
-                       o["reliability"], None, rfs[f], covariation, decoded[f][1], rows_ss[f])
+                _final(ctx, res, seed_names + [names[j]], seed_seqs + [seqs[j]], f * n, alns[f][0], alns[f][1], finals[f], rls[f], None,
+                       rfs[f], covariation, rows_ss[f])
                 out.results[j] = res
                 out.score[j] = oj["score"]
                 out.iterations[j] = oj["iterations"]
@@ -905,6 +964,10 @@ def add_each(seed_names, seed_rows, names, seqs, ctx=None, max_bytes=None, **opt
         src.close()
         if own and ctx is not None:
             ctx.close()
+    if merged:
+        t_merge = time.perf_counter()
+        out.merged = _merge_each(seed_names, seed_rows, seed_ss, names, seqs, [r.z[0] for r in out.results], pps)
+        secs["merge"] = time.perf_counter() - t_merge
     secs["total"] = time.perf_counter() - t_start
     out.seconds = secs
     return out

@@ -20,7 +20,10 @@ PP_cons.
 
 read_seed reads a seed alignment for pipeline.add: Stockholm or aligned FASTA; a file the library
 refuses raises SeedError with the message `dafs --seed` prints.  read_seed_structure also returns the seed's consensus
-structure."""
+structure.
+
+block_merged writes the merged alignment of all placements of pipeline.add_each: the rows, then PP
+lines for the placed rows only, SS_cons, PP_cons over the placed rows, RF."""
 import ctypes as C
 
 import numpy as np
@@ -79,6 +82,25 @@ def block(tree_line, row_names, rows, residue_rel, col_rel, ss_str, rf=None, cov
     return capi.host_text(capi._stockholm_block_rows, text[0], len(rows), len(col), capi.c_strings(row_names), capi.c_strings(rows),
                           (C.c_void_p * max(len(rel), 1))(*[r.ctypes.data for r in rel]), col.ctypes.data, text[1],
                           None if rf8 is None else rf8.ctypes.data, text[2], None if row_ss is None else capi.c_strings(list(row_ss)))
+
+
+def block_merged(row_names, rows, residue_rel, ss_str, rf):
+    """The merged alignment of pipeline.add_each as one block (dafs_host_stockholm_block_merged): the rows,
+    then `#=GR <name> PP` for every row whose residue_rel entry is not None (the placed rows), `#=GC SS_cons`, `#=GC PP_cons`
+    (per column the mean of those rows' values, '.' where none has a residue), `#=GC RF`, `//`.  Returns (text, col): col the
+    means behind PP_cons, NaN for a '.' column."""
+    row_names, rows = list(row_names), list(rows)
+    rel = [None if r is None else np.ascontiguousarray(r, np.float64) for r in residue_rel]
+    if not len(row_names) == len(rel) == len(rows):
+        raise ValueError("stockholm.block_merged: one name and one reliability entry per row")
+    if any(r is not None and len(r) < len(row) - row.count("-") for r, row in zip(rel, rows)):
+        raise ValueError("stockholm.block_merged: one reliability per residue")
+    rf8 = np.ascontiguousarray(np.asarray(rf, bool), np.uint8)
+    col = np.zeros(max(len(rf8), 1), np.float64)
+    text = capi.host_text(capi._stockholm_block_merged, len(rows), len(rf8), capi.c_strings(row_names), capi.c_strings(rows),
+                          (C.c_void_p * max(len(rel), 1))(*[None if r is None else r.ctypes.data for r in rel]), ss_str.encode("latin-1"),
+                          rf8.ctypes.data, col.ctypes.data)
+    return text, col[:len(rf8)]
 
 
 class SeedError(ValueError):

@@ -276,6 +276,16 @@ int dafs_host_stockholm_block(const char* tree_line, uint32_t n, uint32_t len, c
 int dafs_host_stockholm_block_rows(const char* tree_line, uint32_t n, uint32_t len, const char* const* names, const char* const* rows,
                                    const double* const* residue_rel, const double* col_rel, const char* ss, const uint8_t* rf,
                                    const char* cov, const char* const* row_ss, char** block);
+/* The merged alignment of a --seed-each run as one Stockholm block: the n rows, then a "#=GR <name> PP"
+ * line for every row r with residue_rel[r] not NULL (the placed rows; a seed row has none), "#=GC SS_cons", "#=GC PP_cons",
+ * "#=GC RF" ('x' where rf is nonzero) and "//"; no "#=GF CC" line.  PP_cons: per column the mean of the values that the rows
+ * with a PP line hold there, a running double sum in row order; '.' for a column where none of them has a residue.  col_rel
+ * (len entries, or NULL) receives those means, NaN for a '.' column.  The labels are padded to the longest of the names, the
+ * "#=GR <name> PP" labels that are written and the "#=GC" labels, plus one. */
+int dafs_host_stockholm_block_merged(uint32_t n, uint32_t len, const char* const* names, const char* const* rows,
+                                     const double* const* residue_rel, const char* ss, const uint8_t* rf, double* col_rel, char** block);
+/* What both drivers say when a merged alignment is asked for without the seed's structure */
+const char* dafs_host_merged_refusal(void);
 /* The code of a residue for dafs_hip_alignment_covariation: A 0, C 1, G 2, U / T 3 in either case, everything else 4 */
 uint8_t dafs_host_cov_code(char residue);
 /* The cov_SS_cons characters: '2' at both columns of every pair of ss with pair_e <= e_max (a NaN never is), '.' elsewhere */
@@ -338,6 +348,9 @@ uint64_t dafs_host_seed_each_bytes(uint32_t m, const uint32_t* seed_lens, uint32
  * default budget of one of its chunks. */
 uint64_t dafs_host_structure_bytes(uint32_t n_rows, uint32_t len);
 uint64_t dafs_host_structures_batch_bytes(void);
+/* The same two for dafs_hip_alignment_reliabilities. */
+uint64_t dafs_host_reliability_bytes(uint32_t n_rows, uint32_t len);
+uint64_t dafs_host_reliability_batch_bytes(void);
 int dafs_host_pack_greedy(uint32_t n, const uint64_t* sizes, uint64_t max_bytes, uint32_t* group_of);
 
 /* ------------------------------------------------------------------------------------------
@@ -361,9 +374,9 @@ int dafs_hip_fourway_consistency(dafs_hip_ctx* ctx, float w_pct_f);
 int dafs_hip_consistency_match_range(dafs_hip_ctx* ctx, float w_pct_a, uint64_t pair_begin, uint64_t pair_end);
 /* The same for a list of output pairs: npairs >= 1 strictly ascending pair ids of the context (families one after another,
  * row-major inside each).  The listed pairs' relaxed rows are those of dafs_hip_consistency_match, bit for bit; the others are
- * empty (zero counts, offsets and row pointers).  The relaxed store is marked as holding listed pairs only until another call
- * produces it: dafs_hip_alignment_reliability refuses to read it (DAFS_HIP_EINVAL) instead of taking the empty pairs for zero
- * probabilities.  DAFS_HIP_EINVAL also for w_pct_a = 0, an empty list, an id that does not ascend or is not a pair of the
+ * empty (zero counts, offsets and row pointers).  The relaxed store is marked as holding listed pairs only, and keeps the list,
+ * until another call produces it: dafs_hip_alignment_reliabilities refuses an alignment that needs a pair outside the list
+ * (DAFS_HIP_EINVAL) instead of taking the empty pairs for zero probabilities.  DAFS_HIP_EINVAL also for w_pct_a = 0, an empty list, an id that does not ascend or is not a pair of the
  * context, and a missing or partial un-relaxed store. */
 int dafs_hip_consistency_match_pairs(dafs_hip_ctx* ctx, float w_pct_a, uint64_t npairs, const uint64_t* pair_ids);
 
@@ -496,8 +509,9 @@ int dafs_hip_update_basepairing(dafs_hip_ctx* ctx, uint32_t n, uint32_t len, con
  * residue of its sequence.  ss: the consensus structure over the len columns in the decoders' convention (ss[c] = right
  * partner at the left column, DAFS_HIP_NONE otherwise; every column in at most one pair), or NULL for no pairs.
  * mp_relaxed / bp_relaxed: 0 = the un-relaxed store (with -f the four-way result), 1 = the relaxed one, negative = the
- * store the progressive phase reads now; the matching store must be valid and hold every pair (not needed for n = 1), the
- * base-pairing store must be valid when ss is given.  Every sum is taken in double, rows in ascending sequence order, so
+ * store the progressive phase reads now; the matching store must be valid and hold every pair of the context, or every pair
+ * of these rows when it is a listed one (not needed for n = 1), the base-pairing store must be valid when ss is given, and no
+ * folding may be in flight.  Every sum is taken in double, rows in ascending sequence order, so
  * the order of the given rows changes no bit.  Outputs (host; any may be NULL):
  *   res_rel[sum of the rows' lengths]  rel(r, i): the rows in the given order, residues in sequence order (1.0 for n = 1)
  *   col_rel[len]                       mean of rel over the residues of each column (0 for a column of gaps)
@@ -507,6 +521,26 @@ int dafs_hip_update_basepairing(dafs_hip_ctx* ctx, uint32_t n, uint32_t len, con
 int dafs_hip_alignment_reliability(dafs_hip_ctx* ctx, uint32_t n, uint32_t len, const uint32_t* seq, const uint8_t* mask,
                                    const uint32_t* ss, int mp_relaxed, int bp_relaxed, double* res_rel, double* col_rel,
                                    double* pair_rel, uint32_t* pair_rows, double* expected_accuracy);
+/* The same for nalign alignments in one call, laid out as in dafs_hip_consensus_structures (n_rows, len,
+ * seq, mask) and dafs_hip_structure_support (ss: the len[a] entries of every alignment one after another, or NULL for no pairs
+ * anywhere).  Rows of different alignments may belong to different families and a sequence may sit in many alignments.
+ * want: one byte per row, nonzero = compute its residue values; NULL = every row.  Outputs (host; any may be NULL):
+ *   res_rel            the residues of all rows one after another, rows in the given order; the entries of a row that is not
+ *                      wanted are left untouched
+ *   col_rel, pair_rel, pair_rows   the len[a] entries of every alignment one after another
+ *   expected_accuracy[nalign]
+ * col_rel and expected_accuracy of an alignment with a row that is not wanted are NaN.  Every value that is computed equals, bit
+ * for bit, what dafs_hip_alignment_reliability returns for that alignment's rows, which is this call with nalign = 1.
+ * The matching store (needed by an alignment of more than one row) must be valid and whole, or a relaxed store of
+ * dafs_hip_consistency_match_pairs whose list holds every pair (x, y) with x a wanted row and y another row of x's alignment.
+ * The alignments run in chunks under a budget of device memory (dafs_host_reliability_batch_bytes; DAFS_HIP_REL_BATCH_BYTES
+ * overrides it), three launches per chunk; the chunking changes no result.  DAFS_HIP_EINVAL before any launch (outputs
+ * untouched, context usable): a row count or length of 0, an unknown sequence, a sequence twice in one alignment, rows of two
+ * families in one alignment, a mask that does not place every residue of its sequence, a bad ss, an invalid or partial store, a
+ * needed pair that a listed store does not hold, or a folding in flight. */
+int dafs_hip_alignment_reliabilities(dafs_hip_ctx* ctx, uint32_t nalign, const uint32_t* n_rows, const uint32_t* len, const uint32_t* seq,
+                                     const uint8_t* mask, const uint32_t* ss, const uint8_t* want, int mp_relaxed, int bp_relaxed,
+                                     double* res_rel, double* col_rel, double* pair_rel, uint32_t* pair_rows, double* expected_accuracy);
 
 /* How far every row of an alignment keeps a given structure, for nalign alignments laid out as in
  * dafs_hip_consensus_structures (n_rows, len, seq, mask), ss holding their len[a] entries one after another (the convention
