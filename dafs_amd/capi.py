@@ -211,6 +211,19 @@ _alignment_reliabilities = _sig("dafs_hip_alignment_reliabilities", C.c_int,
                                 [C.c_void_p, C.c_uint32] + [C.c_void_p] * 6 + [C.c_int, C.c_int] + [C.c_void_p] * 5)
 _alignment_covariation = _sig("dafs_hip_alignment_covariation", C.c_int,
                               [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64] + [C.c_void_p] * 11)
+_alignment_identity = _sig("dafs_hip_alignment_identity", C.c_int,
+                           [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double] + [C.c_void_p] * 7)
+_alignment_weights = _sig("dafs_hip_alignment_weights", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p])
+_nr_select = _sig("dafs_host_nr_select", C.c_int, [C.c_uint32] + [C.c_void_p] * 5)
+_ali_code = _sig("dafs_host_ali_code", C.c_uint8, [C.c_char])
+_identity_summary = _sig("dafs_host_identity_summary", C.c_int, [C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p])
+_identity_table = _sig("dafs_host_identity_table", C.c_int, [C.c_uint32, C.c_uint32, _strs] + [C.c_void_p] * 6 + [_text])
+_identity_matrix_table = _sig("dafs_host_identity_matrix_table", C.c_int, [C.c_uint32, _strs] + [C.c_void_p] * 3 + [_text])
+_stockholm_weights = _sig("dafs_host_stockholm_weights", C.c_int, [C.c_char_p, C.c_uint32, _strs, C.c_void_p, _text])
+_stockholm_nr = _sig("dafs_host_stockholm_nr", C.c_int, [C.c_char_p, C.c_uint32, _strs, C.c_void_p, C.c_uint32, C.c_double, _text])
+_alistat_refusal = _sig("dafs_host_alistat_refusal", C.c_char_p, [C.c_int])
+NO_PAIRWISE, NR_NEEDS_MERGED, NR_THRESHOLD, TOO_MANY_ROWS = range(4)  # dafs_host_alistat_refusal
+_seed_table_nearest = _sig("dafs_host_seed_table_nearest", C.c_int, [C.c_uint32, _strs] + [C.c_void_p] * 8 + [_strs, C.c_void_p, _text])
 # dafs_allgather_fn(user, send, recv, bytes, hip_stream): the caller's collective of a sharded phase 1
 _allgather_fn = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 _phase1_sharded = _sig("dafs_hip_phase1_sharded", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_float, C.c_float, C.c_float,
@@ -269,6 +282,89 @@ def encode_alignment(rows):
     if not rows or any(len(r) != len(rows[0]) for r in rows):
         raise ValueError("encode_alignment: at least one row, all of one length")
     return _COV_CODE[np.frombuffer(b"".join(rows), np.uint8)].reshape(len(rows), len(rows[0]))
+
+
+_ALI_CODE = np.array([_ali_code(bytes([i])) for i in range(256)], np.uint8)
+
+
+def encode_cells(rows):
+    """Alignment text (equally long rows) -> the uint8 [n, len] cells of Context.alignment_identity / alignment_weights
+    (DESIGN.md section 18): A 0, C 1, G 2, U / T 3 in either case, any other letter 4, '-' and '.' 5; anything else is refused."""
+    rows = [r.encode("latin-1") if isinstance(r, str) else bytes(r) for r in rows]
+    if not rows or any(len(r) != len(rows[0]) for r in rows):
+        raise ValueError("encode_cells: at least one row, all of one length")
+    cell = _ALI_CODE[np.frombuffer(b"".join(rows), np.uint8)].reshape(len(rows), len(rows[0]))
+    if (cell == 255).any():
+        r, c = np.argwhere(cell == 255)[0]
+        raise ValueError("encode_cells: row %d, column %d holds neither a letter nor a gap" % (r + 1, c + 1))
+    return cell
+
+
+def _cells(rows, who):
+    """text rows or a 2-D integer array of cell codes -> uint8 [n, len]"""
+    if isinstance(rows, np.ndarray):
+        if rows.ndim != 2 or rows.dtype.kind not in "iu":
+            raise ValueError("%s: rows are text rows or a 2-D integer array of cells" % who)
+        if rows.size and (rows.min() < 0 or rows.max() > 255):
+            raise ValueError("%s: cells must fit a byte (the library refuses a code above 5)" % who)
+        return np.ascontiguousarray(rows, np.uint8)
+    return encode_cells(rows)
+
+
+def _byte_mask(mask, size, who, what):
+    if mask is None:
+        return None
+    mask = np.ascontiguousarray(np.asarray(mask) != 0, np.uint8)
+    if mask.shape != (size,):
+        raise ValueError("%s: %s" % (who, what))
+    return mask
+
+
+def alistat_refusal(which):
+    """what both drivers say when they refuse a combination of the alignment statistics' options (dafs_host_alistat_refusal)"""
+    return _alistat_refusal(which).decode()
+
+
+class Identity:
+    """Result of Context.alignment_identity: .res, .nearest (NONE without a candidate), .nearest_ident, .nearest_den,
+    .pid_nearest (NaN without a candidate); with matrix, .ident and .aligned ([n, n]); with nr, .red ([n, ceil(n / 32)] bits)."""
+
+    def bit(self, r, s):
+        """red(r, s)"""
+        return bool((int(self.red[r, s // 32]) >> (s % 32)) & 1)
+
+
+def nr_select(red, rank, forced=None):
+    """dafs_host_nr_select: the non-redundant subset from the bit matrix red ([n, ceil(n / 32)] uint32),
+    visiting the rows in the order rank (a permutation, else ValueError); forced rows are always kept.  Returns (kept as bool
+    [n], by as uint32 [n]: the first kept row that removes a dropped one, NONE for a kept row)."""
+    red = np.ascontiguousarray(red, np.uint32)
+    n = red.shape[0] if red.ndim == 2 else 0
+    if n == 0 or red.shape[1] != (n + 31) // 32:
+        raise ValueError("nr_select: red is a [n, ceil(n / 32)] bit matrix")
+    rank = np.ascontiguousarray(rank, np.uint32).reshape(-1)
+    if len(rank) != n:
+        raise ValueError("nr_select: the visiting order is not a permutation of the rows")
+    forced = _byte_mask(forced, n, "nr_select", "forced needs one entry per row")
+    kept = np.zeros(n, np.uint8)
+    by = np.zeros(n, np.uint32)
+    rc = _nr_select(n, red.ctypes.data, rank.ctypes.data, None if forced is None else forced.ctypes.data, kept.ctypes.data, by.ctypes.data)
+    if rc == -1:
+        raise ValueError(_last_error().decode("latin-1"))
+    check(rc)
+    return kept.astype(bool), by
+
+
+def identity_summary(ident, res):
+    """dafs_host_identity_summary: (average, minimum, maximum) pid over the pairs r < s; three NaN for one row"""
+    ident = np.ascontiguousarray(ident, np.uint32)
+    res = np.ascontiguousarray(res, np.uint32)
+    n = len(res)
+    if ident.shape != (n, n):
+        raise ValueError("identity_summary: ident is the [n, n] matrix of the rows of res")
+    out = np.zeros(3, np.float64)
+    check(_identity_summary(n, ident.ctypes.data, res.ctypes.data, out.ctypes.data))
+    return tuple(float(x) for x in out)
 
 
 class PairPosteriors:
@@ -622,10 +718,10 @@ class Context:
 
     def stage_report(self):
         """{kernel: (ms summed over its launches, longest launch ms, launches)} since the last report"""
-        buf = (StageTime * 32)()
+        buf = (StageTime * 64)()
         n = C.c_uint32()
-        check(_stage_report(self._h, buf, 32, C.byref(n)))
-        return {buf[k].kernel.decode(): (buf[k].ms, buf[k].longest_ms, buf[k].launches) for k in range(min(n.value, 32))}
+        check(_stage_report(self._h, buf, 64, C.byref(n)))
+        return {buf[k].kernel.decode(): (buf[k].ms, buf[k].longest_ms, buf[k].launches) for k in range(min(n.value, 64))}
 
     def nodes_demotions(self):
         """split-mode nodes that lost their folding workgroups and went on in the one-workgroup form (since nodes_close)"""
@@ -796,6 +892,47 @@ class Context:
         if matrix:
             out["g"] = g
         return out
+
+
+    def alignment_identity(self, rows, use=None, cand=None, nr=None, matrix=False, nearest=True):
+        """How identical the rows of an alignment are (dafs_hip_alignment_identity).  rows: the text
+        rows, or their cells (uint8 [n, len], encode_cells).  use: the columns that count (None: all); cand: the rows that may
+        be somebody's nearest (None: all); nr: the threshold of the redundancy bit matrix (None: none); matrix: the whole
+        ident and aligned matrices too; nearest=False: no nearest rows (their pass is not run; the three arrays and
+        pid_nearest are absent).  Returns an Identity."""
+        cell = _cells(rows, "alignment_identity")
+        n, L = cell.shape
+        use = _byte_mask(use, L, "alignment_identity", "use needs one entry per column")
+        cand = _byte_mask(cand, n, "alignment_identity", "cand needs one entry per row")
+        if nr is not None and not (0.0 < float(nr) <= 1.0):
+            raise ValueError(alistat_refusal(NR_THRESHOLD))
+        out = Identity()
+        out.res = np.zeros(n, np.uint32)
+        near = [np.zeros(n, np.uint32) for _ in range(3)] if nearest else [None] * 3
+        ident = np.zeros((n, n), np.uint32) if matrix else None
+        aligned = np.zeros((n, n), np.uint32) if matrix else None
+        red = np.zeros((n, (n + 31) // 32), np.uint32) if nr is not None else None
+        ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+        check(_alignment_identity(self._h, n, L, cell.ctypes.data, ptr(use), ptr(cand), 0.0 if nr is None else float(nr), ptr(out.res),
+                                  ptr(ident), ptr(aligned), ptr(near[0]), ptr(near[1]), ptr(near[2]), ptr(red)))
+        if nearest:
+            out.nearest, out.nearest_ident, out.nearest_den = near
+            with np.errstate(invalid="ignore", divide="ignore"):
+                out.pid_nearest = np.where(out.nearest == NONE, np.nan, out.nearest_ident.astype(np.float64) / out.nearest_den.astype(np.float64))
+        if matrix:
+            out.ident, out.aligned = ident, aligned
+        if nr is not None:
+            out.red = red
+        return out
+
+    def alignment_weights(self, rows, use=None):
+        """Position-based sequence weights of an alignment's rows (dafs_hip_alignment_weights): float64 [n]"""
+        cell = _cells(rows, "alignment_weights")
+        n, L = cell.shape
+        use = _byte_mask(use, L, "alignment_weights", "use needs one entry per column")
+        weight = np.zeros(n, np.float64)
+        check(_alignment_weights(self._h, n, L, cell.ctypes.data, None if use is None else use.ctypes.data, weight.ctypes.data))
+        return weight
 
 
 def fold_complementary(a, b):

@@ -86,6 +86,12 @@ struct Options {
   uint64_t cov_seed = 1;        // --cov-seed S
   bool cov_shuffles_given = false, cov_seed_given = false;
   bool refinement_given = false;
+  std::string identity;         // --identity OUT
+  std::string identity_matrix;  // --identity-matrix OUT
+  bool seed_nearest = false;    // --seed-nearest: two more columns in --seed-scores
+  double seed_nr = 0.0;         // --seed-nr T: --seed-merged holds the non-redundant block
+  bool seed_nr_given = false;
+  std::string describe;         // --describe ALIGNMENT: the alignment-only statistics of a finished alignment
   std::string input;
   std::vector<std::string> inputs;  // every FILE argument; with two or more, one output block per file
 };
@@ -146,6 +152,24 @@ const char* kHelp =
     "                        With --stockholm a #=GC cov_SS_cons line marks the pairs with E <= 0.05.  Not with --pairwise\n"
     "      --cov-shuffles K  Shuffled alignments behind E (default: 100; 0: no E-values); needs --covariation\n"
     "      --cov-seed S      Seed of the shuffles (default: 1); needs --covariation\n"
+    "      --identity OUT    Also write how similar the rows of every printed alignment are to OUT: the line\n"
+    "                        \"# rows n columns len average A min B max C\" (pairwise identity over all row pairs), then one\n"
+    "                        tab-separated line per row: r name residues weight nearest nearest_name pid (1-based rows; residues:\n"
+    "                        cells that hold a letter; weight: position-based sequence weight; nearest: the most identical other\n"
+    "                        row; pid: identical columns / the shorter of the two rows' residue counts).  With --stockholm the\n"
+    "                        blocks gain #=GS <name> WT lines.  At most 32768 rows (the summary reads the whole identity\n"
+    "                        matrix).  Not with --pairwise or --seed-each\n"
+    "      --identity-matrix OUT  With --identity: one tab-separated line per row pair:\n"
+    "                        r s name_r name_s identical aligned residues pid\n"
+    "      --seed-nearest    With --seed-each and --seed-scores: two more columns at the end of the table, the seed row most\n"
+    "                        identical to the new sequence in the seed's columns of its own placement, and that identity\n"
+    "      --seed-nr T       With --seed-merged: OUT holds the non-redundant rows only: the seed rows, then, by descending score,\n"
+    "                        every new row that is less than T (0 < T <= 1) identical, in the seed's columns, to every row kept\n"
+    "                        before it; a line \"#=GF CC nr T kept K of M hits\" precedes the rows\n"
+    "      --describe ALIGNMENT  No FILE: read a finished alignment (Stockholm or aligned FASTA, as --seed reads it, with its\n"
+    "                        SS_cons if it has one) and write --identity / --identity-matrix and, if given, --covariation for\n"
+    "                        it (--identity: at most 32768 rows); nothing is aligned and nothing is printed.  Only --device and\n"
+    "                        the --cov-* options go with it\n"
     "\n Aligning options:\n"
     "  -a, --align-model arg Alignment model (value=CONTRAlign, ProbCons) (default: ProbCons)\n"
     "  -p, --align-pct arg   Weight of PCT for matching probabilities (default: 0.25)\n"
@@ -187,12 +211,14 @@ Options parse(int argc, char** argv) {
       {"save-fold-aux", {0, true}}, {"device", {0, true}}, {"devices", {0, true}}, {"input", {0, true}},
       {"stockholm", {0, true}}, {"row-structures", {0, false}}, {"seed", {0, true}}, {"pairwise", {0, false}}, {"pairwise-scores", {0, true}},
       {"seed-each", {0, false}}, {"seed-scores", {0, true}}, {"seed-merged", {0, true}}, {"seed-structure", {0, false}},
-      {"covariation", {0, true}}, {"cov-shuffles", {0, true}}, {"cov-seed", {0, true}}};
+      {"covariation", {0, true}}, {"cov-shuffles", {0, true}}, {"cov-seed", {0, true}}, {"identity", {0, true}},
+      {"identity-matrix", {0, true}}, {"seed-nearest", {0, false}}, {"seed-nr", {0, true}}, {"describe", {0, true}}};
   std::map<char, std::string> shorts;
   for (const auto& kv : spec)
     if (kv.second.first) shorts[kv.second.first] = kv.first;
   std::vector<float> gamma, gamma1;
   bool th_given = false, th1_given = false;
+  std::vector<std::string> given;  // every option as it was named, for --describe
   for (int i = 1; i < argc; ++i) {
     std::string arg = argv[i], name, value;
     bool have_value = false;
@@ -215,6 +241,7 @@ Options parse(int argc, char** argv) {
       if (i + 1 >= argc) throw std::string("Option requires a value: ") + arg;
       value = argv[++i];
     }
+    given.push_back(name);
     if (name == "help") { std::cout << kHelp << std::endl; exit(0); }
     else if (name == "version") { std::cout << "DAFS version " << DAFS_VERSION << std::endl; exit(0); }
     else if (name == "refinement") { o.refinement = std::stoi(value); o.refinement_given = true; }
@@ -275,6 +302,21 @@ Options parse(int argc, char** argv) {
       if (value.empty()) throw std::string("--covariation needs a file name");
       o.covariation = value;
     }
+    else if (name == "identity" || name == "identity-matrix" || name == "describe") {
+      if (value.empty()) throw "--" + name + " needs a file name";
+      (name == "identity" ? o.identity : name == "describe" ? o.describe : o.identity_matrix) = value;
+    }
+    else if (name == "seed-nearest") o.seed_nearest = true;
+    else if (name == "seed-nr") {
+      size_t used = 0;
+      try {
+        o.seed_nr = std::stod(value, &used);
+      } catch (const std::exception&) {
+        used = 0;
+      }
+      if (used == 0 || used != value.size() || !(o.seed_nr > 0.0 && o.seed_nr <= 1.0)) throw std::string(dafs_host_alistat_refusal(DAFS_ALISTAT_NR_THRESHOLD));
+      o.seed_nr_given = true;
+    }
     else if (name == "cov-shuffles" || name == "cov-seed") {
       size_t used = 0;
       unsigned long long v = 0;
@@ -294,6 +336,18 @@ Options parse(int argc, char** argv) {
   if ((o.cov_shuffles_given || o.cov_seed_given) && o.covariation.empty()) throw std::string("--cov-shuffles and --cov-seed need --covariation");
   if (o.pairwise && (!o.covariation.empty() || o.cov_shuffles_given || o.cov_seed_given))
     throw std::string("--pairwise: two rows carry no covariation; --covariation, --cov-shuffles and --cov-seed cannot be combined with --pairwise");
+  if (!o.describe.empty()) {  // a finished alignment: nothing that aligns, and no FILE
+    for (const std::string& g : given)
+      if (g != "describe" && g != "identity" && g != "identity-matrix" && g != "covariation" && g != "cov-shuffles" && g != "cov-seed" && g != "device")
+        throw "--describe reads a finished alignment: --" + g + " cannot be combined with --describe";
+    if (!o.inputs.empty()) throw std::string("--describe takes no FILE: the alignment is its argument");
+    if (o.identity.empty() && o.covariation.empty()) throw std::string("--describe needs --identity or --covariation");
+  }
+  if (!o.identity_matrix.empty() && o.identity.empty()) throw std::string("--identity-matrix needs --identity");
+  if (o.pairwise && !o.identity.empty()) throw std::string(dafs_host_alistat_refusal(DAFS_ALISTAT_NO_PAIRWISE));
+  if (o.seed_each && !o.identity.empty()) throw std::string("--seed-each: --identity cannot be combined with --seed-each (--seed-nearest names each new sequence's nearest seed row)");
+  if (o.seed_nearest && (!o.seed_each || o.seed_scores.empty())) throw std::string("--seed-nearest needs --seed-each and --seed-scores");
+  if (o.seed_nr_given && o.seed_merged.empty()) throw std::string(dafs_host_alistat_refusal(DAFS_ALISTAT_NR_NEEDS_MERGED));
   if (!o.pairwise_scores.empty() && !o.pairwise) throw std::string("--pairwise-scores needs --pairwise");
   if (o.seed_each && o.seed.empty()) throw std::string("--seed-each needs --seed");
   if (!o.seed_scores.empty() && !o.seed_each) throw std::string("--seed-scores needs --seed-each");
@@ -338,7 +392,7 @@ Options parse(int argc, char** argv) {
       o.fold_th1 = o.fold_th;
     }
   }
-  if (o.input.empty()) { std::cout << kHelp << std::endl; exit(0); }
+  if (o.input.empty() && o.describe.empty()) { std::cout << kHelp << std::endl; exit(0); }
   return o;
 }
 
@@ -686,6 +740,60 @@ void write_covariation(const std::string& file, const std::vector<std::string>& 
   if (!os) throw "--covariation: cannot write " + file;
 }
 
+// --identity: how similar the rows of one printed alignment are (dafs_hip_alignment_identity, dafs_hip_alignment_weights;
+// DESIGN.md section 18)
+struct IdentityText {
+  std::string table, matrix;    // the tables of --identity and --identity-matrix
+  std::vector<double> weight;   // the WT lines of the Stockholm block
+};
+
+std::vector<uint8_t> cells_of(const std::vector<std::string>& rows) {
+  const size_t L = rows.empty() ? 0 : rows[0].size();
+  std::vector<uint8_t> cell(rows.size() * L);
+  for (size_t r = 0; r < rows.size(); ++r)
+    for (size_t c = 0; c < L; ++c) cell[r * L + c] = dafs_host_ali_code(rows[r][c]);
+  return cell;
+}
+
+// names: the rows' Stockholm names; matrix: the pair table too
+void identity_of(dafs_hip_ctx* ctx, const std::vector<std::string>& names, const std::vector<std::string>& rows, bool matrix, IdentityText& out) {
+  const uint32_t n = (uint32_t)rows.size(), L = (uint32_t)rows[0].size();
+  if (n > 32768) throw std::string(dafs_host_alistat_refusal(DAFS_ALISTAT_TOO_MANY_ROWS));  // the summary reads the whole matrix
+  const std::vector<uint8_t> cell = cells_of(rows);
+  std::vector<uint32_t> res(n), near(n), ni(n), nd(n), ident((size_t)n * n), aligned(matrix ? (size_t)n * n : 0);
+  check(dafs_hip_alignment_identity(ctx, n, L, cell.data(), nullptr, nullptr, 0.0, res.data(), ident.data(), matrix ? aligned.data() : nullptr,
+                                    near.data(), ni.data(), nd.data(), nullptr));
+  out.weight.assign(n, 0.0);
+  check(dafs_hip_alignment_weights(ctx, n, L, cell.data(), nullptr, out.weight.data()));
+  double summary[3];
+  check(dafs_host_identity_summary(n, ident.data(), res.data(), summary));
+  char* text = nullptr;
+  check_text(dafs_host_identity_table(n, L, c_strs(names).data(), res.data(), out.weight.data(), near.data(), ni.data(), nd.data(), summary, &text));
+  out.table = take(text);
+  if (matrix) {
+    check_text(dafs_host_identity_matrix_table(n, c_strs(names).data(), res.data(), ident.data(), aligned.data(), &text));
+    out.matrix = take(text);
+  }
+}
+
+void write_tables(const std::string& option, const std::string& file, const std::vector<std::string>& tables, const std::vector<std::string>* headers) {
+  std::ofstream os(file.c_str(), std::ios::binary);
+  if (!os.is_open()) throw option + ": cannot open " + file;
+  for (size_t k = 0; k < tables.size(); ++k) {
+    if (headers) os << "==> " << (*headers)[k] << " <==\n";
+    os << tables[k];
+  }
+  os.flush();
+  if (!os) throw option + ": cannot write " + file;
+}
+
+void write_identity(const Options& o, const std::vector<IdentityText>& idt, const std::vector<std::string>* headers) {
+  std::vector<std::string> tables, matrices;
+  for (const IdentityText& t : idt) { tables.push_back(t.table); matrices.push_back(t.matrix); }
+  write_tables("--identity", o.identity, tables, headers);
+  if (!o.identity_matrix.empty()) write_tables("--identity-matrix", o.identity_matrix, matrices, headers);
+}
+
 void write_stockholm(const std::string& file, const std::vector<std::string>& blocks) {
   std::ofstream os(file.c_str(), std::ios::binary);
   if (!os.is_open()) throw "--stockholm: cannot open " + file;
@@ -699,9 +807,10 @@ void write_stockholm(const std::string& file, const std::vector<std::string>& bl
 // by the library: names and rows without their all-gap columns, '-' for every gap
 // ss (--seed-structure): also the seed's consensus structure over the cleaned columns; a seed without
 // one is refused
-void read_seed(const std::string& file, std::vector<std::string>& names, std::vector<std::string>& rows, VU* ss = nullptr) {
+// describe (--describe): the structure is optional -- without one ss comes back with every column unpaired
+void read_seed(const std::string& file, std::vector<std::string>& names, std::vector<std::string>& rows, VU* ss = nullptr, bool describe = false) {
   std::ifstream is(file.c_str(), std::ios::binary);
-  if (!is.is_open()) throw "--seed: cannot open " + file;
+  if (!is.is_open()) throw (describe ? "--describe: cannot open " : "--seed: cannot open ") + file;
   const std::string text((std::istreambuf_iterator<char>(is)), std::istreambuf_iterator<char>());
   uint32_t n = 0;
   char *nm = nullptr, *rw = nullptr, *st = nullptr;
@@ -718,6 +827,12 @@ void read_seed(const std::string& file, std::vector<std::string>& names, std::ve
   names = lines_of(take(nm), n);
   rows = lines_of(take(rw), n);
   const std::string structure = take(st);
+  if (!has && describe) {
+    check_text(dafs_host_seed_clean(n, c_strs(names).data(), c_strs(rows).data(), &rw));
+    rows = lines_of(take(rw), n);
+    ss->assign(rows[0].size(), DAFS_HIP_NONE);
+    return;
+  }
   if (!has) throw "--seed-structure: " + file + " holds no SS_cons";
   ss->assign(rows.empty() ? 1 : rows[0].size() + 1, DAFS_HIP_NONE);
   uint32_t columns = 0;
@@ -915,7 +1030,8 @@ struct PairChunk {
 
 int align_group(dafs_hip_ctx* ctx, const Options& o, Ranks& rk, int align_model, const std::vector<std::vector<Fasta> >& fams,
                 const std::vector<size_t>& members, const std::vector<std::ostream*>& out, const std::vector<std::string*>& sto,
-                PairChunk* pc = nullptr, const std::vector<std::string*>& cov = std::vector<std::string*>());
+                PairChunk* pc = nullptr, const std::vector<std::string*>& cov = std::vector<std::string*>(),
+                const std::vector<IdentityText*>& idt = std::vector<IdentityText*>());
 
 struct Guard {  // the context of a run, destroyed however the run ends
   dafs_hip_ctx* c;
@@ -1111,6 +1227,19 @@ void reliabilities(dafs_hip_ctx* ctx, const std::vector<Fasta>& fa, const std::v
   }
 }
 
+// the rows of an alignment as text: residues in their columns, '-' elsewhere
+std::vector<std::string> row_texts(const std::vector<Fasta>& fa, const ALN& aln) {
+  std::vector<std::string> rows;
+  for (const auto& row : aln) {
+    const std::string& sq = fa[row.first].seq();
+    std::string text(row.second.size(), '-');
+    for (uint j = 0, k = 0; j != row.second.size(); ++j)
+      if (row.second[j]) text[j] = sq[k++];
+    rows.push_back(text);
+  }
+  return rows;
+}
+
 // The output of a final alignment with its final structure ss_final (:1876-1879, :1584-1601) on os: ">SS_cons", the brackets,
 // then the rows sorted by sequence index.  fa: the context's sequences; ff: the family's, its first one at index first.  With
 // sto, also the family's Stockholm block from rl (reliabilities, made while root held its rows in the present order): tree_line
@@ -1119,7 +1248,8 @@ void reliabilities(dafs_hip_ctx* ctx, const std::vector<Fasta>& fa, const std::v
 // (row_structures), written as the block's #=GR SS lines.
 void finish_alignment(dafs_hip_ctx* ctx, const Options& o, const std::vector<Fasta>& fa, ALN& root, const std::vector<Fasta>& ff,
                       uint32_t first, std::ostream& os, std::string* sto, const std::string* tree_line, const std::vector<uint8_t>* rf,
-                      std::string* cov, const VU& ss_final, const Reliability* rl, const std::map<uint32_t, VU>* row_ss = nullptr) {
+                      std::string* cov, const VU& ss_final, const Reliability* rl, const std::map<uint32_t, VU>* row_ss = nullptr,
+                      IdentityText* idt = nullptr) {
   std::string str;
   std::map<uint32_t, size_t> rel_at;  // sequence -> its first residue in rl->rel
   {
@@ -1146,17 +1276,20 @@ void finish_alignment(dafs_hip_ctx* ctx, const Options& o, const std::vector<Fas
   }
   std::string cov_chars;
   if (cov) covariation_of(ctx, o, rows, ss_final, *cov, cov_chars);
-  if (sto) {
-    std::vector<std::string> headers, names;
+  std::vector<std::string> names;  // the printed rows' Stockholm names
+  if (sto || idt) {
+    std::vector<std::string> headers;
     for (const Fasta& s : ff) headers.push_back(s.name());
     char* text = nullptr;
     check_text(dafs_host_stockholm_names((uint32_t)headers.size(), c_strs(headers).data(), &text));
     const std::vector<std::string> all_names = lines_of(take(text), headers.size());
+    for (const auto& row : root) names.push_back(all_names[row.first - first]);
+  }
+  if (idt) identity_of(ctx, names, rows, !o.identity_matrix.empty(), *idt);
+  if (sto) {
+    char* text = nullptr;
     std::vector<const double*> rr;
-    for (const auto& row : root) {
-      names.push_back(all_names[row.first - first]);
-      rr.push_back(rl->rel.data() + rel_at[row.first]);
-    }
+    for (const auto& row : root) rr.push_back(rl->rel.data() + rel_at[row.first]);
     std::vector<std::string> rss;  // each row's own structure in the row's columns
     for (size_t r = 0; row_ss && r < root.size(); ++r) {
       const VU& own = row_ss->at(root[r].first);
@@ -1172,6 +1305,10 @@ void finish_alignment(dafs_hip_ctx* ctx, const Options& o, const std::vector<Fas
                                               rf ? rf->data() : nullptr, cov ? cov_chars.c_str() : nullptr,
                                               row_ss ? c_strs(rss).data() : nullptr, &text));
     *sto = take(text);
+    if (idt) {  // --identity: the sequence weights as #=GS WT lines
+      check_text(dafs_host_stockholm_weights(sto->c_str(), (uint32_t)names.size(), c_strs(names).data(), idt->weight.data(), &text));
+      *sto = take(text);
+    }
   }
 }
 
@@ -1271,6 +1408,7 @@ int run_add(const Options& o, int align_model) {
   std::vector<uint8_t> rf(width, 0);
   for (uint32_t c = 0; c < C; ++c) rf[seed_col[c]] = 1;
   std::string sto, cov;
+  IdentityText idt;
   std::map<uint32_t, VU> row_ss;
   if (o.row_structures) {
     std::vector<uint32_t> every(m + k);
@@ -1283,10 +1421,11 @@ int run_add(const Options& o, int align_model) {
   std::vector<Reliability> rl(1);
   if (!o.stockholm.empty()) reliabilities(ctx, fa, {&root}, {ss}, false, rl);
   finish_alignment(ctx, o, fa, root, fa, 0, std::cout, o.stockholm.empty() ? nullptr : &sto, nullptr, &rf, o.covariation.empty() ? nullptr : &cov,
-                   ss, &rl[0], o.row_structures ? &row_ss : nullptr);
+                   ss, &rl[0], o.row_structures ? &row_ss : nullptr, o.identity.empty() ? nullptr : &idt);
   std::cout.flush();
   if (!o.stockholm.empty()) write_stockholm(o.stockholm, {sto});
   if (!o.covariation.empty()) write_covariation(o.covariation, {cov}, nullptr);
+  if (!o.identity.empty()) write_identity(o, {idt}, nullptr);
   return 0;
 }
 
@@ -1357,6 +1496,8 @@ int run_add_each(const Options& o, int align_model) {
   std::vector<int64_t> iterations(k, 0);
   std::vector<uint32_t> sup_both(k, 0), sup_can(k, 0), sup_half(k, 0);  // --seed-structure: the support of each new sequence's row
   std::vector<double> sup_exp(k, 0.0);
+  std::vector<uint32_t> near_row(k, DAFS_HIP_NONE);  // --seed-nearest: per new sequence its nearest seed row and the identity to it
+  std::vector<double> near_pid(k, std::nan(""));
   std::vector<std::string> sto_blocks, cov_tables, cov_headers;
   std::vector<VU> all_z(k);                     // --seed-merged: every placement's map, kept until the last chunk is done,
   std::vector<std::vector<double> > new_pp(k);  // and the residue values of its row in its own family
@@ -1472,6 +1613,17 @@ int run_add_each(const Options& o, int align_model) {
       finish_alignment(ctx, o, fa, roots[f], ff, f * n, os, o.stockholm.empty() ? nullptr : &sto, nullptr, &rfs[f],
                        o.covariation.empty() ? nullptr : &cov, ss[f], &rl[f], o.row_structures ? &row_ss : nullptr);
       std::cout << "==> " << j0 + f + 1 << " <==" << std::endl << os.str();
+      if (o.seed_nearest && matched[j0 + f]) {  // the printed rows (finish_alignment sorted them): the m seed rows, then the new one
+        const std::vector<std::string> rows = row_texts(fa, roots[f]);
+        const std::vector<uint8_t> cell = cells_of(rows);
+        std::vector<uint8_t> cand(n, 1);
+        cand[m] = 0;
+        std::vector<uint32_t> near(n), ni(n), nd(n);
+        check(dafs_hip_alignment_identity(ctx, n, (uint32_t)rfs[f].size(), cell.data(), rfs[f].data(), cand.data(), 0.0, nullptr, nullptr, nullptr,
+                                          near.data(), ni.data(), nd.data(), nullptr));
+        near_row[j0 + f] = near[m];
+        near_pid[j0 + f] = (double)ni[m] / (double)nd[m];
+      }
       if (!o.stockholm.empty()) sto_blocks.push_back(sto);
       if (!o.covariation.empty()) { cov_tables.push_back(cov); cov_headers.push_back(std::to_string(j0 + f + 1)); }
     }
@@ -1510,9 +1662,39 @@ int run_add_each(const Options& o, int align_model) {
     const std::vector<std::string> names = lines_of(take(text), headers.size());
     check_text(dafs_host_stockholm_block_merged(m + k, width, c_strs(names).data(), c_strs(rows).data(), rr.data(), brackets.data(), rf.data(),
                                                 nullptr, &text));
+    std::string block = take(text);
+    if (o.seed_nr_given) {  // the non-redundant rows: the rows with a residue in a seed column are compared
+      std::vector<uint32_t> inc, pos(m + k, DAFS_HIP_NONE);
+      std::vector<std::string> inc_rows;
+      for (uint32_t r = 0; r < m + k; ++r)
+        if (r < m || matched[r - m]) {
+          pos[r] = (uint32_t)inc.size();
+          inc.push_back(r);
+          inc_rows.push_back(rows[r]);
+        }
+      const uint32_t ni = (uint32_t)inc.size();
+      const std::vector<uint8_t> cell = cells_of(inc_rows);
+      std::vector<uint32_t> red((size_t)ni * ((ni + 31) / 32));
+      check(dafs_hip_alignment_identity(ctx, ni, width, cell.data(), rf.data(), nullptr, o.seed_nr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                        nullptr, red.data()));
+      // the visiting order: the seed rows, then the new rows by descending score, ties in file order
+      std::vector<uint32_t> hits(k), rank;
+      for (uint32_t j = 0; j < k; ++j) hits[j] = j;
+      std::stable_sort(hits.begin(), hits.end(), [&](uint32_t a, uint32_t b) { return score[a] > score[b]; });
+      for (uint32_t r = 0; r < m; ++r) rank.push_back(r);
+      for (uint32_t j : hits)
+        if (pos[m + j] != DAFS_HIP_NONE) rank.push_back(pos[m + j]);
+      std::vector<uint8_t> forced(ni, 0), kept_inc(ni), kept(m + k, 1);
+      std::fill(forced.begin(), forced.begin() + m, 1);
+      std::vector<uint32_t> by(ni);
+      check_text(dafs_host_nr_select(ni, red.data(), rank.data(), forced.data(), kept_inc.data(), by.data()));
+      for (uint32_t q = 0; q < ni; ++q) kept[inc[q]] = kept_inc[q];
+      check_text(dafs_host_stockholm_nr(block.c_str(), m + k, c_strs(names).data(), kept.data(), m, o.seed_nr, &text));
+      block = take(text);
+    }
     std::ofstream ms(o.seed_merged.c_str(), std::ios::binary);
     if (!ms.is_open()) throw "--seed-merged: cannot open " + o.seed_merged;
-    ms << take(text);
+    ms << block;
     ms.flush();
     if (!ms) throw "--seed-merged: cannot write " + o.seed_merged;
   }
@@ -1522,9 +1704,16 @@ int run_add_each(const Options& o, int align_model) {
     std::vector<std::string> headers;
     for (const Fasta& s : added) headers.push_back(s.name());
     char* text = nullptr;
-    check_text(dafs_host_seed_table_support(k, c_strs(headers).data(), lens.data(), matched.data(), score.data(), iterations.data(),
+    std::vector<std::string> near_name;  // --seed-nearest: the Stockholm names of the nearest seed rows
+    if (o.seed_nearest) {
+      check_text(dafs_host_stockholm_names(m, c_strs(snames).data(), &text));
+      const std::vector<std::string> seed_names = lines_of(take(text), m);
+      for (uint32_t j = 0; j < k; ++j) near_name.push_back(near_row[j] == DAFS_HIP_NONE ? "-" : seed_names[near_row[j]]);
+    }
+    check_text(dafs_host_seed_table_nearest(k, c_strs(headers).data(), lens.data(), matched.data(), score.data(), iterations.data(),
                                             o.seed_structure ? sup_both.data() : nullptr, o.seed_structure ? sup_can.data() : nullptr,
-                                            o.seed_structure ? sup_half.data() : nullptr, o.seed_structure ? sup_exp.data() : nullptr, &text));
+                                            o.seed_structure ? sup_half.data() : nullptr, o.seed_structure ? sup_exp.data() : nullptr,
+                                            o.seed_nearest ? c_strs(near_name).data() : nullptr, o.seed_nearest ? near_pid.data() : nullptr, &text));
     ts << take(text);
     ts.flush();
     if (!ts) throw "--seed-scores: cannot write " + o.seed_scores;
@@ -1629,6 +1818,31 @@ int run_pairwise(const Options& o, int align_model) {
   return 0;
 }
 
+// `dafs --describe ALIGNMENT` (pipeline.describe is the Python twin): the calls that read an alignment
+// alone, on a finished alignment that the seed reader reads.  Nothing is aligned and nothing is printed.
+int run_describe(const Options& o) {
+  std::vector<std::string> headers, rows;
+  VU ss;
+  read_seed(o.describe, headers, rows, &ss, true);
+  char* text = nullptr;
+  check_text(dafs_host_stockholm_names((uint32_t)headers.size(), c_strs(headers).data(), &text));
+  const std::vector<std::string> names = lines_of(take(text), headers.size());
+  dafs_hip_ctx* ctx = nullptr;
+  check(dafs_hip_create(o.device, &ctx));
+  Guard guard{ctx};
+  if (!o.identity.empty()) {
+    IdentityText idt;
+    identity_of(ctx, names, rows, !o.identity_matrix.empty(), idt);
+    write_identity(o, {idt}, nullptr);
+  }
+  if (!o.covariation.empty()) {
+    std::string cov, chars;
+    covariation_of(ctx, o, rows, ss, cov, chars);
+    write_covariation(o.covariation, {cov}, nullptr);
+  }
+  return 0;
+}
+
 int run(const Options& o, Ranks& rk) {
   // ---- option checks mirroring parse_options (:1683-1763)
   int align_model;
@@ -1649,6 +1863,7 @@ int run(const Options& o, Ranks& rk) {
     if (!o.no_alifold) std::cerr << "note: RNAalifold is not available in this build; running as with --no-alifold" << std::endl;
     if (!o.fold_model_given && o.fold_aux.empty()) std::cerr << "note: default folding model is CONTRAfold in this build" << std::endl;
   }
+  if (!o.describe.empty()) return rk.rank == 0 ? run_describe(o) : 0;
   if (!o.seed.empty()) return o.seed_each ? run_add_each(o, align_model) : run_add(o, align_model);
   if (o.pairwise) return run_pairwise(o, align_model);
 
@@ -1689,10 +1904,19 @@ int run(const Options& o, Ranks& rk) {
       for (size_t f : members) v.push_back(&cov_tables[f]);
     return v;
   };
+  // --identity: the same, one pair of tables per input file
+  std::vector<IdentityText> idts(o.identity.empty() ? 0 : o.inputs.size());
+  auto idt_of = [&](const std::vector<size_t>& members) {
+    std::vector<IdentityText*> v;
+    if (!idts.empty())
+      for (size_t f : members) v.push_back(&idts[f]);
+    return v;
+  };
   if (!multi) {
-    align_group(ctx, o, rk, align_model, fams, {0}, {&std::cout}, sto_of({0}), nullptr, cov_of({0}));
+    align_group(ctx, o, rk, align_model, fams, {0}, {&std::cout}, sto_of({0}), nullptr, cov_of({0}), idt_of({0}));
     if (rk.rank == 0 && !o.stockholm.empty()) write_stockholm(o.stockholm, sto_blocks);
     if (rk.rank == 0 && !o.covariation.empty()) write_covariation(o.covariation, cov_tables, nullptr);
+    if (rk.rank == 0 && !o.identity.empty()) write_identity(o, idts, nullptr);
     return 0;
   }
   // Several files: every file with two or more sequences in one batch (dafs_hip_set_families: shared launches, one guide
@@ -1711,7 +1935,7 @@ int run(const Options& o, Ranks& rk) {
     std::vector<std::ostream*> os;
     for (size_t f : members) os.push_back(&outs[f]);
     try {
-      align_group(ctx, o, rk, align_model, fams, members, os, sto_of(members), nullptr, cov_of(members));
+      align_group(ctx, o, rk, align_model, fams, members, os, sto_of(members), nullptr, cov_of(members), idt_of(members));
     } catch (const char* str) {
       throw names(members) + ": " + str;
     } catch (const std::string& str) {
@@ -1725,16 +1949,18 @@ int run(const Options& o, Ranks& rk) {
   std::cout.flush();
   if (!o.stockholm.empty()) write_stockholm(o.stockholm, sto_blocks);
   if (!o.covariation.empty()) write_covariation(o.covariation, cov_tables, &o.inputs);
+  if (!o.identity.empty()) write_identity(o, idts, &o.inputs);
   return 0;
 }
 
 // The run of one or more families (members: indices into fams) on the context: phase 1 once over all of them, one guide
 // tree per family, the progressive phase over the forest (the ready nodes of every family share each round), then per
 // family the refinement, the common structure and the output on *out[k]; with --stockholm (sto not empty) also the
-// family's Stockholm block in *sto[k], and with --covariation (cov not empty) its covariation table in *cov[k].
+// family's Stockholm block in *sto[k], with --covariation (cov not empty) its covariation table in *cov[k], and with
+// --identity (idt not empty) its identity tables and weights in *idt[k].
 int align_group(dafs_hip_ctx* ctx, const Options& o, Ranks& rk, int align_model, const std::vector<std::vector<Fasta> >& fams,
                 const std::vector<size_t>& members, const std::vector<std::ostream*>& out, const std::vector<std::string*>& sto,
-                PairChunk* pc, const std::vector<std::string*>& cov) {
+                PairChunk* pc, const std::vector<std::string*>& cov, const std::vector<IdentityText*>& idt) {
   const uint F = (uint)members.size();
   std::vector<Fasta> fa;         // every sequence of the group, family after family
   std::vector<uint32_t> first(1, 0);
@@ -1886,7 +2112,7 @@ int align_group(dafs_hip_ctx* ctx, const Options& o, Ranks& rk, int align_model,
       tree_line = tl.str();
     }
     finish_alignment(ctx, o, fa, root, fams[members[f]], first[f], *out[f], sto.empty() ? nullptr : sto[f], &tree_line, nullptr,
-                     cov.empty() ? nullptr : cov[f], ss0[f], &rl[f], row_ss.empty() ? nullptr : &row_ss);
+                     cov.empty() ? nullptr : cov[f], ss0[f], &rl[f], row_ss.empty() ? nullptr : &row_ss, idt.empty() ? nullptr : idt[f]);
   }
   return 0;
 }

@@ -1,5 +1,5 @@
 // dafs_amd/csrc/host_text.cpp -- the text formats and memory estimates of both drivers as C entry points (include/dafs_hip.h,
-// "host text"): the Stockholm block, the --covariation and --pairwise-scores tables, the seed reader of --seed, the estimates
+// "host text"): the Stockholm block, the --covariation, --pairwise-scores and --identity tables, the seed reader of --seed, the estimates
 // and the greedy chunking.  The C++ command line calls them directly and the Python driver through capi.py, so every byte and
 // every formula is defined here once.  Host logic only: nothing here includes HIP or touches a device.
 #include <algorithm>
@@ -444,6 +444,150 @@ extern "C" int dafs_host_covariation_table(uint32_t n, uint32_t L, const uint8_t
   });
 }
 
+extern "C" const char* dafs_host_alistat_refusal(int which) {
+  switch (which) {
+    case DAFS_ALISTAT_NO_PAIRWISE:
+      return "identity statistics (--identity, identity) cannot be combined with pairwise alignments (--pairwise, pipeline.pairwise): they "
+             "go with a run, several files or a seed";
+    case DAFS_ALISTAT_NR_NEEDS_MERGED:
+      return "a non-redundant subset (--seed-nr, nr) selects rows of the merged alignment: it needs --seed-merged / merged";
+    case DAFS_ALISTAT_NR_THRESHOLD:
+      return "the threshold of the non-redundant subset (--seed-nr, nr) is a number in (0, 1]";
+    case DAFS_ALISTAT_TOO_MANY_ROWS:
+      return "identity statistics (--identity, identity) hold the whole identity matrix for their summary: at most 32768 rows";
+    default:
+      return "";
+  }
+}
+
+// Alignment statistics: the cell code, the summary and the tables of --identity and --identity-matrix
+extern "C" uint8_t dafs_host_ali_code(char ch) {
+  if (ch == '-' || ch == '.') return 5;
+  if (!is_alpha(ch)) return 255;
+  return dafs_host_cov_code(ch);  // A C G U/T 0..3, every other letter 4
+}
+
+namespace {
+
+double pid_of(uint32_t ident, uint32_t den) { return (double)ident / (double)den; }
+
+// (i1, d1) is more identical than (i2, d2): no floating point decides an order
+bool more_identical(uint32_t i1, uint32_t d1, uint32_t i2, uint32_t d2) { return (uint64_t)i1 * d2 > (uint64_t)i2 * d1; }
+
+}  // namespace
+
+extern "C" int dafs_host_identity_summary(uint32_t n, const uint32_t* ident, const uint32_t* res, double* summary) {
+  if (!n || !summary || (n > 1 && (!ident || !res))) return DAFS_HIP_EINVAL;
+  summary[0] = summary[1] = summary[2] = std::nan("");
+  if (n == 1) return DAFS_HIP_OK;
+  for (uint32_t r = 0; r < n; ++r)
+    if (!res[r]) return DAFS_HIP_EINVAL;
+  double sum = 0.0;
+  uint32_t lo_i = 0, lo_d = 0, hi_i = 0, hi_d = 0;
+  for (uint32_t r = 0; r < n; ++r)
+    for (uint32_t s = r + 1; s < n; ++s) {
+      const uint32_t i = ident[(size_t)r * n + s], d = std::min(res[r], res[s]);
+      sum += pid_of(i, d);
+      if (!lo_d || more_identical(lo_i, lo_d, i, d)) { lo_i = i; lo_d = d; }
+      if (!hi_d || more_identical(i, d, hi_i, hi_d)) { hi_i = i; hi_d = d; }
+    }
+  summary[0] = sum / (double)((uint64_t)n * (n - 1) / 2);
+  summary[1] = pid_of(lo_i, lo_d);
+  summary[2] = pid_of(hi_i, hi_d);
+  return DAFS_HIP_OK;
+}
+
+extern "C" int dafs_host_identity_table(uint32_t n, uint32_t len, const char* const* names, const uint32_t* res, const double* weight,
+                                        const uint32_t* nearest, const uint32_t* nearest_ident, const uint32_t* nearest_den,
+                                        const double* summary, char** table) {
+  return text_out(table, [&]() {
+    const std::vector<std::string> nm = strings(n, names);
+    if (!n || !res || !weight || !nearest || !nearest_ident || !nearest_den || !summary) throw kBadArgument;
+    std::ostringstream os;
+    os << "# rows " << n << " columns " << len << " average " << fmt9d(summary[0]) << " min " << fmt9d(summary[1]) << " max " << fmt9d(summary[2]) << "\n";
+    for (uint32_t r = 0; r < n; ++r) {
+      os << r + 1 << "\t" << nm[r] << "\t" << res[r] << "\t" << fmt9d(weight[r]) << "\t";
+      if (nearest[r] == DAFS_HIP_NONE) {
+        os << "0\t-\tnan\n";
+        continue;
+      }
+      if (nearest[r] >= n || !nearest_den[r]) throw std::string("identity table: a nearest row is outside the alignment");
+      os << nearest[r] + 1 << "\t" << nm[nearest[r]] << "\t" << fmt9d(pid_of(nearest_ident[r], nearest_den[r])) << "\n";
+    }
+    return os.str();
+  });
+}
+
+extern "C" int dafs_host_identity_matrix_table(uint32_t n, const char* const* names, const uint32_t* res, const uint32_t* ident,
+                                               const uint32_t* aligned, char** table) {
+  return text_out(table, [&]() {
+    const std::vector<std::string> nm = strings(n, names);
+    if (!n || !res || !ident || !aligned) throw kBadArgument;
+    std::ostringstream os;
+    for (uint32_t r = 0; r < n; ++r)
+      for (uint32_t s = r + 1; s < n; ++s) {
+        const uint32_t den = std::min(res[r], res[s]);
+        if (!den) throw std::string("identity matrix: a row without residues");
+        const size_t at = (size_t)r * n + s;
+        os << r + 1 << "\t" << s + 1 << "\t" << nm[r] << "\t" << nm[s] << "\t" << ident[at] << "\t" << aligned[at] << "\t" << den << "\t"
+           << fmt9d(pid_of(ident[at], den)) << "\n";
+      }
+    return os.str();
+  });
+}
+
+extern "C" int dafs_host_stockholm_weights(const char* block, uint32_t n, const char* const* names, const double* weight, char** out) {
+  return text_out(out, [&]() {
+    const std::vector<std::string> nm = strings(n, names);
+    if (!block || (n && !weight)) throw kBadArgument;
+    const std::string text(block);
+    const std::string first = "# STOCKHOLM 1.0\n";
+    if (text.compare(0, first.size(), first) != 0) throw std::string("stockholm weights: not a Stockholm block");
+    size_t at = first.size();
+    while (text.compare(at, 5, "#=GF ") == 0) {
+      const size_t nl = text.find('\n', at);
+      if (nl == std::string::npos) throw std::string("stockholm weights: not a Stockholm block");
+      at = nl + 1;
+    }
+    std::string lines;
+    for (uint32_t r = 0; r < n; ++r) {
+      char buf[64];
+      snprintf(buf, sizeof buf, "%.6f", weight[r]);
+      lines += "#=GS " + nm[r] + " WT " + buf + "\n";
+    }
+    return text.substr(0, at) + lines + text.substr(at);
+  });
+}
+
+extern "C" int dafs_host_stockholm_nr(const char* block, uint32_t n, const char* const* names, const uint8_t* kept, uint32_t nseed,
+                                      double threshold, char** out) {
+  return text_out(out, [&]() {
+    const std::vector<std::string> nm = strings(n, names);
+    if (!block || !kept || nseed > n) throw kBadArgument;
+    const std::string text(block);
+    const std::string first = "# STOCKHOLM 1.0\n";
+    if (text.compare(0, first.size(), first) != 0) throw std::string("stockholm nr: not a Stockholm block");
+    std::set<std::string> dropped;  // the labels of the lines that leave: the row's and its "#=GR <name> ..." lines
+    uint32_t hits = 0;
+    for (uint32_t r = 0; r < n; ++r) {
+      if (r >= nseed && kept[r]) ++hits;
+      if (!kept[r]) dropped.insert(nm[r]);
+    }
+    std::string res = first + "#=GF CC nr " + fmt9d(threshold) + " kept " + std::to_string(hits) + " of " + std::to_string(n - nseed) + " hits\n";
+    for (size_t at = first.size(); at < text.size();) {
+      size_t nl = text.find('\n', at);
+      nl = nl == std::string::npos ? text.size() : nl + 1;
+      const std::string line = text.substr(at, nl - at);
+      at = nl;
+      std::vector<std::string> f = fields(line);
+      const bool gr = f.size() >= 2 && f[0] == "#=GR";
+      if (!f.empty() && (gr ? dropped.count(f[1]) : (f[0][0] != '#' && dropped.count(f[0])))) continue;
+      res += line;
+    }
+    return res;
+  });
+}
+
 // --pairwise-scores: one line per pair
 extern "C" int dafs_host_pairwise_table(uint64_t npairs, const uint32_t* x, const uint32_t* y, uint32_t nnames, const char* const* names,
                                         const double* sim, const double* score, const int64_t* iterations, char** table) {
@@ -461,11 +605,16 @@ extern "C" int dafs_host_pairwise_table(uint64_t npairs, const uint32_t* x, cons
 }
 
 // --seed-scores: one line per new sequence of a --seed-each run, named by the Stockholm rule over the file's headers; with
-// --seed-structure four more columns, the sequence's structure support
-extern "C" int dafs_host_seed_table_support(uint32_t n, const char* const* headers, const uint32_t* length, const uint32_t* matched,
+// --seed-structure four more columns, the sequence's structure support; with
+// --seed-nearest two more: the nearest seed row and the identity to it
+extern "C" int dafs_host_seed_table_nearest(uint32_t n, const char* const* headers, const uint32_t* length, const uint32_t* matched,
                                             const double* score, const int64_t* iterations, const uint32_t* both, const uint32_t* canonical,
-                                            const uint32_t* half, const double* expected, char** table) {
+                                            const uint32_t* half, const double* expected, const char* const* nearest_name,
+                                            const double* identity, char** table) {
   return text_out(table, [&]() {
+    const bool near = nearest_name || identity;
+    if (near && n && (!nearest_name || !identity)) throw kBadArgument;
+    const std::vector<std::string> nn = near ? strings(n, nearest_name) : std::vector<std::string>();
     const std::vector<std::string> nm = stockholm_names(strings(n, headers));
     if (n && (!length || !matched || !score || !iterations)) throw kBadArgument;
     const bool support = both || canonical || half || expected;
@@ -479,10 +628,17 @@ extern "C" int dafs_host_seed_table_support(uint32_t n, const char* const* heade
         if (canonical[j] > both[j]) throw std::string("seed table: more canonical pairs than pairs");
         ts << "\t" << both[j] << "\t" << canonical[j] << "\t" << half[j] << "\t" << fmt9d(expected[j]);
       }
+      if (near) ts << "\t" << nn[j] << "\t" << fmt9d(identity[j]);
       ts << "\n";
     }
     return ts.str();
   });
+}
+
+extern "C" int dafs_host_seed_table_support(uint32_t n, const char* const* headers, const uint32_t* length, const uint32_t* matched,
+                                            const double* score, const int64_t* iterations, const uint32_t* both, const uint32_t* canonical,
+                                            const uint32_t* half, const double* expected, char** table) {
+  return dafs_host_seed_table_nearest(n, headers, length, matched, score, iterations, both, canonical, half, expected, nullptr, nullptr, table);
 }
 
 extern "C" int dafs_host_seed_table(uint32_t n, const char* const* headers, const uint32_t* length, const uint32_t* matched, const double* score,

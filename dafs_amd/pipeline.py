@@ -54,7 +54,7 @@ class Result:
 def run(names, seqs, ctx=None, bp=None, w=4.0, eta0=0.5, t_max=600, w_pct_a=0.25, w_pct_s=0.25, th_a=0.01,
         th_s=0.2, th_s1=None, align_model=capi.ALIGN_PROBCONS, force_iters=0, timers=None, level_sync=False, slice_iters=None,
         mp=None, skip_uncoupled_folds=True, shard=None, round_us=None, w_pct_f=0.0, bp_update=False, bp_update1=False,
-        reliability=False, covariation=False, row_structures=False):
+        reliability=False, covariation=False, row_structures=False, identity=False):
     """The whole run.  bp: per-sequence (rowptr, col, val) base-pairing rows (--fold-aux); None
     computes them with the device fold model.  mp: supplied matching probabilities (--align-aux), see Context.set_mp.
     shard: (torch.distributed module, torch device) of an initialised process group -- phase 1 (folds, pair posteriors,
@@ -62,7 +62,8 @@ def run(names, seqs, ctx=None, bp=None, w=4.0, eta0=0.5, t_max=600, w_pct_a=0.25
     finishes the run and holds the same result.  reliability: the result also gets .reliability and .stockholm (see
     _phase2_forest).  covariation: True or a dict with shuffles (100), seed (1), e_max (0.05): the result also gets
     .covariation (see _final).  row_structures: the result also gets .row_ss and .row_ss_str, the structure of every printed
-    row on its own (see _phase2_forest)."""
+    row on its own (see _phase2_forest).  identity: the result also gets .identity (see alignment_identity) and its
+    Stockholm block the `#=GS <name> WT` lines."""
     import time
     # combinations this driver does not implement are refused, not ignored (the command line, cli_main.cpp, has no level
     # batches: its --bp-update runs in the resident-node rounds and in the refinement's solve_node)
@@ -86,7 +87,7 @@ def run(names, seqs, ctx=None, bp=None, w=4.0, eta0=0.5, t_max=600, w_pct_a=0.25
     t.append(time.perf_counter())
     fam = dict(names=names, seqs=seqs, first=0, sim=sim, tree=(score, left, right))
     return _phase2_forest(ctx, own, [fam], t, w, eta0, t_max, th_a, th_s, th_s1, force_iters, level_sync, slice_iters,
-                          skip_uncoupled_folds, round_us, bp_update, bp_update1, reliability, covariation, row_structures)[0]
+                          skip_uncoupled_folds, round_us, bp_update, bp_update1, reliability, covariation, row_structures, identity)[0]
 
 
 def _phase1_local(ctx, seqs, bp, mp, align_model, th_a, w_pct_a, w_pct_s, t, w_pct_f=0.0, first=None, constraints=None):
@@ -185,7 +186,7 @@ def _solve_nodes(ctx, prm, take_ready, finish, level_sync=False, slice_iters=Non
 
 def _phase2_forest(ctx, own, fams, t, w, eta0, t_max, th_a, th_s, th_s1, force_iters, level_sync, slice_iters,
                    skip_uncoupled_folds, round_us=None, bp_update=False, bp_update1=False, reliability=False, covariation=False,
-                   row_structures=False):
+                   row_structures=False, identity=False):
     """The progressive phase and the output of every family of the context at once.  fams: per family a dict with names,
     seqs, first (index of its first sequence in the context), sim and tree = (score, left, right).  The guide trees form one
     forest: a node is ready when both of its children are done, whatever its family, and the ready nodes of all families
@@ -287,7 +288,8 @@ def _phase2_forest(ctx, own, fams, t, w, eta0, t_max, th_a, th_s, th_s1, force_i
         res.levels = levels
         res.rounds = rounds
         sidx, mask = roots[f]
-        _final(ctx, res, fm["names"], fm["seqs"], fm["first"], sidx, mask, finals[f], rls[f], res.tree_line, None, covariation, rows_ss[f])
+        _final(ctx, res, fm["names"], fm["seqs"], fm["first"], sidx, mask, finals[f], rls[f], res.tree_line, None, covariation, rows_ss[f],
+               identity)
     t.append(time.perf_counter())
     # fold_launch: the folding is only started there; its kernels overlap `pair` and the first half of `pct_fold_tree`,
     # which also holds the wait for them
@@ -335,7 +337,73 @@ def _final_structure(ctx, sidx, mask, th1, bp_update1, ss):
     return ss
 
 
-def _final(ctx, res, names, seqs, first, sidx, mask, ss, rl, tree_line, rf=None, covariation=None, row_ss=None):
+def alignment_identity(ctx, rows, use=None):
+    """How similar the rows of an alignment are: Context.alignment_identity with its matrices, plus
+    .weights (Context.alignment_weights), .pid (the identity to the nearest row, NaN for a single row) and .summary (average,
+    minimum, maximum pid over all pairs; capi.identity_summary).  use: the columns that count (None: all)."""
+    if len(rows) > 32768:
+        raise ValueError(capi.alistat_refusal(capi.TOO_MANY_ROWS))
+    ident = ctx.alignment_identity(rows, use=use, matrix=True)
+    ident.weights = ctx.alignment_weights(rows, use=use)
+    ident.pid = ident.pid_nearest
+    ident.summary = capi.identity_summary(ident.ident, ident.res)
+    ident.columns = len(rows[0])
+    return ident
+
+
+def identity_tsv(row_names, identity):
+    """The table of `dafs --identity OUT` for one alignment (dafs_host_identity_table): the line "# rows n columns len average
+    A min B max C", then per row "r<TAB>name<TAB>residues<TAB>weight<TAB>nearest<TAB>nearest_name<TAB>pid" with 1-based
+    indices and the floats as %.9g.  row_names: the rows' Stockholm names."""
+    row_names = list(row_names)
+    n = len(identity.res)
+    if len(row_names) != n:
+        raise ValueError("identity_tsv: one name per row")
+    arrs = [np.ascontiguousarray(a, t) for a, t in ((identity.res, np.uint32), (identity.weights, np.float64), (identity.nearest, np.uint32),
+                                                    (identity.nearest_ident, np.uint32), (identity.nearest_den, np.uint32),
+                                                    (identity.summary, np.float64))]
+    return capi.host_text(capi._identity_table, n, int(identity.columns), capi.c_strings(row_names), *[a.ctypes.data for a in arrs])
+
+
+def identity_matrix_tsv(row_names, identity):
+    """The table of `dafs --identity-matrix OUT` (dafs_host_identity_matrix_table): per pair r < s the line
+    r, s, name_r, name_s, ident, aligned, den, pid, tab-separated"""
+    row_names = list(row_names)
+    n = len(identity.res)
+    if len(row_names) != n:
+        raise ValueError("identity_matrix_tsv: one name per row")
+    arrs = [np.ascontiguousarray(a, np.uint32) for a in (identity.res, identity.ident, identity.aligned)]
+    return capi.host_text(capi._identity_matrix_table, n, capi.c_strings(row_names), *[a.ctypes.data for a in arrs])
+
+
+def describe(names, rows, ss=None, ctx=None, identity=True, covariation=False):
+    """The alignment-only statistics of a finished alignment (`dafs --describe ALIGNMENT`): nothing is
+    aligned.  names / rows / ss: as stockholm.read_seed_structure returns them (ss None: no structure).  Returns a Result with
+    .rows, .row_names (stockholm.names), .ss and, as asked, .identity (alignment_identity over all columns) and .covariation
+    (as run's)."""
+    covariation = cov_options(covariation)
+    names, rows = stockholm.clean_seed(names, rows)
+    res = Result()
+    res.rows, res.row_names = rows, stockholm.names(names)
+    res.ss = np.full(len(rows[0]), NONE, np.uint32) if ss is None else np.ascontiguousarray(ss, np.uint32)
+    if len(res.ss) != len(rows[0]):
+        raise ValueError("pipeline.describe: the structure needs one entry per column")
+    own = ctx is None
+    if own:
+        ctx = capi.Context(0)
+    try:
+        if identity:
+            res.identity = alignment_identity(ctx, rows)
+        if covariation:
+            res.covariation = ctx.alignment_covariation(rows, res.ss, shuffles=covariation["shuffles"], seed=covariation["seed"])
+            res.covariation.update(covariation)
+    finally:
+        if own:
+            ctx.close()
+    return res
+
+
+def _final(ctx, res, names, seqs, first, sidx, mask, ss, rl, tree_line, rf=None, covariation=None, row_ss=None, identity=False):
     """The output of a final alignment (sidx: global sequence index per row, mask) with its common structure ss
     (_final_structure), into res: .ss, .ss_str, .rows, .output and, with rl, .reliability and .stockholm.  names / seqs: the
     family's, its first sequence at global index `first`.  rl: the alignment's dict of Context.alignment_reliabilities for
@@ -343,7 +411,8 @@ def _final(ctx, res, names, seqs, first, sidx, mask, ss, rl, tree_line, rf=None,
     tree line (pipeline.add); rf: the RF line of the Stockholm block.  covariation (cov_options): .covariation, the dict of
     Context.alignment_covariation on the printed rows and structure with the options' shuffles, seed
     and e_max beside the arrays; the Stockholm block then carries a `#=GC cov_SS_cons` line.  row_ss: per printed row its own structure (_row_structures) -> .row_ss, .row_ss_str
-    and the `#=GR <name> SS` lines of the Stockholm block."""
+    and the `#=GR <name> SS` lines of the Stockholm block.  identity: .identity, alignment_identity of the printed rows in
+    printed order over all columns, and .row_names, their Stockholm names; the Stockholm block then carries the `#=GS <name> WT` lines."""
     res.ss = ss
     res.ss_str = capi.make_brackets(ss)
     order = np.argsort(sidx, kind="stable")  # std::sort(aln) :1876
@@ -366,6 +435,10 @@ def _final(ctx, res, names, seqs, first, sidx, mask, ss, rl, tree_line, rf=None,
         cv.update(covariation)
         res.covariation = cv
         cov_chars = stockholm.cov_ss_cons(ss, cv["pair_e"], cv["e_max"])
+    if identity:
+        res.identity = alignment_identity(ctx, res.rows)
+        sto_names = stockholm.names(names)
+        res.row_names = [sto_names[int(sidx[r]) - first] for r in order]
     if rl is not None:
         rl = dict(rl)
         cuts = np.cumsum([len(seqs[int(s) - first]) for s in sidx])[:-1]
@@ -374,7 +447,8 @@ def _final(ctx, res, names, seqs, first, sidx, mask, ss, rl, tree_line, rf=None,
         res.reliability = rl
         sto_names = stockholm.names(names)
         res.stockholm = stockholm.block(tree_line, [sto_names[int(sidx[r]) - first] for r in order], res.rows, rl["residue"],
-                                        rl["col"], res.ss_str, rf, cov_chars, None if row_ss is None else res.row_ss_str)
+                                        rl["col"], res.ss_str, rf, cov_chars, None if row_ss is None else res.row_ss_str,
+                                        res.identity.weights if identity else None)
 
 
 def _seed_structure(seed_ss, seed_mask, seed_seqs, th_s1, bp_update1, who):
@@ -413,7 +487,8 @@ def _printed_support(sup, sidx):
 
 def add(seed_names, seed_rows, names, seqs, ctx=None, w=4.0, eta0=0.5, t_max=600, w_pct_a=0.25, w_pct_s=0.25, th_a=0.01,
         th_s=0.2, th_s1=None, align_model=capi.ALIGN_PROBCONS, force_iters=0, slice_iters=None, skip_uncoupled_folds=True,
-        round_us=None, w_pct_f=0.0, bp_update1=False, reliability=False, covariation=False, row_structures=False, seed_ss=None):
+        round_us=None, w_pct_f=0.0, bp_update1=False, reliability=False, covariation=False, row_structures=False, seed_ss=None,
+        identity=False):
     """Add new sequences to a fixed seed alignment without changing its columns (`dafs --seed`).
     seed_names / seed_rows: the seed's rows (letters and '.' / '-' gaps; stockholm.read_seed reads a file), checked and
     without their all-gap columns (stockholm.clean_seed).  names / seqs: the new sequences.  The options are run()'s.
@@ -425,7 +500,7 @@ def add(seed_names, seed_rows, names, seqs, ctx=None, w=4.0, eta0=0.5, t_max=600
     .z (per new sequence its column map into the seed), .rf (per merged column True for a seed column), .dd_log
     ({j: (iterations, violated, ncbp, score)}), .dd_memory, .seconds; with reliability, .reliability and .stockholm (no CC
     line, a `#=GC RF` line); with covariation (as in run), .covariation; with row_structures (as in run), .row_ss and
-    .row_ss_str.
+    .row_ss_str; with identity (as in run), .identity.
 
     seed_ss (`dafs --seed-structure`): the seed's consensus structure over its cleaned columns
     (stockholm.read_seed_structure), fixed like the columns.  The seed rows are folded under the constraints it puts on them
@@ -487,7 +562,7 @@ def add(seed_names, seed_rows, names, seqs, ctx=None, w=4.0, eta0=0.5, t_max=600
             ss_m = _final_structure(ctx, sidx, rows_mask, th1, bp_update1, ctx.consensus_structure(sidx, rows_mask, th1)[1])
         rl = ctx.alignment_reliability(sidx, rows_mask, ss_m) if reliability else None
         _final(ctx, res, all_names, all_seqs, 0, sidx, rows_mask, ss_m, rl, None, rf, covariation,
-               _row_structures(ctx, [sidx], dict(enumerate(map(len, all_seqs))), th1)[0] if row_structures else None)
+               _row_structures(ctx, [sidx], dict(enumerate(map(len, all_seqs))), th1)[0] if row_structures else None, identity)
         t.append(time.perf_counter())
         res.seconds = dict(phase1=t[3] - t[0], nodes=t[4] - t[3], final=t[5] - t[4], total=t[5] - t[0])
     finally:
@@ -564,7 +639,8 @@ def run_batch(families, ctx=None, max_bytes=None, **kw):
             t.append(time.perf_counter())
             res = _phase2_forest(ctx, False, fams, t, opts["w"], opts["eta0"], opts["t_max"], opts["th_a"], opts["th_s"], opts["th_s1"],
                                  opts["force_iters"], opts["level_sync"], opts["slice_iters"], opts["skip_uncoupled_folds"], opts["round_us"],
-                                 opts["bp_update"], opts["bp_update1"], opts["reliability"], opts["covariation"], opts["row_structures"])
+                                 opts["bp_update"], opts["bp_update1"], opts["reliability"], opts["covariation"], opts["row_structures"],
+                                 opts["identity"])
             for k, r in zip(grp, res):
                 out[k] = r
     finally:
@@ -672,6 +748,8 @@ def pairwise(names, seqs, pairs=None, ctx=None, max_bytes=None, **opts):
             raise ValueError("pipeline.pairwise: %s is a single-run option (use run)" % k)
     if opts.get("covariation"):
         raise ValueError("pipeline.pairwise: two rows carry no covariation; covariation is an option of run, run_batch and add")
+    if opts.get("identity"):
+        raise ValueError(capi.alistat_refusal(capi.NO_PAIRWISE))
     if opts.get("level_sync") and opts.get("bp_update"):
         raise ValueError("pipeline.pairwise: bp_update needs the resident-node schedule (level_sync=False)")
     o = {k: p.default for k, p in inspect.signature(run).parameters.items() if k not in ("names", "seqs", "ctx", "bp", "mp", "shard")}
@@ -750,18 +828,27 @@ def seed_scores_tsv(names, each):
     """The table of `dafs --seed SEED --seed-each --seed-scores OUT` (dafs_host_seed_table) for the result of add_each on the
     new sequences `names`: per sequence "j<TAB>name<TAB>length<TAB>matched<TAB>inserted<TAB>score<TAB>iterations" with 1-based j,
     the Stockholm name (stockholm.names over the new sequences' headers) and the floats as %.9g.  A result of add_each with
-    seed_ss has four more columns, "pairs<TAB>canonical<TAB>half<TAB>expected" of the sequence's structure support."""
+    seed_ss has four more columns, "pairs<TAB>canonical<TAB>half<TAB>expected" of the sequence's structure support.  A result
+    of add_each with nearest has two more at the end (dafs_host_seed_table_nearest): the Stockholm name of the nearest seed row
+    ("-" for none) and the identity to it as %.9g."""
     names = list(names)
     if len(names) != len(each.results):
         raise ValueError("seed_scores_tsv: one name per new sequence")
     arrs = [np.ascontiguousarray(a, t) for a, t in ((each.lengths, np.uint32), (each.matched, np.uint32), (each.score, np.float64),
                                                     (each.iterations, np.int64))]
     sup = getattr(each, "support", None)
-    if sup is None:
+    near = getattr(each, "nearest", None)
+    if sup is None and near is None:
         return capi.host_text(capi._seed_table, len(names), capi.c_strings(names), *[a.ctypes.data for a in arrs])
-    arrs += [np.ascontiguousarray(sup[key], t) for key, t in (("both", np.uint32), ("canonical", np.uint32), ("half", np.uint32),
-                                                             ("expected", np.float64))]
-    return capi.host_text(capi._seed_table_support, len(names), capi.c_strings(names), *[a.ctypes.data for a in arrs])
+    if sup is not None:
+        arrs += [np.ascontiguousarray(sup[key], t) for key, t in (("both", np.uint32), ("canonical", np.uint32), ("half", np.uint32),
+                                                                 ("expected", np.float64))]
+    if near is None:
+        return capi.host_text(capi._seed_table_support, len(names), capi.c_strings(names), *[a.ctypes.data for a in arrs])
+    ptrs = [a.ctypes.data for a in arrs] + [None] * (8 - len(arrs))
+    pid = np.ascontiguousarray(near.pid, np.float64)
+    return capi.host_text(capi._seed_table_nearest, len(names), capi.c_strings(names), *ptrs,
+                          capi.c_strings(["-" if r == NONE else near.names[int(r)] for r in near.row]), pid.ctypes.data)
 
 
 class AddEach:
@@ -769,6 +856,10 @@ class AddEach:
 
 
 class Merged:
+    pass
+
+
+class Nearest:
     pass
 
 
@@ -796,7 +887,26 @@ def _merge_each(seed_names, seed_rows, seed_ss, names, seqs, zs, pps):
     return mg
 
 
-def add_each(seed_names, seed_rows, names, seqs, ctx=None, max_bytes=None, merged=False, **opts):
+def _select_nr(ctx, mg, m, score, matched, t):
+    """The non-redundant subset of a merged alignment (add_each's nr) into mg: .kept, .by, .nr_rows, .nr_names, .nr_stockholm"""
+    total = len(mg.rows)
+    inc = np.array([r for r in range(total) if r < m or matched[r - m]], np.uint32)  # the rows with a residue in a seed column
+    red = ctx.alignment_identity([mg.rows[r] for r in inc], use=mg.rf, nr=t, nearest=False).red
+    pos = {int(r): q for q, r in enumerate(inc)}
+    order = list(range(m)) + [m + int(j) for j in np.argsort(-np.asarray(score, np.float64), kind="stable")]
+    rank = np.array([pos[r] for r in order if r in pos], np.uint32)
+    kept, by = capi.nr_select(red, rank, np.arange(len(inc)) < m)
+    mg.kept = np.ones(total, bool)
+    mg.by = np.full(total, NONE, np.uint32)
+    mg.kept[inc] = kept
+    mg.by[inc] = np.where(by == NONE, NONE, inc[np.minimum(by, len(inc) - 1)])
+    mg.nr_rows = [row for row, keep in zip(mg.rows, mg.kept) if keep]
+    mg.nr_names = [nm for nm, keep in zip(mg.names, mg.kept) if keep]
+    kept8 = np.ascontiguousarray(mg.kept, np.uint8)
+    mg.nr_stockholm = capi.host_text(capi._stockholm_nr, mg.stockholm.encode("latin-1"), total, capi.c_strings(mg.names), kept8.ctypes.data, m, t)
+
+
+def add_each(seed_names, seed_rows, names, seqs, ctx=None, max_bytes=None, merged=False, nearest=False, nr=None, **opts):
     """Each new sequence added to a fixed seed alignment on its own (`dafs --seed SEED --seed-each`).
     opts: the options of add().  results[j] is, bit for bit, what add(seed_names, seed_rows, [names[j]], [seqs[j]], **opts)
     returns (.output, .rows, .ss, .ss_str, .z, .rf, .dd_log and, when asked, .reliability / .stockholm / .row_ss* /
@@ -824,8 +934,24 @@ def add_each(seed_names, seed_rows, names, seqs, ctx=None, max_bytes=None, merge
     .ss / .ss_str (the seed's structure carried into the merged columns), .z (the k maps), .pp (per new row the residue
     values of that row in its own family seed + [j]: one Context.alignment_reliabilities call per chunk that wants the new row
     of every family, so the matching transform stays the listed one), .col (per column the mean of the new rows' values, NaN
-    where none has a residue), .stockholm (stockholm.block_merged) and .output (as add prints)."""
+    where none has a residue), .stockholm (stockholm.block_merged) and .output (as add prints).
+
+    nearest (`dafs --seed-nearest`): the object gains .nearest with .row, .ident, .den and .pid: for every
+    new sequence the seed row nearest to it in the columns of its own result j -- one Context.alignment_identity call per
+    result over its printed rows with use = its rf and the seed rows as candidates -- and .names, the seed rows' Stockholm
+    names.  A new sequence without a residue in a seed column has no nearest row (NONE, NaN).  The results do not change.
+
+    nr (a threshold in (0, 1]; needs merged; `dafs --seed-nr`): the non-redundant subset of the merged rows.  One
+    Context.alignment_identity call over .merged.rows with use = .merged.rf gives the redundancy bits, capi.nr_select the
+    subset: the seed rows are forced and visited first, in seed order, then the new rows by descending .score, ties in input
+    order.  .merged gains .kept, .by (capi.nr_select), .nr_rows, .nr_names and .nr_stockholm: the merged block without the
+    dropped rows and with a `#=GF CC nr T kept K of M hits` line, nothing else changed (dafs_host_stockholm_nr).  A new row
+    without a residue in a seed column is compared with nothing and kept."""
     import time
+    if nr is not None and not merged:
+        raise ValueError(capi.alistat_refusal(capi.NR_NEEDS_MERGED))
+    if nr is not None and not (0.0 < float(nr) <= 1.0):
+        raise ValueError(capi.alistat_refusal(capi.NR_THRESHOLD))
     o = {k: p.default for k, p in inspect.signature(add).parameters.items() if k not in ("seed_names", "seed_rows", "names", "seqs", "ctx")}
     unknown = set(opts) - set(o)
     if unknown:
@@ -867,6 +993,12 @@ def add_each(seed_names, seed_rows, names, seqs, ctx=None, max_bytes=None, merge
     out.lengths = np.array([len(sq) for sq in seqs], np.uint32)
     out.matched = np.zeros(k, np.uint32)
     pps = [None] * k  # merged: per new sequence the residue values of its row
+    if nearest:
+        out.nearest = Nearest()
+        out.nearest.names = stockholm.names(seed_names)
+        out.nearest.row = np.full(k, NONE, np.uint32)
+        out.nearest.ident, out.nearest.den = np.zeros(k, np.uint32), np.zeros(k, np.uint32)
+        out.nearest.pid = np.full(k, np.nan, np.float64)
     if seed_ss is not None:
         out.support = dict(both=np.zeros(k, np.uint32), canonical=np.zeros(k, np.uint32), half=np.zeros(k, np.uint32),
                            expected=np.zeros(k, np.float64))
@@ -952,22 +1084,28 @@ def add_each(seed_names, seed_rows, names, seqs, ctx=None, max_bytes=None, merge
                     for key in out.support:  # the new sequence is the first row of its alignment
                         out.support[key][j] = support[f][key][0]
                 _final(ctx, res, seed_names + [names[j]], seed_seqs + [seqs[j]], f * n, alns[f][0], alns[f][1], finals[f], rls[f], None,
-                       rfs[f], covariation, rows_ss[f])
+                       rfs[f], covariation, rows_ss[f], o["identity"])
                 out.results[j] = res
                 out.score[j] = oj["score"]
                 out.iterations[j] = oj["iterations"]
                 out.matched[j] = int((np.asarray(oj["z"]) != NONE).sum())
+                if nearest and out.matched[j]:  # printed rows: the m seed rows, then the new one
+                    idn = ctx.alignment_identity(res.rows, use=rfs[f], cand=np.arange(n) < m)
+                    out.nearest.row[j], out.nearest.ident[j], out.nearest.den[j] = idn.nearest[m], idn.nearest_ident[m], idn.nearest_den[m]
+                    out.nearest.pid[j] = idn.pid_nearest[m]
             t.append(time.perf_counter())
             for key, a, b in (("gather", 0, 1), ("transforms", 1, 2), ("nodes", 2, 3), ("final", 3, 4)):
                 secs[key] += t[b] - t[a]
+        if merged:
+            t_merge = time.perf_counter()
+            out.merged = _merge_each(seed_names, seed_rows, seed_ss, names, seqs, [r.z[0] for r in out.results], pps)
+            if nr is not None:
+                _select_nr(ctx, out.merged, m, out.score, out.matched, float(nr))
+            secs["merge"] = time.perf_counter() - t_merge
     finally:
         src.close()
         if own and ctx is not None:
             ctx.close()
-    if merged:
-        t_merge = time.perf_counter()
-        out.merged = _merge_each(seed_names, seed_rows, seed_ss, names, seqs, [r.z[0] for r in out.results], pps)
-        secs["merge"] = time.perf_counter() - t_merge
     secs["total"] = time.perf_counter() - t_start
     out.seconds = secs
     return out

@@ -59,13 +59,24 @@ def row_ss_str(row, ss):
     return "".join("." if ch == "-" else next(chars) for ch in row)
 
 
-def block(tree_line, row_names, rows, residue_rel, col_rel, ss_str, rf=None, cov=None, row_ss=None):
+def with_weights(text, row_names, weights):
+    """A block with one `#=GS <name> WT <%.6f>` line per row directly after its `#=GF` lines (dafs_host_stockholm_weights;
+    DESIGN.md section 18): the sequence weights of Context.alignment_weights.  Every other byte stays."""
+    row_names = list(row_names)
+    w = np.ascontiguousarray(weights, np.float64)
+    if w.shape != (len(row_names),):
+        raise ValueError("stockholm.with_weights: one weight per row")
+    return capi.host_text(capi._stockholm_weights, text.encode("latin-1"), len(row_names), capi.c_strings(row_names), w.ctypes.data)
+
+
+def block(tree_line, row_names, rows, residue_rel, col_rel, ss_str, rf=None, cov=None, row_ss=None, weights=None):
     """One alignment.  row_names / rows / residue_rel: per printed row (stdout order) its Stockholm name, its text and its
     residues' reliabilities; col_rel: per column; a column without residues gets '.' in PP_cons.  tree_line None: no
     `#=GF CC` line.  rf: per column True for a seed column ('x'), False for an insert column ('.'), written as `#=GC RF`
     after PP_cons; None: no RF line.  cov: the cov_SS_cons characters (cov_ss_cons), written as `#=GC cov_SS_cons` directly after
     PP_cons; None: no such line, and the labels are as wide as without it.  row_ss: per row its own structure in the row's
-    columns (row_ss_str), written as `#=GR <name> SS` after the row's PP line; None: no such lines."""
+    columns (row_ss_str), written as `#=GR <name> SS` after the row's PP line; None: no such lines.  weights: per row its
+    sequence weight, written as `#=GS <name> WT` lines (with_weights); None: the block byte for byte as without them."""
     row_names, rows = list(row_names), list(rows)
     col = np.ascontiguousarray(col_rel, np.float64)
     rel = [np.ascontiguousarray(r, np.float64) for r in residue_rel]
@@ -79,9 +90,10 @@ def block(tree_line, row_names, rows, residue_rel, col_rel, ss_str, rf=None, cov
     text = [None if t is None else t.encode("latin-1") for t in (tree_line, ss_str, cov)]
     if row_ss is not None and len(row_ss) != len(rows):
         raise ValueError("stockholm.block: one structure per row")
-    return capi.host_text(capi._stockholm_block_rows, text[0], len(rows), len(col), capi.c_strings(row_names), capi.c_strings(rows),
-                          (C.c_void_p * max(len(rel), 1))(*[r.ctypes.data for r in rel]), col.ctypes.data, text[1],
-                          None if rf8 is None else rf8.ctypes.data, text[2], None if row_ss is None else capi.c_strings(list(row_ss)))
+    out = capi.host_text(capi._stockholm_block_rows, text[0], len(rows), len(col), capi.c_strings(row_names), capi.c_strings(rows),
+                         (C.c_void_p * max(len(rel), 1))(*[r.ctypes.data for r in rel]), col.ctypes.data, text[1],
+                         None if rf8 is None else rf8.ctypes.data, text[2], None if row_ss is None else capi.c_strings(list(row_ss)))
+    return out if weights is None else with_weights(out, row_names, weights)
 
 
 def block_merged(row_names, rows, residue_rel, ss_str, rf):

@@ -583,6 +583,79 @@ int dafs_hip_alignment_covariation(dafs_hip_ctx* ctx, uint32_t n, uint32_t len, 
                                    double* best_e, double* pair_score, double* pair_e, uint32_t* pair_rows,
                                    uint32_t* pair_canonical, uint32_t* pair_types, int64_t* total, int64_t* g);
 
+/* Alignment statistics: how similar the rows of an alignment are to one another (no counterpart in the reference; definitions,
+ * to the bit, in DESIGN.md section 18 "Alignment statistics").  Both device calls read the alignment alone, none of the
+ * context's stores, and work on a context on which no sequences were set.
+ *   cell[n * len]  row-major, one byte per cell: A 0, C 1, G 2, U/T 3, any other letter 4 (a residue that matches nothing),
+ *                  a gap 5 (dafs_host_ali_code)
+ *   use[len]       the columns that count, or NULL: all of them.  Everything below sees used columns only.
+ *   cand[n]        the rows that may be somebody's nearest, or NULL: every row
+ * res(r) = cells of r with code <= 4; aligned(r, s) = columns where both have code <= 4; ident(r, s) = columns where both codes
+ * are equal and <= 3; den = min(res(r), res(s)); pid = (double)ident / (double)den.  (i1, d1) is more identical than (i2, d2)
+ * iff i1 * d2 > i2 * d1 in uint64.  nearest(r) = the s != r with cand[s] of the most identical (ident, den), the smallest s
+ * among equals, DAFS_HIP_NONE without a candidate (nearest_ident and nearest_den are then 0).  red(r, s) <=> (double)ident >=
+ * nr_threshold * (double)den, one multiplication and one comparison in double.  Outputs (host; any may be NULL):
+ *   res[n]
+ *   ident[n * n], aligned[n * n]        the whole matrices (n <= 32768); diagonal: the cells of r with code <= 3, and res(r)
+ *   nearest[n], nearest_ident[n], nearest_den[n]
+ *   red[n * ceil(n / 32)]               bit s % 32 of word s / 32 of row r = red(r, s), the diagonal and the padding 0
+ *                                       (n <= 65536); with nr_threshold = 0 it is not computed and not written
+ * DAFS_HIP_EINVAL before any launch (outputs untouched, context usable): n or len 0 or above 2^20, a code above 5, a row
+ * without a residue in the used columns, nr_threshold outside [0, 1], a matrix beyond its limit. */
+int dafs_hip_alignment_identity(dafs_hip_ctx* ctx, uint32_t n, uint32_t len, const uint8_t* cell, const uint8_t* use,
+                                const uint8_t* cand, double nr_threshold, uint32_t* res, uint32_t* ident, uint32_t* aligned,
+                                uint32_t* nearest, uint32_t* nearest_ident, uint32_t* nearest_den, uint32_t* red);
+/* Henikoff position-based weights in Easel's form, in double and in this order: k_c(a) = rows with code
+ * a in column c (a = 0..4), t_c = how many a have k_c(a) > 0; v_r = the running sum over the used columns c, ascending, where r
+ * has a code <= 4, of 1.0 / (double)(t_c * k_c(code)); u_r = v_r / (double)res(r); U = the running sum of u_r, r ascending;
+ * weight[r] = (u_r * (double)n) / U.  n = 1: 1.0 without a launch.  Refusals as above. */
+int dafs_hip_alignment_weights(dafs_hip_ctx* ctx, uint32_t n, uint32_t len, const uint8_t* cell, const uint8_t* use, double* weight);
+/* The non-redundant subset (host code) from the bit matrix `red` of dafs_hip_alignment_identity.  The
+ * rows are visited in the order rank[0], rank[1], ... (a permutation of 0..n-1, else DAFS_HIP_EINVAL with a message in
+ * dafs_hip_last_error).  A row with forced[r] != 0 (NULL: none) is always kept; any other row is kept iff it is redundant with
+ * no row kept before it.  kept[n]: 1 or 0; by[n]: the first kept row, in visiting order, that removes r, DAFS_HIP_NONE for a
+ * kept row. */
+int dafs_host_nr_select(uint32_t n, const uint32_t* red, const uint32_t* rank, const uint8_t* forced, uint8_t* kept, uint32_t* by);
+/* What both drivers say when they refuse a combination of the alignment statistics' options */
+enum {
+  DAFS_ALISTAT_NO_PAIRWISE = 0, /* identity statistics asked of pairwise alignments */
+  DAFS_ALISTAT_NR_NEEDS_MERGED, /* a non-redundant subset without the merged alignment */
+  DAFS_ALISTAT_NR_THRESHOLD,    /* a threshold outside (0, 1] */
+  DAFS_ALISTAT_TOO_MANY_ROWS    /* the summary needs the identity matrix: more than 32768 rows */
+};
+const char* dafs_host_alistat_refusal(int which);
+/* The cell code of a character for the two calls above; 255 for a character that is neither a letter nor '-' or '.' */
+uint8_t dafs_host_ali_code(char ch);
+/* Average, minimum and maximum pid over the pairs r < s into summary[3]: the average a running double
+ * sum with r ascending, then s ascending, divided by the number of pairs; minimum and maximum by the integer order.  n = 1:
+ * three NaN.  ident is the n x n matrix, res as returned. */
+int dafs_host_identity_summary(uint32_t n, const uint32_t* ident, const uint32_t* res, double* summary);
+/* The --identity table: the line "# rows n columns len average A min B max C", then per row r the line "r+1 name residues
+ * weight nearest+1 nearest_name pid", tab-separated, floats as %.9g, "nan" for a NaN; a row without a nearest row has "0",
+ * "-" and "nan" in the last three fields. */
+int dafs_host_identity_table(uint32_t n, uint32_t len, const char* const* names, const uint32_t* res, const double* weight,
+                             const uint32_t* nearest, const uint32_t* nearest_ident, const uint32_t* nearest_den,
+                             const double* summary, char** table);
+/* The --identity-matrix table, one line per pair r < s as dafs_host_pairwise_table lays its pairs out: "r+1 s+1 names[r]
+ * names[s] ident aligned den pid" */
+int dafs_host_identity_matrix_table(uint32_t n, const char* const* names, const uint32_t* res, const uint32_t* ident,
+                                    const uint32_t* aligned, char** table);
+/* A Stockholm block with one "#=GS <name> WT <%.6f>" line per row directly after its "#=GF" lines (after "# STOCKHOLM 1.0"
+ * when it has none); every other byte of `block` is kept. */
+int dafs_host_stockholm_weights(const char* block, uint32_t n, const char* const* names, const double* weight, char** out);
+/* The non-redundant block of a merged alignment: `block` (dafs_host_stockholm_block_merged over the n
+ * rows `names`, the first nseed of them the seed's) without the row and the "#=GR" lines of every row with kept[r] = 0, and
+ * with the line "#=GF CC nr <threshold as %.9g> kept K of M hits" after "# STOCKHOLM 1.0" (M = n - nseed, K of them kept).
+ * Nothing else changes: columns that become all-gap stay, and so do the "#=GC" lines. */
+int dafs_host_stockholm_nr(const char* block, uint32_t n, const char* const* names, const uint8_t* kept, uint32_t nseed,
+                           double threshold, char** out);
+/* dafs_host_seed_table_support with two more columns at the end: the Stockholm name of the seed row nearest to the sequence
+ * (nearest_name[j], "-" for none) and its identity as %.9g.  Both NULL: the table of dafs_host_seed_table_support. */
+int dafs_host_seed_table_nearest(uint32_t n, const char* const* headers, const uint32_t* length, const uint32_t* matched,
+                                 const double* score, const int64_t* iterations, const uint32_t* both, const uint32_t* canonical,
+                                 const uint32_t* half, const double* expected, const char* const* nearest_name,
+                                 const double* identity, char** table);
+
 /* ---- device-resident exchange of the sparse stores (multi-GPU runs) ---------------------------------------------------
  * One process per GPU shards phase 1 of DAFS::run (src/dafs.cpp:1787-1827): the folds (src/fold.cpp:66-67), the pair jobs
  * (src/align.cpp:46-50) and the output pairs of relax_matching_probability (src/dafs.cpp:265-315) are independent.  The
