@@ -214,6 +214,22 @@ _alignment_covariation = _sig("dafs_hip_alignment_covariation", C.c_int,
 _alignment_identity = _sig("dafs_hip_alignment_identity", C.c_int,
                            [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double] + [C.c_void_p] * 7)
 _alignment_weights = _sig("dafs_hip_alignment_weights", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p])
+
+
+class CompareOut(C.Structure):
+    """dafs_compare_out"""
+    _fields_ = [(k, C.c_void_p) for k in ("residues", "shared", "refp", "testp", "sps", "ppv", "total", "score", "k", "m", "colref", "colshared",
+                                         "reproduced", "tc", "pair_shared", "pair_refp", "pair_testp", "pp_count", "tp", "nref", "ntest", "ss_total")]
+
+
+_alignment_compare = _sig("dafs_hip_alignment_compare", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32] + [C.c_void_p] * 7 + [C.POINTER(CompareOut)])
+_compare_refusal = _sig("dafs_host_compare_refusal", C.c_char_p, [C.c_int])
+CMP_NEEDS_REF, CMP_NEEDS_COMPARE, CMP_NO_PAIRWISE, CMP_NEEDS_MERGED, CMP_TOO_MANY_ROWS = range(5)  # dafs_host_compare_refusal
+_compare_match = _sig("dafs_host_compare_match", C.c_int, [C.c_uint32, C.POINTER(C.c_char_p), C.c_uint32, C.POINTER(C.c_char_p)] + [C.c_void_p] * 3)
+_seed_pp = _sig("dafs_host_seed_pp", C.c_int, [C.c_char_p, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_int), C.POINTER(C.c_void_p)])
+_compare_table = _sig("dafs_host_compare_table", C.c_int, [C.c_uint32, C.POINTER(C.c_char_p)] + [C.c_uint32] * 4 + [C.c_void_p] * 10 + [C.POINTER(C.c_void_p)])
+_compare_columns_table = _sig("dafs_host_compare_columns_table", C.c_int, [C.c_uint32] + [C.c_void_p] * 4 + [C.POINTER(C.c_void_p)])
+_compare_matrix_table = _sig("dafs_host_compare_matrix_table", C.c_int, [C.c_uint32, C.POINTER(C.c_char_p)] + [C.c_void_p] * 3 + [C.POINTER(C.c_void_p)])
 _nr_select = _sig("dafs_host_nr_select", C.c_int, [C.c_uint32] + [C.c_void_p] * 5)
 _ali_code = _sig("dafs_host_ali_code", C.c_uint8, [C.c_char])
 _identity_summary = _sig("dafs_host_identity_summary", C.c_int, [C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p])
@@ -365,6 +381,51 @@ def identity_summary(ident, res):
     out = np.zeros(3, np.float64)
     check(_identity_summary(n, ident.ctypes.data, res.ctypes.data, out.ctypes.data))
     return tuple(float(x) for x in out)
+
+
+PP_CLASSES = "0123456789*"  # the characters of a "#=GR PP" line, by class
+
+
+def encode_pp(rows):
+    """The characters of "#=GR PP" lines (equally long rows, or None for a row without one) -> the uint8 [n, len] classes of
+    Context.alignment_compare: '0'..'9' 0..9, '*' 10, anything else (the '.' of a gap) 255."""
+    table = np.full(256, 255, np.uint8)
+    for q, ch in enumerate(PP_CLASSES):
+        table[ord(ch)] = q
+    length = max((len(r) for r in rows if r is not None), default=0)
+    rows = [b"." * length if r is None else r.encode("latin-1") if isinstance(r, str) else bytes(r) for r in rows]
+    if not rows or any(len(r) != length for r in rows):
+        raise ValueError("encode_pp: at least one row, all of one length")
+    return table[np.frombuffer(b"".join(rows), np.uint8)].reshape(len(rows), length)
+
+
+def compare_refusal(which):
+    """what both drivers say when they refuse a combination of the comparison's options (dafs_host_compare_refusal)"""
+    return _compare_refusal(which).decode()
+
+
+def compare_match(ref_names, test_names):
+    """dafs_host_compare_match: the rows to compare, as (ref_row, test_row) index arrays over the names in both alignments in
+    the reference's order; ValueError for a name on two rows of either, or fewer than two common names"""
+    ref_names, test_names = list(ref_names), list(test_names)
+    room = max(min(len(ref_names), len(test_names)), 1)
+    count = C.c_uint32()
+    ref_row, test_row = np.zeros(room, np.uint32), np.zeros(room, np.uint32)
+    rc = _compare_match(len(ref_names), c_strings(ref_names), len(test_names), c_strings(test_names), C.byref(count), ref_row.ctypes.data,
+                        test_row.ctypes.data)
+    if rc == -1:
+        raise ValueError(_last_error().decode("latin-1"))
+    check(rc)
+    return ref_row[:count.value].copy(), test_row[:count.value].copy()
+
+
+class Comparison:
+    """Result of Context.alignment_compare, R the reference and T the test alignment.
+    Per row: .residues, .shared, .refp, .testp (uint64), .row_sps, .row_ppv.  Totals: .total_shared, .total_refp, .total_testp,
+    .sps, .ppv.  Per column: .k [len_r], .m [len_t], .colref, .colshared, .reproduced [len_r]; .tc_reproduced, .tc_columns, .tc.
+    With matrix: .pair_shared, .pair_refp, .pair_testp ([n, n] uint32).  With pp: .pp_residues, .pp_ref, .pp_shared (uint64 [11])
+    and .pp_accuracy (NaN for a class without pairs).  With both structures: .tp, .nref, .ntest per row, .total_tp, .total_nref,
+    .total_ntest, .sensitivity, .ss_ppv, .f."""
 
 
 class PairPosteriors:
@@ -933,6 +994,69 @@ class Context:
         weight = np.zeros(n, np.float64)
         check(_alignment_weights(self._h, n, L, cell.ctypes.data, None if use is None else use.ctypes.data, weight.ctypes.data))
         return weight
+
+    def alignment_compare(self, ref_rows, test_rows, use_ref=None, use_test=None, ss_ref=None, ss_test=None, pp=None, matrix=False):
+        """How far two alignments of the same sequences agree (dafs_hip_alignment_compare).  ref_rows,
+        test_rows: the text rows, or their cells (uint8 [n, len], encode_cells), row r of both holding the same residues.
+        use_ref, use_test: the aligned columns (None: all).  ss_ref, ss_test: partner arrays (NONE for unpaired), both or
+        neither.  pp: the PP classes of the test's cells (uint8 [n, len_test], encode_pp).  matrix: the three pair matrices
+        too.  Returns a Comparison."""
+        cr = _cells(ref_rows, "alignment_compare")
+        ct = _cells(test_rows, "alignment_compare")
+        if cr.shape[0] != ct.shape[0]:
+            raise ValueError("alignment_compare: both alignments need the same rows")
+        n, lr = cr.shape
+        lt = ct.shape[1]
+        use_ref = _byte_mask(use_ref, lr, "alignment_compare", "use_ref needs one entry per column of the reference")
+        use_test = _byte_mask(use_test, lt, "alignment_compare", "use_test needs one entry per column of the test")
+        if (ss_ref is None) != (ss_test is None):
+            raise ValueError("alignment_compare: the structure part needs ss_ref and ss_test")
+        if ss_ref is not None:
+            ss_ref = np.ascontiguousarray(ss_ref, np.uint32)
+            ss_test = np.ascontiguousarray(ss_test, np.uint32)
+            if ss_ref.shape != (lr,) or ss_test.shape != (lt,):
+                raise ValueError("alignment_compare: a structure needs one entry per column")
+        if pp is not None:
+            pp = np.ascontiguousarray(pp, np.uint8)
+            if pp.shape != (n, lt):
+                raise ValueError("alignment_compare: pp needs one entry per cell of the test")
+        u64 = lambda *shape: np.zeros(shape, np.uint64)  # noqa: E731
+        arr = dict(residues=np.zeros(n, np.uint32), shared=u64(n), refp=u64(n), testp=u64(n), sps=np.zeros(n), ppv=np.zeros(n), total=u64(3),
+                   score=np.zeros(3), k=np.zeros(lr, np.uint32), m=np.zeros(lt, np.uint32), colref=u64(lr), colshared=u64(lr),
+                   reproduced=np.zeros(lr, np.uint8), tc=u64(2))
+        if matrix:
+            arr.update(pair_shared=np.zeros((n, n), np.uint32), pair_refp=np.zeros((n, n), np.uint32), pair_testp=np.zeros((n, n), np.uint32))
+        if pp is not None:
+            arr.update(pp_count=u64(3, 11))
+        if ss_ref is not None:
+            arr.update(tp=u64(n), nref=u64(n), ntest=u64(n), ss_total=u64(3))
+        o = CompareOut(**{k: v.ctypes.data for k, v in arr.items()})
+        ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+        check(_alignment_compare(self._h, n, lr, lt, cr.ctypes.data, ct.ctypes.data, ptr(use_ref), ptr(use_test), ptr(ss_ref), ptr(ss_test),
+                                 ptr(pp), C.byref(o)))
+        out = Comparison()
+        for key in ("residues", "shared", "refp", "testp", "k", "m", "colref", "colshared"):
+            setattr(out, key, arr[key])
+        out.row_sps, out.row_ppv = arr["sps"], arr["ppv"]
+        out.reproduced = arr["reproduced"].astype(bool)
+        out.total_shared, out.total_refp, out.total_testp = (int(x) for x in arr["total"])
+        out.sps, out.ppv, out.tc = (float(x) for x in arr["score"])
+        out.tc_reproduced, out.tc_columns = (int(x) for x in arr["tc"])
+        if matrix:
+            out.pair_shared, out.pair_refp, out.pair_testp = arr["pair_shared"], arr["pair_refp"], arr["pair_testp"]
+        if pp is not None:
+            out.pp_residues, out.pp_ref, out.pp_shared = arr["pp_count"]
+            with np.errstate(invalid="ignore", divide="ignore"):
+                out.pp_accuracy = np.where(out.pp_ref == 0, np.nan, out.pp_shared.astype(np.float64) / out.pp_ref.astype(np.float64))
+        if ss_ref is not None:
+            out.tp, out.nref, out.ntest = arr["tp"], arr["nref"], arr["ntest"]
+            tp, nref, ntest = (int(x) for x in arr["ss_total"])
+            out.total_tp, out.total_nref, out.total_ntest = tp, nref, ntest
+            nan = float("nan")
+            out.sensitivity = float(tp) / float(nref) if nref else nan
+            out.ss_ppv = float(tp) / float(ntest) if ntest else nan
+            out.f = float(2 * tp) / float(nref + ntest) if nref + ntest else nan
+        return out
 
 
 def fold_complementary(a, b):

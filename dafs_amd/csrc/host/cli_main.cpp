@@ -92,6 +92,10 @@ struct Options {
   double seed_nr = 0.0;         // --seed-nr T: --seed-merged holds the non-redundant block
   bool seed_nr_given = false;
   std::string describe;         // --describe ALIGNMENT: the alignment-only statistics of a finished alignment
+  std::string compare;          // --compare OUT: every printed alignment against the reference
+  std::string compare_ref;      // --compare-ref REF
+  std::string compare_columns;  // --compare-columns OUT
+  std::string compare_matrix;   // --compare-matrix OUT
   std::string input;
   std::vector<std::string> inputs;  // every FILE argument; with two or more, one output block per file
 };
@@ -169,7 +173,19 @@ const char* kHelp =
     "      --describe ALIGNMENT  No FILE: read a finished alignment (Stockholm or aligned FASTA, as --seed reads it, with its\n"
     "                        SS_cons if it has one) and write --identity / --identity-matrix and, if given, --covariation for\n"
     "                        it (--identity: at most 32768 rows); nothing is aligned and nothing is printed.  Only --device and\n"
-    "                        the --cov-* options go with it\n"
+    "                        the --cov-* and --compare* options go with it\n"
+    "      --compare OUT     With --compare-ref REF: also write to OUT how far every printed alignment agrees with the\n"
+    "                        reference alignment REF of the same sequences (read as --seed reads a seed, with its SS_cons if it\n"
+    "                        has one).  The rows compared are the names in both.  Lines \"# rows ..\", \"# pairs shared S ref P\n"
+    "                        test Q sps A ppv B\" (aligned residue pairs in both / in REF / in the alignment), \"# columns\n"
+    "                        reproduced K of M tc C\", \"# structure ..\" when both have a structure, \"# pp class residues ref\n"
+    "                        shared accuracy\" per PP class when the alignment has PP values (--describe of a Stockholm file with\n"
+    "                        PP lines, --seed-merged), then per row: r name residues shared ref test sps ppv [tp nref ntest].\n"
+    "                        With --seed-each it needs --seed-merged and compares the merged alignment in the seed's columns.\n"
+    "                        Not with --pairwise\n"
+    "      --compare-ref REF The reference alignment of --compare\n"
+    "      --compare-columns OUT  With --compare: per column of REF: c residues pairs shared_pairs reproduced\n"
+    "      --compare-matrix OUT   With --compare: per row pair: r s name_r name_s shared ref test sps ppv (at most 16384 rows)\n"
     "\n Aligning options:\n"
     "  -a, --align-model arg Alignment model (value=CONTRAlign, ProbCons) (default: ProbCons)\n"
     "  -p, --align-pct arg   Weight of PCT for matching probabilities (default: 0.25)\n"
@@ -212,7 +228,8 @@ Options parse(int argc, char** argv) {
       {"stockholm", {0, true}}, {"row-structures", {0, false}}, {"seed", {0, true}}, {"pairwise", {0, false}}, {"pairwise-scores", {0, true}},
       {"seed-each", {0, false}}, {"seed-scores", {0, true}}, {"seed-merged", {0, true}}, {"seed-structure", {0, false}},
       {"covariation", {0, true}}, {"cov-shuffles", {0, true}}, {"cov-seed", {0, true}}, {"identity", {0, true}},
-      {"identity-matrix", {0, true}}, {"seed-nearest", {0, false}}, {"seed-nr", {0, true}}, {"describe", {0, true}}};
+      {"identity-matrix", {0, true}}, {"seed-nearest", {0, false}}, {"seed-nr", {0, true}}, {"describe", {0, true}},
+      {"compare", {0, true}}, {"compare-ref", {0, true}}, {"compare-columns", {0, true}}, {"compare-matrix", {0, true}}};
   std::map<char, std::string> shorts;
   for (const auto& kv : spec)
     if (kv.second.first) shorts[kv.second.first] = kv.first;
@@ -306,6 +323,10 @@ Options parse(int argc, char** argv) {
       if (value.empty()) throw "--" + name + " needs a file name";
       (name == "identity" ? o.identity : name == "describe" ? o.describe : o.identity_matrix) = value;
     }
+    else if (name == "compare" || name == "compare-ref" || name == "compare-columns" || name == "compare-matrix") {
+      if (value.empty()) throw "--" + name + " needs a file name";
+      (name == "compare" ? o.compare : name == "compare-ref" ? o.compare_ref : name == "compare-columns" ? o.compare_columns : o.compare_matrix) = value;
+    }
     else if (name == "seed-nearest") o.seed_nearest = true;
     else if (name == "seed-nr") {
       size_t used = 0;
@@ -338,11 +359,17 @@ Options parse(int argc, char** argv) {
     throw std::string("--pairwise: two rows carry no covariation; --covariation, --cov-shuffles and --cov-seed cannot be combined with --pairwise");
   if (!o.describe.empty()) {  // a finished alignment: nothing that aligns, and no FILE
     for (const std::string& g : given)
-      if (g != "describe" && g != "identity" && g != "identity-matrix" && g != "covariation" && g != "cov-shuffles" && g != "cov-seed" && g != "device")
+      if (g != "describe" && g != "identity" && g != "identity-matrix" && g != "covariation" && g != "cov-shuffles" && g != "cov-seed" && g != "device" &&
+          g.compare(0, 7, "compare") != 0)
         throw "--describe reads a finished alignment: --" + g + " cannot be combined with --describe";
     if (!o.inputs.empty()) throw std::string("--describe takes no FILE: the alignment is its argument");
-    if (o.identity.empty() && o.covariation.empty()) throw std::string("--describe needs --identity or --covariation");
+    if (o.identity.empty() && o.covariation.empty() && o.compare.empty() && o.compare_ref.empty())
+      throw std::string("--describe needs --identity or --covariation");
   }
+  if (o.compare.empty() != o.compare_ref.empty()) throw std::string(dafs_host_compare_refusal(DAFS_COMPARE_NEEDS_REF));
+  if ((!o.compare_columns.empty() || !o.compare_matrix.empty()) && o.compare.empty()) throw std::string(dafs_host_compare_refusal(DAFS_COMPARE_NEEDS_COMPARE));
+  if (o.pairwise && !o.compare.empty()) throw std::string(dafs_host_compare_refusal(DAFS_COMPARE_NO_PAIRWISE));
+  if (o.seed_each && !o.compare.empty() && o.seed_merged.empty()) throw std::string(dafs_host_compare_refusal(DAFS_COMPARE_NEEDS_MERGED));
   if (!o.identity_matrix.empty() && o.identity.empty()) throw std::string("--identity-matrix needs --identity");
   if (o.pairwise && !o.identity.empty()) throw std::string(dafs_host_alistat_refusal(DAFS_ALISTAT_NO_PAIRWISE));
   if (o.seed_each && !o.identity.empty()) throw std::string("--seed-each: --identity cannot be combined with --seed-each (--seed-nearest names each new sequence's nearest seed row)");
@@ -794,6 +821,135 @@ void write_identity(const Options& o, const std::vector<IdentityText>& idt, cons
   if (!o.identity_matrix.empty()) write_tables("--identity-matrix", o.identity_matrix, matrices, headers);
 }
 
+// --compare: a printed alignment against the reference of --compare-ref (dafs_hip_alignment_compare; DESIGN.md section 19;
+// pipeline.compare is the Python twin)
+struct CompareText {
+  std::string table, columns, matrix;  // the tables of --compare, --compare-columns and --compare-matrix
+};
+
+// An alignment file as the seed reader reads it: names, cleaned rows, the structure over the cleaned columns if it has one
+// (has_ss), and with pp the PP rows of a Stockholm file (left empty when it has no PP line)
+void read_alignment(const std::string& file, const std::string& option, std::vector<std::string>& names, std::vector<std::string>& rows, VU& ss,
+                    bool& has_ss, std::vector<std::string>* pp = nullptr) {
+  std::ifstream is(file.c_str(), std::ios::binary);
+  if (!is.is_open()) throw option + ": cannot open " + file;
+  const std::string text((std::istreambuf_iterator<char>(is)), std::istreambuf_iterator<char>());
+  uint32_t n = 0;
+  char *nm = nullptr, *rw = nullptr, *st = nullptr;
+  int has = 0;
+  check_text(dafs_host_seed_parse_structure(text.data(), text.size(), &n, &has, &nm, &rw, &st));
+  names = lines_of(take(nm), n);
+  rows = lines_of(take(rw), n);
+  const std::string structure = take(st);
+  has_ss = has != 0;
+  if (has_ss) {
+    ss.assign(rows.empty() ? 1 : rows[0].size() + 1, DAFS_HIP_NONE);
+    uint32_t columns = 0;
+    check_text(dafs_host_seed_clean_structure(n, c_strs(names).data(), c_strs(rows).data(), structure.c_str(), ss.data(), &columns, &rw));
+    rows = lines_of(take(rw), n);
+    ss.resize(columns);
+  } else {
+    check_text(dafs_host_seed_clean(n, c_strs(names).data(), c_strs(rows).data(), &rw));
+    rows = lines_of(take(rw), n);
+  }
+  if (pp) {
+    int has_pp = 0;
+    char* pt = nullptr;
+    check_text(dafs_host_seed_pp(text.data(), text.size(), &n, &has_pp, &pt));
+    const std::vector<std::string> got = lines_of(take(pt), n);
+    if (has_pp) *pp = got;
+  }
+}
+
+struct Reference {
+  std::vector<std::string> names, rows;
+  VU ss;
+  bool has_ss = false;
+};
+
+// the reference of --compare-ref, read once
+const Reference& reference_of(const Options& o) {
+  static Reference ref;
+  static bool loaded = false;
+  if (!loaded) {
+    read_alignment(o.compare_ref, "--compare-ref", ref.names, ref.rows, ref.ss, ref.has_ss);
+    loaded = true;
+  }
+  return ref;
+}
+
+// names: the rows' Stockholm names; ss: the alignment's structure or nullptr; use: its aligned columns or nullptr (all); pp:
+// per row its PP characters ("" for a row without) or nullptr
+void compare_of(dafs_hip_ctx* ctx, const Options& o, const std::vector<std::string>& names, const std::vector<std::string>& rows, const VU* ss,
+                const uint8_t* use, const std::vector<std::string>* pp, CompareText& out) {
+  const Reference& ref = reference_of(o);
+  const uint32_t nr = (uint32_t)ref.names.size(), nt = (uint32_t)names.size();
+  std::vector<uint32_t> ref_row(std::min(nr, nt) + 1), test_row(std::min(nr, nt) + 1);
+  uint32_t n = 0;
+  check_text(dafs_host_compare_match(nr, c_strs(ref.names).data(), nt, c_strs(names).data(), &n, ref_row.data(), test_row.data()));
+  const bool matrix = !o.compare_matrix.empty(), both = ref.has_ss && ss;
+  if (matrix && n > 16384) throw std::string(dafs_host_compare_refusal(DAFS_COMPARE_TOO_MANY_ROWS));
+  std::vector<std::string> rr, tr, row_names;
+  for (uint32_t k = 0; k < n; ++k) {
+    rr.push_back(ref.rows[ref_row[k]]);
+    tr.push_back(rows[test_row[k]]);
+    const std::string& h = ref.names[ref_row[k]];
+    const size_t b = h.find_first_not_of(" \t\n\v\f\r"), e = h.find_first_of(" \t\n\v\f\r", b);
+    row_names.push_back(b == std::string::npos ? std::string() : h.substr(b, e == std::string::npos ? e : e - b));
+  }
+  const uint32_t len_r = (uint32_t)rr[0].size(), len_t = (uint32_t)tr[0].size();
+  const std::vector<uint8_t> cell_r = cells_of(rr), cell_t = cells_of(tr);
+  std::vector<uint8_t> classes;
+  if (pp) {
+    classes.assign((size_t)n * len_t, 255);
+    const std::string chars = "0123456789*";
+    for (uint32_t k = 0; k < n; ++k) {
+      const std::string& line = (*pp)[test_row[k]];
+      for (size_t c = 0; c < line.size() && c < len_t; ++c) {
+        const size_t q = chars.find(line[c]);
+        if (q != std::string::npos) classes[(size_t)k * len_t + c] = (uint8_t)q;
+      }
+    }
+  }
+  std::vector<uint32_t> residues(n), kc(len_r), md(len_t), ps, pr, pt;
+  std::vector<uint64_t> shared(n), refp(n), testp(n), total(3), tc(2), colref(len_r), colshared(len_r), tp(n), nref(n), ntest(n), pp_count(33);
+  std::vector<uint8_t> reproduced(len_r);
+  if (matrix) {
+    ps.resize((size_t)n * n);
+    pr.resize((size_t)n * n);
+    pt.resize((size_t)n * n);
+  }
+  dafs_compare_out c;
+  memset(&c, 0, sizeof c);
+  c.residues = residues.data(); c.shared = shared.data(); c.refp = refp.data(); c.testp = testp.data();
+  c.total = total.data(); c.tc = tc.data(); c.k = kc.data(); c.m = md.data();
+  c.colref = colref.data(); c.colshared = colshared.data(); c.reproduced = reproduced.data();
+  if (matrix) { c.pair_shared = ps.data(); c.pair_refp = pr.data(); c.pair_testp = pt.data(); }
+  if (pp) c.pp_count = pp_count.data();
+  if (both) { c.tp = tp.data(); c.nref = nref.data(); c.ntest = ntest.data(); }
+  check_text(dafs_hip_alignment_compare(ctx, n, len_r, len_t, cell_r.data(), cell_t.data(), nullptr, use, both ? ref.ss.data() : nullptr,
+                                        both ? ss->data() : nullptr, pp ? classes.data() : nullptr, &c));
+  char* text = nullptr;
+  check_text(dafs_host_compare_table(n, c_strs(row_names).data(), nr - n, nt - n, len_r, len_t, residues.data(), shared.data(), refp.data(),
+                                     testp.data(), total.data(), tc.data(), both ? tp.data() : nullptr, both ? nref.data() : nullptr,
+                                     both ? ntest.data() : nullptr, pp ? pp_count.data() : nullptr, &text));
+  out.table = take(text);
+  check_text(dafs_host_compare_columns_table(len_r, kc.data(), colref.data(), colshared.data(), reproduced.data(), &text));
+  out.columns = take(text);
+  if (matrix) {
+    check_text(dafs_host_compare_matrix_table(n, c_strs(row_names).data(), ps.data(), pr.data(), pt.data(), &text));
+    out.matrix = take(text);
+  }
+}
+
+void write_compare(const Options& o, const std::vector<CompareText>& cmp, const std::vector<std::string>* headers) {
+  std::vector<std::string> tables, columns, matrices;
+  for (const CompareText& t : cmp) { tables.push_back(t.table); columns.push_back(t.columns); matrices.push_back(t.matrix); }
+  write_tables("--compare", o.compare, tables, headers);
+  if (!o.compare_columns.empty()) write_tables("--compare-columns", o.compare_columns, columns, headers);
+  if (!o.compare_matrix.empty()) write_tables("--compare-matrix", o.compare_matrix, matrices, headers);
+}
+
 void write_stockholm(const std::string& file, const std::vector<std::string>& blocks) {
   std::ofstream os(file.c_str(), std::ios::binary);
   if (!os.is_open()) throw "--stockholm: cannot open " + file;
@@ -1031,7 +1187,8 @@ struct PairChunk {
 int align_group(dafs_hip_ctx* ctx, const Options& o, Ranks& rk, int align_model, const std::vector<std::vector<Fasta> >& fams,
                 const std::vector<size_t>& members, const std::vector<std::ostream*>& out, const std::vector<std::string*>& sto,
                 PairChunk* pc = nullptr, const std::vector<std::string*>& cov = std::vector<std::string*>(),
-                const std::vector<IdentityText*>& idt = std::vector<IdentityText*>());
+                const std::vector<IdentityText*>& idt = std::vector<IdentityText*>(),
+                const std::vector<CompareText*>& cmp = std::vector<CompareText*>());
 
 struct Guard {  // the context of a run, destroyed however the run ends
   dafs_hip_ctx* c;
@@ -1249,7 +1406,7 @@ std::vector<std::string> row_texts(const std::vector<Fasta>& fa, const ALN& aln)
 void finish_alignment(dafs_hip_ctx* ctx, const Options& o, const std::vector<Fasta>& fa, ALN& root, const std::vector<Fasta>& ff,
                       uint32_t first, std::ostream& os, std::string* sto, const std::string* tree_line, const std::vector<uint8_t>* rf,
                       std::string* cov, const VU& ss_final, const Reliability* rl, const std::map<uint32_t, VU>* row_ss = nullptr,
-                      IdentityText* idt = nullptr) {
+                      IdentityText* idt = nullptr, CompareText* cmp = nullptr) {
   std::string str;
   std::map<uint32_t, size_t> rel_at;  // sequence -> its first residue in rl->rel
   {
@@ -1277,7 +1434,7 @@ void finish_alignment(dafs_hip_ctx* ctx, const Options& o, const std::vector<Fas
   std::string cov_chars;
   if (cov) covariation_of(ctx, o, rows, ss_final, *cov, cov_chars);
   std::vector<std::string> names;  // the printed rows' Stockholm names
-  if (sto || idt) {
+  if (sto || idt || cmp) {
     std::vector<std::string> headers;
     for (const Fasta& s : ff) headers.push_back(s.name());
     char* text = nullptr;
@@ -1286,6 +1443,7 @@ void finish_alignment(dafs_hip_ctx* ctx, const Options& o, const std::vector<Fas
     for (const auto& row : root) names.push_back(all_names[row.first - first]);
   }
   if (idt) identity_of(ctx, names, rows, !o.identity_matrix.empty(), *idt);
+  if (cmp) compare_of(ctx, o, names, rows, &ss_final, nullptr, nullptr, *cmp);
   if (sto) {
     char* text = nullptr;
     std::vector<const double*> rr;
@@ -1409,6 +1567,7 @@ int run_add(const Options& o, int align_model) {
   for (uint32_t c = 0; c < C; ++c) rf[seed_col[c]] = 1;
   std::string sto, cov;
   IdentityText idt;
+  CompareText cmp;
   std::map<uint32_t, VU> row_ss;
   if (o.row_structures) {
     std::vector<uint32_t> every(m + k);
@@ -1421,11 +1580,12 @@ int run_add(const Options& o, int align_model) {
   std::vector<Reliability> rl(1);
   if (!o.stockholm.empty()) reliabilities(ctx, fa, {&root}, {ss}, false, rl);
   finish_alignment(ctx, o, fa, root, fa, 0, std::cout, o.stockholm.empty() ? nullptr : &sto, nullptr, &rf, o.covariation.empty() ? nullptr : &cov,
-                   ss, &rl[0], o.row_structures ? &row_ss : nullptr, o.identity.empty() ? nullptr : &idt);
+                   ss, &rl[0], o.row_structures ? &row_ss : nullptr, o.identity.empty() ? nullptr : &idt, o.compare.empty() ? nullptr : &cmp);
   std::cout.flush();
   if (!o.stockholm.empty()) write_stockholm(o.stockholm, {sto});
   if (!o.covariation.empty()) write_covariation(o.covariation, {cov}, nullptr);
   if (!o.identity.empty()) write_identity(o, {idt}, nullptr);
+  if (!o.compare.empty()) write_compare(o, {cmp}, nullptr);
   return 0;
 }
 
@@ -1663,6 +1823,15 @@ int run_add_each(const Options& o, int align_model) {
     check_text(dafs_host_stockholm_block_merged(m + k, width, c_strs(names).data(), c_strs(rows).data(), rr.data(), brackets.data(), rf.data(),
                                                 nullptr, &text));
     std::string block = take(text);
+    if (!o.compare.empty()) {  // the merged alignment in the seed's columns, with the PP classes of its own block
+      std::vector<std::string> pp(m, std::string());
+      pp.resize(m + k, std::string(width, '.'));
+      for (uint32_t j = 0, off = 0; j < k; off += lens[j], ++j)
+        for (uint32_t i = 0; i < lens[j]; ++i) pp[m + j][res_col[off + i]] = dafs_host_pp_char(new_pp[j][i]);
+      CompareText cmp;
+      compare_of(ctx, o, names, rows, &carried, rf.data(), &pp, cmp);
+      write_compare(o, {cmp}, nullptr);
+    }
     if (o.seed_nr_given) {  // the non-redundant rows: the rows with a residue in a seed column are compared
       std::vector<uint32_t> inc, pos(m + k, DAFS_HIP_NONE);
       std::vector<std::string> inc_rows;
@@ -1840,6 +2009,15 @@ int run_describe(const Options& o) {
     covariation_of(ctx, o, rows, ss, cov, chars);
     write_covariation(o.covariation, {cov}, nullptr);
   }
+  if (!o.compare.empty()) {  // the file again: whether it has a structure, and its PP lines
+    std::vector<std::string> h2, r2, pp;
+    VU ss2;
+    bool has_ss = false;
+    read_alignment(o.describe, "--describe", h2, r2, ss2, has_ss, &pp);
+    CompareText cmp;
+    compare_of(ctx, o, names, rows, has_ss ? &ss2 : nullptr, nullptr, pp.empty() ? nullptr : &pp, cmp);
+    write_compare(o, {cmp}, nullptr);
+  }
   return 0;
 }
 
@@ -1912,11 +2090,20 @@ int run(const Options& o, Ranks& rk) {
       for (size_t f : members) v.push_back(&idts[f]);
     return v;
   };
+  // --compare: the same, one set of tables per input file
+  std::vector<CompareText> cmps(o.compare.empty() ? 0 : o.inputs.size());
+  auto cmp_of = [&](const std::vector<size_t>& members) {
+    std::vector<CompareText*> v;
+    if (!cmps.empty())
+      for (size_t f : members) v.push_back(&cmps[f]);
+    return v;
+  };
   if (!multi) {
-    align_group(ctx, o, rk, align_model, fams, {0}, {&std::cout}, sto_of({0}), nullptr, cov_of({0}), idt_of({0}));
+    align_group(ctx, o, rk, align_model, fams, {0}, {&std::cout}, sto_of({0}), nullptr, cov_of({0}), idt_of({0}), cmp_of({0}));
     if (rk.rank == 0 && !o.stockholm.empty()) write_stockholm(o.stockholm, sto_blocks);
     if (rk.rank == 0 && !o.covariation.empty()) write_covariation(o.covariation, cov_tables, nullptr);
     if (rk.rank == 0 && !o.identity.empty()) write_identity(o, idts, nullptr);
+    if (rk.rank == 0 && !o.compare.empty()) write_compare(o, cmps, nullptr);
     return 0;
   }
   // Several files: every file with two or more sequences in one batch (dafs_hip_set_families: shared launches, one guide
@@ -1935,7 +2122,7 @@ int run(const Options& o, Ranks& rk) {
     std::vector<std::ostream*> os;
     for (size_t f : members) os.push_back(&outs[f]);
     try {
-      align_group(ctx, o, rk, align_model, fams, members, os, sto_of(members), nullptr, cov_of(members), idt_of(members));
+      align_group(ctx, o, rk, align_model, fams, members, os, sto_of(members), nullptr, cov_of(members), idt_of(members), cmp_of(members));
     } catch (const char* str) {
       throw names(members) + ": " + str;
     } catch (const std::string& str) {
@@ -1950,6 +2137,7 @@ int run(const Options& o, Ranks& rk) {
   if (!o.stockholm.empty()) write_stockholm(o.stockholm, sto_blocks);
   if (!o.covariation.empty()) write_covariation(o.covariation, cov_tables, &o.inputs);
   if (!o.identity.empty()) write_identity(o, idts, &o.inputs);
+  if (!o.compare.empty()) write_compare(o, cmps, &o.inputs);
   return 0;
 }
 
@@ -1957,10 +2145,10 @@ int run(const Options& o, Ranks& rk) {
 // tree per family, the progressive phase over the forest (the ready nodes of every family share each round), then per
 // family the refinement, the common structure and the output on *out[k]; with --stockholm (sto not empty) also the
 // family's Stockholm block in *sto[k], with --covariation (cov not empty) its covariation table in *cov[k], and with
-// --identity (idt not empty) its identity tables and weights in *idt[k].
+// --identity (idt not empty) its identity tables and weights in *idt[k], with --compare (cmp not empty) its comparison in *cmp[k].
 int align_group(dafs_hip_ctx* ctx, const Options& o, Ranks& rk, int align_model, const std::vector<std::vector<Fasta> >& fams,
                 const std::vector<size_t>& members, const std::vector<std::ostream*>& out, const std::vector<std::string*>& sto,
-                PairChunk* pc, const std::vector<std::string*>& cov, const std::vector<IdentityText*>& idt) {
+                PairChunk* pc, const std::vector<std::string*>& cov, const std::vector<IdentityText*>& idt, const std::vector<CompareText*>& cmp) {
   const uint F = (uint)members.size();
   std::vector<Fasta> fa;         // every sequence of the group, family after family
   std::vector<uint32_t> first(1, 0);
@@ -2112,7 +2300,8 @@ int align_group(dafs_hip_ctx* ctx, const Options& o, Ranks& rk, int align_model,
       tree_line = tl.str();
     }
     finish_alignment(ctx, o, fa, root, fams[members[f]], first[f], *out[f], sto.empty() ? nullptr : sto[f], &tree_line, nullptr,
-                     cov.empty() ? nullptr : cov[f], ss0[f], &rl[f], row_ss.empty() ? nullptr : &row_ss, idt.empty() ? nullptr : idt[f]);
+                     cov.empty() ? nullptr : cov[f], ss0[f], &rl[f], row_ss.empty() ? nullptr : &row_ss, idt.empty() ? nullptr : idt[f],
+                     cmp.empty() ? nullptr : cmp[f]);
   }
   return 0;
 }

@@ -1,5 +1,5 @@
 // dafs_amd/csrc/host_text.cpp -- the text formats and memory estimates of both drivers as C entry points (include/dafs_hip.h,
-// "host text"): the Stockholm block, the --covariation, --pairwise-scores and --identity tables, the seed reader of --seed, the estimates
+// "host text"): the Stockholm block, the --covariation, --pairwise-scores, --identity and --compare tables, the seed reader of --seed, the estimates
 // and the greedy chunking.  The C++ command line calls them directly and the Python driver through capi.py, so every byte and
 // every formula is defined here once.  Host logic only: nothing here includes HIP or touches a device.
 #include <algorithm>
@@ -720,6 +720,176 @@ extern "C" int dafs_host_seed_clean_structure(uint32_t n, const char* const* nam
     }
     *columns = (uint32_t)kept.size();
     return joined(rw);
+  });
+}
+
+// The "#=GR <name> PP" lines of a Stockholm file's first alignment, over the columns the seed reader keeps
+extern "C" int dafs_host_seed_pp(const char* text, size_t bytes, uint32_t* n, int* has_pp, char** pp) {
+  return text_out(pp, [&]() {
+    if (!n || !has_pp || (bytes && !text)) throw kBadArgument;
+    const std::string all(bytes ? text : "", bytes);
+    std::vector<std::string> nm, rw;
+    parse_seed(all, nm, rw);
+    std::map<std::string, std::string> of;  // name -> its PP characters, the blocks concatenated
+    std::istringstream is(all);
+    std::string ln;
+    bool first = true, stockholm = false;
+    size_t line = 0;
+    while (std::getline(is, ln)) {
+      ++line;
+      const size_t e = ln.find_last_not_of(kSpace);
+      ln = e == std::string::npos ? std::string() : ln.substr(0, e + 1);
+      if (first) {
+        stockholm = ln == "# STOCKHOLM 1.0";
+        first = false;
+      }
+      if (!stockholm || ln == "//") break;
+      if (ln.compare(0, 4, "#=GR") != 0) continue;
+      const std::vector<std::string> f = fields(ln);
+      if (f.size() < 3 || f[2] != "PP") continue;
+      if (f.size() != 4) throw "seed: line " + std::to_string(line) + " is not '#=GR name PP characters'";
+      of[f[1]] += f[3];
+    }
+    const size_t raw = rw.empty() ? 0 : rw[0].size();
+    std::vector<size_t> kept;
+    clean_seed(nm, rw, &kept);
+    for (const auto& kv : of) {
+      if (std::find(nm.begin(), nm.end(), kv.first) == nm.end()) throw "seed: the PP line of " + kv.first + " names no row";
+      if (kv.second.size() != raw)
+        throw "seed: the PP line of " + kv.first + " has " + std::to_string(kv.second.size()) + " columns, the rows have " + std::to_string(raw);
+    }
+    std::vector<std::string> out;
+    for (const std::string& name : nm) {
+      std::string row(kept.size(), '.');
+      const auto it = of.find(name);
+      if (it != of.end())
+        for (size_t k = 0; k < kept.size(); ++k) row[k] = it->second[kept[k]];
+      out.push_back(row);
+    }
+    *n = (uint32_t)nm.size();
+    *has_pp = of.empty() ? 0 : 1;
+    return joined(out);
+  });
+}
+
+// Comparing two alignments: the refusals, the row matching and the tables of --compare,
+// --compare-columns and --compare-matrix
+extern "C" const char* dafs_host_compare_refusal(int which) {
+  switch (which) {
+    case DAFS_COMPARE_NEEDS_REF:
+      return "comparing (--compare OUT, --compare-ref REF) needs both: where the table goes and the reference alignment";
+    case DAFS_COMPARE_NEEDS_COMPARE:
+      return "--compare-columns and --compare-matrix need --compare";
+    case DAFS_COMPARE_NO_PAIRWISE:
+      return "comparing (--compare, compare) cannot be combined with pairwise alignments (--pairwise, pipeline.pairwise): a pair of rows is no "
+             "alignment of the reference's sequences";
+    case DAFS_COMPARE_NEEDS_MERGED:
+      return "comparing (--compare, compare) with --seed-each / add_each compares the merged alignment: it needs --seed-merged / merged";
+    case DAFS_COMPARE_TOO_MANY_ROWS:
+      return "the pair table of a comparison (--compare-matrix) holds the whole matrices: at most 16384 rows";
+    default:
+      return "";
+  }
+}
+
+extern "C" int dafs_host_compare_match(uint32_t n_ref, const char* const* ref_names, uint32_t n_test, const char* const* test_names,
+                                       uint32_t* count, uint32_t* ref_row, uint32_t* test_row) {
+  char* unused = nullptr;
+  const int rc = text_out(&unused, [&]() {
+    if (!count || !ref_row || !test_row) throw kBadArgument;
+    auto first_word = [](std::vector<std::string> v) {  // a Stockholm name: what a row of a Stockholm file is called
+      for (std::string& h : v) {
+        const std::vector<std::string> f = fields(h);
+        h = f.empty() ? std::string() : f[0];
+      }
+      return v;
+    };
+    const std::vector<std::string> rn = first_word(strings(n_ref, ref_names)), tn = first_word(strings(n_test, test_names));
+    std::map<std::string, uint32_t> at;
+    for (uint32_t k = 0; k < n_test; ++k) {
+      if (at.count(tn[k])) throw "compare: the name " + tn[k] + " is on two rows of the test alignment";
+      at[tn[k]] = k;
+    }
+    std::set<std::string> seen;
+    uint32_t m = 0;
+    for (uint32_t k = 0; k < n_ref; ++k) {
+      if (!seen.insert(rn[k]).second) throw "compare: the name " + rn[k] + " is on two rows of the reference alignment";
+      const auto it = at.find(rn[k]);
+      if (it == at.end()) continue;
+      ref_row[m] = k;
+      test_row[m] = it->second;
+      ++m;
+    }
+    if (m < 2)
+      throw "compare: the two alignments share " + std::to_string(m) + " row name" + (m == 1 ? "" : "s") + "; a comparison needs two at least";
+    *count = m;
+    return std::string();
+  });
+  free(unused);
+  return rc;
+}
+
+namespace {
+double quotient(uint64_t a, uint64_t b) { return b ? (double)a / (double)b : std::nan(""); }
+}  // namespace
+
+extern "C" int dafs_host_compare_table(uint32_t n, const char* const* names, uint32_t only_ref, uint32_t only_test, uint32_t len_r,
+                                       uint32_t len_t, const uint32_t* residues, const uint64_t* shared, const uint64_t* refp,
+                                       const uint64_t* testp, const uint64_t* total, const uint64_t* tc, const uint64_t* tp,
+                                       const uint64_t* nref, const uint64_t* ntest, const uint64_t* pp_count, char** table) {
+  return text_out(table, [&]() {
+    const std::vector<std::string> nm = strings(n, names);
+    if (!n || !residues || !shared || !refp || !testp || !total || !tc || (tp && (!nref || !ntest))) throw kBadArgument;
+    std::ostringstream os;
+    os << "# rows " << n << " only_ref " << only_ref << " only_test " << only_test << " columns_ref " << len_r << " columns_test " << len_t << "\n";
+    os << "# pairs shared " << total[0] << " ref " << total[1] << " test " << total[2] << " sps " << fmt9d(quotient(total[0], total[1])) << " ppv "
+       << fmt9d(quotient(total[0], total[2])) << "\n";
+    os << "# columns reproduced " << tc[0] << " of " << tc[1] << " tc " << fmt9d(quotient(tc[0], tc[1])) << "\n";
+    if (tp) {
+      uint64_t t[3] = {0, 0, 0};
+      for (uint32_t r = 0; r < n; ++r) { t[0] += tp[r]; t[1] += nref[r]; t[2] += ntest[r]; }
+      os << "# structure tp " << t[0] << " ref " << t[1] << " test " << t[2] << " sensitivity " << fmt9d(quotient(t[0], t[1])) << " ppv "
+         << fmt9d(quotient(t[0], t[2])) << " f " << fmt9d(quotient(2 * t[0], t[1] + t[2])) << "\n";
+    }
+    if (pp_count)
+      for (uint32_t q = 0; q < 11; ++q)
+        if (pp_count[q])
+          os << "# pp " << "0123456789*"[q] << " " << pp_count[q] << " " << pp_count[11 + q] << " " << pp_count[22 + q] << " "
+             << fmt9d(quotient(pp_count[22 + q], pp_count[11 + q])) << "\n";
+    for (uint32_t r = 0; r < n; ++r) {
+      os << r + 1 << "\t" << nm[r] << "\t" << residues[r] << "\t" << shared[r] << "\t" << refp[r] << "\t" << testp[r] << "\t"
+         << fmt9d(quotient(shared[r], refp[r])) << "\t" << fmt9d(quotient(shared[r], testp[r]));
+      if (tp) os << "\t" << tp[r] << "\t" << nref[r] << "\t" << ntest[r];
+      os << "\n";
+    }
+    return os.str();
+  });
+}
+
+extern "C" int dafs_host_compare_columns_table(uint32_t len_r, const uint32_t* k, const uint64_t* colref, const uint64_t* colshared,
+                                               const uint8_t* reproduced, char** table) {
+  return text_out(table, [&]() {
+    if (!len_r || !k || !colref || !colshared || !reproduced) throw kBadArgument;
+    std::ostringstream os;
+    for (uint32_t c = 0; c < len_r; ++c)
+      os << c + 1 << "\t" << k[c] << "\t" << colref[c] << "\t" << colshared[c] << "\t" << (reproduced[c] ? 1 : 0) << "\n";
+    return os.str();
+  });
+}
+
+extern "C" int dafs_host_compare_matrix_table(uint32_t n, const char* const* names, const uint32_t* pair_shared, const uint32_t* pair_refp,
+                                              const uint32_t* pair_testp, char** table) {
+  return text_out(table, [&]() {
+    const std::vector<std::string> nm = strings(n, names);
+    if (!n || !pair_shared || !pair_refp || !pair_testp) throw kBadArgument;
+    std::ostringstream os;
+    for (uint32_t r = 0; r < n; ++r)
+      for (uint32_t s = r + 1; s < n; ++s) {
+        const size_t at = (size_t)r * n + s;
+        os << r + 1 << "\t" << s + 1 << "\t" << nm[r] << "\t" << nm[s] << "\t" << pair_shared[at] << "\t" << pair_refp[at] << "\t" << pair_testp[at]
+           << "\t" << fmt9d(quotient(pair_shared[at], pair_refp[at])) << "\t" << fmt9d(quotient(pair_shared[at], pair_testp[at])) << "\n";
+      }
+    return os.str();
   });
 }
 

@@ -54,7 +54,7 @@ class Result:
 def run(names, seqs, ctx=None, bp=None, w=4.0, eta0=0.5, t_max=600, w_pct_a=0.25, w_pct_s=0.25, th_a=0.01,
         th_s=0.2, th_s1=None, align_model=capi.ALIGN_PROBCONS, force_iters=0, timers=None, level_sync=False, slice_iters=None,
         mp=None, skip_uncoupled_folds=True, shard=None, round_us=None, w_pct_f=0.0, bp_update=False, bp_update1=False,
-        reliability=False, covariation=False, row_structures=False, identity=False):
+        reliability=False, covariation=False, row_structures=False, identity=False, compare=None):
     """The whole run.  bp: per-sequence (rowptr, col, val) base-pairing rows (--fold-aux); None
     computes them with the device fold model.  mp: supplied matching probabilities (--align-aux), see Context.set_mp.
     shard: (torch.distributed module, torch device) of an initialised process group -- phase 1 (folds, pair posteriors,
@@ -63,7 +63,8 @@ def run(names, seqs, ctx=None, bp=None, w=4.0, eta0=0.5, t_max=600, w_pct_a=0.25
     _phase2_forest).  covariation: True or a dict with shuffles (100), seed (1), e_max (0.05): the result also gets
     .covariation (see _final).  row_structures: the result also gets .row_ss and .row_ss_str, the structure of every printed
     row on its own (see _phase2_forest).  identity: the result also gets .identity (see alignment_identity) and its
-    Stockholm block the `#=GS <name> WT` lines."""
+    Stockholm block the `#=GS <name> WT` lines.  compare: (ref_names, ref_rows[, ref_ss]), a reference alignment of the same
+    sequences as stockholm.read_seed_structure returns it: the result also gets .compare (see compare)."""
     import time
     # combinations this driver does not implement are refused, not ignored (the command line, cli_main.cpp, has no level
     # batches: its --bp-update runs in the resident-node rounds and in the refinement's solve_node)
@@ -87,7 +88,7 @@ def run(names, seqs, ctx=None, bp=None, w=4.0, eta0=0.5, t_max=600, w_pct_a=0.25
     t.append(time.perf_counter())
     fam = dict(names=names, seqs=seqs, first=0, sim=sim, tree=(score, left, right))
     return _phase2_forest(ctx, own, [fam], t, w, eta0, t_max, th_a, th_s, th_s1, force_iters, level_sync, slice_iters,
-                          skip_uncoupled_folds, round_us, bp_update, bp_update1, reliability, covariation, row_structures, identity)[0]
+                          skip_uncoupled_folds, round_us, bp_update, bp_update1, reliability, covariation, row_structures, identity, compare)[0]
 
 
 def _phase1_local(ctx, seqs, bp, mp, align_model, th_a, w_pct_a, w_pct_s, t, w_pct_f=0.0, first=None, constraints=None):
@@ -186,7 +187,7 @@ def _solve_nodes(ctx, prm, take_ready, finish, level_sync=False, slice_iters=Non
 
 def _phase2_forest(ctx, own, fams, t, w, eta0, t_max, th_a, th_s, th_s1, force_iters, level_sync, slice_iters,
                    skip_uncoupled_folds, round_us=None, bp_update=False, bp_update1=False, reliability=False, covariation=False,
-                   row_structures=False, identity=False):
+                   row_structures=False, identity=False, compare=None):
     """The progressive phase and the output of every family of the context at once.  fams: per family a dict with names,
     seqs, first (index of its first sequence in the context), sim and tree = (score, left, right).  The guide trees form one
     forest: a node is ready when both of its children are done, whatever its family, and the ready nodes of all families
@@ -289,7 +290,7 @@ def _phase2_forest(ctx, own, fams, t, w, eta0, t_max, th_a, th_s, th_s1, force_i
         res.rounds = rounds
         sidx, mask = roots[f]
         _final(ctx, res, fm["names"], fm["seqs"], fm["first"], sidx, mask, finals[f], rls[f], res.tree_line, None, covariation, rows_ss[f],
-               identity)
+               identity, compare)
     t.append(time.perf_counter())
     # fold_launch: the folding is only started there; its kernels overlap `pair` and the first half of `pct_fold_tree`,
     # which also holds the wait for them
@@ -376,11 +377,12 @@ def identity_matrix_tsv(row_names, identity):
     return capi.host_text(capi._identity_matrix_table, n, capi.c_strings(row_names), *[a.ctypes.data for a in arrs])
 
 
-def describe(names, rows, ss=None, ctx=None, identity=True, covariation=False):
+def describe(names, rows, ss=None, ctx=None, identity=True, covariation=False, compare=None, pp=None):
     """The alignment-only statistics of a finished alignment (`dafs --describe ALIGNMENT`): nothing is
     aligned.  names / rows / ss: as stockholm.read_seed_structure returns them (ss None: no structure).  Returns a Result with
     .rows, .row_names (stockholm.names), .ss and, as asked, .identity (alignment_identity over all columns) and .covariation
-    (as run's)."""
+    (as run's).  compare (as run's): .compare, this alignment against the reference; pp: its PP rows (stockholm.read_seed_pp)
+    for the comparison's PP part."""
     covariation = cov_options(covariation)
     names, rows = stockholm.clean_seed(names, rows)
     res = Result()
@@ -397,13 +399,73 @@ def describe(names, rows, ss=None, ctx=None, identity=True, covariation=False):
         if covariation:
             res.covariation = ctx.alignment_covariation(rows, res.ss, shuffles=covariation["shuffles"], seed=covariation["seed"])
             res.covariation.update(covariation)
+        if compare is not None:
+            res.compare = compare_result(ctx, compare, res.row_names, rows, None if ss is None else res.ss, pp=pp)
     finally:
         if own:
             ctx.close()
     return res
 
 
-def _final(ctx, res, names, seqs, first, sidx, mask, ss, rl, tree_line, rf=None, covariation=None, row_ss=None, identity=False):
+def compare(ref_names, ref_rows, names, rows, ref_ss=None, ss=None, use_ref=None, use_test=None, pp=None, ctx=None, matrix=True):
+    """How far the alignment (names, rows) agrees with the reference (ref_names, ref_rows) of the same sequences (DESIGN.md
+    section 19; `dafs --compare`).  The compared rows are the names (first words) present in both, in the reference's order
+    (capi.compare_match); both alignments are cut to them and keep their columns.  ref_ss / ss: the two structures, both or
+    the structure part is left out; use_ref / use_test: the aligned columns; pp: per row of `rows` its PP characters, or
+    None.  Returns (result, table, columns_table, matrix_table): the Context.alignment_compare result with .row_names,
+    .only_ref and .only_test, and the texts of --compare, --compare-columns and --compare-matrix (None without matrix)."""
+    ref_names, names = list(ref_names), list(names)
+    if len(ref_names) != len(ref_rows) or len(names) != len(rows):
+        raise ValueError("pipeline.compare: one name per row")
+    ref_row, test_row = capi.compare_match(ref_names, names)
+    n = len(ref_row)
+    if matrix and n > 16384:
+        raise ValueError(capi.compare_refusal(capi.CMP_TOO_MANY_ROWS))
+    both = ref_ss is not None and ss is not None
+    own = ctx is None
+    if own:
+        ctx = capi.Context(0)
+    try:
+        res = ctx.alignment_compare([ref_rows[i] for i in ref_row], [rows[i] for i in test_row], use_ref=use_ref, use_test=use_test,
+                                    ss_ref=ref_ss if both else None, ss_test=ss if both else None,
+                                    pp=None if pp is None else capi.encode_pp([pp[i] for i in test_row]), matrix=matrix)
+    finally:
+        if own:
+            ctx.close()
+    res.row_names = [(ref_names[i].split() or [""])[0] for i in ref_row]
+    res.only_ref, res.only_test = len(ref_names) - n, len(names) - n
+    u64 = lambda a: np.ascontiguousarray(a, np.uint64)  # noqa: E731
+    ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+    names_c = capi.c_strings(res.row_names)
+    total, tc = u64([res.total_shared, res.total_refp, res.total_testp]), u64([res.tc_reproduced, res.tc_columns])
+    ss_arrs = [u64(a) for a in (res.tp, res.nref, res.ntest)] if both else [None] * 3
+    pp_count = u64(np.concatenate([res.pp_residues, res.pp_ref, res.pp_shared])) if pp is not None else None
+    table = capi.host_text(capi._compare_table, n, names_c, res.only_ref, res.only_test, len(res.k), len(res.m), res.residues.ctypes.data,
+                           res.shared.ctypes.data, res.refp.ctypes.data, res.testp.ctypes.data, total.ctypes.data, tc.ctypes.data,
+                           *[ptr(a) for a in ss_arrs], ptr(pp_count))
+    rep8 = np.ascontiguousarray(res.reproduced, np.uint8)
+    columns = capi.host_text(capi._compare_columns_table, len(res.k), res.k.ctypes.data, res.colref.ctypes.data, res.colshared.ctypes.data,
+                             rep8.ctypes.data)
+    pairs = None
+    if matrix:
+        pairs = capi.host_text(capi._compare_matrix_table, n, names_c, res.pair_shared.ctypes.data, res.pair_refp.ctypes.data,
+                               res.pair_testp.ctypes.data)
+    return res, table, columns, pairs
+
+
+def compare_result(ctx, reference, row_names, rows, ss, use_test=None, pp=None):
+    """compare() for a driver's compare=(ref_names, ref_rows[, ref_ss]) option: the result with the three texts as .table,
+    .columns_table and .matrix_table"""
+    if len(reference) not in (2, 3):
+        raise ValueError("compare: the reference is (ref_names, ref_rows) or (ref_names, ref_rows, ref_ss)")
+    ref_ss = reference[2] if len(reference) == 3 else None
+    res, table, columns, pairs = compare(reference[0], reference[1], row_names, rows, ref_ss, ss, use_test=use_test, pp=pp, ctx=ctx,
+                                         matrix=len(rows) <= 16384)
+    res.table, res.columns_table, res.matrix_table = table, columns, pairs
+    return res
+
+
+def _final(ctx, res, names, seqs, first, sidx, mask, ss, rl, tree_line, rf=None, covariation=None, row_ss=None, identity=False, compare=None):
     """The output of a final alignment (sidx: global sequence index per row, mask) with its common structure ss
     (_final_structure), into res: .ss, .ss_str, .rows, .output and, with rl, .reliability and .stockholm.  names / seqs: the
     family's, its first sequence at global index `first`.  rl: the alignment's dict of Context.alignment_reliabilities for
@@ -412,7 +474,8 @@ def _final(ctx, res, names, seqs, first, sidx, mask, ss, rl, tree_line, rf=None,
     Context.alignment_covariation on the printed rows and structure with the options' shuffles, seed
     and e_max beside the arrays; the Stockholm block then carries a `#=GC cov_SS_cons` line.  row_ss: per printed row its own structure (_row_structures) -> .row_ss, .row_ss_str
     and the `#=GR <name> SS` lines of the Stockholm block.  identity: .identity, alignment_identity of the printed rows in
-    printed order over all columns, and .row_names, their Stockholm names; the Stockholm block then carries the `#=GS <name> WT` lines."""
+    printed order over all columns, and .row_names, their Stockholm names; the Stockholm block then carries the `#=GS <name> WT` lines.
+    compare: a reference (run's compare) -> .compare, the printed rows and ss against it (compare_result), and .row_names."""
     res.ss = ss
     res.ss_str = capi.make_brackets(ss)
     order = np.argsort(sidx, kind="stable")  # std::sort(aln) :1876
@@ -435,10 +498,13 @@ def _final(ctx, res, names, seqs, first, sidx, mask, ss, rl, tree_line, rf=None,
         cv.update(covariation)
         res.covariation = cv
         cov_chars = stockholm.cov_ss_cons(ss, cv["pair_e"], cv["e_max"])
-    if identity:
-        res.identity = alignment_identity(ctx, res.rows)
+    if identity or compare is not None:
         sto_names = stockholm.names(names)
         res.row_names = [sto_names[int(sidx[r]) - first] for r in order]
+    if identity:
+        res.identity = alignment_identity(ctx, res.rows)
+    if compare is not None:
+        res.compare = compare_result(ctx, compare, res.row_names, res.rows, ss)
     if rl is not None:
         rl = dict(rl)
         cuts = np.cumsum([len(seqs[int(s) - first]) for s in sidx])[:-1]
@@ -488,7 +554,7 @@ def _printed_support(sup, sidx):
 def add(seed_names, seed_rows, names, seqs, ctx=None, w=4.0, eta0=0.5, t_max=600, w_pct_a=0.25, w_pct_s=0.25, th_a=0.01,
         th_s=0.2, th_s1=None, align_model=capi.ALIGN_PROBCONS, force_iters=0, slice_iters=None, skip_uncoupled_folds=True,
         round_us=None, w_pct_f=0.0, bp_update1=False, reliability=False, covariation=False, row_structures=False, seed_ss=None,
-        identity=False):
+        identity=False, compare=None):
     """Add new sequences to a fixed seed alignment without changing its columns (`dafs --seed`).
     seed_names / seed_rows: the seed's rows (letters and '.' / '-' gaps; stockholm.read_seed reads a file), checked and
     without their all-gap columns (stockholm.clean_seed).  names / seqs: the new sequences.  The options are run()'s.
@@ -500,7 +566,7 @@ def add(seed_names, seed_rows, names, seqs, ctx=None, w=4.0, eta0=0.5, t_max=600
     .z (per new sequence its column map into the seed), .rf (per merged column True for a seed column), .dd_log
     ({j: (iterations, violated, ncbp, score)}), .dd_memory, .seconds; with reliability, .reliability and .stockholm (no CC
     line, a `#=GC RF` line); with covariation (as in run), .covariation; with row_structures (as in run), .row_ss and
-    .row_ss_str; with identity (as in run), .identity.
+    .row_ss_str; with identity (as in run), .identity; with compare (as in run), .compare.
 
     seed_ss (`dafs --seed-structure`): the seed's consensus structure over its cleaned columns
     (stockholm.read_seed_structure), fixed like the columns.  The seed rows are folded under the constraints it puts on them
@@ -562,7 +628,7 @@ def add(seed_names, seed_rows, names, seqs, ctx=None, w=4.0, eta0=0.5, t_max=600
             ss_m = _final_structure(ctx, sidx, rows_mask, th1, bp_update1, ctx.consensus_structure(sidx, rows_mask, th1)[1])
         rl = ctx.alignment_reliability(sidx, rows_mask, ss_m) if reliability else None
         _final(ctx, res, all_names, all_seqs, 0, sidx, rows_mask, ss_m, rl, None, rf, covariation,
-               _row_structures(ctx, [sidx], dict(enumerate(map(len, all_seqs))), th1)[0] if row_structures else None, identity)
+               _row_structures(ctx, [sidx], dict(enumerate(map(len, all_seqs))), th1)[0] if row_structures else None, identity, compare)
         t.append(time.perf_counter())
         res.seconds = dict(phase1=t[3] - t[0], nodes=t[4] - t[3], final=t[5] - t[4], total=t[5] - t[0])
     finally:
@@ -750,6 +816,8 @@ def pairwise(names, seqs, pairs=None, ctx=None, max_bytes=None, **opts):
         raise ValueError("pipeline.pairwise: two rows carry no covariation; covariation is an option of run, run_batch and add")
     if opts.get("identity"):
         raise ValueError(capi.alistat_refusal(capi.NO_PAIRWISE))
+    if opts.get("compare") is not None:
+        raise ValueError(capi.compare_refusal(capi.CMP_NO_PAIRWISE))
     if opts.get("level_sync") and opts.get("bp_update"):
         raise ValueError("pipeline.pairwise: bp_update needs the resident-node schedule (level_sync=False)")
     o = {k: p.default for k, p in inspect.signature(run).parameters.items() if k not in ("names", "seqs", "ctx", "bp", "mp", "shard")}
@@ -906,7 +974,7 @@ def _select_nr(ctx, mg, m, score, matched, t):
     mg.nr_stockholm = capi.host_text(capi._stockholm_nr, mg.stockholm.encode("latin-1"), total, capi.c_strings(mg.names), kept8.ctypes.data, m, t)
 
 
-def add_each(seed_names, seed_rows, names, seqs, ctx=None, max_bytes=None, merged=False, nearest=False, nr=None, **opts):
+def add_each(seed_names, seed_rows, names, seqs, ctx=None, max_bytes=None, merged=False, nearest=False, nr=None, compare=None, **opts):
     """Each new sequence added to a fixed seed alignment on its own (`dafs --seed SEED --seed-each`).
     opts: the options of add().  results[j] is, bit for bit, what add(seed_names, seed_rows, [names[j]], [seqs[j]], **opts)
     returns (.output, .rows, .ss, .ss_str, .z, .rf, .dd_log and, when asked, .reliability / .stockholm / .row_ss* /
@@ -946,8 +1014,13 @@ def add_each(seed_names, seed_rows, names, seqs, ctx=None, max_bytes=None, merge
     subset: the seed rows are forced and visited first, in seed order, then the new rows by descending .score, ties in input
     order.  .merged gains .kept, .by (capi.nr_select), .nr_rows, .nr_names and .nr_stockholm: the merged block without the
     dropped rows and with a `#=GF CC nr T kept K of M hits` line, nothing else changed (dafs_host_stockholm_nr).  A new row
-    without a residue in a seed column is compared with nothing and kept."""
+    without a residue in a seed column is compared with nothing and kept.
+
+    compare (run's; it needs merged): .merged.compare, the merged alignment against the reference with use_test = .merged.rf
+    -- insert columns are left-justified, not aligned -- and the PP classes of the merged block's own reliabilities."""
     import time
+    if compare is not None and not merged:
+        raise ValueError(capi.compare_refusal(capi.CMP_NEEDS_MERGED))
     if nr is not None and not merged:
         raise ValueError(capi.alistat_refusal(capi.NR_NEEDS_MERGED))
     if nr is not None and not (0.0 < float(nr) <= 1.0):
@@ -1101,6 +1174,14 @@ def add_each(seed_names, seed_rows, names, seqs, ctx=None, max_bytes=None, merge
             out.merged = _merge_each(seed_names, seed_rows, seed_ss, names, seqs, [r.z[0] for r in out.results], pps)
             if nr is not None:
                 _select_nr(ctx, out.merged, m, out.score, out.matched, float(nr))
+            if compare is not None:
+                mg = out.merged
+                pp_rows = [None] * m
+                for row, rel in zip(mg.rows[m:], pps):
+                    chars = iter(() if rel is None else [stockholm.pp_char(p) for p in rel])
+                    pp_rows.append(None if rel is None else "".join("." if ch == "-" else next(chars) for ch in row))
+                mg.compare = compare_result(ctx, compare, mg.names, mg.rows, None if seed_ss is None else mg.ss, use_test=mg.rf,
+                                            pp=None if all(r is None for r in pp_rows) else pp_rows)
             secs["merge"] = time.perf_counter() - t_merge
     finally:
         src.close()

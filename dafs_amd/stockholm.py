@@ -186,3 +186,14 @@ def read_seed_structure(path):
     if structure is None:
         return clean_seed(names, rows) + (None,)
     return clean_seed_structure(names, rows, structure)
+
+
+def read_seed_pp(path):
+    """The `#=GR <name> PP` lines of a Stockholm file's first alignment (dafs_host_seed_pp), read beside read_seed: per row of the
+    file the PP characters over the columns read_seed keeps (a row without a PP line is all '.'), or None when the file holds no
+    PP line"""
+    with open(path, "rb") as fh:
+        data = fh.read()
+    n, has = C.c_uint32(), C.c_int()
+    got = capi.host_text(capi._seed_pp, data, len(data), C.byref(n), C.byref(has), refusal=SeedError)
+    return capi.split_lines(got, n.value) if has.value else None

@@ -656,6 +656,91 @@ int dafs_host_seed_table_nearest(uint32_t n, const char* const* headers, const u
                                  const uint32_t* half, const double* expected, const char* const* nearest_name,
                                  const double* identity, char** table);
 
+/* Alignment comparison: how far two alignments of the same n >= 2 sequences agree (no counterpart in the reference;
+ * definitions, to the integer, in DESIGN.md section 19 "Comparing two alignments").  R is the reference (len_r columns), T the
+ * test (len_t columns).  The call reads the two alignments alone, none of the context's stores, and works on a context on which
+ * no sequences were set.  Inputs (host):
+ *   cell_r[n * len_r], cell_t[n * len_t]  cells in the codes of dafs_host_ali_code; row r of both holds the same residue codes
+ *                                         in the same order
+ *   use_r[len_r], use_t[len_t]            the columns that are aligned, or NULL: all of them
+ *   ss_r[len_r], ss_t[len_t]              structures as dafs_host_seed_clean_structure gives them (the partner at the left
+ *                                         column of a pair, DAFS_HIP_NONE elsewhere; the symmetric form, with the left column
+ *                                         at the right one, is taken too), or NULL: no structure part (it needs both)
+ *   pp[n * len_t]                         per cell of T the PP class 0..10 ('0'..'9', '*'), 255 for none, or NULL: no PP part
+ * For residue k of row r, a = its column in R if use_r has it, else none; b = the same in T.  k_c = residues with a = c, m_d =
+ * residues with b = d, cnt(c, d) = residues with a = c and b = d.  refn = k_a - 1, testn = m_b - 1, shr = cnt(a, b) - 1, each 0
+ * where a key it needs is none.  Outputs (host; any may be NULL, and only the kernels that a non-NULL output needs are run): */
+typedef struct {
+  uint32_t* residues;                    /* [n] residues of the row */
+  uint64_t *shared, *refp, *testp;       /* [n] the sums of shr, refn, testn over the row's residues */
+  double *sps, *ppv;                     /* [n] (double)shared / (double)refp and / (double)testp; NaN for a denominator of 0 */
+  uint64_t* total;                       /* [3] half the sums over the rows of shared, refp, testp */
+  double* score;                         /* [3] SPS and PPV of the totals, TC = tc[0] / tc[1]; NaN for a denominator of 0 */
+  uint32_t *k, *m;                       /* [len_r] k_c, [len_t] m_d */
+  uint64_t *colref, *colshared;          /* [len_r] k_c (k_c - 1) / 2; the sum over d of cnt(c, d) (cnt(c, d) - 1) / 2 */
+  uint8_t* reproduced;                   /* [len_r] 1 iff k_c >= 2 and some d has cnt(c, d) = k_c = m_d */
+  uint64_t* tc;                          /* [2] reproduced columns, columns with k_c >= 2 */
+  uint32_t *pair_shared, *pair_refp, *pair_testp; /* [n * n], n <= 16384: for r != s the residue pairs of the two rows with
+                                            equal a and equal b, with equal a, with equal b (none is never equal); symmetric,
+                                            the diagonal 0; row r sums to shared[r], refp[r], testp[r] */
+  uint64_t* pp_count;                    /* [3 * 11], needs pp: per class q the residues [q], the sum of refn [11 + q] and of
+                                            shr [22 + q] */
+  uint64_t *tp, *nref, *ntest;           /* [n], need ss_r and ss_t (the masks play no part): the pairs of residues of the row
+                                            whose R columns are partners in ss_r (nref), whose T columns are in ss_t (ntest),
+                                            and those in both (tp) */
+  uint64_t* ss_total;                    /* [3] the sums over the rows of tp, nref, ntest */
+} dafs_compare_out;
+/* DAFS_HIP_EINVAL before any launch (outputs untouched, context usable): n < 2 or above 2^20; a length of 0 or above 2^20;
+ * len_r * len_t above 2^30; a pair matrix with n above 16384; a code above 5; a PP class that is neither 0..10 nor 255; a
+ * structure with a partner beyond its length, a column in two pairs or a one-sided right column; a structure output with one
+ * of ss_r and ss_t missing or pp_count without pp; and a row whose residue codes differ between R and T, which
+ * dafs_hip_last_error() then names.  DAFS_CMP_CHUNK_COLS and DAFS_CMP_BAND_BLOCKS shrink the pair
+ * pass's LDS stage and its launches for tests and change no result. */
+int dafs_hip_alignment_compare(dafs_hip_ctx* ctx, uint32_t n, uint32_t len_r, uint32_t len_t, const uint8_t* cell_r,
+                               const uint8_t* cell_t, const uint8_t* use_r, const uint8_t* use_t, const uint32_t* ss_r,
+                               const uint32_t* ss_t, const uint8_t* pp, const dafs_compare_out* out);
+
+/* Host text of the comparison.  What both drivers say when they refuse a combination of its options: */
+enum {
+  DAFS_COMPARE_NEEDS_REF = 0,   /* one of --compare and --compare-ref without the other */
+  DAFS_COMPARE_NEEDS_COMPARE,   /* --compare-columns or --compare-matrix without --compare */
+  DAFS_COMPARE_NO_PAIRWISE,     /* a comparison asked of pairwise alignments */
+  DAFS_COMPARE_NEEDS_MERGED,    /* a comparison of --seed-each placements without the merged alignment */
+  DAFS_COMPARE_TOO_MANY_ROWS    /* the pair table with more than 16384 rows */
+};
+const char* dafs_host_compare_refusal(int which);
+/* The rows to compare: the names (the first word of each string, as a Stockholm file names a row) present in both alignments,
+ * in the reference's order.  ref_row[k] and test_row[k] (room for
+ * min(n_ref, n_test) entries each) are the rows of the k-th common name, *count their number.  Refused (DAFS_HIP_EINVAL, message
+ * in dafs_hip_last_error): a name on two rows of either alignment, fewer than two common names. */
+int dafs_host_compare_match(uint32_t n_ref, const char* const* ref_names, uint32_t n_test, const char* const* test_names,
+                            uint32_t* count, uint32_t* ref_row, uint32_t* test_row);
+/* The "#=GR <name> PP" lines of the first alignment of a Stockholm file, read beside dafs_host_seed_parse / _clean: per row of
+ * the file, in its order, the PP characters over the columns that dafs_host_seed_clean keeps, joined by '\n'; a row without a
+ * PP line is all '.'.  *has_pp = 0 when the file holds no PP line (aligned FASTA never does).  Refused: what the seed reader
+ * refuses, a PP line that names no row or has another length than the rows. */
+int dafs_host_seed_pp(const char* text, size_t bytes, uint32_t* n, int* has_pp, char** pp);
+/* The --compare table of n compared rows (only_ref / only_test: rows of one alignment alone, which were left out).  Lines:
+ *   "# rows n only_ref x only_test y columns_ref len_r columns_test len_t"
+ *   "# pairs shared S ref P test Q sps A ppv B"
+ *   "# columns reproduced K of M tc C"
+ *   with tp: "# structure tp .. ref .. test .. sensitivity .. ppv .. f .." (the sums of tp, nref, ntest)
+ *   with pp_count: per class with residues "# pp <class character> residues ref shared accuracy"
+ *   per row, tab-separated: "r+1 name residues shared ref test sps ppv", then "tp nref ntest" with tp
+ * Floats as %.9g, "nan" for a NaN.  The arrays are those of dafs_compare_out; tp / nref / ntest and pp_count may be NULL. */
+int dafs_host_compare_table(uint32_t n, const char* const* names, uint32_t only_ref, uint32_t only_test, uint32_t len_r,
+                            uint32_t len_t, const uint32_t* residues, const uint64_t* shared, const uint64_t* refp,
+                            const uint64_t* testp, const uint64_t* total, const uint64_t* tc, const uint64_t* tp,
+                            const uint64_t* nref, const uint64_t* ntest, const uint64_t* pp_count, char** table);
+/* The --compare-columns table: per column of the reference "c+1 residues colref colshared reproduced" (residues = k_c,
+ * reproduced 1 or 0), tab-separated */
+int dafs_host_compare_columns_table(uint32_t len_r, const uint32_t* k, const uint64_t* colref, const uint64_t* colshared,
+                                    const uint8_t* reproduced, char** table);
+/* The --compare-matrix table, one line per pair r < s as dafs_host_identity_matrix_table lays its pairs out: "r+1 s+1 names[r]
+ * names[s] shared ref test sps ppv" */
+int dafs_host_compare_matrix_table(uint32_t n, const char* const* names, const uint32_t* pair_shared, const uint32_t* pair_refp,
+                                   const uint32_t* pair_testp, char** table);
+
 /* ---- device-resident exchange of the sparse stores (multi-GPU runs) ---------------------------------------------------
  * One process per GPU shards phase 1 of DAFS::run (src/dafs.cpp:1787-1827): the folds (src/fold.cpp:66-67), the pair jobs
  * (src/align.cpp:46-50) and the output pairs of relax_matching_probability (src/dafs.cpp:265-315) are independent.  The
