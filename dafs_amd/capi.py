@@ -85,6 +85,8 @@ _mp_result_size = _sig("dafs_hip_mp_result_size", C.c_int,
                       [C.c_void_p, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)])
 _mp_fetch = _sig("dafs_hip_mp_fetch", C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 6)
 _get_sim = _sig("dafs_hip_get_sim", C.c_int, [C.c_void_p, C.c_void_p])
+_similarity = _sig("dafs_hip_similarity", C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_uint64, C.POINTER(C.c_uint64)])
+_similarity_ranges = _sig("dafs_host_similarity_ranges", C.c_int, [C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)])
 _set_bp = _sig("dafs_hip_set_bp", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])
 _bp_result_size = _sig("dafs_hip_bp_result_size", C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)])
 _bp_fetch = _sig("dafs_hip_bp_fetch", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p])
@@ -155,6 +157,9 @@ _dd_default_params = _sig("dafs_hip_dd_default_params", None, [C.POINTER(DDParam
 _solve_nodes = _sig("dafs_hip_solve_nodes", C.c_int,
                     [C.c_void_p, C.c_uint32, C.POINTER(NodeInput), C.POINTER(DDParams), C.POINTER(NodeOutput)])
 _build_tree = _sig("dafs_host_build_tree", C.c_int, [C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])
+_cluster_cut = _sig("dafs_host_cluster_cut", C.c_int, [C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_uint32, C.c_void_p, u32p])
+CLUSTER_THRESHOLD, CLUSTER_COUNT = 0, 1  # the modes of dafs_host_cluster_cut
+_cluster_table = _sig("dafs_host_cluster_table", C.c_int, [C.c_uint32, C.POINTER(C.c_char_p)] + [C.c_void_p] * 6 + [C.POINTER(C.c_void_p)])
 _merge_added = _sig("dafs_host_merge_added", C.c_int, [C.c_uint32, C.c_uint32] + [C.c_void_p] * 5)
 # host text (dafs_amd/csrc/host_text.cpp): returned text is a char* the caller frees with dafs_host_free
 _strs = C.POINTER(C.c_char_p)
@@ -534,6 +539,15 @@ class Context:
             out.append(flat[o:o + n * n].reshape(n, n).copy())
             o += n * n
         return out
+
+    def similarity(self, model=ALIGN_PROBCONS, th=0.01, max_bytes=None):
+        """dafs_hip_similarity: the N x N similarity matrix of a one-family context of any size, the pairs computed in ranges
+        under max_bytes of estimated device memory (None: the library's budget; similarity_ranges gives the ranges).  Returns
+        (sim, n_ranges); sim is what sim() returns after a full-pair-set align_posteriors, bit for bit.  The matching stores
+        are invalid afterwards, whatever the number of ranges."""
+        n_ranges = C.c_uint64()
+        check(_similarity(self._h, model, th, 0 if max_bytes is None else int(max_bytes), C.byref(n_ranges)))
+        return self.sim(), n_ranges.value
 
     def set_bp(self, rows):
         """rows: per sequence (rowptr[len+1], col, val)"""
@@ -1087,6 +1101,67 @@ def build_tree(sim):
     score = np.zeros(2 * n - 1, np.float32); left = np.zeros(2 * n - 1, np.int32); right = np.zeros(2 * n - 1, np.int32)
     check(_build_tree(n, sim.ctypes.data, score.ctypes.data, left.ctypes.data, right.ctypes.data))
     return score, left.astype(np.int64), right.astype(np.int64)
+
+
+def similarity_ranges(lens, max_bytes=None):
+    """dafs_host_similarity_ranges (host code in the library): the ranges [begin, end) of the row-major pair enumeration that
+    Context.similarity walks for sequences of these lengths under max_bytes (None: the library's budget), as a list"""
+    lens = np.ascontiguousarray([int(x) for x in lens], np.uint32)
+    budget = 0 if max_bytes is None else int(max_bytes)
+    if budget < 0 or (max_bytes is not None and budget == 0):
+        raise ValueError("similarity_ranges: max_bytes must be positive (None: the library's budget)")
+    count = C.c_uint64()
+    check(_similarity_ranges(len(lens), lens.ctypes.data, budget, None, 0, C.byref(count)))
+    end = np.zeros(max(count.value, 1), np.uint64)
+    check(_similarity_ranges(len(lens), lens.ctypes.data, budget, end.ctypes.data, count.value, C.byref(count)))
+    ends = [int(e) for e in end[:count.value]]
+    return list(zip([0] + ends[:-1], ends))
+
+
+def _tree_arrays(tree, who):
+    """(score, left, right) of build_tree as the library's arrays; n from their length"""
+    score, left, right = tree
+    score = np.ascontiguousarray(score, np.float32).reshape(-1)
+    left = np.ascontiguousarray(left, np.int32).reshape(-1)
+    right = np.ascontiguousarray(right, np.int32).reshape(-1)
+    if len(score) % 2 != 1 or len(left) != len(score) or len(right) != len(score):
+        raise ValueError("%s: a tree of n leaves is three arrays of 2 n - 1 entries" % who)
+    return score, left, right, (len(score) + 1) // 2
+
+
+def cluster_cut(tree, threshold=None, count=None):
+    """dafs_host_cluster_cut (host code in the library): the cut of the guide tree `tree` = (score, left,
+    right) of build_tree into clusters.  threshold: a join is kept when its score is >= threshold and every join below it is
+    kept; count: exactly that many clusters, the joins made last undone.  Exactly one of the two.  Returns (labels as uint32
+    [n], the number of clusters); the clusters are numbered by their smallest member.  ValueError for what the library
+    refuses."""
+    if (threshold is None) == (count is None):
+        raise ValueError("cluster_cut: exactly one of threshold and count")
+    score, left, right, n = _tree_arrays(tree, "cluster_cut")
+    if count is not None and not 0 <= int(count) <= 0xFFFFFFFF:
+        raise ValueError("cluster cut: the number of clusters must be 1 .. the number of sequences")
+    labels = np.zeros(n, np.uint32)
+    k = C.c_uint32()
+    rc = _cluster_cut(n, score.ctypes.data, left.ctypes.data, right.ctypes.data, CLUSTER_THRESHOLD if count is None else CLUSTER_COUNT,
+                      0.0 if threshold is None else float(threshold), 0 if count is None else int(count), labels.ctypes.data, C.byref(k))
+    if rc == -1:
+        raise ValueError(_last_error().decode("latin-1"))
+    check(rc)
+    return labels, k.value
+
+
+def cluster_table(headers, lengths, labels, tree, sim):
+    """dafs_host_cluster_table: the text of `dafs --cluster-table` -- per sequence "i name length cluster size join nearest_in
+    sim_in nearest_out sim_out" (1-based indices, floats as %.9g, "0" and "nan" where there is none)"""
+    headers = list(headers)
+    score, left, right, n = _tree_arrays(tree, "cluster_table")
+    lengths = np.ascontiguousarray(lengths, np.uint32).reshape(-1)
+    labels = np.ascontiguousarray(labels, np.uint32).reshape(-1)
+    sim = np.ascontiguousarray(sim, np.float32)
+    if len(headers) != n or len(lengths) != n or len(labels) != n or sim.shape != (n, n):
+        raise ValueError("cluster_table: one header, length and label per leaf of the tree and an n x n similarity matrix")
+    return host_text(_cluster_table, n, c_strings(headers), lengths.ctypes.data, labels.ctypes.data, score.ctypes.data, left.ctypes.data,
+                     right.ctypes.data, sim.ctypes.data)
 
 
 def merge_added(ncols, zs):

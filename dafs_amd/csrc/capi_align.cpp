@@ -151,6 +151,42 @@ extern "C" int dafs_hip_align_posteriors(dafs_hip_ctx* c, int model, float th, u
   return DAFS_HIP_EOVERFLOW;
 }
 
+// The similarity block of one family of any size: the pairs in the ranges of
+// dafs_host_similarity_ranges, each one dafs_hip_align_posteriors launch into the same buffers, its task_sim scattered as
+// store_sim_blocks scatters the whole set's.  The stores are left invalid whatever the number of ranges.
+extern "C" int dafs_hip_similarity(dafs_hip_ctx* c, int model, float th, uint64_t max_bytes, uint64_t* n_ranges_out) {
+  if (!c || c->len.size() < 2 || c->fam.nfam() != 1 || !(th >= 0.0f)) return DAFS_HIP_EINVAL;
+  if (model != DAFS_ALIGN_PROBCONS && model != DAFS_ALIGN_CONTRALIGN) return DAFS_HIP_EINVAL;
+  const uint32_t n = (uint32_t)c->len.size();
+  uint64_t nr = 0;
+  int rc;
+  if ((rc = dafs_host_similarity_ranges(n, c->len.data(), max_bytes, nullptr, 0, &nr))) return rc;
+  std::vector<uint64_t> end(nr);
+  if ((rc = dafs_host_similarity_ranges(n, c->len.data(), max_bytes, end.data(), nr, &nr))) return rc;
+  std::vector<float> sim((size_t)n * n, 0.0f), ts;
+  for (uint32_t i = 0; i < n; ++i) sim[(size_t)i * n + i] = 1.0f;
+  mp_store& st = c->mp[0];
+  rc = DAFS_HIP_OK;
+  for (uint64_t r = 0, begin = 0; r < nr && !rc; begin = end[r++]) {
+    if ((rc = dafs_hip_align_posteriors(c, model, th, begin, end[r]))) break;
+    ts.resize(st.n_tasks);
+    if ((rc = c->task_sim.download(ts.data(), st.n_tasks))) break;
+    for (uint64_t p = 0; p < st.n_tasks; ++p) {
+      const float s = ts[st.task_of_pair[p]];
+      sim[(size_t)st.pair_x[p] * n + st.pair_y[p]] = s;
+      sim[(size_t)st.pair_y[p] * n + st.pair_x[p]] = s;
+    }
+  }
+  st.valid = false;  // the last range's rows, or after a failure nothing: no store of the whole set either way
+  c->mp[1].valid = false;
+  c->sim.clear();
+  if (rc) return rc;
+  c->sim.swap(sim);
+  if ((rc = c->d_sim.upload(c->sim.data(), c->sim.size(), c->stream))) { c->sim.clear(); return rc; }
+  if (n_ranges_out) *n_ranges_out = nr;
+  return DAFS_HIP_OK;
+}
+
 // AUXAlign::calculate (src/align.cpp:204-246, --align-aux) and the hand-over point after an all-gather of
 // shards: the caller supplies the rows of mp[x][y] for every pair x < y (row-major pair order); the
 // transposes (transpose_mp, dafs.cpp:155-167) are laid out here and the similarity scores

@@ -24,6 +24,7 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -96,6 +97,14 @@ struct Options {
   std::string compare_ref;      // --compare-ref REF
   std::string compare_columns;  // --compare-columns OUT
   std::string compare_matrix;   // --compare-matrix OUT
+  bool cluster_given = false;         // --cluster T: the one FILE cut into clusters at threshold T, each aligned
+  double cluster = 0.0;
+  bool cluster_count_given = false;   // --cluster-count K: the same cut into exactly K clusters
+  uint32_t cluster_count = 0;
+  bool cluster_min_size_given = false;
+  uint32_t cluster_min_size = 1;      // --cluster-min-size M
+  std::string cluster_table;          // --cluster-table OUT
+  std::string cluster_tree;           // --cluster-tree OUT
   std::string input;
   std::vector<std::string> inputs;  // every FILE argument; with two or more, one output block per file
 };
@@ -186,6 +195,23 @@ const char* kHelp =
     "      --compare-ref REF The reference alignment of --compare\n"
     "      --compare-columns OUT  With --compare: per column of REF: c residues pairs shared_pairs reproduced\n"
     "      --compare-matrix OUT   With --compare: per row pair: r s name_r name_s shared ref test sps ppv (at most 16384 rows)\n"
+    "      --cluster T       The one FILE holds sequences of mixed origin: cluster them and align every cluster.  The similarity\n"
+    "                        scores of all pairs (the alignment model's, with -a and -u) give the guide tree of the whole set; a\n"
+    "                        join is kept when its score is >= T and every join below it is kept, and a cluster is the leaves of a\n"
+    "                        maximal kept join, or a single sequence.  Clusters are numbered by their first member and keep the\n"
+    "                        file's order.  Per cluster a line \"==> cluster c <==\" (1-based) and then what dafs prints for a file\n"
+    "                        of that cluster's sequences; --stockholm, --covariation and --identity write one block or table per\n"
+    "                        printed cluster.  With -f the clustering still reads the raw scores; -f acts inside each cluster's\n"
+    "                        run.  Not with --seed*, --pairwise*, --describe, --devices, --compare*, --align-aux, --fold-aux or\n"
+    "                        --save-*-aux\n"
+    "      --cluster-count K Instead of --cluster T: exactly K clusters (1 <= K <= sequences in FILE), the joins made last undone\n"
+    "      --cluster-min-size M  With --cluster or --cluster-count: clusters of fewer than M sequences are listed in the table\n"
+    "                        but not aligned or printed (default: 1)\n"
+    "      --cluster-table OUT  With --cluster or --cluster-count: a tab-separated table, one line per sequence:\n"
+    "                        i name length cluster size join nearest_in sim_in nearest_out sim_out (join: the score of the\n"
+    "                        cluster's top join; the most similar sequence inside and outside the cluster; 0 and nan for none)\n"
+    "      --cluster-tree OUT   With --cluster or --cluster-count: the guide tree of the whole set, as dafs prints a tree line;\n"
+    "                        its join scores are the values T chooses between\n"
     "\n Aligning options:\n"
     "  -a, --align-model arg Alignment model (value=CONTRAlign, ProbCons) (default: ProbCons)\n"
     "  -p, --align-pct arg   Weight of PCT for matching probabilities (default: 0.25)\n"
@@ -229,7 +255,9 @@ Options parse(int argc, char** argv) {
       {"seed-each", {0, false}}, {"seed-scores", {0, true}}, {"seed-merged", {0, true}}, {"seed-structure", {0, false}},
       {"covariation", {0, true}}, {"cov-shuffles", {0, true}}, {"cov-seed", {0, true}}, {"identity", {0, true}},
       {"identity-matrix", {0, true}}, {"seed-nearest", {0, false}}, {"seed-nr", {0, true}}, {"describe", {0, true}},
-      {"compare", {0, true}}, {"compare-ref", {0, true}}, {"compare-columns", {0, true}}, {"compare-matrix", {0, true}}};
+      {"compare", {0, true}}, {"compare-ref", {0, true}}, {"compare-columns", {0, true}}, {"compare-matrix", {0, true}},
+      {"cluster", {0, true}}, {"cluster-count", {0, true}}, {"cluster-min-size", {0, true}}, {"cluster-table", {0, true}},
+      {"cluster-tree", {0, true}}};
   std::map<char, std::string> shorts;
   for (const auto& kv : spec)
     if (kv.second.first) shorts[kv.second.first] = kv.first;
@@ -327,6 +355,33 @@ Options parse(int argc, char** argv) {
       if (value.empty()) throw "--" + name + " needs a file name";
       (name == "compare" ? o.compare : name == "compare-ref" ? o.compare_ref : name == "compare-columns" ? o.compare_columns : o.compare_matrix) = value;
     }
+    else if (name == "cluster") {
+      size_t used = 0;
+      try {
+        o.cluster = std::stod(value, &used);
+      } catch (const std::exception&) {
+        used = 0;
+      }
+      if (used == 0 || used != value.size() || !std::isfinite(o.cluster)) throw std::string("--cluster needs a finite threshold");
+      o.cluster_given = true;
+    }
+    else if (name == "cluster-count" || name == "cluster-min-size") {
+      size_t used = 0;
+      unsigned long long v = 0;
+      try {
+        if (value.empty() || value[0] < '0' || value[0] > '9') throw std::invalid_argument(value);
+        v = std::stoull(value, &used, 10);
+      } catch (const std::exception&) {
+        used = 0;
+      }
+      if (used == 0 || used != value.size() || v < 1 || v > 0xFFFFFFFFull) throw "--" + name + " needs a positive integer";
+      if (name == "cluster-count") { o.cluster_count = (uint32_t)v; o.cluster_count_given = true; }
+      else { o.cluster_min_size = (uint32_t)v; o.cluster_min_size_given = true; }
+    }
+    else if (name == "cluster-table" || name == "cluster-tree") {
+      if (value.empty()) throw "--" + name + " needs a file name";
+      (name == "cluster-table" ? o.cluster_table : o.cluster_tree) = value;
+    }
     else if (name == "seed-nearest") o.seed_nearest = true;
     else if (name == "seed-nr") {
       size_t used = 0;
@@ -352,6 +407,19 @@ Options parse(int argc, char** argv) {
       if (name == "cov-shuffles") { o.cov_shuffles = (uint32_t)v; o.cov_shuffles_given = true; }
       else { o.cov_seed = v; o.cov_seed_given = true; }
     }
+  }
+  if (o.cluster_given && o.cluster_count_given) throw std::string("--cluster and --cluster-count cut the same tree: give one of them");
+  if (!o.cluster_given && !o.cluster_count_given) {
+    if (o.cluster_min_size_given || !o.cluster_table.empty() || !o.cluster_tree.empty())
+      throw std::string("--cluster-min-size, --cluster-table and --cluster-tree need --cluster or --cluster-count");
+  } else {  // the clusters are runs of their own: nothing that reads or writes one run's whole state, and one FILE to cut
+    for (const std::string& g : given) {
+      const bool other_mode = g.compare(0, 4, "seed") == 0 || g.compare(0, 8, "pairwise") == 0 || g.compare(0, 7, "compare") == 0 ||
+                              g == "describe" || g == "devices";
+      const bool aux = g == "align-aux" || g == "fold-aux" || g == "save-align-aux" || g == "save-fold-aux";
+      if (other_mode || aux) throw "--cluster: --" + g + " cannot be combined with --cluster and --cluster-count";
+    }
+    if (o.inputs.size() != 1) throw std::string("--cluster needs exactly one input FILE");
   }
   if (o.row_structures && o.stockholm.empty()) throw std::string("--row-structures needs --stockholm");
   if ((o.cov_shuffles_given || o.cov_seed_given) && o.covariation.empty()) throw std::string("--cov-shuffles and --cov-seed need --covariation");
@@ -1987,6 +2055,105 @@ int run_pairwise(const Options& o, int align_model) {
   return 0;
 }
 
+// `dafs --cluster T FILE` (pipeline.cluster is the Python twin).  The similarity scores of all pairs come
+// from dafs_hip_similarity, which walks the pairs in ranges under the library's budget and keeps no store; the guide tree of
+// the whole set is cut by dafs_host_cluster_cut; the clusters of at least --cluster-min-size members are the families of
+// align_group, as the FILEs of a run of several are: those of two or more sequences in sub-batches under
+// dafs_host_batch_bytes() of dafs_host_family_bytes, a cluster of one sequence on the single-sequence path.  Each printed
+// cluster is "==> cluster c <==" and then what `dafs` prints for a file of its sequences.
+int run_cluster(const Options& o, int align_model) {
+  std::vector<Fasta> fa;
+  Fasta::load(fa, o.input.c_str());
+  if (fa.empty()) throw "no sequences in the input";
+  const uint32_t N = (uint32_t)fa.size();
+  if (o.cluster_count_given && o.cluster_count > N)
+    throw "--cluster-count: " + std::to_string(o.cluster_count) + " clusters asked of " + std::to_string(N) + " sequences";
+  dafs_hip_ctx* ctx = nullptr;
+  check(dafs_hip_create(o.device, &ctx));
+  Guard guard{ctx};
+  std::vector<float> sim((size_t)N * N, 1.0f);
+  if (N > 1) {
+    set_sequences(ctx, fa);
+    check(dafs_hip_similarity(ctx, align_model, o.align_th, 0, nullptr));
+    check(dafs_hip_get_sim(ctx, sim.data()));
+  }
+  std::vector<float> score(2 * N - 1);
+  std::vector<int32_t> left(2 * N - 1), right(2 * N - 1);
+  check(dafs_host_build_tree(N, sim.data(), score.data(), left.data(), right.data()));
+  std::vector<uint32_t> labels(N);
+  uint32_t K = 0;
+  check_text(dafs_host_cluster_cut(N, score.data(), left.data(), right.data(), o.cluster_given ? DAFS_CLUSTER_THRESHOLD : DAFS_CLUSTER_COUNT,
+                                   (float)o.cluster, o.cluster_count, labels.data(), &K));
+  if (!o.cluster_table.empty()) {
+    std::vector<std::string> headers;
+    std::vector<uint32_t> lens;
+    for (const Fasta& s : fa) { headers.push_back(s.name()); lens.push_back(s.size()); }
+    char* text = nullptr;
+    check_text(dafs_host_cluster_table(N, c_strs(headers).data(), lens.data(), labels.data(), score.data(), left.data(), right.data(), sim.data(), &text));
+    write_tables("--cluster-table", o.cluster_table, {take(text)}, nullptr);
+  }
+  if (!o.cluster_tree.empty()) {
+    std::vector<node_t> tree(2 * N - 1);
+    for (uint i = 0; i < 2 * N - 1; ++i) tree[i] = std::make_pair(score[i], std::make_pair((uint)left[i], (uint)right[i]));
+    std::ostringstream tl;
+    print_tree(tl, tree, fa, (int)tree.size() - 1);
+    tl << std::endl;
+    write_tables("--cluster-tree", o.cluster_tree, {tl.str()}, nullptr);
+  }
+  // the clusters that are aligned, as the families of a run of several files
+  std::vector<std::vector<Fasta> > all(K);
+  for (uint32_t i = 0; i < N; ++i) all[labels[i]].push_back(fa[i]);
+  std::vector<std::vector<Fasta> > fams;
+  std::vector<std::string> headers;
+  for (uint32_t c = 0; c < K; ++c)
+    if (all[c].size() >= o.cluster_min_size) {
+      fams.push_back(all[c]);
+      headers.push_back("cluster " + std::to_string(c + 1));
+    }
+  const size_t P = fams.size();
+  std::vector<std::ostringstream> outs(P);
+  std::vector<std::string> sto_blocks(o.stockholm.empty() ? 0 : P), cov_tables(o.covariation.empty() ? 0 : P);
+  std::vector<IdentityText> idts(o.identity.empty() ? 0 : P);
+  Ranks rk;  // one process
+  auto group = [&](const std::vector<size_t>& members) {
+    std::vector<std::ostream*> os;
+    std::vector<std::string*> sp, cp;
+    std::vector<IdentityText*> ip;
+    for (size_t f : members) {
+      os.push_back(&outs[f]);
+      if (!sto_blocks.empty()) sp.push_back(&sto_blocks[f]);
+      if (!cov_tables.empty()) cp.push_back(&cov_tables[f]);
+      if (!idts.empty()) ip.push_back(&idts[f]);
+    }
+    align_group(ctx, o, rk, align_model, fams, members, os, sp, nullptr, cp, ip);
+  };
+  std::vector<size_t> batch;
+  std::vector<uint64_t> bytes;
+  for (size_t f = 0; f < P; ++f)
+    if (fams[f].size() > 1) {
+      std::vector<uint32_t> lens;
+      for (const Fasta& s : fams[f]) lens.push_back(s.size());
+      batch.push_back(f);
+      bytes.push_back(dafs_host_family_bytes((uint32_t)lens.size(), lens.data()));
+    }
+  std::vector<uint32_t> group_of(batch.size());
+  check(dafs_host_pack_greedy((uint32_t)batch.size(), bytes.data(), dafs_host_batch_bytes(), group_of.data()));
+  for (size_t b0 = 0; b0 < batch.size();) {
+    size_t b1 = b0;
+    while (b1 < batch.size() && group_of[b1] == group_of[b0]) ++b1;
+    group(std::vector<size_t>(batch.begin() + b0, batch.begin() + b1));
+    b0 = b1;
+  }
+  for (size_t f = 0; f < P; ++f)
+    if (fams[f].size() == 1) group({f});
+  for (size_t f = 0; f < P; ++f) std::cout << "==> " << headers[f] << " <==" << std::endl << outs[f].str();
+  std::cout.flush();
+  if (!o.stockholm.empty()) write_stockholm(o.stockholm, sto_blocks);
+  if (!o.covariation.empty()) write_covariation(o.covariation, cov_tables, &headers);
+  if (!o.identity.empty()) write_identity(o, idts, &headers);
+  return 0;
+}
+
 // `dafs --describe ALIGNMENT` (pipeline.describe is the Python twin): the calls that read an alignment
 // alone, on a finished alignment that the seed reader reads.  Nothing is aligned and nothing is printed.
 int run_describe(const Options& o) {
@@ -2044,6 +2211,7 @@ int run(const Options& o, Ranks& rk) {
   if (!o.describe.empty()) return rk.rank == 0 ? run_describe(o) : 0;
   if (!o.seed.empty()) return o.seed_each ? run_add_each(o, align_model) : run_add(o, align_model);
   if (o.pairwise) return run_pairwise(o, align_model);
+  if (o.cluster_given || o.cluster_count_given) return run_cluster(o, align_model);
 
   // one family per input file
   const bool multi = o.inputs.size() > 1;

@@ -604,6 +604,54 @@ extern "C" int dafs_host_pairwise_table(uint64_t npairs, const uint32_t* x, cons
   });
 }
 
+// --cluster-table: one line per sequence, named by the Stockholm rule over the file's headers.  A cluster's join is found on
+// the tree: the node whose leaves all carry the cluster's label and are as many as the cluster has members.
+extern "C" int dafs_host_cluster_table(uint32_t n, const char* const* headers, const uint32_t* length, const uint32_t* labels,
+                                       const float* score, const int32_t* left, const int32_t* right, const float* sim, char** table) {
+  return text_out(table, [&]() {
+    const std::vector<std::string> nm = stockholm_names(strings(n, headers));
+    if (!n || !length || !labels || !score || !left || !right || !sim) throw kBadArgument;
+    const std::string bad = "cluster table: the clusters are not those of a cut of this tree";
+    std::vector<uint32_t> size(n, 0);
+    for (uint32_t i = 0; i < n; ++i) {
+      if (labels[i] >= n) throw bad;
+      ++size[labels[i]];
+    }
+    const double nan = std::nan("");
+    std::vector<double> join(n, nan);
+    std::vector<uint8_t> found(n, 0);
+    const uint32_t T = 2 * n - 1;
+    std::vector<uint32_t> lab(T, DAFS_HIP_NONE), leaves(T, 1);  // per node: the one label of its leaves (or none), their number
+    for (uint32_t i = 0; i < T; ++i) {
+      if (i < n) {
+        lab[i] = labels[i];
+      } else {
+        if (left[i] < 0 || right[i] < 0 || (uint32_t)left[i] >= i || (uint32_t)right[i] >= i) throw bad;
+        leaves[i] = leaves[left[i]] + leaves[right[i]];
+        if (lab[left[i]] != DAFS_HIP_NONE && lab[left[i]] == lab[right[i]]) lab[i] = lab[left[i]];
+      }
+      if (lab[i] != DAFS_HIP_NONE && leaves[i] == size[lab[i]]) {
+        found[lab[i]] = 1;
+        if (i >= n) join[lab[i]] = score[i];
+      }
+    }
+    std::ostringstream ts;
+    for (uint32_t i = 0; i < n; ++i) {
+      if (!found[labels[i]]) throw bad;
+      uint32_t best[2] = {DAFS_HIP_NONE, DAFS_HIP_NONE};  // inside, outside: the first of the most similar
+      for (uint32_t j = 0; j < n; ++j) {
+        if (j == i) continue;
+        uint32_t& b = best[labels[j] == labels[i] ? 0 : 1];
+        if (b == DAFS_HIP_NONE || sim[(size_t)i * n + j] > sim[(size_t)i * n + b]) b = j;
+      }
+      ts << i + 1 << "\t" << nm[i] << "\t" << length[i] << "\t" << labels[i] + 1 << "\t" << size[labels[i]] << "\t" << fmt9d(join[labels[i]]);
+      for (uint32_t b : best) ts << "\t" << (b == DAFS_HIP_NONE ? 0 : b + 1) << "\t" << fmt9d(b == DAFS_HIP_NONE ? nan : (double)sim[(size_t)i * n + b]);
+      ts << "\n";
+    }
+    return ts.str();
+  });
+}
+
 // --seed-scores: one line per new sequence of a --seed-each run, named by the Stockholm rule over the file's headers; with
 // --seed-structure four more columns, the sequence's structure support; with
 // --seed-nearest two more: the nearest seed row and the identity to it
@@ -1007,5 +1055,33 @@ extern "C" int dafs_host_pack_greedy(uint32_t n, const uint64_t* sizes, uint64_t
     group_of[k] = group;
     used += sizes[k];
   }
+  return DAFS_HIP_OK;
+}
+
+// The ranges of dafs_hip_similarity: dafs_host_pack_greedy's rule over the row-major pairs, each at the
+// size dafs_hip_align_posteriors gives it before the launch -- 2 * min(len) * 24 entries of a 4-byte column and a 4-byte value,
+// and its row pointers in both directions.  The launch's scratch planes belong to the launch, not to a pair, and are left out.
+extern "C" int dafs_host_similarity_ranges(uint32_t n, const uint32_t* lens, uint64_t max_bytes, uint64_t* end, uint64_t cap,
+                                           uint64_t* n_ranges) {
+  if (!n_ranges || (n && !lens) || (cap && !end)) return DAFS_HIP_EINVAL;
+  if (max_bytes == 0) max_bytes = dafs_host_batch_bytes();
+  uint64_t ranges = 0, used = 0, held = 0, p = 0;
+  for (uint32_t x = 0; x < n; ++x)
+    for (uint32_t y = x + 1; y < n; ++y, ++p) {
+      const uint64_t lx = lens[x], ly = lens[y];
+      const uint64_t bytes = 2 * std::min(lx, ly) * 24 * 8 + 4 * (lx + ly + 2);
+      if (held && (used > max_bytes || bytes > max_bytes - used || held == 0xFFFFFFFFull)) {  // close the range in front of this pair
+        if (ranges < cap) end[ranges] = p;
+        ++ranges;
+        used = held = 0;
+      }
+      used += bytes;
+      ++held;
+    }
+  if (held) {
+    if (ranges < cap) end[ranges] = p;
+    ++ranges;
+  }
+  *n_ranges = ranges;
   return DAFS_HIP_OK;
 }

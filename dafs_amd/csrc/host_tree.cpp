@@ -1,14 +1,17 @@
 // dafs_amd/csrc/host_tree.cpp -- DAFS::build_tree (reference src/dafs.cpp:446-492) as a C entry point, so that
 // every host (the C++ command line, the Python driver of tests and bench.py) builds the guide tree with the same
 // code: greedy joins taken from a max-heap of (similarity, (i, j)), merged distance (d[ii][l] + d[ii][r]) * s / 2.
-// Also the merge of new sequences into a fixed seed alignment (dafs_host_merge_added), shared the same way.
+// Also the merge of new sequences into a fixed seed alignment (dafs_host_merge_added) and the cut of a guide tree into
+// clusters (dafs_host_cluster_cut), shared the same way.
 // Host logic only; nothing here touches the device.
+#include <cmath>
 #include <cstdint>
 #include <queue>
 #include <utility>
 #include <vector>
 
 #include "../../include/dafs_hip.h"
+#include "last_error.h"
 
 extern "C" int dafs_host_build_tree(uint32_t n0, const float* sim, float* score, int32_t* left, int32_t* right) {
   if (!n0 || !sim || !score || !left || !right) return DAFS_HIP_EINVAL;
@@ -43,6 +46,50 @@ extern "C" int dafs_host_build_tree(uint32_t n0, const float* sim, float* score,
     right[n] = (int32_t)b;
     idx[n++] = l;
   }
+  return DAFS_HIP_OK;
+}
+
+// The cut of `dafs --cluster`.  A join's children always have lower node indices than the join, so one
+// ascending pass decides every join after the joins below it.
+extern "C" int dafs_host_cluster_cut(uint32_t n, const float* score, const int32_t* left, const int32_t* right, int mode, float threshold,
+                                     uint32_t count, uint32_t* labels, uint32_t* n_clusters) {
+  auto refuse = [](const char* why) { dafs::set_last_error(why); return DAFS_HIP_EINVAL; };
+  if (!n || !score || !left || !right || !labels || !n_clusters) return refuse("cluster cut: invalid argument");
+  if (mode != DAFS_CLUSTER_THRESHOLD && mode != DAFS_CLUSTER_COUNT) return refuse("cluster cut: unknown mode");
+  if (mode == DAFS_CLUSTER_THRESHOLD && std::isnan(threshold)) return refuse("cluster cut: the threshold is not a number");
+  if (mode == DAFS_CLUSTER_COUNT && (count < 1 || count > n)) return refuse("cluster cut: the number of clusters must be 1 .. the number of sequences");
+  if (n > 0x7FFFFFFFu / 2) return refuse("cluster cut: too many sequences");
+  const uint32_t T = 2 * n - 1;
+  std::vector<uint32_t> parent(T, UINT32_MAX);
+  for (uint32_t i = 0; i < T; ++i) {
+    if (i < n) {
+      if (left[i] != -1 || right[i] != -1) return refuse("cluster cut: malformed tree (a leaf with a child)");
+      continue;
+    }
+    const int64_t ch[2] = {left[i], right[i]};
+    if (ch[0] == ch[1]) return refuse("cluster cut: malformed tree (a join of a node with itself)");
+    for (int64_t c : ch) {
+      if (c < 0 || c >= (int64_t)i) return refuse("cluster cut: malformed tree (a child that is not an earlier node)");
+      if (parent[c] != UINT32_MAX) return refuse("cluster cut: malformed tree (a node that is a child twice)");
+      parent[c] = i;
+    }
+  }
+  // 2n - 2 child slots were filled with distinct nodes below the root: every node but the root has its parent
+  std::vector<uint8_t> kept(T, 1);  // leaves count as kept
+  const uint32_t undone_from = mode == DAFS_CLUSTER_COUNT ? T - (count - 1) : T;
+  for (uint32_t i = n; i < T; ++i) {
+    const bool own = mode == DAFS_CLUSTER_COUNT ? i < undone_from : score[i] >= threshold;
+    kept[i] = own && kept[left[i]] && kept[right[i]];
+  }
+  std::vector<uint32_t> label_of(T, UINT32_MAX);
+  uint32_t next = 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    uint32_t top = i;
+    while (parent[top] != UINT32_MAX && kept[parent[top]]) top = parent[top];
+    if (label_of[top] == UINT32_MAX) label_of[top] = next++;
+    labels[i] = label_of[top];
+  }
+  *n_clusters = next;
   return DAFS_HIP_OK;
 }
 

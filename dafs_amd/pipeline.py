@@ -1215,3 +1215,96 @@ def fold_each(names, seqs, th=0.2, ctx=None):
         res.name, res.ss, res.ss_str, res.score = nm, ss, capi.make_brackets(ss), score
         out.append(res)
     return out
+
+
+# ------------------------------------------------------------------------------------- a mixed input cut into families
+class Clustering:
+    pass
+
+
+def _tree_line(score, left, right, names):
+    """tree_string of the whole tree without recursion: the guide tree of a large mixed set can be a chain as deep as the set"""
+    text = {}
+    for i in range(len(score)):  # a join's children have lower indices
+        if left[i] < 0:
+            text[i] = names[i]
+        else:
+            text[i] = "[ %g %s %s ]" % (float(score[i]), text.pop(int(left[i])), text.pop(int(right[i])))
+    return text[len(score) - 1]
+
+
+def cluster(names, seqs, threshold=None, count=None, min_size=1, ctx=None, max_bytes=None, **opts):
+    """Cluster a mixed set of sequences into families and align each (`dafs --cluster`).  The N x N
+    similarity matrix of the pair kernels (Context.similarity: the pairs in ranges under max_bytes, so that the set's
+    posteriors are never held at once), the guide tree of the whole set (capi.build_tree) and its cut (capi.cluster_cut):
+    threshold keeps a join when its score is >= threshold and every join below it is kept, count undoes the joins made last
+    until that many clusters are left.  Exactly one of the two.  Every cluster of at least min_size members then goes through
+    run_batch (sub-batches under max_bytes; default DEFAULT_BATCH_BYTES for both), so its Result is, bit for bit, what
+    run(names_c, seqs_c, **opts) gives.  opts: the options of run() except mp / bp / shard / compare.  With w_pct_f the
+    clustering still reads the raw scores; -f acts inside each cluster's run.
+
+    Returns an object with .sim, .tree = (score, left, right), .tree_line, .labels (uint32 [N]), .clusters (per cluster the
+    indices of its members, ascending; the clusters are numbered by their smallest member), .results (per cluster a Result,
+    or None below min_size), .ranges (launches of the similarity pass), .table (the text of --cluster-table) and .seconds
+    (similarity, tree, batch, total)."""
+    import math
+    import time
+    for k in ("mp", "bp", "shard"):
+        if k in opts:
+            raise ValueError("pipeline.cluster: %s is a single-family option (use run)" % k)
+    if opts.get("compare") is not None:
+        raise ValueError("pipeline.cluster: the clusters are not known in advance; compare is an option of run")
+    if opts.get("level_sync") and opts.get("bp_update"):
+        raise ValueError("pipeline.cluster: bp_update needs the resident-node schedule (level_sync=False)")
+    known = {k: p.default for k, p in inspect.signature(run).parameters.items() if k not in ("names", "seqs", "ctx", "bp", "mp", "shard")}
+    unknown = set(opts) - set(known)
+    if unknown:
+        raise TypeError("pipeline.cluster: unknown options %s" % sorted(unknown))
+    cov_options(opts.get("covariation"))
+    names, seqs = list(names), list(seqs)
+    n = len(seqs)
+    if n == 0 or len(names) != n or any(len(s) == 0 for s in seqs):
+        raise ValueError("pipeline.cluster: at least one sequence, none empty, and one name per sequence")
+    if (threshold is None) == (count is None):
+        raise ValueError("pipeline.cluster: exactly one of threshold and count")
+    if threshold is not None and not math.isfinite(float(threshold)):
+        raise ValueError("pipeline.cluster: the threshold must be a finite number")
+    if count is not None and (int(count) != count or not 1 <= int(count) <= n):
+        raise ValueError("pipeline.cluster: count must be 1 .. %d, the number of sequences" % n)
+    if int(min_size) != min_size or int(min_size) < 1:
+        raise ValueError("pipeline.cluster: min_size must be a positive integer")
+    if max_bytes is not None and int(max_bytes) <= 0:
+        raise ValueError("pipeline.cluster: max_bytes must be positive")
+    align_model, th_a = opts.get("align_model", known["align_model"]), opts.get("th_a", known["th_a"])
+    own = ctx is None
+    if own:
+        ctx = capi.Context(0)
+    out = Clustering()
+    try:
+        t0 = time.perf_counter()
+        if n == 1:  # no pair: the unit matrix, no launch
+            out.sim, out.ranges = np.ones((1, 1), np.float32), 0
+        else:
+            ctx.set_sequences(seqs)
+            out.sim, out.ranges = ctx.similarity(align_model, th_a, max_bytes)
+        t1 = time.perf_counter()
+        out.tree = capi.build_tree(out.sim)
+        out.labels, k = capi.cluster_cut(out.tree, threshold=threshold, count=None if count is None else int(count))
+        out.clusters = [[] for _ in range(k)]
+        for i, c in enumerate(out.labels):
+            out.clusters[int(c)].append(i)
+        out.tree_line = _tree_line(out.tree[0], out.tree[1], out.tree[2], names)
+        out.table = capi.cluster_table(names, [len(s) for s in seqs], out.labels, out.tree, out.sim)
+        t2 = time.perf_counter()
+        aligned = [c for c, members in enumerate(out.clusters) if len(members) >= int(min_size)]
+        res = run_batch([([names[i] for i in out.clusters[c]], [seqs[i] for i in out.clusters[c]]) for c in aligned], ctx=ctx,
+                        max_bytes=max_bytes, **opts) if aligned else []
+        out.results = [None] * k
+        for c, r in zip(aligned, res):
+            out.results[c] = r
+        t3 = time.perf_counter()
+        out.seconds = dict(similarity=t1 - t0, tree=t2 - t1, batch=t3 - t2, total=t3 - t0)
+    finally:
+        if own:
+            ctx.close()
+    return out

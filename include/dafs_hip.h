@@ -199,6 +199,24 @@ int dafs_hip_mp_install(dafs_hip_ctx* ctx, int relaxed, const uint32_t* nnz, con
 /* sim_ (src/dafs.cpp:1813-1819): N*N floats, unit diagonal -- with families, the n_f*n_f blocks one after another; needs a
  * full-pair-set align_posteriors, dafs_hip_set_mp or dafs_hip_mp_install. */
 int dafs_hip_get_sim(dafs_hip_ctx* ctx, float* sim);
+/* The similarity scores of a set too large to hold all its posteriors at once (dafs --cluster, pipeline.cluster; DESIGN.md
+ * section 20).  On a one-family context of N >= 2 sequences (after dafs_hip_set_sequences) the row-major pair enumeration is
+ * walked in the ranges of dafs_host_similarity_ranges(N, lens, max_bytes): each range is one dafs_hip_align_posteriors launch
+ * into the context's buffers, which the next range reuses, and its scores go into the similarity block.  Afterwards
+ * dafs_hip_get_sim returns, bit for bit, what it returns after a full-pair-set dafs_hip_align_posteriors, whatever the
+ * budget; both matching stores are marked invalid in every case, also when one range held every pair, so that no caller comes
+ * to depend on the budget (a transform or a fetch is refused, DAFS_HIP_EINVAL).  max_bytes = 0: dafs_host_batch_bytes().
+ * n_ranges_out (may be NULL): the launches made.  DAFS_HIP_EINVAL: more than one family, fewer than two sequences, an unknown
+ * model, th < 0; DAFS_HIP_ETOOLONG as dafs_hip_align_posteriors. */
+int dafs_hip_similarity(dafs_hip_ctx* ctx, int model, float th, uint64_t max_bytes, uint64_t* n_ranges_out);
+/* Host-side helper (no device work): the ranges dafs_hip_similarity walks for n sequences of lengths lens.  The pairs x < y, in
+ * row-major order, are packed greedily under max_bytes (0: dafs_host_batch_bytes()) of estimated device memory; a pair over the
+ * budget is a range of its own, and a range holds fewer than 2^32 pairs.  The estimate of a pair is what
+ * dafs_hip_align_posteriors starts its entry pool from, 2 * min(len_x, len_y) * 24 entries of 8 bytes (column and value), plus
+ * its len_x + 1 + len_y + 1 row pointers of 4 bytes.  The launch's scratch planes depend on the launch plan and not on the
+ * number of pairs, and are left out.  *n_ranges: the number of ranges (0 for n < 2); range r is [end[r - 1], end[r]) with
+ * end[-1] = 0, and the first min(*n_ranges, cap) entries of end are written (end may be NULL with cap = 0: the count alone). */
+int dafs_host_similarity_ranges(uint32_t n, const uint32_t* lens, uint64_t max_bytes, uint64_t* end, uint64_t cap, uint64_t* n_ranges);
 
 /* ------------------------------------------------------------------------------------------
  * L1: base-pairing probabilities.
@@ -239,6 +257,18 @@ int dafs_hip_fold_posterior_dense(dafs_hip_ctx* ctx, const char* seq, uint32_t l
 /* Host-side helper (no device work): DAFS::build_tree (src/dafs.cpp:446-492) on the N*N similarity matrix.
  * score/left/right: 2N-1 entries; leaves have left = right = -1, node N+k is the k-th join of slots left, right. */
 int dafs_host_build_tree(uint32_t n, const float* sim, float* score, int32_t* left, int32_t* right);
+/* Host-side helper (no device work): the cut of a guide tree of n leaves (the arrays of dafs_host_build_tree) into clusters
+ * (dafs --cluster, pipeline.cluster).  mode DAFS_CLUSTER_THRESHOLD: a join is kept when its score is >=
+ * threshold and every join below it is kept.  mode DAFS_CLUSTER_COUNT: the count - 1 joins with the highest node indices are
+ * undone and all others are kept, which leaves exactly `count` clusters.  A cluster is the leaf set of a maximal kept join, or
+ * a single leaf.  labels[n]: the cluster of every leaf; the clusters are numbered from 0 by their smallest leaf.  *n_clusters:
+ * their number.  n = 1 gives one cluster.  The argument that the mode does not read is ignored.  DAFS_HIP_EINVAL (message in
+ * dafs_hip_last_error): n = 0, a null pointer, an unknown mode, a NaN threshold, a count outside 1..n, a malformed tree (a leaf
+ * with a child; a join whose children are not two different earlier nodes; a node that is a child twice or, the root apart,
+ * never). */
+enum { DAFS_CLUSTER_THRESHOLD = 0, DAFS_CLUSTER_COUNT = 1 };
+int dafs_host_cluster_cut(uint32_t n, const float* score, const int32_t* left, const int32_t* right, int mode, float threshold,
+                          uint32_t count, uint32_t* labels, uint32_t* n_clusters);
 
 /* Host-side helper (no device work): the merge of `dafs --seed` and pipeline.add, k new sequences
  * placed into a fixed seed alignment of C columns.  lens: k sequence lengths; z: their column maps from the k nodes (leaf j
@@ -299,6 +329,15 @@ int dafs_host_covariation_table(uint32_t n, uint32_t len, const uint8_t* code, c
  * %.9g; iterations is signed (-1: a pair that was not asked) */
 int dafs_host_pairwise_table(uint64_t npairs, const uint32_t* x, const uint32_t* y, uint32_t nnames, const char* const* names,
                              const double* sim, const double* score, const int64_t* iterations, char** table);
+/* The --cluster-table table: per sequence i the line "i+1 name length cluster size join nearest_in sim_in
+ * nearest_out sim_out", tab-separated, floats as %.9g; the names are dafs_host_stockholm_names of the n headers.  labels: the
+ * clusters of dafs_host_cluster_cut on the tree score / left / right (cluster is labels[i] + 1, size its number of members, join
+ * the score of the join whose leaves are the cluster, "nan" for a cluster of one); sim: the n x n similarity matrix.  nearest_in
+ * / nearest_out: the most similar other sequence inside / outside i's cluster (1-based, the smallest index among equals) and
+ * that similarity; "0" and "nan" where there is none.  Refused (DAFS_HIP_EINVAL): a cluster that is not the leaf set of one
+ * node of the tree. */
+int dafs_host_cluster_table(uint32_t n, const char* const* headers, const uint32_t* length, const uint32_t* labels, const float* score,
+                            const int32_t* left, const int32_t* right, const float* sim, char** table);
 /* The --seed-scores table of a --seed-each run: per new sequence j the line "j+1 name length matched
  * length-matched score iterations", tab-separated, floats as %.9g; the names are dafs_host_stockholm_names of the n headers.
  * matched[j] > length[j] is refused (DAFS_HIP_EINVAL). */
