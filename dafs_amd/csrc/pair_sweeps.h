@@ -70,10 +70,11 @@ __device__ __forceinline__ int pair_width(int L2) {
 // Entries are rare (a few per row), so sweep 3 does not write the thresholded plane back for a fourth sweep over every
 // cell to re-read: a lane with at least one entry in a step appends ONE record for that step to a private list (`list`: a
 // second plane of the wave's scratch), {entry mask of its WR cells, row-1 | entries of the row left of its columns << 16,
-// the WR posteriors}, padded to whole 16-byte words (WR <= 6: 32 bytes, two dwordx4 stores, one branch per step), and
-// sweep 4 walks the lists, rebuilding an entry's position in its row from the carried count plus the mask's lower bits
-// and its position in its column from a running count per column -- a third less HBM traffic for the whole kernel, and
-// one list step per lane-step with entries instead of ~190 grid steps.  A lane whose list is full (entries in most of
+// the WR posteriors}, padded to whole 16-byte words (WR <= 6: 32 bytes, two 16-byte buffer stores that every lane
+// issues in every step and the range check drops for the lanes without a record: no branch), and sweep 4 walks the
+// lists four records at a time, rebuilding an entry's position in its row from the carried count plus the mask's lower
+// bits and its position in its column from a running position per column -- a third less HBM traffic for the whole
+// kernel, and one list step per lane-step with entries instead of ~190 grid steps.  A lane whose list is full (entries in most of
 // its steps: th near 0) makes the call return false with nothing emitted and the slab untouched; the caller then runs
 // the dense = true instantiation, which is the plane-and-rescan form.
 template <int WR>
@@ -86,6 +87,14 @@ __device__ __forceinline__ bool pair_finish(const Args& a, float* __restrict__ s
                                             int lane, int t, int g, int L1, int L2, int nsteps, bool act, uint32_t task, float th, Post post) {
   const int tlast = (L2 >= 0 ? L2 : 0) / WR;  // lane (within the group) that owns column L2
   const int j0 = t * WR;
+  // The wave's list plane as a buffer.  Sweep 3: the record stores of a step are issued by every lane, and a lane without
+  // a record gives an offset outside the buffer, which the range check drops without traffic.  Unconditional vector
+  // stores keep the step free of branches around memory operations, so every wait of the loop can be counted (loads
+  // and stores share one in-order counter; behind a branch the compiler has to wait for everything).  Sweep 4: a lane
+  // that has run out of records reads outside the buffer and gets zeros, an empty entry mask.
+  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+  const __amdgpu_buffer_rsrc_t list_rs = __builtin_amdgcn_make_buffer_rsrc((void*)list, 0, list_cap * 256, 0x00020000);
+  constexpr uint32_t NO_RECORD = 0x80000000u;  // beyond any list plane, and no wrap with the accesses' immediates
   // ------------------------------------------------------------------ sweep 3: posterior + sim + counts
   int colcnt[WR];
   float simv = 0.0f;
@@ -102,12 +111,19 @@ __device__ __forceinline__ bool pair_finish(const Args& a, float* __restrict__ s
     if (t == G - 1) s_rowptr[0] = 0;
     int nrec = 0;       // records in this lane's list
     bool ovf = false;
-    // slab values are fetched one step ahead (a load issued where it is needed waits for itself and for the stores of
-    // the step before: loads and stores share one in-order counter)
-    float sv[WR];
+    // Slab values are fetched TWO steps ahead, into two register sets that take turns: the values a step starts with
+    // were requested before the record stores of the step before, so waiting for them does not wait for those stores.
+    // The last two steps refetch the last step's slots.
+    float sva[WR], svb[WR];
 #pragma unroll
-    for (int c = 0; c < WR; ++c) sv[c] = slab[c * 64 + lane];
-    for (int s = 0; s < nsteps; ++s) {
+    for (int c = 0; c < WR; ++c) sva[c] = slab[c * 64 + lane];
+#pragma unroll
+    for (int c = 0; c < WR; ++c) svb[c] = slab[(W + c) * 64 + lane];  // nsteps >= G >= 16: step 1 exists
+    // both sets have arrived before the loop starts (the empty asm uses them), so the waits inside the loop count
+    // what the loop itself has issued and not the order of these first requests
+#pragma unroll
+    for (int c = 0; c < WR; ++c) asm volatile("" : "+v"(sva[c]), "+v"(svb[c]));
+    auto step = [&](const int s, float (&sv)[WR]) __attribute__((always_inline)) {
       const int i = s - t;
       const bool rowv = (i >= 0) && (i <= L1);
       float* __restrict__ slab_s = slab + (size_t)s * (W * 64);
@@ -117,13 +133,13 @@ __device__ __forceinline__ bool pair_finish(const Args& a, float* __restrict__ s
       int dtr = dgtr, ltr = rtr, run = rcnt;
       float pp[WR];
       post(sv, pp);  // the model's posteriors of the WR cells, table reads batched
-      {  // private slots: unguarded (cells outside the grid are ignored below); the last step refetches its own
-        const float* __restrict__ slab_n = slab_s + (s + 1 < nsteps ? W * 64 : 0);
+      {  // private slots: unguarded (cells outside the grid are ignored below)
+        const float* __restrict__ slab_n = slab + (size_t)min(s + 2, nsteps - 1) * (W * 64);
 #pragma unroll
         for (int c = 0; c < WR; ++c) sv[c] = slab_n[c * 64 + lane];
       }
       // One straight-line block for the WR cells (the posteriors' polynomials, the similarity DP and the counts as
-      // selects: five independent chains the scheduler can interleave), then the rare appends.  Written as per-cell
+      // selects: five independent chains the scheduler can interleave), then the step's record.  Written as per-cell
       // if / else, every cell becomes a handful of basic blocks and its polynomial waits for the cell before it.
       uint32_t emask = 0;  // entries among the WR cells, bit c = cell c
 #pragma unroll
@@ -156,23 +172,29 @@ __device__ __forceinline__ bool pair_finish(const Args& a, float* __restrict__ s
         colcnt[c] += e;
         emask |= (uint32_t)e << c;
       }
-      if (!dense && emask != 0) {  // one record for the step (pair_rec): the only branch of the step's entries
-        if ((nrec + 1) * pair_rec<WR>::D <= list_cap) {
-          float w[pair_rec<WR>::D];
-          w[0] = __uint_as_float(emask);
-          w[1] = __int_as_float((i - 1) | (rcnt << 16));
+      if (!dense) {  // one record for the step (pair_rec), stored by the lanes that have entries and room for it
+        const bool fits = (nrec + 1) * pair_rec<WR>::D <= list_cap;
+        const bool app = emask != 0 && fits;
+        ovf = ovf || (emask != 0 && !fits);
+        float w[pair_rec<WR>::D];
+        w[0] = __uint_as_float(emask);
+        w[1] = __int_as_float((i - 1) | (rcnt << 16));
 #pragma unroll
-          for (int c = 0; c < WR; ++c) w[2 + c] = pp[c];
+        for (int c = 0; c < WR; ++c) w[2 + c] = pp[c];
 #pragma unroll
-          for (int c = 2 + WR; c < pair_rec<WR>::D; ++c) w[c] = 0.0f;
-          // 32-bit byte offset from the wave's list base (scalar base + vector offset: no 64-bit address per lane)
-          char* __restrict__ r = (char*)list + (uint32_t)(((uint32_t)nrec * pair_rec<WR>::Q * 64 + lane) * 16);
+        for (int c = 2 + WR; c < pair_rec<WR>::D; ++c) w[c] = 0.0f;
+        // 32-bit byte offset into the wave's list plane
+        const uint32_t ro = app ? (uint32_t)(((uint32_t)nrec * pair_rec<WR>::Q * 64 + lane) * 16) : NO_RECORD;
+#if !defined(PAIR_EXP_NORECSTORE)  // tuning experiment: what the record stores cost sweep 3
 #pragma unroll
-          for (int q = 0; q < pair_rec<WR>::Q; ++q) *(float4*)(r + q * 1024) = make_float4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
-          ++nrec;
-        } else {
-          ovf = true;
+        for (int q = 0; q < pair_rec<WR>::Q; ++q) {
+          const u32x4 d = {__float_as_uint(w[4 * q]), __float_as_uint(w[4 * q + 1]), __float_as_uint(w[4 * q + 2]), __float_as_uint(w[4 * q + 3])};
+          __builtin_amdgcn_raw_buffer_store_b128(d, list_rs, (int)(ro + q * 1024), 0, 0);
         }
+#else
+        (void)ro; (void)list_rs;
+#endif
+        nrec += app ? 1 : 0;
       }
       dgdp = rdp; dgtr = rtr;
       lastdp = ldp; lasttr = ltr; lastcnt = run;
@@ -189,6 +211,16 @@ __device__ __forceinline__ bool pair_finish(const Args& a, float* __restrict__ s
         rowacc += (uint32_t)run;
         s_rowptr[i] = rowacc;
       }
+    };
+    // Two steps per turn: each register set is refilled by the step that used it.  The sparse form rounds an odd step
+    // count up instead of leaving the loop half way (one straight-line body, whose waits the compiler can count): in
+    // step nsteps every lane's row lies beyond L1, so it finds no entry, appends nothing and writes no row pointer.
+    // The dense form stores into the slab and must not run a step the slab does not have.
+    const int nrun = dense ? nsteps : (nsteps + 1) & ~1;
+    for (int s = 0; s < nrun; s += 2) {
+      step(s, sva);
+      if (dense && s + 1 >= nsteps) break;
+      step(s + 1, svb);
     }
     nnz = rowacc;
     if (!dense && __any(ovf)) return false;  // wave-uniform: every pair of the wave takes the dense form
@@ -214,6 +246,9 @@ __device__ __forceinline__ bool pair_finish(const Args& a, float* __restrict__ s
     for (int c = 0; c < WR; ++c) { colbase[c] = run; run += colcnt[c]; }
   }
 
+#if defined(PAIR_EXP_STOP) && PAIR_EXP_STOP == 3  // tuning experiment: everything up to sweep 3 (splits sweeps 3 and 4)
+  if (simv != 12345.0f || nnz != 12345u || colbase[WR - 1] != 12345) return true;
+#endif
   // reserve 2*nnz entries in the pool
   unsigned long long off = 0;
   if (t == 0 && act) off = atomicAdd(a.pool_top, 2ull * nnz);
@@ -246,42 +281,55 @@ __device__ __forceinline__ bool pair_finish(const Args& a, float* __restrict__ s
       for (int o = 1; o < 64; o <<= 1) maxrec = max(maxrec, __shfl_xor(maxrec, o));
       maxrec = __builtin_amdgcn_readfirstlane(maxrec);
       constexpr int Q = pair_rec<WR>::Q;
-      int colrun[WR];  // entries of this lane's column c in the rows before the record's
+      uint32_t colpos[WR];  // where the next entry of this lane's column c goes in the pair's transposed half
 #pragma unroll
-      for (int c = 0; c < WR; ++c) colrun[c] = 0;
-      float4 nx[Q];  // next record, one iteration ahead
+      for (int c = 0; c < WR; ++c) colpos[c] = nnz + (uint32_t)colbase[c];
+      // The scatter stores sit behind per-entry branches, which the compiler cannot count: a wait for a record's load
+      // is a wait for every store issued before it.  Records are therefore fetched K at a time and all K have arrived
+      // before the turn's first store (the empty asm uses them): one wait per K records, for the turn's loads and the
+      // stores of the turn before together, instead of one round trip per record.
+      constexpr int K = 4;
+      int jm1 = j0 - 1;  // column numbers from one register: WR constants of the lane would be kept (spilled) kernel-wide
+      asm volatile("" : "+v"(jm1));
+      u32x4 cur[K][Q];
+      auto fetch = [&](u32x4 (&r)[K][Q], const int k0) __attribute__((always_inline)) {
 #pragma unroll
-      for (int q = 0; q < Q; ++q) nx[q] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-      if (slab_nrec > 0) {
+        for (int kk = 0; kk < K; ++kk) {
+          const uint32_t ro = (k0 + kk < slab_nrec) ? (uint32_t)(((uint32_t)(k0 + kk) * Q * 64 + lane) * 16) : NO_RECORD;
 #pragma unroll
-        for (int q = 0; q < Q; ++q) nx[q] = *(const float4*)((const char*)list + (uint32_t)((q * 64 + lane) * 16));
-      }
-      for (int k = 0; k < maxrec; ++k) {
-        float w[4 * Q];
-#pragma unroll
-        for (int q = 0; q < Q; ++q) { w[4 * q] = nx[q].x; w[4 * q + 1] = nx[q].y; w[4 * q + 2] = nx[q].z; w[4 * q + 3] = nx[q].w; }
-        if (k + 1 < slab_nrec) {
-#pragma unroll
-          for (int q = 0; q < Q; ++q) nx[q] = *(const float4*)((const char*)list + (uint32_t)((((uint32_t)(k + 1) * Q + q) * 64 + lane) * 16));
+          for (int q = 0; q < Q; ++q) r[kk][q] = __builtin_amdgcn_raw_buffer_load_b128(list_rs, (int)(ro + q * 1024), 0, 0);
         }
-        const uint32_t m = (k < slab_nrec) ? __float_as_uint(w[0]) : 0u;
-        const int im1 = __float_as_int(w[1]) & 0xFFFF;
-        const uint32_t rowpos = s_rowptr[im1] + (uint32_t)(__float_as_int(w[1]) >> 16);  // the row's first entry of this lane
-        int before = 0;  // entries of the record left of cell c
+      };
+      for (int k0 = 0; k0 < maxrec; k0 += K) {
+        fetch(cur, k0);
 #pragma unroll
-        for (int c = 0; c < WR; ++c) {
-          const int e = (int)((m >> c) & 1u);
-          if (e && ok) {
-            const float p = w[2 + c];
-            const unsigned long long pos = off + rowpos + (uint32_t)before;
-            a.ent_col[pos] = (uint32_t)(j0 + c - 1);
-            a.ent_val[pos] = p;
-            const unsigned long long tpos = off + nnz + (uint32_t)(colbase[c] + colrun[c]);
-            a.ent_col[tpos] = (uint32_t)im1;
-            a.ent_val[tpos] = p;
+        for (int kk = 0; kk < K; ++kk)
+#pragma unroll
+          for (int q = 0; q < Q; ++q) asm volatile("" : "+v"(cur[kk][q]));
+#pragma unroll
+        for (int kk = 0; kk < K; ++kk) {
+          uint32_t w[4 * Q];
+#pragma unroll
+          for (int q = 0; q < Q; ++q) { w[4 * q] = cur[kk][q].x; w[4 * q + 1] = cur[kk][q].y; w[4 * q + 2] = cur[kk][q].z; w[4 * q + 3] = cur[kk][q].w; }
+          const uint32_t m = w[0];  // 0 beyond the lane's last record
+          const int im1 = (int)w[1] & 0xFFFF;
+          const uint32_t rowpos = s_rowptr[im1] + (uint32_t)((int)w[1] >> 16);  // the row's first entry of this lane
+          int before = 0;  // entries of the record left of cell c
+#pragma unroll
+          for (int c = 0; c < WR; ++c) {
+            const int e = (int)((m >> c) & 1u);
+            if (e && ok) {
+              const float p = __uint_as_float(w[2 + c]);
+              const unsigned long long pos = off + rowpos + (uint32_t)before;
+              a.ent_col[pos] = (uint32_t)(jm1 + c);
+              a.ent_val[pos] = p;
+              const unsigned long long tpos = off + colpos[c];
+              a.ent_col[tpos] = (uint32_t)im1;
+              a.ent_val[tpos] = p;
+            }
+            before += e;
+            colpos[c] += (uint32_t)e;
           }
-          before += e;
-          colrun[c] += e;
         }
       }
     }
@@ -290,6 +338,8 @@ __device__ __forceinline__ bool pair_finish(const Args& a, float* __restrict__ s
 #pragma unroll
     for (int c = 0; c < WR; ++c) colrun[c] = 0;
     int lastcnt = 0;
+    int jm1 = j0 - 1;  // as in the sparse form
+    asm volatile("" : "+v"(jm1));
     float pv[WR];
 #pragma unroll
     for (int c = 0; c < WR; ++c) pv[c] = slab[c * 64 + lane];
@@ -301,13 +351,12 @@ __device__ __forceinline__ bool pair_finish(const Args& a, float* __restrict__ s
       const uint32_t rowbase = (rowv && i >= 1) ? s_rowptr[i - 1] : 0;
 #pragma unroll
       for (int c = 0; c < WR; ++c) {
-        const int j = j0 + c;
         const float p = pv[c];  // sweep 3 left 0 in every non-entry slot
         if (s + 1 < nsteps) pv[c] = slab_s[(W + c) * 64 + lane];
         const bool entry = p != 0.0f;
         if (entry && ok) {
           const unsigned long long pos = off + rowbase + (uint32_t)run;
-          a.ent_col[pos] = (uint32_t)(j - 1);
+          a.ent_col[pos] = (uint32_t)(jm1 + c);
           a.ent_val[pos] = p;
           const unsigned long long tpos = off + nnz + (uint32_t)(colbase[c] + colrun[c]);
           a.ent_col[tpos] = (uint32_t)(i - 1);

@@ -190,17 +190,25 @@ __device__ __forceinline__ void pairhmm3_pair(const dafs_pairhmm3_args& a, const
     for (int c = 0; c < WR; ++c) pM[c] = pX[c] = LZ;
     float firstM = LZ, firstY = LZ;  // this lane's first column, row of the previous step
     float dgM = LZ;                  // right neighbour's first column, one row later
-    // one step ahead, as in sweep 1: the residue class of the row, and the row's F_M values from the slab (each
-    // refetched for the next step as soon as this step has used it, into the same register)
-    int c1n;
+    // One step ahead, as in sweep 1: the residue class of the row, and the row's F_M values from the slab (each
+    // refetched for the next step as soon as this step has used it, into the same register).  In the forward's form:
+    // no access of the step sits behind a branch, so the step's waits are counted ones (loads and stores share one
+    // in-order counter; behind a branch the compiler has to wait for everything).  The slab slots (step, c, lane) are
+    // private and the forward sweep has written every one of them, so cells outside the grid are read and written
+    // like the others: their F and B are both LOG_ZERO-sized, the sum is finite, and sweep 3 ignores it.  The residue
+    // class comes from a clamped index, and what the clamp fetched for a row outside 0 .. L1-1 is replaced by 6 when
+    // the next step uses it.
+    int c1raw;
     float fwd[WR];
     {
-      const int i = nsteps - 1 - t;
-      const bool rowv = (i >= 0) && (i <= L1);
-      c1n = (rowv && i < L1) ? (int)s1[i] : 6;
       const float* __restrict__ q = slab + (size_t)(nsteps - 1) * (W * 64);
 #pragma unroll
-      for (int c = 0; c < WR; ++c) fwd[c] = (rowv && j0 + c <= L2) ? q[c * 64 + lane] : 0.0f;
+      for (int c = 0; c < WR; ++c) fwd[c] = q[c * 64 + lane];
+      c1raw = (int)s1[max(min(nsteps - 1 - t, L1 - 1), 0)];
+      // arrived before the loop starts (the empty asm uses them): the loop's waits count what the loop has issued
+#pragma unroll
+      for (int c = 0; c < WR; ++c) asm volatile("" : "+v"(fwd[c]));
+      asm volatile("" : "+v"(c1raw));
     }
     for (int s = 0; s < nsteps; ++s) {
       // mirrored skew: lane G-1 starts with the last row of the longest pair of the wave (rows beyond a shorter
@@ -208,12 +216,11 @@ __device__ __forceinline__ void pairhmm3_pair(const dafs_pairhmm3_args& a, const
       // stored row i for this lane, sf = i + t, is the same for the whole wave
       const int sf = nsteps - 1 - s;
       const int i = sf - t;
-      const bool rowv = (i >= 0) && (i <= L1);
       float* __restrict__ slab_s = slab + (size_t)sf * (W * 64);
-      const int c1 = c1n;
-      const int in = i - 1;  // the next step's row; its forward step is sf - 1 (never read when sf == 0: in < 0)
-      const bool rowvn = (in >= 0) && (in <= L1);
-      c1n = (rowvn && in < L1) ? (int)s1[in] : 6;
+      // the next step reads forward step sf - 1; the last step has none and refetches its own (wave-uniform select)
+      const float* __restrict__ slab_p = slab + (size_t)(sf > 0 ? sf - 1 : 0) * (W * 64);
+      const int c1 = (i >= 0 && i < L1) ? c1raw : 6;
+      c1raw = (int)s1[max(min(i - 1, L1 - 1), 0)];  // the next step's row
       const float rM = shift_down1<G>(firstM, LZ, t), rY = shift_down1<G>(firstY, LZ, t);
       const float insc1 = s_ins[c1];
       const float2* __restrict__ mi_row = s_mi + c1 * 8;
@@ -254,8 +261,8 @@ __device__ __forceinline__ void pairhmm3_pair(const dafs_pairhmm3_args& a, const
           const int j = j0 + c;
           pM[c] = o[2];
           yprev = o[3];
-          if (rowv && j <= L2) slab_s[c * 64 + lane] = fwd[c] + o[2];  // forward[ij] + backward[ij], :395
-          fwd[c] = (rowvn && j <= L2) ? slab_s[(c - W) * 64 + lane] : 0.0f;
+          slab_s[c * 64 + lane] = fwd[c] + o[2];  // forward[ij] + backward[ij], :395
+          fwd[c] = slab_p[c * 64 + lane];
           if (c <= 1) {  // columns 0 and 1 only exist for c <= 1
             if (i == 1 && j == 1) capM = o[2];
             if (i == 1 && j == 0) capX = pX[c];

@@ -9,6 +9,33 @@ import re
 import sys
 from collections import Counter
 
+
+def memory_order(body):
+    """Vector memory operations, vmcnt waits and branches of a loop body in program order, runs collapsed: what a wait
+    can count (loads and stores share one in-order counter; an operation behind a branch is one it cannot count)"""
+    seq = []
+    for l in body:
+        if not l.startswith("\t") or l.strip().startswith((";", ".")):
+            continue
+        f = l.split()
+        op, tok = f[0], None
+        if op.startswith(("global_", "buffer_", "flat_", "scratch_")):
+            kind = "load" if "_load" in op else "store" if "_store" in op else "atomic"
+            tok = ("scratch_" if op.startswith("scratch_") else "buffer_" if op.startswith("buffer_") else "") + kind
+        elif op == "s_waitcnt":
+            m = re.search(r"vmcnt\((\d+)\)", l)
+            tok = "vmcnt(%s)" % m.group(1) if m else None
+        elif op.startswith(("s_cbranch_", "s_branch")):
+            tok = op[2:]
+        if tok is None:
+            continue
+        if seq and seq[-1][0] == tok:
+            seq[-1][1] += 1
+        else:
+            seq.append([tok, 1])
+    return " ".join(t if n == 1 else "%dx%s" % (n, t) for t, n in seq)
+
+
 lines = open(sys.argv[1]).read().split("\n")
 sel = sys.argv[2] if len(sys.argv) > 2 else None
 if sel:
@@ -36,3 +63,5 @@ for lo, hi in sorted(set(inner)):
     print("loop lines %d-%d: %d instr | valu %d (packed/f64 %d) -> %d pipe cycles | lds %d | vmem %d | salu %d | waitcnt %d | nop %d" %
           (lo, hi, len(ops), n_valu, slow, cyc, lds, vmem, salu, c.get("s_waitcnt", 0), c.get("s_nop", 0)))
     print("   ", ", ".join("%s %d" % kv for kv in sorted(valu.items(), key=lambda kv: -kv[1])[:14]))
+    if not any((a, b) != (lo, hi) and lo <= a and b <= hi for a, b in inner):  # a step loop, not the loop over pairs
+        print("    order:", memory_order(lines[lo:hi + 1]))
