@@ -160,6 +160,10 @@ _build_tree = _sig("dafs_host_build_tree", C.c_int, [C.c_uint32, C.c_void_p, C.c
 _cluster_cut = _sig("dafs_host_cluster_cut", C.c_int, [C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_uint32, C.c_void_p, u32p])
 CLUSTER_THRESHOLD, CLUSTER_COUNT = 0, 1  # the modes of dafs_host_cluster_cut
 _cluster_table = _sig("dafs_host_cluster_table", C.c_int, [C.c_uint32, C.POINTER(C.c_char_p)] + [C.c_void_p] * 6 + [C.POINTER(C.c_void_p)])
+_linkage_tree = _sig("dafs_hip_linkage_tree", C.c_int, [C.c_void_p, C.c_int, C.c_uint32] + [C.c_void_p] * 4)
+linkage_workspace = _sig("dafs_hipk_linkage_workspace", C.c_size_t, [C.c_uint32])
+linkage_launch = _sig("dafs_hipk_linkage", C.c_int, [C.c_int, C.c_uint32] + [C.c_void_p] * 6)
+LINKAGES = ("guide", "single", "complete", "average")  # --cluster-linkage; the index is the library's DAFS_LINKAGE_* code
 _merge_added = _sig("dafs_host_merge_added", C.c_int, [C.c_uint32, C.c_uint32] + [C.c_void_p] * 5)
 # host text (dafs_amd/csrc/host_text.cpp): returned text is a char* the caller frees with dafs_host_free
 _strs = C.POINTER(C.c_char_p)
@@ -548,6 +552,24 @@ class Context:
         n_ranges = C.c_uint64()
         check(_similarity(self._h, model, th, 0 if max_bytes is None else int(max_bytes), C.byref(n_ranges)))
         return self.sim(), n_ranges.value
+
+    def linkage_tree(self, rule, sim=None):
+        """dafs_hip_linkage_tree: the "single", "complete" or "average" linkage tree of the n x n
+        matrix sim (only the entries x < y are read, all of them finite), joined on the device; sim None: of the context's
+        own similarity block (a one-family context after similarity() or a full-pair-set align_posteriors), read on the
+        device and left untouched.  Returns (score, left, right) in build_tree's layout and types.  ValueError before any
+        device work for an unknown rule, "guide" (that is build_tree), a matrix that is not square and a non-finite entry
+        above its diagonal."""
+        code, sim = linkage_check(rule, sim)
+        n = int(len(self._lens)) if sim is None and self._lens is not None else (0 if sim is None else sim.shape[0])
+        if n == 0:
+            raise ValueError("linkage_tree: the context holds no sequences and no matrix was given")
+        score = np.zeros(2 * n - 1, np.float32); left = np.zeros(2 * n - 1, np.int32); right = np.zeros(2 * n - 1, np.int32)
+        rc = _linkage_tree(self._h, code, n, None if sim is None else sim.ctypes.data, score.ctypes.data, left.ctypes.data, right.ctypes.data)
+        if rc == -1:
+            raise ValueError(_last_error().decode("latin-1"))
+        check(rc)
+        return score, left.astype(np.int64), right.astype(np.int64)
 
     def set_bp(self, rows):
         """rows: per sequence (rowptr[len+1], col, val)"""
@@ -1101,6 +1123,24 @@ def build_tree(sim):
     score = np.zeros(2 * n - 1, np.float32); left = np.zeros(2 * n - 1, np.int32); right = np.zeros(2 * n - 1, np.int32)
     check(_build_tree(n, sim.ctypes.data, score.ctypes.data, left.ctypes.data, right.ctypes.data))
     return score, left.astype(np.int64), right.astype(np.int64)
+
+
+def linkage_check(rule, sim=None):
+    """The checks of Context.linkage_tree that need no device: (the library's code of `rule`, sim as a contiguous float32 matrix
+    or None).  ValueError for an unknown rule, for "guide" (the guide tree is build_tree), for a matrix that is not square or
+    is empty, and for a non-finite entry above its diagonal."""
+    if rule not in LINKAGES:
+        raise ValueError("linkage: unknown rule %r (one of %s)" % (rule, ", ".join(LINKAGES)))
+    if rule == "guide":
+        raise ValueError("linkage: \"guide\" is the guide tree's own rule: use build_tree")
+    if sim is None:
+        return LINKAGES.index(rule), None
+    sim = np.ascontiguousarray(sim, np.float32)
+    if sim.ndim != 2 or sim.shape[0] != sim.shape[1] or sim.shape[0] == 0:
+        raise ValueError("linkage: the similarity matrix must be n x n with n >= 1")
+    if not np.isfinite(sim[np.triu_indices(sim.shape[0], 1)]).all():
+        raise ValueError("linkage: an entry above the diagonal is not finite")
+    return LINKAGES.index(rule), sim
 
 
 def similarity_ranges(lens, max_bytes=None):

@@ -105,6 +105,8 @@ struct Options {
   uint32_t cluster_min_size = 1;      // --cluster-min-size M
   std::string cluster_table;          // --cluster-table OUT
   std::string cluster_tree;           // --cluster-tree OUT
+  bool cluster_linkage_given = false;
+  int cluster_linkage = 0;            // --cluster-linkage RULE: 0 the guide tree's own rule, else DAFS_LINKAGE_*
   std::string input;
   std::vector<std::string> inputs;  // every FILE argument; with two or more, one output block per file
 };
@@ -212,6 +214,10 @@ const char* kHelp =
     "                        cluster's top join; the most similar sequence inside and outside the cluster; 0 and nan for none)\n"
     "      --cluster-tree OUT   With --cluster or --cluster-count: the guide tree of the whole set, as dafs prints a tree line;\n"
     "                        its join scores are the values T chooses between\n"
+    "      --cluster-linkage RULE  With --cluster or --cluster-count: the tree that is cut.  guide (default): the guide tree of\n"
+    "                        the whole set; single, complete, average: that linkage of the similarity scores, joined on the\n"
+    "                        device (a join scores the largest, the smallest or the size-weighted mean similarity between its\n"
+    "                        two clusters).  --cluster-tree writes the tree that was cut\n"
     "\n Aligning options:\n"
     "  -a, --align-model arg Alignment model (value=CONTRAlign, ProbCons) (default: ProbCons)\n"
     "  -p, --align-pct arg   Weight of PCT for matching probabilities (default: 0.25)\n"
@@ -257,7 +263,7 @@ Options parse(int argc, char** argv) {
       {"identity-matrix", {0, true}}, {"seed-nearest", {0, false}}, {"seed-nr", {0, true}}, {"describe", {0, true}},
       {"compare", {0, true}}, {"compare-ref", {0, true}}, {"compare-columns", {0, true}}, {"compare-matrix", {0, true}},
       {"cluster", {0, true}}, {"cluster-count", {0, true}}, {"cluster-min-size", {0, true}}, {"cluster-table", {0, true}},
-      {"cluster-tree", {0, true}}};
+      {"cluster-tree", {0, true}}, {"cluster-linkage", {0, true}}};
   std::map<char, std::string> shorts;
   for (const auto& kv : spec)
     if (kv.second.first) shorts[kv.second.first] = kv.first;
@@ -382,6 +388,15 @@ Options parse(int argc, char** argv) {
       if (value.empty()) throw "--" + name + " needs a file name";
       (name == "cluster-table" ? o.cluster_table : o.cluster_tree) = value;
     }
+    else if (name == "cluster-linkage") {
+      static const char* const rules[] = {"guide", "single", "complete", "average"};
+      int code = -1;
+      for (int r = 0; r < 4; ++r)
+        if (value == rules[r]) code = r;
+      if (code < 0) throw "--cluster-linkage: unknown rule '" + value + "' (guide, single, complete, average)";
+      o.cluster_linkage = code;
+      o.cluster_linkage_given = true;
+    }
     else if (name == "seed-nearest") o.seed_nearest = true;
     else if (name == "seed-nr") {
       size_t used = 0;
@@ -412,6 +427,7 @@ Options parse(int argc, char** argv) {
   if (!o.cluster_given && !o.cluster_count_given) {
     if (o.cluster_min_size_given || !o.cluster_table.empty() || !o.cluster_tree.empty())
       throw std::string("--cluster-min-size, --cluster-table and --cluster-tree need --cluster or --cluster-count");
+    if (o.cluster_linkage_given) throw std::string("--cluster-linkage needs --cluster or --cluster-count");
   } else {  // the clusters are runs of their own: nothing that reads or writes one run's whole state, and one FILE to cut
     for (const std::string& g : given) {
       const bool other_mode = g.compare(0, 4, "seed") == 0 || g.compare(0, 8, "pairwise") == 0 || g.compare(0, 7, "compare") == 0 ||
@@ -2057,7 +2073,8 @@ int run_pairwise(const Options& o, int align_model) {
 
 // `dafs --cluster T FILE` (pipeline.cluster is the Python twin).  The similarity scores of all pairs come
 // from dafs_hip_similarity, which walks the pairs in ranges under the library's budget and keeps no store; the guide tree of
-// the whole set is cut by dafs_host_cluster_cut; the clusters of at least --cluster-min-size members are the families of
+// the whole set (with --cluster-linkage single, complete or average the linkage tree of dafs_hip_linkage_tree, DESIGN.md section
+// 21) is cut by dafs_host_cluster_cut; the clusters of at least --cluster-min-size members are the families of
 // align_group, as the FILEs of a run of several are: those of two or more sequences in sub-batches under
 // dafs_host_batch_bytes() of dafs_host_family_bytes, a cluster of one sequence on the single-sequence path.  Each printed
 // cluster is "==> cluster c <==" and then what `dafs` prints for a file of its sequences.
@@ -2079,7 +2096,9 @@ int run_cluster(const Options& o, int align_model) {
   }
   std::vector<float> score(2 * N - 1);
   std::vector<int32_t> left(2 * N - 1), right(2 * N - 1);
-  check(dafs_host_build_tree(N, sim.data(), score.data(), left.data(), right.data()));
+  if (o.cluster_linkage == 0) check(dafs_host_build_tree(N, sim.data(), score.data(), left.data(), right.data()));
+  else if (N == 1) { score[0] = 0.0f; left[0] = right[0] = -1; }  // the one-leaf tree
+  else check_text(dafs_hip_linkage_tree(ctx, o.cluster_linkage, N, nullptr, score.data(), left.data(), right.data()));  // on the block the pass left on the device
   std::vector<uint32_t> labels(N);
   uint32_t K = 0;
   check_text(dafs_host_cluster_cut(N, score.data(), left.data(), right.data(), o.cluster_given ? DAFS_CLUSTER_THRESHOLD : DAFS_CLUSTER_COUNT,

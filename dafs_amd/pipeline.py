@@ -1233,7 +1233,7 @@ def _tree_line(score, left, right, names):
     return text[len(score) - 1]
 
 
-def cluster(names, seqs, threshold=None, count=None, min_size=1, ctx=None, max_bytes=None, **opts):
+def cluster(names, seqs, threshold=None, count=None, min_size=1, ctx=None, max_bytes=None, linkage="guide", **opts):
     """Cluster a mixed set of sequences into families and align each (`dafs --cluster`).  The N x N
     similarity matrix of the pair kernels (Context.similarity: the pairs in ranges under max_bytes, so that the set's
     posteriors are never held at once), the guide tree of the whole set (capi.build_tree) and its cut (capi.cluster_cut):
@@ -1241,9 +1241,11 @@ def cluster(names, seqs, threshold=None, count=None, min_size=1, ctx=None, max_b
     until that many clusters are left.  Exactly one of the two.  Every cluster of at least min_size members then goes through
     run_batch (sub-batches under max_bytes; default DEFAULT_BATCH_BYTES for both), so its Result is, bit for bit, what
     run(names_c, seqs_c, **opts) gives.  opts: the options of run() except mp / bp / shard / compare.  With w_pct_f the
-    clustering still reads the raw scores; -f acts inside each cluster's run.
+    clustering still reads the raw scores; -f acts inside each cluster's run.  linkage: "guide" cuts the guide tree
+    (capi.build_tree, on the host); "single", "complete" and "average" cut that linkage tree instead, joined on the device from
+    the similarity block the pass has just left there (Context.linkage_tree).
 
-    Returns an object with .sim, .tree = (score, left, right), .tree_line, .labels (uint32 [N]), .clusters (per cluster the
+    Returns an object with .linkage, .sim, .tree = (score, left, right), .tree_line, .labels (uint32 [N]), .clusters (per cluster the
     indices of its members, ascending; the clusters are numbered by their smallest member), .results (per cluster a Result,
     or None below min_size), .ranges (launches of the similarity pass), .table (the text of --cluster-table) and .seconds
     (similarity, tree, batch, total)."""
@@ -1275,6 +1277,8 @@ def cluster(names, seqs, threshold=None, count=None, min_size=1, ctx=None, max_b
         raise ValueError("pipeline.cluster: min_size must be a positive integer")
     if max_bytes is not None and int(max_bytes) <= 0:
         raise ValueError("pipeline.cluster: max_bytes must be positive")
+    if linkage not in capi.LINKAGES:
+        raise ValueError("pipeline.cluster: unknown linkage %r (one of %s)" % (linkage, ", ".join(capi.LINKAGES)))
     align_model, th_a = opts.get("align_model", known["align_model"]), opts.get("th_a", known["th_a"])
     own = ctx is None
     if own:
@@ -1288,7 +1292,13 @@ def cluster(names, seqs, threshold=None, count=None, min_size=1, ctx=None, max_b
             ctx.set_sequences(seqs)
             out.sim, out.ranges = ctx.similarity(align_model, th_a, max_bytes)
         t1 = time.perf_counter()
-        out.tree = capi.build_tree(out.sim)
+        out.linkage = linkage
+        if linkage == "guide":
+            out.tree = capi.build_tree(out.sim)
+        elif n == 1:  # the one-leaf tree
+            out.tree = (np.zeros(1, np.float32), np.full(1, -1, np.int64), np.full(1, -1, np.int64))
+        else:
+            out.tree = ctx.linkage_tree(linkage)
         out.labels, k = capi.cluster_cut(out.tree, threshold=threshold, count=None if count is None else int(count))
         out.clusters = [[] for _ in range(k)]
         for i, c in enumerate(out.labels):

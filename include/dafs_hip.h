@@ -270,6 +270,34 @@ enum { DAFS_CLUSTER_THRESHOLD = 0, DAFS_CLUSTER_COUNT = 1 };
 int dafs_host_cluster_cut(uint32_t n, const float* score, const int32_t* left, const int32_t* right, int mode, float threshold,
                           uint32_t count, uint32_t* labels, uint32_t* n_clusters);
 
+/* Single, complete and average linkage (UPGMA) of an n x n similarity matrix, joined on the device (no counterpart in the
+ * reference; the contract, to the bit; `dafs --cluster-linkage`, pipeline.cluster(linkage=...)).
+ * score/left/right: 2n-1 entries in the layout of dafs_host_build_tree, so dafs_host_cluster_cut and dafs_host_cluster_table
+ * take them unchanged.  Join t (node n + t) takes the pair of active slots a < b with the highest current similarity (compared
+ * as floats; among equals the smallest a, then the smallest b), and slot a then holds the joined cluster with, for every other
+ * active slot k, p = S(a,k), q = S(b,k): single p >= q ? p : q, complete p <= q ? p : q, average
+ * (float)(((double)n_a * p + (double)n_b * q) / (double)(n_a + n_b)).  Join scores never rise.
+ * sim: a host n x n matrix of which only the entries x < y are read, all of them finite; or NULL for the context's own
+ * similarity block (a one-family context of n sequences after dafs_hip_similarity, a full-pair-set dafs_hip_align_posteriors,
+ * dafs_hip_set_mp or dafs_hip_mp_install), read from its device copy without a download and left untouched, as are the stores.
+ * n = 1 gives the one-leaf tree without a launch.  n up to 65 536 (a working copy of n * n floats on the device).
+ * DAFS_HIP_EINVAL with a message in dafs_hip_last_error, outputs untouched and the context usable: a null pointer, an unknown
+ * linkage, n = 0 or above 65 536, a non-finite entry above the diagonal (no join runs), sim = NULL on a context without a
+ * similarity block, with several families or with another number of sequences.  DAFS_HIP_ENOMEM: the device allocation
+ * failed. */
+enum { DAFS_LINKAGE_SINGLE = 1, DAFS_LINKAGE_COMPLETE = 2, DAFS_LINKAGE_AVERAGE = 3 };
+int dafs_hip_linkage_tree(dafs_hip_ctx* ctx, int linkage, uint32_t n, const float* sim, float* score, int32_t* left, int32_t* right);
+/* L0 of the same (no counterpart in the reference): the caller's device matrix d_sim (n x n floats, the
+ * entries x < y read, left untouched), the caller's workspace of dafs_hipk_linkage_workspace(n) bytes (256-byte aligned; 0 for
+ * n = 0 or above 65 536) and device outputs of 2n-1 entries; two kernels on hip_stream, no allocation and no wait.  n >= 2.
+ * When the stream has drained the workspace begins with { uint32 nonfinite; uint32 joins; uint64 rescans }: nonfinite > 0 is
+ * the refusal of a non-finite entry above the diagonal, after which no join ran and only the leaves are written; otherwise
+ * joins = n - 1.  DAFS_HIP_LINKAGE_LDS=0 (read per call, here and in dafs_hip_linkage_tree) keeps the per-row state in the
+ * workspace at every n instead of in LDS up to n = 10 224; it changes no result. */
+size_t dafs_hipk_linkage_workspace(uint32_t n);
+int dafs_hipk_linkage(int linkage, uint32_t n, const float* d_sim, void* d_workspace, float* d_score, int32_t* d_left, int32_t* d_right,
+                      void* hip_stream);
+
 /* Host-side helper (no device work): the merge of `dafs --seed` and pipeline.add, k new sequences
  * placed into a fixed seed alignment of C columns.  lens: k sequence lengths; z: their column maps from the k nodes (leaf j
  * against the seed) concatenated, per residue a seed column or DAFS_HIP_NONE, the seed columns strictly increasing within
