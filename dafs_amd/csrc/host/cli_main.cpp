@@ -818,6 +818,25 @@ std::vector<std::string> lines_of(const std::string& joined, size_t n) {  // the
   return out;
 }
 
+std::vector<std::string> stockholm_names(const std::vector<std::string>& headers) {  // the Stockholm names of these headers
+  char* text = nullptr;
+  check_text(dafs_host_stockholm_names((uint32_t)headers.size(), c_strs(headers).data(), &text));
+  return lines_of(take(text), headers.size());
+}
+
+// The chunks of items of these estimated device bytes: greedy in order under dafs_host_batch_bytes(), an item over the budget
+// alone; [begin, end) each
+std::vector<std::pair<size_t, size_t> > chunks(const std::vector<uint64_t>& bytes) {
+  std::vector<uint32_t> chunk_of(bytes.size());
+  check(dafs_host_pack_greedy((uint32_t)bytes.size(), bytes.data(), dafs_host_batch_bytes(), chunk_of.data()));
+  std::vector<std::pair<size_t, size_t> > out;
+  for (size_t k = 0; k < bytes.size(); ++k) {
+    if (k == 0 || chunk_of[k] != chunk_of[k - 1]) out.push_back(std::make_pair(k, k));
+    out.back().second = k + 1;
+  }
+  return out;
+}
+
 // --covariation: the statistics of one printed alignment (dafs_hip_alignment_covariation).
 const double kCovEMax = 0.05;  // the cut of cov_SS_cons
 
@@ -838,17 +857,6 @@ void covariation_of(dafs_hip_ctx* ctx, const Options& o, const std::vector<std::
   check_text(dafs_host_covariation_table(n, L, code.data(), ss.data(), best.data(), bscore.data(), be.data(), pscore.data(), pe.data(),
                                          prow.data(), pcan.data(), ptyp.data(), &text));
   tsv = take(text);
-}
-
-void write_covariation(const std::string& file, const std::vector<std::string>& tables, const std::vector<std::string>* headers) {
-  std::ofstream os(file.c_str(), std::ios::binary);
-  if (!os.is_open()) throw "--covariation: cannot open " + file;
-  for (size_t k = 0; k < tables.size(); ++k) {
-    if (headers) os << "==> " << (*headers)[k] << " <==\n";
-    os << tables[k];
-  }
-  os.flush();
-  if (!os) throw "--covariation: cannot write " + file;
 }
 
 // --identity: how similar the rows of one printed alignment are (dafs_hip_alignment_identity, dafs_hip_alignment_weights;
@@ -897,6 +905,8 @@ void write_tables(const std::string& option, const std::string& file, const std:
   os.flush();
   if (!os) throw option + ": cannot write " + file;
 }
+
+void write_text(const std::string& option, const std::string& file, const std::string& text) { write_tables(option, file, {text}, nullptr); }
 
 void write_identity(const Options& o, const std::vector<IdentityText>& idt, const std::vector<std::string>* headers) {
   std::vector<std::string> tables, matrices;
@@ -1034,12 +1044,43 @@ void write_compare(const Options& o, const std::vector<CompareText>& cmp, const 
   if (!o.compare_matrix.empty()) write_tables("--compare-matrix", o.compare_matrix, matrices, headers);
 }
 
-void write_stockholm(const std::string& file, const std::vector<std::string>& blocks) {
-  std::ofstream os(file.c_str(), std::ios::binary);
-  if (!os.is_open()) throw "--stockholm: cannot open " + file;
-  for (const std::string& b : blocks) os << b;
-  os.flush();
-  if (!os) throw "--stockholm: cannot write " + file;
+// Everything one family (an input file, a cluster, a pair, a placement) produces: its text, printed as it is made or kept for
+// the block the run prints later, and the side outputs that are wanted of it
+enum : unsigned { kSto = 1, kCov = 2, kIdt = 4, kCmp = 8 };  // --stockholm, --covariation, --identity, --compare
+
+struct FamilyOut {
+  unsigned wanted = 0;
+  std::ostringstream text;
+  std::ostream* os = &text;  // &text, or &std::cout
+  std::string sto, cov;
+  IdentityText idt;
+  CompareText cmp;
+  FamilyOut() {}
+  FamilyOut(const FamilyOut&) = delete;  // os points into the record
+};
+
+std::vector<FamilyOut> records(size_t n, unsigned wanted) {
+  std::vector<FamilyOut> recs(n);
+  for (FamilyOut& r : recs) r.wanted = wanted;
+  return recs;
+}
+
+// the side outputs the options ask for; a mode that does not produce one of them clears its flag
+unsigned wanted_of(const Options& o) {
+  return (o.stockholm.empty() ? 0 : kSto) | (o.covariation.empty() ? 0 : kCov) | (o.identity.empty() ? 0 : kIdt) | (o.compare.empty() ? 0 : kCmp);
+}
+
+// The files of the wanted side outputs, one block or table per record in order; headers: a line "==> header <==" before every
+// record's table (the Stockholm blocks carry none)
+void write_outputs(const Options& o, unsigned wanted, const std::vector<FamilyOut>& recs, const std::vector<std::string>* headers) {
+  std::vector<std::string> sto, cov;
+  std::vector<IdentityText> idt;
+  std::vector<CompareText> cmp;
+  for (const FamilyOut& r : recs) { sto.push_back(r.sto); cov.push_back(r.cov); idt.push_back(r.idt); cmp.push_back(r.cmp); }
+  if (wanted & kSto) write_tables("--stockholm", o.stockholm, sto, nullptr);
+  if (wanted & kCov) write_tables("--covariation", o.covariation, cov, headers);
+  if (wanted & kIdt) write_identity(o, idt, headers);
+  if (wanted & kCmp) write_compare(o, cmp, headers);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1081,18 +1122,53 @@ void read_seed(const std::string& file, std::vector<std::string>& names, std::ve
   ss->resize(columns);
 }
 
-// the folding constraint of every seed row under the seed's structure (dafs_host_row_constraint)
-std::vector<std::string> seed_constraints(const std::vector<std::string>& srows, const std::vector<uint8_t>& smask, const VU& ss) {
-  const uint32_t C = (uint32_t)ss.size();
-  std::vector<std::string> out;
-  for (size_t r = 0; r < srows.size(); ++r) {
+// The seed of a run: its m rows over C columns as read_seed returns them, with --seed-structure its structure, and the rows
+// taken apart into the ungapped sequences and the row-major mask of the cells that hold a residue
+struct Seed {
+  std::vector<std::string> names, rows;
+  VU ss;
+  std::vector<Fasta> fa;
+  std::vector<uint8_t> mask;
+  std::vector<uint32_t> lens;
+  uint32_t m = 0, C = 0;
+};
+
+Seed load_seed(const Options& o) {
+  Seed sd;
+  read_seed(o.seed, sd.names, sd.rows, o.seed_structure ? &sd.ss : nullptr);
+  sd.m = (uint32_t)sd.rows.size();
+  sd.C = (uint32_t)sd.rows[0].size();
+  sd.mask.assign((size_t)sd.m * sd.C, 0);
+  for (uint32_t r = 0; r < sd.m; ++r) {
     std::string sq;
-    for (char ch : srows[r])
-      if (ch != '-') sq += ch;
-    std::vector<char> buf(sq.size() + 1);
-    check(dafs_host_row_constraint(C, smask.data() + r * C, ss.data(), sq.c_str(), buf.data()));
-    out.push_back(buf.data());
+    for (uint32_t c = 0; c < sd.C; ++c)
+      if (sd.rows[r][c] != '-') { sq += sd.rows[r][c]; sd.mask[(size_t)r * sd.C + c] = 1; }
+    sd.fa.push_back(Fasta(sd.names[r], sq));
+    sd.lens.push_back((uint32_t)sq.size());
   }
+  return sd;
+}
+
+// --seed-structure: the folding constraints of a context that holds the seed's sequences and then k new ones -- every seed row
+// under the seed's structure (dafs_host_row_constraint), nullptr (a free fold) for the new ones.  Without --seed-structure, empty.
+struct Constraints {
+  std::vector<std::string> text;
+  std::vector<const char*> ptr;  // into text
+  Constraints() {}
+  Constraints(const Constraints&) = delete;
+  Constraints(Constraints&&) = default;  // a moved vector keeps its strings where they are
+};
+
+Constraints seed_constraints(const Options& o, const Seed& sd, uint32_t k) {
+  Constraints out;
+  if (!o.seed_structure) return out;
+  for (uint32_t r = 0; r < sd.m; ++r) {
+    std::vector<char> buf(sd.lens[r] + 1);
+    check(dafs_host_row_constraint(sd.C, sd.mask.data() + (size_t)r * sd.C, sd.ss.data(), sd.fa[r].seq().c_str(), buf.data()));
+    out.text.push_back(buf.data());
+  }
+  for (const std::string& s : out.text) out.ptr.push_back(s.c_str());
+  out.ptr.resize(sd.m + k, nullptr);
   return out;
 }
 
@@ -1102,6 +1178,43 @@ VU carry_structure(const VU& ss, const std::vector<uint32_t>& seed_col, uint32_t
   for (size_t c = 0; c < ss.size(); ++c)
     if (ss[c] != DAFS_HIP_NONE) out[seed_col[c]] = seed_col[ss[c]];
   return out;
+}
+
+// Where dafs_host_merge_added places k new sequences (lens; zs: each one's map onto the seed's columns, from its node) into
+// the seed: the merged column of every seed column and of every new residue (one sequence after another), the merged width,
+// and the RF mask (1: a seed column)
+struct Placement {
+  std::vector<uint32_t> seed_col, res_col;
+  uint32_t width = 0;
+  std::vector<uint8_t> rf;
+};
+
+Placement place(const Seed& sd, uint32_t k, const uint32_t* lens, const VU* zs) {
+  Placement p;
+  std::vector<uint32_t> z;
+  for (uint32_t j = 0; j < k; ++j) z.insert(z.end(), zs[j].begin(), zs[j].end());
+  p.seed_col.resize(sd.C);
+  p.res_col.resize(z.size() ? z.size() : 1);
+  check(dafs_host_merge_added(sd.C, k, lens, z.data(), p.seed_col.data(), p.res_col.data(), &p.width));
+  p.rf.assign(p.width, 0);
+  for (uint32_t c = 0; c < sd.C; ++c) p.rf[p.seed_col[c]] = 1;
+  return p;
+}
+
+// the placed alignment: the k new rows (sequences new_first, new_first + 1, ...), then the seed rows (seed_first, ...)
+ALN placed_rows(const Seed& sd, const Placement& p, uint32_t k, const uint32_t* lens, uint32_t new_first, uint32_t seed_first) {
+  ALN aln;
+  for (uint32_t j = 0, off = 0; j < k; off += lens[j], ++j) {
+    std::vector<bool> msk(p.width, false);
+    for (uint32_t i = 0; i < lens[j]; ++i) msk[p.res_col[off + i]] = true;
+    aln.push_back(std::make_pair(new_first + j, msk));
+  }
+  for (uint32_t r = 0; r < sd.m; ++r) {
+    std::vector<bool> msk(p.width, false);
+    for (uint32_t c = 0; c < sd.C; ++c) msk[p.seed_col[c]] = sd.mask[(size_t)r * sd.C + c] != 0;
+    aln.push_back(std::make_pair(seed_first + r, msk));
+  }
+  return aln;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1268,12 +1381,6 @@ struct PairChunk {
   std::vector<uint32_t> iterations;
 };
 
-int align_group(dafs_hip_ctx* ctx, const Options& o, Ranks& rk, int align_model, const std::vector<std::vector<Fasta> >& fams,
-                const std::vector<size_t>& members, const std::vector<std::ostream*>& out, const std::vector<std::string*>& sto,
-                PairChunk* pc = nullptr, const std::vector<std::string*>& cov = std::vector<std::string*>(),
-                const std::vector<IdentityText*>& idt = std::vector<IdentityText*>(),
-                const std::vector<CompareText*>& cmp = std::vector<CompareText*>());
-
 struct Guard {  // the context of a run, destroyed however the run ends
   dafs_hip_ctx* c;
   ~Guard() { dafs_hip_destroy(c); }
@@ -1341,71 +1448,76 @@ dafs_dd_params dd_params_of(const Options& o) {
   return prm;
 }
 
+// Many alignments as the library's batched calls take them: per alignment its rows and columns, then every alignment's
+// sequence indices and row-major mask, one alignment after another
+struct Packed {
+  std::vector<uint32_t> n_rows, len, seq;
+  std::vector<uint8_t> mask;
+};
+
+Packed pack(const std::vector<const ALN*>& alns) {
+  Packed p;
+  std::vector<uint32_t> rs;
+  std::vector<uint8_t> rm;
+  for (const ALN* a : alns) {
+    flatten(*a, rs, rm);
+    p.n_rows.push_back((uint32_t)a->size());
+    p.len.push_back((uint32_t)(*a)[0].second.size());
+    p.seq.insert(p.seq.end(), rs.begin(), rs.end());
+    p.mask.insert(p.mask.end(), rm.begin(), rm.end());
+  }
+  return p;
+}
+
+// where each part of a flat result begins: part k of these lengths is [at[k], at[k + 1])
+std::vector<size_t> starts_of(const std::vector<uint32_t>& len) {
+  std::vector<size_t> at(1, 0);
+  for (uint32_t l : len) at.push_back(at.back() + l);
+  return at;
+}
+
+VU concat(const std::vector<VU>& parts) {
+  VU all;
+  for (const VU& p : parts) all.insert(all.end(), p.begin(), p.end());
+  return all;
+}
+
 // The first decode of many final alignments in one library call (dafs_hip_consensus_structures): ss[k] of *alns[k], decoded
 // over the rows in the order each holds them.
 void consensus_structures(dafs_hip_ctx* ctx, const std::vector<const ALN*>& alns, float th, std::vector<VU>& ss) {
-  std::vector<uint32_t> n_rows, len, seq, all;
-  std::vector<uint8_t> mask;
-  for (const ALN* a : alns) {
-    std::vector<uint32_t> rs;
-    std::vector<uint8_t> rm;
-    flatten(*a, rs, rm);
-    n_rows.push_back((uint32_t)a->size());
-    len.push_back((uint32_t)(*a)[0].second.size());
-    seq.insert(seq.end(), rs.begin(), rs.end());
-    mask.insert(mask.end(), rm.begin(), rm.end());
-  }
-  size_t total = 0;
-  for (uint32_t l : len) total += l;
-  all.resize(total ? total : 1);
-  check(dafs_hip_consensus_structures(ctx, (uint32_t)alns.size(), n_rows.data(), len.data(), seq.data(), mask.data(), th, all.data(), nullptr));
+  const Packed p = pack(alns);
+  const std::vector<size_t> at = starts_of(p.len);
+  VU all(at.back() ? at.back() : 1);
+  check(dafs_hip_consensus_structures(ctx, (uint32_t)alns.size(), p.n_rows.data(), p.len.data(), p.seq.data(), p.mask.data(), th, all.data(), nullptr));
   ss.clear();
-  size_t at = 0;
-  for (uint32_t l : len) {
-    ss.push_back(VU(all.begin() + at, all.begin() + at + l));
-    at += l;
-  }
+  for (size_t k = 0; k < alns.size(); ++k) ss.push_back(VU(all.begin() + at[k], all.begin() + at[k + 1]));
 }
 
 // The structure support of every row of many alignments in one library call (dafs_hip_structure_support): the rows of *alns[0]
 // in the order it holds them, then those of *alns[1], ...
 void structure_support(dafs_hip_ctx* ctx, const std::vector<const ALN*>& alns, const std::vector<VU>& ss, std::vector<uint32_t>& both,
                        std::vector<uint32_t>& canonical, std::vector<uint32_t>& half, std::vector<double>& expected) {
-  std::vector<uint32_t> n_rows, len, seq, all;
-  std::vector<uint8_t> mask;
-  for (size_t k = 0; k < alns.size(); ++k) {
-    std::vector<uint32_t> rs;
-    std::vector<uint8_t> rm;
-    flatten(*alns[k], rs, rm);
-    n_rows.push_back((uint32_t)alns[k]->size());
-    len.push_back((uint32_t)(*alns[k])[0].second.size());
-    seq.insert(seq.end(), rs.begin(), rs.end());
-    mask.insert(mask.end(), rm.begin(), rm.end());
-    all.insert(all.end(), ss[k].begin(), ss[k].end());
-  }
-  both.assign(seq.size(), 0); canonical.assign(seq.size(), 0); half.assign(seq.size(), 0); expected.assign(seq.size(), 0.0);
-  check(dafs_hip_structure_support(ctx, (uint32_t)alns.size(), n_rows.data(), len.data(), seq.data(), mask.data(), all.data(), both.data(),
+  const Packed p = pack(alns);
+  const VU all = concat(ss);
+  both.assign(p.seq.size(), 0); canonical.assign(p.seq.size(), 0); half.assign(p.seq.size(), 0); expected.assign(p.seq.size(), 0.0);
+  check(dafs_hip_structure_support(ctx, (uint32_t)alns.size(), p.n_rows.data(), p.len.data(), p.seq.data(), p.mask.data(), all.data(), both.data(),
                                    canonical.data(), half.data(), expected.data()));
 }
 
-// --row-structures: the structure of every listed sequence alone -- its one-row alignment decoded from the base-pairing
-// store the progressive phase read, at the threshold of SS_cons -- all in one library call
-std::map<uint32_t, VU> row_structures(dafs_hip_ctx* ctx, const std::vector<Fasta>& fa, const std::vector<uint32_t>& seqs, float th) {
-  std::vector<uint32_t> n_rows(seqs.size(), 1), len, all;
-  size_t total = 0;
-  for (uint32_t x : seqs) {
-    len.push_back((uint32_t)fa[x].size());
-    total += fa[x].size();
+// --row-structures: the structure of every sequence of the context alone -- its one-row alignment decoded from the base-pairing
+// store the progressive phase read, at the threshold of SS_cons -- all in one library call; indexed by sequence
+std::vector<VU> row_structures(dafs_hip_ctx* ctx, const std::vector<Fasta>& fa, float th) {
+  std::vector<uint32_t> n_rows(fa.size(), 1), len, seqs;
+  for (const Fasta& s : fa) {
+    seqs.push_back((uint32_t)seqs.size());
+    len.push_back((uint32_t)s.size());
   }
-  const std::vector<uint8_t> mask(total ? total : 1, 1);
-  all.resize(total ? total : 1);
+  const std::vector<size_t> at = starts_of(len);
+  const std::vector<uint8_t> mask(at.back() ? at.back() : 1, 1);
+  VU all(at.back() ? at.back() : 1);
   check(dafs_hip_consensus_structures(ctx, (uint32_t)seqs.size(), n_rows.data(), len.data(), seqs.data(), mask.data(), th, all.data(), nullptr));
-  std::map<uint32_t, VU> out;
-  size_t at = 0;
-  for (size_t k = 0; k < seqs.size(); ++k) {
-    out[seqs[k]] = VU(all.begin() + at, all.begin() + at + len[k]);
-    at += len[k];
-  }
+  std::vector<VU> out;
+  for (size_t k = 0; k < seqs.size(); ++k) out.push_back(VU(all.begin() + at[k], all.begin() + at[k + 1]));
   return out;
 }
 
@@ -1436,35 +1548,25 @@ struct Reliability {
 };
 void reliabilities(dafs_hip_ctx* ctx, const std::vector<Fasta>& fa, const std::vector<const ALN*>& alns, const std::vector<VU>& ss,
                    bool first_row_only, std::vector<Reliability>& out) {
-  std::vector<uint32_t> n_rows, len, seq, all_ss;
-  std::vector<uint8_t> mask, want;
-  std::vector<uint32_t> rs;
-  std::vector<uint8_t> rm;
-  out.assign(alns.size(), Reliability());
-  size_t residues = 0;
-  for (size_t k = 0; k < alns.size(); ++k) {
-    flatten(*alns[k], rs, rm);
-    n_rows.push_back((uint32_t)alns[k]->size());
-    len.push_back((uint32_t)(*alns[k])[0].second.size());
-    seq.insert(seq.end(), rs.begin(), rs.end());
-    mask.insert(mask.end(), rm.begin(), rm.end());
-    all_ss.insert(all_ss.end(), ss[k].begin(), ss[k].end());
-    for (size_t r = 0; r < rs.size(); ++r) {
+  const Packed p = pack(alns);
+  const VU all_ss = concat(ss);
+  std::vector<uint8_t> want;
+  std::vector<uint32_t> residues;  // per alignment, over its rows
+  for (const ALN* a : alns) {
+    residues.push_back(0);
+    for (size_t r = 0; r < a->size(); ++r) {
       want.push_back(r == 0 || !first_row_only ? 1 : 0);
-      residues += fa[rs[r]].size();
+      residues.back() += fa[(*a)[r].first].size();
     }
   }
-  std::vector<double> rel(residues ? residues : 1), col(all_ss.size() ? all_ss.size() : 1);
-  check(dafs_hip_alignment_reliabilities(ctx, (uint32_t)alns.size(), n_rows.data(), len.data(), seq.data(), mask.data(), all_ss.data(),
+  const std::vector<size_t> at = starts_of(residues), col_at = starts_of(p.len);
+  std::vector<double> rel(at.back() ? at.back() : 1), col(all_ss.size() ? all_ss.size() : 1);
+  check(dafs_hip_alignment_reliabilities(ctx, (uint32_t)alns.size(), p.n_rows.data(), p.len.data(), p.seq.data(), p.mask.data(), all_ss.data(),
                                          first_row_only ? want.data() : nullptr, -1, -1, rel.data(), col.data(), nullptr, nullptr, nullptr));
-  size_t at = 0, col_at = 0;
+  out.assign(alns.size(), Reliability());
   for (size_t k = 0; k < alns.size(); ++k) {
-    size_t tot = 0;
-    for (const auto& row : *alns[k]) tot += fa[row.first].size();
-    out[k].rel.assign(rel.begin() + at, rel.begin() + at + tot);
-    out[k].col.assign(col.begin() + col_at, col.begin() + col_at + len[k]);
-    at += tot;
-    col_at += len[k];
+    out[k].rel.assign(rel.begin() + at[k], rel.begin() + at[k + 1]);
+    out[k].col.assign(col.begin() + col_at[k], col.begin() + col_at[k + 1]);
   }
 }
 
@@ -1481,60 +1583,46 @@ std::vector<std::string> row_texts(const std::vector<Fasta>& fa, const ALN& aln)
   return rows;
 }
 
-// The output of a final alignment with its final structure ss_final (:1876-1879, :1584-1601) on os: ">SS_cons", the brackets,
-// then the rows sorted by sequence index.  fa: the context's sequences; ff: the family's, its first one at index first.  With
-// sto, also the family's Stockholm block from rl (reliabilities, made while root held its rows in the present order): tree_line
-// (nullptr: no CC line), rf (nullptr: no RF line).  With cov (--covariation), the alignment's covariation table into *cov, and
-// its cov_SS_cons line into the Stockholm block.  row_ss (--row-structures): per sequence of the alignment its own structure
-// (row_structures), written as the block's #=GR SS lines.
-void finish_alignment(dafs_hip_ctx* ctx, const Options& o, const std::vector<Fasta>& fa, ALN& root, const std::vector<Fasta>& ff,
-                      uint32_t first, std::ostream& os, std::string* sto, const std::string* tree_line, const std::vector<uint8_t>* rf,
-                      std::string* cov, const VU& ss_final, const Reliability* rl, const std::map<uint32_t, VU>* row_ss = nullptr,
-                      IdentityText* idt = nullptr, CompareText* cmp = nullptr) {
-  std::string str;
-  std::map<uint32_t, size_t> rel_at;  // sequence -> its first residue in rl->rel
-  {
-    const uint32_t L = (uint32_t)root[0].second.size();
-    std::vector<char> buf(L + 1);
-    dafs_hip_make_brackets(L, ss_final.data(), buf.data());
-    str.assign(buf.data());
-    size_t tot = 0;
-    for (const auto& row : root) { rel_at[row.first] = tot; tot += fa[row.first].size(); }
-  }
+// The output of a final alignment with its final structure ss_final (:1876-1879, :1584-1601) on *out.os: ">SS_cons", the
+// brackets, then the rows sorted by sequence index.  fa: the context's sequences, the family's from index first on, one per
+// row.  What out.wanted asks for goes into out: the family's Stockholm block from rl (reliabilities, made while root held its
+// rows in the present order) with tree_line (nullptr: no CC line), rf (nullptr: no RF line) and row_ss (--row-structures,
+// nullptr without: per sequence of the context its own structure, row_structures, written as the block's #=GR SS lines); the
+// covariation table, whose cov_SS_cons line joins the block; the identity tables, whose weights join the block; the comparison.
+void finish_alignment(dafs_hip_ctx* ctx, const Options& o, const std::vector<Fasta>& fa, ALN& root, uint32_t first, FamilyOut& out,
+                      const std::string* tree_line, const std::vector<uint8_t>* rf, const VU& ss_final, const Reliability& rl,
+                      const std::vector<VU>* row_ss) {
+  const uint32_t L = (uint32_t)root[0].second.size();
+  std::vector<char> str(L + 1);
+  dafs_hip_make_brackets(L, ss_final.data(), str.data());
+  std::map<uint32_t, size_t> rel_at;  // sequence -> its first residue in rl.rel
+  size_t tot = 0;
+  for (const auto& row : root) { rel_at[row.first] = tot; tot += fa[row.first].size(); }
 
   // output (:1876-1879, :1584-1601)
   std::sort(root.begin(), root.end());
-  os << ">SS_cons" << std::endl << str << std::endl;
-  std::vector<std::string> rows;
-  for (const auto& row : root) {
-    const std::string& sq = fa[row.first].seq();
-    os << "> " << fa[row.first].name() << std::endl;
-    std::string text(row.second.size(), '-');
-    for (uint j = 0, k = 0; j != row.second.size(); ++j)
-      if (row.second[j]) text[j] = sq[k++];
-    os << text << std::endl;
-    rows.push_back(text);
-  }
+  std::ostream& os = *out.os;
+  os << ">SS_cons" << std::endl << str.data() << std::endl;
+  const std::vector<std::string> rows = row_texts(fa, root);
+  for (size_t r = 0; r < root.size(); ++r) os << "> " << fa[root[r].first].name() << std::endl << rows[r] << std::endl;
   std::string cov_chars;
-  if (cov) covariation_of(ctx, o, rows, ss_final, *cov, cov_chars);
+  if (out.wanted & kCov) covariation_of(ctx, o, rows, ss_final, out.cov, cov_chars);
   std::vector<std::string> names;  // the printed rows' Stockholm names
-  if (sto || idt || cmp) {
+  if (out.wanted & (kSto | kIdt | kCmp)) {
     std::vector<std::string> headers;
-    for (const Fasta& s : ff) headers.push_back(s.name());
-    char* text = nullptr;
-    check_text(dafs_host_stockholm_names((uint32_t)headers.size(), c_strs(headers).data(), &text));
-    const std::vector<std::string> all_names = lines_of(take(text), headers.size());
+    for (size_t i = 0; i < root.size(); ++i) headers.push_back(fa[first + i].name());
+    const std::vector<std::string> all_names = stockholm_names(headers);
     for (const auto& row : root) names.push_back(all_names[row.first - first]);
   }
-  if (idt) identity_of(ctx, names, rows, !o.identity_matrix.empty(), *idt);
-  if (cmp) compare_of(ctx, o, names, rows, &ss_final, nullptr, nullptr, *cmp);
-  if (sto) {
+  if (out.wanted & kIdt) identity_of(ctx, names, rows, !o.identity_matrix.empty(), out.idt);
+  if (out.wanted & kCmp) compare_of(ctx, o, names, rows, &ss_final, nullptr, nullptr, out.cmp);
+  if (out.wanted & kSto) {
     char* text = nullptr;
     std::vector<const double*> rr;
-    for (const auto& row : root) rr.push_back(rl->rel.data() + rel_at[row.first]);
+    for (const auto& row : root) rr.push_back(rl.rel.data() + rel_at[row.first]);
     std::vector<std::string> rss;  // each row's own structure in the row's columns
     for (size_t r = 0; row_ss && r < root.size(); ++r) {
-      const VU& own = row_ss->at(root[r].first);
+      const VU& own = (*row_ss)[root[r].first];
       std::vector<char> buf(own.size() + 1);
       dafs_hip_make_brackets((uint32_t)own.size(), own.data(), buf.data());
       std::string line(rows[r].size(), '.');
@@ -1542,14 +1630,14 @@ void finish_alignment(dafs_hip_ctx* ctx, const Options& o, const std::vector<Fas
         if (rows[r][c] != '-') line[c] = buf[k++];
       rss.push_back(line);
     }
-    check_text(dafs_host_stockholm_block_rows(tree_line ? tree_line->c_str() : nullptr, (uint32_t)rows.size(), (uint32_t)rl->col.size(),
-                                              c_strs(names).data(), c_strs(rows).data(), rr.data(), rl->col.data(), str.c_str(),
-                                              rf ? rf->data() : nullptr, cov ? cov_chars.c_str() : nullptr,
+    check_text(dafs_host_stockholm_block_rows(tree_line ? tree_line->c_str() : nullptr, (uint32_t)rows.size(), (uint32_t)rl.col.size(),
+                                              c_strs(names).data(), c_strs(rows).data(), rr.data(), rl.col.data(), str.data(),
+                                              rf ? rf->data() : nullptr, (out.wanted & kCov) ? cov_chars.c_str() : nullptr,
                                               row_ss ? c_strs(rss).data() : nullptr, &text));
-    *sto = take(text);
-    if (idt) {  // --identity: the sequence weights as #=GS WT lines
-      check_text(dafs_host_stockholm_weights(sto->c_str(), (uint32_t)names.size(), c_strs(names).data(), idt->weight.data(), &text));
-      *sto = take(text);
+    out.sto = take(text);
+    if (out.wanted & kIdt) {  // --identity: the sequence weights as #=GS WT lines
+      check_text(dafs_host_stockholm_weights(out.sto.c_str(), (uint32_t)names.size(), c_strs(names).data(), out.idt.weight.data(), &text));
+      out.sto = take(text);
     }
   }
 }
@@ -1571,772 +1659,15 @@ struct FreshRand {
   }
 };
 
-// `dafs --seed SEED FILE` (DESIGN.md section 11; pipeline.add is the Python twin).  The context holds the seed's m sequences
-// in seed order and then FILE's k.  Phase 1 is a normal run's over all of them; one node per new sequence j, its leaf (left)
-// against the seed (right), and all k go through the resident-node rounds together; dafs_host_merge_added places them into
-// the seed; the structure is decoded over the rows new sequences, then seed rows, as in a run whose tree joins a leaf last.
-int run_add(const Options& o, int align_model) {
-  std::vector<std::string> snames, srows;
-  VU seed_ss;
-  read_seed(o.seed, snames, srows, o.seed_structure ? &seed_ss : nullptr);
-  std::vector<Fasta> added;
-  Fasta::load(added, o.input.c_str());
-  if (added.empty()) throw "no sequences in the input";
-  const uint32_t m = (uint32_t)srows.size(), k = (uint32_t)added.size(), C = (uint32_t)srows[0].size();
-  std::vector<Fasta> fa;
-  std::vector<uint8_t> smask((size_t)m * C, 0);
-  for (uint32_t r = 0; r < m; ++r) {
-    std::string sq;
-    for (uint32_t c = 0; c < C; ++c)
-      if (srows[r][c] != '-') { sq += srows[r][c]; smask[(size_t)r * C + c] = 1; }
-    fa.push_back(Fasta(snames[r], sq));
-  }
-  fa.insert(fa.end(), added.begin(), added.end());
-
-  dafs_hip_ctx* ctx = nullptr;
-  check(dafs_hip_create(o.device, &ctx));
-  Guard guard{ctx};
-  set_sequences(ctx, fa);
-  std::vector<float> sim;
-  std::vector<std::string> cons;  // --seed-structure: the seed rows under their constraints, the new sequences free
-  std::vector<const char*> cons_ptr;
-  if (o.seed_structure) {
-    cons = seed_constraints(srows, smask, seed_ss);
-    for (const std::string& s : cons) cons_ptr.push_back(s.c_str());
-    cons_ptr.resize(m + k, nullptr);
-  }
-  phase1_local(ctx, o, align_model, fa, {0, m + k}, sim, nullptr, o.seed_structure ? &cons_ptr : nullptr);
-
-  // the k nodes: all opened in the first round
-  dafs_dd_params prm = dd_params_of(o);
-  prm.skip_uncoupled_folds = o.verbose == 0 ? 1 : 0;  // as the progressive loop of a run without -r
-  std::vector<uint32_t> seed_idx(m), lens(k);
-  for (uint32_t r = 0; r < m; ++r) seed_idx[r] = r;
-  for (uint32_t j = 0; j < k; ++j) lens[j] = added[j].size();
-  std::vector<VU> zs(k);
-  bool opened = false;
-  run_rounds(ctx, prm, o.verbose, [&]() {
-    std::vector<std::pair<size_t, NodeJob> > ready(opened ? 0 : k);
-    for (uint32_t j = 0; j < ready.size(); ++j) {
-      NodeJob& jb = ready[j].second;
-      ready[j].first = j;
-      jb.s1.assign(1, m + j);
-      jb.m1.assign(lens[j], 1);
-      jb.s2 = seed_idx;
-      jb.m2 = smask;
-      node_job(ctx, jb, false, prm.th_s);
-    }
-    opened = true;
-    return ready;
-  }, [&](size_t j, NodeJob& jb) { zs[j].swap(jb.z); });
-
-  // the merge; the rows new sequences (file order), then seed rows (seed order)
-  std::vector<uint32_t> z, seed_col(C), res_col;
-  for (uint32_t j = 0; j < k; ++j) z.insert(z.end(), zs[j].begin(), zs[j].end());
-  res_col.resize(z.size() ? z.size() : 1);
-  uint32_t width = 0;
-  check(dafs_host_merge_added(C, k, lens.data(), z.data(), seed_col.data(), res_col.data(), &width));
-  ALN root;
-  for (uint32_t j = 0, off = 0; j < k; off += lens[j], ++j) {
-    std::vector<bool> msk(width, false);
-    for (uint32_t i = 0; i < lens[j]; ++i) msk[res_col[off + i]] = true;
-    root.push_back(std::make_pair(m + j, msk));
-  }
-  for (uint32_t r = 0; r < m; ++r) {
-    std::vector<bool> msk(width, false);
-    for (uint32_t c = 0; c < C; ++c) msk[seed_col[c]] = smask[(size_t)r * C + c] != 0;
-    root.push_back(std::make_pair(r, msk));
-  }
-  std::vector<uint8_t> rf(width, 0);
-  for (uint32_t c = 0; c < C; ++c) rf[seed_col[c]] = 1;
-  std::string sto, cov;
-  IdentityText idt;
-  CompareText cmp;
-  std::map<uint32_t, VU> row_ss;
-  if (o.row_structures) {
-    std::vector<uint32_t> every(m + k);
-    for (uint32_t x = 0; x < m + k; ++x) every[x] = x;
-    row_ss = row_structures(ctx, fa, every, o.fold_th1[0]);
-  }
-  VU carried;  // --seed-structure: nothing is decoded
-  if (o.seed_structure) carried = carry_structure(seed_ss, seed_col, width);
-  const VU ss = final_structure(ctx, o, root, o.seed_structure ? &carried : nullptr);
-  std::vector<Reliability> rl(1);
-  if (!o.stockholm.empty()) reliabilities(ctx, fa, {&root}, {ss}, false, rl);
-  finish_alignment(ctx, o, fa, root, fa, 0, std::cout, o.stockholm.empty() ? nullptr : &sto, nullptr, &rf, o.covariation.empty() ? nullptr : &cov,
-                   ss, &rl[0], o.row_structures ? &row_ss : nullptr, o.identity.empty() ? nullptr : &idt, o.compare.empty() ? nullptr : &cmp);
-  std::cout.flush();
-  if (!o.stockholm.empty()) write_stockholm(o.stockholm, {sto});
-  if (!o.covariation.empty()) write_covariation(o.covariation, {cov}, nullptr);
-  if (!o.identity.empty()) write_identity(o, {idt}, nullptr);
-  if (!o.compare.empty()) write_compare(o, {cmp}, nullptr);
-  return 0;
-}
-
-// `dafs --seed SEED --seed-each FILE` (DESIGN.md section 15; pipeline.add_each is the Python twin): every sequence of FILE added
-// to the seed as run_add adds a file of that sequence alone.  Phase 1 runs once in a source context over the seed's m sequences
-// and then FILE's k: the folds and the posteriors of the pairs with a seed sequence on the left, no transform.  The new
-// sequences go in chunks under dafs_host_batch_bytes() (dafs_host_seed_each_bytes each) through a second context, where
-// dafs_hip_families_from gathers the chunk's families seed + [new]; then the transforms -- the matching transform for the pairs
-// (seed, new) alone unless --stockholm's reliabilities read the seed-seed rows --, one node per family in shared rounds,
-// run_add's merge per family and the structures of the chunk in one call.  --seed-merged: the placements' maps are kept, and
-// after the last chunk dafs_host_merge_added places all k into the seed at once.
-int run_add_each(const Options& o, int align_model) {
-  std::vector<std::string> snames, srows;
-  VU seed_ss;
-  read_seed(o.seed, snames, srows, o.seed_structure ? &seed_ss : nullptr);
-  std::vector<Fasta> added;
-  Fasta::load(added, o.input.c_str());
-  if (added.empty()) throw "no sequences in the input";
-  const uint32_t m = (uint32_t)srows.size(), k = (uint32_t)added.size(), C = (uint32_t)srows[0].size(), n = m + 1;
-  std::vector<Fasta> seed;
-  std::vector<uint8_t> smask((size_t)m * C, 0);
-  std::vector<uint32_t> seed_lens(m), lens(k);
-  for (uint32_t r = 0; r < m; ++r) {
-    std::string sq;
-    for (uint32_t c = 0; c < C; ++c)
-      if (srows[r][c] != '-') { sq += srows[r][c]; smask[(size_t)r * C + c] = 1; }
-    seed.push_back(Fasta(snames[r], sq));
-    seed_lens[r] = (uint32_t)sq.size();
-  }
-  for (uint32_t j = 0; j < k; ++j) lens[j] = added[j].size();
-
-  dafs_hip_ctx* src = nullptr;
-  check(dafs_hip_create(o.device, &src));
-  Guard src_guard{src};
-  {
-    std::vector<Fasta> all(seed);
-    all.insert(all.end(), added.begin(), added.end());
-    set_sequences(src, all);
-  }
-  {  // --seed-structure: the seed rows under their constraints, the new sequences free, once for every chunk
-    std::vector<std::string> cons;
-    std::vector<const char*> cons_ptr;
-    if (o.seed_structure) {
-      cons = seed_constraints(srows, smask, seed_ss);
-      for (const std::string& s : cons) cons_ptr.push_back(s.c_str());
-      cons_ptr.resize(m + k, nullptr);
-    }
-    check(dafs_hip_fold_posteriors_constrained_begin(src, DAFS_FOLD_CONTRAFOLD, kCutoff, o.seed_structure ? cons_ptr.data() : nullptr));
-  }
-  // the pairs (x, y) with x < m are the first m (m + k) - m (m + 1) / 2 pair ids
-  const int rc_align = dafs_hip_align_posteriors(src, align_model, o.align_th, 0, (uint64_t)m * (m + k) - (uint64_t)m * (m + 1) / 2);
-  const int rc_fold = dafs_hip_fold_posteriors_end(src);
-  check(rc_align);
-  check(rc_fold);
-  dafs_hip_ctx* ctx = nullptr;
-  check(dafs_hip_create(o.device, &ctx));
-  Guard guard{ctx};
-
-  std::vector<uint64_t> bytes(k);
-  for (uint32_t j = 0; j < k; ++j) bytes[j] = dafs_host_seed_each_bytes(m, seed_lens.data(), C, lens[j]);
-  std::vector<uint32_t> chunk_of(k);
-  check(dafs_host_pack_greedy(k, bytes.data(), dafs_host_batch_bytes(), chunk_of.data()));
-  dafs_dd_params prm = dd_params_of(o);
-  prm.skip_uncoupled_folds = o.verbose == 0 ? 1 : 0;  // as run_add
-  const bool listed = o.stockholm.empty() && o.align_pct != 0.0f;  // the reliabilities of --stockholm read the seed-seed rows
-  std::vector<uint32_t> matched(k, 0);
-  std::vector<double> score(k, 0.0);
-  std::vector<int64_t> iterations(k, 0);
-  std::vector<uint32_t> sup_both(k, 0), sup_can(k, 0), sup_half(k, 0);  // --seed-structure: the support of each new sequence's row
-  std::vector<double> sup_exp(k, 0.0);
-  std::vector<uint32_t> near_row(k, DAFS_HIP_NONE);  // --seed-nearest: per new sequence its nearest seed row and the identity to it
-  std::vector<double> near_pid(k, std::nan(""));
-  std::vector<std::string> sto_blocks, cov_tables, cov_headers;
-  std::vector<VU> all_z(k);                     // --seed-merged: every placement's map, kept until the last chunk is done,
-  std::vector<std::vector<double> > new_pp(k);  // and the residue values of its row in its own family
-  for (uint32_t j0 = 0; j0 < k;) {
-    uint32_t j1 = j0;
-    while (j1 < k && chunk_of[j1] == chunk_of[j0]) ++j1;
-    const uint32_t nf = j1 - j0;
-    // family f: the seed's sequences at f n .. f n + m - 1, the new one at f n + m
-    std::vector<uint32_t> first(nf + 1), member;
-    std::vector<Fasta> fa;
-    for (uint32_t f = 0; f < nf; ++f) {
-      first[f] = f * n;
-      for (uint32_t r = 0; r < m; ++r) member.push_back(r);
-      member.push_back(m + j0 + f);
-      fa.insert(fa.end(), seed.begin(), seed.end());
-      fa.push_back(added[j0 + f]);
-    }
-    first[nf] = nf * n;
-    check(dafs_hip_families_from(ctx, src, nf, first.data(), member.data()));
-    if (o.fourway != 0.0f) check(dafs_hip_fourway_consistency(ctx, o.fourway));
-    check(dafs_hip_consistency_bp(ctx, o.fold_pct));
-    if (listed) {  // the pairs (s, new) of every family: local id s n - s (s + 1) / 2 + m - s - 1
-      std::vector<uint64_t> ids;
-      for (uint32_t f = 0; f < nf; ++f)
-        for (uint64_t s = 0; s < m; ++s) ids.push_back((uint64_t)f * ((uint64_t)n * m / 2) + s * n - s * (s + 1) / 2 + m - s - 1);
-      check(dafs_hip_consistency_match_pairs(ctx, o.align_pct, ids.size(), ids.data()));
-    } else {
-      check(dafs_hip_consistency_match(ctx, o.align_pct));
-    }
-
-    // the nf nodes: all opened in the first round
-    std::vector<VU> zs(nf);
-    bool opened = false;
-    run_rounds(ctx, prm, o.verbose, [&]() {
-      std::vector<std::pair<size_t, NodeJob> > ready(opened ? 0 : nf);
-      for (uint32_t f = 0; f < ready.size(); ++f) {
-        NodeJob& jb = ready[f].second;
-        ready[f].first = f;
-        jb.s1.assign(1, f * n + m);
-        jb.m1.assign(lens[j0 + f], 1);
-        jb.s2.resize(m);
-        for (uint32_t r = 0; r < m; ++r) jb.s2[r] = f * n + r;
-        jb.m2 = smask;
-        node_job(ctx, jb, false, prm.th_s);
-      }
-      opened = true;
-      return ready;
-    }, [&](size_t f, NodeJob& jb) {
-      score[j0 + f] = jb.out.score;
-      iterations[j0 + f] = jb.out.iterations;
-      zs[f].swap(jb.z);
-    });
-
-    // per family run_add's merge of its one map; the rows new sequence, then seed rows
-    std::vector<ALN> roots(nf);
-    std::vector<std::vector<uint8_t> > rfs(nf);
-    for (uint32_t f = 0; f < nf; ++f) {
-      const uint32_t len = lens[j0 + f];
-      for (uint32_t z : zs[f]) matched[j0 + f] += z != DAFS_HIP_NONE ? 1 : 0;
-      std::vector<uint32_t> seed_col(C), res_col(len ? len : 1);
-      uint32_t width = 0;
-      check(dafs_host_merge_added(C, 1, &len, zs[f].data(), seed_col.data(), res_col.data(), &width));
-      std::vector<bool> msk(width, false);
-      for (uint32_t i = 0; i < len; ++i) msk[res_col[i]] = true;
-      roots[f].push_back(std::make_pair(f * n + m, msk));
-      for (uint32_t r = 0; r < m; ++r) {
-        std::vector<bool> row(width, false);
-        for (uint32_t c = 0; c < C; ++c) row[seed_col[c]] = smask[(size_t)r * C + c] != 0;
-        roots[f].push_back(std::make_pair(f * n + r, row));
-      }
-      rfs[f].assign(width, 0);
-      for (uint32_t c = 0; c < C; ++c) rfs[f][seed_col[c]] = 1;
-    }
-    std::vector<const ALN*> ptrs;
-    for (const ALN& a : roots) ptrs.push_back(&a);
-    std::vector<VU> ss;
-    if (!o.seed_structure) {
-      consensus_structures(ctx, ptrs, o.fold_th1[0], ss);
-    } else {  // nothing is decoded: the seed's structure in every family's merged columns, and each row's support of it
-      for (uint32_t f = 0; f < nf; ++f) {
-        std::vector<uint32_t> seed_col;
-        for (uint32_t c = 0; c < rfs[f].size(); ++c)
-          if (rfs[f][c]) seed_col.push_back(c);
-        ss.push_back(carry_structure(seed_ss, seed_col, (uint32_t)rfs[f].size()));
-      }
-      std::vector<uint32_t> both, can, half;
-      std::vector<double> expd;
-      structure_support(ctx, ptrs, ss, both, can, half, expd);
-      for (uint32_t f = 0; f < nf; ++f) {  // the new sequence is the first row of its alignment
-        sup_both[j0 + f] = both[(size_t)f * n]; sup_can[j0 + f] = can[(size_t)f * n]; sup_half[j0 + f] = half[(size_t)f * n];
-        sup_exp[j0 + f] = expd[(size_t)f * n];
-      }
-    }
-    std::map<uint32_t, VU> row_ss;
-    if (o.row_structures) {
-      std::vector<uint32_t> every(nf * n);
-      for (uint32_t x = 0; x < nf * n; ++x) every[x] = x;
-      row_ss = row_structures(ctx, fa, every, o.fold_th1[0]);
-    }
-    for (uint32_t f = 0; f < nf; ++f) ss[f] = final_structure(ctx, o, roots[f], &ss[f]);
-    // the annotation, once every structure is final: all rows of every family for --stockholm, or for --seed-merged alone the
-    // new row of every family (the first), which reads the listed pairs only
-    std::vector<Reliability> rl(nf);
-    if (!o.stockholm.empty() || !o.seed_merged.empty()) reliabilities(ctx, fa, ptrs, ss, o.stockholm.empty(), rl);
-    for (uint32_t f = 0; !o.seed_merged.empty() && f < nf; ++f) {
-      all_z[j0 + f] = zs[f];
-      new_pp[j0 + f].assign(rl[f].rel.begin(), rl[f].rel.begin() + lens[j0 + f]);
-    }
-    for (uint32_t f = 0; f < nf; ++f) {
-      const std::vector<Fasta> ff(fa.begin() + (size_t)f * n, fa.begin() + (size_t)(f + 1) * n);
-      std::ostringstream os;
-      std::string sto, cov;
-      finish_alignment(ctx, o, fa, roots[f], ff, f * n, os, o.stockholm.empty() ? nullptr : &sto, nullptr, &rfs[f],
-                       o.covariation.empty() ? nullptr : &cov, ss[f], &rl[f], o.row_structures ? &row_ss : nullptr);
-      std::cout << "==> " << j0 + f + 1 << " <==" << std::endl << os.str();
-      if (o.seed_nearest && matched[j0 + f]) {  // the printed rows (finish_alignment sorted them): the m seed rows, then the new one
-        const std::vector<std::string> rows = row_texts(fa, roots[f]);
-        const std::vector<uint8_t> cell = cells_of(rows);
-        std::vector<uint8_t> cand(n, 1);
-        cand[m] = 0;
-        std::vector<uint32_t> near(n), ni(n), nd(n);
-        check(dafs_hip_alignment_identity(ctx, n, (uint32_t)rfs[f].size(), cell.data(), rfs[f].data(), cand.data(), 0.0, nullptr, nullptr, nullptr,
-                                          near.data(), ni.data(), nd.data(), nullptr));
-        near_row[j0 + f] = near[m];
-        near_pid[j0 + f] = (double)ni[m] / (double)nd[m];
-      }
-      if (!o.stockholm.empty()) sto_blocks.push_back(sto);
-      if (!o.covariation.empty()) { cov_tables.push_back(cov); cov_headers.push_back(std::to_string(j0 + f + 1)); }
-    }
-    j0 = j1;
-  }
-  std::cout.flush();
-  if (!o.stockholm.empty()) write_stockholm(o.stockholm, sto_blocks);
-  if (!o.covariation.empty()) write_covariation(o.covariation, cov_tables, &cov_headers);
-  if (!o.seed_merged.empty()) {  // all k placements in one alignment (DESIGN.md section 17): the seed rows, then the new rows
-    std::vector<uint32_t> z, seed_col(C), res_col;
-    for (uint32_t j = 0; j < k; ++j) z.insert(z.end(), all_z[j].begin(), all_z[j].end());
-    res_col.resize(z.size() ? z.size() : 1);
-    uint32_t width = 0;
-    check(dafs_host_merge_added(C, k, lens.data(), z.data(), seed_col.data(), res_col.data(), &width));
-    std::vector<std::string> headers, rows;
-    std::vector<const double*> rr(m, nullptr);
-    for (uint32_t r = 0; r < m; ++r) {
-      headers.push_back(snames[r]);
-      rows.push_back(std::string(width, '-'));
-      for (uint32_t c = 0; c < C; ++c) rows.back()[seed_col[c]] = srows[r][c];
-    }
-    for (uint32_t j = 0, off = 0; j < k; off += lens[j], ++j) {
-      headers.push_back(added[j].name());
-      rows.push_back(std::string(width, '-'));
-      const std::string& sq = added[j].seq();
-      for (uint32_t i = 0; i < lens[j]; ++i) rows.back()[res_col[off + i]] = sq[i];
-      rr.push_back(new_pp[j].data());
-    }
-    std::vector<uint8_t> rf(width, 0);
-    for (uint32_t c = 0; c < C; ++c) rf[seed_col[c]] = 1;
-    const VU carried = carry_structure(seed_ss, seed_col, width);
-    std::vector<char> brackets(width + 1);
-    dafs_hip_make_brackets(width, carried.data(), brackets.data());
-    char* text = nullptr;
-    check_text(dafs_host_stockholm_names((uint32_t)headers.size(), c_strs(headers).data(), &text));
-    const std::vector<std::string> names = lines_of(take(text), headers.size());
-    check_text(dafs_host_stockholm_block_merged(m + k, width, c_strs(names).data(), c_strs(rows).data(), rr.data(), brackets.data(), rf.data(),
-                                                nullptr, &text));
-    std::string block = take(text);
-    if (!o.compare.empty()) {  // the merged alignment in the seed's columns, with the PP classes of its own block
-      std::vector<std::string> pp(m, std::string());
-      pp.resize(m + k, std::string(width, '.'));
-      for (uint32_t j = 0, off = 0; j < k; off += lens[j], ++j)
-        for (uint32_t i = 0; i < lens[j]; ++i) pp[m + j][res_col[off + i]] = dafs_host_pp_char(new_pp[j][i]);
-      CompareText cmp;
-      compare_of(ctx, o, names, rows, &carried, rf.data(), &pp, cmp);
-      write_compare(o, {cmp}, nullptr);
-    }
-    if (o.seed_nr_given) {  // the non-redundant rows (DESIGN.md section 18): the rows with a residue in a seed column are compared
-      std::vector<uint32_t> inc, pos(m + k, DAFS_HIP_NONE);
-      std::vector<std::string> inc_rows;
-      for (uint32_t r = 0; r < m + k; ++r)
-        if (r < m || matched[r - m]) {
-          pos[r] = (uint32_t)inc.size();
-          inc.push_back(r);
-          inc_rows.push_back(rows[r]);
-        }
-      const uint32_t ni = (uint32_t)inc.size();
-      const std::vector<uint8_t> cell = cells_of(inc_rows);
-      std::vector<uint32_t> red((size_t)ni * ((ni + 31) / 32));
-      check(dafs_hip_alignment_identity(ctx, ni, width, cell.data(), rf.data(), nullptr, o.seed_nr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                        nullptr, red.data()));
-      // the visiting order: the seed rows, then the new rows by descending score, ties in file order
-      std::vector<uint32_t> hits(k), rank;
-      for (uint32_t j = 0; j < k; ++j) hits[j] = j;
-      std::stable_sort(hits.begin(), hits.end(), [&](uint32_t a, uint32_t b) { return score[a] > score[b]; });
-      for (uint32_t r = 0; r < m; ++r) rank.push_back(r);
-      for (uint32_t j : hits)
-        if (pos[m + j] != DAFS_HIP_NONE) rank.push_back(pos[m + j]);
-      std::vector<uint8_t> forced(ni, 0), kept_inc(ni), kept(m + k, 1);
-      std::fill(forced.begin(), forced.begin() + m, 1);
-      std::vector<uint32_t> by(ni);
-      check_text(dafs_host_nr_select(ni, red.data(), rank.data(), forced.data(), kept_inc.data(), by.data()));
-      for (uint32_t q = 0; q < ni; ++q) kept[inc[q]] = kept_inc[q];
-      check_text(dafs_host_stockholm_nr(block.c_str(), m + k, c_strs(names).data(), kept.data(), m, o.seed_nr, &text));
-      block = take(text);
-    }
-    std::ofstream ms(o.seed_merged.c_str(), std::ios::binary);
-    if (!ms.is_open()) throw "--seed-merged: cannot open " + o.seed_merged;
-    ms << block;
-    ms.flush();
-    if (!ms) throw "--seed-merged: cannot write " + o.seed_merged;
-  }
-  if (!o.seed_scores.empty()) {
-    std::ofstream ts(o.seed_scores.c_str(), std::ios::binary);
-    if (!ts.is_open()) throw "--seed-scores: cannot open " + o.seed_scores;
-    std::vector<std::string> headers;
-    for (const Fasta& s : added) headers.push_back(s.name());
-    char* text = nullptr;
-    std::vector<std::string> near_name;  // --seed-nearest: the Stockholm names of the nearest seed rows
-    if (o.seed_nearest) {
-      check_text(dafs_host_stockholm_names(m, c_strs(snames).data(), &text));
-      const std::vector<std::string> seed_names = lines_of(take(text), m);
-      for (uint32_t j = 0; j < k; ++j) near_name.push_back(near_row[j] == DAFS_HIP_NONE ? "-" : seed_names[near_row[j]]);
-    }
-    check_text(dafs_host_seed_table_nearest(k, c_strs(headers).data(), lens.data(), matched.data(), score.data(), iterations.data(),
-                                            o.seed_structure ? sup_both.data() : nullptr, o.seed_structure ? sup_can.data() : nullptr,
-                                            o.seed_structure ? sup_half.data() : nullptr, o.seed_structure ? sup_exp.data() : nullptr,
-                                            o.seed_nearest ? c_strs(near_name).data() : nullptr, o.seed_nearest ? near_pid.data() : nullptr, &text));
-    ts << take(text);
-    ts.flush();
-    if (!ts) throw "--seed-scores: cannot write " + o.seed_scores;
-  }
-  return 0;
-}
-
-// `dafs --pairwise FILE` (DESIGN.md section 12; pipeline.pairwise is the Python twin).  Phase 1 runs once over FILE's N
-// sequences in a source context, the folding beside the all-pairs posteriors and no transform; the pairs, row-major, go in
-// chunks under dafs_host_batch_bytes() through a second context, where dafs_hip_pairs_from gathers a chunk's two-sequence
-// families and align_group runs them as one batch of families.  Each pair prints "==> i j <==" and then what `dafs` prints
-// for a file of its two sequences.
-int run_pairwise(const Options& o, int align_model) {
-  std::vector<Fasta> fa;
-  Fasta::load(fa, o.input.c_str());
-  if (fa.size() < 2) throw std::string("--pairwise needs at least two sequences in the input");
-  const uint32_t N = (uint32_t)fa.size();
-  dafs_hip_ctx* src = nullptr;
-  check(dafs_hip_create(o.device, &src));
-  Guard src_guard{src};
-  set_sequences(src, fa);
-  check(dafs_hip_fold_posteriors_begin(src, DAFS_FOLD_CONTRAFOLD, kCutoff));
-  const int rc_align = dafs_hip_align_posteriors(src, align_model, o.align_th, 0, 0);
-  const int rc_fold = dafs_hip_fold_posteriors_end(src);
-  check(rc_align);
-  check(rc_fold);
-  std::vector<float> sim((size_t)N * N);
-  check(dafs_hip_get_sim(src, sim.data()));
-  dafs_hip_ctx* ctx = nullptr;
-  check(dafs_hip_create(o.device, &ctx));
-  Guard guard{ctx};
-
-  std::vector<std::pair<uint32_t, uint32_t> > pairs;
-  for (uint32_t x = 0; x < N; ++x)
-    for (uint32_t y = x + 1; y < N; ++y) pairs.push_back(std::make_pair(x, y));
-  std::vector<double> score(pairs.size(), 0.0);
-  std::vector<int64_t> iterations(pairs.size(), 0);
-  std::vector<std::string> sto_blocks;
-  Ranks rk;  // one process
-  // the chunks: greedy in pair order under the estimated device memory of each pair, its phase-1 stores and its root node,
-  // which is resident for the whole chunk; a pair over the budget runs alone
-  std::vector<uint64_t> bytes(pairs.size());
-  for (size_t k = 0; k < pairs.size(); ++k) {
-    const uint32_t l[2] = {(uint32_t)fa[pairs[k].first].size(), (uint32_t)fa[pairs[k].second].size()};
-    bytes[k] = dafs_host_family_bytes(2, l) + dafs_host_node_bytes(l[0], l[1]);
-  }
-  std::vector<uint32_t> chunk_of(pairs.size());
-  check(dafs_host_pack_greedy((uint32_t)pairs.size(), bytes.data(), dafs_host_batch_bytes(), chunk_of.data()));
-  for (size_t p0 = 0; p0 < pairs.size();) {
-    size_t p1 = p0;
-    while (p1 < pairs.size() && chunk_of[p1] == chunk_of[p0]) ++p1;
-    const size_t n = p1 - p0;
-    PairChunk pc;
-    pc.src = src;
-    pc.score.assign(n, 0.0f);
-    pc.iterations.assign(n, 0);
-    std::vector<std::vector<Fasta> > fams;
-    for (size_t k = p0; k < p1; ++k) {
-      pc.px.push_back(pairs[k].first);
-      pc.py.push_back(pairs[k].second);
-      fams.push_back({fa[pairs[k].first], fa[pairs[k].second]});
-    }
-    std::vector<size_t> members(n);
-    std::vector<std::ostringstream> outs(n);
-    std::vector<std::ostream*> os(n);
-    std::vector<std::string> sto(o.stockholm.empty() ? 0 : n);
-    std::vector<std::string*> sp;
-    for (size_t j = 0; j < n; ++j) {
-      members[j] = j;
-      os[j] = &outs[j];
-      if (!sto.empty()) sp.push_back(&sto[j]);
-    }
-    align_group(ctx, o, rk, align_model, fams, members, os, sp, &pc);
-    for (size_t j = 0; j < n; ++j) {
-      std::cout << "==> " << pairs[p0 + j].first + 1 << " " << pairs[p0 + j].second + 1 << " <==" << std::endl << outs[j].str();
-      score[p0 + j] = pc.score[j];
-      iterations[p0 + j] = pc.iterations[j];
-    }
-    sto_blocks.insert(sto_blocks.end(), sto.begin(), sto.end());
-    p0 = p1;
-  }
-  std::cout.flush();
-  if (!o.stockholm.empty()) write_stockholm(o.stockholm, sto_blocks);
-  if (!o.pairwise_scores.empty()) {
-    std::ofstream ts(o.pairwise_scores.c_str(), std::ios::binary);
-    if (!ts.is_open()) throw "--pairwise-scores: cannot open " + o.pairwise_scores;
-    std::vector<uint32_t> px, py;
-    std::vector<double> psim;
-    std::vector<std::string> names;
-    for (const Fasta& s : fa) names.push_back(s.name());
-    for (const auto& pr : pairs) {
-      px.push_back(pr.first);
-      py.push_back(pr.second);
-      psim.push_back(sim[(size_t)pr.first * N + pr.second]);
-    }
-    char* text = nullptr;
-    check_text(dafs_host_pairwise_table(pairs.size(), px.data(), py.data(), N, c_strs(names).data(), psim.data(), score.data(), iterations.data(), &text));
-    ts << take(text);
-    ts.flush();
-    if (!ts) throw "--pairwise-scores: cannot write " + o.pairwise_scores;
-  }
-  return 0;
-}
-
-// `dafs --cluster T FILE` (DESIGN.md section 20; pipeline.cluster is the Python twin).  The similarity scores of all pairs come
-// from dafs_hip_similarity, which walks the pairs in ranges under the library's budget and keeps no store; the guide tree of
-// the whole set (with --cluster-linkage single, complete or average the linkage tree of dafs_hip_linkage_tree, DESIGN.md section
-// 21) is cut by dafs_host_cluster_cut; the clusters of at least --cluster-min-size members are the families of
-// align_group, as the FILEs of a run of several are: those of two or more sequences in sub-batches under
-// dafs_host_batch_bytes() of dafs_host_family_bytes, a cluster of one sequence on the single-sequence path.  Each printed
-// cluster is "==> cluster c <==" and then what `dafs` prints for a file of its sequences.
-int run_cluster(const Options& o, int align_model) {
-  std::vector<Fasta> fa;
-  Fasta::load(fa, o.input.c_str());
-  if (fa.empty()) throw "no sequences in the input";
-  const uint32_t N = (uint32_t)fa.size();
-  if (o.cluster_count_given && o.cluster_count > N)
-    throw "--cluster-count: " + std::to_string(o.cluster_count) + " clusters asked of " + std::to_string(N) + " sequences";
-  dafs_hip_ctx* ctx = nullptr;
-  check(dafs_hip_create(o.device, &ctx));
-  Guard guard{ctx};
-  std::vector<float> sim((size_t)N * N, 1.0f);
-  if (N > 1) {
-    set_sequences(ctx, fa);
-    check(dafs_hip_similarity(ctx, align_model, o.align_th, 0, nullptr));
-    check(dafs_hip_get_sim(ctx, sim.data()));
-  }
-  std::vector<float> score(2 * N - 1);
-  std::vector<int32_t> left(2 * N - 1), right(2 * N - 1);
-  if (o.cluster_linkage == 0) check(dafs_host_build_tree(N, sim.data(), score.data(), left.data(), right.data()));
-  else if (N == 1) { score[0] = 0.0f; left[0] = right[0] = -1; }  // the one-leaf tree
-  else check_text(dafs_hip_linkage_tree(ctx, o.cluster_linkage, N, nullptr, score.data(), left.data(), right.data()));  // on the block the pass left on the device
-  std::vector<uint32_t> labels(N);
-  uint32_t K = 0;
-  check_text(dafs_host_cluster_cut(N, score.data(), left.data(), right.data(), o.cluster_given ? DAFS_CLUSTER_THRESHOLD : DAFS_CLUSTER_COUNT,
-                                   (float)o.cluster, o.cluster_count, labels.data(), &K));
-  if (!o.cluster_table.empty()) {
-    std::vector<std::string> headers;
-    std::vector<uint32_t> lens;
-    for (const Fasta& s : fa) { headers.push_back(s.name()); lens.push_back(s.size()); }
-    char* text = nullptr;
-    check_text(dafs_host_cluster_table(N, c_strs(headers).data(), lens.data(), labels.data(), score.data(), left.data(), right.data(), sim.data(), &text));
-    write_tables("--cluster-table", o.cluster_table, {take(text)}, nullptr);
-  }
-  if (!o.cluster_tree.empty()) {
-    std::vector<node_t> tree(2 * N - 1);
-    for (uint i = 0; i < 2 * N - 1; ++i) tree[i] = std::make_pair(score[i], std::make_pair((uint)left[i], (uint)right[i]));
-    std::ostringstream tl;
-    print_tree(tl, tree, fa, (int)tree.size() - 1);
-    tl << std::endl;
-    write_tables("--cluster-tree", o.cluster_tree, {tl.str()}, nullptr);
-  }
-  // the clusters that are aligned, as the families of a run of several files
-  std::vector<std::vector<Fasta> > all(K);
-  for (uint32_t i = 0; i < N; ++i) all[labels[i]].push_back(fa[i]);
-  std::vector<std::vector<Fasta> > fams;
-  std::vector<std::string> headers;
-  for (uint32_t c = 0; c < K; ++c)
-    if (all[c].size() >= o.cluster_min_size) {
-      fams.push_back(all[c]);
-      headers.push_back("cluster " + std::to_string(c + 1));
-    }
-  const size_t P = fams.size();
-  std::vector<std::ostringstream> outs(P);
-  std::vector<std::string> sto_blocks(o.stockholm.empty() ? 0 : P), cov_tables(o.covariation.empty() ? 0 : P);
-  std::vector<IdentityText> idts(o.identity.empty() ? 0 : P);
-  Ranks rk;  // one process
-  auto group = [&](const std::vector<size_t>& members) {
-    std::vector<std::ostream*> os;
-    std::vector<std::string*> sp, cp;
-    std::vector<IdentityText*> ip;
-    for (size_t f : members) {
-      os.push_back(&outs[f]);
-      if (!sto_blocks.empty()) sp.push_back(&sto_blocks[f]);
-      if (!cov_tables.empty()) cp.push_back(&cov_tables[f]);
-      if (!idts.empty()) ip.push_back(&idts[f]);
-    }
-    align_group(ctx, o, rk, align_model, fams, members, os, sp, nullptr, cp, ip);
-  };
-  std::vector<size_t> batch;
-  std::vector<uint64_t> bytes;
-  for (size_t f = 0; f < P; ++f)
-    if (fams[f].size() > 1) {
-      std::vector<uint32_t> lens;
-      for (const Fasta& s : fams[f]) lens.push_back(s.size());
-      batch.push_back(f);
-      bytes.push_back(dafs_host_family_bytes((uint32_t)lens.size(), lens.data()));
-    }
-  std::vector<uint32_t> group_of(batch.size());
-  check(dafs_host_pack_greedy((uint32_t)batch.size(), bytes.data(), dafs_host_batch_bytes(), group_of.data()));
-  for (size_t b0 = 0; b0 < batch.size();) {
-    size_t b1 = b0;
-    while (b1 < batch.size() && group_of[b1] == group_of[b0]) ++b1;
-    group(std::vector<size_t>(batch.begin() + b0, batch.begin() + b1));
-    b0 = b1;
-  }
-  for (size_t f = 0; f < P; ++f)
-    if (fams[f].size() == 1) group({f});
-  for (size_t f = 0; f < P; ++f) std::cout << "==> " << headers[f] << " <==" << std::endl << outs[f].str();
-  std::cout.flush();
-  if (!o.stockholm.empty()) write_stockholm(o.stockholm, sto_blocks);
-  if (!o.covariation.empty()) write_covariation(o.covariation, cov_tables, &headers);
-  if (!o.identity.empty()) write_identity(o, idts, &headers);
-  return 0;
-}
-
-// `dafs --describe ALIGNMENT` (DESIGN.md section 18; pipeline.describe is the Python twin): the calls that read an alignment
-// alone, on a finished alignment that the seed reader reads.  Nothing is aligned and nothing is printed.
-int run_describe(const Options& o) {
-  std::vector<std::string> headers, rows;
-  VU ss;
-  read_seed(o.describe, headers, rows, &ss, true);
-  char* text = nullptr;
-  check_text(dafs_host_stockholm_names((uint32_t)headers.size(), c_strs(headers).data(), &text));
-  const std::vector<std::string> names = lines_of(take(text), headers.size());
-  dafs_hip_ctx* ctx = nullptr;
-  check(dafs_hip_create(o.device, &ctx));
-  Guard guard{ctx};
-  if (!o.identity.empty()) {
-    IdentityText idt;
-    identity_of(ctx, names, rows, !o.identity_matrix.empty(), idt);
-    write_identity(o, {idt}, nullptr);
-  }
-  if (!o.covariation.empty()) {
-    std::string cov, chars;
-    covariation_of(ctx, o, rows, ss, cov, chars);
-    write_covariation(o.covariation, {cov}, nullptr);
-  }
-  if (!o.compare.empty()) {  // the file again: whether it has a structure, and its PP lines
-    std::vector<std::string> h2, r2, pp;
-    VU ss2;
-    bool has_ss = false;
-    read_alignment(o.describe, "--describe", h2, r2, ss2, has_ss, &pp);
-    CompareText cmp;
-    compare_of(ctx, o, names, rows, has_ss ? &ss2 : nullptr, nullptr, pp.empty() ? nullptr : &pp, cmp);
-    write_compare(o, {cmp}, nullptr);
-  }
-  return 0;
-}
-
-int run(const Options& o, Ranks& rk) {
-  // ---- option checks mirroring parse_options (:1683-1763)
-  int align_model;
-  if (o.align_model == "ProbCons") align_model = DAFS_ALIGN_PROBCONS;
-  else if (o.align_model == "CONTRAlign") align_model = DAFS_ALIGN_CONTRALIGN;
-  else throw "Unknown alignment model: " + o.align_model;
-  if (o.fold_aux.empty()) {
-    if (o.fold_model == "Boltzmann" || o.fold_model == "Vienna")
-      throw "Folding model " + o.fold_model + " needs ViennaRNA, which this build does not contain; use -s CONTRAfold or --fold-aux";
-    if (o.fold_model != "CONTRAfold") throw "Unknown folding model: " + o.fold_model;
-  }
-  if (o.fold_decoder != "Nussinov" || o.ipknot) throw "Folding decoder IPknot needs an ILP solver, which this build does not contain";
-  if (o.max_iter <= 0) throw "-m 0 (exact ILP) needs an ILP solver, which this build does not contain";
-  if ((o.bp_update || o.bp_update1) && !o.fold_aux.empty()) throw "--bp-update / --bp-update1 need a folding model (-s CONTRAfold), not --fold-aux";
-  if (!o.devices.empty() && (!o.fold_aux.empty() || !o.align_aux.empty() || o.fourway != 0.0f))
-    throw std::string("--devices shards the posterior models and the consistency transform; --fold-aux, --align-aux and -f run on one device (--device)");
-  if (o.verbose >= 1) {
-    if (!o.no_alifold) std::cerr << "note: RNAalifold is not available in this build; running as with --no-alifold" << std::endl;
-    if (!o.fold_model_given && o.fold_aux.empty()) std::cerr << "note: default folding model is CONTRAfold in this build" << std::endl;
-  }
-  if (!o.describe.empty()) return rk.rank == 0 ? run_describe(o) : 0;
-  if (!o.seed.empty()) return o.seed_each ? run_add_each(o, align_model) : run_add(o, align_model);
-  if (o.pairwise) return run_pairwise(o, align_model);
-  if (o.cluster_given || o.cluster_count_given) return run_cluster(o, align_model);
-
-  // one family per input file
-  const bool multi = o.inputs.size() > 1;
-  std::vector<std::vector<Fasta> > fams(o.inputs.size());
-  for (size_t f = 0; f < o.inputs.size(); ++f) {
-    const std::string& file = o.inputs[f];
-    try {
-      Fasta::load(fams[f], file.c_str());
-    } catch (const std::system_error& e) {
-      if (multi) throw file + ": " + e.code().message();
-      throw;
-    }
-    if (fams[f].empty()) {
-      if (multi) throw file + ": no sequences in the input";
-      throw "no sequences in the input";
-    }
-  }
-
-  dafs_hip_ctx* ctx = nullptr;
-  check(dafs_hip_create(o.devices.empty() ? o.device : o.devices[rk.rank], &ctx));
-  Guard guard{ctx};
-
-  // --stockholm: one block per input file, in input order, written by the process that prints
-  std::vector<std::string> sto_blocks(o.stockholm.empty() ? 0 : o.inputs.size());
-  auto sto_of = [&](const std::vector<size_t>& members) {
-    std::vector<std::string*> v;
-    if (!sto_blocks.empty())
-      for (size_t f : members) v.push_back(&sto_blocks[f]);
-    return v;
-  };
-  // --covariation: one table per input file, in input order, written by the process that prints
-  std::vector<std::string> cov_tables(o.covariation.empty() ? 0 : o.inputs.size());
-  auto cov_of = [&](const std::vector<size_t>& members) {
-    std::vector<std::string*> v;
-    if (!cov_tables.empty())
-      for (size_t f : members) v.push_back(&cov_tables[f]);
-    return v;
-  };
-  // --identity: the same, one pair of tables per input file
-  std::vector<IdentityText> idts(o.identity.empty() ? 0 : o.inputs.size());
-  auto idt_of = [&](const std::vector<size_t>& members) {
-    std::vector<IdentityText*> v;
-    if (!idts.empty())
-      for (size_t f : members) v.push_back(&idts[f]);
-    return v;
-  };
-  // --compare: the same, one set of tables per input file
-  std::vector<CompareText> cmps(o.compare.empty() ? 0 : o.inputs.size());
-  auto cmp_of = [&](const std::vector<size_t>& members) {
-    std::vector<CompareText*> v;
-    if (!cmps.empty())
-      for (size_t f : members) v.push_back(&cmps[f]);
-    return v;
-  };
-  if (!multi) {
-    align_group(ctx, o, rk, align_model, fams, {0}, {&std::cout}, sto_of({0}), nullptr, cov_of({0}), idt_of({0}), cmp_of({0}));
-    if (rk.rank == 0 && !o.stockholm.empty()) write_stockholm(o.stockholm, sto_blocks);
-    if (rk.rank == 0 && !o.covariation.empty()) write_covariation(o.covariation, cov_tables, nullptr);
-    if (rk.rank == 0 && !o.identity.empty()) write_identity(o, idts, nullptr);
-    if (rk.rank == 0 && !o.compare.empty()) write_compare(o, cmps, nullptr);
-    return 0;
-  }
-  // Several files: every file with two or more sequences in one batch (dafs_hip_set_families: shared launches, one guide
-  // tree per family, the forest walked together); a file of one sequence takes the single-sequence path of a run of its
-  // own (no pairs, no consistency transforms) on the same context.  Each block is what `dafs FILE` prints.
-  std::vector<std::ostringstream> outs(o.inputs.size());
-  std::vector<size_t> batch;
-  for (size_t f = 0; f < fams.size(); ++f)
-    if (fams[f].size() > 1) batch.push_back(f);
-  auto names = [&](const std::vector<size_t>& members) {
-    std::string s;
-    for (size_t f : members) s += (s.empty() ? "" : ", ") + o.inputs[f];
-    return s;
-  };
-  auto group = [&](const std::vector<size_t>& members) {
-    std::vector<std::ostream*> os;
-    for (size_t f : members) os.push_back(&outs[f]);
-    try {
-      align_group(ctx, o, rk, align_model, fams, members, os, sto_of(members), nullptr, cov_of(members), idt_of(members), cmp_of(members));
-    } catch (const char* str) {
-      throw names(members) + ": " + str;
-    } catch (const std::string& str) {
-      throw names(members) + ": " + str;
-    }
-  };
-  if (!batch.empty()) group(batch);
-  for (size_t f = 0; f < fams.size(); ++f)
-    if (fams[f].size() == 1) group({f});
-  for (size_t f = 0; f < fams.size(); ++f) std::cout << "==> " << o.inputs[f] << " <==" << std::endl << outs[f].str();
-  std::cout.flush();
-  if (!o.stockholm.empty()) write_stockholm(o.stockholm, sto_blocks);
-  if (!o.covariation.empty()) write_covariation(o.covariation, cov_tables, &o.inputs);
-  if (!o.identity.empty()) write_identity(o, idts, &o.inputs);
-  if (!o.compare.empty()) write_compare(o, cmps, &o.inputs);
-  return 0;
-}
-
 // The run of one or more families (members: indices into fams) on the context: phase 1 once over all of them, one guide
 // tree per family, the progressive phase over the forest (the ready nodes of every family share each round), then per
-// family the refinement, the common structure and the output on *out[k]; with --stockholm (sto not empty) also the
-// family's Stockholm block in *sto[k], with --covariation (cov not empty) its covariation table in *cov[k], and with
-// --identity (idt not empty) its identity tables and weights in *idt[k], with --compare (cmp not empty) its comparison in *cmp[k].
+// family the refinement, the common structure and the output into its record out[k] (finish_alignment): the text on
+// *out[k]->os, and what out[k]->wanted asks for -- the same of every family of a group -- of the family's Stockholm block,
+// covariation table, identity tables and weights, and comparison.
 int align_group(dafs_hip_ctx* ctx, const Options& o, Ranks& rk, int align_model, const std::vector<std::vector<Fasta> >& fams,
-                const std::vector<size_t>& members, const std::vector<std::ostream*>& out, const std::vector<std::string*>& sto,
-                PairChunk* pc, const std::vector<std::string*>& cov, const std::vector<IdentityText*>& idt, const std::vector<CompareText*>& cmp) {
+                const std::vector<size_t>& members, const std::vector<FamilyOut*>& out, PairChunk* pc = nullptr) {
   const uint F = (uint)members.size();
+  const bool sto = (out[0]->wanted & kSto) != 0;
   std::vector<Fasta> fa;         // every sequence of the group, family after family
   std::vector<uint32_t> first(1, 0);
   for (size_t f : members) {
@@ -2377,8 +1708,8 @@ int align_group(dafs_hip_ctx* ctx, const Options& o, Ranks& rk, int align_model,
   }
   for (uint f = 0; f < F; ++f) {
     const std::vector<Fasta>& ff = fams[members[f]];
-    print_tree(*out[f], trees[f], ff, (int)trees[f].size() - 1);
-    *out[f] << std::endl;
+    print_tree(*out[f]->os, trees[f], ff, (int)trees[f].size() - 1);
+    *out[f]->os << std::endl;
   }
 
   // progressive alignment (:1838): every node whose children are ready is solved in the same batch
@@ -2468,28 +1799,610 @@ int align_group(dafs_hip_ctx* ctx, const Options& o, Ranks& rk, int align_model,
   for (uint f = 0; f < F; ++f) roots.push_back(&aln[tbase[f + 1] - 1]);
   std::vector<VU> ss0;
   consensus_structures(ctx, roots, o.fold_th1[0], ss0);
-  std::map<uint32_t, VU> row_ss;
-  if (o.row_structures && !sto.empty()) {
-    std::vector<uint32_t> every(N);
-    for (uint x = 0; x < N; ++x) every[x] = x;
-    row_ss = row_structures(ctx, fa, every, o.fold_th1[0]);
-  }
+  std::vector<VU> row_ss;
+  if (o.row_structures && sto) row_ss = row_structures(ctx, fa, o.fold_th1[0]);
   // the annotation of all of them in one call, once every structure is final (-r and --bp-update1 are behind it)
   for (uint f = 0; f < F; ++f) ss0[f] = final_structure(ctx, o, *roots[f], &ss0[f]);
   std::vector<Reliability> rl(F);
-  if (!sto.empty()) reliabilities(ctx, fa, roots, ss0, false, rl);
+  if (sto) reliabilities(ctx, fa, roots, ss0, false, rl);
   for (uint f = 0; f < F; ++f) {
-    ALN& root = aln[tbase[f + 1] - 1];
     std::string tree_line;
-    if (!sto.empty()) {
+    if (sto) {
       std::ostringstream tl;
       print_tree(tl, trees[f], fams[members[f]], (int)trees[f].size() - 1);
       tree_line = tl.str();
     }
-    finish_alignment(ctx, o, fa, root, fams[members[f]], first[f], *out[f], sto.empty() ? nullptr : sto[f], &tree_line, nullptr,
-                     cov.empty() ? nullptr : cov[f], ss0[f], &rl[f], row_ss.empty() ? nullptr : &row_ss, idt.empty() ? nullptr : idt[f],
-                     cmp.empty() ? nullptr : cmp[f]);
+    finish_alignment(ctx, o, fa, aln[tbase[f + 1] - 1], first[f], *out[f], &tree_line, nullptr, ss0[f], rl[f], row_ss.empty() ? nullptr : &row_ss);
   }
+  return 0;
+}
+
+// a family's block of a run that prints several: the header line, then the family's text, which is not kept
+void print_block(const std::string& header, FamilyOut& rec) {
+  std::cout << "==> " << header << " <==" << std::endl << rec.text.str();
+  rec.text.str(std::string());
+}
+
+// One node per new sequence against the seed, all count of them opened in the first round (run_rounds): fill(j, job) sets job
+// j's left side (the new sequence's leaf) and right side (the seed's rows); finish as run_rounds calls it.
+void placement_rounds(dafs_hip_ctx* ctx, const dafs_dd_params& prm, int verbose, size_t count, const std::function<void(size_t, NodeJob&)>& fill,
+                      const std::function<void(size_t, NodeJob&)>& finish) {
+  bool opened = false;
+  run_rounds(ctx, prm, verbose, [&]() {
+    std::vector<std::pair<size_t, NodeJob> > ready(opened ? 0 : count);
+    for (size_t j = 0; j < ready.size(); ++j) {
+      ready[j].first = j;
+      fill(j, ready[j].second);
+      node_job(ctx, ready[j].second, false, prm.th_s);
+    }
+    opened = true;
+    return ready;
+  }, finish);
+}
+
+// `dafs --seed SEED FILE` (DESIGN.md section 11; pipeline.add is the Python twin).  The context holds the seed's m sequences
+// in seed order and then FILE's k.  Phase 1 is a normal run's over all of them; one node per new sequence j, its leaf (left)
+// against the seed (right), and all k go through the resident-node rounds together (placement_rounds); place() puts them into
+// the seed; the structure is decoded over the rows new sequences, then seed rows, as in a run whose tree joins a leaf last.
+int run_add(const Options& o, int align_model) {
+  const Seed sd = load_seed(o);
+  std::vector<Fasta> added;
+  Fasta::load(added, o.input.c_str());
+  if (added.empty()) throw "no sequences in the input";
+  const uint32_t m = sd.m, k = (uint32_t)added.size();
+  std::vector<Fasta> fa(sd.fa);
+  fa.insert(fa.end(), added.begin(), added.end());
+
+  dafs_hip_ctx* ctx = nullptr;
+  check(dafs_hip_create(o.device, &ctx));
+  Guard guard{ctx};
+  set_sequences(ctx, fa);
+  std::vector<float> sim;
+  const Constraints cons = seed_constraints(o, sd, k);
+  phase1_local(ctx, o, align_model, fa, {0, m + k}, sim, nullptr, o.seed_structure ? &cons.ptr : nullptr);
+
+  dafs_dd_params prm = dd_params_of(o);
+  prm.skip_uncoupled_folds = o.verbose == 0 ? 1 : 0;  // as the progressive loop of a run without -r
+  std::vector<uint32_t> seed_idx(m), lens(k);
+  for (uint32_t r = 0; r < m; ++r) seed_idx[r] = r;
+  for (uint32_t j = 0; j < k; ++j) lens[j] = added[j].size();
+  std::vector<VU> zs(k);
+  placement_rounds(ctx, prm, o.verbose, k, [&](size_t j, NodeJob& jb) {
+    jb.s1.assign(1, m + (uint32_t)j);
+    jb.m1.assign(lens[j], 1);
+    jb.s2 = seed_idx;
+    jb.m2 = sd.mask;
+  }, [&](size_t j, NodeJob& jb) { zs[j].swap(jb.z); });
+
+  // the rows new sequences (file order), then seed rows (seed order)
+  const Placement pl = place(sd, k, lens.data(), zs.data());
+  ALN root = placed_rows(sd, pl, k, lens.data(), m, 0);
+  std::vector<FamilyOut> recs = records(1, wanted_of(o));
+  recs[0].os = &std::cout;
+  std::vector<VU> row_ss;
+  if (o.row_structures) row_ss = row_structures(ctx, fa, o.fold_th1[0]);
+  VU carried;  // --seed-structure: nothing is decoded
+  if (o.seed_structure) carried = carry_structure(sd.ss, pl.seed_col, pl.width);
+  const VU ss = final_structure(ctx, o, root, o.seed_structure ? &carried : nullptr);
+  std::vector<Reliability> rl(1);
+  if (recs[0].wanted & kSto) reliabilities(ctx, fa, {&root}, {ss}, false, rl);
+  finish_alignment(ctx, o, fa, root, 0, recs[0], nullptr, &pl.rf, ss, rl[0], o.row_structures ? &row_ss : nullptr);
+  std::cout.flush();
+  write_outputs(o, recs[0].wanted, recs, nullptr);
+  return 0;
+}
+
+// `dafs --seed SEED --seed-each FILE` (DESIGN.md section 15; pipeline.add_each is the Python twin): every sequence of FILE added
+// to the seed as run_add adds a file of that sequence alone.  Phase 1 runs once in a source context over the seed's m sequences
+// and then FILE's k: the folds and the posteriors of the pairs with a seed sequence on the left, no transform.  The new
+// sequences go in chunks under dafs_host_batch_bytes() (dafs_host_seed_each_bytes each) through a second context, where
+// dafs_hip_families_from gathers the chunk's families seed + [new]; then the transforms -- the matching transform for the pairs
+// (seed, new) alone unless --stockholm's reliabilities read the seed-seed rows --, one node per family in shared rounds,
+// run_add's placement per family and the structures of the chunk in one call.  No identity output and no comparison per family.
+// --seed-merged: the placements' maps are kept, and after the last chunk place() puts all k into the seed at once (DESIGN.md
+// section 17).
+int run_add_each(const Options& o, int align_model) {
+  const Seed sd = load_seed(o);
+  std::vector<Fasta> added;
+  Fasta::load(added, o.input.c_str());
+  if (added.empty()) throw "no sequences in the input";
+  const uint32_t m = sd.m, k = (uint32_t)added.size(), C = sd.C, n = m + 1;
+  std::vector<uint32_t> lens(k);
+  for (uint32_t j = 0; j < k; ++j) lens[j] = added[j].size();
+
+  dafs_hip_ctx* src = nullptr;
+  check(dafs_hip_create(o.device, &src));
+  Guard src_guard{src};
+  {
+    std::vector<Fasta> all(sd.fa);
+    all.insert(all.end(), added.begin(), added.end());
+    set_sequences(src, all);
+  }
+  {  // --seed-structure: the seed rows under their constraints, the new sequences free, once for every chunk
+    const Constraints cons = seed_constraints(o, sd, k);
+    check(dafs_hip_fold_posteriors_constrained_begin(src, DAFS_FOLD_CONTRAFOLD, kCutoff, o.seed_structure ? cons.ptr.data() : nullptr));
+  }
+  // the pairs (x, y) with x < m are the first m (m + k) - m (m + 1) / 2 pair ids
+  const int rc_align = dafs_hip_align_posteriors(src, align_model, o.align_th, 0, (uint64_t)m * (m + k) - (uint64_t)m * (m + 1) / 2);
+  const int rc_fold = dafs_hip_fold_posteriors_end(src);
+  check(rc_align);
+  check(rc_fold);
+  dafs_hip_ctx* ctx = nullptr;
+  check(dafs_hip_create(o.device, &ctx));
+  Guard guard{ctx};
+
+  std::vector<uint64_t> bytes(k);
+  for (uint32_t j = 0; j < k; ++j) bytes[j] = dafs_host_seed_each_bytes(m, sd.lens.data(), C, lens[j]);
+  dafs_dd_params prm = dd_params_of(o);
+  prm.skip_uncoupled_folds = o.verbose == 0 ? 1 : 0;  // as run_add
+  const unsigned wanted = wanted_of(o) & ~(kIdt | kCmp);
+  const bool listed = !(wanted & kSto) && o.align_pct != 0.0f;  // the reliabilities of --stockholm read the seed-seed rows
+  std::vector<uint32_t> matched(k, 0);
+  std::vector<double> score(k, 0.0);
+  std::vector<int64_t> iterations(k, 0);
+  std::vector<uint32_t> sup_both(k, 0), sup_can(k, 0), sup_half(k, 0);  // --seed-structure: the support of each new sequence's row
+  std::vector<double> sup_exp(k, 0.0);
+  std::vector<uint32_t> near_row(k, DAFS_HIP_NONE);  // --seed-nearest: per new sequence its nearest seed row and the identity to it
+  std::vector<double> near_pid(k, std::nan(""));
+  std::vector<FamilyOut> recs = records(k, wanted);  // one per new sequence
+  std::vector<std::string> headers;
+  for (uint32_t j = 0; j < k; ++j) headers.push_back(std::to_string(j + 1));
+  std::vector<VU> all_z(k);                     // --seed-merged: every placement's map, kept until the last chunk is done,
+  std::vector<std::vector<double> > new_pp(k);  // and the residue values of its row in its own family
+  for (const auto& chunk : chunks(bytes)) {
+    const uint32_t j0 = (uint32_t)chunk.first, nf = (uint32_t)(chunk.second - chunk.first);
+    // family f: the seed's sequences at f n .. f n + m - 1, the new one at f n + m
+    std::vector<uint32_t> first(nf + 1), member;
+    std::vector<Fasta> fa;
+    for (uint32_t f = 0; f < nf; ++f) {
+      first[f] = f * n;
+      for (uint32_t r = 0; r < m; ++r) member.push_back(r);
+      member.push_back(m + j0 + f);
+      fa.insert(fa.end(), sd.fa.begin(), sd.fa.end());
+      fa.push_back(added[j0 + f]);
+    }
+    first[nf] = nf * n;
+    check(dafs_hip_families_from(ctx, src, nf, first.data(), member.data()));
+    if (o.fourway != 0.0f) check(dafs_hip_fourway_consistency(ctx, o.fourway));
+    check(dafs_hip_consistency_bp(ctx, o.fold_pct));
+    if (listed) {  // the pairs (s, new) of every family: local id s n - s (s + 1) / 2 + m - s - 1
+      std::vector<uint64_t> ids;
+      for (uint32_t f = 0; f < nf; ++f)
+        for (uint64_t s = 0; s < m; ++s) ids.push_back((uint64_t)f * ((uint64_t)n * m / 2) + s * n - s * (s + 1) / 2 + m - s - 1);
+      check(dafs_hip_consistency_match_pairs(ctx, o.align_pct, ids.size(), ids.data()));
+    } else {
+      check(dafs_hip_consistency_match(ctx, o.align_pct));
+    }
+
+    std::vector<VU> zs(nf);
+    placement_rounds(ctx, prm, o.verbose, nf, [&](size_t f, NodeJob& jb) {
+      jb.s1.assign(1, (uint32_t)f * n + m);
+      jb.m1.assign(lens[j0 + f], 1);
+      jb.s2.resize(m);
+      for (uint32_t r = 0; r < m; ++r) jb.s2[r] = (uint32_t)f * n + r;
+      jb.m2 = sd.mask;
+    }, [&](size_t f, NodeJob& jb) {
+      score[j0 + f] = jb.out.score;
+      iterations[j0 + f] = jb.out.iterations;
+      zs[f].swap(jb.z);
+    });
+
+    // per family run_add's placement of its one map; the rows new sequence, then seed rows
+    std::vector<Placement> pl;
+    std::vector<ALN> roots;
+    for (uint32_t f = 0; f < nf; ++f) {
+      for (uint32_t z : zs[f]) matched[j0 + f] += z != DAFS_HIP_NONE ? 1 : 0;
+      pl.push_back(place(sd, 1, &lens[j0 + f], &zs[f]));
+      roots.push_back(placed_rows(sd, pl[f], 1, &lens[j0 + f], f * n + m, f * n));
+    }
+    std::vector<const ALN*> ptrs;
+    for (const ALN& a : roots) ptrs.push_back(&a);
+    std::vector<VU> ss;
+    if (!o.seed_structure) {
+      consensus_structures(ctx, ptrs, o.fold_th1[0], ss);
+    } else {  // nothing is decoded: the seed's structure in every family's merged columns, and each row's support of it
+      for (uint32_t f = 0; f < nf; ++f) ss.push_back(carry_structure(sd.ss, pl[f].seed_col, pl[f].width));
+      std::vector<uint32_t> both, can, half;
+      std::vector<double> expd;
+      structure_support(ctx, ptrs, ss, both, can, half, expd);
+      for (uint32_t f = 0; f < nf; ++f) {  // the new sequence is the first row of its alignment
+        sup_both[j0 + f] = both[(size_t)f * n]; sup_can[j0 + f] = can[(size_t)f * n]; sup_half[j0 + f] = half[(size_t)f * n];
+        sup_exp[j0 + f] = expd[(size_t)f * n];
+      }
+    }
+    std::vector<VU> row_ss;
+    if (o.row_structures) row_ss = row_structures(ctx, fa, o.fold_th1[0]);
+    for (uint32_t f = 0; f < nf; ++f) ss[f] = final_structure(ctx, o, roots[f], &ss[f]);
+    // the annotation, once every structure is final: all rows of every family for --stockholm, or for --seed-merged alone the
+    // new row of every family (the first), which reads the listed pairs only
+    std::vector<Reliability> rl(nf);
+    if ((wanted & kSto) || !o.seed_merged.empty()) reliabilities(ctx, fa, ptrs, ss, !(wanted & kSto), rl);
+    for (uint32_t f = 0; !o.seed_merged.empty() && f < nf; ++f) {
+      all_z[j0 + f] = zs[f];
+      new_pp[j0 + f].assign(rl[f].rel.begin(), rl[f].rel.begin() + lens[j0 + f]);
+    }
+    for (uint32_t f = 0; f < nf; ++f) {
+      finish_alignment(ctx, o, fa, roots[f], f * n, recs[j0 + f], nullptr, &pl[f].rf, ss[f], rl[f], o.row_structures ? &row_ss : nullptr);
+      print_block(headers[j0 + f], recs[j0 + f]);
+      if (o.seed_nearest && matched[j0 + f]) {  // the printed rows (finish_alignment sorted them): the m seed rows, then the new one
+        const std::vector<std::string> rows = row_texts(fa, roots[f]);
+        const std::vector<uint8_t> cell = cells_of(rows);
+        std::vector<uint8_t> cand(n, 1);
+        cand[m] = 0;
+        std::vector<uint32_t> near(n), ni(n), nd(n);
+        check(dafs_hip_alignment_identity(ctx, n, pl[f].width, cell.data(), pl[f].rf.data(), cand.data(), 0.0, nullptr, nullptr, nullptr,
+                                          near.data(), ni.data(), nd.data(), nullptr));
+        near_row[j0 + f] = near[m];
+        near_pid[j0 + f] = (double)ni[m] / (double)nd[m];
+      }
+    }
+  }
+  std::cout.flush();
+  write_outputs(o, wanted, recs, &headers);
+  if (!o.seed_merged.empty()) {  // all k placements in one alignment (DESIGN.md section 17): the seed rows, then the new rows
+    const Placement pl = place(sd, k, lens.data(), all_z.data());
+    std::vector<std::string> row_headers, rows;
+    std::vector<const double*> rr(m, nullptr);
+    for (uint32_t r = 0; r < m; ++r) {
+      row_headers.push_back(sd.names[r]);
+      rows.push_back(std::string(pl.width, '-'));
+      for (uint32_t c = 0; c < C; ++c) rows.back()[pl.seed_col[c]] = sd.rows[r][c];
+    }
+    for (uint32_t j = 0, off = 0; j < k; off += lens[j], ++j) {
+      row_headers.push_back(added[j].name());
+      rows.push_back(std::string(pl.width, '-'));
+      const std::string& sq = added[j].seq();
+      for (uint32_t i = 0; i < lens[j]; ++i) rows.back()[pl.res_col[off + i]] = sq[i];
+      rr.push_back(new_pp[j].data());
+    }
+    const VU carried = carry_structure(sd.ss, pl.seed_col, pl.width);
+    std::vector<char> brackets(pl.width + 1);
+    dafs_hip_make_brackets(pl.width, carried.data(), brackets.data());
+    const std::vector<std::string> names = stockholm_names(row_headers);
+    char* text = nullptr;
+    check_text(dafs_host_stockholm_block_merged(m + k, pl.width, c_strs(names).data(), c_strs(rows).data(), rr.data(), brackets.data(),
+                                                pl.rf.data(), nullptr, &text));
+    std::string block = take(text);
+    if (!o.compare.empty()) {  // the merged alignment in the seed's columns, with the PP classes of its own block
+      std::vector<std::string> pp(m, std::string());
+      pp.resize(m + k, std::string(pl.width, '.'));
+      for (uint32_t j = 0, off = 0; j < k; off += lens[j], ++j)
+        for (uint32_t i = 0; i < lens[j]; ++i) pp[m + j][pl.res_col[off + i]] = dafs_host_pp_char(new_pp[j][i]);
+      CompareText cmp;
+      compare_of(ctx, o, names, rows, &carried, pl.rf.data(), &pp, cmp);
+      write_compare(o, {cmp}, nullptr);
+    }
+    if (o.seed_nr_given) {  // the non-redundant rows (DESIGN.md section 18): the rows with a residue in a seed column are compared
+      std::vector<uint32_t> inc, pos(m + k, DAFS_HIP_NONE);
+      std::vector<std::string> inc_rows;
+      for (uint32_t r = 0; r < m + k; ++r)
+        if (r < m || matched[r - m]) {
+          pos[r] = (uint32_t)inc.size();
+          inc.push_back(r);
+          inc_rows.push_back(rows[r]);
+        }
+      const uint32_t ni = (uint32_t)inc.size();
+      const std::vector<uint8_t> cell = cells_of(inc_rows);
+      std::vector<uint32_t> red((size_t)ni * ((ni + 31) / 32));
+      check(dafs_hip_alignment_identity(ctx, ni, pl.width, cell.data(), pl.rf.data(), nullptr, o.seed_nr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                        nullptr, red.data()));
+      // the visiting order: the seed rows, then the new rows by descending score, ties in file order
+      std::vector<uint32_t> hits(k), rank;
+      for (uint32_t j = 0; j < k; ++j) hits[j] = j;
+      std::stable_sort(hits.begin(), hits.end(), [&](uint32_t a, uint32_t b) { return score[a] > score[b]; });
+      for (uint32_t r = 0; r < m; ++r) rank.push_back(r);
+      for (uint32_t j : hits)
+        if (pos[m + j] != DAFS_HIP_NONE) rank.push_back(pos[m + j]);
+      std::vector<uint8_t> forced(ni, 0), kept_inc(ni), kept(m + k, 1);
+      std::fill(forced.begin(), forced.begin() + m, 1);
+      std::vector<uint32_t> by(ni);
+      check_text(dafs_host_nr_select(ni, red.data(), rank.data(), forced.data(), kept_inc.data(), by.data()));
+      for (uint32_t q = 0; q < ni; ++q) kept[inc[q]] = kept_inc[q];
+      check_text(dafs_host_stockholm_nr(block.c_str(), m + k, c_strs(names).data(), kept.data(), m, o.seed_nr, &text));
+      block = take(text);
+    }
+    write_text("--seed-merged", o.seed_merged, block);
+  }
+  if (!o.seed_scores.empty()) {
+    std::vector<std::string> added_headers;
+    for (const Fasta& s : added) added_headers.push_back(s.name());
+    std::vector<std::string> near_name;  // --seed-nearest: the Stockholm names of the nearest seed rows
+    if (o.seed_nearest) {
+      const std::vector<std::string> seed_names = stockholm_names(sd.names);
+      for (uint32_t j = 0; j < k; ++j) near_name.push_back(near_row[j] == DAFS_HIP_NONE ? "-" : seed_names[near_row[j]]);
+    }
+    char* text = nullptr;
+    check_text(dafs_host_seed_table_nearest(k, c_strs(added_headers).data(), lens.data(), matched.data(), score.data(), iterations.data(),
+                                            o.seed_structure ? sup_both.data() : nullptr, o.seed_structure ? sup_can.data() : nullptr,
+                                            o.seed_structure ? sup_half.data() : nullptr, o.seed_structure ? sup_exp.data() : nullptr,
+                                            o.seed_nearest ? c_strs(near_name).data() : nullptr, o.seed_nearest ? near_pid.data() : nullptr, &text));
+    write_text("--seed-scores", o.seed_scores, take(text));
+  }
+  return 0;
+}
+
+// `dafs --pairwise FILE` (DESIGN.md section 12; pipeline.pairwise is the Python twin).  Phase 1 runs once over FILE's N
+// sequences in a source context, the folding beside the all-pairs posteriors and no transform; the pairs, row-major, go in
+// chunks under dafs_host_batch_bytes() through a second context, where dafs_hip_pairs_from gathers a chunk's two-sequence
+// families and align_group runs them as one batch of families.  Each pair prints "==> i j <==" and then what `dafs` prints
+// for a file of its two sequences.  Of the side outputs a pair has its Stockholm block alone.
+int run_pairwise(const Options& o, int align_model) {
+  std::vector<Fasta> fa;
+  Fasta::load(fa, o.input.c_str());
+  if (fa.size() < 2) throw std::string("--pairwise needs at least two sequences in the input");
+  const uint32_t N = (uint32_t)fa.size();
+  dafs_hip_ctx* src = nullptr;
+  check(dafs_hip_create(o.device, &src));
+  Guard src_guard{src};
+  set_sequences(src, fa);
+  check(dafs_hip_fold_posteriors_begin(src, DAFS_FOLD_CONTRAFOLD, kCutoff));
+  const int rc_align = dafs_hip_align_posteriors(src, align_model, o.align_th, 0, 0);
+  const int rc_fold = dafs_hip_fold_posteriors_end(src);
+  check(rc_align);
+  check(rc_fold);
+  std::vector<float> sim((size_t)N * N);
+  check(dafs_hip_get_sim(src, sim.data()));
+  dafs_hip_ctx* ctx = nullptr;
+  check(dafs_hip_create(o.device, &ctx));
+  Guard guard{ctx};
+
+  std::vector<std::pair<uint32_t, uint32_t> > pairs;
+  for (uint32_t x = 0; x < N; ++x)
+    for (uint32_t y = x + 1; y < N; ++y) pairs.push_back(std::make_pair(x, y));
+  std::vector<double> score(pairs.size(), 0.0);
+  std::vector<int64_t> iterations(pairs.size(), 0);
+  const unsigned wanted = wanted_of(o) & kSto;
+  std::vector<FamilyOut> recs = records(pairs.size(), wanted);
+  Ranks rk;  // one process
+  // the chunks: greedy in pair order under the estimated device memory of each pair, its phase-1 stores and its root node,
+  // which is resident for the whole chunk; a pair over the budget runs alone
+  std::vector<uint64_t> bytes(pairs.size());
+  for (size_t k = 0; k < pairs.size(); ++k) {
+    const uint32_t l[2] = {(uint32_t)fa[pairs[k].first].size(), (uint32_t)fa[pairs[k].second].size()};
+    bytes[k] = dafs_host_family_bytes(2, l) + dafs_host_node_bytes(l[0], l[1]);
+  }
+  for (const auto& chunk : chunks(bytes)) {
+    const size_t p0 = chunk.first, n = chunk.second - chunk.first;
+    PairChunk pc;
+    pc.src = src;
+    pc.score.assign(n, 0.0f);
+    pc.iterations.assign(n, 0);
+    std::vector<std::vector<Fasta> > fams;
+    std::vector<size_t> members;
+    std::vector<FamilyOut*> out;
+    for (size_t j = 0; j < n; ++j) {
+      pc.px.push_back(pairs[p0 + j].first);
+      pc.py.push_back(pairs[p0 + j].second);
+      fams.push_back({fa[pairs[p0 + j].first], fa[pairs[p0 + j].second]});
+      members.push_back(j);
+      out.push_back(&recs[p0 + j]);
+    }
+    align_group(ctx, o, rk, align_model, fams, members, out, &pc);
+    for (size_t j = 0; j < n; ++j) {
+      print_block(std::to_string(pairs[p0 + j].first + 1) + " " + std::to_string(pairs[p0 + j].second + 1), recs[p0 + j]);
+      score[p0 + j] = pc.score[j];
+      iterations[p0 + j] = pc.iterations[j];
+    }
+  }
+  std::cout.flush();
+  write_outputs(o, wanted, recs, nullptr);
+  if (!o.pairwise_scores.empty()) {
+    std::vector<uint32_t> px, py;
+    std::vector<double> psim;
+    std::vector<std::string> names;
+    for (const Fasta& s : fa) names.push_back(s.name());
+    for (const auto& pr : pairs) {
+      px.push_back(pr.first);
+      py.push_back(pr.second);
+      psim.push_back(sim[(size_t)pr.first * N + pr.second]);
+    }
+    char* text = nullptr;
+    check_text(dafs_host_pairwise_table(pairs.size(), px.data(), py.data(), N, c_strs(names).data(), psim.data(), score.data(), iterations.data(), &text));
+    write_text("--pairwise-scores", o.pairwise_scores, take(text));
+  }
+  return 0;
+}
+
+// `dafs --cluster T FILE` (DESIGN.md section 20; pipeline.cluster is the Python twin).  The similarity scores of all pairs come
+// from dafs_hip_similarity, which walks the pairs in ranges under the library's budget and keeps no store; the guide tree of
+// the whole set (with --cluster-linkage single, complete or average the linkage tree of dafs_hip_linkage_tree, DESIGN.md section
+// 21) is cut by dafs_host_cluster_cut; the clusters of at least --cluster-min-size members are the families of
+// align_group, as the FILEs of a run of several are: those of two or more sequences in sub-batches under
+// dafs_host_batch_bytes() of dafs_host_family_bytes, a cluster of one sequence on the single-sequence path.  Each printed
+// cluster is "==> cluster c <==" and then what `dafs` prints for a file of its sequences.
+int run_cluster(const Options& o, int align_model) {
+  std::vector<Fasta> fa;
+  Fasta::load(fa, o.input.c_str());
+  if (fa.empty()) throw "no sequences in the input";
+  const uint32_t N = (uint32_t)fa.size();
+  if (o.cluster_count_given && o.cluster_count > N)
+    throw "--cluster-count: " + std::to_string(o.cluster_count) + " clusters asked of " + std::to_string(N) + " sequences";
+  dafs_hip_ctx* ctx = nullptr;
+  check(dafs_hip_create(o.device, &ctx));
+  Guard guard{ctx};
+  std::vector<float> sim((size_t)N * N, 1.0f);
+  if (N > 1) {
+    set_sequences(ctx, fa);
+    check(dafs_hip_similarity(ctx, align_model, o.align_th, 0, nullptr));
+    check(dafs_hip_get_sim(ctx, sim.data()));
+  }
+  std::vector<float> score(2 * N - 1);
+  std::vector<int32_t> left(2 * N - 1), right(2 * N - 1);
+  if (o.cluster_linkage == 0) check(dafs_host_build_tree(N, sim.data(), score.data(), left.data(), right.data()));
+  else if (N == 1) { score[0] = 0.0f; left[0] = right[0] = -1; }  // the one-leaf tree
+  else check_text(dafs_hip_linkage_tree(ctx, o.cluster_linkage, N, nullptr, score.data(), left.data(), right.data()));  // on the block the pass left on the device
+  std::vector<uint32_t> labels(N);
+  uint32_t K = 0;
+  check_text(dafs_host_cluster_cut(N, score.data(), left.data(), right.data(), o.cluster_given ? DAFS_CLUSTER_THRESHOLD : DAFS_CLUSTER_COUNT,
+                                   (float)o.cluster, o.cluster_count, labels.data(), &K));
+  if (!o.cluster_table.empty()) {
+    std::vector<std::string> headers;
+    std::vector<uint32_t> lens;
+    for (const Fasta& s : fa) { headers.push_back(s.name()); lens.push_back(s.size()); }
+    char* text = nullptr;
+    check_text(dafs_host_cluster_table(N, c_strs(headers).data(), lens.data(), labels.data(), score.data(), left.data(), right.data(), sim.data(), &text));
+    write_text("--cluster-table", o.cluster_table, take(text));
+  }
+  if (!o.cluster_tree.empty()) {
+    std::vector<node_t> tree(2 * N - 1);
+    for (uint i = 0; i < 2 * N - 1; ++i) tree[i] = std::make_pair(score[i], std::make_pair((uint)left[i], (uint)right[i]));
+    std::ostringstream tl;
+    print_tree(tl, tree, fa, (int)tree.size() - 1);
+    tl << std::endl;
+    write_text("--cluster-tree", o.cluster_tree, tl.str());
+  }
+  // the clusters that are aligned, as the families of a run of several files
+  std::vector<std::vector<Fasta> > all(K);
+  for (uint32_t i = 0; i < N; ++i) all[labels[i]].push_back(fa[i]);
+  std::vector<std::vector<Fasta> > fams;
+  std::vector<std::string> headers;
+  for (uint32_t c = 0; c < K; ++c)
+    if (all[c].size() >= o.cluster_min_size) {
+      fams.push_back(all[c]);
+      headers.push_back("cluster " + std::to_string(c + 1));
+    }
+  const size_t P = fams.size();
+  const unsigned wanted = wanted_of(o) & ~kCmp;
+  std::vector<FamilyOut> recs = records(P, wanted);
+  Ranks rk;  // one process
+  auto group = [&](const std::vector<size_t>& members) {
+    std::vector<FamilyOut*> out;
+    for (size_t f : members) out.push_back(&recs[f]);
+    align_group(ctx, o, rk, align_model, fams, members, out);
+  };
+  std::vector<size_t> batch;
+  std::vector<uint64_t> bytes;
+  for (size_t f = 0; f < P; ++f)
+    if (fams[f].size() > 1) {
+      std::vector<uint32_t> lens;
+      for (const Fasta& s : fams[f]) lens.push_back(s.size());
+      batch.push_back(f);
+      bytes.push_back(dafs_host_family_bytes((uint32_t)lens.size(), lens.data()));
+    }
+  for (const auto& chunk : chunks(bytes)) group(std::vector<size_t>(batch.begin() + chunk.first, batch.begin() + chunk.second));
+  for (size_t f = 0; f < P; ++f)
+    if (fams[f].size() == 1) group({f});
+  for (size_t f = 0; f < P; ++f) print_block(headers[f], recs[f]);
+  std::cout.flush();
+  write_outputs(o, wanted, recs, &headers);
+  return 0;
+}
+
+// `dafs --describe ALIGNMENT` (DESIGN.md section 18; pipeline.describe is the Python twin): the calls that read an alignment
+// alone, on a finished alignment that the seed reader reads.  Nothing is aligned and nothing is printed.
+int run_describe(const Options& o) {
+  std::vector<std::string> headers, rows;
+  VU ss;
+  read_seed(o.describe, headers, rows, &ss, true);
+  const std::vector<std::string> names = stockholm_names(headers);
+  dafs_hip_ctx* ctx = nullptr;
+  check(dafs_hip_create(o.device, &ctx));
+  Guard guard{ctx};
+  if (!o.identity.empty()) {
+    IdentityText idt;
+    identity_of(ctx, names, rows, !o.identity_matrix.empty(), idt);
+    write_identity(o, {idt}, nullptr);
+  }
+  if (!o.covariation.empty()) {
+    std::string cov, chars;
+    covariation_of(ctx, o, rows, ss, cov, chars);
+    write_text("--covariation", o.covariation, cov);
+  }
+  if (!o.compare.empty()) {  // the file again: whether it has a structure, and its PP lines
+    std::vector<std::string> h2, r2, pp;
+    VU ss2;
+    bool has_ss = false;
+    read_alignment(o.describe, "--describe", h2, r2, ss2, has_ss, &pp);
+    CompareText cmp;
+    compare_of(ctx, o, names, rows, has_ss ? &ss2 : nullptr, nullptr, pp.empty() ? nullptr : &pp, cmp);
+    write_compare(o, {cmp}, nullptr);
+  }
+  return 0;
+}
+
+int run(const Options& o, Ranks& rk) {
+  // ---- option checks mirroring parse_options (:1683-1763)
+  int align_model;
+  if (o.align_model == "ProbCons") align_model = DAFS_ALIGN_PROBCONS;
+  else if (o.align_model == "CONTRAlign") align_model = DAFS_ALIGN_CONTRALIGN;
+  else throw "Unknown alignment model: " + o.align_model;
+  if (o.fold_aux.empty()) {
+    if (o.fold_model == "Boltzmann" || o.fold_model == "Vienna")
+      throw "Folding model " + o.fold_model + " needs ViennaRNA, which this build does not contain; use -s CONTRAfold or --fold-aux";
+    if (o.fold_model != "CONTRAfold") throw "Unknown folding model: " + o.fold_model;
+  }
+  if (o.fold_decoder != "Nussinov" || o.ipknot) throw "Folding decoder IPknot needs an ILP solver, which this build does not contain";
+  if (o.max_iter <= 0) throw "-m 0 (exact ILP) needs an ILP solver, which this build does not contain";
+  if ((o.bp_update || o.bp_update1) && !o.fold_aux.empty()) throw "--bp-update / --bp-update1 need a folding model (-s CONTRAfold), not --fold-aux";
+  if (!o.devices.empty() && (!o.fold_aux.empty() || !o.align_aux.empty() || o.fourway != 0.0f))
+    throw std::string("--devices shards the posterior models and the consistency transform; --fold-aux, --align-aux and -f run on one device (--device)");
+  if (o.verbose >= 1) {
+    if (!o.no_alifold) std::cerr << "note: RNAalifold is not available in this build; running as with --no-alifold" << std::endl;
+    if (!o.fold_model_given && o.fold_aux.empty()) std::cerr << "note: default folding model is CONTRAfold in this build" << std::endl;
+  }
+  if (!o.describe.empty()) return rk.rank == 0 ? run_describe(o) : 0;
+  if (!o.seed.empty()) return o.seed_each ? run_add_each(o, align_model) : run_add(o, align_model);
+  if (o.pairwise) return run_pairwise(o, align_model);
+  if (o.cluster_given || o.cluster_count_given) return run_cluster(o, align_model);
+
+  // one family per input file
+  const bool multi = o.inputs.size() > 1;
+  std::vector<std::vector<Fasta> > fams(o.inputs.size());
+  for (size_t f = 0; f < o.inputs.size(); ++f) {
+    const std::string& file = o.inputs[f];
+    try {
+      Fasta::load(fams[f], file.c_str());
+    } catch (const std::system_error& e) {
+      if (multi) throw file + ": " + e.code().message();
+      throw;
+    }
+    if (fams[f].empty()) {
+      if (multi) throw file + ": no sequences in the input";
+      throw "no sequences in the input";
+    }
+  }
+
+  dafs_hip_ctx* ctx = nullptr;
+  check(dafs_hip_create(o.devices.empty() ? o.device : o.devices[rk.rank], &ctx));
+  Guard guard{ctx};
+
+  // one record per input file, in input order; the files are written by the process that prints
+  const unsigned wanted = wanted_of(o);
+  std::vector<FamilyOut> recs = records(o.inputs.size(), wanted);
+  if (!multi) {  // printed as it is made
+    recs[0].os = &std::cout;
+    align_group(ctx, o, rk, align_model, fams, {0}, {&recs[0]});
+    if (rk.rank == 0) write_outputs(o, wanted, recs, nullptr);
+    return 0;
+  }
+  // Several files: every file with two or more sequences in one batch (dafs_hip_set_families: shared launches, one guide
+  // tree per family, the forest walked together); a file of one sequence takes the single-sequence path of a run of its
+  // own (no pairs, no consistency transforms) on the same context.  Each block is what `dafs FILE` prints.
+  std::vector<size_t> batch;
+  for (size_t f = 0; f < fams.size(); ++f)
+    if (fams[f].size() > 1) batch.push_back(f);
+  auto names = [&](const std::vector<size_t>& members) {
+    std::string s;
+    for (size_t f : members) s += (s.empty() ? "" : ", ") + o.inputs[f];
+    return s;
+  };
+  auto group = [&](const std::vector<size_t>& members) {
+    std::vector<FamilyOut*> out;
+    for (size_t f : members) out.push_back(&recs[f]);
+    try {
+      align_group(ctx, o, rk, align_model, fams, members, out);
+    } catch (const char* str) {
+      throw names(members) + ": " + str;
+    } catch (const std::string& str) {
+      throw names(members) + ": " + str;
+    }
+  };
+  if (!batch.empty()) group(batch);
+  for (size_t f = 0; f < fams.size(); ++f)
+    if (fams[f].size() == 1) group({f});
+  for (size_t f = 0; f < fams.size(); ++f) print_block(o.inputs[f], recs[f]);
+  std::cout.flush();
+  write_outputs(o, wanted, recs, &o.inputs);
   return 0;
 }
 

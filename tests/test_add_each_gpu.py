@@ -175,3 +175,25 @@ def test_cli_equals_python_and_single_sequence_files(tmp_path):
         one = tmp_path / ("one_%d.fa" % j)
         one.write_text(synth.to_fasta([(names[j], seqs[j])]))
         assert blocks[j] == "%d <==\n" % (j + 1) + _cli("--seed", seed_sto, one)
+
+
+def test_cli_covariation_and_row_structures_equal_python(tmp_path):
+    """--seed-each with --covariation and --stockholm --row-structures: per new sequence a table under its "==> j <==" line and a
+    block with the #=GR SS lines and the cov_SS_cons line, all the Python driver's"""
+    snames, srows, names, seqs, _ = _inputs()
+    pick = [0, 5, 6]  # a family member, the unrelated one, the 9-nt one
+    names, seqs = [names[j] for j in pick], [seqs[j] for j in pick]
+    new_fa, seed_sto = tmp_path / "new.fa", tmp_path / "seed.sto"
+    new_fa.write_text(synth.to_fasta(list(zip(names, seqs))))
+    _write_sto(seed_sto, snames, srows)
+    want = pipeline.add_each(snames, srows, names, seqs, reliability=True, row_structures=True, covariation=dict(shuffles=20, seed=5))
+    sto, cov = tmp_path / "out.sto", tmp_path / "cov.tsv"
+    out = _cli("--seed", seed_sto, "--seed-each", "--stockholm", sto, "--row-structures", "--covariation", cov, "--cov-shuffles", 20,
+               "--cov-seed", 5, new_fa)
+    heads = ["==> %d <==\n" % (j + 1) for j in range(len(names))]
+    assert out == "".join(h + r.output for h, r in zip(heads, want.results))
+    assert sto.read_text() == "".join(r.stockholm for r in want.results)
+    lines = sto.read_text().split("\n")
+    assert sum(1 for ln in lines if ln.startswith("#=GR ") and ln.split()[2] == "SS") == len(names) * (len(snames) + 1)
+    assert sum(1 for ln in lines if ln.startswith("#=GC cov_SS_cons")) == len(names)
+    assert cov.read_text() == "".join(h + pipeline.covariation_tsv(r) for h, r in zip(heads, want.results))

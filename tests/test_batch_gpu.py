@@ -171,6 +171,29 @@ def test_cli_several_files(tmp_path):
     assert rc == 1 and "missing.fa" in err and out == ""
 
 
+def test_cli_several_files_row_structures(tmp_path):
+    """`dafs --stockholm OUT --row-structures A B C`: one block per file with a #=GR SS line per row, each the Python driver's; a
+    file of one sequence among them"""
+    from dafs_amd import pipeline
+    fams = [_split(synth.family_set(4, 50, seed=91)), _split(synth.random_set(3, 40, seed=92)), _split(synth.random_set(1, 30, seed=93))]
+    files = []
+    for k, (names, seqs) in enumerate(fams):
+        p = tmp_path / ("rs%d.fa" % k)
+        p.write_text(synth.to_fasta(list(zip(names, seqs))))
+        files.append(str(p))
+    sto = str(tmp_path / "out.sto")
+    rc, out, err = _run_cli("--stockholm", sto, "--row-structures", *files)
+    assert rc == 0, err
+    ctx = _ctx()
+    try:
+        want = pipeline.run_batch(fams, ctx=ctx, reliability=True, row_structures=True)
+    finally:
+        ctx.close()
+    assert out == "".join("==> %s <==\n" % f + r.output for f, r in zip(files, want))
+    assert open(sto).read() == "".join(r.stockholm for r in want)
+    assert sum(1 for ln in open(sto).read().split("\n") if ln.startswith("#=GR ") and ln.split()[2] == "SS") == 8
+
+
 def test_errors_leave_the_context_usable():
     from dafs_amd import capi, pipeline
     good = [_split(synth.family_set(4, 60, seed=81)), _split(synth.random_set(3, 50, seed=82))]

@@ -216,3 +216,27 @@ def test_cli_cluster_equals_python_and_files_of_the_clusters(ctx, tmp_path):
     out2 = _cli("--cluster-count", len(res.clusters), "--cluster-min-size", 2, "--cluster-table", tsv2, fa)
     assert out2 == "".join("==> cluster %d <==\n" % (c + 1) + r.output for c, r in enumerate(res.results) if len(res.clusters[c]) >= 2)
     assert tsv2.read_text() == res.table
+
+
+def test_cli_cluster_side_outputs_equal_python(ctx, tmp_path):
+    """--stockholm with --row-structures, --covariation and --identity with --identity-matrix under --cluster: one block or table
+    per printed cluster, the tables under the cluster's header line, all the Python driver's; a cluster of one sequence among them"""
+    names, seqs = _small()
+    threshold = _middle_join(_full_sim(ctx, seqs, capi.ALIGN_PROBCONS))
+    res = pipeline.cluster(names, seqs, threshold=threshold, ctx=ctx, reliability=True, row_structures=True, identity=True,
+                           covariation=dict(shuffles=20, seed=3))
+    assert len(res.clusters) > 1 and min(len(m) for m in res.clusters) == 1
+    fa = tmp_path / "six.fa"
+    fa.write_text(synth.to_fasta(list(zip(names, seqs))))
+    sto, cov, idt, mat = tmp_path / "out.sto", tmp_path / "cov.tsv", tmp_path / "id.tsv", tmp_path / "id.mat"
+    out = _cli("--cluster", repr(threshold), "--stockholm", sto, "--row-structures", "--covariation", cov, "--cov-shuffles", 20, "--cov-seed", 3,
+               "--identity", idt, "--identity-matrix", mat, fa)
+    heads = ["==> cluster %d <==\n" % (c + 1) for c in range(len(res.clusters))]
+    assert out == "".join(h + r.output for h, r in zip(heads, res.results))
+    assert sto.read_text() == "".join(r.stockholm for r in res.results)
+    lines = sto.read_text().split("\n")
+    assert sum(1 for ln in lines if ln.startswith("#=GR ") and ln.split()[2] == "SS") == len(seqs)
+    assert sum(1 for ln in lines if ln.startswith("#=GS ") and ln.split()[2] == "WT") == len(seqs)
+    assert cov.read_text() == "".join(h + pipeline.covariation_tsv(r) for h, r in zip(heads, res.results))
+    assert idt.read_text() == "".join(h + pipeline.identity_tsv(r.row_names, r.identity) for h, r in zip(heads, res.results))
+    assert mat.read_text() == "".join(h + pipeline.identity_matrix_tsv(r.row_names, r.identity) for h, r in zip(heads, res.results))
