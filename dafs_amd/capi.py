@@ -220,6 +220,13 @@ _alignment_reliabilities = _sig("dafs_hip_alignment_reliabilities", C.c_int,
                                 [C.c_void_p, C.c_uint32] + [C.c_void_p] * 6 + [C.c_int, C.c_int] + [C.c_void_p] * 5)
 _alignment_covariation = _sig("dafs_hip_alignment_covariation", C.c_int,
                               [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64] + [C.c_void_p] * 11)
+_alignment_covariation_null = _sig("dafs_hip_alignment_covariation_null", C.c_int,
+                                   [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_int, C.c_void_p,
+                                    C.c_void_p] + [C.c_void_p] * 11)
+_covariation_null_alignment = _sig("dafs_hip_covariation_null_alignment", C.c_int,
+                                   [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32,
+                                    C.c_void_p])
+COV_NULLS = ("shuffle", "tree")  # --cov-null; the index is the library's DAFS_COV_NULL_* code
 _alignment_identity = _sig("dafs_hip_alignment_identity", C.c_int,
                            [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double] + [C.c_void_p] * 7)
 _alignment_weights = _sig("dafs_hip_alignment_weights", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p])
@@ -958,21 +965,18 @@ class Context:
                 for a in range(len(als))]
 
 
-    def alignment_covariation(self, rows, ss=None, shuffles=100, seed=1, matrix=False):
-        """Covariation statistics of an alignment (dafs_hip_alignment_covariation).  rows: the text
-        rows, or their codes (uint8 [n, len], encode_alignment).  ss: the consensus structure or None.  shuffles, seed: the
-        column-shuffle null behind the E-values (0: no null, every E is NaN).  Returns a dict of numpy arrays per column:
-        col_sum (int64), best, best_score, best_e, and at the left column of each pair of ss pair_score, pair_e, pair_rows,
-        pair_canonical, pair_types; total (int); with matrix, g (int64 [len, len])."""
-        if isinstance(rows, np.ndarray) and rows.ndim == 2 and rows.dtype.kind in "iu":  # codes: any integer type, checked
-            if rows.size and (rows.min() < 0 or rows.max() > 255):
-                raise ValueError("alignment_covariation: codes must fit a byte (the library refuses a code above 4)")
-            code = np.ascontiguousarray(rows, np.uint8)
-        elif isinstance(rows, np.ndarray):
-            raise ValueError("alignment_covariation: rows are text rows or a 2-D integer array of codes")
-        else:
-            code = encode_alignment(rows)
+    def alignment_covariation(self, rows, ss=None, shuffles=100, seed=1, matrix=False, null="shuffle", tree=None):
+        """Covariation statistics of an alignment (dafs_hip_alignment_covariation_null).  rows: the text
+        rows, or their codes (uint8 [n, len], encode_alignment).  ss: the consensus structure or None.  shuffles, seed: how
+        many null alignments stand behind the E-values (0: no null, every E is NaN) and their seed.  null: one of COV_NULLS,
+        "shuffle" (every column permuted on its own; it ignores phylogeny) or "tree" (the substitutions of every branch of a
+        tree over the rows, moved to other columns); tree: with "tree", a (left, right) pair in build_tree's layout, None for
+        average linkage on the rows' identities.  Returns a dict of numpy arrays per column: col_sum (int64), best,
+        best_score, best_e, and at the left column of each pair of ss pair_score, pair_e, pair_rows, pair_canonical,
+        pair_types; total (int); with matrix, g (int64 [len, len])."""
+        code = _cov_codes(rows, "alignment_covariation")
         n, L = code.shape
+        which, left, right = _cov_null(null, tree, n, "alignment_covariation")
         ss = None if ss is None else np.ascontiguousarray(ss, np.uint32)
         if ss is not None and ss.shape != (L,):
             raise ValueError("alignment_covariation: ss needs one entry per column")
@@ -981,13 +985,25 @@ class Context:
                    pair_rows=np.zeros(L, np.uint32), pair_canonical=np.zeros(L, np.uint32), pair_types=np.zeros(L, np.uint32))
         total = C.c_int64()
         g = np.zeros((L, L), np.int64) if matrix else None
-        check(_alignment_covariation(self._h, n, L, code.ctypes.data, None if ss is None else ss.ctypes.data, int(shuffles), int(seed),
-                                     *[out[k].ctypes.data for k in ("col_sum", "best", "best_score", "best_e", "pair_score", "pair_e",
-                                                                     "pair_rows", "pair_canonical", "pair_types")],
-                                     C.byref(total), None if g is None else g.ctypes.data))
+        check(_alignment_covariation_null(self._h, n, L, code.ctypes.data, None if ss is None else ss.ctypes.data, int(shuffles), int(seed),
+                                          which, None if left is None else left.ctypes.data, None if right is None else right.ctypes.data,
+                                          *[out[k].ctypes.data for k in ("col_sum", "best", "best_score", "best_e", "pair_score", "pair_e",
+                                                                          "pair_rows", "pair_canonical", "pair_types")],
+                                          C.byref(total), None if g is None else g.ctypes.data))
         out["total"] = total.value
         if matrix:
             out["g"] = g
+        return out
+
+    def covariation_null_alignment(self, rows, k, null="shuffle", tree=None, seed=1):
+        """Null alignment k (0-based) behind the E-values of alignment_covariation(rows, seed=seed, null=null, tree=tree), as
+        codes (uint8 [n, len]; dafs_hip_covariation_null_alignment)."""
+        code = _cov_codes(rows, "covariation_null_alignment")
+        n, L = code.shape
+        which, left, right = _cov_null(null, tree, n, "covariation_null_alignment")
+        out = np.zeros((n, L), np.uint8)
+        check(_covariation_null_alignment(self._h, n, L, code.ctypes.data, which, None if left is None else left.ctypes.data,
+                                          None if right is None else right.ctypes.data, int(seed), int(k), out.ctypes.data))
         return out
 
 
@@ -1123,6 +1139,33 @@ def build_tree(sim):
     score = np.zeros(2 * n - 1, np.float32); left = np.zeros(2 * n - 1, np.int32); right = np.zeros(2 * n - 1, np.int32)
     check(_build_tree(n, sim.ctypes.data, score.ctypes.data, left.ctypes.data, right.ctypes.data))
     return score, left.astype(np.int64), right.astype(np.int64)
+
+
+def _cov_codes(rows, who):
+    """text rows, or a 2-D integer array of codes (any integer type, checked) -> uint8 [n, len]"""
+    if isinstance(rows, np.ndarray) and rows.ndim == 2 and rows.dtype.kind in "iu":
+        if rows.size and (rows.min() < 0 or rows.max() > 255):
+            raise ValueError("%s: codes must fit a byte (the library refuses a code above 4)" % who)
+        return np.ascontiguousarray(rows, np.uint8)
+    if isinstance(rows, np.ndarray):
+        raise ValueError("%s: rows are text rows or a 2-D integer array of codes" % who)
+    return encode_alignment(rows)
+
+
+def _cov_null(null, tree, n, who):
+    """(the library's code of the null, left, right as int32 arrays or None).  What cannot be handed over is a ValueError
+    here; everything else (a tree under "shuffle", a malformed tree) is the library's to refuse."""
+    if null not in COV_NULLS:
+        raise ValueError("%s: unknown null %r (one of %s)" % (who, null, ", ".join(COV_NULLS)))
+    if tree is None:
+        return COV_NULLS.index(null), None, None
+    if len(tree) != 2:
+        raise ValueError("%s: tree is a (left, right) pair" % who)
+    left, right = (None if a is None else np.ascontiguousarray(a, np.int32) for a in tree)
+    for a in (left, right):
+        if a is not None and a.shape != (2 * n - 1,):
+            raise ValueError("%s: a tree of n rows has 2n - 1 nodes" % who)
+    return COV_NULLS.index(null), left, right
 
 
 def linkage_check(rule, sim=None):

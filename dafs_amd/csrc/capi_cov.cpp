@@ -1,9 +1,12 @@
-// dafs_amd/csrc/capi_cov.cpp -- dafs_hip_alignment_covariation: how far the sequences of an alignment support its column pairs
-// (cov.hip; definitions in DESIGN.md section 13).  The reference has no counterpart.  The call reads the alignment's codes and
-// the structure alone, none of the context's stores, so it annotates any alignment.
+// dafs_amd/csrc/capi_cov.cpp -- dafs_hip_alignment_covariation[_null]: how far the sequences of an alignment support its column
+// pairs (cov.hip; definitions in DESIGN.md section 13), and dafs_hip_covariation_null_alignment: one alignment of its null.  The
+// reference has no counterpart.  The calls read the alignment's codes and the structure alone, none of the context's stores, so
+// they annotate any alignment.
 //
 // Host work: the checks, the table of fixed-point logarithms, the order of the passes, the sorted candidate scores of the
-// null and the suffix sum that turns its bucket counters into tails.
+// null and the suffix sum that turns its bucket counters into tails; for the tree null the checks of the caller's tree and its
+// parents, or the default tree: the identity matrices of dafs_hip_alignment_identity, divided on the host, joined by
+// dafs_hip_linkage_tree under the average rule (both through host memory, so n <= 32768 there).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdlib.h>
@@ -16,6 +19,7 @@
 #include "cov.h"
 #include "ctx.h"
 #include "hip_util.h"
+#include "last_error.h"
 
 using namespace dafs;
 
@@ -46,17 +50,142 @@ struct stream_drain {
   ~stream_drain() { (void)hipStreamSynchronize(st); }
 };
 
+int refuse(const char* what) {
+  set_last_error(what);
+  return DAFS_HIP_EINVAL;
+}
+
+// what the arguments say about the null, before anything is read through them
+int null_args_check(int null, const int32_t* tree_left, const int32_t* tree_right) {
+  if (null != DAFS_COV_NULL_SHUFFLE && null != DAFS_COV_NULL_TREE) return refuse("covariation: unknown null");
+  if (null == DAFS_COV_NULL_SHUFFLE && (tree_left || tree_right)) return refuse("covariation: the shuffle null takes no tree");
+  if (!tree_left != !tree_right) return refuse("covariation: a tree needs both of its arrays");
+  return DAFS_HIP_OK;
+}
+
+// tree = left, right, parent of the 2n-1 nodes, one after the other.  The caller's arrays pass the checks of
+// dafs_host_cluster_cut; without them it is the default tree of DESIGN.md section 13.
+int tree_of(dafs_hip_ctx* c, uint32_t n, uint32_t len, const uint8_t* code, const int32_t* tree_left, const int32_t* tree_right,
+            std::vector<int32_t>& tree) {
+  const size_t T = 2 * (size_t)n - 1;
+  tree.assign(3 * T, -1);
+  int32_t *left = tree.data(), *right = left + T, *parent = right + T;
+  if (tree_left) {
+    std::copy(tree_left, tree_left + T, left);
+    std::copy(tree_right, tree_right + T, right);
+  } else {
+    if (n > 32768) return refuse("covariation: the default tree takes at most 32768 rows (pass a tree)");
+    std::vector<uint8_t> cell((size_t)n * len);
+    for (uint32_t r = 0; r < n; ++r) {
+      bool any = false;
+      for (uint32_t col = 0; col < len; ++col) {
+        const uint8_t v = code[(size_t)r * len + col];
+        cell[(size_t)r * len + col] = v == 4 ? 5 : v;  // the gap code of dafs_hip_alignment_identity: matches and aligns with nothing
+        any = any || v < 4;
+      }
+      if (!any) return refuse("covariation: the default tree needs a base in every row");
+    }
+    std::vector<uint32_t> ident((size_t)n * n), both((size_t)n * n);
+    int rc = dafs_hip_alignment_identity(c, n, len, cell.data(), nullptr, nullptr, 0.0, nullptr, ident.data(), both.data(), nullptr, nullptr,
+                                         nullptr, nullptr);
+    if (rc) return rc;
+    std::vector<float> sim((size_t)n * n, 0.0f), score(T);
+    for (uint32_t r = 0; r < n; ++r)
+      for (uint32_t s = r + 1; s < n; ++s) {
+        const size_t at = (size_t)r * n + s;
+        sim[at] = both[at] ? (float)((double)ident[at] / (double)both[at]) : 0.0f;
+      }
+    if ((rc = dafs_hip_linkage_tree(c, DAFS_LINKAGE_AVERAGE, n, sim.data(), score.data(), left, right))) return rc;
+  }
+  for (size_t i = 0; i < T; ++i) {
+    if (i < n) {
+      if (left[i] != -1 || right[i] != -1) return refuse("covariation: malformed tree (a leaf with a child)");
+      continue;
+    }
+    if (left[i] == right[i]) return refuse("covariation: malformed tree (a join of a node with itself)");
+    for (const int64_t ch : {(int64_t)left[i], (int64_t)right[i]}) {
+      if (ch < 0 || ch >= (int64_t)i) return refuse("covariation: malformed tree (a child that is not an earlier node)");
+      if (parent[ch] != -1) return refuse("covariation: malformed tree (a node that is a child twice)");
+      parent[ch] = (int32_t)i;
+    }
+  }
+  return DAFS_HIP_OK;  // 2n - 2 child slots hold distinct nodes below the root: every node but the root has its parent
+}
+
+int input_check(dafs_hip_ctx* c, uint32_t n, uint32_t len, const uint8_t* code) {
+  if (!c || !n || !len || !code) return DAFS_HIP_EINVAL;
+  if (n > (1u << 20) || (double)n * (double)len * (double)len > 35184372088832.0) return DAFS_HIP_EINVAL;  // 2^45: T fits an int64
+  if (hip_check(hipSetDevice(c->device))) return DAFS_HIP_ENODEV;
+  for (size_t k = 0; k < (size_t)n * len; ++k)
+    if (code[k] > 4) return DAFS_HIP_EINVAL;
+  return DAFS_HIP_OK;
+}
+
+// DAFS_COV_TREE_LDS=0 (read per call): k_cov_evolve keeps the joins' states in global memory at every n (tests reach that
+// form at a small n)
+bool evolve_in_lds(uint32_t n) {
+  const char* e = getenv("DAFS_COV_TREE_LDS");
+  if (e && *e && strtol(e, nullptr, 10) == 0) return false;
+  return cov_evolve_fits_lds(n);
+}
+
+uint64_t null_base(uint64_t seed, uint32_t k) { return mix64(seed + 0x9E3779B97F4A7C15ull * ((uint64_t)k + 1)); }
+
 }  // namespace
 
 extern "C" int dafs_hip_alignment_covariation(dafs_hip_ctx* c, uint32_t n, uint32_t len, const uint8_t* code, const uint32_t* ss,
                                               uint32_t shuffles, uint64_t seed, int64_t* col_sum, uint32_t* best, double* best_score,
                                               double* best_e, double* pair_score, double* pair_e, uint32_t* pair_rows,
                                               uint32_t* pair_canonical, uint32_t* pair_types, int64_t* total, int64_t* g) {
-  if (!c || !n || !len || !code) return DAFS_HIP_EINVAL;
-  if (n > (1u << 20) || (double)n * (double)len * (double)len > 35184372088832.0) return DAFS_HIP_EINVAL;  // 2^45: T fits an int64
-  if (hip_check(hipSetDevice(c->device))) return DAFS_HIP_ENODEV;
-  for (size_t k = 0; k < (size_t)n * len; ++k)
-    if (code[k] > 4) return DAFS_HIP_EINVAL;
+  return dafs_hip_alignment_covariation_null(c, n, len, code, ss, shuffles, seed, DAFS_COV_NULL_SHUFFLE, nullptr, nullptr, col_sum, best,
+                                             best_score, best_e, pair_score, pair_e, pair_rows, pair_canonical, pair_types, total, g);
+}
+
+extern "C" int dafs_hip_covariation_null_alignment(dafs_hip_ctx* c, uint32_t n, uint32_t len, const uint8_t* code, int null,
+                                                   const int32_t* tree_left, const int32_t* tree_right, uint64_t seed, uint32_t k,
+                                                   uint8_t* out_code) {
+  int rc;
+  if ((rc = null_args_check(null, tree_left, tree_right))) return rc;
+  if (!out_code) return DAFS_HIP_EINVAL;
+  if ((rc = input_check(c, n, len, code))) return rc;
+  const bool by_tree = null == DAFS_COV_NULL_TREE;
+  std::vector<int32_t> tree;
+  if (by_tree && (tree_left || n >= 2) && (rc = tree_of(c, n, len, code, tree_left, tree_right, tree))) return rc;
+  if (n < 2) {  // one row: nothing to permute, no branch to change on; no launch
+    std::copy(code, code + len, out_code);
+    return DAFS_HIP_OK;
+  }
+  const size_t cells = (size_t)n * len, T = 2 * (size_t)n - 1;
+  size_t used = 0;
+  auto take = [&](size_t bytes) { const size_t at = used; used += (bytes + 255) & ~(size_t)255; return at; };
+  const size_t o_code = take(cells), o_out = take(cells), o_node = take(by_tree ? T * len : 0), o_chg = take(by_tree ? T * len : 0);
+  const size_t o_tree = take(by_tree ? 3 * T * 4 : 0);
+  if ((rc = c->work.reserve(used + 256))) return rc;
+  uint8_t* w = c->work.ptr;
+  hipStream_t st = c->stream;
+  stream_drain drain{st};
+  if (hip_check(hipMemcpyAsync(w + o_code, code, cells, hipMemcpyHostToDevice, st))) return DAFS_HIP_ELAUNCH;
+  if (by_tree) {
+    if (hip_check(hipMemcpyAsync(w + o_tree, tree.data(), 3 * T * 4, hipMemcpyHostToDevice, st))) return DAFS_HIP_ELAUNCH;
+    const int32_t* d_tree = (const int32_t*)(w + o_tree);
+    const cov_tree t = {d_tree, d_tree + T, d_tree + 2 * T};
+    if ((rc = cov_fitch(w + o_code, t, n, len, w + o_node, w + o_chg, st))) return rc;
+    if ((rc = cov_evolve(w + o_code, w + o_chg, t, n, len, null_base(seed, k), w + o_node, w + o_out, evolve_in_lds(n), st))) return rc;
+  } else if ((rc = cov_shuffle(w + o_code, w + o_out, n, len, null_base(seed, k), st))) {
+    return rc;
+  }
+  if (hip_check(hipMemcpyAsync(out_code, w + o_out, cells, hipMemcpyDeviceToHost, st))) return DAFS_HIP_ELAUNCH;
+  return hip_check(hipStreamSynchronize(st)) ? DAFS_HIP_ELAUNCH : DAFS_HIP_OK;
+}
+
+extern "C" int dafs_hip_alignment_covariation_null(dafs_hip_ctx* c, uint32_t n, uint32_t len, const uint8_t* code, const uint32_t* ss,
+                                                   uint32_t shuffles, uint64_t seed, int null, const int32_t* tree_left,
+                                                   const int32_t* tree_right, int64_t* col_sum, uint32_t* best, double* best_score,
+                                                   double* best_e, double* pair_score, double* pair_e, uint32_t* pair_rows,
+                                                   uint32_t* pair_canonical, uint32_t* pair_types, int64_t* total, int64_t* g) {
+  int rc;
+  if ((rc = null_args_check(null, tree_left, tree_right))) return rc;
+  if ((rc = input_check(c, n, len, code))) return rc;
   std::vector<uint32_t> lefts;
   if (ss) {  // left column -> right column, each column in at most one pair (as dafs_hip_alignment_reliability)
     std::vector<uint8_t> used(len, 0);
@@ -68,6 +197,11 @@ extern "C" int dafs_hip_alignment_covariation(dafs_hip_ctx* c, uint32_t n, uint3
       lefts.push_back(col);
     }
   }
+  // the tree null's tree, before any output is written: the caller's is checked whenever it is there, the default one is
+  // built only where the new kernels will run (n >= 2, len >= 2, a null that somebody reads)
+  const bool by_tree = null == DAFS_COV_NULL_TREE && n >= 2 && len >= 2 && shuffles && (best_e || pair_e);
+  std::vector<int32_t> tree;
+  if ((tree_left || by_tree) && (rc = tree_of(c, n, len, code, tree_left, tree_right, tree))) return rc;
   const double nan = std::numeric_limits<double>::quiet_NaN();
   const double e0 = shuffles ? 0.0 : nan;
   // everything 0, no partners, E = 0 (NaN without shuffles); the statistics overwrite it below
@@ -106,7 +240,8 @@ extern "C" int dafs_hip_alignment_covariation(dafs_hip_ctx* c, uint32_t n, uint3
   const size_t o_lnq = take(((size_t)n + 1) * 8), o_sum = take((size_t)len * 8), o_tot = take(8), o_key = take((size_t)len * 8);
   const size_t o_best = take((size_t)len * 4), o_ss = take((size_t)len * 4), o_ps = take((size_t)len * 8), o_pr = take((size_t)len * 4 * 3);
   const size_t o_cand = take((size_t)ncand * 8), o_tail = take(shuffles ? (size_t)copies * ncand * 8 : 0);
-  int rc;
+  const size_t T = 2 * (size_t)n - 1;  // the tree null: Fitch's scratch, the change records, left / right / parent
+  const size_t o_node = take(by_tree ? T * len : 0), o_chg = take(by_tree ? T * len : 0), o_tree = take(by_tree ? 3 * T * 4 : 0);
   if ((rc = c->work.reserve(used + 256))) return rc;
   uint8_t* w = c->work.ptr;
   dev_mem gm;
@@ -171,9 +306,18 @@ extern "C" int dafs_hip_alignment_covariation(dafs_hip_ctx* c, uint32_t n, uint3
   for (uint32_t l : lefts) cand.push_back(ps[l]);
   std::sort(cand.begin(), cand.end());
   if (up(o_cand, cand.data(), (size_t)ncand * 8) || zero(o_tail, 0, (size_t)copies * ncand * 8)) return DAFS_HIP_ELAUNCH;
+  const int32_t* d_tree = (const int32_t*)(w + o_tree);
+  const cov_tree t = {d_tree, d_tree + T, d_tree + 2 * T};
+  const bool in_lds = by_tree && evolve_in_lds(n);
+  if (by_tree) {  // once per call: the change records of every branch
+    if (up(o_tree, tree.data(), 3 * T * 4)) return DAFS_HIP_ELAUNCH;
+    if ((rc = cov_fitch(w + o_code, t, n, len, w + o_node, w + o_chg, st))) return rc;
+  }
   for (uint32_t k = 0; k < shuffles; ++k) {
-    const uint64_t base = mix64(seed + 0x9E3779B97F4A7C15ull * ((uint64_t)k + 1));
-    if ((rc = cov_shuffle(w + o_code, w + o_shuf, n, len, base, st))) return rc;
+    const uint64_t base = null_base(seed, k);
+    if (by_tree) rc = cov_evolve(w + o_code, w + o_chg, t, n, len, base, w + o_node, w + o_shuf, in_lds, st);
+    else rc = cov_shuffle(w + o_code, w + o_shuf, n, len, base, st);
+    if (rc) return rc;
     if ((rc = cov_pack(w + o_shuf, n, len, (uint32_t*)(w + o_planes), st))) return rc;
     if (zero(o_sum, 0, (size_t)len * 8)) return DAFS_HIP_ELAUNCH;
     cov_args b = a;

@@ -36,6 +36,23 @@ constexpr uint32_t kCovMaxChunk = 32;  // words of 32 rows per LDS stage: 40 KB
 int cov_pack(const uint8_t* code, uint32_t n, uint32_t len, uint32_t* planes, hipStream_t st);
 // out = code with every column shuffled on its own: the Fisher-Yates of DESIGN.md section 13 with base = mix(seed + golden * (k + 1))
 int cov_shuffle(const uint8_t* code, uint8_t* out, uint32_t n, uint32_t len, uint64_t base, hipStream_t st);
+// A tree of 2n-1 nodes on the device in dafs_host_build_tree's layout, checked by the host: the children of join v are
+// earlier nodes, parent[v] > v for every node but the root 2n-2 (whose entry is not read).
+struct cov_tree {
+  const int32_t *left, *right, *parent;
+};
+constexpr uint32_t kCovTreeThreads = 64;  // k_cov_fitch, k_cov_draw, k_cov_evolve: one wavefront of columns per workgroup
+// Fitch sets and states of every column along the tree: chg[(2n-1) * len] gets the change records, node[(2n-1) * len]
+// (one byte per node and column) is the kernel's scratch and holds state(root) in its last row afterwards
+int cov_fitch(const uint8_t* code, const cov_tree& t, uint32_t n, uint32_t len, uint8_t* node, uint8_t* chg, hipStream_t st);
+// out = null alignment by evolution along the tree with base = mix(seed + golden * (k + 1)), in two kernels: every branch's
+// drawn change records into its row of node (the last row, the root's, is left as cov_fitch wrote it), then the states
+// root-down.  With lds the states of the n-1 joins live in LDS (64 bytes per join: while cov_evolve_fits_lds), else each
+// replaces the join's record in node.  n >= 2.
+constexpr uint32_t kCovEvolveLdsBytes = 64 * 1024;  // what a workgroup gets without asking for more
+inline bool cov_evolve_fits_lds(uint32_t n) { return (size_t)(n - 1) * kCovTreeThreads <= kCovEvolveLdsBytes; }
+int cov_evolve(const uint8_t* code, const uint8_t* chg, const cov_tree& t, uint32_t n, uint32_t len, uint64_t base, uint8_t* node,
+               uint8_t* out, bool lds, hipStream_t st);
 // one pass over every column pair c1 < c2
 int cov_pairs(cov_pass pass, const cov_args& a, hipStream_t st);
 // *total = sum of col_sum

@@ -10,6 +10,10 @@
 // owns c1 = i0 + v, lane l owns c2 = j0 + l, so a lane owns one column pair and keeps its 16 counts in registers.  The planes
 // of both column blocks are staged in LDS in chunks of `chunk` words (32 rows each): the c2 words word-major, so the lanes
 // read consecutive banks, the c1 words a broadcast.
+//
+// A null alignment comes from k_cov_shuffle (every column permuted on its own) or from k_cov_fitch, once, and k_cov_draw +
+// k_cov_evolve per alignment (the substitutions of every branch of a tree, moved to other columns); the pair passes do not
+// care which.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/dafs_hip.h"
@@ -195,6 +199,101 @@ __global__ __launch_bounds__(256) void k_cov_shuffle(const uint8_t* __restrict__
   }
 }
 
+// ---- the null by evolution along a tree.  Both kernels keep one byte per (node, column) in a
+// scratch laid out [node][column]: at every node the lanes of a wavefront touch 64 adjacent bytes, and a thread reads
+// only cells of its own column, which it wrote itself.
+
+// one thread per column: Fitch sets leaves-up, then states and change records root-down
+__global__ __launch_bounds__(kCovTreeThreads) void k_cov_fitch(const uint8_t* __restrict__ code, const int32_t* __restrict__ left,
+                                                               const int32_t* __restrict__ right, const int32_t* __restrict__ parent, uint32_t n,
+                                                               uint32_t len, uint8_t* node, uint8_t* __restrict__ chg) {
+  const uint32_t c = blockIdx.x * kCovTreeThreads + threadIdx.x;
+  if (c >= len) return;
+  const uint32_t root = 2 * n - 2;
+  for (uint32_t r = 0; r < n; ++r) {
+    const uint32_t v = code[(size_t)r * len + c];
+    node[(size_t)r * len + c] = (uint8_t)(v < 4 ? 1u << v : 15u);
+  }
+  for (uint32_t v = n; v <= root; ++v) {
+    const uint32_t a = node[(size_t)left[v] * len + c], b = node[(size_t)right[v] * len + c];
+    node[(size_t)v * len + c] = (uint8_t)((a & b) ? (a & b) : (a | b));
+  }
+  // a set is never empty, so __ffs is at least 1; a state overwrites its node's set once the set has been read
+  node[(size_t)root * len + c] = (uint8_t)(__ffs((int)node[(size_t)root * len + c]) - 1);
+  chg[(size_t)root * len + c] = 0;
+  for (uint32_t v = root; v-- > 0;) {
+    const uint32_t p = node[(size_t)parent[v] * len + c], s = node[(size_t)v * len + c];
+    const uint32_t state = ((s >> p) & 1u) ? p : (uint32_t)__ffs((int)s) - 1u;
+    node[(size_t)v * len + c] = (uint8_t)state;
+    chg[(size_t)v * len + c] = (uint8_t)(state == p ? 0u : 1u + 4u * p + state);
+  }
+}
+
+// F: four Feistel rounds on the two h-bit halves of x, a bijection of [0, 4^h)
+__device__ __forceinline__ uint32_t cov_feistel(uint64_t key, uint32_t h, uint32_t mask, uint32_t x) {
+  uint32_t L = x >> h, R = x & mask;
+#pragma unroll
+  for (uint64_t r = 1; r <= 4; ++r) {
+    const uint32_t t = L ^ ((uint32_t)cov_mix(key + 0x9E3779B97F4A7C15ull * r + R) & mask);
+    L = R;
+    R = t;
+  }
+  return (L << h) | R;
+}
+
+// pi(key, len, c): F's cycle walked from c until it is back below len.  At most walk = 4^h - len + 1 applications get
+// there, and that is the trip count: nothing here can spin.
+__device__ __forceinline__ uint32_t cov_pi(uint64_t key, uint32_t len, uint32_t h, uint32_t walk, uint32_t c) {
+  const uint32_t mask = (1u << h) - 1u;
+  uint32_t x = cov_feistel(key, h, mask, c);
+  for (uint32_t t = 1; t < walk && x >= len; ++t) x = cov_feistel(key, h, mask, x);
+  return x < len ? x : c;  // always x: the index of a load stays inside the row whatever happens
+}
+
+// one thread per (branch, column) of one null alignment: the change record that branch v = v0 + blockIdx.y brings to
+// column c, drawn by pi, into the branch's row of `node`.  Every draw depends on (base, v, c) alone, so the grid fills the
+// device however short the alignment is; the root (no branch) keeps its row, state(root) from k_cov_fitch.
+__global__ __launch_bounds__(kCovTreeThreads) void k_cov_draw(const uint8_t* __restrict__ chg, uint32_t len, uint32_t h, uint32_t walk,
+                                                              uint64_t base, uint32_t v0, uint8_t* __restrict__ node) {
+  const uint32_t c = blockIdx.x * kCovTreeThreads + threadIdx.x, v = v0 + blockIdx.y;
+  if (c >= len) return;
+  const uint64_t key = cov_mix(base ^ ((uint64_t)(v + 1) << 32));  // uniform per workgroup
+  node[(size_t)v * len + c] = chg[(size_t)v * len + cov_pi(key, len, h, walk, c)];
+}
+
+// one thread per column, after k_cov_draw: root-down, the state of every node from its parent's and its drawn record.  The
+// states of the joins (a leaf is nobody's parent) are the one chain of dependent reads: with LDS they live in the
+// workgroup's LDS as [join][lane], else each takes the place of the join's record in `node` once that has been read.  A
+// node's record and a leaf's own code do not depend on that chain and are fetched one node ahead.
+template <bool LDS>
+__global__ __launch_bounds__(kCovTreeThreads) void k_cov_evolve(const uint8_t* __restrict__ code, const int32_t* __restrict__ parent, uint32_t n,
+                                                                uint32_t len, uint8_t* node, uint8_t* __restrict__ out) {
+  extern __shared__ uint8_t ns_lds[];
+  const uint32_t c = blockIdx.x * kCovTreeThreads + threadIdx.x;
+  if (c >= len) return;
+  const uint32_t root = 2 * n - 2;
+  auto at = [&](uint32_t v) {  // the state of join v in this column (n <= v <= root)
+    return LDS ? ns_lds + (size_t)(v - n) * kCovTreeThreads + threadIdx.x : node + (size_t)v * len + c;
+  };
+  if (LDS) *at(root) = node[(size_t)root * len + c];
+  uint32_t rec_next = node[(size_t)(root - 1) * len + c], cell_next = root - 1 < n ? code[(size_t)(root - 1) * len + c] : 0u;  // n >= 2
+  for (uint32_t v = root; v-- > 0;) {
+    const uint32_t rec = rec_next, cell = cell_next;
+    if (v) {
+      rec_next = node[(size_t)(v - 1) * len + c];
+      cell_next = v - 1 < n ? code[(size_t)(v - 1) * len + c] : 0u;
+    }
+    const uint32_t p = *at((uint32_t)parent[v]);  // a parent is a join
+    uint32_t s = p;
+    if (rec) {
+      const uint32_t a = ((rec - 1) >> 2) & 3u, b = (rec - 1) & 3u;
+      s = b != p ? b : a;
+    }
+    if (v >= n) *at(v) = (uint8_t)s;
+    else out[(size_t)v * len + c] = cell == 4 ? (uint8_t)4 : (uint8_t)s;
+  }
+}
+
 __global__ __launch_bounds__(1024) void k_cov_total(const unsigned long long* __restrict__ col_sum, uint32_t len, long long* total) {
   __shared__ unsigned long long acc;
   if (threadIdx.x == 0) acc = 0;
@@ -255,6 +354,34 @@ int cov_pack(const uint8_t* code, uint32_t n, uint32_t len, uint32_t* planes, hi
 
 int cov_shuffle(const uint8_t* code, uint8_t* out, uint32_t n, uint32_t len, uint64_t base, hipStream_t st) {
   STAGE_LAUNCH(ST_COV_SHUFFLE, st) hipLaunchKernelGGL(k_cov_shuffle, dim3((len + 255) / 256), dim3(256), 0, st, code, out, n, len, base);
+  return hip_check(hipGetLastError()) ? DAFS_HIP_ELAUNCH : DAFS_HIP_OK;
+}
+
+int cov_fitch(const uint8_t* code, const cov_tree& t, uint32_t n, uint32_t len, uint8_t* node, uint8_t* chg, hipStream_t st) {
+  STAGE_LAUNCH(ST_COV_FITCH, st)
+  hipLaunchKernelGGL(k_cov_fitch, dim3((len + kCovTreeThreads - 1) / kCovTreeThreads), dim3(kCovTreeThreads), 0, st, code, t.left, t.right,
+                     t.parent, n, len, node, chg);
+  return hip_check(hipGetLastError()) ? DAFS_HIP_ELAUNCH : DAFS_HIP_OK;
+}
+
+int cov_evolve(const uint8_t* code, const uint8_t* chg, const cov_tree& t, uint32_t n, uint32_t len, uint64_t base, uint8_t* node,
+               uint8_t* out, bool lds, hipStream_t st) {
+  if (n < 2 || (lds && !cov_evolve_fits_lds(n))) return DAFS_HIP_EINVAL;
+  uint32_t h = 1;
+  while (((uint64_t)1 << (2 * h)) < len) ++h;
+  const uint32_t walk = (uint32_t)(((uint64_t)1 << (2 * h)) - len + 1), cols = (len + kCovTreeThreads - 1) / kCovTreeThreads;
+  for (uint32_t v0 = 0; v0 < 2 * n - 2; v0 += 65535) {  // grid.y holds 65535 at most
+    const uint32_t vn = 2 * n - 2 - v0 < 65535 ? 2 * n - 2 - v0 : 65535;
+    STAGE_LAUNCH(ST_COV_DRAW, st) hipLaunchKernelGGL(k_cov_draw, dim3(cols, vn), dim3(kCovTreeThreads), 0, st, chg, len, h, walk, base, v0, node);
+    if (hip_check(hipGetLastError())) return DAFS_HIP_ELAUNCH;
+  }
+  STAGE_LAUNCH(ST_COV_EVOLVE, st) {
+    if (lds)
+      hipLaunchKernelGGL(k_cov_evolve<true>, dim3(cols), dim3(kCovTreeThreads), (size_t)(n - 1) * kCovTreeThreads, st, code, t.parent, n, len, node,
+                         out);
+    else
+      hipLaunchKernelGGL(k_cov_evolve<false>, dim3(cols), dim3(kCovTreeThreads), 0, st, code, t.parent, n, len, node, out);
+  }
   return hip_check(hipGetLastError()) ? DAFS_HIP_ELAUNCH : DAFS_HIP_OK;
 }
 

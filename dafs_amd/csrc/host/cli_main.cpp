@@ -86,6 +86,8 @@ struct Options {
   uint32_t cov_shuffles = 100;  // --cov-shuffles K
   uint64_t cov_seed = 1;        // --cov-seed S
   bool cov_shuffles_given = false, cov_seed_given = false;
+  int cov_null = DAFS_COV_NULL_SHUFFLE;  // --cov-null NAME
+  bool cov_null_given = false;
   bool refinement_given = false;
   std::string identity;         // --identity OUT
   std::string identity_matrix;  // --identity-matrix OUT
@@ -167,6 +169,9 @@ const char* kHelp =
     "                        With --stockholm a #=GC cov_SS_cons line marks the pairs with E <= 0.05.  Not with --pairwise\n"
     "      --cov-shuffles K  Shuffled alignments behind E (default: 100; 0: no E-values); needs --covariation\n"
     "      --cov-seed S      Seed of the shuffles (default: 1); needs --covariation\n"
+    "      --cov-null NAME   The null behind E.  shuffle (default): every column permuted on its own, which ignores phylogeny.\n"
+    "                        tree: the substitutions of every branch of a tree over the rows (average linkage of their\n"
+    "                        identities), moved to other columns; K and S as above.  Needs --covariation\n"
     "      --identity OUT    Also write how similar the rows of every printed alignment are to OUT: the line\n"
     "                        \"# rows n columns len average A min B max C\" (pairwise identity over all row pairs), then one\n"
     "                        tab-separated line per row: r name residues weight nearest nearest_name pid (1-based rows; residues:\n"
@@ -259,7 +264,7 @@ Options parse(int argc, char** argv) {
       {"save-fold-aux", {0, true}}, {"device", {0, true}}, {"devices", {0, true}}, {"input", {0, true}},
       {"stockholm", {0, true}}, {"row-structures", {0, false}}, {"seed", {0, true}}, {"pairwise", {0, false}}, {"pairwise-scores", {0, true}},
       {"seed-each", {0, false}}, {"seed-scores", {0, true}}, {"seed-merged", {0, true}}, {"seed-structure", {0, false}},
-      {"covariation", {0, true}}, {"cov-shuffles", {0, true}}, {"cov-seed", {0, true}}, {"identity", {0, true}},
+      {"covariation", {0, true}}, {"cov-shuffles", {0, true}}, {"cov-seed", {0, true}}, {"cov-null", {0, true}}, {"identity", {0, true}},
       {"identity-matrix", {0, true}}, {"seed-nearest", {0, false}}, {"seed-nr", {0, true}}, {"describe", {0, true}},
       {"compare", {0, true}}, {"compare-ref", {0, true}}, {"compare-columns", {0, true}}, {"compare-matrix", {0, true}},
       {"cluster", {0, true}}, {"cluster-count", {0, true}}, {"cluster-min-size", {0, true}}, {"cluster-table", {0, true}},
@@ -408,6 +413,12 @@ Options parse(int argc, char** argv) {
       if (used == 0 || used != value.size() || !(o.seed_nr > 0.0 && o.seed_nr <= 1.0)) throw std::string(dafs_host_alistat_refusal(DAFS_ALISTAT_NR_THRESHOLD));
       o.seed_nr_given = true;
     }
+    else if (name == "cov-null") {
+      if (value == "shuffle") o.cov_null = DAFS_COV_NULL_SHUFFLE;
+      else if (value == "tree") o.cov_null = DAFS_COV_NULL_TREE;
+      else throw "--cov-null: unknown null '" + value + "' (shuffle, tree)";
+      o.cov_null_given = true;
+    }
     else if (name == "cov-shuffles" || name == "cov-seed") {
       size_t used = 0;
       unsigned long long v = 0;
@@ -439,11 +450,12 @@ Options parse(int argc, char** argv) {
   }
   if (o.row_structures && o.stockholm.empty()) throw std::string("--row-structures needs --stockholm");
   if ((o.cov_shuffles_given || o.cov_seed_given) && o.covariation.empty()) throw std::string("--cov-shuffles and --cov-seed need --covariation");
+  if (o.cov_null_given && o.covariation.empty()) throw std::string("--cov-null needs --covariation");
   if (o.pairwise && (!o.covariation.empty() || o.cov_shuffles_given || o.cov_seed_given))
     throw std::string("--pairwise: two rows carry no covariation; --covariation, --cov-shuffles and --cov-seed cannot be combined with --pairwise");
   if (!o.describe.empty()) {  // a finished alignment: nothing that aligns, and no FILE
     for (const std::string& g : given)
-      if (g != "describe" && g != "identity" && g != "identity-matrix" && g != "covariation" && g != "cov-shuffles" && g != "cov-seed" && g != "device" &&
+      if (g != "describe" && g != "identity" && g != "identity-matrix" && g != "covariation" && g != "cov-shuffles" && g != "cov-seed" && g != "cov-null" && g != "device" &&
           g.compare(0, 7, "compare") != 0)
         throw "--describe reads a finished alignment: --" + g + " cannot be combined with --describe";
     if (!o.inputs.empty()) throw std::string("--describe takes no FILE: the alignment is its argument");
@@ -837,7 +849,7 @@ std::vector<std::pair<size_t, size_t> > chunks(const std::vector<uint64_t>& byte
   return out;
 }
 
-// --covariation: the statistics of one printed alignment (dafs_hip_alignment_covariation).
+// --covariation: the statistics of one printed alignment (dafs_hip_alignment_covariation_null).
 const double kCovEMax = 0.05;  // the cut of cov_SS_cons
 
 // rows: the printed rows; ss: the structure.  tsv: the table of this alignment; chars: the cov_SS_cons characters.
@@ -849,8 +861,11 @@ void covariation_of(dafs_hip_ctx* ctx, const Options& o, const std::vector<std::
     for (uint32_t c = 0; c < L; ++c) code[(size_t)r * L + c] = dafs_host_cov_code(rows[r][c]);
   std::vector<uint32_t> best(L), prow(L), pcan(L), ptyp(L);
   std::vector<double> bscore(L), be(L), pscore(L), pe(L);
-  check(dafs_hip_alignment_covariation(ctx, n, L, code.data(), ss.data(), o.cov_shuffles, o.cov_seed, nullptr, best.data(), bscore.data(),
-                                       be.data(), pscore.data(), pe.data(), prow.data(), pcan.data(), ptyp.data(), nullptr, nullptr));
+  const int rc = dafs_hip_alignment_covariation_null(ctx, n, L, code.data(), ss.data(), o.cov_shuffles, o.cov_seed, o.cov_null, nullptr, nullptr,
+                                                     nullptr, best.data(), bscore.data(), be.data(), pscore.data(), pe.data(), prow.data(),
+                                                     pcan.data(), ptyp.data(), nullptr, nullptr);
+  if (o.cov_null == DAFS_COV_NULL_TREE) check_text(rc);  // the tree null's refusals carry a message (a row without a base)
+  else check(rc);
   char* text = nullptr;
   check_text(dafs_host_cov_ss_cons(L, ss.data(), pe.data(), kCovEMax, &text));
   chars = take(text);

@@ -60,7 +60,7 @@ def run(names, seqs, ctx=None, bp=None, w=4.0, eta0=0.5, t_max=600, w_pct_a=0.25
     shard: (torch.distributed module, torch device) of an initialised process group -- phase 1 (folds, pair posteriors,
     matching consistency transform) is then split over the ranks and gathered (dist.phase1_sharded); every rank
     finishes the run and holds the same result.  reliability: the result also gets .reliability and .stockholm (see
-    _phase2_forest).  covariation: True or a dict with shuffles (100), seed (1), e_max (0.05): the result also gets
+    _phase2_forest).  covariation: True or a dict with shuffles (100), seed (1), e_max (0.05), null ("shuffle"): the result also gets
     .covariation (see _final).  row_structures: the result also gets .row_ss and .row_ss_str, the structure of every printed
     row on its own (see _phase2_forest).  identity: the result also gets .identity (see alignment_identity) and its
     Stockholm block the `#=GS <name> WT` lines.  compare: (ref_names, ref_rows[, ref_ss]), a reference alignment of the same
@@ -304,15 +304,19 @@ def _phase2_forest(ctx, own, fams, t, w, eta0, t_max, th_a, th_s, th_s1, force_i
 
 
 def cov_options(covariation):
-    """The covariation option of run / run_batch / add as a dict with shuffles, seed and e_max, or None for off"""
+    """The covariation option of run / run_batch / add as a dict with shuffles, seed and e_max, or None for off.  The key
+    null (one of capi.COV_NULLS; "tree" takes the default tree of the printed rows) is kept only where the caller gave it:
+    without it the null is "shuffle"."""
     if covariation is None or covariation is False:
         return None
     opt = dict(shuffles=100, seed=1, e_max=0.05)
     if covariation is not True:
-        unknown = set(covariation) - set(opt)
+        unknown = set(covariation) - set(opt) - {"null"}
         if unknown:
-            raise ValueError("covariation: unknown keys %s (shuffles, seed, e_max)" % sorted(unknown))
+            raise ValueError("covariation: unknown keys %s (shuffles, seed, e_max, null)" % sorted(unknown))
         opt.update(covariation)
+    if opt.get("null", "shuffle") not in capi.COV_NULLS:
+        raise ValueError("covariation: unknown null %r (one of %s)" % (opt["null"], ", ".join(capi.COV_NULLS)))
     return opt
 
 
@@ -397,7 +401,7 @@ def describe(names, rows, ss=None, ctx=None, identity=True, covariation=False, c
         if identity:
             res.identity = alignment_identity(ctx, rows)
         if covariation:
-            res.covariation = ctx.alignment_covariation(rows, res.ss, shuffles=covariation["shuffles"], seed=covariation["seed"])
+            res.covariation = ctx.alignment_covariation(rows, res.ss, shuffles=covariation["shuffles"], seed=covariation["seed"], null=covariation.get("null", "shuffle"))
             res.covariation.update(covariation)
         if compare is not None:
             res.compare = compare_result(ctx, compare, res.row_names, rows, None if ss is None else res.ss, pp=pp)
@@ -494,7 +498,7 @@ def _final(ctx, res, names, seqs, first, sidx, mask, ss, rl, tree_line, rf=None,
         res.row_ss_str = [stockholm.row_ss_str(row, x) for row, x in zip(res.rows, row_ss)]
     cov_chars = None
     if covariation:
-        cv = ctx.alignment_covariation(res.rows, ss, shuffles=covariation["shuffles"], seed=covariation["seed"])
+        cv = ctx.alignment_covariation(res.rows, ss, shuffles=covariation["shuffles"], seed=covariation["seed"], null=covariation.get("null", "shuffle"))
         cv.update(covariation)
         res.covariation = cv
         cov_chars = stockholm.cov_ss_cons(ss, cv["pair_e"], cv["e_max"])

@@ -649,6 +649,33 @@ int dafs_hip_alignment_covariation(dafs_hip_ctx* ctx, uint32_t n, uint32_t len, 
                                    uint32_t shuffles, uint64_t seed, int64_t* col_sum, uint32_t* best, double* best_score,
                                    double* best_e, double* pair_score, double* pair_e, uint32_t* pair_rows,
                                    uint32_t* pair_canonical, uint32_t* pair_types, int64_t* total, int64_t* g);
+/* The same statistics under a chosen null ("Null by evolution along a tree").  dafs_hip_alignment_covariation
+ * is this call with DAFS_COV_NULL_SHUFFLE and no tree, to the bit.
+ *   null                    DAFS_COV_NULL_SHUFFLE: every column permuted on its own, which ignores phylogeny.
+ *                           DAFS_COV_NULL_TREE: the rows are the leaves of a tree; Fitch parsimony places every column's
+ *                           substitutions on its branches, and null alignment k evolves from the root's states with every
+ *                           branch keeping its number of substitutions, on columns drawn afresh per (k, branch) by a stateless
+ *                           permutation.  Gaps (code 4) stay where they are.  All of it is integer arithmetic.
+ *   tree_left, tree_right   2n-1 entries each in the layout of dafs_host_build_tree (leaf r is row r; the children of join n + t
+ *                           are earlier nodes; the root is 2n-2), or both NULL under DAFS_COV_NULL_TREE: average linkage
+ *                           (dafs_hip_linkage_tree) of sim(r, s) = (float)((double)ident / (double)both), ident and both counted
+ *                           over the columns where both rows hold a base (0.0f where there is none); that takes n <= 32768.
+ * DAFS_HIP_EINVAL with a message in dafs_hip_last_error, outputs untouched and the context usable, beyond the refusals above: an
+ * unknown null, a tree under DAFS_COV_NULL_SHUFFLE, only one of the two arrays, a malformed tree (the checks of
+ * dafs_host_cluster_cut), and under the default tree a row without a base.  With n < 2, len < 2 or shuffles = 0 the call behaves
+ * as above: no tree is built and none of the tree null's kernels is launched (a tree that is passed is still checked). */
+enum { DAFS_COV_NULL_SHUFFLE = 0, DAFS_COV_NULL_TREE = 1 };
+int dafs_hip_alignment_covariation_null(dafs_hip_ctx* ctx, uint32_t n, uint32_t len, const uint8_t* code, const uint32_t* ss,
+                                        uint32_t shuffles, uint64_t seed, int null, const int32_t* tree_left, const int32_t* tree_right,
+                                        int64_t* col_sum, uint32_t* best, double* best_score, double* best_e, double* pair_score,
+                                        double* pair_e, uint32_t* pair_rows, uint32_t* pair_canonical, uint32_t* pair_types,
+                                        int64_t* total, int64_t* g);
+/* Null alignment k (0-based) of either null as out_code[n * len], the codes the statistics above are computed from: what a user
+ * looks at to see what the null keeps, and what the tests compare byte for byte.  Arguments and refusals as above; one row comes
+ * back as it is. */
+int dafs_hip_covariation_null_alignment(dafs_hip_ctx* ctx, uint32_t n, uint32_t len, const uint8_t* code, int null,
+                                        const int32_t* tree_left, const int32_t* tree_right, uint64_t seed, uint32_t k,
+                                        uint8_t* out_code);
 
 /* Alignment statistics: how similar the rows of an alignment are to one another (no counterpart in the reference; definitions,
  * to the bit, in DESIGN.md section 18 "Alignment statistics").  Both device calls read the alignment alone, none of the
