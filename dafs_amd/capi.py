@@ -164,6 +164,13 @@ _linkage_tree = _sig("dafs_hip_linkage_tree", C.c_int, [C.c_void_p, C.c_int, C.c
 linkage_workspace = _sig("dafs_hipk_linkage_workspace", C.c_size_t, [C.c_uint32])
 linkage_launch = _sig("dafs_hipk_linkage", C.c_int, [C.c_int, C.c_uint32] + [C.c_void_p] * 6)
 LINKAGES = ("guide", "single", "complete", "average")  # --cluster-linkage; the index is the library's DAFS_LINKAGE_* code
+_nj_tree = _sig("dafs_hip_nj_tree", C.c_int, [C.c_void_p, C.c_uint32] + [C.c_void_p] * 4)
+nj_workspace = _sig("dafs_hipk_nj_workspace", C.c_size_t, [C.c_uint32])
+nj_launch = _sig("dafs_hipk_nj", C.c_int, [C.c_uint32] + [C.c_void_p] * 6)
+_nj_distances = _sig("dafs_host_nj_distances", C.c_int, [C.c_uint32, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p])
+NJ_MODELS = ("p", "jc")  # --phylogeny-model; the index is the library's DAFS_NJ_* code
+NJ_MAX_ROWS = 16384
+COV_TREES = ("average", "nj")  # --cov-tree
 _merge_added = _sig("dafs_host_merge_added", C.c_int, [C.c_uint32, C.c_uint32] + [C.c_void_p] * 5)
 # host text (dafs_amd/csrc/host_text.cpp): returned text is a char* the caller frees with dafs_host_free
 _strs = C.POINTER(C.c_char_p)
@@ -255,6 +262,10 @@ _stockholm_weights = _sig("dafs_host_stockholm_weights", C.c_int, [C.c_char_p, C
 _stockholm_nr = _sig("dafs_host_stockholm_nr", C.c_int, [C.c_char_p, C.c_uint32, _strs, C.c_void_p, C.c_uint32, C.c_double, _text])
 _alistat_refusal = _sig("dafs_host_alistat_refusal", C.c_char_p, [C.c_int])
 NO_PAIRWISE, NR_NEEDS_MERGED, NR_THRESHOLD, TOO_MANY_ROWS = range(4)  # dafs_host_alistat_refusal
+_newick = _sig("dafs_host_newick", C.c_int, [C.c_uint32, _strs, C.c_void_p, C.c_void_p, C.c_void_p, _text])
+_phylogeny_refusal = _sig("dafs_host_phylogeny_refusal", C.c_char_p, [C.c_int])
+(PHY_NO_PAIRWISE, PHY_NO_SEED_EACH, PHY_TOO_MANY_ROWS, PHY_MODEL_NEEDS_TREE, PHY_UNKNOWN_MODEL, PHY_COV_TREE_NEEDS_NULL,
+ PHY_UNKNOWN_COV_TREE) = range(7)  # dafs_host_phylogeny_refusal
 _seed_table_nearest = _sig("dafs_host_seed_table_nearest", C.c_int, [C.c_uint32, _strs] + [C.c_void_p] * 8 + [_strs, C.c_void_p, _text])
 # dafs_allgather_fn(user, send, recv, bytes, hip_stream): the caller's collective of a sharded phase 1
 _allgather_fn = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
@@ -577,6 +588,37 @@ class Context:
             raise ValueError(_last_error().decode("latin-1"))
         check(rc)
         return score, left.astype(np.int64), right.astype(np.int64)
+
+    def nj_tree(self, dist):
+        """dafs_hip_nj_tree: the neighbour-joining tree of the n x n matrix dist (float64; only the
+        entries x < y are read, all of them finite), joined on the device.  Returns (left, right, length): int64 children in
+        build_tree's layout and the float64 length of the branch above each node (0.0 at the root; negative lengths are kept).
+        ValueError for a matrix that is not square, more than NJ_MAX_ROWS rows, a non-finite entry above the diagonal and an
+        overflow during the joins."""
+        dist = np.ascontiguousarray(dist, np.float64)
+        if dist.ndim != 2 or dist.shape[0] != dist.shape[1] or dist.shape[0] == 0:
+            raise ValueError("nj_tree: the distance matrix must be n x n with n >= 1")
+        n = dist.shape[0]
+        if n > NJ_MAX_ROWS:
+            raise ValueError(phylogeny_refusal(PHY_TOO_MANY_ROWS))
+        left = np.zeros(2 * n - 1, np.int32); right = np.zeros(2 * n - 1, np.int32); length = np.zeros(2 * n - 1, np.float64)
+        rc = _nj_tree(self._h, n, dist.ctypes.data, left.ctypes.data, right.ctypes.data, length.ctypes.data)
+        if rc == -1:
+            raise ValueError(_last_error().decode("latin-1"))
+        check(rc)
+        return left.astype(np.int64), right.astype(np.int64), length
+
+    def alignment_tree(self, cell, use=None, model="jc"):
+        """The neighbour-joining tree of an alignment's rows: the identity counts of
+        alignment_identity(cell, use, matrix=True), nj_distances under `model` ("jc" or "p"), nj_tree.  cell: the text rows or
+        their cells (encode_cells); use: the columns that count (None: all).  Returns (left, right, length)."""
+        if model not in NJ_MODELS:
+            raise ValueError(phylogeny_refusal(PHY_UNKNOWN_MODEL))
+        cell = _cells(cell, "alignment_tree")
+        if cell.shape[0] > NJ_MAX_ROWS:
+            raise ValueError(phylogeny_refusal(PHY_TOO_MANY_ROWS))
+        idt = self.alignment_identity(cell, use=use, matrix=True, nearest=False)
+        return self.nj_tree(nj_distances(idt.ident, idt.aligned, model))
 
     def set_bp(self, rows):
         """rows: per sequence (rowptr[len+1], col, val)"""
@@ -1245,6 +1287,47 @@ def cluster_table(headers, lengths, labels, tree, sim):
         raise ValueError("cluster_table: one header, length and label per leaf of the tree and an n x n similarity matrix")
     return host_text(_cluster_table, n, c_strings(headers), lengths.ctypes.data, labels.ctypes.data, score.ctypes.data, left.ctypes.data,
                      right.ctypes.data, sim.ctypes.data)
+
+
+def phylogeny_refusal(which):
+    """what both drivers say when they refuse a combination of the phylogeny options (dafs_host_phylogeny_refusal)"""
+    return _phylogeny_refusal(which).decode()
+
+
+def nj_distances(ident, aligned, model="jc"):
+    """dafs_host_nj_distances: the float64 [n, n] distances of an alignment's rows from the integer
+    matrices of Context.alignment_identity(matrix=True), under the model "jc" (Jukes-Cantor, quantised to 2^-20 and capped at
+    3.0) or "p" (the share of differing columns).  A letter outside ACGU counts as a difference."""
+    if model not in NJ_MODELS:
+        raise ValueError(phylogeny_refusal(PHY_UNKNOWN_MODEL))
+    ident = np.ascontiguousarray(ident, np.uint32)
+    aligned = np.ascontiguousarray(aligned, np.uint32)
+    if ident.ndim != 2 or ident.shape[0] != ident.shape[1] or ident.shape[0] == 0 or aligned.shape != ident.shape:
+        raise ValueError("nj_distances: ident and aligned are n x n matrices with n >= 1")
+    n = ident.shape[0]
+    dist = np.zeros((n, n), np.float64)
+    rc = _nj_distances(n, ident.ctypes.data, aligned.ctypes.data, NJ_MODELS.index(model), dist.ctypes.data)
+    if rc == -1:
+        raise ValueError(_last_error().decode("latin-1"))
+    check(rc)
+    return dist
+
+
+def newick(names, left, right, length=None):
+    """dafs_host_newick: the tree (left, right in build_tree's layout, length per node or None for the topology alone) as one
+    Newick line ending in ";\n": "(L:len,R:len)" nested with the left child first, lengths as %.9g, none on the root, names
+    quoted where they hold any of ()[]':;, or white space.  ValueError for a malformed tree."""
+    names = list(names)
+    n = len(names)
+    left = np.ascontiguousarray(left, np.int32).reshape(-1)
+    right = np.ascontiguousarray(right, np.int32).reshape(-1)
+    if n == 0 or len(left) != 2 * n - 1 or len(right) != 2 * n - 1:
+        raise ValueError("newick: a tree of n names has 2n - 1 nodes")
+    if length is not None:
+        length = np.ascontiguousarray(length, np.float64).reshape(-1)
+        if len(length) != 2 * n - 1:
+            raise ValueError("newick: one length per node")
+    return host_text(_newick, n, c_strings(names), left.ctypes.data, right.ctypes.data, None if length is None else length.ctypes.data)
 
 
 def merge_added(ncols, zs):

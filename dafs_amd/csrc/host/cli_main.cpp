@@ -91,6 +91,11 @@ struct Options {
   bool refinement_given = false;
   std::string identity;         // --identity OUT
   std::string identity_matrix;  // --identity-matrix OUT
+  std::string phylogeny;        // --phylogeny OUT: the neighbour-joining tree of every printed alignment's rows, in Newick
+  int phylogeny_model = DAFS_NJ_JC;  // --phylogeny-model jc|p
+  bool phylogeny_model_given = false;
+  bool cov_tree_nj = false;     // --cov-tree nj: the tree null evolves along the neighbour-joining tree
+  bool cov_tree_given = false;
   bool seed_nearest = false;    // --seed-nearest: two more columns in --seed-scores
   double seed_nr = 0.0;         // --seed-nr T: --seed-merged holds the non-redundant block
   bool seed_nr_given = false;
@@ -172,6 +177,16 @@ const char* kHelp =
     "      --cov-null NAME   The null behind E.  shuffle (default): every column permuted on its own, which ignores phylogeny.\n"
     "                        tree: the substitutions of every branch of a tree over the rows (average linkage of their\n"
     "                        identities), moved to other columns; K and S as above.  Needs --covariation\n"
+    "      --cov-tree NAME   With --cov-null tree: the tree over the rows.  average (default): average linkage of their identities,\n"
+    "                        which assumes a molecular clock.  nj: the neighbour-joining tree of --phylogeny (model jc), which does\n"
+    "                        not; at most 16384 rows\n"
+    "      --phylogeny OUT   Also write the neighbour-joining tree of every printed alignment's rows to OUT, one Newick line per\n"
+    "                        alignment: \"(L:len,R:len)\" nested, the names those of --stockholm, lengths as %.9g (negative ones\n"
+    "                        are kept), the root in the middle of the last edge joined; one row gives \"name;\".  The distances\n"
+    "                        come from the identity counts of the rows (a letter outside ACGU counts as a difference); the\n"
+    "                        joins run on the device.  At most 16384 rows.  Not with --pairwise or --seed-each\n"
+    "      --phylogeny-model M  With --phylogeny: jc (default): Jukes-Cantor distances, capped at 3.0; p: the share of aligned\n"
+    "                        columns that differ\n"
     "      --identity OUT    Also write how similar the rows of every printed alignment are to OUT: the line\n"
     "                        \"# rows n columns len average A min B max C\" (pairwise identity over all row pairs), then one\n"
     "                        tab-separated line per row: r name residues weight nearest nearest_name pid (1-based rows; residues:\n"
@@ -188,8 +203,8 @@ const char* kHelp =
     "                        before it; a line \"#=GF CC nr T kept K of M hits\" precedes the rows\n"
     "      --describe ALIGNMENT  No FILE: read a finished alignment (Stockholm or aligned FASTA, as --seed reads it, with its\n"
     "                        SS_cons if it has one) and write --identity / --identity-matrix and, if given, --covariation for\n"
-    "                        it (--identity: at most 32768 rows); nothing is aligned and nothing is printed.  Only --device and\n"
-    "                        the --cov-* and --compare* options go with it\n"
+    "                        it (--identity: at most 32768 rows); nothing is aligned and nothing is printed.  Only --device,\n"
+    "                        --phylogeny, --phylogeny-model and the --cov-* and --compare* options go with it\n"
     "      --compare OUT     With --compare-ref REF: also write to OUT how far every printed alignment agrees with the\n"
     "                        reference alignment REF of the same sequences (read as --seed reads a seed, with its SS_cons if it\n"
     "                        has one).  The rows compared are the names in both.  Lines \"# rows ..\", \"# pairs shared S ref P\n"
@@ -265,6 +280,7 @@ Options parse(int argc, char** argv) {
       {"stockholm", {0, true}}, {"row-structures", {0, false}}, {"seed", {0, true}}, {"pairwise", {0, false}}, {"pairwise-scores", {0, true}},
       {"seed-each", {0, false}}, {"seed-scores", {0, true}}, {"seed-merged", {0, true}}, {"seed-structure", {0, false}},
       {"covariation", {0, true}}, {"cov-shuffles", {0, true}}, {"cov-seed", {0, true}}, {"cov-null", {0, true}}, {"identity", {0, true}},
+      {"phylogeny", {0, true}}, {"phylogeny-model", {0, true}}, {"cov-tree", {0, true}},
       {"identity-matrix", {0, true}}, {"seed-nearest", {0, false}}, {"seed-nr", {0, true}}, {"describe", {0, true}},
       {"compare", {0, true}}, {"compare-ref", {0, true}}, {"compare-columns", {0, true}}, {"compare-matrix", {0, true}},
       {"cluster", {0, true}}, {"cluster-count", {0, true}}, {"cluster-min-size", {0, true}}, {"cluster-table", {0, true}},
@@ -362,6 +378,22 @@ Options parse(int argc, char** argv) {
       if (value.empty()) throw "--" + name + " needs a file name";
       (name == "identity" ? o.identity : name == "describe" ? o.describe : o.identity_matrix) = value;
     }
+    else if (name == "phylogeny") {
+      if (value.empty()) throw std::string("--phylogeny needs a file name");
+      o.phylogeny = value;
+    }
+    else if (name == "phylogeny-model") {
+      if (value == "jc") o.phylogeny_model = DAFS_NJ_JC;
+      else if (value == "p") o.phylogeny_model = DAFS_NJ_P;
+      else throw std::string(dafs_host_phylogeny_refusal(DAFS_PHYLOGENY_UNKNOWN_MODEL));
+      o.phylogeny_model_given = true;
+    }
+    else if (name == "cov-tree") {
+      if (value == "average") o.cov_tree_nj = false;
+      else if (value == "nj") o.cov_tree_nj = true;
+      else throw std::string(dafs_host_phylogeny_refusal(DAFS_PHYLOGENY_UNKNOWN_COV_TREE));
+      o.cov_tree_given = true;
+    }
     else if (name == "compare" || name == "compare-ref" || name == "compare-columns" || name == "compare-matrix") {
       if (value.empty()) throw "--" + name + " needs a file name";
       (name == "compare" ? o.compare : name == "compare-ref" ? o.compare_ref : name == "compare-columns" ? o.compare_columns : o.compare_matrix) = value;
@@ -451,15 +483,20 @@ Options parse(int argc, char** argv) {
   if (o.row_structures && o.stockholm.empty()) throw std::string("--row-structures needs --stockholm");
   if ((o.cov_shuffles_given || o.cov_seed_given) && o.covariation.empty()) throw std::string("--cov-shuffles and --cov-seed need --covariation");
   if (o.cov_null_given && o.covariation.empty()) throw std::string("--cov-null needs --covariation");
+  if (o.cov_tree_given && (!o.cov_null_given || o.cov_null != DAFS_COV_NULL_TREE)) throw std::string(dafs_host_phylogeny_refusal(DAFS_PHYLOGENY_COV_TREE_NEEDS_NULL));
+  if (o.phylogeny_model_given && o.phylogeny.empty()) throw std::string(dafs_host_phylogeny_refusal(DAFS_PHYLOGENY_MODEL_NEEDS_TREE));
+  if (o.pairwise && !o.phylogeny.empty()) throw std::string(dafs_host_phylogeny_refusal(DAFS_PHYLOGENY_NO_PAIRWISE));
+  if (o.seed_each && !o.phylogeny.empty()) throw std::string(dafs_host_phylogeny_refusal(DAFS_PHYLOGENY_NO_SEED_EACH));
   if (o.pairwise && (!o.covariation.empty() || o.cov_shuffles_given || o.cov_seed_given))
     throw std::string("--pairwise: two rows carry no covariation; --covariation, --cov-shuffles and --cov-seed cannot be combined with --pairwise");
   if (!o.describe.empty()) {  // a finished alignment: nothing that aligns, and no FILE
     for (const std::string& g : given)
       if (g != "describe" && g != "identity" && g != "identity-matrix" && g != "covariation" && g != "cov-shuffles" && g != "cov-seed" && g != "cov-null" && g != "device" &&
+          g != "phylogeny" && g != "phylogeny-model" && g != "cov-tree" &&
           g.compare(0, 7, "compare") != 0)
         throw "--describe reads a finished alignment: --" + g + " cannot be combined with --describe";
     if (!o.inputs.empty()) throw std::string("--describe takes no FILE: the alignment is its argument");
-    if (o.identity.empty() && o.covariation.empty() && o.compare.empty() && o.compare_ref.empty())
+    if (o.identity.empty() && o.covariation.empty() && o.compare.empty() && o.compare_ref.empty() && o.phylogeny.empty())
       throw std::string("--describe needs --identity or --covariation");
   }
   if (o.compare.empty() != o.compare_ref.empty()) throw std::string(dafs_host_compare_refusal(DAFS_COMPARE_NEEDS_REF));
@@ -849,6 +886,42 @@ std::vector<std::pair<size_t, size_t> > chunks(const std::vector<uint64_t>& byte
   return out;
 }
 
+std::vector<uint8_t> cells_of(const std::vector<std::string>& rows) {
+  const size_t L = rows.empty() ? 0 : rows[0].size();
+  std::vector<uint8_t> cell(rows.size() * L);
+  for (size_t r = 0; r < rows.size(); ++r)
+    for (size_t c = 0; c < L; ++c) cell[r * L + c] = dafs_host_ali_code(rows[r][c]);
+  return cell;
+}
+
+// The neighbour-joining tree of an alignment's rows (Context.alignment_tree is the Python twin): the
+// identity counts, the distances under `model`, the joins on the device.  left, right, length: 2n-1 entries.
+void nj_of(dafs_hip_ctx* ctx, int model, const std::vector<std::string>& rows, std::vector<int32_t>& left, std::vector<int32_t>& right,
+           std::vector<double>& length) {
+  const uint32_t n = (uint32_t)rows.size(), L = (uint32_t)rows[0].size();
+  if (n > 16384) throw std::string(dafs_host_phylogeny_refusal(DAFS_PHYLOGENY_TOO_MANY_ROWS));
+  const std::vector<uint8_t> cell = cells_of(rows);
+  std::vector<uint32_t> ident((size_t)n * n), aligned((size_t)n * n);
+  check(dafs_hip_alignment_identity(ctx, n, L, cell.data(), nullptr, nullptr, 0.0, nullptr, ident.data(), aligned.data(), nullptr, nullptr, nullptr,
+                                    nullptr));
+  std::vector<double> dist((size_t)n * n);
+  check_text(dafs_host_nj_distances(n, ident.data(), aligned.data(), model, dist.data()));
+  left.assign(2 * (size_t)n - 1, -1);
+  right.assign(2 * (size_t)n - 1, -1);
+  length.assign(2 * (size_t)n - 1, 0.0);
+  check_text(dafs_hip_nj_tree(ctx, n, dist.data(), left.data(), right.data(), length.data()));
+}
+
+// --phylogeny: the Newick line of one printed alignment; names: the rows' Stockholm names
+void phylogeny_of(dafs_hip_ctx* ctx, const Options& o, const std::vector<std::string>& names, const std::vector<std::string>& rows, std::string& newick) {
+  std::vector<int32_t> left, right;
+  std::vector<double> length;
+  nj_of(ctx, o.phylogeny_model, rows, left, right, length);
+  char* text = nullptr;
+  check_text(dafs_host_newick((uint32_t)rows.size(), c_strs(names).data(), left.data(), right.data(), length.data(), &text));
+  newick = take(text);
+}
+
 // --covariation: the statistics of one printed alignment (dafs_hip_alignment_covariation_null).
 const double kCovEMax = 0.05;  // the cut of cov_SS_cons
 
@@ -861,7 +934,13 @@ void covariation_of(dafs_hip_ctx* ctx, const Options& o, const std::vector<std::
     for (uint32_t c = 0; c < L; ++c) code[(size_t)r * L + c] = dafs_host_cov_code(rows[r][c]);
   std::vector<uint32_t> best(L), prow(L), pcan(L), ptyp(L);
   std::vector<double> bscore(L), be(L), pscore(L), pe(L);
-  const int rc = dafs_hip_alignment_covariation_null(ctx, n, L, code.data(), ss.data(), o.cov_shuffles, o.cov_seed, o.cov_null, nullptr, nullptr,
+  std::vector<int32_t> left, right;  // --cov-tree nj: the neighbour-joining tree of the rows (model jc); else the library's default
+  if (o.cov_tree_nj && n >= 2) {
+    std::vector<double> length;
+    nj_of(ctx, DAFS_NJ_JC, rows, left, right, length);
+  }
+  const int rc = dafs_hip_alignment_covariation_null(ctx, n, L, code.data(), ss.data(), o.cov_shuffles, o.cov_seed, o.cov_null,
+                                                     left.empty() ? nullptr : left.data(), right.empty() ? nullptr : right.data(),
                                                      nullptr, best.data(), bscore.data(), be.data(), pscore.data(), pe.data(), prow.data(),
                                                      pcan.data(), ptyp.data(), nullptr, nullptr);
   if (o.cov_null == DAFS_COV_NULL_TREE) check_text(rc);  // the tree null's refusals carry a message (a row without a base)
@@ -880,14 +959,6 @@ struct IdentityText {
   std::string table, matrix;    // the tables of --identity and --identity-matrix
   std::vector<double> weight;   // the WT lines of the Stockholm block
 };
-
-std::vector<uint8_t> cells_of(const std::vector<std::string>& rows) {
-  const size_t L = rows.empty() ? 0 : rows[0].size();
-  std::vector<uint8_t> cell(rows.size() * L);
-  for (size_t r = 0; r < rows.size(); ++r)
-    for (size_t c = 0; c < L; ++c) cell[r * L + c] = dafs_host_ali_code(rows[r][c]);
-  return cell;
-}
 
 // names: the rows' Stockholm names; matrix: the pair table too
 void identity_of(dafs_hip_ctx* ctx, const std::vector<std::string>& names, const std::vector<std::string>& rows, bool matrix, IdentityText& out) {
@@ -1061,13 +1132,13 @@ void write_compare(const Options& o, const std::vector<CompareText>& cmp, const 
 
 // Everything one family (an input file, a cluster, a pair, a placement) produces: its text, printed as it is made or kept for
 // the block the run prints later, and the side outputs that are wanted of it
-enum : unsigned { kSto = 1, kCov = 2, kIdt = 4, kCmp = 8 };  // --stockholm, --covariation, --identity, --compare
+enum : unsigned { kSto = 1, kCov = 2, kIdt = 4, kCmp = 8, kPhy = 16 };  // --stockholm, --covariation, --identity, --compare, --phylogeny
 
 struct FamilyOut {
   unsigned wanted = 0;
   std::ostringstream text;
   std::ostream* os = &text;  // &text, or &std::cout
-  std::string sto, cov;
+  std::string sto, cov, phy;
   IdentityText idt;
   CompareText cmp;
   FamilyOut() {}
@@ -1082,19 +1153,21 @@ std::vector<FamilyOut> records(size_t n, unsigned wanted) {
 
 // the side outputs the options ask for; a mode that does not produce one of them clears its flag
 unsigned wanted_of(const Options& o) {
-  return (o.stockholm.empty() ? 0 : kSto) | (o.covariation.empty() ? 0 : kCov) | (o.identity.empty() ? 0 : kIdt) | (o.compare.empty() ? 0 : kCmp);
+  return (o.stockholm.empty() ? 0 : kSto) | (o.covariation.empty() ? 0 : kCov) | (o.identity.empty() ? 0 : kIdt) | (o.compare.empty() ? 0 : kCmp) |
+         (o.phylogeny.empty() ? 0 : kPhy);
 }
 
 // The files of the wanted side outputs, one block or table per record in order; headers: a line "==> header <==" before every
 // record's table (the Stockholm blocks carry none)
 void write_outputs(const Options& o, unsigned wanted, const std::vector<FamilyOut>& recs, const std::vector<std::string>* headers) {
-  std::vector<std::string> sto, cov;
+  std::vector<std::string> sto, cov, phy;
   std::vector<IdentityText> idt;
   std::vector<CompareText> cmp;
-  for (const FamilyOut& r : recs) { sto.push_back(r.sto); cov.push_back(r.cov); idt.push_back(r.idt); cmp.push_back(r.cmp); }
+  for (const FamilyOut& r : recs) { sto.push_back(r.sto); cov.push_back(r.cov); idt.push_back(r.idt); cmp.push_back(r.cmp); phy.push_back(r.phy); }
   if (wanted & kSto) write_tables("--stockholm", o.stockholm, sto, nullptr);
   if (wanted & kCov) write_tables("--covariation", o.covariation, cov, headers);
   if (wanted & kIdt) write_identity(o, idt, headers);
+  if (wanted & kPhy) write_tables("--phylogeny", o.phylogeny, phy, headers);
   if (wanted & kCmp) write_compare(o, cmp, headers);
 }
 
@@ -1623,13 +1696,14 @@ void finish_alignment(dafs_hip_ctx* ctx, const Options& o, const std::vector<Fas
   std::string cov_chars;
   if (out.wanted & kCov) covariation_of(ctx, o, rows, ss_final, out.cov, cov_chars);
   std::vector<std::string> names;  // the printed rows' Stockholm names
-  if (out.wanted & (kSto | kIdt | kCmp)) {
+  if (out.wanted & (kSto | kIdt | kCmp | kPhy)) {
     std::vector<std::string> headers;
     for (size_t i = 0; i < root.size(); ++i) headers.push_back(fa[first + i].name());
     const std::vector<std::string> all_names = stockholm_names(headers);
     for (const auto& row : root) names.push_back(all_names[row.first - first]);
   }
   if (out.wanted & kIdt) identity_of(ctx, names, rows, !o.identity_matrix.empty(), out.idt);
+  if (out.wanted & kPhy) phylogeny_of(ctx, o, names, rows, out.phy);
   if (out.wanted & kCmp) compare_of(ctx, o, names, rows, &ss_final, nullptr, nullptr, out.cmp);
   if (out.wanted & kSto) {
     char* text = nullptr;
@@ -1950,7 +2024,7 @@ int run_add_each(const Options& o, int align_model) {
   for (uint32_t j = 0; j < k; ++j) bytes[j] = dafs_host_seed_each_bytes(m, sd.lens.data(), C, lens[j]);
   dafs_dd_params prm = dd_params_of(o);
   prm.skip_uncoupled_folds = o.verbose == 0 ? 1 : 0;  // as run_add
-  const unsigned wanted = wanted_of(o) & ~(kIdt | kCmp);
+  const unsigned wanted = wanted_of(o) & ~(kIdt | kCmp | kPhy);
   const bool listed = !(wanted & kSto) && o.align_pct != 0.0f;  // the reliabilities of --stockholm read the seed-seed rows
   std::vector<uint32_t> matched(k, 0);
   std::vector<double> score(k, 0.0);
@@ -2317,6 +2391,11 @@ int run_describe(const Options& o) {
     IdentityText idt;
     identity_of(ctx, names, rows, !o.identity_matrix.empty(), idt);
     write_identity(o, {idt}, nullptr);
+  }
+  if (!o.phylogeny.empty()) {
+    std::string newick;
+    phylogeny_of(ctx, o, names, rows, newick);
+    write_text("--phylogeny", o.phylogeny, newick);
   }
   if (!o.covariation.empty()) {
     std::string cov, chars;

@@ -1,6 +1,6 @@
 // dafs_amd/csrc/host_text.cpp -- the text formats and memory estimates of both drivers as C entry points (include/dafs_hip.h,
-// "host text"): the Stockholm block, the --covariation, --pairwise-scores, --identity and --compare tables, the seed reader of --seed, the estimates
-// and the greedy chunking.  The C++ command line calls them directly and the Python driver through capi.py, so every byte and
+// "host text"): the Stockholm block, the --covariation, --pairwise-scores, --identity and --compare tables, the Newick line of --phylogeny,
+// the seed reader of --seed, the estimates and the greedy chunking.  The C++ command line calls them directly and the Python driver through capi.py, so every byte and
 // every formula is defined here once.  Host logic only: nothing here includes HIP or touches a device.
 #include <algorithm>
 #include <cmath>
@@ -458,6 +458,87 @@ extern "C" const char* dafs_host_alistat_refusal(int which) {
     default:
       return "";
   }
+}
+
+extern "C" const char* dafs_host_phylogeny_refusal(int which) {
+  switch (which) {
+    case DAFS_PHYLOGENY_NO_PAIRWISE:
+      return "a neighbour-joining tree (--phylogeny, phylogeny) cannot be combined with pairwise alignments (--pairwise, pipeline.pairwise): "
+             "it goes with a run, several files or a seed";
+    case DAFS_PHYLOGENY_NO_SEED_EACH:
+      return "a neighbour-joining tree (--phylogeny, phylogeny) cannot be combined with per-sequence placements (--seed-each, "
+             "pipeline.add_each): it goes with a run, several files or --seed";
+    case DAFS_PHYLOGENY_TOO_MANY_ROWS:
+      return "a neighbour-joining tree (--phylogeny, phylogeny, --cov-tree nj) holds the whole distance matrix on the device: at most 16384 rows";
+    case DAFS_PHYLOGENY_MODEL_NEEDS_TREE:
+      return "--phylogeny-model needs --phylogeny";
+    case DAFS_PHYLOGENY_UNKNOWN_MODEL:
+      return "the distance model of the neighbour-joining tree (--phylogeny-model, phylogeny) is jc or p";
+    case DAFS_PHYLOGENY_COV_TREE_NEEDS_NULL:
+      return "the tree of the covariation null (--cov-tree, tree) needs the tree null (--cov-null tree, null=\"tree\")";
+    case DAFS_PHYLOGENY_UNKNOWN_COV_TREE:
+      return "the tree of the covariation null (--cov-tree, tree) is average or nj";
+    default:
+      return "";
+  }
+}
+
+// The Newick line of a tree in the arrays of dafs_host_build_tree.  The walk keeps its own stack of
+// (node, next step), so a chain of any depth uses none of the call stack.
+extern "C" int dafs_host_newick(uint32_t n, const char* const* names, const int32_t* left, const int32_t* right, const double* length,
+                                char** out) {
+  return text_out(out, [&]() {
+    if (!n || !left || !right) throw kBadArgument;
+    if (n > 0x7FFFFFFFu / 2) throw std::string("newick: too many leaves");
+    const std::vector<std::string> nm = strings(n, names);
+    const uint32_t T = 2 * n - 1;
+    std::vector<uint8_t> is_child(T, 0);  // the checks of dafs_host_cluster_cut
+    for (uint32_t i = 0; i < T; ++i) {
+      if (i < n) {
+        if (left[i] != -1 || right[i] != -1) throw std::string("newick: malformed tree (a leaf with a child)");
+        continue;
+      }
+      const int64_t ch[2] = {left[i], right[i]};
+      if (ch[0] == ch[1]) throw std::string("newick: malformed tree (a join of a node with itself)");
+      for (int64_t c : ch) {
+        if (c < 0 || c >= (int64_t)i) throw std::string("newick: malformed tree (a child that is not an earlier node)");
+        if (is_child[c]) throw std::string("newick: malformed tree (a node that is a child twice)");
+        is_child[c] = 1;
+      }
+    }
+    auto quoted = [](const std::string& s) {
+      bool plain = !s.empty();
+      for (char ch : s)
+        if (strchr("()[]':;,", ch) || is_space(ch)) plain = false;
+      if (plain) return s;
+      std::string q = "'";
+      for (char ch : s) { q += ch; if (ch == '\'') q += '\''; }
+      return q + "'";
+    };
+    std::string text;
+    std::vector<std::pair<uint32_t, uint8_t> > stack;
+    stack.push_back(std::make_pair(T - 1, (uint8_t)0));
+    while (!stack.empty()) {
+      const uint32_t node = stack.back().first;
+      const uint8_t step = stack.back().second++;
+      if (node < n) {
+        text += quoted(nm[node]);
+      } else if (step == 0) {
+        text += "(";
+        stack.push_back(std::make_pair((uint32_t)left[node], (uint8_t)0));
+        continue;
+      } else if (step == 1) {
+        text += ",";
+        stack.push_back(std::make_pair((uint32_t)right[node], (uint8_t)0));
+        continue;
+      } else {
+        text += ")";
+      }
+      if (length && node != T - 1) text += ":" + fmt9d(length[node]);
+      stack.pop_back();
+    }
+    return text + ";\n";
+  });
 }
 
 // Alignment statistics: the cell code, the summary and the tables of --identity and --identity-matrix

@@ -54,7 +54,7 @@ class Result:
 def run(names, seqs, ctx=None, bp=None, w=4.0, eta0=0.5, t_max=600, w_pct_a=0.25, w_pct_s=0.25, th_a=0.01,
         th_s=0.2, th_s1=None, align_model=capi.ALIGN_PROBCONS, force_iters=0, timers=None, level_sync=False, slice_iters=None,
         mp=None, skip_uncoupled_folds=True, shard=None, round_us=None, w_pct_f=0.0, bp_update=False, bp_update1=False,
-        reliability=False, covariation=False, row_structures=False, identity=False, compare=None):
+        reliability=False, covariation=False, row_structures=False, identity=False, compare=None, phylogeny=False):
     """The whole run.  bp: per-sequence (rowptr, col, val) base-pairing rows (--fold-aux); None
     computes them with the device fold model.  mp: supplied matching probabilities (--align-aux), see Context.set_mp.
     shard: (torch.distributed module, torch device) of an initialised process group -- phase 1 (folds, pair posteriors,
@@ -64,8 +64,10 @@ def run(names, seqs, ctx=None, bp=None, w=4.0, eta0=0.5, t_max=600, w_pct_a=0.25
     .covariation (see _final).  row_structures: the result also gets .row_ss and .row_ss_str, the structure of every printed
     row on its own (see _phase2_forest).  identity: the result also gets .identity (see alignment_identity) and its
     Stockholm block the `#=GS <name> WT` lines.  compare: (ref_names, ref_rows[, ref_ss]), a reference alignment of the same
-    sequences as stockholm.read_seed_structure returns it: the result also gets .compare (see compare)."""
+    sequences as stockholm.read_seed_structure returns it: the result also gets .compare (see compare).  phylogeny: "jc" or
+    "p": the result also gets .phylogeny (see alignment_phylogeny), the neighbour-joining tree of the printed rows."""
     import time
+    phylogeny_model(phylogeny)
     # combinations this driver does not implement are refused, not ignored (the command line, cli_main.cpp, has no level
     # batches: its --bp-update runs in the resident-node rounds and in the refinement's solve_node)
     if level_sync and bp_update:
@@ -88,7 +90,8 @@ def run(names, seqs, ctx=None, bp=None, w=4.0, eta0=0.5, t_max=600, w_pct_a=0.25
     t.append(time.perf_counter())
     fam = dict(names=names, seqs=seqs, first=0, sim=sim, tree=(score, left, right))
     return _phase2_forest(ctx, own, [fam], t, w, eta0, t_max, th_a, th_s, th_s1, force_iters, level_sync, slice_iters,
-                          skip_uncoupled_folds, round_us, bp_update, bp_update1, reliability, covariation, row_structures, identity, compare)[0]
+                          skip_uncoupled_folds, round_us, bp_update, bp_update1, reliability, covariation, row_structures, identity, compare,
+                          phylogeny)[0]
 
 
 def _phase1_local(ctx, seqs, bp, mp, align_model, th_a, w_pct_a, w_pct_s, t, w_pct_f=0.0, first=None, constraints=None):
@@ -187,7 +190,7 @@ def _solve_nodes(ctx, prm, take_ready, finish, level_sync=False, slice_iters=Non
 
 def _phase2_forest(ctx, own, fams, t, w, eta0, t_max, th_a, th_s, th_s1, force_iters, level_sync, slice_iters,
                    skip_uncoupled_folds, round_us=None, bp_update=False, bp_update1=False, reliability=False, covariation=False,
-                   row_structures=False, identity=False, compare=None):
+                   row_structures=False, identity=False, compare=None, phylogeny=False):
     """The progressive phase and the output of every family of the context at once.  fams: per family a dict with names,
     seqs, first (index of its first sequence in the context), sim and tree = (score, left, right).  The guide trees form one
     forest: a node is ready when both of its children are done, whatever its family, and the ready nodes of all families
@@ -290,7 +293,7 @@ def _phase2_forest(ctx, own, fams, t, w, eta0, t_max, th_a, th_s, th_s1, force_i
         res.rounds = rounds
         sidx, mask = roots[f]
         _final(ctx, res, fm["names"], fm["seqs"], fm["first"], sidx, mask, finals[f], rls[f], res.tree_line, None, covariation, rows_ss[f],
-               identity, compare)
+               identity, compare, phylogeny)
     t.append(time.perf_counter())
     # fold_launch: the folding is only started there; its kernels overlap `pair` and the first half of `pct_fold_tree`,
     # which also holds the wait for them
@@ -306,18 +309,62 @@ def _phase2_forest(ctx, own, fams, t, w, eta0, t_max, th_a, th_s, th_s1, force_i
 def cov_options(covariation):
     """The covariation option of run / run_batch / add as a dict with shuffles, seed and e_max, or None for off.  The key
     null (one of capi.COV_NULLS; "tree" takes the default tree of the printed rows) is kept only where the caller gave it:
-    without it the null is "shuffle"."""
+    without it the null is "shuffle".  The key tree (one of capi.COV_TREES, with null="tree" only; `dafs --cov-tree`) names
+    that tree: "average", the default, or "nj", the neighbour-joining tree of the printed rows."""
     if covariation is None or covariation is False:
         return None
     opt = dict(shuffles=100, seed=1, e_max=0.05)
     if covariation is not True:
-        unknown = set(covariation) - set(opt) - {"null"}
+        unknown = set(covariation) - set(opt) - {"null", "tree"}
         if unknown:
-            raise ValueError("covariation: unknown keys %s (shuffles, seed, e_max, null)" % sorted(unknown))
+            raise ValueError("covariation: unknown keys %s (shuffles, seed, e_max, null, tree)" % sorted(unknown))
         opt.update(covariation)
     if opt.get("null", "shuffle") not in capi.COV_NULLS:
         raise ValueError("covariation: unknown null %r (one of %s)" % (opt["null"], ", ".join(capi.COV_NULLS)))
+    if "tree" in opt:  # --cov-tree: "average" is the library's default tree, "nj" the neighbour-joining tree of the rows
+        if opt["tree"] not in capi.COV_TREES:
+            raise ValueError(capi.phylogeny_refusal(capi.PHY_UNKNOWN_COV_TREE))
+        if opt.get("null", "shuffle") != "tree":
+            raise ValueError(capi.phylogeny_refusal(capi.PHY_COV_TREE_NEEDS_NULL))
     return opt
+
+
+def _covariation(ctx, rows, ss, covariation):
+    """Context.alignment_covariation under the options of cov_options, the options beside the arrays.  tree="nj": the tree null
+    evolves along the neighbour-joining tree of the rows (Context.alignment_tree, model "jc")."""
+    tree = None
+    if covariation.get("tree") == "nj" and len(rows) >= 2:
+        tree = ctx.alignment_tree(rows)[:2]
+    cv = ctx.alignment_covariation(rows, ss, shuffles=covariation["shuffles"], seed=covariation["seed"], null=covariation.get("null", "shuffle"),
+                                   tree=tree)
+    cv.update(covariation)
+    return cv
+
+
+class Phylogeny:
+    """Result of alignment_phylogeny: .model, .left, .right, .length (Context.alignment_tree) and .newick (capi.newick)"""
+
+
+def phylogeny_model(phylogeny):
+    """The phylogeny option of run / run_batch / add / describe / cluster as a model name, or None for off (False, None).
+    True is "jc"."""
+    if phylogeny is None or phylogeny is False:
+        return None
+    if phylogeny is True:
+        return "jc"
+    if phylogeny not in capi.NJ_MODELS:
+        raise ValueError(capi.phylogeny_refusal(capi.PHY_UNKNOWN_MODEL))
+    return phylogeny
+
+
+def alignment_phylogeny(ctx, row_names, rows, model="jc"):
+    """The neighbour-joining tree of an alignment's rows (`dafs --phylogeny OUT`): Context.alignment_tree
+    over all columns under `model`, and the Newick line with the rows' Stockholm names, byte for byte the command line's."""
+    out = Phylogeny()
+    out.model = model
+    out.left, out.right, out.length = ctx.alignment_tree(rows, model=model)
+    out.newick = capi.newick(row_names, out.left, out.right, out.length)
+    return out
 
 
 def _row_structures(ctx, sidx_per_alignment, lens, th):
@@ -381,13 +428,14 @@ def identity_matrix_tsv(row_names, identity):
     return capi.host_text(capi._identity_matrix_table, n, capi.c_strings(row_names), *[a.ctypes.data for a in arrs])
 
 
-def describe(names, rows, ss=None, ctx=None, identity=True, covariation=False, compare=None, pp=None):
+def describe(names, rows, ss=None, ctx=None, identity=True, covariation=False, compare=None, pp=None, phylogeny=False):
     """The alignment-only statistics of a finished alignment (`dafs --describe ALIGNMENT`): nothing is
     aligned.  names / rows / ss: as stockholm.read_seed_structure returns them (ss None: no structure).  Returns a Result with
     .rows, .row_names (stockholm.names), .ss and, as asked, .identity (alignment_identity over all columns) and .covariation
     (as run's).  compare (as run's): .compare, this alignment against the reference; pp: its PP rows (stockholm.read_seed_pp)
-    for the comparison's PP part."""
+    for the comparison's PP part.  phylogeny (as run's): .phylogeny."""
     covariation = cov_options(covariation)
+    phylogeny = phylogeny_model(phylogeny)
     names, rows = stockholm.clean_seed(names, rows)
     res = Result()
     res.rows, res.row_names = rows, stockholm.names(names)
@@ -400,9 +448,10 @@ def describe(names, rows, ss=None, ctx=None, identity=True, covariation=False, c
     try:
         if identity:
             res.identity = alignment_identity(ctx, rows)
+        if phylogeny:
+            res.phylogeny = alignment_phylogeny(ctx, res.row_names, rows, phylogeny)
         if covariation:
-            res.covariation = ctx.alignment_covariation(rows, res.ss, shuffles=covariation["shuffles"], seed=covariation["seed"], null=covariation.get("null", "shuffle"))
-            res.covariation.update(covariation)
+            res.covariation = _covariation(ctx, rows, res.ss, covariation)
         if compare is not None:
             res.compare = compare_result(ctx, compare, res.row_names, rows, None if ss is None else res.ss, pp=pp)
     finally:
@@ -469,7 +518,8 @@ def compare_result(ctx, reference, row_names, rows, ss, use_test=None, pp=None):
     return res
 
 
-def _final(ctx, res, names, seqs, first, sidx, mask, ss, rl, tree_line, rf=None, covariation=None, row_ss=None, identity=False, compare=None):
+def _final(ctx, res, names, seqs, first, sidx, mask, ss, rl, tree_line, rf=None, covariation=None, row_ss=None, identity=False, compare=None,
+           phylogeny=False):
     """The output of a final alignment (sidx: global sequence index per row, mask) with its common structure ss
     (_final_structure), into res: .ss, .ss_str, .rows, .output and, with rl, .reliability and .stockholm.  names / seqs: the
     family's, its first sequence at global index `first`.  rl: the alignment's dict of Context.alignment_reliabilities for
@@ -479,7 +529,9 @@ def _final(ctx, res, names, seqs, first, sidx, mask, ss, rl, tree_line, rf=None,
     and e_max beside the arrays; the Stockholm block then carries a `#=GC cov_SS_cons` line.  row_ss: per printed row its own structure (_row_structures) -> .row_ss, .row_ss_str
     and the `#=GR <name> SS` lines of the Stockholm block.  identity: .identity, alignment_identity of the printed rows in
     printed order over all columns, and .row_names, their Stockholm names; the Stockholm block then carries the `#=GS <name> WT` lines.
-    compare: a reference (run's compare) -> .compare, the printed rows and ss against it (compare_result), and .row_names."""
+    compare: a reference (run's compare) -> .compare, the printed rows and ss against it (compare_result), and .row_names.
+    phylogeny: a model -> .phylogeny (alignment_phylogeny of the printed rows), and .row_names."""
+    phylogeny = phylogeny_model(phylogeny)
     res.ss = ss
     res.ss_str = capi.make_brackets(ss)
     order = np.argsort(sidx, kind="stable")  # std::sort(aln) :1876
@@ -498,15 +550,16 @@ def _final(ctx, res, names, seqs, first, sidx, mask, ss, rl, tree_line, rf=None,
         res.row_ss_str = [stockholm.row_ss_str(row, x) for row, x in zip(res.rows, row_ss)]
     cov_chars = None
     if covariation:
-        cv = ctx.alignment_covariation(res.rows, ss, shuffles=covariation["shuffles"], seed=covariation["seed"], null=covariation.get("null", "shuffle"))
-        cv.update(covariation)
+        cv = _covariation(ctx, res.rows, ss, covariation)
         res.covariation = cv
         cov_chars = stockholm.cov_ss_cons(ss, cv["pair_e"], cv["e_max"])
-    if identity or compare is not None:
+    if identity or compare is not None or phylogeny:
         sto_names = stockholm.names(names)
         res.row_names = [sto_names[int(sidx[r]) - first] for r in order]
     if identity:
         res.identity = alignment_identity(ctx, res.rows)
+    if phylogeny:
+        res.phylogeny = alignment_phylogeny(ctx, res.row_names, res.rows, phylogeny)
     if compare is not None:
         res.compare = compare_result(ctx, compare, res.row_names, res.rows, ss)
     if rl is not None:
@@ -558,7 +611,7 @@ def _printed_support(sup, sidx):
 def add(seed_names, seed_rows, names, seqs, ctx=None, w=4.0, eta0=0.5, t_max=600, w_pct_a=0.25, w_pct_s=0.25, th_a=0.01,
         th_s=0.2, th_s1=None, align_model=capi.ALIGN_PROBCONS, force_iters=0, slice_iters=None, skip_uncoupled_folds=True,
         round_us=None, w_pct_f=0.0, bp_update1=False, reliability=False, covariation=False, row_structures=False, seed_ss=None,
-        identity=False, compare=None):
+        identity=False, compare=None, phylogeny=False):
     """Add new sequences to a fixed seed alignment without changing its columns (`dafs --seed`).
     seed_names / seed_rows: the seed's rows (letters and '.' / '-' gaps; stockholm.read_seed reads a file), checked and
     without their all-gap columns (stockholm.clean_seed).  names / seqs: the new sequences.  The options are run()'s.
@@ -570,7 +623,8 @@ def add(seed_names, seed_rows, names, seqs, ctx=None, w=4.0, eta0=0.5, t_max=600
     .z (per new sequence its column map into the seed), .rf (per merged column True for a seed column), .dd_log
     ({j: (iterations, violated, ncbp, score)}), .dd_memory, .seconds; with reliability, .reliability and .stockholm (no CC
     line, a `#=GC RF` line); with covariation (as in run), .covariation; with row_structures (as in run), .row_ss and
-    .row_ss_str; with identity (as in run), .identity; with compare (as in run), .compare.
+    .row_ss_str; with identity (as in run), .identity; with compare (as in run), .compare; with phylogeny (as in run),
+    .phylogeny.
 
     seed_ss (`dafs --seed-structure`): the seed's consensus structure over its cleaned columns
     (stockholm.read_seed_structure), fixed like the columns.  The seed rows are folded under the constraints it puts on them
@@ -579,6 +633,7 @@ def add(seed_names, seed_rows, names, seqs, ctx=None, w=4.0, eta0=0.5, t_max=600
     canonical, half and expected of Context.structure_support."""
     import time
     covariation = cov_options(covariation)
+    phylogeny_model(phylogeny)
     seed_names, seed_rows = stockholm.clean_seed(seed_names, seed_rows)
     names, seqs = list(names), list(seqs)
     if not seqs or len(names) != len(seqs):
@@ -632,7 +687,7 @@ def add(seed_names, seed_rows, names, seqs, ctx=None, w=4.0, eta0=0.5, t_max=600
             ss_m = _final_structure(ctx, sidx, rows_mask, th1, bp_update1, ctx.consensus_structure(sidx, rows_mask, th1)[1])
         rl = ctx.alignment_reliability(sidx, rows_mask, ss_m) if reliability else None
         _final(ctx, res, all_names, all_seqs, 0, sidx, rows_mask, ss_m, rl, None, rf, covariation,
-               _row_structures(ctx, [sidx], dict(enumerate(map(len, all_seqs))), th1)[0] if row_structures else None, identity, compare)
+               _row_structures(ctx, [sidx], dict(enumerate(map(len, all_seqs))), th1)[0] if row_structures else None, identity, compare, phylogeny)
         t.append(time.perf_counter())
         res.seconds = dict(phase1=t[3] - t[0], nodes=t[4] - t[3], final=t[5] - t[4], total=t[5] - t[0])
     finally:
@@ -684,6 +739,7 @@ def run_batch(families, ctx=None, max_bytes=None, **kw):
     if unknown:
         raise TypeError("pipeline.run_batch: unknown options %s" % sorted(unknown))
     opts.update(kw)
+    phylogeny_model(opts["phylogeny"])
     families = [(list(nm), list(sq)) for nm, sq in families]
     for nm, sq in families:
         if not sq or len(nm) != len(sq):
@@ -710,7 +766,7 @@ def run_batch(families, ctx=None, max_bytes=None, **kw):
             res = _phase2_forest(ctx, False, fams, t, opts["w"], opts["eta0"], opts["t_max"], opts["th_a"], opts["th_s"], opts["th_s1"],
                                  opts["force_iters"], opts["level_sync"], opts["slice_iters"], opts["skip_uncoupled_folds"], opts["round_us"],
                                  opts["bp_update"], opts["bp_update1"], opts["reliability"], opts["covariation"], opts["row_structures"],
-                                 opts["identity"])
+                                 opts["identity"], None, opts["phylogeny"])
             for k, r in zip(grp, res):
                 out[k] = r
     finally:
@@ -820,6 +876,8 @@ def pairwise(names, seqs, pairs=None, ctx=None, max_bytes=None, **opts):
         raise ValueError("pipeline.pairwise: two rows carry no covariation; covariation is an option of run, run_batch and add")
     if opts.get("identity"):
         raise ValueError(capi.alistat_refusal(capi.NO_PAIRWISE))
+    if opts.get("phylogeny"):
+        raise ValueError(capi.phylogeny_refusal(capi.PHY_NO_PAIRWISE))
     if opts.get("compare") is not None:
         raise ValueError(capi.compare_refusal(capi.CMP_NO_PAIRWISE))
     if opts.get("level_sync") and opts.get("bp_update"):
@@ -1034,6 +1092,8 @@ def add_each(seed_names, seed_rows, names, seqs, ctx=None, max_bytes=None, merge
     if unknown:
         raise TypeError("pipeline.add_each: unknown options %s" % sorted(unknown))
     o.update(opts)
+    if o["phylogeny"]:
+        raise ValueError(capi.phylogeny_refusal(capi.PHY_NO_SEED_EACH))
     covariation = cov_options(o["covariation"])
     seed_names, seed_rows = stockholm.clean_seed(seed_names, seed_rows)
     names, seqs = list(names), list(seqs)
@@ -1161,7 +1221,7 @@ def add_each(seed_names, seed_rows, names, seqs, ctx=None, max_bytes=None, merge
                     for key in out.support:  # the new sequence is the first row of its alignment
                         out.support[key][j] = support[f][key][0]
                 _final(ctx, res, seed_names + [names[j]], seed_seqs + [seqs[j]], f * n, alns[f][0], alns[f][1], finals[f], rls[f], None,
-                       rfs[f], covariation, rows_ss[f], o["identity"])
+                       rfs[f], covariation, rows_ss[f], o["identity"])  # no tree per placement: refused above
                 out.results[j] = res
                 out.score[j] = oj["score"]
                 out.iterations[j] = oj["iterations"]
@@ -1267,6 +1327,7 @@ def cluster(names, seqs, threshold=None, count=None, min_size=1, ctx=None, max_b
     if unknown:
         raise TypeError("pipeline.cluster: unknown options %s" % sorted(unknown))
     cov_options(opts.get("covariation"))
+    phylogeny_model(opts.get("phylogeny"))
     names, seqs = list(names), list(seqs)
     n = len(seqs)
     if n == 0 or len(names) != n or any(len(s) == 0 for s in seqs):

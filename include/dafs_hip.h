@@ -298,6 +298,60 @@ size_t dafs_hipk_linkage_workspace(uint32_t n);
 int dafs_hipk_linkage(int linkage, uint32_t n, const float* d_sim, void* d_workspace, float* d_score, int32_t* d_left, int32_t* d_right,
                       void* hip_stream);
 
+/* The neighbour-joining tree (Saitou & Nei in the Studier-Keppler form) of an n x n distance matrix, joined on the device (no
+ * counterpart in the reference; the contract, to the bit; `dafs --phylogeny`, `--cov-tree nj`,
+ * Context.nj_tree).  dist: a host n x n matrix of doubles of which only the entries x < y are read, all of them finite; the rest
+ * may hold anything.  left/right: 2n-1 entries in the layout of dafs_host_build_tree, so dafs_hip_alignment_covariation_null,
+ * dafs_host_cluster_table and dafs_host_newick take them unchanged.  length[2n-1]: the length of the branch above each node, 0.0
+ * at the root; the last join puts the root in the middle of the last edge.  With m active slots, R[k] the running sum of row k
+ * and D symmetric, join t (node n + t) takes the active pair a < b with the smallest
+ * Q = ((double)(m - 2) * D(a,b) - R[a]) - R[b] (compared as doubles; among equals the smallest a, then the smallest b), writes
+ * la = 0.5 * D(a,b) + (R[a] - R[b]) / (2.0 * (double)(m - 2)) (0.5 * D(a,b) when m = 2) and lb = D(a,b) - la as they are
+ * computed (negative lengths are not clamped), and slot a then holds the join with, for every other active k,
+ * D(a,k) = 0.5 * ((D(a,k) + D(b,k)) - D(a,b)).  n = 1 gives the one-leaf tree without a launch.  n up to 16 384 (a working copy
+ * of n * n doubles on the device).
+ * DAFS_HIP_EINVAL with a message in dafs_hip_last_error, outputs untouched and the context usable: a null pointer, n = 0 or
+ * above 16 384, a non-finite entry above the diagonal (no join runs), and any non-finite value that the joins write into the
+ * distances, the row sums or the lengths (overflow: the joins run to their end and the call then refuses).  DAFS_HIP_ENOMEM: the
+ * device allocation failed. */
+int dafs_hip_nj_tree(dafs_hip_ctx* ctx, uint32_t n, const double* dist, int32_t* left, int32_t* right, double* length);
+/* L0 of the same: the caller's device matrix d_dist (n x n doubles, the entries x < y read, left
+ * untouched), the caller's workspace of dafs_hipk_nj_workspace(n) bytes (256-byte aligned; 0 for n = 0 or above 16 384) and
+ * device outputs of 2n-1 entries; 2 + 2 (n - 1) kernels on hip_stream, no allocation and no wait.  n >= 2.  When the stream has
+ * drained the workspace begins with { uint32 nonfinite; uint32 written; uint32 joins; uint32 fault }: nonfinite > 0 is the
+ * refusal of a non-finite entry above the diagonal, after which no join ran and only the leaves are written; written > 0 is the
+ * refusal of an overflow (the outputs are then to be discarded); otherwise joins = n - 1 and fault = 0. */
+size_t dafs_hipk_nj_workspace(uint32_t n);
+int dafs_hipk_nj(uint32_t n, const double* d_dist, void* d_workspace, int32_t* d_left, int32_t* d_right, double* d_length,
+                 void* hip_stream);
+/* Host-side helper (no device work): the distances of an alignment's rows for the call above, from the n x n integer matrices
+ * of dafs_hip_alignment_identity.  For r != s, comp = aligned(r,s) and mism = comp - ident(r,s): a letter
+ * outside ACGU is aligned and identical to nothing, so it counts as a difference.  DAFS_NJ_P: (double)mism / (double)comp, 1.0
+ * when comp = 0.  DAFS_NJ_JC (Jukes-Cantor): 3.0 when comp = 0 or 4 mism >= 3 comp (in uint64); otherwise, with
+ * x = 1.0 - (4.0 * (double)mism) / (3.0 * (double)comp) and k = floor(-0.75 * log(x) * 1048576.0 + 0.5), the value
+ * min(k, 3 * 2^20) / 1048576.0.  dist[n * n] is written whole, 0.0 on the diagonal.  DAFS_HIP_EINVAL: a null pointer, n = 0, an
+ * unknown model, ident(r,s) > aligned(r,s). */
+enum { DAFS_NJ_P = 0, DAFS_NJ_JC = 1 };
+int dafs_host_nj_distances(uint32_t n, const uint32_t* ident, const uint32_t* aligned, int model, double* dist);
+/* Host-side helper (no device work): a tree of n leaves (the arrays of dafs_host_build_tree) as one Newick line into *out
+ * (dafs_host_free).  A join is "(L:len,R:len)" with the left child first, nested; the root carries no length and the text
+ * ends in ";\n"; lengths are written as %.9g; length = NULL writes the topology only.  A name holding any of ()[]':;, or white
+ * space is put in single quotes with every ' doubled.  n = 1 gives "name;\n".  The walk keeps its own stack: a chain of any
+ * depth uses none of the call stack.  DAFS_HIP_EINVAL (message in dafs_hip_last_error): n = 0, a null pointer or name, and a
+ * malformed tree by the checks of dafs_host_cluster_cut. */
+int dafs_host_newick(uint32_t n, const char* const* names, const int32_t* left, const int32_t* right, const double* length, char** out);
+/* What both drivers say when they refuse a combination of the phylogeny options */
+enum {
+  DAFS_PHYLOGENY_NO_PAIRWISE = 0,      /* a tree asked of pairwise alignments */
+  DAFS_PHYLOGENY_NO_SEED_EACH,         /* a tree asked of per-sequence placements */
+  DAFS_PHYLOGENY_TOO_MANY_ROWS,        /* more than 16 384 rows */
+  DAFS_PHYLOGENY_MODEL_NEEDS_TREE,     /* --phylogeny-model without --phylogeny */
+  DAFS_PHYLOGENY_UNKNOWN_MODEL,        /* a model that is neither jc nor p */
+  DAFS_PHYLOGENY_COV_TREE_NEEDS_NULL,  /* --cov-tree without --cov-null tree */
+  DAFS_PHYLOGENY_UNKNOWN_COV_TREE      /* a tree that is neither average nor nj */
+};
+const char* dafs_host_phylogeny_refusal(int which);
+
 /* Host-side helper (no device work): the merge of `dafs --seed` and pipeline.add, k new sequences
  * placed into a fixed seed alignment of C columns.  lens: k sequence lengths; z: their column maps from the k nodes (leaf j
  * against the seed) concatenated, per residue a seed column or DAFS_HIP_NONE, the seed columns strictly increasing within
