@@ -169,6 +169,16 @@ nj_workspace = _sig("dafs_hipk_nj_workspace", C.c_size_t, [C.c_uint32])
 nj_launch = _sig("dafs_hipk_nj", C.c_int, [C.c_uint32] + [C.c_void_p] * 6)
 _nj_distances = _sig("dafs_host_nj_distances", C.c_int, [C.c_uint32, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p])
 NJ_MODELS = ("p", "jc")  # --phylogeny-model; the index is the library's DAFS_NJ_* code
+_nj_trees = _sig("dafs_hip_nj_trees", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32] + [C.c_void_p] * 4)
+nj_batch_workspace = _sig("dafs_hipk_nj_batch_workspace", C.c_size_t, [C.c_uint32, C.c_uint32])
+nj_batch_launch = _sig("dafs_hipk_nj_batch", C.c_int, [C.c_uint32, C.c_uint32] + [C.c_void_p] * 6)
+_alignment_bootstrap = _sig("dafs_hip_alignment_bootstrap", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int,
+                                                                     C.c_uint32, C.c_uint64] + [C.c_void_p] * 5)
+_bootstrap_alignment = _sig("dafs_hip_bootstrap_alignment", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64,
+                                                                     C.c_uint32, C.c_void_p])
+bootstrap_fixups = _sig("dafs_hip_bootstrap_fixups", C.c_uint64, [])
+_tree_support = _sig("dafs_host_tree_support", C.c_int, [C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p])
+BOOTSTRAP_MAX = 65536
 NJ_MAX_ROWS = 16384
 COV_TREES = ("average", "nj")  # --cov-tree
 _merge_added = _sig("dafs_host_merge_added", C.c_int, [C.c_uint32, C.c_uint32] + [C.c_void_p] * 5)
@@ -263,9 +273,13 @@ _stockholm_nr = _sig("dafs_host_stockholm_nr", C.c_int, [C.c_char_p, C.c_uint32,
 _alistat_refusal = _sig("dafs_host_alistat_refusal", C.c_char_p, [C.c_int])
 NO_PAIRWISE, NR_NEEDS_MERGED, NR_THRESHOLD, TOO_MANY_ROWS = range(4)  # dafs_host_alistat_refusal
 _newick = _sig("dafs_host_newick", C.c_int, [C.c_uint32, _strs, C.c_void_p, C.c_void_p, C.c_void_p, _text])
+_newick_support = _sig("dafs_host_newick_support", C.c_int, [C.c_uint32, _strs] + [C.c_void_p] * 4 + [C.c_uint32, _text])
+_support_table = _sig("dafs_host_support_table", C.c_int, [C.c_uint32, _strs] + [C.c_void_p] * 3 + [C.c_uint32, C.c_uint64, C.c_int, _text])
 _phylogeny_refusal = _sig("dafs_host_phylogeny_refusal", C.c_char_p, [C.c_int])
 (PHY_NO_PAIRWISE, PHY_NO_SEED_EACH, PHY_TOO_MANY_ROWS, PHY_MODEL_NEEDS_TREE, PHY_UNKNOWN_MODEL, PHY_COV_TREE_NEEDS_NULL,
  PHY_UNKNOWN_COV_TREE) = range(7)  # dafs_host_phylogeny_refusal
+_bootstrap_refusal = _sig("dafs_host_bootstrap_refusal", C.c_char_p, [C.c_int])
+BOOT_NEEDS_TREE, BOOT_COUNT, BOOT_NEEDS_REPLICATES, BOOT_NO_COLUMN = range(4)  # dafs_host_bootstrap_refusal
 _seed_table_nearest = _sig("dafs_host_seed_table_nearest", C.c_int, [C.c_uint32, _strs] + [C.c_void_p] * 8 + [_strs, C.c_void_p, _text])
 # dafs_allgather_fn(user, send, recv, bytes, hip_stream): the caller's collective of a sharded phase 1
 _allgather_fn = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
@@ -619,6 +633,72 @@ class Context:
             raise ValueError(phylogeny_refusal(PHY_TOO_MANY_ROWS))
         idt = self.alignment_identity(cell, use=use, matrix=True, nearest=False)
         return self.nj_tree(nj_distances(idt.ident, idt.aligned, model))
+
+    def nj_trees(self, dists):
+        """dafs_hip_nj_trees: the neighbour-joining trees of `count` n x n matrices (float64
+        [count, n, n]; of each only the entries x < y are read), all matrices in one launch up to 2 048 rows.  Returns (left,
+        right, length) as [count, 2n-1] arrays, each row what nj_tree gives the matrix.  ValueError for what nj_tree refuses,
+        with the matrix named."""
+        dists = np.ascontiguousarray(dists, np.float64)
+        if dists.ndim != 3 or dists.shape[1] != dists.shape[2] or dists.shape[0] == 0 or dists.shape[1] == 0:
+            raise ValueError("nj_trees: the distance matrices are [count, n, n] with count >= 1 and n >= 1")
+        count, n = dists.shape[:2]
+        if n > NJ_MAX_ROWS:
+            raise ValueError(phylogeny_refusal(PHY_TOO_MANY_ROWS))
+        left = np.zeros((count, 2 * n - 1), np.int32); right = np.zeros((count, 2 * n - 1), np.int32)
+        length = np.zeros((count, 2 * n - 1), np.float64)
+        rc = _nj_trees(self._h, n, count, dists.ctypes.data, left.ctypes.data, right.ctypes.data, length.ctypes.data)
+        if rc == -1:
+            raise ValueError(_last_error().decode("latin-1"))
+        check(rc)
+        return left.astype(np.int64), right.astype(np.int64), length
+
+    def alignment_bootstrap(self, cell, use=None, model="jc", B=100, seed=12345, tree=None, trees=False):
+        """Bootstrap support of a tree of an alignment's rows (dafs_hip_alignment_bootstrap): B replicate
+        alignments drawn from the used columns with replacement, their distances under `model` and their neighbour-joining
+        trees, all on the device.  tree: (left, right) or (left, right, length) of the main tree; None: alignment_tree(cell,
+        use, model).  Returns support (int64 [2n-1]: the number of replicate trees holding the node's split, -1 for the root
+        and trivial splits); with trees=True (support, rep_left, rep_right), the replicate trees as [B, 2n-1]."""
+        if model not in NJ_MODELS:
+            raise ValueError(phylogeny_refusal(PHY_UNKNOWN_MODEL))
+        cell = _cells(cell, "alignment_bootstrap")
+        n, L = cell.shape
+        if n > NJ_MAX_ROWS:
+            raise ValueError(phylogeny_refusal(PHY_TOO_MANY_ROWS))
+        if not 1 <= int(B) <= BOOTSTRAP_MAX:
+            raise ValueError(bootstrap_refusal(BOOT_COUNT))
+        use = _byte_mask(use, L, "alignment_bootstrap", "use needs one entry per column")
+        if tree is None:
+            tree = self.alignment_tree(cell, use=use, model=model)
+        left = np.ascontiguousarray(tree[0], np.int32).reshape(-1)
+        right = np.ascontiguousarray(tree[1], np.int32).reshape(-1)
+        if n == 0 or len(left) != 2 * n - 1 or len(right) != 2 * n - 1:
+            raise ValueError("alignment_bootstrap: a tree of n rows has 2n - 1 nodes")
+        support = np.zeros(2 * n - 1, np.int32)
+        rep = [np.zeros((int(B), 2 * n - 1), np.int32) for _ in range(2)] if trees else [None, None]
+        rc = _alignment_bootstrap(self._h, n, L, cell.ctypes.data, None if use is None else use.ctypes.data, NJ_MODELS.index(model), int(B),
+                                  int(seed) & 0xFFFFFFFFFFFFFFFF, left.ctypes.data, right.ctypes.data, support.ctypes.data,
+                                  None if rep[0] is None else rep[0].ctypes.data, None if rep[1] is None else rep[1].ctypes.data)
+        if rc == -1:
+            raise ValueError(_last_error().decode("latin-1"))
+        check(rc)
+        support = support.astype(np.int64)
+        return (support, rep[0].astype(np.int64), rep[1].astype(np.int64)) if trees else support
+
+    def bootstrap_alignment(self, cell, k, use=None, seed=12345):
+        """Replicate k (0-based) behind alignment_bootstrap(cell, use, seed=seed) as cells (uint8 [n, U], U the number of used
+        columns; dafs_hip_bootstrap_alignment)."""
+        cell = _cells(cell, "bootstrap_alignment")
+        n, L = cell.shape
+        use = _byte_mask(use, L, "bootstrap_alignment", "use needs one entry per column")
+        U = L if use is None else int(use.sum())
+        out = np.zeros((n, max(U, 1)), np.uint8)
+        rc = _bootstrap_alignment(self._h, n, L, cell.ctypes.data, None if use is None else use.ctypes.data, int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                  int(k), out.ctypes.data)
+        if rc == -1:
+            raise ValueError(_last_error().decode("latin-1"))
+        check(rc)
+        return out[:, :U]
 
     def set_bp(self, rows):
         """rows: per sequence (rowptr[len+1], col, val)"""
@@ -1294,6 +1374,11 @@ def phylogeny_refusal(which):
     return _phylogeny_refusal(which).decode()
 
 
+def bootstrap_refusal(which):
+    """what both drivers say when they refuse a combination of the bootstrap options (dafs_host_bootstrap_refusal)"""
+    return _bootstrap_refusal(which).decode()
+
+
 def nj_distances(ident, aligned, model="jc"):
     """dafs_host_nj_distances: the float64 [n, n] distances of an alignment's rows from the integer
     matrices of Context.alignment_identity(matrix=True), under the model "jc" (Jukes-Cantor, quantised to 2^-20 and capped at
@@ -1313,10 +1398,47 @@ def nj_distances(ident, aligned, model="jc"):
     return dist
 
 
-def newick(names, left, right, length=None):
+def tree_support(left, right, rep_left, rep_right):
+    """dafs_host_tree_support (host code in the library): per node of the tree (left, right) the number
+    of the replicate trees (rep_left, rep_right: [B, 2n-1]) that hold the node's split, as int64 [2n-1]; -1 for the root and
+    for a split with fewer than two leaves on a side.  ValueError for a malformed tree."""
+    left = np.ascontiguousarray(left, np.int32).reshape(-1)
+    right = np.ascontiguousarray(right, np.int32).reshape(-1)
+    rep_left = np.ascontiguousarray(rep_left, np.int32)
+    rep_right = np.ascontiguousarray(rep_right, np.int32)
+    T = len(left)
+    if T % 2 != 1 or len(right) != T or rep_left.ndim != 2 or rep_left.shape[1] != T or rep_right.shape != rep_left.shape:
+        raise ValueError("tree_support: a tree of n leaves has 2n - 1 nodes and the replicates are [B, 2n - 1]")
+    support = np.zeros(T, np.int32)
+    rc = _tree_support((T + 1) // 2, left.ctypes.data, right.ctypes.data, rep_left.shape[0], rep_left.ctypes.data, rep_right.ctypes.data,
+                       support.ctypes.data)
+    if rc == -1:
+        raise ValueError(_last_error().decode("latin-1"))
+    check(rc)
+    return support.astype(np.int64)
+
+
+def support_table(names, left, right, support, replicates, seed=12345, model="jc"):
+    """dafs_host_support_table: the text of `dafs --phylogeny-support` -- "# rows n replicates B seed S model M", then per
+    non-trivial split of the tree "node support B percent size leaves", tab-separated"""
+    if model not in NJ_MODELS:
+        raise ValueError(phylogeny_refusal(PHY_UNKNOWN_MODEL))
+    names = list(names)
+    n = len(names)
+    left = np.ascontiguousarray(left, np.int32).reshape(-1)
+    right = np.ascontiguousarray(right, np.int32).reshape(-1)
+    support = np.ascontiguousarray(support, np.int32).reshape(-1)
+    if n == 0 or len(left) != 2 * n - 1 or len(right) != 2 * n - 1 or len(support) != 2 * n - 1:
+        raise ValueError("support_table: a tree of n names has 2n - 1 nodes")
+    return host_text(_support_table, n, c_strings(names), left.ctypes.data, right.ctypes.data, support.ctypes.data, int(replicates),
+                     int(seed) & 0xFFFFFFFFFFFFFFFF, NJ_MODELS.index(model))
+
+
+def newick(names, left, right, length=None, support=None, replicates=None):
     """dafs_host_newick: the tree (left, right in build_tree's layout, length per node or None for the topology alone) as one
     Newick line ending in ";\n": "(L:len,R:len)" nested with the left child first, lengths as %.9g, none on the root, names
-    quoted where they hold any of ()[]':;, or white space.  ValueError for a malformed tree."""
+    quoted where they hold any of ()[]':;, or white space.  ValueError for a malformed tree.  support (per node, -1: none)
+    and replicates: dafs_host_newick_support, the support in percent as the label of the joins."""
     names = list(names)
     n = len(names)
     left = np.ascontiguousarray(left, np.int32).reshape(-1)
@@ -1327,6 +1449,12 @@ def newick(names, left, right, length=None):
         length = np.ascontiguousarray(length, np.float64).reshape(-1)
         if len(length) != 2 * n - 1:
             raise ValueError("newick: one length per node")
+    if support is not None:
+        support = np.ascontiguousarray(support, np.int32).reshape(-1)
+        if len(support) != 2 * n - 1 or replicates is None:
+            raise ValueError("newick: one support value per node and the number of replicates")
+        return host_text(_newick_support, n, c_strings(names), left.ctypes.data, right.ctypes.data,
+                         None if length is None else length.ctypes.data, support.ctypes.data, int(replicates))
     return host_text(_newick, n, c_strings(names), left.ctypes.data, right.ctypes.data, None if length is None else length.ctypes.data)
 
 

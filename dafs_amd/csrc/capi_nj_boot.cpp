@@ -1,0 +1,373 @@
+// dafs_amd/csrc/capi_nj_boot.cpp -- dafs_hip_nj_trees (L1), dafs_hipk_nj_batch (L0), dafs_hip_alignment_bootstrap and
+// dafs_hip_bootstrap_alignment: many neighbour-joining trees in one call, and the bootstrap support of a tree from replicate
+// alignments drawn, measured and joined on the device (nj_boot.hip; the contract in DESIGN.md section 23).  The reference has
+// no counterpart.
+//
+// Host work: the checks (everything is refused before the first launch), the used columns transposed for the device, the
+// chunks of replicates under a byte budget, the entries of the fix-up list recomputed with the host's log(), the refusals a
+// launch reports in its heads, and the count of the splits (tree_support.h).  Device memory belongs to one call.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <algorithm>
+#include <new>
+#include <vector>
+
+#include "../../include/dafs_hip.h"
+#include "alistat.h"
+#include "ctx.h"
+#include "hip_util.h"
+#include "last_error.h"
+#include "nj_boot.h"
+#include "tree_support.h"
+
+using namespace dafs;
+
+namespace {
+
+struct dev_mem {  // the arrays of one call
+  void* p = nullptr;
+  ~dev_mem() { if (p) (void)hipFree(p); }
+};
+
+int refuse(const char* what) {
+  set_last_error(what);
+  return DAFS_HIP_EINVAL;
+}
+
+thread_local uint64_t g_fixups = 0;
+
+// what the heads of `count` joined matrices say; `who` names the call and `what` a matrix ("matrix", "replicate"), k0 its number
+int heads_verdict(const char* who, const char* what, uint32_t n, uint32_t k0, const std::vector<nj_head>& heads) {
+  char msg[200];
+  for (size_t k = 0; k < heads.size(); ++k) {
+    const nj_head& h = heads[k];
+    if (h.nonfinite) {
+      snprintf(msg, sizeof msg, "%s: %s %u: %u entries above the diagonal are not finite", who, what, k0 + (uint32_t)k, h.nonfinite);
+      return refuse(msg);
+    }
+    if (h.fault || h.joins != n - 1) {
+      snprintf(msg, sizeof msg, "%s: %s %u: the joins ended early", who, what, k0 + (uint32_t)k);
+      set_last_error(msg);
+      return DAFS_HIP_ELAUNCH;
+    }
+    if (h.written) {
+      snprintf(msg, sizeof msg,
+               "%s: %s %u: the joins overflowed: %u values written into the distances, the row sums or the lengths are not finite", who, what,
+               k0 + (uint32_t)k, h.written);
+      return refuse(msg);
+    }
+  }
+  return DAFS_HIP_OK;
+}
+
+// dafs_host_nj_distances' value of one pair, the same expressions in the same order
+double host_distance(int model, uint32_t mism, uint32_t comp) {
+  const double kQ = 1048576.0, kCapK = 3.0 * 1048576.0;
+  if (model == DAFS_NJ_P) return comp ? (double)mism / (double)comp : 1.0;
+  if (comp == 0 || 4 * (uint64_t)mism >= 3 * (uint64_t)comp) return 3.0;
+  const double x = 1.0 - (4.0 * (double)mism) / (3.0 * (double)comp);
+  double k = floor(-0.75 * log(x) * kQ + 0.5);
+  if (!(k < kCapK)) k = kCapK;
+  return k / kQ;
+}
+
+uint64_t host_mix(uint64_t z) {
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+
+// The matrix of replicate k on the host, from the transposed used columns: the overflow path of the fix-up list.
+void host_replicate_distances(uint32_t n, uint32_t U, const uint8_t* cells, uint64_t seed, uint32_t k, int model, double* dist) {
+  const uint64_t base = host_mix(seed + 0x9E3779B97F4A7C15ull * (uint64_t)(k + 1));
+  std::vector<uint32_t> draw(U);
+  for (uint32_t i = 0; i < U; ++i) draw[i] = (uint32_t)(((host_mix(base + i) >> 32) * (uint64_t)U) >> 32);
+  std::vector<uint8_t> rep((size_t)n * U);  // row-major
+  for (uint32_t i = 0; i < U; ++i)
+    for (uint32_t r = 0; r < n; ++r) rep[(size_t)r * U + i] = cells[(size_t)draw[i] * n + r];
+  for (uint32_t r = 0; r < n; ++r)
+    for (uint32_t s = r + 1; s < n; ++s) {
+      const uint8_t* x = &rep[(size_t)r * U];
+      const uint8_t* y = &rep[(size_t)s * U];
+      uint32_t comp = 0, ident = 0;
+      for (uint32_t i = 0; i < U; ++i) {
+        comp += x[i] <= 4 && y[i] <= 4 ? 1u : 0u;
+        ident += x[i] <= 3 && x[i] == y[i] ? 1u : 0u;
+      }
+      dist[(size_t)r * n + s] = host_distance(model, comp - ident, comp);
+    }
+}
+
+double env_double(const char* name, double fallback) {
+  if (const char* e = getenv(name)) {
+    char* end = nullptr;
+    const double v = strtod(e, &end);
+    if (end != e && v >= 0.0) return v;
+  }
+  return fallback;
+}
+
+// the checks the two alignment calls share; the used columns in ascending order into cols
+int columns_of(const char* who, uint32_t n, uint32_t len, const uint8_t* cell, const uint8_t* use, std::vector<uint32_t>& cols) {
+  char msg[160];
+  if (n == 0 || n > kNjMaxN) { snprintf(msg, sizeof msg, "%s: it takes 1 to 16384 rows", who); return refuse(msg); }
+  if (len == 0 || len > kAliMaxLen) { snprintf(msg, sizeof msg, "%s: it takes 1 to 1048576 columns", who); return refuse(msg); }
+  for (size_t at = 0; at < (size_t)n * len; ++at)
+    if (cell[at] > 5) { snprintf(msg, sizeof msg, "%s: a cell code above 5", who); return refuse(msg); }
+  for (uint32_t c = 0; c < len; ++c)
+    if (!use || use[c]) cols.push_back(c);
+  if (cols.empty()) return refuse(dafs_host_bootstrap_refusal(DAFS_BOOTSTRAP_NO_COLUMN));
+  return DAFS_HIP_OK;
+}
+
+// cells[u * n + r] = cell[r][cols[u]]
+std::vector<uint8_t> transposed(uint32_t n, uint32_t len, const uint8_t* cell, const std::vector<uint32_t>& cols) {
+  std::vector<uint8_t> out(cols.size() * (size_t)n);
+  for (size_t u = 0; u < cols.size(); ++u)
+    for (uint32_t r = 0; r < n; ++r) out[u * n + r] = cell[(size_t)r * len + cols[u]];
+  return out;
+}
+
+}  // namespace
+
+extern "C" uint64_t dafs_hip_bootstrap_fixups(void) { return g_fixups; }
+
+extern "C" size_t dafs_hipk_nj_batch_workspace(uint32_t n, uint32_t count) {
+  return n >= 2 && n <= kNjMaxN && count ? nj_batch_workspace_bytes(n, count) : 0;
+}
+
+extern "C" int dafs_hipk_nj_batch(uint32_t n, uint32_t count, const double* d_dist, void* d_workspace, int32_t* d_left, int32_t* d_right,
+                                  double* d_length, void* hip_stream) {
+  if (n < 2 || n > kNjMaxN) return refuse("nj_batch: the launch takes 2 to 16384 rows");
+  if (!count) return refuse("nj_batch: no matrix");
+  if (!d_dist || !d_workspace || !d_left || !d_right || !d_length) return refuse("nj_batch: a missing argument");
+  if ((uintptr_t)d_workspace & 255) return refuse("nj_batch: the workspace must be 256-byte aligned");
+  return nj_batch_launch(n, count, d_dist, d_workspace, d_left, d_right, d_length, n <= nj_batch_max_n(), (hipStream_t)hip_stream);
+}
+
+extern "C" int dafs_hip_nj_trees(dafs_hip_ctx* c, uint32_t n, uint32_t count, const double* dist, int32_t* left, int32_t* right,
+                                 double* length) {
+  if (!c || !dist || !left || !right || !length) return refuse("nj_trees: a missing argument");
+  if (n == 0 || n > kNjMaxN) return refuse("nj_trees: it takes 1 to 16384 rows");
+  if (!count) return refuse("nj_trees: no matrix");
+  for (uint32_t k = 0; k < count; ++k) {
+    const double* d = dist + (size_t)k * n * n;
+    for (uint32_t x = 0; x + 1 < n; ++x)
+      for (uint32_t y = x + 1; y < n; ++y)
+        if (!isfinite(d[(size_t)x * n + y])) {
+          char msg[160];
+          snprintf(msg, sizeof msg, "nj_trees: matrix %u: the entry (%u, %u) above the diagonal is not finite", k, x, y);
+          return refuse(msg);
+        }
+  }
+  if (n == 1) {  // one-leaf trees: no launch
+    for (uint32_t k = 0; k < count; ++k) {
+      left[k] = right[k] = -1;
+      length[k] = 0.0;
+    }
+    return DAFS_HIP_OK;
+  }
+  if (hip_check(hipSetDevice(c->device))) return DAFS_HIP_ENODEV;
+  const size_t T = 2 * (size_t)n - 1, all = (size_t)count * T;
+  const size_t o_len = (all * 8 + 255) & ~(size_t)255, o_idx = (all * 4 + 255) & ~(size_t)255;
+  dev_mem in, ws, out;
+  if (hip_check(hipMalloc(&in.p, (size_t)count * n * n * 8)) || hip_check(hipMalloc(&ws.p, nj_batch_workspace_bytes(n, count))) ||
+      hip_check(hipMalloc(&out.p, o_len + 2 * o_idx)))
+    return DAFS_HIP_ENOMEM;
+  hipStream_t st = c->stream;
+  double* d_length = (double*)out.p;
+  int32_t* d_left = (int32_t*)((uint8_t*)out.p + o_len);
+  int32_t* d_right = (int32_t*)((uint8_t*)out.p + o_len + o_idx);
+  std::vector<nj_head> heads(count);
+  int rc = DAFS_HIP_OK;
+  if (hip_check(hipMemcpyAsync(in.p, dist, (size_t)count * n * n * 8, hipMemcpyHostToDevice, st))) rc = DAFS_HIP_ELAUNCH;
+  if (!rc) rc = nj_batch_launch(n, count, (const double*)in.p, ws.p, d_left, d_right, d_length, n <= nj_batch_max_n(), st);
+  if (!rc && hip_check(hipMemcpyAsync(heads.data(), ws.p, (size_t)count * sizeof(nj_head), hipMemcpyDeviceToHost, st))) rc = DAFS_HIP_ELAUNCH;
+  if (hip_check(hipStreamSynchronize(st)) && !rc) rc = DAFS_HIP_ELAUNCH;  // in every case: the copies read and write the caller's memory
+  if (rc) return rc;
+  if ((rc = heads_verdict("nj_trees", "matrix", n, 0, heads))) return rc;
+  if (hip_check(hipMemcpy(length, d_length, all * 8, hipMemcpyDeviceToHost)) || hip_check(hipMemcpy(left, d_left, all * 4, hipMemcpyDeviceToHost)) ||
+      hip_check(hipMemcpy(right, d_right, all * 4, hipMemcpyDeviceToHost)))
+    return DAFS_HIP_ELAUNCH;
+  return DAFS_HIP_OK;
+}
+
+extern "C" int dafs_hip_bootstrap_alignment(dafs_hip_ctx* c, uint32_t n, uint32_t len, const uint8_t* cell, const uint8_t* use, uint64_t seed,
+                                            uint32_t k, uint8_t* out_cell) {
+  if (!c || !cell || !out_cell) return refuse("bootstrap_alignment: a missing argument");
+  if (k >= kBootMaxReplicates) return refuse("bootstrap_alignment: the replicates are numbered 0 to 65535");
+  std::vector<uint32_t> cols;
+  if (int rc = columns_of("bootstrap_alignment", n, len, cell, use, cols)) return rc;
+  if (hip_check(hipSetDevice(c->device))) return DAFS_HIP_ENODEV;
+  const uint32_t U = (uint32_t)cols.size(), words = (U + 63) / 64;
+  const std::vector<uint8_t> cells = transposed(n, len, cell, cols);
+  std::vector<uint64_t> planes((size_t)words * 4 * n);
+  dev_mem d_cells, d_planes;
+  if (hip_check(hipMalloc(&d_cells.p, cells.size())) || hip_check(hipMalloc(&d_planes.p, planes.size() * 8))) return DAFS_HIP_ENOMEM;
+  hipStream_t st = c->stream;
+  boot_args a;
+  memset(&a, 0, sizeof a);
+  a.cells = (const uint8_t*)d_cells.p;
+  a.planes = (uint64_t*)d_planes.p;
+  a.seed = seed;
+  a.n = n; a.U = U; a.words = words; a.k0 = k; a.count = 1;
+  int rc = DAFS_HIP_OK;
+  if (hip_check(hipMemcpyAsync(d_cells.p, cells.data(), cells.size(), hipMemcpyHostToDevice, st))) rc = DAFS_HIP_ELAUNCH;
+  if (!rc) rc = boot_pack(a, st);
+  if (!rc && hip_check(hipMemcpyAsync(planes.data(), d_planes.p, planes.size() * 8, hipMemcpyDeviceToHost, st))) rc = DAFS_HIP_ELAUNCH;
+  if (hip_check(hipStreamSynchronize(st)) && !rc) rc = DAFS_HIP_ELAUNCH;
+  if (rc) return rc;
+  for (uint32_t r = 0; r < n; ++r)
+    for (uint32_t i = 0; i < U; ++i) {
+      const uint64_t* w = &planes[(size_t)(i / 64) * 4 * n];
+      const uint32_t b = i % 64;
+      const uint32_t lo = (uint32_t)(w[(size_t)ALI_LO * n + r] >> b) & 1, hi = (uint32_t)(w[(size_t)ALI_HI * n + r] >> b) & 1;
+      const bool base = (w[(size_t)ALI_BASE * n + r] >> b) & 1, res = (w[(size_t)ALI_RES * n + r] >> b) & 1;
+      out_cell[(size_t)r * U + i] = (uint8_t)(base ? (lo | (hi << 1)) : res ? 4 : 5);
+    }
+  return DAFS_HIP_OK;
+}
+
+extern "C" int dafs_hip_alignment_bootstrap(dafs_hip_ctx* c, uint32_t n, uint32_t len, const uint8_t* cell, const uint8_t* use, int model, uint32_t B,
+                                            uint64_t seed, const int32_t* main_left, const int32_t* main_right, int32_t* support, int32_t* rep_left,
+                                            int32_t* rep_right) {
+  g_fixups = 0;
+  if (!c || !cell || !main_left || !main_right || !support || (rep_left == nullptr) != (rep_right == nullptr))
+    return refuse("alignment_bootstrap: a missing argument");
+  if (model != DAFS_NJ_P && model != DAFS_NJ_JC) return refuse(dafs_host_phylogeny_refusal(DAFS_PHYLOGENY_UNKNOWN_MODEL));
+  if (B == 0 || B > kBootMaxReplicates) return refuse(dafs_host_bootstrap_refusal(DAFS_BOOTSTRAP_COUNT));
+  std::vector<uint32_t> cols;
+  if (int rc = columns_of("alignment_bootstrap", n, len, cell, use, cols)) return rc;
+  if (const char* bad = tree_malformed(n, main_left, main_right)) {
+    char msg[160];
+    snprintf(msg, sizeof msg, "alignment_bootstrap: the main tree: %s", bad);
+    return refuse(msg);
+  }
+  const size_t T = 2 * (size_t)n - 1;
+  if (n <= 3) {  // no split with two leaves on either side: nothing is drawn or launched
+    for (size_t v = 0; v < T; ++v) support[v] = -1;
+    if (rep_left)
+      for (size_t v = 0; v < (size_t)B * T; ++v) rep_left[v] = rep_right[v] = -1;
+    return DAFS_HIP_OK;
+  }
+  if (hip_check(hipSetDevice(c->device))) return DAFS_HIP_ENODEV;
+  const uint32_t U = (uint32_t)cols.size(), words = (U + 63) / 64;
+  const bool batched = n <= nj_batch_max_n();
+  const double guard = env_double("DAFS_NJ_BOOT_GUARD", 1.0 / 1048576.0);
+  uint32_t fix_cap = 65536;
+  if (const char* e = getenv("DAFS_NJ_BOOT_FIXUPS")) {  // tests: a list that overflows
+    const long v = strtol(e, nullptr, 10);
+    if (v >= 1 && v <= 65536) fix_cap = (uint32_t)v;
+  }
+  // replicates per chunk under the byte budget: the planes, the matrix, the working copy and the outputs of each
+  const size_t plane_bytes = (size_t)words * 4 * n * 8, dist_bytes = (size_t)n * n * 8;
+  const size_t per = plane_bytes + dist_bytes + (batched ? nj_batch_copy_bytes(n) : 0) + T * 16 + sizeof(nj_head);
+  // 8 GiB, or half of what the device has free: at 2 048 rows a replicate takes 67 MB, and a chunk should hold a workgroup
+  // for every compute unit where the replicates allow it
+  size_t budget = (size_t)8 << 30, free_bytes = 0, total_bytes = 0;
+  if (!hip_check(hipMemGetInfo(&free_bytes, &total_bytes)) && free_bytes / 2 < budget) budget = free_bytes / 2;
+  if (const char* e = getenv("DAFS_NJ_BOOT_BYTES")) {  // tests: small chunks (the results do not depend on them)
+    const long long v = strtoll(e, nullptr, 10);
+    if (v >= 1) budget = (size_t)v;
+  }
+  const uint32_t chunk_reps = (uint32_t)std::max<size_t>(1, std::min<size_t>(std::min<size_t>(B, kBootChunkReplicates), budget / per));
+  const size_t all = (size_t)chunk_reps * T, o_len = (all * 8 + 255) & ~(size_t)255, o_idx = (all * 4 + 255) & ~(size_t)255;
+
+  std::vector<uint8_t> cells;
+  std::vector<int32_t> h_left, h_right, all_left, all_right;
+  std::vector<nj_head> heads;
+  std::vector<boot_fix> fix;
+  std::vector<double> patch, whole;
+  try {
+    cells = transposed(n, len, cell, cols);
+    h_left.resize(all);
+    h_right.resize(all);
+    if (rep_left) { all_left.resize((size_t)B * T); all_right.resize((size_t)B * T); }  // the caller's stay untouched by a refusal
+  } catch (const std::bad_alloc&) {
+    return DAFS_HIP_ENOMEM;
+  }
+  dev_mem d_cells, d_planes, d_dist, d_ws, d_out, d_fix;
+  if (hip_check(hipMalloc(&d_cells.p, cells.size())) || hip_check(hipMalloc(&d_planes.p, chunk_reps * plane_bytes)) ||
+      hip_check(hipMalloc(&d_dist.p, chunk_reps * dist_bytes)) ||
+      hip_check(hipMalloc(&d_ws.p, batched ? nj_batch_workspace_bytes(n, chunk_reps) : nj_batch_heads_bytes(chunk_reps) + nj_workspace_bytes(n))) ||
+      hip_check(hipMalloc(&d_out.p, o_len + 2 * o_idx)) || hip_check(hipMalloc(&d_fix.p, 256 + (size_t)fix_cap * sizeof(boot_fix))))
+    return DAFS_HIP_ENOMEM;
+  hipStream_t st = c->stream;
+  struct drain { hipStream_t st; ~drain() { (void)hipStreamSynchronize(st); } } wait_at_exit{st};  // queued copies use this call's vectors
+  double* d_length = (double*)d_out.p;
+  int32_t* d_left = (int32_t*)((uint8_t*)d_out.p + o_len);
+  int32_t* d_right = (int32_t*)((uint8_t*)d_out.p + o_len + o_idx);
+  if (hip_check(hipMemcpyAsync(d_cells.p, cells.data(), cells.size(), hipMemcpyHostToDevice, st))) return DAFS_HIP_ELAUNCH;
+
+  try {
+  support_counter counter(n, main_left, main_right);
+  boot_args a;
+  memset(&a, 0, sizeof a);
+  a.cells = (const uint8_t*)d_cells.p;
+  a.planes = (uint64_t*)d_planes.p;
+  a.dist = (double*)d_dist.p;
+  a.fix_count = (uint32_t*)d_fix.p;
+  a.fix = (boot_fix*)((uint8_t*)d_fix.p + 256);
+  a.seed = seed;
+  a.guard = guard;
+  a.n = n; a.U = U; a.words = words; a.chunk = std::min(words, kAliMaxChunk);
+  a.fix_cap = fix_cap;
+  a.model = model;
+  int rc;
+  for (uint32_t k0 = 0; k0 < B; k0 += chunk_reps) {
+    const uint32_t count = std::min(chunk_reps, B - k0);
+    a.k0 = k0;
+    a.count = count;
+    if (hip_check(hipMemsetAsync(a.fix_count, 0, 4, st))) return DAFS_HIP_ELAUNCH;
+    if ((rc = boot_pack(a, st)) || (rc = boot_dist(a, st))) return rc;
+    // the one wait of a chunk: the length of the fix-up list
+    uint32_t fixes = 0;
+    if (hip_check(hipMemcpyAsync(&fixes, a.fix_count, 4, hipMemcpyDeviceToHost, st)) || hip_check(hipStreamSynchronize(st))) return DAFS_HIP_ELAUNCH;
+    g_fixups += fixes;
+    if (fixes > fix_cap) {  // the list overflowed: this chunk's matrices whole, on the host
+      whole.assign((size_t)count * n * n, 0.0);
+      for (uint32_t kk = 0; kk < count; ++kk) host_replicate_distances(n, U, cells.data(), seed, k0 + kk, model, &whole[(size_t)kk * n * n]);
+      if (hip_check(hipMemcpyAsync(d_dist.p, whole.data(), whole.size() * 8, hipMemcpyHostToDevice, st))) return DAFS_HIP_ELAUNCH;
+    } else if (fixes) {
+      fix.resize(fixes);
+      if (hip_check(hipMemcpy(fix.data(), a.fix, (size_t)fixes * sizeof(boot_fix), hipMemcpyDeviceToHost))) return DAFS_HIP_ELAUNCH;
+      if (fixes <= 64) {  // the usual few: one word each
+        patch.resize(fixes);
+        for (uint32_t f = 0; f < fixes; ++f) {
+          patch[f] = host_distance(model, fix[f].mism, fix[f].comp);
+          if (hip_check(hipMemcpyAsync(a.dist + ((size_t)fix[f].k * n + fix[f].r) * n + fix[f].s, &patch[f], 8, hipMemcpyHostToDevice, st)))
+            return DAFS_HIP_ELAUNCH;
+        }
+      } else {  // many: the matrices make the round trip once
+        whole.resize((size_t)count * n * n);
+        if (hip_check(hipMemcpy(whole.data(), d_dist.p, whole.size() * 8, hipMemcpyDeviceToHost))) return DAFS_HIP_ELAUNCH;
+        for (const boot_fix& f : fix) whole[((size_t)f.k * n + f.r) * n + f.s] = host_distance(model, f.mism, f.comp);
+        if (hip_check(hipMemcpyAsync(d_dist.p, whole.data(), whole.size() * 8, hipMemcpyHostToDevice, st))) return DAFS_HIP_ELAUNCH;
+      }
+    }
+    if ((rc = nj_batch_launch(n, count, a.dist, d_ws.p, d_left, d_right, d_length, batched, st))) return rc;
+    heads.resize(count);
+    if (hip_check(hipMemcpyAsync(heads.data(), d_ws.p, (size_t)count * sizeof(nj_head), hipMemcpyDeviceToHost, st)) ||
+        hip_check(hipMemcpyAsync(h_left.data(), d_left, (size_t)count * T * 4, hipMemcpyDeviceToHost, st)) ||
+        hip_check(hipMemcpyAsync(h_right.data(), d_right, (size_t)count * T * 4, hipMemcpyDeviceToHost, st)) || hip_check(hipStreamSynchronize(st)))
+      return DAFS_HIP_ELAUNCH;
+    if ((rc = heads_verdict("alignment_bootstrap", "replicate", n, k0, heads))) return rc;
+    for (uint32_t kk = 0; kk < count; ++kk) counter.add(&h_left[kk * T], &h_right[kk * T]);
+    if (rep_left) {
+      memcpy(&all_left[(size_t)k0 * T], h_left.data(), (size_t)count * T * 4);
+      memcpy(&all_right[(size_t)k0 * T], h_right.data(), (size_t)count * T * 4);
+    }
+  }
+  counter.result(support);
+  if (rep_left) {
+    memcpy(rep_left, all_left.data(), all_left.size() * 4);
+    memcpy(rep_right, all_right.data(), all_right.size() * 4);
+  }
+  } catch (const std::bad_alloc&) {
+    return DAFS_HIP_ENOMEM;
+  }
+  return DAFS_HIP_OK;
+}

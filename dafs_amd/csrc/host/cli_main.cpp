@@ -94,6 +94,10 @@ struct Options {
   std::string phylogeny;        // --phylogeny OUT: the neighbour-joining tree of every printed alignment's rows, in Newick
   int phylogeny_model = DAFS_NJ_JC;  // --phylogeny-model jc|p
   bool phylogeny_model_given = false;
+  uint32_t phylogeny_bootstrap = 0;  // --phylogeny-bootstrap B: replicates behind the support values of the tree (0: none)
+  uint64_t phylogeny_seed = 12345;   // --phylogeny-seed S
+  std::string phylogeny_support;     // --phylogeny-support OUT: the table of the splits
+  bool phylogeny_bootstrap_given = false, phylogeny_seed_given = false;
   bool cov_tree_nj = false;     // --cov-tree nj: the tree null evolves along the neighbour-joining tree
   bool cov_tree_given = false;
   bool seed_nearest = false;    // --seed-nearest: two more columns in --seed-scores
@@ -187,6 +191,14 @@ const char* kHelp =
     "                        joins run on the device.  At most 16384 rows.  Not with --pairwise or --seed-each\n"
     "      --phylogeny-model M  With --phylogeny: jc (default): Jukes-Cantor distances, capped at 3.0; p: the share of aligned\n"
     "                        columns that differ\n"
+    "      --phylogeny-bootstrap B  With --phylogeny: B (1 to 65536) bootstrap replicates of every alignment, their columns drawn\n"
+    "                        with replacement, their trees joined on the device; every join of the Newick line whose split has\n"
+    "                        two rows or more on both sides then carries the share of the replicate trees that hold the split,\n"
+    "                        in percent, as its label: \"(A:0.1,B:0.2)87:0.05\"\n"
+    "      --phylogeny-seed S  Seed of the replicates (default: 12345); needs --phylogeny-bootstrap\n"
+    "      --phylogeny-support OUT  With --phylogeny-bootstrap: also write the table of the splits to OUT, laid out as --phylogeny\n"
+    "                        lays out its lines: \"# rows n replicates B seed S model M\", then per split, tab-separated:\n"
+    "                        node support B percent size leaves (the rows on the side without the first row)\n"
     "      --identity OUT    Also write how similar the rows of every printed alignment are to OUT: the line\n"
     "                        \"# rows n columns len average A min B max C\" (pairwise identity over all row pairs), then one\n"
     "                        tab-separated line per row: r name residues weight nearest nearest_name pid (1-based rows; residues:\n"
@@ -204,7 +216,7 @@ const char* kHelp =
     "      --describe ALIGNMENT  No FILE: read a finished alignment (Stockholm or aligned FASTA, as --seed reads it, with its\n"
     "                        SS_cons if it has one) and write --identity / --identity-matrix and, if given, --covariation for\n"
     "                        it (--identity: at most 32768 rows); nothing is aligned and nothing is printed.  Only --device,\n"
-    "                        --phylogeny, --phylogeny-model and the --cov-* and --compare* options go with it\n"
+    "                        the --phylogeny*, --cov-* and --compare* options go with it\n"
     "      --compare OUT     With --compare-ref REF: also write to OUT how far every printed alignment agrees with the\n"
     "                        reference alignment REF of the same sequences (read as --seed reads a seed, with its SS_cons if it\n"
     "                        has one).  The rows compared are the names in both.  Lines \"# rows ..\", \"# pairs shared S ref P\n"
@@ -281,6 +293,7 @@ Options parse(int argc, char** argv) {
       {"seed-each", {0, false}}, {"seed-scores", {0, true}}, {"seed-merged", {0, true}}, {"seed-structure", {0, false}},
       {"covariation", {0, true}}, {"cov-shuffles", {0, true}}, {"cov-seed", {0, true}}, {"cov-null", {0, true}}, {"identity", {0, true}},
       {"phylogeny", {0, true}}, {"phylogeny-model", {0, true}}, {"cov-tree", {0, true}},
+      {"phylogeny-bootstrap", {0, true}}, {"phylogeny-seed", {0, true}}, {"phylogeny-support", {0, true}},
       {"identity-matrix", {0, true}}, {"seed-nearest", {0, false}}, {"seed-nr", {0, true}}, {"describe", {0, true}},
       {"compare", {0, true}}, {"compare-ref", {0, true}}, {"compare-columns", {0, true}}, {"compare-matrix", {0, true}},
       {"cluster", {0, true}}, {"cluster-count", {0, true}}, {"cluster-min-size", {0, true}}, {"cluster-table", {0, true}},
@@ -388,6 +401,29 @@ Options parse(int argc, char** argv) {
       else throw std::string(dafs_host_phylogeny_refusal(DAFS_PHYLOGENY_UNKNOWN_MODEL));
       o.phylogeny_model_given = true;
     }
+    else if (name == "phylogeny-support") {
+      if (value.empty()) throw std::string("--phylogeny-support needs a file name");
+      o.phylogeny_support = value;
+    }
+    else if (name == "phylogeny-bootstrap" || name == "phylogeny-seed") {
+      size_t used = 0;
+      unsigned long long v = 0;
+      try {
+        if (value.empty() || value[0] < '0' || value[0] > '9') throw std::invalid_argument(value);
+        v = std::stoull(value, &used, 10);
+      } catch (const std::exception&) {
+        used = 0;
+      }
+      if (name == "phylogeny-seed") {
+        if (used == 0 || used != value.size()) throw std::string("--phylogeny-seed needs a non-negative integer");
+        o.phylogeny_seed = v;
+        o.phylogeny_seed_given = true;
+      } else {
+        if (used == 0 || used != value.size() || v < 1 || v > 65536) throw std::string(dafs_host_bootstrap_refusal(DAFS_BOOTSTRAP_COUNT));
+        o.phylogeny_bootstrap = (uint32_t)v;
+        o.phylogeny_bootstrap_given = true;
+      }
+    }
     else if (name == "cov-tree") {
       if (value == "average") o.cov_tree_nj = false;
       else if (value == "nj") o.cov_tree_nj = true;
@@ -485,6 +521,10 @@ Options parse(int argc, char** argv) {
   if (o.cov_null_given && o.covariation.empty()) throw std::string("--cov-null needs --covariation");
   if (o.cov_tree_given && (!o.cov_null_given || o.cov_null != DAFS_COV_NULL_TREE)) throw std::string(dafs_host_phylogeny_refusal(DAFS_PHYLOGENY_COV_TREE_NEEDS_NULL));
   if (o.phylogeny_model_given && o.phylogeny.empty()) throw std::string(dafs_host_phylogeny_refusal(DAFS_PHYLOGENY_MODEL_NEEDS_TREE));
+  if ((o.phylogeny_bootstrap_given || o.phylogeny_seed_given || !o.phylogeny_support.empty()) && o.phylogeny.empty())
+    throw std::string(dafs_host_bootstrap_refusal(DAFS_BOOTSTRAP_NEEDS_TREE));
+  if ((o.phylogeny_seed_given || !o.phylogeny_support.empty()) && !o.phylogeny_bootstrap_given)
+    throw std::string(dafs_host_bootstrap_refusal(DAFS_BOOTSTRAP_NEEDS_REPLICATES));
   if (o.pairwise && !o.phylogeny.empty()) throw std::string(dafs_host_phylogeny_refusal(DAFS_PHYLOGENY_NO_PAIRWISE));
   if (o.seed_each && !o.phylogeny.empty()) throw std::string(dafs_host_phylogeny_refusal(DAFS_PHYLOGENY_NO_SEED_EACH));
   if (o.pairwise && (!o.covariation.empty() || o.cov_shuffles_given || o.cov_seed_given))
@@ -492,7 +532,7 @@ Options parse(int argc, char** argv) {
   if (!o.describe.empty()) {  // a finished alignment: nothing that aligns, and no FILE
     for (const std::string& g : given)
       if (g != "describe" && g != "identity" && g != "identity-matrix" && g != "covariation" && g != "cov-shuffles" && g != "cov-seed" && g != "cov-null" && g != "device" &&
-          g != "phylogeny" && g != "phylogeny-model" && g != "cov-tree" &&
+          g.compare(0, 9, "phylogeny") != 0 && g != "cov-tree" &&
           g.compare(0, 7, "compare") != 0)
         throw "--describe reads a finished alignment: --" + g + " cannot be combined with --describe";
     if (!o.inputs.empty()) throw std::string("--describe takes no FILE: the alignment is its argument");
@@ -912,14 +952,29 @@ void nj_of(dafs_hip_ctx* ctx, int model, const std::vector<std::string>& rows, s
   check_text(dafs_hip_nj_tree(ctx, n, dist.data(), left.data(), right.data(), length.data()));
 }
 
-// --phylogeny: the Newick line of one printed alignment; names: the rows' Stockholm names
-void phylogeny_of(dafs_hip_ctx* ctx, const Options& o, const std::vector<std::string>& names, const std::vector<std::string>& rows, std::string& newick) {
+// --phylogeny: the Newick line of one printed alignment; names: the rows' Stockholm names.  With --phylogeny-bootstrap the joins
+// carry their support and table is the text of --phylogeny-support.
+void phylogeny_of(dafs_hip_ctx* ctx, const Options& o, const std::vector<std::string>& names, const std::vector<std::string>& rows, std::string& newick,
+                  std::string& table) {
   std::vector<int32_t> left, right;
   std::vector<double> length;
   nj_of(ctx, o.phylogeny_model, rows, left, right, length);
+  const uint32_t n = (uint32_t)rows.size();
   char* text = nullptr;
-  check_text(dafs_host_newick((uint32_t)rows.size(), c_strs(names).data(), left.data(), right.data(), length.data(), &text));
+  if (!o.phylogeny_bootstrap) {
+    check_text(dafs_host_newick(n, c_strs(names).data(), left.data(), right.data(), length.data(), &text));
+    newick = take(text);
+    return;
+  }
+  const std::vector<uint8_t> cell = cells_of(rows);
+  std::vector<int32_t> support(2 * (size_t)n - 1, -1);
+  check_text(dafs_hip_alignment_bootstrap(ctx, n, (uint32_t)rows[0].size(), cell.data(), nullptr, o.phylogeny_model, o.phylogeny_bootstrap,
+                                          o.phylogeny_seed, left.data(), right.data(), support.data(), nullptr, nullptr));
+  check_text(dafs_host_newick_support(n, c_strs(names).data(), left.data(), right.data(), length.data(), support.data(), o.phylogeny_bootstrap, &text));
   newick = take(text);
+  check_text(dafs_host_support_table(n, c_strs(names).data(), left.data(), right.data(), support.data(), o.phylogeny_bootstrap, o.phylogeny_seed,
+                                     o.phylogeny_model, &text));
+  table = take(text);
 }
 
 // --covariation: the statistics of one printed alignment (dafs_hip_alignment_covariation_null).
@@ -1138,7 +1193,7 @@ struct FamilyOut {
   unsigned wanted = 0;
   std::ostringstream text;
   std::ostream* os = &text;  // &text, or &std::cout
-  std::string sto, cov, phy;
+  std::string sto, cov, phy, phy_table;
   IdentityText idt;
   CompareText cmp;
   FamilyOut() {}
@@ -1160,14 +1215,15 @@ unsigned wanted_of(const Options& o) {
 // The files of the wanted side outputs, one block or table per record in order; headers: a line "==> header <==" before every
 // record's table (the Stockholm blocks carry none)
 void write_outputs(const Options& o, unsigned wanted, const std::vector<FamilyOut>& recs, const std::vector<std::string>* headers) {
-  std::vector<std::string> sto, cov, phy;
+  std::vector<std::string> sto, cov, phy, phy_table;
   std::vector<IdentityText> idt;
   std::vector<CompareText> cmp;
-  for (const FamilyOut& r : recs) { sto.push_back(r.sto); cov.push_back(r.cov); idt.push_back(r.idt); cmp.push_back(r.cmp); phy.push_back(r.phy); }
+  for (const FamilyOut& r : recs) { sto.push_back(r.sto); cov.push_back(r.cov); idt.push_back(r.idt); cmp.push_back(r.cmp); phy.push_back(r.phy); phy_table.push_back(r.phy_table); }
   if (wanted & kSto) write_tables("--stockholm", o.stockholm, sto, nullptr);
   if (wanted & kCov) write_tables("--covariation", o.covariation, cov, headers);
   if (wanted & kIdt) write_identity(o, idt, headers);
   if (wanted & kPhy) write_tables("--phylogeny", o.phylogeny, phy, headers);
+  if ((wanted & kPhy) && !o.phylogeny_support.empty()) write_tables("--phylogeny-support", o.phylogeny_support, phy_table, headers);
   if (wanted & kCmp) write_compare(o, cmp, headers);
 }
 
@@ -1703,7 +1759,7 @@ void finish_alignment(dafs_hip_ctx* ctx, const Options& o, const std::vector<Fas
     for (const auto& row : root) names.push_back(all_names[row.first - first]);
   }
   if (out.wanted & kIdt) identity_of(ctx, names, rows, !o.identity_matrix.empty(), out.idt);
-  if (out.wanted & kPhy) phylogeny_of(ctx, o, names, rows, out.phy);
+  if (out.wanted & kPhy) phylogeny_of(ctx, o, names, rows, out.phy, out.phy_table);
   if (out.wanted & kCmp) compare_of(ctx, o, names, rows, &ss_final, nullptr, nullptr, out.cmp);
   if (out.wanted & kSto) {
     char* text = nullptr;
@@ -2393,9 +2449,10 @@ int run_describe(const Options& o) {
     write_identity(o, {idt}, nullptr);
   }
   if (!o.phylogeny.empty()) {
-    std::string newick;
-    phylogeny_of(ctx, o, names, rows, newick);
+    std::string newick, table;
+    phylogeny_of(ctx, o, names, rows, newick, table);
     write_text("--phylogeny", o.phylogeny, newick);
+    if (!o.phylogeny_support.empty()) write_text("--phylogeny-support", o.phylogeny_support, table);
   }
   if (!o.covariation.empty()) {
     std::string cov, chars;

@@ -1,5 +1,5 @@
 // dafs_amd/csrc/host_text.cpp -- the text formats and memory estimates of both drivers as C entry points (include/dafs_hip.h,
-// "host text"): the Stockholm block, the --covariation, --pairwise-scores, --identity and --compare tables, the Newick line of --phylogeny,
+// "host text"): the Stockholm block, the --covariation, --pairwise-scores, --identity and --compare tables, the Newick line of --phylogeny, its bootstrap support and the table of --phylogeny-support,
 // the seed reader of --seed, the estimates and the greedy chunking.  The C++ command line calls them directly and the Python driver through capi.py, so every byte and
 // every formula is defined here once.  Host logic only: nothing here includes HIP or touches a device.
 #include <algorithm>
@@ -18,6 +18,7 @@
 
 #include "../../include/dafs_hip.h"
 #include "last_error.h"
+#include "tree_support.h"
 
 namespace {
 
@@ -483,12 +484,43 @@ extern "C" const char* dafs_host_phylogeny_refusal(int which) {
   }
 }
 
+extern "C" const char* dafs_host_bootstrap_refusal(int which) {
+  switch (which) {
+    case DAFS_BOOTSTRAP_NEEDS_TREE:
+      return "--phylogeny-bootstrap, --phylogeny-seed and --phylogeny-support (phylogeny_bootstrap) need --phylogeny (phylogeny)";
+    case DAFS_BOOTSTRAP_COUNT:
+      return "the number of bootstrap replicates (--phylogeny-bootstrap, phylogeny_bootstrap) is 1 to 65536";
+    case DAFS_BOOTSTRAP_NEEDS_REPLICATES:
+      return "--phylogeny-seed and --phylogeny-support need bootstrap replicates (--phylogeny-bootstrap)";
+    case DAFS_BOOTSTRAP_NO_COLUMN:
+      return "bootstrap replicates (--phylogeny-bootstrap, phylogeny_bootstrap) need one used column at least";
+    default:
+      return "";
+  }
+}
+
+namespace {
+
+// (200 s + B) / (2 B) in integers: the share of the replicates in percent, halves rounded up
+uint32_t support_percent(int32_t s, uint32_t B) { return (uint32_t)((200ull * (uint64_t)s + B) / (2ull * B)); }
+
+// The two children of the root carry one split.  It is shown once: on the left child if that is a join, otherwise on the
+// right child.  The node that stays silent, or UINT32_MAX.
+uint32_t silent_root_child(uint32_t n, const int32_t* left, const int32_t* right) {
+  if (n < 2) return UINT32_MAX;
+  const uint32_t root = 2 * n - 2;
+  return (uint32_t)left[root] >= n ? (uint32_t)right[root] : UINT32_MAX;
+}
+
+}  // namespace
+
 // The Newick line of a tree in the arrays of dafs_host_build_tree.  The walk keeps its own stack of
-// (node, next step), so a chain of any depth uses none of the call stack.
-extern "C" int dafs_host_newick(uint32_t n, const char* const* names, const int32_t* left, const int32_t* right, const double* length,
-                                char** out) {
+// (node, next step), so a chain of any depth uses none of the call stack.  support (or null) labels the joins (section 23).
+static int newick_text(uint32_t n, const char* const* names, const int32_t* left, const int32_t* right, const double* length,
+                       const int32_t* support, uint32_t B, char** out) {
   return text_out(out, [&]() {
     if (!n || !left || !right) throw kBadArgument;
+    if (support && !B) throw std::string("newick: support values need the number of replicates");
     if (n > 0x7FFFFFFFu / 2) throw std::string("newick: too many leaves");
     const std::vector<std::string> nm = strings(n, names);
     const uint32_t T = 2 * n - 1;
@@ -515,6 +547,7 @@ extern "C" int dafs_host_newick(uint32_t n, const char* const* names, const int3
       for (char ch : s) { q += ch; if (ch == '\'') q += '\''; }
       return q + "'";
     };
+    const uint32_t silent = support ? silent_root_child(n, left, right) : UINT32_MAX;
     std::string text;
     std::vector<std::pair<uint32_t, uint8_t> > stack;
     stack.push_back(std::make_pair(T - 1, (uint8_t)0));
@@ -533,11 +566,93 @@ extern "C" int dafs_host_newick(uint32_t n, const char* const* names, const int3
         continue;
       } else {
         text += ")";
+        if (support && node != T - 1 && node != silent && support[node] >= 0) {
+          if ((uint32_t)support[node] > B) throw std::string("newick: a support value above the number of replicates");
+          text += std::to_string(support_percent(support[node], B));
+        }
       }
       if (length && node != T - 1) text += ":" + fmt9d(length[node]);
       stack.pop_back();
     }
     return text + ";\n";
+  });
+}
+
+extern "C" int dafs_host_newick(uint32_t n, const char* const* names, const int32_t* left, const int32_t* right, const double* length,
+                                char** out) {
+  return newick_text(n, names, left, right, length, nullptr, 0, out);
+}
+
+extern "C" int dafs_host_newick_support(uint32_t n, const char* const* names, const int32_t* left, const int32_t* right, const double* length,
+                                        const int32_t* support, uint32_t B, char** out) {
+  if (!support) {
+    dafs::set_last_error(kBadArgument.c_str());
+    return DAFS_HIP_EINVAL;
+  }
+  return newick_text(n, names, left, right, length, support, B, out);
+}
+
+// Bootstrap support: per node of the main tree the number of replicate trees that hold its split
+extern "C" int dafs_host_tree_support(uint32_t n, const int32_t* left, const int32_t* right, uint32_t B, const int32_t* rep_left,
+                                      const int32_t* rep_right, int32_t* support) {
+  auto refuse = [](const std::string& why) { dafs::set_last_error(why.c_str()); return DAFS_HIP_EINVAL; };
+  if (!n || !left || !right || !support || (B && (!rep_left || !rep_right))) return refuse("tree support: invalid argument");
+  if (const char* bad = dafs::tree_malformed(n, left, right)) return refuse(std::string("tree support: ") + bad);
+  const size_t T = 2 * (size_t)n - 1;
+  for (uint32_t k = 0; k < B; ++k)
+    if (const char* bad = dafs::tree_malformed(n, rep_left + k * T, rep_right + k * T))
+      return refuse("tree support: replicate " + std::to_string(k) + ": " + bad);
+  try {
+    dafs::support_counter counter(n, left, right);
+    for (uint32_t k = 0; k < B; ++k) counter.add(rep_left + k * T, rep_right + k * T);
+    counter.result(support);
+  } catch (const std::bad_alloc&) {
+    return DAFS_HIP_ENOMEM;
+  }
+  return DAFS_HIP_OK;
+}
+
+// The table of --phylogeny-support: one line per non-trivial split of the main tree, the leaves on the side without the first row
+extern "C" int dafs_host_support_table(uint32_t n, const char* const* names, const int32_t* left, const int32_t* right, const int32_t* support,
+                                       uint32_t B, uint64_t seed, int model, char** out) {
+  return text_out(out, [&]() {
+    if (!n || !left || !right || !support || !B) throw kBadArgument;
+    if (model != DAFS_NJ_P && model != DAFS_NJ_JC) throw std::string(dafs_host_phylogeny_refusal(DAFS_PHYLOGENY_UNKNOWN_MODEL));
+    const std::vector<std::string> nm = strings(n, names);
+    if (const char* bad = dafs::tree_malformed(n, left, right)) throw std::string("support table: ") + bad;
+    const uint32_t T = 2 * n - 1, silent = silent_root_child(n, left, right);
+    std::ostringstream os;
+    os << "# rows " << n << " replicates " << B << " seed " << seed << " model " << (model == DAFS_NJ_JC ? "jc" : "p") << "\n";
+    // below[v]: the leaves below v in ascending order, kept only while a node above still needs them
+    std::vector<std::vector<uint32_t> > below(T);
+    for (uint32_t v = 0; v < T; ++v) {
+      if (v < n) {
+        below[v].assign(1, v);
+      } else {
+        std::vector<uint32_t>& a = below[(uint32_t)left[v]];
+        std::vector<uint32_t>& b = below[(uint32_t)right[v]];
+        below[v].resize(a.size() + b.size());
+        std::merge(a.begin(), a.end(), b.begin(), b.end(), below[v].begin());
+        std::vector<uint32_t>().swap(a);
+        std::vector<uint32_t>().swap(b);
+      }
+      if (v + 1 == T || v == silent || support[v] < 0) continue;
+      if ((uint32_t)support[v] > B) throw std::string("support table: a support value above the number of replicates");
+      std::vector<uint32_t> side;
+      if (below[v][0] != 0) {
+        side = below[v];
+      } else {  // the rest of the leaves
+        size_t at = 0;
+        for (uint32_t leaf = 0; leaf < n; ++leaf) {
+          if (at < below[v].size() && below[v][at] == leaf) ++at;
+          else side.push_back(leaf);
+        }
+      }
+      os << v + 1 << "\t" << support[v] << "\t" << B << "\t" << support_percent(support[v], B) << "\t" << side.size() << "\t";
+      for (size_t k = 0; k < side.size(); ++k) os << (k ? "," : "") << nm[side[k]];
+      os << "\n";
+    }
+    return os.str();
   });
 }
 

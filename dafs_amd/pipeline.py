@@ -54,7 +54,8 @@ class Result:
 def run(names, seqs, ctx=None, bp=None, w=4.0, eta0=0.5, t_max=600, w_pct_a=0.25, w_pct_s=0.25, th_a=0.01,
         th_s=0.2, th_s1=None, align_model=capi.ALIGN_PROBCONS, force_iters=0, timers=None, level_sync=False, slice_iters=None,
         mp=None, skip_uncoupled_folds=True, shard=None, round_us=None, w_pct_f=0.0, bp_update=False, bp_update1=False,
-        reliability=False, covariation=False, row_structures=False, identity=False, compare=None, phylogeny=False):
+        reliability=False, covariation=False, row_structures=False, identity=False, compare=None, phylogeny=False,
+        phylogeny_bootstrap=0, phylogeny_seed=12345):
     """The whole run.  bp: per-sequence (rowptr, col, val) base-pairing rows (--fold-aux); None
     computes them with the device fold model.  mp: supplied matching probabilities (--align-aux), see Context.set_mp.
     shard: (torch.distributed module, torch device) of an initialised process group -- phase 1 (folds, pair posteriors,
@@ -65,9 +66,11 @@ def run(names, seqs, ctx=None, bp=None, w=4.0, eta0=0.5, t_max=600, w_pct_a=0.25
     row on its own (see _phase2_forest).  identity: the result also gets .identity (see alignment_identity) and its
     Stockholm block the `#=GS <name> WT` lines.  compare: (ref_names, ref_rows[, ref_ss]), a reference alignment of the same
     sequences as stockholm.read_seed_structure returns it: the result also gets .compare (see compare).  phylogeny: "jc" or
-    "p": the result also gets .phylogeny (see alignment_phylogeny), the neighbour-joining tree of the printed rows."""
+    "p": the result also gets .phylogeny (see alignment_phylogeny), the neighbour-joining tree of the printed rows;
+    phylogeny_bootstrap: that many bootstrap replicates drawn from phylogeny_seed: .phylogeny also gets
+    .support, .replicates, .seed and .support_table, and .newick carries the support in percent as the labels of the joins."""
     import time
-    phylogeny_model(phylogeny)
+    phylogeny = phylogeny_option(phylogeny, phylogeny_bootstrap, phylogeny_seed)
     # combinations this driver does not implement are refused, not ignored (the command line, cli_main.cpp, has no level
     # batches: its --bp-update runs in the resident-node rounds and in the refinement's solve_node)
     if level_sync and bp_update:
@@ -342,7 +345,34 @@ def _covariation(ctx, rows, ss, covariation):
 
 
 class Phylogeny:
-    """Result of alignment_phylogeny: .model, .left, .right, .length (Context.alignment_tree) and .newick (capi.newick)"""
+    """Result of alignment_phylogeny: .model, .left, .right, .length (Context.alignment_tree) and .newick (capi.newick); with
+    bootstrap replicates also .support (Context.alignment_bootstrap), .replicates, .seed and .support_table
+    (capi.support_table), and .newick then carries the support in percent as the labels of the joins"""
+
+
+class PhylogenyOption(str):
+    """The model name of the phylogeny option as it travels through the drivers, with the bootstrap options beside it:
+    .bootstrap (replicates, 0 for none) and .seed"""
+    bootstrap, seed = 0, 12345
+
+
+def phylogeny_option(phylogeny, bootstrap=0, seed=12345):
+    """phylogeny_model with the bootstrap options of run / run_batch / add / describe / cluster checked and attached
+    (DESIGN.md section 23): None for off, otherwise a PhylogenyOption.  Replicates without a tree are refused with the
+    library's text, as the command line refuses --phylogeny-bootstrap without --phylogeny."""
+    model = phylogeny_model(phylogeny)
+    if isinstance(model, PhylogenyOption):
+        return model
+    bootstrap = int(bootstrap or 0)
+    if model is None:
+        if bootstrap:
+            raise ValueError(capi.bootstrap_refusal(capi.BOOT_NEEDS_TREE))
+        return None
+    if not 0 <= bootstrap <= capi.BOOTSTRAP_MAX:
+        raise ValueError(capi.bootstrap_refusal(capi.BOOT_COUNT))
+    out = PhylogenyOption(model)
+    out.bootstrap, out.seed = bootstrap, int(seed) & 0xFFFFFFFFFFFFFFFF
+    return out
 
 
 def phylogeny_model(phylogeny):
@@ -352,6 +382,8 @@ def phylogeny_model(phylogeny):
         return None
     if phylogeny is True:
         return "jc"
+    if isinstance(phylogeny, PhylogenyOption):
+        return phylogeny
     if phylogeny not in capi.NJ_MODELS:
         raise ValueError(capi.phylogeny_refusal(capi.PHY_UNKNOWN_MODEL))
     return phylogeny
@@ -359,11 +391,19 @@ def phylogeny_model(phylogeny):
 
 def alignment_phylogeny(ctx, row_names, rows, model="jc"):
     """The neighbour-joining tree of an alignment's rows (`dafs --phylogeny OUT`): Context.alignment_tree
-    over all columns under `model`, and the Newick line with the rows' Stockholm names, byte for byte the command line's."""
+    over all columns under `model`, and the Newick line with the rows' Stockholm names, byte for byte the command line's.
+    A model that is a PhylogenyOption with replicates (`--phylogeny-bootstrap B`) adds their support."""
     out = Phylogeny()
-    out.model = model
-    out.left, out.right, out.length = ctx.alignment_tree(rows, model=model)
-    out.newick = capi.newick(row_names, out.left, out.right, out.length)
+    out.model = str(model)
+    out.left, out.right, out.length = ctx.alignment_tree(rows, model=out.model)
+    replicates = getattr(model, "bootstrap", 0)
+    if not replicates:
+        out.newick = capi.newick(row_names, out.left, out.right, out.length)
+        return out
+    out.replicates, out.seed = replicates, model.seed
+    out.support = ctx.alignment_bootstrap(rows, model=out.model, B=replicates, seed=model.seed, tree=(out.left, out.right))
+    out.newick = capi.newick(row_names, out.left, out.right, out.length, support=out.support, replicates=replicates)
+    out.support_table = capi.support_table(row_names, out.left, out.right, out.support, replicates, model.seed, out.model)
     return out
 
 
@@ -428,14 +468,15 @@ def identity_matrix_tsv(row_names, identity):
     return capi.host_text(capi._identity_matrix_table, n, capi.c_strings(row_names), *[a.ctypes.data for a in arrs])
 
 
-def describe(names, rows, ss=None, ctx=None, identity=True, covariation=False, compare=None, pp=None, phylogeny=False):
+def describe(names, rows, ss=None, ctx=None, identity=True, covariation=False, compare=None, pp=None, phylogeny=False,
+             phylogeny_bootstrap=0, phylogeny_seed=12345):
     """The alignment-only statistics of a finished alignment (`dafs --describe ALIGNMENT`): nothing is
     aligned.  names / rows / ss: as stockholm.read_seed_structure returns them (ss None: no structure).  Returns a Result with
     .rows, .row_names (stockholm.names), .ss and, as asked, .identity (alignment_identity over all columns) and .covariation
     (as run's).  compare (as run's): .compare, this alignment against the reference; pp: its PP rows (stockholm.read_seed_pp)
-    for the comparison's PP part.  phylogeny (as run's): .phylogeny."""
+    for the comparison's PP part.  phylogeny, phylogeny_bootstrap, phylogeny_seed (as run's): .phylogeny."""
     covariation = cov_options(covariation)
-    phylogeny = phylogeny_model(phylogeny)
+    phylogeny = phylogeny_option(phylogeny, phylogeny_bootstrap, phylogeny_seed)
     names, rows = stockholm.clean_seed(names, rows)
     res = Result()
     res.rows, res.row_names = rows, stockholm.names(names)
@@ -611,7 +652,7 @@ def _printed_support(sup, sidx):
 def add(seed_names, seed_rows, names, seqs, ctx=None, w=4.0, eta0=0.5, t_max=600, w_pct_a=0.25, w_pct_s=0.25, th_a=0.01,
         th_s=0.2, th_s1=None, align_model=capi.ALIGN_PROBCONS, force_iters=0, slice_iters=None, skip_uncoupled_folds=True,
         round_us=None, w_pct_f=0.0, bp_update1=False, reliability=False, covariation=False, row_structures=False, seed_ss=None,
-        identity=False, compare=None, phylogeny=False):
+        identity=False, compare=None, phylogeny=False, phylogeny_bootstrap=0, phylogeny_seed=12345):
     """Add new sequences to a fixed seed alignment without changing its columns (`dafs --seed`).
     seed_names / seed_rows: the seed's rows (letters and '.' / '-' gaps; stockholm.read_seed reads a file), checked and
     without their all-gap columns (stockholm.clean_seed).  names / seqs: the new sequences.  The options are run()'s.
@@ -633,7 +674,7 @@ def add(seed_names, seed_rows, names, seqs, ctx=None, w=4.0, eta0=0.5, t_max=600
     canonical, half and expected of Context.structure_support."""
     import time
     covariation = cov_options(covariation)
-    phylogeny_model(phylogeny)
+    phylogeny = phylogeny_option(phylogeny, phylogeny_bootstrap, phylogeny_seed)
     seed_names, seed_rows = stockholm.clean_seed(seed_names, seed_rows)
     names, seqs = list(names), list(seqs)
     if not seqs or len(names) != len(seqs):
@@ -739,7 +780,7 @@ def run_batch(families, ctx=None, max_bytes=None, **kw):
     if unknown:
         raise TypeError("pipeline.run_batch: unknown options %s" % sorted(unknown))
     opts.update(kw)
-    phylogeny_model(opts["phylogeny"])
+    opts["phylogeny"] = phylogeny_option(opts["phylogeny"], opts["phylogeny_bootstrap"], opts["phylogeny_seed"])
     families = [(list(nm), list(sq)) for nm, sq in families]
     for nm, sq in families:
         if not sq or len(nm) != len(sq):
@@ -878,6 +919,8 @@ def pairwise(names, seqs, pairs=None, ctx=None, max_bytes=None, **opts):
         raise ValueError(capi.alistat_refusal(capi.NO_PAIRWISE))
     if opts.get("phylogeny"):
         raise ValueError(capi.phylogeny_refusal(capi.PHY_NO_PAIRWISE))
+    if opts.get("phylogeny_bootstrap"):
+        raise ValueError(capi.bootstrap_refusal(capi.BOOT_NEEDS_TREE))
     if opts.get("compare") is not None:
         raise ValueError(capi.compare_refusal(capi.CMP_NO_PAIRWISE))
     if opts.get("level_sync") and opts.get("bp_update"):
@@ -1094,6 +1137,8 @@ def add_each(seed_names, seed_rows, names, seqs, ctx=None, max_bytes=None, merge
     o.update(opts)
     if o["phylogeny"]:
         raise ValueError(capi.phylogeny_refusal(capi.PHY_NO_SEED_EACH))
+    if o.get("phylogeny_bootstrap"):
+        raise ValueError(capi.bootstrap_refusal(capi.BOOT_NEEDS_TREE))
     covariation = cov_options(o["covariation"])
     seed_names, seed_rows = stockholm.clean_seed(seed_names, seed_rows)
     names, seqs = list(names), list(seqs)
@@ -1327,7 +1372,7 @@ def cluster(names, seqs, threshold=None, count=None, min_size=1, ctx=None, max_b
     if unknown:
         raise TypeError("pipeline.cluster: unknown options %s" % sorted(unknown))
     cov_options(opts.get("covariation"))
-    phylogeny_model(opts.get("phylogeny"))
+    phylogeny_option(opts.get("phylogeny"), opts.get("phylogeny_bootstrap", 0), opts.get("phylogeny_seed", 12345))
     names, seqs = list(names), list(seqs)
     n = len(seqs)
     if n == 0 or len(names) != n or any(len(s) == 0 for s in seqs):

@@ -351,6 +351,69 @@ enum {
   DAFS_PHYLOGENY_UNKNOWN_COV_TREE      /* a tree that is neither average nor nj */
 };
 const char* dafs_host_phylogeny_refusal(int which);
+/* What both drivers say when they refuse a combination of the bootstrap options.  The texts have a
+ * function of their own: dafs_host_phylogeny_refusal answers "" to every number above its seven, and keeps doing so. */
+enum {
+  DAFS_BOOTSTRAP_NEEDS_TREE = 0,      /* a bootstrap option without --phylogeny */
+  DAFS_BOOTSTRAP_COUNT,               /* a number of replicates outside 1 .. 65 536 */
+  DAFS_BOOTSTRAP_NEEDS_REPLICATES,    /* the seed or the support table without replicates */
+  DAFS_BOOTSTRAP_NO_COLUMN            /* replicates of an alignment without a used column */
+};
+const char* dafs_host_bootstrap_refusal(int which);
+
+/* Bootstrap support of a neighbour-joining tree (Felsenstein's bootstrap; no counterpart in the reference; the contract, to the
+ * bit; tests/bootstrap_ref.py restates it).
+ *
+ * dafs_hip_nj_trees: `count` neighbour-joining trees in one call.  dist: host matrices [count][n][n], each read and joined as
+ * dafs_hip_nj_tree reads and joins its one; left/right/length: [count][2n-1].  Up to 2 048 rows all joins of a matrix run in one
+ * workgroup and all matrices in one launch (k_nj_batch); above that, or when DAFS_NJ_BATCH_MAX_N (tests only; 0: never) lowers the
+ * limit, the matrices go one by one through the kernels of dafs_hip_nj_tree.  Both forms give identical arrays.  The refusals
+ * of dafs_hip_nj_tree, with the matrix named; count = 0 is refused too.
+ * L0 dafs_hipk_nj_batch: device matrices, the caller's workspace of dafs_hipk_nj_batch_workspace(n, count) bytes (256-byte
+ * aligned; 0 for n < 2, n above 16 384 or count = 0) and device outputs, on hip_stream without allocation or wait.  The
+ * workspace begins with `count` heads { uint32 nonfinite, written, joins, fault } as in dafs_hipk_nj. */
+int dafs_hip_nj_trees(dafs_hip_ctx* ctx, uint32_t n, uint32_t count, const double* dist, int32_t* left, int32_t* right, double* length);
+size_t dafs_hipk_nj_batch_workspace(uint32_t n, uint32_t count);
+int dafs_hipk_nj_batch(uint32_t n, uint32_t count, const double* d_dist, void* d_workspace, int32_t* d_left, int32_t* d_right,
+                       double* d_length, void* hip_stream);
+/* dafs_hip_alignment_bootstrap: B replicate alignments of the used columns of cell[n][len] (codes of dafs_hip_alignment_identity;
+ * use: len bytes or NULL), drawn with replacement: with U used columns cols[0..U) ascending, mix and GOLDEN of section 13 and
+ * base_k = mix(seed + GOLDEN * (k + 1)), column i of replicate k is cols[((mix(base_k + i) >> 32) * U) >> 32].  Every replicate
+ * gets the distances of dafs_host_nj_distances under `model` (DAFS_NJ_JC / DAFS_NJ_P) from its own counts and the tree of
+ * dafs_hip_nj_tree.  support[2n-1]: per node of the main tree (main_left, main_right: the tree of the same rows, any well-formed
+ * tree) the number of replicate trees that hold the node's split (the leaves below it, or the rest if leaf 0 is among them); -1
+ * for the root and for a split with fewer than two leaves on a side; the two children of the root get the same count.
+ * rep_left / rep_right (both or neither; [B][2n-1]) receive the replicate trees.  n <= 3: all -1, nothing drawn or launched,
+ * the replicate arrays are filled with -1.  A row that a replicate leaves without a residue is not refused: its pairs have
+ * comp = 0.  DAFS_HIP_EINVAL with a message, outputs untouched, context usable: a null pointer, n = 0 or above 16 384, len = 0,
+ * B = 0 or above 65 536, no used column, a code above 5, an unknown model, a malformed main tree (the checks of
+ * dafs_host_cluster_cut), and the refusals of dafs_hip_nj_tree for any replicate.  Tests-only switches that change no result:
+ * DAFS_NJ_BOOT_BYTES (device bytes per chunk of replicates), DAFS_NJ_BOOT_GUARD (how near an integer the quantised Jukes-Cantor
+ * value may come before the host recomputes the entry; 0.5: every entry), DAFS_NJ_BOOT_FIXUPS (the capacity of that list),
+ * DAFS_NJ_BATCH_MAX_N. */
+int dafs_hip_alignment_bootstrap(dafs_hip_ctx* ctx, uint32_t n, uint32_t len, const uint8_t* cell, const uint8_t* use, int model, uint32_t B,
+                                 uint64_t seed, const int32_t* main_left, const int32_t* main_right, int32_t* support, int32_t* rep_left,
+                                 int32_t* rep_right);
+/* Replicate k of the call above as cells: out_cell[n][U], packed and read back through the device path of the call. */
+int dafs_hip_bootstrap_alignment(dafs_hip_ctx* ctx, uint32_t n, uint32_t len, const uint8_t* cell, const uint8_t* use, uint64_t seed, uint32_t k,
+                                 uint8_t* out_cell);
+/* How many fix-up entries the last dafs_hip_alignment_bootstrap of this thread sent through the host (measurement aid). */
+uint64_t dafs_hip_bootstrap_fixups(void);
+/* Host-side helper (no device work): support[2n-1] of a main tree against B replicate trees ([B][2n-1] each) as defined above,
+ * exact, without recursion.  DAFS_HIP_EINVAL: a null pointer, n = 0, a malformed tree (the replicate is named). */
+int dafs_host_tree_support(uint32_t n, const int32_t* left, const int32_t* right, uint32_t B, const int32_t* rep_left,
+                           const int32_t* rep_right, int32_t* support);
+/* Host-side helper: dafs_host_newick's line with the support in percent, (200 * support + B) / (2 * B) in integer division, as
+ * the label of every join whose support is >= 0: "(A:0.1,B:0.2)87:0.05".  The split of the root's two children is labelled
+ * once: on the left child if that is a join, otherwise on the right child.  With every support at -1 the text is
+ * dafs_host_newick's.  DAFS_HIP_EINVAL also for B = 0 and a support above B. */
+int dafs_host_newick_support(uint32_t n, const char* const* names, const int32_t* left, const int32_t* right, const double* length,
+                             const int32_t* support, uint32_t B, char** out);
+/* Host-side helper: the table of --phylogeny-support.  "# rows n replicates B seed S model M", then per non-trivial split of the
+ * main tree, in node order and once per split (the rule above), tab-separated: node (1-based) support B percent size leaves;
+ * size and leaves (names, comma-separated, in row order) are those of the side without the first row. */
+int dafs_host_support_table(uint32_t n, const char* const* names, const int32_t* left, const int32_t* right, const int32_t* support,
+                            uint32_t B, uint64_t seed, int model, char** out);
 
 /* Host-side helper (no device work): the merge of `dafs --seed` and pipeline.add, k new sequences
  * placed into a fixed seed alignment of C columns.  lens: k sequence lengths; z: their column maps from the k nodes (leaf j
