@@ -14,24 +14,12 @@
 
 #include "../../include/dafs_hip.h"
 #include "alistat.h"
-#include "ctx.h"
-#include "hip_util.h"
-#include "last_error.h"
+#include "call_frame.h"
+#include "call_host.h"
 
 using namespace dafs;
 
 namespace {
-
-struct dev_mem {  // the matrices of one call: not kept in the context
-  void* p = nullptr;
-  ~dev_mem() { if (p) (void)hipFree(p); }
-};
-
-// Every return waits for the stream: the queued copies read and write the caller's buffers and this call's vectors.
-struct stream_drain {
-  hipStream_t st;
-  ~stream_drain() { (void)hipStreamSynchronize(st); }
-};
 
 // the checks both calls share: sizes, codes, and a residue in the used columns of every row
 bool cells_ok(uint32_t n, uint32_t len, const uint8_t* cell, const uint8_t* use) {
@@ -61,74 +49,61 @@ extern "C" int dafs_hip_alignment_identity(dafs_hip_ctx* c, uint32_t n, uint32_t
   if (hip_check(hipSetDevice(c->device))) return DAFS_HIP_ENODEV;
 
   const uint32_t words = (len + 63) / 64, redw = (n + 31) / 32;
-  uint32_t chunk = std::min(words, kAliMaxChunk);
-  if (const char* e = getenv("DAFS_ALI_CHUNK_WORDS")) {  // tests: a smaller LDS stage (the results do not depend on it)
-    const long v = strtol(e, nullptr, 10);
-    if (v >= 1 && v <= (long)kAliMaxChunk) chunk = std::min(words, (uint32_t)v);
-  }
+  // tests: a smaller LDS stage (the results do not depend on it)
+  const uint32_t chunk = std::min(words, (uint32_t)env_uint("DAFS_ALI_CHUNK_WORDS", 1, kAliMaxChunk, kAliMaxChunk));
+  // tests: several launches per pass at small sizes
+  const uint32_t band_blocks = (uint32_t)env_uint("DAFS_ALI_BAND_BLOCKS", 1, kAliBandBlocks, kAliBandBlocks);
 
-  uint32_t band_blocks = kAliBandBlocks;
-  if (const char* e = getenv("DAFS_ALI_BAND_BLOCKS")) {  // tests: several launches per pass at small sizes
-    const long v = strtol(e, nullptr, 10);
-    if (v >= 1 && v <= (long)kAliBandBlocks) band_blocks = (uint32_t)v;
-  }
-
-  // device workspace, carved from c->work
-  size_t used = 0;
-  auto take = [&](size_t bytes) { const size_t at = used; used += (bytes + 255) & ~(size_t)255; return at; };
-  const size_t o_cell = take((size_t)n * len), o_use = take(use ? len : 0), o_cand = take(cand ? n : 0);
-  const size_t o_planes = take((size_t)words * 4 * n * 8), o_res = take((size_t)n * 4), o_base = take((size_t)n * 4);
-  const size_t o_best = take((size_t)n * 8), o_ni = take((size_t)n * 4), o_nd = take((size_t)n * 4);
+  carve cv;  // device workspace, carved from c->work
+  const size_t o_cell = cv.take((size_t)n * len), o_use = cv.take(use ? len : 0), o_cand = cv.take(cand ? n : 0);
+  const size_t o_planes = cv.take((size_t)words * 4 * n * 8), o_res = cv.take((size_t)n * 4), o_base = cv.take((size_t)n * 4);
+  const size_t o_best = cv.take((size_t)n * 8), o_ni = cv.take((size_t)n * 4), o_nd = cv.take((size_t)n * 4);
   int rc;
-  if ((rc = c->work.reserve(used + 256))) return rc;
+  if ((rc = c->work.reserve(cv.reserve_bytes()))) return rc;
   uint8_t* w = c->work.ptr;
-  dev_mem mi, ma, mr;
-  if (n > 1) {
-    if (ident && hip_check(hipMalloc(&mi.p, (size_t)n * n * 4))) return DAFS_HIP_ENOMEM;
-    if (aligned && hip_check(hipMalloc(&ma.p, (size_t)n * n * 4))) return DAFS_HIP_ENOMEM;
-    if (want_red && hip_check(hipMalloc(&mr.p, (size_t)n * redw * 4))) return DAFS_HIP_ENOMEM;
-  }
-  hipStream_t st = c->stream;
   std::vector<uint32_t> h_res(n), h_base(n), h_ni(n, 0), h_nd(n, 0);
   std::vector<unsigned long long> h_best(n, 0);
-  stream_drain drain{st};  // declared after every host buffer the stream touches, so it waits before they go
-  auto up = [&](size_t off, const void* src, size_t bytes) { return bytes && hip_check(hipMemcpyAsync(w + off, src, bytes, hipMemcpyHostToDevice, st)); };
-  auto down = [&](void* dst, const void* src, size_t bytes) { return hip_check(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st)); };
+  call_frame f(c);
+  hipStream_t st = f.st;
+  void *mi = nullptr, *ma = nullptr, *mr = nullptr;  // the matrices of one call: not kept in the context
+  if (n > 1) {
+    if (ident && !(mi = f.alloc((size_t)n * n * 4))) return DAFS_HIP_ENOMEM;
+    if (aligned && !(ma = f.alloc((size_t)n * n * 4))) return DAFS_HIP_ENOMEM;
+    if (want_red && !(mr = f.alloc((size_t)n * redw * 4))) return DAFS_HIP_ENOMEM;
+  }
 
   ali_args a;
   memset(&a, 0, sizeof a);
   a.planes = (const uint64_t*)(w + o_planes);
   a.res = (const uint32_t*)(w + o_res);
   a.cand = cand ? w + o_cand : nullptr;
-  a.ident = (uint32_t*)mi.p;
-  a.aligned = (uint32_t*)ma.p;
+  a.ident = (uint32_t*)mi;
+  a.aligned = (uint32_t*)ma;
   a.best = (unsigned long long*)(w + o_best);
-  a.red = (uint32_t*)mr.p;
+  a.red = (uint32_t*)mr;
   a.threshold = nr_threshold;
   a.n = n; a.words = words; a.chunk = chunk; a.redw = redw; a.band_blocks = band_blocks;
 
-  if (up(o_cell, cell, (size_t)n * len) || up(o_use, use, use ? len : 0) || up(o_cand, cand, cand ? n : 0)) return DAFS_HIP_ELAUNCH;
-  if (hip_check(hipMemsetAsync(w + o_res, 0, (size_t)n * 4, st)) || hip_check(hipMemsetAsync(w + o_base, 0, (size_t)n * 4, st)) ||
-      hip_check(hipMemsetAsync(w + o_best, 0, (size_t)n * 8, st)))
-    return DAFS_HIP_ELAUNCH;
+  if (f.up(w + o_cell, cell, (size_t)n * len) || f.up(w + o_use, use, use ? len : 0) || f.up(w + o_cand, cand, cand ? n : 0)) return DAFS_HIP_ELAUNCH;
+  if (f.fill(w + o_res, 0, (size_t)n * 4) || f.fill(w + o_base, 0, (size_t)n * 4) || f.fill(w + o_best, 0, (size_t)n * 8)) return DAFS_HIP_ELAUNCH;
   if ((rc = ali_pack(w + o_cell, use ? w + o_use : nullptr, n, len, (uint64_t*)(w + o_planes), (uint32_t*)(w + o_res), (uint32_t*)(w + o_base), st)))
     return rc;
   if (n > 1) {
-    if ((mi.p || ma.p) && (rc = ali_pairs(ALI_MATRIX, a, st))) return rc;
+    if ((mi || ma) && (rc = ali_pairs(ALI_MATRIX, a, st))) return rc;
     if (want_near) {
       if ((rc = ali_pairs(ALI_NEAREST, a, st))) return rc;
       if ((rc = ali_nearest_counts(a, (uint32_t*)(w + o_ni), (uint32_t*)(w + o_nd), st))) return rc;
-      if (down(h_best.data(), w + o_best, (size_t)n * 8) || down(h_ni.data(), w + o_ni, (size_t)n * 4) || down(h_nd.data(), w + o_nd, (size_t)n * 4))
+      if (f.down(h_best.data(), w + o_best, (size_t)n * 8) || f.down(h_ni.data(), w + o_ni, (size_t)n * 4) || f.down(h_nd.data(), w + o_nd, (size_t)n * 4))
         return DAFS_HIP_ELAUNCH;
     }
     if (want_red && (rc = ali_pairs(ALI_RED, a, st))) return rc;
   }
-  if (down(h_res.data(), w + o_res, (size_t)n * 4) || down(h_base.data(), w + o_base, (size_t)n * 4)) return DAFS_HIP_ELAUNCH;
+  if (f.down(h_res.data(), w + o_res, (size_t)n * 4) || f.down(h_base.data(), w + o_base, (size_t)n * 4)) return DAFS_HIP_ELAUNCH;
   // the large outputs go to the caller directly; their diagonal is written after the wait
-  if (mi.p && down(ident, mi.p, (size_t)n * n * 4)) return DAFS_HIP_ELAUNCH;
-  if (ma.p && down(aligned, ma.p, (size_t)n * n * 4)) return DAFS_HIP_ELAUNCH;
-  if (mr.p && down(red, mr.p, (size_t)n * redw * 4)) return DAFS_HIP_ELAUNCH;
-  if (hip_check(hipStreamSynchronize(st))) return DAFS_HIP_ELAUNCH;
+  if (mi && f.down(ident, mi, (size_t)n * n * 4)) return DAFS_HIP_ELAUNCH;
+  if (ma && f.down(aligned, ma, (size_t)n * n * 4)) return DAFS_HIP_ELAUNCH;
+  if (mr && f.down(red, mr, (size_t)n * redw * 4)) return DAFS_HIP_ELAUNCH;
+  if ((rc = f.finish())) return rc;
 
   if (res) std::copy(h_res.begin(), h_res.end(), res);
   for (uint32_t r = 0; r < n; ++r) {
@@ -150,23 +125,21 @@ extern "C" int dafs_hip_alignment_weights(dafs_hip_ctx* c, uint32_t n, uint32_t 
     return DAFS_HIP_OK;
   }
   if (hip_check(hipSetDevice(c->device))) return DAFS_HIP_ENODEV;
-  size_t used = 0;
-  auto take = [&](size_t bytes) { const size_t at = used; used += (bytes + 255) & ~(size_t)255; return at; };
-  const size_t o_cell = take((size_t)n * len), o_cell_t = take((size_t)n * len), o_use = take(use ? len : 0);
-  const size_t o_cnt = take((size_t)5 * len * 4), o_inv = take((size_t)5 * len * 8), o_u = take((size_t)n * 8);
+  carve cv;
+  const size_t o_cell = cv.take((size_t)n * len), o_cell_t = cv.take((size_t)n * len), o_use = cv.take(use ? len : 0);
+  const size_t o_cnt = cv.take((size_t)5 * len * 4), o_inv = cv.take((size_t)5 * len * 8), o_u = cv.take((size_t)n * 8);
   int rc;
-  if ((rc = c->work.reserve(used + 256))) return rc;
+  if ((rc = c->work.reserve(cv.reserve_bytes()))) return rc;
   uint8_t* w = c->work.ptr;
-  hipStream_t st = c->stream;
   std::vector<double> u(n);
-  stream_drain drain{st};
-  if (hip_check(hipMemcpyAsync(w + o_cell, cell, (size_t)n * len, hipMemcpyHostToDevice, st))) return DAFS_HIP_ELAUNCH;
-  if (use && hip_check(hipMemcpyAsync(w + o_use, use, len, hipMemcpyHostToDevice, st))) return DAFS_HIP_ELAUNCH;
+  call_frame f(c);
+  hipStream_t st = f.st;
+  if (f.up(w + o_cell, cell, (size_t)n * len) || f.up(w + o_use, use, use ? len : 0)) return DAFS_HIP_ELAUNCH;
   if ((rc = ali_transpose(w + o_cell, n, len, w + o_cell_t, st))) return rc;
   if ((rc = ali_columns(w + o_cell, n, len, (uint32_t*)(w + o_cnt), (double*)(w + o_inv), st))) return rc;
   if ((rc = ali_row_weights(w + o_cell_t, use ? w + o_use : nullptr, (const double*)(w + o_inv), n, len, (double*)(w + o_u), st))) return rc;
-  if (hip_check(hipMemcpyAsync(u.data(), w + o_u, (size_t)n * 8, hipMemcpyDeviceToHost, st))) return DAFS_HIP_ELAUNCH;
-  if (hip_check(hipStreamSynchronize(st))) return DAFS_HIP_ELAUNCH;
+  if (f.down(u.data(), w + o_u, (size_t)n * 8)) return DAFS_HIP_ELAUNCH;
+  if ((rc = f.finish())) return rc;
   double total = 0.0;
   for (uint32_t r = 0; r < n; ++r) total += u[r];
   for (uint32_t r = 0; r < n; ++r) weight[r] = (u[r] * (double)n) / total;

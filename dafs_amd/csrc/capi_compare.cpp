@@ -14,25 +14,13 @@
 #include <vector>
 
 #include "../../include/dafs_hip.h"
+#include "call_frame.h"
+#include "call_host.h"
 #include "compare.h"
-#include "ctx.h"
-#include "hip_util.h"
-#include "last_error.h"
 
 using namespace dafs;
 
 namespace {
-
-struct dev_mem {  // the large arrays of one call: not kept in the context
-  void* p = nullptr;
-  ~dev_mem() { if (p) (void)hipFree(p); }
-};
-
-// Every return waits for the stream: the queued copies read and write the caller's buffers and this call's vectors.
-struct stream_drain {
-  hipStream_t st;
-  ~stream_drain() { (void)hipStreamSynchronize(st); }
-};
 
 // ss (either form) -> the partner at the left column of a pair, DAFS_HIP_NONE elsewhere; false for a bad structure
 bool left_form(const uint32_t* ss, uint32_t len, std::vector<uint32_t>& left) {
@@ -54,16 +42,6 @@ bool left_form(const uint32_t* ss, uint32_t len, std::vector<uint32_t>& left) {
 }
 
 double quotient(uint64_t a, uint64_t b) { return b ? (double)a / (double)b : std::numeric_limits<double>::quiet_NaN(); }
-
-int refuse(const char* what) {
-  set_last_error(what);
-  return DAFS_HIP_EINVAL;
-}
-
-long env_switch(const char* name) {
-  const char* e = getenv(name);
-  return e ? strtol(e, nullptr, 10) : 0;
-}
 
 }  // namespace
 
@@ -119,42 +97,36 @@ extern "C" int dafs_hip_alignment_compare(dafs_hip_ctx* c, uint32_t n, uint32_t 
     return refuse("alignment_compare: a structure has a partner beyond its length, a column in two pairs or a one-sided right column");
   if (hip_check(hipSetDevice(c->device))) return DAFS_HIP_ENODEV;
 
-  uint32_t chunk = kCmpMaxChunk, band_blocks = kCmpBandBlocks;
-  if (const long v = env_switch("DAFS_CMP_CHUNK_COLS"))  // tests: a smaller LDS stage (the results do not depend on it)
-    if (v >= 1 && v <= (long)kCmpMaxChunk) chunk = (uint32_t)v;
-  if (const long v = env_switch("DAFS_CMP_BAND_BLOCKS"))  // tests: several launches per pass at small sizes
-    if (v >= 1 && v <= (long)kCmpBandBlocks) band_blocks = (uint32_t)v;
+  // tests: a smaller LDS stage (the results do not depend on it)
+  const uint32_t chunk = (uint32_t)env_uint("DAFS_CMP_CHUNK_COLS", 1, kCmpMaxChunk, kCmpMaxChunk);
+  // tests: several launches per pass at small sizes
+  const uint32_t band_blocks = (uint32_t)env_uint("DAFS_CMP_BAND_BLOCKS", 1, kCmpBandBlocks, kCmpBandBlocks);
 
-  // device workspace, carved from c->work; the dense cnt and the pair matrices are this call's own
-  size_t used = 0;
-  auto take = [&](size_t bytes) { const size_t at = used; used += (bytes + 255) & ~(size_t)255; return at; };
+  carve cv;  // device workspace, carved from c->work; the dense cnt and the pair matrices are this call's own
   const size_t nr = (size_t)n * len_r, nt = (size_t)n * len_t;
-  const size_t o_cell_r = take(nr), o_cell_t = take(nt), o_use_r = take(use_r ? len_r : 0), o_use_t = take(use_t ? len_t : 0);
-  const size_t o_ss_r = take(want_ss ? (size_t)len_r * 4 : 0), o_ss_t = take(want_ss ? (size_t)len_t * 4 : 0);
-  const size_t o_pp = take(o.pp_count ? nt : 0);
-  const size_t o_nres = take((size_t)n * 4), o_col_r = take(nr * 4), o_col_t = take(nt * 4), o_idx_r = take(nr * 4), o_key = take(nr * 4);
-  const size_t o_occ = take(o.pair_testp ? nt * 4 : 0);
-  const size_t o_k = take((size_t)len_r * 4), o_m = take((size_t)len_t * 4);
-  const size_t o_row = take((size_t)3 * n * 8), o_bins = take((size_t)3 * kCmpClasses * 8);
-  const size_t o_colref = take((size_t)len_r * 8), o_colshared = take((size_t)len_r * 8), o_rep = take(len_r);
-  const size_t o_ss_row = take(want_ss ? (size_t)3 * n * 8 : 0);
+  const size_t o_cell_r = cv.take(nr), o_cell_t = cv.take(nt), o_use_r = cv.take(use_r ? len_r : 0), o_use_t = cv.take(use_t ? len_t : 0);
+  const size_t o_ss_r = cv.take(want_ss ? (size_t)len_r * 4 : 0), o_ss_t = cv.take(want_ss ? (size_t)len_t * 4 : 0);
+  const size_t o_pp = cv.take(o.pp_count ? nt : 0);
+  const size_t o_nres = cv.take((size_t)n * 4), o_col_r = cv.take(nr * 4), o_col_t = cv.take(nt * 4), o_idx_r = cv.take(nr * 4);
+  const size_t o_key = cv.take(nr * 4), o_occ = cv.take(o.pair_testp ? nt * 4 : 0);
+  const size_t o_k = cv.take((size_t)len_r * 4), o_m = cv.take((size_t)len_t * 4);
+  const size_t o_row = cv.take((size_t)3 * n * 8), o_bins = cv.take((size_t)3 * kCmpClasses * 8);
+  const size_t o_colref = cv.take((size_t)len_r * 8), o_colshared = cv.take((size_t)len_r * 8), o_rep = cv.take(len_r);
+  const size_t o_ss_row = cv.take(want_ss ? (size_t)3 * n * 8 : 0);
   int rc;
-  if ((rc = c->work.reserve(used + 256))) return rc;
+  if ((rc = c->work.reserve(cv.reserve_bytes()))) return rc;
   uint8_t* w = c->work.ptr;
-  dev_mem mc, ms, mp, mt;
-  if (want_count && hip_check(hipMalloc(&mc.p, (size_t)len_r * len_t * 4))) return DAFS_HIP_ENOMEM;
-  if (want_pairs) {  // the shared pass counts refp too: its matrix is there whenever either is asked for
-    if ((o.pair_shared || o.pair_refp) && (hip_check(hipMalloc(&ms.p, (size_t)n * n * 4)) || hip_check(hipMalloc(&mp.p, (size_t)n * n * 4))))
-      return DAFS_HIP_ENOMEM;
-    if (o.pair_testp && hip_check(hipMalloc(&mt.p, (size_t)n * n * 4))) return DAFS_HIP_ENOMEM;
-  }
-  hipStream_t st = c->stream;
   std::vector<uint32_t> h_nres(n), h_k(len_r), h_m(len_t);
   std::vector<uint64_t> h_row((size_t)3 * n), h_bins(3 * kCmpClasses), h_colref(len_r), h_colshared(len_r), h_ss((size_t)3 * n);
   std::vector<uint8_t> h_rep(len_r);
-  stream_drain drain{st};  // declared after every host buffer the stream touches, so it waits before they go
-  auto up = [&](size_t off, const void* src, size_t bytes) { return bytes && hip_check(hipMemcpyAsync(w + off, src, bytes, hipMemcpyHostToDevice, st)); };
-  auto down = [&](void* dst, const void* src, size_t bytes) { return hip_check(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st)); };
+  call_frame f(c);
+  hipStream_t st = f.st;
+  void *mc = nullptr, *ms = nullptr, *mp = nullptr, *mt = nullptr;
+  if (want_count && !(mc = f.alloc((size_t)len_r * len_t * 4))) return DAFS_HIP_ENOMEM;
+  if (want_pairs) {  // the shared pass counts refp too: its matrix is there whenever either is asked for
+    if ((o.pair_shared || o.pair_refp) && (!(ms = f.alloc((size_t)n * n * 4)) || !(mp = f.alloc((size_t)n * n * 4)))) return DAFS_HIP_ENOMEM;
+    if (o.pair_testp && !(mt = f.alloc((size_t)n * n * 4))) return DAFS_HIP_ENOMEM;
+  }
 
   cmp_args a;
   memset(&a, 0, sizeof a);
@@ -174,7 +146,7 @@ extern "C" int dafs_hip_alignment_compare(dafs_hip_ctx* c, uint32_t n, uint32_t 
   a.occ_t = o.pair_testp ? (uint32_t*)(w + o_occ) : nullptr;
   a.k = (uint32_t*)(w + o_k);
   a.m = (uint32_t*)(w + o_m);
-  a.cnt = (uint32_t*)mc.p;
+  a.cnt = (uint32_t*)mc;
   a.row = (unsigned long long*)(w + o_row);
   a.bins = (unsigned long long*)(w + o_bins);
   a.colref = (unsigned long long*)(w + o_colref);
@@ -182,46 +154,44 @@ extern "C" int dafs_hip_alignment_compare(dafs_hip_ctx* c, uint32_t n, uint32_t 
   a.reproduced = w + o_rep;
   a.ss_row = want_ss ? (unsigned long long*)(w + o_ss_row) : nullptr;
 
-  if (up(o_cell_r, cell_r, nr) || up(o_cell_t, cell_t, nt) || up(o_use_r, use_r, use_r ? len_r : 0) || up(o_use_t, use_t, use_t ? len_t : 0) ||
-      up(o_pp, pp, o.pp_count ? nt : 0))
+  if (f.up(w + o_cell_r, cell_r, nr) || f.up(w + o_cell_t, cell_t, nt) || f.up(w + o_use_r, use_r, use_r ? len_r : 0) ||
+      f.up(w + o_use_t, use_t, use_t ? len_t : 0) || f.up(w + o_pp, pp, o.pp_count ? nt : 0))
     return DAFS_HIP_ELAUNCH;
-  if (want_ss && (up(o_ss_r, left_r.data(), (size_t)len_r * 4) || up(o_ss_t, left_t.data(), (size_t)len_t * 4))) return DAFS_HIP_ELAUNCH;
+  if (want_ss && (f.up(w + o_ss_r, left_r.data(), (size_t)len_r * 4) || f.up(w + o_ss_t, left_t.data(), (size_t)len_t * 4))) return DAFS_HIP_ELAUNCH;
   if ((rc = cmp_map(a, st))) return rc;
-  if (down(h_nres.data(), a.nres, (size_t)n * 4)) return DAFS_HIP_ELAUNCH;
+  if (f.down(h_nres.data(), a.nres, (size_t)n * 4)) return DAFS_HIP_ELAUNCH;
   if (want_count) {
     if ((rc = cmp_count(a, st))) return rc;
-    if (down(h_k.data(), a.k, (size_t)len_r * 4) || down(h_m.data(), a.m, (size_t)len_t * 4)) return DAFS_HIP_ELAUNCH;
+    if (f.down(h_k.data(), a.k, (size_t)len_r * 4) || f.down(h_m.data(), a.m, (size_t)len_t * 4)) return DAFS_HIP_ELAUNCH;
   }
   if (want_rows) {
     if ((rc = cmp_residue(a, st))) return rc;
-    if (down(h_row.data(), a.row, (size_t)3 * n * 8) || down(h_bins.data(), a.bins, (size_t)3 * kCmpClasses * 8)) return DAFS_HIP_ELAUNCH;
+    if (f.down(h_row.data(), a.row, (size_t)3 * n * 8) || f.down(h_bins.data(), a.bins, (size_t)3 * kCmpClasses * 8)) return DAFS_HIP_ELAUNCH;
   }
   if (want_cols) {
     if ((rc = cmp_columns(a, st))) return rc;
-    if (down(h_colref.data(), a.colref, (size_t)len_r * 8) || down(h_colshared.data(), a.colshared, (size_t)len_r * 8) ||
-        down(h_rep.data(), a.reproduced, len_r))
+    if (f.down(h_colref.data(), a.colref, (size_t)len_r * 8) || f.down(h_colshared.data(), a.colshared, (size_t)len_r * 8) ||
+        f.down(h_rep.data(), a.reproduced, len_r))
       return DAFS_HIP_ELAUNCH;
   }
   if (want_ss) {
     if ((rc = cmp_ss(a, st))) return rc;
-    if (down(h_ss.data(), a.ss_row, (size_t)3 * n * 8)) return DAFS_HIP_ELAUNCH;
+    if (f.down(h_ss.data(), a.ss_row, (size_t)3 * n * 8)) return DAFS_HIP_ELAUNCH;
   }
   if (want_pairs) {
     const size_t bytes = (size_t)n * n * 4;
-    if (ms.p) {
-      if (hip_check(hipMemsetAsync(ms.p, 0, bytes, st)) || hip_check(hipMemsetAsync(mp.p, 0, bytes, st))) return DAFS_HIP_ELAUNCH;  // the diagonal
-      if ((rc = cmp_pairs(a.key, n, len_r, chunk, band_blocks, (uint32_t*)mp.p, (uint32_t*)ms.p, st))) return rc;
+    if (ms) {
+      if (f.fill(ms, 0, bytes) || f.fill(mp, 0, bytes)) return DAFS_HIP_ELAUNCH;  // the diagonal
+      if ((rc = cmp_pairs(a.key, n, len_r, chunk, band_blocks, (uint32_t*)mp, (uint32_t*)ms, st))) return rc;
     }
-    if (mt.p) {
-      if (hip_check(hipMemsetAsync(mt.p, 0, bytes, st))) return DAFS_HIP_ELAUNCH;
-      if ((rc = cmp_pairs(a.occ_t, n, len_t, chunk, band_blocks, (uint32_t*)mt.p, nullptr, st))) return rc;
+    if (mt) {
+      if (f.fill(mt, 0, bytes)) return DAFS_HIP_ELAUNCH;
+      if ((rc = cmp_pairs(a.occ_t, n, len_t, chunk, band_blocks, (uint32_t*)mt, nullptr, st))) return rc;
     }
     // the large outputs go to the caller directly
-    if (o.pair_shared && down(o.pair_shared, ms.p, bytes)) return DAFS_HIP_ELAUNCH;
-    if (o.pair_refp && down(o.pair_refp, mp.p, bytes)) return DAFS_HIP_ELAUNCH;
-    if (o.pair_testp && down(o.pair_testp, mt.p, bytes)) return DAFS_HIP_ELAUNCH;
+    if (f.down(o.pair_shared, ms, bytes) || f.down(o.pair_refp, mp, bytes) || f.down(o.pair_testp, mt, bytes)) return DAFS_HIP_ELAUNCH;
   }
-  if (hip_check(hipStreamSynchronize(st))) return DAFS_HIP_ELAUNCH;
+  if ((rc = f.finish())) return rc;
 
   if (o.residues) std::copy(h_nres.begin(), h_nres.end(), o.residues);
   if (o.k) std::copy(h_k.begin(), h_k.end(), o.k);

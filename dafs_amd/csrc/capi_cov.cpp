@@ -16,43 +16,19 @@
 #include <vector>
 
 #include "../../include/dafs_hip.h"
+#include "call_frame.h"
+#include "call_host.h"
 #include "cov.h"
-#include "ctx.h"
-#include "hip_util.h"
-#include "last_error.h"
 
 using namespace dafs;
 
 namespace {
-
-uint64_t mix64(uint64_t z) {
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
 
 double key_to_double(unsigned long long k) {  // inverse of cov_key (cov.hip)
   const unsigned long long b = (k >> 63) ? (k & 0x7FFFFFFFFFFFFFFFull) : ~k;
   double d;
   memcpy(&d, &b, 8);
   return d;
-}
-
-struct dev_mem {  // the Gq matrix of one call: not kept in the context
-  void* p = nullptr;
-  ~dev_mem() { if (p) (void)hipFree(p); }
-};
-
-// Every return waits for the stream: the queued copies and kernels read and write the caller's buffers and this call's
-// vectors, which must not die under them when an error ends the call early.
-struct stream_drain {
-  hipStream_t st;
-  ~stream_drain() { (void)hipStreamSynchronize(st); }
-};
-
-int refuse(const char* what) {
-  set_last_error(what);
-  return DAFS_HIP_EINVAL;
 }
 
 // what the arguments say about the null, before anything is read through them
@@ -123,11 +99,7 @@ int input_check(dafs_hip_ctx* c, uint32_t n, uint32_t len, const uint8_t* code) 
 
 // DAFS_COV_TREE_LDS=0 (read per call): k_cov_evolve keeps the joins' states in global memory at every n (tests reach that
 // form at a small n)
-bool evolve_in_lds(uint32_t n) {
-  const char* e = getenv("DAFS_COV_TREE_LDS");
-  if (e && *e && strtol(e, nullptr, 10) == 0) return false;
-  return cov_evolve_fits_lds(n);
-}
+bool evolve_in_lds(uint32_t n) { return !env_off("DAFS_COV_TREE_LDS") && cov_evolve_fits_lds(n); }
 
 uint64_t null_base(uint64_t seed, uint32_t k) { return mix64(seed + 0x9E3779B97F4A7C15ull * ((uint64_t)k + 1)); }
 
@@ -156,17 +128,16 @@ extern "C" int dafs_hip_covariation_null_alignment(dafs_hip_ctx* c, uint32_t n, 
     return DAFS_HIP_OK;
   }
   const size_t cells = (size_t)n * len, T = 2 * (size_t)n - 1;
-  size_t used = 0;
-  auto take = [&](size_t bytes) { const size_t at = used; used += (bytes + 255) & ~(size_t)255; return at; };
-  const size_t o_code = take(cells), o_out = take(cells), o_node = take(by_tree ? T * len : 0), o_chg = take(by_tree ? T * len : 0);
-  const size_t o_tree = take(by_tree ? 3 * T * 4 : 0);
-  if ((rc = c->work.reserve(used + 256))) return rc;
+  carve cv;
+  const size_t o_code = cv.take(cells), o_out = cv.take(cells), o_node = cv.take(by_tree ? T * len : 0), o_chg = cv.take(by_tree ? T * len : 0);
+  const size_t o_tree = cv.take(by_tree ? 3 * T * 4 : 0);
+  if ((rc = c->work.reserve(cv.reserve_bytes()))) return rc;
   uint8_t* w = c->work.ptr;
-  hipStream_t st = c->stream;
-  stream_drain drain{st};
-  if (hip_check(hipMemcpyAsync(w + o_code, code, cells, hipMemcpyHostToDevice, st))) return DAFS_HIP_ELAUNCH;
+  call_frame f(c);
+  hipStream_t st = f.st;
+  if (f.up(w + o_code, code, cells)) return DAFS_HIP_ELAUNCH;
   if (by_tree) {
-    if (hip_check(hipMemcpyAsync(w + o_tree, tree.data(), 3 * T * 4, hipMemcpyHostToDevice, st))) return DAFS_HIP_ELAUNCH;
+    if (f.up(w + o_tree, tree.data(), 3 * T * 4)) return DAFS_HIP_ELAUNCH;
     const int32_t* d_tree = (const int32_t*)(w + o_tree);
     const cov_tree t = {d_tree, d_tree + T, d_tree + 2 * T};
     if ((rc = cov_fitch(w + o_code, t, n, len, w + o_node, w + o_chg, st))) return rc;
@@ -174,8 +145,8 @@ extern "C" int dafs_hip_covariation_null_alignment(dafs_hip_ctx* c, uint32_t n, 
   } else if ((rc = cov_shuffle(w + o_code, w + o_out, n, len, null_base(seed, k), st))) {
     return rc;
   }
-  if (hip_check(hipMemcpyAsync(out_code, w + o_out, cells, hipMemcpyDeviceToHost, st))) return DAFS_HIP_ELAUNCH;
-  return hip_check(hipStreamSynchronize(st)) ? DAFS_HIP_ELAUNCH : DAFS_HIP_OK;
+  if (f.down(out_code, w + o_out, cells)) return DAFS_HIP_ELAUNCH;
+  return f.finish();
 }
 
 extern "C" int dafs_hip_alignment_covariation_null(dafs_hip_ctx* c, uint32_t n, uint32_t len, const uint8_t* code, const uint32_t* ss,
@@ -187,15 +158,11 @@ extern "C" int dafs_hip_alignment_covariation_null(dafs_hip_ctx* c, uint32_t n, 
   if ((rc = null_args_check(null, tree_left, tree_right))) return rc;
   if ((rc = input_check(c, n, len, code))) return rc;
   std::vector<uint32_t> lefts;
-  if (ss) {  // left column -> right column, each column in at most one pair (as dafs_hip_alignment_reliability)
-    std::vector<uint8_t> used(len, 0);
-    for (uint32_t col = 0; col < len; ++col) {
-      const uint32_t p = ss[col];
-      if (p == DAFS_HIP_NONE) continue;
-      if (p <= col || p >= len || used[col] || used[p]) return DAFS_HIP_EINVAL;
-      used[col] = used[p] = 1;
-      lefts.push_back(col);
-    }
+  if (ss) {  // as dafs_hip_alignment_reliability takes it; lefts: the left columns of its pairs
+    std::vector<uint8_t> used;
+    if (!structure_ok(ss, len, used)) return DAFS_HIP_EINVAL;
+    for (uint32_t col = 0; col < len; ++col)
+      if (ss[col] != DAFS_HIP_NONE) lefts.push_back(col);
   }
   // the tree null's tree, before any output is written: the caller's is checked whenever it is there, the default one is
   // built only where the new kernels will run (n >= 2, len >= 2, a null that somebody reads)
@@ -224,36 +191,29 @@ extern "C" int dafs_hip_alignment_covariation_null(dafs_hip_ctx* c, uint32_t n, 
   std::vector<int64_t> lnq((size_t)n + 1, 0);
   for (uint32_t k = 1; k <= n; ++k) lnq[k] = (int64_t)floor(log((double)k) * 65536 + 0.5);
   const uint32_t words = (n + 31) / 32;
-  uint32_t chunk = std::min(words, kCovMaxChunk);
-  if (const char* e = getenv("DAFS_COV_CHUNK_WORDS")) {  // tests: a smaller LDS stage (the results do not depend on it)
-    const long v = strtol(e, nullptr, 10);
-    if (v >= 1 && v <= (long)kCovMaxChunk) chunk = std::min(words, (uint32_t)v);
-  }
+  // tests: a smaller LDS stage (the results do not depend on it)
+  const uint32_t chunk = std::min(words, (uint32_t)env_uint("DAFS_COV_CHUNK_WORDS", 1, kCovMaxChunk, kCovMaxChunk));
   const uint32_t ncand = len + (uint32_t)lefts.size();
   uint32_t copies = 64;
   while (copies > 1 && (size_t)copies * ncand * 8 > ((size_t)64 << 20)) copies /= 2;
 
-  // device workspace, carved from c->work
-  size_t used = 0;
-  auto take = [&](size_t bytes) { const size_t at = used; used += (bytes + 255) & ~(size_t)255; return at; };
-  const size_t o_code = take((size_t)n * len), o_shuf = take(shuffles ? (size_t)n * len : 0), o_planes = take((size_t)words * 4 * len * 4);
-  const size_t o_lnq = take(((size_t)n + 1) * 8), o_sum = take((size_t)len * 8), o_tot = take(8), o_key = take((size_t)len * 8);
-  const size_t o_best = take((size_t)len * 4), o_ss = take((size_t)len * 4), o_ps = take((size_t)len * 8), o_pr = take((size_t)len * 4 * 3);
-  const size_t o_cand = take((size_t)ncand * 8), o_tail = take(shuffles ? (size_t)copies * ncand * 8 : 0);
+  carve cv;  // device workspace, carved from c->work
+  const size_t o_code = cv.take((size_t)n * len), o_shuf = cv.take(shuffles ? (size_t)n * len : 0), o_planes = cv.take((size_t)words * 4 * len * 4);
+  const size_t o_lnq = cv.take(((size_t)n + 1) * 8), o_sum = cv.take((size_t)len * 8), o_tot = cv.take(8), o_key = cv.take((size_t)len * 8);
+  const size_t o_best = cv.take((size_t)len * 4), o_ss = cv.take((size_t)len * 4), o_ps = cv.take((size_t)len * 8);
+  const size_t o_pr = cv.take((size_t)len * 4 * 3);
+  const size_t o_cand = cv.take((size_t)ncand * 8), o_tail = cv.take(shuffles ? (size_t)copies * ncand * 8 : 0);
   const size_t T = 2 * (size_t)n - 1;  // the tree null: Fitch's scratch, the change records, left / right / parent
-  const size_t o_node = take(by_tree ? T * len : 0), o_chg = take(by_tree ? T * len : 0), o_tree = take(by_tree ? 3 * T * 4 : 0);
-  if ((rc = c->work.reserve(used + 256))) return rc;
+  const size_t o_node = cv.take(by_tree ? T * len : 0), o_chg = cv.take(by_tree ? T * len : 0), o_tree = cv.take(by_tree ? 3 * T * 4 : 0);
+  if ((rc = c->work.reserve(cv.reserve_bytes()))) return rc;
   uint8_t* w = c->work.ptr;
-  dev_mem gm;
-  if (g && hip_check(hipMalloc(&gm.p, (size_t)len * len * 8))) return DAFS_HIP_ENOMEM;
-  hipStream_t st = c->stream;
   std::vector<unsigned long long> key(len), tail(shuffles ? (size_t)copies * ncand : 0);
   std::vector<double> bs(len), ps(len, 0.0), cand;
   int64_t tot = 0;
-  stream_drain drain{st};  // declared after every host buffer the stream touches, so it waits before they go
-  auto up = [&](size_t off, const void* src, size_t bytes) { return bytes && hip_check(hipMemcpyAsync(w + off, src, bytes, hipMemcpyHostToDevice, st)); };
-  auto down = [&](void* dst, size_t off, size_t bytes) { return hip_check(hipMemcpyAsync(dst, w + off, bytes, hipMemcpyDeviceToHost, st)); };
-  auto zero = [&](size_t off, int v, size_t bytes) { return hip_check(hipMemsetAsync(w + off, v, bytes, st)); };
+  call_frame f(c);
+  hipStream_t st = f.st;
+  void* gm = nullptr;  // the Gq matrix of one call: not kept in the context
+  if (g && !(gm = f.alloc((size_t)len * len * 8))) return DAFS_HIP_ENOMEM;
 
   cov_args a;
   memset(&a, 0, sizeof a);
@@ -261,7 +221,7 @@ extern "C" int dafs_hip_alignment_covariation_null(dafs_hip_ctx* c, uint32_t n, 
   a.lnq = (const int64_t*)(w + o_lnq);
   a.col_sum = (unsigned long long*)(w + o_sum);
   a.total = (const long long*)(w + o_tot);
-  a.g = (long long*)gm.p;
+  a.g = (long long*)gm;
   a.best_key = (unsigned long long*)(w + o_key);
   a.best = (uint32_t*)(w + o_best);
   a.cand = (const double*)(w + o_cand);
@@ -276,24 +236,25 @@ extern "C" int dafs_hip_alignment_covariation_null(dafs_hip_ctx* c, uint32_t n, 
   sa.types = sa.canonical + len;
 
   // the alignment itself: column sums, total, best partners, consensus pairs
-  if (up(o_code, code, (size_t)n * len) || up(o_lnq, lnq.data(), lnq.size() * 8) || (ss && up(o_ss, ss, (size_t)len * 4))) return DAFS_HIP_ELAUNCH;
-  if (zero(o_sum, 0, (size_t)len * 8) || zero(o_key, 0, (size_t)len * 8) || zero(o_best, 0xFF, (size_t)len * 4)) return DAFS_HIP_ELAUNCH;
-  if (gm.p && hip_check(hipMemsetAsync(gm.p, 0, (size_t)len * len * 8, st))) return DAFS_HIP_ELAUNCH;
+  if (f.up(w + o_code, code, (size_t)n * len) || f.up(w + o_lnq, lnq.data(), lnq.size() * 8) || (ss && f.up(w + o_ss, ss, (size_t)len * 4)))
+    return DAFS_HIP_ELAUNCH;
+  if (f.fill(w + o_sum, 0, (size_t)len * 8) || f.fill(w + o_key, 0, (size_t)len * 8) || f.fill(w + o_best, 0xFF, (size_t)len * 4)) return DAFS_HIP_ELAUNCH;
+  if (gm && f.fill(gm, 0, (size_t)len * len * 8)) return DAFS_HIP_ELAUNCH;
   if ((rc = cov_pack(w + o_code, n, len, (uint32_t*)(w + o_planes), st))) return rc;
   if ((rc = cov_pairs(COV_SUMS, a, st))) return rc;
   if ((rc = cov_total(a.col_sum, len, (long long*)(w + o_tot), st))) return rc;
   if ((rc = cov_pairs(COV_BEST, a, st))) return rc;
   if ((rc = cov_pairs(COV_ARG, a, st))) return rc;
   if (ss && (rc = cov_ss(a, sa, st))) return rc;
-  if (down(key.data(), o_key, (size_t)len * 8) || down(&tot, o_tot, 8)) return DAFS_HIP_ELAUNCH;
-  if (ss && down(ps.data(), o_ps, (size_t)len * 8)) return DAFS_HIP_ELAUNCH;
-  if (col_sum && down(col_sum, o_sum, (size_t)len * 8)) return DAFS_HIP_ELAUNCH;
-  if (best && down(best, o_best, (size_t)len * 4)) return DAFS_HIP_ELAUNCH;
-  if (ss && pair_rows && down(pair_rows, o_pr, (size_t)len * 4)) return DAFS_HIP_ELAUNCH;
-  if (ss && pair_canonical && down(pair_canonical, o_pr + (size_t)len * 4, (size_t)len * 4)) return DAFS_HIP_ELAUNCH;
-  if (ss && pair_types && down(pair_types, o_pr + (size_t)len * 8, (size_t)len * 4)) return DAFS_HIP_ELAUNCH;
-  if (g && hip_check(hipMemcpyAsync(g, gm.p, (size_t)len * len * 8, hipMemcpyDeviceToHost, st))) return DAFS_HIP_ELAUNCH;
-  if (hip_check(hipStreamSynchronize(st))) return DAFS_HIP_ELAUNCH;
+  if (f.down(key.data(), w + o_key, (size_t)len * 8) || f.down(&tot, w + o_tot, 8)) return DAFS_HIP_ELAUNCH;
+  if (ss && f.down(ps.data(), w + o_ps, (size_t)len * 8)) return DAFS_HIP_ELAUNCH;
+  // what the caller asked for goes into its memory directly
+  if (f.down(col_sum, w + o_sum, (size_t)len * 8) || f.down(best, w + o_best, (size_t)len * 4)) return DAFS_HIP_ELAUNCH;
+  if (ss && (f.down(pair_rows, w + o_pr, (size_t)len * 4) || f.down(pair_canonical, w + o_pr + (size_t)len * 4, (size_t)len * 4) ||
+             f.down(pair_types, w + o_pr + (size_t)len * 8, (size_t)len * 4)))
+    return DAFS_HIP_ELAUNCH;
+  if (f.down(g, gm, (size_t)len * len * 8)) return DAFS_HIP_ELAUNCH;
+  if ((rc = f.finish())) return rc;
   for (uint32_t col = 0; col < len; ++col) bs[col] = key_to_double(key[col]);  // len >= 2: every column has a partner
   if (best_score) std::copy(bs.begin(), bs.end(), best_score);
   if (pair_score) std::copy(ps.begin(), ps.end(), pair_score);
@@ -305,12 +266,12 @@ extern "C" int dafs_hip_alignment_covariation_null(dafs_hip_ctx* c, uint32_t n, 
   cand = bs;
   for (uint32_t l : lefts) cand.push_back(ps[l]);
   std::sort(cand.begin(), cand.end());
-  if (up(o_cand, cand.data(), (size_t)ncand * 8) || zero(o_tail, 0, (size_t)copies * ncand * 8)) return DAFS_HIP_ELAUNCH;
+  if (f.up(w + o_cand, cand.data(), (size_t)ncand * 8) || f.fill(w + o_tail, 0, (size_t)copies * ncand * 8)) return DAFS_HIP_ELAUNCH;
   const int32_t* d_tree = (const int32_t*)(w + o_tree);
   const cov_tree t = {d_tree, d_tree + T, d_tree + 2 * T};
   const bool in_lds = by_tree && evolve_in_lds(n);
   if (by_tree) {  // once per call: the change records of every branch
-    if (up(o_tree, tree.data(), 3 * T * 4)) return DAFS_HIP_ELAUNCH;
+    if (f.up(w + o_tree, tree.data(), 3 * T * 4)) return DAFS_HIP_ELAUNCH;
     if ((rc = cov_fitch(w + o_code, t, n, len, w + o_node, w + o_chg, st))) return rc;
   }
   for (uint32_t k = 0; k < shuffles; ++k) {
@@ -319,15 +280,15 @@ extern "C" int dafs_hip_alignment_covariation_null(dafs_hip_ctx* c, uint32_t n, 
     else rc = cov_shuffle(w + o_code, w + o_shuf, n, len, base, st);
     if (rc) return rc;
     if ((rc = cov_pack(w + o_shuf, n, len, (uint32_t*)(w + o_planes), st))) return rc;
-    if (zero(o_sum, 0, (size_t)len * 8)) return DAFS_HIP_ELAUNCH;
+    if (f.fill(w + o_sum, 0, (size_t)len * 8)) return DAFS_HIP_ELAUNCH;
     cov_args b = a;
     b.g = nullptr;
     if ((rc = cov_pairs(COV_SUMS, b, st))) return rc;
     if ((rc = cov_total(b.col_sum, len, (long long*)(w + o_tot), st))) return rc;
     if ((rc = cov_pairs(COV_NULL, b, st))) return rc;
   }
-  if (down(tail.data(), o_tail, tail.size() * 8)) return DAFS_HIP_ELAUNCH;
-  if (hip_check(hipStreamSynchronize(st))) return DAFS_HIP_ELAUNCH;
+  if (f.down(tail.data(), w + o_tail, tail.size() * 8)) return DAFS_HIP_ELAUNCH;
+  if ((rc = f.finish())) return rc;
   std::vector<unsigned long long> reach(ncand + 1, 0);  // reach[i]: null scores >= cand[i]
   for (uint32_t i = ncand; i-- > 0;) {
     unsigned long long s = 0;

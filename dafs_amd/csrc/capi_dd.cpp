@@ -9,6 +9,8 @@
 #include <vector>
 
 #include "../../include/dafs_hip.h"
+#include "call_frame.h"
+#include "call_host.h"
 #include "ctx.h"
 #include "dd.h"
 #include "hip_util.h"
@@ -946,12 +948,8 @@ extern "C" int dafs_hip_consensus_structures(dafs_hip_ctx* c, uint32_t nalign, c
     const int rc = make_geom(c, n_rows[a], len[a], seq + row0[a], mask + mask0[a], g[a]);
     if (rc) return rc;
   }
-  uint64_t budget = dafs_host_structures_batch_bytes();
-  if (const char* e = getenv("DAFS_HIP_CS_BATCH_BYTES")) {  // a value that is no number is ignored
-    char* end = nullptr;
-    const unsigned long long v = strtoull(e, &end, 10);
-    if (end != e && *end == '\0' && *e >= '0' && *e <= '9') budget = v;
-  }
+  // tests: budgets that put every alignment in a chunk of its own
+  const uint64_t budget = env_uint("DAFS_HIP_CS_BATCH_BYTES", 0, UINT64_MAX, dafs_host_structures_batch_bytes());
   std::vector<uint32_t> chunk_of(nalign);
   int rc;
   if ((rc = dafs_host_pack_greedy(nalign, bytes.data(), budget, chunk_of.data()))) return rc;
@@ -963,6 +961,7 @@ extern "C" int dafs_hip_consensus_structures(dafs_hip_ctx* c, uint32_t nalign, c
   std::vector<dd_node> nodes;
   std::vector<cs_desc> descs;
   std::vector<uint8_t> head, out;
+  call_frame f(c);  // `head` and `out` are in flight when an error ends a chunk early
   for (uint32_t a0 = 0; a0 < nalign;) {
     uint32_t a1 = a0;
     while (a1 < nalign && chunk_of[a1] == chunk_of[a0] && a1 - a0 < kCsMaxLaunch) ++a1;
@@ -1053,18 +1052,17 @@ extern "C" int dafs_hip_consensus_structures(dafs_hip_ctx* c, uint32_t nalign, c
       put(f.idx, g[a].idx.data(), g[a].idx.size() * 4);
       put(f.idxoff, g[a].idxoff.data(), (size_t)f.n * 4);
     }
-    if (hip_check(hipMemcpyAsync(cv.base, head.data(), head_bytes, hipMemcpyHostToDevice, c->stream))) return DAFS_HIP_ELAUNCH;
+    if (f.up(cv.base, head.data(), head_bytes)) return DAFS_HIP_ELAUNCH;
     // (no fill of the matrices: k_node_avg writes every cell of every row of p)
     for (uint32_t k = 0; k < kCsClassCount; ++k) {
       const uint32_t n = first_of[k + 1] - first_of[k];
       if (!n) continue;
-      if ((rc = dd_avg_launch(d_nodes + first_of[k], n, len_of[k], none, bpv, 0, 0, c->stream))) break;
-      if ((rc = nussinov_batch_launch(d_descs + first_of[k], n, th, kCsClasses[k].threads, lds_of[k], c->stream))) break;
+      if ((rc = dd_avg_launch(d_nodes + first_of[k], n, len_of[k], none, bpv, 0, 0, f.st))) return rc;
+      if ((rc = nussinov_batch_launch(d_descs + first_of[k], n, th, kCsClasses[k].threads, lds_of[k], f.st))) return rc;
     }
     out.resize(out_bytes);
-    if (!rc && hip_check(hipMemcpyAsync(out.data(), cv.base + out_off, out_bytes, hipMemcpyDeviceToHost, c->stream))) rc = DAFS_HIP_ELAUNCH;
-    if (hip_check(hipStreamSynchronize(c->stream)) && !rc) rc = DAFS_HIP_ELAUNCH;  // also after a failure: `head` is in flight
-    if (rc) return rc;
+    if (f.down(out.data(), cv.base + out_off, out_bytes)) return DAFS_HIP_ELAUNCH;
+    if ((rc = f.finish())) return rc;  // per chunk: the next one rewrites `head`
     for (uint32_t j = 0; j < m; ++j) {
       const uint32_t a = a0 + order[j];
       memcpy(ss + col0[a], out.data() + (ss_off[j] - out_off), (size_t)len[a] * 4);

@@ -9,33 +9,18 @@
 #include <string.h>
 
 #include "../../include/dafs_hip.h"
-#include "ctx.h"
-#include "hip_util.h"
-#include "last_error.h"
+#include "call_frame.h"
+#include "call_host.h"
 #include "linkage.h"
 
 using namespace dafs;
 
 namespace {
 
-struct dev_mem {  // the arrays of one call
-  void* p = nullptr;
-  ~dev_mem() { if (p) (void)hipFree(p); }
-};
-
-int refuse(const char* what) {
-  set_last_error(what);
-  return DAFS_HIP_EINVAL;
-}
-
 bool known_linkage(int l) { return l == DAFS_LINKAGE_SINGLE || l == DAFS_LINKAGE_COMPLETE || l == DAFS_LINKAGE_AVERAGE; }
 
 // DAFS_HIP_LINKAGE_LDS=0: the per-row state in global memory at every n (tests reach that form at a small n)
-bool want_lds(uint32_t n) {
-  const char* e = getenv("DAFS_HIP_LINKAGE_LDS");
-  if (e && strtol(e, nullptr, 10) == 0 && *e) return false;
-  return linkage_fits_lds(n);
-}
+bool want_lds(uint32_t n) { return !env_off("DAFS_HIP_LINKAGE_LDS") && linkage_fits_lds(n); }
 
 }  // namespace
 
@@ -65,22 +50,23 @@ extern "C" int dafs_hip_linkage_tree(dafs_hip_ctx* c, int linkage, uint32_t n, c
     return DAFS_HIP_OK;
   }
   if (hip_check(hipSetDevice(c->device))) return DAFS_HIP_ENODEV;
-  const size_t T = 2 * (size_t)n - 1, o_left = (T * 4 + 255) & ~(size_t)255;
-  dev_mem in, ws, out;
-  if (sim && hip_check(hipMalloc(&in.p, (size_t)n * n * 4))) return DAFS_HIP_ENOMEM;
-  if (hip_check(hipMalloc(&ws.p, linkage_workspace_bytes(n))) || hip_check(hipMalloc(&out.p, 3 * o_left))) return DAFS_HIP_ENOMEM;
-  hipStream_t st = c->stream;
-  float* d_score = (float*)out.p;
-  int32_t* d_left = (int32_t*)((uint8_t*)out.p + o_left);
-  int32_t* d_right = (int32_t*)((uint8_t*)out.p + 2 * o_left);
-  int rc = DAFS_HIP_OK;
+  const size_t T = 2 * (size_t)n - 1;
+  carve cv;  // the three output arrays of one allocation
+  const size_t o_score = cv.take(T * 4), o_left = cv.take(T * 4), o_right = cv.take(T * 4);
   linkage_head head;
   memset(&head, 0, sizeof head);
-  if (sim && hip_check(hipMemcpyAsync(in.p, sim, (size_t)n * n * 4, hipMemcpyHostToDevice, st))) rc = DAFS_HIP_ELAUNCH;
-  if (!rc) rc = linkage_launch(linkage, n, sim ? (const float*)in.p : c->d_sim.ptr, ws.p, d_score, d_left, d_right, want_lds(n), st);
-  if (!rc && hip_check(hipMemcpyAsync(&head, ws.p, sizeof head, hipMemcpyDeviceToHost, st))) rc = DAFS_HIP_ELAUNCH;
-  if (hip_check(hipStreamSynchronize(st)) && !rc) rc = DAFS_HIP_ELAUNCH;  // in every case: the copies read and write the caller's memory
-  if (rc) return rc;
+  call_frame f(c);
+  void *in = nullptr, *ws, *out;
+  if (sim && !(in = f.alloc((size_t)n * n * 4))) return DAFS_HIP_ENOMEM;
+  if (!(ws = f.alloc(linkage_workspace_bytes(n))) || !(out = f.alloc(cv.bytes()))) return DAFS_HIP_ENOMEM;
+  float* d_score = (float*)((uint8_t*)out + o_score);
+  int32_t* d_left = (int32_t*)((uint8_t*)out + o_left);
+  int32_t* d_right = (int32_t*)((uint8_t*)out + o_right);
+  int rc;
+  if (f.up(in, sim, sim ? (size_t)n * n * 4 : 0)) return DAFS_HIP_ELAUNCH;
+  if ((rc = linkage_launch(linkage, n, sim ? (const float*)in : c->d_sim.ptr, ws, d_score, d_left, d_right, want_lds(n), f.st))) return rc;
+  if (f.down(&head, ws, sizeof head)) return DAFS_HIP_ELAUNCH;
+  if ((rc = f.finish())) return rc;
   if (head.nonfinite) {
     char msg[128];
     snprintf(msg, sizeof msg, "linkage_tree: %u entries above the diagonal are not finite", head.nonfinite);

@@ -1,6 +1,6 @@
 // dafs_amd/csrc/capi_nj.cpp -- dafs_hip_nj_tree (L1) and dafs_hipk_nj (L0): the neighbour-joining tree of a distance matrix on
-// the device (nj.hip; the contract in DESIGN.md section 22), and dafs_host_nj_distances, the distances of an alignment's rows
-// from the integer matrices of dafs_hip_alignment_identity.  The reference has no counterpart.
+// the device (nj.hip; the contract in DESIGN.md section 22).  The reference has no counterpart.  (dafs_host_nj_distances, which
+// needs no device, is in host_tree.cpp.)
 //
 // Host work: the checks, the device memory of one call (the uploaded matrix, the workspace, the three output arrays; none of
 // it is kept in the context and none of the context's stores is touched) and the refusals a launch reports in its workspace.
@@ -11,26 +11,26 @@
 #include <string.h>
 
 #include "../../include/dafs_hip.h"
-#include "ctx.h"
-#include "hip_util.h"
-#include "last_error.h"
+#include "call_frame.h"
+#include "call_host.h"
 #include "nj.h"
 
 using namespace dafs;
 
-namespace {
-
-struct dev_mem {  // the arrays of one call
-  void* p = nullptr;
-  ~dev_mem() { if (p) (void)hipFree(p); }
-};
-
-int refuse(const char* what) {
-  set_last_error(what);
-  return DAFS_HIP_EINVAL;
+// What the head words of one join launch say: the message and the code, or DAFS_HIP_OK.  `who` names the call; in a batch
+// `what` names a matrix ("matrix", "replicate") and k is its number.
+int dafs::nj_head_verdict(const char* who, const char* what, uint32_t k, uint32_t n, const nj_head& h) {
+  const bool early = h.fault || h.joins != n - 1;
+  if (!h.nonfinite && !early && !h.written) return DAFS_HIP_OK;
+  char where[64], msg[200];
+  if (what) snprintf(where, sizeof where, "%s: %s %u", who, what, k);
+  else snprintf(where, sizeof where, "%s", who);
+  if (h.nonfinite) snprintf(msg, sizeof msg, "%s: %u entries above the diagonal are not finite", where, h.nonfinite);
+  else if (early) snprintf(msg, sizeof msg, "%s: the joins ended early", where);
+  else snprintf(msg, sizeof msg, "%s: the joins overflowed: %u values written into the distances, the row sums or the lengths are not finite", where, h.written);
+  set_last_error(msg);
+  return !h.nonfinite && early ? DAFS_HIP_ELAUNCH : DAFS_HIP_EINVAL;
 }
-
-}  // namespace
 
 extern "C" size_t dafs_hipk_nj_workspace(uint32_t n) { return n && n <= kNjMaxN ? nj_workspace_bytes(n) : 0; }
 
@@ -58,68 +58,25 @@ extern "C" int dafs_hip_nj_tree(dafs_hip_ctx* c, uint32_t n, const double* dist,
     return DAFS_HIP_OK;
   }
   if (hip_check(hipSetDevice(c->device))) return DAFS_HIP_ENODEV;
-  const size_t T = 2 * (size_t)n - 1, o_len = (T * 8 + 255) & ~(size_t)255, o_idx = (T * 4 + 255) & ~(size_t)255;
-  dev_mem in, ws, out;
-  if (hip_check(hipMalloc(&in.p, (size_t)n * n * 8)) || hip_check(hipMalloc(&ws.p, nj_workspace_bytes(n))) ||
-      hip_check(hipMalloc(&out.p, o_len + 2 * o_idx)))
-    return DAFS_HIP_ENOMEM;
-  hipStream_t st = c->stream;
-  double* d_length = (double*)out.p;
-  int32_t* d_left = (int32_t*)((uint8_t*)out.p + o_len);
-  int32_t* d_right = (int32_t*)((uint8_t*)out.p + o_len + o_idx);
-  int rc = DAFS_HIP_OK;
+  const size_t T = 2 * (size_t)n - 1;
+  carve cv;  // the three output arrays of one allocation
+  const size_t o_length = cv.take(T * 8), o_left = cv.take(T * 4), o_right = cv.take(T * 4);
   nj_head head;
   memset(&head, 0, sizeof head);
-  if (hip_check(hipMemcpyAsync(in.p, dist, (size_t)n * n * 8, hipMemcpyHostToDevice, st))) rc = DAFS_HIP_ELAUNCH;
-  if (!rc) rc = nj_launch(n, (const double*)in.p, ws.p, d_left, d_right, d_length, st);
-  if (!rc && hip_check(hipMemcpyAsync(&head, ws.p, sizeof head, hipMemcpyDeviceToHost, st))) rc = DAFS_HIP_ELAUNCH;
-  if (hip_check(hipStreamSynchronize(st)) && !rc) rc = DAFS_HIP_ELAUNCH;  // in every case: the copies read and write the caller's memory
-  if (rc) return rc;
-  char msg[160];
-  if (head.nonfinite) {
-    snprintf(msg, sizeof msg, "nj_tree: %u entries above the diagonal are not finite", head.nonfinite);
-    return refuse(msg);
-  }
-  if (head.fault || head.joins != n - 1) {
-    set_last_error("nj_tree: the joins ended early");
-    return DAFS_HIP_ELAUNCH;
-  }
-  if (head.written) {
-    snprintf(msg, sizeof msg, "nj_tree: the joins overflowed: %u values written into the distances, the row sums or the lengths are not finite",
-             head.written);
-    return refuse(msg);
-  }
+  call_frame f(c);
+  void *in, *ws, *out;
+  if (!(in = f.alloc((size_t)n * n * 8)) || !(ws = f.alloc(nj_workspace_bytes(n))) || !(out = f.alloc(cv.bytes()))) return DAFS_HIP_ENOMEM;
+  double* d_length = (double*)((uint8_t*)out + o_length);
+  int32_t* d_left = (int32_t*)((uint8_t*)out + o_left);
+  int32_t* d_right = (int32_t*)((uint8_t*)out + o_right);
+  int rc;
+  if (f.up(in, dist, (size_t)n * n * 8)) return DAFS_HIP_ELAUNCH;
+  if ((rc = nj_launch(n, (const double*)in, ws, d_left, d_right, d_length, f.st))) return rc;
+  if (f.down(&head, ws, sizeof head)) return DAFS_HIP_ELAUNCH;
+  if ((rc = f.finish())) return rc;
+  if ((rc = nj_head_verdict("nj_tree", nullptr, 0, n, head))) return rc;
   if (hip_check(hipMemcpy(length, d_length, T * 8, hipMemcpyDeviceToHost)) || hip_check(hipMemcpy(left, d_left, T * 4, hipMemcpyDeviceToHost)) ||
       hip_check(hipMemcpy(right, d_right, T * 4, hipMemcpyDeviceToHost)))
     return DAFS_HIP_ELAUNCH;
-  return DAFS_HIP_OK;
-}
-
-// DESIGN.md section 22, "Distances from an alignment".  The Jukes-Cantor value is quantised to 2^-20 the way LNQ is in section
-// 13, so that an ulp of log() cannot move a bit: it would have to carry -0.75 * log(x) * 2^20 + 0.5 across an integer.
-extern "C" int dafs_host_nj_distances(uint32_t n, const uint32_t* ident, const uint32_t* aligned, int model, double* dist) {
-  if (!n || !ident || !aligned || !dist) return refuse("nj_distances: a missing argument");
-  if (model != DAFS_NJ_P && model != DAFS_NJ_JC) return refuse("nj_distances: unknown model");
-  const double kQ = 1048576.0, kCapK = 3.0 * 1048576.0;
-  for (uint32_t r = 0; r < n; ++r)
-    for (uint32_t s = 0; s < n; ++s) {
-      const size_t at = (size_t)r * n + s;
-      if (r == s) { dist[at] = 0.0; continue; }
-      const uint32_t comp = aligned[at];
-      if (ident[at] > comp) return refuse("nj_distances: more identical columns than aligned ones");
-      const uint32_t mism = comp - ident[at];
-      double d;
-      if (model == DAFS_NJ_P) {
-        d = comp ? (double)mism / (double)comp : 1.0;
-      } else if (comp == 0 || 4 * (uint64_t)mism >= 3 * (uint64_t)comp) {
-        d = 3.0;
-      } else {
-        const double x = 1.0 - (4.0 * (double)mism) / (3.0 * (double)comp);
-        double k = floor(-0.75 * log(x) * kQ + 0.5);
-        if (!(k < kCapK)) k = kCapK;
-        d = k / kQ;
-      }
-      dist[at] = d;
-    }
   return DAFS_HIP_OK;
 }

@@ -17,9 +17,8 @@
 
 #include "../../include/dafs_hip.h"
 #include "alistat.h"
-#include "ctx.h"
-#include "hip_util.h"
-#include "last_error.h"
+#include "call_frame.h"
+#include "call_host.h"
 #include "nj_boot.h"
 #include "tree_support.h"
 
@@ -27,64 +26,20 @@ using namespace dafs;
 
 namespace {
 
-struct dev_mem {  // the arrays of one call
-  void* p = nullptr;
-  ~dev_mem() { if (p) (void)hipFree(p); }
-};
-
-int refuse(const char* what) {
-  set_last_error(what);
-  return DAFS_HIP_EINVAL;
-}
-
 thread_local uint64_t g_fixups = 0;
 
-// what the heads of `count` joined matrices say; `who` names the call and `what` a matrix ("matrix", "replicate"), k0 its number
+// what the heads of the joined matrices k0, k0 + 1, ... say: the first one that has something to say
 int heads_verdict(const char* who, const char* what, uint32_t n, uint32_t k0, const std::vector<nj_head>& heads) {
-  char msg[200];
-  for (size_t k = 0; k < heads.size(); ++k) {
-    const nj_head& h = heads[k];
-    if (h.nonfinite) {
-      snprintf(msg, sizeof msg, "%s: %s %u: %u entries above the diagonal are not finite", who, what, k0 + (uint32_t)k, h.nonfinite);
-      return refuse(msg);
-    }
-    if (h.fault || h.joins != n - 1) {
-      snprintf(msg, sizeof msg, "%s: %s %u: the joins ended early", who, what, k0 + (uint32_t)k);
-      set_last_error(msg);
-      return DAFS_HIP_ELAUNCH;
-    }
-    if (h.written) {
-      snprintf(msg, sizeof msg,
-               "%s: %s %u: the joins overflowed: %u values written into the distances, the row sums or the lengths are not finite", who, what,
-               k0 + (uint32_t)k, h.written);
-      return refuse(msg);
-    }
-  }
+  for (size_t k = 0; k < heads.size(); ++k)
+    if (int rc = nj_head_verdict(who, what, k0 + (uint32_t)k, n, heads[k])) return rc;
   return DAFS_HIP_OK;
-}
-
-// dafs_host_nj_distances' value of one pair, the same expressions in the same order
-double host_distance(int model, uint32_t mism, uint32_t comp) {
-  const double kQ = 1048576.0, kCapK = 3.0 * 1048576.0;
-  if (model == DAFS_NJ_P) return comp ? (double)mism / (double)comp : 1.0;
-  if (comp == 0 || 4 * (uint64_t)mism >= 3 * (uint64_t)comp) return 3.0;
-  const double x = 1.0 - (4.0 * (double)mism) / (3.0 * (double)comp);
-  double k = floor(-0.75 * log(x) * kQ + 0.5);
-  if (!(k < kCapK)) k = kCapK;
-  return k / kQ;
-}
-
-uint64_t host_mix(uint64_t z) {
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
 }
 
 // The matrix of replicate k on the host, from the transposed used columns: the overflow path of the fix-up list.
 void host_replicate_distances(uint32_t n, uint32_t U, const uint8_t* cells, uint64_t seed, uint32_t k, int model, double* dist) {
-  const uint64_t base = host_mix(seed + 0x9E3779B97F4A7C15ull * (uint64_t)(k + 1));
+  const uint64_t base = mix64(seed + 0x9E3779B97F4A7C15ull * (uint64_t)(k + 1));
   std::vector<uint32_t> draw(U);
-  for (uint32_t i = 0; i < U; ++i) draw[i] = (uint32_t)(((host_mix(base + i) >> 32) * (uint64_t)U) >> 32);
+  for (uint32_t i = 0; i < U; ++i) draw[i] = (uint32_t)(((mix64(base + i) >> 32) * (uint64_t)U) >> 32);
   std::vector<uint8_t> rep((size_t)n * U);  // row-major
   for (uint32_t i = 0; i < U; ++i)
     for (uint32_t r = 0; r < n; ++r) rep[(size_t)r * U + i] = cells[(size_t)draw[i] * n + r];
@@ -97,17 +52,8 @@ void host_replicate_distances(uint32_t n, uint32_t U, const uint8_t* cells, uint
         comp += x[i] <= 4 && y[i] <= 4 ? 1u : 0u;
         ident += x[i] <= 3 && x[i] == y[i] ? 1u : 0u;
       }
-      dist[(size_t)r * n + s] = host_distance(model, comp - ident, comp);
+      dist[(size_t)r * n + s] = nj_pair_distance(model, comp - ident, comp);
     }
-}
-
-double env_double(const char* name, double fallback) {
-  if (const char* e = getenv(name)) {
-    char* end = nullptr;
-    const double v = strtod(e, &end);
-    if (end != e && v >= 0.0) return v;
-  }
-  return fallback;
 }
 
 // the checks the two alignment calls share; the used columns in ascending order into cols
@@ -172,22 +118,21 @@ extern "C" int dafs_hip_nj_trees(dafs_hip_ctx* c, uint32_t n, uint32_t count, co
   }
   if (hip_check(hipSetDevice(c->device))) return DAFS_HIP_ENODEV;
   const size_t T = 2 * (size_t)n - 1, all = (size_t)count * T;
-  const size_t o_len = (all * 8 + 255) & ~(size_t)255, o_idx = (all * 4 + 255) & ~(size_t)255;
-  dev_mem in, ws, out;
-  if (hip_check(hipMalloc(&in.p, (size_t)count * n * n * 8)) || hip_check(hipMalloc(&ws.p, nj_batch_workspace_bytes(n, count))) ||
-      hip_check(hipMalloc(&out.p, o_len + 2 * o_idx)))
-    return DAFS_HIP_ENOMEM;
-  hipStream_t st = c->stream;
-  double* d_length = (double*)out.p;
-  int32_t* d_left = (int32_t*)((uint8_t*)out.p + o_len);
-  int32_t* d_right = (int32_t*)((uint8_t*)out.p + o_len + o_idx);
+  carve cv;  // the three output arrays of one allocation
+  const size_t o_length = cv.take(all * 8), o_left = cv.take(all * 4), o_right = cv.take(all * 4);
   std::vector<nj_head> heads(count);
-  int rc = DAFS_HIP_OK;
-  if (hip_check(hipMemcpyAsync(in.p, dist, (size_t)count * n * n * 8, hipMemcpyHostToDevice, st))) rc = DAFS_HIP_ELAUNCH;
-  if (!rc) rc = nj_batch_launch(n, count, (const double*)in.p, ws.p, d_left, d_right, d_length, n <= nj_batch_max_n(), st);
-  if (!rc && hip_check(hipMemcpyAsync(heads.data(), ws.p, (size_t)count * sizeof(nj_head), hipMemcpyDeviceToHost, st))) rc = DAFS_HIP_ELAUNCH;
-  if (hip_check(hipStreamSynchronize(st)) && !rc) rc = DAFS_HIP_ELAUNCH;  // in every case: the copies read and write the caller's memory
-  if (rc) return rc;
+  call_frame f(c);
+  void *in, *ws, *out;
+  if (!(in = f.alloc((size_t)count * n * n * 8)) || !(ws = f.alloc(nj_batch_workspace_bytes(n, count))) || !(out = f.alloc(cv.bytes())))
+    return DAFS_HIP_ENOMEM;
+  double* d_length = (double*)((uint8_t*)out + o_length);
+  int32_t* d_left = (int32_t*)((uint8_t*)out + o_left);
+  int32_t* d_right = (int32_t*)((uint8_t*)out + o_right);
+  int rc;
+  if (f.up(in, dist, (size_t)count * n * n * 8)) return DAFS_HIP_ELAUNCH;
+  if ((rc = nj_batch_launch(n, count, (const double*)in, ws, d_left, d_right, d_length, n <= nj_batch_max_n(), f.st))) return rc;
+  if (f.down(heads.data(), ws, (size_t)count * sizeof(nj_head))) return DAFS_HIP_ELAUNCH;
+  if ((rc = f.finish())) return rc;
   if ((rc = heads_verdict("nj_trees", "matrix", n, 0, heads))) return rc;
   if (hip_check(hipMemcpy(length, d_length, all * 8, hipMemcpyDeviceToHost)) || hip_check(hipMemcpy(left, d_left, all * 4, hipMemcpyDeviceToHost)) ||
       hip_check(hipMemcpy(right, d_right, all * 4, hipMemcpyDeviceToHost)))
@@ -205,21 +150,20 @@ extern "C" int dafs_hip_bootstrap_alignment(dafs_hip_ctx* c, uint32_t n, uint32_
   const uint32_t U = (uint32_t)cols.size(), words = (U + 63) / 64;
   const std::vector<uint8_t> cells = transposed(n, len, cell, cols);
   std::vector<uint64_t> planes((size_t)words * 4 * n);
-  dev_mem d_cells, d_planes;
-  if (hip_check(hipMalloc(&d_cells.p, cells.size())) || hip_check(hipMalloc(&d_planes.p, planes.size() * 8))) return DAFS_HIP_ENOMEM;
-  hipStream_t st = c->stream;
+  call_frame f(c);
+  void *d_cells, *d_planes;
+  if (!(d_cells = f.alloc(cells.size())) || !(d_planes = f.alloc(planes.size() * 8))) return DAFS_HIP_ENOMEM;
   boot_args a;
   memset(&a, 0, sizeof a);
-  a.cells = (const uint8_t*)d_cells.p;
-  a.planes = (uint64_t*)d_planes.p;
+  a.cells = (const uint8_t*)d_cells;
+  a.planes = (uint64_t*)d_planes;
   a.seed = seed;
   a.n = n; a.U = U; a.words = words; a.k0 = k; a.count = 1;
-  int rc = DAFS_HIP_OK;
-  if (hip_check(hipMemcpyAsync(d_cells.p, cells.data(), cells.size(), hipMemcpyHostToDevice, st))) rc = DAFS_HIP_ELAUNCH;
-  if (!rc) rc = boot_pack(a, st);
-  if (!rc && hip_check(hipMemcpyAsync(planes.data(), d_planes.p, planes.size() * 8, hipMemcpyDeviceToHost, st))) rc = DAFS_HIP_ELAUNCH;
-  if (hip_check(hipStreamSynchronize(st)) && !rc) rc = DAFS_HIP_ELAUNCH;
-  if (rc) return rc;
+  int rc;
+  if (f.up(d_cells, cells.data(), cells.size())) return DAFS_HIP_ELAUNCH;
+  if ((rc = boot_pack(a, f.st))) return rc;
+  if (f.down(planes.data(), d_planes, planes.size() * 8)) return DAFS_HIP_ELAUNCH;
+  if ((rc = f.finish())) return rc;
   for (uint32_t r = 0; r < n; ++r)
     for (uint32_t i = 0; i < U; ++i) {
       const uint64_t* w = &planes[(size_t)(i / 64) * 4 * n];
@@ -257,11 +201,7 @@ extern "C" int dafs_hip_alignment_bootstrap(dafs_hip_ctx* c, uint32_t n, uint32_
   const uint32_t U = (uint32_t)cols.size(), words = (U + 63) / 64;
   const bool batched = n <= nj_batch_max_n();
   const double guard = env_double("DAFS_NJ_BOOT_GUARD", 1.0 / 1048576.0);
-  uint32_t fix_cap = 65536;
-  if (const char* e = getenv("DAFS_NJ_BOOT_FIXUPS")) {  // tests: a list that overflows
-    const long v = strtol(e, nullptr, 10);
-    if (v >= 1 && v <= 65536) fix_cap = (uint32_t)v;
-  }
+  const uint32_t fix_cap = (uint32_t)env_uint("DAFS_NJ_BOOT_FIXUPS", 1, 65536, 65536);  // tests: a list that overflows
   // replicates per chunk under the byte budget: the planes, the matrix, the working copy and the outputs of each
   const size_t plane_bytes = (size_t)words * 4 * n * 8, dist_bytes = (size_t)n * n * 8;
   const size_t per = plane_bytes + dist_bytes + (batched ? nj_batch_copy_bytes(n) : 0) + T * 16 + sizeof(nj_head);
@@ -269,12 +209,11 @@ extern "C" int dafs_hip_alignment_bootstrap(dafs_hip_ctx* c, uint32_t n, uint32_
   // for every compute unit where the replicates allow it
   size_t budget = (size_t)8 << 30, free_bytes = 0, total_bytes = 0;
   if (!hip_check(hipMemGetInfo(&free_bytes, &total_bytes)) && free_bytes / 2 < budget) budget = free_bytes / 2;
-  if (const char* e = getenv("DAFS_NJ_BOOT_BYTES")) {  // tests: small chunks (the results do not depend on them)
-    const long long v = strtoll(e, nullptr, 10);
-    if (v >= 1) budget = (size_t)v;
-  }
+  budget = (size_t)env_uint("DAFS_NJ_BOOT_BYTES", 1, SIZE_MAX, budget);  // tests: small chunks (the results do not depend on them)
   const uint32_t chunk_reps = (uint32_t)std::max<size_t>(1, std::min<size_t>(std::min<size_t>(B, kBootChunkReplicates), budget / per));
-  const size_t all = (size_t)chunk_reps * T, o_len = (all * 8 + 255) & ~(size_t)255, o_idx = (all * 4 + 255) & ~(size_t)255;
+  const size_t all = (size_t)chunk_reps * T;
+  carve cv;  // the three output arrays of one allocation
+  const size_t o_length = cv.take(all * 8), o_left = cv.take(all * 4), o_right = cv.take(all * 4);
 
   std::vector<uint8_t> cells;
   std::vector<int32_t> h_left, h_right, all_left, all_right;
@@ -289,28 +228,27 @@ extern "C" int dafs_hip_alignment_bootstrap(dafs_hip_ctx* c, uint32_t n, uint32_
   } catch (const std::bad_alloc&) {
     return DAFS_HIP_ENOMEM;
   }
-  dev_mem d_cells, d_planes, d_dist, d_ws, d_out, d_fix;
-  if (hip_check(hipMalloc(&d_cells.p, cells.size())) || hip_check(hipMalloc(&d_planes.p, chunk_reps * plane_bytes)) ||
-      hip_check(hipMalloc(&d_dist.p, chunk_reps * dist_bytes)) ||
-      hip_check(hipMalloc(&d_ws.p, batched ? nj_batch_workspace_bytes(n, chunk_reps) : nj_batch_heads_bytes(chunk_reps) + nj_workspace_bytes(n))) ||
-      hip_check(hipMalloc(&d_out.p, o_len + 2 * o_idx)) || hip_check(hipMalloc(&d_fix.p, 256 + (size_t)fix_cap * sizeof(boot_fix))))
+  call_frame f(c);  // queued copies use this call's vectors
+  hipStream_t st = f.st;
+  void *d_cells, *d_planes, *d_dist, *d_ws, *d_out, *d_fix;
+  if (!(d_cells = f.alloc(cells.size())) || !(d_planes = f.alloc(chunk_reps * plane_bytes)) || !(d_dist = f.alloc(chunk_reps * dist_bytes)) ||
+      !(d_ws = f.alloc(batched ? nj_batch_workspace_bytes(n, chunk_reps) : nj_batch_heads_bytes(chunk_reps) + nj_workspace_bytes(n))) ||
+      !(d_out = f.alloc(cv.bytes())) || !(d_fix = f.alloc(256 + (size_t)fix_cap * sizeof(boot_fix))))
     return DAFS_HIP_ENOMEM;
-  hipStream_t st = c->stream;
-  struct drain { hipStream_t st; ~drain() { (void)hipStreamSynchronize(st); } } wait_at_exit{st};  // queued copies use this call's vectors
-  double* d_length = (double*)d_out.p;
-  int32_t* d_left = (int32_t*)((uint8_t*)d_out.p + o_len);
-  int32_t* d_right = (int32_t*)((uint8_t*)d_out.p + o_len + o_idx);
-  if (hip_check(hipMemcpyAsync(d_cells.p, cells.data(), cells.size(), hipMemcpyHostToDevice, st))) return DAFS_HIP_ELAUNCH;
+  double* d_length = (double*)((uint8_t*)d_out + o_length);
+  int32_t* d_left = (int32_t*)((uint8_t*)d_out + o_left);
+  int32_t* d_right = (int32_t*)((uint8_t*)d_out + o_right);
+  if (f.up(d_cells, cells.data(), cells.size())) return DAFS_HIP_ELAUNCH;
 
   try {
   support_counter counter(n, main_left, main_right);
   boot_args a;
   memset(&a, 0, sizeof a);
-  a.cells = (const uint8_t*)d_cells.p;
-  a.planes = (uint64_t*)d_planes.p;
-  a.dist = (double*)d_dist.p;
-  a.fix_count = (uint32_t*)d_fix.p;
-  a.fix = (boot_fix*)((uint8_t*)d_fix.p + 256);
+  a.cells = (const uint8_t*)d_cells;
+  a.planes = (uint64_t*)d_planes;
+  a.dist = (double*)d_dist;
+  a.fix_count = (uint32_t*)d_fix;
+  a.fix = (boot_fix*)((uint8_t*)d_fix + 256);
   a.seed = seed;
   a.guard = guard;
   a.n = n; a.U = U; a.words = words; a.chunk = std::min(words, kAliMaxChunk);
@@ -321,38 +259,36 @@ extern "C" int dafs_hip_alignment_bootstrap(dafs_hip_ctx* c, uint32_t n, uint32_
     const uint32_t count = std::min(chunk_reps, B - k0);
     a.k0 = k0;
     a.count = count;
-    if (hip_check(hipMemsetAsync(a.fix_count, 0, 4, st))) return DAFS_HIP_ELAUNCH;
+    if (f.fill(a.fix_count, 0, 4)) return DAFS_HIP_ELAUNCH;
     if ((rc = boot_pack(a, st)) || (rc = boot_dist(a, st))) return rc;
     // the one wait of a chunk: the length of the fix-up list
     uint32_t fixes = 0;
-    if (hip_check(hipMemcpyAsync(&fixes, a.fix_count, 4, hipMemcpyDeviceToHost, st)) || hip_check(hipStreamSynchronize(st))) return DAFS_HIP_ELAUNCH;
+    if (f.down(&fixes, a.fix_count, 4) || f.finish()) return DAFS_HIP_ELAUNCH;
     g_fixups += fixes;
     if (fixes > fix_cap) {  // the list overflowed: this chunk's matrices whole, on the host
       whole.assign((size_t)count * n * n, 0.0);
       for (uint32_t kk = 0; kk < count; ++kk) host_replicate_distances(n, U, cells.data(), seed, k0 + kk, model, &whole[(size_t)kk * n * n]);
-      if (hip_check(hipMemcpyAsync(d_dist.p, whole.data(), whole.size() * 8, hipMemcpyHostToDevice, st))) return DAFS_HIP_ELAUNCH;
+      if (f.up(d_dist, whole.data(), whole.size() * 8)) return DAFS_HIP_ELAUNCH;
     } else if (fixes) {
       fix.resize(fixes);
       if (hip_check(hipMemcpy(fix.data(), a.fix, (size_t)fixes * sizeof(boot_fix), hipMemcpyDeviceToHost))) return DAFS_HIP_ELAUNCH;
       if (fixes <= 64) {  // the usual few: one word each
         patch.resize(fixes);
-        for (uint32_t f = 0; f < fixes; ++f) {
-          patch[f] = host_distance(model, fix[f].mism, fix[f].comp);
-          if (hip_check(hipMemcpyAsync(a.dist + ((size_t)fix[f].k * n + fix[f].r) * n + fix[f].s, &patch[f], 8, hipMemcpyHostToDevice, st)))
-            return DAFS_HIP_ELAUNCH;
+        for (uint32_t i = 0; i < fixes; ++i) {
+          patch[i] = nj_pair_distance(model, fix[i].mism, fix[i].comp);
+          if (f.up(a.dist + ((size_t)fix[i].k * n + fix[i].r) * n + fix[i].s, &patch[i], 8)) return DAFS_HIP_ELAUNCH;
         }
       } else {  // many: the matrices make the round trip once
         whole.resize((size_t)count * n * n);
-        if (hip_check(hipMemcpy(whole.data(), d_dist.p, whole.size() * 8, hipMemcpyDeviceToHost))) return DAFS_HIP_ELAUNCH;
-        for (const boot_fix& f : fix) whole[((size_t)f.k * n + f.r) * n + f.s] = host_distance(model, f.mism, f.comp);
-        if (hip_check(hipMemcpyAsync(d_dist.p, whole.data(), whole.size() * 8, hipMemcpyHostToDevice, st))) return DAFS_HIP_ELAUNCH;
+        if (hip_check(hipMemcpy(whole.data(), d_dist, whole.size() * 8, hipMemcpyDeviceToHost))) return DAFS_HIP_ELAUNCH;
+        for (const boot_fix& x : fix) whole[((size_t)x.k * n + x.r) * n + x.s] = nj_pair_distance(model, x.mism, x.comp);
+        if (f.up(d_dist, whole.data(), whole.size() * 8)) return DAFS_HIP_ELAUNCH;
       }
     }
-    if ((rc = nj_batch_launch(n, count, a.dist, d_ws.p, d_left, d_right, d_length, batched, st))) return rc;
+    if ((rc = nj_batch_launch(n, count, a.dist, d_ws, d_left, d_right, d_length, batched, st))) return rc;
     heads.resize(count);
-    if (hip_check(hipMemcpyAsync(heads.data(), d_ws.p, (size_t)count * sizeof(nj_head), hipMemcpyDeviceToHost, st)) ||
-        hip_check(hipMemcpyAsync(h_left.data(), d_left, (size_t)count * T * 4, hipMemcpyDeviceToHost, st)) ||
-        hip_check(hipMemcpyAsync(h_right.data(), d_right, (size_t)count * T * 4, hipMemcpyDeviceToHost, st)) || hip_check(hipStreamSynchronize(st)))
+    if (f.down(heads.data(), d_ws, (size_t)count * sizeof(nj_head)) || f.down(h_left.data(), d_left, (size_t)count * T * 4) ||
+        f.down(h_right.data(), d_right, (size_t)count * T * 4) || f.finish())
       return DAFS_HIP_ELAUNCH;
     if ((rc = heads_verdict("alignment_bootstrap", "replicate", n, k0, heads))) return rc;
     for (uint32_t kk = 0; kk < count; ++kk) counter.add(&h_left[kk * T], &h_right[kk * T]);

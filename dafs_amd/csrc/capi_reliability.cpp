@@ -17,8 +17,8 @@
 #include <vector>
 
 #include "../../include/dafs_hip.h"
-#include "ctx.h"
-#include "hip_util.h"
+#include "call_frame.h"
+#include "call_host.h"
 #include "reliability.h"
 
 using namespace dafs;
@@ -26,9 +26,8 @@ using namespace dafs;
 namespace {
 
 // The device workspace of one chunk, carved from c->work: what is uploaded, what comes back, then the maps.
-struct rel_carve {
-  size_t o_alns, o_rows, o_blk, o_cblk, o_ss, o_mask, head_bytes, o_res, o_crel, o_prel, o_prows, out_bytes, o_pos, o_col, top = 0;
-  size_t take(size_t b) { const size_t at = top; top += (b + 255) & ~(size_t)255; return at; }
+struct rel_carve : carve {
+  size_t o_alns, o_rows, o_blk, o_cblk, o_ss, o_mask, head_bytes, o_res, o_crel, o_prel, o_prows, out_bytes, o_pos, o_col;
   rel_carve(size_t alns, size_t rows, size_t blocks, size_t col_blocks, size_t cols, size_t cells, size_t wanted, size_t residues, bool ss) {
     o_alns = take(alns * sizeof(rel_aln)); o_rows = take(rows * sizeof(rel_row)); o_blk = take(blocks * 8); o_cblk = take(col_blocks * 8);
     o_ss = take(ss ? cols * 4 : 0); o_mask = take(cells);
@@ -90,15 +89,7 @@ extern "C" int dafs_hip_alignment_reliabilities(dafs_hip_ctx* c, uint32_t nalign
       if (cnt != c->len[seq[row0[a] + r]]) return DAFS_HIP_EINVAL;
       if (want && !want[row0[a] + r]) all_wanted[a] = 0;
     }
-    if (ss) {  // left column -> right column, each column in at most one pair
-      used.assign(L, 0);
-      for (uint32_t col = 0; col < L; ++col) {
-        const uint32_t p = ss[col0[a] + col];
-        if (p == DAFS_HIP_NONE) continue;
-        if (p <= col || p >= L || used[col] || used[p]) return DAFS_HIP_EINVAL;
-        used[col] = used[p] = 1;
-      }
-    }
+    if (ss && !structure_ok(ss + col0[a], L, used)) return DAFS_HIP_EINVAL;
     if (n > 1) {  // the matching store: whole, and holding every pair of a wanted row with another row of the alignment
       if (!mps.valid || mps.n_tasks != c->fam.npairs()) return DAFS_HIP_EINVAL;
       if (mps.listed)
@@ -112,12 +103,8 @@ extern "C" int dafs_hip_alignment_reliabilities(dafs_hip_ctx* c, uint32_t nalign
         }
     }
   }
-  uint64_t budget = dafs_host_reliability_batch_bytes();
-  if (const char* e = getenv("DAFS_HIP_REL_BATCH_BYTES")) {  // a value that is no number is ignored
-    char* end = nullptr;
-    const unsigned long long v = strtoull(e, &end, 10);
-    if (end != e && *end == '\0' && *e >= '0' && *e <= '9') budget = v;
-  }
+  // tests: budgets that put every alignment in a chunk of its own
+  const uint64_t budget = env_uint("DAFS_HIP_REL_BATCH_BYTES", 0, UINT64_MAX, dafs_host_reliability_batch_bytes());
   std::vector<uint32_t> chunk_of(nalign);
   int rc;
   if ((rc = dafs_host_pack_greedy(nalign, bytes.data(), budget, chunk_of.data()))) return rc;
@@ -141,12 +128,12 @@ extern "C" int dafs_hip_alignment_reliabilities(dafs_hip_ctx* c, uint32_t nalign
     }
     const rel_carve cv(a1 - a0, row0[a1] - row0[a0], nblocks, ncol_blocks, col0[a1] - col0[a0], mask0[a1] - mask0[a0], wanted, residues,
                        ss != nullptr);
-    if (cv.top + 256 > estimate) {  // dafs_host_reliability_bytes is the bound of this carving
-      fprintf(stderr, "dafs_hip: a chunk of %u alignments takes %zu bytes, over its estimate of %llu\n", a1 - a0, cv.top + 256,
+    if (cv.reserve_bytes() > estimate) {  // dafs_host_reliability_bytes is the bound of this carving
+      fprintf(stderr, "dafs_hip: a chunk of %u alignments takes %zu bytes, over its estimate of %llu\n", a1 - a0, cv.reserve_bytes(),
               (unsigned long long)estimate);
       return DAFS_HIP_ELAUNCH;
     }
-    work_bytes = std::max(work_bytes, cv.top + 256);
+    work_bytes = std::max(work_bytes, cv.reserve_bytes());
     a0 = a1;
   }
   if ((rc = c->work.reserve(work_bytes))) return rc;
@@ -155,7 +142,7 @@ extern "C" int dafs_hip_alignment_reliabilities(dafs_hip_ctx* c, uint32_t nalign
   std::vector<rel_row> rows;
   std::vector<uint2> blocks, col_blocks;
   std::vector<uint8_t> head, out;
-  hipStream_t st = c->stream;
+  call_frame f(c);  // `head` and `out` are in flight when an error ends a chunk early
   for (uint32_t a0 = 0; a0 < nalign;) {
     uint32_t a1 = a0;
     while (a1 < nalign && chunk_of[a1] == chunk_of[a0]) ++a1;
@@ -216,13 +203,11 @@ extern "C" int dafs_hip_alignment_reliabilities(dafs_hip_ctx* c, uint32_t nalign
     g.pair_rel = (double*)(w + o_prel);
     g.pair_rows = (uint32_t*)(w + o_prows);
     g.nrows = (uint32_t)nrow; g.nblocks = (uint32_t)blocks.size(); g.ncol_blocks = (uint32_t)col_blocks.size();
-    rc = DAFS_HIP_OK;
-    if (hip_check(hipMemcpyAsync(w, head.data(), head_bytes, hipMemcpyHostToDevice, st))) rc = DAFS_HIP_ELAUNCH;
-    if (!rc) rc = rel_launch(g, st);
+    if (f.up(w, head.data(), head_bytes)) return DAFS_HIP_ELAUNCH;
+    if ((rc = rel_launch(g, f.st))) return rc;
     out.resize(out_bytes);
-    if (!rc && hip_check(hipMemcpyAsync(out.data(), w + o_res, out_bytes, hipMemcpyDeviceToHost, st))) rc = DAFS_HIP_ELAUNCH;
-    if (hip_check(hipStreamSynchronize(st)) && !rc) rc = DAFS_HIP_ELAUNCH;  // also after a failure: `head` is in flight
-    if (rc) return rc;
+    if (f.down(out.data(), w + o_res, out_bytes)) return DAFS_HIP_ELAUNCH;
+    if ((rc = f.finish())) return rc;  // per chunk: the next one rewrites `head`
     const double* rel = (const double*)out.data();
     if (col_rel) memcpy(col_rel + col0[a0], out.data() + (o_crel - o_res), cols * 8);
     if (pair_rel) memcpy(pair_rel + col0[a0], out.data() + (o_prel - o_res), cols * 8);

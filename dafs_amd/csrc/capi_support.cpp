@@ -6,8 +6,8 @@
 #include <vector>
 
 #include "../../include/dafs_hip.h"
-#include "ctx.h"
-#include "hip_util.h"
+#include "call_frame.h"
+#include "call_host.h"
 #include "support.h"
 
 using namespace dafs;
@@ -28,14 +28,7 @@ extern "C" int dafs_hip_structure_support(dafs_hip_ctx* c, uint32_t nalign, cons
   for (uint32_t a = 0, r0 = 0; a < nalign; r0 += n_rows[a], ++a) {
     const uint32_t L = len[a];
     if (!n_rows[a] || !L) return DAFS_HIP_EINVAL;
-    // ss: left column -> right column, each column in at most one pair
-    used.assign(L, 0);
-    for (uint32_t col = 0; col < L; ++col) {
-      const uint32_t p = ss[ss_at + col];
-      if (p == DAFS_HIP_NONE) continue;
-      if (p <= col || p >= L || used[col] || used[p]) return DAFS_HIP_EINVAL;
-      used[col] = used[p] = 1;
-    }
+    if (!structure_ok(ss + ss_at, L, used)) return DAFS_HIP_EINVAL;
     for (uint32_t r = 0; r < n_rows[a]; ++r) {
       const uint32_t x = seq[r0 + r];
       if (x >= N) return DAFS_HIP_EINVAL;
@@ -53,13 +46,11 @@ extern "C" int dafs_hip_structure_support(dafs_hip_ctx* c, uint32_t nalign, cons
   const size_t R = rows.size();
   if (R > 0x7fffffffull) return DAFS_HIP_EOVERFLOW;
 
-  // device workspace, carved from c->work
-  size_t top = 0;
-  auto take = [&](size_t bytes) { const size_t at = top; top += (bytes + 255) & ~(size_t)255; return at; };
-  const size_t o_rows = take(R * sizeof(sup_row)), o_ss = take(ss_at * 4), o_mask = take(mask_at), o_pos = take(mask_at * 4);
-  const size_t o_both = take(R * 4), o_can = take(R * 4), o_half = take(R * 4), o_exp = take(R * 8);
+  carve cv;  // device workspace, carved from c->work
+  const size_t o_rows = cv.take(R * sizeof(sup_row)), o_ss = cv.take(ss_at * 4), o_mask = cv.take(mask_at), o_pos = cv.take(mask_at * 4);
+  const size_t o_both = cv.take(R * 4), o_can = cv.take(R * 4), o_half = cv.take(R * 4), o_exp = cv.take(R * 8);
   int rc;
-  if ((rc = c->work.reserve(top + 256))) return rc;
+  if ((rc = c->work.reserve(cv.reserve_bytes()))) return rc;
   uint8_t* w = c->work.ptr;
   sup_args g;
   memset(&g, 0, sizeof g);
@@ -74,14 +65,11 @@ extern "C" int dafs_hip_structure_support(dafs_hip_ctx* c, uint32_t nalign, cons
   g.half = (uint32_t*)(w + o_half);
   g.expected = (double*)(w + o_exp);
   g.nrows = (uint32_t)R;
-  hipStream_t st = c->stream;
-  auto up = [&](size_t off, const void* src, size_t bytes) { return bytes && hip_check(hipMemcpyAsync(w + off, src, bytes, hipMemcpyHostToDevice, st)); };
-  auto down = [&](void* dst, const void* src, size_t bytes) { return dst && hip_check(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st)); };
-  rc = DAFS_HIP_OK;
-  if (up(o_rows, rows.data(), R * sizeof(sup_row)) || up(o_ss, ss, ss_at * 4) || up(o_mask, mask, mask_at)) rc = DAFS_HIP_ELAUNCH;
-  if (!rc) rc = sup_launch(g, st);
-  if (!rc && (down(both, g.both, R * 4) || down(canonical, g.canonical, R * 4) || down(half, g.half, R * 4) || down(expected, g.expected, R * 8)))
-    rc = DAFS_HIP_ELAUNCH;
-  if (hip_check(hipStreamSynchronize(st)) && !rc) rc = DAFS_HIP_ELAUNCH;  // also after a failure: `rows` is in flight
-  return rc;
+  call_frame f(c);  // `rows` is in flight
+  if (f.up(w + o_rows, rows.data(), R * sizeof(sup_row)) || f.up(w + o_ss, ss, ss_at * 4) || f.up(w + o_mask, mask, mask_at)) return DAFS_HIP_ELAUNCH;
+  if ((rc = sup_launch(g, f.st))) return rc;
+  // what the caller asked for goes into its memory directly
+  if (f.down(both, g.both, R * 4) || f.down(canonical, g.canonical, R * 4) || f.down(half, g.half, R * 4) || f.down(expected, g.expected, R * 8))
+    return DAFS_HIP_ELAUNCH;
+  return f.finish();
 }

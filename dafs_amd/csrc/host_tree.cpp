@@ -2,7 +2,8 @@
 // every host (the C++ command line, the Python driver of tests and bench.py) builds the guide tree with the same
 // code: greedy joins taken from a max-heap of (similarity, (i, j)), merged distance (d[ii][l] + d[ii][r]) * s / 2.
 // Also the merge of new sequences into a fixed seed alignment (dafs_host_merge_added) and the cut of a guide tree into
-// clusters (dafs_host_cluster_cut), shared the same way.
+// clusters (dafs_host_cluster_cut), shared the same way, and the distances of an alignment's rows from the integer matrices of
+// dafs_hip_alignment_identity (dafs_host_nj_distances).
 // Host logic only; nothing here touches the device.
 #include <cmath>
 #include <cstdint>
@@ -11,7 +12,9 @@
 #include <vector>
 
 #include "../../include/dafs_hip.h"
-#include "last_error.h"
+#include "call_host.h"
+
+using dafs::refuse;
 
 extern "C" int dafs_host_build_tree(uint32_t n0, const float* sim, float* score, int32_t* left, int32_t* right) {
   if (!n0 || !sim || !score || !left || !right) return DAFS_HIP_EINVAL;
@@ -53,7 +56,6 @@ extern "C" int dafs_host_build_tree(uint32_t n0, const float* sim, float* score,
 // ascending pass decides every join after the joins below it.
 extern "C" int dafs_host_cluster_cut(uint32_t n, const float* score, const int32_t* left, const int32_t* right, int mode, float threshold,
                                      uint32_t count, uint32_t* labels, uint32_t* n_clusters) {
-  auto refuse = [](const char* why) { dafs::set_last_error(why); return DAFS_HIP_EINVAL; };
   if (!n || !score || !left || !right || !labels || !n_clusters) return refuse("cluster cut: invalid argument");
   if (mode != DAFS_CLUSTER_THRESHOLD && mode != DAFS_CLUSTER_COUNT) return refuse("cluster cut: unknown mode");
   if (mode == DAFS_CLUSTER_THRESHOLD && std::isnan(threshold)) return refuse("cluster cut: the threshold is not a number");
@@ -90,6 +92,20 @@ extern "C" int dafs_host_cluster_cut(uint32_t n, const float* score, const int32
     labels[i] = label_of[top];
   }
   *n_clusters = next;
+  return DAFS_HIP_OK;
+}
+
+// DESIGN.md section 22, "Distances from an alignment": nj_pair_distance of every pair of rows, 0 on the diagonal.
+extern "C" int dafs_host_nj_distances(uint32_t n, const uint32_t* ident, const uint32_t* aligned, int model, double* dist) {
+  if (!n || !ident || !aligned || !dist) return refuse("nj_distances: a missing argument");
+  if (model != DAFS_NJ_P && model != DAFS_NJ_JC) return refuse("nj_distances: unknown model");
+  for (uint32_t r = 0; r < n; ++r)
+    for (uint32_t s = 0; s < n; ++s) {
+      const size_t at = (size_t)r * n + s;
+      if (r == s) { dist[at] = 0.0; continue; }
+      if (ident[at] > aligned[at]) return refuse("nj_distances: more identical columns than aligned ones");
+      dist[at] = dafs::nj_pair_distance(model, aligned[at] - ident[at], aligned[at]);
+    }
   return DAFS_HIP_OK;
 }
 

@@ -35,4 +35,7 @@ inline size_t nj_update_lds_bytes(uint32_t n) { return ((size_t)(n + 63) / 64 + 
 // only x < y read, left as it is.  n >= 2.
 int nj_launch(uint32_t n, const double* dist, void* workspace, int32_t* left, int32_t* right, double* length, hipStream_t st);
 
+// What the head of a finished launch says, for every caller (capi_nj.cpp): DAFS_HIP_OK, or the code with the message set.
+int nj_head_verdict(const char* who, const char* what, uint32_t k, uint32_t n, const nj_head& h);
+
 }  // namespace dafs

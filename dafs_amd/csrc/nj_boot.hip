@@ -22,6 +22,7 @@
 
 #include "../../include/dafs_hip.h"
 #include "alistat.h"
+#include "call_host.h"
 #include "hip_util.h"
 #include "nj_boot.h"
 #include "stage.h"
@@ -323,15 +324,8 @@ __global__ __launch_bounds__(kNjBatchThreads) void k_nj_batch(uint32_t n, const 
 
 }  // namespace
 
-uint32_t nj_batch_max_n() {
-  uint32_t limit = kNjBatchMaxN;
-  if (const char* e = getenv("DAFS_NJ_BATCH_MAX_N")) {  // tests: the looped form at small sizes (the results do not depend on it)
-    char* end = nullptr;
-    const unsigned long v = strtoul(e, &end, 10);
-    if (end != e && v < limit) limit = (uint32_t)v;
-  }
-  return limit;
-}
+// tests: the looped form at small sizes (the results do not depend on it)
+uint32_t nj_batch_max_n() { return (uint32_t)env_uint("DAFS_NJ_BATCH_MAX_N", 0, kNjBatchMaxN - 1, kNjBatchMaxN); }
 
 int nj_batch_launch(uint32_t n, uint32_t count, const double* dist, void* workspace, int32_t* left, int32_t* right, double* length, bool batched,
                     hipStream_t st) {

@@ -246,9 +246,9 @@ def test_support_tells_an_evolved_set_from_a_random_one(seed):
 
 
 # ---- memory safety of the host entry points ----
-def test_host_support_under_sanitizers(tmp_path):
-    """tests/host_support_main.cpp calls dafs_host_tree_support, dafs_host_newick_support and dafs_host_support_table, the
-    refusals included, in a program of its own built with -fsanitize=address,undefined: exit status 0, nothing on stderr"""
+def _runs_clean_under_sanitizers(tmp_path, main, with_sources):
+    """tests/<main>.cpp and the named files of dafs_amd/csrc as a program of its own built with -fsanitize=address,undefined:
+    exit status 0, nothing on stderr"""
     cxx = shutil.which(os.environ.get("CXX", "g++"))
     if cxx is None:
         pytest.skip("no C++ compiler")
@@ -258,13 +258,25 @@ def test_host_support_under_sanitizers(tmp_path):
     r = subprocess.run([cxx] + flags + [str(probe), "-o", str(tmp_path / "probe")], capture_output=True, text=True)
     if r.returncode != 0 or subprocess.run([str(tmp_path / "probe")], capture_output=True).returncode != 0:
         pytest.skip("the compiler has no usable address / undefined-behaviour sanitizer runtime: " + r.stderr.strip()[-200:])
-    srcs = [os.path.join(ROOT, "tests", "host_support_main.cpp"), os.path.join(ROOT, "dafs_amd", "csrc", "host_text.cpp"),
-            os.path.join(ROOT, "dafs_amd", "csrc", "host_tree.cpp")]
-    exe = str(tmp_path / "host_support_main")
+    srcs = [os.path.join(ROOT, "tests", main + ".cpp")] + [os.path.join(ROOT, "dafs_amd", "csrc", s) for s in with_sources]
+    exe = str(tmp_path / main)
     r = subprocess.run([cxx] + flags + ["-Wall"] + srcs + ["-o", exe], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
     r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
     assert r.returncode == 0 and r.stderr == "", (r.stdout, r.stderr)
+
+
+def test_host_support_under_sanitizers(tmp_path):
+    """tests/host_support_main.cpp calls dafs_host_tree_support, dafs_host_newick_support and dafs_host_support_table, the
+    refusals included"""
+    _runs_clean_under_sanitizers(tmp_path, "host_support_main", ["host_text.cpp", "host_tree.cpp"])
+
+
+def test_host_call_helpers_under_sanitizers(tmp_path):
+    """tests/host_call_main.cpp checks what dafs_amd/csrc/call_host.h gives the per-call entry points, compiled without a ROCm
+    include path: the offset carver, the knob readers, the structure check, and the distance of a pair of rows against
+    dafs_host_nj_distances to the bit"""
+    _runs_clean_under_sanitizers(tmp_path, "host_call_main", ["host_tree.cpp"])
 
 
 def test_python_refuses_before_it_opens_a_context(monkeypatch):

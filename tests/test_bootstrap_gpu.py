@@ -303,6 +303,7 @@ SWITCHES = {
     "every entry through the fix-up list": {"DAFS_NJ_BOOT_GUARD": "0.5"},
     "a fix-up list that overflows": {"DAFS_NJ_BOOT_GUARD": "0.5", "DAFS_NJ_BOOT_FIXUPS": "100"},
     "a fix-up list of a few entries": {"DAFS_NJ_BOOT_GUARD": None},  # chosen below from the restatement's own values
+    "a few entries for a list of one": {"DAFS_NJ_BOOT_GUARD": None, "DAFS_NJ_BOOT_FIXUPS": "1"},
     "the looped joins": {"DAFS_NJ_BATCH_MAX_N": "0"},
     "the looped joins in chunks": {"DAFS_NJ_BATCH_MAX_N": "0", "DAFS_NJ_BOOT_BYTES": "100000"},
 }
@@ -355,8 +356,10 @@ def test_the_switches_change_no_result(ctx, monkeypatch, switch):
     fixed = capi.bootstrap_fixups()
     if "0.5" in SWITCHES[switch].values():
         assert fixed == len(near)  # every jc entry below the cap
-    elif switch == "a fix-up list of a few entries":
+    elif None in SWITCHES[switch].values():
         assert fixed == sum(1 for d in near if d < few) >= 5
+    if "DAFS_NJ_BOOT_FIXUPS" in SWITCHES[switch]:  # more entries than the capacity asked for: the case is one for the overflow path
+        assert fixed > int(SWITCHES[switch]["DAFS_NJ_BOOT_FIXUPS"])
 
 
 def test_degenerate_sizes_launch_nothing(ctx):
