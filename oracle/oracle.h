@@ -108,6 +108,21 @@ void orc_pipeline_tree(const orc_pipeline* pl, float* score, uint32_t* left, uin
 const char* orc_pipeline_output(orc_pipeline* pl);
 /* per internal node (in solve order): iterations run and final violated count (dafs.cpp:1292) */
 uint32_t orc_pipeline_dd_log(const orc_pipeline* pl, uint32_t* iters, uint32_t* violated, uint32_t cap);
+/* the same log with, per entry, the guide-tree node it belongs to (index into orc_pipeline_tree), the number of consensus
+ * base pairs of the node (the length of solve_by_dd's cbp list) and the score solve_by_dd returned (dafs.cpp:1294) */
+uint32_t orc_pipeline_node_log(const orc_pipeline* pl, uint32_t* node, uint32_t* iters, uint32_t* violated, uint32_t* ncbp, float* score,
+                               uint32_t cap);
+/* One internal node on the current stores (after orc_pipeline_phase1), exactly as align_node solves it: the averages of
+ * the children's base-pairing and matching probabilities, then solve_by_dd (dafs.cpp:896-911, :1006-1295).  Children are
+ * rows (idx: sequence index per row; mask: n*L bytes, 1 = residue, every row placing exactly its sequence's residues).
+ * p_x / p_y: NULL, or L1*L1 / L2*L2 floats that replace the base-pairing averages (the --bp-update input, :919-934).
+ * x[L1], y[L2], z[L1]: the last decodes (ORC_NONE = unpaired / unaligned); score: solve_by_dd's return value; ncbp: the
+ * length of its cbp list; iterations, violated: as in orc_pipeline_dd_log.  Leaves the log and the stores untouched.
+ * Parity unpinned (pipeline.c header); the decoders it calls are pinned.  0, or -1 for arguments that name no node. */
+int orc_pipeline_solve_node(orc_pipeline* pl, uint32_t n1, const uint32_t* idx1, const uint8_t* mask1, uint32_t L1,
+                            uint32_t n2, const uint32_t* idx2, const uint8_t* mask2, uint32_t L2,
+                            const float* p_x, const float* p_y, uint32_t* x, uint32_t* y, uint32_t* z,
+                            float* score, uint32_t* ncbp, uint32_t* iterations, uint32_t* violated);
 double orc_pipeline_seconds(const orc_pipeline* pl, int phase); /* 0 fold,1 pair,2 pct+tree,3 progressive */
 
 /* FASTA reader following Fasta::load src/fa.cpp:37-87. Returns count or -1.

@@ -45,6 +45,7 @@ struct orc_pipeline {
   uint32_t* final_ss; char* final_str;
   char* out; size_t out_len, out_cap;
   uint32_t* dd_iters; uint32_t* dd_viol; uint32_t dd_n;
+  uint32_t* dd_node; uint32_t* dd_ncbp; float* dd_score; /* per entry of the log: guide-tree node, |cbp|, returned score */
   double secs[4];
 };
 
@@ -512,10 +513,13 @@ static void adj_build(adj_t* a, uint32_t nrow, uint64_t* keys, size_t nk) {
   for (uint32_t r = 0; r < nrow; ++r) a->ptr[r + 1] += a->ptr[r];
 }
 
-/* DAFS::solve_by_dd, dafs.cpp:1006-1295 (SPARSE_UPDATE, plain subgradient branch) */
-static float solve_by_dd(orc_pipeline* pl, uint32_t* x, uint32_t* y, uint32_t* z,
+/* DAFS::solve_by_dd, dafs.cpp:1006-1295 (SPARSE_UPDATE, plain subgradient branch).  Returns what the reference returns
+ * (s_prev, :1294); the length of the cbp list, the iterations run and the last violated count (the values of the
+ * reference's log line, :1292) come back through the out-parameters -- the caller keeps the log. */
+static float solve_by_dd(const orc_pipeline* pl, uint32_t* x, uint32_t* y, uint32_t* z,
                          const float* p_x, const float* p_y, const float* p_z,
-                         uint32_t L1, uint32_t L2, uint32_t N1, uint32_t N2) {
+                         uint32_t L1, uint32_t L2, uint32_t N1, uint32_t N2,
+                         uint32_t* o_ncbp, uint32_t* o_iterations, uint32_t* o_violated) {
   const orc_params* prm = &pl->prm;
   const float w_ = prm->w, th_a_ = prm->th_a, eta0_ = prm->eta0;
   const float min_th_s = prm->th_s;
@@ -635,9 +639,9 @@ static float solve_by_dd(orc_pipeline* pl, uint32_t* x, uint32_t* y, uint32_t* z
     }
     s_prev = s;
   }
-  pl->dd_iters[pl->dd_n] = t;
-  pl->dd_viol[pl->dd_n] = violated;
-  pl->dd_n++;
+  *o_ncbp = (uint32_t)ncbp;
+  *o_iterations = t;
+  *o_violated = violated;
   free(cbp); free(c_x.ptr); free(c_x.idx); free(c_y.ptr); free(c_y.idx); free(c_z.ptr); free(c_z.idx);
   free(env); free(q_x); free(q_y); free(q_z); free(t_x); free(t_y); free(t_z);
   return s_prev;
@@ -708,7 +712,14 @@ static void align_node(orc_pipeline* pl, aln_t* out, uint32_t ch) {
   uint32_t* x = (uint32_t*)malloc(((size_t)a1.L + 1) * sizeof(uint32_t));
   uint32_t* y = (uint32_t*)malloc(((size_t)a2.L + 1) * sizeof(uint32_t));
   uint32_t* z = (uint32_t*)malloc(((size_t)a1.L + 1) * sizeof(uint32_t));
-  solve_by_dd(pl, x, y, z, p_x, p_y, p_z, a1.L, a2.L, a1.n, a2.n);
+  uint32_t ncbp, iters, viol;
+  const float score = solve_by_dd(pl, x, y, z, p_x, p_y, p_z, a1.L, a2.L, a1.n, a2.n, &ncbp, &iters, &viol);
+  pl->dd_node[pl->dd_n] = ch;
+  pl->dd_iters[pl->dd_n] = iters;
+  pl->dd_viol[pl->dd_n] = viol;
+  pl->dd_ncbp[pl->dd_n] = ncbp;
+  pl->dd_score[pl->dd_n] = score;
+  pl->dd_n++;
   project_alignment(out, &a1, &a2, z);
   free(p_x); free(p_y); free(p_z); free(x); free(y); free(z);
   aln_free(&a1); aln_free(&a2);
@@ -735,6 +746,9 @@ orc_pipeline* orc_pipeline_new(const orc_params* prm, uint32_t N, const char* co
   pl->tright = (uint32_t*)calloc(2 * N, sizeof(uint32_t));
   pl->dd_iters = (uint32_t*)calloc(N + 1, sizeof(uint32_t));
   pl->dd_viol = (uint32_t*)calloc(N + 1, sizeof(uint32_t));
+  pl->dd_node = (uint32_t*)calloc(N + 1, sizeof(uint32_t));
+  pl->dd_ncbp = (uint32_t*)calloc(N + 1, sizeof(uint32_t));
+  pl->dd_score = (float*)calloc(N + 1, sizeof(float));
   return pl;
 }
 
@@ -744,6 +758,7 @@ void orc_pipeline_free(orc_pipeline* pl) {
   for (size_t e = 0; e < (size_t)pl->N * pl->N; ++e) orc_csr_free(&pl->mp[e]);
   free(pl->names); free(pl->seqs); free(pl->len); free(pl->bp); free(pl->mp); free(pl->sim);
   free(pl->tscore); free(pl->tleft); free(pl->tright); free(pl->dd_iters); free(pl->dd_viol);
+  free(pl->dd_node); free(pl->dd_ncbp); free(pl->dd_score);
   aln_free(&pl->final_aln); free(pl->final_ss); free(pl->final_str); free(pl->out);
   free(pl);
 }
@@ -830,6 +845,45 @@ int orc_pipeline_phase1(orc_pipeline* pl) {
   return 0;
 }
 
+/* One internal node of the progressive phase on the pipeline's current stores (after orc_pipeline_phase1): what
+ * align_node runs between its two recursive calls and project_alignment -- average_basepairing_probability of both
+ * children, average_matching_probability, solve_by_dd (dafs.cpp:896-911) -- for children given as rows (sequence index,
+ * mask) instead of subtrees.  p_x / p_y non-NULL replace the base-pairing averages (L1*L1 / L2*L2 floats): the matrices
+ * the --bp-update branch (:919-934) hands to solve_by_dd.  Nothing is appended to the pipeline's log and no store changes.
+ * PARITY UNPINNED, like the rest of this file (header): it restates dafs.cpp, which cannot be compiled
+ * here.  The decoders it calls (orc_nussinov_decode, orc_nw_envelope, orc_nw_decode) are the pinned ones.
+ * Returns 0, or -1 for arguments that name no node: a null pointer, no row or column, a sequence the pipeline does not
+ * hold, a mask row that does not place exactly that sequence's residues, or missing stores. */
+int orc_pipeline_solve_node(orc_pipeline* pl, uint32_t n1, const uint32_t* idx1, const uint8_t* mask1, uint32_t L1,
+                            uint32_t n2, const uint32_t* idx2, const uint8_t* mask2, uint32_t L2,
+                            const float* p_x, const float* p_y, uint32_t* x, uint32_t* y, uint32_t* z,
+                            float* score, uint32_t* ncbp, uint32_t* iterations, uint32_t* violated) {
+  if (!pl || !n1 || !n2 || !L1 || !L2 || !idx1 || !idx2 || !mask1 || !mask2 || !x || !y || !z) return -1;
+  aln_t a[2] = {{n1, L1, (uint32_t*)idx1, (uint8_t*)mask1}, {n2, L2, (uint32_t*)idx2, (uint8_t*)mask2}};
+  for (int c = 0; c < 2; ++c)
+    for (uint32_t r = 0; r < a[c].n; ++r) {
+      const uint32_t s = a[c].idx[r];
+      if (s >= pl->N || !pl->bp[s].rowptr) return -1;
+      uint32_t res = 0;
+      for (uint32_t i = 0; i < a[c].L; ++i) res += a[c].mask[(size_t)r * a[c].L + i] != 0;
+      if (res != pl->len[s]) return -1;
+    }
+  for (uint32_t r1 = 0; r1 < n1; ++r1)
+    for (uint32_t r2 = 0; r2 < n2; ++r2)
+      if (!MP(pl, idx1[r1], idx2[r2])->rowptr) return -1;
+  float* ax = p_x ? NULL : average_basepairing_probability(pl, &a[0]);
+  float* ay = p_y ? NULL : average_basepairing_probability(pl, &a[1]);
+  float* p_z = average_matching_probability(pl, &a[0], &a[1]);
+  uint32_t nc = 0, it = 0, vi = 0;
+  const float s = solve_by_dd(pl, x, y, z, p_x ? p_x : ax, p_y ? p_y : ay, p_z, L1, L2, n1, n2, &nc, &it, &vi);
+  if (score) *score = s;
+  if (ncbp) *ncbp = nc;
+  if (iterations) *iterations = it;
+  if (violated) *violated = vi;
+  free(ax); free(ay); free(p_z);
+  return 0;
+}
+
 static int cmp_row(const void* a, const void* b) {
   uint32_t x = *(const uint32_t*)a, y = *(const uint32_t*)b;
   return x < y ? -1 : x > y;
@@ -889,6 +943,16 @@ uint32_t orc_pipeline_dd_log(const orc_pipeline* pl, uint32_t* iters, uint32_t* 
   uint32_t n = pl->dd_n < cap ? pl->dd_n : cap;
   memcpy(iters, pl->dd_iters, n * sizeof(uint32_t));
   memcpy(violated, pl->dd_viol, n * sizeof(uint32_t));
+  return pl->dd_n;
+}
+uint32_t orc_pipeline_node_log(const orc_pipeline* pl, uint32_t* node, uint32_t* iters, uint32_t* violated, uint32_t* ncbp, float* score,
+                               uint32_t cap) {
+  uint32_t n = pl->dd_n < cap ? pl->dd_n : cap;
+  memcpy(node, pl->dd_node, n * sizeof(uint32_t));
+  memcpy(iters, pl->dd_iters, n * sizeof(uint32_t));
+  memcpy(violated, pl->dd_viol, n * sizeof(uint32_t));
+  memcpy(ncbp, pl->dd_ncbp, n * sizeof(uint32_t));
+  memcpy(score, pl->dd_score, n * sizeof(float));
   return pl->dd_n;
 }
 double orc_pipeline_seconds(const orc_pipeline* pl, int phase) { return (phase >= 0 && phase < 4) ? pl->secs[phase] : 0.0; }

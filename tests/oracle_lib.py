@@ -72,6 +72,11 @@ class Oracle:
         L.orc_pipeline_tree.argtypes = [C.c_void_p] + [C.c_void_p] * 3
         L.orc_pipeline_dd_log.restype = C.c_uint
         L.orc_pipeline_dd_log.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint]
+        L.orc_pipeline_node_log.restype = C.c_uint
+        L.orc_pipeline_node_log.argtypes = [C.c_void_p] + [C.c_void_p] * 5 + [C.c_uint]
+        L.orc_pipeline_solve_node.restype = C.c_int
+        L.orc_pipeline_solve_node.argtypes = ([C.c_void_p] + [C.c_uint, C.c_void_p, C.c_void_p, C.c_uint] * 2 + [C.c_void_p] * 5
+                                              + [C.POINTER(C.c_float)] + [C.POINTER(C.c_uint32)] * 3)
         L.orc_pipeline_seconds.restype = C.c_double
         L.orc_pipeline_seconds.argtypes = [C.c_void_p, C.c_int]
         L.orc_fasta_load.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p]
@@ -214,6 +219,33 @@ class Pipeline:
         it = np.zeros(self.N + 1, np.uint32); vi = np.zeros(self.N + 1, np.uint32)
         k = self.o.lib.orc_pipeline_dd_log(self.h, it.ctypes.data, vi.ctypes.data, self.N + 1)
         return it[:k], vi[:k]
+
+    def node_log(self):
+        """{guide-tree node: (iterations, violated, ncbp, score)} of the internal nodes phase2 solved (orc_pipeline_node_log)"""
+        n = self.N + 1
+        node, it, vi, nc = (np.zeros(n, np.uint32) for _ in range(4))
+        sc = np.zeros(n, np.float32)
+        k = self.o.lib.orc_pipeline_node_log(self.h, node.ctypes.data, it.ctypes.data, vi.ctypes.data, nc.ctypes.data, sc.ctypes.data, n)
+        return {int(node[e]): (int(it[e]), int(vi[e]), int(nc[e]), sc[e]) for e in range(k)}
+
+    def solve_node(self, idx1, mask1, idx2, mask2, p_x=None, p_y=None):
+        """orc_pipeline_solve_node: one internal node on the current stores (after phase1), children as (sequence index per
+        row, mask [n, L]); p_x / p_y replace the base-pairing averages.  Returns the dict Context.solve_nodes returns per node."""
+        idx1 = np.ascontiguousarray(idx1, np.uint32); idx2 = np.ascontiguousarray(idx2, np.uint32)
+        m1 = np.ascontiguousarray(mask1, np.uint8); m2 = np.ascontiguousarray(mask2, np.uint8)
+        assert m1.ndim == 2 and m2.ndim == 2 and m1.shape[0] == len(idx1) and m2.shape[0] == len(idx2)
+        L1, L2 = m1.shape[1], m2.shape[1]
+        px = None if p_x is None else np.ascontiguousarray(p_x, np.float32)
+        py = None if p_y is None else np.ascontiguousarray(p_y, np.float32)
+        assert px is None or px.shape == (L1, L1)
+        assert py is None or py.shape == (L2, L2)
+        x = np.zeros(L1, np.uint32); y = np.zeros(L2, np.uint32); z = np.zeros(L1, np.uint32)
+        score = C.c_float(); ncbp = C.c_uint32(); it = C.c_uint32(); vi = C.c_uint32()
+        rc = self.o.lib.orc_pipeline_solve_node(self.h, len(idx1), idx1.ctypes.data, m1.ctypes.data, L1, len(idx2), idx2.ctypes.data, m2.ctypes.data, L2,
+                                                None if px is None else px.ctypes.data, None if py is None else py.ctypes.data,
+                                                x.ctypes.data, y.ctypes.data, z.ctypes.data, C.byref(score), C.byref(ncbp), C.byref(it), C.byref(vi))
+        assert rc == 0, rc
+        return dict(x=x, y=y, z=z, score=np.float32(score.value), ncbp=ncbp.value, iterations=it.value, violated=vi.value)
 
     def seconds(self):
         return [self.o.lib.orc_pipeline_seconds(self.h, i) for i in range(4)]

@@ -81,10 +81,37 @@ def test_nussinov_decoder_forms_vs_oracle(ctx, oracle, monkeypatch):
             assert np.float32(a[0]).tobytes() == np.float32(b[0]).tobytes() and np.array_equal(a[1], b[1]), (env, k, p.shape[0])
 
 
+def _leaf_sets(left, right, n):
+    """{leaf set: node} of a guide tree's internal nodes (children are numbered before their parents, dafs.cpp:446-492)"""
+    sets = {i: frozenset([i]) for i in range(n)}
+    for i in range(n, 2 * n - 1):
+        sets[i] = sets[int(left[i])] | sets[int(right[i])]
+    return {sets[i]: i for i in range(n, 2 * n - 1)}
+
+
+def _same_nodes(got, log):
+    """every internal node of the device's run has the (iterations, violated, ncbp, score) of the oracle's node over the same
+    leaves -- the score by its bytes; nodes are matched by leaf set, so the two trees need not number them alike"""
+    onodes, (_, oleft, oright) = log
+    n = len(oleft) // 2 + 1
+    mine = _leaf_sets(got.tree[1], got.tree[2], n)
+    theirs = _leaf_sets(oleft, oright, n)
+    assert set(mine) == set(theirs), "the guide trees differ"
+    assert sorted(got.dd_log) == sorted(mine.values()) and sorted(onodes) == sorted(theirs.values())
+    for leaves, node in sorted(theirs.items(), key=lambda kv: kv[1]):
+        its, viol, ncbp, score = got.dd_log[mine[leaves]]
+        o_its, o_viol, o_ncbp, o_score = onodes[node]
+        for name, a, b in (("iterations", its, o_its), ("violated", viol, o_viol), ("ncbp", ncbp, o_ncbp),
+                           ("score", np.float32(score).tobytes(), np.float32(o_score).tobytes())):
+            assert a == b, "node %d over leaves %s: %s %r, oracle %r (device log %r, oracle log %r)" % (
+                node, sorted(leaves), name, a, b, got.dd_log[mine[leaves]], onodes[node])
+
+
 def _run_both(oracle, names, seqs, bp, **kw):
+    """-> (the oracle's text, (its node log, its guide tree), the device's run)"""
     from dafs_amd import pipeline
     okw = dict(fold_model=1)
-    for k in ("w", "eta0", "t_max", "w_pct_a", "w_pct_s", "th_a", "th_s"):
+    for k in ("w", "eta0", "t_max", "w_pct_a", "w_pct_s", "th_a", "th_s", "force_iters"):
         if k in kw:
             okw[k] = kw[k]
     if "th_s" in kw:
@@ -92,11 +119,11 @@ def _run_both(oracle, names, seqs, bp, **kw):
     pl = oracle.pipeline(names, seqs, oracle.params(**okw), bp=bp)
     pl.phase1(); pl.phase2()
     want = pl.output()
-    it, vi = pl.dd_log()
+    log = (pl.node_log(), pl.tree())
     pl.close()
-    kw.setdefault("skip_uncoupled_folds", False)  # these tests compare the iteration log with the oracle's: the solver as the reference runs it
+    kw.setdefault("skip_uncoupled_folds", False)  # these tests compare the node log with the oracle's: the solver as the reference runs it
     got = pipeline.run(names, seqs, bp=bp, **kw)
-    return want, (it, vi), got
+    return want, log, got
 
 
 def test_rf00005_whole_run(oracle):
@@ -104,12 +131,12 @@ def test_rf00005_whole_run(oracle):
     ka = t.known()
     recs = oracle.fasta(os.path.join(G, "RF00005_0.fa"))
     names, seqs = [n for n, _ in recs], [s for _, s in recs]
-    want, (it, vi), got = _run_both(oracle, names, seqs, t._golden_bp(seqs))
+    want, log, got = _run_both(oracle, names, seqs, t._golden_bp(seqs))
     assert got.tree_line == ka["rf00005.probcons.tree"]
     assert got.rows[0] == ka["rf00005.probcons.contrafold.first_row"]
     assert got.rows[-1] == ka["rf00005.probcons.contrafold.last_row"]
     assert got.output == want
-    assert sorted(v[0] for v in got.dd_log.values()) == sorted(int(x) for x in it)
+    _same_nodes(got, log)
 
 
 @pytest.mark.parametrize("n,length,fam,seed", [(6, 50, True, 1), (8, 90, False, 2), (5, 140, True, 3), (2, 30, False, 4)])
@@ -117,9 +144,9 @@ def test_synthetic_whole_run(oracle, n, length, fam, seed):
     from test_pct_gpu import random_bp
     recs = synth.family_set(n, length, seed=seed) if fam else synth.random_set(n, length, seed=seed)
     names, seqs = [r[0] for r in recs], [r[1] for r in recs]
-    want, (it, vi), got = _run_both(oracle, names, seqs, random_bp(seqs, seed, density=0.02))
+    want, log, got = _run_both(oracle, names, seqs, random_bp(seqs, seed, density=0.02))
     assert got.output == want
-    assert sorted(v[0] for v in got.dd_log.values()) == sorted(int(x) for x in it)
+    _same_nodes(got, log)
 
 
 def test_iteration_cap_and_params(oracle):
@@ -128,8 +155,9 @@ def test_iteration_cap_and_params(oracle):
     names, seqs = [r[0] for r in recs], [r[1] for r in recs]
     bp = random_bp(seqs, 9, density=0.05)
     for kw in (dict(t_max=3), dict(w=2.0, eta0=0.25, th_s=0.1), dict(t_max=1, w_pct_a=0.0)):
-        want, (it, vi), got = _run_both(oracle, names, seqs, bp, **kw)
+        want, log, got = _run_both(oracle, names, seqs, bp, **kw)
         assert got.output == want, kw
+        _same_nodes(got, log)
 
 
 @pytest.mark.parametrize("slice_iters", [1, 7, 64])
@@ -141,11 +169,11 @@ def test_resident_nodes_equal_level_batches(oracle, slice_iters):
     recs = synth.family_set(12, 60, seed=21)
     names, seqs = [r[0] for r in recs], [r[1] for r in recs]
     bp = random_bp(seqs, 21, density=0.04)
-    want, (it, vi), got = _run_both(oracle, names, seqs, bp, slice_iters=slice_iters)
+    want, log, got = _run_both(oracle, names, seqs, bp, slice_iters=slice_iters)
     ref = pipeline.run(names, seqs, bp=bp, level_sync=True, skip_uncoupled_folds=False)
     assert got.output == want == ref.output
     assert got.dd_log == ref.dd_log
-    assert sorted(v[0] for v in got.dd_log.values()) == sorted(int(x) for x in it)
+    _same_nodes(got, log)
 
 
 def test_alignments_beyond_1024_columns(oracle):
@@ -155,8 +183,9 @@ def test_alignments_beyond_1024_columns(oracle):
     recs = synth.random_set(3, 1100, seed=31)
     names, seqs = [r[0] for r in recs], [r[1] for r in recs]
     assert max(len(s) for s in seqs) > 1024
-    want, (it, vi), got = _run_both(oracle, names, seqs, random_bp(seqs, 31, density=0.003), t_max=4)
+    want, log, got = _run_both(oracle, names, seqs, random_bp(seqs, 31, density=0.003), t_max=4)
     assert got.output == want
+    _same_nodes(got, log)
     assert len(got.rows[0]) > 1024
 
 
@@ -168,8 +197,9 @@ def test_split_mode_and_shared_region(oracle, monkeypatch):
     recs = synth.family_set(5, 240, seed=41)
     names, seqs = [r[0] for r in recs], [r[1] for r in recs]
     bp = random_bp(seqs, 41, density=0.01)
-    want, (it, vi), got = _run_both(oracle, names, seqs, bp, t_max=40)
+    want, log, got = _run_both(oracle, names, seqs, bp, t_max=40)
     assert got.output == want
+    _same_nodes(got, log)
     monkeypatch.setenv("DAFS_HIP_DD_SPLIT", "0")  # the same run with the foldings kept inside the leader's workgroup
     ref = pipeline.run(names, seqs, bp=bp, t_max=40, level_sync=True, skip_uncoupled_folds=False)
     assert ref.output == want and ref.dd_log == got.dd_log
@@ -186,9 +216,9 @@ def test_span_form_placements(oracle, monkeypatch, n, length, density, t_max):
     recs = synth.random_set(n, length, seed=77)
     names, seqs = [r[0] for r in recs], [r[1] for r in recs]
     bp = random_bp(seqs, 77, density=density)
-    want, (it, vi), got = _run_both(oracle, names, seqs, bp, t_max=t_max, slice_iters=7)
+    want, log, got = _run_both(oracle, names, seqs, bp, t_max=t_max, slice_iters=7)
     assert got.output == want
-    assert sorted(v[0] for v in got.dd_log.values()) == sorted(int(x) for x in it)
+    _same_nodes(got, log)
     monkeypatch.setenv("DAFS_HIP_DD_SPLIT", "0")  # span form only where both foldings fit the node's workgroup
     one = pipeline.run(names, seqs, bp=bp, t_max=t_max, skip_uncoupled_folds=False)
     assert one.output == want and one.dd_log == got.dd_log
@@ -209,8 +239,9 @@ def test_fast_folding_with_codes_in_hbm(oracle, monkeypatch, length):
     names, seqs = [r[0] for r in recs], [r[1] for r in recs]
     assert 420 < min(len(s) for s in seqs) and max(len(s) for s in seqs) <= 768
     bp = random_bp(seqs, 43, density=0.006)
-    want, (it, vi), got = _run_both(oracle, names, seqs, bp, t_max=25)
+    want, log, got = _run_both(oracle, names, seqs, bp, t_max=25)
     assert got.output == want
+    _same_nodes(got, log)
     monkeypatch.setenv("DAFS_HIP_DD_SPLIT", "0")
     ref = pipeline.run(names, seqs, bp=bp, t_max=25, level_sync=True, skip_uncoupled_folds=False)
     assert ref.output == want and ref.dd_log == got.dd_log
@@ -225,9 +256,10 @@ def test_uncoupled_nodes_without_their_folding_dps(oracle):
     for recs, seed in ((synth.random_set(10, 70, seed=51), 51), (synth.family_set(12, 60, seed=21), 21)):
         names, seqs = [r[0] for r in recs], [r[1] for r in recs]
         bp = random_bp(seqs, seed, density=0.03)
-        want, (it, vi), full = _run_both(oracle, names, seqs, bp)
+        want, log, full = _run_both(oracle, names, seqs, bp)
         lean = pipeline.run(names, seqs, bp=bp, skip_uncoupled_folds=True)
         assert full.output == want == lean.output
+        _same_nodes(full, log)
         for node, (its, viol, ncbp, score) in full.dd_log.items():
             if ncbp:  # coupled nodes are untouched
                 assert lean.dd_log[node] == (its, viol, ncbp, score)
@@ -245,9 +277,9 @@ def test_dense_base_pairs_overflow_the_register_form(oracle, monkeypatch):
     recs = synth.family_set(4, 260, seed=61)
     names, seqs = [r[0] for r in recs], [r[1] for r in recs]
     bp = random_bp(seqs, 61, density=0.04)
-    want, (it, vi), got = _run_both(oracle, names, seqs, bp, t_max=12, slice_iters=5)
+    want, log, got = _run_both(oracle, names, seqs, bp, t_max=12, slice_iters=5)
     assert got.output == want
-    assert sorted(v[0] for v in got.dd_log.values()) == sorted(int(x) for x in it)
+    _same_nodes(got, log)
     monkeypatch.setenv("DAFS_HIP_DD_SPLIT", "0")
     ref = pipeline.run(names, seqs, bp=bp, t_max=12, level_sync=True, skip_uncoupled_folds=False)
     assert ref.output == want and ref.dd_log == got.dd_log
@@ -255,23 +287,16 @@ def test_dense_base_pairs_overflow_the_register_form(oracle, monkeypatch):
 
 def test_forced_iterations_equal_oracle(oracle):
     """force_iters (the bench mode that ignores the violated == 0 exit, dafs_dd_params / oracle pipeline.c:523): every
-    node runs t_max iterations; output and iteration log must still be the oracle's."""
-    from dafs_amd import pipeline
+    node runs t_max iterations; output and node log must still be the oracle's."""
     from test_pct_gpu import random_bp
     recs = synth.family_set(7, 60, seed=31) + synth.random_set(2, 45, seed=32)
     names, seqs = [r[0] for r in recs], [r[1] for r in recs]
     bp = random_bp(seqs, 31, density=0.04)
     for t_max in (1, 17):
-        pl = oracle.pipeline(names, seqs, oracle.params(fold_model=1, t_max=t_max, force_iters=1), bp=bp)
-        pl.phase1(); pl.phase2()
-        want = pl.output()
-        it, vi = pl.dd_log()
-        pl.close()
-        got = pipeline.run(names, seqs, bp=bp, t_max=t_max, force_iters=1, skip_uncoupled_folds=False)
+        want, log, got = _run_both(oracle, names, seqs, bp, t_max=t_max, force_iters=1)
         assert got.output == want, t_max
-        assert [int(x) for x in it] == [t_max] * (len(seqs) - 1)
-        assert sorted(v[0] for v in got.dd_log.values()) == sorted(int(x) for x in it)
-        assert sorted(v[1] for v in got.dd_log.values()) == sorted(int(x) for x in vi)
+        assert [v[0] for v in log[0].values()] == [t_max] * (len(seqs) - 1)
+        _same_nodes(got, log)
 
 
 # ---- the dense decoder classes (SURVEY 8 row f4): Nussinov, NeedlemanWunsch ----

@@ -152,12 +152,25 @@ def test_pairs_equal_the_oracle(oracle):
     names, seqs = _mixed()
     pairs = [(0, 1), (3, 4), (8, 9)]
     pw = pipeline.pairwise(names, seqs, pairs=pairs)
+    # the solver as the reference runs it: with skip_uncoupled_folds (the default) a pair without consensus base pairs keeps
+    # the oracle's text but not its iteration count and score (dafs_dd_params)
+    full = pipeline.pairwise(names, seqs, pairs=pairs, skip_uncoupled_folds=False)
+    coupled = 0
     for k, (x, y) in enumerate(pairs):
         pl = oracle.pipeline([names[x], names[y]], [seqs[x], seqs[y]], oracle.params(fold_model=0, align_model=0))
         pl.phase1(); pl.phase2()
         want = pl.output()
+        its, viol, ncbp, score = pl.node_log()[2]  # the root: the pair's only node
         pl.close()
         assert pw.results[k].output == want, (x, y)
+        assert full.results[k].output == want, (x, y)
+        # the --pairwise-scores columns are the oracle's: solve_by_dd's return value, by its bytes, and its iteration count
+        for r in [full] + ([pw] if ncbp else []):
+            assert r.score[x, y].tobytes() == r.score[y, x].tobytes() == np.float32(score).tobytes(), (x, y, r.score[x, y], score)
+            assert r.iterations[x, y] == r.iterations[y, x] == its, (x, y)
+            assert r.results[k].dd_log[2][:3] == (its, viol, ncbp), (x, y)
+        coupled += ncbp > 0
+    assert coupled >= 1
 
 
 def _cli(*args):
