@@ -6,7 +6,9 @@
 //   sweep 3: p = post(slab value); threshold (wrapper >= th, adapter > th: reference
 //            src/align.cpp:69-78); similarity-score DP (src/dafs.cpp:713-764); entry counts per
 //            row (carried lane to lane with the row) and per column (registers)
-//   sweep 4: scatter into the CSR of mp[x][y] and of mp[y][x] (src/dafs.cpp:155-167)
+//   sweep 4: the CSR of mp[x][y] and of mp[y][x] (src/dafs.cpp:155-167), staged in LDS a window of positions at a
+//            time and copied out coalesced (k_pairhmm3), or scattered entry by entry (k_pairhmm5, and the
+//            plane-and-rescan fallback of both)
 //
 // Column ownership.  A kernel instance is compiled for W columns per lane, but a wavefront whose
 // pairs are short enough runs the W-1 instantiation of every sweep (lane t owns columns
@@ -74,17 +76,21 @@ __device__ __forceinline__ int pair_width(int L2) {
 // issues in every step and the range check drops for the lanes without a record: no branch), and sweep 4 walks the
 // lists four records at a time, rebuilding an entry's position in its row from the carried count plus the mask's lower
 // bits and its position in its column from a running position per column -- a third less HBM traffic for the whole
-// kernel, and one list step per lane-step with entries instead of ~190 grid steps.  A lane whose list is full (entries in most of
-// its steps: th near 0) makes the call return false with nothing emitted and the slab untouched; the caller then runs
-// the dense = true instantiation, which is the plane-and-rescan form.
+// kernel, and one list step per lane-step with entries instead of ~190 grid steps.  The positions index a window of
+// the pair's pool region staged in LDS (`stage`, E positions; the launch derives E: pair_emit_window below).  A lane
+// whose list is full (entries in most of its steps: th near 0) makes the call return false with nothing emitted and
+// the slab untouched; the caller then runs the dense = true instantiation, which is the plane-and-rescan form.
 template <int WR>
 struct pair_rec {
   static constexpr int Q = (2 + WR + 3) / 4;  // 16-byte words per record
   static constexpr int D = 4 * Q;             // dwords per record (a lane's list holds list_cap / D records)
 };
-template <int G, int W, int WR, bool dense, class Args, class Post>
+// staged: sweep 4 of the sparse form goes through windows staged in LDS (`stage`, E positions; k_pairhmm3) or scatters
+// every entry from its lane (k_pairhmm5, which passes no stage).
+template <int G, int W, int WR, bool dense, bool staged, class Args, class Post>
 __device__ __forceinline__ bool pair_finish(const Args& a, float* __restrict__ slab, float* __restrict__ list, int list_cap, uint32_t* __restrict__ s_rowptr,
-                                            int lane, int t, int g, int L1, int L2, int nsteps, bool act, uint32_t task, float th, Post post) {
+                                            uint2* __restrict__ stage, int E, int lane, int t, int g, int L1, int L2, int nsteps, bool act, uint32_t task,
+                                            float th, Post post) {
   const int tlast = (L2 >= 0 ? L2 : 0) / WR;  // lane (within the group) that owns column L2
   const int j0 = t * WR;
   // The wave's list plane as a buffer.  Sweep 3: the record stores of a step are issued by every lane, and a lane without
@@ -276,60 +282,176 @@ __device__ __forceinline__ bool pair_finish(const Args& a, float* __restrict__ s
   // ------------------------------------------------------------------ sweep 4: emit CSR + transposed CSR
   if (!dense) {
     if (__any(ok)) {
-      int maxrec = slab_nrec;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) maxrec = max(maxrec, __shfl_xor(maxrec, o));
-      maxrec = __builtin_amdgcn_readfirstlane(maxrec);
+      // A pair's pool region is one position space of 2 nnz slots, the row-CSR entries at [0, nnz) and the transposed
+      // ones at [nnz, 2 nnz), the same position in ent_col and ent_val.  Both forms walk the lanes' lists K records at a
+      // time (fetch: a lane beyond its n records reads outside the buffer).
       constexpr int Q = pair_rec<WR>::Q;
-      uint32_t colpos[WR];  // where the next entry of this lane's column c goes in the pair's transposed half
-#pragma unroll
-      for (int c = 0; c < WR; ++c) colpos[c] = nnz + (uint32_t)colbase[c];
-      // The scatter stores sit behind per-entry branches, which the compiler cannot count: a wait for a record's load
-      // is a wait for every store issued before it.  Records are therefore fetched K at a time and all K have arrived
-      // before the turn's first store (the empty asm uses them): one wait per K records, for the turn's loads and the
-      // stores of the turn before together, instead of one round trip per record.
-      constexpr int K = 4;
+      constexpr int K = 4;  // records per turn, all arrived before the turn's first use (one wait per K records)
       int jm1 = j0 - 1;  // column numbers from one register: WR constants of the lane would be kept (spilled) kernel-wide
       asm volatile("" : "+v"(jm1));
       u32x4 cur[K][Q];
-      auto fetch = [&](u32x4 (&r)[K][Q], const int k0) __attribute__((always_inline)) {
+      auto fetch = [&](u32x4 (&r)[K][Q], const int k0, const int n) __attribute__((always_inline)) {
 #pragma unroll
         for (int kk = 0; kk < K; ++kk) {
-          const uint32_t ro = (k0 + kk < slab_nrec) ? (uint32_t)(((uint32_t)(k0 + kk) * Q * 64 + lane) * 16) : NO_RECORD;
+          const uint32_t ro = (k0 + kk < n) ? (uint32_t)(((uint32_t)(k0 + kk) * Q * 64 + lane) * 16) : NO_RECORD;
 #pragma unroll
           for (int q = 0; q < Q; ++q) r[kk][q] = __builtin_amdgcn_raw_buffer_load_b128(list_rs, (int)(ro + q * 1024), 0, 0);
         }
-      };
-      for (int k0 = 0; k0 < maxrec; k0 += K) {
-        fetch(cur, k0);
 #pragma unroll
         for (int kk = 0; kk < K; ++kk)
 #pragma unroll
-          for (int q = 0; q < Q; ++q) asm volatile("" : "+v"(cur[kk][q]));
+          for (int q = 0; q < Q; ++q) asm volatile("" : "+v"(r[kk][q]));
+      };
+      if constexpr (!staged) {
+        // Scattered form: every entry is four 4-byte stores from its lane, behind a per-entry branch (the pool is
+        // addressed with 64 bits).  The compiler cannot count stores behind branches, so all K records of a turn have
+        // arrived before the turn's first store: one wait per K records.
+        int maxrec = slab_nrec;
 #pragma unroll
-        for (int kk = 0; kk < K; ++kk) {
-          uint32_t w[4 * Q];
+        for (int o = 1; o < 64; o <<= 1) maxrec = max(maxrec, __shfl_xor(maxrec, o));
+        maxrec = __builtin_amdgcn_readfirstlane(maxrec);
+        uint32_t colpos[WR];  // where the next entry of this lane's column c goes in the pair's transposed half
 #pragma unroll
-          for (int q = 0; q < Q; ++q) { w[4 * q] = cur[kk][q].x; w[4 * q + 1] = cur[kk][q].y; w[4 * q + 2] = cur[kk][q].z; w[4 * q + 3] = cur[kk][q].w; }
-          const uint32_t m = w[0];  // 0 beyond the lane's last record
-          const int im1 = (int)w[1] & 0xFFFF;
-          const uint32_t rowpos = s_rowptr[im1] + (uint32_t)((int)w[1] >> 16);  // the row's first entry of this lane
-          int before = 0;  // entries of the record left of cell c
+        for (int c = 0; c < WR; ++c) colpos[c] = nnz + (uint32_t)colbase[c];
+        for (int k0 = 0; k0 < maxrec; k0 += K) {
+          fetch(cur, k0, slab_nrec);
 #pragma unroll
-          for (int c = 0; c < WR; ++c) {
-            const int e = (int)((m >> c) & 1u);
-            if (e && ok) {
-              const float p = __uint_as_float(w[2 + c]);
-              const unsigned long long pos = off + rowpos + (uint32_t)before;
-              a.ent_col[pos] = (uint32_t)(jm1 + c);
-              a.ent_val[pos] = p;
-              const unsigned long long tpos = off + colpos[c];
-              a.ent_col[tpos] = (uint32_t)im1;
-              a.ent_val[tpos] = p;
+          for (int kk = 0; kk < K; ++kk) {
+            uint32_t w[4 * Q];
+#pragma unroll
+            for (int q = 0; q < Q; ++q) { w[4 * q] = cur[kk][q].x; w[4 * q + 1] = cur[kk][q].y; w[4 * q + 2] = cur[kk][q].z; w[4 * q + 3] = cur[kk][q].w; }
+            const uint32_t m = w[0];  // 0 beyond the lane's last record
+            const int im1 = (int)w[1] & 0xFFFF;
+            const uint32_t rowpos = s_rowptr[im1] + (uint32_t)((int)w[1] >> 16);  // the row's first entry of this lane
+            int before = 0;  // entries of the record left of cell c
+#pragma unroll
+            for (int c = 0; c < WR; ++c) {
+              const int e = (int)((m >> c) & 1u);
+              if (e && ok) {
+                const float p = __uint_as_float(w[2 + c]);
+                const unsigned long long pos = off + rowpos + (uint32_t)before;
+                a.ent_col[pos] = (uint32_t)(jm1 + c);
+                a.ent_val[pos] = p;
+                const unsigned long long tpos = off + colpos[c];
+                a.ent_col[tpos] = (uint32_t)im1;
+                a.ent_val[tpos] = p;
+              }
+              before += e;
+              colpos[c] += (uint32_t)e;
             }
-            before += e;
-            colpos[c] += (uint32_t)e;
           }
+        }
+      } else {
+        // Staged form: the region is produced window by window.  E consecutive positions are staged as {col, val} in the
+        // group's own piece of LDS (`stage`) and then copied out with lane t writing positions t, t + G, ..., so that a
+        // store instruction covers 4 G contiguous bytes per group instead of one scattered 4-byte request per lane.  The
+        // window start w0 is the same for every group of the wave (each group counts in its own pair's positions); a
+        // group whose pair has ended takes no part.  Every cell of a fetched record writes one slot, without a branch:
+        // its position where it is an entry inside the window, and the lane's spare slot behind the window
+        // (stage[E + t]) otherwise.  No workgroup barrier (the wavefronts of a workgroup take different numbers of
+        // pairs): the stage is private to the wavefront, and DS operations of a wave execute in order.
+        const uint32_t uE = (uint32_t)E;
+        const uint32_t spare = uE + (uint32_t)t;
+        const int nrec = ok ? slab_nrec : 0;
+        const uint32_t npos = ok ? 2u * nnz : 0u;
+        uint32_t maxpos = npos;
+#pragma unroll
+        for (int o = G; o < 64; o <<= 1) maxpos = max(maxpos, (uint32_t)__shfl_xor((int)maxpos, o));
+        maxpos = __builtin_amdgcn_readfirstlane(maxpos);
+        // this lane's columns occupy [tlo, thi) of the transposed half: lanes own ascending column ranges
+        const uint32_t tlo = nnz + (uint32_t)colbase[0], thi = nnz + (uint32_t)(colbase[WR - 1] + colcnt[WR - 1]);
+        int cursor = 0;  // row half: this lane's first record with an entry at or behind the window start
+        for (uint32_t w0 = 0; w0 < maxpos; w0 += uE) {
+          const uint32_t wend = w0 + uE;
+          // Row half.  A lane's records are in row order, so their positions ascend: the lane resumes at its cursor and
+          // stops at the first record that reaches beyond the window.  That record stays under the cursor (its entries
+          // in front of the next window fall outside it then); the records wholly inside are passed.
+          bool going = cursor < nrec;
+          while (__any(going)) {
+            fetch(cur, cursor, going ? nrec : 0);
+            int adv = 0;
+            bool stop = false;
+#pragma unroll
+            for (int kk = 0; kk < K; ++kk) {
+              uint32_t w[4 * Q];
+#pragma unroll
+              for (int q = 0; q < Q; ++q) { w[4 * q] = cur[kk][q].x; w[4 * q + 1] = cur[kk][q].y; w[4 * q + 2] = cur[kk][q].z; w[4 * q + 3] = cur[kk][q].w; }
+              const uint32_t m = w[0];  // 0 beyond the lane's last record
+              const int im1 = (int)w[1] & 0xFFFF;
+              const uint32_t rowpos = s_rowptr[im1] + (uint32_t)((int)w[1] >> 16);  // the row's first entry of this lane
+              uint32_t before = 0;  // entries of the record left of cell c
+#pragma unroll
+              for (int c = 0; c < WR; ++c) {
+                const uint32_t e = (m >> c) & 1u;
+                const uint32_t rel = rowpos + before - w0;  // in front of the window: wraps to a large number
+                stage[(e != 0 && rel < uE) ? rel : spare] = make_uint2((uint32_t)(jm1 + c), w[2 + c]);
+                before += e;
+              }
+              const bool have = going && cursor + kk < nrec;  // by the index, so that every turn passes a record or stops
+              const bool whole = have && rowpos + before <= wend;
+              adv += whole ? 1 : 0;
+              stop = stop || (have && !whole);
+            }
+            cursor += adv;
+            going = going && !stop && cursor < nrec;
+          }
+          // Transposed half.  The window covers a contiguous range of columns, so only the lanes whose [tlo, thi) meets it
+          // walk their lists; the others give the offset outside the buffer and cause no traffic.  A lane that takes
+          // part walks its WHOLE list, so its running column positions start from the column bases in every window
+          // it takes part in and have advanced past every earlier row when an entry of the window comes up.
+          const bool part = nrec > 0 && wend > nnz && tlo < wend && thi > w0;
+          int kmax = part ? nrec : 0;
+#pragma unroll
+          for (int o = 1; o < 64; o <<= 1) kmax = max(kmax, __shfl_xor(kmax, o));
+          kmax = __builtin_amdgcn_readfirstlane(kmax);
+          if (kmax > 0) {
+            uint32_t colpos[WR];  // where the next entry of this lane's column c goes
+#pragma unroll
+            for (int c = 0; c < WR; ++c) colpos[c] = nnz + (uint32_t)colbase[c];
+            for (int k0 = 0; k0 < kmax; k0 += K) {
+              fetch(cur, k0, part ? nrec : 0);
+#pragma unroll
+              for (int kk = 0; kk < K; ++kk) {
+                uint32_t w[4 * Q];
+#pragma unroll
+                for (int q = 0; q < Q; ++q) { w[4 * q] = cur[kk][q].x; w[4 * q + 1] = cur[kk][q].y; w[4 * q + 2] = cur[kk][q].z; w[4 * q + 3] = cur[kk][q].w; }
+                const uint32_t m = w[0];
+                const uint32_t im1 = w[1] & 0xFFFFu;
+#pragma unroll
+                for (int c = 0; c < WR; ++c) {
+                  const uint32_t e = (m >> c) & 1u;
+                  const uint32_t rel = colpos[c] - w0;
+                  stage[(e != 0 && rel < uE) ? rel : spare] = make_uint2(im1, w[2 + c]);
+                  colpos[c] += e;
+                }
+              }
+            }
+          }
+          wave_lds_fence();
+          // Copy out [w0, min(w0 + E, 2 nnz)): every position of that range has been written exactly once.
+          const uint32_t n = min(uE, npos - min(npos, w0));  // 0 for a group whose pair has ended
+          const uint32_t nmax = min(uE, maxpos - w0);
+          uint32_t* __restrict__ out_col = a.ent_col + off + w0;
+          float* __restrict__ out_val = a.ent_val + off + w0;
+          // four runs per turn, their LDS reads together in front of the stores (a slot behind the window's end is read
+          // from the first spare slot and not stored).  The lane number is taken afresh from one register here: hoisted
+          // out of the loop over pairs, the lane's copy-out addresses would be kept, spilled, for the whole kernel.
+          uint32_t tt = (uint32_t)t;
+          asm volatile("" : "+v"(tt));
+          for (uint32_t p0 = 0; p0 < nmax; p0 += 4 * G) {
+            uint2 cv[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) cv[u] = stage[min(p0 + (uint32_t)(u * G) + tt, uE)];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+              const uint32_t p = p0 + (uint32_t)(u * G) + tt;
+              if (p < n) {
+                out_col[p] = cv[u].x;
+                out_val[p] = __uint_as_float(cv[u].y);
+              }
+            }
+          }
+          wave_lds_fence();  // the next window overwrites the stage
         }
       }
     }
@@ -380,13 +502,55 @@ struct pair_variant {
   const void* fn;   // kernel entry (hipFuncGetAttributes / launch)
   int vgprs;        // registers per lane of the code object (0 until queried)
   int occ;          // wavefronts per SIMD the instance was compiled for (__launch_bounds__): stands in without a device
+  int lds_static;   // bytes of static LDS of the code object (queried with vgprs)
+  bool optin[16];   // lds_optin_once flags
 };
+
+// registers and static LDS from the code object, once per instance
+inline void pair_query(pair_variant& v) {
+  if (v.vgprs != 0) return;
+  hipFuncAttributes at;
+  if (hipFuncGetAttributes(&at, v.fn) == hipSuccess && at.numRegs > 0) {
+    v.vgprs = at.numRegs;
+    v.lds_static = (int)at.sharedSizeBytes;
+  } else {
+    (void)hipGetLastError();
+    v.vgprs = 512 / v.occ / 8 * 8;
+    v.lds_static = 4096;
+  }
+}
 
 // waves per SIMD the register file allows (MI355X_MICROARCH.md, register files: 512 per lane per SIMD, granule 8)
 inline int pair_occupancy(int vgprs) {
   const int alloc = (vgprs + 7) / 8 * 8;
   const int w = 512 / (alloc < 64 ? 64 : alloc);
   return w < 1 ? 1 : w;
+}
+
+// Sweep 4's staging window (pair_finish): E positions of 8 bytes per (wavefront, group), plus one spare slot per lane.
+// E is what the LDS of a CU leaves when as many workgroups are resident as the registers allow: 160 KiB / workgroups
+// per CU (one wavefront of a workgroup per SIMD, so that is the instance's wavefronts per SIMD), at most the 64 KiB a
+// workgroup gets without opting in, minus the row pointers, the static tables, the spare slots and one allocation
+// granule of slack, / (4 wavefronts x 64/G groups x 8 bytes), rounded down to a multiple of G: the window never costs
+// a resident wavefront.  Where the row pointers leave less than one window of G positions, E = G and the launch opts
+// in to the larger allocation.  DAFS_HIP_EMIT_WINDOW=<positions> (tests and tuning) forces a smaller E: rounded up to
+// a multiple of G, capped by the derived one.  Returns the dynamic LDS of the launch in *lds_bytes.
+inline uint32_t pair_emit_window(pair_variant& v, size_t rowptr_bytes, size_t* lds_bytes) {
+  pair_query(v);
+  const long per_wg = (160L * 1024) / pair_occupancy(v.vgprs);
+  const long spare = 4L * 64 * 8;  // 4 wavefronts x (64/G groups x G lanes) x 8 bytes
+  const long left = (per_wg < 64L * 1024 ? per_wg : 64L * 1024) - 1536 - (long)v.lds_static - (long)rowptr_bytes - spare;
+  const long per_pos = 4L * (64 / v.G) * 8;
+  long e = left > 0 ? left / per_pos / v.G * v.G : 0;
+  if (e < v.G) e = v.G;
+  const char* s = getenv("DAFS_HIP_EMIT_WINDOW");
+  const long f = s ? atol(s) : 0;
+  if (f > 0) {
+    const long fr = (f + v.G - 1) / v.G * v.G;
+    if (fr < e) e = fr;
+  }
+  *lds_bytes = rowptr_bytes + (size_t)(e * per_pos + spare);
+  return (uint32_t)e;
 }
 
 // Picks (G, W) and the number of persistent wavefronts.  The model, fitted to runs of the ProbCons kernel on MI355X
@@ -418,11 +582,7 @@ inline int pair_choose(pair_variant* vs, int nv, uint32_t ntasks, uint32_t max_l
     if ((uint64_t)v.G * v.W < (uint64_t)max_len2 + 1) continue;
     if (force_g && v.G != force_g) continue;
     if (force_w && v.W != force_w) continue;
-    if (v.vgprs == 0) {
-      hipFuncAttributes at;
-      if (hipFuncGetAttributes(&at, v.fn) == hipSuccess && at.numRegs > 0) v.vgprs = at.numRegs;
-      else { (void)hipGetLastError(); v.vgprs = 512 / v.occ / 8 * 8; }
-    }
+    pair_query(v);
     int occ = pair_occupancy(v.vgprs);
     if (cap_occ > 0 && occ > cap_occ) occ = cap_occ;
     const uint64_t waves = ((uint64_t)ntasks + (64 / v.G) - 1) / (64 / v.G);

@@ -17,7 +17,7 @@
 //   3 posterior : P = EXP(min(0,S-total)) thresholded, written in place; the same sweep runs the
 //                 similarity-score DP and counts entries per row (count travels with the row
 //                 from lane to lane) and per column (registers)
-//   4 emit      : scatters the entries into the CSR of mp[x][y] and of mp[y][x]
+//   4 emit      : the entries into the CSR of mp[x][y] and of mp[y][x], through windows staged in LDS
 // The slab is indexed [(step*W + c)*64 + lane], so every slab access of a wave instruction is one
 // contiguous 256-byte segment, in all four sweeps (the backward sweep visits forward step
 // L1+G-1-s, the same for every lane).  Work is handed out by a device-side counter, longest
@@ -39,7 +39,7 @@ namespace dafs {
 // One pair per group of G lanes, all four sweeps, for the compile-time column count WR (W or W-1).
 template <int G, int W, int WR>
 __device__ __forceinline__ void pairhmm3_pair(const dafs_pairhmm3_args& a, const pc_tables* tab, const float* s_match, const float* s_ins, const float2* s_mi,
-                                              float* __restrict__ slab, float* __restrict__ list, int list_cap, uint32_t* __restrict__ s_rowptr, int lane, int t, int g,
+                                              float* __restrict__ slab, float* __restrict__ list, int list_cap, uint32_t* __restrict__ s_rowptr, uint2* __restrict__ s_stage, int E, int lane, int t, int g,
                                               int L1, int L2, int nsteps, bool act, uint32_t task,
                                               const uint8_t* __restrict__ s1, const uint8_t* __restrict__ s2) {
   // everything below lives in the 32x domain of pc_log_add_n (pc_math.h): the launch scaled the model tables
@@ -306,17 +306,17 @@ __device__ __forceinline__ void pairhmm3_pair(const dafs_pairhmm3_args& a, const
   };
   // sparse outputs through per-lane entry lists (pair_sweeps.h); with th near 0 (dense outputs), or when a list
   // is full, the plane-and-rescan form
-  if (a.th < 0.002f || !pair_finish<G, W, WR, false>(a, slab, list, list_cap, s_rowptr, lane, t, g, L1, L2, nsteps, act, task, a.th, post))
-    (void)pair_finish<G, W, WR, true>(a, slab, list, list_cap, s_rowptr, lane, t, g, L1, L2, nsteps, act, task, a.th, post);
+  if (a.th < 0.002f || !pair_finish<G, W, WR, false, true>(a, slab, list, list_cap, s_rowptr, s_stage, E, lane, t, g, L1, L2, nsteps, act, task, a.th, post))
+    (void)pair_finish<G, W, WR, true, true>(a, slab, list, list_cap, s_rowptr, s_stage, E, lane, t, g, L1, L2, nsteps, act, task, a.th, post);
 }
 
 // OCC = wavefronts per SIMD the register allocation must leave room for (the planner reads the result back
 // from the code object).  Resident wavefronts are what keeps the vector pipe busy between the lookups of the
 // log-sum-exps: 2 per SIMD reach a third of its issue rate.
 template <int G, int W, int OCC>
-__global__ __launch_bounds__(256, OCC) void k_pairhmm3(dafs_pairhmm3_args a, uint32_t slab_steps, uint32_t rp_cap) {
+__global__ __launch_bounds__(256, OCC) void k_pairhmm3(dafs_pairhmm3_args a, uint32_t slab_steps, uint32_t rp_cap, uint32_t emit_e) {
   constexpr int NG = 64 / G;  // pairs per wavefront
-  extern __shared__ uint32_t s_dyn[];  // per (wave, group): rp_cap row pointers
+  extern __shared__ __attribute__((aligned(16))) uint32_t s_dyn[];  // per (wave, group): rp_cap row pointers, then sweep 4's staging windows
   __shared__ float s_match[56];
   __shared__ float s_ins[8];
   __shared__ float2 s_mi[56];
@@ -342,6 +342,8 @@ __global__ __launch_bounds__(256, OCC) void k_pairhmm3(dafs_pairhmm3_args a, uin
   float* __restrict__ list = slab + plane;
   const int list_cap = (int)(slab_steps * W);
   uint32_t* __restrict__ s_rowptr = s_dyn + (size_t)(wave_in_wg * NG + g) * rp_cap;
+  // behind the row pointers: sweep 4's staging window of this (wave, group), emit_e positions + one spare slot per lane
+  uint2* __restrict__ s_stage = (uint2*)(s_dyn + (size_t)4 * NG * rp_cap) + (size_t)(wave_in_wg * NG + g) * (emit_e + G);
 
   for (;;) {
     uint32_t base = 0;
@@ -364,9 +366,9 @@ __global__ __launch_bounds__(256, OCC) void k_pairhmm3(dafs_pairhmm3_args a, uin
     // columns per lane of this wave: W, or W-1 when its pairs fit (pair_sweeps.h)
     // columns per lane of this wave: W, or W-1 when its pairs fit (pair_sweeps.h)
     if (pair_width<G, W>(L2) == W)
-      pairhmm3_pair<G, W, W>(a, &s_tab, s_match, s_ins, s_mi, slab, list, list_cap, s_rowptr, lane, t, g, L1, L2, nsteps, act, task, s1, s2);
+      pairhmm3_pair<G, W, W>(a, &s_tab, s_match, s_ins, s_mi, slab, list, list_cap, s_rowptr, s_stage, (int)emit_e, lane, t, g, L1, L2, nsteps, act, task, s1, s2);
     else
-      pairhmm3_pair<G, W, (W > 1 ? W - 1 : 1)>(a, &s_tab, s_match, s_ins, s_mi, slab, list, list_cap, s_rowptr, lane, t, g, L1, L2, nsteps, act, task, s1, s2);
+      pairhmm3_pair<G, W, (W > 1 ? W - 1 : 1)>(a, &s_tab, s_match, s_ins, s_mi, slab, list, list_cap, s_rowptr, s_stage, (int)emit_e, lane, t, g, L1, L2, nsteps, act, task, s1, s2);
   }
 }
 
@@ -398,13 +400,17 @@ extern "C" int dafs_hipk_pairhmm_plan(uint32_t ntasks, uint32_t max_len1, uint32
 extern "C" int dafs_hipk_pairhmm3_launch(const dafs_pairhmm3_args* args, const dafs_pairhmm_plan* plan, void* hip_stream) {
   if (!args || !plan) return DAFS_HIP_EINVAL;
   if (args->ntasks == 0) return DAFS_HIP_OK;
-  const pair_variant* v = nullptr;
-  for (const pair_variant& c : k_variants)
+  pair_variant* v = nullptr;
+  for (pair_variant& c : k_variants)
     if (c.G == (int)plan->group && c.W == (int)plan->width) v = &c;
   if (!v || plan->nwaves % 4) return DAFS_HIP_EINVAL;
   const uint32_t rp_cap = plan->slab_steps - plan->group + 1;  // max_len1 + 1 row pointers
-  const size_t lds = (size_t)4 * (64 / v->G) * rp_cap * sizeof(uint32_t);
-  if (lds > 60 * 1024) return DAFS_HIP_ETOOLONG;
+  const size_t rp_lds = (size_t)4 * (64 / v->G) * rp_cap * sizeof(uint32_t);
+  if (rp_lds > 60 * 1024) return DAFS_HIP_ETOOLONG;
+  // sweep 4's staging window behind the row pointers (pair_sweeps.h); above the default only where the row pointers force it
+  size_t lds = 0;
+  uint32_t emit_e = pair_emit_window(*v, rp_lds, &lds);
+  if (lds + (size_t)v->lds_static > 64 * 1024 && !lds_optin_once(v->fn, 160 * 1024 - v->lds_static, v->optin)) return DAFS_HIP_ELAUNCH;
   dafs_pairhmm3_args a = *args;
   // the kernel works on log-probabilities scaled by 32 (pc_math.h, pc_log_add_n): exact, and undone before EXP
   {
@@ -412,7 +418,7 @@ extern "C" int dafs_hipk_pairhmm3_launch(const dafs_pairhmm3_args* args, const d
     for (size_t k = 0; k < sizeof a.model / sizeof(float); ++k) f[k] *= 32.0f;
   }
   uint32_t steps = plan->slab_steps, cap = rp_cap;
-  void* params[] = {&a, &steps, &cap};
+  void* params[] = {&a, &steps, &cap, &emit_e};
   hipError_t launch_err = hipSuccess;
   STAGE_LAUNCH(dafs::ST_PAIRHMM3, (hipStream_t)hip_stream) launch_err = hipLaunchKernel(v->fn, dim3(plan->nwaves / 4), dim3(256), params, lds, (hipStream_t)hip_stream);
   if (hip_check(launch_err)) return DAFS_HIP_ELAUNCH;
