@@ -87,6 +87,12 @@ _mp_fetch = _sig("dafs_hip_mp_fetch", C.c_int, [C.c_void_p, C.c_int] + [C.c_void
 _get_sim = _sig("dafs_hip_get_sim", C.c_int, [C.c_void_p, C.c_void_p])
 _similarity = _sig("dafs_hip_similarity", C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_uint64, C.POINTER(C.c_uint64)])
 _similarity_ranges = _sig("dafs_host_similarity_ranges", C.c_int, [C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)])
+_structure_scores = _sig("dafs_hip_structure_scores", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])
+_similarity_scored = _sig("dafs_hip_similarity_scored", C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_uint64, C.c_int, C.c_float, C.POINTER(C.c_uint64)])
+_get_pair_scores = _sig("dafs_hip_get_pair_scores", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p])
+structure_score = _sig("dafs_host_structure_score", C.c_float, [C.c_uint64, C.c_uint64, C.c_uint64])
+mix_score = _sig("dafs_host_mix_score", C.c_float, [C.c_float, C.c_float, C.c_float])
+SCORES = ("sequence", "structure", "mix")  # --cluster-score; the index is the library's DAFS_SCORE_* code
 _set_bp = _sig("dafs_hip_set_bp", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])
 _bp_result_size = _sig("dafs_hip_bp_result_size", C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)])
 _bp_fetch = _sig("dafs_hip_bp_fetch", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p])
@@ -576,14 +582,43 @@ class Context:
             o += n * n
         return out
 
-    def similarity(self, model=ALIGN_PROBCONS, th=0.01, max_bytes=None):
+    def similarity(self, model=ALIGN_PROBCONS, th=0.01, max_bytes=None, score="sequence", structure_weight=0.5):
         """dafs_hip_similarity: the N x N similarity matrix of a one-family context of any size, the pairs computed in ranges
         under max_bytes of estimated device memory (None: the library's budget; similarity_ranges gives the ranges).  Returns
         (sim, n_ranges); sim is what sim() returns after a full-pair-set align_posteriors, bit for bit.  The matching stores
-        are invalid afterwards, whatever the number of ranges."""
+        are invalid afterwards, whatever the number of ranges.
+
+        score "structure" or "mix" (dafs_hip_similarity_scored): the matrix returned, and left for
+        sim() and linkage_tree(), is the structural pair score or its mix with the sequence score at structure_weight (read
+        with "mix" only).  They need the base-pairing store (fold_posteriors or set_bp after set_sequences), which stays
+        valid; pair_scores() then gives the sequence and the structure matrix.  "sequence" is the call above."""
+        score_check(score, structure_weight if score == "mix" else None)
         n_ranges = C.c_uint64()
-        check(_similarity(self._h, model, th, 0 if max_bytes is None else int(max_bytes), C.byref(n_ranges)))
+        budget = 0 if max_bytes is None else int(max_bytes)
+        if score == "sequence":
+            check(_similarity(self._h, model, th, budget, C.byref(n_ranges)))
+        else:
+            check(_similarity_scored(self._h, model, th, budget, SCORES.index(score), float(structure_weight), C.byref(n_ranges)))
         return self.sim(), n_ranges.value
+
+    def structure_scores(self):
+        """dafs_hip_structure_scores: (T, terms, W) as uint64 arrays, T and terms per pair of the
+        un-relaxed matching store valid now (in the pair order of align_posteriors' result), W per sequence from the
+        un-relaxed base-pairing store.  Stores installed with set_mp / set_bp count like computed ones."""
+        npairs = C.c_uint64()
+        if _align_result_size(self._h, C.byref(npairs), None, None) != 0:
+            npairs.value = 0  # no matching store: the call below refuses with its own message
+        T = np.zeros(npairs.value, np.uint64); terms = np.zeros(npairs.value, np.uint64); W = np.zeros(len(self._lens), np.uint64)
+        check(_structure_scores(self._h, T.ctypes.data, terms.ctypes.data, W.ctypes.data))
+        return T, terms, W
+
+    def pair_scores(self):
+        """dafs_hip_get_pair_scores: (seq, struct), the raw sequence matrix and the structure matrix of the last
+        similarity() with score "structure" or "mix" (N x N float32 each, unit diagonals)"""
+        n = len(self._lens)
+        seq = np.zeros((n, n), np.float32); st = np.zeros((n, n), np.float32)
+        check(_get_pair_scores(self._h, seq.ctypes.data, st.ctypes.data))
+        return seq, st
 
     def linkage_tree(self, rule, sim=None):
         """dafs_hip_linkage_tree: the "single", "complete" or "average" linkage tree of the n x n
@@ -1306,6 +1341,23 @@ def linkage_check(rule, sim=None):
     if not np.isfinite(sim[np.triu_indices(sim.shape[0], 1)]).all():
         raise ValueError("linkage: an entry above the diagonal is not finite")
     return LINKAGES.index(rule), sim
+
+
+def score_check(score, structure_weight=None, who="similarity"):
+    """ValueError for an unknown score, a weight outside [0, 1] and a weight given with a score other than "mix"
+    (structure_weight None: not given)"""
+    if score not in SCORES:
+        raise ValueError("%s: unknown score %r (one of %s)" % (who, score, ", ".join(SCORES)))
+    if structure_weight is None:
+        return
+    if score != "mix":
+        raise ValueError("%s: structure_weight is the weight of score=\"mix\"; it was given with score=%r" % (who, score))
+    try:
+        w = float(structure_weight)
+    except (TypeError, ValueError):
+        w = float("nan")
+    if not 0.0 <= w <= 1.0:
+        raise ValueError("%s: structure_weight must lie in 0 .. 1" % who)
 
 
 def similarity_ranges(lens, max_bytes=None):

@@ -224,6 +224,8 @@ extern "C" int dafs_hip_set_sequences(dafs_hip_ctx* c, uint32_t nseq, const char
   for (int k = 0; k < 2; ++k) { c->mp[k].valid = false; c->bp[k].valid = false; }
   c->cur_mp = c->cur_bp = 0;
   c->sim.clear();
+  c->pair_seq.clear();
+  c->pair_str.clear();
   return DAFS_HIP_OK;
 }
 
@@ -233,6 +235,8 @@ extern "C" int dafs_hip_set_families(dafs_hip_ctx* c, uint32_t nfam, const uint3
   for (int k = 0; k < 2; ++k) { c->mp[k].valid = false; c->bp[k].valid = false; }
   c->cur_mp = c->cur_bp = 0;
   c->sim.clear();
+  c->pair_seq.clear();
+  c->pair_str.clear();
   return c->fam.build(first, nfam, (uint32_t)c->len.size(), c->stream);
 }
 

@@ -155,6 +155,13 @@ extern "C" int dafs_hip_align_posteriors(dafs_hip_ctx* c, int model, float th, u
 // dafs_host_similarity_ranges, each one dafs_hip_align_posteriors launch into the same buffers, its task_sim scattered as
 // store_sim_blocks scatters the whole set's.  The stores are left invalid whatever the number of ranges.
 extern "C" int dafs_hip_similarity(dafs_hip_ctx* c, int model, float th, uint64_t max_bytes, uint64_t* n_ranges_out) {
+  return dafs_similarity_pass(c, model, th, max_bytes, n_ranges_out, nullptr);
+}
+
+// The loop itself, shared with dafs_hip_similarity_scored (capi_structsim.cpp): per_range, when given, scores a range while its rows
+// are the resident store (ctx.h).
+int dafs_similarity_pass(dafs_hip_ctx* c, int model, float th, uint64_t max_bytes, uint64_t* n_ranges_out,
+                         const std::function<int(const mp_store&)>* per_range) {
   if (!c || c->len.size() < 2 || c->fam.nfam() != 1 || !(th >= 0.0f)) return DAFS_HIP_EINVAL;
   if (model != DAFS_ALIGN_PROBCONS && model != DAFS_ALIGN_CONTRALIGN) return DAFS_HIP_EINVAL;
   const uint32_t n = (uint32_t)c->len.size();
@@ -166,6 +173,8 @@ extern "C" int dafs_hip_similarity(dafs_hip_ctx* c, int model, float th, uint64_
   std::vector<float> sim((size_t)n * n, 0.0f), ts;
   for (uint32_t i = 0; i < n; ++i) sim[(size_t)i * n + i] = 1.0f;
   mp_store& st = c->mp[0];
+  c->pair_seq.clear();
+  c->pair_str.clear();
   rc = DAFS_HIP_OK;
   for (uint64_t r = 0, begin = 0; r < nr && !rc; begin = end[r++]) {
     if ((rc = dafs_hip_align_posteriors(c, model, th, begin, end[r]))) break;
@@ -176,6 +185,7 @@ extern "C" int dafs_hip_similarity(dafs_hip_ctx* c, int model, float th, uint64_
       sim[(size_t)st.pair_x[p] * n + st.pair_y[p]] = s;
       sim[(size_t)st.pair_y[p] * n + st.pair_x[p]] = s;
     }
+    if (per_range && (rc = (*per_range)(st))) break;
   }
   st.valid = false;  // the last range's rows, or after a failure nothing: no store of the whole set either way
   c->mp[1].valid = false;

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <algorithm>
+#include <functional>
 #include <iterator>
 #include <map>
 #include <string>
@@ -194,6 +195,9 @@ struct dafs_hip_ctx {
   std::vector<float> sim;
   dafs::dev_buf<float> d_sim;
   dafs::dev_buf<uint32_t> d_pair_x, d_pair_y;
+  // dafs_hip_similarity_scored with a structural kind: the raw sequence matrix and the structure matrix of its last pass
+  // (n x n each; dafs_hip_get_pair_scores), empty otherwise
+  std::vector<float> pair_seq, pair_str;
   dafs::dev_buf<uint2> mp_ident2;  // rows of an identity matrix, {k, 1.0f}
   dafs::dev_buf<uint2> pct_tasks;  // workgroup order of k_pct_rows (pct_task_order)
   dafs::dev_buf<uint32_t> pct_list;  // the output pairs of dafs_hip_consistency_match_pairs
@@ -329,6 +333,11 @@ struct dafs_hip_ctx {
 
 // capi_align.cpp: similarity scores of all pairs from the rows of a store in row-major pair order (host + device sim)
 int dafs_recompute_sim(dafs_hip_ctx* c, dafs::mp_store& st);
+// capi_align.cpp: the range loop of dafs_hip_similarity.  per_range, when given, runs after every range's
+// launch while that range's rows are the un-relaxed store (its n_tasks tasks; valid until the next range); a non-zero return
+// ends the pass with that code.  Every pass empties pair_seq / pair_str first.
+int dafs_similarity_pass(dafs_hip_ctx* c, int model, float th, uint64_t max_bytes, uint64_t* n_ranges_out,
+                         const std::function<int(const dafs::mp_store&)>* per_range);
 // capi_fold.cpp: CONTRAfold posteriors of the context's sequences seq[0..n) under constraint strings ("?.()", one per row),
 // compacted with threshold th into `out`, whose "sequence" index is the row (Fold::Model::calculate(seq, str, bp), fold.cpp:191-207)
 int dafs_fold_rows_constrained(dafs_hip_ctx* c, uint32_t n, const uint32_t* seq, const std::vector<std::string>& cons, float th, dafs::bp_store& out);

@@ -118,6 +118,10 @@ struct Options {
   std::string cluster_tree;           // --cluster-tree OUT
   bool cluster_linkage_given = false;
   int cluster_linkage = 0;            // --cluster-linkage RULE: 0 the guide tree's own rule, else DAFS_LINKAGE_*
+  bool cluster_score_given = false;
+  int cluster_score = DAFS_SCORE_SEQUENCE;  // --cluster-score NAME
+  bool cluster_weight_given = false;
+  float cluster_weight = 0.5f;        // --cluster-structure-weight W
   std::string input;
   std::vector<std::string> inputs;  // every FILE argument; with two or more, one output block per file
 };
@@ -250,6 +254,12 @@ const char* kHelp =
     "                        the whole set; single, complete, average: that linkage of the similarity scores, joined on the\n"
     "                        device (a join scores the largest, the smallest or the size-weighted mean similarity between its\n"
     "                        two clusters).  --cluster-tree writes the tree that was cut\n"
+    "      --cluster-score NAME  With --cluster or --cluster-count: the pair score that is clustered on.  sequence (default): the\n"
+    "                        alignment model's similarity score; structure: the structural pair score, the base-pairing\n"
+    "                        probabilities of both sequences (CONTRAfold, all sequences folded first) matched through the pair's\n"
+    "                        matching probabilities, 0 .. 1; mix: sequence + W * (structure - sequence).  The table and the tree\n"
+    "                        carry the chosen score; it works with every --cluster-linkage\n"
+    "      --cluster-structure-weight W  With --cluster-score mix: the weight W of the structural score, 0 .. 1 (default: 0.5)\n"
     "\n Aligning options:\n"
     "  -a, --align-model arg Alignment model (value=CONTRAlign, ProbCons) (default: ProbCons)\n"
     "  -p, --align-pct arg   Weight of PCT for matching probabilities (default: 0.25)\n"
@@ -297,7 +307,7 @@ Options parse(int argc, char** argv) {
       {"identity-matrix", {0, true}}, {"seed-nearest", {0, false}}, {"seed-nr", {0, true}}, {"describe", {0, true}},
       {"compare", {0, true}}, {"compare-ref", {0, true}}, {"compare-columns", {0, true}}, {"compare-matrix", {0, true}},
       {"cluster", {0, true}}, {"cluster-count", {0, true}}, {"cluster-min-size", {0, true}}, {"cluster-table", {0, true}},
-      {"cluster-tree", {0, true}}, {"cluster-linkage", {0, true}}};
+      {"cluster-tree", {0, true}}, {"cluster-linkage", {0, true}}, {"cluster-score", {0, true}}, {"cluster-structure-weight", {0, true}}};
   std::map<char, std::string> shorts;
   for (const auto& kv : spec)
     if (kv.second.first) shorts[kv.second.first] = kv.first;
@@ -470,6 +480,28 @@ Options parse(int argc, char** argv) {
       o.cluster_linkage = code;
       o.cluster_linkage_given = true;
     }
+    else if (name == "cluster-score") {
+      static const char* const scores[] = {"sequence", "structure", "mix"};  // the index is the library's DAFS_SCORE_* code
+      int code = -1;
+      for (int r = 0; r < 3; ++r)
+        if (value == scores[r]) code = r;
+      if (code < 0) throw "--cluster-score: unknown score '" + value + "' (sequence, structure, mix)";
+      o.cluster_score = code;
+      o.cluster_score_given = true;
+    }
+    else if (name == "cluster-structure-weight") {
+      size_t used = 0;
+      double w = 0.0;
+      try {
+        w = std::stod(value, &used);
+      } catch (const std::exception&) {
+        used = 0;
+      }
+      if (used == 0 || used != value.size() || !std::isfinite(w) || !(w >= 0.0 && w <= 1.0))
+        throw std::string("--cluster-structure-weight needs a weight in 0 .. 1");
+      o.cluster_weight = (float)w;
+      o.cluster_weight_given = true;
+    }
     else if (name == "seed-nearest") o.seed_nearest = true;
     else if (name == "seed-nr") {
       size_t used = 0;
@@ -507,6 +539,7 @@ Options parse(int argc, char** argv) {
     if (o.cluster_min_size_given || !o.cluster_table.empty() || !o.cluster_tree.empty())
       throw std::string("--cluster-min-size, --cluster-table and --cluster-tree need --cluster or --cluster-count");
     if (o.cluster_linkage_given) throw std::string("--cluster-linkage needs --cluster or --cluster-count");
+    if (o.cluster_score_given || o.cluster_weight_given) throw std::string("--cluster-score and --cluster-structure-weight need --cluster or --cluster-count");
   } else {  // the clusters are runs of their own: nothing that reads or writes one run's whole state, and one FILE to cut
     for (const std::string& g : given) {
       const bool other_mode = g.compare(0, 4, "seed") == 0 || g.compare(0, 8, "pairwise") == 0 || g.compare(0, 7, "compare") == 0 ||
@@ -516,6 +549,7 @@ Options parse(int argc, char** argv) {
     }
     if (o.inputs.size() != 1) throw std::string("--cluster needs exactly one input FILE");
   }
+  if (o.cluster_weight_given && o.cluster_score != DAFS_SCORE_MIX) throw std::string("--cluster-structure-weight is the weight of --cluster-score mix");
   if (o.row_structures && o.stockholm.empty()) throw std::string("--row-structures needs --stockholm");
   if ((o.cov_shuffles_given || o.cov_seed_given) && o.covariation.empty()) throw std::string("--cov-shuffles and --cov-seed need --covariation");
   if (o.cov_null_given && o.covariation.empty()) throw std::string("--cov-null needs --covariation");
@@ -2368,8 +2402,13 @@ int run_cluster(const Options& o, int align_model) {
   std::vector<float> sim((size_t)N * N, 1.0f);
   if (N > 1) {
     set_sequences(ctx, fa);
-    check(dafs_hip_similarity(ctx, align_model, o.align_th, 0, nullptr));
-    check(dafs_hip_get_sim(ctx, sim.data()));
+    if (o.cluster_score == DAFS_SCORE_SEQUENCE) {
+      check(dafs_hip_similarity(ctx, align_model, o.align_th, 0, nullptr));
+    } else {  // all sequences folded as phase 1 of a run folds them, then the pass with the scoring launch in it
+      check(dafs_hip_fold_posteriors(ctx, DAFS_FOLD_CONTRAFOLD, kCutoff));
+      check_text(dafs_hip_similarity_scored(ctx, align_model, o.align_th, 0, o.cluster_score, o.cluster_weight, nullptr));
+    }
+    check(dafs_hip_get_sim(ctx, sim.data()));  // the chosen matrix
   }
   std::vector<float> score(2 * N - 1);
   std::vector<int32_t> left(2 * N - 1), right(2 * N - 1);

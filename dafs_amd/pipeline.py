@@ -1342,7 +1342,8 @@ def _tree_line(score, left, right, names):
     return text[len(score) - 1]
 
 
-def cluster(names, seqs, threshold=None, count=None, min_size=1, ctx=None, max_bytes=None, linkage="guide", **opts):
+def cluster(names, seqs, threshold=None, count=None, min_size=1, ctx=None, max_bytes=None, linkage="guide", score="sequence",
+            structure_weight=None, **opts):
     """Cluster a mixed set of sequences into families and align each (`dafs --cluster`).  The N x N
     similarity matrix of the pair kernels (Context.similarity: the pairs in ranges under max_bytes, so that the set's
     posteriors are never held at once), the guide tree of the whole set (capi.build_tree) and its cut (capi.cluster_cut):
@@ -1352,14 +1353,20 @@ def cluster(names, seqs, threshold=None, count=None, min_size=1, ctx=None, max_b
     run(names_c, seqs_c, **opts) gives.  opts: the options of run() except mp / bp / shard / compare.  With w_pct_f the
     clustering still reads the raw scores; -f acts inside each cluster's run.  linkage: "guide" cuts the guide tree
     (capi.build_tree, on the host); "single", "complete" and "average" cut that linkage tree instead, joined on the device from
-    the similarity block the pass has just left there (Context.linkage_tree).
+    the similarity block the pass has just left there (Context.linkage_tree).  score: "sequence" clusters
+    on the pair kernels' similarity score; "structure" and "mix" on the structural pair score or its mix with the sequence
+    score at structure_weight (0 .. 1, None: 0.5; an argument of "mix" alone), for which all sequences are folded first with
+    the call a run's phase 1 makes (Context.fold_posteriors(0.01)).  .sim, the tree, the cut and the
+    table are then those of the chosen matrix; the runs of the clusters are what they are with any score.
 
-    Returns an object with .linkage, .sim, .tree = (score, left, right), .tree_line, .labels (uint32 [N]), .clusters (per cluster the
+    Returns an object with .score, .seq_sim and .struct_sim (the sequence matrix and the structure matrix; .struct_sim is None
+    with score "sequence"), .linkage, .sim, .tree = (score, left, right), .tree_line, .labels (uint32 [N]), .clusters (per cluster the
     indices of its members, ascending; the clusters are numbered by their smallest member), .results (per cluster a Result,
     or None below min_size), .ranges (launches of the similarity pass), .table (the text of --cluster-table) and .seconds
-    (similarity, tree, batch, total)."""
+    (similarity, tree, batch, total; with a structural score also fold)."""
     import math
     import time
+    capi.score_check(score, structure_weight, who="pipeline.cluster")
     for k in ("mp", "bp", "shard"):
         if k in opts:
             raise ValueError("pipeline.cluster: %s is a single-family option (use run)" % k)
@@ -1395,12 +1402,22 @@ def cluster(names, seqs, threshold=None, count=None, min_size=1, ctx=None, max_b
         ctx = capi.Context(0)
     out = Clustering()
     try:
-        t0 = time.perf_counter()
+        t0 = tf = time.perf_counter()
+        out.score = score
         if n == 1:  # no pair: the unit matrix, no launch
             out.sim, out.ranges = np.ones((1, 1), np.float32), 0
-        else:
+            out.seq_sim, out.struct_sim = out.sim, None if score == "sequence" else out.sim.copy()
+        elif score == "sequence":
             ctx.set_sequences(seqs)
             out.sim, out.ranges = ctx.similarity(align_model, th_a, max_bytes)
+            out.seq_sim, out.struct_sim = out.sim, None
+        else:
+            ctx.set_sequences(seqs)
+            ctx.fold_posteriors(0.01)  # what phase 1 of a run folds with
+            tf = time.perf_counter()
+            out.sim, out.ranges = ctx.similarity(align_model, th_a, max_bytes, score=score,
+                                                 structure_weight=0.5 if structure_weight is None else float(structure_weight))
+            out.seq_sim, out.struct_sim = ctx.pair_scores()
         t1 = time.perf_counter()
         out.linkage = linkage
         if linkage == "guide":
@@ -1423,7 +1440,9 @@ def cluster(names, seqs, threshold=None, count=None, min_size=1, ctx=None, max_b
         for c, r in zip(aligned, res):
             out.results[c] = r
         t3 = time.perf_counter()
-        out.seconds = dict(similarity=t1 - t0, tree=t2 - t1, batch=t3 - t2, total=t3 - t0)
+        out.seconds = dict(similarity=t1 - tf, tree=t2 - t1, batch=t3 - t2, total=t3 - t0)
+        if score != "sequence":
+            out.seconds["fold"] = tf - t0
     finally:
         if own:
             ctx.close()

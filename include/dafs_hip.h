@@ -219,6 +219,45 @@ int dafs_hip_similarity(dafs_hip_ctx* ctx, int model, float th, uint64_t max_byt
 int dafs_host_similarity_ranges(uint32_t n, const uint32_t* lens, uint64_t max_bytes, uint64_t* end, uint64_t cap, uint64_t* n_ranges);
 
 /* ------------------------------------------------------------------------------------------
+ * L1: the structural pair score (no counterpart in the reference; the contract, to the bit, in DESIGN.md section 24;
+ * `dafs --cluster-score`, pipeline.cluster(score=...)).  It is the quantity relax_basepairing_probability sums (reference
+ * src/dafs.cpp:349-361) reduced to one scalar per pair and taken on integers, so that no order of summation, lane mapping or
+ * range budget changes a bit.  With c(v) the stored float as a double clamped into [0, 1] (NaN: 0), a base pair (i, j, p) of x,
+ * a base pair (k, l, q) of y, and the entries (k, a) of row i and (l, b) of row j of mp[x][y]:
+ *   term = (uint64) floor(((c(p) * c(q)) * (c(a) * c(b))) * 2^40)      (doubles, this bracketing; only k < l occurs)
+ *   T(x, y) = the sum of the terms, terms(x, y) = their number (zero terms counted)
+ *   W(x) = the sum over the base pairs of x of (uint64) floor(c(p) * 2^40)
+ * ---------------------------------------------------------------------------------------- */
+/* T and terms of every pair of the un-relaxed matching store that is valid now, in the pair order of dafs_hip_align_fetch
+ * (npairs of dafs_hip_align_result_size entries each), and W of every sequence (nseq entries) from the un-relaxed base-pairing
+ * store.  Stores installed with dafs_hip_set_mp / dafs_hip_set_bp count like computed ones.  Any output may be NULL.  Both
+ * stores are left as they are.  DAFS_HIP_EINVAL with a message in dafs_hip_last_error: either store missing, several families,
+ * no sequences.  DAFS_HIP_EOVERFLOW with a message naming the pair: a pair with 2^24 terms or more (below that T < 2^64 and
+ * the sum is exact); nothing is written then. */
+int dafs_hip_structure_scores(dafs_hip_ctx* ctx, uint64_t* T, uint64_t* terms, uint64_t* W);
+/* The two formulas on the host (no device work), the one copy the library, the tests and both drivers use:
+ * (float) min(1.0, (double)T / (double)min(Wx, Wy)), 0.0f when min(Wx, Wy) = 0; and
+ * (float)((double)sim + (double)w * ((double)str - (double)sim)). */
+float dafs_host_structure_score(uint64_t T, uint64_t Wx, uint64_t Wy);
+float dafs_host_mix_score(float sim, float str, float w);
+/* dafs_hip_similarity with a choice of score: the same range loop, and for the structural kinds one launch of the scoring
+ * kernel over each range while its rows are resident (W once per call).  kind DAFS_SCORE_SEQUENCE is dafs_hip_similarity itself
+ * (weight unread, no base-pairing store needed).  DAFS_SCORE_STRUCTURE: struct(x, y) = dafs_host_structure_score(T, W(x), W(y)),
+ * unit diagonal.  DAFS_SCORE_MIX: dafs_host_mix_score(sim, struct, weight) per entry, weight in [0, 1].  The chosen matrix is
+ * left in the context's similarity block, host and device: dafs_hip_get_sim and dafs_hip_linkage_tree with a NULL matrix see
+ * it.  The raw sequence matrix and the structure matrix are kept for dafs_hip_get_pair_scores.  Both matching stores are
+ * invalid afterwards, as after dafs_hip_similarity; the base-pairing store stays valid.  DAFS_HIP_EINVAL with a message,
+ * the context unchanged and usable: an unknown kind, a weight outside [0, 1] (or NaN) with MIX, and for the structural kinds
+ * no valid un-relaxed base-pairing store (dafs_hip_fold_posteriors or dafs_hip_set_bp after dafs_hip_set_sequences), several
+ * families, fewer than two sequences.  DAFS_HIP_EOVERFLOW as dafs_hip_structure_scores; otherwise as dafs_hip_similarity. */
+enum { DAFS_SCORE_SEQUENCE = 0, DAFS_SCORE_STRUCTURE = 1, DAFS_SCORE_MIX = 2 };
+int dafs_hip_similarity_scored(dafs_hip_ctx* ctx, int model, float th, uint64_t max_bytes, int kind, float weight, uint64_t* n_ranges_out);
+/* The two n x n matrices of the last dafs_hip_similarity_scored pass with a structural kind: seq is, bit for bit, what
+ * dafs_hip_similarity leaves in the similarity block, str the structure matrix.  Either may be NULL.  DAFS_HIP_EINVAL with a
+ * message when there was no such pass since dafs_hip_set_sequences (a later dafs_hip_similarity forgets them too). */
+int dafs_hip_get_pair_scores(dafs_hip_ctx* ctx, float* seq, float* str);
+
+/* ------------------------------------------------------------------------------------------
  * L1: base-pairing probabilities.
  * dafs_hip_set_bp replaces AUXFold::calculate (src/fold.cpp:261-278, --fold-aux): the caller
  * supplies BP rows.  rowptr: per sequence len+1 entries relative to that sequence's first entry,
