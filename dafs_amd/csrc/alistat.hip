@@ -9,57 +9,32 @@
 // k_ali_pairs: the transposed problem of k_cov_pairs (cov.hip).  A workgroup of 16 wavefronts takes a tile of 16 rows r x 64
 // rows s; wavefront v owns r = i0 + v, lane l owns s = j0 + l, so a lane owns one row pair and keeps its counters in
 // registers.  The plane words of both row blocks are staged in LDS in chunks of `chunk` words: the s words word-major, so
-// the 32 lanes of a ds_read_b64 group read 64 consecutive banks, the r words a broadcast.
+// the 32 lanes of a ds_read_b64 group read 64 consecutive banks, the r words a broadcast.  What k_boot_dist (nj_boot.hip)
+// shares with this tile is in ali_tile.h: its shape, its place in LDS, the staging and the counts (ALI_TILE_COUNTS); so are
+// the four plane bits of a cell, for k_ali_pack and k_boot_pack.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/dafs_hip.h"
+#include "ali_tile.h"
 #include "alistat.h"
 #include "hip_util.h"
 #include "stage.h"
 
 namespace dafs {
 
-constexpr uint32_t TI = 16, TJ = 64;
-
-__device__ __forceinline__ uint32_t ali_ident_word(const uint64_t* x, const uint64_t* y) {
-  return (uint32_t)__popcll(~(x[ALI_LO] ^ y[ALI_LO]) & ~(x[ALI_HI] ^ y[ALI_HI]) & x[ALI_BASE] & y[ALI_BASE]);
-}
-
 template <int PASS>
-__global__ __launch_bounds__(1024) void k_ali_pairs(ali_args a, uint32_t i_block0) {
-  extern __shared__ uint64_t lds[];  // y[chunk][4][TJ], then x[chunk][4][TI]
-  __shared__ unsigned long long red_i[TI], red_j[TJ];
-  const uint32_t i0 = (i_block0 + blockIdx.x) * TI, j0 = blockIdx.y * TJ;
-  if (PASS != ALI_RED && j0 + TJ - 1 <= i0) return;  // no pair r < s in this tile (the whole workgroup leaves)
+__global__ __launch_bounds__(ALI_TILE_THREADS) void k_ali_pairs(ali_args a, uint32_t i_block0) {
+  extern __shared__ uint64_t lds[];  // ali_tile_shape::lds
+  __shared__ unsigned long long red_i[ALI_TI], red_j[ALI_TJ];
+  const uint32_t i0 = (i_block0 + blockIdx.x) * ALI_TI, j0 = blockIdx.y * ALI_TJ;
+  if (PASS != ALI_RED && !ali_tile_upper(i0, j0)) return;  // the whole workgroup leaves
   const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const uint32_t r = i0 + wv, s = j0 + lane;
-  uint64_t* ly = lds;
-  uint64_t* lx = lds + (size_t)a.chunk * 4 * TJ;
-  if (PASS == ALI_NEAREST && threadIdx.x < TJ) red_j[threadIdx.x] = 0;
+  uint64_t* ly = ali_tile_y(lds);
+  uint64_t* lx = ali_tile_x(lds, a.chunk);
+  if (PASS == ALI_NEAREST && threadIdx.x < ALI_TJ) red_j[threadIdx.x] = 0;
   uint32_t ident = 0, aligned = 0;
-  for (uint32_t w0 = 0; w0 < a.words; w0 += a.chunk) {
-    const uint32_t wc = a.words - w0 < a.chunk ? a.words - w0 : a.chunk;
-    __syncthreads();
-    for (uint32_t t = threadIdx.x; t < wc * 4 * TJ; t += 1024) {
-      const uint32_t row = j0 + (t & (TJ - 1)), pl = t / TJ;  // pl = w * 4 + plane
-      ly[t] = row < a.n ? a.planes[((size_t)w0 * 4 + pl) * a.n + row] : 0ull;
-    }
-    for (uint32_t t = threadIdx.x; t < wc * 4 * TI; t += 1024) {
-      const uint32_t row = i0 + (t & (TI - 1)), pl = t / TI;
-      lx[t] = row < a.n ? a.planes[((size_t)w0 * 4 + pl) * a.n + row] : 0ull;
-    }
-    __syncthreads();
-    for (uint32_t w = 0; w < wc; ++w) {
-      uint64_t x[4], y[4];
-#pragma unroll
-      for (int p = 0; p < 4; ++p) {
-        x[p] = lx[(w * 4 + p) * TI + wv];
-        y[p] = ly[(w * 4 + p) * TJ + lane];
-      }
-      ident += ali_ident_word(x, y);
-      if (PASS == ALI_MATRIX) aligned += (uint32_t)__popcll(x[ALI_RES] & y[ALI_RES]);
-    }
-  }
+  ALI_TILE_COUNTS(a.planes, a.n, a.words, a.chunk, i0, j0, wv, lane, ly, lx, PASS == ALI_MATRIX, ident, aligned);
 
   if (PASS == ALI_MATRIX) {  // both triangles from the upper one; the diagonal is the host's (res and base)
     if (r < s && s < a.n) {
@@ -88,8 +63,8 @@ __global__ __launch_bounds__(1024) void k_ali_pairs(ali_args a, uint32_t i_block
     if (lane == 0) red_i[wv] = kr;
     if (ks) atomicMax(&red_j[lane], ks);
     __syncthreads();
-    if (threadIdx.x < TI && red_i[threadIdx.x]) atomicMax(&a.best[i0 + threadIdx.x], red_i[threadIdx.x]);  // a key came from rows below n only
-    if (threadIdx.x >= 64 && threadIdx.x < 64 + TJ) {
+    if (threadIdx.x < ALI_TI && red_i[threadIdx.x]) atomicMax(&a.best[i0 + threadIdx.x], red_i[threadIdx.x]);  // a key came from rows below n only
+    if (threadIdx.x >= 64 && threadIdx.x < 64 + ALI_TJ) {
       const uint32_t t = threadIdx.x - 64;
       if (red_j[t]) atomicMax(&a.best[j0 + t], red_j[t]);
     }
@@ -119,11 +94,7 @@ __global__ __launch_bounds__(256) void k_ali_pack(const uint8_t* __restrict__ ce
   for (uint32_t b = 0; b < c1; ++b) {
     const uint32_t col = w * 64 + b;
     if (use && !use[col]) continue;
-    const uint64_t v = cell[(size_t)r * len + col];
-    word[ALI_LO] |= (v & 1) << b;
-    word[ALI_HI] |= ((v >> 1) & 1) << b;
-    word[ALI_BASE] |= (uint64_t)(v <= 3 ? 1 : 0) << b;
-    word[ALI_RES] |= (uint64_t)(v <= 4 ? 1 : 0) << b;
+    ali_pack_cell(cell[(size_t)r * len + col], b, word);
   }
 #pragma unroll
   for (int p = 0; p < 4; ++p) planes[((size_t)w * 4 + p) * n + r] = word[p];
@@ -222,17 +193,16 @@ int ali_pack(const uint8_t* cell, const uint8_t* use, uint32_t n, uint32_t len, 
 int ali_pairs(ali_pass pass, const ali_args& a, hipStream_t st) {
   if (a.n < 2 || a.n > kAliMaxRows || !a.words || !a.chunk || a.chunk > kAliMaxChunk) return DAFS_HIP_EINVAL;
   if (!a.band_blocks) return DAFS_HIP_EINVAL;
-  const uint32_t bi = (a.n + TI - 1) / TI, bj = (a.n + TJ - 1) / TJ;  // <= 2^16 x 2^14
-  const size_t lds = (size_t)a.chunk * 4 * (TI + TJ) * sizeof(uint64_t);
+  const ali_tile_shape tile = ali_tile_shape_of(a.n, a.chunk);  // <= 2^16 x 2^14 blocks
   static const int ids[3] = {ST_ALI_MATRIX, ST_ALI_NEAREST, ST_ALI_RED};
   // bands of rows r, so that one launch stays below band_blocks workgroups (2^21 of 1024 threads: under 2^32 work-items)
-  const uint32_t band = a.band_blocks / bj ? a.band_blocks / bj : 1;
-  for (uint32_t i = 0; i < bi; i += band) {
-    const dim3 grid(bi - i < band ? bi - i : band, bj);
+  const uint32_t band = a.band_blocks / tile.bj ? a.band_blocks / tile.bj : 1;
+  for (uint32_t i = 0; i < tile.bi; i += band) {
+    const dim3 grid(tile.bi - i < band ? tile.bi - i : band, tile.bj);
     STAGE_LAUNCH(ids[pass], st) switch (pass) {
-      case ALI_MATRIX: hipLaunchKernelGGL(k_ali_pairs<ALI_MATRIX>, grid, dim3(1024), lds, st, a, i); break;
-      case ALI_NEAREST: hipLaunchKernelGGL(k_ali_pairs<ALI_NEAREST>, grid, dim3(1024), lds, st, a, i); break;
-      default: hipLaunchKernelGGL(k_ali_pairs<ALI_RED>, grid, dim3(1024), lds, st, a, i); break;
+      case ALI_MATRIX: hipLaunchKernelGGL(k_ali_pairs<ALI_MATRIX>, grid, dim3(ALI_TILE_THREADS), tile.lds, st, a, i); break;
+      case ALI_NEAREST: hipLaunchKernelGGL(k_ali_pairs<ALI_NEAREST>, grid, dim3(ALI_TILE_THREADS), tile.lds, st, a, i); break;
+      default: hipLaunchKernelGGL(k_ali_pairs<ALI_RED>, grid, dim3(ALI_TILE_THREADS), tile.lds, st, a, i); break;
     }
     if (hip_check(hipGetLastError())) return DAFS_HIP_ELAUNCH;
   }
@@ -266,3 +236,5 @@ int ali_row_weights(const uint8_t* cell_t, const uint8_t* use, const double* inv
 }
 
 }  // namespace dafs
+
+#undef ALI_TILE_COUNTS

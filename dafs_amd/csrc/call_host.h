@@ -11,6 +11,7 @@
 
 #include "../../include/dafs_hip.h"
 #include "last_error.h"
+#include "mix64.h"  // dafs::mix64, the mix the kernels draw with
 
 namespace dafs {
 
@@ -59,13 +60,6 @@ inline bool structure_ok(const uint32_t* ss, uint32_t L, std::vector<uint8_t>& u
     used[col] = used[p] = 1;
   }
   return true;
-}
-
-// The splitmix64 finaliser of DESIGN.md section 13: the host's copy of the mix the kernels draw with.
-inline uint64_t mix64(uint64_t z) {
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
 }
 
 // DESIGN.md section 22, "Distances from an alignment": the distance of two rows with `mism` differing of `comp` compared

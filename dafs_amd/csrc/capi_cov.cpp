@@ -101,7 +101,7 @@ int input_check(dafs_hip_ctx* c, uint32_t n, uint32_t len, const uint8_t* code) 
 // form at a small n)
 bool evolve_in_lds(uint32_t n) { return !env_off("DAFS_COV_TREE_LDS") && cov_evolve_fits_lds(n); }
 
-uint64_t null_base(uint64_t seed, uint32_t k) { return mix64(seed + 0x9E3779B97F4A7C15ull * ((uint64_t)k + 1)); }
+uint64_t null_base(uint64_t seed, uint32_t k) { return mix64(seed + kMixGolden * ((uint64_t)k + 1)); }
 
 }  // namespace
 

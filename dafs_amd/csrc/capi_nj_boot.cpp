@@ -37,7 +37,7 @@ int heads_verdict(const char* who, const char* what, uint32_t n, uint32_t k0, co
 
 // The matrix of replicate k on the host, from the transposed used columns: the overflow path of the fix-up list.
 void host_replicate_distances(uint32_t n, uint32_t U, const uint8_t* cells, uint64_t seed, uint32_t k, int model, double* dist) {
-  const uint64_t base = mix64(seed + 0x9E3779B97F4A7C15ull * (uint64_t)(k + 1));
+  const uint64_t base = mix64(seed + kMixGolden * (uint64_t)(k + 1));
   std::vector<uint32_t> draw(U);
   for (uint32_t i = 0; i < U; ++i) draw[i] = (uint32_t)(((mix64(base + i) >> 32) * (uint64_t)U) >> 32);
   std::vector<uint8_t> rep((size_t)n * U);  // row-major

@@ -19,17 +19,12 @@
 #include "../../include/dafs_hip.h"
 #include "cov.h"
 #include "hip_util.h"
+#include "mix64.h"
 #include "stage.h"
 
 namespace dafs {
 
 constexpr uint32_t TI = 16, TJ = 64;
-
-__device__ __forceinline__ uint64_t cov_mix(uint64_t z) {
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
 
 // Gq of one column pair from its counts cnt[a * 4 + b]; *rows = m
 __device__ __forceinline__ long long cov_gq(const uint32_t* cnt, const int64_t* __restrict__ lnq, uint32_t* rows) {
@@ -191,7 +186,7 @@ __global__ __launch_bounds__(256) void k_cov_shuffle(const uint8_t* __restrict__
   if (c >= len) return;
   for (uint32_t r = 0; r < n; ++r) out[(size_t)r * len + c] = code[(size_t)r * len + c];
   for (uint32_t i = n - 1; i >= 1; --i) {
-    const uint64_t u = cov_mix(base + (((uint64_t)c << 32) | i));
+    const uint64_t u = mix64(base + (((uint64_t)c << 32) | i));
     const uint32_t j = (uint32_t)(((u >> 32) * (uint64_t)(i + 1)) >> 32);  // j <= i
     const uint8_t vi = out[(size_t)i * len + c], vj = out[(size_t)j * len + c];
     out[(size_t)i * len + c] = vj;
@@ -234,7 +229,7 @@ __device__ __forceinline__ uint32_t cov_feistel(uint64_t key, uint32_t h, uint32
   uint32_t L = x >> h, R = x & mask;
 #pragma unroll
   for (uint64_t r = 1; r <= 4; ++r) {
-    const uint32_t t = L ^ ((uint32_t)cov_mix(key + 0x9E3779B97F4A7C15ull * r + R) & mask);
+    const uint32_t t = L ^ ((uint32_t)mix64(key + kMixGolden * r + R) & mask);
     L = R;
     R = t;
   }
@@ -257,7 +252,7 @@ __global__ __launch_bounds__(kCovTreeThreads) void k_cov_draw(const uint8_t* __r
                                                               uint64_t base, uint32_t v0, uint8_t* __restrict__ node) {
   const uint32_t c = blockIdx.x * kCovTreeThreads + threadIdx.x, v = v0 + blockIdx.y;
   if (c >= len) return;
-  const uint64_t key = cov_mix(base ^ ((uint64_t)(v + 1) << 32));  // uniform per workgroup
+  const uint64_t key = mix64(base ^ ((uint64_t)(v + 1) << 32));  // uniform per workgroup
   node[(size_t)v * len + c] = chg[(size_t)v * len + cov_pi(key, len, h, walk, c)];
 }
 

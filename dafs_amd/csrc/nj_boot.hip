@@ -3,122 +3,68 @@
 //
 // k_boot_pack  one thread per (replicate, row, word of 64 columns): the draws of its 64 positions (stateless: a draw is one
 //              mix of the replicate's base and the position, so no draw is ever stored), the row's cells in the drawn
-//              columns, and the four plane words of alistat.h, word-major per replicate.
-// k_boot_dist  the tile of k_ali_pairs<ALI_MATRIX> (alistat.hip) with a grid dimension over the replicates: 16 wavefronts,
-//              16 rows r x 64 rows s, the plane words staged in LDS, the counters in registers.  The lane that owns r < s
-//              turns its two counts into the distance of section 22 and writes that one double; the count matrices are
-//              never stored.  A Jukes-Cantor value that comes within `guard` of a quantisation step goes to a list that the
-//              host recomputes with its own log().
+//              columns, and the four plane words of alistat.h (ali_pack_cell), word-major per replicate.
+// k_boot_dist  the pair-count tile of k_ali_pairs<ALI_MATRIX> (alistat.hip) with a grid dimension over the replicates; the
+//              tile's shape, its place in LDS, the staging and the counts are ali_tile.h's (ALI_TILE_COUNTS); only the
+//              planes' base differs.  The lane that owns r < s turns its two counts into the distance of section 22 and
+//              writes that one double; the count matrices are never stored.  A Jukes-Cantor value that comes within `guard`
+//              of a quantisation step goes to a list that the host recomputes with its own log().
 // k_nj_batch   ONE workgroup per matrix: all n - 1 joins of section 22 inside it, in the style of k_linkage_joins.  Every wait
 //              is a __syncthreads(), the loop has exactly n - 1 trips, nothing polls and no workgroup knows of another.  D is
 //              the matrix's working copy in global memory; R, node, the wavefronts' pick tuples and the row of the join
-//              are in LDS.  The pick, the update and the running sum R[a] are those of nj.hip, restated here so that nj.hip's
-//              code objects stay as they are: a wavefront per active row i scans j > i with strict `<`, rows and columns
-//              ascending, so a lane keeps the first smallest (i, j) it met; one butterfly over (Q, i << 16 | j) per wavefront
-//              and one over the 16 wavefronts leave the smallest Q, then the smallest a, then the smallest b.
+//              are in LDS.  Every step of a join is nj_steps.h's, the same code as nj.hip's kernels run.  What is this
+//              kernel's own: a wavefront scans all its active rows i, rows and columns ascending, into one tuple, so a lane
+//              keeps the first smallest (i, j) it met; one butterfly over (Q, i << 16 | j) per wavefront and one over the 16
+//              wavefronts leave the smallest Q, then the smallest a, then the smallest b.  The counts of non-finite values
+//              stay in registers until the last join.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
 
 #include "../../include/dafs_hip.h"
+#include "ali_tile.h"
 #include "alistat.h"
 #include "call_host.h"
 #include "hip_util.h"
 #include "nj_boot.h"
+#include "nj_steps.h"
 #include "stage.h"
 
 namespace dafs {
 
 namespace {
 
-constexpr uint32_t kNone = 0xFFFFFFFFu;
+using namespace nj;
+
 constexpr uint32_t kBatchWaves = kNjBatchThreads / 64;
-constexpr uint32_t TI = 16, TJ = 64;
-
-__device__ __forceinline__ double pos_inf() { return __longlong_as_double(0x7FF0000000000000ll); }
-__device__ __forceinline__ double quiet_nan() { return __longlong_as_double(0x7FF8000000000000ll); }
-__device__ __forceinline__ uint32_t nonfinite(double v) {
-  return ((unsigned long long)__double_as_longlong(v) & 0x7FF0000000000000ull) == 0x7FF0000000000000ull ? 1u : 0u;
-}
-
-// (value ascending, key ascending); a NaN is never better, and (+inf, kNone) is "no candidate"
-__device__ __forceinline__ bool better(double v1, uint32_t i1, double v2, uint32_t i2) { return v1 < v2 || (v1 == v2 && i1 < i2); }
-
-__device__ __forceinline__ void wave_best(double& v, uint32_t& i) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    const double ov = __shfl_xor(v, d, 64);
-    const uint32_t oi = __shfl_xor(i, d, 64);
-    if (better(ov, oi, v, i)) { v = ov; i = oi; }
-  }
-}
-
-__device__ __forceinline__ double lane_value(double v, int l) {
-  const int lo = __builtin_amdgcn_readlane(__double2loint(v), l);
-  const int hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
-  return __hiloint2double(hi, lo);
-}
-
-// mix of DESIGN.md section 13
-__device__ __forceinline__ uint64_t boot_mix(uint64_t z) {
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-constexpr uint64_t kGolden = 0x9E3779B97F4A7C15ull;
+static_assert(kNjBatchMaxN <= 0xFFFFu, "k_nj_batch keeps a pair as i << 16 | j, and kNone must decode to a slot above every n");
 
 __global__ __launch_bounds__(256) void k_boot_pack(boot_args a) {
   const uint32_t r = blockIdx.x * 256 + threadIdx.x, w = blockIdx.y, kk = blockIdx.z;
   if (r >= a.n) return;
-  const uint64_t base = boot_mix(a.seed + kGolden * (uint64_t)(a.k0 + kk + 1));
+  const uint64_t base = mix64(a.seed + kMixGolden * (uint64_t)(a.k0 + kk + 1));
   uint64_t word[4] = {0ull, 0ull, 0ull, 0ull};
   const uint32_t c1 = a.U - w * 64 < 64 ? a.U - w * 64 : 64;
   for (uint32_t b = 0; b < c1; ++b) {
-    const uint32_t u = (uint32_t)(((boot_mix(base + (uint64_t)(w * 64 + b)) >> 32) * (uint64_t)a.U) >> 32);  // below U
-    const uint64_t v = a.cells[(size_t)u * a.n + r];
-    word[ALI_LO] |= (v & 1) << b;
-    word[ALI_HI] |= ((v >> 1) & 1) << b;
-    word[ALI_BASE] |= (uint64_t)(v <= 3 ? 1 : 0) << b;
-    word[ALI_RES] |= (uint64_t)(v <= 4 ? 1 : 0) << b;
+    const uint32_t u = (uint32_t)(((mix64(base + (uint64_t)(w * 64 + b)) >> 32) * (uint64_t)a.U) >> 32);  // below U
+    ali_pack_cell(a.cells[(size_t)u * a.n + r], b, word);
   }
   uint64_t* planes = a.planes + (size_t)kk * a.words * 4 * a.n;
 #pragma unroll
   for (int p = 0; p < 4; ++p) planes[((size_t)w * 4 + p) * a.n + r] = word[p];
 }
 
-__global__ __launch_bounds__(1024) void k_boot_dist(boot_args a, uint32_t kk0) {
-  extern __shared__ uint64_t lds[];  // y[chunk][4][TJ], then x[chunk][4][TI]
-  const uint32_t i0 = blockIdx.x * TI, j0 = blockIdx.y * TJ, kk = kk0 + blockIdx.z;
-  if (j0 + TJ - 1 <= i0) return;  // no pair r < s in this tile (the whole workgroup leaves)
+__global__ __launch_bounds__(ALI_TILE_THREADS) void k_boot_dist(boot_args a, uint32_t kk0) {
+  extern __shared__ uint64_t lds[];  // ali_tile_shape::lds
+  const uint32_t i0 = blockIdx.x * ALI_TI, j0 = blockIdx.y * ALI_TJ, kk = kk0 + blockIdx.z;
+  if (!ali_tile_upper(i0, j0)) return;  // the whole workgroup leaves
   const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const uint32_t r = i0 + wv, s = j0 + lane;
   const uint64_t* planes = a.planes + (size_t)kk * a.words * 4 * a.n;
-  uint64_t* ly = lds;
-  uint64_t* lx = lds + (size_t)a.chunk * 4 * TJ;
+  uint64_t* ly = ali_tile_y(lds);
+  uint64_t* lx = ali_tile_x(lds, a.chunk);
   uint32_t ident = 0, comp = 0;
-  for (uint32_t w0 = 0; w0 < a.words; w0 += a.chunk) {
-    const uint32_t wc = a.words - w0 < a.chunk ? a.words - w0 : a.chunk;
-    __syncthreads();
-    for (uint32_t t = threadIdx.x; t < wc * 4 * TJ; t += 1024) {
-      const uint32_t row = j0 + (t & (TJ - 1)), pl = t / TJ;  // pl = w * 4 + plane
-      ly[t] = row < a.n ? planes[((size_t)w0 * 4 + pl) * a.n + row] : 0ull;
-    }
-    for (uint32_t t = threadIdx.x; t < wc * 4 * TI; t += 1024) {
-      const uint32_t row = i0 + (t & (TI - 1)), pl = t / TI;
-      lx[t] = row < a.n ? planes[((size_t)w0 * 4 + pl) * a.n + row] : 0ull;
-    }
-    __syncthreads();
-    for (uint32_t w = 0; w < wc; ++w) {
-      uint64_t x[4], y[4];
-#pragma unroll
-      for (int p = 0; p < 4; ++p) {
-        x[p] = lx[(w * 4 + p) * TI + wv];
-        y[p] = ly[(w * 4 + p) * TJ + lane];
-      }
-      ident += (uint32_t)__popcll(~(x[ALI_LO] ^ y[ALI_LO]) & ~(x[ALI_HI] ^ y[ALI_HI]) & x[ALI_BASE] & y[ALI_BASE]);
-      comp += (uint32_t)__popcll(x[ALI_RES] & y[ALI_RES]);
-    }
-  }
+  ALI_TILE_COUNTS(planes, a.n, a.words, a.chunk, i0, j0, wv, lane, ly, lx, true, ident, comp);
   if (!(r < s && s < a.n)) return;
   const uint32_t mism = comp - ident;
   double d;
@@ -167,26 +113,8 @@ __global__ __launch_bounds__(kNjBatchThreads) void k_nj_batch(uint32_t n, const 
   if (tid == 0) bad_in = 0;
   __syncthreads();
   uint32_t bad = 0;
-  for (uint32_t row = wave; row < n; row += kBatchWaves) {
-    double* out = D + (size_t)row * n;
-    for (uint32_t j = lane; j < n; j += 64) {
-      double v = 0.0;
-      if (j > row) {
-        v = in[(size_t)row * n + j];
-        bad += nonfinite(v);
-      } else if (j < row) {
-        v = in[(size_t)j * n + row];
-      }
-      out[j] = v;
-    }
-  }
-  for (uint32_t i = tid; i < n; i += kNjBatchThreads) {
-    node[i] = (int32_t)i;
-    left[i] = -1;
-    right[i] = -1;
-    length[i] = 0.0;
-    if (i + 1 < n) length[n + i] = 0.0;  // the root's stays
-  }
+  for (uint32_t row = wave; row < n; row += kBatchWaves) bad += sym_row(n, row, lane, in, D);
+  for (uint32_t i = tid; i < n; i += kNjBatchThreads) leaf(n, i, node, left, right, length);
   if (bad) atomicAdd(&bad_in, bad);
   __syncthreads();
   if (bad_in) {  // refused: no join runs (the whole workgroup leaves)
@@ -196,9 +124,7 @@ __global__ __launch_bounds__(kNjBatchThreads) void k_nj_batch(uint32_t n, const 
   // R[k]: the running sum of column k in ascending row order (k_nj_rowsum)
   uint32_t written = 0;
   for (uint32_t k = tid; k < n; k += kNjBatchThreads) {
-    double s = 0.0;
-#pragma unroll 8
-    for (uint32_t j = 0; j < n; ++j) s += D[(size_t)j * n + k];
+    const double s = column_sum(n, k, D);
     R[k] = s;
     written += nonfinite(s);
   }
@@ -207,43 +133,22 @@ __global__ __launch_bounds__(kNjBatchThreads) void k_nj_batch(uint32_t n, const 
   uint32_t joins = 0;
   for (uint32_t t = 0; t + 1 < n; ++t) {
     const uint32_t m = n - t;
-    // the pick: a wavefront per active row
-    {
-      const double c = (double)(m - 2);
-      double bq = pos_inf();
-      uint32_t bk = kNone;
-      for (uint32_t i = wave; i + 1 < n; i += kBatchWaves) {
-        if (node[i] < 0) continue;
-        const double* Di = D + (size_t)i * n;
-        const double Ri = R[i];
-#pragma unroll 2
-        for (uint32_t j = i + 1 + lane; j < n; j += 64) {
-          const double q = (c * Di[j] - Ri) - R[j];  // NaN at a retired j: never below anything
-          if (q < bq) { bq = q; bk = (i << 16) | j; }
-        }
-      }
-      wave_best(bq, bk);
-      if (lane == 0) { red_v[wave] = bq; red_k[wave] = bk; }
-    }
+    // the pick: a wavefront per active row, all its rows into one tuple
+    const double c = others(m);
+    best p{pos_inf(), kNone};
+    for (uint32_t i = wave; i + 1 < n; i += kBatchWaves)
+      if (node[i] >= 0) p = scan_row<2, true>(n, i, lane, c, D, R, p);
+    wave_best(p.q, p.k);
+    if (lane == 0) { red_v[wave] = p.q; red_k[wave] = p.k; }
     __syncthreads();
     if (wave == 0) {
       double bq = lane < kBatchWaves ? red_v[lane] : pos_inf();
       uint32_t bk = lane < kBatchWaves ? red_k[lane] : kNone;
       wave_best(bq, bk);
       if (lane == 0) {
-        uint32_t a = kNone, b = kNone;
-        if (bk != kNone) {
-          a = bk >> 16;
-          b = bk & 0xFFFFu;
-        } else {  // no Q below +inf: the candidate the scan starts from, the first two active slots
-          for (uint32_t i = 0; i < n && b == kNone; ++i) {
-            if (node[i] < 0) continue;
-            if (a == kNone) a = i; else b = i;
-          }
-        }
-        if (a >= n || b >= n || a >= b || node[a] < 0 || node[b] < 0) a = b = kNone;  // never index beyond the arrays
-        pick[0] = a;
-        pick[1] = b;
+        const slots s = settle_pair(n, node, bk >> 16, bk & 0xFFFFu);  // kNone: a = 0xFFFF, above every n of this form
+        pick[0] = s.a;
+        pick[1] = s.b;
       }
     }
     __syncthreads();
@@ -252,67 +157,14 @@ __global__ __launch_bounds__(kNjBatchThreads) void k_nj_batch(uint32_t n, const 
       if (tid == 0) head->fault = 1;
       continue;
     }
-    double* Da = D + (size_t)a * n;
-    const double* Db = D + (size_t)b * n;
-    const double dab = Da[b];
-    for (uint32_t base = wave * 64; base < n; base += kNjBatchThreads) {  // a wavefront takes whole chunks of 64 slots
-      const uint32_t k = base + lane;
-      const bool part = k < n && k != a && k != b && node[k] >= 0;
-      double u = 0.0;
-      if (part) {
-        const double p = Da[k], q = Db[k];
-        u = 0.5 * ((p + q) - dab);
-        const double r = ((R[k] - p) - q) + u;
-        R[k] = r;
-        Da[k] = u;
-        D[(size_t)k * n + a] = u;
-        written += nonfinite(u) + nonfinite(r);
-      }
-      row_u[k] = u;
-      const unsigned long long m_part = __ballot(part);
-      if (lane == 0) row_part[base >> 6] = m_part;
-    }
-    if (tid == kNjBatchThreads - 1) {  // the join itself, by a thread of the last wavefront
-      double la = 0.5 * dab;
-      if (m > 2) la = la + (R[a] - R[b]) / (2.0 * (double)(m - 2));
-      const double lb = dab - la;
-      const int32_t na = node[a], nb = node[b];
-      length[na] = la;
-      length[nb] = lb;
-      left[n + t] = na;
-      right[n + t] = nb;
-      written += nonfinite(la) + nonfinite(lb);
-    }
+    const double dab = D[(size_t)a * n + b];
+    written += update_row<kNjBatchThreads>(n, a, b, dab, D, R, node, row_u, row_part);
+    if (tid == kNjBatchThreads - 1) written += join_pair(n, t, m, a, b, dab, R, node, left, right, length);  // a thread of the last wavefront
     __syncthreads();  // the new row a in LDS; R[a], R[b], node[a], node[b] still as before the join
     if (wave == 0) {
-      // R[a]: the running sum of the new row a over the remaining active k, ascending (see k_nj_update)
-      double s = 0.0;
-      double v = row_u[lane];
-      unsigned long long m_part = row_part[0];
-      for (uint32_t c = 0; c < chunks; ++c) {
-        const double v_next = row_u[(size_t)(c + 1) * 64 + lane];  // the array ends in one chunk of padding
-        const unsigned long long m_next = row_part[c + 1];
-        unsigned long long todo = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(m_part >> 32)) << 32) |
-                                  (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)m_part);
-        if (__popcll(todo) >= 24) {
-#pragma unroll
-          for (int l = 0; l < 64; ++l) s += lane_value(v, l);
-        } else {
-          while (todo) {
-            const int l = __ffsll((long long)todo) - 1;
-            todo &= todo - 1;
-            s += lane_value(v, l);
-          }
-        }
-        v = v_next;
-        m_part = m_next;
-      }
+      const double s = row_sum(chunks, lane, row_u, row_part);
       if (lane == 0) {
-        R[a] = s;
-        R[b] = quiet_nan();
-        node[a] = (int32_t)(n + t);
-        node[b] = -1;
-        written += nonfinite(s);
+        written += retire(n, t, a, b, s, R, node);
         ++joins;
       }
     }
@@ -358,16 +210,17 @@ int boot_pack(const boot_args& a, hipStream_t st) {
 
 int boot_dist(const boot_args& a, hipStream_t st) {
   if (a.n < 2 || a.n > kNjMaxN || !a.words || !a.chunk || a.chunk > kAliMaxChunk || !a.count || a.count > kBootChunkReplicates) return DAFS_HIP_EINVAL;
-  const uint32_t bi = (a.n + TI - 1) / TI, bj = (a.n + TJ - 1) / TJ;  // <= 2^10 x 2^8
-  const size_t lds = (size_t)a.chunk * 4 * (TI + TJ) * sizeof(uint64_t);
+  const ali_tile_shape tile = ali_tile_shape_of(a.n, a.chunk);  // <= 2^10 x 2^8 blocks
   // so many replicates per launch that it stays below kAliBandBlocks workgroups of 1024 threads: under 2^32 work-items
-  const uint32_t per = kAliBandBlocks / (bi * bj) ? kAliBandBlocks / (bi * bj) : 1;
+  const uint32_t per = kAliBandBlocks / (tile.bi * tile.bj) ? kAliBandBlocks / (tile.bi * tile.bj) : 1;
   for (uint32_t kk = 0; kk < a.count; kk += per) {
     const uint32_t z = a.count - kk < per ? a.count - kk : per;
-    STAGE_LAUNCH(ST_BOOT_DIST, st) hipLaunchKernelGGL(k_boot_dist, dim3(bi, bj, z), dim3(1024), lds, st, a, kk);
+    STAGE_LAUNCH(ST_BOOT_DIST, st) hipLaunchKernelGGL(k_boot_dist, dim3(tile.bi, tile.bj, z), dim3(ALI_TILE_THREADS), tile.lds, st, a, kk);
     if (hip_check(hipGetLastError())) return DAFS_HIP_ELAUNCH;
   }
   return DAFS_HIP_OK;
 }
 
 }  // namespace dafs
+
+#undef ALI_TILE_COUNTS
