@@ -138,6 +138,10 @@ static int consistency_parts(dafs_hip_ctx* c, float w_pct_a, float w_pct_s, int 
   int rc;
   // the row kernels gather {column, value} pairs: one interleaved copy of the input entries per transform
   if ((rc = c->mp_ent2.reserve(raw.pool_used + 32))) return rc;  // + slack: k_pct_rows' unpredicated fetch reads up to 15 entries behind a row
+  // The slack is zeroed, not just reserved: a lane of k_pct_rows without an item prepares item 0 of its chunk, and where every
+  // a-row of the chunk is empty that is the entry at which lane 15's row would start -- the end of the pool for the last pair.
+  // The lane uses the word as k in its unpredicated row-pointer load b_rp + 4 k: {0, 0} keeps that address inside the row pointers.
+  if (hip_check(hipMemsetAsync(c->mp_ent2.ptr + raw.pool_used, 0, 32 * sizeof(uint2), c->stream))) return DAFS_HIP_ELAUNCH;
   if ((rc = pct_interleave_launch(raw.col.ptr, raw.val.ptr, c->mp_ent2.ptr, raw.pool_used, c->stream))) return rc;
   mpv.ent2 = c->mp_ent2.ptr;
   {  // the identity matrix mp[x][x] as an ordinary CSR (entries {k, 1}, row pointers k): the row kernels treat it like any other
