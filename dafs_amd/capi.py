@@ -159,6 +159,10 @@ _nussinov_decode_dense = _sig("dafs_hip_nussinov_decode_dense", C.c_int,
 _nw_decode_dense = _sig("dafs_hip_nw_decode_dense", C.c_int,
                         [C.c_void_p, C.c_float, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)])
 _make_brackets = _sig("dafs_hip_make_brackets", None, [C.c_uint32, C.c_void_p, C.c_char_p])
+_make_brackets_levels = _sig("dafs_hip_make_brackets_levels", None, [C.c_uint32, C.c_void_p, C.c_void_p, C.c_char_p])
+_nussinov_decode_levels = _sig("dafs_hip_nussinov_decode_levels", C.c_int,
+                               [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])
+MAX_LEVELS = 4
 _dd_default_params = _sig("dafs_hip_dd_default_params", None, [C.POINTER(DDParams)])
 _solve_nodes = _sig("dafs_hip_solve_nodes", C.c_int,
                     [C.c_void_p, C.c_uint32, C.POINTER(NodeInput), C.POINTER(DDParams), C.POINTER(NodeOutput)])
@@ -235,6 +239,10 @@ _update_basepairing = _sig("dafs_hip_update_basepairing", C.c_int, [C.c_void_p, 
 _consensus_structure = _sig("dafs_hip_consensus_structure", C.c_int,
                             [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p,
                              C.POINTER(C.c_float), C.c_void_p])
+_structure_levels_bytes = _sig("dafs_host_structure_levels_bytes", C.c_uint64, [C.c_uint32, C.c_uint32])
+_consensus_structures_levels = _sig("dafs_hip_consensus_structures_levels", C.c_int,
+                                    [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p])
 _consensus_structures = _sig("dafs_hip_consensus_structures", C.c_int,
                              [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p])
 _alignment_reliability = _sig("dafs_hip_alignment_reliability", C.c_int,
@@ -868,6 +876,18 @@ class Context:
                                ss.ctypes.data, C.byref(score)))
         return np.float32(score.value), ss
 
+    def nussinov_levels(self, p, ths):
+        """dafs_hip_nussinov_decode_levels: the level-by-level decode of the dense matrix p at the thresholds ths (one per
+        level, at most MAX_LEVELS); returns (scores[len(ths)], ss, level)"""
+        p = np.ascontiguousarray(p, np.float32)
+        th = np.ascontiguousarray(ths, np.float32).reshape(-1)
+        L = p.shape[0]
+        ss = np.zeros(L, np.uint32)
+        level = np.zeros(L, np.uint8)
+        score = np.zeros(max(len(th), 1), np.float32)
+        check(_nussinov_decode_levels(self._h, len(th), th.ctypes.data, L, p.ctypes.data, ss.ctypes.data, level.ctypes.data, score.ctypes.data))
+        return score[:len(th)], ss, level
+
     def nussinov_dense(self, p, q, th, w=0.0):
         """the dense Nussinov class (q None: the final-decode overload); returns (score, ss)"""
         p = np.ascontiguousarray(p, np.float32)
@@ -1011,10 +1031,14 @@ class Context:
 
     def consensus_structures(self, alignments, th):
         """dafs_hip_consensus_structures: the common structures of many alignments in one call.  alignments: a list of
-        (seq, mask) as consensus_structure takes them; returns a list of (score, ss), each what consensus_structure gives."""
+        (seq, mask) as consensus_structure takes them; returns a list of (score, ss), each what consensus_structure gives.
+        th a sequence of thresholds: dafs_hip_consensus_structures_levels, one level per threshold; returns a list of
+        (scores[len(th)], ss, level)."""
         als = [(np.ascontiguousarray(s, np.uint32).reshape(-1), np.ascontiguousarray(m, np.uint8)) for s, m in alignments]
         if any(m.ndim != 2 or m.shape[0] != len(s) for s, m in als):
             raise ValueError("consensus_structures: every alignment is (seq[n], mask[n, len])")
+        if np.ndim(th) != 0:
+            return self._consensus_structures_levels(als, np.ascontiguousarray(th, np.float32).reshape(-1))
         if not als:
             check(_consensus_structures(self._h, 0, None, None, None, None, th, None, None))
             return []
@@ -1028,6 +1052,24 @@ class Context:
                                     ss.ctypes.data, score.ctypes.data))
         cuts = np.cumsum(lens)[:-1]
         return [(sc, x) for sc, x in zip(score, np.split(ss[:int(lens.sum())], cuts))]
+
+    def _consensus_structures_levels(self, als, th):
+        K = len(th)
+        if not als:
+            check(_consensus_structures_levels(self._h, 0, None, None, None, None, K, th.ctypes.data, None, None, None))
+            return []
+        n_rows = np.array([m.shape[0] for _, m in als], np.uint32)
+        lens = np.array([m.shape[1] for _, m in als], np.uint32)
+        seq = np.ascontiguousarray(np.concatenate([s for s, _ in als]), np.uint32)
+        mask = np.ascontiguousarray(np.concatenate([m.reshape(-1) for _, m in als]), np.uint8)
+        total = int(lens.sum())
+        ss = np.zeros(max(total, 1), np.uint32)
+        level = np.zeros(max(total, 1), np.uint8)
+        score = np.zeros(max(len(als) * K, 1), np.float32)
+        check(_consensus_structures_levels(self._h, len(als), n_rows.ctypes.data, lens.ctypes.data, seq.ctypes.data, mask.ctypes.data, K,
+                                           th.ctypes.data, ss.ctypes.data, level.ctypes.data, score.ctypes.data))
+        cuts = np.cumsum(lens)[:-1]
+        return [(score[a * K:(a + 1) * K], x, lv) for a, (x, lv) in enumerate(zip(np.split(ss[:total], cuts), np.split(level[:total], cuts)))]
 
     def structure_support(self, alignments, structures):
         """dafs_hip_structure_support: how far every row of each alignment keeps the structure given for it.  alignments: a
@@ -1566,4 +1608,15 @@ def make_brackets(ss):
     ss = np.ascontiguousarray(ss, np.uint32)
     buf = C.create_string_buffer(len(ss) + 1)
     _make_brackets(len(ss), ss.ctypes.data, buf)
+    return buf.value.decode()
+
+
+def make_brackets_levels(ss, level):
+    """the bracket string of a structure of several levels: "()", "[]", "{}", "<>" for levels 0..3"""
+    ss = np.ascontiguousarray(ss, np.uint32)
+    level = np.ascontiguousarray(level, np.uint8)
+    if len(level) != len(ss):
+        raise ValueError("make_brackets_levels: one level per column")
+    buf = C.create_string_buffer(len(ss) + 1)
+    _make_brackets_levels(len(ss), ss.ctypes.data, level.ctypes.data, buf)
     return buf.value.decode()

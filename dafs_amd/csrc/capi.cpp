@@ -247,3 +247,14 @@ extern "C" void dafs_hip_make_brackets(uint32_t L, const uint32_t* ss, char* str
   for (uint32_t i = 0; i != L; ++i)
     if (ss[i] != DAFS_HIP_NONE) { str[i] = '('; str[ss[i]] = ')'; }
 }
+
+// the same with the bracket kind of the pair's level: the reference's table of four (src/fold.cpp:57-58)
+extern "C" void dafs_hip_make_brackets_levels(uint32_t L, const uint32_t* ss, const uint8_t* level, char* str) {
+  static const char left[] = "([{<", right[] = ")]}>";
+  memset(str, '.', L);
+  str[L] = 0;
+  for (uint32_t i = 0; i != L; ++i) {
+    const uint32_t k = level ? level[i] : 0;
+    if (ss[i] < L && k < DAFS_HIP_MAX_LEVELS) { str[i] = left[k]; str[ss[i]] = right[k]; }
+  }
+}

@@ -923,11 +923,76 @@ uint32_t cs_class_of(uint32_t L, uint32_t form, size_t lds) {
   return lds <= kCsClasses[1].lds_cap ? 1 : 2;
 }
 
+// The level loop of a chunk over m alignments whose matrices stand on the device, in class order.
+struct lv_run {
+  uint32_t m, K;
+  const float* th;           // [K]
+  const uint32_t* first_of;  // [kCsClassCount + 1]: the classes' ranges of the m alignments
+  const size_t* lds_of;      // per class
+  const uint32_t* len_of;
+  const cs_desc* descs;      // host, [m]: ss = the level's own array, score = the first of the alignment's K scores
+  const lv_desc* d_lv;       // device, [m]
+  uint8_t* d_up;             // device, lv_up_bytes(m): the descriptors and indices of the alignments still going, per level
+  uint32_t* d_flags;         // device, [K][m]
+};
+size_t lv_up_bytes(uint32_t m) { return (size_t)m * (sizeof(cs_desc) + 4); }
+
+// Level 0 decodes every alignment; level k > 0 those with a pair at level k - 1, after the mask of that level.  One copy up
+// per level (descriptors with the level's score slot, and the indices), one copy of m flags down between two levels.
+// ran[j]: the levels alignment j was launched at.  up, flags: host buffers that must outlive the frame.
+int run_levels(call_frame& f, const lv_run& r, std::vector<uint8_t>& up, std::vector<uint32_t>& flags, std::vector<uint32_t>& ran) {
+  const uint32_t m = r.m;
+  std::vector<uint32_t> act(m);
+  for (uint32_t j = 0; j < m; ++j) act[j] = j;
+  ran.assign(m, 0);
+  flags.assign(m, 0);
+  cs_desc* d_cs = (cs_desc*)r.d_up;
+  uint32_t* d_act = (uint32_t*)(r.d_up + (size_t)m * sizeof(cs_desc));
+  int rc;
+  for (uint32_t k = 0; k < r.K && !act.empty(); ++k) {
+    const uint32_t n = (uint32_t)act.size();
+    up.resize(lv_up_bytes(m));
+    uint32_t first[kCsClassCount + 1] = {0};  // the classes' ranges of the active ones (act keeps the class order)
+    for (uint32_t x = 0, cls = 0; x < n; ++x) {
+      cs_desc d = r.descs[act[x]];
+      d.score += k;
+      memcpy(up.data() + (size_t)x * sizeof(cs_desc), &d, sizeof d);
+      while (act[x] >= r.first_of[cls + 1]) ++cls;
+      ++first[cls + 1];
+      ++ran[act[x]];
+    }
+    for (uint32_t cls = 0; cls < kCsClassCount; ++cls) first[cls + 1] += first[cls];
+    memcpy(up.data() + (size_t)m * sizeof(cs_desc), act.data(), (size_t)n * 4);
+    if (f.up(d_cs, up.data(), (size_t)n * sizeof(cs_desc)) || f.up(d_act, up.data() + (size_t)m * sizeof(cs_desc), (size_t)n * 4)) return DAFS_HIP_ELAUNCH;
+    for (uint32_t cls = 0; cls < kCsClassCount; ++cls) {
+      const uint32_t nc = first[cls + 1] - first[cls];
+      if (!nc) continue;
+      if (k && (rc = levels_mask_launch(r.d_lv, d_act + first[cls], nc, r.len_of[cls], f.st))) return rc;
+      if ((rc = nussinov_batch_launch(d_cs + first[cls], nc, r.th[k], kCsClasses[cls].threads, r.lds_of[cls], f.st))) return rc;
+    }
+    const bool more = k + 1 < r.K;
+    if ((rc = levels_merge_launch(r.d_lv, d_act, n, k, more, f.st))) return rc;
+    if (!more) break;
+    if (f.down(flags.data(), r.d_flags + (size_t)k * m, (size_t)m * 4)) return DAFS_HIP_ELAUNCH;
+    if ((rc = f.finish())) return rc;  // the one wait between two levels: `up` is rewritten, the next launch list depends on the flags
+    std::vector<uint32_t> next;
+    for (uint32_t j : act)
+      if (flags[j]) next.push_back(j);
+    act.swap(next);
+  }
+  return DAFS_HIP_OK;
+}
+
 }  // namespace
 
-extern "C" int dafs_hip_consensus_structures(dafs_hip_ctx* c, uint32_t nalign, const uint32_t* n_rows, const uint32_t* len, const uint32_t* seq,
-                                             const uint8_t* mask, float th, uint32_t* ss, float* score) {
+// nlevels = 0: the plain call (one decode, straight into the results).  nlevels >= 1: the level-by-level decode of section 25,
+// whose level 0 is that same decode into the level's own array, merged by k_levels_merge.
+static int consensus_structures_impl(dafs_hip_ctx* c, uint32_t nalign, const uint32_t* n_rows, const uint32_t* len, const uint32_t* seq,
+                                     const uint8_t* mask, uint32_t nlevels, const float* ths, uint32_t* ss, uint8_t* level, float* score) {
   if (!c) return DAFS_HIP_EINVAL;
+  const bool levels = nlevels != 0;
+  const uint32_t K = levels ? nlevels : 1;
+  const float th = ths[0];
   if (nalign == 0) return DAFS_HIP_OK;
   if (!n_rows || !len || !seq || !mask || !ss) return DAFS_HIP_EINVAL;
   if (hip_check(hipSetDevice(c->device))) return DAFS_HIP_ENODEV;
@@ -942,7 +1007,7 @@ extern "C" int dafs_hip_consensus_structures(dafs_hip_ctx* c, uint32_t nalign, c
     row0[a + 1] = row0[a] + n_rows[a];
     mask0[a + 1] = mask0[a] + (size_t)n_rows[a] * len[a];
     col0[a + 1] = col0[a] + len[a];
-    bytes[a] = dafs_host_structure_bytes(n_rows[a], len[a]);
+    bytes[a] = levels ? dafs_host_structure_levels_bytes(n_rows[a], len[a]) : dafs_host_structure_bytes(n_rows[a], len[a]);
   }
   for (uint32_t a = 0; a < nalign; ++a) {
     const int rc = make_geom(c, n_rows[a], len[a], seq + row0[a], mask + mask0[a], g[a]);
@@ -960,8 +1025,10 @@ extern "C" int dafs_hip_consensus_structures(dafs_hip_ctx* c, uint32_t nalign, c
   std::vector<uint32_t> order;
   std::vector<dd_node> nodes;
   std::vector<cs_desc> descs;
-  std::vector<uint8_t> head, out;
-  call_frame f(c);  // `head` and `out` are in flight when an error ends a chunk early
+  std::vector<uint8_t> head, out, lv_up;
+  std::vector<lv_desc> lv;
+  std::vector<uint32_t> lv_flags, lv_ran;
+  call_frame f(c);  // `head`, `out` and the level buffers are in flight when an error ends a chunk early
   for (uint32_t a0 = 0; a0 < nalign;) {
     uint32_t a1 = a0;
     while (a1 < nalign && chunk_of[a1] == chunk_of[a0] && a1 - a0 < kCsMaxLaunch) ++a1;
@@ -993,12 +1060,17 @@ extern "C" int dafs_hip_consensus_structures(dafs_hip_ctx* c, uint32_t nalign, c
     dd_node* d_nodes = nullptr;
     cs_desc* d_descs = nullptr;
     size_t head_bytes = 0, out_off = 0, out_bytes = 0;
-    std::vector<size_t> ss_off(m);
+    std::vector<size_t> ss_off(m), level_off(m);
     float* d_scores = nullptr;
+    lv_desc* d_lv = nullptr;
+    uint8_t* d_lv_up = nullptr;
+    uint32_t* d_flags = nullptr;
+    if (levels) lv.assign(m, lv_desc());
     for (int pass = 0; pass < 2; ++pass) {
       cv.used = 0;
       d_nodes = cv.take<dd_node>(m);
-      d_descs = cv.take<cs_desc>(m);
+      if (levels) d_lv = cv.take<lv_desc>(m);  // the decoder descriptors then go up level by level (run_levels)
+      else d_descs = cv.take<cs_desc>(m);
       for (uint32_t j = 0; j < m; ++j) {
         const uint32_t k = order[j], a = a0 + k;
         dd_node& nd = nodes[j];
@@ -1016,16 +1088,30 @@ extern "C" int dafs_hip_consensus_structures(dafs_hip_ctx* c, uint32_t nalign, c
         uint32_t* p = cv.take<uint32_t>((size_t)len[a0 + order[j]] + 1);
         descs[j].ss = p;
         ss_off[j] = (size_t)((uint8_t*)p - cv.base);
+        if (levels) {
+          lv[j].ss = p;
+          lv[j].level = cv.take<uint8_t>(len[a0 + order[j]]);
+          level_off[j] = (size_t)(lv[j].level - cv.base);
+        }
       }
-      d_scores = cv.take<float>(m);
+      d_scores = cv.take<float>((size_t)m * K);
       out_bytes = cv.used - out_off;
+      if (levels) {
+        d_lv_up = cv.take<uint8_t>(lv_up_bytes(m));
+        d_flags = cv.take<uint32_t>((size_t)m * K);
+      }
       for (uint32_t j = 0; j < m; ++j) {
         const uint32_t L = len[a0 + order[j]];
         dd_fold& f = nodes[j].f[0];
         f.p = cv.take<float>((size_t)L * L);
         carve_nuss(cv, L, f.w);
-        nodes[j].score = d_scores + j;
-        descs[j].L = L; descs[j].form = form[order[j]]; descs[j].p = f.p; descs[j].ws = f.w; descs[j].score = d_scores + j;
+        nodes[j].score = d_scores + (size_t)j * K;
+        descs[j].L = L; descs[j].form = form[order[j]]; descs[j].p = f.p; descs[j].ws = f.w; descs[j].score = d_scores + (size_t)j * K;
+        if (levels) {  // the decodes write the level's own array, the merge the results
+          uint32_t* lss = cv.take<uint32_t>((size_t)L + 1);
+          descs[j].ss = lss;
+          lv[j].L = L; lv[j].flag_stride = m; lv[j].p = f.p; lv[j].lss = lss; lv[j].key = cv.take<uint32_t>(L); lv[j].flag = d_flags + j;
+        }
       }
       if (pass == 0) {
         uint64_t estimate = 0;
@@ -1043,7 +1129,8 @@ extern "C" int dafs_hip_consensus_structures(dafs_hip_ctx* c, uint32_t nalign, c
       if (n) memcpy(head.data() + ((const uint8_t*)dst - cv.base), src, n);
     };
     put(d_nodes, nodes.data(), (size_t)m * sizeof(dd_node));
-    put(d_descs, descs.data(), (size_t)m * sizeof(cs_desc));
+    if (levels) put(d_lv, lv.data(), (size_t)m * sizeof(lv_desc));
+    else put(d_descs, descs.data(), (size_t)m * sizeof(cs_desc));
     for (uint32_t j = 0; j < m; ++j) {
       const uint32_t a = a0 + order[j];
       const dd_fold& f = nodes[j].f[0];
@@ -1058,7 +1145,11 @@ extern "C" int dafs_hip_consensus_structures(dafs_hip_ctx* c, uint32_t nalign, c
       const uint32_t n = first_of[k + 1] - first_of[k];
       if (!n) continue;
       if ((rc = dd_avg_launch(d_nodes + first_of[k], n, len_of[k], none, bpv, 0, 0, f.st))) return rc;
-      if ((rc = nussinov_batch_launch(d_descs + first_of[k], n, th, kCsClasses[k].threads, lds_of[k], f.st))) return rc;
+      if (!levels && (rc = nussinov_batch_launch(d_descs + first_of[k], n, th, kCsClasses[k].threads, lds_of[k], f.st))) return rc;
+    }
+    if (levels) {
+      const lv_run run = {m, K, ths, first_of, lds_of, len_of, descs.data(), d_lv, d_lv_up, d_flags};
+      if ((rc = run_levels(f, run, lv_up, lv_flags, lv_ran))) return rc;
     }
     out.resize(out_bytes);
     if (f.down(out.data(), cv.base + out_off, out_bytes)) return DAFS_HIP_ELAUNCH;
@@ -1066,9 +1157,98 @@ extern "C" int dafs_hip_consensus_structures(dafs_hip_ctx* c, uint32_t nalign, c
     for (uint32_t j = 0; j < m; ++j) {
       const uint32_t a = a0 + order[j];
       memcpy(ss + col0[a], out.data() + (ss_off[j] - out_off), (size_t)len[a] * 4);
-      if (score) memcpy(score + a, out.data() + ((size_t)((uint8_t*)(d_scores + j) - cv.base) - out_off), 4);
+      if (levels && level) memcpy(level + col0[a], out.data() + (level_off[j] - out_off), len[a]);
+      if (!score) continue;
+      const uint8_t* got = out.data() + ((size_t)((uint8_t*)(d_scores + (size_t)j * K) - cv.base) - out_off);
+      const uint32_t ran = levels ? lv_ran[j] : 1;  // the levels this alignment was launched at; the others are empty
+      memcpy(score + (size_t)a * K, got, (size_t)ran * 4);
+      for (uint32_t k = ran; k < K; ++k) score[(size_t)a * K + k] = 0.0f;
     }
     a0 = a1;
+  }
+  return DAFS_HIP_OK;
+}
+
+extern "C" int dafs_hip_consensus_structures(dafs_hip_ctx* c, uint32_t nalign, const uint32_t* n_rows, const uint32_t* len, const uint32_t* seq,
+                                             const uint8_t* mask, float th, uint32_t* ss, float* score) {
+  return consensus_structures_impl(c, nalign, n_rows, len, seq, mask, 0, &th, ss, nullptr, score);
+}
+
+static bool levels_args_ok(uint32_t nlevels, const float* th) {
+  if (nlevels < 1 || nlevels > DAFS_HIP_MAX_LEVELS || !th) return false;
+  for (uint32_t k = 1; k < nlevels; ++k)
+    if (!(th[k] > 0.0f)) return false;  // a masked cell (0) must never be a candidate
+  return true;
+}
+
+extern "C" int dafs_hip_consensus_structures_levels(dafs_hip_ctx* c, uint32_t nalign, const uint32_t* n_rows, const uint32_t* len,
+                                                    const uint32_t* seq, const uint8_t* mask, uint32_t nlevels, const float* th, uint32_t* ss,
+                                                    uint8_t* level, float* score) {
+  if (!c || !levels_args_ok(nlevels, th)) return DAFS_HIP_EINVAL;
+  return consensus_structures_impl(c, nalign, n_rows, len, seq, mask, nlevels, th, ss, level, score);
+}
+
+// The same decode of one dense host matrix (no store, no average): the matrix goes up as it is and is masked on the device.
+extern "C" int dafs_hip_nussinov_decode_levels(dafs_hip_ctx* c, uint32_t nlevels, const float* th, uint32_t L, const float* p, uint32_t* ss,
+                                               uint8_t* level, float* score) {
+  if (!c || !p || !ss || L == 0 || !levels_args_ok(nlevels, th)) return DAFS_HIP_EINVAL;
+  if (hip_check(hipSetDevice(c->device))) return DAFS_HIP_ENODEV;
+  const size_t LL = (size_t)L * L;
+  const uint32_t K = nlevels;
+  size_t lds = 0;
+  cs_desc desc;
+  lv_desc lv;
+  memset(&desc, 0, sizeof desc);
+  memset(&lv, 0, sizeof lv);
+  desc.L = lv.L = L;
+  desc.form = nussinov_form(L, &lds);
+  const uint32_t cls = cs_class_of(L, desc.form, lds);
+  uint32_t first_of[kCsClassCount + 1], len_of[kCsClassCount] = {0};
+  size_t lds_of[kCsClassCount] = {0};
+  for (uint32_t k = 0; k <= kCsClassCount; ++k) first_of[k] = k > cls ? 1 : 0;
+  lds_of[cls] = lds; len_of[cls] = L;
+  carver cv;
+  lv_desc* d_lv = nullptr;
+  uint8_t* d_lv_up = nullptr;
+  uint32_t* d_flags = nullptr;
+  size_t out_off = 0, out_bytes = 0;
+  for (int pass = 0; pass < 2; ++pass) {
+    cv.used = 0;
+    d_lv = cv.take<lv_desc>(1);
+    d_lv_up = cv.take<uint8_t>(lv_up_bytes(1));
+    d_flags = cv.take<uint32_t>(K);
+    out_off = (cv.used + 255) & ~(size_t)255;
+    lv.ss = cv.take<uint32_t>((size_t)L + 1);
+    lv.level = cv.take<uint8_t>(L);
+    desc.score = cv.take<float>(K);
+    out_bytes = cv.used - out_off;
+    lv.p = cv.take<float>(LL);
+    desc.p = lv.p;
+    carve_nuss(cv, L, desc.ws);
+    uint32_t* lss = cv.take<uint32_t>((size_t)L + 1);
+    desc.ss = lss; lv.lss = lss;
+    lv.key = cv.take<uint32_t>(L);
+    lv.flag = d_flags; lv.flag_stride = 1;
+    if (pass == 0) {
+      const int rc = c->work.reserve(cv.used + 256);
+      if (rc) return rc;
+      cv.base = c->work.ptr;
+    }
+  }
+  std::vector<uint8_t> out(out_bytes), lv_up;
+  std::vector<uint32_t> lv_flags, lv_ran;
+  call_frame f(c);
+  if (f.up(lv.p, p, LL * 4) || f.up(d_lv, &lv, sizeof lv)) return DAFS_HIP_ELAUNCH;
+  const lv_run run = {1, K, th, first_of, lds_of, len_of, &desc, d_lv, d_lv_up, d_flags};
+  int rc;
+  if ((rc = run_levels(f, run, lv_up, lv_flags, lv_ran))) return rc;
+  if (f.down(out.data(), cv.base + out_off, out_bytes)) return DAFS_HIP_ELAUNCH;
+  if ((rc = f.finish())) return rc;
+  memcpy(ss, out.data() + ((uint8_t*)lv.ss - cv.base - out_off), (size_t)L * 4);
+  if (level) memcpy(level, out.data() + (lv.level - cv.base - out_off), L);
+  if (score) {
+    memcpy(score, out.data() + ((uint8_t*)desc.score - cv.base - out_off), (size_t)lv_ran[0] * 4);
+    for (uint32_t k = lv_ran[0]; k < K; ++k) score[k] = 0.0f;
   }
   return DAFS_HIP_OK;
 }

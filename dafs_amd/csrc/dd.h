@@ -206,6 +206,25 @@ struct cs_desc {
 uint32_t nussinov_form(uint32_t L, size_t* lds_bytes);  // the form of an alignment of L columns and its dynamic LDS
 // descs[0..n): alignments of one size class -- `threads` per workgroup, lds_bytes >= every member's
 int nussinov_batch_launch(const cs_desc* d_descs, uint32_t n, float th, uint32_t threads, size_t lds_bytes, hipStream_t st);
+// One alignment of a level-by-level decode (levels.hip): what k_levels_merge and k_levels_mask read.
+// key[c] after level k's merge: kLvPaired where column c is in a pair of level k, else the left column of the innermost
+// level-k pair that strictly encloses c, or 0xFFFFFFFF.  Two columns free at level k are the ends of a cell that crosses a
+// level-k pair exactly when their keys differ.
+constexpr uint32_t kLvPaired = 0xFFFFFFFEu;
+struct lv_desc {
+  uint32_t L, flag_stride;
+  float* p;             // L*L: masked in place, level after level
+  const uint32_t* lss;  // L: the structure the newest level's decode wrote
+  uint32_t* key;        // L
+  uint32_t* ss;         // L: the merged structure
+  uint8_t* level;       // L: the pair's level at both of its columns, 0xFF elsewhere
+  uint32_t* flag;       // flag[k * flag_stride]: 1 when level k has a pair
+};
+// act[0..n): indices into descs of the alignments that take part.  merge: level k's lss into ss / level (k = 0 initialises
+// them), the flag, and with want_key the keys for level k + 1's mask.  mask: zeroes every cell (i, j), i < j, of p that has
+// an end paired at the newest level or crosses none of its pairs; max_len >= every member's L.
+int levels_merge_launch(const lv_desc* d_descs, const uint32_t* d_act, uint32_t n, uint32_t k, int want_key, hipStream_t st);
+int levels_mask_launch(const lv_desc* d_descs, const uint32_t* d_act, uint32_t n, uint32_t max_len, hipStream_t st);
 int nussinov_dense_launch(uint32_t L, const float* p, const float* q, float w, float th, float* dp, uint32_t* tr, uint32_t* stack, uint32_t* ss,
                           float* score, hipStream_t st);
 int nw_launch(uint32_t L1, uint32_t L2, const float* p, const float* q, float th, uint32_t* env, int compute_env,

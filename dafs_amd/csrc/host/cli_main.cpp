@@ -12,7 +12,8 @@
 // Differences from the reference, all forced by what its tree does not contain:
 //   -s Boltzmann / -s Vienna and the RNAalifold term need ViennaRNA arithmetic: not available.
 //      The default fold model here is CONTRAfold; asking for the others is an error.
-//   --fold-decoder IPknot / --ipknot / -m 0 need an ILP solver: not available.
+//   --fold-decoder IPknot / --ipknot / -m 0 need an ILP solver: not available.  --fold-decoder Levels decodes a structure
+//   with pseudoknots level by level instead, one level per entry of -T / -G.
 // One addition: --devices a,b,... runs phase 1 (:1787-1827) as one process per listed GPU (dafs_hip_phase1_sharded, the
 // shards all-gathered by RCCL); the processes are forked before anything touches a GPU, and the first one goes on alone.
 #include <dlfcn.h>
@@ -268,7 +269,15 @@ const char* kHelp =
     "\n Folding options:\n"
     "  -s, --fold-model arg  Folding model (value=CONTRAfold; Boltzmann and Vienna need ViennaRNA and are\n"
     "                        not available in this build) (default: CONTRAfold)\n"
-    "      --fold-decoder arg Decoder for common secondary structure prediction (value=Nussinov) (default: Nussinov)\n"
+    "      --fold-decoder arg Decoder for common secondary structure prediction (value=Nussinov, Levels) (default: Nussinov)\n"
+    "                        Levels: a structure that may hold pseudoknots, decoded level by level, one level per entry of\n"
+    "                        -T / -G (else of -t / -g), at most four: level 0 is the Nussinov decode at the first entry, level k\n"
+    "                        the same decoder at entry k over the cells whose columns are still free and that cross a pair of\n"
+    "                        every lower level.  Printed as () [] {} <>, in SS_cons and with --row-structures.  Each level is one\n"
+    "                        of IPknot's given the lower ones, without its stacking constraints: not IPknot's optimum.  Not with\n"
+    "                        --bp-update1 or --seed-structure.  The readers of --seed, --describe and --compare-ref refuse\n"
+    "                        structures whose bracket kinds cross, so this output cannot yet be read back as a seed.\n"
+    "                        With Nussinov only the first entry of -T / -G is used.  IPknot needs an ILP solver: not built.\n"
     "  -q, --fold-pct arg    Weight of PCT for base-pairing probabilities (default: 0.25)\n"
     "  -t, --fold-th arg     Threshold for base-pairing probabilities (default: 0.2)\n"
     "  -g, --gamma arg       Specify the threshold for base-pairing probabilities by 1/(gamma+1)\n"
@@ -625,6 +634,15 @@ Options parse(int argc, char** argv) {
     } else {
       o.fold_th1 = o.fold_th;
     }
+  }
+  if (o.fold_decoder == "Levels") {  // one level per entry of -T / -G
+    if (o.bp_update1)
+      throw std::string("--fold-decoder Levels: --bp-update1 is not built for it (the reference folds again per level, under each level's constraint)");
+    if (o.seed_structure) throw std::string("--seed-structure: nothing is decoded; --fold-decoder Levels cannot be combined with --seed-structure");
+    if (o.fold_th1.empty() || o.fold_th1.size() > DAFS_HIP_MAX_LEVELS)
+      throw std::string("--fold-decoder Levels: -T / -G hold " + std::to_string(o.fold_th1.size()) + " thresholds; one to four levels are decoded");
+    for (size_t k = 1; k < o.fold_th1.size(); ++k)
+      if (!(o.fold_th1[k] > 0.0f)) throw std::string("--fold-decoder Levels: the thresholds of the levels above the first must be positive");
   }
   if (o.input.empty() && o.describe.empty()) { std::cout << kHelp << std::endl; exit(0); }
   return o;
@@ -1660,15 +1678,36 @@ VU concat(const std::vector<VU>& parts) {
   return all;
 }
 
-// The first decode of many final alignments in one library call (dafs_hip_consensus_structures): ss[k] of *alns[k], decoded
-// over the rows in the order each holds them.
-void consensus_structures(dafs_hip_ctx* ctx, const std::vector<const ALN*>& alns, float th, std::vector<VU>& ss) {
+// Every decode of the command line goes through here: many alignments, laid out as the library takes them, at the decoder
+// of --fold-decoder.  Nussinov: dafs_hip_consensus_structures at the first entry of -T / -G; level stays empty.  Levels:
+// dafs_hip_consensus_structures_levels with one level per entry; level gets a byte per column.
+typedef std::vector<uint8_t> VL;
+void decode_alignments(dafs_hip_ctx* ctx, const Options& o, const std::vector<uint32_t>& n_rows, const std::vector<uint32_t>& len,
+                       const std::vector<uint32_t>& seq, const std::vector<uint8_t>& mask, VU& ss, VL& level) {
+  level.clear();
+  if (o.fold_decoder != "Levels") {
+    check(dafs_hip_consensus_structures(ctx, (uint32_t)n_rows.size(), n_rows.data(), len.data(), seq.data(), mask.data(), o.fold_th1[0], ss.data(), nullptr));
+    return;
+  }
+  level.assign(ss.size(), 0xFF);
+  check(dafs_hip_consensus_structures_levels(ctx, (uint32_t)n_rows.size(), n_rows.data(), len.data(), seq.data(), mask.data(),
+                                             (uint32_t)o.fold_th1.size(), o.fold_th1.data(), ss.data(), level.data(), nullptr));
+}
+
+// The first decode of many final alignments in one library call: ss[k] of *alns[k], decoded over the rows in the order each
+// holds them; level[k]: its levels, or empty (decode_alignments)
+void consensus_structures(dafs_hip_ctx* ctx, const Options& o, const std::vector<const ALN*>& alns, std::vector<VU>& ss, std::vector<VL>& level) {
   const Packed p = pack(alns);
   const std::vector<size_t> at = starts_of(p.len);
   VU all(at.back() ? at.back() : 1);
-  check(dafs_hip_consensus_structures(ctx, (uint32_t)alns.size(), p.n_rows.data(), p.len.data(), p.seq.data(), p.mask.data(), th, all.data(), nullptr));
+  VL lv;
+  decode_alignments(ctx, o, p.n_rows, p.len, p.seq, p.mask, all, lv);
   ss.clear();
-  for (size_t k = 0; k < alns.size(); ++k) ss.push_back(VU(all.begin() + at[k], all.begin() + at[k + 1]));
+  level.assign(alns.size(), VL());
+  for (size_t k = 0; k < alns.size(); ++k) {
+    ss.push_back(VU(all.begin() + at[k], all.begin() + at[k + 1]));
+    if (!lv.empty()) level[k].assign(lv.begin() + at[k], lv.begin() + at[k + 1]);
+  }
 }
 
 // The structure support of every row of many alignments in one library call (dafs_hip_structure_support): the rows of *alns[0]
@@ -1684,7 +1723,8 @@ void structure_support(dafs_hip_ctx* ctx, const std::vector<const ALN*>& alns, c
 
 // --row-structures: the structure of every sequence of the context alone -- its one-row alignment decoded from the base-pairing
 // store the progressive phase read, at the threshold of SS_cons -- all in one library call; indexed by sequence
-std::vector<VU> row_structures(dafs_hip_ctx* ctx, const std::vector<Fasta>& fa, float th) {
+// (row_level: per sequence its levels, or empty: decode_alignments)
+std::vector<VU> row_structures(dafs_hip_ctx* ctx, const Options& o, const std::vector<Fasta>& fa, std::vector<VL>& row_level) {
   std::vector<uint32_t> n_rows(fa.size(), 1), len, seqs;
   for (const Fasta& s : fa) {
     seqs.push_back((uint32_t)seqs.size());
@@ -1693,23 +1733,34 @@ std::vector<VU> row_structures(dafs_hip_ctx* ctx, const std::vector<Fasta>& fa, 
   const std::vector<size_t> at = starts_of(len);
   const std::vector<uint8_t> mask(at.back() ? at.back() : 1, 1);
   VU all(at.back() ? at.back() : 1);
-  check(dafs_hip_consensus_structures(ctx, (uint32_t)seqs.size(), n_rows.data(), len.data(), seqs.data(), mask.data(), th, all.data(), nullptr));
+  VL lv;
+  decode_alignments(ctx, o, n_rows, len, seqs, mask, all, lv);
   std::vector<VU> out;
-  for (size_t k = 0; k < seqs.size(); ++k) out.push_back(VU(all.begin() + at[k], all.begin() + at[k + 1]));
+  row_level.assign(seqs.size(), VL());
+  for (size_t k = 0; k < seqs.size(); ++k) {
+    out.push_back(VU(all.begin() + at[k], all.begin() + at[k + 1]));
+    if (!lv.empty()) row_level[k].assign(lv.begin() + at[k], lv.begin() + at[k + 1]);
+  }
   return out;
 }
 
 // The common secondary structure of a final alignment (:1857-1871; no RNAalifold term here), decoded over the rows in the
 // order root holds them.  ss0: the first decode of the alignment where the caller has it already (consensus_structures over
-// many alignments).
-VU final_structure(dafs_hip_ctx* ctx, const Options& o, const ALN& root, const VU* ss0) {
+// many alignments); without it the alignment is decoded here, as a batch of one, and level gets its levels (or stays empty).
+VU final_structure(dafs_hip_ctx* ctx, const Options& o, const ALN& root, const VU* ss0, VL* level = nullptr) {
   std::vector<uint32_t> rs;
   std::vector<uint8_t> rm;
   flatten(root, rs, rm);
   const uint32_t L = (uint32_t)root[0].second.size();
   VU ss(L);
   if (ss0) ss = *ss0;
-  else check(dafs_hip_consensus_structure(ctx, (uint32_t)root.size(), L, rs.data(), rm.data(), o.fold_th1[0], ss.data(), nullptr, nullptr));
+  else {
+    std::vector<VU> one;
+    std::vector<VL> one_level;
+    consensus_structures(ctx, o, {&root}, one, one_level);
+    ss = one[0];
+    if (level) *level = one_level[0];
+  }
   if (o.bp_update1) {  // :1863-1869: re-estimate under the decoded structure, decode again (SparseNussinov::decode(p, ss, str))
     std::vector<float> p((size_t)L * L);
     check(dafs_hip_update_basepairing(ctx, (uint32_t)root.size(), L, rs.data(), rm.data(), ss.data(), p.data()));
@@ -1769,10 +1820,11 @@ std::vector<std::string> row_texts(const std::vector<Fasta>& fa, const ALN& aln)
 // covariation table, whose cov_SS_cons line joins the block; the identity tables, whose weights join the block; the comparison.
 void finish_alignment(dafs_hip_ctx* ctx, const Options& o, const std::vector<Fasta>& fa, ALN& root, uint32_t first, FamilyOut& out,
                       const std::string* tree_line, const std::vector<uint8_t>* rf, const VU& ss_final, const Reliability& rl,
-                      const std::vector<VU>* row_ss) {
+                      const std::vector<VU>* row_ss, const VL* level = nullptr, const std::vector<VL>* row_level = nullptr) {
+  // level, row_level: the levels of ss_final and of the rows' structures under --fold-decoder Levels (null or empty: one kind of bracket)
   const uint32_t L = (uint32_t)root[0].second.size();
   std::vector<char> str(L + 1);
-  dafs_hip_make_brackets(L, ss_final.data(), str.data());
+  dafs_hip_make_brackets_levels(L, ss_final.data(), level && !level->empty() ? level->data() : nullptr, str.data());
   std::map<uint32_t, size_t> rel_at;  // sequence -> its first residue in rl.rel
   size_t tot = 0;
   for (const auto& row : root) { rel_at[row.first] = tot; tot += fa[row.first].size(); }
@@ -1803,7 +1855,8 @@ void finish_alignment(dafs_hip_ctx* ctx, const Options& o, const std::vector<Fas
     for (size_t r = 0; row_ss && r < root.size(); ++r) {
       const VU& own = (*row_ss)[root[r].first];
       std::vector<char> buf(own.size() + 1);
-      dafs_hip_make_brackets((uint32_t)own.size(), own.data(), buf.data());
+      const VL* own_level = row_level && !row_level->empty() && !(*row_level)[root[r].first].empty() ? &(*row_level)[root[r].first] : nullptr;
+      dafs_hip_make_brackets_levels((uint32_t)own.size(), own.data(), own_level ? own_level->data() : nullptr, buf.data());
       std::string line(rows[r].size(), '.');
       for (size_t c = 0, k = 0; c < line.size(); ++c)
         if (rows[r][c] != '-') line[c] = buf[k++];
@@ -1977,9 +2030,10 @@ int align_group(dafs_hip_ctx* ctx, const Options& o, Ranks& rk, int align_model,
   std::vector<const ALN*> roots;
   for (uint f = 0; f < F; ++f) roots.push_back(&aln[tbase[f + 1] - 1]);
   std::vector<VU> ss0;
-  consensus_structures(ctx, roots, o.fold_th1[0], ss0);
+  std::vector<VL> level0, row_level;
+  consensus_structures(ctx, o, roots, ss0, level0);
   std::vector<VU> row_ss;
-  if (o.row_structures && sto) row_ss = row_structures(ctx, fa, o.fold_th1[0]);
+  if (o.row_structures && sto) row_ss = row_structures(ctx, o, fa, row_level);
   // the annotation of all of them in one call, once every structure is final (-r and --bp-update1 are behind it)
   for (uint f = 0; f < F; ++f) ss0[f] = final_structure(ctx, o, *roots[f], &ss0[f]);
   std::vector<Reliability> rl(F);
@@ -1991,7 +2045,8 @@ int align_group(dafs_hip_ctx* ctx, const Options& o, Ranks& rk, int align_model,
       print_tree(tl, trees[f], fams[members[f]], (int)trees[f].size() - 1);
       tree_line = tl.str();
     }
-    finish_alignment(ctx, o, fa, aln[tbase[f + 1] - 1], first[f], *out[f], &tree_line, nullptr, ss0[f], rl[f], row_ss.empty() ? nullptr : &row_ss);
+    finish_alignment(ctx, o, fa, aln[tbase[f + 1] - 1], first[f], *out[f], &tree_line, nullptr, ss0[f], rl[f], row_ss.empty() ? nullptr : &row_ss,
+                     &level0[f], &row_level);
   }
   return 0;
 }
@@ -2059,13 +2114,15 @@ int run_add(const Options& o, int align_model) {
   std::vector<FamilyOut> recs = records(1, wanted_of(o));
   recs[0].os = &std::cout;
   std::vector<VU> row_ss;
-  if (o.row_structures) row_ss = row_structures(ctx, fa, o.fold_th1[0]);
+  std::vector<VL> row_level;
+  if (o.row_structures) row_ss = row_structures(ctx, o, fa, row_level);
   VU carried;  // --seed-structure: nothing is decoded
   if (o.seed_structure) carried = carry_structure(sd.ss, pl.seed_col, pl.width);
-  const VU ss = final_structure(ctx, o, root, o.seed_structure ? &carried : nullptr);
+  VL level;
+  const VU ss = final_structure(ctx, o, root, o.seed_structure ? &carried : nullptr, &level);
   std::vector<Reliability> rl(1);
   if (recs[0].wanted & kSto) reliabilities(ctx, fa, {&root}, {ss}, false, rl);
-  finish_alignment(ctx, o, fa, root, 0, recs[0], nullptr, &pl.rf, ss, rl[0], o.row_structures ? &row_ss : nullptr);
+  finish_alignment(ctx, o, fa, root, 0, recs[0], nullptr, &pl.rf, ss, rl[0], o.row_structures ? &row_ss : nullptr, &level, &row_level);
   std::cout.flush();
   write_outputs(o, recs[0].wanted, recs, nullptr);
   return 0;
@@ -2177,8 +2234,9 @@ int run_add_each(const Options& o, int align_model) {
     std::vector<const ALN*> ptrs;
     for (const ALN& a : roots) ptrs.push_back(&a);
     std::vector<VU> ss;
+    std::vector<VL> level(nf), row_level;
     if (!o.seed_structure) {
-      consensus_structures(ctx, ptrs, o.fold_th1[0], ss);
+      consensus_structures(ctx, o, ptrs, ss, level);
     } else {  // nothing is decoded: the seed's structure in every family's merged columns, and each row's support of it
       for (uint32_t f = 0; f < nf; ++f) ss.push_back(carry_structure(sd.ss, pl[f].seed_col, pl[f].width));
       std::vector<uint32_t> both, can, half;
@@ -2190,7 +2248,7 @@ int run_add_each(const Options& o, int align_model) {
       }
     }
     std::vector<VU> row_ss;
-    if (o.row_structures) row_ss = row_structures(ctx, fa, o.fold_th1[0]);
+    if (o.row_structures) row_ss = row_structures(ctx, o, fa, row_level);
     for (uint32_t f = 0; f < nf; ++f) ss[f] = final_structure(ctx, o, roots[f], &ss[f]);
     // the annotation, once every structure is final: all rows of every family for --stockholm, or for --seed-merged alone the
     // new row of every family (the first), which reads the listed pairs only
@@ -2201,7 +2259,8 @@ int run_add_each(const Options& o, int align_model) {
       new_pp[j0 + f].assign(rl[f].rel.begin(), rl[f].rel.begin() + lens[j0 + f]);
     }
     for (uint32_t f = 0; f < nf; ++f) {
-      finish_alignment(ctx, o, fa, roots[f], f * n, recs[j0 + f], nullptr, &pl[f].rf, ss[f], rl[f], o.row_structures ? &row_ss : nullptr);
+      finish_alignment(ctx, o, fa, roots[f], f * n, recs[j0 + f], nullptr, &pl[f].rf, ss[f], rl[f], o.row_structures ? &row_ss : nullptr,
+                       &level[f], &row_level);
       print_block(headers[j0 + f], recs[j0 + f]);
       if (o.seed_nearest && matched[j0 + f]) {  // the printed rows (finish_alignment sorted them): the m seed rows, then the new one
         const std::vector<std::string> rows = row_texts(fa, roots[f]);
@@ -2521,7 +2580,8 @@ int run(const Options& o, Ranks& rk) {
       throw "Folding model " + o.fold_model + " needs ViennaRNA, which this build does not contain; use -s CONTRAfold or --fold-aux";
     if (o.fold_model != "CONTRAfold") throw "Unknown folding model: " + o.fold_model;
   }
-  if (o.fold_decoder != "Nussinov" || o.ipknot) throw "Folding decoder IPknot needs an ILP solver, which this build does not contain";
+  if ((o.fold_decoder != "Nussinov" && o.fold_decoder != "Levels") || o.ipknot)
+    throw "Folding decoder IPknot needs an ILP solver, which this build does not contain; --fold-decoder Levels decodes pseudoknots level by level";
   if (o.max_iter <= 0) throw "-m 0 (exact ILP) needs an ILP solver, which this build does not contain";
   if ((o.bp_update || o.bp_update1) && !o.fold_aux.empty()) throw "--bp-update / --bp-update1 need a folding model (-s CONTRAfold), not --fold-aux";
   if (!o.devices.empty() && (!o.fold_aux.empty() || !o.align_aux.empty() || o.fourway != 0.0f))

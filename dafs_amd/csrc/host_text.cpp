@@ -1218,6 +1218,14 @@ extern "C" uint64_t dafs_host_structure_bytes(uint32_t n_rows, uint32_t len) {
   return 20 * l * l + 8 * n * l + 24 * l + 8 * n + 16 * 256 + 1024;
 }
 
+// The same alignment inside dafs_hip_consensus_structures_levels.  On top: the level's own structure and
+// the column keys (8 bytes a column) and the level bytes (1); the alignment's level descriptor, its per-level decoder
+// descriptor and index, four flags and three more scores (under 200 bytes); the 256-byte alignment of its three more arrays
+// and of a chunk's three more shared ones.
+extern "C" uint64_t dafs_host_structure_levels_bytes(uint32_t n_rows, uint32_t len) {
+  return dafs_host_structure_bytes(n_rows, len) + 12 * (uint64_t)len + 8 * 256 + 512;
+}
+
 // per chunk of dafs_hip_consensus_structures.  A choice, not a limit: 2 GiB hold some 3 500 pair alignments of 170 columns,
 // a dozen times what the device keeps resident at once, and the buffer stays with the context.
 extern "C" uint64_t dafs_host_structures_batch_bytes(void) { return 2ull << 30; }

@@ -51,11 +51,55 @@ class Result:
     pass
 
 
+DECODERS = ("Nussinov", "Levels")
+
+
+class LevelThresholds(tuple):
+    """th_s1 of a run with decoder="Levels" once its options are checked (decoder_option): one threshold per level"""
+
+
+def decoder_option(decoder, th_s, th_s1, bp_update1=False, seed_ss=None, who="pipeline.run"):
+    """The final decode of a driver from its options decoder, th_s, th_s1, checked before any work.
+    Returns what the driver then carries as th_s1: for "Nussinov" th_s1 itself, or its first entry when it is a sequence;
+    for "Levels" a LevelThresholds of every entry (of th_s1, else th_s, when a scalar).  Refused: an unknown decoder, more
+    than capi.MAX_LEVELS thresholds, a threshold of a higher level that is not positive, and "Levels" with bp_update1 or with
+    a seed structure."""
+    if isinstance(th_s1, LevelThresholds):
+        return th_s1
+    if decoder not in DECODERS:
+        raise ValueError("%s: unknown decoder %r (one of %s)" % (who, decoder, ", ".join(DECODERS)))
+    ths = None
+    if th_s1 is not None and np.ndim(th_s1) != 0:
+        ths = [float(x) for x in th_s1]
+        if not 1 <= len(ths) <= capi.MAX_LEVELS:
+            raise ValueError("%s: th_s1 holds %d thresholds; one to %d levels are decoded" % (who, len(ths), capi.MAX_LEVELS))
+    if decoder == "Nussinov":
+        return th_s1 if ths is None else ths[0]
+    if bp_update1:
+        raise ValueError("%s: decoder \"Levels\" with bp_update1 is not built: the reference folds again per level, under each "
+                         "level's constraint" % who)
+    if seed_ss is not None:
+        raise ValueError("%s: with seed_ss nothing is decoded: decoder \"Levels\" cannot be combined with it" % who)
+    if ths is None:
+        ths = [float(th_s if th_s1 is None else th_s1)]
+    if any(not x > 0.0 for x in ths[1:]):
+        raise ValueError("%s: the thresholds of the levels above the first must be positive" % who)
+    return LevelThresholds(ths)
+
+
+def _decode(ctx, alns, th1):
+    """The first decode of many final alignments in one call: per alignment (ss, level, scores); level and scores are None
+    under the plain decoder (th1 a number), the level array and the per-level scores under th1 a LevelThresholds"""
+    if isinstance(th1, LevelThresholds):
+        return [(ss, level, scores) for scores, ss, level in ctx.consensus_structures(alns, th1)]
+    return [(ss, None, None) for _, ss in ctx.consensus_structures(alns, th1)]
+
+
 def run(names, seqs, ctx=None, bp=None, w=4.0, eta0=0.5, t_max=600, w_pct_a=0.25, w_pct_s=0.25, th_a=0.01,
         th_s=0.2, th_s1=None, align_model=capi.ALIGN_PROBCONS, force_iters=0, timers=None, level_sync=False, slice_iters=None,
         mp=None, skip_uncoupled_folds=True, shard=None, round_us=None, w_pct_f=0.0, bp_update=False, bp_update1=False,
         reliability=False, covariation=False, row_structures=False, identity=False, compare=None, phylogeny=False,
-        phylogeny_bootstrap=0, phylogeny_seed=12345):
+        phylogeny_bootstrap=0, phylogeny_seed=12345, decoder="Nussinov"):
     """The whole run.  bp: per-sequence (rowptr, col, val) base-pairing rows (--fold-aux); None
     computes them with the device fold model.  mp: supplied matching probabilities (--align-aux), see Context.set_mp.
     shard: (torch.distributed module, torch device) of an initialised process group -- phase 1 (folds, pair posteriors,
@@ -68,8 +112,14 @@ def run(names, seqs, ctx=None, bp=None, w=4.0, eta0=0.5, t_max=600, w_pct_a=0.25
     sequences as stockholm.read_seed_structure returns it: the result also gets .compare (see compare).  phylogeny: "jc" or
     "p": the result also gets .phylogeny (see alignment_phylogeny), the neighbour-joining tree of the printed rows;
     phylogeny_bootstrap: that many bootstrap replicates drawn from phylogeny_seed: .phylogeny also gets
-    .support, .replicates, .seed and .support_table, and .newick carries the support in percent as the labels of the joins."""
+    .support, .replicates, .seed and .support_table, and .newick carries the support in percent as the labels of the joins.
+    decoder: "Nussinov", or "Levels" (DESIGN.md section 25): the common structure is decoded level by level at the
+    thresholds th_s1 (a sequence, one per level; a scalar or None: one level) and may hold pseudoknots.  .ss is then the
+    union of the levels, .ss_level the level of the pair at each of its columns (0xFF at unpaired ones), .ss_scores the
+    per-level scores, and .ss_str, the Stockholm SS_cons and the per-row structures print "()", "[]", "{}", "<>" for levels
+    0..3.  With "Nussinov" only the first entry of a sequence th_s1 is used."""
     import time
+    th_s1 = decoder_option(decoder, th_s, th_s1, bp_update1, None, "pipeline.run")
     phylogeny = phylogeny_option(phylogeny, phylogeny_bootstrap, phylogeny_seed)
     # combinations this driver does not implement are refused, not ignored (the command line, cli_main.cpp, has no level
     # batches: its --bp-update runs in the resident-node rounds and in the refinement's solve_node)
@@ -284,19 +334,19 @@ def _phase2_forest(ctx, own, fams, t, w, eta0, t_max, th_a, th_s, th_s1, force_i
     t.append(time.perf_counter())
     th1 = th_s if th_s1 is None else th_s1
     roots = [aln[(f, 2 * len(fm["seqs"]) - 2)] for f, fm in enumerate(fams)]
-    decoded = ctx.consensus_structures(roots, th1)
-    rows_ss = [None] * nf
+    decoded = _decode(ctx, roots, th1)
+    rows_ss = rows_level = [None] * nf
     if row_structures:
         lens = {fm["first"] + i: len(sq) for fm in fams for i, sq in enumerate(fm["seqs"])}
-        rows_ss = _row_structures(ctx, [sidx for sidx, _ in roots], lens, th1)
-    finals = [_final_structure(ctx, sidx, mask, th1, bp_update1, ss) for (sidx, mask), (_, ss) in zip(roots, decoded)]
+        rows_ss, rows_level = _row_structures(ctx, [sidx for sidx, _ in roots], lens, th1)
+    finals = [_final_structure(ctx, sidx, mask, th1, bp_update1, ss) for (sidx, mask), (ss, _, _) in zip(roots, decoded)]
     rls = ctx.alignment_reliabilities(roots, finals) if reliability else [None] * nf  # once every structure is final
     for f, (fm, res) in enumerate(zip(fams, results)):
         res.levels = levels
         res.rounds = rounds
         sidx, mask = roots[f]
         _final(ctx, res, fm["names"], fm["seqs"], fm["first"], sidx, mask, finals[f], rls[f], res.tree_line, None, covariation, rows_ss[f],
-               identity, compare, phylogeny)
+               identity, compare, phylogeny, decoded[f][1:], rows_level[f])
     t.append(time.perf_counter())
     # fold_launch: the folding is only started there; its kernels overlap `pair` and the first half of `pct_fold_tree`,
     # which also holds the wait for them
@@ -410,15 +460,17 @@ def alignment_phylogeny(ctx, row_names, rows, model="jc"):
 def _row_structures(ctx, sidx_per_alignment, lens, th):
     """Per alignment (its rows' global sequence indices) and per printed row (ascending index) the structure of that row's
     sequence alone from the context's current base-pairing store: one Context.consensus_structures call over all of them.
-    lens: global sequence index -> length."""
+    lens: global sequence index -> length.  Returns (structures, levels), each a list per alignment of one array per row; the
+    levels of an alignment are None under the plain decoder."""
     printed = [np.sort(np.asarray(sidx, np.uint32), kind="stable") for sidx in sidx_per_alignment]
     flat = [int(x) for rows in printed for x in rows]
-    got = ctx.consensus_structures([(np.array([x], np.uint32), np.ones((1, lens[x]), np.uint8)) for x in flat], th)
-    out, k = [], 0
+    got = _decode(ctx, [(np.array([x], np.uint32), np.ones((1, lens[x]), np.uint8)) for x in flat], th)
+    out, levels, k = [], [], 0
     for rows in printed:
-        out.append([ss for _, ss in got[k:k + len(rows)]])
+        out.append([ss for ss, _, _ in got[k:k + len(rows)]])
+        levels.append([level for _, level, _ in got[k:k + len(rows)]] if isinstance(th, LevelThresholds) else None)
         k += len(rows)
-    return out
+    return out, levels
 
 
 def _final_structure(ctx, sidx, mask, th1, bp_update1, ss):
@@ -560,7 +612,7 @@ def compare_result(ctx, reference, row_names, rows, ss, use_test=None, pp=None):
 
 
 def _final(ctx, res, names, seqs, first, sidx, mask, ss, rl, tree_line, rf=None, covariation=None, row_ss=None, identity=False, compare=None,
-           phylogeny=False):
+           phylogeny=False, levels=None, row_level=None):
     """The output of a final alignment (sidx: global sequence index per row, mask) with its common structure ss
     (_final_structure), into res: .ss, .ss_str, .rows, .output and, with rl, .reliability and .stockholm.  names / seqs: the
     family's, its first sequence at global index `first`.  rl: the alignment's dict of Context.alignment_reliabilities for
@@ -571,10 +623,17 @@ def _final(ctx, res, names, seqs, first, sidx, mask, ss, rl, tree_line, rf=None,
     and the `#=GR <name> SS` lines of the Stockholm block.  identity: .identity, alignment_identity of the printed rows in
     printed order over all columns, and .row_names, their Stockholm names; the Stockholm block then carries the `#=GS <name> WT` lines.
     compare: a reference (run's compare) -> .compare, the printed rows and ss against it (compare_result), and .row_names.
-    phylogeny: a model -> .phylogeny (alignment_phylogeny of the printed rows), and .row_names."""
+    phylogeny: a model -> .phylogeny (alignment_phylogeny of the printed rows), and .row_names.  levels: (level, scores) of a
+    structure decoded level by level (_decode), or None / (None, None) -> .ss_level, .ss_scores, and .ss_str with the bracket
+    kind of each pair's level; row_level: the same per printed row for row_ss."""
     phylogeny = phylogeny_model(phylogeny)
     res.ss = ss
-    res.ss_str = capi.make_brackets(ss)
+    res.root = (sidx, mask)  # the alignment as it was decoded: the rows in this order (the average depends on it)
+    if levels is None or levels[0] is None:
+        res.ss_str = capi.make_brackets(ss)
+    else:
+        res.ss_level, res.ss_scores = levels
+        res.ss_str = capi.make_brackets_levels(ss, res.ss_level)
     order = np.argsort(sidx, kind="stable")  # std::sort(aln) :1876
     lines = ([] if tree_line is None else [tree_line]) + [">SS_cons", res.ss_str]
     res.rows = []
@@ -588,7 +647,11 @@ def _final(ctx, res, names, seqs, first, sidx, mask, ss, rl, tree_line, rf=None,
     res.output = "\n".join(lines) + "\n"
     if row_ss is not None:
         res.row_ss = row_ss
-        res.row_ss_str = [stockholm.row_ss_str(row, x) for row, x in zip(res.rows, row_ss)]
+        if row_level is None:
+            res.row_ss_str = [stockholm.row_ss_str(row, x) for row, x in zip(res.rows, row_ss)]
+        else:
+            res.row_ss_level = row_level
+            res.row_ss_str = [stockholm.row_ss_str(row, x, lv) for row, x, lv in zip(res.rows, row_ss, row_level)]
     cov_chars = None
     if covariation:
         cv = _covariation(ctx, res.rows, ss, covariation)
@@ -652,6 +715,7 @@ def _printed_support(sup, sidx):
 def add(seed_names, seed_rows, names, seqs, ctx=None, w=4.0, eta0=0.5, t_max=600, w_pct_a=0.25, w_pct_s=0.25, th_a=0.01,
         th_s=0.2, th_s1=None, align_model=capi.ALIGN_PROBCONS, force_iters=0, slice_iters=None, skip_uncoupled_folds=True,
         round_us=None, w_pct_f=0.0, bp_update1=False, reliability=False, covariation=False, row_structures=False, seed_ss=None,
+        decoder="Nussinov",
         identity=False, compare=None, phylogeny=False, phylogeny_bootstrap=0, phylogeny_seed=12345):
     """Add new sequences to a fixed seed alignment without changing its columns (`dafs --seed`).
     seed_names / seed_rows: the seed's rows (letters and '.' / '-' gaps; stockholm.read_seed reads a file), checked and
@@ -673,6 +737,7 @@ def add(seed_names, seed_rows, names, seqs, ctx=None, w=4.0, eta0=0.5, t_max=600
     merged columns, insert columns unpaired, and the annotations see it.  The Result gains .support: per printed row, both,
     canonical, half and expected of Context.structure_support."""
     import time
+    th_s1 = decoder_option(decoder, th_s, th_s1, bp_update1, seed_ss, "pipeline.add")  # decoder: as in run()
     covariation = cov_options(covariation)
     phylogeny = phylogeny_option(phylogeny, phylogeny_bootstrap, phylogeny_seed)
     seed_names, seed_rows = stockholm.clean_seed(seed_names, seed_rows)
@@ -722,13 +787,19 @@ def add(seed_names, seed_rows, names, seqs, ctx=None, w=4.0, eta0=0.5, t_max=600
         th1 = th_s if th_s1 is None else th_s1
         rows_mask = np.concatenate([mask[m:], mask[:m]])
         ss_m = None if seed_ss is None else carry_structure(seed_ss, seed_col, width)
+        levels = None
         if ss_m is not None:
             res.support = _printed_support(ctx.structure_support([(sidx, rows_mask)], [ss_m])[0], sidx)
+        elif isinstance(th1, LevelThresholds):  # the batched call with one alignment
+            ss_m, *levels = _decode(ctx, [(sidx, rows_mask)], th1)[0]
         else:
             ss_m = _final_structure(ctx, sidx, rows_mask, th1, bp_update1, ctx.consensus_structure(sidx, rows_mask, th1)[1])
         rl = ctx.alignment_reliability(sidx, rows_mask, ss_m) if reliability else None
-        _final(ctx, res, all_names, all_seqs, 0, sidx, rows_mask, ss_m, rl, None, rf, covariation,
-               _row_structures(ctx, [sidx], dict(enumerate(map(len, all_seqs))), th1)[0] if row_structures else None, identity, compare, phylogeny)
+        row_ss, row_level = None, None
+        if row_structures:
+            row_ss, row_level = (x[0] for x in _row_structures(ctx, [sidx], dict(enumerate(map(len, all_seqs))), th1))
+        _final(ctx, res, all_names, all_seqs, 0, sidx, rows_mask, ss_m, rl, None, rf, covariation, row_ss, identity, compare, phylogeny,
+               levels, row_level)
         t.append(time.perf_counter())
         res.seconds = dict(phase1=t[3] - t[0], nodes=t[4] - t[3], final=t[5] - t[4], total=t[5] - t[0])
     finally:
@@ -780,6 +851,7 @@ def run_batch(families, ctx=None, max_bytes=None, **kw):
     if unknown:
         raise TypeError("pipeline.run_batch: unknown options %s" % sorted(unknown))
     opts.update(kw)
+    opts["th_s1"] = decoder_option(opts["decoder"], opts["th_s"], opts["th_s1"], opts["bp_update1"], None, "pipeline.run_batch")
     opts["phylogeny"] = phylogeny_option(opts["phylogeny"], opts["phylogeny_bootstrap"], opts["phylogeny_seed"])
     families = [(list(nm), list(sq)) for nm, sq in families]
     for nm, sq in families:
@@ -930,6 +1002,7 @@ def pairwise(names, seqs, pairs=None, ctx=None, max_bytes=None, **opts):
     if unknown:
         raise TypeError("pipeline.pairwise: unknown options %s" % sorted(unknown))
     o.update(opts)
+    o["th_s1"] = decoder_option(o["decoder"], o["th_s"], o["th_s1"], o["bp_update1"], None, "pipeline.pairwise")
     names, seqs = list(names), list(seqs)
     if len(names) != len(seqs):
         raise ValueError("pipeline.pairwise: one name per sequence")
@@ -1135,6 +1208,7 @@ def add_each(seed_names, seed_rows, names, seqs, ctx=None, max_bytes=None, merge
     if unknown:
         raise TypeError("pipeline.add_each: unknown options %s" % sorted(unknown))
     o.update(opts)
+    o["th_s1"] = decoder_option(o["decoder"], o["th_s"], o["th_s1"], o["bp_update1"], o["seed_ss"], "pipeline.add_each")
     if o["phylogeny"]:
         raise ValueError(capi.phylogeny_refusal(capi.PHY_NO_SEED_EACH))
     if o.get("phylogeny_bootstrap"):
@@ -1233,15 +1307,15 @@ def add_each(seed_names, seed_rows, names, seqs, ctx=None, max_bytes=None, merge
                 alns.append((np.concatenate([[f * n + m], np.arange(f * n, f * n + m)]).astype(np.uint32), mask))
                 rfs.append(rf)
             if seed_ss is None:
-                decoded = ctx.consensus_structures(alns, th1)
+                decoded = _decode(ctx, alns, th1)
             else:  # nothing is decoded: the seed's structure in every family's merged columns (seed columns where rf is set)
-                decoded = [(None, carry_structure(seed_ss, np.flatnonzero(rf).astype(np.uint32), len(rf))) for rf in rfs]
-                support = ctx.structure_support(alns, [ss for _, ss in decoded])
-            rows_ss = [None] * len(chunk)
+                decoded = [(carry_structure(seed_ss, np.flatnonzero(rf).astype(np.uint32), len(rf)), None, None) for rf in rfs]
+                support = ctx.structure_support(alns, [ss for ss, _, _ in decoded])
+            rows_ss = rows_level = [None] * len(chunk)
             if o["row_structures"]:
                 lens = {f * n + i: ln for f, j in enumerate(chunk) for i, ln in enumerate(seed_lens + [len(seqs[j])])}
-                rows_ss = _row_structures(ctx, [sidx for sidx, _ in alns], lens, th1)
-            finals = [_final_structure(ctx, sidx, mask, th1, o["bp_update1"], ss) for (sidx, mask), (_, ss) in zip(alns, decoded)]
+                rows_ss, rows_level = _row_structures(ctx, [sidx for sidx, _ in alns], lens, th1)
+            finals = [_final_structure(ctx, sidx, mask, th1, o["bp_update1"], ss) for (sidx, mask), (ss, _, _) in zip(alns, decoded)]
             # the annotation, once every structure is final: all rows of every family, or for the merged alignment alone the new
             # row of every family (the first), which reads the listed pairs only
             rls = [None] * len(chunk)
@@ -1266,7 +1340,7 @@ def add_each(seed_names, seed_rows, names, seqs, ctx=None, max_bytes=None, merge
                     for key in out.support:  # the new sequence is the first row of its alignment
                         out.support[key][j] = support[f][key][0]
                 _final(ctx, res, seed_names + [names[j]], seed_seqs + [seqs[j]], f * n, alns[f][0], alns[f][1], finals[f], rls[f], None,
-                       rfs[f], covariation, rows_ss[f], o["identity"])  # no tree per placement: refused above
+                       rfs[f], covariation, rows_ss[f], o["identity"], levels=decoded[f][1:], row_level=rows_level[f])  # no tree per placement: refused above
                 out.results[j] = res
                 out.score[j] = oj["score"]
                 out.iterations[j] = oj["iterations"]
@@ -1301,10 +1375,13 @@ def add_each(seed_names, seed_rows, names, seqs, ctx=None, max_bytes=None, merge
     return out
 
 
-def fold_each(names, seqs, th=0.2, ctx=None):
+def fold_each(names, seqs, th=0.2, ctx=None, decoder="Nussinov"):
     """Every sequence folded alone: CONTRAfold posteriors (Context.fold_posteriors, no consistency transform), then the MEA
     structure of every sequence's own base-pairing rows at threshold th, all in one Context.consensus_structures call.
-    Returns one Result per sequence with .name, .ss (uint32 per residue, NONE for unpaired), .ss_str and .score."""
+    Returns one Result per sequence with .name, .ss (uint32 per residue, NONE for unpaired), .ss_str and .score.
+    decoder "Levels" (as in run(); th may then be a sequence, one threshold per level): also .ss_level, and .score holds the
+    per-level scores."""
+    th = decoder_option(decoder, th, th, False, None, "pipeline.fold_each")
     names, seqs = list(names), list(seqs)
     if not seqs or len(names) != len(seqs):
         raise ValueError("pipeline.fold_each: at least one sequence and one name per sequence")
@@ -1319,9 +1396,14 @@ def fold_each(names, seqs, th=0.2, ctx=None):
         if own:
             ctx.close()
     out = []
-    for nm, (score, ss) in zip(names, got):
+    for nm, one in zip(names, got):
         res = Result()
-        res.name, res.ss, res.ss_str, res.score = nm, ss, capi.make_brackets(ss), score
+        if isinstance(th, LevelThresholds):
+            res.score, res.ss, res.ss_level = one
+            res.name, res.ss_str = nm, capi.make_brackets_levels(res.ss, res.ss_level)
+        else:
+            score, ss = one
+            res.name, res.ss, res.ss_str, res.score = nm, ss, capi.make_brackets(ss), score
         out.append(res)
     return out
 
@@ -1380,6 +1462,8 @@ def cluster(names, seqs, threshold=None, count=None, min_size=1, ctx=None, max_b
         raise TypeError("pipeline.cluster: unknown options %s" % sorted(unknown))
     cov_options(opts.get("covariation"))
     phylogeny_option(opts.get("phylogeny"), opts.get("phylogeny_bootstrap", 0), opts.get("phylogeny_seed", 12345))
+    decoder_option(opts.get("decoder", "Nussinov"), opts.get("th_s", known["th_s"]), opts.get("th_s1"), opts.get("bp_update1"), None,
+                   "pipeline.cluster")
     names, seqs = list(names), list(seqs)
     n = len(seqs)
     if n == 0 or len(names) != n or any(len(s) == 0 for s in seqs):

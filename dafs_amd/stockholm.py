@@ -52,10 +52,11 @@ def cov_ss_cons(ss, pair_e, e_max=0.05):
     return capi.host_text(capi._cov_ss_cons, len(ss), ss.ctypes.data, e.ctypes.data, float(e_max))
 
 
-def row_ss_str(row, ss):
+def row_ss_str(row, ss, level=None):
     """A row's own structure (ss over its residues: partner index at the left one, 0xFFFFFFFF otherwise) laid into the row's
-    columns: the bracket characters of capi.make_brackets at the residues' columns, '.' at gaps"""
-    chars = iter(capi.make_brackets(ss))
+    columns: the bracket characters of capi.make_brackets at the residues' columns, '.' at gaps.  level: the pairs' levels
+    (a structure decoded level by level): the characters of capi.make_brackets_levels."""
+    chars = iter(capi.make_brackets(ss) if level is None else capi.make_brackets_levels(ss, level))
     return "".join("." if ch == "-" else next(chars) for ch in row)
 
 

@@ -571,6 +571,9 @@ uint64_t dafs_host_seed_each_bytes(uint32_t m, const uint32_t* seed_lens, uint32
  * default budget of one of its chunks. */
 uint64_t dafs_host_structure_bytes(uint32_t n_rows, uint32_t len);
 uint64_t dafs_host_structures_batch_bytes(void);
+/* The same estimate inside dafs_hip_consensus_structures_levels: the level's own structure, the column
+ * keys, the level bytes, the per-level descriptors, flags and scores on top of dafs_host_structure_bytes. */
+uint64_t dafs_host_structure_levels_bytes(uint32_t n_rows, uint32_t len);
 /* The same two for dafs_hip_alignment_reliabilities. */
 uint64_t dafs_host_reliability_bytes(uint32_t n_rows, uint32_t len);
 uint64_t dafs_host_reliability_batch_bytes(void);
@@ -627,6 +630,17 @@ int dafs_hip_nw_decode_dense(dafs_hip_ctx* ctx, float th, uint32_t L1, uint32_t 
                              uint32_t* al, float* score);
 /* make_brackets (src/nussinov.cpp:401-413): str needs L+1 bytes. Host-only helper. */
 void dafs_hip_make_brackets(uint32_t L, const uint32_t* ss, char* str);
+/* The same for a structure of several levels: the pair at column i prints with the bracket kind of
+ * level[i], "()", "[]", "{}", "<>" for levels 0..3 (the reference's table, src/fold.cpp:57-58).  A pair whose level is
+ * outside 0..3 or whose partner is outside the structure prints as unpaired.  level == NULL: every pair is of level 0. */
+void dafs_hip_make_brackets_levels(uint32_t L, const uint32_t* ss, const uint8_t* level, char* str);
+/* Level-by-level decode of a dense host matrix (dafs_hip_consensus_structures_levels has the contract):
+ * th[nlevels], 1 <= nlevels <= DAFS_HIP_MAX_LEVELS, th[k] > 0 for k >= 1 (else DAFS_HIP_EINVAL, outputs untouched).
+ * ss[L] the merged structure, level[L] (may be NULL) the pair's level at both of its columns and 0xFF elsewhere,
+ * score[nlevels] (may be NULL).  Level 0 is dafs_hip_nussinov_decode without q at th[0], bit for bit. */
+#define DAFS_HIP_MAX_LEVELS 4u
+int dafs_hip_nussinov_decode_levels(dafs_hip_ctx* ctx, uint32_t nlevels, const float* th, uint32_t L, const float* p, uint32_t* ss,
+                                    uint8_t* level, float* score);
 
 /* ------------------------------------------------------------------------------------------
  * L1: fused guide-tree node solver.
@@ -719,6 +733,18 @@ int dafs_hip_consensus_structure(dafs_hip_ctx* ctx, uint32_t n, uint32_t len, co
  * overrides it), which does not change any result. */
 int dafs_hip_consensus_structures(dafs_hip_ctx* ctx, uint32_t nalign, const uint32_t* n_rows, const uint32_t* len, const uint32_t* seq,
                                   const uint8_t* mask, float th, uint32_t* ss, float* score);
+/* A consensus structure that may hold pseudoknots, decoded level by level; laid out as
+ * dafs_hip_consensus_structures, with th[nlevels], level (the len[a] bytes of every alignment one after another; may be NULL)
+ * and score[nalign * nlevels] (may be NULL).  Level 0 is the decode of dafs_hip_consensus_structures at th[0], bit for bit.
+ * Level k >= 1 is the same decoder at th[k] on the averaged matrix with every cell set to 0 that has a column paired at a
+ * lower level or that crosses no pair of some lower level; levels above an empty one are empty and score 0.  ss is the union
+ * of the levels, level[i] the pair's level at both of its columns and 0xFF at unpaired ones.  Each level is one of IPknot's
+ * (reference src/ipknot.cpp:145-206) given the lower ones; its stacking constraints (:209-247) and its joint optimum over
+ * the levels are not part of this.  Checks and chunks as in dafs_hip_consensus_structures; also DAFS_HIP_EINVAL for nlevels
+ * outside 1..DAFS_HIP_MAX_LEVELS or th[k] <= 0 at a k >= 1.  DAFS_HIP_EINVAL leaves the outputs untouched. */
+int dafs_hip_consensus_structures_levels(dafs_hip_ctx* ctx, uint32_t nalign, const uint32_t* n_rows, const uint32_t* len,
+                                         const uint32_t* seq, const uint8_t* mask, uint32_t nlevels, const float* th, uint32_t* ss,
+                                         uint8_t* level, float* score);
 
 /* DAFS::update_basepairing_probability (src/dafs.cpp:609-712; options --bp-update and --bp-update1), without the RNAalifold
  * term: the sequences of the alignment (rows seq / mask as in dafs_node_input) are folded again with CONTRAfold under the
