@@ -107,6 +107,8 @@ _fold_begin = _sig("dafs_hip_fold_posteriors_begin", C.c_int, [C.c_void_p, C.c_i
 _fold_end = _sig("dafs_hip_fold_posteriors_end", C.c_int, [C.c_void_p])
 _fold_constrained_begin = _sig("dafs_hip_fold_posteriors_constrained_begin", C.c_int, [C.c_void_p, C.c_int, C.c_float, C.POINTER(C.c_char_p)])
 _fold_constrained = _sig("dafs_hip_fold_posteriors_constrained", C.c_int, [C.c_void_p, C.c_int, C.c_float, C.POINTER(C.c_char_p)])
+_fold_levels_begin = _sig("dafs_hip_fold_posteriors_levels_begin", C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_uint32, C.POINTER(C.c_char_p)])
+_fold_levels = _sig("dafs_hip_fold_posteriors_levels", C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_uint32, C.POINTER(C.c_char_p)])
 _structure_support = _sig("dafs_hip_structure_support", C.c_int, [C.c_void_p, C.c_uint32] + [C.c_void_p] * 9)
 _pairs_from = _sig("dafs_hip_pairs_from", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, u32p, u32p])
 _families_from = _sig("dafs_hip_families_from", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, u32p, u32p])
@@ -215,6 +217,10 @@ _seed_parse_structure = _sig("dafs_host_seed_parse_structure", C.c_int, [C.c_cha
 _seed_clean_structure = _sig("dafs_host_seed_clean_structure", C.c_int, [C.c_uint32, _strs, _strs, C.c_char_p, C.c_void_p, u32p, _text])
 _fold_complementary = _sig("dafs_host_fold_complementary", C.c_int, [C.c_char, C.c_char])
 _row_constraint = _sig("dafs_host_row_constraint", C.c_int, [C.c_uint32, C.c_void_p, C.c_void_p, C.c_char_p, C.c_char_p])
+_seed_clean_structure_levels = _sig("dafs_host_seed_clean_structure_levels", C.c_int,
+                                    [C.c_uint32, _strs, _strs, C.c_char_p, C.c_void_p, C.c_void_p, u32p, _text])
+_row_constraint_levels = _sig("dafs_host_row_constraint_levels", C.c_int,
+                              [C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_char_p, C.c_void_p])
 _seed_each_bytes = _sig("dafs_host_seed_each_bytes", C.c_uint64, [C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32])
 _seed_parse = _sig("dafs_host_seed_parse", C.c_int, [C.c_char_p, C.c_size_t, u32p, _text, _text])
 _seed_clean = _sig("dafs_host_seed_clean", C.c_int, [C.c_uint32, _strs, _strs, _text])
@@ -767,31 +773,39 @@ class Context:
         return out
 
     def _constraints(self, constraints):
-        """per sequence a constraint string or None as the char* array of the library"""
+        """per sequence a constraint string or None, or a sequence of up to MAX_LEVELS of them (one per level), as the char*
+        array of the library: (array, None) for one string per sequence, (array[n * K], K) when an entry holds several"""
         cons = list(constraints)
         if self._lens is None or len(cons) != len(self._lens):
             raise ValueError("fold constraints: one entry (a string or None) per sequence of the context")
-        bs = [None if x is None else (x.encode("latin-1") if isinstance(x, str) else bytes(x)) for x in cons]
+        plain = all(x is None or isinstance(x, (str, bytes, bytearray)) for x in cons)
+        per = [[x] if x is None or isinstance(x, (str, bytes, bytearray)) else list(x) for x in cons]
+        K = max([len(x) for x in per] + [1])
+        bs = [None if x is None else (x.encode("latin-1") if isinstance(x, str) else bytes(x)) for row in per for x in row + [None] * (K - len(row))]
         if any(b is not None and b"\0" in b for b in bs):
             raise ValueError("fold constraints: a string holds a NUL byte")
-        return (C.c_char_p * len(bs))(*bs)
+        return (C.c_char_p * len(bs))(*bs), None if plain else K
 
     def fold_posteriors(self, th=0.01, model=0, constraints=None):
         """CONTRAfold base-pairing posteriors of every sequence -> the un-relaxed bp store.  constraints: per sequence None
         or "" (folded free) or len characters of "?.()" (dafs_hip_fold_posteriors_constrained); a refused string raises
-        DafsHipError with the sequence index in its text."""
+        DafsHipError with the sequence index in its text.  An entry may also be a sequence of up to four such strings, one
+        per level (dafs_hip_fold_posteriors_levels): the sequence is folded once per string that is
+        neither None nor empty (once, free, when none is), and a cell's value is the maximum over its folds."""
         if constraints is None:
             check(_fold_posteriors(self._h, model, th))
-        else:
-            check(_fold_constrained(self._h, model, th, self._constraints(constraints)))
+            return
+        arr, K = self._constraints(constraints)
+        check(_fold_constrained(self._h, model, th, arr) if K is None else _fold_levels(self._h, model, th, K, arr))
 
     def fold_begin(self, th=0.01, model=0, constraints=None):
         """enqueue the folding kernels on their own stream; fold_end() waits and fills the bp store.  constraints: as in
         fold_posteriors"""
         if constraints is None:
             check(_fold_begin(self._h, model, th))
-        else:
-            check(_fold_constrained_begin(self._h, model, th, self._constraints(constraints)))
+            return
+        arr, K = self._constraints(constraints)
+        check(_fold_constrained_begin(self._h, model, th, arr) if K is None else _fold_levels_begin(self._h, model, th, K, arr))
 
     def fold_end(self):
         check(_fold_end(self._h))
@@ -1329,6 +1343,29 @@ def row_constraint(mask_row, ss, residues):
     buf = C.create_string_buffer(int(m.astype(bool).sum()) + 1)
     check(_row_constraint(len(m), m.ctypes.data if len(m) else None, ss.ctypes.data if len(m) else None, b, buf))
     return buf.value.decode("latin-1")
+
+
+def row_constraint_levels(mask_row, ss, level, nlevels, residues):
+    """dafs_host_row_constraint_levels: one constraint per level of a structure with levels (level: per
+    column the pair's level, 0xFF at unpaired columns).  Returns a list of nlevels strings: string k forces the pairs of level
+    k as row_constraint does and puts '.' at both residues of a pair of another level that the row holds both ends of; a
+    string k >= 1 that forces nothing is "" (the row is not folded for that level)."""
+    m = np.ascontiguousarray(mask_row, np.uint8).reshape(-1)
+    ss = np.ascontiguousarray(ss, np.uint32).reshape(-1)
+    level = np.ascontiguousarray(level, np.uint8).reshape(-1)
+    if ss.shape != m.shape or level.shape != m.shape:
+        raise ValueError("row_constraint_levels: one structure entry and one level per column")
+    b = residues.encode("latin-1") if isinstance(residues, str) else bytes(residues)
+    if b"\0" in b:
+        raise ValueError("row_constraint_levels: the residues hold a NUL byte")
+    nlevels = int(nlevels)
+    if not 1 <= nlevels <= MAX_LEVELS:
+        raise ValueError("row_constraint_levels: 1 to %d levels" % MAX_LEVELS)
+    stride = int(m.astype(bool).sum()) + 1
+    buf = C.create_string_buffer(stride * nlevels)
+    check(_row_constraint_levels(len(m), m.ctypes.data if len(m) else None, ss.ctypes.data if len(m) else None,
+                                 level.ctypes.data if len(m) else None, nlevels, b, buf))
+    return [C.string_at(C.addressof(buf) + k * stride).decode("latin-1") for k in range(nlevels)]
 
 
 def build_tree(sim):

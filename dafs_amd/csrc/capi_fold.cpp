@@ -150,8 +150,12 @@ int run_job(dafs_hip_ctx* c, const fold_job& job, const uint8_t* d_codes, const 
 
 // The posteriors of a finished job of n sequences compacted with threshold th into st (rows with p > th), whose row pointers
 // lie at rp_off[0..n]; the entry arrays start at 8 entries per residue and grow when the kernel reports an overflow.
-int compact_job(dafs_hip_ctx* c, const cf_batch& B, uint32_t n, float th, const uint64_t* rp_off, uint64_t residues, bp_store& st) {
+// first (optional; a job of several folds per sequence): sequence x owns the folds first[x] .. first[x + 1],
+// and k_bp_compact_levels merges them; nullptr: one fold per sequence, k_bp_compact.
+int compact_job(dafs_hip_ctx* c, const cf_batch& B, uint32_t n, float th, const uint64_t* rp_off, uint64_t residues, bp_store& st,
+                const uint32_t* first = nullptr) {
   int rc;
+  if (first && (rc = c->cf_first.upload(first, n + 1, c->stream))) return rc;
   if ((rc = st.rowptr.reserve(rp_off[n]))) return rc;
   if ((rc = st.nnz.reserve(n))) return rc;
   if ((rc = st.bp_off.reserve(n + 1))) return rc;
@@ -162,9 +166,11 @@ int compact_job(dafs_hip_ctx* c, const cf_batch& B, uint32_t n, float th, const 
     if ((rc = st.col.reserve(cap))) return rc;
     if ((rc = st.val.reserve(cap))) return rc;
     if (hip_check(hipMemsetAsync(c->counters.ptr, 0, 4 * sizeof(unsigned long long), c->stream))) return DAFS_HIP_ELAUNCH;
-    if ((rc = bp_compact_launch(B, n, th, st.rp_off.ptr, st.rowptr.ptr, st.col.ptr, st.val.ptr, st.bp_off.ptr, st.nnz.ptr,
-                                c->counters.ptr, cap, (int*)(c->counters.ptr + 2), c->stream)))
-      return rc;
+    rc = first ? bp_compact_levels_launch(B, n, th, c->cf_first.ptr, st.rp_off.ptr, st.rowptr.ptr, st.col.ptr, st.val.ptr, st.bp_off.ptr, st.nnz.ptr,
+                                          c->counters.ptr, cap, (int*)(c->counters.ptr + 2), c->stream)
+               : bp_compact_launch(B, n, th, st.rp_off.ptr, st.rowptr.ptr, st.col.ptr, st.val.ptr, st.bp_off.ptr, st.nnz.ptr, c->counters.ptr, cap,
+                                   (int*)(c->counters.ptr + 2), c->stream);
+    if (rc) return rc;
     unsigned long long h[4];
     if (hip_check(hipMemcpyAsync(h, c->counters.ptr, sizeof h, hipMemcpyDeviceToHost, c->stream))) return DAFS_HIP_ELAUNCH;
     if (hip_check(hipStreamSynchronize(c->stream))) return DAFS_HIP_ELAUNCH;
@@ -175,34 +181,50 @@ int compact_job(dafs_hip_ctx* c, const cf_batch& B, uint32_t n, float th, const 
   }
 }
 
+// One fold of the context's sequence x into the job: under con (nullptr or empty: free), whose map joins maps.  A refused
+// string leaves the reason in *why.  check_pairs: a forced pair must be one CONTRAfold can form.
+int add_fold(const dafs_hip_ctx* c, uint32_t x, const char* con, bool check_pairs, fold_job& job, std::vector<int>& maps, const char** why) {
+  if (x >= c->len.size()) { *why = "an unknown sequence"; return DAFS_HIP_EINVAL; }
+  const uint32_t L = c->len[x];
+  if (!con || !con[0]) {  // empty = unconstrained (wrapper.cpp:188)
+    job.add(L, c->off[x], false, 0);
+    return DAFS_HIP_OK;
+  }
+  if (strnlen(con, L) < L) { *why = "a constraint shorter than its sequence"; return DAFS_HIP_EINVAL; }
+  std::vector<int> one;
+  const int rc = parse_constraint(con, L, one, why);
+  if (rc) return rc;
+  for (uint32_t i = 1; check_pairs && i <= L; ++i)
+    if (one[i] > (int)i && !dafs_host_fold_complementary(c->seq[c->off[x] + i - 1], c->seq[c->off[x] + one[i] - 1])) {
+      *why = "a forced pair of residues that CONTRAfold cannot pair";
+      return DAFS_HIP_EINVAL;
+    }
+  job.add(L, c->off[x], true, (uint32_t)maps.size());
+  maps.insert(maps.end(), one.begin(), one.end());
+  return DAFS_HIP_OK;
+}
+
 // The job of folding the context's sequences seq[0..n) (seq nullptr: 0 .. n-1), sequence r under cons[r] (nullptr or empty:
 // free), and the constraint maps of the constrained ones one after another.  A refused string leaves its row in *bad and the
 // reason in *why.  check_pairs: a forced pair must be one CONTRAfold can form.
 int make_job(const dafs_hip_ctx* c, uint32_t n, const uint32_t* seq, const char* const* cons, bool check_pairs, fold_job& job,
              std::vector<int>& maps, uint32_t* bad, const char** why) {
-  std::vector<int> one;
   for (uint32_t r = 0; r < n; ++r) {
-    const uint32_t x = seq ? seq[r] : r;
     *bad = r;
-    if (x >= c->len.size()) { *why = "an unknown sequence"; return DAFS_HIP_EINVAL; }
-    const uint32_t L = c->len[x];
-    const char* con = cons ? cons[r] : nullptr;
-    if (!con || !con[0]) {  // empty = unconstrained (wrapper.cpp:188)
-      job.add(L, c->off[x], false, 0);
-      continue;
-    }
-    if (strnlen(con, L) < L) { *why = "a constraint shorter than its sequence"; return DAFS_HIP_EINVAL; }
-    const int rc = parse_constraint(con, L, one, why);
+    const int rc = add_fold(c, seq ? seq[r] : r, cons ? cons[r] : nullptr, check_pairs, job, maps, why);
     if (rc) return rc;
-    for (uint32_t i = 1; check_pairs && i <= L; ++i)
-      if (one[i] > (int)i && !dafs_host_fold_complementary(c->seq[c->off[x] + i - 1], c->seq[c->off[x] + one[i] - 1])) {
-        *why = "a forced pair of residues that CONTRAfold cannot pair";
-        return DAFS_HIP_EINVAL;
-      }
-    job.add(L, c->off[x], true, (uint32_t)maps.size());
-    maps.insert(maps.end(), one.begin(), one.end());
   }
   return DAFS_HIP_OK;
+}
+
+// the job in flight on the folding stream: _end compacts it
+void fold_started(dafs_hip_ctx* c, const cf_batch& B, float th) {
+  c->fold_batch.assign((const uint8_t*)&B, (const uint8_t*)&B + sizeof B);
+  c->fold_pending = true;
+  c->fold_th = th;
+  c->bp[0].valid = false;
+  c->bp[1].valid = false;
+  c->cur_bp = 0;
 }
 
 }  // namespace
@@ -232,13 +254,51 @@ extern "C" int dafs_hip_fold_posteriors_constrained_begin(dafs_hip_ctx* c, int m
   cf_batch B;
   rc = run_job(c, job, c->codes.ptr, maps.empty() ? nullptr : c->cf_cons.ptr, &B, c->fold_stream);
   if (rc) return rc;
-  c->fold_batch.assign((const uint8_t*)&B, (const uint8_t*)&B + sizeof B);
-  c->fold_pending = true;
-  c->fold_th = th;
-  c->bp[0].valid = false;
-  c->bp[1].valid = false;
-  c->cur_bp = 0;
+  c->fold_first.clear();
+  fold_started(c, B, th);
   return DAFS_HIP_OK;
+}
+
+// Several folds per sequence in one batch (DAFS::update_basepairing_probability, dafs.cpp:635-661, folds
+// a row once per level): the folds of sequence x lie one after another in the job and share its codes; _end merges them.
+extern "C" int dafs_hip_fold_posteriors_levels_begin(dafs_hip_ctx* c, int model, float th, uint32_t nlevels, const char* const* constraints) {
+  if (!c || c->len.empty() || model != DAFS_FOLD_CONTRAFOLD) return DAFS_HIP_EINVAL;
+  if (hip_check(hipSetDevice(c->device))) return DAFS_HIP_ENODEV;
+  if (c->fold_pending) return DAFS_HIP_EINVAL;
+  if (nlevels < 1 || nlevels > DAFS_HIP_MAX_LEVELS) {
+    set_last_error(("fold constraints: " + std::to_string(nlevels) + " levels; a sequence has 1 to " + std::to_string(DAFS_HIP_MAX_LEVELS)).c_str());
+    return DAFS_HIP_EINVAL;
+  }
+  const uint32_t n = (uint32_t)c->len.size();
+  fold_job job;
+  std::vector<int> maps;
+  std::vector<uint32_t> first(n + 1, 0);
+  int rc;
+  for (uint32_t x = 0; x < n; ++x) {
+    first[x] = (uint32_t)job.seqs.size();
+    for (uint32_t k = 0; constraints && k < nlevels; ++k) {
+      const char* con = constraints[(size_t)x * nlevels + k];
+      if (!con || !con[0]) continue;  // no fold of x at level k
+      const char* why = "";
+      if ((rc = add_fold(c, x, con, true, job, maps, &why))) {
+        set_last_error(("fold constraints: sequence " + std::to_string(x) + ", level " + std::to_string(k) + ": " + why).c_str());
+        return rc;
+      }
+    }
+    if (job.seqs.size() == first[x]) job.add(c->len[x], c->off[x], false, 0);  // no string at all: once, free
+  }
+  first[n] = (uint32_t)job.seqs.size();
+  if (!maps.empty() && (rc = c->cf_cons.upload(maps.data(), maps.size(), c->fold_stream))) return rc;
+  cf_batch B;
+  if ((rc = run_job(c, job, c->codes.ptr, maps.empty() ? nullptr : c->cf_cons.ptr, &B, c->fold_stream))) return rc;
+  c->fold_first.swap(first);
+  fold_started(c, B, th);
+  return DAFS_HIP_OK;
+}
+
+extern "C" int dafs_hip_fold_posteriors_levels(dafs_hip_ctx* c, int model, float th, uint32_t nlevels, const char* const* constraints) {
+  const int rc = dafs_hip_fold_posteriors_levels_begin(c, model, th, nlevels, constraints);
+  return rc ? rc : dafs_hip_fold_posteriors_end(c);
 }
 
 extern "C" int dafs_hip_fold_posteriors_begin(dafs_hip_ctx* c, int model, float th) {
@@ -253,7 +313,7 @@ extern "C" int dafs_hip_fold_posteriors_end(dafs_hip_ctx* c) {
   cf_batch B;
   memcpy(&B, c->fold_batch.data(), sizeof B);
   const uint32_t n = (uint32_t)c->len.size();
-  return compact_job(c, B, n, c->fold_th, c->seq_rp_off.data(), c->off[n], c->bp[0]);
+  return compact_job(c, B, n, c->fold_th, c->seq_rp_off.data(), c->off[n], c->bp[0], c->fold_first.empty() ? nullptr : c->fold_first.data());
 }
 
 extern "C" int dafs_hip_fold_posteriors_constrained(dafs_hip_ctx* c, int model, float th, const char* const* constraints) {

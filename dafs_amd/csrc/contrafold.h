@@ -49,5 +49,9 @@ int contrafold_launch(const cf_batch& B, uint32_t nseq, uint32_t max_len, hipStr
 int bp_compact_launch(const cf_batch& B, uint32_t nseq, float th, const uint64_t* rp_off, uint32_t* out_rowptr, uint32_t* out_col,
                       float* out_val, uint64_t* out_off, uint32_t* out_nnz, unsigned long long* pool_top, uint64_t pool_cap, int* status,
                       hipStream_t st);
+// the same from several folds per sequence, a cell's value their maximum: sequence x owns the folds first[x] .. first[x + 1]
+int bp_compact_levels_launch(const cf_batch& B, uint32_t nseq, float th, const uint32_t* first, const uint64_t* rp_off, uint32_t* out_rowptr,
+                             uint32_t* out_col, float* out_val, uint64_t* out_off, uint32_t* out_nnz, unsigned long long* pool_top,
+                             uint64_t pool_cap, int* status, hipStream_t st);
 
 }  // namespace dafs

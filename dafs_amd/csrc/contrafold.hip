@@ -817,6 +817,74 @@ __global__ __launch_bounds__(256) void k_bp_compact(cf_batch B, float th, const 
   }
 }
 
+// The same rows from several folds of one sequence: sequence x owns the folds first[x] .. first[x + 1]
+// of the batch (1 to 4, all of its length), and a cell's value is the fmaxf over their dense posteriors, taken in fold order --
+// exact, so the result does not depend on how the work is laid out; no floating-point atomics.  One workgroup per sequence, one
+// wavefront per row i, lanes along j: 64 neighbouring cells per load, the row's count is the popcount of the ballots, and an
+// entry's place is the row's running count plus the ballot's prefix below its lane, which keeps the columns ascending.  The
+// row-pointer scan and the reservation in the entry pool are k_bp_compact's.
+__global__ __launch_bounds__(256) void k_bp_compact_levels(cf_batch B, float th, const uint32_t* first, const uint64_t* rp_off, uint32_t* out_rowptr,
+                                                           uint32_t* out_col, float* out_val, uint64_t* out_off, uint32_t* out_nnz,
+                                                           unsigned long long* pool_top, uint64_t pool_cap, int* status) {
+  const uint32_t x = blockIdx.x;
+  const uint32_t f0 = first[x], nf = first[x + 1] - f0;
+  const int L = (int)B.seqs[f0].len;
+  const float* p0 = B.post + B.seqs[f0].post_off;
+  const float* p1 = nf > 1 ? B.post + B.seqs[f0 + 1].post_off : p0;
+  const float* p2 = nf > 2 ? B.post + B.seqs[f0 + 2].post_off : p0;
+  const float* p3 = nf > 3 ? B.post + B.seqs[f0 + 3].post_off : p0;
+  uint32_t* rowptr = out_rowptr + rp_off[x];
+  __shared__ unsigned long long s_off;
+  __shared__ int s_ok;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, waves = blockDim.x >> 6;
+  auto offs = [L](int i) { return i * (2 * (L + 1) - i - 1) / 2; };
+  auto cell = [&](int at) {  // fold order; a fold the sequence does not have repeats the first, which changes nothing
+    float v = p0[at];
+    if (nf > 1) v = fmaxf(v, p1[at]);
+    if (nf > 2) v = fmaxf(v, p2[at]);
+    if (nf > 3) v = fmaxf(v, p3[at]);
+    return v;
+  };
+  for (int i = 1 + wave; i <= L; i += waves) {
+    uint32_t n = 0;
+    for (int j0 = i; j0 <= L; j0 += 64) {
+      const int j = j0 + lane;
+      const bool keep = j <= L && cell(offs(i) + j) > th;
+      n += (uint32_t)__popcll(__ballot(keep));
+    }
+    if (lane == 0) rowptr[i] = n;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    rowptr[0] = 0;
+    for (int i = 0; i < L; ++i) rowptr[i + 1] += rowptr[i];
+    const uint32_t n = rowptr[L];
+    const unsigned long long o = atomicAdd(pool_top, (unsigned long long)n);
+    s_off = o;
+    s_ok = o + n <= pool_cap;
+    if (!s_ok) atomicExch(status, DAFS_HIP_EOVERFLOW);
+    out_off[x] = o;
+    out_nnz[x] = n;
+  }
+  __syncthreads();
+  if (!s_ok) return;
+  for (int i = 1 + wave; i <= L; i += waves) {
+    unsigned long long pos = s_off + rowptr[i - 1];
+    for (int j0 = i; j0 <= L; j0 += 64) {
+      const int j = j0 + lane;
+      const float v = j <= L ? cell(offs(i) + j) : 0.0f;
+      const bool keep = j <= L && v > th;
+      const uint64_t b = __ballot(keep);
+      if (keep) {
+        const unsigned long long at = pos + (unsigned long long)__popcll(b & ((1ull << lane) - 1ull));
+        out_col[at] = (uint32_t)(j - 1);
+        out_val[at] = v;
+      }
+      pos += (unsigned long long)__popcll(b);
+    }
+  }
+}
+
 int contrafold_launch(const cf_batch& B, uint32_t nseq, uint32_t max_len, hipStream_t st) {
   if (!nseq) return DAFS_HIP_OK;
   const size_t ints = (size_t)CF_INTS(max_len) * sizeof(int);
@@ -875,6 +943,15 @@ int bp_compact_launch(const cf_batch& B, uint32_t nseq, float th, const uint64_t
   if (!nseq) return DAFS_HIP_OK;
   STAGE_LAUNCH(ST_BP_COMPACT, st) hipLaunchKernelGGL(k_bp_compact, dim3(nseq), dim3(256), 0, st, B, th, rp_off, out_rowptr, out_col, out_val, out_off, out_nnz, pool_top,
                      pool_cap, status);
+  return hip_check(hipGetLastError()) ? DAFS_HIP_ELAUNCH : DAFS_HIP_OK;
+}
+
+int bp_compact_levels_launch(const cf_batch& B, uint32_t nseq, float th, const uint32_t* first, const uint64_t* rp_off, uint32_t* out_rowptr,
+                             uint32_t* out_col, float* out_val, uint64_t* out_off, uint32_t* out_nnz, unsigned long long* pool_top,
+                             uint64_t pool_cap, int* status, hipStream_t st) {
+  if (!nseq) return DAFS_HIP_OK;
+  STAGE_LAUNCH(ST_BP_COMPACT_LEVELS, st) hipLaunchKernelGGL(k_bp_compact_levels, dim3(nseq), dim3(256), 0, st, B, th, first, rp_off, out_rowptr, out_col,
+                     out_val, out_off, out_nnz, pool_top, pool_cap, status);
   return hip_check(hipGetLastError()) ? DAFS_HIP_ELAUNCH : DAFS_HIP_OK;
 }
 

@@ -172,6 +172,7 @@ struct dafs_hip_ctx {
   bool fold_pending = false;          // dafs_hip_fold_posteriors_begin without its _end
   float fold_th = 0.0f;
   std::vector<uint8_t> fold_batch;    // the cf_batch of the pending job (contrafold.h), kept opaque here
+  std::vector<uint32_t> fold_first;   // a pending job of dafs_hip_fold_posteriors_levels_begin: per sequence its first fold, [nseq + 1]
   // sequences
   std::string seq;
   std::vector<uint32_t> len, off;
@@ -206,6 +207,7 @@ struct dafs_hip_ctx {
   bool cf_params_ready = false;
   dafs::dev_buf<uint8_t> d_cf_params, cf_seqs, cf_codes;
   dafs::dev_buf<int> cf_iws, cf_cons;
+  dafs::dev_buf<uint32_t> cf_first;  // fold_first on the device
   dafs::dev_buf<float> cf_fws, cf_post, cf_logz;
   dafs::dev_buf<unsigned long long> cf_stamps;
   dafs::stage_recorder stages;  // dafs_hip_stage_timing / _report
@@ -325,7 +327,7 @@ struct dafs_hip_ctx {
     codes.release(); d_len.release(); d_seq_rp_off.release(); fam.release(); tasks.release(); scratch.release(); task_sim.release();
     counters.release(); d_sim.release(); d_pair_x.release(); d_pair_y.release(); mp_ent2.release(); mp_ident2.release(); pct_tasks.release(); pct_list.release(); work.release(); work2.release(); d_nodes.release(); d_paused.release(); d_nodes2.release(); d_paused2.release(); d_tref.release(); for (int k = 0; k < 2; ++k) { d_pack_off[k].release(); d_pack[k].release(); } dd_release();
     for (int k = 0; k < 2; ++k) { if (h_paused[k]) (void)hipHostFree(h_paused[k]); h_paused[k] = nullptr; h_paused_cap[k] = 0; }
-    d_cf_params.release(); cf_seqs.release(); cf_codes.release(); cf_iws.release(); cf_cons.release(); cf_fws.release(); cf_post.release(); cf_logz.release();
+    d_cf_params.release(); cf_seqs.release(); cf_codes.release(); cf_iws.release(); cf_cons.release(); cf_first.release(); cf_fws.release(); cf_post.release(); cf_logz.release();
     for (int k = 0; k < 2; ++k) { mp[k].release(); bp[k].release(); }
     bp_rows.release();
   }

@@ -81,6 +81,7 @@ struct Options {
   std::string seed_scores;      // --seed-scores OUT
   std::string seed_merged;      // --seed-merged OUT: with --seed-each and --seed-structure, all placements in one Stockholm block
   bool seed_structure = false;  // --seed-structure: with --seed, the seed's SS_cons is fixed like its columns
+  bool knots = false;           // --knots: the structures that are read may cross
   bool pairwise = false;  // --pairwise: every pair of FILE's sequences aligned as a two-sequence run
   std::string pairwise_scores;  // --pairwise-scores OUT
   std::string covariation;      // --covariation OUT
@@ -169,6 +170,14 @@ const char* kHelp =
     "                        Stockholm seed, the SS_cons record of an aligned-FASTA seed -- is fixed like its columns: the seed\n"
     "                        rows are folded under it, nothing is decoded, and the printed SS_cons is the seed's with '.' at\n"
     "                        insert columns.  Not with --bp-update1, -T or -G\n"
+    "      --knots           With --seed, --describe or --compare-ref: the structures that are read may cross.  Groups, in\n"
+    "                        this order: () [] {} <>, then the letters A..Z (upper case opens, the same letter in lower case\n"
+    "                        closes, as Rfam marks pseudoknots); each group is matched with itself, and group after group goes\n"
+    "                        to the lowest of four levels at which it crosses no pair already there.  With --seed-structure\n"
+    "                        every seed row is folded once per level, that level's pairs forced and the other levels' pairs\n"
+    "                        unpaired, and a cell keeps the largest of its values; SS_cons prints () [] {} <> for levels 0..3.\n"
+    "                        --describe prints \">SS_cons\" and the structure it read that way.  Without --knots such\n"
+    "                        structures are refused and letters are unpaired\n"
     "      --pairwise        Align every pair of the one FILE's sequences (at least two) as two-sequence runs, the pairs\n"
     "                        in row-major order: per pair a line \"==> i j <==\" (1-based input indices) and then what\n"
     "                        dafs prints for a file of those two sequences; --stockholm writes one block per pair.\n"
@@ -275,8 +284,8 @@ const char* kHelp =
     "                        the same decoder at entry k over the cells whose columns are still free and that cross a pair of\n"
     "                        every lower level.  Printed as () [] {} <>, in SS_cons and with --row-structures.  Each level is one\n"
     "                        of IPknot's given the lower ones, without its stacking constraints: not IPknot's optimum.  Not with\n"
-    "                        --bp-update1 or --seed-structure.  The readers of --seed, --describe and --compare-ref refuse\n"
-    "                        structures whose bracket kinds cross, so this output cannot yet be read back as a seed.\n"
+    "                        --bp-update1 or --seed-structure.  The readers of --seed, --describe and --compare-ref take\n"
+    "                        structures whose bracket kinds cross with --knots, so this output can be a seed again.\n"
     "                        With Nussinov only the first entry of -T / -G is used.  IPknot needs an ILP solver: not built.\n"
     "  -q, --fold-pct arg    Weight of PCT for base-pairing probabilities (default: 0.25)\n"
     "  -t, --fold-th arg     Threshold for base-pairing probabilities (default: 0.2)\n"
@@ -309,7 +318,7 @@ Options parse(int argc, char** argv) {
       {"bp-update", {0, false}}, {"bp-update1", {0, false}}, {"fold-aux", {0, true}}, {"save-align-aux", {0, true}},
       {"save-fold-aux", {0, true}}, {"device", {0, true}}, {"devices", {0, true}}, {"input", {0, true}},
       {"stockholm", {0, true}}, {"row-structures", {0, false}}, {"seed", {0, true}}, {"pairwise", {0, false}}, {"pairwise-scores", {0, true}},
-      {"seed-each", {0, false}}, {"seed-scores", {0, true}}, {"seed-merged", {0, true}}, {"seed-structure", {0, false}},
+      {"seed-each", {0, false}}, {"seed-scores", {0, true}}, {"seed-merged", {0, true}}, {"seed-structure", {0, false}}, {"knots", {0, false}},
       {"covariation", {0, true}}, {"cov-shuffles", {0, true}}, {"cov-seed", {0, true}}, {"cov-null", {0, true}}, {"identity", {0, true}},
       {"phylogeny", {0, true}}, {"phylogeny-model", {0, true}}, {"cov-tree", {0, true}},
       {"phylogeny-bootstrap", {0, true}}, {"phylogeny-seed", {0, true}}, {"phylogeny-support", {0, true}},
@@ -389,6 +398,7 @@ Options parse(int argc, char** argv) {
     }
     else if (name == "seed-each") o.seed_each = true;
     else if (name == "seed-structure") o.seed_structure = true;
+    else if (name == "knots") o.knots = true;
     else if (name == "seed-scores") {
       if (value.empty()) throw std::string("--seed-scores needs a file name");
       o.seed_scores = value;
@@ -574,7 +584,7 @@ Options parse(int argc, char** argv) {
     throw std::string("--pairwise: two rows carry no covariation; --covariation, --cov-shuffles and --cov-seed cannot be combined with --pairwise");
   if (!o.describe.empty()) {  // a finished alignment: nothing that aligns, and no FILE
     for (const std::string& g : given)
-      if (g != "describe" && g != "identity" && g != "identity-matrix" && g != "covariation" && g != "cov-shuffles" && g != "cov-seed" && g != "cov-null" && g != "device" &&
+      if (g != "describe" && g != "identity" && g != "identity-matrix" && g != "covariation" && g != "cov-shuffles" && g != "cov-seed" && g != "cov-null" && g != "device" && g != "knots" &&
           g.compare(0, 9, "phylogeny") != 0 && g != "cov-tree" &&
           g.compare(0, 7, "compare") != 0)
         throw "--describe reads a finished alignment: --" + g + " cannot be combined with --describe";
@@ -596,6 +606,8 @@ Options parse(int argc, char** argv) {
   if (!o.seed_scores.empty() && !o.seed_each) throw std::string("--seed-scores needs --seed-each");
   if (!o.seed_merged.empty() && !o.seed_each) throw std::string("--seed-merged needs --seed-each");
   if (!o.seed_merged.empty() && !o.seed_structure) throw std::string(dafs_host_merged_refusal());
+  if (o.knots && o.seed.empty() && o.describe.empty() && o.compare_ref.empty())
+    throw std::string("--knots says how structures are read: it needs --seed, --describe or --compare-ref");
   if (o.seed_structure) {  // the structure is the seed's: nothing is decoded, so nothing sets a decoder's threshold
     if (o.seed.empty()) throw std::string("--seed-structure needs --seed");
     if (o.bp_update1) throw std::string("--seed-structure: nothing is decoded; --bp-update1 cannot be combined with --seed-structure");
@@ -1108,6 +1120,8 @@ void write_identity(const Options& o, const std::vector<IdentityText>& idt, cons
   if (!o.identity_matrix.empty()) write_tables("--identity-matrix", o.identity_matrix, matrices, headers);
 }
 
+typedef std::vector<uint8_t> VL;  // per column the level of its pair, 0xFF at unpaired columns (DESIGN.md sections 25 and 26)
+
 // --compare: a printed alignment against the reference of --compare-ref (dafs_hip_alignment_compare; DESIGN.md section 19;
 // pipeline.compare is the Python twin)
 struct CompareText {
@@ -1116,8 +1130,9 @@ struct CompareText {
 
 // An alignment file as the seed reader reads it: names, cleaned rows, the structure over the cleaned columns if it has one
 // (has_ss), and with pp the PP rows of a Stockholm file (left empty when it has no PP line)
+// level (--knots): the structure may cross (dafs_host_seed_clean_structure_levels), and *level receives its pairs' levels
 void read_alignment(const std::string& file, const std::string& option, std::vector<std::string>& names, std::vector<std::string>& rows, VU& ss,
-                    bool& has_ss, std::vector<std::string>* pp = nullptr) {
+                    bool& has_ss, std::vector<std::string>* pp = nullptr, VL* level = nullptr) {
   std::ifstream is(file.c_str(), std::ios::binary);
   if (!is.is_open()) throw option + ": cannot open " + file;
   const std::string text((std::istreambuf_iterator<char>(is)), std::istreambuf_iterator<char>());
@@ -1132,7 +1147,14 @@ void read_alignment(const std::string& file, const std::string& option, std::vec
   if (has_ss) {
     ss.assign(rows.empty() ? 1 : rows[0].size() + 1, DAFS_HIP_NONE);
     uint32_t columns = 0;
-    check_text(dafs_host_seed_clean_structure(n, c_strs(names).data(), c_strs(rows).data(), structure.c_str(), ss.data(), &columns, &rw));
+    if (level) {
+      level->assign(ss.size(), 0xFF);
+      check_text(dafs_host_seed_clean_structure_levels(n, c_strs(names).data(), c_strs(rows).data(), structure.c_str(), ss.data(), level->data(),
+                                                       &columns, &rw));
+      level->resize(columns);
+    } else {
+      check_text(dafs_host_seed_clean_structure(n, c_strs(names).data(), c_strs(rows).data(), structure.c_str(), ss.data(), &columns, &rw));
+    }
     rows = lines_of(take(rw), n);
     ss.resize(columns);
   } else {
@@ -1159,7 +1181,8 @@ const Reference& reference_of(const Options& o) {
   static Reference ref;
   static bool loaded = false;
   if (!loaded) {
-    read_alignment(o.compare_ref, "--compare-ref", ref.names, ref.rows, ref.ss, ref.has_ss);
+    VL level;  // --knots: the comparison reads the merged pairs
+    read_alignment(o.compare_ref, "--compare-ref", ref.names, ref.rows, ref.ss, ref.has_ss, nullptr, o.knots ? &level : nullptr);
     loaded = true;
   }
   return ref;
@@ -1285,7 +1308,9 @@ void write_outputs(const Options& o, unsigned wanted, const std::vector<FamilyOu
 // ss (--seed-structure): also the seed's consensus structure over the cleaned columns; a seed without
 // one is refused
 // describe (--describe): the structure is optional -- without one ss comes back with every column unpaired
-void read_seed(const std::string& file, std::vector<std::string>& names, std::vector<std::string>& rows, VU* ss = nullptr, bool describe = false) {
+// level (--knots, with ss): the structure may cross, and *level receives its pairs' levels (empty when the file has no structure)
+void read_seed(const std::string& file, std::vector<std::string>& names, std::vector<std::string>& rows, VU* ss = nullptr, bool describe = false,
+               VL* level = nullptr) {
   std::ifstream is(file.c_str(), std::ios::binary);
   if (!is.is_open()) throw (describe ? "--describe: cannot open " : "--seed: cannot open ") + file;
   const std::string text((std::istreambuf_iterator<char>(is)), std::istreambuf_iterator<char>());
@@ -1313,7 +1338,14 @@ void read_seed(const std::string& file, std::vector<std::string>& names, std::ve
   if (!has) throw "--seed-structure: " + file + " holds no SS_cons";
   ss->assign(rows.empty() ? 1 : rows[0].size() + 1, DAFS_HIP_NONE);
   uint32_t columns = 0;
-  check_text(dafs_host_seed_clean_structure(n, c_strs(names).data(), c_strs(rows).data(), structure.c_str(), ss->data(), &columns, &rw));
+  if (level) {
+    level->assign(ss->size(), 0xFF);
+    check_text(dafs_host_seed_clean_structure_levels(n, c_strs(names).data(), c_strs(rows).data(), structure.c_str(), ss->data(), level->data(),
+                                                     &columns, &rw));
+    level->resize(columns);
+  } else {
+    check_text(dafs_host_seed_clean_structure(n, c_strs(names).data(), c_strs(rows).data(), structure.c_str(), ss->data(), &columns, &rw));
+  }
   rows = lines_of(take(rw), n);
   ss->resize(columns);
 }
@@ -1323,6 +1355,8 @@ void read_seed(const std::string& file, std::vector<std::string>& names, std::ve
 struct Seed {
   std::vector<std::string> names, rows;
   VU ss;
+  VL level;            // --knots: the levels of ss's pairs, else empty
+  uint32_t nlevels = 1;  // the levels in use
   std::vector<Fasta> fa;
   std::vector<uint8_t> mask;
   std::vector<uint32_t> lens;
@@ -1331,7 +1365,9 @@ struct Seed {
 
 Seed load_seed(const Options& o) {
   Seed sd;
-  read_seed(o.seed, sd.names, sd.rows, o.seed_structure ? &sd.ss : nullptr);
+  read_seed(o.seed, sd.names, sd.rows, o.seed_structure ? &sd.ss : nullptr, false, o.seed_structure && o.knots ? &sd.level : nullptr);
+  for (uint8_t lv : sd.level)
+    if (lv != 0xFF) sd.nlevels = std::max(sd.nlevels, (uint32_t)lv + 1);
   sd.m = (uint32_t)sd.rows.size();
   sd.C = (uint32_t)sd.rows[0].size();
   sd.mask.assign((size_t)sd.m * sd.C, 0);
@@ -1347,9 +1383,11 @@ Seed load_seed(const Options& o) {
 
 // --seed-structure: the folding constraints of a context that holds the seed's sequences and then k new ones -- every seed row
 // under the seed's structure (dafs_host_row_constraint), nullptr (a free fold) for the new ones.  Without --seed-structure, empty.
+// --knots: nlevels entries per sequence (dafs_host_row_constraint_levels), for dafs_hip_fold_posteriors_levels_begin.
 struct Constraints {
   std::vector<std::string> text;
   std::vector<const char*> ptr;  // into text
+  uint32_t nlevels = 0;          // --knots: the entries per sequence; 0: one, the plain call
   Constraints() {}
   Constraints(const Constraints&) = delete;
   Constraints(Constraints&&) = default;  // a moved vector keeps its strings where they are
@@ -1358,6 +1396,19 @@ struct Constraints {
 Constraints seed_constraints(const Options& o, const Seed& sd, uint32_t k) {
   Constraints out;
   if (!o.seed_structure) return out;
+  if (o.knots) {
+    out.nlevels = sd.nlevels;
+    for (uint32_t r = 0; r < sd.m; ++r) {
+      const size_t stride = (size_t)sd.lens[r] + 1;
+      std::vector<char> buf(stride * sd.nlevels);
+      check(dafs_host_row_constraint_levels(sd.C, sd.mask.data() + (size_t)r * sd.C, sd.ss.data(), sd.level.data(), sd.nlevels,
+                                            sd.fa[r].seq().c_str(), buf.data()));
+      for (uint32_t lv = 0; lv < sd.nlevels; ++lv) out.text.push_back(buf.data() + lv * stride);
+    }
+    for (const std::string& s : out.text) out.ptr.push_back(s.c_str());
+    out.ptr.resize((size_t)(sd.m + k) * sd.nlevels, nullptr);
+    return out;
+  }
   for (uint32_t r = 0; r < sd.m; ++r) {
     std::vector<char> buf(sd.lens[r] + 1);
     check(dafs_host_row_constraint(sd.C, sd.mask.data() + (size_t)r * sd.C, sd.ss.data(), sd.fa[r].seq().c_str(), buf.data()));
@@ -1373,6 +1424,14 @@ VU carry_structure(const VU& ss, const std::vector<uint32_t>& seed_col, uint32_t
   VU out(width, DAFS_HIP_NONE);
   for (size_t c = 0; c < ss.size(); ++c)
     if (ss[c] != DAFS_HIP_NONE) out[seed_col[c]] = seed_col[ss[c]];
+  return out;
+}
+
+// the levels of the seed's pairs in the merged columns (--knots; empty without): 0xFF at insert columns
+VL carry_levels(const VL& level, const std::vector<uint32_t>& seed_col, uint32_t width) {
+  if (level.empty()) return VL();
+  VL out(width, 0xFF);
+  for (size_t c = 0; c < level.size(); ++c) out[seed_col[c]] = level[c];
   return out;
 }
 
@@ -1595,7 +1654,8 @@ void set_sequences(dafs_hip_ctx* ctx, const std::vector<Fasta>& fa) {
 // another) and both consistency transforms.  The device folding is only started at the beginning: it keeps one workgroup
 // per sequence busy, and the alignment posteriors and the matching-probability transform run beside it.
 void phase1_local(dafs_hip_ctx* ctx, const Options& o, int align_model, const std::vector<Fasta>& fa, const std::vector<uint32_t>& first,
-                  std::vector<float>& sim, const PairChunk* pc = nullptr, const std::vector<const char*>* constraints = nullptr) {
+                  std::vector<float>& sim, const PairChunk* pc = nullptr, const std::vector<const char*>* constraints = nullptr,
+                  uint32_t cons_levels = 0) {
   const uint N = (uint)fa.size(), F = (uint)first.size() - 1;
   bool folding = false;
   if (pc) {  // --pairwise: both raw stores and the similarity blocks gathered from the N-sequence source
@@ -1604,6 +1664,9 @@ void phase1_local(dafs_hip_ctx* ctx, const Options& o, int align_model, const st
     std::vector<BP> bp;
     load_fold_aux(o.fold_aux, fa, bp);
     upload_bp(ctx, bp);
+  } else if (constraints && cons_levels) {  // --knots: cons_levels constraints per sequence, the folds merged by _end
+    check(dafs_hip_fold_posteriors_levels_begin(ctx, DAFS_FOLD_CONTRAFOLD, kCutoff, cons_levels, constraints->data()));
+    folding = true;
   } else {  // constraints: per sequence its folding constraint, nullptr for a free fold (--seed-structure)
     check(dafs_hip_fold_posteriors_constrained_begin(ctx, DAFS_FOLD_CONTRAFOLD, kCutoff, constraints ? constraints->data() : nullptr));
     folding = true;
@@ -1681,7 +1744,6 @@ VU concat(const std::vector<VU>& parts) {
 // Every decode of the command line goes through here: many alignments, laid out as the library takes them, at the decoder
 // of --fold-decoder.  Nussinov: dafs_hip_consensus_structures at the first entry of -T / -G; level stays empty.  Levels:
 // dafs_hip_consensus_structures_levels with one level per entry; level gets a byte per column.
-typedef std::vector<uint8_t> VL;
 void decode_alignments(dafs_hip_ctx* ctx, const Options& o, const std::vector<uint32_t>& n_rows, const std::vector<uint32_t>& len,
                        const std::vector<uint32_t>& seq, const std::vector<uint8_t>& mask, VU& ss, VL& level) {
   level.clear();
@@ -2093,7 +2155,7 @@ int run_add(const Options& o, int align_model) {
   set_sequences(ctx, fa);
   std::vector<float> sim;
   const Constraints cons = seed_constraints(o, sd, k);
-  phase1_local(ctx, o, align_model, fa, {0, m + k}, sim, nullptr, o.seed_structure ? &cons.ptr : nullptr);
+  phase1_local(ctx, o, align_model, fa, {0, m + k}, sim, nullptr, o.seed_structure ? &cons.ptr : nullptr, cons.nlevels);
 
   dafs_dd_params prm = dd_params_of(o);
   prm.skip_uncoupled_folds = o.verbose == 0 ? 1 : 0;  // as the progressive loop of a run without -r
@@ -2120,6 +2182,7 @@ int run_add(const Options& o, int align_model) {
   if (o.seed_structure) carried = carry_structure(sd.ss, pl.seed_col, pl.width);
   VL level;
   const VU ss = final_structure(ctx, o, root, o.seed_structure ? &carried : nullptr, &level);
+  if (o.seed_structure) level = carry_levels(sd.level, pl.seed_col, pl.width);
   std::vector<Reliability> rl(1);
   if (recs[0].wanted & kSto) reliabilities(ctx, fa, {&root}, {ss}, false, rl);
   finish_alignment(ctx, o, fa, root, 0, recs[0], nullptr, &pl.rf, ss, rl[0], o.row_structures ? &row_ss : nullptr, &level, &row_level);
@@ -2156,7 +2219,8 @@ int run_add_each(const Options& o, int align_model) {
   }
   {  // --seed-structure: the seed rows under their constraints, the new sequences free, once for every chunk
     const Constraints cons = seed_constraints(o, sd, k);
-    check(dafs_hip_fold_posteriors_constrained_begin(src, DAFS_FOLD_CONTRAFOLD, kCutoff, o.seed_structure ? cons.ptr.data() : nullptr));
+    if (cons.nlevels) check(dafs_hip_fold_posteriors_levels_begin(src, DAFS_FOLD_CONTRAFOLD, kCutoff, cons.nlevels, cons.ptr.data()));
+    else check(dafs_hip_fold_posteriors_constrained_begin(src, DAFS_FOLD_CONTRAFOLD, kCutoff, o.seed_structure ? cons.ptr.data() : nullptr));
   }
   // the pairs (x, y) with x < m are the first m (m + k) - m (m + 1) / 2 pair ids
   const int rc_align = dafs_hip_align_posteriors(src, align_model, o.align_th, 0, (uint64_t)m * (m + k) - (uint64_t)m * (m + 1) / 2);
@@ -2239,6 +2303,7 @@ int run_add_each(const Options& o, int align_model) {
       consensus_structures(ctx, o, ptrs, ss, level);
     } else {  // nothing is decoded: the seed's structure in every family's merged columns, and each row's support of it
       for (uint32_t f = 0; f < nf; ++f) ss.push_back(carry_structure(sd.ss, pl[f].seed_col, pl[f].width));
+      for (uint32_t f = 0; f < nf; ++f) level[f] = carry_levels(sd.level, pl[f].seed_col, pl[f].width);
       std::vector<uint32_t> both, can, half;
       std::vector<double> expd;
       structure_support(ctx, ptrs, ss, both, can, half, expd);
@@ -2295,7 +2360,8 @@ int run_add_each(const Options& o, int align_model) {
     }
     const VU carried = carry_structure(sd.ss, pl.seed_col, pl.width);
     std::vector<char> brackets(pl.width + 1);
-    dafs_hip_make_brackets(pl.width, carried.data(), brackets.data());
+    const VL carried_level = carry_levels(sd.level, pl.seed_col, pl.width);
+    dafs_hip_make_brackets_levels(pl.width, carried.data(), carried_level.empty() ? nullptr : carried_level.data(), brackets.data());
     const std::vector<std::string> names = stockholm_names(row_headers);
     char* text = nullptr;
     check_text(dafs_host_stockholm_block_merged(m + k, pl.width, c_strs(names).data(), c_strs(rows).data(), rr.data(), brackets.data(),
@@ -2536,7 +2602,13 @@ int run_cluster(const Options& o, int align_model) {
 int run_describe(const Options& o) {
   std::vector<std::string> headers, rows;
   VU ss;
-  read_seed(o.describe, headers, rows, &ss, true);
+  VL level;
+  read_seed(o.describe, headers, rows, &ss, true, o.knots ? &level : nullptr);
+  if (o.knots && !level.empty()) {  // the structure as it was read, each level with its own bracket kind
+    std::vector<char> str(ss.size() + 1);
+    dafs_hip_make_brackets_levels((uint32_t)ss.size(), ss.data(), level.data(), str.data());
+    std::cout << ">SS_cons" << std::endl << str.data() << std::endl;
+  }
   const std::vector<std::string> names = stockholm_names(headers);
   dafs_hip_ctx* ctx = nullptr;
   check(dafs_hip_create(o.device, &ctx));
@@ -2561,7 +2633,8 @@ int run_describe(const Options& o) {
     std::vector<std::string> h2, r2, pp;
     VU ss2;
     bool has_ss = false;
-    read_alignment(o.describe, "--describe", h2, r2, ss2, has_ss, &pp);
+    VL level2;
+    read_alignment(o.describe, "--describe", h2, r2, ss2, has_ss, &pp, o.knots ? &level2 : nullptr);
     CompareText cmp;
     compare_of(ctx, o, names, rows, has_ss ? &ss2 : nullptr, nullptr, pp.empty() ? nullptr : &pp, cmp);
     write_compare(o, {cmp}, nullptr);

@@ -268,6 +268,73 @@ std::vector<uint32_t> structure_pairs(const std::string& st) {
   return partner;
 }
 
+// The pairs of a structure line that may cross: the groups "()", "[]", "{}", "<>" and then the letters
+// 'A'..'Z' (upper case opens, the same letter in lower case closes), each matched last-in-first-out with itself; ". , : _ - ~"
+// unpaired.  partner as structure_pairs gives it, group[c] the group of c's pair (0..29).  Nothing is said about crossing here.
+const char kKnotOpen[] = "([{<", kKnotClose[] = ")]}>";
+const uint32_t kKnotGroups = 30;
+
+char knot_open_char(uint32_t g) { return g < 4 ? kKnotOpen[g] : (char)('A' + (g - 4)); }
+char knot_close_char(uint32_t g) { return g < 4 ? kKnotClose[g] : (char)('a' + (g - 4)); }
+
+std::vector<uint32_t> structure_pairs_groups(const std::string& st, std::vector<uint8_t>& group) {
+  const std::string open = kKnotOpen, close = kKnotClose, unpaired = ".,:_-~";
+  std::vector<uint32_t> partner(st.size(), DAFS_HIP_NONE);
+  group.assign(st.size(), 0xFF);
+  std::vector<size_t> stack[kKnotGroups];
+  for (size_t c = 0; c < st.size(); ++c) {
+    const char ch = st[c];
+    size_t k;
+    if ((k = open.find(ch)) != std::string::npos) stack[k].push_back(c);
+    else if (ch >= 'A' && ch <= 'Z') stack[4 + (ch - 'A')].push_back(c);
+    else if ((k = close.find(ch)) != std::string::npos || (ch >= 'a' && ch <= 'z')) {
+      if (k == std::string::npos) k = 4 + (size_t)(ch - 'a');
+      if (stack[k].empty()) throw "seed: SS_cons has a '" + std::string(1, ch) + "' at column " + std::to_string(c + 1) + " that closes nothing";
+      partner[c] = (uint32_t)stack[k].back();
+      partner[stack[k].back()] = (uint32_t)c;
+      group[c] = group[stack[k].back()] = (uint8_t)k;
+      stack[k].pop_back();
+    } else if (unpaired.find(ch) == std::string::npos)
+      throw "seed: SS_cons holds '" + std::string(1, ch) + "', which is neither a bracket, a letter nor one of \".,:_-~\"";
+  }
+  for (uint32_t k = 0; k < kKnotGroups; ++k)
+    if (!stack[k].empty())
+      throw "seed: SS_cons has a '" + std::string(1, knot_open_char(k)) + "' at column " + std::to_string(stack[k].back() + 1) + " that is never closed";
+  return partner;
+}
+
+// The level of every group of a cleaned structure (ss: the partner at the left column of a pair; group: per column): group
+// after group, a non-empty one goes to the lowest level at which none of its pairs crosses a pair already placed there.
+// level[c]: the pair's level at both of its columns, 0xFF at unpaired ones.
+void assign_levels(const std::vector<uint32_t>& ss, const std::vector<uint8_t>& group, uint8_t* level) {
+  typedef std::pair<uint32_t, uint32_t> pr;
+  std::vector<pr> placed[DAFS_HIP_MAX_LEVELS];
+  for (size_t c = 0; c < ss.size(); ++c) level[c] = 0xFF;
+  for (uint32_t g = 0; g < kKnotGroups; ++g) {
+    std::vector<pr> mine;
+    for (uint32_t c = 0; c < ss.size(); ++c)
+      if (ss[c] != DAFS_HIP_NONE && group[c] == g) mine.push_back(pr(c, ss[c]));
+    if (mine.empty()) continue;
+    uint32_t lv = 0;
+    for (; lv < DAFS_HIP_MAX_LEVELS; ++lv) {
+      bool crosses = false;
+      for (size_t a = 0; a < mine.size() && !crosses; ++a)
+        for (size_t b = 0; b < placed[lv].size() && !crosses; ++b) {
+          const uint32_t i = mine[a].first, j = mine[a].second, p = placed[lv][b].first, q = placed[lv][b].second;
+          crosses = (p < i && i < q && q < j) || (i < p && p < j && j < q);
+        }
+      if (!crosses) break;
+    }
+    if (lv == DAFS_HIP_MAX_LEVELS)
+      throw "seed: the '" + std::string(1, knot_open_char(g)) + "' '" + std::string(1, knot_close_char(g)) + "' pairs of SS_cons cross a pair of each of the " +
+          std::to_string(DAFS_HIP_MAX_LEVELS) + " levels a structure may have";
+    for (const pr& x : mine) {
+      placed[lv].push_back(x);
+      level[x.first] = level[x.second] = (uint8_t)lv;
+    }
+  }
+}
+
 // refuses an empty seed, rows of unequal length, a character that is neither a letter nor a gap ('.', '-') and a row without
 // residues; drops the all-gap columns and writes every gap as '-'
 // kept (optional): the columns that stay.
@@ -967,6 +1034,39 @@ extern "C" int dafs_host_seed_clean_structure(uint32_t n, const char* const* nam
   });
 }
 
+// the seed with a consensus structure whose pairs may cross
+extern "C" int dafs_host_seed_clean_structure_levels(uint32_t n, const char* const* names, const char* const* rows, const char* structure,
+                                                     uint32_t* ss, uint8_t* level, uint32_t* columns, char** cleaned) {
+  return text_out(cleaned, [&]() {
+    if (!structure || !ss || !level || !columns) throw kBadArgument;
+    const std::vector<std::string> nm = strings(n, names);
+    std::vector<std::string> rw = strings(n, rows);
+    const size_t raw = rw.empty() ? 0 : rw[0].size();
+    std::vector<size_t> kept;
+    clean_seed(nm, rw, &kept);
+    const std::string st = structure;
+    if (st.size() != raw)
+      throw "seed: SS_cons has " + std::to_string(st.size()) + " columns, the rows have " + std::to_string(raw);
+    std::vector<uint8_t> group_raw;
+    const std::vector<uint32_t> partner = structure_pairs_groups(st, group_raw);
+    std::vector<uint32_t> now(raw, DAFS_HIP_NONE);  // raw column -> cleaned column
+    for (size_t k = 0; k < kept.size(); ++k) now[kept[k]] = (uint32_t)k;
+    std::vector<uint32_t> out(kept.size(), DAFS_HIP_NONE);
+    std::vector<uint8_t> group(kept.size(), 0xFF);
+    for (size_t k = 0; k < kept.size(); ++k) {  // a pair that lost a column is dropped before the levels are assigned
+      const uint32_t p = partner[kept[k]];
+      if (p == DAFS_HIP_NONE || p < kept[k] || now[p] == DAFS_HIP_NONE) continue;
+      out[k] = now[p];
+      group[k] = group[now[p]] = group_raw[kept[k]];
+    }
+    std::vector<uint8_t> lv(kept.size() + 1);
+    assign_levels(out, group, lv.data());
+    for (size_t k = 0; k < kept.size(); ++k) { ss[k] = out[k]; level[k] = lv[k]; }
+    *columns = (uint32_t)kept.size();
+    return joined(rw);
+  });
+}
+
 // The "#=GR <name> PP" lines of a Stockholm file's first alignment, over the columns the seed reader keeps
 extern "C" int dafs_host_seed_pp(const char* text, size_t bytes, uint32_t* n, int* has_pp, char** pp) {
   return text_out(pp, [&]() {
@@ -1159,6 +1259,44 @@ extern "C" int dafs_host_row_constraint(uint32_t len, const uint8_t* mask_row, c
     if (j - i < 4 || !dafs_host_fold_complementary(residues[i], residues[j])) continue;
     out[i] = '(';
     out[j] = ')';
+  }
+  return DAFS_HIP_OK;
+}
+
+// One constraint per level (DAFS::update_basepairing_probability, dafs.cpp:635-653): string k at
+// out + k * (residues + 1).
+extern "C" int dafs_host_row_constraint_levels(uint32_t len, const uint8_t* mask_row, const uint32_t* ss, const uint8_t* level, uint32_t nlevels,
+                                               const char* residues, char* out) {
+  if ((len && (!mask_row || !ss)) || !residues || !out || nlevels < 1 || nlevels > DAFS_HIP_MAX_LEVELS) return DAFS_HIP_EINVAL;
+  std::vector<uint32_t> rev(len);
+  uint32_t k = 0;
+  for (uint32_t c = 0; c < len; ++c) rev[c] = mask_row[c] ? k++ : DAFS_HIP_NONE;
+  if (strnlen(residues, (size_t)k + 1) != k) return DAFS_HIP_EINVAL;
+  for (uint32_t c = 0; c < len; ++c) {
+    if (ss[c] == DAFS_HIP_NONE) continue;
+    if (ss[c] <= c || ss[c] >= len) return DAFS_HIP_EINVAL;
+    if (level && (level[c] >= nlevels || level[ss[c]] != level[c])) return DAFS_HIP_EINVAL;
+  }
+  const size_t stride = (size_t)k + 1;
+  for (uint32_t lv = 0; lv < nlevels; ++lv) {
+    char* o = out + lv * stride;
+    memset(o, '?', k);
+    o[k] = 0;
+    bool forced = false;
+    for (uint32_t c = 0; c < len; ++c) {
+      if (ss[c] == DAFS_HIP_NONE) continue;
+      const uint32_t i = rev[c], j = rev[ss[c]];
+      if (i == DAFS_HIP_NONE || j == DAFS_HIP_NONE) continue;
+      if ((level ? level[c] : 0) != lv) {  // a pair of another level: both residues unpaired in this fold (dafs.cpp:650)
+        o[i] = o[j] = '.';
+        continue;
+      }
+      if (j - i < 4 || !dafs_host_fold_complementary(residues[i], residues[j])) continue;
+      o[i] = '(';
+      o[j] = ')';
+      forced = true;
+    }
+    if (lv >= 1 && !forced) o[0] = 0;  // nothing to force at this level: the row is not folded for it
   }
   return DAFS_HIP_OK;
 }

@@ -521,12 +521,15 @@ def identity_matrix_tsv(row_names, identity):
 
 
 def describe(names, rows, ss=None, ctx=None, identity=True, covariation=False, compare=None, pp=None, phylogeny=False,
-             phylogeny_bootstrap=0, phylogeny_seed=12345):
+             phylogeny_bootstrap=0, phylogeny_seed=12345, level=None):
     """The alignment-only statistics of a finished alignment (`dafs --describe ALIGNMENT`): nothing is
     aligned.  names / rows / ss: as stockholm.read_seed_structure returns them (ss None: no structure).  Returns a Result with
     .rows, .row_names (stockholm.names), .ss and, as asked, .identity (alignment_identity over all columns) and .covariation
     (as run's).  compare (as run's): .compare, this alignment against the reference; pp: its PP rows (stockholm.read_seed_pp)
-    for the comparison's PP part.  phylogeny, phylogeny_bootstrap, phylogeny_seed (as run's): .phylogeny."""
+    for the comparison's PP part.  phylogeny, phylogeny_bootstrap, phylogeny_seed (as run's): .phylogeny.  level (with ss, both
+    as stockholm.read_seed_knots returns them; `dafs --describe --knots`): the levels of a structure whose
+    pairs may cross -> .ss_level and .ss_str, the brackets of capi.make_brackets_levels, which `dafs` prints after a
+    ">SS_cons" line; the statistics read the merged ss."""
     covariation = cov_options(covariation)
     phylogeny = phylogeny_option(phylogeny, phylogeny_bootstrap, phylogeny_seed)
     names, rows = stockholm.clean_seed(names, rows)
@@ -535,6 +538,11 @@ def describe(names, rows, ss=None, ctx=None, identity=True, covariation=False, c
     res.ss = np.full(len(rows[0]), NONE, np.uint32) if ss is None else np.ascontiguousarray(ss, np.uint32)
     if len(res.ss) != len(rows[0]):
         raise ValueError("pipeline.describe: the structure needs one entry per column")
+    if level is not None:
+        res.ss_level = np.ascontiguousarray(level, np.uint8)
+        if ss is None or len(res.ss_level) != len(res.ss):
+            raise ValueError("pipeline.describe: level needs ss and one entry per column")
+        res.ss_str = capi.make_brackets_levels(res.ss, res.ss_level)
     own = ctx is None
     if own:
         ctx = capi.Context(0)
@@ -678,9 +686,12 @@ def _final(ctx, res, names, seqs, first, sidx, mask, ss, rl, tree_line, rf=None,
                                         res.identity.weights if identity else None)
 
 
-def _seed_structure(seed_ss, seed_mask, seed_seqs, th_s1, bp_update1, who):
+def _seed_structure(seed_ss, seed_mask, seed_seqs, th_s1, bp_update1, who, seed_level=None):
     """The checks of a seed structure (seed_ss over the seed's cleaned columns) and the folding constraint it puts on every
-    seed row (capi.row_constraint).  Returns (seed_ss as uint32, constraints)."""
+    seed row (capi.row_constraint).  Returns (seed_ss as uint32, None, constraints).  seed_level: the
+    pairs' levels, checked too (0xFF exactly at the unpaired columns, equal at both columns of a pair, below capi.MAX_LEVELS,
+    every level nested in itself); returns (seed_ss, seed_level as uint8, constraints), every row's entry then the list of its
+    per-level constraints (capi.row_constraint_levels)."""
     ss = np.ascontiguousarray(seed_ss, np.uint32).reshape(-1)
     C = seed_mask.shape[1]
     if len(ss) != C:
@@ -695,15 +706,41 @@ def _seed_structure(seed_ss, seed_mask, seed_seqs, th_s1, bp_update1, who):
         if p <= c or p >= C or used[c] or used[p]:
             raise ValueError("%s: seed_ss is no structure over the seed's columns (column %d)" % (who, c))
         used[c] = used[p] = True
-    return ss, [capi.row_constraint(seed_mask[r], ss, seed_seqs[r]) for r in range(len(seed_seqs))]
+    if seed_level is None:
+        return ss, None, [capi.row_constraint(seed_mask[r], ss, seed_seqs[r]) for r in range(len(seed_seqs))]
+    level = np.ascontiguousarray(seed_level, np.uint8).reshape(-1)
+    if len(level) != C:
+        raise ValueError("%s: seed_level has %d entries, the seed has %d columns" % (who, len(level), C))
+    open_at = [[] for _ in range(capi.MAX_LEVELS)]  # per level the right columns of its open pairs
+    for c in range(C):
+        lv = int(level[c])
+        if not used[c]:
+            if lv != 0xFF:
+                raise ValueError("%s: seed_level gives the unpaired column %d a level" % (who, c))
+            continue
+        if lv >= capi.MAX_LEVELS:
+            raise ValueError("%s: seed_level holds %d at the paired column %d; the levels are 0..%d" % (who, lv, c, capi.MAX_LEVELS - 1))
+        if ss[c] != NONE:
+            if int(level[ss[c]]) != lv:
+                raise ValueError("%s: seed_level differs at the two columns of the pair at column %d" % (who, c))
+            open_at[lv].append(int(ss[c]))
+        elif not open_at[lv] or open_at[lv].pop() != c:
+            raise ValueError("%s: the pairs of level %d of seed_level cross (column %d)" % (who, lv, c))
+    K = int(level[used].max()) + 1 if used.any() else 1
+    return ss, level, [capi.row_constraint_levels(seed_mask[r], ss, level, K, seed_seqs[r]) for r in range(len(seed_seqs))]
 
 
-def carry_structure(seed_ss, seed_col, width):
-    """The seed's structure in the merged columns: ss_m[seed_col[c]] = seed_col[seed_ss[c]], insert columns unpaired"""
+def carry_structure(seed_ss, seed_col, width, seed_level=None):
+    """The seed's structure in the merged columns: ss_m[seed_col[c]] = seed_col[seed_ss[c]], insert columns unpaired.  seed_level:
+    the pairs' levels travel with their columns (0xFF at insert columns); returns (ss_m, level_m)."""
     ss_m = np.full(width, NONE, np.uint32)
     paired = np.flatnonzero(seed_ss != NONE)
     ss_m[seed_col[paired]] = seed_col[seed_ss[paired]]
-    return ss_m
+    if seed_level is None:
+        return ss_m
+    level_m = np.full(width, 0xFF, np.uint8)
+    level_m[seed_col] = seed_level
+    return ss_m, level_m
 
 
 def _printed_support(sup, sidx):
@@ -715,7 +752,7 @@ def _printed_support(sup, sidx):
 def add(seed_names, seed_rows, names, seqs, ctx=None, w=4.0, eta0=0.5, t_max=600, w_pct_a=0.25, w_pct_s=0.25, th_a=0.01,
         th_s=0.2, th_s1=None, align_model=capi.ALIGN_PROBCONS, force_iters=0, slice_iters=None, skip_uncoupled_folds=True,
         round_us=None, w_pct_f=0.0, bp_update1=False, reliability=False, covariation=False, row_structures=False, seed_ss=None,
-        decoder="Nussinov",
+        decoder="Nussinov", seed_level=None,
         identity=False, compare=None, phylogeny=False, phylogeny_bootstrap=0, phylogeny_seed=12345):
     """Add new sequences to a fixed seed alignment without changing its columns (`dafs --seed`).
     seed_names / seed_rows: the seed's rows (letters and '.' / '-' gaps; stockholm.read_seed reads a file), checked and
@@ -735,9 +772,16 @@ def add(seed_names, seed_rows, names, seqs, ctx=None, w=4.0, eta0=0.5, t_max=600
     (stockholm.read_seed_structure), fixed like the columns.  The seed rows are folded under the constraints it puts on them
     (capi.row_constraint), the new sequences free; nothing is decoded: the output's structure is the seed's carried into the
     merged columns, insert columns unpaired, and the annotations see it.  The Result gains .support: per printed row, both,
-    canonical, half and expected of Context.structure_support."""
+    canonical, half and expected of Context.structure_support.
+
+    seed_level (`dafs --seed-structure --knots`; only with seed_ss): the levels of seed_ss's pairs
+    (stockholm.read_seed_knots), whose pairs may then cross between levels.  Every seed row is folded once per level that
+    forces a pair in it (capi.row_constraint_levels; Context.fold_begin merges the folds); the Result gains .ss_level, and
+    .ss_str and the Stockholm SS_cons print "()", "[]", "{}", "<>" for levels 0..3.  .support reads the merged structure."""
     import time
     th_s1 = decoder_option(decoder, th_s, th_s1, bp_update1, seed_ss, "pipeline.add")  # decoder: as in run()
+    if seed_level is not None and seed_ss is None:
+        raise ValueError("pipeline.add: seed_level gives the levels of seed_ss and needs it")
     covariation = cov_options(covariation)
     phylogeny = phylogeny_option(phylogeny, phylogeny_bootstrap, phylogeny_seed)
     seed_names, seed_rows = stockholm.clean_seed(seed_names, seed_rows)
@@ -750,7 +794,7 @@ def add(seed_names, seed_rows, names, seqs, ctx=None, w=4.0, eta0=0.5, t_max=600
     all_names, all_seqs = seed_names + names, seed_seqs + seqs
     constraints = None
     if seed_ss is not None:
-        seed_ss, constraints = _seed_structure(seed_ss, seed_mask, seed_seqs, th_s1, bp_update1, "pipeline.add")
+        seed_ss, seed_level, constraints = _seed_structure(seed_ss, seed_mask, seed_seqs, th_s1, bp_update1, "pipeline.add", seed_level)
         constraints += [None] * k
     own = ctx is None
     if own:
@@ -788,6 +832,8 @@ def add(seed_names, seed_rows, names, seqs, ctx=None, w=4.0, eta0=0.5, t_max=600
         rows_mask = np.concatenate([mask[m:], mask[:m]])
         ss_m = None if seed_ss is None else carry_structure(seed_ss, seed_col, width)
         levels = None
+        if seed_level is not None:
+            levels = (carry_structure(seed_ss, seed_col, width, seed_level)[1], None)
         if ss_m is not None:
             res.support = _printed_support(ctx.structure_support([(sidx, rows_mask)], [ss_m])[0], sidx)
         elif isinstance(th1, LevelThresholds):  # the batched call with one alignment
@@ -1109,8 +1155,9 @@ class Nearest:
     pass
 
 
-def _merge_each(seed_names, seed_rows, seed_ss, names, seqs, zs, pps):
-    """The merged alignment of add_each from the k column maps zs and the k rows' residue values pps"""
+def _merge_each(seed_names, seed_rows, seed_ss, names, seqs, zs, pps, seed_level=None):
+    """The merged alignment of add_each from the k column maps zs and the k rows' residue values pps.
+    seed_level: the levels of seed_ss -> .ss_level, and .ss_str with each level's bracket kind"""
     m, k, columns = len(seed_rows), len(seqs), len(seed_rows[0])
     seed_col, res_col, width = capi.merge_added(columns, zs)
     mg = Merged()
@@ -1123,8 +1170,12 @@ def _merge_each(seed_names, seed_rows, seed_ss, names, seqs, zs, pps):
     mg.rows = [row.tobytes().decode("latin-1") for row in cells]
     mg.rf = np.zeros(width, bool)
     mg.rf[seed_col] = True
-    mg.ss = carry_structure(seed_ss, seed_col, width)
-    mg.ss_str = capi.make_brackets(mg.ss)
+    if seed_level is None:
+        mg.ss = carry_structure(seed_ss, seed_col, width)
+        mg.ss_str = capi.make_brackets(mg.ss)
+    else:
+        mg.ss, mg.ss_level = carry_structure(seed_ss, seed_col, width, seed_level)
+        mg.ss_str = capi.make_brackets_levels(mg.ss, mg.ss_level)
     mg.stockholm, mg.col = stockholm.block_merged(mg.names, mg.rows, [None] * m + pps, mg.ss_str, mg.rf)
     lines = [">SS_cons", mg.ss_str]
     for nm, row in zip(seed_names + names, mg.rows):
@@ -1170,7 +1221,7 @@ def add_each(seed_names, seed_rows, names, seqs, ctx=None, max_bytes=None, merge
     (indices per chunk), .dd_memory (per chunk the nodes' (reserved, in use, peak) bytes) and .seconds (phase1, gather,
     transforms, nodes, final, total; with merged, merge).
 
-    seed_ss: as in add().  The seed rows are folded under their constraints once, in the source context; every result's
+    seed_ss, seed_level: as in add().  The seed rows are folded under their constraints once, in the source context; every result's
     structure is the seed's carried into its merged columns, and its .support comes from one Context.structure_support call
     per chunk.  The object gains .support: per new sequence both, canonical, half and expected of its own row.
 
@@ -1229,11 +1280,14 @@ def add_each(seed_names, seed_rows, names, seqs, ctx=None, max_bytes=None, merge
     seed_mask = np.array([[ch != "-" for ch in r] for r in seed_rows], np.uint8)
     columns = seed_mask.shape[1]
     seed_lens = [len(sq) for sq in seed_seqs]
-    seed_ss, constraints = None, None
+    seed_ss, seed_level, constraints = None, None, None
     if merged and o["seed_ss"] is None:
         raise ValueError(capi._merged_refusal().decode())
+    if o["seed_level"] is not None and o["seed_ss"] is None:
+        raise ValueError("pipeline.add_each: seed_level gives the levels of seed_ss and needs it")
     if o["seed_ss"] is not None:
-        seed_ss, constraints = _seed_structure(o["seed_ss"], seed_mask, seed_seqs, o["th_s1"], o["bp_update1"], "pipeline.add_each")
+        seed_ss, seed_level, constraints = _seed_structure(o["seed_ss"], seed_mask, seed_seqs, o["th_s1"], o["bp_update1"], "pipeline.add_each",
+                                                           o["seed_level"])
         constraints += [None] * k
     chunks = pack_families([seed_each_bytes(seed_lens, columns, len(sq)) for sq in seqs], budget)
     th1 = o["th_s"] if o["th_s1"] is None else o["th_s1"]
@@ -1310,6 +1364,9 @@ def add_each(seed_names, seed_rows, names, seqs, ctx=None, max_bytes=None, merge
                 decoded = _decode(ctx, alns, th1)
             else:  # nothing is decoded: the seed's structure in every family's merged columns (seed columns where rf is set)
                 decoded = [(carry_structure(seed_ss, np.flatnonzero(rf).astype(np.uint32), len(rf)), None, None) for rf in rfs]
+                if seed_level is not None:  # the levels travel with the seed's columns
+                    decoded = [(ss, carry_structure(seed_ss, np.flatnonzero(rf).astype(np.uint32), len(rf), seed_level)[1], None)
+                               for (ss, _, _), rf in zip(decoded, rfs)]
                 support = ctx.structure_support(alns, [ss for ss, _, _ in decoded])
             rows_ss = rows_level = [None] * len(chunk)
             if o["row_structures"]:
@@ -1354,7 +1411,7 @@ def add_each(seed_names, seed_rows, names, seqs, ctx=None, max_bytes=None, merge
                 secs[key] += t[b] - t[a]
         if merged:
             t_merge = time.perf_counter()
-            out.merged = _merge_each(seed_names, seed_rows, seed_ss, names, seqs, [r.z[0] for r in out.results], pps)
+            out.merged = _merge_each(seed_names, seed_rows, seed_ss, names, seqs, [r.z[0] for r in out.results], pps, seed_level)
             if nr is not None:
                 _select_nr(ctx, out.merged, m, out.score, out.matched, float(nr))
             if compare is not None:

@@ -20,7 +20,7 @@ PP_cons.
 
 read_seed reads a seed alignment for pipeline.add: Stockholm or aligned FASTA; a file the library
 refuses raises SeedError with the message `dafs --seed` prints.  read_seed_structure also returns the seed's consensus
-structure.
+structure; read_seed_knots reads one whose pairs may cross, with the pairs' levels.
 
 block_merged writes the merged alignment of all placements of pipeline.add_each: the rows, then PP
 lines for the placed rows only, SS_cons, PP_cons over the placed rows, RF."""
@@ -187,6 +187,38 @@ def read_seed_structure(path):
     if structure is None:
         return clean_seed(names, rows) + (None,)
     return clean_seed_structure(names, rows, structure)
+
+
+def clean_seed_knots(names, rows, structure):
+    """clean_seed_structure for a structure whose pairs may cross (dafs_host_seed_clean_structure_levels; DESIGN.md section 26;
+    `dafs --knots`): (names, rows, ss, level), level a uint8 array over the cleaned columns with the pair's level at both of its
+    columns and 0xFF at unpaired ones.  Groups, in this order: `()`, `[]`, `{}`, `<>`, then the letters A..Z, an upper-case
+    letter opening and the same letter in lower case closing; each group is matched with itself.  After the all-gap columns
+    have gone (a pair that loses a column is dropped), group after group goes to the lowest level at which none of its pairs
+    crosses a pair already there.  Refuses (SeedError) what clean_seed refuses, any other character, a length that is not the
+    rows', an unbalanced group and a group that would need a fifth level."""
+    names, rows = list(names), list(rows)
+    if len(names) != len(rows):
+        raise SeedError("seed: one name per row")
+    st = structure.encode("latin-1") if isinstance(structure, str) else bytes(structure)
+    if b"\0" in st:
+        raise SeedError("seed: SS_cons holds a NUL byte")
+    width = max(len(rows[0]) if rows else 0, 1)
+    ss, level = np.zeros(width, np.uint32), np.zeros(width, np.uint8)
+    cols = C.c_uint32()
+    cleaned = capi.host_text(capi._seed_clean_structure_levels, len(rows), capi.c_strings(names), capi.c_strings(rows), st, ss.ctypes.data,
+                             level.ctypes.data, C.byref(cols), refusal=SeedError)
+    return names, capi.split_lines(cleaned, len(rows)), ss[:cols.value].copy(), level[:cols.value].copy()
+
+
+def read_seed_knots(path):
+    """read_seed_structure with clean_seed_knots: (names, rows, ss, level), ss and level both None when the file has no
+    structure"""
+    with open(path, "rb") as fh:
+        names, rows, structure = parse_seed_structure(fh.read())
+    if structure is None:
+        return clean_seed(names, rows) + (None, None)
+    return clean_seed_knots(names, rows, structure)
 
 
 def read_seed_pp(path):

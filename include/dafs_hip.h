@@ -286,6 +286,17 @@ int dafs_hip_fold_posteriors_end(dafs_hip_ctx* ctx);
  * stays usable after a refusal. */
 int dafs_hip_fold_posteriors_constrained_begin(dafs_hip_ctx* ctx, int model, float th, const char* const* constraints);
 int dafs_hip_fold_posteriors_constrained(dafs_hip_ctx* ctx, int model, float th, const char* const* constraints);
+/* Several constraints per sequence: the per-level folds of DAFS::update_basepairing_probability
+ * (src/dafs.cpp:635-661, one s_model_->calculate(seq, con, bp) per level) for every sequence of the context, all in one batch
+ * of the folding kernels.  constraints[x * nlevels + k], 1 <= nlevels <= 4: NULL or empty for no fold of sequence x at level k,
+ * otherwise as in dafs_hip_fold_posteriors_constrained_begin; a sequence without any string is folded once, free.  Row x of the
+ * store holds, per cell, the maximum over x's folds of the posterior, kept where it exceeds th, in ascending column order (the
+ * reference sums the levels into a dense matrix instead; --bp-update keeps doing that).  _end is shared.  With nlevels = 1 the
+ * store is dafs_hip_fold_posteriors_constrained's bit for bit.  DAFS_HIP_EINVAL, with sequence and level in
+ * dafs_hip_last_error and the context still usable: nlevels outside 1..4 and what dafs_hip_fold_posteriors_constrained_begin
+ * refuses. */
+int dafs_hip_fold_posteriors_levels_begin(dafs_hip_ctx* ctx, int model, float th, uint32_t nlevels, const char* const* constraints);
+int dafs_hip_fold_posteriors_levels(dafs_hip_ctx* ctx, int model, float th, uint32_t nlevels, const char* const* constraints);
 /* Single-sequence call replacing CONTRAfold<float>::ComputePosterior (src/contrafold/wrapper.cpp:181-200)
  * and, with a constraint string of len chars from "?.()" ('?' free, '.' unpaired, brackets forced),
  * Fold::Model::calculate(seq, str, bp) (src/fold.cpp:191-207).  post: (len+1)(len+2)/2 floats,
@@ -553,6 +564,26 @@ int dafs_host_fold_complementary(char a, char b);
  * receives one character per residue and a NUL.  '?' everywhere; '(' and ')' at the two residues of a pair of ss when the row
  * holds both, they are complementary (dafs_host_fold_complementary) and at least 4 residues apart (j - i >= 4). */
 int dafs_host_row_constraint(uint32_t len, const uint8_t* mask_row, const uint32_t* ss, const char* residues, char* out);
+/* The seed reader for a consensus structure whose pairs may cross (`dafs --knots`).  As
+ * dafs_host_seed_clean_structure, with level (room for strlen(rows[0]) bytes): the pair's level at both of its columns, 0xFF at
+ * unpaired columns, the convention of dafs_hip_consensus_structures_levels.  Groups, in this order: "()", "[]", "{}", "<>", then
+ * the letters 'A'..'Z', an upper-case letter opening and the same letter in lower case closing; each group is matched
+ * last-in-first-out with itself; ". , : _ - ~" are unpaired.  A pair that loses a column with the all-gap columns is dropped;
+ * then, group after group, a non-empty group goes to the lowest level at which none of its pairs crosses (a < i < b < j or
+ * i < a < j < b) a pair already placed there.  Refused (DAFS_HIP_EINVAL, message in dafs_hip_last_error): any other character,
+ * a length that is not the rows', an unbalanced group (a lower-case letter that closes nothing and an upper-case letter never
+ * closed among them), and a group that would need a level beyond DAFS_HIP_MAX_LEVELS, which the message names. */
+int dafs_host_seed_clean_structure_levels(uint32_t n, const char* const* names, const char* const* rows, const char* structure,
+                                          uint32_t* ss, uint8_t* level, uint32_t* columns, char** cleaned);
+/* dafs_host_row_constraint once per level of a structure with levels (the reference makes these strings in
+ * DAFS::update_basepairing_probability, src/dafs.cpp:635-653).  level[len] as above (NULL: every pair of level 0), 1 <= nlevels <=
+ * DAFS_HIP_MAX_LEVELS, every pair's level below nlevels and equal at both columns (else DAFS_HIP_EINVAL).  out: nlevels strings,
+ * string k at out + k * (residues + 1).  String k: '?' everywhere; a pair of level k as dafs_host_row_constraint writes it; a pair
+ * of another level whose two residues the row holds '.' at both, complementary or not (src/dafs.cpp:650); a pair the row holds
+ * one residue of stays '?'.  A string k >= 1 without a '(' is left empty: the row is not folded for that level.  With
+ * nlevels = 1 the one string is dafs_host_row_constraint's. */
+int dafs_host_row_constraint_levels(uint32_t len, const uint8_t* mask_row, const uint32_t* ss, const uint8_t* level, uint32_t nlevels,
+                                    const char* residues, char* out);
 /* dafs_host_seed_table with the structure support of every placed sequence (dafs_hip_structure_support) as four more columns,
  * "pairs canonical half expected" (expected as %.9g); all four arrays NULL: the table of dafs_host_seed_table. */
 int dafs_host_seed_table_support(uint32_t n, const char* const* headers, const uint32_t* length, const uint32_t* matched,
