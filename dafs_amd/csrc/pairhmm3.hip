@@ -403,7 +403,11 @@ extern "C" int dafs_hipk_pairhmm3_launch(const dafs_pairhmm3_args* args, const d
   pair_variant* v = nullptr;
   for (pair_variant& c : k_variants)
     if (c.G == (int)plan->group && c.W == (int)plan->width) v = &c;
-  if (!v || plan->nwaves % 4) return DAFS_HIP_EINVAL;
+  if (!v || plan->nwaves % 4 || plan->nwaves == 0) return DAFS_HIP_EINVAL;
+  // nwaves may be lower than the planner's (the wavefronts then take more batches each), never more than the scratch holds
+  // (nwaves * per_wave > scratch_bytes, written as a division: the product of caller-supplied numbers could wrap)
+  const uint64_t per_wave = (uint64_t)plan->slab_steps * plan->width * 64 * sizeof(float) * 2;  // two planes
+  if (per_wave && plan->nwaves > plan->scratch_bytes / per_wave) return DAFS_HIP_EINVAL;
   const uint32_t rp_cap = plan->slab_steps - plan->group + 1;  // max_len1 + 1 row pointers
   const size_t rp_lds = (size_t)4 * (64 / v->G) * rp_cap * sizeof(uint32_t);
   if (rp_lds > 60 * 1024) return DAFS_HIP_ETOOLONG;

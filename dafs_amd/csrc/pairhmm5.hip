@@ -306,7 +306,10 @@ extern "C" int dafs_hipk_pairhmm5_launch(const dafs_pairhmm5_args* args, const d
   const pair_variant* v = nullptr;
   for (const pair_variant& c : k_variants5)
     if (c.G == (int)plan->group && c.W == (int)plan->width) v = &c;
-  if (!v || plan->nwaves % 4) return DAFS_HIP_EINVAL;
+  if (!v || plan->nwaves % 4 || plan->nwaves == 0) return DAFS_HIP_EINVAL;
+  // as in dafs_hipk_pairhmm3_launch, with five planes per wavefront
+  const uint64_t per_wave = (uint64_t)plan->slab_steps * plan->width * 64 * sizeof(float) * 5;
+  if (per_wave && plan->nwaves > plan->scratch_bytes / per_wave) return DAFS_HIP_EINVAL;
   const uint32_t rp_cap = plan->slab_steps - plan->group + 1;
   const size_t lds = (size_t)4 * (64 / v->G) * rp_cap * sizeof(uint32_t);
   if (lds > 60 * 1024) return DAFS_HIP_ETOOLONG;

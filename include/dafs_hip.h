@@ -61,7 +61,11 @@ typedef struct {
   uint32_t off2, len2; /* sequence y (columns) */
 } dafs_pair_task;
 
-/* Launch geometry chosen by dafs_hipk_pairhmm_plan for a batch. */
+/* Launch geometry chosen by dafs_hipk_pairhmm_plan for a batch.  A caller may lower nwaves to any positive multiple
+ * of 4 before the launch: the wavefronts are persistent and then take more batches of 64/group pairs each, on the
+ * first nwaves regions of the same scratch.  The launches return DAFS_HIP_EINVAL for nwaves == 0, for nwaves % 4 != 0
+ * and for an nwaves whose scratch (nwaves * slab_steps * width * 64 * 4 bytes * planes; 2 planes ProbCons, 5
+ * CONTRAlign) scratch_bytes does not cover.  The scratch may hold anything when a launch starts. */
 typedef struct {
   uint32_t group;        /* lanes cooperating on one pair: 16, 32 or 64           */
   uint32_t width;        /* columns owned by each lane                              */

@@ -104,6 +104,37 @@ def test_plan_covers_lengths():
     assert capi.pairhmm_plan(0, 10, 10, p) == -1
 
 
+def test_pair_launches_refuse_a_wave_count_the_scratch_does_not_cover():
+    """dafs_hipk_pairhmm3_launch / dafs_hipk_pairhmm5_launch: nwaves == 0, nwaves not a multiple of 4 and an nwaves whose
+    scratch plan.scratch_bytes does not cover are DAFS_HIP_EINVAL before any device call (the arguments hold null
+    pointers: nothing here reaches a launch).  The refusal is of the plan alone; a lowered nwaves is not refused for
+    these reasons (that it launches is the GPU tests' part)."""
+    from dafs_amd import capi
+    for plan_fn, launch, Args, planes in ((capi.pairhmm_plan, capi.pairhmm3_launch, capi.Pairhmm3Args, 2),
+                                          (capi.pairhmm5_plan, capi.pairhmm5_launch, capi.Pairhmm5Args, 5)):
+        a = Args()
+        a.ntasks = 65
+
+        def rc(**kw):
+            p = capi.PairhmmPlan()
+            assert plan_fn(65, 70, 70, p) == 0
+            assert p.nwaves >= 8 and p.scratch_bytes == p.nwaves * p.slab_steps * p.width * 64 * 4 * planes
+            for k, v in kw.items():
+                setattr(p, k, v(p))
+            return launch(C.byref(a), C.byref(p), None)
+
+        assert rc(nwaves=lambda p: 0) == -1
+        assert rc(nwaves=lambda p: 2) == -1
+        assert rc(nwaves=lambda p: p.nwaves + 4) == -1                      # one workgroup more than the scratch holds
+        assert rc(scratch_bytes=lambda p: p.scratch_bytes - 1) == -1        # one byte short
+        assert rc(scratch_bytes=lambda p: 0) == -1
+        assert rc(nwaves=lambda p: 0xFFFFFFFC) == -1                        # no wrap of the product
+        assert rc(nwaves=lambda p: 4, scratch_bytes=lambda p: 4 * p.slab_steps * p.width * 64 * 4 * planes - 1) == -1
+        assert rc(group=lambda p: 48) == -1                                 # no such instance (as before)
+        a.ntasks = 0
+        assert rc(nwaves=lambda p: 0) == 0                                  # nothing to do comes first (as before)
+
+
 def test_dd_node_plan_reproduces_the_recorded_plans(monkeypatch):
     """dafs_hipk_dd_node_plan (the solver's node planner, as nodes_open runs it) against the plans recorded in
     tests/golden/dd_node_plan.npz: (L1, L2) across every threshold of the forms, under each switch setting the GPU tests

@@ -4,12 +4,11 @@ pointers, columns and values of both matrices, similarity); the oracle also conf
 window edges where the case wants them."""
 import os
 import random
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
+import pair_raw
 from dafs_amd import synth
 from test_pair_records_gpu import LOW_COMPLEXITY
 from test_pairhmm_gpu import _check_set
@@ -98,54 +97,6 @@ def test_width_w_and_w_minus_1(oracle):
     _run(oracle, [first, _rand(62, 62), _rand(63, 63), _rand(64, 64)], group=32, width=3, window=32)
 
 
-_POOL_CHILD = """
-import ctypes as C
-import sys
-import numpy as np
-import torch  # before the library: both then share torch's HIP runtime, as in bench.py
-torch.cuda.init()
-sys.path.insert(0, %r)
-from dafs_amd import capi
-out, pool_cap, tail, th = sys.argv[1], int(sys.argv[2]), int(sys.argv[3]), float(sys.argv[4])
-seqs = sys.argv[5:]
-dev = torch.device("cuda", 0)
-lens = np.array([len(s) for s in seqs], np.uint32)
-px, py = np.triu_indices(len(seqs), 1)
-n = len(px)
-off = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint32)
-tasks = np.zeros((n, 4), np.uint32)
-tasks[:, 0] = off[px]; tasks[:, 1] = lens[px]; tasks[:, 2] = off[py]; tasks[:, 3] = lens[py]
-rp_sizes = (lens[px] + 1 + lens[py] + 1).astype(np.uint64)
-rp_off = np.concatenate([[0], np.cumsum(rp_sizes)])[:-1].astype(np.uint64)
-plan = capi.PairhmmPlan()
-capi.check(capi.pairhmm_plan(n, int(lens[px].max()), int(lens[py].max()), plan))
-d_codes = torch.from_numpy(np.concatenate([capi.encode(s) for s in seqs])).to(dev)
-d_tasks = torch.from_numpy(tasks.view(np.int32)).to(dev)
-d_rp_off = torch.from_numpy(rp_off.view(np.int64)).to(dev)
-d_scratch = torch.empty(plan.scratch_bytes // 4, dtype=torch.float32, device=dev)
-counters = torch.zeros(4, dtype=torch.int64, device=dev)  # [pool_top, queue, status, -]
-rowptr = torch.zeros(int(rp_sizes.sum()), dtype=torch.int32, device=dev)
-col = torch.full((pool_cap + tail,), 0x5A5A5A5A, dtype=torch.int32, device=dev)
-val = torch.full((pool_cap + tail,), 0x5A5A5A5A, dtype=torch.int32, device=dev)
-pair_off = torch.zeros(n, dtype=torch.int64, device=dev)
-pair_nnz = torch.zeros(n, dtype=torch.int32, device=dev)
-sim = torch.zeros(n, dtype=torch.float32, device=dev)
-a = capi.Pairhmm3Args()
-a.codes = d_codes.data_ptr(); a.tasks = d_tasks.data_ptr(); a.ntasks = n; a.th = th
-a.scratch = d_scratch.data_ptr()
-a.pool_top = counters.data_ptr(); a.queue = counters.data_ptr() + 8; a.status = counters.data_ptr() + 16
-a.rp_off = d_rp_off.data_ptr(); a.rowptr_pool = rowptr.data_ptr()
-a.ent_col = col.data_ptr(); a.ent_val = val.data_ptr(); a.pool_cap = pool_cap
-a.pair_off = pair_off.data_ptr(); a.pair_nnz = pair_nnz.data_ptr(); a.sim = sim.data_ptr()
-capi.pairhmm3_default_model(C.byref(a.model))
-stream = torch.cuda.current_stream()
-capi.check(capi.pairhmm3_launch(C.byref(a), C.byref(plan), C.c_void_p(stream.cuda_stream)))
-torch.cuda.synchronize()
-np.savez(out, status=counters.cpu().numpy().view(np.int32)[4:5], col=col.cpu().numpy().view(np.uint32), val=val.cpu().numpy().view(np.uint32),
-         pair_off=pair_off.cpu().numpy(), pair_nnz=pair_nnz.cpu().numpy())
-"""
-
-
 def test_pool_too_small_is_a_status(oracle, tmp_path):
     """The raw launch, as bench.py drives it, with half the pool the pairs need: DAFS_HIP_EOVERFLOW, the pairs whose
     reservation fitted are complete, nothing else in the pool is touched, and neither is the tail of the allocations
@@ -158,12 +109,8 @@ def test_pool_too_small_is_a_status(oracle, tmp_path):
     pool_cap = need // 2
     tail = 4096
     CANARY = 0x5A5A5A5A
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    path = str(tmp_path / "pool.npz")
-    r = subprocess.run([sys.executable, "-c", _POOL_CHILD % os.path.join(root, "tests"), path, str(pool_cap), str(tail), repr(th)] + seqs,
-                       cwd=root, capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stderr  # a handled status, not a fault
-    got = np.load(path)
+    # run() asserts that the child's return code is 0: a handled status, not a fault
+    got = pair_raw.run(tmp_path, [pair_raw.spec(oracle, 0, th, seqs, pairs, CANARY, pool_cap=pool_cap)], tail=tail)[0]
     assert int(got["status"][0]) == -5, got["status"]  # DAFS_HIP_EOVERFLOW
     h_col, h_val = got["col"], got["val"]
     h_off, h_nnz = got["pair_off"], got["pair_nnz"]

@@ -12,18 +12,23 @@ pytestmark = pytest.mark.gpu
 EX = os.path.join(os.path.dirname(__file__), "golden")
 
 
-def _check_set(oracle, seqs, th=0.01, force_group=None, model=0):
+def _check_set(oracle, seqs, th=0.01, force_group=None, model=0, ctx=None):
+    """ctx: a Context of the caller's, used and left open (its scratch then carries what its earlier calls left);
+    without one, a fresh Context per call"""
     from dafs_amd import capi
     if force_group:
         os.environ["DAFS_HIP_FORCE_GROUP"] = str(force_group)
     else:
         os.environ.pop("DAFS_HIP_FORCE_GROUP", None)
-    ctx = capi.Context(0)
+    own = ctx is None
+    if own:
+        ctx = capi.Context(0)
     try:
         ctx.set_sequences(seqs)
         res = ctx.align_posteriors(model, th)
     finally:
-        ctx.close()
+        if own:
+            ctx.close()
         os.environ.pop("DAFS_HIP_FORCE_GROUP", None)
     n = len(seqs)
     assert len(res) == n * (n - 1) // 2
