@@ -165,6 +165,9 @@ _make_brackets_levels = _sig("dafs_hip_make_brackets_levels", None, [C.c_uint32,
 _nussinov_decode_levels = _sig("dafs_hip_nussinov_decode_levels", C.c_int,
                                [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])
 MAX_LEVELS = 4
+MAX_CANDIDATES = 16
+_nussinov_decode_auto = _sig("dafs_hip_nussinov_decode_auto", C.c_int,
+                             [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32] + [C.c_void_p] * 10)
 _dd_default_params = _sig("dafs_hip_dd_default_params", None, [C.POINTER(DDParams)])
 _solve_nodes = _sig("dafs_hip_solve_nodes", C.c_int,
                     [C.c_void_p, C.c_uint32, C.POINTER(NodeInput), C.POINTER(DDParams), C.POINTER(NodeOutput)])
@@ -249,6 +252,10 @@ _structure_levels_bytes = _sig("dafs_host_structure_levels_bytes", C.c_uint64, [
 _consensus_structures_levels = _sig("dafs_hip_consensus_structures_levels", C.c_int,
                                     [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_void_p])
+_structure_auto_bytes = _sig("dafs_host_structure_auto_bytes", C.c_uint64, [C.c_uint32, C.c_uint32, C.c_uint32])
+_consensus_structures_auto = _sig("dafs_hip_consensus_structures_auto", C.c_int,
+                                  [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
+                                  + [C.c_void_p] * 10)
 _consensus_structures = _sig("dafs_hip_consensus_structures", C.c_int,
                              [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p])
 _alignment_reliability = _sig("dafs_hip_alignment_reliability", C.c_int,
@@ -512,6 +519,66 @@ class PairPosteriors:
         if not transposed:
             return self._rowptr[r0:r0 + l1], self._col[e0:e0 + n], self._val[e0:e0 + n]
         return self._rowptr[r0 + l1:r0 + l1 + l2], self._col[e0 + n:e0 + 2 * n], self._val[e0 + n:e0 + 2 * n]
+
+
+class AutoThresholds:
+    """Thresholds chosen by pseudo-expected accuracy: every level takes the candidate 1 / (1 + gamma)
+    whose structure has the best F against the matrix it was decoded from, and a level is kept only if it raises F.
+    gammas: 1 to MAX_CANDIDATES weights, strictly increasing and positive (the command line's -G); levels: at most this
+    many levels, 1 to MAX_LEVELS."""
+
+    def __init__(self, gammas=(1, 2, 4, 8, 16, 32), levels=1):
+        self.gammas = tuple(float(g) for g in gammas)
+        self.levels = int(levels)
+        if not 1 <= self.levels <= MAX_LEVELS:
+            raise ValueError("AutoThresholds: 1 to %d levels" % MAX_LEVELS)
+        if not 1 <= len(self.gammas) <= MAX_CANDIDATES:
+            raise ValueError("AutoThresholds: 1 to %d candidates" % MAX_CANDIDATES)
+        if not all(g > 0 and np.isfinite(g) for g in self.gammas) or any(b <= a for a, b in zip(self.gammas, self.gammas[1:])):
+            raise ValueError("AutoThresholds: the weights are positive and strictly increasing")
+        self.candidates = np.array([np.float32(1.0 / (1.0 + g)) for g in self.gammas], np.float32)  # as -G is converted
+
+    def __repr__(self):
+        return "AutoThresholds(gammas=%r, levels=%d)" % (self.gammas, self.levels)
+
+
+class AutoChoice:
+    """What an automatic choice kept for one alignment: .chosen [levels] (the candidate's index, NONE for an empty level),
+    .thresholds and .gammas (of the kept levels), .sum_p (S), .tp and .npairs [levels] (T and n of each kept level alone),
+    .cand_tp and .cand_pairs [levels, candidates] (every decode's T and n; 0 for the levels that were not decoded), and .f, the
+    pseudo-expected F of the whole structure, 2 sum(tp) / (sum(npairs) 2^30 + sum_p), a float for display only."""
+
+    def __init__(self, auto, chosen, sum_p, tp, npairs, cand_tp, cand_pairs):
+        self.chosen, self.sum_p, self.tp, self.npairs = chosen, int(sum_p), tp, npairs
+        self.cand_tp, self.cand_pairs = cand_tp, cand_pairs
+        kept = [int(c) for c in chosen if c != NONE]
+        self.thresholds = auto.candidates[kept]
+        self.gammas = tuple(auto.gammas[c] for c in kept)
+        self.f = pseudo_f(sum(int(t) for t in tp), sum(int(n) for n in npairs), self.sum_p)
+
+
+class _AutoArrays:
+    """the arrays dafs_hip_consensus_structures_auto fills beside ss, level and score, for n alignments"""
+
+    def __init__(self, n, K, ncand):
+        self.chosen = np.zeros((n, K), np.uint32)
+        self.sum_p = np.zeros(n, np.uint64)
+        self.tp = np.zeros((n, K), np.uint64)
+        self.npairs = np.zeros((n, K), np.uint32)
+        self.cand_tp = np.zeros((n, K, ncand), np.uint64)
+        self.cand_pairs = np.zeros((n, K, ncand), np.uint32)
+
+    def pointers(self):
+        return [x.ctypes.data for x in (self.chosen, self.sum_p, self.tp, self.npairs, self.cand_tp, self.cand_pairs)]
+
+    def choice(self, auto, a):
+        return AutoChoice(auto, self.chosen[a], self.sum_p[a], self.tp[a], self.npairs[a], self.cand_tp[a], self.cand_pairs[a])
+
+
+def pseudo_f(tp, npairs, sum_p):
+    """2 T / (n 2^30 + S) as a float, 0.0 when the denominator is 0 (display only: the library compares in integers)"""
+    den = int(npairs) * 2 ** 30 + int(sum_p)
+    return 2 * int(tp) / den if den else 0.0
 
 
 class Context:
@@ -902,6 +969,19 @@ class Context:
         check(_nussinov_decode_levels(self._h, len(th), th.ctypes.data, L, p.ctypes.data, ss.ctypes.data, level.ctypes.data, score.ctypes.data))
         return score[:len(th)], ss, level
 
+    def nussinov_auto(self, p, auto):
+        """dafs_hip_nussinov_decode_auto: the level-by-level decode of the dense matrix p with every level's threshold chosen
+        from auto's candidates (an AutoThresholds); returns (scores[auto.levels], ss, level, AutoChoice)"""
+        p = np.ascontiguousarray(p, np.float32)
+        L, K, cand = p.shape[0], auto.levels, auto.candidates
+        ss = np.zeros(L, np.uint32)
+        level = np.zeros(L, np.uint8)
+        score = np.zeros(K, np.float32)
+        o = _AutoArrays(1, K, len(cand))
+        check(_nussinov_decode_auto(self._h, K, len(cand), cand.ctypes.data, L, p.ctypes.data, ss.ctypes.data, level.ctypes.data,
+                                    score.ctypes.data, *o.pointers()))
+        return score, ss, level, o.choice(auto, 0)
+
     def nussinov_dense(self, p, q, th, w=0.0):
         """the dense Nussinov class (q None: the final-decode overload); returns (score, ss)"""
         p = np.ascontiguousarray(p, np.float32)
@@ -1047,10 +1127,14 @@ class Context:
         """dafs_hip_consensus_structures: the common structures of many alignments in one call.  alignments: a list of
         (seq, mask) as consensus_structure takes them; returns a list of (score, ss), each what consensus_structure gives.
         th a sequence of thresholds: dafs_hip_consensus_structures_levels, one level per threshold; returns a list of
-        (scores[len(th)], ss, level)."""
+        (scores[len(th)], ss, level).
+        th an AutoThresholds: dafs_hip_consensus_structures_auto, every level's threshold chosen from its candidates; returns a
+        list of (scores[th.levels], ss, level, AutoChoice)."""
         als = [(np.ascontiguousarray(s, np.uint32).reshape(-1), np.ascontiguousarray(m, np.uint8)) for s, m in alignments]
         if any(m.ndim != 2 or m.shape[0] != len(s) for s, m in als):
             raise ValueError("consensus_structures: every alignment is (seq[n], mask[n, len])")
+        if isinstance(th, AutoThresholds):
+            return self._consensus_structures_auto(als, th)
         if np.ndim(th) != 0:
             return self._consensus_structures_levels(als, np.ascontiguousarray(th, np.float32).reshape(-1))
         if not als:
@@ -1084,6 +1168,26 @@ class Context:
                                            th.ctypes.data, ss.ctypes.data, level.ctypes.data, score.ctypes.data))
         cuts = np.cumsum(lens)[:-1]
         return [(score[a * K:(a + 1) * K], x, lv) for a, (x, lv) in enumerate(zip(np.split(ss[:total], cuts), np.split(level[:total], cuts)))]
+
+    def _consensus_structures_auto(self, als, auto):
+        K, cand = auto.levels, auto.candidates
+        if not als:
+            check(_consensus_structures_auto(self._h, 0, None, None, None, None, K, len(cand), cand.ctypes.data, *[None] * 9))
+            return []
+        n_rows = np.array([m.shape[0] for _, m in als], np.uint32)
+        lens = np.array([m.shape[1] for _, m in als], np.uint32)
+        seq = np.ascontiguousarray(np.concatenate([s for s, _ in als]), np.uint32)
+        mask = np.ascontiguousarray(np.concatenate([m.reshape(-1) for _, m in als]), np.uint8)
+        total = int(lens.sum())
+        ss = np.zeros(max(total, 1), np.uint32)
+        level = np.zeros(max(total, 1), np.uint8)
+        score = np.zeros(len(als) * K, np.float32)
+        o = _AutoArrays(len(als), K, len(cand))
+        check(_consensus_structures_auto(self._h, len(als), n_rows.ctypes.data, lens.ctypes.data, seq.ctypes.data, mask.ctypes.data, K,
+                                         len(cand), cand.ctypes.data, ss.ctypes.data, level.ctypes.data, score.ctypes.data, *o.pointers()))
+        cuts = np.cumsum(lens)[:-1]
+        return [(score[a * K:(a + 1) * K], x, lv, o.choice(auto, a))
+                for a, (x, lv) in enumerate(zip(np.split(ss[:total], cuts), np.split(level[:total], cuts)))]
 
     def structure_support(self, alignments, structures):
         """dafs_hip_structure_support: how far every row of each alignment keeps the structure given for it.  alignments: a

@@ -932,13 +932,71 @@ struct lv_run {
   const uint32_t* len_of;
   const cs_desc* descs;      // host, [m]: ss = the level's own array, score = the first of the alignment's K scores
   const lv_desc* d_lv;       // device, [m]
-  uint8_t* d_up;             // device, lv_up_bytes(m): the descriptors and indices of the alignments still going, per level
+  uint8_t* d_up;             // device, lv_up_bytes(m, C): the descriptors and indices of the alignments still going, per level
   uint32_t* d_flags;         // device, [K][m]
+  // thresholds chosen by pseudo-expected accuracy; C = 0: they are given, th[K], and the rest is unused
+  uint32_t C;
+  const float* cand;         // [C]
+  const pea_desc* pea;       // host, [m]
+  const pea_desc* d_pea;     // device, [m]
 };
-size_t lv_up_bytes(uint32_t m) { return (size_t)m * (sizeof(cs_desc) + 4); }
+size_t lv_up_bytes(uint32_t m, uint32_t C) { return (size_t)m * ((C ? C : 1) * sizeof(cs_desc) + 4); }
+
+// What the choice of section 27 keeps per chunk beside the structures: the sums and the chosen candidates of its m alignments,
+// carved back to back behind the scores, so that one fill clears them and the results' one copy brings them, and the
+// candidates' scores.
+struct pea_arrays {
+  uint64_t *sum = nullptr, *tp = nullptr, *ctp = nullptr, *base = nullptr;
+  uint32_t *chosen = nullptr, *np = nullptr, *cnp = nullptr;
+  float* cscore = nullptr;
+  size_t fill_bytes = 0;
+  void carve_results(carver& cv, size_t m, uint32_t K, uint32_t C) {
+    sum = cv.take<uint64_t>(m);
+    tp = cv.take<uint64_t>(m * K);
+    ctp = cv.take<uint64_t>(m * K * C);
+    chosen = cv.take<uint32_t>(m * K);
+    np = cv.take<uint32_t>(m * K);
+    cnp = cv.take<uint32_t>(m * K * C);
+    base = cv.take<uint64_t>(m * 2);
+    // the one fill: from the first of these arrays to the end of the last (the carver only moves forward; the padding
+    // between them belongs to nobody).  Null in the sizing pass, where nothing is filled.
+    fill_bytes = sum ? (size_t)((const uint8_t*)(base + m * 2) - (const uint8_t*)sum) : 0;
+  }
+  void carve_scores(carver& cv, size_t m, uint32_t C) { cscore = cv.take<float>(m * C); }
+  // alignment j's descriptor; the caller sets css
+  pea_desc desc(size_t j, uint32_t K, uint32_t C, uint32_t L, const float* p, uint32_t* lss, float* score) const {
+    pea_desc d;
+    memset(&d, 0, sizeof d);
+    d.L = L; d.p = p; d.lss = lss; d.score = score; d.cscore = cscore + j * C;
+    d.sum = sum + j; d.base = base + 2 * j; d.tp = tp + j * K; d.ctp = ctp + j * K * C;
+    d.chosen = chosen + j * K; d.np = np + j * K; d.cnp = cnp + j * K * C;
+    return d;
+  }
+};
+
+// the caller's arrays of the choice; each may be null
+struct pea_out { uint32_t* chosen; uint64_t* sum_p; uint64_t* tp; uint32_t* npairs; uint64_t* cand_tp; uint32_t* cand_pairs; };
+
+// Alignment j's part of the copied results (`at` maps a device pointer to its bytes) into the caller's arrays at alignment a.
+// ran: the levels it was launched at; the others chose nothing.
+template <class At>
+void pea_results(const pea_arrays& pa, const At& at, size_t j, size_t a, uint32_t K, uint32_t C, uint32_t ran, const pea_out& o) {
+  if (o.sum_p) memcpy(o.sum_p + a, at(pa.sum + j), 8);
+  if (o.tp) memcpy(o.tp + a * K, at(pa.tp + j * K), (size_t)K * 8);
+  if (o.npairs) memcpy(o.npairs + a * K, at(pa.np + j * K), (size_t)K * 4);
+  if (o.cand_tp) memcpy(o.cand_tp + a * K * C, at(pa.ctp + j * K * C), (size_t)K * C * 8);
+  if (o.cand_pairs) memcpy(o.cand_pairs + a * K * C, at(pa.cnp + j * K * C), (size_t)K * C * 4);
+  if (o.chosen) {
+    memcpy(o.chosen + a * K, at(pa.chosen + j * K), (size_t)ran * 4);
+    for (uint32_t k = ran; k < K; ++k) o.chosen[a * K + k] = DAFS_HIP_NONE;
+  }
+}
 
 // Level 0 decodes every alignment; level k > 0 those with a pair at level k - 1, after the mask of that level.  One copy up
 // per level (descriptors with the level's score slot, and the indices), one copy of m flags down between two levels.
+// With candidates (r.C): S of every matrix before the first mask; per level the decoder once per candidate, each into its
+// own structure and score through its own descriptors (the work tables are shared: the launches follow one another), then
+// k_pea_pick, which leaves the chosen one where the merge reads the level's structure.
 // ran[j]: the levels alignment j was launched at.  up, flags: host buffers that must outlive the frame.
 int run_levels(call_frame& f, const lv_run& r, std::vector<uint8_t>& up, std::vector<uint32_t>& flags, std::vector<uint32_t>& ran) {
   const uint32_t m = r.m;
@@ -946,30 +1004,38 @@ int run_levels(call_frame& f, const lv_run& r, std::vector<uint8_t>& up, std::ve
   for (uint32_t j = 0; j < m; ++j) act[j] = j;
   ran.assign(m, 0);
   flags.assign(m, 0);
+  const uint32_t W = r.C ? r.C : 1;  // decodes per level; descriptors candidate by candidate, m apart
   cs_desc* d_cs = (cs_desc*)r.d_up;
-  uint32_t* d_act = (uint32_t*)(r.d_up + (size_t)m * sizeof(cs_desc));
+  const size_t act_off = (size_t)m * W * sizeof(cs_desc);
+  uint32_t* d_act = (uint32_t*)(r.d_up + act_off);
   int rc;
   for (uint32_t k = 0; k < r.K && !act.empty(); ++k) {
     const uint32_t n = (uint32_t)act.size();
-    up.resize(lv_up_bytes(m));
+    up.resize(lv_up_bytes(m, r.C));
     uint32_t first[kCsClassCount + 1] = {0};  // the classes' ranges of the active ones (act keeps the class order)
     for (uint32_t x = 0, cls = 0; x < n; ++x) {
       cs_desc d = r.descs[act[x]];
       d.score += k;
-      memcpy(up.data() + (size_t)x * sizeof(cs_desc), &d, sizeof d);
+      for (uint32_t c = 0; c < W; ++c) {
+        if (r.C) { d.ss = const_cast<uint32_t*>(r.pea[act[x]].css) + (size_t)c * (d.L + 1); d.score = const_cast<float*>(r.pea[act[x]].cscore) + c; }
+        memcpy(up.data() + ((size_t)c * m + x) * sizeof(cs_desc), &d, sizeof d);
+      }
       while (act[x] >= r.first_of[cls + 1]) ++cls;
       ++first[cls + 1];
       ++ran[act[x]];
     }
     for (uint32_t cls = 0; cls < kCsClassCount; ++cls) first[cls + 1] += first[cls];
-    memcpy(up.data() + (size_t)m * sizeof(cs_desc), act.data(), (size_t)n * 4);
-    if (f.up(d_cs, up.data(), (size_t)n * sizeof(cs_desc)) || f.up(d_act, up.data() + (size_t)m * sizeof(cs_desc), (size_t)n * 4)) return DAFS_HIP_ELAUNCH;
+    memcpy(up.data() + act_off, act.data(), (size_t)n * 4);
+    if (f.up(d_cs, up.data(), ((size_t)(W - 1) * m + n) * sizeof(cs_desc)) || f.up(d_act, up.data() + act_off, (size_t)n * 4)) return DAFS_HIP_ELAUNCH;
     for (uint32_t cls = 0; cls < kCsClassCount; ++cls) {
       const uint32_t nc = first[cls + 1] - first[cls];
       if (!nc) continue;
       if (k && (rc = levels_mask_launch(r.d_lv, d_act + first[cls], nc, r.len_of[cls], f.st))) return rc;
-      if ((rc = nussinov_batch_launch(d_cs + first[cls], nc, r.th[k], kCsClasses[cls].threads, r.lds_of[cls], f.st))) return rc;
+      if (r.C && !k && (rc = pea_total_launch(r.d_pea, d_act + first[cls], nc, r.len_of[cls], f.st))) return rc;
+      for (uint32_t c = 0; c < W; ++c)
+        if ((rc = nussinov_batch_launch(d_cs + (size_t)c * m + first[cls], nc, r.C ? r.cand[c] : r.th[k], kCsClasses[cls].threads, r.lds_of[cls], f.st))) return rc;
     }
+    if (r.C && (rc = pea_pick_launch(r.d_pea, d_act, n, k, r.C, f.st))) return rc;
     const bool more = k + 1 < r.K;
     if ((rc = levels_merge_launch(r.d_lv, d_act, n, k, more, f.st))) return rc;
     if (!more) break;
@@ -986,11 +1052,14 @@ int run_levels(call_frame& f, const lv_run& r, std::vector<uint8_t>& up, std::ve
 }  // namespace
 
 // nlevels = 0: the plain call (one decode, straight into the results).  nlevels >= 1: the level-by-level decode of section 25,
-// whose level 0 is that same decode into the level's own array, merged by k_levels_merge.
+// whose level 0 is that same decode into the level's own array, merged by k_levels_merge.  ncand >= 1 (with nlevels >= 1):
+// ths are the candidates every level chooses its threshold from (section 27), and po receives what the choice kept.
 static int consensus_structures_impl(dafs_hip_ctx* c, uint32_t nalign, const uint32_t* n_rows, const uint32_t* len, const uint32_t* seq,
-                                     const uint8_t* mask, uint32_t nlevels, const float* ths, uint32_t* ss, uint8_t* level, float* score) {
+                                     const uint8_t* mask, uint32_t nlevels, const float* ths, uint32_t* ss, uint8_t* level, float* score,
+                                     uint32_t ncand = 0, const pea_out* po = nullptr) {
   if (!c) return DAFS_HIP_EINVAL;
   const bool levels = nlevels != 0;
+  const uint32_t C = ncand;
   const uint32_t K = levels ? nlevels : 1;
   const float th = ths[0];
   if (nalign == 0) return DAFS_HIP_OK;
@@ -1007,7 +1076,9 @@ static int consensus_structures_impl(dafs_hip_ctx* c, uint32_t nalign, const uin
     row0[a + 1] = row0[a] + n_rows[a];
     mask0[a + 1] = mask0[a] + (size_t)n_rows[a] * len[a];
     col0[a + 1] = col0[a] + len[a];
-    bytes[a] = levels ? dafs_host_structure_levels_bytes(n_rows[a], len[a]) : dafs_host_structure_bytes(n_rows[a], len[a]);
+    bytes[a] = C        ? dafs_host_structure_auto_bytes(n_rows[a], len[a], C)
+               : levels ? dafs_host_structure_levels_bytes(n_rows[a], len[a])
+                        : dafs_host_structure_bytes(n_rows[a], len[a]);
   }
   for (uint32_t a = 0; a < nalign; ++a) {
     const int rc = make_geom(c, n_rows[a], len[a], seq + row0[a], mask + mask0[a], g[a]);
@@ -1028,6 +1099,7 @@ static int consensus_structures_impl(dafs_hip_ctx* c, uint32_t nalign, const uin
   std::vector<uint8_t> head, out, lv_up;
   std::vector<lv_desc> lv;
   std::vector<uint32_t> lv_flags, lv_ran;
+  std::vector<pea_desc> pea;
   call_frame f(c);  // `head`, `out` and the level buffers are in flight when an error ends a chunk early
   for (uint32_t a0 = 0; a0 < nalign;) {
     uint32_t a1 = a0;
@@ -1065,12 +1137,16 @@ static int consensus_structures_impl(dafs_hip_ctx* c, uint32_t nalign, const uin
     lv_desc* d_lv = nullptr;
     uint8_t* d_lv_up = nullptr;
     uint32_t* d_flags = nullptr;
+    pea_desc* d_pea = nullptr;
+    pea_arrays pa;
     if (levels) lv.assign(m, lv_desc());
+    if (C) pea.assign(m, pea_desc());
     for (int pass = 0; pass < 2; ++pass) {
       cv.used = 0;
       d_nodes = cv.take<dd_node>(m);
       if (levels) d_lv = cv.take<lv_desc>(m);  // the decoder descriptors then go up level by level (run_levels)
       else d_descs = cv.take<cs_desc>(m);
+      if (C) d_pea = cv.take<pea_desc>(m);
       for (uint32_t j = 0; j < m; ++j) {
         const uint32_t k = order[j], a = a0 + k;
         dd_node& nd = nodes[j];
@@ -1095,11 +1171,13 @@ static int consensus_structures_impl(dafs_hip_ctx* c, uint32_t nalign, const uin
         }
       }
       d_scores = cv.take<float>((size_t)m * K);
+      if (C) pa.carve_results(cv, m, K, C);
       out_bytes = cv.used - out_off;
       if (levels) {
-        d_lv_up = cv.take<uint8_t>(lv_up_bytes(m));
+        d_lv_up = cv.take<uint8_t>(lv_up_bytes(m, C));
         d_flags = cv.take<uint32_t>((size_t)m * K);
       }
+      if (C) pa.carve_scores(cv, m, C);
       for (uint32_t j = 0; j < m; ++j) {
         const uint32_t L = len[a0 + order[j]];
         dd_fold& f = nodes[j].f[0];
@@ -1111,6 +1189,10 @@ static int consensus_structures_impl(dafs_hip_ctx* c, uint32_t nalign, const uin
           uint32_t* lss = cv.take<uint32_t>((size_t)L + 1);
           descs[j].ss = lss;
           lv[j].L = L; lv[j].flag_stride = m; lv[j].p = f.p; lv[j].lss = lss; lv[j].key = cv.take<uint32_t>(L); lv[j].flag = d_flags + j;
+          if (C) {
+            pea[j] = pa.desc(j, K, C, L, f.p, lss, d_scores + (size_t)j * K);
+            pea[j].css = cv.take<uint32_t>((size_t)C * (L + 1));
+          }
         }
       }
       if (pass == 0) {
@@ -1131,6 +1213,7 @@ static int consensus_structures_impl(dafs_hip_ctx* c, uint32_t nalign, const uin
     put(d_nodes, nodes.data(), (size_t)m * sizeof(dd_node));
     if (levels) put(d_lv, lv.data(), (size_t)m * sizeof(lv_desc));
     else put(d_descs, descs.data(), (size_t)m * sizeof(cs_desc));
+    if (C) put(d_pea, pea.data(), (size_t)m * sizeof(pea_desc));
     for (uint32_t j = 0; j < m; ++j) {
       const uint32_t a = a0 + order[j];
       const dd_fold& f = nodes[j].f[0];
@@ -1148,7 +1231,8 @@ static int consensus_structures_impl(dafs_hip_ctx* c, uint32_t nalign, const uin
       if (!levels && (rc = nussinov_batch_launch(d_descs + first_of[k], n, th, kCsClasses[k].threads, lds_of[k], f.st))) return rc;
     }
     if (levels) {
-      const lv_run run = {m, K, ths, first_of, lds_of, len_of, descs.data(), d_lv, d_lv_up, d_flags};
+      if (C && f.fill(pa.sum, 0, pa.fill_bytes)) return DAFS_HIP_ELAUNCH;
+      const lv_run run = {m, K, ths, first_of, lds_of, len_of, descs.data(), d_lv, d_lv_up, d_flags, C, ths, pea.data(), d_pea};
       if ((rc = run_levels(f, run, lv_up, lv_flags, lv_ran))) return rc;
     }
     out.resize(out_bytes);
@@ -1158,6 +1242,7 @@ static int consensus_structures_impl(dafs_hip_ctx* c, uint32_t nalign, const uin
       const uint32_t a = a0 + order[j];
       memcpy(ss + col0[a], out.data() + (ss_off[j] - out_off), (size_t)len[a] * 4);
       if (levels && level) memcpy(level + col0[a], out.data() + (level_off[j] - out_off), len[a]);
+      if (C && po) pea_results(pa, [&](const void* dev) { return out.data() + ((size_t)((const uint8_t*)dev - cv.base) - out_off); }, j, a, K, C, lv_ran[j], *po);
       if (!score) continue;
       const uint8_t* got = out.data() + ((size_t)((uint8_t*)(d_scores + (size_t)j * K) - cv.base) - out_off);
       const uint32_t ran = levels ? lv_ran[j] : 1;  // the levels this alignment was launched at; the others are empty
@@ -1174,6 +1259,14 @@ extern "C" int dafs_hip_consensus_structures(dafs_hip_ctx* c, uint32_t nalign, c
   return consensus_structures_impl(c, nalign, n_rows, len, seq, mask, 0, &th, ss, nullptr, score);
 }
 
+// the candidates of section 27: 1..16 thresholds inside (0, 1), strictly decreasing
+static bool auto_args_ok(uint32_t nlevels, uint32_t ncand, const float* cand) {
+  if (nlevels < 1 || nlevels > DAFS_HIP_MAX_LEVELS || ncand < 1 || ncand > DAFS_HIP_MAX_CANDIDATES || !cand) return false;
+  for (uint32_t c = 0; c < ncand; ++c)
+    if (!(cand[c] > 0.0f && cand[c] < 1.0f) || (c && !(cand[c] < cand[c - 1]))) return false;
+  return true;
+}
+
 static bool levels_args_ok(uint32_t nlevels, const float* th) {
   if (nlevels < 1 || nlevels > DAFS_HIP_MAX_LEVELS || !th) return false;
   for (uint32_t k = 1; k < nlevels; ++k)
@@ -1188,10 +1281,19 @@ extern "C" int dafs_hip_consensus_structures_levels(dafs_hip_ctx* c, uint32_t na
   return consensus_structures_impl(c, nalign, n_rows, len, seq, mask, nlevels, th, ss, level, score);
 }
 
+extern "C" int dafs_hip_consensus_structures_auto(dafs_hip_ctx* c, uint32_t nalign, const uint32_t* n_rows, const uint32_t* len, const uint32_t* seq,
+                                                  const uint8_t* mask, uint32_t nlevels, uint32_t ncand, const float* cand, uint32_t* ss,
+                                                  uint8_t* level, float* score, uint32_t* chosen, uint64_t* sum_p, uint64_t* tp,
+                                                  uint32_t* npairs, uint64_t* cand_tp, uint32_t* cand_pairs) {
+  if (!c || !auto_args_ok(nlevels, ncand, cand)) return DAFS_HIP_EINVAL;
+  const pea_out po = {chosen, sum_p, tp, npairs, cand_tp, cand_pairs};
+  return consensus_structures_impl(c, nalign, n_rows, len, seq, mask, nlevels, cand, ss, level, score, ncand, &po);
+}
+
 // The same decode of one dense host matrix (no store, no average): the matrix goes up as it is and is masked on the device.
-extern "C" int dafs_hip_nussinov_decode_levels(dafs_hip_ctx* c, uint32_t nlevels, const float* th, uint32_t L, const float* p, uint32_t* ss,
-                                               uint8_t* level, float* score) {
-  if (!c || !p || !ss || L == 0 || !levels_args_ok(nlevels, th)) return DAFS_HIP_EINVAL;
+// ncand >= 1: th are the candidates, as in consensus_structures_impl.
+static int decode_levels_impl(dafs_hip_ctx* c, uint32_t nlevels, const float* th, uint32_t L, const float* p, uint32_t* ss, uint8_t* level,
+                              float* score, uint32_t C, const pea_out* po) {
   if (hip_check(hipSetDevice(c->device))) return DAFS_HIP_ENODEV;
   const size_t LL = (size_t)L * L;
   const uint32_t K = nlevels;
@@ -1211,17 +1313,24 @@ extern "C" int dafs_hip_nussinov_decode_levels(dafs_hip_ctx* c, uint32_t nlevels
   lv_desc* d_lv = nullptr;
   uint8_t* d_lv_up = nullptr;
   uint32_t* d_flags = nullptr;
+  pea_desc pea;
+  pea_desc* d_pea = nullptr;
+  pea_arrays pa;
+  memset(&pea, 0, sizeof pea);
   size_t out_off = 0, out_bytes = 0;
   for (int pass = 0; pass < 2; ++pass) {
     cv.used = 0;
     d_lv = cv.take<lv_desc>(1);
-    d_lv_up = cv.take<uint8_t>(lv_up_bytes(1));
+    d_lv_up = cv.take<uint8_t>(lv_up_bytes(1, C));
     d_flags = cv.take<uint32_t>(K);
+    if (C) d_pea = cv.take<pea_desc>(1);
     out_off = (cv.used + 255) & ~(size_t)255;
     lv.ss = cv.take<uint32_t>((size_t)L + 1);
     lv.level = cv.take<uint8_t>(L);
     desc.score = cv.take<float>(K);
+    if (C) pa.carve_results(cv, 1, K, C);
     out_bytes = cv.used - out_off;
+    if (C) pa.carve_scores(cv, 1, C);
     lv.p = cv.take<float>(LL);
     desc.p = lv.p;
     carve_nuss(cv, L, desc.ws);
@@ -1229,6 +1338,10 @@ extern "C" int dafs_hip_nussinov_decode_levels(dafs_hip_ctx* c, uint32_t nlevels
     desc.ss = lss; lv.lss = lss;
     lv.key = cv.take<uint32_t>(L);
     lv.flag = d_flags; lv.flag_stride = 1;
+    if (C) {
+      pea = pa.desc(0, K, C, L, lv.p, lss, desc.score);
+      pea.css = cv.take<uint32_t>((size_t)C * (L + 1));
+    }
     if (pass == 0) {
       const int rc = c->work.reserve(cv.used + 256);
       if (rc) return rc;
@@ -1239,7 +1352,8 @@ extern "C" int dafs_hip_nussinov_decode_levels(dafs_hip_ctx* c, uint32_t nlevels
   std::vector<uint32_t> lv_flags, lv_ran;
   call_frame f(c);
   if (f.up(lv.p, p, LL * 4) || f.up(d_lv, &lv, sizeof lv)) return DAFS_HIP_ELAUNCH;
-  const lv_run run = {1, K, th, first_of, lds_of, len_of, &desc, d_lv, d_lv_up, d_flags};
+  if (C && (f.up(d_pea, &pea, sizeof pea) || f.fill(pa.sum, 0, pa.fill_bytes))) return DAFS_HIP_ELAUNCH;
+  const lv_run run = {1, K, th, first_of, lds_of, len_of, &desc, d_lv, d_lv_up, d_flags, C, th, &pea, d_pea};
   int rc;
   if ((rc = run_levels(f, run, lv_up, lv_flags, lv_ran))) return rc;
   if (f.down(out.data(), cv.base + out_off, out_bytes)) return DAFS_HIP_ELAUNCH;
@@ -1250,7 +1364,22 @@ extern "C" int dafs_hip_nussinov_decode_levels(dafs_hip_ctx* c, uint32_t nlevels
     memcpy(score, out.data() + ((uint8_t*)desc.score - cv.base - out_off), (size_t)lv_ran[0] * 4);
     for (uint32_t k = lv_ran[0]; k < K; ++k) score[k] = 0.0f;
   }
+  if (C && po) pea_results(pa, [&](const void* dev) { return out.data() + ((size_t)((const uint8_t*)dev - cv.base) - out_off); }, 0, 0, K, C, lv_ran[0], *po);
   return DAFS_HIP_OK;
+}
+
+extern "C" int dafs_hip_nussinov_decode_levels(dafs_hip_ctx* c, uint32_t nlevels, const float* th, uint32_t L, const float* p, uint32_t* ss,
+                                               uint8_t* level, float* score) {
+  if (!c || !p || !ss || L == 0 || !levels_args_ok(nlevels, th)) return DAFS_HIP_EINVAL;
+  return decode_levels_impl(c, nlevels, th, L, p, ss, level, score, 0, nullptr);
+}
+
+extern "C" int dafs_hip_nussinov_decode_auto(dafs_hip_ctx* c, uint32_t nlevels, uint32_t ncand, const float* cand, uint32_t L, const float* p,
+                                             uint32_t* ss, uint8_t* level, float* score, uint32_t* chosen, uint64_t* sum_p, uint64_t* tp,
+                                             uint32_t* npairs, uint64_t* cand_tp, uint32_t* cand_pairs) {
+  if (!c || !p || !ss || L == 0 || !auto_args_ok(nlevels, ncand, cand)) return DAFS_HIP_EINVAL;
+  const pea_out po = {chosen, sum_p, tp, npairs, cand_tp, cand_pairs};
+  return decode_levels_impl(c, nlevels, cand, L, p, ss, level, score, ncand, &po);
 }
 
 // DAFS::update_basepairing_probability (dafs.cpp:609-712, options --bp-update / --bp-update1; no RNAalifold term, one level

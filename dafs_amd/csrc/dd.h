@@ -225,6 +225,28 @@ struct lv_desc {
 // an end paired at the newest level or crosses none of its pairs; max_len >= every member's L.
 int levels_merge_launch(const lv_desc* d_descs, const uint32_t* d_act, uint32_t n, uint32_t k, int want_key, hipStream_t st);
 int levels_mask_launch(const lv_desc* d_descs, const uint32_t* d_act, uint32_t n, uint32_t max_len, hipStream_t st);
+// One alignment of a decode whose thresholds are chosen by pseudo-expected accuracy (pea.hip): what
+// k_pea_total and k_pea_pick read and write.  Level k's C candidates decode into css (C arrays of L + 1) and cscore; the
+// pick leaves the chosen one in the level's own array lss and its score in score[k], for k_levels_merge to go on from.
+struct pea_desc {
+  uint32_t L, pad_;
+  const float* p;        // L*L: the matrix the level's candidates were decoded from
+  const uint32_t* css;   // C*(L+1)
+  const float* cscore;   // [C]
+  uint32_t* lss;         // L
+  float* score;          // [K]
+  uint64_t* sum;         // [1]: S, zero before k_pea_total
+  uint64_t* base;        // [2]: T and n over the levels kept so far, zero before level 0
+  uint64_t* tp;          // [K]
+  uint64_t* ctp;         // [K*C]
+  uint32_t* chosen;      // [K]
+  uint32_t* np;          // [K]
+  uint32_t* cnp;         // [K*C]
+};
+// act[0..n): indices into descs, as above.  total: adds the q of every cell i < j of p to *sum; max_len >= every member's
+// L.  pick: level k's choice among ncand candidates.
+int pea_total_launch(const pea_desc* d_descs, const uint32_t* d_act, uint32_t n, uint32_t max_len, hipStream_t st);
+int pea_pick_launch(const pea_desc* d_descs, const uint32_t* d_act, uint32_t n, uint32_t k, uint32_t ncand, hipStream_t st);
 int nussinov_dense_launch(uint32_t L, const float* p, const float* q, float w, float th, float* dp, uint32_t* tr, uint32_t* stack, uint32_t* ss,
                           float* score, hipStream_t st);
 int nw_launch(uint32_t L1, uint32_t L2, const float* p, const float* q, float th, uint32_t* env, int compute_env,

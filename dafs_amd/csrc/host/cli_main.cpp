@@ -71,6 +71,11 @@ struct Options {
   std::string fold_decoder = "Nussinov";
   float fold_pct = 0.25f;
   std::vector<float> fold_th{0.2f}, fold_th1;
+  // -T auto / -G auto: the levels whose thresholds are chosen (0: the thresholds are given), the
+  // candidates' weights (--auto-gammas) and thresholds 1 / (1 + gamma), and --fold-auto-table OUT
+  uint32_t auto_levels = 0;
+  std::vector<float> auto_gammas{1.0f, 2.0f, 4.0f, 8.0f, 16.0f, 32.0f}, auto_cand;
+  std::string auto_table;
   bool no_alifold = false, ipknot = false, bp_update = false, bp_update1 = false;
   int device = 0;
   std::vector<int> devices;  // --devices: one process per entry for phase 1
@@ -293,6 +298,20 @@ const char* kHelp =
     "      --no-alifold      No use of RNAalifold (always the case in this build)\n"
     "  -T, --fold-th1 arg    Threshold for base-pairing probabilities of the conclusive common secondary structures\n"
     "  -G, --gamma1 arg      ... specified by 1/(gamma+1)\n"
+    "                        -T auto / -G auto: the threshold is chosen among the candidates 1/(gamma+1) of --auto-gammas by\n"
+    "                        pseudo-expected accuracy: every candidate is decoded and valued against the averaged base-pairing\n"
+    "                        matrix by F = 2T / (n + S) (T: the probability mass of its pairs, n: their number, S: the mass of\n"
+    "                        the matrix; integers, no rounding decides), and the best stays; ties go to the higher threshold.\n"
+    "                        With --fold-decoder Levels one auto per level (auto,auto: up to two levels, at most four): a level\n"
+    "                        stays only if it raises F.  >SS_cons is the chosen structure.  Not mixed with numbers, not as -t / -g,\n"
+    "                        not with --bp-update1 or --seed-structure; with Nussinov one entry\n"
+    "      --auto-gammas LIST  With -T auto / -G auto: the candidates' weights, strictly increasing, positive, at most 16\n"
+    "                        (default: 1,2,4,8,16,32)\n"
+    "      --fold-auto-table OUT  With -T auto / -G auto: per printed alignment a line\n"
+    "                        \"# alignment NAME columns L sum_p S\" (NAME: the first row's name in the --stockholm block) and one\n"
+    "                        tab-separated line per decoded (level, candidate): level gamma threshold pairs tp f chosen (level\n"
+    "                        0-based; tp and S in units of 2^-30; f: F of the levels kept below plus this candidate; chosen 0 / 1)\n"
+    "                        With --stockholm every block gains \"#=GF CC SS_cons auto thresholds T0,T1|none f F\"\n"
     "      --bp-update       Re-estimate the base-pairing matrices of the last alignment step under the predicted structure\n"
     "      --bp-update1      The same for the conclusive common secondary structure\n"
     "      --fold-aux FILENAME        Load base-pairing probability matrices from FILENAME\n"
@@ -304,6 +323,22 @@ std::vector<float> parse_floats(const std::string& s) {  // cxxopts vector<float
   std::string item;
   while (std::getline(ss, item, ',')) v.push_back(std::stof(item));
   return v;
+}
+
+// "auto" or "auto,auto,...": the number of entries; 0 when the value does not name auto at all.  Mixed with numbers, or more
+// than four entries: refused
+uint32_t parse_auto(const std::string& opt, const std::string& s) {
+  if (s.find("auto") == std::string::npos) return 0;
+  uint32_t n = 0;
+  std::stringstream ss(s);
+  std::string item;
+  while (std::getline(ss, item, ',')) {
+    if (item != "auto") throw opt + ": auto cannot be mixed with numbers (every level's threshold is chosen, or none is)";
+    ++n;
+  }
+  if (!s.empty() && s.back() == ',') throw opt + ": an empty entry";
+  if (n < 1 || n > DAFS_HIP_MAX_LEVELS) throw opt + ": " + std::to_string(n) + " entries; one to four levels are decoded";
+  return n;
 }
 
 Options parse(int argc, char** argv) {
@@ -325,12 +360,13 @@ Options parse(int argc, char** argv) {
       {"identity-matrix", {0, true}}, {"seed-nearest", {0, false}}, {"seed-nr", {0, true}}, {"describe", {0, true}},
       {"compare", {0, true}}, {"compare-ref", {0, true}}, {"compare-columns", {0, true}}, {"compare-matrix", {0, true}},
       {"cluster", {0, true}}, {"cluster-count", {0, true}}, {"cluster-min-size", {0, true}}, {"cluster-table", {0, true}},
-      {"cluster-tree", {0, true}}, {"cluster-linkage", {0, true}}, {"cluster-score", {0, true}}, {"cluster-structure-weight", {0, true}}};
+      {"cluster-tree", {0, true}}, {"cluster-linkage", {0, true}}, {"cluster-score", {0, true}}, {"cluster-structure-weight", {0, true}},
+      {"auto-gammas", {0, true}}, {"fold-auto-table", {0, true}}};
   std::map<char, std::string> shorts;
   for (const auto& kv : spec)
     if (kv.second.first) shorts[kv.second.first] = kv.first;
   std::vector<float> gamma, gamma1;
-  bool th_given = false, th1_given = false;
+  bool th_given = false, th1_given = false, auto_gammas_given = false;
   std::vector<std::string> given;  // every option as it was named, for --describe
   for (int i = 1; i < argc; ++i) {
     std::string arg = argv[i], name, value;
@@ -370,11 +406,34 @@ Options parse(int argc, char** argv) {
     else if (name == "fold-model") { o.fold_model = value; o.fold_model_given = true; }
     else if (name == "fold-decoder") o.fold_decoder = value;
     else if (name == "fold-pct") o.fold_pct = std::stof(value);
+    else if ((name == "fold-th" || name == "gamma") && parse_auto("-t / -g", value))
+      throw std::string("-t / -g: the threshold inside the dual-decomposition loop cannot be chosen automatically (-T auto / -G auto can)");
     else if (name == "fold-th") { o.fold_th = parse_floats(value); th_given = true; }
     else if (name == "gamma") gamma = parse_floats(value);
     else if (name == "no-alifold") o.no_alifold = true;
-    else if (name == "fold-th1") { o.fold_th1 = parse_floats(value); th1_given = true; }
-    else if (name == "gamma1") gamma1 = parse_floats(value);
+    else if ((name == "fold-th1" || name == "gamma1") && (o.auto_levels = parse_auto("-T / -G", value))) {}
+    else if (name == "fold-th1") { o.fold_th1 = parse_floats(value); th1_given = true; o.auto_levels = 0; }
+    else if (name == "gamma1") { gamma1 = parse_floats(value); o.auto_levels = 0; }
+    else if (name == "auto-gammas") {
+      size_t used = 0;
+      o.auto_gammas.clear();
+      std::stringstream gs(value);
+      std::string item;
+      while (std::getline(gs, item, ',')) {
+        float g = 0.0f;
+        try { g = std::stof(item, &used); } catch (const std::exception&) { used = 0; }
+        if (used == 0 || used != item.size() || !std::isfinite(g) || !(g > 0.0f) || (!o.auto_gammas.empty() && !(g > o.auto_gammas.back())))
+          throw std::string("--auto-gammas needs positive, strictly increasing weights");
+        o.auto_gammas.push_back(g);
+      }
+      if (o.auto_gammas.empty() || o.auto_gammas.size() > DAFS_HIP_MAX_CANDIDATES || value.back() == ',')
+        throw std::string("--auto-gammas needs one to sixteen weights");
+      auto_gammas_given = true;
+    }
+    else if (name == "fold-auto-table") {
+      if (value.empty()) throw std::string("--fold-auto-table needs a file name");
+      o.auto_table = value;
+    }
     else if (name == "ipknot") o.ipknot = true;
     else if (name == "bp-update") o.bp_update = true;
     else if (name == "bp-update1") o.bp_update1 = true;
@@ -608,6 +667,16 @@ Options parse(int argc, char** argv) {
   if (!o.seed_merged.empty() && !o.seed_structure) throw std::string(dafs_host_merged_refusal());
   if (o.knots && o.seed.empty() && o.describe.empty() && o.compare_ref.empty())
     throw std::string("--knots says how structures are read: it needs --seed, --describe or --compare-ref");
+  if ((auto_gammas_given || !o.auto_table.empty()) && !o.auto_levels) throw std::string("--auto-gammas and --fold-auto-table need -T auto or -G auto");
+  if (o.auto_levels) {
+    if (o.bp_update1) throw std::string("-T auto / -G auto: what the second decode of --bp-update1 would choose is undecided; they cannot be combined");
+    if (o.seed_structure) throw std::string("--seed-structure: nothing is decoded; -T auto and -G auto cannot be combined with --seed-structure");
+    if (o.fold_decoder == "Nussinov" && o.auto_levels > 1)
+      throw std::string("--fold-decoder Nussinov decodes one level: -T auto / -G auto with " + std::to_string(o.auto_levels) + " entries needs --fold-decoder Levels");
+    for (float g : o.auto_gammas) o.auto_cand.push_back(1.0 / (1.0 + g));  // the conversion of -G below
+    for (size_t c = 1; c < o.auto_cand.size(); ++c)
+      if (!(o.auto_cand[c] < o.auto_cand[c - 1])) throw std::string("--auto-gammas: two weights give the same threshold");
+  }
   if (o.seed_structure) {  // the structure is the seed's: nothing is decoded, so nothing sets a decoder's threshold
     if (o.seed.empty()) throw std::string("--seed-structure needs --seed");
     if (o.bp_update1) throw std::string("--seed-structure: nothing is decoded; --bp-update1 cannot be combined with --seed-structure");
@@ -647,7 +716,8 @@ Options parse(int argc, char** argv) {
       o.fold_th1 = o.fold_th;
     }
   }
-  if (o.fold_decoder == "Levels") {  // one level per entry of -T / -G
+  if (o.auto_levels) o.fold_th1 = o.fold_th;  // not read: every decode chooses among auto_cand
+  if (o.fold_decoder == "Levels" && !o.auto_levels) {  // one level per entry of -T / -G
     if (o.bp_update1)
       throw std::string("--fold-decoder Levels: --bp-update1 is not built for it (the reference folds again per level, under each level's constraint)");
     if (o.seed_structure) throw std::string("--seed-structure: nothing is decoded; --fold-decoder Levels cannot be combined with --seed-structure");
@@ -1268,7 +1338,7 @@ struct FamilyOut {
   unsigned wanted = 0;
   std::ostringstream text;
   std::ostream* os = &text;  // &text, or &std::cout
-  std::string sto, cov, phy, phy_table;
+  std::string sto, cov, phy, phy_table, auto_table;
   IdentityText idt;
   CompareText cmp;
   FamilyOut() {}
@@ -1300,6 +1370,11 @@ void write_outputs(const Options& o, unsigned wanted, const std::vector<FamilyOu
   if (wanted & kPhy) write_tables("--phylogeny", o.phylogeny, phy, headers);
   if ((wanted & kPhy) && !o.phylogeny_support.empty()) write_tables("--phylogeny-support", o.phylogeny_support, phy_table, headers);
   if (wanted & kCmp) write_compare(o, cmp, headers);
+  if (!o.auto_table.empty()) {
+    std::vector<std::string> tables;
+    for (const FamilyOut& r : recs) tables.push_back(r.auto_table);
+    write_tables("--fold-auto-table", o.auto_table, tables, headers);
+  }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1744,9 +1819,42 @@ VU concat(const std::vector<VU>& parts) {
 // Every decode of the command line goes through here: many alignments, laid out as the library takes them, at the decoder
 // of --fold-decoder.  Nussinov: dafs_hip_consensus_structures at the first entry of -T / -G; level stays empty.  Levels:
 // dafs_hip_consensus_structures_levels with one level per entry; level gets a byte per column.
+// -T auto / -G auto: dafs_hip_consensus_structures_auto over the candidates of --auto-gammas, one level
+// under Nussinov and up to one per entry under Levels; autos (optional) gets what every alignment's choice kept.
+struct AutoInfo {
+  uint32_t columns = 0;
+  uint64_t sum_p = 0;
+  std::vector<uint32_t> chosen, npairs, cand_pairs;  // [K], [K], [K * C]
+  std::vector<uint64_t> tp, cand_tp;                 // [K], [K * C]
+};
+
 void decode_alignments(dafs_hip_ctx* ctx, const Options& o, const std::vector<uint32_t>& n_rows, const std::vector<uint32_t>& len,
-                       const std::vector<uint32_t>& seq, const std::vector<uint8_t>& mask, VU& ss, VL& level) {
+                       const std::vector<uint32_t>& seq, const std::vector<uint8_t>& mask, VU& ss, VL& level, std::vector<AutoInfo>* autos = nullptr) {
   level.clear();
+  if (o.auto_levels) {
+    const size_t n = n_rows.size(), K = o.auto_levels, C = o.auto_cand.size();
+    std::vector<uint32_t> chosen(n * K + 1), np(n * K + 1), cnp(n * K * C + 1);
+    std::vector<uint64_t> sum(n + 1), tp(n * K + 1), ctp(n * K * C + 1);
+    VL lv(ss.size(), 0xFF);
+    check(dafs_hip_consensus_structures_auto(ctx, (uint32_t)n, n_rows.data(), len.data(), seq.data(), mask.data(), (uint32_t)K, (uint32_t)C,
+                                             o.auto_cand.data(), ss.data(), lv.data(), nullptr, chosen.data(), sum.data(), tp.data(), np.data(),
+                                             ctp.data(), cnp.data()));
+    if (o.fold_decoder == "Levels") level.swap(lv);
+    if (autos) {
+      autos->assign(n, AutoInfo());
+      for (size_t a = 0; a < n; ++a) {
+        AutoInfo& au = (*autos)[a];
+        au.columns = len[a];
+        au.sum_p = sum[a];
+        au.chosen.assign(chosen.begin() + a * K, chosen.begin() + (a + 1) * K);
+        au.npairs.assign(np.begin() + a * K, np.begin() + (a + 1) * K);
+        au.tp.assign(tp.begin() + a * K, tp.begin() + (a + 1) * K);
+        au.cand_pairs.assign(cnp.begin() + a * K * C, cnp.begin() + (a + 1) * K * C);
+        au.cand_tp.assign(ctp.begin() + a * K * C, ctp.begin() + (a + 1) * K * C);
+      }
+    }
+    return;
+  }
   if (o.fold_decoder != "Levels") {
     check(dafs_hip_consensus_structures(ctx, (uint32_t)n_rows.size(), n_rows.data(), len.data(), seq.data(), mask.data(), o.fold_th1[0], ss.data(), nullptr));
     return;
@@ -1758,12 +1866,14 @@ void decode_alignments(dafs_hip_ctx* ctx, const Options& o, const std::vector<ui
 
 // The first decode of many final alignments in one library call: ss[k] of *alns[k], decoded over the rows in the order each
 // holds them; level[k]: its levels, or empty (decode_alignments)
-void consensus_structures(dafs_hip_ctx* ctx, const Options& o, const std::vector<const ALN*>& alns, std::vector<VU>& ss, std::vector<VL>& level) {
+// autos (optional): with -T auto / -G auto what every alignment's choice kept, else left empty
+void consensus_structures(dafs_hip_ctx* ctx, const Options& o, const std::vector<const ALN*>& alns, std::vector<VU>& ss, std::vector<VL>& level,
+                          std::vector<AutoInfo>* autos = nullptr) {
   const Packed p = pack(alns);
   const std::vector<size_t> at = starts_of(p.len);
   VU all(at.back() ? at.back() : 1);
   VL lv;
-  decode_alignments(ctx, o, p.n_rows, p.len, p.seq, p.mask, all, lv);
+  decode_alignments(ctx, o, p.n_rows, p.len, p.seq, p.mask, all, lv, autos);
   ss.clear();
   level.assign(alns.size(), VL());
   for (size_t k = 0; k < alns.size(); ++k) {
@@ -1809,7 +1919,7 @@ std::vector<VU> row_structures(dafs_hip_ctx* ctx, const Options& o, const std::v
 // The common secondary structure of a final alignment (:1857-1871; no RNAalifold term here), decoded over the rows in the
 // order root holds them.  ss0: the first decode of the alignment where the caller has it already (consensus_structures over
 // many alignments); without it the alignment is decoded here, as a batch of one, and level gets its levels (or stays empty).
-VU final_structure(dafs_hip_ctx* ctx, const Options& o, const ALN& root, const VU* ss0, VL* level = nullptr) {
+VU final_structure(dafs_hip_ctx* ctx, const Options& o, const ALN& root, const VU* ss0, VL* level = nullptr, AutoInfo* au = nullptr) {
   std::vector<uint32_t> rs;
   std::vector<uint8_t> rm;
   flatten(root, rs, rm);
@@ -1819,9 +1929,11 @@ VU final_structure(dafs_hip_ctx* ctx, const Options& o, const ALN& root, const V
   else {
     std::vector<VU> one;
     std::vector<VL> one_level;
-    consensus_structures(ctx, o, {&root}, one, one_level);
+    std::vector<AutoInfo> one_auto;
+    consensus_structures(ctx, o, {&root}, one, one_level, &one_auto);
     ss = one[0];
     if (level) *level = one_level[0];
+    if (au && !one_auto.empty()) *au = one_auto[0];
   }
   if (o.bp_update1) {  // :1863-1869: re-estimate under the decoded structure, decode again (SparseNussinov::decode(p, ss, str))
     std::vector<float> p((size_t)L * L);
@@ -1874,6 +1986,54 @@ std::vector<std::string> row_texts(const std::vector<Fasta>& fa, const ALN& aln)
   return rows;
 }
 
+// 2 T / (n 2^30 + S) for display; 0 for a zero denominator
+double pseudo_f(uint64_t t, uint64_t n, uint64_t S) {
+  const double den = (double)n * 1073741824.0 + (double)S;
+  return den > 0.0 ? 2.0 * (double)t / den : 0.0;
+}
+
+// --fold-auto-table: the header line and one line per decoded (level, candidate) of one alignment
+std::string auto_table_of(const Options& o, const AutoInfo& au, const std::string& name) {
+  const size_t K = au.chosen.size(), C = o.auto_cand.size();
+  char buf[256];
+  snprintf(buf, sizeof buf, "# alignment %s columns %u sum_p %llu\n", name.c_str(), au.columns, (unsigned long long)au.sum_p);
+  std::string out = buf;
+  uint64_t t_low = 0, n_low = 0;
+  for (size_t k = 0; k < K; ++k) {
+    for (size_t c = 0; c < C; ++c) {
+      const uint64_t t = au.cand_tp[k * C + c], n = au.cand_pairs[k * C + c];
+      snprintf(buf, sizeof buf, "%zu\t%g\t%g\t%llu\t%llu\t%.6f\t%d\n", k, (double)o.auto_gammas[c], (double)o.auto_cand[c], (unsigned long long)n,
+               (unsigned long long)t, pseudo_f(t_low + t, n_low + n, au.sum_p), au.chosen[k] == c ? 1 : 0);
+      out += buf;
+    }
+    if (au.chosen[k] == DAFS_HIP_NONE) break;  // the higher levels were not decoded
+    t_low += au.tp[k];
+    n_low += au.npairs[k];
+  }
+  return out;
+}
+
+// the "#=GF CC SS_cons auto ..." line of a block, behind its other #=GF lines
+std::string with_auto_line(const Options& o, const AutoInfo& au, const std::string& block) {
+  std::string line = "#=GF CC SS_cons auto thresholds ";
+  uint64_t t = 0, n = 0;
+  bool any = false;
+  char buf[64];
+  for (size_t k = 0; k < au.chosen.size() && au.chosen[k] != DAFS_HIP_NONE; ++k) {
+    snprintf(buf, sizeof buf, "%s%g", any ? "," : "", (double)o.auto_cand[au.chosen[k]]);
+    line += buf;
+    any = true;
+    t += au.tp[k];
+    n += au.npairs[k];
+  }
+  if (!any) line += "none";
+  snprintf(buf, sizeof buf, " f %.6f\n", pseudo_f(t, n, au.sum_p));
+  line += buf;
+  size_t at = block.find('\n') + 1;  // behind "# STOCKHOLM 1.0"
+  while (block.compare(at, 5, "#=GF ") == 0) at = block.find('\n', at) + 1;
+  return block.substr(0, at) + line + block.substr(at);
+}
+
 // The output of a final alignment with its final structure ss_final (:1876-1879, :1584-1601) on *out.os: ">SS_cons", the
 // brackets, then the rows sorted by sequence index.  fa: the context's sequences, the family's from index first on, one per
 // row.  What out.wanted asks for goes into out: the family's Stockholm block from rl (reliabilities, made while root held its
@@ -1882,7 +2042,10 @@ std::vector<std::string> row_texts(const std::vector<Fasta>& fa, const ALN& aln)
 // covariation table, whose cov_SS_cons line joins the block; the identity tables, whose weights join the block; the comparison.
 void finish_alignment(dafs_hip_ctx* ctx, const Options& o, const std::vector<Fasta>& fa, ALN& root, uint32_t first, FamilyOut& out,
                       const std::string* tree_line, const std::vector<uint8_t>* rf, const VU& ss_final, const Reliability& rl,
-                      const std::vector<VU>* row_ss, const VL* level = nullptr, const std::vector<VL>* row_level = nullptr) {
+                      const std::vector<VU>* row_ss, const VL* level = nullptr, const std::vector<VL>* row_level = nullptr,
+                      const AutoInfo* au = nullptr) {
+  // au: with -T auto / -G auto what the alignment's choice kept (--fold-auto-table, the block's "#=GF CC SS_cons auto" line)
+  if (au && au->chosen.empty()) au = nullptr;
   // level, row_level: the levels of ss_final and of the rows' structures under --fold-decoder Levels (null or empty: one kind of bracket)
   const uint32_t L = (uint32_t)root[0].second.size();
   std::vector<char> str(L + 1);
@@ -1900,12 +2063,13 @@ void finish_alignment(dafs_hip_ctx* ctx, const Options& o, const std::vector<Fas
   std::string cov_chars;
   if (out.wanted & kCov) covariation_of(ctx, o, rows, ss_final, out.cov, cov_chars);
   std::vector<std::string> names;  // the printed rows' Stockholm names
-  if (out.wanted & (kSto | kIdt | kCmp | kPhy)) {
+  if ((out.wanted & (kSto | kIdt | kCmp | kPhy)) || (au && !o.auto_table.empty())) {
     std::vector<std::string> headers;
     for (size_t i = 0; i < root.size(); ++i) headers.push_back(fa[first + i].name());
     const std::vector<std::string> all_names = stockholm_names(headers);
     for (const auto& row : root) names.push_back(all_names[row.first - first]);
   }
+  if (au && !o.auto_table.empty()) out.auto_table = auto_table_of(o, *au, names[0]);
   if (out.wanted & kIdt) identity_of(ctx, names, rows, !o.identity_matrix.empty(), out.idt);
   if (out.wanted & kPhy) phylogeny_of(ctx, o, names, rows, out.phy, out.phy_table);
   if (out.wanted & kCmp) compare_of(ctx, o, names, rows, &ss_final, nullptr, nullptr, out.cmp);
@@ -1929,6 +2093,7 @@ void finish_alignment(dafs_hip_ctx* ctx, const Options& o, const std::vector<Fas
                                               rf ? rf->data() : nullptr, (out.wanted & kCov) ? cov_chars.c_str() : nullptr,
                                               row_ss ? c_strs(rss).data() : nullptr, &text));
     out.sto = take(text);
+    if (au) out.sto = with_auto_line(o, *au, out.sto);
     if (out.wanted & kIdt) {  // --identity: the sequence weights as #=GS WT lines
       check_text(dafs_host_stockholm_weights(out.sto.c_str(), (uint32_t)names.size(), c_strs(names).data(), out.idt.weight.data(), &text));
       out.sto = take(text);
@@ -2093,7 +2258,8 @@ int align_group(dafs_hip_ctx* ctx, const Options& o, Ranks& rk, int align_model,
   for (uint f = 0; f < F; ++f) roots.push_back(&aln[tbase[f + 1] - 1]);
   std::vector<VU> ss0;
   std::vector<VL> level0, row_level;
-  consensus_structures(ctx, o, roots, ss0, level0);
+  std::vector<AutoInfo> autos;
+  consensus_structures(ctx, o, roots, ss0, level0, &autos);
   std::vector<VU> row_ss;
   if (o.row_structures && sto) row_ss = row_structures(ctx, o, fa, row_level);
   // the annotation of all of them in one call, once every structure is final (-r and --bp-update1 are behind it)
@@ -2108,7 +2274,7 @@ int align_group(dafs_hip_ctx* ctx, const Options& o, Ranks& rk, int align_model,
       tree_line = tl.str();
     }
     finish_alignment(ctx, o, fa, aln[tbase[f + 1] - 1], first[f], *out[f], &tree_line, nullptr, ss0[f], rl[f], row_ss.empty() ? nullptr : &row_ss,
-                     &level0[f], &row_level);
+                     &level0[f], &row_level, autos.empty() ? nullptr : &autos[f]);
   }
   return 0;
 }
@@ -2181,11 +2347,12 @@ int run_add(const Options& o, int align_model) {
   VU carried;  // --seed-structure: nothing is decoded
   if (o.seed_structure) carried = carry_structure(sd.ss, pl.seed_col, pl.width);
   VL level;
-  const VU ss = final_structure(ctx, o, root, o.seed_structure ? &carried : nullptr, &level);
+  AutoInfo au;
+  const VU ss = final_structure(ctx, o, root, o.seed_structure ? &carried : nullptr, &level, &au);
   if (o.seed_structure) level = carry_levels(sd.level, pl.seed_col, pl.width);
   std::vector<Reliability> rl(1);
   if (recs[0].wanted & kSto) reliabilities(ctx, fa, {&root}, {ss}, false, rl);
-  finish_alignment(ctx, o, fa, root, 0, recs[0], nullptr, &pl.rf, ss, rl[0], o.row_structures ? &row_ss : nullptr, &level, &row_level);
+  finish_alignment(ctx, o, fa, root, 0, recs[0], nullptr, &pl.rf, ss, rl[0], o.row_structures ? &row_ss : nullptr, &level, &row_level, &au);
   std::cout.flush();
   write_outputs(o, recs[0].wanted, recs, nullptr);
   return 0;
@@ -2299,8 +2466,9 @@ int run_add_each(const Options& o, int align_model) {
     for (const ALN& a : roots) ptrs.push_back(&a);
     std::vector<VU> ss;
     std::vector<VL> level(nf), row_level;
+    std::vector<AutoInfo> autos;
     if (!o.seed_structure) {
-      consensus_structures(ctx, o, ptrs, ss, level);
+      consensus_structures(ctx, o, ptrs, ss, level, &autos);
     } else {  // nothing is decoded: the seed's structure in every family's merged columns, and each row's support of it
       for (uint32_t f = 0; f < nf; ++f) ss.push_back(carry_structure(sd.ss, pl[f].seed_col, pl[f].width));
       for (uint32_t f = 0; f < nf; ++f) level[f] = carry_levels(sd.level, pl[f].seed_col, pl[f].width);
@@ -2325,7 +2493,7 @@ int run_add_each(const Options& o, int align_model) {
     }
     for (uint32_t f = 0; f < nf; ++f) {
       finish_alignment(ctx, o, fa, roots[f], f * n, recs[j0 + f], nullptr, &pl[f].rf, ss[f], rl[f], o.row_structures ? &row_ss : nullptr,
-                       &level[f], &row_level);
+                       &level[f], &row_level, autos.empty() ? nullptr : &autos[f]);
       print_block(headers[j0 + f], recs[j0 + f]);
       if (o.seed_nearest && matched[j0 + f]) {  // the printed rows (finish_alignment sorted them): the m seed rows, then the new one
         const std::vector<std::string> rows = row_texts(fa, roots[f]);

@@ -1364,6 +1364,15 @@ extern "C" uint64_t dafs_host_structure_levels_bytes(uint32_t n_rows, uint32_t l
   return dafs_host_structure_bytes(n_rows, len) + 12 * (uint64_t)len + 8 * 256 + 512;
 }
 
+// The same alignment inside dafs_hip_consensus_structures_auto with ncand candidates.  On top, per
+// candidate: its structure (4 bytes a column and one entry more), its score, its decoder descriptor (72 bytes) and its row
+// of the table at four levels (48), under 160 bytes together; the alignment's descriptor, S, the running sums, and the
+// chosen candidates, T and n of four levels (under 300 bytes); the 256-byte alignment of its one more array and of a
+// chunk's nine more shared ones.
+extern "C" uint64_t dafs_host_structure_auto_bytes(uint32_t n_rows, uint32_t len, uint32_t ncand) {
+  return dafs_host_structure_levels_bytes(n_rows, len) + (uint64_t)ncand * (4 * (uint64_t)len + 160) + 12 * 256 + 512;
+}
+
 // per chunk of dafs_hip_consensus_structures.  A choice, not a limit: 2 GiB hold some 3 500 pair alignments of 170 columns,
 // a dozen times what the device keeps resident at once, and the buffer stays with the context.
 extern "C" uint64_t dafs_host_structures_batch_bytes(void) { return 2ull << 30; }

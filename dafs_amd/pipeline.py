@@ -63,11 +63,25 @@ def decoder_option(decoder, th_s, th_s1, bp_update1=False, seed_ss=None, who="pi
     Returns what the driver then carries as th_s1: for "Nussinov" th_s1 itself, or its first entry when it is a sequence;
     for "Levels" a LevelThresholds of every entry (of th_s1, else th_s, when a scalar).  Refused: an unknown decoder, more
     than capi.MAX_LEVELS thresholds, a threshold of a higher level that is not positive, and "Levels" with bp_update1 or with
-    a seed structure."""
+    a seed structure.  th_s1 a capi.AutoThresholds: the thresholds are chosen by pseudo-expected accuracy
+    and the object is carried as it is; refused with bp_update1 (what the second decode would mean is undecided), with a seed
+    structure (nothing is decoded), with more than one level under "Nussinov", and as th_s, the threshold inside the loop."""
     if isinstance(th_s1, LevelThresholds):
         return th_s1
     if decoder not in DECODERS:
         raise ValueError("%s: unknown decoder %r (one of %s)" % (who, decoder, ", ".join(DECODERS)))
+    if isinstance(th_s, capi.AutoThresholds):
+        raise ValueError("%s: th_s, the threshold inside the dual-decomposition loop, cannot be chosen automatically; "
+                         "th_s1 can" % who)
+    if isinstance(th_s1, capi.AutoThresholds):
+        if bp_update1:
+            raise ValueError("%s: automatic thresholds cannot be combined with bp_update1" % who)
+        if seed_ss is not None:
+            raise ValueError("%s: with seed_ss nothing is decoded: automatic thresholds cannot be combined with it" % who)
+        if decoder == "Nussinov" and th_s1.levels != 1:
+            raise ValueError("%s: decoder \"Nussinov\" decodes one level; automatic thresholds of %d levels need decoder "
+                             "\"Levels\"" % (who, th_s1.levels))
+        return th_s1
     ths = None
     if th_s1 is not None and np.ndim(th_s1) != 0:
         ths = [float(x) for x in th_s1]
@@ -88,11 +102,19 @@ def decoder_option(decoder, th_s, th_s1, bp_update1=False, seed_ss=None, who="pi
 
 
 def _decode(ctx, alns, th1):
-    """The first decode of many final alignments in one call: per alignment (ss, level, scores); level and scores are None
-    under the plain decoder (th1 a number), the level array and the per-level scores under th1 a LevelThresholds"""
+    """The first decode of many final alignments in one call: per alignment (ss, level, scores, auto); level and scores are
+    None under the plain decoder (th1 a number), the level array and the per-level scores under th1 a LevelThresholds or a
+    capi.AutoThresholds; auto is the capi.AutoChoice of the latter, else None"""
+    if isinstance(th1, capi.AutoThresholds):
+        return [(ss, level, scores, auto) for scores, ss, level, auto in ctx.consensus_structures(alns, th1)]
     if isinstance(th1, LevelThresholds):
-        return [(ss, level, scores) for scores, ss, level in ctx.consensus_structures(alns, th1)]
-    return [(ss, None, None) for _, ss in ctx.consensus_structures(alns, th1)]
+        return [(ss, level, scores, None) for scores, ss, level in ctx.consensus_structures(alns, th1)]
+    return [(ss, None, None, None) for _, ss in ctx.consensus_structures(alns, th1)]
+
+
+def _by_level(th):
+    """the decode at th returns levels"""
+    return isinstance(th, (LevelThresholds, capi.AutoThresholds))
 
 
 def run(names, seqs, ctx=None, bp=None, w=4.0, eta0=0.5, t_max=600, w_pct_a=0.25, w_pct_s=0.25, th_a=0.01,
@@ -117,7 +139,11 @@ def run(names, seqs, ctx=None, bp=None, w=4.0, eta0=0.5, t_max=600, w_pct_a=0.25
     thresholds th_s1 (a sequence, one per level; a scalar or None: one level) and may hold pseudoknots.  .ss is then the
     union of the levels, .ss_level the level of the pair at each of its columns (0xFF at unpaired ones), .ss_scores the
     per-level scores, and .ss_str, the Stockholm SS_cons and the per-row structures print "()", "[]", "{}", "<>" for levels
-    0..3.  With "Nussinov" only the first entry of a sequence th_s1 is used."""
+    0..3.  With "Nussinov" only the first entry of a sequence th_s1 is used.  th_s1 a capi.AutoThresholds (DESIGN.md section
+    27): every level's threshold is chosen from its candidates by pseudo-expected accuracy, up to its .levels levels under
+    "Levels" and one under "Nussinov"; the result gets .ss_level and .ss_scores as under "Levels" and .ss_auto, the
+    capi.AutoChoice (chosen, thresholds, sum_p, tp, npairs, the candidates' table, f); with row_structures every row chooses
+    its own thresholds (.row_ss_auto)."""
     import time
     th_s1 = decoder_option(decoder, th_s, th_s1, bp_update1, None, "pipeline.run")
     phylogeny = phylogeny_option(phylogeny, phylogeny_bootstrap, phylogeny_seed)
@@ -335,18 +361,18 @@ def _phase2_forest(ctx, own, fams, t, w, eta0, t_max, th_a, th_s, th_s1, force_i
     th1 = th_s if th_s1 is None else th_s1
     roots = [aln[(f, 2 * len(fm["seqs"]) - 2)] for f, fm in enumerate(fams)]
     decoded = _decode(ctx, roots, th1)
-    rows_ss = rows_level = [None] * nf
+    rows_ss = rows_level = rows_auto = [None] * nf
     if row_structures:
         lens = {fm["first"] + i: len(sq) for fm in fams for i, sq in enumerate(fm["seqs"])}
-        rows_ss, rows_level = _row_structures(ctx, [sidx for sidx, _ in roots], lens, th1)
-    finals = [_final_structure(ctx, sidx, mask, th1, bp_update1, ss) for (sidx, mask), (ss, _, _) in zip(roots, decoded)]
+        rows_ss, rows_level, rows_auto = _row_structures(ctx, [sidx for sidx, _ in roots], lens, th1)
+    finals = [_final_structure(ctx, sidx, mask, th1, bp_update1, ss) for (sidx, mask), (ss, *_) in zip(roots, decoded)]
     rls = ctx.alignment_reliabilities(roots, finals) if reliability else [None] * nf  # once every structure is final
     for f, (fm, res) in enumerate(zip(fams, results)):
         res.levels = levels
         res.rounds = rounds
         sidx, mask = roots[f]
         _final(ctx, res, fm["names"], fm["seqs"], fm["first"], sidx, mask, finals[f], rls[f], res.tree_line, None, covariation, rows_ss[f],
-               identity, compare, phylogeny, decoded[f][1:], rows_level[f])
+               identity, compare, phylogeny, decoded[f][1:], rows_level[f], rows_auto[f])
     t.append(time.perf_counter())
     # fold_launch: the folding is only started there; its kernels overlap `pair` and the first half of `pct_fold_tree`,
     # which also holds the wait for them
@@ -460,17 +486,20 @@ def alignment_phylogeny(ctx, row_names, rows, model="jc"):
 def _row_structures(ctx, sidx_per_alignment, lens, th):
     """Per alignment (its rows' global sequence indices) and per printed row (ascending index) the structure of that row's
     sequence alone from the context's current base-pairing store: one Context.consensus_structures call over all of them.
-    lens: global sequence index -> length.  Returns (structures, levels), each a list per alignment of one array per row; the
-    levels of an alignment are None under the plain decoder."""
+    lens: global sequence index -> length.  Returns (structures, levels, choices), each a list per alignment of one entry per
+    row; the levels of an alignment are None under the plain decoder, and the choices (capi.AutoChoice: every row chooses its
+    own thresholds) unless th is a capi.AutoThresholds."""
     printed = [np.sort(np.asarray(sidx, np.uint32), kind="stable") for sidx in sidx_per_alignment]
     flat = [int(x) for rows in printed for x in rows]
     got = _decode(ctx, [(np.array([x], np.uint32), np.ones((1, lens[x]), np.uint8)) for x in flat], th)
-    out, levels, k = [], [], 0
+    out, levels, autos, k = [], [], [], 0
     for rows in printed:
-        out.append([ss for ss, _, _ in got[k:k + len(rows)]])
-        levels.append([level for _, level, _ in got[k:k + len(rows)]] if isinstance(th, LevelThresholds) else None)
+        mine = got[k:k + len(rows)]
+        out.append([ss for ss, *_ in mine])
+        levels.append([level for _, level, _, _ in mine] if _by_level(th) else None)
+        autos.append([auto for *_, auto in mine] if isinstance(th, capi.AutoThresholds) else None)
         k += len(rows)
-    return out, levels
+    return out, levels, autos
 
 
 def _final_structure(ctx, sidx, mask, th1, bp_update1, ss):
@@ -620,7 +649,7 @@ def compare_result(ctx, reference, row_names, rows, ss, use_test=None, pp=None):
 
 
 def _final(ctx, res, names, seqs, first, sidx, mask, ss, rl, tree_line, rf=None, covariation=None, row_ss=None, identity=False, compare=None,
-           phylogeny=False, levels=None, row_level=None):
+           phylogeny=False, levels=None, row_level=None, row_auto=None):
     """The output of a final alignment (sidx: global sequence index per row, mask) with its common structure ss
     (_final_structure), into res: .ss, .ss_str, .rows, .output and, with rl, .reliability and .stockholm.  names / seqs: the
     family's, its first sequence at global index `first`.  rl: the alignment's dict of Context.alignment_reliabilities for
@@ -633,15 +662,18 @@ def _final(ctx, res, names, seqs, first, sidx, mask, ss, rl, tree_line, rf=None,
     compare: a reference (run's compare) -> .compare, the printed rows and ss against it (compare_result), and .row_names.
     phylogeny: a model -> .phylogeny (alignment_phylogeny of the printed rows), and .row_names.  levels: (level, scores) of a
     structure decoded level by level (_decode), or None / (None, None) -> .ss_level, .ss_scores, and .ss_str with the bracket
-    kind of each pair's level; row_level: the same per printed row for row_ss."""
+    kind of each pair's level; row_level: the same per printed row for row_ss.  levels may carry a third entry, the
+    capi.AutoChoice of thresholds chosen automatically -> .ss_auto; row_auto: per printed row -> .row_ss_auto."""
     phylogeny = phylogeny_model(phylogeny)
     res.ss = ss
     res.root = (sidx, mask)  # the alignment as it was decoded: the rows in this order (the average depends on it)
     if levels is None or levels[0] is None:
         res.ss_str = capi.make_brackets(ss)
     else:
-        res.ss_level, res.ss_scores = levels
+        res.ss_level, res.ss_scores = levels[:2]
         res.ss_str = capi.make_brackets_levels(ss, res.ss_level)
+        if len(levels) > 2 and levels[2] is not None:
+            res.ss_auto = levels[2]
     order = np.argsort(sidx, kind="stable")  # std::sort(aln) :1876
     lines = ([] if tree_line is None else [tree_line]) + [">SS_cons", res.ss_str]
     res.rows = []
@@ -660,6 +692,8 @@ def _final(ctx, res, names, seqs, first, sidx, mask, ss, rl, tree_line, rf=None,
         else:
             res.row_ss_level = row_level
             res.row_ss_str = [stockholm.row_ss_str(row, x, lv) for row, x, lv in zip(res.rows, row_ss, row_level)]
+        if row_auto is not None:
+            res.row_ss_auto = row_auto
     cov_chars = None
     if covariation:
         cv = _covariation(ctx, res.rows, ss, covariation)
@@ -836,16 +870,16 @@ def add(seed_names, seed_rows, names, seqs, ctx=None, w=4.0, eta0=0.5, t_max=600
             levels = (carry_structure(seed_ss, seed_col, width, seed_level)[1], None)
         if ss_m is not None:
             res.support = _printed_support(ctx.structure_support([(sidx, rows_mask)], [ss_m])[0], sidx)
-        elif isinstance(th1, LevelThresholds):  # the batched call with one alignment
+        elif _by_level(th1):  # the batched call with one alignment
             ss_m, *levels = _decode(ctx, [(sidx, rows_mask)], th1)[0]
         else:
             ss_m = _final_structure(ctx, sidx, rows_mask, th1, bp_update1, ctx.consensus_structure(sidx, rows_mask, th1)[1])
         rl = ctx.alignment_reliability(sidx, rows_mask, ss_m) if reliability else None
-        row_ss, row_level = None, None
+        row_ss, row_level, row_auto = None, None, None
         if row_structures:
-            row_ss, row_level = (x[0] for x in _row_structures(ctx, [sidx], dict(enumerate(map(len, all_seqs))), th1))
+            row_ss, row_level, row_auto = (x[0] for x in _row_structures(ctx, [sidx], dict(enumerate(map(len, all_seqs))), th1))
         _final(ctx, res, all_names, all_seqs, 0, sidx, rows_mask, ss_m, rl, None, rf, covariation, row_ss, identity, compare, phylogeny,
-               levels, row_level)
+               levels, row_level, row_auto)
         t.append(time.perf_counter())
         res.seconds = dict(phase1=t[3] - t[0], nodes=t[4] - t[3], final=t[5] - t[4], total=t[5] - t[0])
     finally:
@@ -1366,13 +1400,13 @@ def add_each(seed_names, seed_rows, names, seqs, ctx=None, max_bytes=None, merge
                 decoded = [(carry_structure(seed_ss, np.flatnonzero(rf).astype(np.uint32), len(rf)), None, None) for rf in rfs]
                 if seed_level is not None:  # the levels travel with the seed's columns
                     decoded = [(ss, carry_structure(seed_ss, np.flatnonzero(rf).astype(np.uint32), len(rf), seed_level)[1], None)
-                               for (ss, _, _), rf in zip(decoded, rfs)]
+                               for (ss, *_), rf in zip(decoded, rfs)]
                 support = ctx.structure_support(alns, [ss for ss, _, _ in decoded])
-            rows_ss = rows_level = [None] * len(chunk)
+            rows_ss = rows_level = rows_auto = [None] * len(chunk)
             if o["row_structures"]:
                 lens = {f * n + i: ln for f, j in enumerate(chunk) for i, ln in enumerate(seed_lens + [len(seqs[j])])}
-                rows_ss, rows_level = _row_structures(ctx, [sidx for sidx, _ in alns], lens, th1)
-            finals = [_final_structure(ctx, sidx, mask, th1, o["bp_update1"], ss) for (sidx, mask), (ss, _, _) in zip(alns, decoded)]
+                rows_ss, rows_level, rows_auto = _row_structures(ctx, [sidx for sidx, _ in alns], lens, th1)
+            finals = [_final_structure(ctx, sidx, mask, th1, o["bp_update1"], ss) for (sidx, mask), (ss, *_) in zip(alns, decoded)]
             # the annotation, once every structure is final: all rows of every family, or for the merged alignment alone the new
             # row of every family (the first), which reads the listed pairs only
             rls = [None] * len(chunk)
@@ -1397,7 +1431,7 @@ def add_each(seed_names, seed_rows, names, seqs, ctx=None, max_bytes=None, merge
                     for key in out.support:  # the new sequence is the first row of its alignment
                         out.support[key][j] = support[f][key][0]
                 _final(ctx, res, seed_names + [names[j]], seed_seqs + [seqs[j]], f * n, alns[f][0], alns[f][1], finals[f], rls[f], None,
-                       rfs[f], covariation, rows_ss[f], o["identity"], levels=decoded[f][1:], row_level=rows_level[f])  # no tree per placement: refused above
+                       rfs[f], covariation, rows_ss[f], o["identity"], levels=decoded[f][1:], row_level=rows_level[f], row_auto=rows_auto[f])  # no tree per placement: refused above
                 out.results[j] = res
                 out.score[j] = oj["score"]
                 out.iterations[j] = oj["iterations"]
@@ -1437,8 +1471,9 @@ def fold_each(names, seqs, th=0.2, ctx=None, decoder="Nussinov"):
     structure of every sequence's own base-pairing rows at threshold th, all in one Context.consensus_structures call.
     Returns one Result per sequence with .name, .ss (uint32 per residue, NONE for unpaired), .ss_str and .score.
     decoder "Levels" (as in run(); th may then be a sequence, one threshold per level): also .ss_level, and .score holds the
-    per-level scores."""
-    th = decoder_option(decoder, th, th, False, None, "pipeline.fold_each")
+    per-level scores.  th a capi.AutoThresholds: every sequence chooses its own thresholds; as with
+    "Levels", and also .ss_auto, its capi.AutoChoice."""
+    th = decoder_option(decoder, 0.2 if isinstance(th, capi.AutoThresholds) else th, th, False, None, "pipeline.fold_each")
     names, seqs = list(names), list(seqs)
     if not seqs or len(names) != len(seqs):
         raise ValueError("pipeline.fold_each: at least one sequence and one name per sequence")
@@ -1455,9 +1490,11 @@ def fold_each(names, seqs, th=0.2, ctx=None, decoder="Nussinov"):
     out = []
     for nm, one in zip(names, got):
         res = Result()
-        if isinstance(th, LevelThresholds):
-            res.score, res.ss, res.ss_level = one
+        if _by_level(th):
+            res.score, res.ss, res.ss_level = one[:3]
             res.name, res.ss_str = nm, capi.make_brackets_levels(res.ss, res.ss_level)
+            if isinstance(th, capi.AutoThresholds):
+                res.ss_auto = one[3]
         else:
             score, ss = one
             res.name, res.ss, res.ss_str, res.score = nm, ss, capi.make_brackets(ss), score

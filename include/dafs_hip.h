@@ -609,6 +609,9 @@ uint64_t dafs_host_structures_batch_bytes(void);
 /* The same estimate inside dafs_hip_consensus_structures_levels: the level's own structure, the column
  * keys, the level bytes, the per-level descriptors, flags and scores on top of dafs_host_structure_bytes. */
 uint64_t dafs_host_structure_levels_bytes(uint32_t n_rows, uint32_t len);
+/* The same inside dafs_hip_consensus_structures_auto with ncand candidates: on top of the levels'
+ * estimate, every candidate's structure, score and decoder descriptor, and the sums. */
+uint64_t dafs_host_structure_auto_bytes(uint32_t n_rows, uint32_t len, uint32_t ncand);
 /* The same two for dafs_hip_alignment_reliabilities. */
 uint64_t dafs_host_reliability_bytes(uint32_t n_rows, uint32_t len);
 uint64_t dafs_host_reliability_batch_bytes(void);
@@ -676,6 +679,12 @@ void dafs_hip_make_brackets_levels(uint32_t L, const uint32_t* ss, const uint8_t
 #define DAFS_HIP_MAX_LEVELS 4u
 int dafs_hip_nussinov_decode_levels(dafs_hip_ctx* ctx, uint32_t nlevels, const float* th, uint32_t L, const float* p, uint32_t* ss,
                                     uint8_t* level, float* score);
+/* The same with the thresholds chosen by pseudo-expected accuracy (DESIGN.md section 27;
+ * dafs_hip_consensus_structures_auto has the contract) from the candidates cand[ncand]. */
+#define DAFS_HIP_MAX_CANDIDATES 16u
+int dafs_hip_nussinov_decode_auto(dafs_hip_ctx* ctx, uint32_t nlevels, uint32_t ncand, const float* cand, uint32_t L, const float* p,
+                                  uint32_t* ss, uint8_t* level, float* score, uint32_t* chosen, uint64_t* sum_p, uint64_t* tp,
+                                  uint32_t* npairs, uint64_t* cand_tp, uint32_t* cand_pairs);
 
 /* ------------------------------------------------------------------------------------------
  * L1: fused guide-tree node solver.
@@ -780,6 +789,26 @@ int dafs_hip_consensus_structures(dafs_hip_ctx* ctx, uint32_t nalign, const uint
 int dafs_hip_consensus_structures_levels(dafs_hip_ctx* ctx, uint32_t nalign, const uint32_t* n_rows, const uint32_t* len,
                                          const uint32_t* seq, const uint8_t* mask, uint32_t nlevels, const float* th, uint32_t* ss,
                                          uint8_t* level, float* score);
+/* The same decode with every level's threshold chosen from cand[ncand] by pseudo-expected accuracy, as
+ * CentroidAlifold and IPknot choose theirs.  cand: 1 <= ncand <= DAFS_HIP_MAX_CANDIDATES thresholds, strictly decreasing, each
+ * inside (0, 1).  Every cell counts as the integer q(p) = (uint64_t)(fminf(fmaxf(p, 0), 1) * 2^30) and every sum is a sum of
+ * those in uint64, so no floating-point rounding takes part in a choice.  S is the sum of q over the cells i < j of the
+ * averaged matrix; a structure has T, the sum of q over its pairs, and n, their number, and its pseudo-expected F is
+ * 2 T / (n 2^30 + S).  (Ta, na) beats (Tb, nb) when Ta (nb 2^30 + S) > Tb (na 2^30 + S) in 128-bit integers.  Level k: every
+ * candidate is decoded on the level's masked matrix (the decoder, its ties and its score are those of the call above) and
+ * valued with the levels already kept added in; the first candidate in list order that no earlier one equals or beats is the
+ * best; the level is its structure when that beats the levels already kept alone, else the level is empty, and so is every
+ * higher one.  ss, level and score[nalign * nlevels] are those of dafs_hip_consensus_structures_levels at the thresholds
+ * cand[chosen[0 .. m - 1]] of the m kept levels (the scores of the others are 0; m = 0: all unpaired).  Per alignment, one
+ * after another, each may be NULL: chosen[nlevels] (the candidate's index, DAFS_HIP_NONE for an empty level), sum_p[1] (S),
+ * tp[nlevels] and npairs[nlevels] (T and n of each kept level alone, 0 for an empty one), and the whole table
+ * cand_tp / cand_pairs[nlevels * ncand] (level-major; 0 for the levels that were not decoded).  Checks and chunks as above
+ * (dafs_host_structure_auto_bytes is the estimate); DAFS_HIP_EINVAL, outputs untouched, also for nlevels outside
+ * 1..DAFS_HIP_MAX_LEVELS, ncand outside 1..DAFS_HIP_MAX_CANDIDATES and a list that is not as described. */
+int dafs_hip_consensus_structures_auto(dafs_hip_ctx* ctx, uint32_t nalign, const uint32_t* n_rows, const uint32_t* len, const uint32_t* seq,
+                                       const uint8_t* mask, uint32_t nlevels, uint32_t ncand, const float* cand, uint32_t* ss,
+                                       uint8_t* level, float* score, uint32_t* chosen, uint64_t* sum_p, uint64_t* tp, uint32_t* npairs,
+                                       uint64_t* cand_tp, uint32_t* cand_pairs);
 
 /* DAFS::update_basepairing_probability (src/dafs.cpp:609-712; options --bp-update and --bp-update1), without the RNAalifold
  * term: the sequences of the alignment (rows seq / mask as in dafs_node_input) are folded again with CONTRAfold under the
