@@ -506,6 +506,12 @@ struct pair_variant {
   bool optin[16];   // lds_optin_once flags
 };
 
+// The row pointers of a launch live in LDS: per workgroup 4 wavefronts x 64/G groups x (max_len1 + 1) words, at most
+// kPairRowptrLdsMax bytes.  The launches refuse more (DAFS_HIP_ETOOLONG) and pair_choose skips an instance that would
+// need more, so first sequences reach 959 residues at G = 16, 1919 at G = 32 and 3839 at G = 64.
+constexpr size_t kPairRowptrLdsMax = 60 * 1024;
+inline size_t pair_rowptr_lds(int G, uint64_t rp_cap) { return (size_t)(4 * (64 / G) * rp_cap * sizeof(uint32_t)); }
+
 // registers and static LDS from the code object, once per instance
 inline void pair_query(pair_variant& v) {
   if (v.vgprs != 0) return;
@@ -582,6 +588,7 @@ inline int pair_choose(pair_variant* vs, int nv, uint32_t ntasks, uint32_t max_l
     if ((uint64_t)v.G * v.W < (uint64_t)max_len2 + 1) continue;
     if (force_g && v.G != force_g) continue;
     if (force_w && v.W != force_w) continue;
+    if (pair_rowptr_lds(v.G, (uint64_t)max_len1 + 1) > kPairRowptrLdsMax) continue;  // the launch would refuse it
     pair_query(v);
     int occ = pair_occupancy(v.vgprs);
     if (cap_occ > 0 && occ > cap_occ) occ = cap_occ;

@@ -409,8 +409,8 @@ extern "C" int dafs_hipk_pairhmm3_launch(const dafs_pairhmm3_args* args, const d
   const uint64_t per_wave = (uint64_t)plan->slab_steps * plan->width * 64 * sizeof(float) * 2;  // two planes
   if (per_wave && plan->nwaves > plan->scratch_bytes / per_wave) return DAFS_HIP_EINVAL;
   const uint32_t rp_cap = plan->slab_steps - plan->group + 1;  // max_len1 + 1 row pointers
-  const size_t rp_lds = (size_t)4 * (64 / v->G) * rp_cap * sizeof(uint32_t);
-  if (rp_lds > 60 * 1024) return DAFS_HIP_ETOOLONG;
+  const size_t rp_lds = pair_rowptr_lds(v->G, rp_cap);
+  if (rp_lds > kPairRowptrLdsMax) return DAFS_HIP_ETOOLONG;
   // sweep 4's staging window behind the row pointers (pair_sweeps.h); above the default only where the row pointers force it
   size_t lds = 0;
   uint32_t emit_e = pair_emit_window(*v, rp_lds, &lds);

@@ -311,8 +311,8 @@ extern "C" int dafs_hipk_pairhmm5_launch(const dafs_pairhmm5_args* args, const d
   const uint64_t per_wave = (uint64_t)plan->slab_steps * plan->width * 64 * sizeof(float) * 5;
   if (per_wave && plan->nwaves > plan->scratch_bytes / per_wave) return DAFS_HIP_EINVAL;
   const uint32_t rp_cap = plan->slab_steps - plan->group + 1;
-  const size_t lds = (size_t)4 * (64 / v->G) * rp_cap * sizeof(uint32_t);
-  if (lds > 60 * 1024) return DAFS_HIP_ETOOLONG;
+  const size_t lds = pair_rowptr_lds(v->G, rp_cap);
+  if (lds > kPairRowptrLdsMax) return DAFS_HIP_ETOOLONG;
   dafs_pairhmm5_args a = *args;
   uint32_t steps = plan->slab_steps, cap = rp_cap;
   void* params[] = {&a, &steps, &cap};

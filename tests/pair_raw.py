@@ -17,7 +17,9 @@ pool_cap (the pool is allocated with `tail` more entries behind it) and what the
 The words behind plan.scratch_bytes (a tail of `scratch_tail` words, and whatever a larger launch of the same child
 used) are set to the canary before every launch, and the pool, the row pointers, pair_off, pair_nnz and sim are filled
 with it.  DAFS_HIP_FORCE_GROUP, DAFS_HIP_FORCE_WIDTH and DAFS_HIP_EMIT_WINDOW reach the library through the child's
-environment (run(env=...)).
+environment (run(env=...)), for every launch of the child, or per launch: spec(force=(group, width)) sets the first two
+around that launch's plan call and spec(window=positions) the third around its launch, and the child puts back what its
+environment held before (the library reads all three with getenv on every call).  One child can so run many instances.
 
 The child synchronises after every launch and stops at the first non-zero return code or HIP error: it starts nothing
 further and exits non-zero with the message."""
@@ -53,16 +55,19 @@ def nnz(oracle, seqs, tasks, th, model):
     return [len(want(oracle, seqs[x], seqs[y], th, model)[1]) for x, y in tasks]
 
 
-def spec(oracle, model, th, seqs, tasks, scratch, nwaves=None, pool_cap=None, plan_for=None):
+def spec(oracle, model, th, seqs, tasks, scratch, nwaves=None, pool_cap=None, plan_for=None, force=None, window=None):
     """One launch.  pool_cap defaults to what the oracle says the tasks need plus 64 entries; plan_for = (ntasks,
-    max_len1, max_len2) replaces the launch's own numbers in the plan call (two launches that must share a geometry)."""
+    max_len1, max_len2) replaces the launch's own numbers in the plan call (two launches that must share a geometry);
+    force = (group, width) and window = positions hold for this launch alone (see above)."""
     tasks = [(int(x), int(y)) for x, y in tasks]
     assert tasks and all(x != y for x, y in tasks)
     assert scratch in ("keep", "spread") or 0 <= scratch <= 0xFFFFFFFF
     if pool_cap is None:
         pool_cap = 2 * sum(nnz(oracle, seqs, tasks, th, model)) + 64
+    assert force is None or (len(force) == 2 and all(int(v) > 0 for v in force))
+    assert window is None or int(window) > 0
     return {"model": model, "th": float(np.float32(th)), "seqs": list(seqs), "tasks": tasks, "scratch": scratch, "nwaves": nwaves,
-            "pool_cap": int(pool_cap), "plan_for": plan_for}
+            "pool_cap": int(pool_cap), "plan_for": plan_for, "force": force and [int(v) for v in force], "window": window and int(window)}
 
 
 def run(tmp_path, launches, env=None, tail=4096, scratch_tail=4096, timeout=120):
@@ -158,6 +163,24 @@ def _i32(word):
     return word - (1 << 32) if word >= (1 << 31) else word
 
 
+class _setenv:
+    """names set to values (None: left alone) for the block, then whatever they held before"""
+
+    def __init__(self, **kw):
+        self.kw = {k: str(v) for k, v in kw.items() if v is not None}
+
+    def __enter__(self):
+        self.old = {k: os.environ.get(k) for k in self.kw}
+        os.environ.update(self.kw)  # os.environ calls putenv: the library's getenv sees it
+
+    def __exit__(self, *exc):
+        for k, v in self.old.items():
+            if v is None:
+                del os.environ[k]
+            else:
+                os.environ[k] = v
+
+
 def _child(job_path, out_path):
     import ctypes as C
     import torch  # before the library: both then share torch's HIP runtime, as in bench.py
@@ -187,7 +210,9 @@ def _child(job_path, out_path):
         plan = capi.PairhmmPlan()
         nt, m1, m2 = L["plan_for"] or (n, int(lens[px].max()), int(lens[py].max()))
         assert nt >= n and m1 >= int(lens[px].max()) and m2 >= int(lens[py].max())
-        capi.check((capi.pairhmm5_plan if L["model"] else capi.pairhmm_plan)(nt, m1, m2, plan))
+        fg, fw = L.get("force") or (None, None)
+        with _setenv(DAFS_HIP_FORCE_GROUP=fg, DAFS_HIP_FORCE_WIDTH=fw):
+            capi.check((capi.pairhmm5_plan if L["model"] else capi.pairhmm_plan)(nt, m1, m2, plan))
         planned = plan.nwaves
         if L["nwaves"]:
             plan.nwaves = L["nwaves"]  # the scratch stays the planner's; the launch refuses an nwaves it does not cover
@@ -237,7 +262,8 @@ def _child(job_path, out_path):
         (capi.pairhmm5_default_model if contra else capi.pairhmm3_default_model)(C.byref(a.model))
         try:
             torch.cuda.synchronize()
-            rc = (capi.pairhmm5_launch if contra else capi.pairhmm3_launch)(C.byref(a), C.byref(plan), C.c_void_p(stream.cuda_stream))
+            with _setenv(DAFS_HIP_EMIT_WINDOW=L.get("window")):
+                rc = (capi.pairhmm5_launch if contra else capi.pairhmm3_launch)(C.byref(a), C.byref(plan), C.c_void_p(stream.cuda_stream))
             if rc:
                 sys.exit("launch %d: %s" % (k, capi._strerror(rc).decode()))
             torch.cuda.synchronize()
