@@ -33,14 +33,17 @@ extern "C" int dafs_hip_mp_export_dev(dafs_hip_ctx* c, int relaxed, uint64_t fir
   if (!nnz || !rowptr || (sim && relaxed != 0)) return DAFS_HIP_EINVAL;
   const uint64_t rp0 = st.rp_by_pair[first], rp1 = first + count < st.n_tasks ? st.rp_by_pair[first + count] : st.rp_total;
   int rc;
-  if ((rc = gather_tasks_launch(st.d_task_of_pair.ptr, first, count, st.pair_nnz.ptr, sim ? c->task_sim.ptr : nullptr, nnz, sim, c->stream))) return rc;
-  if ((rc = c->work2.reserve((count + 1) * sizeof(uint64_t) + 64))) return rc;
+  // the counts are gathered and summed in the workspace first: an export that is refused for its capacity writes nothing
+  if ((rc = c->work2.reserve((count + 1) * sizeof(uint64_t) + count * sizeof(uint32_t) + 64))) return rc;
   uint64_t* prefix = (uint64_t*)c->work2.ptr;
-  if ((rc = scan_excl_launch(nnz, 2u, prefix, count, c->stream))) return rc;
+  uint32_t* counts = (uint32_t*)(prefix + count + 1);
+  if ((rc = gather_tasks_launch(st.d_task_of_pair.ptr, first, count, st.pair_nnz.ptr, nullptr, counts, nullptr, c->stream))) return rc;
+  if ((rc = scan_excl_launch(counts, 2u, prefix, count, c->stream))) return rc;
   uint64_t total = 0;
   if (hip_check(hipMemcpyAsync(&total, prefix + count, sizeof total, hipMemcpyDeviceToHost, c->stream)) || hip_check(hipStreamSynchronize(c->stream))) return DAFS_HIP_ELAUNCH;
   if (total > cap_entries) return DAFS_HIP_EOVERFLOW;
   if (total && (!col || !val)) return DAFS_HIP_EINVAL;
+  if ((rc = gather_tasks_launch(st.d_task_of_pair.ptr, first, count, st.pair_nnz.ptr, sim ? c->task_sim.ptr : nullptr, nnz, sim, c->stream))) return rc;
   if ((rc = d2d(rowptr, st.rowptr_pool.ptr + rp0, (rp1 - rp0) * sizeof(uint32_t), c->stream))) return rc;
   if (total && (rc = mp_pack_launch(st.d_task_of_pair.ptr, first, count, st.pair_off.ptr, st.pair_nnz.ptr, st.col.ptr, st.val.ptr, prefix, col, val, c->stream))) return rc;
   if (hip_check(hipStreamSynchronize(c->stream))) return DAFS_HIP_ELAUNCH;  // the caller's streams may read the buffers now

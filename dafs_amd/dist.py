@@ -34,6 +34,12 @@ def pair_id(x, y, n):
     return x * n - x * (x + 1) // 2 + (y - x - 1)
 
 
+def pair_ranges(npairs, world):
+    """[(begin, end)] per rank: the contiguous ranges of the row-major pair enumeration that a sharded phase 1 gives its
+    ranks (dafs_hip_pair_range)"""
+    return [(npairs * r // world, npairs * (r + 1) // world) for r in range(world)]
+
+
 class GatheredPairs:
     """Every rank's shard after the all-gather; csr(x, y) returns the rows of mp[x][y] for any x != y."""
 

@@ -1097,7 +1097,13 @@ int dafs_host_compare_matrix_table(uint32_t n, const char* const* names, const u
  *   dafs_hip_bp_export_dev   the un-relaxed base-pairing store, sequences in input order (dafs_hip_bp_fetch's layout).
  *   dafs_hip_set_bp_dev      the un-relaxed base-pairing store from nblocks = N blocks in any order: block k holds the rows
  *                            of sequence seq_of_block[k] (host array); rowptr / col / val are the blocks' arrays concatenated
- *                            in block order -- what the ranks' exports look like after the gather. */
+ *                            in block order -- what the ranks' exports look like after the gather.
+ * DAFS_HIP_EINVAL: a range beyond the store's pairs (first > npairs or count > npairs - first), sim with relaxed = 1, a relaxed
+ * install without an un-relaxed store, an n_entries that is not what the counts (mp) or the blocks' last row pointers (bp) add
+ * up to, nblocks != N, a sequence named twice or beyond N.  DAFS_HIP_EOVERFLOW: cap_entries below the entries of the range (of
+ * the store, for bp).  A refused export writes nothing into the caller's buffers; an install refused for its n_entries or for
+ * the sequences its blocks name leaves the store it was to fill invalid until a correct one (dafs_hip_mp_install_dev checks
+ * the total only, dafs_hip_mp_install every pair's row pointers).  count = 0 is no error and writes nothing. */
 int dafs_hip_mp_export_dev(dafs_hip_ctx* ctx, int relaxed, uint64_t first, uint64_t count, uint32_t* nnz, uint32_t* rowptr, uint32_t* col, float* val,
                            float* sim, uint64_t cap_entries, uint64_t* n_rowptr, uint64_t* n_entries);
 int dafs_hip_mp_install_dev(dafs_hip_ctx* ctx, int relaxed, const uint32_t* nnz, const uint32_t* rowptr, const uint32_t* col, const float* val,
