@@ -62,6 +62,50 @@ inline bool structure_ok(const uint32_t* ss, uint32_t L, std::vector<uint8_t>& u
   return true;
 }
 
+// DESIGN.md section 5.1, "Sweep 2p": the cut of the pair-HMM kernel's candidate pick.  pair_cut(th) is a value c <= -0.5
+// such that every float v with -16 < v < c has EXP(v) <= th, EXP being the reference's quartic pieces (ScoreType.h:37-57,
+// pc_math.h: evaluated in double, narrowed to float; 0 for v <= -16).  The pieces are not known to be monotone across their
+// seams, so the bound is computed, not assumed: on the grid g_k = -16 + k / 1024 (every seam is a grid point, and an interval
+// (g_k-1, g_k] lies in one piece) the piece's quartic P obeys  max over [a, b] of P <= max(P(a), P(b)) + max|P''| (b - a)^2 / 8,
+// with |P''| bounded term by term (and max = P(b) where a term-by-term lower bound of P' is positive, which makes the cut
+// -0.5 for every th above EXP(-0.5)); M[k] is the running maximum of those bounds plus 1e-12 for the rounding of the double
+// Horner form (narrowing to float is monotone, and th is a float).  The cut is the largest g_k <= -0.5 with M[k] <= th:
+// at most 1/1024 and the bound's slack (< 3e-7 in EXP) below the best possible one.
+inline float pair_cut(float th) {
+  static const std::vector<double> M = [] {
+    static const double e[5][5] = {  // pieces (-1, -1/2], (-2, -1], (-4, -2], (-8, -4], (-16, -8]: k4 .. k0
+        {0.01973899026052090000, 0.13822379685007000000, 0.48056651562365000000, 0.99326940370383500000, 0.99906756856399500000},
+        {0.00940528203591384000, 0.09414963667859410000, 0.40825793595877300000, 0.93933625499130400000, 0.98369508190545300000},
+        {0.00217245711583303000, 0.03484829428350620000, 0.22118199801337800000, 0.67049462206469500000, 0.83556950223398500000},
+        {0.00012398771025456900, 0.00349155785951272000, 0.03727721426017900000, 0.17974997741536900000, 0.33249299994217400000},
+        {0.00000051741713416603, 0.00002721456879608080, 0.00053418601865636800, 0.00464101989351936000, 0.01507447981459420000}};
+    const int n = (16 * 1024) - 512;  // grid points above -16 up to -0.5
+    std::vector<double> m((size_t)n + 1, 0.0);
+    const double h = 1.0 / 1024.0;
+    for (int k = 1; k <= n; ++k) {
+      const double a = -16.0 + (k - 1) * h, b = -16.0 + k * h;
+      const double* q = e[b <= -8.0 ? 4 : b <= -4.0 ? 3 : b <= -2.0 ? 2 : b <= -1.0 ? 1 : 0];  // the piece of (a, b]
+      const double pa = (((q[0] * a + q[1]) * a + q[2]) * a + q[3]) * a + q[4];
+      const double pb = (((q[0] * b + q[1]) * b + q[2]) * b + q[3]) * b + q[4];
+      const double x = -a;  // the largest |v| of the interval
+      const double d2 = 12.0 * q[0] * x * x + 6.0 * q[1] * x + 2.0 * q[2];
+      const double d1 = q[3] - 2.0 * q[2] * x - 4.0 * q[0] * x * x * x;  // P' >= d1 on [a, b]: where d1 > 0, P rises to P(b)
+      const double bound = (d1 > 0.0 ? pb : (pa > pb ? pa : pb) + d2 * h * h / 8.0) + 1e-12;
+      m[(size_t)k] = bound > m[(size_t)k - 1] ? bound : m[(size_t)k - 1];
+    }
+    return m;
+  }();
+  size_t lo = 0, hi = M.size() - 1;  // the largest k with M[k] <= th (M[0] = 0; th < 0 or NaN: -16, every cell a candidate)
+  if (!(M[hi] <= (double)th)) {
+    while (hi - lo > 1) {
+      const size_t mid = (lo + hi) / 2;
+      if (M[mid] <= (double)th) lo = mid; else hi = mid;
+    }
+    hi = lo;
+  }
+  return (float)(-16.0 + (double)hi / 1024.0);
+}
+
 // DESIGN.md section 22, "Distances from an alignment": the distance of two rows with `mism` differing of `comp` compared
 // columns.  The Jukes-Cantor value is quantised to 2^-20 the way LNQ is in section 13, so that an ulp of log() cannot move a
 // bit: it would have to carry -0.75 * log(x) * 2^20 + 0.5 across an integer.

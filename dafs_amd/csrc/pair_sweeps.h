@@ -87,10 +87,21 @@ struct pair_rec {
 };
 // staged: sweep 4 of the sparse form goes through windows staged in LDS (`stage`, E positions; k_pairhmm3) or scatters
 // every entry from its lane (k_pairhmm5, which passes no stage).
-template <int G, int W, int WR, bool dense, bool staged, class Args, class Post>
+//
+// picked = true (k_pairhmm3, pairhmm3.hip "sweep 2p"): the backward sweep has stored no plane.  `slab` is then the plane
+// of the lanes' CANDIDATE lists ({candidate mask, row, the WR sums F + B}, ncand records in descending row order, only
+// the lane-steps with a cell that can reach th) and `list` the plane the final records go to; sweep 3 becomes
+//   3b: every lane walks its own candidate list, two records per turn: p = post(sums), exact entry mask
+//       = candidate && p >= th && p > th, the record goes back in place as {entry mask, row, p}
+//   3c: the step of sweep 3 without slab loads and without post: a lane takes the entry mask and the posteriors of row
+//       i from the record of that row (consumed from its last record downwards, i.e. rows ascending) and an empty
+//       mask otherwise; similarity DP, counts, row pointers and the final records are those of sweep 3.
+// The final records are a subset of the candidate records, so a list that held the candidates holds them too.
+template <int G, int W, int WR, bool dense, bool staged, bool picked = false, class Args, class Post>
 __device__ __forceinline__ bool pair_finish(const Args& a, float* __restrict__ slab, float* __restrict__ list, int list_cap, uint32_t* __restrict__ s_rowptr,
                                             uint2* __restrict__ stage, int E, int lane, int t, int g, int L1, int L2, int nsteps, bool act, uint32_t task,
-                                            float th, Post post) {
+                                            float th, Post post, int ncand = 0) {
+  static_assert(!(picked && dense), "the candidate form is a sparse form");
   const int tlast = (L2 >= 0 ? L2 : 0) / WR;  // lane (within the group) that owns column L2
   const int j0 = t * WR;
   // The wave's list plane as a buffer.  Sweep 3: the record stores of a step are issued by every lane, and a lane without
@@ -106,7 +117,143 @@ __device__ __forceinline__ bool pair_finish(const Args& a, float* __restrict__ s
   float simv = 0.0f;
   uint32_t nnz = 0;
   int slab_nrec = 0;
-  {
+  if constexpr (picked) {
+    constexpr int Q = pair_rec<WR>::Q;
+    const __amdgpu_buffer_rsrc_t cand_rs = __builtin_amdgcn_make_buffer_rsrc((void*)slab, 0, list_cap * 256, 0x00020000);
+    auto rec_off = [lane](const int k, const bool have) { return have ? (uint32_t)(((uint32_t)k * Q * 64 + lane) * 16) : NO_RECORD; };
+    // ---------------------------------------------------------------- sweep 3b: posteriors of the candidate records
+    {
+      int maxc = ncand;
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) maxc = max(maxc, __shfl_xor(maxc, o));
+      maxc = __builtin_amdgcn_readfirstlane(maxc);
+      constexpr int K = 2;  // records per turn, their loads issued together
+      for (int k0 = 0; k0 < maxc; k0 += K) {
+        u32x4 r[K][Q];
+#pragma unroll
+        for (int kk = 0; kk < K; ++kk)
+#pragma unroll
+          for (int q = 0; q < Q; ++q) r[kk][q] = __builtin_amdgcn_raw_buffer_load_b128(cand_rs, (int)(rec_off(k0 + kk, k0 + kk < ncand) + q * 1024), 0, 0);
+#pragma unroll
+        for (int kk = 0; kk < K; ++kk) {
+          uint32_t w[4 * Q];
+#pragma unroll
+          for (int q = 0; q < Q; ++q) { w[4 * q] = r[kk][q].x; w[4 * q + 1] = r[kk][q].y; w[4 * q + 2] = r[kk][q].z; w[4 * q + 3] = r[kk][q].w; }
+          float sv[WR], pp[WR];
+#pragma unroll
+          for (int c = 0; c < WR; ++c) sv[c] = __uint_as_float(w[2 + c]);
+          post(sv, pp);
+          uint32_t exact = 0;  // wrapper (>= th keeps) then adapter (> th keeps), as in sweep 3
+#pragma unroll
+          for (int c = 0; c < WR; ++c) exact |= (uint32_t)((pp[c] >= th) && (pp[c] > th) ? 1 : 0) << c;
+          w[0] &= exact;
+#pragma unroll
+          for (int c = 0; c < WR; ++c) w[2 + c] = __float_as_uint(pp[c]);
+#pragma unroll
+          for (int q = 0; q < Q; ++q) {  // a lane beyond its last record stores outside the buffer: dropped
+            const u32x4 d = {w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]};
+            __builtin_amdgcn_raw_buffer_store_b128(d, cand_rs, (int)(rec_off(k0 + kk, k0 + kk < ncand) + q * 1024), 0, 0);
+          }
+        }
+      }
+    }
+#if defined(PAIR_EXP_STOP) && PAIR_EXP_STOP == 4  // tuning experiment: everything up to sweep 3b
+    if (ncand != 12345) return true;
+#endif
+    // ---------------------------------------------------------------- sweep 3c: sim + counts from the records
+    float pdp[WR];
+    int ptr[WR];
+#pragma unroll
+    for (int c = 0; c < WR; ++c) { pdp[c] = 0.0f; ptr[c] = 0; colcnt[c] = 0; }
+    float lastdp = 0.0f, dgdp = 0.0f;
+    int lasttr = 0, dgtr = 0, lastcnt = 0;
+    uint32_t rowacc = 0;
+    if (t == G - 1) s_rowptr[0] = 0;
+    int nrec = 0;  // final records of this lane
+    // The lane's next record (the one with the lowest row not yet passed) waits in `cur`.  A step that consumes it
+    // requests the one before it at once, into `pend`, which replaces `cur` at the top of the next step: a lane
+    // consumes at most one record per step, and every lane issues the load in every step (outside the buffer where it
+    // has consumed nothing), so the step has no branch around a memory operation and its waits are counted ones.
+    int left = ncand;
+    u32x4 cur[Q], pend[Q];
+#pragma unroll
+    for (int q = 0; q < Q; ++q) cur[q] = __builtin_amdgcn_raw_buffer_load_b128(cand_rs, (int)(rec_off(left - 1, left > 0) + q * 1024), 0, 0);
+#pragma unroll
+    for (int q = 0; q < Q; ++q) { asm volatile("" : "+v"(cur[q])); pend[q] = cur[q]; }
+    bool took = false;
+    for (int s = 0; s < nsteps; ++s) {
+      const int i = s - t;
+      const bool rowv = (i >= 0) && (i <= L1);
+      if (took) {
+#pragma unroll
+        for (int q = 0; q < Q; ++q) cur[q] = pend[q];
+      }
+      const bool hit = left > 0 && (int)cur[0].y == i;
+      left -= hit ? 1 : 0;
+#pragma unroll
+      for (int q = 0; q < Q; ++q) pend[q] = __builtin_amdgcn_raw_buffer_load_b128(cand_rs, (int)(rec_off(left - 1, hit && left > 0) + q * 1024), 0, 0);
+      took = hit;
+      uint32_t w[4 * Q];
+#pragma unroll
+      for (int q = 0; q < Q; ++q) { w[4 * q] = cur[q].x; w[4 * q + 1] = cur[q].y; w[4 * q + 2] = cur[q].z; w[4 * q + 3] = cur[q].w; }
+      const uint32_t emask = hit ? w[0] : 0u;  // entries among the WR cells, bit c = cell c
+      const float rdp = shift_up1<G>(lastdp, 0.0f, t);
+      const int rtr = shift_up1<G>(lasttr, 0, t), rcnt = shift_up1<G>(lastcnt, 0, t);
+      float ddp = dgdp, ldp = rdp;
+      int dtr = dgtr, ltr = rtr, run = rcnt;
+#pragma unroll
+      for (int c = 0; c < WR; ++c) {  // the cell of sweep 3, with the entry bit and the posterior from the record
+        const int j = j0 + c;
+        const bool inner = rowv && (j <= L2) && i >= 1 && j >= 1;
+        const bool entry = ((emask >> c) & 1u) != 0;
+        const float p = __uint_as_float(w[2 + c]);
+        const float udp = pdp[c];
+        const int utr = ptr[c];
+        const float dpe = entry ? ddp + p : -1.0f;
+        const bool fl = dpe < ldp;
+        float dp = fl ? ldp : dpe;
+        int tr = fl ? ltr : dtr;
+        const bool fu = dp < udp;
+        dp = fu ? udp : dp;
+        tr = (fu ? utr : tr) + 1;
+        if (!inner) { dp = 0.0f; tr = 0; }
+        ddp = udp; dtr = utr;
+        pdp[c] = dp; ptr[c] = tr;
+        ldp = dp; ltr = tr;
+        const int e = entry ? 1 : 0;
+        run += e;
+        colcnt[c] += e;
+      }
+      {  // the step's final record (pair_rec): never more of them than candidate records, so it always fits
+        w[0] = emask;
+        w[1] = (uint32_t)((i - 1) | (rcnt << 16));
+        const uint32_t ro = emask != 0 ? (uint32_t)(((uint32_t)nrec * Q * 64 + lane) * 16) : NO_RECORD;
+#pragma unroll
+        for (int q = 0; q < Q; ++q) {
+          const u32x4 d = {w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]};
+          __builtin_amdgcn_raw_buffer_store_b128(d, list_rs, (int)(ro + q * 1024), 0, 0);
+        }
+        nrec += emask != 0 ? 1 : 0;
+      }
+      dgdp = rdp; dgtr = rtr;
+      lastdp = ldp; lasttr = ltr; lastcnt = run;
+      if (i == L1 && t == tlast) {  // dafs.cpp:763; one lane of the group, once
+        const int cl = L2 - j0;
+        float sdp = 0.0f;
+        int str = 1;
+#pragma unroll
+        for (int c = 0; c < WR; ++c)
+          if (c == cl) { sdp = pdp[c]; str = ptr[c]; }
+        simv = sdp / (float)str;
+      }
+      if (t == G - 1 && rowv && i >= 1) {  // row i is complete: its count has crossed the group
+        rowacc += (uint32_t)run;
+        s_rowptr[i] = rowacc;
+      }
+    }
+    nnz = rowacc;
+    slab_nrec = nrec;
+  } else {
     float pdp[WR];
     int ptr[WR];
 #pragma unroll

@@ -11,13 +11,20 @@
 // (L1+1) x (L2+1) DP grid and keeps the previous row of its columns in registers; rows are
 // skewed so that at wavefront step s lane t works on row i = s - t (a register-resident
 // anti-diagonal wavefront: no LDS traffic and no barriers, the only cross-lane exchange is one
-// lane-to-neighbour shuffle of the boundary column per step).  Four sweeps share that shape:
-//   1 forward   : writes F_M(i,j) to the wave's slab in HBM
-//   2 backward  : mirrored skew; reads F_M, writes S = F_M + B_M in place
-//   3 posterior : P = EXP(min(0,S-total)) thresholded, written in place; the same sweep runs the
-//                 similarity-score DP and counts entries per row (count travels with the row
-//                 from lane to lane) and per column (registers)
-//   4 emit      : the entries into the CSR of mp[x][y] and of mp[y][x], through windows staged in LDS
+// lane-to-neighbour shuffle of the boundary column per step).  The sweeps share that shape:
+//   1  forward  : writes F_M(i,j) to the wave's slab in HBM (plane 0)
+//   2p backward : mirrored skew; reads F_M, keeps S = F_M + B_M in registers and appends the lane-steps that hold a
+//                 CANDIDATE (a cell whose posterior can reach th: S - totF >= 32 (cut(th) - delta)) to per-lane lists
+//                 in plane 1.  No plane is stored; the forward plane stays intact.
+//   3b records  : P = EXP(min(0,S-total)) and the exact entry mask of every candidate record, in place
+//   3c sim      : the similarity-score DP and the entry counts per row (the count travels with the row from lane to
+//                 lane) and per column (registers) over all cells, entries and posteriors taken from the records;
+//                 the final entry records go over plane 0
+//   4  emit     : the entries into the CSR of mp[x][y] and of mp[y][x], through windows staged in LDS
+// A wavefront with a pair whose totB lies further than the margin from totF, or whose candidate list is full, and every
+// wavefront at th < 0.002 (dense outputs) or under DAFS_HIP_PAIR_PICK=0 takes the classic path instead:
+//   2  backward : the same sweep, writes S = F_M + B_M over the forward plane
+//   3  posterior: P of every cell, thresholded; similarity DP and counts; entry records into plane 1 (or, dense, P in place)
 // The slab is indexed [(step*W + c)*64 + lane], so every slab access of a wave instruction is one
 // contiguous 256-byte segment, in all four sweeps (the backward sweep visits forward step
 // L1+G-1-s, the same for every lane).  Work is handed out by a device-side counter, longest
@@ -28,7 +35,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
+#include <type_traits>
 #include "../../include/dafs_hip.h"
+#include "call_host.h"
 #include "pc_math.h"
 #include "hip_util.h"
 #include "stage.h"
@@ -36,9 +45,16 @@
 
 namespace dafs {
 
+// What the launch tells sweep 2p (below), in the 32x domain of the sweeps
+struct pair_pick {
+  float cut;    // a cell is a candidate when S - totF >= cut: 32 * (pair_cut(th) - delta)
+  float trust;  // a pair's candidates stand when |totB - totF| <= trust: 32 * delta, or negative (no pair passes)
+  uint32_t on;  // 0: every wavefront takes the classic backward sweep
+};
+
 // One pair per group of G lanes, all four sweeps, for the compile-time column count WR (W or W-1).
 template <int G, int W, int WR>
-__device__ __forceinline__ void pairhmm3_pair(const dafs_pairhmm3_args& a, const pc_tables* tab, const float* s_match, const float* s_ins, const float2* s_mi,
+__device__ __forceinline__ void pairhmm3_pair(const dafs_pairhmm3_args& a, const pair_pick& pk, const pc_tables* tab, const float* s_match, const float* s_ins, const float2* s_mi,
                                               float* __restrict__ slab, float* __restrict__ list, int list_cap, uint32_t* __restrict__ s_rowptr, uint2* __restrict__ s_stage, int E, int lane, int t, int g,
                                               int L1, int L2, int nsteps, bool act, uint32_t task,
                                               const uint8_t* __restrict__ s1, const uint8_t* __restrict__ s2) {
@@ -183,8 +199,24 @@ __device__ __forceinline__ void pairhmm3_pair(const dafs_pairhmm3_args& a, const
   //   bm  = bm1 (+) (ty+tMY)         by = (pxy+tYM) (+) (ty+tYY)          ty = B_Y(i,j+1) + ins(y_{j+1})
   // bm and by wait for the cell to the right; same pipeline, columns descending: iteration `it` runs bm1, bx of cell
   // WR-1-it and bm, by of cell WR-it.
+  //
+  // Two forms of the one sweep.  The classic one (pick = false) stores S = F_M + B_M over the forward plane.  Sweep 2p
+  // (pick = true) stores no plane and leaves the forward plane intact: the step keeps its WR sums in registers, and a
+  // lane with at least one CANDIDATE among them -- S - totF >= pk.cut, i.e. a cell whose posterior can reach th by the
+  // bound of pair_cut (call_host.h), taken against totF with a margin because totB is known only when the sweep ends --
+  // appends one record {candidate mask, row, S[WR]} to its list in plane 1 (pair_rec layout, the unconditional
+  // buffer stores of sweep 3: an offset outside the buffer where there is nothing to store, no branch).  Cells outside the
+  // grid, row 0, column 0 and idle groups carry LOG_ZERO-sized sums and never pass.  A lane's records come in descending
+  // row order; ncand counts them, and the call returns whether a list was full.
   float capM = LZ, capX = LZ, capY = LZ;  // B_M(1,1), B_X(1,0), B_Y(0,1)
-  {
+  int ncand = 0;
+  auto backward = [&](auto pick_tag) __attribute__((always_inline)) -> bool {
+    constexpr bool pick = decltype(pick_tag)::value;
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    const __amdgpu_buffer_rsrc_t cand_rs = __builtin_amdgcn_make_buffer_rsrc((void*)list, 0, list_cap * 256, 0x00020000);
+    bool ovf = false;
+    capM = capX = capY = LZ;
+    ncand = 0;
     float pM[WR], pX[WR];  // row i+1 at this lane's columns
 #pragma unroll
     for (int c = 0; c < WR; ++c) pM[c] = pX[c] = LZ;
@@ -227,6 +259,8 @@ __device__ __forceinline__ void pairhmm3_pair(const dafs_pairhmm3_args& a, const
       // pM/pX updated in place (see sweep 1); bm1, by0 and B_Y live for one iteration
       float bm1prev = LZ, by0prev = LZ, yprev = LZ, insprev = 0.0f;
       float2 mi_next = mi_row[cc[WR]];  // {match(x_{i+1}, y_{j+1}), ins(y_{j+1})} of the cell the next iteration starts
+      float sums[WR];      // sweep 2p: the step's S values
+      uint32_t cmask = 0;  // and which of them are candidates
 #pragma unroll
       for (int it = 0; it < WR + 1; ++it) {
         float x[4], y[4], o[4];
@@ -261,7 +295,13 @@ __device__ __forceinline__ void pairhmm3_pair(const dafs_pairhmm3_args& a, const
           const int j = j0 + c;
           pM[c] = o[2];
           yprev = o[3];
-          slab_s[c * 64 + lane] = fwd[c] + o[2];  // forward[ij] + backward[ij], :395
+          const float sum = fwd[c] + o[2];  // forward[ij] + backward[ij], :395
+          if constexpr (pick) {
+            sums[c] = sum;
+            cmask |= (uint32_t)(sum - totF >= pk.cut ? 1 : 0) << c;
+          } else {
+            slab_s[c * 64 + lane] = sum;
+          }
           fwd[c] = slab_p[c * 64 + lane];
           if (c <= 1) {  // columns 0 and 1 only exist for c <= 1
             if (i == 1 && j == 1) capM = o[2];
@@ -277,22 +317,66 @@ __device__ __forceinline__ void pairhmm3_pair(const dafs_pairhmm3_args& a, const
           pX[c] = o[1];
         }
       }
+      if constexpr (pick) {  // one record for the step, stored by the lanes that have a candidate and room for it
+        constexpr int Q = pair_rec<WR>::Q, D = pair_rec<WR>::D;
+        const bool fits = (ncand + 1) * D <= list_cap;
+        const bool app = cmask != 0 && fits;
+        ovf = ovf || (cmask != 0 && !fits);
+        uint32_t w[D];
+        w[0] = cmask;
+        w[1] = (uint32_t)i;
+#pragma unroll
+        for (int c = 0; c < WR; ++c) w[2 + c] = __float_as_uint(sums[c]);
+#pragma unroll
+        for (int c = 2 + WR; c < D; ++c) w[c] = 0u;
+        const uint32_t ro = app ? (uint32_t)(((uint32_t)ncand * Q * 64 + lane) * 16) : 0x80000000u;  // or beyond any plane
+#pragma unroll
+        for (int q = 0; q < Q; ++q) {
+          const u32x4 d = {w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]};
+          __builtin_amdgcn_raw_buffer_store_b128(d, cand_rs, (int)(ro + q * 1024), 0, 0);
+        }
+        ncand += app ? 1 : 0;
+      }
       dgM = rM;
       firstM = pM[0];
       firstY = yprev;
     }
-  }
-#if defined(PAIR_EXP_STOP) && PAIR_EXP_STOP == 2  // tuning experiment: forward + backward
-  if (capM != 12345.0f) return;
-#endif
+    return ovf;
+  };
   // ComputeTotalProbability, :349-364
-  capM = __shfl(capM, g * G + (1 / WR));
-  capX = __shfl(capX, g * G);
-  capY = __shfl(capY, g * G + (1 / WR));
-  float totB = fM11 + capM;
-  totB = pc_log_add_s(tab, totB, fX10 + capX);
-  totB = pc_log_add_s(tab, totB, fY01 + capY);
-  const float total = (totF + totB) / 2;
+  float totB = LZ, total = LZ;
+  auto totals = [&]() __attribute__((always_inline)) {
+    capM = __shfl(capM, g * G + (1 / WR));
+    capX = __shfl(capX, g * G);
+    capY = __shfl(capY, g * G + (1 / WR));
+    totB = fM11 + capM;
+    totB = pc_log_add_s(tab, totB, fX10 + capX);
+    totB = pc_log_add_s(tab, totB, fY01 + capY);
+    total = (totF + totB) / 2;
+  };
+  // Sweep 2p first where the outputs are sparse.  Its candidates rest on totF standing in for total within the margin and
+  // on lists that held every record; a wavefront with a pair where either fails (wave-uniform) runs the classic sweep
+  // from the intact forward plane instead, so no result ever depends on the margin: it costs time only.
+  bool picked = false;
+  if (pk.on && a.th >= 0.002f) {
+    const bool ovf = backward(std::true_type());
+#if defined(PAIR_EXP_STOP) && PAIR_EXP_STOP == 2  // tuning experiment: forward + backward
+    if (capM != 12345.0f) return;
+#endif
+    totals();
+    const bool bad = act && (ovf || !(fabsf(totB - totF) <= pk.trust));
+    picked = !__any(bad);
+#if defined(PAIR_EXP_COUNT_CLASSIC)  // tuning build: *status = pairs whose wavefront took the classic path, << 8
+    if (!picked && act && t == 0) atomicAdd(a.status, 256);
+#endif
+  }
+  if (!picked) {
+    (void)backward(std::false_type());
+#if defined(PAIR_EXP_STOP) && PAIR_EXP_STOP == 2
+    if (capM != 12345.0f) return;
+#endif
+    totals();
+  }
 
   // sweeps 3 + 4 (pair_sweeps.h): ComputePosteriorMatrix :395 = EXP(min(LOG_ONE, F+B-total)), then sparse outputs
   auto post = [total, tab](const float (&sv)[WR], float (&p)[WR]) {
@@ -306,7 +390,9 @@ __device__ __forceinline__ void pairhmm3_pair(const dafs_pairhmm3_args& a, const
   };
   // sparse outputs through per-lane entry lists (pair_sweeps.h); with th near 0 (dense outputs), or when a list
   // is full, the plane-and-rescan form
-  if (a.th < 0.002f || !pair_finish<G, W, WR, false, true>(a, slab, list, list_cap, s_rowptr, s_stage, E, lane, t, g, L1, L2, nsteps, act, task, a.th, post))
+  if (picked)  // candidate lists in plane 1; the final lists go over the forward plane, which is dead by now
+    (void)pair_finish<G, W, WR, false, true, true>(a, list, slab, list_cap, s_rowptr, s_stage, E, lane, t, g, L1, L2, nsteps, act, task, a.th, post, ncand);
+  else if (a.th < 0.002f || !pair_finish<G, W, WR, false, true>(a, slab, list, list_cap, s_rowptr, s_stage, E, lane, t, g, L1, L2, nsteps, act, task, a.th, post))
     (void)pair_finish<G, W, WR, true, true>(a, slab, list, list_cap, s_rowptr, s_stage, E, lane, t, g, L1, L2, nsteps, act, task, a.th, post);
 }
 
@@ -314,7 +400,7 @@ __device__ __forceinline__ void pairhmm3_pair(const dafs_pairhmm3_args& a, const
 // from the code object).  Resident wavefronts are what keeps the vector pipe busy between the lookups of the
 // log-sum-exps: 2 per SIMD reach a third of its issue rate.
 template <int G, int W, int OCC>
-__global__ __launch_bounds__(256, OCC) void k_pairhmm3(dafs_pairhmm3_args a, uint32_t slab_steps, uint32_t rp_cap, uint32_t emit_e) {
+__global__ __launch_bounds__(256, OCC) void k_pairhmm3(dafs_pairhmm3_args a, uint32_t slab_steps, uint32_t rp_cap, uint32_t emit_e, pair_pick pk) {
   constexpr int NG = 64 / G;  // pairs per wavefront
   extern __shared__ __attribute__((aligned(16))) uint32_t s_dyn[];  // per (wave, group): rp_cap row pointers, then sweep 4's staging windows
   __shared__ float s_match[56];
@@ -364,11 +450,10 @@ __global__ __launch_bounds__(256, OCC) void k_pairhmm3(dafs_pairhmm3_args a, uin
     for (int o = G; o < 64; o <<= 1) maxL1 = max(maxL1, __shfl_xor(maxL1, o));
     const int nsteps = __builtin_amdgcn_readfirstlane(maxL1) + G;
     // columns per lane of this wave: W, or W-1 when its pairs fit (pair_sweeps.h)
-    // columns per lane of this wave: W, or W-1 when its pairs fit (pair_sweeps.h)
     if (pair_width<G, W>(L2) == W)
-      pairhmm3_pair<G, W, W>(a, &s_tab, s_match, s_ins, s_mi, slab, list, list_cap, s_rowptr, s_stage, (int)emit_e, lane, t, g, L1, L2, nsteps, act, task, s1, s2);
+      pairhmm3_pair<G, W, W>(a, pk, &s_tab, s_match, s_ins, s_mi, slab, list, list_cap, s_rowptr, s_stage, (int)emit_e, lane, t, g, L1, L2, nsteps, act, task, s1, s2);
     else
-      pairhmm3_pair<G, W, (W > 1 ? W - 1 : 1)>(a, &s_tab, s_match, s_ins, s_mi, slab, list, list_cap, s_rowptr, s_stage, (int)emit_e, lane, t, g, L1, L2, nsteps, act, task, s1, s2);
+      pairhmm3_pair<G, W, (W > 1 ? W - 1 : 1)>(a, pk, &s_tab, s_match, s_ins, s_mi, slab, list, list_cap, s_rowptr, s_stage, (int)emit_e, lane, t, g, L1, L2, nsteps, act, task, s1, s2);
   }
 }
 
@@ -397,6 +482,8 @@ extern "C" int dafs_hipk_pairhmm_plan(uint32_t ntasks, uint32_t max_len1, uint32
   return pair_choose(k_variants, k_nvariants, ntasks, max_len1, max_len2, 2, 600.0, 370.0, 0.83, 0.17, plan);  // two planes: slab + entry lists
 }
 
+extern "C" float dafs_hip_pair_cut(float th) { return pair_cut(th); }
+
 extern "C" int dafs_hipk_pairhmm3_launch(const dafs_pairhmm3_args* args, const dafs_pairhmm_plan* plan, void* hip_stream) {
   if (!args || !plan) return DAFS_HIP_EINVAL;
   if (args->ntasks == 0) return DAFS_HIP_OK;
@@ -421,8 +508,13 @@ extern "C" int dafs_hipk_pairhmm3_launch(const dafs_pairhmm3_args* args, const d
     float* f = &a.model.init[0];
     for (size_t k = 0; k < sizeof a.model / sizeof(float); ++k) f[k] *= 32.0f;
   }
+  // sweep 2p's switches, read per launch: DAFS_HIP_PAIR_PICK=0 sends every wavefront down the classic path;
+  // DAFS_HIP_PAIR_PICK_MARGIN=n sets delta to n/1024 log units (default 128: 1/8; 0 fails every trust check)
+  const uint64_t margin = env_uint("DAFS_HIP_PAIR_PICK_MARGIN", 0, 8192, 128);
+  const float delta = (float)margin / 1024.0f;
+  pair_pick pk = {32.0f * (pair_cut(a.th) - delta), margin ? 32.0f * delta : -1.0f, env_off("DAFS_HIP_PAIR_PICK") ? 0u : 1u};
   uint32_t steps = plan->slab_steps, cap = rp_cap;
-  void* params[] = {&a, &steps, &cap, &emit_e};
+  void* params[] = {&a, &steps, &cap, &emit_e, &pk};
   hipError_t launch_err = hipSuccess;
   STAGE_LAUNCH(dafs::ST_PAIRHMM3, (hipStream_t)hip_stream) launch_err = hipLaunchKernel(v->fn, dim3(plan->nwaves / 4), dim3(256), params, lds, (hipStream_t)hip_stream);
   if (hip_check(launch_err)) return DAFS_HIP_ELAUNCH;

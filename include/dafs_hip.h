@@ -109,6 +109,9 @@ typedef struct {
 
 int dafs_hipk_pairhmm_plan(uint32_t ntasks, uint32_t max_len1, uint32_t max_len2, dafs_pairhmm_plan* plan);
 int dafs_hipk_pairhmm3_launch(const dafs_pairhmm3_args* args, const dafs_pairhmm_plan* plan, void* hip_stream);
+/* The cut of the launch's candidate pick: a value c <= -0.5 such that every float v with -16 < v < c has EXP(v) <= th
+ * (EXP: ScoreType.h:37-57), i.e. no cell whose log posterior lies below c can be an entry.  Host arithmetic only. */
+float dafs_hip_pair_cut(float th);
 /* Host-side model tables: log of the ProbCons defaults, computed with logf like the reference
  * constructor (ProbabilisticModel.h:55-88). */
 void dafs_hip_pairhmm3_default_model(dafs_pairhmm3_model* m);
