@@ -108,6 +108,158 @@ void pct_task_order(const uint32_t* pair_x, const uint32_t* pair_y, const uint32
 }
 }  // namespace dafs
 
+// Dense tiles for one launch: toff[k] is the offset of the k-th tile, cells their sum.  The tile memory is the pair kernels'
+// scratch, the offsets go to work, the launch's sums of weights to work2.  Synchronises, so toff may die with the caller's scope.
+template <class Args>
+static int pct_place_tiles(dafs_hip_ctx* c, const std::vector<uint64_t>& toff, uint64_t cells, Args& a) {
+  int rc;
+  const size_t cnt = toff.size();
+  if ((rc = c->scratch.reserve(cells + 64))) return rc;
+  if ((rc = c->work.reserve(cnt * 8 + 256))) return rc;
+  if ((rc = c->work2.reserve(cnt * 4 + 256))) return rc;
+  if (hip_check(hipMemcpyAsync(c->work.ptr, toff.data(), cnt * 8, hipMemcpyHostToDevice, c->stream))) return DAFS_HIP_ELAUNCH;
+  if (hip_check(hipStreamSynchronize(c->stream))) return DAFS_HIP_ELAUNCH;
+  a.tile = c->scratch.ptr; a.tile_off = (const uint64_t*)c->work.ptr; a.sum_w = (float*)c->work2.ptr;
+  return DAFS_HIP_OK;
+}
+
+// A transform into out's bump-allocated pool (out.col / out.val) of cap entries, a first guess: launch() enqueues it with
+// pool_top = counters and status = counters + 2; after DAFS_HIP_EOVERFLOW the pool grows to what the kernels asked for, or to
+// twice its size, and the transform runs again, five times at the most.  used: the entries taken; cap: the capacity that held them.
+template <class Store, class Launch>
+static int pct_into_pool(dafs_hip_ctx* c, Store& out, uint64_t& cap, uint64_t& used, Launch launch) {
+  for (int attempt = 0;; ++attempt) {
+    int rc;
+    if ((rc = out.col.reserve(cap))) return rc;
+    if ((rc = out.val.reserve(cap))) return rc;
+    if (hip_check(hipMemsetAsync(c->counters.ptr, 0, 4 * sizeof(unsigned long long), c->stream))) return DAFS_HIP_ELAUNCH;
+    if ((rc = launch())) return rc;
+    unsigned long long h[4];
+    if (hip_check(hipMemcpyAsync(h, c->counters.ptr, sizeof h, hipMemcpyDeviceToHost, c->stream))) return DAFS_HIP_ELAUNCH;
+    if (hip_check(hipStreamSynchronize(c->stream))) return DAFS_HIP_ELAUNCH;
+    const int status = (int)(h[2] & 0xffffffffu);
+    if (status == 0) { used = h[0]; return DAFS_HIP_OK; }
+    if (status != DAFS_HIP_EOVERFLOW || attempt >= 4) return status;
+    cap = std::max<uint64_t>(h[0], cap * 2);
+  }
+}
+
+// relax_basepairing_probability (dafs.cpp:326-375): bp[0] -> bp[1]
+static int consistency_bp(dafs_hip_ctx* c, const mp_store_dev& mpv, float w_pct_s) {
+  if (!c->bp[0].valid) return DAFS_HIP_EINVAL;
+  const uint32_t n = (uint32_t)c->len.size();
+  bp_store& in = c->bp[0];
+  bp_store& out = c->bp[1];
+  out.valid = false;
+  int rc;
+  if ((rc = out.rowptr.reserve(c->seq_rp_off[n]))) return rc;
+  if ((rc = out.nnz.reserve(n))) return rc;
+  if ((rc = out.bp_off.reserve(n + 1))) return rc;
+  if ((rc = out.rp_off.upload(c->seq_rp_off.data(), n + 1, c->stream))) return rc;
+  uint64_t cap = std::max<uint64_t>(4 * in.total_nnz + 1024, 16ull * c->off[n]);
+  rc = pct_into_pool(c, out, cap, out.total_nnz, [&]() -> int {
+    pct_bp_args a;
+    memset(&a, 0, sizeof a);
+    a.mp = mpv; a.bp = in.view(); a.sim = c->d_sim.ptr; a.w_pct = w_pct_s;
+    a.out_rowptr = out.rowptr.ptr; a.out_col = out.col.ptr; a.out_val = out.val.ptr;
+    a.pool_top = c->counters.ptr; a.pool_cap = cap; a.out_off = out.bp_off.ptr; a.out_nnz = out.nnz.ptr;
+    a.status = (int*)(c->counters.ptr + 2);
+    std::vector<uint64_t> toff(n);  // dense tiles, one per sequence
+    uint64_t cells = 0;
+    for (uint32_t x = 0; x < n; ++x) { toff[x] = cells; cells += (uint64_t)c->len[x] * c->len[x]; }
+    int rc;
+    if ((rc = pct_place_tiles(c, toff, cells, a))) return rc;
+    return pct_bp_launch(a, c->max_len(), c->stream);
+  });
+  if (rc) return rc;
+  out.valid = true;
+  c->cur_bp = 1;
+  return DAFS_HIP_OK;
+}
+
+// relax_matching_probability (dafs.cpp:258-324), or with fourway DAFS::relax_fourway_consistency: mp[0] -> mp[1], for the
+// output pairs at the positions [pair_begin, pair_end) of plist (list) or of the row-major order
+static int consistency_match(dafs_hip_ctx* c, const mp_store_dev& mpv, float w_pct_a, uint64_t pair_begin, uint64_t pair_end, bool fourway, bool list,
+                             const std::vector<uint32_t>& plist) {
+  const uint32_t n = (uint32_t)c->len.size(), max_len = c->max_len();
+  const uint64_t all = c->fam.npairs();
+  const bool shard = list || pair_begin != 0 || pair_end != all;  // only these output pairs are computed, the others stay empty
+  mp_store& raw = c->mp[0];
+  mp_store& out = c->mp[1];
+  out.valid = false;
+  out.listed = list;
+  out.listed_pairs = plist;
+  out.n_tasks = all;
+  out.pair_x = raw.pair_x;
+  out.pair_y = raw.pair_y;
+  out.rp_by_pair = raw.rp_by_pair;
+  out.rp_total = raw.rp_total;
+  out.task_of_pair.resize(all);
+  for (uint64_t p = 0; p < all; ++p) out.task_of_pair[p] = (uint32_t)p;
+  int rc;
+  if ((rc = out.d_task_of_pair.upload(out.task_of_pair.data(), all, c->stream))) return rc;
+  if ((rc = out.rp_off.upload(out.rp_by_pair.data(), all, c->stream))) return rc;
+  if ((rc = out.rowptr_pool.reserve(out.rp_total))) return rc;
+  if ((rc = out.pair_off.reserve(all))) return rc;
+  if ((rc = out.pair_nnz.reserve(all))) return rc;
+  if ((rc = c->d_pair_x.upload(raw.pair_x.data(), all, c->stream))) return rc;
+  if ((rc = c->d_pair_y.upload(raw.pair_y.data(), all, c->stream))) return rc;
+  if (list && (rc = c->pct_list.upload(plist.data(), plist.size(), c->stream))) return rc;
+  uint64_t cap = std::max<uint64_t>(raw.pool_used * 2 + 1024, out.pool_cap_hint);
+  rc = pct_into_pool(c, out, cap, out.pool_used, [&]() -> int {
+    int rc;
+    if (shard) {  // pairs outside the shard: no entries, all row pointers 0
+      if (hip_check(hipMemsetAsync(out.rowptr_pool.ptr, 0, out.rp_total * sizeof(uint32_t), c->stream))) return DAFS_HIP_ELAUNCH;
+      if (hip_check(hipMemsetAsync(out.pair_off.ptr, 0, all * sizeof(uint64_t), c->stream))) return DAFS_HIP_ELAUNCH;
+      if (hip_check(hipMemsetAsync(out.pair_nnz.ptr, 0, all * sizeof(uint32_t), c->stream))) return DAFS_HIP_ELAUNCH;
+    }
+    pct_match_args a;
+    memset(&a, 0, sizeof a);
+    a.in = mpv; a.sim = c->d_sim.ptr; a.pair_x = c->d_pair_x.ptr; a.pair_y = c->d_pair_y.ptr;
+    a.pair_list = list ? c->pct_list.ptr : nullptr;
+    a.npairs = (uint32_t)all; a.w_pct = w_pct_a;
+    a.rp_off = out.rp_off.ptr; a.rowptr_pool = out.rowptr_pool.ptr; a.col = out.col.ptr; a.val = out.val.ptr;
+    a.pool_top = c->counters.ptr; a.pool_cap = cap; a.pair_off = out.pair_off.ptr; a.pair_nnz = out.pair_nnz.ptr;
+    a.status = (int*)(c->counters.ptr + 2);
+    if (fourway) { a.bp = c->bp[0].view(); a.w_f = w_pct_a; }
+    // dense row tiles, in batches of at most kTileFloats
+    const uint64_t kTileFloats = 1ull << 31;  // 8 GiB
+    for (uint64_t p0 = pair_begin; p0 < pair_end;) {
+      std::vector<uint64_t> toff;
+      uint64_t cells = 0, p1 = p0;
+      while (p1 < pair_end) {
+        const uint64_t pr = list ? plist[p1] : p1;
+        const uint64_t need = (uint64_t)c->len[raw.pair_x[pr]] * c->len[raw.pair_y[pr]];
+        if (p1 > p0 && cells + need > kTileFloats) break;
+        toff.push_back(cells);
+        cells += need;
+        ++p1;
+      }
+      if ((rc = pct_place_tiles(c, toff, cells, a))) return rc;
+      const size_t cnt = (size_t)(p1 - p0);
+      a.wg_task = nullptr; a.wg_tasks = 0;
+      // DAFS_HIP_PCT_YORDER=1 (tuning aid): workgroups ordered by (y, row block, x) and dealt to the XCDs in contiguous ranges.
+      // Measured slower than the plain 2-D grid (N=128: 13.3 against 12.8 ms for the stage, N=256: 135 against 120): the
+      // gathers are not what binds the kernel, so the default stays the 2-D grid.  A pair list always takes the 2-D grid.
+      if (!fourway && !list && getenv("DAFS_HIP_PCT_YORDER")) {
+        std::vector<uint2> order;
+        pct_task_order(raw.pair_x.data(), raw.pair_y.data(), c->len.data(), n, p0, (uint32_t)cnt, order);
+        if ((rc = c->pct_tasks.upload(order.data(), order.size(), c->stream))) return rc;  // synchronises
+        a.wg_task = c->pct_tasks.ptr; a.wg_tasks = (uint32_t)order.size();
+      }
+      if ((rc = fourway ? pct_fourway_launch(a, max_len, (uint32_t)p0, (uint32_t)cnt, c->stream)
+                        : pct_match_launch(a, max_len, (uint32_t)p0, (uint32_t)cnt, c->stream))) return rc;
+      p0 = p1;
+    }
+    return DAFS_HIP_OK;
+  });
+  if (rc) return rc;
+  out.pool_cap_hint = cap;
+  out.valid = true;
+  c->cur_mp = 1;
+  return DAFS_HIP_OK;
+}
+
 // relax_basepairing_probability then relax_matching_probability, both from the un-relaxed
 // stores (dafs.cpp:1822-1827).  A weight of 0 skips that transform, as the reference does.
 // which: bit 0 the base-pairing transform, bit 1 the matching transform (the two read only un-relaxed stores, so they
@@ -119,7 +271,6 @@ static int consistency_parts(dafs_hip_ctx* c, float w_pct_a, float w_pct_s, int 
                              bool fourway = false, uint64_t nlist = 0, const uint64_t* list = nullptr) {
   if (!c || c->len.empty()) return DAFS_HIP_EINVAL;
   if (hip_check(hipSetDevice(c->device))) return DAFS_HIP_ENODEV;
-  const uint32_t n = (uint32_t)c->len.size();
   const uint64_t all = c->fam.npairs();  // every output pair reads its own family only (sparse_view.h)
   mp_store& raw = c->mp[0];
   if (!raw.valid || raw.n_tasks != all || (c->sim.empty() && !fourway)) return DAFS_HIP_EINVAL;
@@ -133,7 +284,6 @@ static int consistency_parts(dafs_hip_ctx* c, float w_pct_a, float w_pct_s, int 
       plist[q] = (uint32_t)list[q];
     }
   }
-  const uint32_t max_len = c->max_len();
   mp_store_dev mpv = c->mp_view(raw);
   int rc;
   // the row kernels gather {column, value} pairs: one interleaved copy of the input entries per transform
@@ -145,7 +295,7 @@ static int consistency_parts(dafs_hip_ctx* c, float w_pct_a, float w_pct_s, int 
   if ((rc = pct_interleave_launch(raw.col.ptr, raw.val.ptr, c->mp_ent2.ptr, raw.pool_used, c->stream))) return rc;
   mpv.ent2 = c->mp_ent2.ptr;
   {  // the identity matrix mp[x][x] as an ordinary CSR (entries {k, 1}, row pointers k): the row kernels treat it like any other
-    const uint32_t ni = max_len + 1 + 32;
+    const uint32_t ni = c->max_len() + 1 + 32;
     if ((rc = c->mp_ident2.reserve((size_t)ni + ni / 2 + 2))) return rc;
     uint32_t* ident_rp = (uint32_t*)(c->mp_ident2.ptr + ni);
     if ((rc = pct_ident_launch(c->mp_ident2.ptr, ident_rp, ni, c->stream))) return rc;
@@ -156,136 +306,11 @@ static int consistency_parts(dafs_hip_ctx* c, float w_pct_a, float w_pct_s, int 
   if (pair_end == 0) pair_end = all;
   if (pair_begin > pair_end || pair_end > all) return DAFS_HIP_EINVAL;
   if (list) { pair_begin = 0; pair_end = nlist; }  // the launches walk the positions of the list
-  const bool shard = list || pair_begin != 0 || pair_end != all;  // only these output pairs are computed, the others stay empty
 
   if (which & 1) c->cur_bp = 0;
-  if ((which & 1) && w_pct_s != 0.0f) {
-    if (!c->bp[0].valid) return DAFS_HIP_EINVAL;
-    bp_store& in = c->bp[0];
-    bp_store& out = c->bp[1];
-    out.valid = false;
-    if ((rc = out.rowptr.reserve(c->seq_rp_off[n]))) return rc;
-    if ((rc = out.nnz.reserve(n))) return rc;
-    if ((rc = out.bp_off.reserve(n + 1))) return rc;
-    if ((rc = out.rp_off.upload(c->seq_rp_off.data(), n + 1, c->stream))) return rc;
-    uint64_t cap = std::max<uint64_t>(4 * in.total_nnz + 1024, 16ull * c->off[n]);
-    for (int attempt = 0;; ++attempt) {
-      if ((rc = out.col.reserve(cap))) return rc;
-      if ((rc = out.val.reserve(cap))) return rc;
-      if (hip_check(hipMemsetAsync(c->counters.ptr, 0, 4 * sizeof(unsigned long long), c->stream))) return DAFS_HIP_ELAUNCH;
-      pct_bp_args a;
-      memset(&a, 0, sizeof a);
-      a.mp = mpv; a.bp = in.view(); a.sim = c->d_sim.ptr; a.w_pct = w_pct_s;
-      a.out_rowptr = out.rowptr.ptr; a.out_col = out.col.ptr; a.out_val = out.val.ptr;
-      a.pool_top = c->counters.ptr; a.pool_cap = cap; a.out_off = out.bp_off.ptr; a.out_nnz = out.nnz.ptr;
-      a.status = (int*)(c->counters.ptr + 2);
-      {  // dense tiles, one per sequence
-        std::vector<uint64_t> toff(n);
-        uint64_t cells = 0;
-        for (uint32_t x = 0; x < n; ++x) { toff[x] = cells; cells += (uint64_t)c->len[x] * c->len[x]; }
-        if ((rc = c->scratch.reserve(cells + 64))) return rc;
-        if ((rc = c->work.reserve((size_t)n * 8 + 256))) return rc;
-        if ((rc = c->work2.reserve((size_t)n * 4 + 256))) return rc;
-        if (hip_check(hipMemcpyAsync(c->work.ptr, toff.data(), (size_t)n * 8, hipMemcpyHostToDevice, c->stream))) return DAFS_HIP_ELAUNCH;
-        if (hip_check(hipStreamSynchronize(c->stream))) return DAFS_HIP_ELAUNCH;
-        a.tile = c->scratch.ptr; a.tile_off = (const uint64_t*)c->work.ptr; a.sum_w = (float*)c->work2.ptr;
-      }
-      if ((rc = pct_bp_launch(a, max_len, c->stream))) return rc;
-      unsigned long long h[4];
-      if (hip_check(hipMemcpyAsync(h, c->counters.ptr, sizeof h, hipMemcpyDeviceToHost, c->stream))) return DAFS_HIP_ELAUNCH;
-      if (hip_check(hipStreamSynchronize(c->stream))) return DAFS_HIP_ELAUNCH;
-      const int status = (int)(h[2] & 0xffffffffu);
-      if (status == 0) { out.total_nnz = h[0]; out.valid = true; break; }
-      if (status != DAFS_HIP_EOVERFLOW || attempt >= 4) return status;
-      cap = std::max<uint64_t>(h[0], cap * 2);
-    }
-    c->cur_bp = 1;
-  }
-
+  if ((which & 1) && w_pct_s != 0.0f && (rc = consistency_bp(c, mpv, w_pct_s))) return rc;
   if (which & 2) c->cur_mp = 0;
-  if ((which & 2) && w_pct_a != 0.0f) {
-    mp_store& out = c->mp[1];
-    out.valid = false;
-    out.listed = list != nullptr;
-    out.listed_pairs = plist;
-    out.n_tasks = all;
-    out.pair_x = raw.pair_x;
-    out.pair_y = raw.pair_y;
-    out.rp_by_pair = raw.rp_by_pair;
-    out.rp_total = raw.rp_total;
-    out.task_of_pair.resize(all);
-    for (uint64_t p = 0; p < all; ++p) out.task_of_pair[p] = (uint32_t)p;
-    if ((rc = out.d_task_of_pair.upload(out.task_of_pair.data(), all, c->stream))) return rc;
-    if ((rc = out.rp_off.upload(out.rp_by_pair.data(), all, c->stream))) return rc;
-    if ((rc = out.rowptr_pool.reserve(out.rp_total))) return rc;
-    if ((rc = out.pair_off.reserve(all))) return rc;
-    if ((rc = out.pair_nnz.reserve(all))) return rc;
-    if ((rc = c->d_pair_x.upload(raw.pair_x.data(), all, c->stream))) return rc;
-    if ((rc = c->d_pair_y.upload(raw.pair_y.data(), all, c->stream))) return rc;
-    if (list && (rc = c->pct_list.upload(plist.data(), nlist, c->stream))) return rc;
-    uint64_t cap = std::max<uint64_t>(raw.pool_used * 2 + 1024, out.pool_cap_hint);
-    for (int attempt = 0;; ++attempt) {
-      if ((rc = out.col.reserve(cap))) return rc;
-      if ((rc = out.val.reserve(cap))) return rc;
-      if (hip_check(hipMemsetAsync(c->counters.ptr, 0, 4 * sizeof(unsigned long long), c->stream))) return DAFS_HIP_ELAUNCH;
-      if (shard) {  // pairs outside the shard: no entries, all row pointers 0
-        if (hip_check(hipMemsetAsync(out.rowptr_pool.ptr, 0, out.rp_total * sizeof(uint32_t), c->stream))) return DAFS_HIP_ELAUNCH;
-        if (hip_check(hipMemsetAsync(out.pair_off.ptr, 0, all * sizeof(uint64_t), c->stream))) return DAFS_HIP_ELAUNCH;
-        if (hip_check(hipMemsetAsync(out.pair_nnz.ptr, 0, all * sizeof(uint32_t), c->stream))) return DAFS_HIP_ELAUNCH;
-      }
-      pct_match_args a;
-      memset(&a, 0, sizeof a);
-      a.in = mpv; a.sim = c->d_sim.ptr; a.pair_x = c->d_pair_x.ptr; a.pair_y = c->d_pair_y.ptr;
-      a.pair_list = list ? c->pct_list.ptr : nullptr;
-      a.npairs = (uint32_t)all; a.w_pct = w_pct_a;
-      a.rp_off = out.rp_off.ptr; a.rowptr_pool = out.rowptr_pool.ptr; a.col = out.col.ptr; a.val = out.val.ptr;
-      a.pool_top = c->counters.ptr; a.pool_cap = cap; a.pair_off = out.pair_off.ptr; a.pair_nnz = out.pair_nnz.ptr;
-      a.status = (int*)(c->counters.ptr + 2);
-      if (fourway) { a.bp = c->bp[0].view(); a.w_f = w_pct_a; }
-      // dense row tiles, in batches of at most kTileFloats; the tile memory is the pair kernels' scratch
-      const uint64_t kTileFloats = 1ull << 31;  // 8 GiB
-      for (uint64_t p0 = pair_begin; p0 < pair_end;) {
-        std::vector<uint64_t> toff;
-        uint64_t cells = 0, p1 = p0;
-        while (p1 < pair_end) {
-          const uint64_t pr = list ? plist[p1] : p1;
-          const uint64_t need = (uint64_t)c->len[raw.pair_x[pr]] * c->len[raw.pair_y[pr]];
-          if (p1 > p0 && cells + need > kTileFloats) break;
-          toff.push_back(cells);
-          cells += need;
-          ++p1;
-        }
-        if ((rc = c->scratch.reserve(cells + 64))) return rc;
-        const size_t cnt = (size_t)(p1 - p0);
-        if ((rc = c->work.reserve(cnt * 8 + 256))) return rc;
-        if ((rc = c->work2.reserve(cnt * 4 + 256))) return rc;
-        if (hip_check(hipMemcpyAsync(c->work.ptr, toff.data(), cnt * 8, hipMemcpyHostToDevice, c->stream))) return DAFS_HIP_ELAUNCH;
-        if (hip_check(hipStreamSynchronize(c->stream))) return DAFS_HIP_ELAUNCH;  // toff dies at the end of the scope
-        a.tile = c->scratch.ptr; a.tile_off = (const uint64_t*)c->work.ptr; a.sum_w = (float*)c->work2.ptr;
-        a.wg_task = nullptr; a.wg_tasks = 0;
-        // DAFS_HIP_PCT_YORDER=1 (tuning aid): workgroups ordered by (y, row block, x) and dealt to the XCDs in contiguous ranges.
-        // Measured slower than the plain 2-D grid (N=128: 13.3 against 12.8 ms for the stage, N=256: 135 against 120): the
-        // gathers are not what binds the kernel, so the default stays the 2-D grid.  A pair list always takes the 2-D grid.
-        if (!fourway && !list && getenv("DAFS_HIP_PCT_YORDER")) {
-          std::vector<uint2> order;
-          pct_task_order(raw.pair_x.data(), raw.pair_y.data(), c->len.data(), n, p0, (uint32_t)cnt, order);
-          if ((rc = c->pct_tasks.upload(order.data(), order.size(), c->stream))) return rc;  // synchronises
-          a.wg_task = c->pct_tasks.ptr; a.wg_tasks = (uint32_t)order.size();
-        }
-        if ((rc = fourway ? pct_fourway_launch(a, max_len, (uint32_t)p0, (uint32_t)cnt, c->stream)
-                          : pct_match_launch(a, max_len, (uint32_t)p0, (uint32_t)cnt, c->stream))) return rc;
-        p0 = p1;
-      }
-      unsigned long long h[4];
-      if (hip_check(hipMemcpyAsync(h, c->counters.ptr, sizeof h, hipMemcpyDeviceToHost, c->stream))) return DAFS_HIP_ELAUNCH;
-      if (hip_check(hipStreamSynchronize(c->stream))) return DAFS_HIP_ELAUNCH;
-      const int status = (int)(h[2] & 0xffffffffu);
-      if (status == 0) { out.pool_used = h[0]; out.pool_cap_hint = cap; out.valid = true; break; }
-      if (status != DAFS_HIP_EOVERFLOW || attempt >= 4) return status;
-      cap = std::max<uint64_t>(h[0], cap * 2);
-    }
-    c->cur_mp = 1;
-  }
+  if ((which & 2) && w_pct_a != 0.0f && (rc = consistency_match(c, mpv, w_pct_a, pair_begin, pair_end, fourway, list != nullptr, plist))) return rc;
   return DAFS_HIP_OK;
 }
 

@@ -5,13 +5,14 @@
 //
 // Both are sparse triple loops that accumulate float products into a dense per-output matrix in a
 // fixed order (z, then k ascending).  Bit-exact parity needs every cell to receive its addends in
-// that order, so the work is split by OUTPUT ROW: one workgroup owns one output matrix, keeps a
-// tile of it in LDS, and each thread owns whole rows of the tile -- it walks the reference's
-// (z, k) order itself, so no atomics and no reduction tree are involved.  The tile is as many rows
-// as fit in LDS; when an output needs several tiles the transform is computed twice (count,
-// reserve pool space, then recompute and emit), single-tile outputs emit straight from LDS.
-// Output: rows with v > CUTOFF (0.01) as CSR, plus the transposed CSR for the matching matrices,
-// bump-allocated from a pool exactly like k_pairhmm3's.
+// that order, so the work is split by OUTPUT ROW: a group of 16 lanes owns one output row, keeps
+// its accumulator in LDS and walks the reference's (z, k) order itself, so no atomics and no
+// reduction tree are involved.  Four groups share a wavefront, sixteen a workgroup; a workgroup
+// takes a block of 16 rows of one output matrix.  The row kernels (k_pct_rows, k_pct_bp_rows)
+// write finished rows to a dense tile in HBM, once; the emit kernels (k_pct_emit, k_pct_bp_emit),
+// one workgroup per output matrix, turn the tile into the rows with v > CUTOFF (0.01) as CSR,
+// plus the transposed CSR for the matching matrices, bump-allocated from a pool exactly like
+// k_pairhmm3's.  DESIGN 5.4 has the measurements behind this shape.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/dafs_hip.h"
@@ -27,14 +28,14 @@ namespace dafs {
 // ---------------------------------------------------------------------------------------------
 // relax_matching_probability in two kernels.
 //
-// k_pct_rows: one wavefront per output row i of a pair (x,y).  The addends of the row are
+// k_pct_rows: one group of 16 lanes per output row i of a pair (x,y).  The addends of the row are
 //   mp[x][z][i][k] * mp[z][y][k][j] * w_z, added to cell j in the order z, k, j (dafs.cpp:290-318).
-//   For a chunk of 32 sequences z the wave first fetches all rows mp[x][z][i] (one lane per z), then
-//   the row pointers of every mp[z][y][k] they reference (one lane per (z,k) "item"), then the entries
-//   of those rows (one lane per addend), so the pointer chases of a whole chunk overlap; the addends
-//   are applied item by item -- the columns of one item are distinct, so its lanes update the row
-//   accumulator (LDS) together, and consecutive items follow each other in program order.  The
-//   finished row goes to a dense tile in HBM.
+//   For a chunk of 16 sequences z the group first fetches all rows mp[x][z][i] (one lane per z); then,
+//   in rounds of 16 (z,k) "items", the row pointers of the rows mp[z][y][k] they reference (one lane
+//   per item) and the first 16 entries of all 16 of those b-rows (one lane per addend), so the pointer
+//   chases of a round overlap; the addends are applied item by item -- the columns of one item are
+//   distinct, so its lanes update the row accumulator (LDS) together, and consecutive items follow
+//   each other in program order.  The finished row goes to a dense tile in HBM.
 // k_pct_emit: one workgroup per pair turns the tile into the thresholded CSR and transposed CSR
 //   (rows by wavefronts with ballot compaction, columns by threads), bump-allocated like k_pairhmm3's.
 // ---------------------------------------------------------------------------------------------
@@ -56,66 +57,88 @@ struct pct_item {  // one (z, k) of a row, held by one lane of the row's group
   float pik, w;
 };
 
-// Items Q..15 of a round: phase A fetches the first 16 entries of every item's b-row (all loads in flight
-// together), phase B applies the items in order.  Entries of one item have distinct columns, so the lanes
-// of a group update the row accumulator together; the groups of a wavefront are different rows.
 // which of the 16 item slots of a round hold, in some group of the wavefront, a b-row longer than a group (wave-uniform)
 __device__ __forceinline__ uint32_t pct_long_slots(uint32_t n) {
   const unsigned long long m = __ballot(n > 16u);
   return (uint32_t)((m | (m >> 16) | (m >> 32) | (m >> 48)) & 0xFFFFull);
 }
+// The largest of the four groups' values of lane t: the same in every lane of the wavefront where v is the same in every lane
+// of a group.  (The chunk prologues of the two row kernels keep their own copy of this loop, and of the 16-lane scan before it,
+// written out: through a helper the compiler hoists the lane arithmetic of the shuffles in another order, and the kernels,
+// though equal in every opcode count, measured outside the range of the parent's own runs -- DESIGN 5.4.)
+__device__ __forceinline__ uint32_t pct_groups_max(uint32_t v) {
+#pragma unroll
+  for (int o = 16; o < 64; o <<= 1) v = max(v, (uint32_t)__shfl_xor((int)v, o));
+  return v;
+}
 
+// The rest of a b-row longer than a group (its entries from 16 on), applied before the next item: 16 entries a turn, as many
+// turns as the longest such row among the wavefront's four groups needs.  n, pik, w and base are the item's, already broadcast
+// to the group; only columns >= jlo take part.
+__device__ __forceinline__ void pct_long_tail(const pct_gent* base, uint32_t n, float pik, float w, uint32_t t, uint32_t jlo, float* acc) {
+  const uint32_t nmax = pct_groups_max(n);
+  for (uint32_t e0 = 16; e0 < nmax; e0 += 16) {
+    wave_lds_fence();
+    if (e0 + t < n) {
+      const pct_u2 cv = base[e0 + t];
+      if (cv.x >= jlo) acc[cv.x] += pik * __uint_as_float(cv.y) * w;
+    }
+  }
+}
+
+// A round of 16 items is a fetch -- the first 16 entries of every item's b-row, all loads in flight together -- and an apply,
+// item after item.  Entries of one item have distinct columns, so the lanes of a group update the row accumulator together;
+// the groups of a wavefront are different rows.  The round exists in two forms, and both stay:
+//   pct_round  (k_pct_bp_rows) predicates the fetch and the update on t < n, so an item may be {address 0, n = 0} -- which is
+//              what that kernel builds for lanes without an entry -- and takes the lower column bound jlo (i < j);
+//   pct_step   (k_pct_rows) is the lean form below: unpredicated fetch through DPP-folded address arithmetic.  Every item,
+//              also one of length 0, must carry an address that can be read 16 entries far, hence the padded, zeroed pools.
+// Putting k_pct_bp_rows on the lean step would change its speed and its memory-safety argument: not done without measurements.
 template <int Q>
 struct pct_round {
-  static __device__ __forceinline__ void fetch(const uint2* __restrict__ ent, const pct_item& it, int t, uint32_t (&jc)[16], float (&pv)[16]) {
+  static __device__ __forceinline__ void fetch(const pct_item& it, int t, uint32_t (&jc)[16], float (&pv)[16]) {
     const uint32_t n = row_bcast<Q>(it.n), lo = row_bcast<Q>(it.ptr_lo), hi = row_bcast<Q>(it.ptr_hi);
     // column and value in one 8-byte load; the pair leaves the branch as loaded (taking it apart inside would make every
     // load wait for itself) and is taken apart after the last one has been issued
     pct_u2 cv = {lo, hi};  // lanes without an entry keep what is in the registers anyway (never used: apply tests t < n)
     if ((uint32_t)t < n) cv = ((const pct_gent*)(((uint64_t)hi << 32) | lo))[t];
-    pct_round<Q + 1>::fetch(ent, it, t, jc, pv);
+    pct_round<Q + 1>::fetch(it, t, jc, pv);
     jc[Q] = cv.x; pv[Q] = __uint_as_float(cv.y);
   }
   // jlo: only columns >= jlo take part (the base-pair transform keeps i < j)
-  static __device__ __forceinline__ void apply(const uint2* __restrict__ ent, const pct_item& it, int t, uint32_t jlo, const uint32_t (&jc)[16],
-                                               const float (&pv)[16], float* acc, uint32_t longq) {
+  static __device__ __forceinline__ void apply(const pct_item& it, int t, uint32_t jlo, const uint32_t (&jc)[16], const float (&pv)[16], float* acc,
+                                               uint32_t longq) {
     const uint32_t n = row_bcast<Q>(it.n);
     const float pik = row_bcastf<Q>(it.pik), w = row_bcastf<Q>(it.w);
     if ((uint32_t)t < n && jc[Q] >= jlo) acc[jc[Q]] += pik * pv[Q] * w;  // dafs.cpp:300 / :308 / :316, :359 / :368
-    if (longq & (1u << Q)) {  // (scalar) a b-row longer than the group: the rest of it, before the next item
+    if (longq & (1u << Q)) {  // (scalar)
       const uint32_t lo = row_bcast<Q>(it.ptr_lo), hi = row_bcast<Q>(it.ptr_hi);
-      const pct_gent* base = (const pct_gent*)(((uint64_t)hi << 32) | lo);
-      uint32_t nmax = n;
-#pragma unroll
-      for (int o = 16; o < 64; o <<= 1) nmax = max(nmax, (uint32_t)__shfl_xor((int)nmax, o));
-      for (uint32_t e0 = 16; e0 < nmax; e0 += 16) {
-        wave_lds_fence();
-        if (e0 + (uint32_t)t < n) {
-          const pct_u2 cv = base[e0 + (uint32_t)t];
-          if (cv.x >= jlo) acc[cv.x] += pik * __uint_as_float(cv.y) * w;
-        }
-      }
+      pct_long_tail((const pct_gent*)(((uint64_t)hi << 32) | lo), n, pik, w, (uint32_t)t, jlo, acc);
     }
     wave_lds_fence();
-    pct_round<Q + 1>::apply(ent, it, t, jlo, jc, pv, acc, longq);
+    pct_round<Q + 1>::apply(it, t, jlo, jc, pv, acc, longq);
   }
 };
 template <>
 struct pct_round<16> {
-  static __device__ __forceinline__ void fetch(const uint2*, const pct_item&, int, uint32_t (&)[16], float (&)[16]) {}
-  static __device__ __forceinline__ void apply(const uint2*, const pct_item&, int, uint32_t, const uint32_t (&)[16], const float (&)[16], float*, uint32_t) {}
+  static __device__ __forceinline__ void fetch(const pct_item&, int, uint32_t (&)[16], float (&)[16]) {}
+  static __device__ __forceinline__ void apply(const pct_item&, int, uint32_t, const uint32_t (&)[16], const float (&)[16], float*, uint32_t) {}
 };
 
-// ---- round 3: the lean step ----------------------------------------------------------------------------------------
+// ---- the lean step ----------------------------------------------------------------------------------------------------
 // k_pct_rows is bound by vector issue (profiles/r02_j: 4.7 G VALU wave-instructions for 6.1 G addends) and the steps of
-// a round were 14 VALU instructions each: three broadcasts for the fetch, three for the apply, two compares with their
+// pct_round are 14 VALU instructions each: three broadcasts for the fetch, three for the apply, two compares with their
 // exec juggling, 64-bit address arithmetic.  Here a step is 8:
 //   fetch  address of entry t = item's byte address + 8 t as v_add_co / v_addc_co with the DPP broadcast folded into the
 //          operand (no v_mov_dpp); the load is NOT predicated -- lanes beyond the item's length read the entries that follow
-//          in the pool (the pools are padded by 16 entries), which costs no additional cache line
-//   apply  column = item length > t ? loaded column : the lane's own trash cell behind the row (one v_cmp_dpp + v_cndmask:
-//          no exec change, hence no exec-write -> DPP hazard stalls), two v_mul_f32_dpp (p_ik and w_z arrive through the DPP
-//          operand), address, LDS read, add, LDS write.
+//          in the pool, which costs no additional cache line.  So every pool the items point into has 32 entries of slack
+//          behind it (mp_ent2 and ident2, consistency_parts), and the slack of mp_ent2 is zeroed: a lane without an item
+//          prepares item 0 of its chunk again, which can be the first slack entry, and uses that entry's first word as the
+//          row k of its row-pointer load ("The slack behind the interleaved copy is zeroed").
+//   apply  lane predicate = item length > t, as the borrow of a v_sub_co_u32_dpp (pct_sel_bc), two v_mul_f32_dpp (p_ik and
+//          w_z arrive through the DPP operand); only the lanes with an entry do the LDS read, add, LDS write.
+// Measured and dropped: every lane updating a cell, the ones without an entry a trash cell of their own behind
+// the row, took the same time with more bank-conflict cycles; a predicated fetch took the same time.
 // The DPP operands are inline assembly (the compiler does not fold v_mov_dpp row_newbcast into its users); "s_nop 1" in
 // front keeps the VALU-write -> DPP-read distance whatever the scheduler puts before the block.
 template <int Q>
@@ -142,72 +165,54 @@ __device__ __forceinline__ uint64_t pct_addr_bc(uint32_t lo_item, uint32_t hi_it
   return ((uint64_t)hi << 32) | lo;
 }
 
-#ifndef PCT_TRASH_CELLS
-#define PCT_TRASH_CELLS 0
-#endif
-#ifndef PCT_FETCH_ALL
-#define PCT_FETCH_ALL 1  // 1: unpredicated fetch (two VALU instructions fewer per step; 0, predicated, measures the same: the kernel is issue-bound, not line-bound)
-#endif
 template <int Q>
 struct pct_step {
-  static __device__ __forceinline__ void fetch(const pct_item& it, uint32_t t8, uint32_t zero, uint32_t trash, pct_u2 (&cv)[16]) {
-#if PCT_FETCH_ALL
+  static __device__ __forceinline__ void fetch(const pct_item& it, uint32_t t8, uint32_t zero, pct_u2 (&cv)[16]) {
     cv[Q] = *(const pct_gent*)pct_addr_bc<Q>(it.ptr_lo, it.ptr_hi, t8, zero);
-#else
-    // only the lanes that have an entry load: a 16-lane span behind a row's start crosses a 128-byte line far more often than
-    // the row's own ~6 entries do, and the kernel is bound by the line requests its gathers make
-    const uint64_t adr = pct_addr_bc<Q>(it.ptr_lo, it.ptr_hi, t8, zero);
-    pct_u2 e = {trash, 0u};
-    if (pct_sel_bc<Q>(it.n, (t8 >> 3) + 1u, 1u, 0u)) e = *(const pct_gent*)adr;
-    cv[Q] = e;
-#endif
-    pct_step<Q + 1>::fetch(it, t8, zero, trash, cv);
+    pct_step<Q + 1>::fetch(it, t8, zero, cv);
   }
-  static __device__ __forceinline__ void apply(const pct_item& it, uint32_t t, uint32_t trash, const pct_u2 (&cv)[16], float* acc, uint32_t longq) {
+  static __device__ __forceinline__ void apply(const pct_item& it, uint32_t t, const pct_u2 (&cv)[16], float* acc, uint32_t longq) {
     const float v = pct_mul_bc<Q>(it.w, pct_mul_bc<Q>(it.pik, __uint_as_float(cv[Q].y)));  // (p_ik * p_kj) * w_z, dafs.cpp:300 / :308 / :316
-#if PCT_TRASH_CELLS
-    // every lane updates a cell, the ones without an entry their own trash cell: no exec change, but all 64 lanes go through
-    // the LDS, and the LDS is what binds (profiles/r03_a_pct_pmc.json: its pipe is busy 70 % of the kernel, 40 % of that conflicts)
-#if PCT_FETCH_ALL
-    const uint32_t col = pct_sel_bc<Q>(it.n, t + 1u, cv[Q].x, trash);
-#else
-    const uint32_t col = cv[Q].x;  // lanes without an entry carry {their trash cell, 0} from the fetch
-#endif
-    acc[col] += v;
-#else
     if (pct_sel_bc<Q>(it.n, t + 1u, 1u, 0u)) acc[cv[Q].x] += v;  // only the lanes with an entry touch the LDS
-#endif
-    if (longq & (1u << Q)) {  // (scalar, rare) a b-row longer than the group: the rest of it, before the next item
+    if (longq & (1u << Q)) {  // (scalar, rare)
       const uint32_t n = row_bcast<Q>(it.n), lo = row_bcast<Q>(it.ptr_lo), hi = row_bcast<Q>(it.ptr_hi);
-      const float pik = row_bcastf<Q>(it.pik), w = row_bcastf<Q>(it.w);
-      const pct_gent* base = (const pct_gent*)(((uint64_t)hi << 32) | lo);
-      uint32_t nmax = n;
-#pragma unroll
-      for (int o = 16; o < 64; o <<= 1) nmax = max(nmax, (uint32_t)__shfl_xor((int)nmax, o));
-      for (uint32_t e0 = 16; e0 < nmax; e0 += 16) {
-        wave_lds_fence();
-        if (e0 + t < n) {
-          const pct_u2 e = base[e0 + t];
-          acc[e.x] += pik * __uint_as_float(e.y) * w;
-        }
-      }
+      pct_long_tail((const pct_gent*)(((uint64_t)hi << 32) | lo), n, row_bcastf<Q>(it.pik), row_bcastf<Q>(it.w), t, 0u, acc);
     }
     wave_lds_fence();
-    pct_step<Q + 1>::apply(it, t, trash, cv, acc, longq);
+    pct_step<Q + 1>::apply(it, t, cv, acc, longq);
   }
 };
 template <>
 struct pct_step<16> {
-  static __device__ __forceinline__ void fetch(const pct_item&, uint32_t, uint32_t, uint32_t, pct_u2 (&)[16]) {}
-  static __device__ __forceinline__ void apply(const pct_item&, uint32_t, uint32_t, const pct_u2 (&)[16], float*, uint32_t) {}
+  static __device__ __forceinline__ void fetch(const pct_item&, uint32_t, uint32_t, pct_u2 (&)[16]) {}
+  static __device__ __forceinline__ void apply(const pct_item&, uint32_t, const pct_u2 (&)[16], float*, uint32_t) {}
 };
 
-// LDS of one group (= one output row), in words: 16 trash cells behind the accumulator row, then the chunk's bookkeeping
-// (item address bases 16 x 2, exclusive item offsets 20; 16 spare).  row_cap = 28 (mod 32) makes the stride 16 (mod 32):
-// the two rows a 32-lane half updates sit sixteen banks apart (see pct_match_launch).
-#define PCT_TRASH 16
-#define PCT_BOOK_WORDS (16 * 2 + 20 + 16)
-__host__ __device__ static inline size_t pct_group_words(uint32_t row_cap) { return (size_t)row_cap + PCT_TRASH + PCT_BOOK_WORDS; }
+// ---- dynamic LDS of the row kernels -----------------------------------------------------------------------------------
+// First the workgroup's tables per sequence z of the largest family of the launch (max_fam): four 8-byte words and a float,
+// the floats rounded up to an even count.  Then one block per group (= per output row), in 4-byte words:
+//   k_pct_rows     accumulator row [row_cap], padding [PCT_ROW_PAD], item address bases of the 16 z-lanes [16 x 2],
+//                  exclusive item offsets zoff [17, rounded to 20], spare [16]
+//   k_pct_bp_rows  entry bases of the 16 y-lanes [16 x 2], zoff [17, rounded to 20], the lanes' sequences zid [16],
+//                  accumulator row [row_cap]
+// and 64 bytes for alignment.  The four rows a wavefront accumulates sit one block apart, and the two rows of a 32-lane half
+// add into nearly the same 16-column window (rows i and i + 1 of one pair).  With row_cap a multiple of 16 the second row
+// was four banks away from the first: two lanes per bank on almost every update, 1.9 G conflict cycles per 2.3 G LDS
+// instructions at N = 128.  So row_cap is max_len rounded up to the residue mod 32 that makes the stride 16 (mod 32),
+// sixteen banks apart: 28 for k_pct_rows (row_cap + 84), 12 for k_pct_bp_rows (row_cap + 68).  The padding behind
+// k_pct_rows' accumulator row is part of that stride and nothing else: no lane reads or writes it.
+#define PCT_ROW_PAD 16
+#define PCT_BOOK_WORDS (16 * 2 + 20 + 16)  // of either kernel: 16 addresses, zoff, and 16 spare or zid
+__host__ __device__ static inline size_t pct_group_words(uint32_t row_cap) { return (size_t)row_cap + PCT_ROW_PAD + PCT_BOOK_WORDS; }  // k_pct_rows
+__host__ __device__ static inline size_t pct_bp_group_words(uint32_t row_cap) { return PCT_BOOK_WORDS + (size_t)row_cap; }          // k_pct_bp_rows
+static inline size_t pct_lds_bytes(uint32_t max_fam, size_t group_words) {
+  return (size_t)max_fam * 32 + (((size_t)max_fam + 1) & ~(size_t)1) * 4 + (size_t)PCT_ROWS_PER_WG * group_words * 4 + 64;
+}
+#define PCT_MATCH_RESIDUE 28u
+#define PCT_BP_RESIDUE 12u
+static inline uint32_t pct_row_cap(uint32_t max_len, uint32_t residue) { return max_len + ((residue - max_len) & 31u); }
+static size_t pct_match_lds_bytes(uint32_t max_fam, uint32_t row_cap) { return pct_lds_bytes(max_fam, pct_group_words(row_cap)); }
+static size_t pct_bp_lds_bytes(uint32_t max_fam, uint32_t row_cap) { return pct_lds_bytes(max_fam, pct_bp_group_words(row_cap)); }
 
 __global__ __launch_bounds__(256) void k_pct_rows(pct_match_args a, uint32_t pair0, uint32_t row_cap) {
   extern __shared__ unsigned char s_raw[];
@@ -224,9 +229,9 @@ __global__ __launch_bounds__(256) void k_pct_rows(pct_match_args a, uint32_t pai
   uint64_t* b_rp = a_ent + Z;
   uint64_t* b_ent = b_rp + Z;
   float* wz = (float*)(b_ent + Z);
-  // per group (= per output row): the accumulator row, the lanes' trash cells, the a-row bookkeeping of the current chunk
+  // per group (= per output row): the accumulator row, its padding, the a-row bookkeeping of the current chunk
   float* acc = wz + ((Z + 1) & ~1u) + (size_t)gw * pct_group_words(row_cap);
-  uint64_t* zabase = (uint64_t*)(acc + row_cap + PCT_TRASH);  // per z-lane: address of item tl of the chunk = zabase + 8 tl
+  uint64_t* zabase = (uint64_t*)(acc + row_cap + PCT_ROW_PAD);  // per z-lane: address of item tl of the chunk = zabase + 8 tl
   uint32_t* zoff = (uint32_t*)(zabase + 16);                   // exclusive item offsets of the z-lanes (zoff[16] = items of the chunk)
 
   // which (pair, block of 16 rows) this workgroup takes: from the launch's task table (pct_match_launch: ordered so that the
@@ -279,7 +284,7 @@ __global__ __launch_bounds__(256) void k_pct_rows(pct_match_args a, uint32_t pai
 
   const uint32_t i = row0 + (uint32_t)gw;
   const bool rowact = i < L1;
-  const uint32_t t8 = t * 8u, zero = 0u, trash = row_cap + t;
+  const uint32_t t8 = t * 8u, zero = 0u;
   for (uint32_t j = t; j < L2; j += PCT_G) acc[j] = 0.0f;
 
   // One item = one (z, k) of the row: lane tl - w0 of the group prepares item tl of the chunk -- the a-entry (k, p_ik), then
@@ -347,15 +352,54 @@ __global__ __launch_bounds__(256) void k_pct_rows(pct_match_args a, uint32_t pai
     for (uint32_t w0 = 0; w0 < T1max; w0 += PCT_G) {
       const half_item hn = item_a(w0 + PCT_G + t, T1);   // a-entry load of the next round: in flight during this round's fetch
       pct_u2 cv[16];
-      pct_step<0>::fetch(it, t8, zero, trash, cv);
+      pct_step<0>::fetch(it, t8, zero, cv);
       const item_loads qn = item_b_loads(hn);            // its row-pointer load: in flight during this round's apply
-      pct_step<0>::apply(it, t, trash, cv, acc, pct_long_slots(it.n));
+      pct_step<0>::apply(it, t, cv, acc, pct_long_slots(it.n));
       it = item_b_finish(qn);
     }
     wave_lds_fence();
   }
   if (rowact)
     for (uint32_t j = t; j < L2; j += PCT_G) tile[(size_t)i * L2 + j] = acc[j];
+}
+
+// ---- the steps the two emit kernels share (256 threads, four wavefronts; a wavefront takes every fourth row of the tile) ----
+// UPPER: only the columns j > i take part (the base-pair transform's upper triangle).  The block prefix sum stays written out
+// in both kernels, and the loops over j0 around these steps too: as helpers they change the kernels' code.
+
+// A wavefront's step over columns j0 .. j0 + 63 of row i of the L-column tile, lane by column: how many entries the row
+// keeps there (the same in every lane) ...
+template <bool UPPER>
+__device__ __forceinline__ uint32_t pct_seg_count(const float* tile, uint32_t i, uint32_t j0, uint32_t L, float sum_w, int lane) {
+  const uint32_t j = j0 + lane;
+  const bool keep = j < L && (!UPPER || j > i) && tile[(size_t)i * L + j] / sum_w > PCT_CUTOFF;
+  return (uint32_t)__popcll(__ballot(keep));
+}
+// ... and the same step storing them, columns ascending, to col / val from position pos on (ballot compaction)
+template <bool UPPER>
+__device__ __forceinline__ uint32_t pct_seg_store(const float* tile, uint32_t i, uint32_t j0, uint32_t L, float sum_w, int lane, unsigned long long pos,
+                                                  uint32_t* col, float* val) {
+  const uint32_t j = j0 + lane;
+  const float v = j < L ? tile[(size_t)i * L + j] / sum_w : 0.0f;
+  const bool keep = j < L && (!UPPER || j > i) && v > PCT_CUTOFF;
+  const unsigned long long m = __ballot(keep);
+  if (keep) {
+    const unsigned long long q = pos + (uint32_t)__popcll(m & ((1ull << lane) - 1));
+    col[q] = j; val[q] = v;
+  }
+  return (uint32_t)__popcll(m);
+}
+
+// One thread takes n entries of the output pool for its workgroup and leaves their offset and whether they fit in LDS for
+// the others (read after a barrier).  A pool too small is reported through status; the caller then still writes its row
+// pointers, so that the counts are there, but no entry.  Returns the offset.
+__device__ __forceinline__ unsigned long long pct_pool_reserve(unsigned long long n, unsigned long long* pool_top, uint64_t pool_cap, int* status,
+                                                               unsigned long long* s_off, int* s_ok) {
+  const unsigned long long o = atomicAdd(pool_top, n);
+  *s_off = o;
+  *s_ok = (o + n <= pool_cap) ? 1 : 0;
+  if (!*s_ok) atomicExch(status, DAFS_HIP_EOVERFLOW);
+  return o;
 }
 
 __global__ __launch_bounds__(256) void k_pct_emit(pct_match_args a, uint32_t pair0) {
@@ -375,11 +419,7 @@ __global__ __launch_bounds__(256) void k_pct_emit(pct_match_args a, uint32_t pai
   // counts: rows by wavefronts, columns by threads
   for (uint32_t i = (uint32_t)wave; i < L1; i += 4) {
     uint32_t c = 0;
-    for (uint32_t j0 = 0; j0 < L2; j0 += 64) {
-      const uint32_t j = j0 + lane;
-      const bool keep = j < L2 && tile[(size_t)i * L2 + j] / sum_w > PCT_CUTOFF;
-      c += (uint32_t)__popcll(__ballot(keep));
-    }
+    for (uint32_t j0 = 0; j0 < L2; j0 += 64) c += pct_seg_count<false>(tile, i, j0, L2, sum_w, lane);
     if (lane == 0) rowptr[i + 1] = c;
   }
   for (uint32_t j = tid; j < L2; j += nt) {
@@ -409,12 +449,8 @@ __global__ __launch_bounds__(256) void k_pct_emit(pct_match_args a, uint32_t pai
     __syncthreads();
   }
   const uint32_t nnz = rowptr[L1];
-  if (tid == 0) {
-    const unsigned long long o = atomicAdd(a.pool_top, 2ull * nnz);
-    s_off = o;
-    s_ok = (o + 2ull * nnz <= a.pool_cap) ? 1 : 0;
-    if (!s_ok) atomicExch(a.status, DAFS_HIP_EOVERFLOW);
-    a.pair_off[p] = o;
+  if (tid == 0) {  // rows, then transposed rows: 2 nnz entries
+    a.pair_off[p] = pct_pool_reserve(2ull * nnz, a.pool_top, a.pool_cap, a.status, &s_off, &s_ok);
     a.pair_nnz[p] = nnz;
   }
   __syncthreads();
@@ -425,17 +461,7 @@ __global__ __launch_bounds__(256) void k_pct_emit(pct_match_args a, uint32_t pai
   if (!s_ok) return;
   for (uint32_t i = (uint32_t)wave; i < L1; i += 4) {
     unsigned long long pos = off + rowptr[i];
-    for (uint32_t j0 = 0; j0 < L2; j0 += 64) {
-      const uint32_t j = j0 + lane;
-      const float v = j < L2 ? tile[(size_t)i * L2 + j] / sum_w : 0.0f;
-      const bool keep = j < L2 && v > PCT_CUTOFF;
-      const unsigned long long m = __ballot(keep);
-      if (keep) {
-        const unsigned long long q = pos + (uint32_t)__popcll(m & ((1ull << lane) - 1));
-        a.col[q] = j; a.val[q] = v;
-      }
-      pos += (uint32_t)__popcll(m);
-    }
+    for (uint32_t j0 = 0; j0 < L2; j0 += 64) pos += pct_seg_store<false>(tile, i, j0, L2, sum_w, lane, pos, a.col, a.val);
   }
   for (uint32_t j = tid; j < L2; j += nt) {
     unsigned long long pos = off + nnz + colptr[j];
@@ -463,8 +489,8 @@ __global__ __launch_bounds__(256) void k_pct_bp_rows(pct_bp_args a, uint32_t row
   uint64_t* c_rp = a_ent + Z;
   uint64_t* c_ent = c_rp + Z;
   float* wy = (float*)(c_ent + Z);
-  unsigned char* gbase = (unsigned char*)(wy + ((Z + 1) & ~1u)) + (size_t)gw * ((size_t)row_cap * 4 + 16 * 8 + 20 * 4 + 16 * 4);
-  uint64_t* zaent = (uint64_t*)gbase;
+  // per group (= per output row): the bookkeeping of the current chunk, then the accumulator row
+  uint64_t* zaent = (uint64_t*)((unsigned char*)(wy + ((Z + 1) & ~1u)) + (size_t)gw * (pct_bp_group_words(row_cap) * 4));
   uint32_t* zoff = (uint32_t*)(zaent + 16);
   uint32_t* zid = zoff + 20;
   float* acc = (float*)(zid + 16);
@@ -555,10 +581,7 @@ __global__ __launch_bounds__(256) void k_pct_bp_rows(pct_bp_args a, uint32_t row
       // ---- the 16 (y, k) of the round in turn: the entries of bp[y][k] are the items
       for (int q = 0; q < PCT_G; ++q) {
         const uint32_t nb = (uint32_t)__shfl((int)my_nb, q, PCT_G);
-        uint32_t nbmax = nb;
-#pragma unroll
-        for (int o = 16; o < 64; o <<= 1) nbmax = max(nbmax, (uint32_t)__shfl_xor((int)nbmax, o));
-        nbmax = __builtin_amdgcn_readfirstlane(nbmax);
+        const uint32_t nbmax = __builtin_amdgcn_readfirstlane(pct_groups_max(nb));
         if (nbmax == 0) continue;
         const uint32_t yq = (uint32_t)__shfl((int)my_y, q, PCT_G);
         const float pik = __shfl(my_pik, q, PCT_G);
@@ -583,8 +606,8 @@ __global__ __launch_bounds__(256) void k_pct_bp_rows(pct_bp_args a, uint32_t row
           }
           uint32_t jc[16];
           float pv[16];
-          pct_round<0>::fetch(a.mp.ent2, it, t, jc, pv);
-          pct_round<0>::apply(a.mp.ent2, it, t, i + 1, jc, pv, acc, pct_long_slots(it.n));
+          pct_round<0>::fetch(it, t, jc, pv);
+          pct_round<0>::apply(it, t, i + 1, jc, pv, acc, pct_long_slots(it.n));
         }
       }
     }
@@ -609,16 +632,12 @@ __global__ __launch_bounds__(256) void k_pct_bp_emit(pct_bp_args a) {
   const float sum_w = a.sum_w[x];
   for (uint32_t i = (uint32_t)wave; i < L1; i += 4) {
     uint32_t c = 0;
-    for (uint32_t j0 = 0; j0 < L1; j0 += 64) {
-      const uint32_t j = j0 + lane;
-      const bool keep = j < L1 && j > i && tile[(size_t)i * L1 + j] / sum_w > PCT_CUTOFF;
-      c += (uint32_t)__popcll(__ballot(keep));
-    }
+    for (uint32_t j0 = 0; j0 < L1; j0 += 64) c += pct_seg_count<true>(tile, i, j0, L1, sum_w, lane);
     if (lane == 0) rowptr[i + 1] = c;
   }
   if (tid == 0) rowptr[0] = 0;
   __syncthreads();
-  {
+  {  // inclusive prefix sum in LDS, as in k_pct_emit
     uint32_t* arr = rowptr + 1;
     const uint32_t n = L1;
     const uint32_t chunk = (n + nt - 1) / nt;
@@ -638,11 +657,7 @@ __global__ __launch_bounds__(256) void k_pct_bp_emit(pct_bp_args a) {
   }
   if (tid == 0) {
     const uint32_t n = rowptr[L1];
-    const unsigned long long o = atomicAdd(a.pool_top, (unsigned long long)n);
-    s_off = o;
-    s_ok = (o + n <= a.pool_cap) ? 1 : 0;
-    if (!s_ok) atomicExch(a.status, DAFS_HIP_EOVERFLOW);
-    a.out_off[x] = o;
+    a.out_off[x] = pct_pool_reserve(n, a.pool_top, a.pool_cap, a.status, &s_off, &s_ok);
     a.out_nnz[x] = n;
   }
   __syncthreads();
@@ -652,17 +667,7 @@ __global__ __launch_bounds__(256) void k_pct_bp_emit(pct_bp_args a) {
   if (!s_ok) return;
   for (uint32_t i = (uint32_t)wave; i < L1; i += 4) {
     unsigned long long pos = off + rowptr[i];
-    for (uint32_t j0 = 0; j0 < L1; j0 += 64) {
-      const uint32_t j = j0 + lane;
-      const float v = j < L1 ? tile[(size_t)i * L1 + j] / sum_w : 0.0f;
-      const bool keep = j < L1 && j > i && v > PCT_CUTOFF;
-      const unsigned long long m = __ballot(keep);
-      if (keep) {
-        const unsigned long long q = pos + (uint32_t)__popcll(m & ((1ull << lane) - 1));
-        a.out_col[q] = j; a.out_val[q] = v;
-      }
-      pos += (uint32_t)__popcll(m);
-    }
+    for (uint32_t j0 = 0; j0 < L1; j0 += 64) pos += pct_seg_store<true>(tile, i, j0, L1, sum_w, lane, pos, a.out_col, a.out_val);
   }
 }
 
@@ -716,16 +721,6 @@ int mp_sim_launch(mp_store_dev in, const uint32_t* pair_x, const uint32_t* pair_
 
 static const size_t kPctLdsBytes = 150 * 1024;  // leave room for the static LDS and alignment
 
-// The per-z (per-y) tables take 36 bytes per sequence of the largest family of the launch (max_fam), not of the context.
-size_t pct_rows_lds_bytes(uint32_t max_fam, uint32_t row_cap) {
-  return (size_t)max_fam * 32 + (((size_t)max_fam + 1) & ~(size_t)1) * 4 + (size_t)PCT_ROWS_PER_WG * ((size_t)row_cap * 4 + 16 * 8 + 20 * 4 + 16 * 4) + 64;
-}
-// k_pct_rows (round 3 layout: trash cells behind every accumulator row)
-size_t pct_rows2_lds_bytes(uint32_t max_fam, uint32_t row_cap) {
-  return (size_t)max_fam * 32 + (((size_t)max_fam + 1) & ~(size_t)1) * 4 + (size_t)PCT_ROWS_PER_WG * pct_group_words(row_cap) * 4 + 64;
-}
-
-// pairs [pair0, pair0 + count) whose tiles (a.tile, a.tile_off, a.sum_w) have been laid out by the caller
 // ---------------------------------------------------------------------------------------------
 // DAFS::relax_fourway_consistency, reference src/dafs.cpp:377-444 (option -f): every entry (a, b) of mp[x][y] becomes
 //   p_ab (1 - w)  +  w * sum over base pairs (a, j) of x, (b, l) of y with (j, l) in mp[x][y] of  p_aj p_bl p_jl
@@ -824,14 +819,11 @@ int pct_fourway_launch(pct_match_args a, uint32_t max_len, uint32_t pair0, uint3
   return hip_check(hipGetLastError()) ? DAFS_HIP_ELAUNCH : DAFS_HIP_OK;
 }
 
+// pairs [pair0, pair0 + count) whose tiles (a.tile, a.tile_off, a.sum_w) have been laid out by the caller
 int pct_match_launch(pct_match_args a, uint32_t max_len, uint32_t pair0, uint32_t count, hipStream_t st) {
   if (!count) return DAFS_HIP_OK;
-  // The four rows a wavefront accumulates sit pct_group_words(row_cap) = row_cap + 84 words apart in LDS, and the two rows
-  // of a 32-lane half add into nearly the same 16-column window (rows i and i+1 of one pair): row_cap = 28 (mod 32) puts the
-  // second row sixteen banks away from the first (four banks away: two lanes per bank on almost every update -- 1.9 G
-  // conflict cycles per 2.3 G LDS instructions at N = 128).
-  const uint32_t row_cap = max_len + ((28u - max_len) & 31u);
-  const size_t lds = pct_rows2_lds_bytes(a.in.max_fam, row_cap);
+  const uint32_t row_cap = pct_row_cap(max_len, PCT_MATCH_RESIDUE);
+  const size_t lds = pct_match_lds_bytes(a.in.max_fam, row_cap);
   if (lds > kPctLdsBytes) return DAFS_HIP_ETOOLONG;
   a.max_len = max_len;
   static bool attr[16] = {false};
@@ -847,12 +839,8 @@ int pct_match_launch(pct_match_args a, uint32_t max_len, uint32_t pair0, uint32_
 }
 
 int pct_bp_launch(pct_bp_args a, uint32_t max_len, hipStream_t st) {
-  // The four rows a wavefront accumulates sit row_cap + 68 words apart in LDS, and the two rows of a 32-lane half
-  // add into nearly the same 16-column window (rows i and i+1 of one pair): row_cap = 12 (mod 32) puts the second row
-  // sixteen banks away from the first (a multiple of 16, as before, put it four banks away: two lanes per bank on
-  // almost every update -- 1.9 G conflict cycles per 2.3 G LDS instructions at N = 128).
-  const uint32_t row_cap = max_len + ((12u - max_len) & 31u);
-  const size_t lds = pct_rows_lds_bytes(a.mp.max_fam, row_cap);
+  const uint32_t row_cap = pct_row_cap(max_len, PCT_BP_RESIDUE);
+  const size_t lds = pct_bp_lds_bytes(a.mp.max_fam, row_cap);
   if (lds > kPctLdsBytes) return DAFS_HIP_ETOOLONG;
   a.max_len = max_len;
   static bool attr[16] = {false};

@@ -111,7 +111,7 @@ def test_wide(oracle, make):
 
 
 def test_limits_are_the_kernels():
-    """MATCH_TOP and BP_TOP restate pct_rows2_lds_bytes / pct_rows_lds_bytes with the row_cap of pct_match_launch /
+    """MATCH_TOP and BP_TOP restate pct_match_lds_bytes / pct_bp_lds_bytes with the row_cap of pct_match_launch /
     pct_bp_launch (pct.hip) for a family of three against kPctLdsBytes = 150 KiB"""
     def match_bytes(L, fam=3):
         row_cap = L + ((28 - L) & 31)
@@ -132,14 +132,14 @@ def test_overflow(oracle):
     ref = pc.reference(oracle, case)
     nnz_in = sum(_nnz(m) for m in case.mps.values())
     nnz_out = sum(_nnz(ref.mp[p]) for p in case.pairs)
-    # capi_pct.cpp, consistency_parts: `uint64_t cap = std::max<uint64_t>(raw.pool_used * 2 + 1024, out.pool_cap_hint);`
+    # capi_pct.cpp, consistency_match: `uint64_t cap = std::max<uint64_t>(raw.pool_used * 2 + 1024, out.pool_cap_hint);`
     # (pool_used counts every entry twice, rows and transposed rows, and so does k_pct_emit's 2 * nnz; a fresh context's hint is 0)
     first_mp = 2 * (2 * nnz_in) + 1024
     assert (nnz_in, nnz_out) == (8000, 24000)
     assert 2 * nnz_out > first_mp, "the matching pool's first guess holds the result: the case needs resizing"
     bp_in = sum(_nnz(b) for b in case.bps)
     bp_out = sum(_nnz(b) for b in ref.bp)
-    # capi_pct.cpp, consistency_parts: `uint64_t cap = std::max<uint64_t>(4 * in.total_nnz + 1024, 16ull * c->off[n]);`
+    # capi_pct.cpp, consistency_bp: `uint64_t cap = std::max<uint64_t>(4 * in.total_nnz + 1024, 16ull * c->off[n]);`
     first_bp = max(4 * bp_in + 1024, 16 * sum(case.lens))
     assert (bp_in, bp_out) == (12, 4680)
     assert bp_out > first_bp, "the base-pairing pool's first guess holds the result: the case needs resizing"

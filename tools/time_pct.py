@@ -8,9 +8,13 @@ recs = synth.family_set(n, L, seed=12346) if fam else synth.random_set(n, L, see
 seqs = [r[1] for r in recs]
 ctx = capi.Context(0)
 ctx.set_sequences(seqs)
+stages = bool(os.environ.get("STAGES"))  # STAGES=1: also the device time of every k_pct_* kernel (dafs_hip_stage_timing)
+ctx.stage_timing(stages)
 for rep in range(int(os.environ.get("REPS", "2"))):
     t = [time.perf_counter()]
     ctx.fold_posteriors(0.01); t.append(time.perf_counter())
     ctx.align_posteriors(fetch=False, model=model) if model else ctx.align_posteriors(fetch=False); t.append(time.perf_counter())
     sim = ctx.sim(); ctx.consistency(0.25, 0.25); t.append(time.perf_counter())
     print("fold %.1f | pair %.1f | pct %.1f ms" % tuple(1e3 * (b - a) for a, b in zip(t, t[1:])), flush=True)
+    if stages:
+        print(" ".join("%s %.4f" % (k, v[0]) for k, v in sorted(ctx.stage_report().items()) if k.startswith("k_pct")), flush=True)
