@@ -42,6 +42,10 @@ class DdNodePlan(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("lds_flags", "fold_fast", "nw_w", "lds", "split_lds", "s_x", "s_y", "s_xs", "s_ys")]
 
 
+class ContrafoldPlan(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("threads", "cell_waves", "use_ring", "pool_floats", "pool_bufs", "lds", "static_lds")]
+
+
 class Pairhmm3Model(C.Structure):
     _fields_ = [("init", C.c_float * 3), ("trans", (C.c_float * 3) * 3), ("match", (C.c_float * 8) * 7),
                 ("ins", C.c_float * 8)]
@@ -329,6 +333,7 @@ pairhmm5_default_model = _sig("dafs_hip_pairhmm5_default_model", None, [C.POINTE
 residue_code = _sig("dafs_hip_residue_code", C.c_uint8, [C.c_char])
 dd_node_plan = _sig("dafs_hipk_dd_node_plan", C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(DdNodePlan)])
 dd_lds_words = _sig("dafs_hipk_dd_lds_words", C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int])
+contrafold_plan = _sig("dafs_hipk_contrafold_plan", C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(ContrafoldPlan)])
 
 
 def check(rc):

@@ -53,7 +53,8 @@ struct cf_ctx {  // per-workgroup view
   const int* plist;
   const int* pcnt;
   CF_LDS float* ring;    // LDS ring of the last 33 spans of FC (inside) / FCo (outside): ring[(span % 33)*(L+1) + row]
-  bool has_ring;         // false: no room for it (sequences beyond ~540 nt), FC/FCo are read from HBM/L2.  Kept as a flag: the
+  bool has_ring;         // false: the plan gave its room to the term pool (batches whose longest sequence is beyond ~260 nt, see
+                         // dafs_hipk_contrafold_plan), FC/FCo are read from HBM/L2.  Kept as a flag: the
                          // null of the LDS address space is not the generic null, a pointer test after the cast is a trap
   const cf_params* P;    // score tables (LDS copy)
   bool free;             // no constraint string: every map entry is -1 and cum is all zero, the lookups are skipped
@@ -619,8 +620,11 @@ __global__ __launch_bounds__(CF_FOLD_THREADS) void k_contrafold(cf_batch B, int 
     for (int i = 1; i <= L; ++i) { run += (map[i] == -1 || map[i] == 0) ? 0 : 1; cum[i] = run; }
     cum[L + 1] = run;
   }
-  if (tid >= 64 && tid < 68) {  // partner list of symbol y: positions whose symbol pairs with y
-    const int y = tid - 64;
+  // partner list of symbol y: positions whose symbol pairs with y.  Four lanes of the second wavefront, beside lane 0 of the
+  // first; a workgroup of one wavefront (DAFS_HIP_CF_THREADS=64) has no second, its lanes 0..3 build them
+  const int pl0 = nt > 64 ? 64 : 0;
+  if (tid >= pl0 && tid < pl0 + 4) {
+    const int y = tid - pl0;
     int n = 0;
     pcnt[y * (L + 2)] = 0;
     for (int q = 1; q <= L; ++q) {
@@ -885,20 +889,29 @@ __global__ __launch_bounds__(256) void k_bp_compact_levels(cf_batch B, float th,
   }
 }
 
-int contrafold_launch(const cf_batch& B, uint32_t nseq, uint32_t max_len, hipStream_t st) {
-  if (!nseq) return DAFS_HIP_OK;
-  const size_t ints = (size_t)CF_INTS(max_len) * sizeof(int);
-  const size_t ring = (size_t)CF_RING * (max_len + 1) * sizeof(float);
-  const size_t budget = 100 * 1024;  // dynamic LDS (static: score tables ~11 KB)
+constexpr size_t kCfDynBudget = 100 * 1024;      // integer tables and ring of k_contrafold; the most k_contrafold_posterior asks for
+constexpr size_t kCfLdsTotal = 160 * 1024 - 512;  // static + dynamic LDS of k_contrafold
+
+}  // namespace dafs
+
+// The launch plan of k_contrafold, stated once: contrafold_launch takes every decision from here.
+extern "C" int dafs_hipk_contrafold_plan(uint32_t max_len, uint32_t static_lds, dafs_contrafold_plan* out) {
+  using namespace dafs;
+  if (!out) return DAFS_HIP_EINVAL;
+  const size_t ints = CF_INTS((size_t)max_len) * sizeof(int);
+  const size_t ring = (size_t)CF_RING * ((size_t)max_len + 1) * sizeof(float);
+  const size_t budget = kCfDynBudget;  // dynamic LDS (static: score tables ~11 KB)
   if (ints > budget) return DAFS_HIP_ETOOLONG;
   // What the CU's LDS is split into, behind the kernel's static tables: the integer side tables (always), the term pool and
   // the ring of recent FC spans.  The pool comes first: it is what takes the term evaluation out of the chains; the
   // ring only shortens the FC reads of that evaluation, which the whole workgroup issues in parallel anyway.  So the
   // ring is kept when a pool of ~80 terms per row (the demand of a random sequence: 3/8 of the cells close a pair,
-  // ~150 terms each) still fits beside it, and dropped otherwise (from ~330 nt on).
-  size_t stat = 28 * 1024;  // static LDS of k_contrafold (score tables, log-sum-exp tables)
-  const size_t total = 160 * 1024 - 512;
-  {
+  // ~150 terms each) still fits beside it, and dropped otherwise (from 260 nt on at 28 KB of static LDS).  Two pool
+  // buffers go first (below), from 161 nt on; past 2040 nt not even a pool of two longest lists is left.
+  size_t stat = static_lds;  // static LDS of k_contrafold (score tables, log-sum-exp tables)
+  const size_t total = kCfLdsTotal;
+  if (!stat) {
+    stat = 28 * 1024;
     hipFuncAttributes at;
     if (hipFuncGetAttributes(&at, (const void*)k_contrafold) == hipSuccess) stat = at.sharedSizeBytes;
     else (void)hipGetLastError();
@@ -922,16 +935,34 @@ int contrafold_launch(const cf_batch& B, uint32_t nseq, uint32_t max_len, hipStr
     const int v = atoi(e);
     if (v >= 1 && v <= CF_FOLD_THREADS / 64) cell_waves = v;
   }
-  const size_t optin = total - stat;  // the most dynamic LDS a launch may ask for
-  static bool attr_a[16] = {false}, attr_b[16] = {false};
-  if (!lds_optin_once((const void*)k_contrafold, (int)optin, attr_a)) return DAFS_HIP_ELAUNCH;
-  if (!lds_optin_once((const void*)k_contrafold_posterior, (int)budget, attr_b)) return DAFS_HIP_ELAUNCH;
   int fold_threads = CF_FOLD_THREADS;
   if (const char* e = getenv("DAFS_HIP_CF_THREADS")) {  // tuning aid: 64..1024 in whole wavefronts
     const int v = atoi(e);
     if (v >= 64 && v <= CF_FOLD_THREADS && v % 64 == 0) fold_threads = v;
   }
-  STAGE_LAUNCH(ST_CONTRAFOLD, st) hipLaunchKernelGGL(k_contrafold, dim3(nseq), dim3(fold_threads), lds, st, B, use_ring, pool_floats, cell_waves, pool_bufs);
+  out->threads = (uint32_t)fold_threads;
+  out->cell_waves = (uint32_t)cell_waves;
+  out->use_ring = (uint32_t)use_ring;
+  out->pool_floats = (uint32_t)pool_floats;
+  out->pool_bufs = (uint32_t)pool_bufs;
+  out->lds = (uint32_t)lds;
+  out->static_lds = (uint32_t)stat;
+  return DAFS_HIP_OK;
+}
+
+namespace dafs {
+
+int contrafold_launch(const cf_batch& B, uint32_t nseq, uint32_t max_len, hipStream_t st) {
+  if (!nseq) return DAFS_HIP_OK;
+  dafs_contrafold_plan pl;
+  if (const int rc = dafs_hipk_contrafold_plan(max_len, 0, &pl)) return rc;
+  const size_t ints = (size_t)CF_INTS(max_len) * sizeof(int);  // all the posterior kernel carves
+  const size_t optin = kCfLdsTotal - pl.static_lds;            // the most dynamic LDS a launch may ask for
+  static bool attr_a[16] = {false}, attr_b[16] = {false};
+  if (!lds_optin_once((const void*)k_contrafold, (int)optin, attr_a)) return DAFS_HIP_ELAUNCH;
+  if (!lds_optin_once((const void*)k_contrafold_posterior, (int)kCfDynBudget, attr_b)) return DAFS_HIP_ELAUNCH;
+  STAGE_LAUNCH(ST_CONTRAFOLD, st) hipLaunchKernelGGL(k_contrafold, dim3(nseq), dim3(pl.threads), pl.lds, st, B, (int)pl.use_ring, (int)pl.pool_floats,
+                     (int)pl.cell_waves, (int)pl.pool_bufs);
   if (hip_check(hipGetLastError())) return DAFS_HIP_ELAUNCH;
   STAGE_LAUNCH(ST_CF_POSTERIOR, st) hipLaunchKernelGGL(k_contrafold_posterior, dim3(max_len + 1, nseq), dim3(CF_THREADS), ints, st, B);
   return hip_check(hipGetLastError()) ? DAFS_HIP_ELAUNCH : DAFS_HIP_OK;

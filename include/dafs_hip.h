@@ -760,6 +760,17 @@ int dafs_hipk_dd_node_plan(uint32_t len1, uint32_t len2, dafs_dd_node_plan* out)
 /* 32-bit words of dynamic LDS the solver's layout gives a node's workgroup (role 0, lds_flags) or its x / y folder
  * (role 1 / 2, the folder's form in fold_fast).                                                                        */
 uint32_t dafs_hipk_dd_lds_words(uint32_t len1, uint32_t len2, uint32_t lds_flags, uint32_t fold_fast, int role);
+/* The plan the CONTRAfold launch gives a batch whose longest sequence has max_len residues, under the kernel's environment
+ * switches (DAFS_HIP_CF_*), read as the launch reads them.  static_lds: bytes of k_contrafold's static LDS; 0 = ask the
+ * runtime, 28 KB where it does not answer, as the launch does.  DAFS_HIP_ETOOLONG where the launch refuses.               */
+typedef struct {
+  uint32_t threads, cell_waves;    /* workgroup size; wavefronts the cells of a span are dealt to                            */
+  uint32_t use_ring;               /* 1 = the LDS ring of the 33 most recent spans of FC / FCo                               */
+  uint32_t pool_floats, pool_bufs; /* term pool: floats in all (0 = none), 2 = two halves filled beside the cells, else 1    */
+  uint32_t lds;                    /* dynamic LDS bytes of the launch                                                        */
+  uint32_t static_lds;             /* the static size the plan was made for (static_lds, or what 0 resolved to)              */
+} dafs_contrafold_plan;
+int dafs_hipk_contrafold_plan(uint32_t max_len, uint32_t static_lds, dafs_contrafold_plan* out);
 int dafs_hip_nodes_close(dafs_hip_ctx* ctx);
 /* Device memory of the resident nodes (diagnostics): bytes reserved from the device, bytes held by open nodes now, and
  * the largest value the latter has had.  A node's memory is returned when dafs_hip_nodes_result has copied it out. */

@@ -413,16 +413,20 @@ int orc_contrafold_posterior(const char* seq, uint32_t Lu, const char* constrain
   return n;
 }
 
-float orc_contrafold_logz(const char* seq, uint32_t Lu) {
+/* log Z = F5i[L] of the inside pass, under the constraint string (NULL or empty: none) */
+float orc_contrafold_logz_constrained(const char* seq, uint32_t Lu, const char* constraint) {
   cf_t e;
   memset(&e, 0, sizeof e);
-  if (load_sequence(&e, seq, (int)Lu, NULL)) return 0.0f / 0.0f;
+  if (constraint && !constraint[0]) constraint = NULL;
+  if (load_sequence(&e, seq, (int)Lu, constraint)) { cf_free(&e); return 0.0f / 0.0f; }
   initialize_cache(&e);
   compute_inside(&e);
   float z = e.F5i[e.L];
   cf_free(&e);
   return z;
 }
+
+float orc_contrafold_logz(const char* seq, uint32_t Lu) { return orc_contrafold_logz_constrained(seq, Lu, NULL); }
 
 /* CONTRAfold::calculate, src/fold.cpp:174-207: rows (i-1) -> (j-1, p) for p > th, i != 0 */
 int orc_fold_calculate(const char* seq, uint32_t L, const char* constraint, float th, uint32_t* rowptr, uint32_t* col, float* val) {

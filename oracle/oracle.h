@@ -44,6 +44,7 @@ int orc_align_calculate(int model, const char* s1, uint32_t L1, const char* s2, 
 /* upper-triangular posterior, (L+1)(L+2)/2 floats; constraint NULL or L chars of "?.()" */
 int orc_contrafold_posterior(const char* seq, uint32_t L, const char* constraint, float* out);
 float orc_contrafold_logz(const char* seq, uint32_t L);
+float orc_contrafold_logz_constrained(const char* seq, uint32_t L, const char* constraint); /* NULL or "": as orc_contrafold_logz */
 /* Fold::Model adapter: triangular -> BP rows with p > th (src/fold.cpp:174-207) */
 int orc_fold_calculate(const char* seq, uint32_t L, const char* constraint, float th,
                        uint32_t* rowptr, uint32_t* col, float* val);

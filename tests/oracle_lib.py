@@ -46,6 +46,10 @@ class Oracle:
         L.orc_align_calculate.argtypes = [C.c_int, C.c_char_p, C.c_uint, C.c_char_p, C.c_uint, C.c_float] + [C.c_void_p] * 3
         L.orc_contrafold_posterior.argtypes = [C.c_char_p, C.c_uint, C.c_char_p, C.c_void_p]
         L.orc_fold_calculate.argtypes = [C.c_char_p, C.c_uint, C.c_char_p, C.c_float] + [C.c_void_p] * 3
+        L.orc_contrafold_logz.restype = C.c_float
+        L.orc_contrafold_logz.argtypes = [C.c_char_p, C.c_uint]
+        L.orc_contrafold_logz_constrained.restype = C.c_float
+        L.orc_contrafold_logz_constrained.argtypes = [C.c_char_p, C.c_uint, C.c_char_p]
         L.orc_nussinov_decode.restype = C.c_float
         L.orc_nussinov_decode.argtypes = [C.c_float, C.c_float, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p]
         L.orc_nw_envelope.argtypes = [C.c_float, C.c_uint, C.c_uint, C.c_void_p, C.c_void_p]

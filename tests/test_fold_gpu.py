@@ -19,12 +19,17 @@ def ctx():
     c.close()
 
 
-def test_golden_posteriors(ctx):
+def _orc_logz(oracle, s):
+    return np.float32(oracle.lib.orc_contrafold_logz(s.encode(), len(s)))
+
+
+def test_golden_posteriors(ctx, oracle):
     z = np.load(os.path.join(G, "contrafold_post.npz"))
     for k, s in enumerate(z["seqs"]):
         post, logz = ctx.fold_posterior_dense(str(s))
         want = z["post"][z["off"][k]:z["off"][k + 1]]
         assert post.tobytes() == want.tobytes(), (k, len(str(s)), np.abs(post - want).max(), int((post != want).sum()))
+        assert logz.tobytes() == _orc_logz(oracle, str(s)).tobytes(), (k, float(logz))
 
 
 def test_golden_constrained(ctx):
@@ -39,8 +44,9 @@ def test_fuzz_vs_oracle(ctx, oracle):
     for k in range(14):
         L = int(rng.choice([1, 2, 3, 5, 9, 31, 33, 64, 100, 181]))
         s = "".join(rng.choice(list("ACGU" if k % 3 else "ACGUTNacgu-"), L))
-        post, _ = ctx.fold_posterior_dense(s)
+        post, logz = ctx.fold_posterior_dense(s)
         assert post.tobytes() == t._orc_fold_post(oracle, s).tobytes(), (k, L)
+        assert logz.tobytes() == _orc_logz(oracle, s).tobytes(), (k, L, float(logz))
     # constraints: unpaired stretches and forced pairs
     s = "GGGAAACUUCGGUUUCCCAAGGGAAACCC"
     for cons in ("?" * len(s), "." * 3 + "?" * (len(s) - 3), "(" + "?" * (len(s) - 2) + ")", "((?..........?))" + "?" * (len(s) - 16)):
@@ -49,9 +55,10 @@ def test_fuzz_vs_oracle(ctx, oracle):
 
 
 def test_sequences_too_long_for_the_lds_ring(ctx, oracle, monkeypatch):
-    """Beyond ~540 nt the 33 most recent spans of FC/FCo no longer fit LDS and the single-branch terms read them
-    from HBM/L2 instead.  One sequence of that length against the oracle, and the short fuzz set with that form
-    forced (DAFS_HIP_CF_NORING)."""
+    """From about 260 nt on (dafs_hipk_contrafold_plan; the length depends on the kernel's static LDS) the plan gives the
+    room of the ring of the 33 most recent spans of FC/FCo to the term pool, and the single-branch terms read those spans
+    from HBM/L2 instead.  One sequence well beyond that length against the oracle, and the short fuzz set with that
+    form forced (DAFS_HIP_CF_NORING)."""
     import test_oracle_cpu as t
     rng = np.random.default_rng(5)
     s = "".join(rng.choice(list("ACGU"), 600))
