@@ -246,6 +246,11 @@ _nodes_round = _sig("dafs_hip_nodes_round", C.c_int, [C.c_void_p, C.c_uint32, C.
                                                       C.POINTER(DDParams), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p])
 _nodes_result = _sig("dafs_hip_nodes_result", C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(NodeOutput)])
 _nodes_close = _sig("dafs_hip_nodes_close", C.c_int, [C.c_void_p])
+_node_peek = _sig("dafs_hip_node_peek", C.c_int, [C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)])
+# the arrays of dafs_hip_node_peek (DAFS_PEEK_* of dafs_hip.h, in their order) and their element types
+NODE_PEEK = ("p_x", "p_y", "p_z", "x_ptr", "x_col", "x_map", "y_ptr", "y_col", "y_map", "pz_ptr", "pz_k", "cz_ptr", "cz_k", "zmap", "env", "env4",
+             "cbp_cnt", "cbp")
+_NODE_PEEK_TYPE = {"p_x": np.float32, "p_y": np.float32, "p_z": np.float32, "x_map": np.int32, "y_map": np.int32, "zmap": np.int32}
 _nodes_memory = _sig("dafs_hip_nodes_memory", C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)])
 _nodes_demotions = _sig("dafs_hip_nodes_demotions", C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)])
 _update_basepairing = _sig("dafs_hip_update_basepairing", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])
@@ -594,6 +599,7 @@ class Context:
         check(_create(device, C.byref(self._h)))
         self._lens = None
         self._first = np.array([0, 0], np.uint32)
+        self._node_lens = {}  # handle -> (len1, len2) of the nodes opened since nodes_close (node_peek shapes its arrays by them)
         self.device_index = device
 
     def close(self):
@@ -1054,7 +1060,9 @@ class Context:
         ins, keep = _node_inputs(nodes)
         handles = np.zeros(n, np.uint32)
         check(_nodes_open(self._h, n, ins, C.byref(prm), handles.ctypes.data))
-        return [int(h) for h in handles], [(k[2].shape[1], k[3].shape[1]) for k in keep]
+        lens = [(k[2].shape[1], k[3].shape[1]) for k in keep]
+        self._node_lens.update(zip((int(h) for h in handles), lens))
+        return [int(h) for h in handles], lens
 
     def nodes_advance(self, handles, prm, max_iterations):
         """one launch: at most max_iterations more iterations for every listed node; returns the finished flags"""
@@ -1074,7 +1082,9 @@ class Context:
         fo = np.zeros(max(len(h), 1), np.uint8); fn = np.zeros(max(n, 1), np.uint8)
         check(_nodes_round(self._h, n, ins, nh.ctypes.data, len(h), h.ctypes.data if len(h) else None, C.byref(prm), max_iterations,
                            budget_us, fo.ctypes.data, fn.ctypes.data))
-        return ([int(x) for x in nh[:n]], [(k[2].shape[1], k[3].shape[1]) for k in keep], fo[:len(h)].astype(bool), fn[:n].astype(bool))
+        lens = [(k[2].shape[1], k[3].shape[1]) for k in keep]
+        self._node_lens.update(zip((int(x) for x in nh[:n]), lens))
+        return ([int(x) for x in nh[:n]], lens, fo[:len(h)].astype(bool), fn[:n].astype(bool))
 
     def nodes_result(self, handle, len1, len2):
         out = NodeOutput()
@@ -1083,8 +1093,26 @@ class Context:
         check(_nodes_result(self._h, handle, C.byref(out)))
         return dict(x=x, y=y, z=z, score=np.float32(out.score), ncbp=out.ncbp, iterations=out.iterations, violated=out.violated)
 
+    def node_peek(self, handle, what):
+        """dafs_hip_node_peek: a copy of array `what` (a name of NODE_PEEK) of the open node `handle`, as the set-up kernels left
+        it -- flat, but the matrices and dense maps in their shape and cbp as [pairs, 8]"""
+        if what not in NODE_PEEK:
+            raise DafsHipError("node_peek: unknown array %r" % (what,))
+        len1, len2 = self._node_lens.get(handle, (0, 0))  # an unknown handle: the library refuses it
+        cells = {"p_x": (len1, len1), "p_y": (len2, len2), "p_z": (len1, len2), "x_map": (len1, len1), "y_map": (len2, len2), "zmap": (len1, len2)}
+        words = max(len1, len2) ** 2 + 2 * (max(len1, len2) + 130)  # no array of a node is longer, cbp apart
+        if what == "cbp":  # as many pairs as the node's own counts say
+            n = self.node_peek(handle, "cbp_cnt")
+            words = 8 * (int(n[-1]) if len(n) else 0) + 8
+        buf = np.zeros(words, _NODE_PEEK_TYPE.get(what, np.uint32))
+        got = C.c_uint64()
+        check(_node_peek(self._h, handle, NODE_PEEK.index(what), buf.ctypes.data, buf.nbytes, C.byref(got)))
+        out = buf[:got.value // 4].copy()
+        return out.reshape(cells[what]) if what in cells else out.reshape(-1, 8) if what == "cbp" else out
+
     def nodes_close(self):
         check(_nodes_close(self._h))
+        self._node_lens.clear()
 
     def nodes_memory(self):
         """(reserved, in_use, peak) bytes of the resident nodes' device memory"""

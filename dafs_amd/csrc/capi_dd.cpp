@@ -785,6 +785,55 @@ extern "C" int dafs_hip_nodes_result(dafs_hip_ctx* c, uint32_t handle, dafs_node
   return nodes_result(c, handle, out, read_switches().stamps);
 }
 
+// A read-only look at what the set-up kernels of nodes_open wrote for one resident node (tests).  The sizes come from the
+// descriptor the open call kept (dd_open_node::nd); the lengths of the entry lists from their own last row pointer.
+extern "C" int dafs_hip_node_peek(dafs_hip_ctx* c, uint32_t handle, int what, void* dst, uint64_t capacity_bytes, uint64_t* bytes_out) {
+  if (!c || !dst || !bytes_out) return DAFS_HIP_EINVAL;
+  if (handle >= c->dd_open.size() || c->dd_open[handle].released || c->dd_open[handle].in_flight) return DAFS_HIP_EINVAL;
+  if (hip_check(hipSetDevice(c->device))) return DAFS_HIP_ENODEV;
+  const dd_node& nd = c->dd_open[handle].nd;
+  const dd_fold &fx = nd.f[0], &fy = nd.f[1];
+  const size_t L1 = fx.L, L2 = fy.L;
+  // both lanes: the node may have been opened or advanced on either (dafs_hip_nodes_round)
+  if (hip_check(hipStreamSynchronize(c->stream)) || (c->node_stream && hip_check(hipStreamSynchronize(c->node_stream)))) return DAFS_HIP_ELAUNCH;
+  const void* src = nullptr;
+  size_t bytes = 0;
+  const uint32_t* count_at = nullptr;  // entry lists: as many words as this row pointer says
+  switch (what) {
+    case DAFS_PEEK_P_X: src = fx.p; bytes = L1 * L1 * 4; break;
+    case DAFS_PEEK_P_Y: src = fy.p; bytes = L2 * L2 * 4; break;
+    case DAFS_PEEK_P_Z: src = nd.p_z; bytes = L1 * L2 * 4; break;
+    case DAFS_PEEK_X_PTR: src = fx.ptr; bytes = (L1 + 1) * 4; break;
+    case DAFS_PEEK_Y_PTR: src = fy.ptr; bytes = (L2 + 1) * 4; break;
+    case DAFS_PEEK_X_COL: src = fx.col; count_at = fx.ptr + L1; break;
+    case DAFS_PEEK_Y_COL: src = fy.col; count_at = fy.ptr + L2; break;
+    case DAFS_PEEK_X_MAP: src = fx.map; bytes = L1 * L1 * 4; break;
+    case DAFS_PEEK_Y_MAP: src = fy.map; bytes = L2 * L2 * 4; break;
+    case DAFS_PEEK_PZ_PTR: src = nd.pz_ptr; bytes = (L1 + 1) * 4; break;
+    case DAFS_PEEK_PZ_K: src = nd.pz_k; count_at = nd.pz_ptr + L1; break;
+    case DAFS_PEEK_CZ_PTR: src = nd.cz_ptr; bytes = (L1 + 1) * 4; break;
+    case DAFS_PEEK_CZ_K: src = nd.cz_k; count_at = nd.cz_ptr + L1; break;
+    case DAFS_PEEK_ZMAP: src = nd.zmap; bytes = L1 * L2 * 4; break;
+    case DAFS_PEEK_ENV: src = nd.env; bytes = 2 * (L1 + 1) * 4; break;
+    case DAFS_PEEK_ENV4: src = nd.env4; bytes = 2 * (L1 + 130) * 4; break;
+    case DAFS_PEEK_CBP_CNT: src = nd.cbp_cnt; count_at = fx.ptr + L1; break;
+    case DAFS_PEEK_CBP:  // carved with the folding arrays' block: a node that does not fold (skip_uncoupled_folds) has no pair and keeps none
+      if (!fx.w.dp) return DAFS_HIP_EINVAL;
+      src = nd.cbp; bytes = (size_t)nd.ncbp_cap * 32; break;
+    default: return DAFS_HIP_EINVAL;
+  }
+  if (!src) return DAFS_HIP_EINVAL;
+  if (count_at) {
+    uint32_t n = 0;
+    if (hip_check(hipMemcpy(&n, count_at, 4, hipMemcpyDeviceToHost))) return DAFS_HIP_ELAUNCH;
+    bytes = (size_t)n * 4;
+  }
+  if (bytes > capacity_bytes) return DAFS_HIP_EINVAL;
+  if (bytes && hip_check(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost))) return DAFS_HIP_ELAUNCH;
+  *bytes_out = bytes;
+  return DAFS_HIP_OK;
+}
+
 extern "C" int dafs_hip_nodes_close(dafs_hip_ctx* c) {
   if (!c) return DAFS_HIP_EINVAL;
   if (hip_check(hipSetDevice(c->device))) return DAFS_HIP_ENODEV;

@@ -771,6 +771,22 @@ typedef struct {
   uint32_t static_lds;             /* the static size the plan was made for (static_lds, or what 0 resolved to)              */
 } dafs_contrafold_plan;
 int dafs_hipk_contrafold_plan(uint32_t max_len, uint32_t static_lds, dafs_contrafold_plan* out);
+/* A read-only copy of one array that the set-up kernels of dafs_hip_nodes_open / dafs_hip_nodes_round wrote for a resident
+ * node (tests; nothing in a run calls it).  The node's streams are drained first.  p_*: the matrices solve_by_dd starts from;
+ * *_PTR / *_COL / *_K: row pointers (rows + 1 words) and entries of the lists of p_x, p_y (cells above the cut-off, j > i), p_z
+ * and c_z (cells of z in a consensus base pair); *_MAP: per dense cell its entry or -1 (ZMAP: into the c_z list); ENV:
+ * 2 * (len1 + 1) words; ENV4: 2 * (len1 + 130) words, written by the node's first iteration, not by the set-up; CBP_CNT: a word
+ * per entry of p_x -- its consensus pairs, and from the fill on (nodes with at least one pair) their running total; CBP: 8
+ * words per consensus base pair (i j k l, entry of p_x, entry of p_y, c_z entries of (i, k) and (j, l)), bytes_out / 32 pairs.
+ * DAFS_HIP_EINVAL, with dst and bytes_out untouched and the context usable, for a handle that names no node holding its
+ * memory (unknown, in a launch, or given back by dafs_hip_nodes_result), an unknown `what`, a capacity below the array's
+ * bytes, or CBP of a node opened without its folding arrays (skip_uncoupled_folds and no consensus pair).                 */
+enum {
+  DAFS_PEEK_P_X = 0, DAFS_PEEK_P_Y, DAFS_PEEK_P_Z, DAFS_PEEK_X_PTR, DAFS_PEEK_X_COL, DAFS_PEEK_X_MAP, DAFS_PEEK_Y_PTR, DAFS_PEEK_Y_COL,
+  DAFS_PEEK_Y_MAP, DAFS_PEEK_PZ_PTR, DAFS_PEEK_PZ_K, DAFS_PEEK_CZ_PTR, DAFS_PEEK_CZ_K, DAFS_PEEK_ZMAP, DAFS_PEEK_ENV, DAFS_PEEK_ENV4,
+  DAFS_PEEK_CBP_CNT, DAFS_PEEK_CBP
+};
+int dafs_hip_node_peek(dafs_hip_ctx* ctx, uint32_t handle, int what, void* dst, uint64_t capacity_bytes, uint64_t* bytes_out);
 int dafs_hip_nodes_close(dafs_hip_ctx* ctx);
 /* Device memory of the resident nodes (diagnostics): bytes reserved from the device, bytes held by open nodes now, and
  * the largest value the latter has had.  A node's memory is returned when dafs_hip_nodes_result has copied it out. */

@@ -124,6 +124,14 @@ int orc_pipeline_solve_node(orc_pipeline* pl, uint32_t n1, const uint32_t* idx1,
                             uint32_t n2, const uint32_t* idx2, const uint8_t* mask2, uint32_t L2,
                             const float* p_x, const float* p_y, uint32_t* x, uint32_t* y, uint32_t* z,
                             float* score, uint32_t* ncbp, uint32_t* iterations, uint32_t* violated);
+/* What solve_by_dd starts from at that node, under the same arguments and checks: the matrices it is handed (the averages,
+ * or the supplied p_x / p_y) in o_px[L1*L1], o_py[L2*L2], o_pz[L1*L2]; the alignment envelope of p_z in env[2*(L1+1)]; its
+ * consensus base pairs (dafs.cpp:1022-1044) in its order as (i, j, k, l) in cbp[4*cbp_cap] -- the first cbp_cap of them,
+ * *ncbp being the length of the whole list.  0, or -1 for arguments that name no node. */
+int orc_pipeline_node_setup(orc_pipeline* pl, uint32_t n1, const uint32_t* idx1, const uint8_t* mask1, uint32_t L1,
+                            uint32_t n2, const uint32_t* idx2, const uint8_t* mask2, uint32_t L2,
+                            const float* p_x, const float* p_y, float* o_px, float* o_py, float* o_pz, uint32_t* env,
+                            uint32_t* cbp, uint32_t cbp_cap, uint32_t* ncbp);
 double orc_pipeline_seconds(const orc_pipeline* pl, int phase); /* 0 fold,1 pair,2 pct+tree,3 progressive */
 
 /* FASTA reader following Fasta::load src/fa.cpp:37-87. Returns count or -1.

@@ -513,15 +513,12 @@ static void adj_build(adj_t* a, uint32_t nrow, uint64_t* keys, size_t nk) {
   for (uint32_t r = 0; r < nrow; ++r) a->ptr[r + 1] += a->ptr[r];
 }
 
-/* DAFS::solve_by_dd, dafs.cpp:1006-1295 (SPARSE_UPDATE, plain subgradient branch).  Returns what the reference returns
- * (s_prev, :1294); the length of the cbp list, the iterations run and the last violated count (the values of the
- * reference's log line, :1292) come back through the out-parameters -- the caller keeps the log. */
-static float solve_by_dd(const orc_pipeline* pl, uint32_t* x, uint32_t* y, uint32_t* z,
-                         const float* p_x, const float* p_y, const float* p_z,
-                         uint32_t L1, uint32_t L2, uint32_t N1, uint32_t N2,
-                         uint32_t* o_ncbp, uint32_t* o_iterations, uint32_t* o_violated) {
-  const orc_params* prm = &pl->prm;
-  const float w_ = prm->w, th_a_ = prm->th_a, eta0_ = prm->eta0;
+/* The consensus base pairs of a node, dafs.cpp:1022-1044, in the reference's order: (i, j) of p_x row by row, per pair the
+ * columns k of row i of p_z, per k the pairs (k, l) of p_y whose l matches j.  The one enumeration that solve_by_dd and
+ * orc_pipeline_node_setup share.  Returns a malloc'ed list of *o_n entries. */
+static cbp_t* consensus_base_pairs(const orc_params* prm, const float* p_x, const float* p_y, const float* p_z,
+                                   uint32_t L1, uint32_t L2, uint32_t N1, uint32_t N2, size_t* o_n) {
+  const float w_ = prm->w, th_a_ = prm->th_a;
   const float min_th_s = prm->th_s;
   size_t ncbp = 0, cap = 1024;
   cbp_t* cbp = (cbp_t*)malloc(cap * sizeof(cbp_t));
@@ -543,6 +540,24 @@ static float solve_by_dd(const orc_pipeline* pl, uint32_t* x, uint32_t* y, uint3
                   cbp[ncbp++] = c;
                 }
               }
+#undef PX
+#undef PY
+#undef PZ
+  *o_n = ncbp;
+  return cbp;
+}
+
+/* DAFS::solve_by_dd, dafs.cpp:1006-1295 (SPARSE_UPDATE, plain subgradient branch).  Returns what the reference returns
+ * (s_prev, :1294); the length of the cbp list, the iterations run and the last violated count (the values of the
+ * reference's log line, :1292) come back through the out-parameters -- the caller keeps the log. */
+static float solve_by_dd(const orc_pipeline* pl, uint32_t* x, uint32_t* y, uint32_t* z,
+                         const float* p_x, const float* p_y, const float* p_z,
+                         uint32_t L1, uint32_t L2, uint32_t N1, uint32_t N2,
+                         uint32_t* o_ncbp, uint32_t* o_iterations, uint32_t* o_violated) {
+  const orc_params* prm = &pl->prm;
+  const float w_ = prm->w, th_a_ = prm->th_a, eta0_ = prm->eta0;
+  size_t ncbp = 0;
+  cbp_t* cbp = consensus_base_pairs(prm, p_x, p_y, p_z, L1, L2, N1, N2, &ncbp);
   adj_t c_x, c_y, c_z;
   {
     uint64_t* kx = (uint64_t*)malloc((ncbp + 1) * sizeof(uint64_t));
@@ -845,6 +860,22 @@ int orc_pipeline_phase1(orc_pipeline* pl) {
   return 0;
 }
 
+/* the checks of a node's arguments that orc_pipeline_solve_node and orc_pipeline_node_setup share: 0 when they name a node, else -1 */
+static int node_args_check(const orc_pipeline* pl, const aln_t a[2]) {
+  for (int c = 0; c < 2; ++c)
+    for (uint32_t r = 0; r < a[c].n; ++r) {
+      const uint32_t s = a[c].idx[r];
+      if (s >= pl->N || !pl->bp[s].rowptr) return -1;
+      uint32_t res = 0;
+      for (uint32_t i = 0; i < a[c].L; ++i) res += a[c].mask[(size_t)r * a[c].L + i] != 0;
+      if (res != pl->len[s]) return -1;
+    }
+  for (uint32_t r1 = 0; r1 < a[0].n; ++r1)
+    for (uint32_t r2 = 0; r2 < a[1].n; ++r2)
+      if (!MP(pl, a[0].idx[r1], a[1].idx[r2])->rowptr) return -1;
+  return 0;
+}
+
 /* One internal node of the progressive phase on the pipeline's current stores (after orc_pipeline_phase1): what
  * align_node runs between its two recursive calls and project_alignment -- average_basepairing_probability of both
  * children, average_matching_probability, solve_by_dd (dafs.cpp:896-911) -- for children given as rows (sequence index,
@@ -860,17 +891,7 @@ int orc_pipeline_solve_node(orc_pipeline* pl, uint32_t n1, const uint32_t* idx1,
                             float* score, uint32_t* ncbp, uint32_t* iterations, uint32_t* violated) {
   if (!pl || !n1 || !n2 || !L1 || !L2 || !idx1 || !idx2 || !mask1 || !mask2 || !x || !y || !z) return -1;
   aln_t a[2] = {{n1, L1, (uint32_t*)idx1, (uint8_t*)mask1}, {n2, L2, (uint32_t*)idx2, (uint8_t*)mask2}};
-  for (int c = 0; c < 2; ++c)
-    for (uint32_t r = 0; r < a[c].n; ++r) {
-      const uint32_t s = a[c].idx[r];
-      if (s >= pl->N || !pl->bp[s].rowptr) return -1;
-      uint32_t res = 0;
-      for (uint32_t i = 0; i < a[c].L; ++i) res += a[c].mask[(size_t)r * a[c].L + i] != 0;
-      if (res != pl->len[s]) return -1;
-    }
-  for (uint32_t r1 = 0; r1 < n1; ++r1)
-    for (uint32_t r2 = 0; r2 < n2; ++r2)
-      if (!MP(pl, idx1[r1], idx2[r2])->rowptr) return -1;
+  if (node_args_check(pl, a)) return -1;
   float* ax = p_x ? NULL : average_basepairing_probability(pl, &a[0]);
   float* ay = p_y ? NULL : average_basepairing_probability(pl, &a[1]);
   float* p_z = average_matching_probability(pl, &a[0], &a[1]);
@@ -881,6 +902,32 @@ int orc_pipeline_solve_node(orc_pipeline* pl, uint32_t n1, const uint32_t* idx1,
   if (iterations) *iterations = it;
   if (violated) *violated = vi;
   free(ax); free(ay); free(p_z);
+  return 0;
+}
+
+/* What solve_by_dd starts from at the same node (same arguments, same checks as orc_pipeline_solve_node): the matrices it
+ * is handed -- the averages, or the supplied p_x / p_y -- into o_px[L1*L1], o_py[L2*L2], o_pz[L1*L2]; the alignment
+ * envelope of p_z into env[2*(L1+1)]; and its consensus base pairs, in its order, as (i, j, k, l) into cbp[4*cbp_cap] (the
+ * first cbp_cap of them; *ncbp is the length of the whole list, so a caller may ask with cbp_cap = 0 first). */
+int orc_pipeline_node_setup(orc_pipeline* pl, uint32_t n1, const uint32_t* idx1, const uint8_t* mask1, uint32_t L1,
+                            uint32_t n2, const uint32_t* idx2, const uint8_t* mask2, uint32_t L2,
+                            const float* p_x, const float* p_y, float* o_px, float* o_py, float* o_pz, uint32_t* env,
+                            uint32_t* cbp, uint32_t cbp_cap, uint32_t* ncbp) {
+  if (!pl || !n1 || !n2 || !L1 || !L2 || !idx1 || !idx2 || !mask1 || !mask2 || !o_px || !o_py || !o_pz || !env || !ncbp || (cbp_cap && !cbp)) return -1;
+  aln_t a[2] = {{n1, L1, (uint32_t*)idx1, (uint8_t*)mask1}, {n2, L2, (uint32_t*)idx2, (uint8_t*)mask2}};
+  if (node_args_check(pl, a)) return -1;
+  float* ax = p_x ? NULL : average_basepairing_probability(pl, &a[0]);
+  float* ay = p_y ? NULL : average_basepairing_probability(pl, &a[1]);
+  float* p_z = average_matching_probability(pl, &a[0], &a[1]);
+  memcpy(o_px, p_x ? p_x : ax, (size_t)L1 * L1 * sizeof(float));
+  memcpy(o_py, p_y ? p_y : ay, (size_t)L2 * L2 * sizeof(float));
+  memcpy(o_pz, p_z, (size_t)L1 * L2 * sizeof(float));
+  orc_nw_envelope(pl->prm.th_a, L1, L2, p_z, env);
+  size_t n = 0;
+  cbp_t* list = consensus_base_pairs(&pl->prm, o_px, o_py, o_pz, L1, L2, n1, n2, &n);
+  for (size_t u = 0; u < n && u < cbp_cap; ++u) { cbp[4 * u] = list[u].i; cbp[4 * u + 1] = list[u].j; cbp[4 * u + 2] = list[u].k; cbp[4 * u + 3] = list[u].l; }
+  *ncbp = (uint32_t)n;
+  free(list); free(ax); free(ay); free(p_z);
   return 0;
 }
 

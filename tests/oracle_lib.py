@@ -81,6 +81,9 @@ class Oracle:
         L.orc_pipeline_solve_node.restype = C.c_int
         L.orc_pipeline_solve_node.argtypes = ([C.c_void_p] + [C.c_uint, C.c_void_p, C.c_void_p, C.c_uint] * 2 + [C.c_void_p] * 5
                                               + [C.POINTER(C.c_float)] + [C.POINTER(C.c_uint32)] * 3)
+        L.orc_pipeline_node_setup.restype = C.c_int
+        L.orc_pipeline_node_setup.argtypes = ([C.c_void_p] + [C.c_uint, C.c_void_p, C.c_void_p, C.c_uint] * 2 + [C.c_void_p] * 7
+                                              + [C.c_uint, C.POINTER(C.c_uint32)])
         L.orc_pipeline_seconds.restype = C.c_double
         L.orc_pipeline_seconds.argtypes = [C.c_void_p, C.c_int]
         L.orc_fasta_load.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p]
@@ -250,6 +253,32 @@ class Pipeline:
                                                 x.ctypes.data, y.ctypes.data, z.ctypes.data, C.byref(score), C.byref(ncbp), C.byref(it), C.byref(vi))
         assert rc == 0, rc
         return dict(x=x, y=y, z=z, score=np.float32(score.value), ncbp=ncbp.value, iterations=it.value, violated=vi.value)
+
+    def node_setup(self, idx1, mask1, idx2, mask2, p_x=None, p_y=None):
+        """orc_pipeline_node_setup: what solve_by_dd starts from at the node solve_node would solve -- dict of p_x [L1, L1],
+        p_y [L2, L2], p_z [L1, L2] (float32), env [2 * (L1 + 1)] and cbp [ncbp, 4] = (i, j, k, l) in the reference's order"""
+        idx1 = np.ascontiguousarray(idx1, np.uint32); idx2 = np.ascontiguousarray(idx2, np.uint32)
+        m1 = np.ascontiguousarray(mask1, np.uint8); m2 = np.ascontiguousarray(mask2, np.uint8)
+        assert m1.ndim == 2 and m2.ndim == 2 and m1.shape[0] == len(idx1) and m2.shape[0] == len(idx2)
+        L1, L2 = m1.shape[1], m2.shape[1]
+        px = None if p_x is None else np.ascontiguousarray(p_x, np.float32)
+        py = None if p_y is None else np.ascontiguousarray(p_y, np.float32)
+        assert px is None or px.shape == (L1, L1)
+        assert py is None or py.shape == (L2, L2)
+        ox = np.zeros((L1, L1), np.float32); oy = np.zeros((L2, L2), np.float32); oz = np.zeros((L1, L2), np.float32)
+        env = np.zeros(2 * (L1 + 1), np.uint32)
+        n = C.c_uint32()
+        cbp = np.zeros((0, 4), np.uint32)
+        for _ in range(2):  # the count, then the list
+            rc = self.o.lib.orc_pipeline_node_setup(self.h, len(idx1), idx1.ctypes.data, m1.ctypes.data, L1, len(idx2), idx2.ctypes.data, m2.ctypes.data, L2,
+                                                    None if px is None else px.ctypes.data, None if py is None else py.ctypes.data,
+                                                    ox.ctypes.data, oy.ctypes.data, oz.ctypes.data, env.ctypes.data,
+                                                    cbp.ctypes.data if len(cbp) else None, len(cbp), C.byref(n))
+            assert rc == 0, rc
+            if len(cbp) == n.value:
+                break
+            cbp = np.zeros((n.value, 4), np.uint32)
+        return dict(p_x=ox, p_y=oy, p_z=oz, env=env, cbp=cbp)
 
     def seconds(self):
         return [self.o.lib.orc_pipeline_seconds(self.h, i) for i in range(4)]
