@@ -132,6 +132,20 @@ int orc_pipeline_node_setup(orc_pipeline* pl, uint32_t n1, const uint32_t* idx1,
                             uint32_t n2, const uint32_t* idx2, const uint8_t* mask2, uint32_t L2,
                             const float* p_x, const float* p_y, float* o_px, float* o_py, float* o_pz, uint32_t* env,
                             uint32_t* cbp, uint32_t cbp_cap, uint32_t* ncbp);
+/* The averaged base-pairing matrix of one alignment given as rows (idx, mask as above), on the current base-pairing store
+ * (orc_pipeline_set_bp, or as orc_pipeline_phase1 left it): average_basepairing_probability, dafs.cpp:561-607 without the
+ * alifold term -- row r adds val / n to cell (column of i, column of j) of every entry of its sequence, rows in order, and
+ * cells of the upper triangle at or below CUTOFF become 0.  out[L*L].  Parity unpinned.  0, or -1 (out untouched) for a
+ * null pointer, no row or column, an index that names no sequence with rows in the store, or a mask row that does not
+ * place exactly its sequence's residues. */
+int orc_pipeline_average_basepairing(orc_pipeline* pl, uint32_t n, const uint32_t* idx, const uint8_t* mask, uint32_t L, float* out);
+/* The same matrix re-estimated under the structure ss[L] (decoders' convention: ss[i] = j at the left column of a pair,
+ * ORC_NONE elsewhere): update_basepairing_probability, dafs.cpp:609-712, no alifold term, one level of brackets, the
+ * bracket string from orc_make_brackets.  Row r is folded again (orc_fold_calculate at CUTOFF) under '(' / ')' where both
+ * columns of a pair hold a residue of it and '?' elsewhere (:637-653), and the folds are averaged and cut like the free
+ * ones.  The stores are neither read nor changed.  Parity unpinned.  0 or -1 as above; a partner ss[i] >= L is refused. */
+int orc_pipeline_update_basepairing(orc_pipeline* pl, uint32_t n, const uint32_t* idx, const uint8_t* mask, uint32_t L, const uint32_t* ss,
+                                    float* out);
 double orc_pipeline_seconds(const orc_pipeline* pl, int phase); /* 0 fold,1 pair,2 pct+tree,3 progressive */
 
 /* FASTA reader following Fasta::load src/fa.cpp:37-87. Returns count or -1.

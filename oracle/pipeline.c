@@ -931,6 +931,53 @@ int orc_pipeline_node_setup(orc_pipeline* pl, uint32_t n1, const uint32_t* idx1,
   return 0;
 }
 
+/* the checks of one alignment's rows: every index names a sequence of the pipeline (need_bp: one whose base-pairing rows are
+ * in the store) and every mask row places exactly that sequence's residues.  0, else -1. */
+static int rows_args_check(const orc_pipeline* pl, const aln_t* a, int need_bp) {
+  for (uint32_t r = 0; r < a->n; ++r) {
+    const uint32_t s = a->idx[r];
+    if (s >= pl->N || (need_bp && !pl->bp[s].rowptr)) return -1;
+    uint32_t res = 0;
+    for (uint32_t i = 0; i < a->L; ++i) res += a->mask[(size_t)r * a->L + i] != 0;
+    if (res != pl->len[s]) return -1;
+  }
+  return 0;
+}
+
+/* average_basepairing_probability (dafs.cpp:561-607, no alifold term) of one alignment given as rows, on the pipeline's
+ * current base-pairing store -- supplied with orc_pipeline_set_bp, or as orc_pipeline_phase1 left it -- into out[L*L].
+ * The function the node entry points and orc_pipeline_phase2 call, unchanged.  PARITY UNPINNED like the rest of this file.
+ * Returns 0, or -1 for a null pointer, no row or column, an index that names no sequence (or one without rows in the
+ * store), or a mask row that does not place exactly its sequence's residues; out is untouched then. */
+int orc_pipeline_average_basepairing(orc_pipeline* pl, uint32_t n, const uint32_t* idx, const uint8_t* mask, uint32_t L, float* out) {
+  if (!pl || !n || !L || !idx || !mask || !out) return -1;
+  const aln_t a = {n, L, (uint32_t*)idx, (uint8_t*)mask};
+  if (rows_args_check(pl, &a, 1)) return -1;
+  float* p = average_basepairing_probability(pl, &a);
+  memcpy(out, p, (size_t)L * L * sizeof(float));
+  free(p);
+  return 0;
+}
+
+/* update_basepairing_probability (dafs.cpp:609-712, no alifold term, one level) of one alignment given as rows under the
+ * structure ss[L] (ss[i] = j at the left column of a pair, ORC_NONE elsewhere: what the decoders return), into out[L*L].
+ * The bracket string comes from orc_make_brackets, as bp_update() makes it; the rows are folded here, so the stores are
+ * neither read nor changed.  Same return values as orc_pipeline_average_basepairing; a partner ss[i] >= L is refused too. */
+int orc_pipeline_update_basepairing(orc_pipeline* pl, uint32_t n, const uint32_t* idx, const uint8_t* mask, uint32_t L, const uint32_t* ss,
+                                    float* out) {
+  if (!pl || !n || !L || !idx || !mask || !ss || !out) return -1;
+  const aln_t a = {n, L, (uint32_t*)idx, (uint8_t*)mask};
+  if (rows_args_check(pl, &a, 0)) return -1;
+  for (uint32_t i = 0; i < L; ++i)
+    if (ss[i] != ORC_NONE && ss[i] >= L) return -1;
+  char* str = (char*)malloc((size_t)L + 1);
+  orc_make_brackets(L, ss, str);
+  float* p = update_basepairing_probability(pl, &a, ss, str);
+  memcpy(out, p, (size_t)L * L * sizeof(float));
+  free(p); free(str);
+  return 0;
+}
+
 static int cmp_row(const void* a, const void* b) {
   uint32_t x = *(const uint32_t*)a, y = *(const uint32_t*)b;
   return x < y ? -1 : x > y;

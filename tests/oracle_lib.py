@@ -84,6 +84,10 @@ class Oracle:
         L.orc_pipeline_node_setup.restype = C.c_int
         L.orc_pipeline_node_setup.argtypes = ([C.c_void_p] + [C.c_uint, C.c_void_p, C.c_void_p, C.c_uint] * 2 + [C.c_void_p] * 7
                                               + [C.c_uint, C.POINTER(C.c_uint32)])
+        L.orc_pipeline_average_basepairing.restype = C.c_int
+        L.orc_pipeline_average_basepairing.argtypes = [C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p, C.c_uint, C.c_void_p]
+        L.orc_pipeline_update_basepairing.restype = C.c_int
+        L.orc_pipeline_update_basepairing.argtypes = [C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p]
         L.orc_pipeline_seconds.restype = C.c_double
         L.orc_pipeline_seconds.argtypes = [C.c_void_p, C.c_int]
         L.orc_fasta_load.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p]
@@ -279,6 +283,35 @@ class Pipeline:
                 break
             cbp = np.zeros((n.value, 4), np.uint32)
         return dict(p_x=ox, p_y=oy, p_z=oz, env=env, cbp=cbp)
+
+    def average_basepairing(self, idx, mask, out=None):
+        """orc_pipeline_average_basepairing: the averaged base-pairing matrix [L, L] of the rows (sequence index per row, mask
+        [n, L]) on the current base-pairing store.  out: the array to fill; then the return code comes back instead."""
+        idx = np.ascontiguousarray(idx, np.uint32); m = np.ascontiguousarray(mask, np.uint8)
+        assert m.ndim == 2 and m.shape[0] == len(idx)
+        L = m.shape[1]
+        p = np.zeros((L, L), np.float32) if out is None else out
+        assert p.dtype == np.float32 and p.shape == (L, L) and p.flags.c_contiguous
+        rc = self.o.lib.orc_pipeline_average_basepairing(self.h, len(idx), idx.ctypes.data, m.ctypes.data, L, p.ctypes.data)
+        if out is not None:
+            return rc
+        assert rc == 0, rc
+        return p
+
+    def update_basepairing(self, idx, mask, ss, out=None):
+        """orc_pipeline_update_basepairing: the matrix [L, L] of the rows folded again under the structure ss [L] (ss[i] = j at
+        the left column of a pair, NONE elsewhere).  out: as in average_basepairing."""
+        idx = np.ascontiguousarray(idx, np.uint32); m = np.ascontiguousarray(mask, np.uint8)
+        ss = np.ascontiguousarray(ss, np.uint32)
+        assert m.ndim == 2 and m.shape[0] == len(idx) and ss.shape == (m.shape[1],)
+        L = m.shape[1]
+        p = np.zeros((L, L), np.float32) if out is None else out
+        assert p.dtype == np.float32 and p.shape == (L, L) and p.flags.c_contiguous
+        rc = self.o.lib.orc_pipeline_update_basepairing(self.h, len(idx), idx.ctypes.data, m.ctypes.data, L, ss.ctypes.data, p.ctypes.data)
+        if out is not None:
+            return rc
+        assert rc == 0, rc
+        return p
 
     def seconds(self):
         return [self.o.lib.orc_pipeline_seconds(self.h, i) for i in range(4)]

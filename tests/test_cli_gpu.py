@@ -63,22 +63,30 @@ def test_contralign_and_flags(oracle):
 def test_fourway_and_bp_update_flags(oracle, tmp_path):
     """-f (relax_fourway_consistency, dafs.cpp:377-444), --bp-update (root node, :919-934) and --bp-update1 (final structure,
     :1863-1869) through the command line and through the Python driver, against the oracle pipeline.  Parity unpinned:
-    the oracle restates dafs.cpp, which cannot be built in this image."""
+    the oracle restates dafs.cpp, which cannot be built in this image.  On the first family the oracle's final structure
+    has no pair, so --bp-update1 leaves its text as it is; on the two inputs of bp_update_cases.whole_run_inputs each of the
+    two flags changes it (test_bp_update_cpu.py::test_whole_runs_are_not_vacuous)."""
+    import bp_update_cases
     from dafs_amd import pipeline
-    recs = synth.family_set(6, 70, seed=31)
-    fa = tmp_path / "fam.fa"
-    fa.write_text(synth.to_fasta(recs))
-    names, seqs = [r[0] for r in recs], [r[1] for r in recs]
-    for args, kw, pkw in ((["-f", "0.4"], dict(w_pct_f=0.4), dict(w_pct_f=0.4)),
-                          (["--bp-update"], dict(bp_update=1), dict(bp_update=True)),
-                          (["--bp-update1"], dict(bp_update1=1), dict(bp_update1=True)),
-                          (["-f", "0.2", "--bp-update", "--bp-update1", "-m", "40"], dict(w_pct_f=0.2, bp_update=1, bp_update1=1, t_max=40),
-                           dict(w_pct_f=0.2, bp_update=True, bp_update1=True, t_max=40))):
-        want, _ = oracle_output(oracle, str(fa), **kw)
-        rc, out, err = run_cli(*(args + [str(fa)]))
-        assert rc == 0, err
-        assert out == want, args
-        assert pipeline.run(names, seqs, **pkw).output == want, args
+    inputs = [("fam", synth.to_fasta(synth.family_set(6, 70, seed=31)))] + bp_update_cases.whole_run_inputs()
+    for key, text in inputs:
+        fa = tmp_path / (key + ".fa")
+        fa.write_text(text)
+        recs = oracle.fasta(str(fa))
+        names, seqs = [r[0] for r in recs], [r[1] for r in recs]
+        plain, _ = oracle_output(oracle, str(fa))
+        for args, kw, pkw in ((["-f", "0.4"], dict(w_pct_f=0.4), dict(w_pct_f=0.4)),
+                              (["--bp-update"], dict(bp_update=1), dict(bp_update=True)),
+                              (["--bp-update1"], dict(bp_update1=1), dict(bp_update1=True)),
+                              (["-f", "0.2", "--bp-update", "--bp-update1", "-m", "40"], dict(w_pct_f=0.2, bp_update=1, bp_update1=1, t_max=40),
+                               dict(w_pct_f=0.2, bp_update=True, bp_update1=True, t_max=40))):
+            want, _ = oracle_output(oracle, str(fa), **kw)
+            if key != "fam" and len(args) == 1:
+                assert want != plain, (key, args)
+            rc, out, err = run_cli(*(args + [str(fa)]))
+            assert rc == 0, err
+            assert out == want, (key, args)
+            assert pipeline.run(names, seqs, **pkw).output == want, (key, args)
 
 
 def test_synthetic_family_verbose_log(oracle, tmp_path):

@@ -117,6 +117,7 @@ def _bits(results):
 def test_mixed_batch_against_the_oracle_and_the_single_call(batch, ctx, oracle):
     got, launches = _launches(ctx, lambda: ctx.consensus_structures(batch.alns, TH))
     assert len(got) == len(batch.alns)
+    pl = oracle.pipeline(["s%d" % k for k in range(len(LENS))], batch.seqs, oracle.params(fold_model=1), bp=batch.rows)
     assert launches == len({_size_class(m.shape[1]) for _, m in batch.alns}) == 3  # up to 256 columns; 257 and 262; 1 100
     for k, (score, ss) in enumerate(got):
         seq, mask = batch.alns[k]
@@ -126,6 +127,7 @@ def test_mixed_batch_against_the_oracle_and_the_single_call(batch, ctx, oracle):
             assert np.array_equal(p1, batch.p[k]), k  # the one row's own matrix, as supplied
             ws, wss = batch.want[k]
         else:
+            assert p1.tobytes() == pl.average_basepairing(seq, mask).tobytes(), k  # the rows' average: orc_pipeline_average_basepairing
             ws, wss = oracle.nussinov(p1, None, TH)
         assert ss.tobytes() == wss.tobytes() and np.float32(score).tobytes() == np.float32(ws).tobytes(), k
         paired = int(np.sum(wss != NONE))
@@ -135,6 +137,7 @@ def test_mixed_batch_against_the_oracle_and_the_single_call(batch, ctx, oracle):
             assert paired >= 1, k  # an all-unpaired answer cannot pass
         elif mask.shape[1] < 4:
             assert paired == 0
+    pl.close()
     # the multi-row averages depend on the order of the rows: the same rows in index order are another alignment
     seq, mask = batch.alns[batch.single_row + 1]
     order = np.argsort(seq)
