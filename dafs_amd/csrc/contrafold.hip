@@ -131,9 +131,23 @@ __device__ __forceinline__ float cf_single_nuc(const cf_ctx& c, int i, int j, in
 // nothing else.  Same terms, same order, same arithmetic: the values are bit-identical to the in-loop form, which
 // stays for constrained sequences and for cells whose list did not fit the pool.
 // ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t cf_ring_slot(const cf_ctx& c, int row, int col) {  // where the ring keeps cell (row, col)
+  return ((uint32_t)(col - row) % (uint32_t)CF_RING) * (uint32_t)(c.L + 1) + (uint32_t)row;
+}
 __device__ __forceinline__ float cf_fc_load(const cf_ctx& c, const float* FC, int row, int col) {  // FC[row][col], recent spans from LDS
-  if (c.has_ring) return c.ring[((uint32_t)(col - row) % (uint32_t)CF_RING) * (uint32_t)(c.L + 1) + (uint32_t)row];
+  if (c.has_ring) return c.ring[cf_ring_slot(c, row, col)];
   return FC[c.off[row] + col];
+}
+
+// The inside single-branch term, stated once: the term evaluation (cf_inside_terms) and both loops of cf_inside_cell call it.
+// sy, sp, sq_, sq1 = the symbols at p + 1, p, q, q + 1; inner = FC[p + 1][q - 1].  ScoreBasePair(p+1,q) and ScoreJunctionB(q,p)
+// from the symbols the caller has read, once per p or ahead of the term
+__device__ __forceinline__ float cf_in_term(const cf_ctx& c, int i, int j, int p, int q, int sy, int sp, int sq_, int sq1, float inner,
+                                            float score_helix, float score_other) {
+  const float bp = 0.0f + c.P->base_pair[sy * 5 + sq_];
+  const float jb = 0.0f + c.P->helix_closing[sq_ * 5 + sy] + c.P->terminal_mismatch[((sq_ * 5 + sy) * 5 + sq1) * 5 + sp];
+  return (p == i && q == j) ? (score_helix + inner)
+                            : (score_other + c.P->cache_single[(p - i) * 31 + (j - q)] + inner + bp + jb + cf_single_nuc(c, i, j, p, q));
 }
 __device__ __forceinline__ int cf_half_prefix(int n, int hl, int* total) {  // inclusive prefix over the 32 lanes of a half-wave
   int incl = n;
@@ -193,11 +207,7 @@ __device__ void cf_inside_terms(const cf_ctx& c, int d, const float* FCi, int bu
     for (int k = 0; k < n; ++k) {
       const int q = pl[ehi - k];
       const float inner = cf_fc_load(c, FCi, p + 1, q - 1);
-      const int sq_ = c.s[q], sq1 = c.s[q + 1];
-      const float bp = 0.0f + c.P->base_pair[sy * 5 + sq_];
-      const float jb = 0.0f + c.P->helix_closing[sq_ * 5 + sy] + c.P->terminal_mismatch[((sq_ * 5 + sy) * 5 + sq1) * 5 + sp];
-      out[k] = (p == i && q == j) ? (score_helix + inner)
-                                  : (score_other + c.P->cache_single[(p - i) * 31 + (j - q)] + inner + bp + jb + cf_single_nuc(c, i, j, p, q));
+      out[k] = cf_in_term(c, i, j, p, q, sy, sp, c.s[q], c.s[q + 1], inner, score_helix, score_other);
     }
   }
 }
@@ -324,11 +334,7 @@ __device__ void cf_inside_cell(const cf_ctx& c, int i, int j, float* FCi, float*
         for (;;) {
           const bool more = e >= 1;
           const int qn = more ? pl[e - 1] : -1;
-          const float bp = 0.0f + c.P->base_pair[sy * 5 + sq_];
-          const float jb = 0.0f + c.P->helix_closing[sq_ * 5 + sy] + c.P->terminal_mismatch[((sq_ * 5 + sy) * 5 + sq1) * 5 + sp];
-          const float score = (p == i && q == j)
-                                  ? (score_helix + inner)
-                                  : (score_other + c.P->cache_single[(p - i) * 31 + (j - q)] + inner + bp + jb + cf_single_nuc(c, i, j, p, q));
+          const float score = cf_in_term(c, i, j, p, q, sy, sp, sq_, sq1, inner, score_helix, score_other);
           const bool next_ok = more && qn >= q_min;
           float inner_n = 0.0f;
           int sqn = 4, sq1n = 4;
@@ -347,19 +353,14 @@ __device__ void cf_inside_cell(const cf_ctx& c, int i, int j, float* FCi, float*
         const float inner = cf_fc_load(c, FCi, p + 1, q - 1);
         // ScoreBasePair(p+1,q) and ScoreJunctionB(q,p) with the symbols of p and p+1 read once per p
         const int sq_ = c.s[q], sq1 = c.s[q + 1];
-        const float bp = 0.0f + c.P->base_pair[sy * 5 + sq_];
-        const float jb = 0.0f + c.P->helix_closing[sq_ * 5 + sy] + c.P->terminal_mismatch[((sq_ * 5 + sy) * 5 + sq1) * 5 + sp];
-        const float score = (p == i && q == j)
-                                ? (score_helix + inner)
-                                : (score_other + c.P->cache_single[(p - i) * 31 + (j - q)] + inner + bp + jb + cf_single_nuc(c, i, j, p, q));
-        sum = cf_lpe(sum, score);
+        sum = cf_lpe(sum, cf_in_term(c, i, j, p, q, sy, sp, sq_, sq1, inner, score_helix, score_other));
       }
     }
     sum = cf_lpe(sum, FM2i + cf_junction_a(c, i, j) + c.P->multi_paired + c.P->multi_base);
     FCi[off[i] + j] = sum;
     fc = sum;
   }
-  if (c.has_ring) c.ring[((uint32_t)(j - i) % (uint32_t)CF_RING) * (uint32_t)(L + 1) + (uint32_t)i] = fc;
+  if (c.has_ring) c.ring[cf_ring_slot(c, i, j)] = fc;
   if (0 < i && i + 2 <= j && j < L) {
     float sum = CONTRA_NEG_INF;
     if (cf_allow_paired(c, i + 1, j))
@@ -464,7 +465,7 @@ __device__ void cf_outside_cell(const cf_ctx& c, int a, int b, const float* FCi,
     }
     FCo[off[a] + b] = fco;
   }
-  if (c.has_ring) c.ring[((uint32_t)(b - a) % (uint32_t)CF_RING) * (uint32_t)(L + 1) + (uint32_t)a] = fco;
+  if (c.has_ring) c.ring[cf_ring_slot(c, a, b)] = fco;
 
   // ---- FM1o[a][b]: block 2 of source (a-1,b), block 4 of sources (a,j) j = L..b+1, block 1 of source (a,b)
   float fm1o = CONTRA_NEG_INF;
@@ -493,6 +494,11 @@ __device__ float cf_posterior_cell(const cf_ctx& c, int a, int q, const float* F
   const int* off = c.off;
   float acc = 0.0f;
   const float inner = FCi[off[p + 1] + q - 1];  // FCptr[q]
+  // multi-loop closing pair, :4741-4745: the addend of source (p,q), taken right after its single-branch block
+  auto multi = [&](float a) {
+    if (0 < p && p + 2 <= q) a += contra_exp(FM1o[off[p] + q] + inner + cf_junction_a(c, q, p) + c.P->multi_paired + cf_base_pair(c, p + 1, q) - Z);
+    return a;
+  };
   if (q < L) {  // single-branch sources need j >= q and j < L
     for (int i = p; i >= max(1, p - CF_MAX_SINGLE); i--) {
       const int l1 = p - i;
@@ -508,7 +514,7 @@ __device__ float cf_posterior_cell(const cf_ctx& c, int a, int q, const float* F
           const int l2 = j - q;
           if (l2 > 0 && !cf_all_unpaired(c, q, j)) break;
           if (!slot_done && j > q) {  // passed the (p,q) slot without a helix term
-            if (0 < p && p + 2 <= q) acc += contra_exp(FM1o[off[p] + q] + inner + cf_junction_a(c, q, p) + c.P->multi_paired + cf_base_pair(c, p + 1, q) - Z);
+            acc = multi(acc);
             slot_done = true;
           }
           if (!cf_map_ok(c, i, j + 1)) continue;
@@ -519,15 +525,13 @@ __device__ float cf_posterior_cell(const cf_ctx& c, int a, int q, const float* F
             term = contra_exp((outside + cf_junction_b(c, i, j)) + c.P->cache_single[l1 * 31 + l2] + inner + cf_base_pair(c, p + 1, q) +
                               cf_junction_b(c, q, p) + cf_single_nuc(c, i, j, p, q));
           acc += term;
-          if (i == p && j == q) {  // multi-loop closing pair, :4741-4745 (source (p,q), right after its single-branch block)
-            if (0 < p && p + 2 <= q) acc += contra_exp(FM1o[off[p] + q] + inner + cf_junction_a(c, q, p) + c.P->multi_paired + cf_base_pair(c, p + 1, q) - Z);
+          if (i == p && j == q) {
+            acc = multi(acc);
             slot_done = true;
           }
         }
       }
-      if (!slot_done) {
-        if (0 < p && p + 2 <= q) acc += contra_exp(FM1o[off[p] + q] + inner + cf_junction_a(c, q, p) + c.P->multi_paired + cf_base_pair(c, p + 1, q) - Z);
-      }
+      if (!slot_done) acc = multi(acc);
     }
   }
   // exterior, :4750-4760
@@ -781,23 +785,15 @@ __global__ __launch_bounds__(CF_THREADS) void k_contrafold_posterior(cf_batch B)
     post[c.off[a] + q] = (a >= 1 && q > a) ? cf_posterior_cell(c, a, q, FCi, F5i, F5o, FCo, FM1o, Z) : 0.0f;
 }
 
-// dense triangular posterior -> BP rows (i-1) -> (j-1, p) with p > th (fold.cpp:181-188)
-__global__ __launch_bounds__(256) void k_bp_compact(cf_batch B, float th, const uint64_t* rp_off, uint32_t* out_rowptr, uint32_t* out_col,
-                                                    float* out_val, uint64_t* out_off, uint32_t* out_nnz, unsigned long long* pool_top,
-                                                    uint64_t pool_cap, int* status) {
-  const uint32_t x = blockIdx.x;
-  const cf_seq sq = B.seqs[x];
-  const int L = (int)sq.len;
-  const float* post = B.post + sq.post_off;
-  uint32_t* rowptr = out_rowptr + rp_off[x];
+__device__ __forceinline__ int cf_tri_off(int L, int i) { return i * (2 * (L + 1) - i - 1) / 2; }  // row i of a triangular table
+
+// The step between counting and writing the rows of sequence x, by the whole workgroup: rowptr[1..L] hold the rows' counts;
+// thread 0 turns them into offsets and reserves the entries' room in the pool.  Returns whether the pool had the room
+// (DAFS_HIP_EOVERFLOW in *status otherwise), *first = where the sequence's entries start.
+__device__ __forceinline__ bool bp_rows_reserve(uint32_t* rowptr, int L, uint32_t x, uint64_t* out_off, uint32_t* out_nnz,
+                                                unsigned long long* pool_top, uint64_t pool_cap, int* status, unsigned long long* first) {
   __shared__ unsigned long long s_off;
   __shared__ int s_ok;
-  auto offs = [L](int i) { return i * (2 * (L + 1) - i - 1) / 2; };
-  for (int i = 1 + threadIdx.x; i <= L; i += blockDim.x) {
-    uint32_t n = 0;
-    for (int j = i; j <= L; ++j) n += post[offs(i) + j] > th ? 1 : 0;
-    rowptr[i] = n;
-  }
   __syncthreads();
   if (threadIdx.x == 0) {
     rowptr[0] = 0;
@@ -811,11 +807,30 @@ __global__ __launch_bounds__(256) void k_bp_compact(cf_batch B, float th, const 
     out_nnz[x] = n;
   }
   __syncthreads();
-  if (!s_ok) return;
+  *first = s_off;
+  return s_ok;
+}
+
+// dense triangular posterior -> BP rows (i-1) -> (j-1, p) with p > th (fold.cpp:181-188); a thread per row
+__global__ __launch_bounds__(256) void k_bp_compact(cf_batch B, float th, const uint64_t* rp_off, uint32_t* out_rowptr, uint32_t* out_col,
+                                                    float* out_val, uint64_t* out_off, uint32_t* out_nnz, unsigned long long* pool_top,
+                                                    uint64_t pool_cap, int* status) {
+  const uint32_t x = blockIdx.x;
+  const cf_seq sq = B.seqs[x];
+  const int L = (int)sq.len;
+  const float* post = B.post + sq.post_off;
+  uint32_t* rowptr = out_rowptr + rp_off[x];
   for (int i = 1 + threadIdx.x; i <= L; i += blockDim.x) {
-    unsigned long long pos = s_off + rowptr[i - 1];
+    uint32_t n = 0;
+    for (int j = i; j <= L; ++j) n += post[cf_tri_off(L, i) + j] > th ? 1 : 0;
+    rowptr[i] = n;
+  }
+  unsigned long long first;
+  if (!bp_rows_reserve(rowptr, L, x, out_off, out_nnz, pool_top, pool_cap, status, &first)) return;
+  for (int i = 1 + threadIdx.x; i <= L; i += blockDim.x) {
+    unsigned long long pos = first + rowptr[i - 1];
     for (int j = i; j <= L; ++j) {
-      const float v = post[offs(i) + j];
+      const float v = post[cf_tri_off(L, i) + j];
       if (v > th) { out_col[pos] = (uint32_t)(j - 1); out_val[pos] = v; ++pos; }
     }
   }
@@ -825,8 +840,7 @@ __global__ __launch_bounds__(256) void k_bp_compact(cf_batch B, float th, const 
 // of the batch (1 to 4, all of its length), and a cell's value is the fmaxf over their dense posteriors, taken in fold order --
 // exact, so the result does not depend on how the work is laid out; no floating-point atomics.  One workgroup per sequence, one
 // wavefront per row i, lanes along j: 64 neighbouring cells per load, the row's count is the popcount of the ballots, and an
-// entry's place is the row's running count plus the ballot's prefix below its lane, which keeps the columns ascending.  The
-// row-pointer scan and the reservation in the entry pool are k_bp_compact's.
+// entry's place is the row's running count plus the ballot's prefix below its lane, which keeps the columns ascending.
 __global__ __launch_bounds__(256) void k_bp_compact_levels(cf_batch B, float th, const uint32_t* first, const uint64_t* rp_off, uint32_t* out_rowptr,
                                                            uint32_t* out_col, float* out_val, uint64_t* out_off, uint32_t* out_nnz,
                                                            unsigned long long* pool_top, uint64_t pool_cap, int* status) {
@@ -838,10 +852,7 @@ __global__ __launch_bounds__(256) void k_bp_compact_levels(cf_batch B, float th,
   const float* p2 = nf > 2 ? B.post + B.seqs[f0 + 2].post_off : p0;
   const float* p3 = nf > 3 ? B.post + B.seqs[f0 + 3].post_off : p0;
   uint32_t* rowptr = out_rowptr + rp_off[x];
-  __shared__ unsigned long long s_off;
-  __shared__ int s_ok;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, waves = blockDim.x >> 6;
-  auto offs = [L](int i) { return i * (2 * (L + 1) - i - 1) / 2; };
   auto cell = [&](int at) {  // fold order; a fold the sequence does not have repeats the first, which changes nothing
     float v = p0[at];
     if (nf > 1) v = fmaxf(v, p1[at]);
@@ -853,30 +864,18 @@ __global__ __launch_bounds__(256) void k_bp_compact_levels(cf_batch B, float th,
     uint32_t n = 0;
     for (int j0 = i; j0 <= L; j0 += 64) {
       const int j = j0 + lane;
-      const bool keep = j <= L && cell(offs(i) + j) > th;
+      const bool keep = j <= L && cell(cf_tri_off(L, i) + j) > th;
       n += (uint32_t)__popcll(__ballot(keep));
     }
     if (lane == 0) rowptr[i] = n;
   }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    rowptr[0] = 0;
-    for (int i = 0; i < L; ++i) rowptr[i + 1] += rowptr[i];
-    const uint32_t n = rowptr[L];
-    const unsigned long long o = atomicAdd(pool_top, (unsigned long long)n);
-    s_off = o;
-    s_ok = o + n <= pool_cap;
-    if (!s_ok) atomicExch(status, DAFS_HIP_EOVERFLOW);
-    out_off[x] = o;
-    out_nnz[x] = n;
-  }
-  __syncthreads();
-  if (!s_ok) return;
+  unsigned long long first_entry;
+  if (!bp_rows_reserve(rowptr, L, x, out_off, out_nnz, pool_top, pool_cap, status, &first_entry)) return;
   for (int i = 1 + wave; i <= L; i += waves) {
-    unsigned long long pos = s_off + rowptr[i - 1];
+    unsigned long long pos = first_entry + rowptr[i - 1];
     for (int j0 = i; j0 <= L; j0 += 64) {
       const int j = j0 + lane;
-      const float v = j <= L ? cell(offs(i) + j) : 0.0f;
+      const float v = j <= L ? cell(cf_tri_off(L, i) + j) : 0.0f;
       const bool keep = j <= L && v > th;
       const uint64_t b = __ballot(keep);
       if (keep) {
@@ -891,6 +890,13 @@ __global__ __launch_bounds__(256) void k_bp_compact_levels(cf_batch B, float th,
 
 constexpr size_t kCfDynBudget = 100 * 1024;      // integer tables and ring of k_contrafold; the most k_contrafold_posterior asks for
 constexpr size_t kCfLdsTotal = 160 * 1024 - 512;  // static + dynamic LDS of k_contrafold
+// The longest list of a cell: one term per (l1, l2) with l1, l2 >= 0 and l1 + l2 <= CF_MAX_SINGLE unpaired positions on the two
+// sides, when every one of them pairs (a GC repeat comes close): 31 + 30 + ... + 1.  A pool buffer that cannot hold it is no pool.
+constexpr size_t kCfLongestList = (CF_MAX_SINGLE + 1) * (CF_MAX_SINGLE + 2) / 2;
+static_assert(kCfLongestList == 496, "the launch plan's switch points are documented and tested for 496 terms");
+// Terms per row of a span that a buffer should hold: the typical demand, that of a random sequence (3/8 of the cells close a
+// pair, ~150 terms each) with room to spare
+constexpr size_t kCfTypicalTerms = 80;
 
 }  // namespace dafs
 
@@ -917,8 +923,8 @@ extern "C" int dafs_hipk_contrafold_plan(uint32_t max_len, uint32_t static_lds, 
     else (void)hipGetLastError();
   }
   const size_t pool_ints = (4 * ((size_t)max_len + 1) + 2) * sizeof(int);
-  const size_t pool_want = (size_t)80 * (max_len + 1) * sizeof(float);
-  const bool pool_on = !getenv("DAFS_HIP_CF_NOPOOL") && stat + ints + pool_ints + 2 * 496 * sizeof(float) <= total;
+  const size_t pool_want = kCfTypicalTerms * (max_len + 1) * sizeof(float);
+  const bool pool_on = !getenv("DAFS_HIP_CF_NOPOOL") && stat + ints + pool_ints + 2 * kCfLongestList * sizeof(float) <= total;
   int use_ring = ints + ring <= budget && !getenv("DAFS_HIP_CF_NORING");  // the env switches are tuning aids
   if (use_ring && pool_on && stat + ints + ring + pool_ints + pool_want > total) use_ring = 0;
   size_t lds = ints + (use_ring ? ring : 0);

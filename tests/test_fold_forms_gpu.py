@@ -197,6 +197,17 @@ def test_lists_overflow_the_pool_without_the_ring(ctx, oracle, device_plan):
     check_fold(ctx, oracle, "GC" * (L // 2), tag="GC repeat")
 
 
+def test_lists_overflow_a_half_of_the_pool_with_the_ring(ctx, oracle, device_plan):
+    """the same repeat at the even length up to La: two buffers and the ring, so the wavefronts without cells lay out the next
+    span's lists beside the cells of this one, most lists do not fit their half, and the cells that walk their partners
+    themselves read FC from the ring"""
+    _, la, _ = device_plan
+    s = "GC" * (la // 2)
+    want, wz = orc_fold(oracle, s)
+    assert not np.isnan(want).any() and not np.isnan(wz)
+    check_fold(ctx, oracle, s, tag="GC repeat, two buffers")
+
+
 # ----- the chunked F5 chain
 
 CHUNKED = [(64, L) for L in (63, 64, 65, 128, 129, 200)] + [(128, 300)]
