@@ -198,6 +198,14 @@ _bootstrap_alignment = _sig("dafs_hip_bootstrap_alignment", C.c_int, [C.c_void_p
 bootstrap_fixups = _sig("dafs_hip_bootstrap_fixups", C.c_uint64, [])
 _tree_support = _sig("dafs_host_tree_support", C.c_int, [C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p])
 BOOTSTRAP_MAX = 65536
+_alignment_bootstrap_transfer = _sig("dafs_hip_alignment_bootstrap_transfer", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                                                                       C.c_int, C.c_uint32, C.c_uint64] + [C.c_void_p] * 6)
+_tree_transfer = _sig("dafs_hip_tree_transfer", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32] + [C.c_void_p] * 4)
+tree_transfer_workspace = _sig("dafs_hipk_tree_transfer_workspace", C.c_size_t, [C.c_uint32, C.c_uint32])
+tree_transfer_launch = _sig("dafs_hipk_tree_transfer", C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32] + [C.c_void_p] * 8)
+_transfer_runs = _sig("dafs_host_transfer_runs", C.c_int, [C.c_uint32] + [C.c_void_p] * 5)
+_split_depth = _sig("dafs_host_split_depth", C.c_int, [C.c_uint32] + [C.c_void_p] * 3)
+_transfer_percent = _sig("dafs_host_transfer_percent", C.c_int32, [C.c_int64, C.c_uint32, C.c_uint32])
 NJ_MAX_ROWS = 16384
 COV_TREES = ("average", "nj")  # --cov-tree
 _merge_added = _sig("dafs_host_merge_added", C.c_int, [C.c_uint32, C.c_uint32] + [C.c_void_p] * 5)
@@ -315,6 +323,10 @@ _phylogeny_refusal = _sig("dafs_host_phylogeny_refusal", C.c_char_p, [C.c_int])
 (PHY_NO_PAIRWISE, PHY_NO_SEED_EACH, PHY_TOO_MANY_ROWS, PHY_MODEL_NEEDS_TREE, PHY_UNKNOWN_MODEL, PHY_COV_TREE_NEEDS_NULL,
  PHY_UNKNOWN_COV_TREE) = range(7)  # dafs_host_phylogeny_refusal
 _bootstrap_refusal = _sig("dafs_host_bootstrap_refusal", C.c_char_p, [C.c_int])
+_newick_transfer = _sig("dafs_host_newick_transfer", C.c_int, [C.c_uint32, _strs] + [C.c_void_p] * 4 + [C.c_uint32, _text])
+_transfer_table = _sig("dafs_host_transfer_table", C.c_int, [C.c_uint32, _strs] + [C.c_void_p] * 4 + [C.c_uint32, C.c_uint64, C.c_int, _text])
+_transfer_refusal = _sig("dafs_host_transfer_refusal", C.c_char_p, [C.c_int])
+TRANSFER_NEEDS_REPLICATES = 0  # dafs_host_transfer_refusal
 BOOT_NEEDS_TREE, BOOT_COUNT, BOOT_NEEDS_REPLICATES, BOOT_NO_COLUMN = range(4)  # dafs_host_bootstrap_refusal
 _seed_table_nearest = _sig("dafs_host_seed_table_nearest", C.c_int, [C.c_uint32, _strs] + [C.c_void_p] * 8 + [_strs, C.c_void_p, _text])
 # dafs_allgather_fn(user, send, recv, bytes, hip_stream): the caller's collective of a sharded phase 1
@@ -780,12 +792,15 @@ class Context:
         check(rc)
         return left.astype(np.int64), right.astype(np.int64), length
 
-    def alignment_bootstrap(self, cell, use=None, model="jc", B=100, seed=12345, tree=None, trees=False):
+    def alignment_bootstrap(self, cell, use=None, model="jc", B=100, seed=12345, tree=None, trees=False, transfer=False):
         """Bootstrap support of a tree of an alignment's rows (dafs_hip_alignment_bootstrap): B replicate
         alignments drawn from the used columns with replacement, their distances under `model` and their neighbour-joining
         trees, all on the device.  tree: (left, right) or (left, right, length) of the main tree; None: alignment_tree(cell,
         use, model).  Returns support (int64 [2n-1]: the number of replicate trees holding the node's split, -1 for the root
-        and trivial splits); with trees=True (support, rep_left, rep_right), the replicate trees as [B, 2n-1]."""
+        and trivial splits); with trees=True (support, rep_left, rep_right), the replicate trees as [B, 2n-1].  transfer=True
+        (dafs_hip_alignment_bootstrap_transfer) appends the transfer sums (int64 [2n-1]: per split the
+        sum over the replicates of its transfer index, -1 where support is -1) to what is returned: (support, transfer) or
+        (support, rep_left, rep_right, transfer)."""
         if model not in NJ_MODELS:
             raise ValueError(phylogeny_refusal(PHY_UNKNOWN_MODEL))
         cell = _cells(cell, "alignment_bootstrap")
@@ -803,14 +818,41 @@ class Context:
             raise ValueError("alignment_bootstrap: a tree of n rows has 2n - 1 nodes")
         support = np.zeros(2 * n - 1, np.int32)
         rep = [np.zeros((int(B), 2 * n - 1), np.int32) for _ in range(2)] if trees else [None, None]
-        rc = _alignment_bootstrap(self._h, n, L, cell.ctypes.data, None if use is None else use.ctypes.data, NJ_MODELS.index(model), int(B),
-                                  int(seed) & 0xFFFFFFFFFFFFFFFF, left.ctypes.data, right.ctypes.data, support.ctypes.data,
-                                  None if rep[0] is None else rep[0].ctypes.data, None if rep[1] is None else rep[1].ctypes.data)
+        sums = np.zeros(2 * n - 1, np.int64) if transfer else None
+        args = (self._h, n, L, cell.ctypes.data, None if use is None else use.ctypes.data, NJ_MODELS.index(model), int(B),
+                int(seed) & 0xFFFFFFFFFFFFFFFF, left.ctypes.data, right.ctypes.data, support.ctypes.data,
+                None if rep[0] is None else rep[0].ctypes.data, None if rep[1] is None else rep[1].ctypes.data)
+        rc = _alignment_bootstrap_transfer(*args, sums.ctypes.data) if transfer else _alignment_bootstrap(*args)
         if rc == -1:
             raise ValueError(_last_error().decode("latin-1"))
         check(rc)
         support = support.astype(np.int64)
-        return (support, rep[0].astype(np.int64), rep[1].astype(np.int64)) if trees else support
+        out = (support, rep[0].astype(np.int64), rep[1].astype(np.int64)) if trees else (support,)
+        if transfer:
+            return out + (sums,)
+        return out if trees else support
+
+    def tree_transfer(self, tree, rep_left, rep_right, each=False):
+        """Transfer bootstrap of a tree against replicate trees (dafs_hip_tree_transfer).  tree: (left,
+        right[, length]) of the main tree; rep_left, rep_right: [B, 2n-1].  Returns transfer (int64 [2n-1]: per split the sum
+        over the replicates of the transfer index, the fewest leaves that have to move for the replicate to hold the split;
+        -1 for the root and trivial splits); with each=True (transfer, phi), phi int64 [B, 2n-1] the index per replicate."""
+        left = np.ascontiguousarray(tree[0], np.int32).reshape(-1)
+        right = np.ascontiguousarray(tree[1], np.int32).reshape(-1)
+        rep_left = np.ascontiguousarray(rep_left, np.int32)
+        rep_right = np.ascontiguousarray(rep_right, np.int32)
+        T = len(left)
+        if T % 2 != 1 or len(right) != T or rep_left.ndim != 2 or rep_left.shape[1] != T or rep_right.shape != rep_left.shape:
+            raise ValueError("tree_transfer: a tree of n leaves has 2n - 1 nodes and the replicates are [B, 2n - 1]")
+        B = rep_left.shape[0]
+        sums = np.zeros(T, np.int64)
+        phi = np.zeros((B, T), np.int32) if each else None
+        rc = _tree_transfer(self._h, (T + 1) // 2, left.ctypes.data, right.ctypes.data, B, rep_left.ctypes.data, rep_right.ctypes.data,
+                            sums.ctypes.data, None if phi is None else phi.ctypes.data)
+        if rc == -1:
+            raise ValueError(_last_error().decode("latin-1"))
+        check(rc)
+        return (sums, phi.astype(np.int64)) if each else sums
 
     def bootstrap_alignment(self, cell, k, use=None, seed=12345):
         """Replicate k (0-based) behind alignment_bootstrap(cell, use, seed=seed) as cells (uint8 [n, U], U the number of used
@@ -1647,6 +1689,56 @@ def bootstrap_refusal(which):
     return _bootstrap_refusal(which).decode()
 
 
+def transfer_refusal(which):
+    """what both drivers say when they refuse the transfer option (dafs_host_transfer_refusal)"""
+    return _transfer_refusal(which).decode()
+
+
+def split_depth(left, right):
+    """dafs_host_split_depth: per node of the tree the depth of its split, the size of the smaller side, as int64 [2n-1]; -1
+    for the root and for a split with fewer than two leaves on a side"""
+    left = np.ascontiguousarray(left, np.int32).reshape(-1)
+    right = np.ascontiguousarray(right, np.int32).reshape(-1)
+    T = len(left)
+    if T % 2 != 1 or len(right) != T:
+        raise ValueError("split_depth: a tree of n leaves has 2n - 1 nodes")
+    depth = np.zeros(T, np.int32)
+    rc = _split_depth((T + 1) // 2, left.ctypes.data, right.ctypes.data, depth.ctypes.data)
+    if rc == -1:
+        raise ValueError(_last_error().decode("latin-1"))
+    check(rc)
+    return depth.astype(np.int64)
+
+
+def transfer_percent(transfer, depth, B):
+    """dafs_host_transfer_percent: the transfer bootstrap expectation of a split in percent, (200 (M - transfer) + M) / (2 M)
+    with M = B (depth - 1) in integer division (halves round up).  ValueError for depth < 2, B = 0 or a sum outside 0 .. M."""
+    if not (0 <= int(transfer) < 2 ** 63 and 0 <= int(depth) < 2 ** 31 and 0 <= int(B) < 2 ** 32):
+        raise ValueError("transfer_percent: a transfer sum, a depth and a number of replicates that are not negative")
+    p = _transfer_percent(int(transfer), int(depth), int(B))
+    if p < 0:
+        raise ValueError("transfer_percent: depth >= 2, B >= 1 and a transfer sum in 0 .. B (depth - 1)")
+    return p
+
+
+def transfer_table(names, left, right, support, transfer, replicates, seed=12345, model="jc"):
+    """dafs_host_transfer_table: the text of `dafs --phylogeny-support` under --phylogeny-transfer -- "# rows n replicates B
+    seed S model M measure transfer", then per non-trivial split "node support B percent size leaves depth transfer tbe",
+    tab-separated"""
+    if model not in NJ_MODELS:
+        raise ValueError(phylogeny_refusal(PHY_UNKNOWN_MODEL))
+    names = list(names)
+    n = len(names)
+    left = np.ascontiguousarray(left, np.int32).reshape(-1)
+    right = np.ascontiguousarray(right, np.int32).reshape(-1)
+    support = np.ascontiguousarray(support, np.int32).reshape(-1)
+    transfer = np.ascontiguousarray(transfer, np.int64).reshape(-1)
+    if n == 0 or any(len(a) != 2 * n - 1 for a in (left, right, support, transfer)):
+        raise ValueError("transfer_table: a tree of n names has 2n - 1 nodes")
+    return host_text(_transfer_table, n, c_strings(names), left.ctypes.data, right.ctypes.data, support.ctypes.data, transfer.ctypes.data,
+                     int(replicates), int(seed) & 0xFFFFFFFFFFFFFFFF, NJ_MODELS.index(model))
+
+
 def nj_distances(ident, aligned, model="jc"):
     """dafs_host_nj_distances: the float64 [n, n] distances of an alignment's rows from the integer
     matrices of Context.alignment_identity(matrix=True), under the model "jc" (Jukes-Cantor, quantised to 2^-20 and capped at
@@ -1702,11 +1794,13 @@ def support_table(names, left, right, support, replicates, seed=12345, model="jc
                      int(seed) & 0xFFFFFFFFFFFFFFFF, NJ_MODELS.index(model))
 
 
-def newick(names, left, right, length=None, support=None, replicates=None):
+def newick(names, left, right, length=None, support=None, replicates=None, transfer=None, depth=None):
     """dafs_host_newick: the tree (left, right in build_tree's layout, length per node or None for the topology alone) as one
     Newick line ending in ";\n": "(L:len,R:len)" nested with the left child first, lengths as %.9g, none on the root, names
     quoted where they hold any of ()[]':;, or white space.  ValueError for a malformed tree.  support (per node, -1: none)
-    and replicates: dafs_host_newick_support, the support in percent as the label of the joins."""
+    and replicates: dafs_host_newick_support, the support in percent as the label of the joins.
+    transfer (per node, -1: none) and replicates: dafs_host_newick_transfer, the transfer bootstrap expectation in percent as
+    the labels instead (section 28); depth, if given, must be split_depth(left, right), which the library uses."""
     names = list(names)
     n = len(names)
     left = np.ascontiguousarray(left, np.int32).reshape(-1)
@@ -1717,6 +1811,14 @@ def newick(names, left, right, length=None, support=None, replicates=None):
         length = np.ascontiguousarray(length, np.float64).reshape(-1)
         if len(length) != 2 * n - 1:
             raise ValueError("newick: one length per node")
+    if transfer is not None:
+        transfer = np.ascontiguousarray(transfer, np.int64).reshape(-1)
+        if len(transfer) != 2 * n - 1 or replicates is None:
+            raise ValueError("newick: one transfer sum per node and the number of replicates")
+        if depth is not None and not np.array_equal(np.asarray(depth, np.int64).reshape(-1), split_depth(left, right)):
+            raise ValueError("newick: depth is not the depth of the tree's splits")
+        return host_text(_newick_transfer, n, c_strings(names), left.ctypes.data, right.ctypes.data,
+                         None if length is None else length.ctypes.data, transfer.ctypes.data, int(replicates))
     if support is not None:
         support = np.ascontiguousarray(support, np.int32).reshape(-1)
         if len(support) != 2 * n - 1 or replicates is None:

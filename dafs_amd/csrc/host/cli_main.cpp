@@ -105,6 +105,7 @@ struct Options {
   uint64_t phylogeny_seed = 12345;   // --phylogeny-seed S
   std::string phylogeny_support;     // --phylogeny-support OUT: the table of the splits
   bool phylogeny_bootstrap_given = false, phylogeny_seed_given = false;
+  bool phylogeny_transfer = false;  // --phylogeny-transfer: the labels and the table show the transfer bootstrap
   bool cov_tree_nj = false;     // --cov-tree nj: the tree null evolves along the neighbour-joining tree
   bool cov_tree_given = false;
   bool seed_nearest = false;    // --seed-nearest: two more columns in --seed-scores
@@ -218,6 +219,10 @@ const char* kHelp =
     "      --phylogeny-support OUT  With --phylogeny-bootstrap: also write the table of the splits to OUT, laid out as --phylogeny\n"
     "                        lays out its lines: \"# rows n replicates B seed S model M\", then per split, tab-separated:\n"
     "                        node support B percent size leaves (the rows on the side without the first row)\n"
+    "      --phylogeny-transfer  With --phylogeny-bootstrap: the labels are the transfer bootstrap expectation in percent (how\n"
+    "                        few rows would have to move for the replicate trees to hold the split) instead of the share of the\n"
+    "                        replicate trees that hold it exactly, the table's header ends in \"measure transfer\" and every line\n"
+    "                        gains depth transfer tbe\n"
     "      --identity OUT    Also write how similar the rows of every printed alignment are to OUT: the line\n"
     "                        \"# rows n columns len average A min B max C\" (pairwise identity over all row pairs), then one\n"
     "                        tab-separated line per row: r name residues weight nearest nearest_name pid (1-based rows; residues:\n"
@@ -357,6 +362,7 @@ Options parse(int argc, char** argv) {
       {"covariation", {0, true}}, {"cov-shuffles", {0, true}}, {"cov-seed", {0, true}}, {"cov-null", {0, true}}, {"identity", {0, true}},
       {"phylogeny", {0, true}}, {"phylogeny-model", {0, true}}, {"cov-tree", {0, true}},
       {"phylogeny-bootstrap", {0, true}}, {"phylogeny-seed", {0, true}}, {"phylogeny-support", {0, true}},
+      {"phylogeny-transfer", {0, false}},
       {"identity-matrix", {0, true}}, {"seed-nearest", {0, false}}, {"seed-nr", {0, true}}, {"describe", {0, true}},
       {"compare", {0, true}}, {"compare-ref", {0, true}}, {"compare-columns", {0, true}}, {"compare-matrix", {0, true}},
       {"cluster", {0, true}}, {"cluster-count", {0, true}}, {"cluster-min-size", {0, true}}, {"cluster-table", {0, true}},
@@ -458,6 +464,7 @@ Options parse(int argc, char** argv) {
     else if (name == "seed-each") o.seed_each = true;
     else if (name == "seed-structure") o.seed_structure = true;
     else if (name == "knots") o.knots = true;
+    else if (name == "phylogeny-transfer") o.phylogeny_transfer = true;
     else if (name == "seed-scores") {
       if (value.empty()) throw std::string("--seed-scores needs a file name");
       o.seed_scores = value;
@@ -637,6 +644,7 @@ Options parse(int argc, char** argv) {
     throw std::string(dafs_host_bootstrap_refusal(DAFS_BOOTSTRAP_NEEDS_TREE));
   if ((o.phylogeny_seed_given || !o.phylogeny_support.empty()) && !o.phylogeny_bootstrap_given)
     throw std::string(dafs_host_bootstrap_refusal(DAFS_BOOTSTRAP_NEEDS_REPLICATES));
+  if (o.phylogeny_transfer && !o.phylogeny_bootstrap_given) throw std::string(dafs_host_transfer_refusal(DAFS_TRANSFER_NEEDS_REPLICATES));
   if (o.pairwise && !o.phylogeny.empty()) throw std::string(dafs_host_phylogeny_refusal(DAFS_PHYLOGENY_NO_PAIRWISE));
   if (o.seed_each && !o.phylogeny.empty()) throw std::string(dafs_host_phylogeny_refusal(DAFS_PHYLOGENY_NO_SEED_EACH));
   if (o.pairwise && (!o.covariation.empty() || o.cov_shuffles_given || o.cov_seed_given))
@@ -1087,7 +1095,8 @@ void nj_of(dafs_hip_ctx* ctx, int model, const std::vector<std::string>& rows, s
 }
 
 // --phylogeny: the Newick line of one printed alignment; names: the rows' Stockholm names.  With --phylogeny-bootstrap the joins
-// carry their support and table is the text of --phylogeny-support.
+// carry their support and table is the text of --phylogeny-support; with --phylogeny-transfer both show
+// the transfer bootstrap (section 28).
 void phylogeny_of(dafs_hip_ctx* ctx, const Options& o, const std::vector<std::string>& names, const std::vector<std::string>& rows, std::string& newick,
                   std::string& table) {
   std::vector<int32_t> left, right;
@@ -1102,6 +1111,17 @@ void phylogeny_of(dafs_hip_ctx* ctx, const Options& o, const std::vector<std::st
   }
   const std::vector<uint8_t> cell = cells_of(rows);
   std::vector<int32_t> support(2 * (size_t)n - 1, -1);
+  if (o.phylogeny_transfer) {
+    std::vector<int64_t> transfer(2 * (size_t)n - 1, -1);
+    check_text(dafs_hip_alignment_bootstrap_transfer(ctx, n, (uint32_t)rows[0].size(), cell.data(), nullptr, o.phylogeny_model, o.phylogeny_bootstrap,
+                                                     o.phylogeny_seed, left.data(), right.data(), support.data(), nullptr, nullptr, transfer.data()));
+    check_text(dafs_host_newick_transfer(n, c_strs(names).data(), left.data(), right.data(), length.data(), transfer.data(), o.phylogeny_bootstrap, &text));
+    newick = take(text);
+    check_text(dafs_host_transfer_table(n, c_strs(names).data(), left.data(), right.data(), support.data(), transfer.data(), o.phylogeny_bootstrap,
+                                        o.phylogeny_seed, o.phylogeny_model, &text));
+    table = take(text);
+    return;
+  }
   check_text(dafs_hip_alignment_bootstrap(ctx, n, (uint32_t)rows[0].size(), cell.data(), nullptr, o.phylogeny_model, o.phylogeny_bootstrap,
                                           o.phylogeny_seed, left.data(), right.data(), support.data(), nullptr, nullptr));
   check_text(dafs_host_newick_support(n, c_strs(names).data(), left.data(), right.data(), length.data(), support.data(), o.phylogeny_bootstrap, &text));

@@ -566,6 +566,15 @@ extern "C" const char* dafs_host_bootstrap_refusal(int which) {
   }
 }
 
+extern "C" const char* dafs_host_transfer_refusal(int which) {
+  switch (which) {
+    case DAFS_TRANSFER_NEEDS_REPLICATES:
+      return "the transfer bootstrap (--phylogeny-transfer, phylogeny_transfer) needs bootstrap replicates (--phylogeny-bootstrap, phylogeny_bootstrap)";
+    default:
+      return "";
+  }
+}
+
 namespace {
 
 // (200 s + B) / (2 B) in integers: the share of the replicates in percent, halves rounded up
@@ -579,15 +588,56 @@ uint32_t silent_root_child(uint32_t n, const int32_t* left, const int32_t* right
   return (uint32_t)left[root] >= n ? (uint32_t)right[root] : UINT32_MAX;
 }
 
+// per node the depth of its split, min(leaves below, the rest); -1 for the root and trivial splits (a well-formed tree)
+std::vector<int32_t> split_depths(uint32_t n, const int32_t* left, const int32_t* right) {
+  const uint32_t T = 2 * n - 1;
+  std::vector<uint32_t> below(T, 1);
+  std::vector<int32_t> depth(T, -1);
+  for (uint32_t v = 0; v + 1 < T; ++v) {
+    if (v >= n) below[v] = below[(uint32_t)left[v]] + below[(uint32_t)right[v]];
+    const uint32_t d = std::min(below[v], n - below[v]);
+    if (d >= 2) depth[v] = (int32_t)d;
+  }
+  return depth;
+}
+
+// the transfer bootstrap expectation in percent, halves rounded up like support_percent; what the
+// sum cannot be for its split and B throws
+uint32_t transfer_percent(const char* who, int64_t transfer, int32_t depth, uint32_t B) {
+  if (depth < 2 || !B) throw std::string(who) + ": a transfer sum on a trivial split";
+  const uint64_t most = (uint64_t)B * (uint64_t)(depth - 1);
+  if (transfer < 0 || (uint64_t)transfer > most) throw std::string(who) + ": a transfer sum above replicates x (depth - 1)";
+  return (uint32_t)((200ull * (most - (uint64_t)transfer) + most) / (2ull * most));
+}
+
 }  // namespace
+
+extern "C" int32_t dafs_host_transfer_percent(int64_t transfer, uint32_t depth, uint32_t B) {
+  if (depth < 2 || depth > 0x7FFFFFFFu || !B || transfer < 0 || (uint64_t)transfer > (uint64_t)B * (depth - 1)) return -1;
+  return (int32_t)transfer_percent("transfer percent", transfer, (int32_t)depth, B);
+}
+
+extern "C" int dafs_host_split_depth(uint32_t n, const int32_t* left, const int32_t* right, int32_t* depth) {
+  auto refuse = [](const std::string& why) { dafs::set_last_error(why.c_str()); return DAFS_HIP_EINVAL; };
+  if (!n || !left || !right || !depth) return refuse("split depth: invalid argument");
+  if (const char* bad = dafs::tree_malformed(n, left, right)) return refuse(std::string("split depth: ") + bad);
+  try {
+    const std::vector<int32_t> d = split_depths(n, left, right);
+    std::copy(d.begin(), d.end(), depth);
+  } catch (const std::bad_alloc&) {
+    return DAFS_HIP_ENOMEM;
+  }
+  return DAFS_HIP_OK;
+}
 
 // The Newick line of a tree in the arrays of dafs_host_build_tree.  The walk keeps its own stack of
 // (node, next step), so a chain of any depth uses none of the call stack.  support (or null) labels the joins (section 23).
+// transfer (or null; section 28) labels them with the transfer bootstrap expectation instead, under the same root-child rule.
 static int newick_text(uint32_t n, const char* const* names, const int32_t* left, const int32_t* right, const double* length,
-                       const int32_t* support, uint32_t B, char** out) {
+                       const int32_t* support, uint32_t B, char** out, const int64_t* transfer = nullptr) {
   return text_out(out, [&]() {
     if (!n || !left || !right) throw kBadArgument;
-    if (support && !B) throw std::string("newick: support values need the number of replicates");
+    if ((support || transfer) && !B) throw std::string("newick: support values need the number of replicates");
     if (n > 0x7FFFFFFFu / 2) throw std::string("newick: too many leaves");
     const std::vector<std::string> nm = strings(n, names);
     const uint32_t T = 2 * n - 1;
@@ -614,7 +664,8 @@ static int newick_text(uint32_t n, const char* const* names, const int32_t* left
       for (char ch : s) { q += ch; if (ch == '\'') q += '\''; }
       return q + "'";
     };
-    const uint32_t silent = support ? silent_root_child(n, left, right) : UINT32_MAX;
+    const uint32_t silent = support || transfer ? silent_root_child(n, left, right) : UINT32_MAX;
+    const std::vector<int32_t> depth = transfer ? split_depths(n, left, right) : std::vector<int32_t>();
     std::string text;
     std::vector<std::pair<uint32_t, uint8_t> > stack;
     stack.push_back(std::make_pair(T - 1, (uint8_t)0));
@@ -637,6 +688,8 @@ static int newick_text(uint32_t n, const char* const* names, const int32_t* left
           if ((uint32_t)support[node] > B) throw std::string("newick: a support value above the number of replicates");
           text += std::to_string(support_percent(support[node], B));
         }
+        if (transfer && node != T - 1 && node != silent && transfer[node] >= 0)
+          text += std::to_string(transfer_percent("newick", transfer[node], depth[node], B));
       }
       if (length && node != T - 1) text += ":" + fmt9d(length[node]);
       stack.pop_back();
@@ -657,6 +710,15 @@ extern "C" int dafs_host_newick_support(uint32_t n, const char* const* names, co
     return DAFS_HIP_EINVAL;
   }
   return newick_text(n, names, left, right, length, support, B, out);
+}
+
+extern "C" int dafs_host_newick_transfer(uint32_t n, const char* const* names, const int32_t* left, const int32_t* right, const double* length,
+                                         const int64_t* transfer, uint32_t B, char** out) {
+  if (!transfer) {
+    dafs::set_last_error(kBadArgument.c_str());
+    return DAFS_HIP_EINVAL;
+  }
+  return newick_text(n, names, left, right, length, nullptr, B, out, transfer);
 }
 
 // Bootstrap support: per node of the main tree the number of replicate trees that hold its split
@@ -680,8 +742,9 @@ extern "C" int dafs_host_tree_support(uint32_t n, const int32_t* left, const int
 }
 
 // The table of --phylogeny-support: one line per non-trivial split of the main tree, the leaves on the side without the first row
-extern "C" int dafs_host_support_table(uint32_t n, const char* const* names, const int32_t* left, const int32_t* right, const int32_t* support,
-                                       uint32_t B, uint64_t seed, int model, char** out) {
+// transfer (or null; section 28): the header names the measure and every line gains depth, transfer and tbe
+static int support_table_text(uint32_t n, const char* const* names, const int32_t* left, const int32_t* right, const int32_t* support,
+                              const int64_t* transfer, uint32_t B, uint64_t seed, int model, char** out) {
   return text_out(out, [&]() {
     if (!n || !left || !right || !support || !B) throw kBadArgument;
     if (model != DAFS_NJ_P && model != DAFS_NJ_JC) throw std::string(dafs_host_phylogeny_refusal(DAFS_PHYLOGENY_UNKNOWN_MODEL));
@@ -689,7 +752,9 @@ extern "C" int dafs_host_support_table(uint32_t n, const char* const* names, con
     if (const char* bad = dafs::tree_malformed(n, left, right)) throw std::string("support table: ") + bad;
     const uint32_t T = 2 * n - 1, silent = silent_root_child(n, left, right);
     std::ostringstream os;
-    os << "# rows " << n << " replicates " << B << " seed " << seed << " model " << (model == DAFS_NJ_JC ? "jc" : "p") << "\n";
+    const std::vector<int32_t> depth = transfer ? split_depths(n, left, right) : std::vector<int32_t>();
+    os << "# rows " << n << " replicates " << B << " seed " << seed << " model " << (model == DAFS_NJ_JC ? "jc" : "p")
+       << (transfer ? " measure transfer" : "") << "\n";
     // below[v]: the leaves below v in ascending order, kept only while a node above still needs them
     std::vector<std::vector<uint32_t> > below(T);
     for (uint32_t v = 0; v < T; ++v) {
@@ -717,10 +782,25 @@ extern "C" int dafs_host_support_table(uint32_t n, const char* const* names, con
       }
       os << v + 1 << "\t" << support[v] << "\t" << B << "\t" << support_percent(support[v], B) << "\t" << side.size() << "\t";
       for (size_t k = 0; k < side.size(); ++k) os << (k ? "," : "") << nm[side[k]];
+      if (transfer) os << "\t" << depth[v] << "\t" << transfer[v] << "\t" << transfer_percent("transfer table", transfer[v], depth[v], B);
       os << "\n";
     }
     return os.str();
   });
+}
+
+extern "C" int dafs_host_support_table(uint32_t n, const char* const* names, const int32_t* left, const int32_t* right, const int32_t* support,
+                                       uint32_t B, uint64_t seed, int model, char** out) {
+  return support_table_text(n, names, left, right, support, nullptr, B, seed, model, out);
+}
+
+extern "C" int dafs_host_transfer_table(uint32_t n, const char* const* names, const int32_t* left, const int32_t* right, const int32_t* support,
+                                        const int64_t* transfer, uint32_t B, uint64_t seed, int model, char** out) {
+  if (!transfer) {
+    dafs::set_last_error(kBadArgument.c_str());
+    return DAFS_HIP_EINVAL;
+  }
+  return support_table_text(n, names, left, right, support, transfer, B, seed, model, out);
 }
 
 // Alignment statistics: the cell code, the summary and the tables of --identity and --identity-matrix

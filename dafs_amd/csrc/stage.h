@@ -18,7 +18,8 @@ enum stage_id {
   ST_CMP_MAP, ST_CMP_COUNT_COLS, ST_CMP_COUNT, ST_CMP_RESIDUE, ST_CMP_COLUMNS, ST_CMP_SS, ST_CMP_PAIRS, ST_CMP_PAIRS_OCC,
   ST_LINKAGE_INIT, ST_LINKAGE_JOINS, ST_COV_FITCH, ST_COV_DRAW, ST_COV_EVOLVE,
   ST_NJ_INIT, ST_NJ_ROWSUM, ST_NJ_PICK, ST_NJ_UPDATE, ST_BOOT_PACK, ST_BOOT_DIST, ST_NJ_BATCH,
-  ST_STRUCT_SIM, ST_STRUCT_W, ST_LEVELS_MASK, ST_LEVELS_MERGE, ST_BP_COMPACT_LEVELS, ST_PEA_TOTAL, ST_PEA_PICK, ST_COUNT
+  ST_STRUCT_SIM, ST_STRUCT_W, ST_LEVELS_MASK, ST_LEVELS_MERGE, ST_BP_COMPACT_LEVELS, ST_PEA_TOTAL, ST_PEA_PICK,
+  ST_TRANSFER_SIDES, ST_TRANSFER, ST_COUNT
 };
 static const char* const kStageNames[ST_COUNT] = {
   "k_contrafold", "k_contrafold_posterior", "k_bp_compact", "k_pairhmm3", "k_pairhmm5", "k_mp_sim", "k_mp_interleave", "k_pct_rows", "k_pct_emit",
@@ -30,7 +31,8 @@ static const char* const kStageNames[ST_COUNT] = {
   "k_cmp_map", "k_cmp_count_cols", "k_cmp_count", "k_cmp_residue", "k_cmp_columns", "k_cmp_ss", "k_cmp_pairs<shared>", "k_cmp_pairs<occupancy>",
   "k_linkage_init", "k_linkage_joins", "k_cov_fitch", "k_cov_draw", "k_cov_evolve",
   "k_nj_init", "k_nj_rowsum", "k_nj_pick", "k_nj_update", "k_boot_pack", "k_boot_dist", "k_nj_batch",
-  "k_struct_sim", "k_struct_w", "k_levels_mask", "k_levels_merge", "k_bp_compact_levels", "k_pea_total", "k_pea_pick"};
+  "k_struct_sim", "k_struct_w", "k_levels_mask", "k_levels_merge", "k_bp_compact_levels", "k_pea_total", "k_pea_pick",
+  "k_transfer_sides", "k_transfer"};
 
 struct stage_recorder {
   struct rec { int id; hipEvent_t a, b; };

@@ -95,6 +95,19 @@ class support_counter {
     for (uint32_t v = 0; v < T_; ++v) support[v] = split_of_[v] < 0 ? -1 : (int32_t)hits_[split_of_[v]];
   }
 
+  // The transfer bootstrap compares sets of positions on the device: the position of every leaf, and
+  // per node of the tree given (the main tree) the run [lo, lo + len) of its side; len = 0 for the root and trivial splits.
+  const std::vector<uint32_t>& positions() const { return pos_; }
+  void runs(const int32_t* left, const int32_t* right, std::vector<uint32_t>& lo, std::vector<uint32_t>& len) const {
+    lo.assign(T_, 0);
+    len.assign(T_, 0);
+    if (n_ < 4) return;
+    std::vector<run> side;
+    sides(left, right, side);
+    for (uint32_t v = 0; v + 1 < T_; ++v)
+      if (side[v].count >= 2 && n_ - side[v].count >= 2) { lo[v] = side[v].lo; len[v] = side[v].count; }
+  }
+
  private:
   struct run { uint32_t lo, hi, count; };
   static uint64_t key(const run& s) { return ((uint64_t)s.lo << 32) | s.hi; }

@@ -121,7 +121,7 @@ def run(names, seqs, ctx=None, bp=None, w=4.0, eta0=0.5, t_max=600, w_pct_a=0.25
         th_s=0.2, th_s1=None, align_model=capi.ALIGN_PROBCONS, force_iters=0, timers=None, level_sync=False, slice_iters=None,
         mp=None, skip_uncoupled_folds=True, shard=None, round_us=None, w_pct_f=0.0, bp_update=False, bp_update1=False,
         reliability=False, covariation=False, row_structures=False, identity=False, compare=None, phylogeny=False,
-        phylogeny_bootstrap=0, phylogeny_seed=12345, decoder="Nussinov"):
+        phylogeny_bootstrap=0, phylogeny_seed=12345, decoder="Nussinov", phylogeny_transfer=False):
     """The whole run.  bp: per-sequence (rowptr, col, val) base-pairing rows (--fold-aux); None
     computes them with the device fold model.  mp: supplied matching probabilities (--align-aux), see Context.set_mp.
     shard: (torch.distributed module, torch device) of an initialised process group -- phase 1 (folds, pair posteriors,
@@ -135,6 +135,8 @@ def run(names, seqs, ctx=None, bp=None, w=4.0, eta0=0.5, t_max=600, w_pct_a=0.25
     "p": the result also gets .phylogeny (see alignment_phylogeny), the neighbour-joining tree of the printed rows;
     phylogeny_bootstrap: that many bootstrap replicates drawn from phylogeny_seed: .phylogeny also gets
     .support, .replicates, .seed and .support_table, and .newick carries the support in percent as the labels of the joins.
+    phylogeny_transfer (with replicates): .phylogeny also gets .transfer and .depth, .newick carries the
+    transfer bootstrap expectation in percent instead and .support_table is the transfer table.
     decoder: "Nussinov", or "Levels" (DESIGN.md section 25): the common structure is decoded level by level at the
     thresholds th_s1 (a sequence, one per level; a scalar or None: one level) and may hold pseudoknots.  .ss is then the
     union of the levels, .ss_level the level of the pair at each of its columns (0xFF at unpaired ones), .ss_scores the
@@ -146,7 +148,7 @@ def run(names, seqs, ctx=None, bp=None, w=4.0, eta0=0.5, t_max=600, w_pct_a=0.25
     its own thresholds (.row_ss_auto)."""
     import time
     th_s1 = decoder_option(decoder, th_s, th_s1, bp_update1, None, "pipeline.run")
-    phylogeny = phylogeny_option(phylogeny, phylogeny_bootstrap, phylogeny_seed)
+    phylogeny = phylogeny_option(phylogeny, phylogeny_bootstrap, phylogeny_seed, phylogeny_transfer)
     # combinations this driver does not implement are refused, not ignored (the command line, cli_main.cpp, has no level
     # batches: its --bp-update runs in the resident-node rounds and in the refinement's solve_node)
     if level_sync and bp_update:
@@ -423,19 +425,22 @@ def _covariation(ctx, rows, ss, covariation):
 class Phylogeny:
     """Result of alignment_phylogeny: .model, .left, .right, .length (Context.alignment_tree) and .newick (capi.newick); with
     bootstrap replicates also .support (Context.alignment_bootstrap), .replicates, .seed and .support_table
-    (capi.support_table), and .newick then carries the support in percent as the labels of the joins"""
+    (capi.support_table), and .newick then carries the support in percent as the labels of the joins; with the transfer
+    option also .transfer and .depth, .newick carries the transfer bootstrap expectation in percent
+    and .support_table is capi.transfer_table's"""
 
 
 class PhylogenyOption(str):
     """The model name of the phylogeny option as it travels through the drivers, with the bootstrap options beside it:
-    .bootstrap (replicates, 0 for none) and .seed"""
-    bootstrap, seed = 0, 12345
+    .bootstrap (replicates, 0 for none), .seed and .transfer (the transfer bootstrap of DESIGN.md section 28)"""
+    bootstrap, seed, transfer = 0, 12345, False
 
 
-def phylogeny_option(phylogeny, bootstrap=0, seed=12345):
+def phylogeny_option(phylogeny, bootstrap=0, seed=12345, transfer=False):
     """phylogeny_model with the bootstrap options of run / run_batch / add / describe / cluster checked and attached
     (DESIGN.md section 23): None for off, otherwise a PhylogenyOption.  Replicates without a tree are refused with the
-    library's text, as the command line refuses --phylogeny-bootstrap without --phylogeny."""
+    library's text, as the command line refuses --phylogeny-bootstrap without --phylogeny; so is the transfer option
+    (section 28) without replicates."""
     model = phylogeny_model(phylogeny)
     if isinstance(model, PhylogenyOption):
         return model
@@ -443,11 +448,15 @@ def phylogeny_option(phylogeny, bootstrap=0, seed=12345):
     if model is None:
         if bootstrap:
             raise ValueError(capi.bootstrap_refusal(capi.BOOT_NEEDS_TREE))
+        if transfer:
+            raise ValueError(capi.transfer_refusal(capi.TRANSFER_NEEDS_REPLICATES))
         return None
     if not 0 <= bootstrap <= capi.BOOTSTRAP_MAX:
         raise ValueError(capi.bootstrap_refusal(capi.BOOT_COUNT))
+    if transfer and not bootstrap:
+        raise ValueError(capi.transfer_refusal(capi.TRANSFER_NEEDS_REPLICATES))
     out = PhylogenyOption(model)
-    out.bootstrap, out.seed = bootstrap, int(seed) & 0xFFFFFFFFFFFFFFFF
+    out.bootstrap, out.seed, out.transfer = bootstrap, int(seed) & 0xFFFFFFFFFFFFFFFF, bool(transfer)
     return out
 
 
@@ -477,6 +486,13 @@ def alignment_phylogeny(ctx, row_names, rows, model="jc"):
         out.newick = capi.newick(row_names, out.left, out.right, out.length)
         return out
     out.replicates, out.seed = replicates, model.seed
+    if getattr(model, "transfer", False):
+        out.support, out.transfer = ctx.alignment_bootstrap(rows, model=out.model, B=replicates, seed=model.seed, tree=(out.left, out.right),
+                                                            transfer=True)
+        out.depth = capi.split_depth(out.left, out.right)
+        out.newick = capi.newick(row_names, out.left, out.right, out.length, transfer=out.transfer, depth=out.depth, replicates=replicates)
+        out.support_table = capi.transfer_table(row_names, out.left, out.right, out.support, out.transfer, replicates, model.seed, out.model)
+        return out
     out.support = ctx.alignment_bootstrap(rows, model=out.model, B=replicates, seed=model.seed, tree=(out.left, out.right))
     out.newick = capi.newick(row_names, out.left, out.right, out.length, support=out.support, replicates=replicates)
     out.support_table = capi.support_table(row_names, out.left, out.right, out.support, replicates, model.seed, out.model)
@@ -550,17 +566,17 @@ def identity_matrix_tsv(row_names, identity):
 
 
 def describe(names, rows, ss=None, ctx=None, identity=True, covariation=False, compare=None, pp=None, phylogeny=False,
-             phylogeny_bootstrap=0, phylogeny_seed=12345, level=None):
+             phylogeny_bootstrap=0, phylogeny_seed=12345, level=None, phylogeny_transfer=False):
     """The alignment-only statistics of a finished alignment (`dafs --describe ALIGNMENT`): nothing is
     aligned.  names / rows / ss: as stockholm.read_seed_structure returns them (ss None: no structure).  Returns a Result with
     .rows, .row_names (stockholm.names), .ss and, as asked, .identity (alignment_identity over all columns) and .covariation
     (as run's).  compare (as run's): .compare, this alignment against the reference; pp: its PP rows (stockholm.read_seed_pp)
-    for the comparison's PP part.  phylogeny, phylogeny_bootstrap, phylogeny_seed (as run's): .phylogeny.  level (with ss, both
+    for the comparison's PP part.  phylogeny, phylogeny_bootstrap, phylogeny_seed, phylogeny_transfer (as run's): .phylogeny.  level (with ss, both
     as stockholm.read_seed_knots returns them; `dafs --describe --knots`): the levels of a structure whose
     pairs may cross -> .ss_level and .ss_str, the brackets of capi.make_brackets_levels, which `dafs` prints after a
     ">SS_cons" line; the statistics read the merged ss."""
     covariation = cov_options(covariation)
-    phylogeny = phylogeny_option(phylogeny, phylogeny_bootstrap, phylogeny_seed)
+    phylogeny = phylogeny_option(phylogeny, phylogeny_bootstrap, phylogeny_seed, phylogeny_transfer)
     names, rows = stockholm.clean_seed(names, rows)
     res = Result()
     res.rows, res.row_names = rows, stockholm.names(names)
@@ -787,7 +803,7 @@ def add(seed_names, seed_rows, names, seqs, ctx=None, w=4.0, eta0=0.5, t_max=600
         th_s=0.2, th_s1=None, align_model=capi.ALIGN_PROBCONS, force_iters=0, slice_iters=None, skip_uncoupled_folds=True,
         round_us=None, w_pct_f=0.0, bp_update1=False, reliability=False, covariation=False, row_structures=False, seed_ss=None,
         decoder="Nussinov", seed_level=None,
-        identity=False, compare=None, phylogeny=False, phylogeny_bootstrap=0, phylogeny_seed=12345):
+        identity=False, compare=None, phylogeny=False, phylogeny_bootstrap=0, phylogeny_seed=12345, phylogeny_transfer=False):
     """Add new sequences to a fixed seed alignment without changing its columns (`dafs --seed`).
     seed_names / seed_rows: the seed's rows (letters and '.' / '-' gaps; stockholm.read_seed reads a file), checked and
     without their all-gap columns (stockholm.clean_seed).  names / seqs: the new sequences.  The options are run()'s.
@@ -817,7 +833,7 @@ def add(seed_names, seed_rows, names, seqs, ctx=None, w=4.0, eta0=0.5, t_max=600
     if seed_level is not None and seed_ss is None:
         raise ValueError("pipeline.add: seed_level gives the levels of seed_ss and needs it")
     covariation = cov_options(covariation)
-    phylogeny = phylogeny_option(phylogeny, phylogeny_bootstrap, phylogeny_seed)
+    phylogeny = phylogeny_option(phylogeny, phylogeny_bootstrap, phylogeny_seed, phylogeny_transfer)
     seed_names, seed_rows = stockholm.clean_seed(seed_names, seed_rows)
     names, seqs = list(names), list(seqs)
     if not seqs or len(names) != len(seqs):
@@ -932,7 +948,7 @@ def run_batch(families, ctx=None, max_bytes=None, **kw):
         raise TypeError("pipeline.run_batch: unknown options %s" % sorted(unknown))
     opts.update(kw)
     opts["th_s1"] = decoder_option(opts["decoder"], opts["th_s"], opts["th_s1"], opts["bp_update1"], None, "pipeline.run_batch")
-    opts["phylogeny"] = phylogeny_option(opts["phylogeny"], opts["phylogeny_bootstrap"], opts["phylogeny_seed"])
+    opts["phylogeny"] = phylogeny_option(opts["phylogeny"], opts["phylogeny_bootstrap"], opts["phylogeny_seed"], opts["phylogeny_transfer"])
     families = [(list(nm), list(sq)) for nm, sq in families]
     for nm, sq in families:
         if not sq or len(nm) != len(sq):
@@ -1073,6 +1089,8 @@ def pairwise(names, seqs, pairs=None, ctx=None, max_bytes=None, **opts):
         raise ValueError(capi.phylogeny_refusal(capi.PHY_NO_PAIRWISE))
     if opts.get("phylogeny_bootstrap"):
         raise ValueError(capi.bootstrap_refusal(capi.BOOT_NEEDS_TREE))
+    if opts.get("phylogeny_transfer"):
+        raise ValueError(capi.transfer_refusal(capi.TRANSFER_NEEDS_REPLICATES))
     if opts.get("compare") is not None:
         raise ValueError(capi.compare_refusal(capi.CMP_NO_PAIRWISE))
     if opts.get("level_sync") and opts.get("bp_update"):
@@ -1298,6 +1316,8 @@ def add_each(seed_names, seed_rows, names, seqs, ctx=None, max_bytes=None, merge
         raise ValueError(capi.phylogeny_refusal(capi.PHY_NO_SEED_EACH))
     if o.get("phylogeny_bootstrap"):
         raise ValueError(capi.bootstrap_refusal(capi.BOOT_NEEDS_TREE))
+    if o.get("phylogeny_transfer"):
+        raise ValueError(capi.transfer_refusal(capi.TRANSFER_NEEDS_REPLICATES))
     covariation = cov_options(o["covariation"])
     seed_names, seed_rows = stockholm.clean_seed(seed_names, seed_rows)
     names, seqs = list(names), list(seqs)
@@ -1555,7 +1575,8 @@ def cluster(names, seqs, threshold=None, count=None, min_size=1, ctx=None, max_b
     if unknown:
         raise TypeError("pipeline.cluster: unknown options %s" % sorted(unknown))
     cov_options(opts.get("covariation"))
-    phylogeny_option(opts.get("phylogeny"), opts.get("phylogeny_bootstrap", 0), opts.get("phylogeny_seed", 12345))
+    phylogeny_option(opts.get("phylogeny"), opts.get("phylogeny_bootstrap", 0), opts.get("phylogeny_seed", 12345),
+                     opts.get("phylogeny_transfer", False))
     decoder_option(opts.get("decoder", "Nussinov"), opts.get("th_s", known["th_s"]), opts.get("th_s1"), opts.get("bp_update1"), None,
                    "pipeline.cluster")
     names, seqs = list(names), list(seqs)

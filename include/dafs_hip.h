@@ -472,6 +472,59 @@ int dafs_host_newick_support(uint32_t n, const char* const* names, const int32_t
 int dafs_host_support_table(uint32_t n, const char* const* names, const int32_t* left, const int32_t* right, const int32_t* support,
                             uint32_t B, uint64_t seed, int model, char** out);
 
+/* Transfer bootstrap of a neighbour-joining tree (the transfer bootstrap expectation of Lemoine et al., Nature 2018; no counterpart
+ * in the reference; the contract, to the bit and in integers only; tests/transfer_ref.py restates it).
+ * Sides, trivial splits and the root's two children are those of dafs_hip_alignment_bootstrap.  For a node v of the main tree with
+ * a non-trivial split, depth(v) = min(|side(v)|, n - |side(v)|), and for a replicate tree T the transfer index phi(v, T) is the
+ * minimum over all nodes u of T below its root, leaves included, of min(H, n - H) with H = |side(v) xor side(u)|: an integer in
+ * 0 .. depth(v) - 1, 0 exactly when T holds the split.  transfer[v] is the sum of phi(v, T_k) over the B replicates; -1 for the
+ * root and for trivial splits; both children of the root get the same sum.
+ *
+ * dafs_hip_tree_transfer: host trees, main (left, right)[2n-1] and replicates [B][2n-1], compared on the device
+ * (tree_transfer.hip) in chunks under the byte budget of dafs_hip_alignment_bootstrap (DAFS_NJ_BOOT_BYTES shrinks them too).
+ * transfer[2n-1]; transfer_each: NULL or [B][2n-1], phi per replicate, -1 where transfer is -1.  n <= 3: all -1, nothing
+ * launched.  DAFS_HIP_EINVAL with a message, outputs untouched, context usable: a null pointer, n = 0 or above 16 384, B = 0 or
+ * above 65 536, a malformed main tree, a malformed replicate tree (the replicate is named).
+ *
+ * L0 dafs_hipk_tree_transfer: `count` (1 to 32 768) device replicate trees d_left / d_right [count][2n-1] of n >= 4 leaves, on
+ * hip_stream without allocation or wait.  d_pos[n]: the position of every leaf in the walk of the main tree, leaf 0 at position 0;
+ * d_split: `splits` pairs (lo, len) of uint32, the sides of the main tree as runs [lo, lo + len) of positions, lo >= 1, len >= 2;
+ * dafs_host_transfer_runs forms both from a host tree (pos[n], and per node lo and len, len = 0 for the root and trivial
+ * splits).  d_transfer[splits]: 64-bit sums that the call ADDS to (the caller zeroes them before the first chunk); d_each: NULL
+ * or [count][splits].  The workspace of dafs_hipk_tree_transfer_workspace(n, count) bytes (256-byte aligned; 0 for n < 4, n above
+ * 16 384, count = 0 or above 32 768) begins with `count` heads { uint32 bad_tree, bad_split }, zeroed by the call: what the
+ * kernels refuse (a leaf with a child, a child that is not an earlier node, a position that is not below n; a run that does not
+ * lie in 1 .. n).  A refused replicate adds nothing and no index of it leaves its arrays. */
+int dafs_hip_tree_transfer(dafs_hip_ctx* ctx, uint32_t n, const int32_t* main_left, const int32_t* main_right, uint32_t B,
+                           const int32_t* rep_left, const int32_t* rep_right, int64_t* transfer, int32_t* transfer_each);
+size_t dafs_hipk_tree_transfer_workspace(uint32_t n, uint32_t count);
+int dafs_hipk_tree_transfer(uint32_t n, uint32_t count, uint32_t splits, const uint32_t* d_pos, const uint32_t* d_split, const int32_t* d_left,
+                            const int32_t* d_right, void* d_workspace, uint64_t* d_transfer, int32_t* d_each, void* hip_stream);
+int dafs_host_transfer_runs(uint32_t n, const int32_t* left, const int32_t* right, uint32_t* pos, uint32_t* lo, uint32_t* len);
+/* dafs_hip_alignment_bootstrap with the transfer sums beside the counts: the same arguments, results and refusals, and
+ * transfer[2n-1] (not NULL).  Per chunk the kernels run on the replicate trees where the joins left them, on the same stream;
+ * only the sums come back, at the end. */
+int dafs_hip_alignment_bootstrap_transfer(dafs_hip_ctx* ctx, uint32_t n, uint32_t len, const uint8_t* cell, const uint8_t* use, int model,
+                                          uint32_t B, uint64_t seed, const int32_t* main_left, const int32_t* main_right, int32_t* support,
+                                          int32_t* rep_left, int32_t* rep_right, int64_t* transfer);
+/* Host-side helpers.  dafs_host_split_depth: depth[2n-1], -1 for the root and trivial splits.  dafs_host_transfer_percent: the
+ * transfer bootstrap expectation in percent, (200 * (M - transfer) + M) / (2 * M) with M = B * (depth - 1) in integer division
+ * (halves round up, as the percent of dafs_host_newick_support); -1 for depth < 2, B = 0 or a sum outside 0 .. M.
+ * dafs_host_newick_transfer: dafs_host_newick_support's text with that percent as the labels, under the same root-child rule.
+ * dafs_host_transfer_table: "# rows n replicates B seed S model M measure transfer", then per non-trivial split the six fields of
+ * dafs_host_support_table and depth, transfer, tbe.  dafs_host_transfer_refusal: what both drivers say when they refuse the
+ * option; a function of its own, as dafs_host_bootstrap_refusal answers "" above its four. */
+enum {
+  DAFS_TRANSFER_NEEDS_REPLICATES = 0  /* --phylogeny-transfer without --phylogeny-bootstrap */
+};
+const char* dafs_host_transfer_refusal(int which);
+int dafs_host_split_depth(uint32_t n, const int32_t* left, const int32_t* right, int32_t* depth);
+int32_t dafs_host_transfer_percent(int64_t transfer, uint32_t depth, uint32_t B);
+int dafs_host_newick_transfer(uint32_t n, const char* const* names, const int32_t* left, const int32_t* right, const double* length,
+                              const int64_t* transfer, uint32_t B, char** out);
+int dafs_host_transfer_table(uint32_t n, const char* const* names, const int32_t* left, const int32_t* right, const int32_t* support,
+                             const int64_t* transfer, uint32_t B, uint64_t seed, int model, char** out);
+
 /* Host-side helper (no device work): the merge of `dafs --seed` and pipeline.add, k new sequences
  * placed into a fixed seed alignment of C columns.  lens: k sequence lengths; z: their column maps from the k nodes (leaf j
  * against the seed) concatenated, per residue a seed column or DAFS_HIP_NONE, the seed columns strictly increasing within
